@@ -22,6 +22,12 @@ arguments>` as a CHILD process (never an exec), relays its output and exits with
 directly (WORLD_SIZE set) it is a rank.  Every rank reports the device it runs on (index, gcnArchName, PCI bus id, uuid); the
 JSON line carries them under "ranks", and fewer distinct devices than ranks is an error unless --share-device (rehearsal).
 
+A plain run sets up, warms up, times the steps and prints the line.  The legs the headline figure does not need run only with
+--full, after the timed region: the frame download (value_incl_d2h, d2h_ms), parity against the CPU oracle on a reduced frame
+(parity, psnr_vs_cpu_db) and the CPU baselines (cpu_baseline, cpu_baseline_8threads); without --full those fields are null.
+--dump-outputs DIR writes the frame the timed steps accumulated (seeded inputs: identical from run to run), to compare two builds;
+its non-finite values are written as 0 beside a map of where they were, so that every array it writes is finite.
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -53,7 +59,7 @@ def parse_args():
                     help="chess_high: conf.json with model_quality high honoured (296 k triangles; the shipped executable cannot reach it)")
     ap.add_argument("--pool-paths", type=int, default=0)
     ap.add_argument("--pass-steps", type=int, default=1,
-                    help="the library renders in passes of this many steps' samples times the rank count (its per-pass result buffer; tools/pass_size.py: 256 spp per rank-share of the frame is within 1 % of the best)")
+                    help="the library renders in passes of this many steps' samples times the rank count (its per-pass result buffer; tools/pass_size.py: 256 spp per rank-share of the frame is within 1 %% of the best)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-spp", type=int, default=8, help="spp of the bounded CPU-baseline sample (full frame) on all cores; the 8-thread leg uses half")
     ap.add_argument("--serialized", action="store_true",
@@ -65,7 +71,17 @@ def parse_args():
                     help="gloo + --share-device rehearses the N>1 path on a one-GPU box (the reduce goes through host memory)")
     ap.add_argument("--share-device", action="store_true", help="rehearsal only: every rank uses cuda:0")
     ap.add_argument("--per-step-calls", action="store_true", help="one library call per step (drains between steps)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the legs the headline figure does not need: the frame download (value_incl_d2h), "
+                         "parity against the CPU oracle (--no-psnr drops it) and the CPU baselines (--no-cpu-baseline drops them)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the framebuffer the timed steps accumulated to DIR/framebuffer.npy (float32, H x W x 3, non-finite values as 0) "
+                         "and DIR/framebuffer_nonfinite.npy (same shape: 0 finite, 1 NaN, 2 +inf, 3 -inf); above 64 MB a seeded sample of "
+                         "pixels instead: DIR/framebuffer_sample.npy and DIR/framebuffer_sample_nonfinite.npy (n x 3) at DIR/framebuffer_sample_pixels.npy")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    return args
 
 
 def make_scene(pkg, args):
@@ -90,6 +106,42 @@ def host_cores():
     except (OSError, ValueError):
         pass
     return n
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def split_nonfinite(a):
+    """(a with every non-finite value stored as 0, codes of the same shape: 0 finite, 1 NaN, 2 +inf, 3 -inf), both float32.  The frame
+    can hold NaN: like the reference, a path stopped by Russian roulette returns its raw direct term, which can be NaN,
+    and one NaN sample keeps its pixel NaN.  The two finite arrays keep that information for a comparison with a tolerance."""
+    import numpy as np
+    codes = np.zeros(a.shape, np.float32)
+    codes[np.isnan(a)] = 1
+    codes[np.isposinf(a)] = 2
+    codes[np.isneginf(a)] = 3
+    return np.where(codes == 0, a, np.float32(0)).astype(np.float32), codes
+
+
+def dump_outputs(out_dir, fb_host, W, H):
+    """--dump-outputs: the frame the timed steps accumulated (what a caller of mcpt_render_device receives), so that two builds can be
+    compared output for output: framebuffer.npy with its non-finite values as 0, and framebuffer_nonfinite.npy saying which they were
+    (split_nonfinite).  A frame whose two arrays exceed DUMP_LIMIT_BYTES is replaced by a fixed sample of its pixels (seed 0: the same
+    pixels in every run of the same size)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    img = fb_host.numpy().reshape(H, W, 3).astype(np.float32, copy=False)
+    if 2 * img.nbytes + 1024 <= DUMP_LIMIT_BYTES:
+        name, pix = "framebuffer", None
+    else:
+        n = DUMP_LIMIT_BYTES // 40  # 12 B of values + 12 B of codes (float32) + 8 B of float64 index per pixel, with room for the headers
+        pix = np.sort(np.random.default_rng(0).choice(H * W, size=n, replace=False))
+        img = img.reshape(-1, 3)[pix]
+        name = "framebuffer_sample"
+        np.save(os.path.join(out_dir, "framebuffer_sample_pixels.npy"), pix.astype(np.float64))
+    values, codes = split_nonfinite(img)
+    np.save(os.path.join(out_dir, name + ".npy"), values)
+    np.save(os.path.join(out_dir, name + "_nonfinite.npy"), codes)
 
 
 def load_traffic():
@@ -246,10 +298,16 @@ def main():
         return
 
     value = tot_samples / dt / 1e6
-    # PCIe-inclusive variant (SURVEY 8(d) defines t_render with the framebuffer download; `value` leaves the frame in HBM)
-    t1 = time.perf_counter()
-    fb_host = fb.cpu()
-    d2h_s = time.perf_counter() - t1
+    fb_host, d2h_s = None, None
+    if args.full:
+        # PCIe-inclusive variant (SURVEY 8(d) defines t_render with the framebuffer download; `value` leaves the frame in HBM)
+        t1 = time.perf_counter()
+        fb_host = fb.cpu()
+        d2h_s = time.perf_counter() - t1
+    if fb_host is None and (args.dump_outputs or args.save_png):
+        fb_host = fb.cpu()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, fb_host, W, H)
 
     # ---- roofline of the dominant kernel.  Durations: HIP events recorded by the library on the stream each kernel is
     # launched on, summed over the timed region (rocprofv3 --kernel-trace --stats of this command gives the same averages).
@@ -321,7 +379,7 @@ def main():
 
     # ---- parity vs the CPU oracle, same Philox seed, on a reduced configuration of the same scene
     parity = None
-    if not args.no_psnr:
+    if args.full and not args.no_psnr:
         import numpy as np
         from oracle import oracle as orc
         small = make_scene(pkg, argparse.Namespace(**{**vars(args), "width": 240, "height": 136}))
@@ -336,7 +394,7 @@ def main():
     # ---- CPU baseline: the oracle (a port of the reference path) on this box's host cores, bounded samples:
     # all cores the cgroup grants, and 8 threads (the reference's fixed PARALLELISM, Renderer.cpp:16)
     cpu, cpu8 = None, None
-    if not args.no_cpu_baseline and world == 1:  # (rank 0 at N = 1 only)
+    if args.full and not args.no_cpu_baseline and world == 1:  # (rank 0 at N = 1 only)
         from oracle import oracle as orc
         ncores = host_cores()
         osc = orc.OracleScene(sd)
@@ -364,7 +422,8 @@ def main():
                    "streams": "one (serialised)" if args.serialized else "three"},
         "wall_clock_1920x1080_spp2048_s": round(1920 * 1080 * 2048 / (value * 1e6), 2),
         # the frame stays in HBM inside the timed region; with its download to host memory (mcpt_render's contract):
-        "value_incl_d2h": round(tot_samples / (dt + d2h_s) / 1e6, 3), "d2h_ms": round(d2h_s * 1e3, 3),
+        "value_incl_d2h": None if d2h_s is None else round(tot_samples / (dt + d2h_s) / 1e6, 3),
+        "d2h_ms": None if d2h_s is None else round(d2h_s * 1e3, 3),
         "psnr_vs_cpu_db": None if parity is None else parity["psnr_db"],
         "parity": parity,
         "roofline": roofline,

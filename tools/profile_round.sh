@@ -11,7 +11,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/prof_$TAG
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-python3 $R/bench.py > $O/bench.json 2> $O/bench.err || exit 1
+python3 $R/bench.py --full > $O/bench.json 2> $O/bench.err || exit 1
 echo "bench done"; tail -c 300 $O/bench.json; echo
 # (--warmup 0: every launch of the profiled process lies in bench.py's timed region, so the per-kernel averages of its JSON line and of
 # the rocprofv3 statistics are averages over the same launches)
@@ -42,13 +42,13 @@ profile_config cornell_rc --scene cornell_rc --width 784 --height 784 || exit 1
 profile_config cornell_demo --scene cornell_demo || exit 1
 profile_config chess_high --scene chess_high || exit 1
 # the other BASELINE configurations (bench lines only)
-python3 $R/bench.py --scene cornell_rc --width 784 --height 784 --steps 1 --spp-per-step 256 --cpu-spp 16 > $O/bench_config2_cornell_rc_784_spp256.json 2>> $O/bench.err || exit 1
-python3 $R/bench.py --steps 2 --no-cpu-baseline > $O/bench_config3_chess_spp512.json 2>> $O/bench.err || exit 1
-python3 $R/bench.py --n-dir 32 --no-cpu-baseline > $O/bench_config4_chess_spp2048_ndir32.json 2>> $O/bench.err || exit 1
-python3 $R/bench.py --scene cornell_demo --no-cpu-baseline > $O/bench_cornell_demo_1080p.json 2>> $O/bench.err || exit 1
-python3 $R/bench.py --scene chess_high --no-cpu-baseline > $O/bench_chess_high_sah.json 2>> $O/bench.err || exit 1
-MCPT_BVH=ploc python3 $R/bench.py --scene chess_high --no-cpu-baseline > $O/bench_chess_high_ploc.json 2>> $O/bench.err || exit 1
-MCPT_BVH=ploc python3 $R/bench.py --no-cpu-baseline > $O/bench_chess_ploc.json 2>> $O/bench.err || exit 1
-MCPT_BVH=lbvh python3 $R/bench.py --no-cpu-baseline > $O/bench_chess_lbvh.json 2>> $O/bench.err || exit 1
+python3 $R/bench.py --full --scene cornell_rc --width 784 --height 784 --steps 1 --spp-per-step 256 --cpu-spp 16 > $O/bench_config2_cornell_rc_784_spp256.json 2>> $O/bench.err || exit 1
+python3 $R/bench.py --full --steps 2 --no-cpu-baseline > $O/bench_config3_chess_spp512.json 2>> $O/bench.err || exit 1
+python3 $R/bench.py --full --n-dir 32 --no-cpu-baseline > $O/bench_config4_chess_spp2048_ndir32.json 2>> $O/bench.err || exit 1
+python3 $R/bench.py --full --scene cornell_demo --no-cpu-baseline > $O/bench_cornell_demo_1080p.json 2>> $O/bench.err || exit 1
+python3 $R/bench.py --full --scene chess_high --no-cpu-baseline > $O/bench_chess_high_sah.json 2>> $O/bench.err || exit 1
+MCPT_BVH=ploc python3 $R/bench.py --full --scene chess_high --no-cpu-baseline > $O/bench_chess_high_ploc.json 2>> $O/bench.err || exit 1
+MCPT_BVH=ploc python3 $R/bench.py --full --no-cpu-baseline > $O/bench_chess_ploc.json 2>> $O/bench.err || exit 1
+MCPT_BVH=lbvh python3 $R/bench.py --full --no-cpu-baseline > $O/bench_chess_lbvh.json 2>> $O/bench.err || exit 1
 echo "config benches done"
 ls $O
