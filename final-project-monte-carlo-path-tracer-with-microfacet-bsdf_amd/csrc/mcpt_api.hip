@@ -19,6 +19,7 @@
 
 #include "mcpt_kernels.h"
 #include "mcpt_cull.h"
+#include "mcpt_adaptive.h"
 #include "mcpt_lbvh.h"
 
 using namespace mcpt;
@@ -400,6 +401,7 @@ struct AccumPlan {
     uint32_t n_pix;
     const uint32_t *pixel_list;
     float *result[2];
+    double *moments;  // adaptive sampling: per-pixel sums of v and v*v (nullptr: the plain fold)
 };
 
 // Runs the wavefront loop over a schedule of passes (mode 0) or over `plan[0].n_work` explicit paths (mode 1).
@@ -482,7 +484,7 @@ int run_wavefront(mcpt_scene *sc, PoolCtx &ctx, const RenderConst &C0, const Cam
         while (acc && have_counters && accum_next < issue_pass && issue_done_iter[accum_next] < it &&
                (C.track_live ? w.h_counters->live[accum_next & 1].v == 0 : (n_cur_max == 0 && issue_pass >= P))) {
             int ev = T.begin(s);
-            launch_accumulate(acc->result[accum_next & 1], acc->pixel_list, acc->n_pix, plan[accum_next].s_pass, acc->spp_total, acc->fb, s);
+            launch_accumulate(acc->result[accum_next & 1], acc->pixel_list, acc->n_pix, plan[accum_next].s_pass, acc->spp_total, acc->fb, acc->moments, s);
             T.end(ev, K_RESOLVE, s);
             accum_next++;
         }
@@ -684,18 +686,18 @@ uint64_t bytes_per_pool_path(int n_dir, int max_depth) {
     return (uint64_t)(2 * wave + scratch + retrace + 16.0 * max_depth + 16.0);
 }
 
-int render_impl(mcpt_scene *sc, const mcpt_camera *cam, const mcpt_params *pp, float *fb_dev, hipStream_t st,
-                mcpt_stats *stats) {
-    if (!sc || !cam || !pp || !fb_dev) return fail(MCPT_ERR_ARG, "mcpt_render: null argument");
-    const mcpt_params &p = *pp;
-    if (cam->width <= 0 || cam->height <= 0 || p.spp <= 0 || p.n_dir_sample <= 0 || !(p.rr_rate > 0.f))
-        return fail(MCPT_ERR_ARG, "mcpt_render: width/height/spp/n_dir_sample/rr_rate must be positive");
-    if ((uint64_t)cam->width * cam->height > 0x7fffffffull) return fail(MCPT_ERR_ARG, "mcpt_render: frame too large");
-    HIP_TRY(hipSetDevice(sc->device));
-    (void)hipGetLastError();  // an earlier, already reported failure of this thread must not be taken for one of this call
-    const auto t0 = std::chrono::steady_clock::now();
-    const int W = cam->width, H = cam->height;
+// The owned pixels of a render call once the sky cull has run: the traced ones (with their candidate lists, or none) and the culled ones.
+struct PixelSet {
+    uint32_t n_owned = 0, n_pix = 0;  // owned pixels, traced pixels
+    const uint32_t *list = nullptr;   // the traced pixels
+    const int4 *cand = nullptr;       // their sky-cull candidate entries (nullptr: primary rays walk the tree)
+    const uint32_t *sky = nullptr;    // the n_owned - n_pix culled pixels
+};
 
+// Uploads the owned pixels (when the partition changed), clears the framebuffer unless p.accumulate, and runs the sky cull: the culled
+// pixels get spp additions of background / spp_total here.
+int prepare_pixels(mcpt_scene *sc, const CameraConst &cc, int W, int H, const mcpt_params &p, int32_t spp, float spp_total, float *fb_dev,
+                   hipStream_t st, PixelSet &ps) {
     // owned pixels: rebuilt and uploaded only when the partition changes (progressive calls reuse it)
     SharedBufs &sh = sc->shared;
     const int pk[5] = {W, H, p.tile_size, p.nranks > 1 ? p.rank : 0, p.nranks > 1 ? p.nranks : 1};
@@ -708,15 +710,14 @@ int render_impl(mcpt_scene *sc, const mcpt_camera *cam, const mcpt_params *pp, f
         std::memcpy(sh.pix_key, pk, sizeof pk);
     }
     const uint32_t n_pix_owned = sh.n_pix;
-    const CameraConst cc = make_camera(*cam);
-    const float spp_total = (float)(p.spp_total > 0 ? p.spp_total : p.spp);
     if (!p.accumulate) HIP_TRY(hipMemsetAsync(fb_dev, 0, (size_t)W * H * 3 * sizeof(float), st));
 
     // Pixels that can only see the background (no environment map: every sample returns the same constant) are finished here,
-    // without a ray; the wavefront loop below runs over the others.  csrc/mcpt_cull.hip has the conservative bound.
+    // without a ray; the wavefront loop runs over the others.  csrc/mcpt_cull.hip has the conservative bound.
     uint32_t n_pix = n_pix_owned;
     const uint32_t *pixel_list = sh.pixel_list.p;
     const int4 *pixel_cand = nullptr;
+    const uint32_t *sky = nullptr;
     if (sc->knobs.sky_cull && sc->view.env_w <= 0 && n_pix_owned > 0) {
         const size_t tb = cull_temp_bytes(n_pix_owned);
         HIP_TRY(sh.culled_list.alloc(n_pix_owned));
@@ -729,7 +730,8 @@ int render_impl(mcpt_scene *sc, const mcpt_camera *cam, const mcpt_params *pp, f
         HIP_TRY(cull_sky_pixels(sc->view, cc, sh.pixel_list.p, n_pix_owned, sh.culled_list.p, sh.cull_flags.p, sh.cand_tmp.p, sh.cand_list.p, sh.cull_temp.p,
                                 tb, sh.cull_count.p, &n_trace, st));
         if (n_trace <= n_pix_owned) {  // classified: the traced pixels come first, in their original order, with their candidate lists
-            launch_sky_fill(sh.culled_list.p + n_trace, n_pix_owned - n_trace, sc->view.background, p.spp, spp_total, fb_dev, st);
+            sky = sh.culled_list.p + n_trace;
+            launch_sky_fill(sky, n_pix_owned - n_trace, sc->view.background, spp, spp_total, fb_dev, st);
             n_pix = n_trace;
             pixel_list = sh.culled_list.p;
             // (candidate lists skip the float box tests of a primitive's ancestors: a ray that grazes a box face within rounding is a hit
@@ -738,7 +740,42 @@ int render_impl(mcpt_scene *sc, const mcpt_camera *cam, const mcpt_params *pp, f
             pixel_cand = sc->info.builder == 1 ? nullptr : sh.cand_list.p;
         }
     }
+    ps.n_owned = n_pix_owned;
+    ps.n_pix = n_pix;
+    ps.list = pixel_list;
+    ps.cand = pixel_cand;
+    ps.sky = sky;
+    return MCPT_OK;
+}
 
+// What the wavefront loop of one or more render_list calls did.
+struct RunTotals {
+    LoopTotals sum;
+    uint64_t pushes = 0, overflow = 0;
+    double ms[K_NCLASS] = {0, 0, 0, 0, 0, 0};
+    uint64_t cnt[K_NCLASS] = {0, 0, 0, 0, 0, 0};
+    void add(const RunTotals &o) {
+        sum.iterations += o.sum.iterations;
+        sum.shaded += o.sum.shaded;
+        sum.closest += o.sum.closest;
+        sum.shadow += o.sum.shadow;
+        sum.direct += o.sum.direct;
+        pushes += o.pushes;
+        overflow += o.overflow;
+        for (int c = 0; c < K_NCLASS; ++c) {
+            ms[c] += o.ms[c];
+            cnt[c] += o.cnt[c];
+        }
+    }
+};
+
+// Renders the n_pix listed pixels (with their candidate entries, or none) for samples [sample_offset, sample_offset + spp), each added as
+// value / spp_total into fb_dev in sample order (moments != nullptr: the per-pixel sums of v and v*v as well).  Blocks until done.
+// p supplies everything else (rr_rate, n_dir_sample, shadows, seed, spp_per_pass, pool_paths, max_depth).
+int render_list(mcpt_scene *sc, const CameraConst &cc, const mcpt_params &p, const uint32_t *pixel_list, const int4 *pixel_cand, uint32_t n_pix,
+                int32_t sample_offset, int32_t spp, float spp_total, float *fb_dev, double *moments, hipStream_t st,
+                std::chrono::steady_clock::time_point t0, RunTotals &rt) {
+    SharedBufs &sh = sc->shared;
     const int max_depth = derive_max_depth(p);
     // default: the smallest pool within 1 % of the best rate.  Measured on the chess frame (round 3, A/B on one box): 40 Mi paths 5031-5045,
     // 48 Mi 5061, 60 Mi 5052-5066 Msamples/s (round 2: 28 Mi 4467, 40 Mi 4557, 60 Mi 4617, 80 Mi 4605); 40 Mi paths are 38 GB of workspace
@@ -769,13 +806,13 @@ int render_impl(mcpt_scene *sc, const mcpt_camera *cam, const mcpt_params *pp, f
     if (s_pass_req <= 0) {
         const uint64_t want = 16ull * (pool64 / 3) / std::max<uint32_t>(n_pix, 1u) + 1ull;
         int cap = 32;
-        while (cap < p.spp && cap < (1 << 20)) cap *= 2;  // (no larger than the call needs: the buffer of a short call stays small)
+        while (cap < spp && cap < (1 << 20)) cap *= 2;  // (no larger than the call needs: the buffer of a short call stays small)
         s_pass_req = 32;
         while ((uint64_t)s_pass_req < want && s_pass_req < cap) s_pass_req *= 2;
         if (have_mem) while (s_pass_req > 32 && (uint64_t)n_pix * s_pass_req * 3ull * 4ull * 2ull > have / 4) s_pass_req /= 2;
     }
     while ((uint64_t)n_pix * s_pass_req * 3ull > 0xfffffff0ull && s_pass_req > 1) s_pass_req /= 2;
-    const int s_pass = std::min(s_pass_req, p.spp);
+    const int s_pass = std::min(s_pass_req, spp);
     // keep the clamp stack within 48 GiB
     while (pool64 * (uint64_t)max_depth * 16ull > (48ull << 30) && pool64 > 3 * 4096) pool64 /= 2;
     // light-sample indices (record * n_dir + k) are 32-bit
@@ -794,17 +831,12 @@ int render_impl(mcpt_scene *sc, const mcpt_camera *cam, const mcpt_params *pp, f
     if ((uint64_t)n_pix * s_pass < min_work || pool64 / 2 < 3 * 256) n_pools = 1;
     const uint32_t pool = (uint32_t)(pool64 / n_pools / 3 * 3);
 
-    if (n_pix_owned == 0) {
-        HIP_TRY(hipStreamSynchronize(st));
-        if (stats) std::memset(stats, 0, sizeof *stats);
-        return MCPT_OK;
-    }
     // (n_pix == 0 with owned pixels: every one of them was culled; the loop below then has no samples to issue and falls through)
     const auto t_alloc0 = std::chrono::steady_clock::now();
     for (int k = 0; k < n_pools; ++k) HIP_TRY(ensure_workspace(sc->pools[k], pool, p.n_dir_sample, max_depth, stack_uses_retry(sc->view.height)));
     // two halves: a pass accumulates from one while the next pass fills the other (one half with a single pass)
     const size_t half_floats = (size_t)n_pix * s_pass * 3;
-    const bool two_halves = n_pools == 1 && p.spp > s_pass;
+    const bool two_halves = n_pools == 1 && spp > s_pass;
     // both halves are allocated, for the REQUESTED pass size, even when this call needs less: a later call with more or longer passes
     // (a warm-up followed by the real frame) must not pay a multi-GB hipFree + hipMalloc
     HIP_TRY(sh.result.alloc((size_t)n_pix * s_pass_req * 3 * (n_pools == 1 ? 2 : 1)));
@@ -834,16 +866,16 @@ int render_impl(mcpt_scene *sc, const mcpt_camera *cam, const mcpt_params *pp, f
     if (n_pools == 1) {
         // one pool: all passes of the call go through one pipelined schedule
         std::vector<PassPlan> plan;
-        for (int k0 = 0; k0 < p.spp; k0 += s_pass) {
-            const int s_now = std::min(s_pass, p.spp - k0);
-            plan.push_back(PassPlan{0u, n_pix * (uint32_t)s_now, s_now, p.sample_offset + k0});
+        for (int k0 = 0; k0 < spp; k0 += s_pass) {
+            const int s_now = std::min(s_pass, spp - k0);
+            plan.push_back(PassPlan{0u, n_pix * (uint32_t)s_now, s_now, sample_offset + k0});
         }
-        AccumPlan acc{fb_dev, spp_total, n_pix, pixel_list, {C.result[0], C.result[1]}};
+        AccumPlan acc{fb_dev, spp_total, n_pix, pixel_list, {C.result[0], C.result[1]}, moments};
         const int rc = drained(run_wavefront(sc, sc->pools[0], C, &cc, plan, &acc, st, tot[0]));
         if (rc != MCPT_OK) return rc;
     } else {
-        for (int k0 = 0; k0 < p.spp; k0 += s_pass) {
-            const int s_now = std::min(s_pass, p.spp - k0);
+        for (int k0 = 0; k0 < spp; k0 += s_pass) {
+            const int s_now = std::min(s_pass, spp - k0);
             const uint32_t n_work = n_pix * (uint32_t)s_now;
             // pool 1 (own stream, own host thread) takes the second half of the pass; it starts after the
             // framebuffer clear / pixel-list upload / previous accumulate queued on the caller's stream
@@ -852,8 +884,8 @@ int render_impl(mcpt_scene *sc, const mcpt_camera *cam, const mcpt_params *pp, f
             PoolCtx &c1 = sc->pools[1];
             HIP_TRY(hipStreamWaitEvent(c1.main, sc->fork, 0));
             c1.rc = MCPT_OK;
-            const std::vector<PassPlan> plan0{PassPlan{0u, half, s_now, p.sample_offset + k0}};
-            const std::vector<PassPlan> plan1{PassPlan{half, n_work - half, s_now, p.sample_offset + k0}};
+            const std::vector<PassPlan> plan0{PassPlan{0u, half, s_now, sample_offset + k0}};
+            const std::vector<PassPlan> plan1{PassPlan{half, n_work - half, s_now, sample_offset + k0}};
             std::thread worker([&]() {
                 if (hipSetDevice(sc->device) != hipSuccess) {
                     c1.rc = MCPT_ERR_HIP;
@@ -869,62 +901,88 @@ int render_impl(mcpt_scene *sc, const mcpt_camera *cam, const mcpt_params *pp, f
             if (c1.rc != MCPT_OK) return drained(fail(c1.rc, c1.err));
             Timer &T0 = sc->pools[0].timer;
             int ev = T0.begin(st);
-            launch_accumulate(C.result[0], pixel_list, n_pix, s_now, spp_total, fb_dev, st);
+            launch_accumulate(C.result[0], pixel_list, n_pix, s_now, spp_total, fb_dev, moments, st);
             T0.end(ev, K_RESOLVE, st);
         }
     }
     HIP_TRY(hipStreamSynchronize(st));
     sc->pools[0].timer.collect();
     HIP_TRY(hipGetLastError());
-    uint64_t pushes = 0, overflow = 0;
-    LoopTotals sum;
-    double ms[K_NCLASS] = {0, 0, 0, 0, 0, 0};
-    uint64_t cnt[K_NCLASS] = {0, 0, 0, 0, 0, 0};
     for (int k = 0; k < n_pools; ++k) {
-        pushes += sc->pools[k].pushes;
-        overflow += sc->pools[k].overflow;
-        sum.iterations += tot[k].iterations;
-        sum.shaded += tot[k].shaded;
-        sum.closest += tot[k].closest;
-        sum.shadow += tot[k].shadow;
-        sum.direct += tot[k].direct;
+        rt.pushes += sc->pools[k].pushes;
+        rt.overflow += sc->pools[k].overflow;
+        rt.sum.iterations += tot[k].iterations;
+        rt.sum.shaded += tot[k].shaded;
+        rt.sum.closest += tot[k].closest;
+        rt.sum.shadow += tot[k].shadow;
+        rt.sum.direct += tot[k].direct;
         for (int c = 0; c < K_NCLASS; ++c) {
-            ms[c] += sc->pools[k].timer.ms[c];
-            cnt[c] += sc->pools[k].timer.count[c];
+            rt.ms[c] += sc->pools[k].timer.ms[c];
+            rt.cnt[c] += sc->pools[k].timer.count[c];
         }
     }
-    if (stats) {
-        std::memset(stats, 0, sizeof *stats);
-        // (culled pixels count like traced ones: the reference runs one camera ray and three castRay invocations, each with one
-        // Scene::intersect, for every sample of them too)
-        stats->samples = (uint64_t)n_pix_owned * p.spp;
-        stats->paths = 3 * stats->samples;
-        stats->vertices = stats->paths + pushes;
-        stats->shaded = sum.shaded;
-        stats->closest_rays = sum.closest;
-        stats->shadow_rays = sum.shadow;
-        stats->direct_vertices = sum.direct;
-        // Scene::intersect calls of the reference: one per castRay invocation (Scene.cpp:87), n_dir per shaded
-        // vertex (Scene.cpp:73), one look-ahead per vertex that survives roulette (Scene.cpp:134,161).
-        const uint64_t cont = sum.closest - (uint64_t)n_pix * p.spp;  // closest-hit rays beyond the primary rays actually traced
-        stats->ref_scene_rays = stats->vertices + (uint64_t)p.n_dir_sample * sum.shaded + cont;
-        stats->iterations = sum.iterations;
-        stats->overflow_paths = overflow;
-        stats->ms_trace_closest = ms[K_CLOSEST];
-        stats->ms_trace_shadow = ms[K_SHADOW];
-        stats->ms_shade = ms[K_SHADE];
-        stats->ms_generate = ms[K_GENERATE];
-        stats->ms_resolve = ms[K_RESOLVE];
-        stats->ms_direct = ms[K_DIRECT];
-        stats->n_direct = cnt[K_DIRECT];
-        stats->n_trace_closest = cnt[K_CLOSEST];
-        stats->n_trace_shadow = cnt[K_SHADOW];
-        stats->n_shade = cnt[K_SHADE];
-        stats->n_generate = cnt[K_GENERATE];
-        stats->n_resolve = cnt[K_RESOLVE];
-        stats->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return MCPT_OK;
+}
+
+// mcpt_stats of a call that rendered `samples` camera samples, `traced_primary` of them through the wavefront loop (the rest: sky cull).
+void fill_stats(mcpt_stats *stats, uint64_t samples, uint64_t traced_primary, int32_t n_dir, const RunTotals &rt,
+                std::chrono::steady_clock::time_point t0) {
+    std::memset(stats, 0, sizeof *stats);
+    // (culled pixels count like traced ones: the reference runs one camera ray and three castRay invocations, each with one
+    // Scene::intersect, for every sample of them too)
+    stats->samples = samples;
+    stats->paths = 3 * stats->samples;
+    stats->vertices = stats->paths + rt.pushes;
+    stats->shaded = rt.sum.shaded;
+    stats->closest_rays = rt.sum.closest;
+    stats->shadow_rays = rt.sum.shadow;
+    stats->direct_vertices = rt.sum.direct;
+    // Scene::intersect calls of the reference: one per castRay invocation (Scene.cpp:87), n_dir per shaded
+    // vertex (Scene.cpp:73), one look-ahead per vertex that survives roulette (Scene.cpp:134,161).
+    const uint64_t cont = rt.sum.closest - traced_primary;  // closest-hit rays beyond the primary rays actually traced
+    stats->ref_scene_rays = stats->vertices + (uint64_t)n_dir * rt.sum.shaded + cont;
+    stats->iterations = rt.sum.iterations;
+    stats->overflow_paths = rt.overflow;
+    stats->ms_trace_closest = rt.ms[K_CLOSEST];
+    stats->ms_trace_shadow = rt.ms[K_SHADOW];
+    stats->ms_shade = rt.ms[K_SHADE];
+    stats->ms_generate = rt.ms[K_GENERATE];
+    stats->ms_resolve = rt.ms[K_RESOLVE];
+    stats->ms_direct = rt.ms[K_DIRECT];
+    stats->n_direct = rt.cnt[K_DIRECT];
+    stats->n_trace_closest = rt.cnt[K_CLOSEST];
+    stats->n_trace_shadow = rt.cnt[K_SHADOW];
+    stats->n_shade = rt.cnt[K_SHADE];
+    stats->n_generate = rt.cnt[K_GENERATE];
+    stats->n_resolve = rt.cnt[K_RESOLVE];
+    stats->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+int render_impl(mcpt_scene *sc, const mcpt_camera *cam, const mcpt_params *pp, float *fb_dev, hipStream_t st,
+                mcpt_stats *stats) {
+    if (!sc || !cam || !pp || !fb_dev) return fail(MCPT_ERR_ARG, "mcpt_render: null argument");
+    const mcpt_params &p = *pp;
+    if (cam->width <= 0 || cam->height <= 0 || p.spp <= 0 || p.n_dir_sample <= 0 || !(p.rr_rate > 0.f))
+        return fail(MCPT_ERR_ARG, "mcpt_render: width/height/spp/n_dir_sample/rr_rate must be positive");
+    if ((uint64_t)cam->width * cam->height > 0x7fffffffull) return fail(MCPT_ERR_ARG, "mcpt_render: frame too large");
+    HIP_TRY(hipSetDevice(sc->device));
+    (void)hipGetLastError();  // an earlier, already reported failure of this thread must not be taken for one of this call
+    const auto t0 = std::chrono::steady_clock::now();
+    const CameraConst cc = make_camera(*cam);
+    const float spp_total = (float)(p.spp_total > 0 ? p.spp_total : p.spp);
+    PixelSet ps;
+    int rc = prepare_pixels(sc, cc, cam->width, cam->height, p, p.spp, spp_total, fb_dev, st, ps);
+    if (rc != MCPT_OK) return rc;
+    if (ps.n_owned == 0) {
+        HIP_TRY(hipStreamSynchronize(st));
+        if (stats) std::memset(stats, 0, sizeof *stats);
+        return MCPT_OK;
     }
-    if (overflow) return fail(MCPT_ERR_OVERFLOW, "some paths outran the clamp stack (raise params.max_depth)");
+    RunTotals rt;
+    rc = render_list(sc, cc, p, ps.list, ps.cand, ps.n_pix, p.sample_offset, p.spp, spp_total, fb_dev, nullptr, st, t0, rt);
+    if (rc != MCPT_OK) return rc;
+    if (stats) fill_stats(stats, (uint64_t)ps.n_owned * p.spp, (uint64_t)ps.n_pix * p.spp, p.n_dir_sample, rt, t0);
+    if (rt.overflow) return fail(MCPT_ERR_OVERFLOW, "some paths outran the clamp stack (raise params.max_depth)");
     return MCPT_OK;
 }
 
@@ -1360,6 +1418,119 @@ int mcpt_render(mcpt_scene *sc, const mcpt_camera *cam, const mcpt_params *p, fl
         if (e != hipSuccess) return fail(MCPT_ERR_HIP, std::string("framebuffer download: ") + hipGetErrorString(e));
     }
     return rc;
+}
+
+int mcpt_render_adaptive(mcpt_scene *sc, const mcpt_camera *cam, const mcpt_params *pp, const mcpt_adaptive *opts, float *fb_host, int32_t *spp_host,
+                         float *err_host, mcpt_adaptive_info *info, mcpt_stats *stats) {
+    if (!sc || !cam || !pp || !opts || !fb_host) return fail(MCPT_ERR_ARG, "mcpt_render_adaptive: null argument");
+    const mcpt_params &p = *pp;
+    const mcpt_adaptive &o = *opts;
+    if (cam->width <= 0 || cam->height <= 0 || p.spp <= 0 || p.n_dir_sample <= 0 || !(p.rr_rate > 0.f))
+        return fail(MCPT_ERR_ARG, "mcpt_render_adaptive: width/height/spp/n_dir_sample/rr_rate must be positive");
+    if ((uint64_t)cam->width * cam->height > 0x7fffffffull) return fail(MCPT_ERR_ARG, "mcpt_render_adaptive: frame too large");
+    if (p.accumulate != 0 || p.spp_total != 0 || p.sample_offset != 0)
+        return fail(MCPT_ERR_ARG, "mcpt_render_adaptive: accumulate, spp_total and sample_offset must be 0");
+    if (o.min_spp < 2) return fail(MCPT_ERR_ARG, "mcpt_render_adaptive: min_spp must be at least 2");
+    int R = 0;
+    while (R <= 15 && ((int64_t)o.min_spp << R) < p.spp) ++R;
+    if (R > 15 || ((int64_t)o.min_spp << R) != p.spp) return fail(MCPT_ERR_ARG, "mcpt_render_adaptive: params.spp must be min_spp * 2^R, 0 <= R <= 15");
+    if (!(o.threshold >= 0.f) || !std::isfinite(o.threshold)) return fail(MCPT_ERR_ARG, "mcpt_render_adaptive: threshold must be finite and >= 0");
+    if (!(o.rel_floor > 0.f)) return fail(MCPT_ERR_ARG, "mcpt_render_adaptive: rel_floor must be > 0");
+    if (o.dilate != 0 && o.dilate != 1) return fail(MCPT_ERR_ARG, "mcpt_render_adaptive: dilate must be 0 or 1");
+    HIP_TRY(hipSetDevice(sc->device));
+    (void)hipGetLastError();
+    const auto t0 = std::chrono::steady_clock::now();
+    const hipStream_t st = nullptr;
+    const int W = cam->width, H = cam->height;
+    const size_t n_px = (size_t)W * H;
+    const int32_t S0 = o.min_spp;
+    const double rel_floor = (double)o.rel_floor, threshold = (double)o.threshold;
+    DevBuf<float> fb, err;
+    DevBuf<double> mom;
+    DevBuf<int32_t> sppm;
+    DevBuf<uint8_t> stamp;
+    HIP_TRY(fb.alloc(n_px * 3));
+    HIP_TRY(err.alloc(n_px));
+    HIP_TRY(mom.alloc(n_px * 6));
+    HIP_TRY(sppm.alloc(n_px));
+    HIP_TRY(stamp.alloc(n_px));
+    HIP_TRY(hipMemsetAsync(err.p, 0, n_px * sizeof(float), st));
+    HIP_TRY(hipMemsetAsync(mom.p, 0, n_px * 6 * sizeof(double), st));
+    HIP_TRY(hipMemsetAsync(sppm.p, 0, n_px * sizeof(int32_t), st));
+    HIP_TRY(hipMemsetAsync(stamp.p, 0, n_px, st));
+    const CameraConst cc = make_camera(*cam);
+    PixelSet ps;
+    int rc = prepare_pixels(sc, cc, W, H, p, S0, (float)S0, fb.p, st, ps);  // round 0 of the culled pixels: S0 additions of background / S0
+    if (rc != MCPT_OK) return rc;
+    mcpt_adaptive_info inf;
+    std::memset(&inf, 0, sizeof inf);
+    RunTotals all;
+    uint64_t samples = 0, traced_primary = 0;
+    if (ps.n_owned > 0) {
+        // the culled pixels are final at S0: their estimate from the constant samples, no mark (they take no part in dilation)
+        const uint32_t n_sky = ps.n_owned - ps.n_pix;
+        if (n_sky > 0) {
+            launch_sky_moments(ps.sky, n_sky, sc->view.background, S0, mom.p, st);
+            launch_adapt_eval(ps.sky, n_sky, mom.p, S0, rel_floor, threshold, 0u, err.p, nullptr, sppm.p, st);
+        }
+        // the active pixels of the current and of the next round (with their candidate entries when the cull produced them)
+        DevBuf<uint32_t> list[2];
+        DevBuf<int4> cand[2];
+        DevBuf<uint8_t> flags, temp;
+        DevBuf<uint32_t> count;
+        uint32_t n_act = ps.n_pix;
+        const size_t tb = adapt_temp_bytes(std::max<uint32_t>(n_act, 1u));
+        for (int k = 0; k < 2; ++k) {
+            HIP_TRY(list[k].alloc(std::max<uint32_t>(n_act, 1u)));
+            if (ps.cand) HIP_TRY(cand[k].alloc(std::max<uint32_t>(n_act, 1u)));
+        }
+        HIP_TRY(flags.alloc(std::max<uint32_t>(n_act, 1u)));
+        HIP_TRY(temp.alloc(tb));
+        HIP_TRY(count.alloc(1));
+        if (n_act > 0) {
+            HIP_TRY(hipMemcpyAsync(list[0].p, ps.list, n_act * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+            if (ps.cand) HIP_TRY(hipMemcpyAsync(cand[0].p, ps.cand, n_act * sizeof(int4), hipMemcpyDeviceToDevice, st));
+        }
+        samples = (uint64_t)ps.n_owned * S0;
+        int cur = 0;
+        for (int r = 0;; ++r) {
+            const auto tr = r == 0 ? t0 : std::chrono::steady_clock::now();
+            const int32_t n = S0 << r;                   // samples per active pixel after this round
+            const int32_t first = r == 0 ? 0 : n / 2;    // this round renders samples [first, n), divisor n
+            const bool can_double = 2 * (int64_t)n <= p.spp;
+            uint32_t n_next = 0;
+            if (n_act > 0) {
+                RunTotals rt;
+                rc = render_list(sc, cc, p, list[cur].p, ps.cand ? cand[cur].p : nullptr, n_act, first, n - first, (float)n, fb.p, mom.p, st, tr, rt);
+                if (rc != MCPT_OK) return rc;
+                all.add(rt);
+                traced_primary += (uint64_t)n_act * (n - first);
+                if (r > 0) samples += (uint64_t)n_act * (n - first);
+                const uint32_t round_stamp = (uint32_t)r + 1u;
+                launch_adapt_eval(list[cur].p, n_act, mom.p, n, rel_floor, threshold, round_stamp, err.p, stamp.p, sppm.p, st);
+                launch_adapt_select(list[cur].p, n_act, W, H, stamp.p, round_stamp, o.dilate, can_double ? 1 : 0, n, fb.p, sppm.p, flags.p, st);
+                if (can_double)
+                    HIP_TRY(adapt_compact(list[cur].p, ps.cand ? cand[cur].p : nullptr, flags.p, n_act, list[cur ^ 1].p, ps.cand ? cand[cur ^ 1].p : nullptr,
+                                          temp.p, tb, count.p, &n_next, st));
+                else
+                    HIP_TRY(hipStreamSynchronize(st));
+            }
+            inf.active_pixels[r] = r == 0 ? ps.n_owned : n_act;
+            inf.ms_round[r] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tr).count();
+            inf.rounds = r + 1;
+            if (n_next == 0) break;
+            n_act = n_next;
+            cur ^= 1;
+        }
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpy(fb_host, fb.p, n_px * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    if (spp_host) HIP_TRY(hipMemcpy(spp_host, sppm.p, n_px * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (err_host) HIP_TRY(hipMemcpy(err_host, err.p, n_px * sizeof(float), hipMemcpyDeviceToHost));
+    if (info) *info = inf;
+    if (stats) fill_stats(stats, samples, traced_primary, p.n_dir_sample, all, t0);
+    if (all.overflow) return fail(MCPT_ERR_OVERFLOW, "some paths outran the clamp stack (raise params.max_depth)");
+    return MCPT_OK;
 }
 
 int mcpt_intersect(mcpt_scene *sc, int64_t n, const float *origins, const float *dirs, double *out_t, int32_t *out_prim) {

@@ -210,7 +210,9 @@ void launch_tonemap(const float *fb, uint32_t n_pix, unsigned char *rgba, hipStr
 void launch_debug_fmath(int kind, uint32_t n, const float *x, const float *y, float *out, hipStream_t s);
 void launch_debug_scene(const DevScene &S, int kind, uint32_t n, const float *in, float *out, hipStream_t s);
 void launch_debug_material(const DevScene &S, int kind, uint32_t n, const float *in, const int32_t *sel, float *out, hipStream_t s);
+// framebuffer[m] += result / spp_total over s_pass samples per listed pixel, in sample order; moments != nullptr (adaptive sampling): also
+// the per-pixel sums of v and v*v in double, moments[6m + c] and moments[6m + 3 + c]
 void launch_accumulate(const float *result, const uint32_t *pixel_list, uint32_t n_pix, int32_t s_pass, float spp_total,
-                       float *fb, hipStream_t s);
+                       float *fb, double *moments, hipStream_t s);
 
 }  // namespace mcpt

@@ -1599,15 +1599,23 @@ __global__ __launch_bounds__(kBlock, MCPT_DIRECT_WAVES) void k_direct(DevScene S
 
 // ------------------------------------------------------------------------------------------------
 // k_accumulate: framebuffer[m] += Vector3f(R,G,B)/spp, samples in order (Renderer.cpp:80).
-// One lane per (owned pixel, channel).
+// One lane per (owned pixel, channel).  kMoments (adaptive sampling, mcpt_render_adaptive): the same fold, and besides it the
+// lane adds v and v*v, in double and in sample order, into moments[6m + c] and moments[6m + 3 + c].
 // ------------------------------------------------------------------------------------------------
+template <bool kMoments>
 __global__ __launch_bounds__(kBlock) void k_accumulate(const float *__restrict__ result, const uint32_t *__restrict__ pixel_list,
-                                                       uint32_t n_pix, int32_t s_pass, float spp_total, float *__restrict__ fb) {
+                                                       uint32_t n_pix, int32_t s_pass, float spp_total, float *__restrict__ fb,
+                                                       double *__restrict__ moments) {
     const uint32_t g = blockIdx.x * kBlock + threadIdx.x;
     if (g >= n_pix * 3u) return;
     const uint32_t pl = g / 3u, c = g % 3u;
     const uint32_t m = pixel_list ? pixel_list[pl] : pl;
     float acc = fb[(size_t)m * 3 + c];
+    double s1 = 0.0, s2 = 0.0;
+    if (kMoments) {
+        s1 = moments[(size_t)m * 6 + c];
+        s2 = moments[(size_t)m * 6 + 3 + c];
+    }
     const float *src = result + (size_t)pl * s_pass * 3 + c;
     int k = 0;
     for (; k + 8 <= s_pass; k += 8) {  // eight loads in flight; the additions stay in sample order (Renderer.cpp:80)
@@ -1615,10 +1623,29 @@ __global__ __launch_bounds__(kBlock) void k_accumulate(const float *__restrict__
 #pragma unroll
         for (int u = 0; u < 8; ++u) v[u] = src[(size_t)(k + u) * 3];
 #pragma unroll
-        for (int u = 0; u < 8; ++u) acc += v[u] / spp_total;
+        for (int u = 0; u < 8; ++u) {
+            acc += v[u] / spp_total;
+            if (kMoments) {
+                const double d = (double)v[u];
+                s1 += d;
+                s2 += d * d;
+            }
+        }
     }
-    for (; k < s_pass; ++k) acc += src[(size_t)k * 3] / spp_total;
+    for (; k < s_pass; ++k) {
+        const float v = src[(size_t)k * 3];
+        acc += v / spp_total;
+        if (kMoments) {
+            const double d = (double)v;
+            s1 += d;
+            s2 += d * d;
+        }
+    }
     fb[(size_t)m * 3 + c] = acc;
+    if (kMoments) {
+        moments[(size_t)m * 6 + c] = s1;
+        moments[(size_t)m * 6 + 3 + c] = s2;
+    }
 }
 
 __global__ __launch_bounds__(kBlock) void k_mask_unowned(float *fb, int W, int H, int tile, int rank, int nranks) {
@@ -1898,9 +1925,12 @@ void launch_debug_material(const DevScene &S, int kind, uint32_t n, const float 
 }
 
 void launch_accumulate(const float *result, const uint32_t *pixel_list, uint32_t n_pix, int32_t s_pass, float spp_total,
-                       float *fb, hipStream_t s) {
+                       float *fb, double *moments, hipStream_t s) {
     if (n_pix == 0) return;
-    hipLaunchKernelGGL(k_accumulate, dim3(blocks(n_pix * 3u)), dim3(kBlock), 0, s, result, pixel_list, n_pix, s_pass, spp_total, fb);
+    if (moments)
+        hipLaunchKernelGGL(k_accumulate<true>, dim3(blocks(n_pix * 3u)), dim3(kBlock), 0, s, result, pixel_list, n_pix, s_pass, spp_total, fb, moments);
+    else
+        hipLaunchKernelGGL(k_accumulate<false>, dim3(blocks(n_pix * 3u)), dim3(kBlock), 0, s, result, pixel_list, n_pix, s_pass, spp_total, fb, moments);
 }
 
 }  // namespace mcpt

@@ -15,7 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MCPT_LIB") or os.path.join(HERE, "libmcpt_hip.so")  # MCPT_LIB: diagnostic builds only
 CHECK_LIB_PATH = os.path.join(HERE, "libmcpt_hip_check.so")  # the checking build (build.build_check); tests only
 
-EXPORTS = ["mcpt_scene_create", "mcpt_scene_destroy", "mcpt_render", "mcpt_render_device", "mcpt_intersect",
+EXPORTS = ["mcpt_scene_create", "mcpt_scene_destroy", "mcpt_render", "mcpt_render_device", "mcpt_render_adaptive", "mcpt_intersect",
            "mcpt_cast_rays", "mcpt_camera_rays", "mcpt_scene_get_info", "mcpt_bvh_dump", "mcpt_scene_create_ex", "mcpt_scene_dump_bvh", "mcpt_tonemap", "mcpt_tonemap_device", "mcpt_debug_fmath", "mcpt_debug_material", "mcpt_debug_scene", "mcpt_debug_counters",
            "mcpt_group_create", "mcpt_group_render", "mcpt_group_size", "mcpt_group_get_info", "mcpt_group_scene", "mcpt_group_destroy", "mcpt_group_last_error",
            "mcpt_last_error", "mcpt_version"]
@@ -51,6 +51,18 @@ class Stats(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class Adaptive(C.Structure):
+    _fields_ = [("min_spp", C.c_int32), ("dilate", C.c_int32), ("threshold", C.c_float), ("rel_floor", C.c_float), ("reserved", C.c_int32 * 4)]
+
+
+class AdaptiveInfo(C.Structure):
+    _fields_ = [("rounds", C.c_int32), ("reserved", C.c_int32), ("active_pixels", C.c_uint64 * 16), ("ms_round", C.c_double * 16)]
+
+    def as_dict(self):
+        n = self.rounds
+        return {"rounds": n, "active_pixels": [int(x) for x in self.active_pixels[:n]], "ms_round": [float(x) for x in self.ms_round[:n]]}
 
 
 class BuildOptions(C.Structure):
@@ -101,6 +113,9 @@ def lib(path=None):
         L.mcpt_bvh_dump.argtypes = [C.POINTER(SceneDesc), C.POINTER(BvhInfo), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.mcpt_render.restype = C.c_int
         L.mcpt_render.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(Params), C.c_void_p, C.POINTER(Stats)]
+        L.mcpt_render_adaptive.restype = C.c_int
+        L.mcpt_render_adaptive.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(Params), C.POINTER(Adaptive), C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.POINTER(AdaptiveInfo), C.POINTER(Stats)]
         L.mcpt_render_device.restype = C.c_int
         L.mcpt_render_device.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_void_p, C.POINTER(Stats)]
         L.mcpt_intersect.restype = C.c_int
@@ -265,6 +280,23 @@ class HipScene:
         st = Stats()
         _check(self.L.mcpt_render(self.h, _ptr(cam), C.byref(p), _ptr(fb), C.byref(st)), L=self.L)
         return fb, st
+
+    def render_adaptive(self, min_spp, threshold, rel_floor=1e-3, dilate=1, camera=None, **kw):
+        """mcpt_render_adaptive: pixels stop at the first level S0 * 2^r whose estimate (include/mcpt.h) is at most `threshold`; params
+        spp (keyword `spp`, default the scene's) is the maximum.  Every pixel equals render(spp=its count) bit for bit.
+        Returns (fb[H,W,3] float32, spp[H,W] int32, err[H,W] float32, info dict, Stats)."""
+        cam = np.ascontiguousarray(camera if camera is not None else self.sd.camera)
+        W, H = int(cam["width"].reshape(-1)[0]), int(cam["height"].reshape(-1)[0])
+        fb = np.zeros((H, W, 3), dtype=np.float32)
+        spp = np.zeros((H, W), dtype=np.int32)
+        err = np.zeros((H, W), dtype=np.float32)
+        p = self.params(**kw)
+        o = Adaptive(min_spp=int(min_spp), dilate=int(dilate), threshold=float(threshold), rel_floor=float(rel_floor))
+        info = AdaptiveInfo()
+        st = Stats()
+        _check(self.L.mcpt_render_adaptive(self.h, _ptr(cam), C.byref(p), C.byref(o), _ptr(fb), _ptr(spp), _ptr(err), C.byref(info), C.byref(st)),
+               L=self.L)
+        return fb, spp, err, info.as_dict(), st
 
     def render_device(self, fb_ptr, stream_ptr=0, camera=None, **kw):
         """Same, into a device framebuffer (W*H*3 floats at fb_ptr) on the given hipStream_t handle."""

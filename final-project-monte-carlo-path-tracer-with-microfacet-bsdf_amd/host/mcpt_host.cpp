@@ -332,7 +332,25 @@ void Renderer::Render(const Scene &scene) {
         total.ms_total += st.ms_total;
         return rc;
     };
-    if (checkpoint_path.empty()) {
+    if (adaptive && scene.groupHandle()) {
+        std::cerr << "mcpt: adaptive sampling renders on one GPU (no --gpus / --devices)" << std::endl;
+        return;
+    }
+    if (adaptive) {
+        mcpt_adaptive o{};
+        o.min_spp = adaptive_min > 0 ? adaptive_min : std::min(64, spp);
+        o.dilate = 1;
+        o.threshold = adaptive_threshold;
+        o.rel_floor = 1e-3f;
+        mcpt_adaptive_info ai{};
+        const int rc = mcpt_render_adaptive(scene.handle(), &c, &p, &o, framebuffer.data(), nullptr, nullptr, &ai, &st);
+        if (rc != MCPT_OK) std::cerr << "mcpt: " << mcpt_last_error() << std::endl;
+        if (rc != MCPT_OK && rc != MCPT_ERR_OVERFLOW) return;
+        total = st;
+        std::cout << "[mcpt] adaptive: threshold " << o.threshold << ", " << o.min_spp << " to " << spp << " spp, " << ai.rounds << " rounds, active pixels";
+        for (int r = 0; r < ai.rounds; ++r) std::cout << (r ? " " : ": ") << ai.active_pixels[r];
+        std::cout << "; " << st.samples << " samples in total (" << (double)st.samples / ((double)camera.width * camera.height) << " spp on average)" << std::endl;
+    } else if (checkpoint_path.empty()) {
         const int rc = render(p);
         if (rc != MCPT_OK && rc != MCPT_ERR_OVERFLOW) return;
     } else {

@@ -257,6 +257,11 @@ class Renderer {
     std::string checkpoint_path;
     int checkpoint_every = 64;
     int stop_after = 0;  // test hook: leave after this many spp have been rendered in total (simulates an interruption)
+    // Adaptive sampling (mcpt_render_adaptive): spp is then the maximum, adaptive_min the first level (0: 64, or spp when smaller).
+    // One GPU; not combined with a checkpoint.
+    bool adaptive = false;
+    float adaptive_threshold = 0.f;
+    int adaptive_min = 0;
 
   private:
     int spp = 2048;

@@ -9,6 +9,8 @@
 //                 scene.addDiamond:false (main.cpp:197-199 tests presence only)
 //   --gpus N      render on GPUs 0..N-1 (tile partition + RCCL merge inside the library); --devices 0,0 lists them explicitly
 //   --checkpoint FILE [--checkpoint-every N]   render in chunks of N spp (default 64), keep the running frame in FILE and resume from it
+//   --adaptive THRESHOLD [--adaptive-min N]   adaptive sampling (mcpt_render_adaptive): pixels stop at the first of the levels N, 2N, ...,
+//                 spp whose relative error estimate is at most THRESHOLD; the conf.json / --spp value is the maximum (N: 64 by default)
 //   --dump FILE   write the flattened scene (what mcpt_scene_create receives) and exit without touching the GPU
 #include <chrono>
 #include <cstring>
@@ -60,6 +62,11 @@ int main(int argc, char **argv) {
         else if (a == "--checkpoint") r.checkpoint_path = argv[i + 1];
         else if (a == "--checkpoint-every") r.checkpoint_every = std::atoi(argv[i + 1]);
         else if (a == "--stop-after") r.stop_after = std::atoi(argv[i + 1]);
+        else if (a == "--adaptive") {
+            r.adaptive = true;
+            r.adaptive_threshold = std::strtof(argv[i + 1], nullptr);
+        }
+        else if (a == "--adaptive-min") r.adaptive_min = std::atoi(argv[i + 1]);
         else if (a == "--gpus") {
             std::vector<int> dev;
             for (int k = 0; k < std::atoi(argv[i + 1]); ++k) dev.push_back(k);
@@ -71,6 +78,10 @@ int main(int argc, char **argv) {
             while (std::getline(ss, tok, ',')) dev.push_back(std::atoi(tok.c_str()));
             scene.setDevices(dev);
         }
+    }
+    if (r.adaptive && !r.checkpoint_path.empty()) {
+        std::cerr << "--adaptive cannot be combined with --checkpoint" << std::endl;
+        return 1;
     }
     bool use_diamond = false;
     std::string model_quality = "low";  // the conf value is read after the paths are composed (main.cpp:24-26,200-202)

@@ -163,6 +163,39 @@ int mcpt_render(mcpt_scene *scene, const mcpt_camera *camera, const mcpt_params 
 int mcpt_render_device(mcpt_scene *scene, const mcpt_camera *camera, const mcpt_params *params, float *fb_device,
                        void *hip_stream, mcpt_stats *stats);
 
+/* ---- Adaptive sampling.  Levels S0, 2 S0, 4 S0, ..., params.spp with S0 = opts.min_spp >= 2 and params.spp = S0 * 2^R, 0 <= R <= 15.
+ * Round 0 renders every owned pixel at S0.  After each round every pixel active in it (n samples so far) is evaluated in double, in
+ * exactly this order, s1 / s2 being the sums of v and v*v over its samples in sample order, v = (double) the float sample value:
+ *     for c in 0..2:  m = s1[c]/n;  q = s2[c]/n - m*m;  var = max(q, 0) * n / (n - 1);  e_c = sqrt(var / n) / (m + rel_floor)
+ *     e = max(e_0, e_1, e_2)            (NaN if any e_c is NaN; max(q, 0) keeps a NaN q; rel_floor and threshold widened to double)
+ *     continue  iff  (e > threshold  or  (dilate and some 8-neighbour active in this round has e > threshold))  and  2n <= params.spp
+ * A NaN estimate stops the pixel.  A continuing pixel's value is scaled by 0.5 and it gets samples [n, 2n), divisor 2n: halving is exact
+ * (outside the subnormal range), so EVERY PIXEL IS BIT-IDENTICAL TO THE SAME PIXEL OF mcpt_render AT ITS FINAL SAMPLE COUNT.  Pixels the
+ * sky cull finishes are final at S0 (their estimate is reported; they are not "active" for dilation).  Unowned pixels
+ * (tile_size / rank / nranks) are 0 in every output.
+ *   fb_host   W*H*3 floats, as mcpt_render
+ *   spp_host  W*H final sample counts (nullable)
+ *   err_host  W*H estimates e at the final counts: the rule is evaluated once more at params.spp, so capped pixels report one (nullable)
+ *   info      rounds run, active pixels per round (round 0: every owned pixel), wall time per round (nullable)
+ *   stats     sums over all rounds; samples = the sum of spp_host over owned pixels (nullable)
+ * MCPT_ERR_ARG: params.spp not S0 * 2^R, S0 < 2, a negative or non-finite threshold, rel_floor <= 0, dilate not 0 or 1, or a non-zero
+ * accumulate / spp_total / sample_offset.  MCPT_ERR_OVERFLOW as mcpt_render (the outputs are still written). */
+typedef struct {
+    int32_t min_spp;   /* S0 */
+    int32_t dilate;    /* 0 | 1 */
+    float threshold;   /* relative standard error of the mean that stops a pixel */
+    float rel_floor;   /* added to the mean in the denominator */
+    int32_t reserved[4];
+} mcpt_adaptive; /* 32 bytes */
+typedef struct {
+    int32_t rounds;
+    int32_t reserved;
+    uint64_t active_pixels[16];
+    double ms_round[16];
+} mcpt_adaptive_info; /* 264 bytes */
+int mcpt_render_adaptive(mcpt_scene *scene, const mcpt_camera *camera, const mcpt_params *params, const mcpt_adaptive *opts,
+                         float *fb_host, int32_t *spp_host, float *err_host, mcpt_adaptive_info *info, mcpt_stats *stats);
+
 /* Replaces Scene::intersect (Scene.hpp:128, Scene.cpp:19-21) for a list of rays (host pointers; n*3 floats each).
  * out_t: hit distance as the reference's double Intersection::distance (DBL_MAX on a miss);
  * out_prim: global primitive id (triangle index, or n_triangles + object index for a sphere; -1 on a miss). */
