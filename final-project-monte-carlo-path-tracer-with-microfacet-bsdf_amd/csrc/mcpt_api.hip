@@ -20,6 +20,7 @@
 #include "mcpt_kernels.h"
 #include "mcpt_cull.h"
 #include "mcpt_adaptive.h"
+#include "mcpt_denoise.h"
 #include "mcpt_lbvh.h"
 
 using namespace mcpt;
@@ -1530,6 +1531,213 @@ int mcpt_render_adaptive(mcpt_scene *sc, const mcpt_camera *cam, const mcpt_para
     if (info) *info = inf;
     if (stats) fill_stats(stats, samples, traced_primary, p.n_dir_sample, all, t0);
     if (all.overflow) return fail(MCPT_ERR_OVERFLOW, "some paths outran the clamp stack (raise params.max_depth)");
+    return MCPT_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+constexpr uint32_t kAovChunkRays = 4u << 20;  // at most this many rays per chunk of the AOV pass
+constexpr int32_t kMaxAovSpp = 65536;
+
+// The AOV pass (include/mcpt.h): aov_dev[8m ..] for every pixel of the frame, samples 0 .. aov_spp-1 of `seed`, queued on `st`.  Chunks of
+// whole pixels, pixel-major.  It runs inside the wavefront workspace of pool 0 when that holds at least one pixel's rays (after a render it
+// holds millions): camera rays and hits in wave 0's ray / hit arrays, the per-sample records in wave 1's, the keys in wave 1's path
+// records, the retrace list of the closest-hit rays.  Otherwise (no render yet on this scene) it uses buffers of its own for the call.
+int aov_pass(mcpt_scene *sc, const CameraConst &cc, uint32_t seed, int32_t aov_spp, float *aov_dev, hipStream_t st) {
+    const uint32_t n_px = (uint32_t)cc.width * (uint32_t)cc.height;
+    const uint64_t need = std::min<uint64_t>(kAovChunkRays, (uint64_t)n_px * aov_spp);
+    Workspace &w = sc->pools[0].ws;
+    // rays that fit: the ray arrays (ray_cap entries) and, for the keys, two uint32 per ray in wave 1's rec0 (4 per entry)
+    const uint64_t ws_rays = w.pool ? std::min<uint64_t>(w.ray_cap, 2ull * w.pool) : 0;
+    const bool retry = stack_uses_retry(sc->view.height);
+    const bool in_ws = ws_rays >= (uint64_t)aov_spp && (!retry || w.retry.cap[0] >= std::min<uint64_t>(need, ws_rays));
+    DevBuf<uint32_t> keys;
+    DevBuf<float4> o4, d4, s0, s1;
+    DevBuf<uint4> hit;
+    RetryBufs own_retry;
+    uint64_t cap = need;
+    uint32_t *key_pixel, *key_sample;
+    float4 *ray_o, *ray_d, *rec0, *rec1;
+    uint4 *hits;
+    RetryList rl;
+    if (in_ws) {
+        cap = std::min<uint64_t>(need, ws_rays);
+        key_pixel = reinterpret_cast<uint32_t *>(w.wave[1].rec0.p);
+        key_sample = key_pixel + cap;
+        ray_o = w.wave[0].ray_o.p;
+        ray_d = w.wave[0].ray_d.p;
+        hits = w.wave[0].hit.p;
+        rec0 = w.wave[1].ray_o.p;
+        rec1 = w.wave[1].ray_d.p;
+        rl = w.retry.list(0);
+    } else {
+        HIP_TRY(keys.alloc(2 * cap));
+        HIP_TRY(o4.alloc(cap));
+        HIP_TRY(d4.alloc(cap));
+        HIP_TRY(hit.alloc(cap));
+        HIP_TRY(s0.alloc(cap));
+        HIP_TRY(s1.alloc(cap));
+        if (retry) {
+            const uint32_t want[3] = {(uint32_t)cap, 1u, 1u};
+            HIP_TRY(own_retry.alloc(want));
+        }
+        key_pixel = keys.p;
+        key_sample = keys.p + cap;
+        ray_o = o4.p;
+        ray_d = d4.p;
+        hits = hit.p;
+        rec0 = s0.p;
+        rec1 = s1.p;
+        rl = own_retry.list(0);
+    }
+    const uint32_t px_chunk = (uint32_t)std::max<uint64_t>(1, cap / (uint64_t)aov_spp);
+    for (uint32_t p0 = 0; p0 < n_px; p0 += px_chunk) {
+        const uint32_t np = std::min(px_chunk, n_px - p0), n = np * (uint32_t)aov_spp;
+        launch_aov_keys(p0, n, aov_spp, key_pixel, key_sample, st);
+        launch_camera_rays(cc, seed, n, key_pixel, key_sample, ray_o, ray_d, st);
+        launch_trace_closest(sc->view, n, nullptr, ray_o, ray_d, hits, rl, st);
+        launch_aov_resolve(sc->view, n, ray_o, ray_d, hits, rec0, rec1, st);
+        launch_aov_fold(p0, np, aov_spp, rec0, rec1, aov_dev, st);
+    }
+    HIP_TRY(hipGetLastError());
+    if (!in_ws) HIP_TRY(hipStreamSynchronize(st));  // (the call's own buffers are freed on return)
+    return MCPT_OK;
+}
+
+// Working buffers of the filter for one call: two record buffers and the depth gradient, 72 bytes per pixel.
+struct DenoiseBufs {
+    DevBuf<dn::Rec> rec[2];
+    DevBuf<float2> grad;
+    hipError_t alloc(size_t n_px) {
+        hipError_t e = rec[0].alloc(n_px);
+        if (e == hipSuccess) e = rec[1].alloc(n_px);
+        if (e == hipSuccess) e = grad.alloc(n_px);
+        return e;
+    }
+};
+
+bool frame_ok(int W, int H) { return W > 0 && H > 0 && (uint64_t)W * H <= 0x7fffffffull / 8; }
+
+}  // namespace
+
+extern "C" {
+
+int mcpt_render_aovs(mcpt_scene *sc, const mcpt_camera *cam, uint32_t seed, int32_t aov_spp, float *aov_host) {
+    if (!sc || !cam || !aov_host) return fail(MCPT_ERR_ARG, "mcpt_render_aovs: null argument");
+    if (!frame_ok(cam->width, cam->height)) return fail(MCPT_ERR_ARG, "mcpt_render_aovs: width and height must be positive (and the frame not too large)");
+    if (aov_spp < 0 || aov_spp > kMaxAovSpp) return fail(MCPT_ERR_ARG, "mcpt_render_aovs: aov_spp must be 0..65536");
+    const int32_t n_spp = aov_spp == 0 ? 4 : aov_spp;
+    HIP_TRY(hipSetDevice(sc->device));
+    (void)hipGetLastError();
+    const size_t n_px = (size_t)cam->width * cam->height;
+    DevBuf<float> aov;
+    HIP_TRY(aov.alloc(n_px * 8));
+    const int rc = aov_pass(sc, make_camera(*cam), seed, n_spp, aov.p, nullptr);
+    if (rc != MCPT_OK) return drained(rc);
+    HIP_TRY(hipMemcpy(aov_host, aov.p, n_px * 8 * sizeof(float), hipMemcpyDeviceToHost));
+    return MCPT_OK;
+}
+
+int mcpt_denoise(mcpt_scene *sc, int32_t width, int32_t height, const float *color_host, const float *variance_host, const float *aov_host,
+                 const mcpt_denoise_opts *opts, float *out_host) {
+    if (!sc || !color_host || !variance_host || !aov_host || !opts || !out_host) return fail(MCPT_ERR_ARG, "mcpt_denoise: null argument");
+    if (!frame_ok(width, height)) return fail(MCPT_ERR_ARG, "mcpt_denoise: width and height must be positive (and the frame not too large)");
+    dn::Opts o;
+    if (dn::resolve_opts(*opts, o) != 0) return fail(MCPT_ERR_ARG, "mcpt_denoise: option out of range");
+    HIP_TRY(hipSetDevice(sc->device));
+    (void)hipGetLastError();
+    const size_t n_px = (size_t)width * height;
+    DevBuf<float> col, var, aov, out;
+    HIP_TRY(col.alloc(n_px * 3));
+    HIP_TRY(var.alloc(n_px));
+    HIP_TRY(aov.alloc(n_px * 8));
+    HIP_TRY(out.alloc(n_px * 3));
+    HIP_TRY(hipMemcpy(col.p, color_host, n_px * 3 * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(var.p, variance_host, n_px * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(aov.p, aov_host, n_px * 8 * sizeof(float), hipMemcpyHostToDevice));
+    DenoiseBufs db;
+    HIP_TRY(db.alloc(n_px));
+    launch_denoise(width, height, o, col.p, var.p, aov.p, db.rec[0].p, db.rec[1].p, db.grad.p, out.p, nullptr);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(out_host, out.p, n_px * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    return MCPT_OK;
+}
+
+int mcpt_render_denoised(mcpt_scene *sc, const mcpt_camera *cam, const mcpt_params *pp, const mcpt_denoise_opts *opts, float *fb_host,
+                         float *denoised_host, float *variance_host, float *aov_host, mcpt_denoise_info *info, mcpt_stats *stats) {
+    if (!sc || !cam || !pp || !opts || !fb_host || !denoised_host) return fail(MCPT_ERR_ARG, "mcpt_render_denoised: null argument");
+    const mcpt_params &p = *pp;
+    if (!frame_ok(cam->width, cam->height) || p.n_dir_sample <= 0 || !(p.rr_rate > 0.f))
+        return fail(MCPT_ERR_ARG, "mcpt_render_denoised: width/height/n_dir_sample/rr_rate must be positive");
+    if (p.spp < 2) return fail(MCPT_ERR_ARG, "mcpt_render_denoised: params.spp must be at least 2");
+    if (p.nranks != 1) return fail(MCPT_ERR_ARG, "mcpt_render_denoised: nranks must be 1 (a partitioned frame is not denoised)");
+    if (p.accumulate != 0 || p.spp_total != 0 || p.sample_offset != 0)
+        return fail(MCPT_ERR_ARG, "mcpt_render_denoised: accumulate, spp_total and sample_offset must be 0");
+    dn::Opts o;
+    if (dn::resolve_opts(*opts, o) != 0) return fail(MCPT_ERR_ARG, "mcpt_render_denoised: option out of range");
+    if (opts->aov_spp > p.spp || opts->aov_spp > kMaxAovSpp) return fail(MCPT_ERR_ARG, "mcpt_render_denoised: aov_spp must be at most params.spp and 65536");
+    const int32_t aov_spp = opts->aov_spp == 0 ? std::min(4, p.spp) : opts->aov_spp;
+    HIP_TRY(hipSetDevice(sc->device));
+    (void)hipGetLastError();
+    const auto t0 = std::chrono::steady_clock::now();
+    const hipStream_t st = nullptr;
+    const int W = cam->width, H = cam->height;
+    const size_t n_px = (size_t)W * H;
+    DevBuf<float> fb, var, aov, out;
+    DevBuf<double> mom;
+    HIP_TRY(fb.alloc(n_px * 3));
+    HIP_TRY(var.alloc(n_px));
+    HIP_TRY(aov.alloc(n_px * 8));
+    HIP_TRY(out.alloc(n_px * 3));
+    HIP_TRY(mom.alloc(n_px * 6));
+    DenoiseBufs db;
+    HIP_TRY(db.alloc(n_px));
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    struct EvGuard {
+        hipEvent_t *e;
+        ~EvGuard() {
+            for (int k = 0; k < 4; ++k)
+                if (e[k]) (void)hipEventDestroy(e[k]);
+        }
+    } guard{ev};
+    for (int k = 0; k < 4; ++k) HIP_TRY(hipEventCreate(&ev[k]));
+    HIP_TRY(hipEventRecord(ev[0], st));
+    HIP_TRY(hipMemsetAsync(mom.p, 0, n_px * 6 * sizeof(double), st));
+    const CameraConst cc = make_camera(*cam);
+    PixelSet ps;
+    int rc = prepare_pixels(sc, cc, W, H, p, p.spp, (float)p.spp, fb.p, st, ps);
+    if (rc != MCPT_OK) return rc;
+    RunTotals rt;
+    if (ps.n_owned > ps.n_pix) launch_sky_moments(ps.sky, ps.n_owned - ps.n_pix, sc->view.background, p.spp, mom.p, st);
+    if (ps.n_pix > 0) {
+        rc = render_list(sc, cc, p, ps.list, ps.cand, ps.n_pix, 0, p.spp, (float)p.spp, fb.p, mom.p, st, t0, rt);
+        if (rc != MCPT_OK) return rc;
+    }
+    launch_dn_variance((uint32_t)n_px, mom.p, p.spp, var.p, st);
+    HIP_TRY(hipEventRecord(ev[1], st));
+    rc = aov_pass(sc, cc, p.seed, aov_spp, aov.p, st);
+    if (rc != MCPT_OK) return drained(rc);
+    HIP_TRY(hipEventRecord(ev[2], st));
+    launch_denoise(W, H, o, fb.p, var.p, aov.p, db.rec[0].p, db.rec[1].p, db.grad.p, out.p, st);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(ev[3], st));
+    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpy(fb_host, fb.p, n_px * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(denoised_host, out.p, n_px * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    if (variance_host) HIP_TRY(hipMemcpy(variance_host, var.p, n_px * sizeof(float), hipMemcpyDeviceToHost));
+    if (aov_host) HIP_TRY(hipMemcpy(aov_host, aov.p, n_px * 8 * sizeof(float), hipMemcpyDeviceToHost));
+    if (info) {
+        float ms[3] = {0.f, 0.f, 0.f};
+        for (int k = 0; k < 3; ++k) HIP_TRY(hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]));
+        info->ms_render = ms[0];
+        info->ms_aov = ms[1];
+        info->ms_denoise = ms[2];
+        info->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
+    if (stats) fill_stats(stats, (uint64_t)ps.n_owned * p.spp, (uint64_t)ps.n_pix * p.spp, p.n_dir_sample, rt, t0);
+    if (rt.overflow) return fail(MCPT_ERR_OVERFLOW, "some paths outran the clamp stack (raise params.max_depth)");
     return MCPT_OK;
 }
 

@@ -336,7 +336,29 @@ void Renderer::Render(const Scene &scene) {
         std::cerr << "mcpt: adaptive sampling renders on one GPU (no --gpus / --devices)" << std::endl;
         return;
     }
-    if (adaptive) {
+    if (!denoise_path.empty() && (scene.groupHandle() || adaptive || !checkpoint_path.empty())) {
+        std::cerr << "mcpt: denoising renders one plain frame on one GPU (no --gpus / --devices, --adaptive or --checkpoint)" << std::endl;
+        return;
+    }
+    if (!denoise_path.empty()) {
+        mcpt_denoise_opts o{};
+        o.aov_spp = denoise_aov_spp;
+        mcpt_denoise_info di{};
+        std::vector<float> denoised(framebuffer.size());
+        const int rc = mcpt_render_denoised(scene.handle(), &c, &p, &o, framebuffer.data(), denoised.data(), nullptr, nullptr, &di, &st);
+        if (rc != MCPT_OK) std::cerr << "mcpt: " << mcpt_last_error() << std::endl;
+        if (rc != MCPT_OK && rc != MCPT_ERR_OVERFLOW) return;
+        total = st;
+        std::cout << "[mcpt] denoise: render " << di.ms_render << " ms, AOVs " << di.ms_aov << " ms, filter " << di.ms_denoise << " ms" << std::endl;
+        std::cout << "Writing denoised image to " << denoise_path << std::endl;
+        std::vector<unsigned char> raw((size_t)4 * camera.width * camera.height);
+        if (mcpt_tonemap(scene.handle(), denoised.data(), (int64_t)camera.width * camera.height, raw.data()) != MCPT_OK) {
+            std::cerr << "mcpt: " << mcpt_last_error() << std::endl;
+            return;
+        }
+        const std::string err = png_min::encode_rgba(denoise_path, raw, camera.width, camera.height);
+        if (!err.empty()) std::cerr << "Error when writing image : " << err << std::endl;
+    } else if (adaptive) {
         mcpt_adaptive o{};
         o.min_spp = adaptive_min > 0 ? adaptive_min : std::min(64, spp);
         o.dilate = 1;

@@ -11,6 +11,8 @@
 //   --checkpoint FILE [--checkpoint-every N]   render in chunks of N spp (default 64), keep the running frame in FILE and resume from it
 //   --adaptive THRESHOLD [--adaptive-min N]   adaptive sampling (mcpt_render_adaptive): pixels stop at the first of the levels N, 2N, ...,
 //                 spp whose relative error estimate is at most THRESHOLD; the conf.json / --spp value is the maximum (N: 64 by default)
+//   --denoise FILE [--denoise-aov-spp N]   also write a denoised frame (mcpt_render_denoised: N feature samples per pixel, default
+//                 min(4, spp)) to FILE; --output stays the plain frame, byte for byte
 //   --dump FILE   write the flattened scene (what mcpt_scene_create receives) and exit without touching the GPU
 #include <chrono>
 #include <cstring>
@@ -43,6 +45,7 @@ int main(int argc, char **argv) {
     std::string models = "../models", conf_path = "conf.json", out_override, dump_path;
     int w_override = 0, h_override = 0, spp_override = 0;
     bool fixed = false;
+    int n_devices = 1;
     for (int i = 1; i < argc; ++i)
         if (std::string(argv[i]) == "--fixed") {  // the only flag without a value: take it out of the (flag, value) list
             fixed = true;
@@ -67,17 +70,26 @@ int main(int argc, char **argv) {
             r.adaptive_threshold = std::strtof(argv[i + 1], nullptr);
         }
         else if (a == "--adaptive-min") r.adaptive_min = std::atoi(argv[i + 1]);
+        else if (a == "--denoise") r.denoise_path = argv[i + 1];
+        else if (a == "--denoise-aov-spp") r.denoise_aov_spp = std::atoi(argv[i + 1]);
         else if (a == "--gpus") {
             std::vector<int> dev;
             for (int k = 0; k < std::atoi(argv[i + 1]); ++k) dev.push_back(k);
             scene.setDevices(dev);
+            n_devices = (int)dev.size();
         } else if (a == "--devices") {
             std::vector<int> dev;
             std::stringstream ss(argv[i + 1]);
             std::string tok;
             while (std::getline(ss, tok, ',')) dev.push_back(std::atoi(tok.c_str()));
             scene.setDevices(dev);
+            n_devices = (int)dev.size();
         }
+    }
+    if (!r.denoise_path.empty() && (r.adaptive || !r.checkpoint_path.empty() || n_devices > 1)) {
+        std::cerr << "--denoise cannot be combined with " << (r.adaptive ? "--adaptive" : (!r.checkpoint_path.empty() ? "--checkpoint" : "more than one device"))
+                  << std::endl;
+        return 1;
     }
     if (r.adaptive && !r.checkpoint_path.empty()) {
         std::cerr << "--adaptive cannot be combined with --checkpoint" << std::endl;

@@ -196,6 +196,70 @@ typedef struct {
 int mcpt_render_adaptive(mcpt_scene *scene, const mcpt_camera *camera, const mcpt_params *params, const mcpt_adaptive *opts,
                          float *fb_host, int32_t *spp_host, float *err_host, mcpt_adaptive_info *info, mcpt_stats *stats);
 
+/* ---- Feature buffers (AOVs) and a variance-guided a-trous denoiser (Dammertz et al. 2010; variance guidance of SVGF, Schied et al. 2017).
+ *
+ * AOV record: 8 floats per pixel, row-major m = j*W + i:  {albedo r,g,b, normal x,y,z, depth, coverage}.
+ * Feature sample k of pixel m is EXACTLY the camera ray of render sample k (Philox key (seed, m), camera stream; mcpt_camera_rays),
+ * traced with the scene's closest-hit traversal (mcpt_intersect) for every pixel (no sky cull).  Per sample:
+ *   albedo    conductors: the reflectance of the hit, the checkerboard included (Material.hpp:134-151); dielectrics, emitters and misses: 1
+ *   normal    the shading normal (the triangle's normal, or normalized(p - c) of a sphere), flipped to face the ray (dot(n, d) > 0 ? -n : n);
+ *             a miss: 0
+ *   depth     (float) of the double hit distance t;  coverage: 1 for a hit, 0 for a miss
+ * Folded per pixel in sample order, in float: albedo and normal acc += v_k / aov_spp (normals are NOT renormalised: a silhouette pixel
+ * carries a shorter one); depth = (sum of t_k over the hits) / hits, 0 without a hit; coverage = hits / aov_spp.
+ *
+ * Filter, in float32 (csrc/mcpt_denoise.h has every expression in its order; the device and a CPU build of it agree bit for bit):
+ *   1. demodulate: A = max(albedo, 1e-3) per channel, e = colour / A; the variance input (the luminance variance of the colour mean)
+ *      becomes v / lum(A)^2, lum = 0.2126 r + 0.7152 g + 0.0722 b.  A pixel whose colour, variance, e or scaled variance is not finite,
+ *      or whose variance is negative, passes through unchanged and has weight 0 as a neighbour (in the prefilter too).
+ *   2. depth gradient grad z: central differences over covered in-image neighbours; one-sided when one is missing, 0 when both are.
+ *   3. iteration i = 0 .. iterations-1, step s = 2^i: g_p = the 3x3 binomial (1,2,1)^2 prefilter of v over the usable in-image neighbours
+ *      on p's surface (both uncovered, or both covered with n_p.n_q > 0: the pairs whose tap weight below can be non-zero), normalised by
+ *      the weights it used, so that not even the variance crosses a coverage seam or a seam of orthogonal normals; taps q = p + s (dx, dy),
+ *      dy = -2..2, dx = -2..2 in that order, outside taps skipped:
+ *          w = h(dx) h(dy) max(0, n_p.n_q)^sigma_n exp(-( |z_p - z_q| / (sigma_z |grad z_p . (s dx, s dy)| + 1e-3 max(z_p, z_q) + 1e-6)
+ *                                                       + |l_p - l_q| / (sigma_l sqrt(g_p) + 1e-6) ))
+ *      h = (1/16, 1/4, 3/8, 1/4, 1/16), l = lum(e).  Exactly one of cov_p, cov_q zero: w = 0; both zero: normal and depth terms are 1.
+ *      e'_p = sum (w / sum w) e_q;  v'_p = sum (w / sum w)^2 v_q  (sum w e_q / sum w and sum w^2 v_q / (sum w)^2 in a form that keeps
+ *      its precision: the weights of an edge pixel with a short folded normal can be subnormal); a pixel whose weights sum to 0 keeps its
+ *      values.
+ *      ^sigma_n by square-and-multiply with the integer sigma_n; exp is the library's own plain-IEEE exp (within 1 ulp; 0 below -87).
+ *   4. remodulate: out = e * A.
+ * MCPT_ERR_ARG for null pointers that are not nullable, width or height <= 0 and out-of-range options (a non-zero reserved word included). */
+typedef struct {
+    int32_t aov_spp;     /* feature samples per pixel; 0 => min(4, params.spp) (mcpt_render_denoised; mcpt_denoise ignores it) */
+    int32_t iterations;  /* a-trous passes, step 2^i for i = 0..iterations-1; 0 => 5; at most 8 */
+    float sigma_l;       /* luminance weight, > 0; 0 => 4 */
+    float sigma_n;       /* normal exponent, an integer 1..1024; 0 => 128 */
+    float sigma_z;       /* depth weight, > 0; 0 => 1 */
+    int32_t reserved[3]; /* must be 0 */
+} mcpt_denoise_opts;     /* 32 bytes */
+
+typedef struct { double ms_render, ms_aov, ms_denoise, ms_total; } mcpt_denoise_info; /* 32 bytes: HIP-event times of the stages, host wall time */
+
+/* The AOV record of every pixel (aov_host: W*H*8 floats) for feature samples 0 .. aov_spp-1 of `seed`; aov_spp 0 => 4, at most 65536. */
+int mcpt_render_aovs(mcpt_scene *scene, const mcpt_camera *camera, uint32_t seed, int32_t aov_spp, float *aov_host);
+
+/* The filter on host arrays: color_host W*H*3, variance_host W*H (luminance variance of each colour mean), aov_host W*H*8 (as
+ * mcpt_render_aovs), out_host W*H*3.  The scene only picks the device and stream, as in mcpt_tonemap. */
+int mcpt_denoise(mcpt_scene *scene, int32_t width, int32_t height, const float *color_host, const float *variance_host, const float *aov_host,
+                 const mcpt_denoise_opts *opts, float *out_host);
+
+/* mcpt_render, then the filter, on one stream:
+ *   1. the frame with the per-pixel moments of adaptive round 0 (mcpt_render_adaptive): fb_host is BIT-IDENTICAL to mcpt_render's frame
+ *      (sky-culled pixels take their moments from the constant background samples);
+ *   2. the luminance variance of the mean, in double, rounded once to float, n = params.spp, w = (0.2126, 0.7152, 0.0722):
+ *          for c in 0..2:  m = s1/n;  q = s2/n - m*m;  var_c = max(q, 0) * n / (n - 1) / n;   v = sum_c w_c^2 var_c
+ *      It ignores the covariance between the channels: the R, G and B paths are separate Philox streams and share only the camera ray;
+ *   3. the AOVs of mcpt_render_aovs(params.seed, opts.aov_spp);  4. mcpt_denoise of the three.
+ * So fb, variance and aov are what the separate calls return, and denoised equals mcpt_denoise(fb, variance, aov, opts) bit for bit.
+ *   fb_host, denoised_host  W*H*3 floats;  variance_host W*H floats (nullable);  aov_host W*H*8 floats (nullable);  info (nullable);
+ *   stats as mcpt_render (nullable).
+ * MCPT_ERR_ARG also for params.spp < 2, opts.aov_spp > params.spp, nranks != 1, or a non-zero accumulate / spp_total / sample_offset
+ * (a partial or partitioned frame is not denoised).  MCPT_ERR_OVERFLOW as mcpt_render (the outputs are still written). */
+int mcpt_render_denoised(mcpt_scene *scene, const mcpt_camera *camera, const mcpt_params *params, const mcpt_denoise_opts *opts, float *fb_host,
+                         float *denoised_host, float *variance_host, float *aov_host, mcpt_denoise_info *info, mcpt_stats *stats);
+
 /* Replaces Scene::intersect (Scene.hpp:128, Scene.cpp:19-21) for a list of rays (host pointers; n*3 floats each).
  * out_t: hit distance as the reference's double Intersection::distance (DBL_MAX on a miss);
  * out_prim: global primitive id (triangle index, or n_triangles + object index for a sphere; -1 on a miss). */
