@@ -1545,22 +1545,34 @@ constexpr int32_t kMaxAovSpp = 65536;
 // whole pixels, pixel-major.  It runs inside the wavefront workspace of pool 0 when that holds at least one pixel's rays (after a render it
 // holds millions): camera rays and hits in wave 0's ray / hit arrays, the per-sample records in wave 1's, the keys in wave 1's path
 // records, the retrace list of the closest-hit rays.  Otherwise (no render yet on this scene) it uses buffers of its own for the call.
-int aov_pass(mcpt_scene *sc, const CameraConst &cc, uint32_t seed, int32_t aov_spp, float *aov_dev, hipStream_t st) {
+// spec_depth > 0 (mcpt_render_aovs_ex): each chunk runs the specular chains instead of k_aov_resolve -- k_aov_chain on the traced list, then
+// up to spec_depth times k_trace_closest + k_aov_chain on the compacted list of the samples that continue (its length read back once per
+// bounce).  In the workspace the second ray list is vtx0 / vtx1 with wave 1's hits, the chain states wave 0's and wave 1's rec1 with the
+// sums in wave 0's rec0 and vtx2, the count vtx_j[0] (chunks then hold at most `pool` rays); otherwise the call allocates them for a chunk.
+int aov_pass(mcpt_scene *sc, const CameraConst &cc, uint32_t seed, int32_t aov_spp, int32_t spec_depth, float *aov_dev, hipStream_t st) {
     const uint32_t n_px = (uint32_t)cc.width * (uint32_t)cc.height;
     const uint64_t need = std::min<uint64_t>(kAovChunkRays, (uint64_t)n_px * aov_spp);
     Workspace &w = sc->pools[0].ws;
-    // rays that fit: the ray arrays (ray_cap entries) and, for the keys, two uint32 per ray in wave 1's rec0 (4 per entry)
-    const uint64_t ws_rays = w.pool ? std::min<uint64_t>(w.ray_cap, 2ull * w.pool) : 0;
+    const bool chain = spec_depth > 0;
+    // rays that fit: the ray arrays (ray_cap entries) and, for the keys, two uint32 per ray in wave 1's rec0 (4 per entry); the chains use
+    // arrays of `pool` entries too
+    const uint64_t ws_rays = w.pool ? std::min<uint64_t>(w.ray_cap, (chain ? 1ull : 2ull) * w.pool) : 0;
     const bool retry = stack_uses_retry(sc->view.height);
     const bool in_ws = ws_rays >= (uint64_t)aov_spp && (!retry || w.retry.cap[0] >= std::min<uint64_t>(need, ws_rays));
-    DevBuf<uint32_t> keys;
-    DevBuf<float4> o4, d4, s0, s1;
-    DevBuf<uint4> hit;
+    DevBuf<uint32_t> keys, count;
+    DevBuf<float4> o4, d4, s0, s1, o4b, d4b, chb[2];
+    DevBuf<double> tsb[2];
+    DevBuf<uint4> hit, hitb;
     RetryBufs own_retry;
     uint64_t cap = need;
     uint32_t *key_pixel, *key_sample;
     float4 *ray_o, *ray_d, *rec0, *rec1;
     uint4 *hits;
+    // the specular chains: ray list 1 (list 0 is ray_o / ray_d / hits), the chain states of both lists, the count of the next list
+    float4 *ray2_o = nullptr, *ray2_d = nullptr, *chain_st[2] = {nullptr, nullptr};
+    double *chain_t[2] = {nullptr, nullptr};
+    uint4 *hits2 = nullptr;
+    uint32_t *n_next = nullptr;
     RetryList rl;
     if (in_ws) {
         cap = std::min<uint64_t>(need, ws_rays);
@@ -1572,6 +1584,16 @@ int aov_pass(mcpt_scene *sc, const CameraConst &cc, uint32_t seed, int32_t aov_s
         rec0 = w.wave[1].ray_o.p;
         rec1 = w.wave[1].ray_d.p;
         rl = w.retry.list(0);
+        if (chain) {
+            ray2_o = w.vtx0.p;
+            ray2_d = w.vtx1.p;
+            hits2 = w.wave[1].hit.p;
+            chain_st[0] = w.wave[0].rec1.p;
+            chain_st[1] = w.wave[1].rec1.p;
+            chain_t[0] = reinterpret_cast<double *>(w.wave[0].rec0.p);
+            chain_t[1] = reinterpret_cast<double *>(w.vtx2.p);
+            n_next = w.vtx_j.p;
+        }
     } else {
         HIP_TRY(keys.alloc(2 * cap));
         HIP_TRY(o4.alloc(cap));
@@ -1591,14 +1613,47 @@ int aov_pass(mcpt_scene *sc, const CameraConst &cc, uint32_t seed, int32_t aov_s
         rec0 = s0.p;
         rec1 = s1.p;
         rl = own_retry.list(0);
+        if (chain) {
+            HIP_TRY(o4b.alloc(cap));
+            HIP_TRY(d4b.alloc(cap));
+            HIP_TRY(hitb.alloc(cap));
+            HIP_TRY(count.alloc(1));
+            for (int k = 0; k < 2; ++k) {
+                HIP_TRY(chb[k].alloc(cap));
+                HIP_TRY(tsb[k].alloc(cap));
+                chain_st[k] = chb[k].p;
+                chain_t[k] = tsb[k].p;
+            }
+            ray2_o = o4b.p;
+            ray2_d = d4b.p;
+            hits2 = hitb.p;
+            n_next = count.p;
+        }
     }
+    float4 *const list_o[2] = {ray_o, ray2_o}, *const list_d[2] = {ray_d, ray2_d};
+    uint4 *const list_hit[2] = {hits, hits2};
     const uint32_t px_chunk = (uint32_t)std::max<uint64_t>(1, cap / (uint64_t)aov_spp);
     for (uint32_t p0 = 0; p0 < n_px; p0 += px_chunk) {
         const uint32_t np = std::min(px_chunk, n_px - p0), n = np * (uint32_t)aov_spp;
         launch_aov_keys(p0, n, aov_spp, key_pixel, key_sample, st);
         launch_camera_rays(cc, seed, n, key_pixel, key_sample, ray_o, ray_d, st);
         launch_trace_closest(sc->view, n, nullptr, ray_o, ray_d, hits, rl, st);
-        launch_aov_resolve(sc->view, n, ray_o, ray_d, hits, rec0, rec1, st);
+        if (!chain) {
+            launch_aov_resolve(sc->view, n, ray_o, ray_d, hits, rec0, rec1, st);
+        } else {
+            uint32_t m = n;  // rays in list `cur`, whose samples have all followed b bounces
+            for (int b = 0, cur = 0;; ++b, cur ^= 1) {
+                if (b < spec_depth) HIP_TRY(hipMemsetAsync(n_next, 0, sizeof(uint32_t), st));
+                launch_aov_chain(sc->view, m, b, spec_depth, list_o[cur], list_d[cur], list_hit[cur], b == 0 ? nullptr : chain_st[cur],
+                                 b == 0 ? nullptr : chain_t[cur], rec0, rec1, list_o[cur ^ 1], list_d[cur ^ 1], chain_st[cur ^ 1], chain_t[cur ^ 1],
+                                 n_next, st);
+                if (b == spec_depth) break;
+                HIP_TRY(hipMemcpyAsync(&m, n_next, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+                HIP_TRY(hipStreamSynchronize(st));
+                if (m == 0) break;
+                launch_trace_closest(sc->view, m, nullptr, list_o[cur ^ 1], list_d[cur ^ 1], list_hit[cur ^ 1], rl, st);
+            }
+        }
         launch_aov_fold(p0, np, aov_spp, rec0, rec1, aov_dev, st);
     }
     HIP_TRY(hipGetLastError());
@@ -1620,24 +1675,39 @@ struct DenoiseBufs {
 
 bool frame_ok(int W, int H) { return W > 0 && H > 0 && (uint64_t)W * H <= 0x7fffffffull / 8; }
 
-}  // namespace
-
-extern "C" {
-
-int mcpt_render_aovs(mcpt_scene *sc, const mcpt_camera *cam, uint32_t seed, int32_t aov_spp, float *aov_host) {
-    if (!sc || !cam || !aov_host) return fail(MCPT_ERR_ARG, "mcpt_render_aovs: null argument");
-    if (!frame_ok(cam->width, cam->height)) return fail(MCPT_ERR_ARG, "mcpt_render_aovs: width and height must be positive (and the frame not too large)");
-    if (aov_spp < 0 || aov_spp > kMaxAovSpp) return fail(MCPT_ERR_ARG, "mcpt_render_aovs: aov_spp must be 0..65536");
+// mcpt_render_aovs and mcpt_render_aovs_ex (`name` for the messages)
+int render_aovs(const char *name, mcpt_scene *sc, const mcpt_camera *cam, uint32_t seed, int32_t aov_spp, int32_t spec_depth, float *aov_host) {
+    char msg[160];
+    const auto bad = [&](const char *what) {
+        std::snprintf(msg, sizeof(msg), "%s: %s", name, what);
+        return fail(MCPT_ERR_ARG, msg);
+    };
+    if (!sc || !cam || !aov_host) return bad("null argument");
+    if (!frame_ok(cam->width, cam->height)) return bad("width and height must be positive (and the frame not too large)");
+    if (aov_spp < 0 || aov_spp > kMaxAovSpp) return bad("aov_spp must be 0..65536");
+    if (spec_depth < 0 || spec_depth > dn::kMaxSpecularDepth) return bad("specular_depth must be 0..8");
     const int32_t n_spp = aov_spp == 0 ? 4 : aov_spp;
     HIP_TRY(hipSetDevice(sc->device));
     (void)hipGetLastError();
     const size_t n_px = (size_t)cam->width * cam->height;
     DevBuf<float> aov;
     HIP_TRY(aov.alloc(n_px * 8));
-    const int rc = aov_pass(sc, make_camera(*cam), seed, n_spp, aov.p, nullptr);
+    const int rc = aov_pass(sc, make_camera(*cam), seed, n_spp, spec_depth, aov.p, nullptr);
     if (rc != MCPT_OK) return drained(rc);
     HIP_TRY(hipMemcpy(aov_host, aov.p, n_px * 8 * sizeof(float), hipMemcpyDeviceToHost));
     return MCPT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mcpt_render_aovs(mcpt_scene *sc, const mcpt_camera *cam, uint32_t seed, int32_t aov_spp, float *aov_host) {
+    return render_aovs("mcpt_render_aovs", sc, cam, seed, aov_spp, 0, aov_host);
+}
+
+int mcpt_render_aovs_ex(mcpt_scene *sc, const mcpt_camera *cam, uint32_t seed, int32_t aov_spp, int32_t specular_depth, float *aov_host) {
+    return render_aovs("mcpt_render_aovs_ex", sc, cam, seed, aov_spp, specular_depth, aov_host);
 }
 
 int mcpt_denoise(mcpt_scene *sc, int32_t width, int32_t height, const float *color_host, const float *variance_host, const float *aov_host,
@@ -1717,7 +1787,7 @@ int mcpt_render_denoised(mcpt_scene *sc, const mcpt_camera *cam, const mcpt_para
     }
     launch_dn_variance((uint32_t)n_px, mom.p, p.spp, var.p, st);
     HIP_TRY(hipEventRecord(ev[1], st));
-    rc = aov_pass(sc, cc, p.seed, aov_spp, aov.p, st);
+    rc = aov_pass(sc, cc, p.seed, aov_spp, opts->specular_depth, aov.p, st);
     if (rc != MCPT_OK) return drained(rc);
     HIP_TRY(hipEventRecord(ev[2], st));
     launch_denoise(W, H, o, fb.p, var.p, aov.p, db.rec[0].p, db.rec[1].p, db.grad.p, out.p, st);

@@ -42,6 +42,7 @@ constexpr float kInvalid = -1.0f;    // Rec::v of a pixel that passes through
 constexpr float kUncovered = -1.0f;  // Rec::z of a pixel with coverage 0
 constexpr float kAlbedoFloor = 1e-3f;
 constexpr int kMaxIterations = 8;
+constexpr int kMaxSpecularDepth = 8;  // mcpt_denoise_opts::specular_depth, mcpt_render_aovs_ex
 
 // Options after the defaults of include/mcpt.h have been applied.
 struct Opts {
@@ -53,7 +54,8 @@ struct Opts {
 // 0 on success, -1 if an option is out of range (aov_spp is checked by the callers that use it).
 MCPT_DN int resolve_opts(const mcpt_denoise_opts &o, Opts &out) {
     if (o.aov_spp < 0) return -1;
-    if (o.reserved[0] != 0 || o.reserved[1] != 0 || o.reserved[2] != 0) return -1;
+    if (o.specular_depth < 0 || o.specular_depth > kMaxSpecularDepth) return -1;
+    if (o.reserved[0] != 0 || o.reserved[1] != 0) return -1;
     out.iterations = o.iterations == 0 ? 5 : o.iterations;
     if (out.iterations < 1 || out.iterations > kMaxIterations) return -1;
     const float sl = o.sigma_l == 0.0f ? 4.0f : o.sigma_l, sz = o.sigma_z == 0.0f ? 1.0f : o.sigma_z;
@@ -301,6 +303,12 @@ namespace mcpt {
 void launch_aov_keys(uint32_t p0, uint32_t n, int32_t aov_spp, uint32_t *pixel, uint32_t *sample, hipStream_t st);
 // ... the per-sample records of the traced rays {albedo.rgb, depth} {normal.xyz, hit} ...
 void launch_aov_resolve(const DevScene &S, uint32_t n, const float4 *ray_o, const float4 *ray_d, const uint4 *hit, float4 *s0, float4 *s1, hipStream_t st);
+// ... or, following specular chains (mcpt_render_aovs_ex), one step for the n rays of a list whose samples have followed b bounces (chain_in
+// {thr.rgb, j as bits} and tsum_in; both nullptr for the camera rays: j = i): a finished sample writes s0[j], s1[j]; a continuing one
+// (b < max_b) is appended to next_o / next_d / chain_out / tsum_out at an index counted on *n_next ...
+void launch_aov_chain(const DevScene &S, uint32_t n, int32_t b, int32_t max_b, const float4 *ray_o, const float4 *ray_d, const uint4 *hit,
+                      const float4 *chain_in, const double *tsum_in, float4 *s0, float4 *s1, float4 *next_o, float4 *next_d, float4 *chain_out,
+                      double *tsum_out, uint32_t *n_next, hipStream_t st);
 // ... folded in sample order into aov[8 (p0 + i) ...] for the chunk's n_pix pixels
 void launch_aov_fold(uint32_t p0, uint32_t n_pix, int32_t aov_spp, const float4 *s0, const float4 *s1, float *aov, hipStream_t st);
 // var[m] = dn::luminance_variance of the moments (6 doubles per pixel) of n samples, for every pixel of the frame

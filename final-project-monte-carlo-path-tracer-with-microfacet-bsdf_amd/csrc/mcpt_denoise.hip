@@ -6,6 +6,8 @@
 //   k_trace_closest the scene's closest-hit traversal (mcpt_intersect)
 //   k_aov_resolve   hit -> per-sample record {albedo.rgb, depth} {normal.xyz, hit}
 //   k_aov_fold      one lane per pixel: the samples folded in sample order into the 8-float AOV record
+// With specular_depth > 0 (mcpt_render_aovs_ex) k_aov_chain takes k_aov_resolve's place: a sample whose hit is a Dirac (mirror or glass)
+// vertex continues, compacted into the next ray list, which k_trace_closest traces; at most specular_depth more steps, then k_aov_fold.
 // Denoise (csrc/mcpt_denoise.h has the arithmetic, shared with the CPU build the tests compare against):
 //   k_dn_prep       demodulation, scaled variance, depth gradient -> 32-byte records {e.rgb, v} {n.xyz, z}
 //   k_dn_atrous     one iteration (step 2^i), 16 x 16 pixel blocks, two 16-byte loads per tap, ping-pong between two record buffers
@@ -76,6 +78,103 @@ __global__ __launch_bounds__(kB) void k_aov_resolve(DevScene S, uint32_t n, cons
     }
     s0[j] = make_float4(alb[0], alb[1], alb[2], (float)t);
     s1[j] = make_float4(nrm.x, nrm.y, nrm.z, 1.f);
+}
+
+MCPT_DI uint32_t lane_id() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
+
+// One step of the specular chains (include/mcpt.h: mcpt_render_aovs_ex) for the n rays of a list whose samples have all followed b bounces:
+// ray i belongs to sample j with throughput thr and summed distance tsum (chain_in / tsum_in; nullptr for the camera rays: j = i, thr = 1,
+// tsum = 0).  A sample that stops writes its per-sample record s0[j], s1[j] as k_aov_resolve does; one that follows a Dirac bounce
+// (b < max_b) appends its next ray and state to the next list (ballot + prefix count, one atomic per wave on n_next).
+__global__ __launch_bounds__(kB) void k_aov_chain(DevScene S, uint32_t n, int32_t b, int32_t max_b, const float4 *__restrict__ ray_o,
+                                                  const float4 *__restrict__ ray_d, const uint4 *__restrict__ hit,
+                                                  const float4 *__restrict__ chain_in, const double *__restrict__ tsum_in,
+                                                  float4 *__restrict__ s0, float4 *__restrict__ s1, float4 *__restrict__ next_o,
+                                                  float4 *__restrict__ next_d, float4 *__restrict__ chain_out, double *__restrict__ tsum_out,
+                                                  uint32_t *__restrict__ n_next) {
+    const uint32_t i = blockIdx.x * kB + threadIdx.x;
+    bool cont = false;  // (no early return: every lane takes part in the ballot)
+    uint32_t j = i;
+    float thr[3] = {1.f, 1.f, 1.f};
+    double tsum = 0.0;
+    f3 p2 = mk3(0, 0, 0), wi = mk3(0, 0, 1);
+    if (i < n) {
+        if (chain_in) {
+            const float4 c = chain_in[i];
+            thr[0] = c.x;
+            thr[1] = c.y;
+            thr[2] = c.z;
+            j = __float_as_uint(c.w);
+            tsum = tsum_in[i];
+        }
+        const uint4 h = hit[i];
+        const int32_t prim = (int32_t)h.z;
+        if (prim < 0) {
+            s0[j] = make_float4(thr[0], thr[1], thr[2], 0.f);
+            s1[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+        } else {
+            const double t = __longlong_as_double((long long)(((unsigned long long)h.y << 32) | h.x));
+            tsum += t;
+            const uint32_t mat_bits = h.w;
+            const float4 o4 = ray_o[i], d4 = ray_d[i];
+            const f3 ro = mk3(o4.x, o4.y, o4.z), rd = mk3(d4.x, d4.y, d4.z);
+            const f3 p = ro + rd * (float)t;
+            f3 nrm;
+            f2 uv{0.f, 0.f};
+            if (prim < S.n_tri) {
+                const TriShade ts = S.tri_shade[prim];
+                nrm = mk3(ts.n[0], ts.n[1], ts.n[2]);
+                if (mat_bits & kMatTextured) {
+                    double tt, u, v;
+                    const Ray rr = make_ray(ro, rd);
+                    if (tri_hit(S.tri_geom[prim], rr, tt, u, v)) {
+                        const float a = (float)(1 - u - v), bb = (float)u, c = (float)v;
+                        uv.x = a * ts.t0[0] + bb * ts.t1[0] + c * ts.t2[0];
+                        uv.y = a * ts.t0[1] + bb * ts.t1[1] + c * ts.t2[1];
+                    }
+                }
+            } else {
+                const SphereRec sp = S.spheres[prim - S.n_tri];
+                nrm = normalized(p - mk3(sp.c[0], sp.c[1], sp.c[2]));
+            }
+            const MaterialRec &M = S.mats[mat_bits & kMatIndexMask];
+            const bool emitter = (mat_bits >> 31) != 0;
+            const bool conductor = M.type == MCPT_SMOOTH_CONDUCTOR || M.type == MCPT_ROUGH_CONDUCTOR;
+            cont = b < max_b && M.isDirac && !emitter;
+            if (cont) {  // k_shade's vertex (Scene.cpp:109-159) with mfn = n, channel 1, the more likely branch
+                const f3 wo = -rd;
+                const float kr = mat_fresnel(M, rd, nrm, 1);
+                const bool isReflect = kr > 0.5f;
+                if (isReflect) p2 = (dot(wo, nrm) < 0) ? (p - nrm * kEps) : (p + nrm * kEps);
+                else p2 = (dot(wo, nrm) < 0) ? (p + nrm * kEps) : (p - nrm * kEps);
+                wi = isReflect ? mat_reflect(wo, nrm) : mat_refract(M, rd, nrm, 1);
+                if (conductor)
+                    for (int c = 0; c < 3; ++c) thr[c] *= mat_eval(M, wi, wo, nrm, c, uv, true);
+            } else {
+                if (dot(nrm, rd) > 0) nrm = -nrm;
+                float alb[3] = {1.f, 1.f, 1.f};
+                if (!emitter && conductor) {
+                    alb[0] = get_reflectance(M, uv, 0);
+                    alb[1] = get_reflectance(M, uv, 1);
+                    alb[2] = get_reflectance(M, uv, 2);
+                }
+                s0[j] = make_float4(thr[0] * alb[0], thr[1] * alb[1], thr[2] * alb[2], (float)tsum);
+                s1[j] = make_float4(nrm.x, nrm.y, nrm.z, 1.f);
+            }
+        }
+    }
+    const unsigned long long mask = __ballot(cont);
+    if (mask == 0ull) return;
+    uint32_t base = 0;
+    if (lane_id() == 0) base = atomicAdd(n_next, (uint32_t)__popcll(mask));
+    base = __shfl(base, 0);
+    if (cont) {
+        const uint32_t k = base + __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+        next_o[k] = make_float4(p2.x, p2.y, p2.z, 0.f);
+        next_d[k] = make_float4(wi.x, wi.y, wi.z, 0.f);
+        chain_out[k] = make_float4(thr[0], thr[1], thr[2], __uint_as_float(j));
+        tsum_out[k] = tsum;
+    }
 }
 
 __global__ __launch_bounds__(kB) void k_aov_fold(uint32_t p0, uint32_t n_pix, int32_t aov_spp, const float4 *__restrict__ s0,
@@ -165,6 +264,14 @@ void launch_aov_keys(uint32_t p0, uint32_t n, int32_t aov_spp, uint32_t *pixel, 
 void launch_aov_resolve(const DevScene &S, uint32_t n, const float4 *ray_o, const float4 *ray_d, const uint4 *hit, float4 *s0, float4 *s1, hipStream_t st) {
     if (n == 0) return;
     hipLaunchKernelGGL(k_aov_resolve, dim3(nblocks(n)), dim3(kB), 0, st, S, n, ray_o, ray_d, hit, s0, s1);
+}
+
+void launch_aov_chain(const DevScene &S, uint32_t n, int32_t b, int32_t max_b, const float4 *ray_o, const float4 *ray_d, const uint4 *hit,
+                      const float4 *chain_in, const double *tsum_in, float4 *s0, float4 *s1, float4 *next_o, float4 *next_d, float4 *chain_out,
+                      double *tsum_out, uint32_t *n_next, hipStream_t st) {
+    if (n == 0) return;
+    hipLaunchKernelGGL(k_aov_chain, dim3(nblocks(n)), dim3(kB), 0, st, S, n, b, max_b, ray_o, ray_d, hit, chain_in, tsum_in, s0, s1, next_o, next_d,
+                       chain_out, tsum_out, n_next);
 }
 
 void launch_aov_fold(uint32_t p0, uint32_t n_pix, int32_t aov_spp, const float4 *s0, const float4 *s1, float *aov, hipStream_t st) {

@@ -16,7 +16,7 @@ LIB_PATH = os.environ.get("MCPT_LIB") or os.path.join(HERE, "libmcpt_hip.so")  #
 CHECK_LIB_PATH = os.path.join(HERE, "libmcpt_hip_check.so")  # the checking build (build.build_check); tests only
 
 EXPORTS = ["mcpt_scene_create", "mcpt_scene_destroy", "mcpt_render", "mcpt_render_device", "mcpt_render_adaptive", "mcpt_render_aovs",
-           "mcpt_denoise", "mcpt_render_denoised", "mcpt_intersect",
+           "mcpt_render_aovs_ex", "mcpt_denoise", "mcpt_render_denoised", "mcpt_intersect",
            "mcpt_cast_rays", "mcpt_camera_rays", "mcpt_scene_get_info", "mcpt_bvh_dump", "mcpt_scene_create_ex", "mcpt_scene_dump_bvh", "mcpt_tonemap", "mcpt_tonemap_device", "mcpt_debug_fmath", "mcpt_debug_material", "mcpt_debug_scene", "mcpt_debug_counters",
            "mcpt_group_create", "mcpt_group_render", "mcpt_group_size", "mcpt_group_get_info", "mcpt_group_scene", "mcpt_group_destroy", "mcpt_group_last_error",
            "mcpt_last_error", "mcpt_version"]
@@ -68,7 +68,7 @@ class AdaptiveInfo(C.Structure):
 
 class DenoiseOpts(C.Structure):
     _fields_ = [("aov_spp", C.c_int32), ("iterations", C.c_int32), ("sigma_l", C.c_float), ("sigma_n", C.c_float), ("sigma_z", C.c_float),
-                ("reserved", C.c_int32 * 3)]
+                ("specular_depth", C.c_int32), ("reserved", C.c_int32 * 2)]
 
 
 class DenoiseInfo(C.Structure):
@@ -78,9 +78,10 @@ class DenoiseInfo(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
-def denoise_opts(aov_spp=0, iterations=0, sigma_l=0.0, sigma_n=0.0, sigma_z=0.0):
-    """mcpt_denoise_opts (0 = the library's default for every field)."""
-    return DenoiseOpts(aov_spp=int(aov_spp), iterations=int(iterations), sigma_l=float(sigma_l), sigma_n=float(sigma_n), sigma_z=float(sigma_z))
+def denoise_opts(aov_spp=0, iterations=0, sigma_l=0.0, sigma_n=0.0, sigma_z=0.0, specular_depth=0):
+    """mcpt_denoise_opts (0 = the library's default for every field; specular_depth 0: first-hit AOVs)."""
+    return DenoiseOpts(aov_spp=int(aov_spp), iterations=int(iterations), sigma_l=float(sigma_l), sigma_n=float(sigma_n), sigma_z=float(sigma_z),
+                       specular_depth=int(specular_depth))
 
 
 class BuildOptions(C.Structure):
@@ -136,6 +137,8 @@ def lib(path=None):
                                            C.POINTER(AdaptiveInfo), C.POINTER(Stats)]
         L.mcpt_render_aovs.restype = C.c_int
         L.mcpt_render_aovs.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.c_void_p]
+        L.mcpt_render_aovs_ex.restype = C.c_int
+        L.mcpt_render_aovs_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.c_int32, C.c_void_p]
         L.mcpt_denoise.restype = C.c_int
         L.mcpt_denoise.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(DenoiseOpts), C.c_void_p]
         L.mcpt_render_denoised.restype = C.c_int
@@ -323,12 +326,16 @@ class HipScene:
                L=self.L)
         return fb, spp, err, info.as_dict(), st
 
-    def render_aovs(self, aov_spp=0, seed=1, camera=None):
-        """mcpt_render_aovs: aov[H,W,8] float32 = {albedo rgb, normal xyz, depth, coverage} from feature samples 0 .. aov_spp-1 (0: 4) of `seed`."""
+    def render_aovs(self, aov_spp=0, seed=1, camera=None, specular_depth=0):
+        """mcpt_render_aovs: aov[H,W,8] float32 = {albedo rgb, normal xyz, depth, coverage} from feature samples 0 .. aov_spp-1 (0: 4) of `seed`;
+        specular_depth > 0: mcpt_render_aovs_ex, the features taken behind up to that many mirror / glass bounces."""
         cam = np.ascontiguousarray(camera if camera is not None else self.sd.camera)
         W, H = int(cam["width"].reshape(-1)[0]), int(cam["height"].reshape(-1)[0])
         aov = np.zeros((H, W, 8), dtype=np.float32)
-        _check(self.L.mcpt_render_aovs(self.h, _ptr(cam), int(seed), int(aov_spp), _ptr(aov)), L=self.L)
+        if specular_depth == 0:
+            _check(self.L.mcpt_render_aovs(self.h, _ptr(cam), int(seed), int(aov_spp), _ptr(aov)), L=self.L)
+        else:
+            _check(self.L.mcpt_render_aovs_ex(self.h, _ptr(cam), int(seed), int(aov_spp), int(specular_depth), _ptr(aov)), L=self.L)
         return aov
 
     def denoise(self, color, variance, aov, **opts):
@@ -345,8 +352,8 @@ class HipScene:
         _check(self.L.mcpt_denoise(self.h, W, H, _ptr(color), _ptr(variance), _ptr(aov), C.byref(o), _ptr(out)), L=self.L)
         return out
 
-    def render_denoised(self, camera=None, aov_spp=0, iterations=0, sigma_l=0.0, sigma_n=0.0, sigma_z=0.0, features=True, **kw):
-        """mcpt_render_denoised: the frame of render(**kw) (bit for bit), its luminance variance, the AOVs of render_aovs(aov_spp, seed) and
+    def render_denoised(self, camera=None, aov_spp=0, iterations=0, sigma_l=0.0, sigma_n=0.0, sigma_z=0.0, features=True, specular_depth=0, **kw):
+        """mcpt_render_denoised: the frame of render(**kw) (bit for bit), its luminance variance, the AOVs of render_aovs(aov_spp, seed, specular_depth) and
         the denoised frame.  Returns dict(fb[H,W,3], denoised[H,W,3], variance[H,W], aov[H,W,8], info dict, stats); features=False leaves
         the variance and the AOVs on the device (None here: 36 bytes per pixel less to copy)."""
         cam = np.ascontiguousarray(camera if camera is not None else self.sd.camera)
@@ -356,7 +363,7 @@ class HipScene:
         var = np.zeros((H, W), dtype=np.float32) if features else None
         aov = np.zeros((H, W, 8), dtype=np.float32) if features else None
         p = self.params(**kw)
-        o = denoise_opts(aov_spp, iterations, sigma_l, sigma_n, sigma_z)
+        o = denoise_opts(aov_spp, iterations, sigma_l, sigma_n, sigma_z, specular_depth)
         info = DenoiseInfo()
         st = Stats()
         _check(self.L.mcpt_render_denoised(self.h, _ptr(cam), C.byref(p), C.byref(o), _ptr(fb), _ptr(den), None if var is None else _ptr(var),

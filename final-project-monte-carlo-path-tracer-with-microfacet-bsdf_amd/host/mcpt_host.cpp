@@ -343,6 +343,7 @@ void Renderer::Render(const Scene &scene) {
     if (!denoise_path.empty()) {
         mcpt_denoise_opts o{};
         o.aov_spp = denoise_aov_spp;
+        o.specular_depth = denoise_specular_depth;
         mcpt_denoise_info di{};
         std::vector<float> denoised(framebuffer.size());
         const int rc = mcpt_render_denoised(scene.handle(), &c, &p, &o, framebuffer.data(), denoised.data(), nullptr, nullptr, &di, &st);

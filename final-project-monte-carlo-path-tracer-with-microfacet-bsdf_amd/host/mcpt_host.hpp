@@ -264,9 +264,10 @@ class Renderer {
     int adaptive_min = 0;
     // Denoising (mcpt_render_denoised): the plain frame goes to `path` as without it (bit-identical), the denoised one, through the same
     // tone map, to denoise_path; denoise_aov_spp feature samples per pixel (0: min(4, spp)).  One GPU; not combined with a checkpoint or
-    // adaptive sampling.
+    // adaptive sampling.  denoise_specular_depth: mirror / glass bounces the feature samples follow (0: first-hit features).
     std::string denoise_path;
     int denoise_aov_spp = 0;
+    int denoise_specular_depth = 0;
 
   private:
     int spp = 2048;

@@ -13,6 +13,7 @@
 //                 spp whose relative error estimate is at most THRESHOLD; the conf.json / --spp value is the maximum (N: 64 by default)
 //   --denoise FILE [--denoise-aov-spp N]   also write a denoised frame (mcpt_render_denoised: N feature samples per pixel, default
 //                 min(4, spp)) to FILE; --output stays the plain frame, byte for byte
+//   --denoise-specular-depth N   the feature samples follow up to N mirror / glass bounces (0..8, default 0: first-hit features)
 //   --dump FILE   write the flattened scene (what mcpt_scene_create receives) and exit without touching the GPU
 #include <chrono>
 #include <cstring>
@@ -72,6 +73,7 @@ int main(int argc, char **argv) {
         else if (a == "--adaptive-min") r.adaptive_min = std::atoi(argv[i + 1]);
         else if (a == "--denoise") r.denoise_path = argv[i + 1];
         else if (a == "--denoise-aov-spp") r.denoise_aov_spp = std::atoi(argv[i + 1]);
+        else if (a == "--denoise-specular-depth") r.denoise_specular_depth = std::atoi(argv[i + 1]);
         else if (a == "--gpus") {
             std::vector<int> dev;
             for (int k = 0; k < std::atoi(argv[i + 1]); ++k) dev.push_back(k);

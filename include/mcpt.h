@@ -232,13 +232,40 @@ typedef struct {
     float sigma_l;       /* luminance weight, > 0; 0 => 4 */
     float sigma_n;       /* normal exponent, an integer 1..1024; 0 => 128 */
     float sigma_z;       /* depth weight, > 0; 0 => 1 */
-    int32_t reserved[3]; /* must be 0 */
+    int32_t specular_depth; /* delta bounces a feature sample follows, 0..8 (mcpt_render_aovs_ex); 0 => the first-hit AOVs
+                               (mcpt_render_denoised; mcpt_denoise range-checks it and ignores it) */
+    int32_t reserved[2]; /* must be 0 */
 } mcpt_denoise_opts;     /* 32 bytes */
 
 typedef struct { double ms_render, ms_aov, ms_denoise, ms_total; } mcpt_denoise_info; /* 32 bytes: HIP-event times of the stages, host wall time */
 
 /* The AOV record of every pixel (aov_host: W*H*8 floats) for feature samples 0 .. aov_spp-1 of `seed`; aov_spp 0 => 4, at most 65536. */
 int mcpt_render_aovs(mcpt_scene *scene, const mcpt_camera *camera, uint32_t seed, int32_t aov_spp, float *aov_host);
+
+/* Feature samples that see through mirrors and glass.  specular_depth, 0..8, is the largest number of delta (Dirac) bounces one feature
+ * sample follows.  Feature sample k of pixel m starts from the camera ray of render sample k (as above) with thr = (1,1,1) (float),
+ * tsum = 0 (double) and a bounce count b = 0, then repeats:
+ *   1. trace the closest hit of the current ray (d) with the scene's closest-hit traversal (mcpt_intersect);
+ *   2. a miss: the sample records albedo thr, normal 0, coverage 0 and no depth; stop;
+ *   3. a hit: tsum += t (the double hit distance); the hit point p = o + d * (float) t, the unflipped shading normal n, the uv and the
+ *      material as for the first-hit AOVs above (and as the shading kernel forms them);
+ *   4. if b < specular_depth, the material is Dirac (smooth conductor or smooth dielectric) and the hit is not an emitter, follow the
+ *      bounce with the shading kernel's expressions at that vertex (Scene.cpp:109-159; mfn = n, what Material::sample returns for a smooth
+ *      material), in channel 1 wherever an expression needs a channel:
+ *        kr = fresnel(d, n, channel 1);  isReflect = kr > 0.5 (the more likely branch: always for conductors, kr = 1, and under total
+ *        internal reflection);  wo = -d;
+ *        p2 = isReflect ? (dot(wo, n) < 0 ? p - n*EPS : p + n*EPS) : (dot(wo, n) < 0 ? p + n*EPS : p - n*EPS)   (EPS = 1e-4f);
+ *        wi = isReflect ? reflect(wo, n) : refract(d, n, channel 1);
+ *        conductors: thr[c] *= eval(wi, wo, n, c, uv, isReflect = 1) for c = 0, 1, 2 (the weight the render gives that mirror bounce
+ *        in that channel, the checkerboard included); dielectrics leave thr unchanged;
+ *      then b += 1 and the next ray is (p2, wi): back to 1;
+ *   5. otherwise the sample records this hit: albedo = thr[c] * the first-hit albedo of this hit (above), normal = this hit's n flipped
+ *      to face the ray that reached it, depth = (float) tsum, coverage 1.
+ * The samples are folded per pixel exactly as above.  The direction follows channel 1 of a dispersive material; the colour frame, its
+ * Philox streams and fb are untouched.  specular_depth 0 gives exactly mcpt_render_aovs (1 * x = x and (float) tsum = (float) t), and the
+ * call then runs the first-hit kernels themselves.  MCPT_ERR_ARG as mcpt_render_aovs, and for specular_depth outside 0..8, before any
+ * device call. */
+int mcpt_render_aovs_ex(mcpt_scene *scene, const mcpt_camera *camera, uint32_t seed, int32_t aov_spp, int32_t specular_depth, float *aov_host);
 
 /* The filter on host arrays: color_host W*H*3, variance_host W*H (luminance variance of each colour mean), aov_host W*H*8 (as
  * mcpt_render_aovs), out_host W*H*3.  The scene only picks the device and stream, as in mcpt_tonemap. */
@@ -251,7 +278,7 @@ int mcpt_denoise(mcpt_scene *scene, int32_t width, int32_t height, const float *
  *   2. the luminance variance of the mean, in double, rounded once to float, n = params.spp, w = (0.2126, 0.7152, 0.0722):
  *          for c in 0..2:  m = s1/n;  q = s2/n - m*m;  var_c = max(q, 0) * n / (n - 1) / n;   v = sum_c w_c^2 var_c
  *      It ignores the covariance between the channels: the R, G and B paths are separate Philox streams and share only the camera ray;
- *   3. the AOVs of mcpt_render_aovs(params.seed, opts.aov_spp);  4. mcpt_denoise of the three.
+ *   3. the AOVs of mcpt_render_aovs_ex(params.seed, opts.aov_spp, opts.specular_depth);  4. mcpt_denoise of the three.
  * So fb, variance and aov are what the separate calls return, and denoised equals mcpt_denoise(fb, variance, aov, opts) bit for bit.
  *   fb_host, denoised_host  W*H*3 floats;  variance_host W*H floats (nullable);  aov_host W*H*8 floats (nullable);  info (nullable);
  *   stats as mcpt_render (nullable).

@@ -1,15 +1,20 @@
 """Registers, LDS, scratch and static instruction counts of every kernel in csrc/mcpt_kernels.hip (cross-compiled for gfx950; no GPU
 needed).  A guard against silent code-generation changes: +2 VGPRs on a kernel at 79 means 88 allocated and one resident wave less.
-python tools/kernel_resources.py [extra -D flags]"""
+python tools/kernel_resources.py [--src mcpt_denoise.hip] [extra -D flags]   (--src: another file of csrc/)"""
 import os, re, subprocess, sys, tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "final-project-monte-carlo-path-tracer-with-microfacet-bsdf_amd", "csrc", "mcpt_kernels.hip")
+CSRC = os.path.join(ROOT, "final-project-monte-carlo-path-tracer-with-microfacet-bsdf_amd", "csrc")
+args = sys.argv[1:]
+name = "mcpt_kernels.hip"
+if args[:1] == ["--src"]:
+    name, args = args[1], args[2:]
+SRC = os.path.join(CSRC, name)
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize"]
 
 with tempfile.TemporaryDirectory() as d:
     out = os.path.join(d, "k.s")
-    subprocess.check_call(["/opt/rocm/bin/hipcc"] + FLAGS + sys.argv[1:] + ["-x", "hip", "-S", "--cuda-device-only", "-o", out, SRC], stderr=subprocess.DEVNULL)
+    subprocess.check_call(["/opt/rocm/bin/hipcc"] + FLAGS + args + ["-x", "hip", "-S", "--cuda-device-only", "-o", out, SRC], stderr=subprocess.DEVNULL)
     t = open(out).read()
 md = t[t.index("amdhsa.kernels"):]
 print("%-46s %5s %5s %7s %8s %6s %7s %6s" % ("kernel", "vgpr", "sgpr", "lds B", "scratch", "spills", "instrs", "waves"), " (waves per SIMD allowed by the VGPRs alone)")
