@@ -1,4 +1,4 @@
-// Adaptive sampling: the selection step between the rounds of mcpt_render_adaptive (csrc/mcpt_api.hip).
+// Adaptive sampling: the selection step between the rounds of mcpt_render_adaptive (csrc/mcpt_render.hip).
 //
 // A round renders every active pixel up to n samples (round 0: n = S0 for every owned pixel; later rounds: samples [n/2, n) of the
 // pixels that continued, divisor n).  Then:

@@ -1,0 +1,391 @@
+// The host layer behind the C ABI (include/mcpt.h): error plumbing, the owners of device resources, the wavefront workspace, the
+// environment knobs, the event timer, struct mcpt_scene, and what its translation units call in each other:
+//   mcpt_wavefront.hip  the wavefront loop, workspace / pass sizing (render_list), the pixel list and sky cull set-up
+//   mcpt_upload.hip     scene create / upload / destroy / info, the BVH dumps
+//   mcpt_render.hip     the frame-level entry points (render, adaptive, AOVs, denoise)
+//   mcpt_query.hip      ray queries, tone map and the debug entry points
+//   mcpt_multi.hip      mcpt_group_*
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <chrono>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "mcpt_kernels.h"
+
+namespace mcpt {
+
+extern thread_local std::string g_err;  // what mcpt_last_error returns (defined in mcpt_upload.hip)
+
+inline int fail(int code, const std::string &msg) {
+    g_err = msg;
+    return code;
+}
+
+#define HIP_TRY(expr)                                                                                   \
+    do {                                                                                                \
+        hipError_t e_ = (expr);                                                                         \
+        if (e_ != hipSuccess)                                                                           \
+            return fail(e_ == hipErrorOutOfMemory ? MCPT_ERR_OOM : MCPT_ERR_HIP,                        \
+                        std::string(#expr) + ": " + hipGetErrorString(e_));                             \
+    } while (0)
+
+using Clock = std::chrono::steady_clock;
+inline double ms_since(Clock::time_point t) { return std::chrono::duration<double, std::milli>(Clock::now() - t).count(); }
+
+// ---- owners.  Each frees what it holds when it goes out of scope (the device it was made on must be current), so an early error
+// return cannot leak it and nothing is listed a second time for release.  None can be copied or moved.
+
+// Device allocation; release() frees early.
+template <typename T>
+struct DevBuf {
+    T *p = nullptr;
+    size_t n = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { release(); }
+    hipError_t alloc(size_t count) {
+        if (count <= n && p) return hipSuccess;
+        release();
+        hipError_t e = hipMalloc((void **)&p, std::max<size_t>(count, 1) * sizeof(T));
+        if (e == hipSuccess) n = count;
+        else p = nullptr;
+        return e;
+    }
+    void release() {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        n = 0;
+    }
+    size_t bytes() const { return n * sizeof(T); }
+};
+
+template <typename T>
+hipError_t upload(DevBuf<T> &b, const T *src, size_t count) {
+    hipError_t e = b.alloc(count);
+    if (e != hipSuccess || count == 0) return e;
+    return hipMemcpy(b.p, src, count * sizeof(T), hipMemcpyHostToDevice);
+}
+template <typename T>
+hipError_t upload(DevBuf<T> &b, const std::vector<T> &v) {
+    return upload(b, v.data(), v.size());
+}
+template <typename T>
+hipError_t download(T *dst, const DevBuf<T> &b, size_t count) {
+    return hipMemcpy(dst, b.p, count * sizeof(T), hipMemcpyDeviceToHost);
+}
+
+// Non-blocking stream.  Destroyed only after the work queued on it is known to be done (drained(), or a synchronise that returned).
+struct Stream {
+    hipStream_t s = nullptr;
+    Stream() = default;
+    Stream(const Stream &) = delete;
+    Stream &operator=(const Stream &) = delete;
+    ~Stream() {
+        if (s) (void)hipStreamDestroy(s);
+    }
+    hipError_t create() { return hipStreamCreateWithFlags(&s, hipStreamNonBlocking); }
+    operator hipStream_t() const { return s; }
+};
+
+struct Event {
+    hipEvent_t e = nullptr;
+    Event() = default;
+    Event(const Event &) = delete;
+    Event &operator=(const Event &) = delete;
+    ~Event() {
+        if (e) (void)hipEventDestroy(e);
+    }
+    hipError_t create(bool timing = false) { return timing ? hipEventCreate(&e) : hipEventCreateWithFlags(&e, hipEventDisableTiming); }
+    operator hipEvent_t() const { return e; }
+};
+
+// The pinned host copy of the device counters.
+struct PinnedCounters {
+    Counters *p = nullptr;
+    PinnedCounters() = default;
+    PinnedCounters(const PinnedCounters &) = delete;
+    PinnedCounters &operator=(const PinnedCounters &) = delete;
+    ~PinnedCounters() {
+        if (p) (void)hipHostFree(p);
+    }
+    hipError_t alloc() { return p ? hipSuccess : hipHostMalloc((void **)&p, sizeof(Counters)); }
+    Counters *operator->() const { return p; }
+};
+
+struct WaveBufs {
+    DevBuf<uint4> rec0, hit;
+    DevBuf<float4> rec1, ray_o, ray_d;
+    DevBuf<float> contrib;
+    DevBuf<uint2> fresh;
+    Wave view() const { return Wave{rec0.p, rec1.p, ray_o.p, ray_d.p, hit.p, contrib.p, fresh.p}; }
+};
+
+// The retrace lists of the traversal kernels (RetryList, csrc/mcpt_kernels.h): allocated only for scenes whose tree runs the retry
+// flavour of the traversal stack (stack_uses_retry); each list holds as many entries as one launch can have rays.
+struct RetryBufs {
+    DevBuf<uint32_t> ctl;  // {count, done} x 3, zero between launches
+    DevBuf<uint32_t> items[3];
+    uint32_t cap[3] = {0, 0, 0};
+    hipError_t alloc(const uint32_t want[3]) {
+        hipError_t e = ctl.alloc(8);
+        if (e != hipSuccess) return e;
+        if ((e = hipMemset(ctl.p, 0, 8 * sizeof(uint32_t))) != hipSuccess) return e;
+        for (int k = 0; k < 3; ++k) {
+            if ((e = items[k].alloc(want[k])) != hipSuccess) return e;
+            cap[k] = want[k];
+        }
+        return hipSuccess;
+    }
+    // the closest-hit list alone, for launches of up to n rays outside the wavefront loop; nothing when the tree needs no retrace
+    hipError_t for_rays(uint32_t n, int height) {
+        const uint32_t want[3] = {n, 1u, 1u};
+        return stack_uses_retry(height) ? alloc(want) : hipSuccess;
+    }
+    RetryList list(int k) const { return ctl.p ? RetryList{ctl.p + 2 * k, ctl.p + 2 * k + 1, items[k].p, cap[k]} : RetryList{nullptr, nullptr, nullptr, 0u}; }
+};
+
+struct Workspace {
+    uint32_t pool = 0, free_ring = 0, ray_cap = 0;
+    RetryBufs retry;  // 0 closest-hit rays, 1 shadow rays, 2 primary samples
+    int32_t n_dir = 0, max_depth = 0;
+    WaveBufs wave[2];
+    DevBuf<float4> vtx0, vtx1, vtx2, shq_o, shq_d;
+    DevBuf<uint32_t> vtx_j;
+    Scratch scratch() const { return Scratch{vtx0.p, vtx1.p, vtx2.p, vtx_j.p, shq_o.p, shq_d.p}; }
+    DevBuf<float4> stack;
+    DevBuf<uint32_t> free_slots;
+    DevBuf<Counters> counters;
+    PinnedCounters h_counters;
+};
+
+// Buffers shared by the wavefront pools of one scene.
+struct SharedBufs {
+    DevBuf<float> result;
+    DevBuf<uint32_t> pixel_list, key_pixel, key_sample;
+    DevBuf<uint32_t> culled_list, cull_count;  // pixel_list partitioned: [may hit | background only] (csrc/mcpt_cull.hip)
+    DevBuf<uint8_t> cull_flags, cull_temp;
+    DevBuf<int4> cand_tmp, cand_list;  // per pixel: the few primitives its rays can hit (aligned with culled_list)
+    DevBuf<int32_t> key_channel;
+    int pix_key[5] = {0, 0, 0, 0, 0};  // (W, H, tile, rank, nranks) of the pixel list currently in HBM
+    uint32_t n_pix = 0;
+};
+
+// Environment knobs, read ONCE per scene in mcpt_scene_create: a render call never calls getenv.
+struct Knobs {
+    bool overlap = true;        // MCPT_OVERLAP=0: one stream instead of three
+    bool queue_ahead = true;    // MCPT_QUEUE_AHEAD=0: wait for the counters before launching the chains
+    bool timing = true;         // MCPT_TIMING=0: no per-kernel HIP events
+    bool verbose = false;       // MCPT_RENDER_VERBOSE=1: a line per render call on stderr (pass size, pool, time of the allocations)
+    int pools = 1;              // MCPT_POOLS=2: two pools on two host threads
+    int drain_batch = 4;        // MCPT_DRAIN_BATCH: iterations per host sync in the drain tail
+    uint64_t pool_min_work = 1ull << 20;  // MCPT_POOL_MIN_WORK: smallest pass (samples) that uses two pools
+    // Grid caps, in workgroups per CU.  Every workgroup of k_trace_shadow computes the prefix sums of the queue's shards first, and the
+    // LDS-resident flavours copy the scene into LDS first: with 128 / 64 per CU a workgroup strides over several chunks for one such
+    // prologue and the hardware still balances uneven rays (round 3, A/B: cornell_rc 784^2 471 -> 490 Msamples/s, DEMO 1080p 873 -> 924,
+    // k_trace_shadow -11 %, k_direct -14 %; chess within noise for 64..1024.  8 per CU, a persistent grid, was 30 % slower in round 1).
+    uint32_t shadow_grid_per_cu = 128;    // MCPT_SHADOW_GRID_PER_CU: grid cap of k_trace_shadow
+    uint32_t direct_grid_per_cu = 64;     // MCPT_DIRECT_GRID_PER_CU: grid cap of k_direct for LDS-resident scenes (0: none)
+    // pure test hooks, compiled only into the checking build (-DMCPT_TEST_HOOKS, libmcpt_hip_check.so)
+    uint32_t ring_start = 0;    // MCPT_RING_START: the free ring's counters start here (exercises the 2^32 wrap)
+    int host_delay_us = 0;      // MCPT_HOST_DELAY_US: a slow host
+    bool sky_cull = true;       // MCPT_SKY_CULL=0: trace the pixels that can only see the background too
+    bool small_scene = true;    // MCPT_SMALL_SCENE=0: no LDS-resident flavour for scenes of a few KB
+    uint64_t fake_free_mb = 0;  // MCPT_FAKE_FREE_MB: pretend that only this much device memory is free (exercises the pool shrink)
+    void read();
+};
+
+enum KClass { K_CLOSEST = 0, K_SHADOW, K_SHADE, K_GENERATE, K_RESOLVE, K_DIRECT, K_NCLASS };
+
+struct Timer {
+    // Two banks of events: the host runs one iteration ahead of the GPU, so the events of iteration i are only known to be
+    // complete once the read-back of iteration i+1 has arrived; iteration i+1 meanwhile records into the other bank.
+    bool enabled = true;
+    int bank = 0;
+    std::vector<hipEvent_t> pool[2];  // owned
+    struct Rec { int a, b, cls; };
+    std::vector<Rec> recs[2];
+    size_t used[2] = {0, 0};
+    double ms[K_NCLASS] = {0, 0, 0, 0, 0, 0};
+    uint64_t count[K_NCLASS] = {0, 0, 0, 0, 0, 0};
+    Timer() = default;
+    Timer(const Timer &) = delete;
+    Timer &operator=(const Timer &) = delete;
+    ~Timer() {
+        for (int k = 0; k < 2; ++k)
+            for (hipEvent_t e : pool[k]) (void)hipEventDestroy(e);
+    }
+    int get() {
+        if (used[bank] == pool[bank].size()) {
+            hipEvent_t e;
+            if (hipEventCreate(&e) != hipSuccess) return -1;
+            pool[bank].push_back(e);
+        }
+        return (int)used[bank]++;
+    }
+    // One launch of class `cls` on stream s: counted, and (timing on) bracketed by two events on s.
+    template <typename Launch>
+    void timed(int cls, hipStream_t s, Launch &&launch) {
+        const int a = enabled ? get() : -1;
+        if (a >= 0) (void)hipEventRecord(pool[bank][a], s);
+        launch();
+        count[cls]++;
+        const int b = a >= 0 ? get() : -1;
+        if (b < 0) return;
+        (void)hipEventRecord(pool[bank][b], s);
+        recs[bank].push_back({a, b, cls});
+    }
+    void collect_bank(int k) {  // every event of bank k must have completed
+        for (const Rec &r : recs[k]) {
+            float t = 0.f;
+            if (hipEventElapsedTime(&t, pool[k][r.a], pool[k][r.b]) == hipSuccess) ms[r.cls] += t;
+        }
+        recs[k].clear();
+        used[k] = 0;
+    }
+    void collect() {  // call after a full stream sync
+        collect_bank(0);
+        collect_bank(1);
+    }
+    void reset() {
+        for (int i = 0; i < K_NCLASS; ++i) { ms[i] = 0; count[i] = 0; }
+        for (int k = 0; k < 2; ++k) { recs[k].clear(); used[k] = 0; }
+        bank = 0;
+    }
+};
+
+// What the wavefront loop did, summed over pools, passes and calls.
+struct Totals {
+    uint64_t iterations = 0, shaded = 0, closest = 0, shadow = 0, direct = 0, pushes = 0, overflow = 0;
+    double ms[K_NCLASS] = {0, 0, 0, 0, 0, 0};
+    uint64_t cnt[K_NCLASS] = {0, 0, 0, 0, 0, 0};
+    Totals &operator+=(const Totals &o) {
+        iterations += o.iterations;
+        shaded += o.shaded;
+        closest += o.closest;
+        shadow += o.shadow;
+        direct += o.direct;
+        pushes += o.pushes;
+        overflow += o.overflow;
+        for (int c = 0; c < K_NCLASS; ++c) {
+            ms[c] += o.ms[c];
+            cnt[c] += o.cnt[c];
+        }
+        return *this;
+    }
+};
+
+}  // namespace mcpt
+
+// Members are destroyed in reverse order, with the scene's device current (mcpt_scene_destroy): the pools' workspaces and timers, their
+// events, their streams, the shared buffers, then the scene arrays.
+struct mcpt_scene {
+    int device = 0;
+    int device_sharers = 1;  // scenes of one group that live on this device (mcpt_group_create with a device listed several times)
+    int32_t n_inner = 0;  // inner nodes of the traversal tree (0: the root is a leaf)
+    mcpt::Knobs knobs;
+    mcpt_scene_info info{};
+    mcpt::DevBuf<mcpt::Node> nodes;
+    mcpt::DevBuf<mcpt::QNode> qnodes;
+    mcpt::DevBuf<mcpt::TriGeom> tri_geom;
+    mcpt::DevBuf<mcpt::TriShade> tri_shade;
+    mcpt::DevBuf<mcpt::SphereRec> spheres;
+    mcpt::DevBuf<mcpt::MaterialRec> mats;
+    mcpt::DevBuf<mcpt::LightRec> lights;
+    mcpt::DevBuf<mcpt::LightNode> light_nodes;
+    mcpt::DevBuf<mcpt::LightTri> light_tris;
+    mcpt::DevBuf<mcpt::InstRec> inst;
+    mcpt::DevBuf<float> env;
+    mcpt::DevBuf<unsigned long long> dbg;
+    mcpt::DevScene view{};
+    mcpt::Event fork;
+    mcpt::SharedBufs shared;
+    // A wavefront pool: its own path lists, queues, clamp stack, counters and streams.  With MCPT_POOLS=2 two pools
+    // are driven by two host threads on disjoint halves of each pass, so that one pool's k_shade (and its host
+    // round trip) overlaps the other pool's traversal kernels.
+    struct PoolCtx {
+        mcpt::Stream main;  // owned stream (pool 0 uses the caller's stream instead)
+        // The three chains of one iteration (direct -> shadow, continuation rays, new primary rays) are
+        // independent: they run on separate streams and are joined before the next k_shade.
+        mcpt::Stream side[2];
+        mcpt::Event join[2];
+        mcpt::Event book;  // main -> primary stream: the previous iteration's k_bookkeep has cleared the list counters
+        mcpt::Event shaded, readback;  // k_shade done (-> closest stream); counters are in host memory
+        int rc = 0;
+        std::string err;
+        mcpt::Timer timer;
+        mcpt::Workspace ws;
+    };
+    static constexpr int kMaxPools = 2;
+    PoolCtx pools[kMaxPools];
+    int n_pools = 2;
+};
+
+namespace mcpt {
+
+using PoolCtx = mcpt_scene::PoolCtx;
+
+// ---- mcpt_upload.hip
+// The two halves of mcpt_scene_create, exposed for mcpt_group_create (csrc/mcpt_multi.hip), which flattens the scene and builds its
+// tree once and then uploads it to every device from one thread per device.
+struct HostBuild {
+    HostScene hs;
+    BuildChoice choice;
+    double build_ms = 0.0;  // flattening + host tree build
+    double init_ms = 0.0;   // first use of the device by this process (context, code objects), overlapped with the host build
+};
+int build_scene_host(const mcpt_scene_desc *desc, const mcpt_build_options *options, HostBuild &hb);
+int upload_scene(const mcpt_scene_desc *desc, HostBuild &hb, int device, mcpt_scene **out);
+double warm_up_device(int device);
+
+// ---- mcpt_wavefront.hip
+hipError_t ensure_workspace(PoolCtx &ctx, uint32_t pool, int32_t n_dir, int32_t max_depth, bool retry_lists);
+int derive_max_depth(const mcpt_params &p);
+CameraConst make_camera(const mcpt_camera &c);
+// RenderConst with what the params decide (rr_rate, n_dir_sample, shadows, seed) and max_depth; the rest zero
+RenderConst base_consts(const mcpt_params &p, int max_depth);
+
+// One pass of a render call: `n_work` camera samples whose results live in one half of the result buffer.
+struct PassPlan {
+    uint32_t first_work;  // first sample slot of the pass handled by this pool
+    uint32_t n_work;      // sample slots handled by this pool
+    int32_t s_pass, sample_offset;
+};
+
+// Where finished passes go.  acc == nullptr: the caller accumulates (single pass only).
+struct AccumPlan {
+    float *fb;
+    float spp_total;
+    uint32_t n_pix;
+    const uint32_t *pixel_list;
+    float *result[2];
+    double *moments;  // adaptive sampling: per-pixel sums of v and v*v (nullptr: the plain fold)
+};
+
+int run_wavefront(mcpt_scene *sc, PoolCtx &ctx, const RenderConst &C0, const CameraConst *cam, const std::vector<PassPlan> &plan,
+                  const AccumPlan *acc, hipStream_t st, Totals &tot);
+// After a failed run_wavefront the side streams may still hold kernels that use the workspace: wait for them before the
+// caller sees the error (and possibly frees buffers).  The error text of the failure is kept.
+int drained(int rc);
+
+// The owned pixels of a render call once the sky cull has run: the traced ones (with their candidate lists, or none) and the culled ones.
+struct PixelSet {
+    uint32_t n_owned = 0, n_pix = 0;  // owned pixels, traced pixels
+    const uint32_t *list = nullptr;   // the traced pixels
+    const int4 *cand = nullptr;       // their sky-cull candidate entries (nullptr: primary rays walk the tree)
+    const uint32_t *sky = nullptr;    // the n_owned - n_pix culled pixels
+};
+int prepare_pixels(mcpt_scene *sc, const CameraConst &cc, const mcpt_params &p, int32_t spp, float spp_total, float *fb_dev, hipStream_t st,
+                   PixelSet &ps);
+int render_list(mcpt_scene *sc, const CameraConst &cc, const mcpt_params &p, const uint32_t *pixel_list, const int4 *pixel_cand, uint32_t n_pix,
+                int32_t sample_offset, int32_t spp, float spp_total, float *fb_dev, double *moments, hipStream_t st, Clock::time_point t0,
+                Totals &rt);
+
+// ---- mcpt_render.hip
+void add(mcpt_stats &a, const mcpt_stats &b);  // every count and kernel time of b into a (ms_total is the caller's)
+
+}  // namespace mcpt

@@ -1,6 +1,6 @@
 // HIP kernels of the wavefront path tracer for gfx950 (MI355X, CDNA4; 64-wide wavefronts).
 //
-// Pipeline per wavefront iteration (host loop in mcpt_api.cpp):
+// Pipeline per wavefront iteration (host loop in mcpt_wavefront.hip):
 //   k_shade          one lane per path record: resolves the pending vertex (direct-light sum, continuation
 //                    hit), finishes the path or pushes a clamp-stack level, samples the BSDF at the next vertex and
 //                    emits a vertex record + at most one continuation ray; survivors are stream-compacted into

@@ -22,7 +22,7 @@
 #include <thread>
 #include <vector>
 
-#include "mcpt_kernels.h"
+#include "mcpt_host.h"
 
 using namespace mcpt;
 
@@ -65,8 +65,7 @@ struct RcclApi {
 struct mcpt_group {
     std::vector<int> devices;
     std::vector<mcpt_scene *> scenes;
-    std::vector<float *> fb;       // one device framebuffer per entry (W*H*3 floats), grown on demand
-    std::vector<size_t> fb_floats;
+    std::vector<DevBuf<float>> fb;  // one device framebuffer per entry (W*H*3 floats), grown on demand
     std::vector<hipStream_t> streams;
     bool same_device = true;
     RcclApi rccl;
@@ -94,7 +93,7 @@ void mcpt_group_destroy(mcpt_group *g) {
     for (size_t i = 0; i < g->scenes.size(); ++i) {
         if (!g->scenes[i]) continue;  // (never created: its device index may not even exist)
         (void)hipSetDevice(g->devices[i]);
-        if (i < g->fb.size() && g->fb[i]) (void)hipFree(g->fb[i]);
+        if (i < g->fb.size()) g->fb[i].release();
         if (i < g->streams.size() && g->streams[i]) (void)hipStreamDestroy(g->streams[i]);
         if (g->scenes[i]) mcpt_scene_destroy(g->scenes[i]);
     }
@@ -109,8 +108,7 @@ int mcpt_group_create(const mcpt_scene_desc *desc, int n_devices, const int *dev
     if (!g) return gfail(MCPT_ERR_OOM, "mcpt_group_create: host allocation failed");
     g->devices.assign(devices, devices + n_devices);
     g->scenes.assign(n_devices, nullptr);
-    g->fb.assign(n_devices, nullptr);
-    g->fb_floats.assign(n_devices, 0);
+    g->fb = std::vector<DevBuf<float>>((size_t)n_devices);
     g->streams.assign(n_devices, nullptr);
     g->same_device = true;
     for (int i = 1; i < n_devices; ++i) g->same_device = g->same_device && devices[i] == devices[0];
@@ -191,7 +189,7 @@ int mcpt_group_create(const mcpt_scene_desc *desc, int n_devices, const int *dev
     for (int i = 0; i < n_devices; ++i) {
         int sharers = 0;
         for (int j = 0; j < n_devices; ++j) sharers += devices[j] == devices[i] ? 1 : 0;
-        set_device_sharers(g->scenes[(size_t)i], sharers);
+        g->scenes[(size_t)i]->device_sharers = sharers;  // replicas on one device divide its free memory between them
     }
     g->setup_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     *out = g;
@@ -249,28 +247,22 @@ int mcpt_group_render(mcpt_group *g, const mcpt_camera *cam, const mcpt_params *
             return false;
         };
         if (!hip_ok(hipSetDevice(g->devices[i]), "hipSetDevice")) return;
-        if (g->fb_floats[i] < n) {
-            if (g->fb[i]) (void)hipFree(g->fb[i]);
-            g->fb[i] = nullptr;
-            g->fb_floats[i] = 0;
-            if (!hip_ok(hipMalloc((void **)&g->fb[i], n * sizeof(float)), "hipMalloc(framebuffer)")) return;
-            g->fb_floats[i] = n;
-        }
+        if (!hip_ok(g->fb[i].alloc(n), "hipMalloc(framebuffer)")) return;
         mcpt_params p = *pp;
         p.tile_size = tile;
         p.rank = i;
         p.nranks = N;
         hipStream_t s = g->streams[i];
         if (p.accumulate) {  // every replica continues from the caller's frame on ITS pixels; the others are zeroed before the merge
-            if (!hip_ok(hipMemcpyAsync(g->fb[i], fb_host, n * sizeof(float), hipMemcpyHostToDevice, s), "framebuffer upload")) return;
+            if (!hip_ok(hipMemcpyAsync(g->fb[i].p, fb_host, n * sizeof(float), hipMemcpyHostToDevice, s), "framebuffer upload")) return;
         }
-        rc[i] = mcpt_render_device(g->scenes[i], cam, &p, g->fb[i], (void *)s, &st[i]);
+        rc[i] = mcpt_render_device(g->scenes[i], cam, &p, g->fb[i].p, (void *)s, &st[i]);
         if (rc[i] != MCPT_OK && rc[i] != MCPT_ERR_OVERFLOW) {
             err[i] = mcpt_last_error();
             return;
         }
         if (rc[i] == MCPT_ERR_OVERFLOW) err[i] = mcpt_last_error();
-        if (p.accumulate) launch_mask_unowned(g->fb[i], cam->width, cam->height, tile, i, N, s);
+        if (p.accumulate) launch_mask_unowned(g->fb[i].p, cam->width, cam->height, tile, i, N, s);
         (void)hip_ok(hipStreamSynchronize(s), "hipStreamSynchronize");
     };
     {
@@ -291,7 +283,7 @@ int mcpt_group_render(mcpt_group *g, const mcpt_camera *cam, const mcpt_params *
         // over all communicators (the single-process multi-GPU pattern), then every stream is waited for.
         ncclResult_t r = g->rccl.GroupStart();
         for (int i = 0; i < N && r == ncclSuccess; ++i)
-            r = g->rccl.Reduce(g->fb[i], g->fb[i], n, ncclFloat, ncclSum, 0, g->comms[i], g->streams[i]);
+            r = g->rccl.Reduce(g->fb[i].p, g->fb[i].p, n, ncclFloat, ncclSum, 0, g->comms[i], g->streams[i]);
         const ncclResult_t r2 = g->rccl.GroupEnd();
         if (r == ncclSuccess) r = r2;
         if (r != ncclSuccess) return gfail(MCPT_ERR_HIP, std::string("mcpt_group_render: ncclReduce: ") + g->rccl.GetErrorString(r));
@@ -302,25 +294,16 @@ int mcpt_group_render(mcpt_group *g, const mcpt_camera *cam, const mcpt_params *
     }
     if (hipSetDevice(g->devices[0]) != hipSuccess) return gfail(MCPT_ERR_HIP, "mcpt_group_render: hipSetDevice");
     if (g->same_device) {  // rehearsal: every frame lives on this device
-        for (int i = 1; i < N; ++i) launch_add_frame(g->fb[0], g->fb[i], (uint32_t)n, g->streams[0]);
+        for (int i = 1; i < N; ++i) launch_add_frame(g->fb[0].p, g->fb[i].p, (uint32_t)n, g->streams[0]);
     }
-    hipError_t e = hipMemcpyAsync(fb_host, g->fb[0], n * sizeof(float), hipMemcpyDeviceToHost, g->streams[0]);
+    hipError_t e = hipMemcpyAsync(fb_host, g->fb[0].p, n * sizeof(float), hipMemcpyDeviceToHost, g->streams[0]);
     if (e == hipSuccess) e = hipStreamSynchronize(g->streams[0]);
     if (e != hipSuccess) return gfail(MCPT_ERR_HIP, std::string("mcpt_group_render: framebuffer download: ") + hipGetErrorString(e));
 
     if (stats) {
         std::memset(stats, 0, sizeof *stats);
-        for (int i = 0; i < N; ++i) {
-            const mcpt_stats &a = st[i];
-            stats->samples += a.samples; stats->paths += a.paths; stats->vertices += a.vertices; stats->shaded += a.shaded;
-            stats->closest_rays += a.closest_rays; stats->shadow_rays += a.shadow_rays; stats->ref_scene_rays += a.ref_scene_rays;
-            stats->iterations += a.iterations; stats->overflow_paths += a.overflow_paths; stats->direct_vertices += a.direct_vertices;
-            stats->ms_trace_closest += a.ms_trace_closest; stats->ms_trace_shadow += a.ms_trace_shadow; stats->ms_shade += a.ms_shade;
-            stats->ms_generate += a.ms_generate; stats->ms_resolve += a.ms_resolve; stats->ms_direct += a.ms_direct;
-            stats->n_trace_closest += a.n_trace_closest; stats->n_trace_shadow += a.n_trace_shadow; stats->n_shade += a.n_shade;
-            stats->n_generate += a.n_generate; stats->n_resolve += a.n_resolve; stats->n_direct += a.n_direct;
-        }
-        stats->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        for (int i = 0; i < N; ++i) add(*stats, st[i]);
+        stats->ms_total = ms_since(t0);
     }
     if (worst == MCPT_ERR_OVERFLOW) return gfail(worst, "some paths outran the clamp stack (raise params.max_depth)");
     return MCPT_OK;

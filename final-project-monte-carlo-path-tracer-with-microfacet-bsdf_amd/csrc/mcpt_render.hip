@@ -1,0 +1,502 @@
+// The frame-level entry points of the C ABI (include/mcpt.h): mcpt_render / mcpt_render_device, mcpt_render_adaptive, mcpt_render_aovs[_ex],
+// mcpt_denoise and mcpt_render_denoised.  What they share -- the checks of (camera, params), the start of a call, its statistics -- is
+// here once; each entry point is the part that differs.
+#include <cmath>
+#include <cstdio>
+
+#include "mcpt_host.h"
+#include "mcpt_adaptive.h"
+#include "mcpt_denoise.h"
+
+using namespace mcpt;
+
+void mcpt::add(mcpt_stats &a, const mcpt_stats &b) {
+    a.samples += b.samples; a.paths += b.paths; a.vertices += b.vertices; a.shaded += b.shaded;
+    a.closest_rays += b.closest_rays; a.shadow_rays += b.shadow_rays; a.ref_scene_rays += b.ref_scene_rays;
+    a.iterations += b.iterations; a.overflow_paths += b.overflow_paths; a.direct_vertices += b.direct_vertices;
+    a.ms_trace_closest += b.ms_trace_closest; a.ms_trace_shadow += b.ms_trace_shadow; a.ms_shade += b.ms_shade;
+    a.ms_generate += b.ms_generate; a.ms_resolve += b.ms_resolve; a.ms_direct += b.ms_direct;
+    a.n_trace_closest += b.n_trace_closest; a.n_trace_shadow += b.n_trace_shadow; a.n_shade += b.n_shade;
+    a.n_generate += b.n_generate; a.n_resolve += b.n_resolve; a.n_direct += b.n_direct;
+}
+
+namespace {
+
+constexpr uint32_t kAovChunkRays = 4u << 20;  // at most this many rays per chunk of the AOV pass
+constexpr int32_t kMaxAovSpp = 65536;
+
+// a frame whose AOV records (8 floats per pixel) can be indexed
+bool frame_ok(int W, int H) { return W > 0 && H > 0 && (uint64_t)W * H <= 0x7fffffffull / 8; }
+
+// What an entry point forbids on top of the common checks of (cam, params).
+enum : unsigned {
+    kOneCallFrame = 1u,  // no progressive accumulation: accumulate, spp_total and sample_offset must be 0
+    kOneRank = 2u,       // nranks must be 1
+    kDenoisedFrame = 4u  // spp >= 2 (a variance needs two samples) and a frame the AOV pass can hold (frame_ok)
+};
+
+// The checks of (cam, params) every frame-level call makes before it touches the scene, in the order the entry points have always made
+// them; `name` is the entry point's, for the message.
+int check_frame_call(const char *name, const mcpt_camera &cam, const mcpt_params &p, unsigned forbid) {
+    const auto bad = [&](const char *what) { return fail(MCPT_ERR_ARG, std::string(name) + ": " + what); };
+    const bool positive = cam.width > 0 && cam.height > 0 && p.n_dir_sample > 0 && p.rr_rate > 0.f;
+    if (forbid & kDenoisedFrame) {
+        if (!positive || !frame_ok(cam.width, cam.height)) return bad("width/height/n_dir_sample/rr_rate must be positive");
+        if (p.spp < 2) return bad("params.spp must be at least 2");
+    } else {
+        if (!positive || p.spp <= 0) return bad("width/height/spp/n_dir_sample/rr_rate must be positive");
+        if ((uint64_t)cam.width * cam.height > 0x7fffffffull) return bad("frame too large");
+    }
+    if ((forbid & kOneRank) && p.nranks != 1) return bad("nranks must be 1 (a partitioned frame is not denoised)");
+    if ((forbid & kOneCallFrame) && (p.accumulate != 0 || p.spp_total != 0 || p.sample_offset != 0))
+        return bad("accumulate, spp_total and sample_offset must be 0");
+    return MCPT_OK;
+}
+
+// mcpt_stats of a call that rendered `samples` camera samples, `traced_primary` of them through the wavefront loop (the rest: sky cull).
+void fill_stats(mcpt_stats *stats, uint64_t samples, uint64_t traced_primary, int32_t n_dir, const Totals &rt, Clock::time_point t0) {
+    std::memset(stats, 0, sizeof *stats);
+    // (culled pixels count like traced ones: the reference runs one camera ray and three castRay invocations, each with one
+    // Scene::intersect, for every sample of them too)
+    stats->samples = samples;
+    stats->paths = 3 * stats->samples;
+    stats->vertices = stats->paths + rt.pushes;
+    stats->shaded = rt.shaded;
+    stats->closest_rays = rt.closest;
+    stats->shadow_rays = rt.shadow;
+    stats->direct_vertices = rt.direct;
+    // Scene::intersect calls of the reference: one per castRay invocation (Scene.cpp:87), n_dir per shaded
+    // vertex (Scene.cpp:73), one look-ahead per vertex that survives roulette (Scene.cpp:134,161).
+    const uint64_t cont = rt.closest - traced_primary;  // closest-hit rays beyond the primary rays actually traced
+    stats->ref_scene_rays = stats->vertices + (uint64_t)n_dir * rt.shaded + cont;
+    stats->iterations = rt.iterations;
+    stats->overflow_paths = rt.overflow;
+    stats->ms_trace_closest = rt.ms[K_CLOSEST];
+    stats->ms_trace_shadow = rt.ms[K_SHADOW];
+    stats->ms_shade = rt.ms[K_SHADE];
+    stats->ms_generate = rt.ms[K_GENERATE];
+    stats->ms_resolve = rt.ms[K_RESOLVE];
+    stats->ms_direct = rt.ms[K_DIRECT];
+    stats->n_direct = rt.cnt[K_DIRECT];
+    stats->n_trace_closest = rt.cnt[K_CLOSEST];
+    stats->n_trace_shadow = rt.cnt[K_SHADOW];
+    stats->n_shade = rt.cnt[K_SHADE];
+    stats->n_generate = rt.cnt[K_GENERATE];
+    stats->n_resolve = rt.cnt[K_RESOLVE];
+    stats->ms_total = ms_since(t0);
+}
+
+// The start and the end every frame-level render call shares, once its arguments have passed the checks.
+struct FrameCall {
+    mcpt_scene *sc;
+    const mcpt_params &p;
+    Clock::time_point t0;
+    CameraConst cc;
+    PixelSet ps;
+    int begin(const mcpt_camera &cam) {
+        HIP_TRY(hipSetDevice(sc->device));
+        (void)hipGetLastError();  // an earlier, already reported failure of this thread must not be taken for one of this call
+        t0 = Clock::now();
+        cc = make_camera(cam);
+        return MCPT_OK;
+    }
+    // the owned pixels, the cleared frame and the sky cull, whose pixels get `spp` additions of background / spp_total
+    int pixels(int32_t spp, float spp_total, float *fb_dev, hipStream_t st) { return prepare_pixels(sc, cc, p, spp, spp_total, fb_dev, st, ps); }
+    int end(mcpt_stats *stats, uint64_t samples, uint64_t traced_primary, const Totals &rt) const {
+        if (stats) fill_stats(stats, samples, traced_primary, p.n_dir_sample, rt, t0);
+        if (rt.overflow) return fail(MCPT_ERR_OVERFLOW, "some paths outran the clamp stack (raise params.max_depth)");
+        return MCPT_OK;
+    }
+};
+
+int render_impl(mcpt_scene *sc, const mcpt_camera *cam, const mcpt_params *pp, float *fb_dev, hipStream_t st, mcpt_stats *stats) {
+    if (!sc || !cam || !pp || !fb_dev) return fail(MCPT_ERR_ARG, "mcpt_render: null argument");
+    const mcpt_params &p = *pp;
+    int rc = check_frame_call("mcpt_render", *cam, p, 0);
+    if (rc != MCPT_OK) return rc;
+    FrameCall f{sc, p};
+    if ((rc = f.begin(*cam)) != MCPT_OK) return rc;
+    const float spp_total = (float)(p.spp_total > 0 ? p.spp_total : p.spp);
+    if ((rc = f.pixels(p.spp, spp_total, fb_dev, st)) != MCPT_OK) return rc;
+    const PixelSet &ps = f.ps;
+    if (ps.n_owned == 0) {
+        HIP_TRY(hipStreamSynchronize(st));
+        if (stats) std::memset(stats, 0, sizeof *stats);
+        return MCPT_OK;
+    }
+    Totals rt;
+    rc = render_list(sc, f.cc, p, ps.list, ps.cand, ps.n_pix, p.sample_offset, p.spp, spp_total, fb_dev, nullptr, st, f.t0, rt);
+    if (rc != MCPT_OK) return rc;
+    return f.end(stats, (uint64_t)ps.n_owned * p.spp, (uint64_t)ps.n_pix * p.spp, rt);
+}
+
+// What the chunk loop of the AOV pass works in.
+struct AovPtrs {
+    uint32_t *key_pixel, *key_sample;
+    float4 *rec0, *rec1;  // the per-sample records
+    // ray list 0 holds the camera rays and their hits; the specular chains add ray list 1, the chain states and sums of both lists and the
+    // count of the next list (all nullptr without chains)
+    float4 *list_o[2], *list_d[2];
+    uint4 *list_hit[2];
+    float4 *chain_st[2];
+    double *chain_t[2];
+    uint32_t *n_next;
+    RetryList rl;
+};
+
+// ... inside the wavefront workspace (aov_pass says what goes where) ...
+AovPtrs aov_in_workspace(const Workspace &w, uint64_t cap, bool chain) {
+    uint32_t *keys = reinterpret_cast<uint32_t *>(w.wave[1].rec0.p);
+    AovPtrs a{keys, keys + cap, w.wave[1].ray_o.p, w.wave[1].ray_d.p, {w.wave[0].ray_o.p, nullptr}, {w.wave[0].ray_d.p, nullptr}, {w.wave[0].hit.p, nullptr},
+              {nullptr, nullptr}, {nullptr, nullptr}, nullptr, w.retry.list(0)};
+    if (chain) {
+        a.list_o[1] = w.vtx0.p;
+        a.list_d[1] = w.vtx1.p;
+        a.list_hit[1] = w.wave[1].hit.p;
+        a.chain_st[0] = w.wave[0].rec1.p;
+        a.chain_st[1] = w.wave[1].rec1.p;
+        a.chain_t[0] = reinterpret_cast<double *>(w.wave[0].rec0.p);
+        a.chain_t[1] = reinterpret_cast<double *>(w.vtx2.p);
+        a.n_next = w.vtx_j.p;
+    }
+    return a;
+}
+
+// ... or in buffers of the call's own, for chunks of `cap` rays.
+struct AovOwn {
+    DevBuf<uint32_t> keys, count;
+    DevBuf<float4> s0, s1, ray_o[2], ray_d[2], chain_st[2];
+    DevBuf<double> chain_t[2];
+    DevBuf<uint4> hit[2];
+    RetryBufs retry;
+    hipError_t alloc(uint64_t cap, bool chain, int height, AovPtrs &a) {
+        hipError_t e = keys.alloc(2 * cap);
+        const auto also = [&](auto &buf, size_t n) {
+            if (e == hipSuccess) e = buf.alloc(n);
+        };
+        also(ray_o[0], cap);
+        also(ray_d[0], cap);
+        also(hit[0], cap);
+        also(s0, cap);
+        also(s1, cap);
+        if (e == hipSuccess) e = retry.for_rays((uint32_t)cap, height);
+        if (chain) {
+            also(ray_o[1], cap);
+            also(ray_d[1], cap);
+            also(hit[1], cap);
+            also(count, 1);
+            for (int k = 0; k < 2; ++k) {
+                also(chain_st[k], cap);
+                also(chain_t[k], cap);
+            }
+        }
+        a = AovPtrs{keys.p, keys.p + cap, s0.p, s1.p, {ray_o[0].p, ray_o[1].p}, {ray_d[0].p, ray_d[1].p}, {hit[0].p, hit[1].p},
+                    {chain_st[0].p, chain_st[1].p}, {chain_t[0].p, chain_t[1].p}, count.p, retry.list(0)};
+        return e;
+    }
+};
+
+// The AOV pass (include/mcpt.h): aov_dev[8m ..] for every pixel of the frame, samples 0 .. aov_spp-1 of `seed`, queued on `st`.  Chunks of
+// whole pixels, pixel-major.  It runs inside the wavefront workspace of pool 0 when that holds at least one pixel's rays (after a render it
+// holds millions): camera rays and hits in wave 0's ray / hit arrays, the per-sample records in wave 1's, the keys in wave 1's path
+// records, the retrace list of the closest-hit rays.  Otherwise (no render yet on this scene) it uses buffers of its own for the call.
+// spec_depth > 0 (mcpt_render_aovs_ex): each chunk runs the specular chains instead of k_aov_resolve -- k_aov_chain on the traced list, then
+// up to spec_depth times k_trace_closest + k_aov_chain on the compacted list of the samples that continue (its length read back once per
+// bounce).  In the workspace the second ray list is vtx0 / vtx1 with wave 1's hits, the chain states wave 0's and wave 1's rec1 with the
+// sums in wave 0's rec0 and vtx2, the count vtx_j[0] (chunks then hold at most `pool` rays); otherwise the call allocates them for a chunk.
+int aov_pass(mcpt_scene *sc, const CameraConst &cc, uint32_t seed, int32_t aov_spp, int32_t spec_depth, float *aov_dev, hipStream_t st) {
+    const uint32_t n_px = (uint32_t)cc.width * (uint32_t)cc.height;
+    const uint64_t need = std::min<uint64_t>(kAovChunkRays, (uint64_t)n_px * aov_spp);
+    Workspace &w = sc->pools[0].ws;
+    const bool chain = spec_depth > 0;
+    // rays that fit: the ray arrays (ray_cap entries) and, for the keys, two uint32 per ray in wave 1's rec0 (4 per entry); the chains use
+    // arrays of `pool` entries too
+    const uint64_t ws_rays = w.pool ? std::min<uint64_t>(w.ray_cap, (chain ? 1ull : 2ull) * w.pool) : 0;
+    const bool in_ws = ws_rays >= (uint64_t)aov_spp && (!stack_uses_retry(sc->view.height) || w.retry.cap[0] >= std::min<uint64_t>(need, ws_rays));
+    const uint64_t cap = in_ws ? std::min<uint64_t>(need, ws_rays) : need;
+    AovOwn own;
+    AovPtrs a;
+    if (in_ws) a = aov_in_workspace(w, cap, chain);
+    else HIP_TRY(own.alloc(cap, chain, sc->view.height, a));
+    const uint32_t px_chunk = (uint32_t)std::max<uint64_t>(1, cap / (uint64_t)aov_spp);
+    for (uint32_t p0 = 0; p0 < n_px; p0 += px_chunk) {
+        const uint32_t np = std::min(px_chunk, n_px - p0), n = np * (uint32_t)aov_spp;
+        launch_aov_keys(p0, n, aov_spp, a.key_pixel, a.key_sample, st);
+        launch_camera_rays(cc, seed, n, a.key_pixel, a.key_sample, a.list_o[0], a.list_d[0], st);
+        launch_trace_closest(sc->view, n, nullptr, a.list_o[0], a.list_d[0], a.list_hit[0], a.rl, st);
+        if (!chain) {
+            launch_aov_resolve(sc->view, n, a.list_o[0], a.list_d[0], a.list_hit[0], a.rec0, a.rec1, st);
+        } else {
+            uint32_t m = n;  // rays in list `cur`, whose samples have all followed b bounces
+            for (int b = 0, cur = 0;; ++b, cur ^= 1) {
+                if (b < spec_depth) HIP_TRY(hipMemsetAsync(a.n_next, 0, sizeof(uint32_t), st));
+                launch_aov_chain(sc->view, m, b, spec_depth, a.list_o[cur], a.list_d[cur], a.list_hit[cur], b == 0 ? nullptr : a.chain_st[cur],
+                                 b == 0 ? nullptr : a.chain_t[cur], a.rec0, a.rec1, a.list_o[cur ^ 1], a.list_d[cur ^ 1], a.chain_st[cur ^ 1],
+                                 a.chain_t[cur ^ 1], a.n_next, st);
+                if (b == spec_depth) break;
+                HIP_TRY(hipMemcpyAsync(&m, a.n_next, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+                HIP_TRY(hipStreamSynchronize(st));
+                if (m == 0) break;
+                launch_trace_closest(sc->view, m, nullptr, a.list_o[cur ^ 1], a.list_d[cur ^ 1], a.list_hit[cur ^ 1], a.rl, st);
+            }
+        }
+        launch_aov_fold(p0, np, aov_spp, a.rec0, a.rec1, aov_dev, st);
+    }
+    HIP_TRY(hipGetLastError());
+    if (!in_ws) HIP_TRY(hipStreamSynchronize(st));  // (the call's own buffers are freed on return)
+    return MCPT_OK;
+}
+
+// Working buffers of the filter for one call: two record buffers and the depth gradient, 72 bytes per pixel.
+struct DenoiseBufs {
+    DevBuf<dn::Rec> rec[2];
+    DevBuf<float2> grad;
+    hipError_t alloc(size_t n_px) {
+        hipError_t e = rec[0].alloc(n_px);
+        if (e == hipSuccess) e = rec[1].alloc(n_px);
+        if (e == hipSuccess) e = grad.alloc(n_px);
+        return e;
+    }
+};
+
+// mcpt_render_aovs and mcpt_render_aovs_ex (`name` for the messages)
+int render_aovs(const char *name, mcpt_scene *sc, const mcpt_camera *cam, uint32_t seed, int32_t aov_spp, int32_t spec_depth, float *aov_host) {
+    const auto bad = [&](const char *what) { return fail(MCPT_ERR_ARG, std::string(name) + ": " + what); };
+    if (!sc || !cam || !aov_host) return bad("null argument");
+    if (!frame_ok(cam->width, cam->height)) return bad("width and height must be positive (and the frame not too large)");
+    if (aov_spp < 0 || aov_spp > kMaxAovSpp) return bad("aov_spp must be 0..65536");
+    if (spec_depth < 0 || spec_depth > dn::kMaxSpecularDepth) return bad("specular_depth must be 0..8");
+    const int32_t n_spp = aov_spp == 0 ? 4 : aov_spp;
+    HIP_TRY(hipSetDevice(sc->device));
+    (void)hipGetLastError();
+    const size_t n_px = (size_t)cam->width * cam->height;
+    DevBuf<float> aov;
+    HIP_TRY(aov.alloc(n_px * 8));
+    const int rc = aov_pass(sc, make_camera(*cam), seed, n_spp, spec_depth, aov.p, nullptr);
+    if (rc != MCPT_OK) return drained(rc);
+    HIP_TRY(download(aov_host, aov, n_px * 8));
+    return MCPT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mcpt_render_device(mcpt_scene *sc, const mcpt_camera *cam, const mcpt_params *p, float *fb_device, void *hip_stream,
+                       mcpt_stats *stats) {
+    return render_impl(sc, cam, p, fb_device, (hipStream_t)hip_stream, stats);
+}
+
+int mcpt_render(mcpt_scene *sc, const mcpt_camera *cam, const mcpt_params *p, float *fb_host, mcpt_stats *stats) {
+    if (!sc || !cam || !p || !fb_host) return fail(MCPT_ERR_ARG, "mcpt_render: null argument");
+    HIP_TRY(hipSetDevice(sc->device));
+    const size_t n = (size_t)cam->width * cam->height * 3;
+    DevBuf<float> fb;
+    HIP_TRY(fb.alloc(n));
+    if (p->accumulate) HIP_TRY(upload(fb, fb_host, n));
+    const int rc = render_impl(sc, cam, p, fb.p, nullptr, stats);
+    if (rc == MCPT_OK || rc == MCPT_ERR_OVERFLOW) {
+        const hipError_t e = download(fb_host, fb, n);
+        if (e != hipSuccess) return fail(MCPT_ERR_HIP, std::string("framebuffer download: ") + hipGetErrorString(e));
+    }
+    return rc;
+}
+
+int mcpt_render_adaptive(mcpt_scene *sc, const mcpt_camera *cam, const mcpt_params *pp, const mcpt_adaptive *opts, float *fb_host, int32_t *spp_host,
+                         float *err_host, mcpt_adaptive_info *info, mcpt_stats *stats) {
+    const auto bad = [](const char *what) { return fail(MCPT_ERR_ARG, std::string("mcpt_render_adaptive: ") + what); };
+    if (!sc || !cam || !pp || !opts || !fb_host) return bad("null argument");
+    const mcpt_params &p = *pp;
+    const mcpt_adaptive &o = *opts;
+    int rc = check_frame_call("mcpt_render_adaptive", *cam, p, kOneCallFrame);
+    if (rc != MCPT_OK) return rc;
+    if (o.min_spp < 2) return bad("min_spp must be at least 2");
+    int R = 0;
+    while (R <= 15 && ((int64_t)o.min_spp << R) < p.spp) ++R;
+    if (R > 15 || ((int64_t)o.min_spp << R) != p.spp) return bad("params.spp must be min_spp * 2^R, 0 <= R <= 15");
+    if (!(o.threshold >= 0.f) || !std::isfinite(o.threshold)) return bad("threshold must be finite and >= 0");
+    if (!(o.rel_floor > 0.f)) return bad("rel_floor must be > 0");
+    if (o.dilate != 0 && o.dilate != 1) return bad("dilate must be 0 or 1");
+    FrameCall f{sc, p};
+    if ((rc = f.begin(*cam)) != MCPT_OK) return rc;
+    const hipStream_t st = nullptr;
+    const int W = cam->width, H = cam->height;
+    const size_t n_px = (size_t)W * H;
+    const int32_t S0 = o.min_spp;
+    const double rel_floor = (double)o.rel_floor, threshold = (double)o.threshold;
+    DevBuf<float> fb, err;
+    DevBuf<double> mom;
+    DevBuf<int32_t> sppm;
+    DevBuf<uint8_t> stamp;
+    HIP_TRY(fb.alloc(n_px * 3));
+    HIP_TRY(err.alloc(n_px));
+    HIP_TRY(mom.alloc(n_px * 6));
+    HIP_TRY(sppm.alloc(n_px));
+    HIP_TRY(stamp.alloc(n_px));
+    HIP_TRY(hipMemsetAsync(err.p, 0, n_px * sizeof(float), st));
+    HIP_TRY(hipMemsetAsync(mom.p, 0, n_px * 6 * sizeof(double), st));
+    HIP_TRY(hipMemsetAsync(sppm.p, 0, n_px * sizeof(int32_t), st));
+    HIP_TRY(hipMemsetAsync(stamp.p, 0, n_px, st));
+    if ((rc = f.pixels(S0, (float)S0, fb.p, st)) != MCPT_OK) return rc;  // round 0 of the culled pixels: S0 additions of background / S0
+    const PixelSet &ps = f.ps;
+    mcpt_adaptive_info inf;
+    std::memset(&inf, 0, sizeof inf);
+    Totals all;
+    uint64_t samples = 0, traced_primary = 0;
+    if (ps.n_owned > 0) {
+        // the culled pixels are final at S0: their estimate from the constant samples, no mark (they take no part in dilation)
+        const uint32_t n_sky = ps.n_owned - ps.n_pix;
+        if (n_sky > 0) {
+            launch_sky_moments(ps.sky, n_sky, sc->view.background, S0, mom.p, st);
+            launch_adapt_eval(ps.sky, n_sky, mom.p, S0, rel_floor, threshold, 0u, err.p, nullptr, sppm.p, st);
+        }
+        // the active pixels of the current and of the next round (with their candidate entries when the cull produced them)
+        DevBuf<uint32_t> list[2];
+        DevBuf<int4> cand[2];
+        DevBuf<uint8_t> flags, temp;
+        DevBuf<uint32_t> count;
+        uint32_t n_act = ps.n_pix;
+        const size_t tb = adapt_temp_bytes(std::max<uint32_t>(n_act, 1u));
+        for (int k = 0; k < 2; ++k) {
+            HIP_TRY(list[k].alloc(std::max<uint32_t>(n_act, 1u)));
+            if (ps.cand) HIP_TRY(cand[k].alloc(std::max<uint32_t>(n_act, 1u)));
+        }
+        HIP_TRY(flags.alloc(std::max<uint32_t>(n_act, 1u)));
+        HIP_TRY(temp.alloc(tb));
+        HIP_TRY(count.alloc(1));
+        if (n_act > 0) {
+            HIP_TRY(hipMemcpyAsync(list[0].p, ps.list, n_act * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+            if (ps.cand) HIP_TRY(hipMemcpyAsync(cand[0].p, ps.cand, n_act * sizeof(int4), hipMemcpyDeviceToDevice, st));
+        }
+        samples = (uint64_t)ps.n_owned * S0;
+        int cur = 0;
+        for (int r = 0;; ++r) {
+            const auto tr = r == 0 ? f.t0 : Clock::now();
+            const int32_t n = S0 << r;                   // samples per active pixel after this round
+            const int32_t first = r == 0 ? 0 : n / 2;    // this round renders samples [first, n), divisor n
+            const bool can_double = 2 * (int64_t)n <= p.spp;
+            uint32_t n_next = 0;
+            if (n_act > 0) {
+                rc = render_list(sc, f.cc, p, list[cur].p, ps.cand ? cand[cur].p : nullptr, n_act, first, n - first, (float)n, fb.p, mom.p, st, tr, all);
+                if (rc != MCPT_OK) return rc;
+                traced_primary += (uint64_t)n_act * (n - first);
+                if (r > 0) samples += (uint64_t)n_act * (n - first);
+                const uint32_t round_stamp = (uint32_t)r + 1u;
+                launch_adapt_eval(list[cur].p, n_act, mom.p, n, rel_floor, threshold, round_stamp, err.p, stamp.p, sppm.p, st);
+                launch_adapt_select(list[cur].p, n_act, W, H, stamp.p, round_stamp, o.dilate, can_double ? 1 : 0, n, fb.p, sppm.p, flags.p, st);
+                if (can_double)
+                    HIP_TRY(adapt_compact(list[cur].p, ps.cand ? cand[cur].p : nullptr, flags.p, n_act, list[cur ^ 1].p, ps.cand ? cand[cur ^ 1].p : nullptr,
+                                          temp.p, tb, count.p, &n_next, st));
+                else
+                    HIP_TRY(hipStreamSynchronize(st));
+            }
+            inf.active_pixels[r] = r == 0 ? ps.n_owned : n_act;
+            inf.ms_round[r] = ms_since(tr);
+            inf.rounds = r + 1;
+            if (n_next == 0) break;
+            n_act = n_next;
+            cur ^= 1;
+        }
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(download(fb_host, fb, n_px * 3));
+    if (spp_host) HIP_TRY(download(spp_host, sppm, n_px));
+    if (err_host) HIP_TRY(download(err_host, err, n_px));
+    if (info) *info = inf;
+    return f.end(stats, samples, traced_primary, all);
+}
+
+int mcpt_render_aovs(mcpt_scene *sc, const mcpt_camera *cam, uint32_t seed, int32_t aov_spp, float *aov_host) {
+    return render_aovs("mcpt_render_aovs", sc, cam, seed, aov_spp, 0, aov_host);
+}
+
+int mcpt_render_aovs_ex(mcpt_scene *sc, const mcpt_camera *cam, uint32_t seed, int32_t aov_spp, int32_t specular_depth, float *aov_host) {
+    return render_aovs("mcpt_render_aovs_ex", sc, cam, seed, aov_spp, specular_depth, aov_host);
+}
+
+int mcpt_denoise(mcpt_scene *sc, int32_t width, int32_t height, const float *color_host, const float *variance_host, const float *aov_host,
+                 const mcpt_denoise_opts *opts, float *out_host) {
+    if (!sc || !color_host || !variance_host || !aov_host || !opts || !out_host) return fail(MCPT_ERR_ARG, "mcpt_denoise: null argument");
+    if (!frame_ok(width, height)) return fail(MCPT_ERR_ARG, "mcpt_denoise: width and height must be positive (and the frame not too large)");
+    dn::Opts o;
+    if (dn::resolve_opts(*opts, o) != 0) return fail(MCPT_ERR_ARG, "mcpt_denoise: option out of range");
+    HIP_TRY(hipSetDevice(sc->device));
+    (void)hipGetLastError();
+    const size_t n_px = (size_t)width * height;
+    DevBuf<float> col, var, aov, out;
+    HIP_TRY(col.alloc(n_px * 3));
+    HIP_TRY(var.alloc(n_px));
+    HIP_TRY(aov.alloc(n_px * 8));
+    HIP_TRY(out.alloc(n_px * 3));
+    HIP_TRY(upload(col, color_host, n_px * 3));
+    HIP_TRY(upload(var, variance_host, n_px));
+    HIP_TRY(upload(aov, aov_host, n_px * 8));
+    DenoiseBufs db;
+    HIP_TRY(db.alloc(n_px));
+    launch_denoise(width, height, o, col.p, var.p, aov.p, db.rec[0].p, db.rec[1].p, db.grad.p, out.p, nullptr);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(download(out_host, out, n_px * 3));
+    return MCPT_OK;
+}
+
+int mcpt_render_denoised(mcpt_scene *sc, const mcpt_camera *cam, const mcpt_params *pp, const mcpt_denoise_opts *opts, float *fb_host,
+                         float *denoised_host, float *variance_host, float *aov_host, mcpt_denoise_info *info, mcpt_stats *stats) {
+    if (!sc || !cam || !pp || !opts || !fb_host || !denoised_host) return fail(MCPT_ERR_ARG, "mcpt_render_denoised: null argument");
+    const mcpt_params &p = *pp;
+    int rc = check_frame_call("mcpt_render_denoised", *cam, p, kDenoisedFrame | kOneRank | kOneCallFrame);
+    if (rc != MCPT_OK) return rc;
+    dn::Opts o;
+    if (dn::resolve_opts(*opts, o) != 0) return fail(MCPT_ERR_ARG, "mcpt_render_denoised: option out of range");
+    if (opts->aov_spp > p.spp || opts->aov_spp > kMaxAovSpp) return fail(MCPT_ERR_ARG, "mcpt_render_denoised: aov_spp must be at most params.spp and 65536");
+    const int32_t aov_spp = opts->aov_spp == 0 ? std::min(4, p.spp) : opts->aov_spp;
+    FrameCall f{sc, p};
+    if ((rc = f.begin(*cam)) != MCPT_OK) return rc;
+    const hipStream_t st = nullptr;
+    const int W = cam->width, H = cam->height;
+    const size_t n_px = (size_t)W * H;
+    DevBuf<float> fb, var, aov, out;
+    DevBuf<double> mom;
+    HIP_TRY(fb.alloc(n_px * 3));
+    HIP_TRY(var.alloc(n_px));
+    HIP_TRY(aov.alloc(n_px * 8));
+    HIP_TRY(out.alloc(n_px * 3));
+    HIP_TRY(mom.alloc(n_px * 6));
+    DenoiseBufs db;
+    HIP_TRY(db.alloc(n_px));
+    Event ev[4];  // around the three stages: render, AOV pass, filter
+    for (int k = 0; k < 4; ++k) HIP_TRY(ev[k].create(true));
+    HIP_TRY(hipEventRecord(ev[0], st));
+    HIP_TRY(hipMemsetAsync(mom.p, 0, n_px * 6 * sizeof(double), st));
+    if ((rc = f.pixels(p.spp, (float)p.spp, fb.p, st)) != MCPT_OK) return rc;
+    const PixelSet &ps = f.ps;
+    Totals rt;
+    if (ps.n_owned > ps.n_pix) launch_sky_moments(ps.sky, ps.n_owned - ps.n_pix, sc->view.background, p.spp, mom.p, st);
+    if (ps.n_pix > 0) {
+        rc = render_list(sc, f.cc, p, ps.list, ps.cand, ps.n_pix, 0, p.spp, (float)p.spp, fb.p, mom.p, st, f.t0, rt);
+        if (rc != MCPT_OK) return rc;
+    }
+    launch_dn_variance((uint32_t)n_px, mom.p, p.spp, var.p, st);
+    HIP_TRY(hipEventRecord(ev[1], st));
+    rc = aov_pass(sc, f.cc, p.seed, aov_spp, opts->specular_depth, aov.p, st);
+    if (rc != MCPT_OK) return drained(rc);
+    HIP_TRY(hipEventRecord(ev[2], st));
+    launch_denoise(W, H, o, fb.p, var.p, aov.p, db.rec[0].p, db.rec[1].p, db.grad.p, out.p, st);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(ev[3], st));
+    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(download(fb_host, fb, n_px * 3));
+    HIP_TRY(download(denoised_host, out, n_px * 3));
+    if (variance_host) HIP_TRY(download(variance_host, var, n_px));
+    if (aov_host) HIP_TRY(download(aov_host, aov, n_px * 8));
+    if (info) {
+        float ms[3] = {0.f, 0.f, 0.f};
+        for (int k = 0; k < 3; ++k) HIP_TRY(hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]));
+        info->ms_render = ms[0];
+        info->ms_aov = ms[1];
+        info->ms_denoise = ms[2];
+        info->ms_total = ms_since(f.t0);
+    }
+    return f.end(stats, (uint64_t)ps.n_owned * p.spp, (uint64_t)ps.n_pix * p.spp, rt);
+}
+
+}  // extern "C"

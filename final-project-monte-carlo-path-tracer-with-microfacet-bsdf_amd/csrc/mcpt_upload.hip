@@ -1,0 +1,381 @@
+// Scene create / upload / destroy / info and the BVH dumps of the C ABI (include/mcpt.h); mcpt_last_error and mcpt_version.
+#include <cstdio>
+#include <cstdlib>
+#include <memory>
+#include <thread>
+
+#include "mcpt_host.h"
+#include "mcpt_lbvh.h"
+
+using namespace mcpt;
+
+thread_local std::string mcpt::g_err;
+
+void Knobs::read() {
+    auto off = [](const char *n) { const char *v = std::getenv(n); return v && v[0] == '0'; };
+    overlap = !off("MCPT_OVERLAP");
+    queue_ahead = !off("MCPT_QUEUE_AHEAD");
+    timing = !off("MCPT_TIMING");
+    verbose = std::getenv("MCPT_RENDER_VERBOSE") != nullptr;
+    sky_cull = !off("MCPT_SKY_CULL");
+    small_scene = !off("MCPT_SMALL_SCENE");
+    const char *v;
+    if ((v = std::getenv("MCPT_POOLS"))) pools = (v[0] == '2') ? 2 : 1;
+    if ((v = std::getenv("MCPT_DRAIN_BATCH"))) drain_batch = std::max(1, std::atoi(v));
+    if ((v = std::getenv("MCPT_POOL_MIN_WORK"))) pool_min_work = (uint64_t)std::max(1, std::atoi(v));
+    if ((v = std::getenv("MCPT_SHADOW_GRID_PER_CU"))) shadow_grid_per_cu = (uint32_t)std::max(1, std::atoi(v));
+    if ((v = std::getenv("MCPT_DIRECT_GRID_PER_CU"))) direct_grid_per_cu = (uint32_t)std::max(0, std::atoi(v));
+#ifdef MCPT_TEST_HOOKS
+    if ((v = std::getenv("MCPT_RING_START"))) ring_start = (uint32_t)std::strtoul(v, nullptr, 0);
+    if ((v = std::getenv("MCPT_HOST_DELAY_US"))) host_delay_us = std::atoi(v);
+    if ((v = std::getenv("MCPT_FAKE_FREE_MB"))) fake_free_mb = (uint64_t)std::max(1, std::atoi(v));
+#endif
+}
+
+// First use of a device by this process: context creation and the load of this library's code objects cost 100-150 ms (round 2's
+// `upload_ms` of 129-155 ms for a 6.8 KB scene was exactly this, not the copies).  It does not depend on the scene, so it runs on a
+// helper thread while the calling thread flattens the scene and builds its tree, and it is reported on its own (mcpt_scene_info).
+double mcpt::warm_up_device(int device) {
+    const auto t0 = Clock::now();
+    if (hipSetDevice(device) != hipSuccess) return 0.0;
+    uint32_t *p = nullptr;
+    if (hipMalloc((void **)&p, 256) == hipSuccess) {
+        launch_add_frame(reinterpret_cast<float *>(p), reinterpret_cast<float *>(p), 0u, nullptr);  // (n = 0: no launch; keeps the symbol referenced)
+        (void)hipMemset(p, 0, 256);
+        launch_mask_unowned(reinterpret_cast<float *>(p), 1, 1, 1, 0, 1, nullptr);  // one tiny kernel of this library: forces its code objects in
+        (void)hipDeviceSynchronize();
+        (void)hipFree(p);
+    }
+    (void)hipGetLastError();
+    return ms_since(t0);
+}
+
+int mcpt::build_scene_host(const mcpt_scene_desc *desc, const mcpt_build_options *options, HostBuild &hb) {
+    if (!desc) return fail(MCPT_ERR_ARG, "mcpt_scene_create: null argument");
+    const char *err = "";
+    const auto t_build = Clock::now();
+    hb.choice = resolve_build_choice(options);
+    // (a single primitive has no inner node: nothing for the device builder to do)
+    if ((hb.choice.builder == MCPT_BUILD_GPU_LBVH || hb.choice.builder == MCPT_BUILD_GPU_PLOC) && desc->objects) {
+        int64_t n_prim = desc->n_triangles;
+        for (int i = 0; i < desc->n_objects; ++i) n_prim += desc->objects[i].kind == MCPT_OBJ_SPHERE ? 1 : 0;
+        if (n_prim < 2) hb.choice.builder = MCPT_BUILD_SAH;
+    }
+    const int rc = build_host_scene(*desc, hb.hs, &err, hb.choice);
+    if (rc != MCPT_OK) return fail(rc, std::string("mcpt_scene_create: ") + err);
+    hb.build_ms = ms_since(t_build);
+    return MCPT_OK;
+}
+
+// The device half of mcpt_scene_create: copies a flattened scene to `device` (and, for MCPT_BUILD_GPU_LBVH, builds the tree there).
+// mcpt_group_create builds the host scene ONCE and calls this from one thread per device.
+int mcpt::upload_scene(const mcpt_scene_desc *desc, HostBuild &hb, int device, mcpt_scene **out) {
+    HostScene &hs = hb.hs;
+    const BuildChoice &choice = hb.choice;
+    HIP_TRY(hipSetDevice(device));
+    const auto t_upload = Clock::now();
+
+    // (an error exit below destroys what exists so far, with this device current)
+    std::unique_ptr<mcpt_scene, decltype(&mcpt_scene_destroy)> sc(new (std::nothrow) mcpt_scene(), mcpt_scene_destroy);
+    if (!sc) return fail(MCPT_ERR_OOM, "mcpt_scene_create: host allocation failed");
+    sc->device = device;
+    hipError_t e = hipSuccess;
+    sc->knobs.read();
+    // One pool by default: two pools measured +1..2 % at equal total size (2772 vs 2748 Msamples/s), within noise.
+    sc->n_pools = sc->knobs.pools;
+    for (int q = 0; q < sc->n_pools && e == hipSuccess; ++q) {
+        PoolCtx &c = sc->pools[q];
+        if (q > 0) e = c.main.create();
+        if (sc->knobs.overlap) {
+            for (int k = 0; k < 2 && e == hipSuccess; ++k) {
+                e = c.side[k].create();
+                if (e == hipSuccess) e = c.join[k].create();
+            }
+            if (e == hipSuccess) e = c.book.create();
+            if (e == hipSuccess) e = c.shaded.create();
+        }
+    }
+    for (int q = 0; q < sc->n_pools && e == hipSuccess; ++q) e = sc->pools[q].readback.create();
+    if (e == hipSuccess) e = sc->fork.create();
+    auto up = [&](auto &buf, const auto &vec) {
+        if (e == hipSuccess) e = upload(buf, vec);
+    };
+    if (hs.builder < 2) {
+        up(sc->nodes, hs.nodes);
+        if (!hs.qnodes.empty()) up(sc->qnodes, hs.qnodes);
+    }
+    up(sc->tri_geom, hs.tri_geom);
+    up(sc->tri_shade, hs.tri_shade);
+    up(sc->spheres, hs.spheres);
+    up(sc->mats, hs.materials);
+    up(sc->lights, hs.lights);
+    up(sc->light_nodes, hs.light_nodes);
+    up(sc->light_tris, hs.light_tris);
+    up(sc->env, hs.env);
+    if (!hs.instances.empty()) up(sc->inst, hs.instances);
+    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? MCPT_ERR_OOM : MCPT_ERR_HIP, std::string("scene upload: ") + hipGetErrorString(e));
+    double gpu_build_ms = 0.0;
+    if (hs.builder >= 2) {  // the traversal tree is built on the device from the caller's triangles (csrc/mcpt_lbvh.hip)
+        const auto tb = Clock::now();
+        const int n_sph = (int)hs.sphere_objects.size();
+        const int n_prim = hs.n_triangles + n_sph;
+        DevBuf<mcpt_triangle> d_tris;
+        DevBuf<int32_t> d_sph;
+        e = upload(d_tris, desc->triangles, (size_t)hs.n_triangles);
+        if (e == hipSuccess) e = upload(d_sph, hs.sphere_objects);
+        if (e == hipSuccess) e = sc->nodes.alloc((size_t)n_prim - 1);
+        if (e == hipSuccess) e = sc->qnodes.alloc((size_t)n_prim - 1);
+        LbvhResult R;
+        if (e == hipSuccess) e = build_lbvh_device(d_tris.p, hs.n_triangles, d_sph.p, sc->spheres.p, n_sph, choice.quantise, hs.builder == 3 ? 1 : 0, choice.ploc_radius, choice.ploc_top,
+                                                 sc->nodes.p, sc->qnodes.p, &R, nullptr);
+        if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? MCPT_ERR_OOM : MCPT_ERR_HIP, std::string("GPU BVH build: ") + hipGetErrorString(e));
+        if (R.height > kMaxBvhHeight) return fail(MCPT_ERR_LIMIT, "the GPU-built BVH is deeper than the traversal stack (kMaxBvhHeight); use MCPT_BUILD_SAH");
+        hs.root = R.root;
+        hs.height = R.height;
+        for (int k = 0; k < 3; ++k) {
+            hs.root_min[k] = R.root_min[k];
+            hs.root_max[k] = R.root_max[k];
+            hs.q_origin[k] = R.q_origin[k];
+            hs.q_cell[k] = R.q_cell[k];
+        }
+        if (!R.quantised) sc->qnodes.release();
+        sc->n_inner = R.n_nodes;
+        gpu_build_ms = ms_since(tb);
+    } else {
+        sc->n_inner = hs.root < 0 ? 0 : (int32_t)hs.nodes.size();
+    }
+    if (traversal_stack_entries(hs.height) < hs.height - 1)  // whatever built the tree: a push beyond the stack (one entry per inner ancestor) would be dropped
+        return fail(MCPT_ERR_LIMIT, "the BVH is deeper than the traversal stack (kMaxBvhHeight)");
+    DevScene &v = sc->view;
+    v.nodes = sc->nodes.p;
+    v.light_area_sum = hs.light_area_sum;
+    v.qnodes = sc->qnodes.p;  // nullptr: the float nodes are traversed
+    v.pnodes = nullptr;       // (set by the SMALL kernels to their LDS copy)
+    for (int k = 0; k < 3; ++k) {
+        v.q_origin[k] = hs.q_origin[k];
+        v.q_cell[k] = hs.q_cell[k];
+    }
+    v.tri_geom = sc->tri_geom.p;
+    v.tri_shade = sc->tri_shade.p;
+    v.spheres = sc->spheres.p;
+    v.mats = sc->mats.p;
+    v.lights = sc->lights.p;
+    v.light_nodes = sc->light_nodes.p;
+    v.light_tris = sc->light_tris.p;
+    v.inst = hs.instances.empty() ? nullptr : sc->inst.p;
+    v.n_leaf_prims = hs.n_leaf_prims;
+    v.env = sc->env.p;
+    for (int k = 0; k < 3; ++k) {
+        v.root_min[k] = hs.root_min[k];
+        v.root_max[k] = hs.root_max[k];
+        v.background[k] = hs.background[k];
+    }
+    v.root = hs.root;
+    v.n_tri = hs.n_triangles;
+    v.n_lights = (int32_t)hs.lights.size();
+    v.env_w = hs.env_w;
+    v.env_h = hs.env_h;
+    v.height = hs.height;
+    for (int k = 0; k < 3; ++k) v.light_center[k] = hs.light_center[k];
+    v.light_radius = hs.light_radius;
+    v.n_inner = sc->n_inner;
+    v.n_sphere_slots = (int32_t)hs.spheres.size();
+    v.n_mats = (int32_t)hs.materials.size();
+    v.n_light_nodes = (int32_t)hs.light_nodes.size();
+    v.n_light_tris = (int32_t)hs.light_tris.size();
+    // the LDS-resident flavour (SMALL kernels): everything the traversal and light sampling read fits the kSmall* limits
+    v.small = 0;
+#if !defined(MCPT_FORCE_RETRY) && !defined(MCPT_LDS_ONLY_STACKS)
+    if (sc->knobs.small_scene && !v.inst && v.root >= 0 && v.n_inner <= kSmallNodes && v.n_tri <= kSmallTris && v.n_sphere_slots <= kSmallSphereSlots &&
+        v.n_mats <= kSmallMats && v.n_lights <= kSmallLights && v.n_light_nodes <= kSmallLightNodes && v.n_light_tris <= kSmallLightTris &&
+        v.height - 1 <= kSmallStk)
+        v.small = 1;
+#endif
+    v.dbg = nullptr;
+#if defined(MCPT_TRAVERSAL_STATS) || defined(MCPT_CHECK_DIRECT_SKIP)
+    if (sc->dbg.alloc(32) == hipSuccess) {  // (16 reported by mcpt_debug_counters; the statistics build prints the rest at destruction)
+        (void)hipMemset(sc->dbg.p, 0, 32 * sizeof(unsigned long long));
+        v.dbg = sc->dbg.p;
+    }
+#endif
+    sc->info.build_ms = hb.build_ms + gpu_build_ms;
+    sc->info.init_ms = hb.init_ms;
+    sc->info.upload_ms = ms_since(t_upload) - gpu_build_ms;
+    sc->info.builder = hs.builder;
+    sc->info.quantised = sc->qnodes.p ? 1 : 0;
+    sc->info.n_instances = (int32_t)hs.instances.size();
+    sc->info.lds_resident = v.small;
+    sc->info.n_nodes = sc->n_inner;
+    sc->info.bvh_height = hs.height;
+    sc->info.n_lights = v.n_lights;
+    sc->info.n_prims = hs.n_triangles + hs.n_objects;
+    sc->info.scene_bytes = sc->nodes.bytes() + sc->qnodes.bytes() + sc->tri_geom.bytes() + sc->tri_shade.bytes() + sc->spheres.bytes() +
+                           sc->mats.bytes() + sc->lights.bytes() + sc->light_nodes.bytes() + sc->light_tris.bytes() + sc->inst.bytes() +
+                           sc->env.bytes();
+    *out = sc.release();
+    return MCPT_OK;
+}
+
+// The layout of mcpt_bvh_dump / mcpt_scene_dump_bvh: per node 12 floats {lmin, lmax, rmin, rmax}, two child references and (qn != nullptr) the
+// twelve 16-bit grid coordinates of its quantised boxes.
+static void export_nodes(int32_t n, const Node *nodes, const QNode *qn, float *boxes, int32_t *children, uint16_t *qboxes) {
+    for (int32_t i = 0; i < n; ++i) {
+        const Node &N = nodes[i];
+        float *b = boxes + (size_t)i * 12;
+        for (int k = 0; k < 3; ++k) {
+            b[k] = N.lmin[k];
+            b[3 + k] = N.lmax[k];
+            b[6 + k] = N.rmin[k];
+            b[9 + k] = N.rmax[k];
+        }
+        children[2 * i] = N.left;
+        children[2 * i + 1] = N.right;
+        if (!qn) continue;
+        uint16_t *q = qboxes + (size_t)i * 12;
+        for (int w = 0; w < 6; ++w) {
+            q[2 * w] = (uint16_t)(qn[i].w[w] & 0xffffu);
+            q[2 * w + 1] = (uint16_t)(qn[i].w[w] >> 16);
+        }
+    }
+}
+
+extern "C" {
+
+const char *mcpt_last_error(void) { return g_err.c_str(); }
+const char *mcpt_version(void) {
+#if defined(MCPT_TEST_HOOKS) || defined(MCPT_CHECK_DIRECT_SKIP) || defined(MCPT_TRAVERSAL_STATS)
+    return "mcpt-hip 0.2 (gfx950) checking build";
+#else
+    return "mcpt-hip 0.2 (gfx950)";
+#endif
+}
+
+int mcpt_scene_create(const mcpt_scene_desc *desc, int device, mcpt_scene **out) { return mcpt_scene_create_ex(desc, device, nullptr, out); }
+
+int mcpt_scene_create_ex(const mcpt_scene_desc *desc, int device, const mcpt_build_options *options, mcpt_scene **out) {
+    if (!desc || !out) return fail(MCPT_ERR_ARG, "mcpt_scene_create: null argument");
+    *out = nullptr;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+        return fail(MCPT_ERR_HIP, "mcpt_scene_create: no HIP device available (this library has no CPU fallback)");
+    if (device < 0) {
+        if (hipGetDevice(&device) != hipSuccess) device = 0;
+    }
+    if (device >= ndev) return fail(MCPT_ERR_ARG, "mcpt_scene_create: device index out of range");
+    double init_ms = 0.0;
+    std::thread warm([&]() { init_ms = warm_up_device(device); });  // beside the host build
+    HostBuild hb;
+    const int rc = build_scene_host(desc, options, hb);
+    warm.join();
+    if (rc != MCPT_OK) return rc;
+    hb.init_ms = init_ms;
+    return upload_scene(desc, hb, device, out);
+}
+
+void mcpt_scene_destroy(mcpt_scene *sc) {
+    if (!sc) return;
+    (void)hipSetDevice(sc->device);
+#if defined(MCPT_TRAVERSAL_STATS) || defined(MCPT_CHECK_DIRECT_SKIP)
+    if (sc->dbg.p) {
+        unsigned long long h[32];
+        if (hipMemcpy(h, sc->dbg.p, sizeof h, hipMemcpyDeviceToHost) == hipSuccess) {
+            if (h[23])
+                std::fprintf(stderr, "[mcpt k_shade stats] %llu waves: %.0f cycles from start to the end of the allocation, of which %.0f in its first half (ballots, first barrier) and %.0f in the second barrier\n",
+                             h[23], (double)h[22] / h[23], (double)h[20] / h[23], (double)h[21] / h[23]);
+            if (h[24] + h[25] + h[26] + h[27] + h[28])
+                std::fprintf(stderr, "[mcpt k_shade stats] waves by the number of material types among their shading lanes: 0: %llu, 1: %llu, 2: %llu, 3: %llu, 4: %llu; shading lanes %llu\n",
+                             h[24], h[25], h[26], h[27], h[28], h[29]);
+            if (h[14]) std::fprintf(stderr, "[mcpt direct-skip check] light samples at skipped vertices: %llu, non-zero contributions among them: %llu\n", h[14], h[15]);
+            for (int k = 0; k < 2; ++k) {
+                const unsigned long long *d = h + 8 * k;
+                if (!d[0]) continue;
+                std::fprintf(stderr, "[mcpt traversal stats] %s: rays %llu, node visits/ray %.2f, prim tests/ray %.2f, %s %.3f, found %.3f, SIMD efficiency %.3f\n",
+                             k ? "shadow" : "closest", d[0], (double)d[1] / d[0], (double)d[2] / d[0], k ? "occluded" : "hit",
+                             (double)d[3] / d[0], (double)d[5] / d[0], (double)(d[1] + d[2]) / (double)d[4]);
+            }
+        }
+    }
+#endif
+    delete sc;  // every member frees what it owns, in the order stated at struct mcpt_scene
+}
+
+int mcpt_bvh_dump(const mcpt_scene_desc *desc, mcpt_bvh_info *info, float *boxes, int32_t *children, uint16_t *qboxes,
+                  float *inst_shift, int32_t *inst_root_first) {
+    if (!desc || !info) return fail(MCPT_ERR_ARG, "mcpt_bvh_dump: null argument");
+    HostScene hs;
+    const char *err = "";
+    const BuildChoice choice = resolve_build_choice(nullptr);
+    if (choice.builder == MCPT_BUILD_GPU_LBVH || choice.builder == MCPT_BUILD_GPU_PLOC)
+        return fail(MCPT_ERR_ARG, "mcpt_bvh_dump: the tree is built on the device (MCPT_BVH=lbvh / ploc): use mcpt_scene_dump_bvh");
+    const int rc = build_host_scene(*desc, hs, &err, choice);
+    if (rc != MCPT_OK) return fail(rc, std::string("mcpt_bvh_dump: ") + err);
+    std::memset(info, 0, sizeof *info);
+    const bool placeholder = hs.root < 0;  // a single primitive: no inner node (the array holds one unused record)
+    info->n_nodes = placeholder ? 0 : (int32_t)hs.nodes.size();
+    info->root = hs.root;
+    info->stack_entries = hs.height;
+    info->quantised = hs.qnodes.empty() ? 0 : 1;
+    info->n_instances = (int32_t)hs.instances.size();
+    info->n_leaf_prims = hs.n_leaf_prims;
+    for (int k = 0; k < 3; ++k) {
+        info->root_min[k] = hs.root_min[k];
+        info->root_max[k] = hs.root_max[k];
+        info->q_origin[k] = hs.q_origin[k];
+        info->q_cell[k] = hs.q_cell[k];
+    }
+    for (size_t k = 0; k < hs.instances.size() && inst_shift && inst_root_first; ++k) {
+        for (int c = 0; c < 3; ++c) inst_shift[3 * k + c] = hs.instances[k].shift[c];
+        inst_root_first[2 * k] = hs.instances[k].root;
+        inst_root_first[2 * k + 1] = hs.instances[k].first_tri;
+    }
+    if (!boxes || !children) return MCPT_OK;
+    export_nodes(info->n_nodes, hs.nodes.data(), qboxes && info->quantised ? hs.qnodes.data() : nullptr, boxes, children, qboxes);
+    return MCPT_OK;
+}
+
+int mcpt_scene_dump_bvh(mcpt_scene *sc, mcpt_bvh_info *info, float *boxes, int32_t *children, uint16_t *qboxes, float *inst_shift,
+                        int32_t *inst_root_first) {
+    if (!sc || !info) return fail(MCPT_ERR_ARG, "mcpt_scene_dump_bvh: null argument");
+    HIP_TRY(hipSetDevice(sc->device));
+    std::memset(info, 0, sizeof *info);
+    const DevScene &v = sc->view;
+    info->n_nodes = sc->n_inner;
+    info->root = v.root;
+    info->stack_entries = v.height;
+    info->quantised = v.qnodes ? 1 : 0;
+    info->n_instances = sc->info.n_instances;
+    info->n_leaf_prims = v.n_leaf_prims;
+    if (info->n_instances > 0 && inst_shift && inst_root_first) {
+        std::vector<InstRec> I((size_t)info->n_instances);
+        HIP_TRY(download(I.data(), sc->inst, I.size()));
+        for (size_t k = 0; k < I.size(); ++k) {
+            for (int c = 0; c < 3; ++c) inst_shift[3 * k + c] = I[k].shift[c];
+            inst_root_first[2 * k] = I[k].root;
+            inst_root_first[2 * k + 1] = I[k].first_tri;
+        }
+    }
+    for (int k = 0; k < 3; ++k) {
+        info->root_min[k] = v.root_min[k];
+        info->root_max[k] = v.root_max[k];
+        info->q_origin[k] = v.q_origin[k];
+        info->q_cell[k] = v.q_cell[k];
+    }
+    if (!boxes || !children || info->n_nodes == 0) return MCPT_OK;
+    std::vector<Node> nodes((size_t)info->n_nodes);
+    HIP_TRY(download(nodes.data(), sc->nodes, nodes.size()));
+    std::vector<QNode> qn;
+    if (qboxes && info->quantised) {
+        qn.resize(nodes.size());
+        HIP_TRY(download(qn.data(), sc->qnodes, qn.size()));
+    }
+    export_nodes(info->n_nodes, nodes.data(), qn.empty() ? nullptr : qn.data(), boxes, children, qboxes);
+    return MCPT_OK;
+}
+
+int mcpt_scene_get_info(const mcpt_scene *sc, mcpt_scene_info *info) {
+    if (!sc || !info) return fail(MCPT_ERR_ARG, "mcpt_scene_get_info: null argument");
+    *info = sc->info;
+    return MCPT_OK;
+}
+
+}  // extern "C"
