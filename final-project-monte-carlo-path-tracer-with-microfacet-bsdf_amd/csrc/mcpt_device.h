@@ -83,6 +83,7 @@ MCPT_DI void rng_block(const RngKey &k, uint32_t depth, uint32_t block, float u[
 }
 
 // ---------------------------------------------------------------- scene view passed to kernels by value
+constexpr float kHalfspaceSlack = 1e-5f;  // relative margin of direct_is_zero's half-space rule (derived there: > 10x the float error bound)
 struct DevScene {
     const Node *nodes;
     const QNode *qnodes;  // quantised nodes, or nullptr (then `nodes` is traversed)
@@ -101,6 +102,9 @@ struct DevScene {
     float root_min[3], root_max[3];
     float background[3];
     float light_center[3], light_radius, light_area_sum;
+    // direct_is_zero's half-space rule (mcpt_kernels.hip): with L = light_center - q, every emitter lies behind the tangent plane of a
+    // vertex (q, n) if  n.L < -(light_plane[0] + light_plane[1] * |L|_1);  {R + kHalfspaceSlack * (|light_center|_1 + R), kHalfspaceSlack}
+    float light_plane[2];
     int32_t root, n_tri, n_lights, env_w, env_h, height;
     // Small-scene flavour (kernels' SMALL template flag, mcpt_kernels.hip): the whole traversal data set -- nodes, TriGeom, spheres -- and
     // the light tables fit a few KB, and every workgroup copies them into LDS once.  The counts say how much there is to copy.

@@ -1161,16 +1161,40 @@ MCPT_DI bool sample_light(const DevScene &S, const float u[4], f3 &x_l, f3 &n_l,
 //     Every light sample lies inside the cone of half-angle asin(R / D) around the direction to the centre of the
 //     emitters' bounding sphere (radius R, distance D > 1.01 R).  If r is farther from that cone than the tolerance
 //     (0.06 rad for reflection, 0.15 rad for refraction: > 1.5x the bounds above) no sample can give a non-zero eval.
+//   * the half-space rule, for EVERY material (emitters_behind): all emitters lie behind the tangent plane of the vertex.
+//     k_direct evaluates eval(ws, wo, n, isReflect = !inside) with ws = normalized(x_l - q) and inside = (wo.n < 0).  If the float value
+//     ws.n it computes is < 0, every branch of mat_eval returns 0.f at its first test:
+//       rough reflect  (wo.n >= 0): (ws.n)(wo.n) <= 0 -- negative, or -0 when wo.n is +-0 (then `inside` is false and the product is a zero);
+//       Dirac reflect  (wo.n >= 0): the same product is the first operand of its `||`, h is never looked at;
+//       rough refract  (wo.n <  0): conductors return 0 outright, dielectrics on (ws.n)(wo.n) >= 0 -- positive, or +0 on underflow;
+//       Dirac refract  (wo.n <  0): conductors or the same product in its `||`, whatever h is.
+//     Then c = emit * 0 * (ws.n) * (-ws.n_l) / dist^2 / pdf / n_dir is +-0 and not NaN: emit and pdf are finite and positive, the two
+//     cosines are finite, and dist exceeds the slack, which is >= 1e-5 * R >= 1e-8 (the host pads R by 1e-3), so dist^2 is a normal
+//     number.  Margin: the exact emitters lie within r of the centre c, and R = 1.001 r + 1e-3 >= r (mcpt_scene.cpp).  With unit
+//     roundoff u = 2^-24, D = |L|, |n| <= 1 + 2u:  a sampled x_l leaves the emitters' hull by at most 6u (|c| + r) (three rounded
+//     products and two sums of coordinates of that size; a sphere sample by less);  fl(x_l - q) errs by u |x_l - q|, its normalisation
+//     by 4u per component and the dot product with n by 3u, together 8u (D + r) in units of length;  this test's own L = fl(c - q) and
+//     n.L err by 4u D.  So the computed ws.n is negative whenever  n.L < -(r + 6u (|c| + r) + 12u (D + r)),  which
+//     n.L < -(R + kHalfspaceSlack * (|c|_1 + R + |L|_1))  implies with kHalfspaceSlack = 1e-5 >= 10 x 12u = 7.2e-7 to spare (the
+//     1-norms are upper bounds of |c| and D that cost no square root).  The distance gate D > 1.01 R of the cone rule stays in front.
 // tests: the -DMCPT_CHECK_DIRECT_SKIP build evaluates the skipped vertices anyway and counts non-zero contributions.
 // ------------------------------------------------------------------------------------------------
+MCPT_DI bool emitters_behind(const DevScene &S, f3 n, f3 L) {
+    return dot(n, L) < -(S.light_plane[0] + S.light_plane[1] * (fabsf(L.x) + (fabsf(L.y) + fabsf(L.z))));
+}
+
+// kHalfspace = false: without the half-space rule (the statistics build lists those vertices to count them, see k_direct).
+template <bool kHalfspace = true>
 MCPT_DI bool direct_is_zero(const DevScene &S, const MaterialRec &m, f3 q, f3 n, f3 wo, bool inside, int ch) {
     if (S.n_lights == 0) return true;
     const bool conductor = (m.type == MCPT_SMOOTH_CONDUCTOR || m.type == MCPT_ROUGH_CONDUCTOR);
     if (inside && conductor) return true;
-    if (!m.isDirac) return false;
+    if (!kHalfspace && !m.isDirac) return false;
     const f3 L = mk3(S.light_center[0], S.light_center[1], S.light_center[2]) - q;
     const float D2 = dot(L, L), R = S.light_radius;
     if (!(D2 > R * R * 1.0201f)) return false;
+    if (kHalfspace && emitters_behind(S, n, L)) return true;  // (cheap: before the cone test's square roots and divisions)
+    if (!m.isDirac) return false;
     const float D = sqrtf(D2);
     const float sl = R / D, cl = sqrtf(1.0f - sl * sl);
     f3 r;
@@ -1376,7 +1400,21 @@ __global__ __launch_bounds__(kShadeBlock, 8) void k_shade(DevScene S, RenderCons
 
     const f3 q = p + n * kEps;                       // Scene.cpp:114
     const bool inside = dot(wo, n) < 0;              // Scene.cpp:115
+#if defined(MCPT_TRAVERSAL_STATS) && !defined(MCPT_CHECK_DIRECT_SKIP)
+    // statistics build: the vertices only the half-space rule would skip stay on the list, marked, so that k_direct can count them
+    const bool zero_direct = do_shade && direct_is_zero<false>(S, m, q, n, wo, inside, ch);
+#else
     const bool zero_direct = do_shade && direct_is_zero(S, m, q, n, wo, inside, ch);
+#endif
+#if defined(MCPT_TRAVERSAL_STATS) || defined(MCPT_CHECK_DIRECT_SKIP)
+    bool behind = false;  // the half-space rule on its own (k_direct's counters)
+    if (do_shade && S.n_lights > 0) {
+        const f3 L = mk3(S.light_center[0], S.light_center[1], S.light_center[2]) - q;
+        behind = dot(L, L) > S.light_radius * S.light_radius * 1.0201f && emitters_behind(S, n, L);
+    }
+#else
+    const bool behind = false;
+#endif
 #ifdef MCPT_CHECK_DIRECT_SKIP
     const bool need_direct = do_shade;  // checking build: evaluate the skipped vertices too (k_direct counts violations)
 #else
@@ -1462,7 +1500,7 @@ __global__ __launch_bounds__(kShadeBlock, 8) void k_shade(DevScene S, RenderCons
         Xs.vtx0[dj] = make_float4(q.x, q.y, q.z, uv.x);
         Xs.vtx1[dj] = make_float4(n.x, n.y, n.z, uv.y);
         Xs.vtx2[dj] = make_float4(wo.x, wo.y, wo.z, __uint_as_float((uint32_t)mat_id | ((uint32_t)ch << 16) | (inside ? (1u << 18) : 0u) |
-                                                                    (zero_direct ? (1u << 19) : 0u)));
+                                                                    (zero_direct ? (1u << 19) : 0u) | (behind ? (1u << 20) : 0u)));
         Xs.vtx_j[dj] = j;
     }
     uint32_t flags = depth | (inside ? kInside : 0u) | (need_direct ? 0u : kNoDirect) | (pq ? kPassBit : 0u);
@@ -1512,6 +1550,9 @@ __global__ __launch_bounds__(kBlock, MCPT_DIRECT_WAVES) void k_direct(DevScene S
     f3 q = mk3(0, 0, 0), ws = mk3(0, 0, 1);
     float dist = 0.f;
     uint32_t target = 0;
+#ifdef MCPT_TRAVERSAL_STATS
+    bool st_nonzero = false, st_first = false, st_behind = false, st_dirac = false;
+#endif
     if (valid) {
         uint32_t dj, k;
         if (n_dir == 4u) {  // the reference's fixed count (Scene.hpp:28): no division
@@ -1570,10 +1611,44 @@ __global__ __launch_bounds__(kBlock, MCPT_DIRECT_WAVES) void k_direct(DevScene S
         if (((bits >> 19) & 1u) && S.dbg) {
             atomicAdd(&S.dbg[14], 1ull);
             if (!(c == 0.f)) atomicAdd(&S.dbg[15], 1ull);
+#ifndef MCPT_TRAVERSAL_STATS  // (that build keeps its shadow-ray statistics in 8..13)
+            if ((bits >> 20) & 1u) {  // the same two counts for the vertices the half-space rule claims, with or without another rule
+                atomicAdd(&S.dbg[12], 1ull);
+                if (!(c == 0.f)) atomicAdd(&S.dbg[13], 1ull);
+            }
+#endif
         }
+#endif
+#ifdef MCPT_TRAVERSAL_STATS
+        st_nonzero = !(c == 0.f);
+        st_first = k == 0u;
+        st_behind = (bits >> 20) & 1u;
+        st_dirac = m.isDirac;
 #endif
         next.contrib[target] = c;
     }
+#ifdef MCPT_TRAVERSAL_STATS
+    // Where the zero light samples come from (tools/direct_stats.py): samples, samples with c == 0, and -- the samples of a vertex are
+    // n_dir neighbouring lanes of one wave when n_dir is a power of two -- vertices ALL of whose samples are zero, by cause: (a) every
+    // emitter behind the tangent plane (emitters_behind; k_shade's statistics flavour lists those instead of skipping them),
+    // (b) Dirac BSDF and not (a), (c) rough BSDF and not (a).
+    if (S.dbg) {
+        const unsigned long long mv = __ballot(valid), mz = __ballot(valid && !st_nonzero), mn = __ballot(st_nonzero), mf = __ballot(st_first);
+        bool all_zero = false;
+        if (st_first && n_dir <= 64u && (n_dir & (n_dir - 1u)) == 0u)
+            all_zero = ((mn >> lane_id()) & (n_dir == 64u ? ~0ull : (1ull << n_dir) - 1ull)) == 0ull;
+        const unsigned long long ma = __ballot(all_zero && st_behind), mb = __ballot(all_zero && !st_behind && st_dirac),
+                                 mc = __ballot(all_zero && !st_behind && !st_dirac);
+        if (lane_id() == 0) {
+            atomicAdd(&S.dbg[16], (unsigned long long)__popcll(mv));
+            atomicAdd(&S.dbg[17], (unsigned long long)__popcll(mz));
+            atomicAdd(&S.dbg[18], (unsigned long long)__popcll(ma));
+            atomicAdd(&S.dbg[19], (unsigned long long)__popcll(mb));
+            atomicAdd(&S.dbg[30], (unsigned long long)__popcll(mc));
+            atomicAdd(&S.dbg[31], (unsigned long long)__popcll(mf));
+        }
+    }
+#endif
     // queue entries: one atomic per wave and kind on the counters of the wave's shard (see Counters): no barrier, no LDS
     const unsigned long long mf = __ballot(cast && !window), mw = __ballot(cast && window);
     if (mf | mw) {

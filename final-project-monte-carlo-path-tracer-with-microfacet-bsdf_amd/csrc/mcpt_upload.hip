@@ -28,6 +28,7 @@ void Knobs::read() {
 #ifdef MCPT_TEST_HOOKS
     if ((v = std::getenv("MCPT_RING_START"))) ring_start = (uint32_t)std::strtoul(v, nullptr, 0);
     if ((v = std::getenv("MCPT_HOST_DELAY_US"))) host_delay_us = std::atoi(v);
+    if ((v = std::getenv("MCPT_HALFSPACE_SLACK_SCALE"))) halfspace_slack_scale = (float)std::atof(v);
     if ((v = std::getenv("MCPT_FAKE_FREE_MB"))) fake_free_mb = (uint64_t)std::max(1, std::atoi(v));
 #endif
 }
@@ -178,6 +179,12 @@ int mcpt::upload_scene(const mcpt_scene_desc *desc, HostBuild &hb, int device, m
     v.height = hs.height;
     for (int k = 0; k < 3; ++k) v.light_center[k] = hs.light_center[k];
     v.light_radius = hs.light_radius;
+    {  // the half-space rule's margin (direct_is_zero): relative to every length whose rounding enters, scaled by the checking build's knob
+        const float k = kHalfspaceSlack * sc->knobs.halfspace_slack_scale;
+        const float c1 = std::fabs(hs.light_center[0]) + std::fabs(hs.light_center[1]) + std::fabs(hs.light_center[2]);
+        v.light_plane[0] = hs.light_radius + k * (c1 + hs.light_radius);
+        v.light_plane[1] = k;
+    }
     v.n_inner = sc->n_inner;
     v.n_sphere_slots = (int32_t)hs.spheres.size();
     v.n_mats = (int32_t)hs.materials.size();
@@ -285,6 +292,9 @@ void mcpt_scene_destroy(mcpt_scene *sc) {
             if (h[24] + h[25] + h[26] + h[27] + h[28])
                 std::fprintf(stderr, "[mcpt k_shade stats] waves by the number of material types among their shading lanes: 0: %llu, 1: %llu, 2: %llu, 3: %llu, 4: %llu; shading lanes %llu\n",
                              h[24], h[25], h[26], h[27], h[28], h[29]);
+            if (h[16])
+                std::fprintf(stderr, "[mcpt k_direct stats] vertices %llu, light samples %llu, zero samples %llu, vertices with only zero samples by cause: emitters behind the tangent plane %llu, Dirac otherwise %llu, rough otherwise %llu\n",
+                             h[31], h[16], h[17], h[18], h[19], h[30]);
             if (h[14]) std::fprintf(stderr, "[mcpt direct-skip check] light samples at skipped vertices: %llu, non-zero contributions among them: %llu\n", h[14], h[15]);
             for (int k = 0; k < 2; ++k) {
                 const unsigned long long *d = h + 8 * k;
