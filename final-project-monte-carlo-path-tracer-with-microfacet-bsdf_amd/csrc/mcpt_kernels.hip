@@ -1177,15 +1177,37 @@ MCPT_DI bool sample_light(const DevScene &S, const float u[4], f3 &x_l, f3 &n_l,
 //     n.L err by 4u D.  So the computed ws.n is negative whenever  n.L < -(r + 6u (|c| + r) + 12u (D + r)),  which
 //     n.L < -(R + kHalfspaceSlack * (|c|_1 + R + |L|_1))  implies with kHalfspaceSlack = 1e-5 >= 10 x 12u = 7.2e-7 to spare (the
 //     1-norms are upper bounds of |c| and D that cost no square root).  The distance gate D > 1.01 R of the cone rule stays in front.
+//   * total internal reflection: a Dirac dielectric seen from inside (wo.N < 0) is evaluated with isReflect = false, and with
+//     eta = ior when ws.N > 0 (ws.N <= 0 returns 0 on the product of the cosines).  h is the direction of hv = -ws - ior wo, whose part
+//     tangential to N is at least ior |wo_t| - |ws| long, while |hv| <= |ws| + ior |wo|.  `h.N >= 1 - EPSILON` in float means
+//     h.N >= 1 - 1.01e-4 exactly (h = normalized(hv) and its dot product with N err by less than 16u = 1e-6 together, u = 2^-24), so
+//     |hv_t| <= sin(acos(1 - 1.01e-4)) |hv| = 0.014212 |hv|, i.e.  ior |wo_t| <= |ws| + 0.014212 (|ws| + ior |wo|).  ws is normalised in
+//     k_direct and wo = -rd is a normalised ray direction: both are 1 to within 2u, and N is a normalised float normal.  With
+//     sin2 = ior^2 |wo_t|^2 as computed below (relative error < 1e-6) no light sample can pass if
+//     sin2 > 1.001 (1 + 0.0143 (1 + ior))^2:  0.0143 for 0.014212 and the factor 1.001 leave 6e-4 relative to the square root, 600 x
+//     what the roundings and the 2u of the lengths can move it.  The rule does not look at the emitters, but it stays behind the
+//     distance gate D > 1.01 R like the others: the gate is what keeps dist^2 a normal number, so that c = emit * 0 * ... is +-0 and
+//     not NaN.  (Measured, profiles/direct_tir_stats.txt: 78 % of the Dirac vertices of the chess frame whose samples are all zero and
+//     that the cone rule leaves are of this kind; the cone rule cannot see them, it needs a Snell direction.)
 // tests: the -DMCPT_CHECK_DIRECT_SKIP build evaluates the skipped vertices anyway and counts non-zero contributions.
 // ------------------------------------------------------------------------------------------------
 MCPT_DI bool emitters_behind(const DevScene &S, f3 n, f3 L) {
     return dot(n, L) < -(S.light_plane[0] + S.light_plane[1] * (fabsf(L.x) + (fabsf(L.y) + fabsf(L.z))));
 }
 
-// kHalfspace = false: without the half-space rule (the statistics build lists those vertices to count them, see k_direct).
-template <bool kHalfspace = true>
-MCPT_DI bool direct_is_zero(const DevScene &S, const MaterialRec &m, f3 q, f3 n, f3 wo, bool inside, int ch) {
+// The factor on the total-internal-reflection bound: 1.001, or what the checking build's knob MCPT_TIR_BOUND_SCALE made of it.
+MCPT_DI float tir_bound_factor(const DevScene &S) {
+#ifdef MCPT_TEST_HOOKS
+    return S.tir_bound_factor;
+#else
+    return 1.001f;
+#endif
+}
+
+// kHalfspace = false / kTir = false: without the half-space rule / the total-internal-reflection rule (the statistics build lists those
+// vertices to count them, see k_direct).  by_tir (statistics and checking builds): the total-internal-reflection rule claims the vertex.
+template <bool kHalfspace = true, bool kTir = true>
+MCPT_DI bool direct_is_zero(const DevScene &S, const MaterialRec &m, f3 q, f3 n, f3 wo, bool inside, int ch, bool *by_tir = nullptr) {
     if (S.n_lights == 0) return true;
     const bool conductor = (m.type == MCPT_SMOOTH_CONDUCTOR || m.type == MCPT_ROUGH_CONDUCTOR);
     if (inside && conductor) return true;
@@ -1208,7 +1230,12 @@ MCPT_DI bool direct_is_zero(const DevScene &S, const MaterialRec &m, f3 q, f3 n,
         const float won = dot(wo, n);
         const f3 wot = wo - n * won;
         const float sin2 = ior * ior * dot(wot, wot);
-        if (!(sin2 < 0.81f)) return false;
+        if (!(sin2 < 0.81f)) {  // no Snell direction for the cone test; beyond total internal reflection no sample can pass (see above)
+            const float b = 1.0f + 0.0143f * (1.0f + ior);
+            const bool tir = sin2 > tir_bound_factor(S) * (b * b);
+            if (by_tir) *by_tir = tir;
+            return kTir && tir;
+        }
         r = wot * (-ior) + n * sqrtf(1.0f - sin2);
         cm = 0.98877108f;  // cos(0.15)
         sm = 0.14943813f;  // sin(0.15)
@@ -1401,9 +1428,20 @@ __global__ __launch_bounds__(kShadeBlock, 8) void k_shade(DevScene S, RenderCons
     const f3 q = p + n * kEps;                       // Scene.cpp:114
     const bool inside = dot(wo, n) < 0;              // Scene.cpp:115
 #if defined(MCPT_TRAVERSAL_STATS) && !defined(MCPT_CHECK_DIRECT_SKIP)
-    // statistics build: the vertices only the half-space rule would skip stay on the list, marked, so that k_direct can count them
-    const bool zero_direct = do_shade && direct_is_zero<false>(S, m, q, n, wo, inside, ch);
+    // statistics build: the vertices only the half-space rule or only the total-internal-reflection rule would skip stay on the list,
+    // marked, so that k_direct can count them
+    bool by_tir = false, past_gate = false;  // past_gate: a Dirac dielectric seen from inside beyond the refraction gate sin2 < 0.81
+    const bool zero_direct = do_shade && direct_is_zero<false, false>(S, m, q, n, wo, inside, ch, &by_tir);
+    if (do_shade && m.isDirac && inside) {
+        const f3 wot = wo - n * dot(wo, n);
+        past_gate = !(get_ior(m, ch) * get_ior(m, ch) * dot(wot, wot) < 0.81f);
+    }
+#elif defined(MCPT_CHECK_DIRECT_SKIP)
+    bool by_tir = false;  // claimed by the total-internal-reflection rule (k_direct's counters)
+    const bool past_gate = false;
+    const bool zero_direct = do_shade && direct_is_zero(S, m, q, n, wo, inside, ch, &by_tir);
 #else
+    const bool by_tir = false, past_gate = false;
     const bool zero_direct = do_shade && direct_is_zero(S, m, q, n, wo, inside, ch);
 #endif
 #if defined(MCPT_TRAVERSAL_STATS) || defined(MCPT_CHECK_DIRECT_SKIP)
@@ -1500,7 +1538,8 @@ __global__ __launch_bounds__(kShadeBlock, 8) void k_shade(DevScene S, RenderCons
         Xs.vtx0[dj] = make_float4(q.x, q.y, q.z, uv.x);
         Xs.vtx1[dj] = make_float4(n.x, n.y, n.z, uv.y);
         Xs.vtx2[dj] = make_float4(wo.x, wo.y, wo.z, __uint_as_float((uint32_t)mat_id | ((uint32_t)ch << 16) | (inside ? (1u << 18) : 0u) |
-                                                                    (zero_direct ? (1u << 19) : 0u) | (behind ? (1u << 20) : 0u)));
+                                                                    (zero_direct ? (1u << 19) : 0u) | (behind ? (1u << 20) : 0u) | (by_tir ? (1u << 21) : 0u) |
+                                                                    (past_gate ? (1u << 22) : 0u)));
         Xs.vtx_j[dj] = j;
     }
     uint32_t flags = depth | (inside ? kInside : 0u) | (need_direct ? 0u : kNoDirect) | (pq ? kPassBit : 0u);
@@ -1551,7 +1590,7 @@ __global__ __launch_bounds__(kBlock, MCPT_DIRECT_WAVES) void k_direct(DevScene S
     float dist = 0.f;
     uint32_t target = 0;
 #ifdef MCPT_TRAVERSAL_STATS
-    bool st_nonzero = false, st_first = false, st_behind = false, st_dirac = false;
+    bool st_nonzero = false, st_first = false, st_behind = false, st_dirac = false, st_inside = false, st_gate = false, st_tir = false;
 #endif
     if (valid) {
         uint32_t dj, k;
@@ -1616,6 +1655,10 @@ __global__ __launch_bounds__(kBlock, MCPT_DIRECT_WAVES) void k_direct(DevScene S
                 atomicAdd(&S.dbg[12], 1ull);
                 if (!(c == 0.f)) atomicAdd(&S.dbg[13], 1ull);
             }
+            if ((bits >> 21) & 1u) {  // and for the vertices the total-internal-reflection rule claims
+                atomicAdd(&S.dbg[10], 1ull);
+                if (!(c == 0.f)) atomicAdd(&S.dbg[11], 1ull);
+            }
 #endif
         }
 #endif
@@ -1624,6 +1667,9 @@ __global__ __launch_bounds__(kBlock, MCPT_DIRECT_WAVES) void k_direct(DevScene S
         st_first = k == 0u;
         st_behind = (bits >> 20) & 1u;
         st_dirac = m.isDirac;
+        st_inside = inside;
+        st_tir = (bits >> 21) & 1u;
+        st_gate = (bits >> 22) & 1u;
 #endif
         next.contrib[target] = c;
     }
@@ -1639,6 +1685,7 @@ __global__ __launch_bounds__(kBlock, MCPT_DIRECT_WAVES) void k_direct(DevScene S
             all_zero = ((mn >> lane_id()) & (n_dir == 64u ? ~0ull : (1ull << n_dir) - 1ull)) == 0ull;
         const unsigned long long ma = __ballot(all_zero && st_behind), mb = __ballot(all_zero && !st_behind && st_dirac),
                                  mc = __ballot(all_zero && !st_behind && !st_dirac);
+        const unsigned long long mi = __ballot(st_inside), mg = __ballot(st_gate), mt = __ballot(st_tir);
         if (lane_id() == 0) {
             atomicAdd(&S.dbg[16], (unsigned long long)__popcll(mv));
             atomicAdd(&S.dbg[17], (unsigned long long)__popcll(mz));
@@ -1646,6 +1693,12 @@ __global__ __launch_bounds__(kBlock, MCPT_DIRECT_WAVES) void k_direct(DevScene S
             atomicAdd(&S.dbg[19], (unsigned long long)__popcll(mb));
             atomicAdd(&S.dbg[30], (unsigned long long)__popcll(mc));
             atomicAdd(&S.dbg[31], (unsigned long long)__popcll(mf));
+            // (b) split: reflection; refraction within the sin2 < 0.81 gate; beyond the gate and not / and claimed by the
+            // total-internal-reflection rule (slots of their own: 6 and 7 hold the deepest traversal stacks)
+            atomicAdd(&S.dbg[32], (unsigned long long)__popcll(mb & ~mi));
+            atomicAdd(&S.dbg[33], (unsigned long long)__popcll(mb & mi & ~mg));
+            atomicAdd(&S.dbg[34], (unsigned long long)__popcll(mb & mi & mg & ~mt));
+            atomicAdd(&S.dbg[35], (unsigned long long)__popcll(mb & mi & mg & mt));
         }
     }
 #endif

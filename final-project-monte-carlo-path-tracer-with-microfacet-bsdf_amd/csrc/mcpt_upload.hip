@@ -29,6 +29,7 @@ void Knobs::read() {
     if ((v = std::getenv("MCPT_RING_START"))) ring_start = (uint32_t)std::strtoul(v, nullptr, 0);
     if ((v = std::getenv("MCPT_HOST_DELAY_US"))) host_delay_us = std::atoi(v);
     if ((v = std::getenv("MCPT_HALFSPACE_SLACK_SCALE"))) halfspace_slack_scale = (float)std::atof(v);
+    if ((v = std::getenv("MCPT_TIR_BOUND_SCALE"))) tir_bound_scale = (float)std::atof(v);
     if ((v = std::getenv("MCPT_FAKE_FREE_MB"))) fake_free_mb = (uint64_t)std::max(1, std::atoi(v));
 #endif
 }
@@ -185,6 +186,7 @@ int mcpt::upload_scene(const mcpt_scene_desc *desc, HostBuild &hb, int device, m
         v.light_plane[0] = hs.light_radius + k * (c1 + hs.light_radius);
         v.light_plane[1] = k;
     }
+    v.tir_bound_factor = 1.001f * sc->knobs.tir_bound_scale;
     v.n_inner = sc->n_inner;
     v.n_sphere_slots = (int32_t)hs.spheres.size();
     v.n_mats = (int32_t)hs.materials.size();
@@ -200,8 +202,8 @@ int mcpt::upload_scene(const mcpt_scene_desc *desc, HostBuild &hb, int device, m
 #endif
     v.dbg = nullptr;
 #if defined(MCPT_TRAVERSAL_STATS) || defined(MCPT_CHECK_DIRECT_SKIP)
-    if (sc->dbg.alloc(32) == hipSuccess) {  // (16 reported by mcpt_debug_counters; the statistics build prints the rest at destruction)
-        (void)hipMemset(sc->dbg.p, 0, 32 * sizeof(unsigned long long));
+    if (sc->dbg.alloc(36) == hipSuccess) {  // (16 reported by mcpt_debug_counters; the statistics build prints the rest at destruction)
+        (void)hipMemset(sc->dbg.p, 0, 36 * sizeof(unsigned long long));
         v.dbg = sc->dbg.p;
     }
 #endif
@@ -284,7 +286,7 @@ void mcpt_scene_destroy(mcpt_scene *sc) {
     (void)hipSetDevice(sc->device);
 #if defined(MCPT_TRAVERSAL_STATS) || defined(MCPT_CHECK_DIRECT_SKIP)
     if (sc->dbg.p) {
-        unsigned long long h[32];
+        unsigned long long h[36];
         if (hipMemcpy(h, sc->dbg.p, sizeof h, hipMemcpyDeviceToHost) == hipSuccess) {
             if (h[23])
                 std::fprintf(stderr, "[mcpt k_shade stats] %llu waves: %.0f cycles from start to the end of the allocation, of which %.0f in its first half (ballots, first barrier) and %.0f in the second barrier\n",
@@ -295,6 +297,9 @@ void mcpt_scene_destroy(mcpt_scene *sc) {
             if (h[16])
                 std::fprintf(stderr, "[mcpt k_direct stats] vertices %llu, light samples %llu, zero samples %llu, vertices with only zero samples by cause: emitters behind the tangent plane %llu, Dirac otherwise %llu, rough otherwise %llu\n",
                              h[31], h[16], h[17], h[18], h[19], h[30]);
+            if (h[16])
+                std::fprintf(stderr, "[mcpt k_direct stats] Dirac otherwise, split: reflection %llu, refraction within the sin2 < 0.81 gate %llu, beyond the gate %llu, of which the total-internal-reflection rule claims %llu\n",
+                             h[32], h[33], h[34] + h[35], h[35]);
             if (h[14]) std::fprintf(stderr, "[mcpt direct-skip check] light samples at skipped vertices: %llu, non-zero contributions among them: %llu\n", h[14], h[15]);
             for (int k = 0; k < 2; ++k) {
                 const unsigned long long *d = h + 8 * k;

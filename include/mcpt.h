@@ -393,6 +393,8 @@ int mcpt_debug_scene(mcpt_scene *scene, int kind, int64_t n, const float *in, fl
  * entries are filled only by a -DMCPT_TRAVERSAL_STATS build); all zero in the product build.
  *   out[0..5]   closest-hit rays: rays, node visits, primitive tests, hits, 64 x wave iterations, -
  *   out[8..13]  shadow rays: rays, node visits, primitive tests, occluded, 64 x wave iterations, found in the window
+ *   out[10..13] (checking build) the counts of out[14] / out[15] for the vertices the total-internal-reflection rule claims (10, 11)
+ *               and for those the half-space rule claims (12, 13)
  *   out[14]     light samples evaluated at vertices the product would have skipped as "provably zero" (direct_is_zero)
  *   out[15]     how many of those had a non-zero contribution (must be 0) */
 int mcpt_debug_counters(mcpt_scene *scene, uint64_t out[16]);
