@@ -1,7 +1,8 @@
 // The host layer behind the C ABI (include/mcpt.h): error plumbing, the owners of device resources, the wavefront workspace, the
 // environment knobs, the event timer, struct mcpt_scene, and what its translation units call in each other:
 //   mcpt_wavefront.hip  the wavefront loop, workspace / pass sizing (render_list), the pixel list and sky cull set-up
-//   mcpt_upload.hip     scene create / upload / destroy / info, the BVH dumps
+//   mcpt_upload.hip     scene create / upload / update / destroy / info, the BVH dumps
+//   mcpt_update.hip     the kernel that moves objects in HBM (the device path of mcpt_scene_update), mcpt_transform_triangles
 //   mcpt_render.hip     the frame-level entry points (render, adaptive, AOVs, denoise)
 //   mcpt_query.hip      ray queries, tone map and the debug entry points
 //   mcpt_multi.hip      mcpt_group_*
@@ -62,6 +63,10 @@ struct DevBuf {
         n = 0;
     }
     size_t bytes() const { return n * sizeof(T); }
+    void swap(DevBuf &o) {
+        std::swap(p, o.p);
+        std::swap(n, o.n);
+    }
 };
 
 template <typename T>
@@ -283,6 +288,71 @@ struct Totals {
     }
 };
 
+// The device arrays that depend on where the objects are.  mcpt_scene_update fills a second set beside the live one and swaps the two
+// once the new tree is known to be usable, so that a failed update leaves the scene as it was.
+struct GeomBufs {
+    DevBuf<Node> nodes;
+    DevBuf<QNode> qnodes;
+    DevBuf<TriGeom> tri_geom;
+    DevBuf<TriShade> tri_shade;
+    DevBuf<SphereRec> spheres;
+    DevBuf<mcpt_triangle> tris;  // device builders, after the first update: the moved triangles the tree was built from
+    DevBuf<LightRec> lights;
+    DevBuf<LightNode> light_nodes;
+    DevBuf<LightTri> light_tris;
+    void swap_prims(GeomBufs &o) {  // the tree and the primitive records
+        nodes.swap(o.nodes);
+        qnodes.swap(o.qnodes);
+        tri_geom.swap(o.tri_geom);
+        tri_shade.swap(o.tri_shade);
+        spheres.swap(o.spheres);
+        tris.swap(o.tris);
+    }
+    void swap_lights(GeomBufs &o) {
+        lights.swap(o.lights);
+        light_nodes.swap(o.light_nodes);
+        light_tris.swap(o.light_tris);
+    }
+};
+
+// What DevScene and mcpt_scene_info take from a flattened scene besides the arrays (fill_view, csrc/mcpt_upload.hip).
+struct SceneMeta {
+    int32_t root = 0, height = 0, n_inner = 0, n_leaf_prims = 0;
+    float root_min[3] = {0, 0, 0}, root_max[3] = {0, 0, 0}, q_origin[3] = {0, 0, 0}, q_cell[3] = {1, 1, 1};
+    int32_t n_triangles = 0, n_objects = 0, builder = 0, n_instances = 0;
+    int32_t n_sphere_slots = 0, n_mats = 0, n_lights = 0, n_light_nodes = 0, n_light_tris = 0;
+    int32_t env_w = 0, env_h = 0;
+    float background[3] = {0, 0, 0};
+    float light_area_sum = 0.f, light_center[3] = {0, 0, 0}, light_radius = 0.f;
+};
+
+// The creation-time description of a scene and the transforms its objects currently have (mcpt_scene_update: transforms are absolute,
+// so every update starts from these arrays).
+struct SceneSource {
+    std::vector<mcpt_triangle> triangles;
+    std::vector<mcpt_object> objects;
+    std::vector<mcpt_material> materials;
+    std::vector<uint8_t> moved;  // per object: 1 once it has been given a transform
+    std::vector<float> xf;       // per object: its row-major 3x4 matrix (unused while moved == 0)
+    BuildChoice choice;          // the builder and its options as resolved at creation
+};
+
+// One run of lanes of the update kernel (csrc/mcpt_update.hip): the triangles of a moved mesh, or one moved sphere.
+struct alignas(16) MoveSeg {
+    int32_t first_lane;  // lanes [first_lane, first_lane + count) work on this segment
+    int32_t count;       // mesh: its triangles; sphere: 1
+    int32_t first_tri;   // mesh: its first triangle; sphere: -1
+    int32_t object;      // sphere: its slot in the SphereRec array
+    float m[12];
+    float c0[3];         // sphere: the creation-time centre
+    int32_t raw;         // 1: the object has no transform: the creation-time values are copied, not multiplied by an identity
+};
+static_assert(sizeof(MoveSeg) == 80, "MoveSeg must be 80 bytes");
+// Writes, for every listed segment, the moved triangle into tris_cur and the geometry words of its TriGeom / TriShade records (mat_bits,
+// mat and the texture coordinates stay), or the moved centre into its SphereRec.  tris0: the creation-time triangles.
+void launch_move_objects(const MoveSeg *d_segs, int32_t n_segs, int32_t n_lanes, const mcpt_triangle *tris0, mcpt_triangle *tris_cur,
+                         TriGeom *tri_geom, TriShade *tri_shade, SphereRec *spheres, hipStream_t s);
+
 }  // namespace mcpt
 
 // Members are destroyed in reverse order, with the scene's device current (mcpt_scene_destroy): the pools' workspaces and timers, their
@@ -290,18 +360,15 @@ struct Totals {
 struct mcpt_scene {
     int device = 0;
     int device_sharers = 1;  // scenes of one group that live on this device (mcpt_group_create with a device listed several times)
-    int32_t n_inner = 0;  // inner nodes of the traversal tree (0: the root is a leaf)
     mcpt::Knobs knobs;
     mcpt_scene_info info{};
-    mcpt::DevBuf<mcpt::Node> nodes;
-    mcpt::DevBuf<mcpt::QNode> qnodes;
-    mcpt::DevBuf<mcpt::TriGeom> tri_geom;
-    mcpt::DevBuf<mcpt::TriShade> tri_shade;
-    mcpt::DevBuf<mcpt::SphereRec> spheres;
+    mcpt::SceneMeta meta;
+    mcpt::SceneSource src;
+    mcpt::GeomBufs geom;
+    mcpt::DevBuf<mcpt_triangle> tris0;   // device builders: the creation-time triangles
+    mcpt::DevBuf<int32_t> sphere_obj;    // device builders: object index of every sphere (the builder's primitive list)
+    mcpt::DevBuf<mcpt::MoveSeg> segs;    // the update kernel's segment table
     mcpt::DevBuf<mcpt::MaterialRec> mats;
-    mcpt::DevBuf<mcpt::LightRec> lights;
-    mcpt::DevBuf<mcpt::LightNode> light_nodes;
-    mcpt::DevBuf<mcpt::LightTri> light_tris;
     mcpt::DevBuf<mcpt::InstRec> inst;
     mcpt::DevBuf<float> env;
     mcpt::DevBuf<unsigned long long> dbg;
@@ -344,6 +411,13 @@ struct HostBuild {
 };
 int build_scene_host(const mcpt_scene_desc *desc, const mcpt_build_options *options, HostBuild &hb);
 int upload_scene(const mcpt_scene_desc *desc, HostBuild &hb, int device, mcpt_scene **out);
+// mcpt_scene_update without the argument checks: gives the scene the transform table (moved, xf), of which the objects in `touched`
+// differ from the table it has.  Also the way back for mcpt_group_update when another replica fails.
+int apply_transforms(mcpt_scene *sc, const std::vector<uint8_t> &moved, const std::vector<float> &xf, const std::vector<int32_t> &touched,
+                     mcpt_update_info *info);
+// The argument checks of mcpt_scene_update, before any device call; fills the table the scene would have afterwards.
+int check_moves(const mcpt_scene *sc, int32_t n, const mcpt_object_transform *moves, std::vector<uint8_t> &moved, std::vector<float> &xf,
+                std::vector<int32_t> &touched);
 double warm_up_device(int device);
 
 // ---- mcpt_wavefront.hip

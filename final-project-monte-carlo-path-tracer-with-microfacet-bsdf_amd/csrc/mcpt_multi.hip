@@ -200,6 +200,42 @@ int mcpt_group_size(const mcpt_group *g) { return g ? (int)g->scenes.size() : 0;
 
 mcpt_scene *mcpt_group_scene(mcpt_group *g, int index) { return (g && index >= 0 && index < (int)g->scenes.size()) ? g->scenes[(size_t)index] : nullptr; }
 
+int mcpt_group_update(mcpt_group *g, int32_t n, const mcpt_object_transform *moves) {
+    if (!g || g->scenes.empty()) return gfail(MCPT_ERR_ARG, "mcpt_group_update: null group");
+    const int N = (int)g->scenes.size();
+    // every replica holds the same description and the same transforms: one check, before any device call
+    std::vector<uint8_t> moved, moved_old = g->scenes[0]->src.moved;
+    std::vector<float> xf, xf_old = g->scenes[0]->src.xf;
+    std::vector<int32_t> touched;
+    const int rc0 = check_moves(g->scenes[0], n, moves, moved, xf, touched);
+    if (rc0 != MCPT_OK) return gfail(rc0, std::string("mcpt_group_update: ") + mcpt_last_error());
+    std::vector<int> rc((size_t)N, MCPT_OK);
+    std::vector<std::string> err((size_t)N);
+    auto run = [&](const std::vector<uint8_t> &mv_, const std::vector<float> &xf_, const std::vector<int> &which) {
+        auto work = [&](int i) {
+            rc[(size_t)i] = apply_transforms(g->scenes[(size_t)i], mv_, xf_, touched, nullptr);
+            if (rc[(size_t)i] != MCPT_OK) err[(size_t)i] = mcpt_last_error();
+        };
+        std::vector<std::thread> th;
+        for (size_t k = 1; k < which.size(); ++k) th.emplace_back(work, which[k]);
+        if (!which.empty()) work(which[0]);
+        for (std::thread &t : th) t.join();
+    };
+    std::vector<int> all, done;
+    for (int i = 0; i < N; ++i) all.push_back(i);
+    run(moved, xf, all);
+    int bad = -1;
+    for (int i = 0; i < N; ++i) {
+        if (rc[(size_t)i] == MCPT_OK) done.push_back(i);
+        else if (bad < 0) bad = i;
+    }
+    if (bad < 0) return MCPT_OK;
+    const int code = rc[(size_t)bad];
+    const std::string e = "mcpt_group_update: device " + std::to_string(g->devices[(size_t)bad]) + ": " + err[(size_t)bad];
+    run(moved_old, xf_old, done);  // the replicas that had moved go back: the group stays one scene
+    return gfail(code, e);
+}
+
 int mcpt_group_get_info(const mcpt_group *g, mcpt_group_info *info) {
     if (!g || !info) return gfail(MCPT_ERR_ARG, "mcpt_group_get_info: null argument");
     std::memset(info, 0, sizeof *info);

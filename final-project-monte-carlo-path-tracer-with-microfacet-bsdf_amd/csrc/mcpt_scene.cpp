@@ -19,17 +19,16 @@
 #include <chrono>
 
 #include "mcpt_internal.h"
+#include "mcpt_move.h"
 
 namespace mcpt {
 namespace {
 
-struct V3 {
-    float x, y, z;
-};
-inline V3 ld(const float *p) { return {p[0], p[1], p[2]}; }
-inline V3 operator-(V3 a, V3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-inline float dot3(V3 a, V3 b) { return a.x * b.x + (a.y * b.y + a.z * b.z); }  // Eigen's 3-term redux order
-inline V3 cross3(V3 a, V3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
+// (the vector type and the per-triangle expressions are shared with the update kernel: csrc/mcpt_move.h)
+using mv::V3;
+using mv::ld;
+using mv::dot3;
+inline V3 operator-(V3 a, V3 b) { return mv::sub(a, b); }
 
 struct Box {
     V3 mn, mx;
@@ -646,20 +645,12 @@ int build_host_scene(const mcpt_scene_desc &d, HostScene &hs, const char **err, 
                 tri_seen[ti] = 1;
                 const mcpt_triangle &t = d.triangles[ti];
                 const V3 v0 = ld(t.v0), v1 = ld(t.v1), v2 = ld(t.v2);
-                const V3 e1 = v1 - v0, e2 = v2 - v0;  // Triangle.hpp:52-55
-                const V3 c = cross3(e1, e2);
-                const float z = dot3(c, c);
-                const V3 n = z > 0.f ? V3{c.x / sqrtf(z), c.y / sqrtf(z), c.z / sqrtf(z)} : c;
-                const float a = sqrtf(dot3(c, c)) * 0.5f;
+                const mv::TriDerived D = mv::derive_triangle(v0, v1, v2);  // Triangle.hpp:52-55
+                const V3 n = D.n;
+                const float a = D.area;
                 TriGeom &g = hs.tri_geom[ti];
                 std::memset(&g, 0, sizeof g);
-                store3(g.v0, v0);
-                g.e1x = e1.x;
-                g.e1yz[0] = e1.y;
-                g.e1yz[1] = e1.z;
-                g.e2xy[0] = e2.x;
-                g.e2xy[1] = e2.y;
-                g.e2z = e2.z;
+                mv::store_geom(g, v0, D);
                 g.mat_bits = (uint32_t)o.material | (hs.materials[o.material].hasEmission ? kMatEmissive : 0u) | (hs.materials[o.material].textured ? kMatTextured : 0u);
                 TriShade &s = hs.tri_shade[ti];
                 std::memset(&s, 0, sizeof s);

@@ -1,0 +1,83 @@
+// Moving objects in a live scene (include/mcpt.h: mcpt_scene_update): the kernel of the device path and the host helper
+// mcpt_transform_triangles.  The scene-level part (argument checks, the two paths, the swap of the new arrays) is beside
+// mcpt_scene_create in csrc/mcpt_upload.hip; the arithmetic is csrc/mcpt_move.h, shared with the scene builder.
+#include <cmath>
+
+#include "mcpt_host.h"
+#include "mcpt_move.h"
+
+namespace mcpt {
+
+namespace {
+
+constexpr int kB = 256;
+
+// One lane per triangle of the moved meshes (and one per moved sphere).  The lane finds its segment by bisection over first_lane, reads
+// the CREATION-TIME triangle (transforms are absolute), and writes the moved triangle for the tree builder and the geometry words of
+// the two 48-byte records: 16-byte loads and stores of whole quarters, so that mat_bits, mat, the texture coordinates and the padding
+// pass through untouched.
+__global__ __launch_bounds__(kB) void k_move_objects(const MoveSeg *__restrict__ segs, int32_t n_segs, int32_t n_lanes, const mcpt_triangle *__restrict__ tris0,
+                                                      mcpt_triangle *__restrict__ tris_cur, TriGeom *__restrict__ tri_geom, TriShade *__restrict__ tri_shade,
+                                                      SphereRec *__restrict__ spheres) {
+    const int32_t lane = (int32_t)(blockIdx.x * kB + threadIdx.x);
+    if (lane >= n_lanes) return;
+    int32_t lo = 0, hi = n_segs - 1;  // the last segment whose first_lane <= lane
+    while (lo < hi) {
+        const int32_t mid = (lo + hi + 1) >> 1;
+        if (segs[mid].first_lane <= lane) lo = mid;
+        else hi = mid - 1;
+    }
+    const MoveSeg *sg = segs + lo;
+    const float4 r0 = *reinterpret_cast<const float4 *>(sg->m), r1 = *reinterpret_cast<const float4 *>(sg->m + 4), r2 = *reinterpret_cast<const float4 *>(sg->m + 8);
+    const float m[12] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w, r2.x, r2.y, r2.z, r2.w};
+    const bool raw = sg->raw != 0;
+    if (sg->first_tri < 0) {  // a sphere: the centre moves, the radius stays
+        const mv::V3 c0 = {sg->c0[0], sg->c0[1], sg->c0[2]};
+        const mv::V3 c = raw ? c0 : mv::move_point(m, c0);
+        float4 *rec = reinterpret_cast<float4 *>(spheres + sg->object);
+        float4 q = rec[0];  // {c.xyz, radius}
+        q.x = c.x;
+        q.y = c.y;
+        q.z = c.z;
+        rec[0] = q;
+        return;
+    }
+    const int32_t ti = sg->first_tri + (lane - sg->first_lane);
+    mcpt_triangle t = tris0[ti];
+    if (!raw) mv::move_triangle(m, t, t);
+    tris_cur[ti] = t;
+    const mv::V3 v0 = mv::ld(t.v0);
+    const mv::TriDerived D = mv::derive_triangle(v0, mv::ld(t.v1), mv::ld(t.v2));
+    float4 *g = reinterpret_cast<float4 *>(tri_geom + ti);
+    float4 g2 = g[2];  // {e2z, mat_bits, pad, pad}
+    g2.x = D.e2.z;
+    g[0] = make_float4(v0.x, v0.y, v0.z, D.e1.x);
+    g[1] = make_float4(D.e1.y, D.e1.z, D.e2.x, D.e2.y);
+    g[2] = g2;
+    float4 *s = reinterpret_cast<float4 *>(tri_shade + ti);
+    float4 s0 = s[0];  // {n.xyz, mat}
+    s0.x = D.n.x;
+    s0.y = D.n.y;
+    s0.z = D.n.z;
+    s[0] = s0;
+}
+
+}  // namespace
+
+void launch_move_objects(const MoveSeg *d_segs, int32_t n_segs, int32_t n_lanes, const mcpt_triangle *tris0, mcpt_triangle *tris_cur, TriGeom *tri_geom,
+                         TriShade *tri_shade, SphereRec *spheres, hipStream_t s) {
+    if (n_lanes <= 0 || n_segs <= 0) return;
+    hipLaunchKernelGGL(k_move_objects, dim3((uint32_t)((n_lanes + kB - 1) / kB)), dim3(kB), 0, s, d_segs, n_segs, n_lanes, tris0, tris_cur, tri_geom, tri_shade,
+                       spheres);
+}
+
+}  // namespace mcpt
+
+extern "C" int mcpt_transform_triangles(const float m[12], int64_t n, const mcpt_triangle *in, mcpt_triangle *out) {
+    using namespace mcpt;
+    if (!m || n < 0 || (n > 0 && (!in || !out))) return fail(MCPT_ERR_ARG, "mcpt_transform_triangles: bad argument");
+    for (int k = 0; k < 12; ++k)
+        if (!std::isfinite(m[k])) return fail(MCPT_ERR_ARG, "mcpt_transform_triangles: a matrix entry is not finite");
+    for (int64_t i = 0; i < n; ++i) mv::move_triangle(m, in[i], out[i]);
+    return MCPT_OK;
+}

@@ -1,4 +1,5 @@
 // Scene create / upload / destroy / info and the BVH dumps of the C ABI (include/mcpt.h); mcpt_last_error and mcpt_version.
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <memory>
@@ -6,6 +7,7 @@
 
 #include "mcpt_host.h"
 #include "mcpt_lbvh.h"
+#include "mcpt_move.h"
 
 using namespace mcpt;
 
@@ -69,6 +71,170 @@ int mcpt::build_scene_host(const mcpt_scene_desc *desc, const mcpt_build_options
     return MCPT_OK;
 }
 
+namespace {
+
+SceneMeta meta_of(const HostScene &hs) {
+    SceneMeta m;
+    m.root = hs.root;
+    m.height = hs.height;
+    m.n_inner = hs.root < 0 ? 0 : (int32_t)hs.nodes.size();  // (device builders: set by build_device_tree)
+    m.n_leaf_prims = hs.n_leaf_prims;
+    for (int k = 0; k < 3; ++k) {
+        m.root_min[k] = hs.root_min[k];
+        m.root_max[k] = hs.root_max[k];
+        m.q_origin[k] = hs.q_origin[k];
+        m.q_cell[k] = hs.q_cell[k];
+        m.background[k] = hs.background[k];
+        m.light_center[k] = hs.light_center[k];
+    }
+    m.n_triangles = hs.n_triangles;
+    m.n_objects = hs.n_objects;
+    m.builder = hs.builder;
+    m.n_instances = (int32_t)hs.instances.size();
+    m.n_sphere_slots = (int32_t)hs.spheres.size();
+    m.n_mats = (int32_t)hs.materials.size();
+    m.n_lights = (int32_t)hs.lights.size();
+    m.n_light_nodes = (int32_t)hs.light_nodes.size();
+    m.n_light_tris = (int32_t)hs.light_tris.size();
+    m.env_w = hs.env_w;
+    m.env_h = hs.env_h;
+    m.light_area_sum = hs.light_area_sum;
+    m.light_radius = hs.light_radius;
+    return m;
+}
+
+// The traversal tree of a device-built scene (csrc/mcpt_lbvh.hip), from triangles and sphere records that are on the device, into
+// g.nodes / g.qnodes; the tree fields of `meta` are the builder's.
+int build_device_tree(const mcpt_triangle *d_tris, const int32_t *d_sphere_obj, int n_sph, const BuildChoice &choice, GeomBufs &g, SceneMeta &meta) {
+    const int n_prim = meta.n_triangles + n_sph;
+    hipError_t e = g.nodes.alloc((size_t)n_prim - 1);
+    if (e == hipSuccess) e = g.qnodes.alloc((size_t)n_prim - 1);
+    LbvhResult R;
+    if (e == hipSuccess) e = build_lbvh_device(d_tris, meta.n_triangles, d_sphere_obj, g.spheres.p, n_sph, choice.quantise, meta.builder == 3 ? 1 : 0, choice.ploc_radius, choice.ploc_top,
+                                             g.nodes.p, g.qnodes.p, &R, nullptr);
+    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? MCPT_ERR_OOM : MCPT_ERR_HIP, std::string("GPU BVH build: ") + hipGetErrorString(e));
+    if (R.height > kMaxBvhHeight) return fail(MCPT_ERR_LIMIT, "the GPU-built BVH is deeper than the traversal stack (kMaxBvhHeight); use MCPT_BUILD_SAH");
+    meta.root = R.root;
+    meta.height = R.height;
+    for (int k = 0; k < 3; ++k) {
+        meta.root_min[k] = R.root_min[k];
+        meta.root_max[k] = R.root_max[k];
+        meta.q_origin[k] = R.q_origin[k];
+        meta.q_cell[k] = R.q_cell[k];
+    }
+    if (!R.quantised) g.qnodes.release();
+    meta.n_inner = R.n_nodes;
+    return MCPT_OK;
+}
+
+// Copies the arrays of a flattened scene that depend on where its objects are into `g`; for the device builders the tree is then built
+// there from d_tris (the triangles `hs` was flattened from).  Shared by mcpt_scene_create and the host path of mcpt_scene_update.
+int upload_geometry(const HostScene &hs, const BuildChoice &choice, const mcpt_triangle *d_tris, const int32_t *d_sphere_obj, GeomBufs &g, SceneMeta &meta,
+                    double &gpu_build_ms) {
+    hipError_t e = hipSuccess;
+    auto up = [&](auto &buf, const auto &vec) {
+        if (e == hipSuccess) e = upload(buf, vec);
+    };
+    if (hs.builder < 2) {
+        up(g.nodes, hs.nodes);
+        if (!hs.qnodes.empty()) up(g.qnodes, hs.qnodes);
+    }
+    up(g.tri_geom, hs.tri_geom);
+    up(g.tri_shade, hs.tri_shade);
+    up(g.spheres, hs.spheres);
+    up(g.lights, hs.lights);
+    up(g.light_nodes, hs.light_nodes);
+    up(g.light_tris, hs.light_tris);
+    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? MCPT_ERR_OOM : MCPT_ERR_HIP, std::string("scene upload: ") + hipGetErrorString(e));
+    gpu_build_ms = 0.0;
+    if (hs.builder >= 2) {  // the traversal tree is built on the device from the caller's triangles (csrc/mcpt_lbvh.hip)
+        const auto tb = Clock::now();
+        const int rc = build_device_tree(d_tris, d_sphere_obj, (int)hs.sphere_objects.size(), choice, g, meta);
+        if (rc != MCPT_OK) return rc;
+        gpu_build_ms = ms_since(tb);
+    }
+    if (traversal_stack_entries(meta.height) < meta.height - 1)  // whatever built the tree: a push beyond the stack (one entry per inner ancestor) would be dropped
+        return fail(MCPT_ERR_LIMIT, "the BVH is deeper than the traversal stack (kMaxBvhHeight)");
+    return MCPT_OK;
+}
+
+// DevScene and the geometry fields of mcpt_scene_info from the scene's arrays and sc->meta: after creation and after every update.
+void fill_view(mcpt_scene *sc) {
+    const SceneMeta &m = sc->meta;
+    const GeomBufs &g = sc->geom;
+    DevScene &v = sc->view;
+    v.nodes = g.nodes.p;
+    v.light_area_sum = m.light_area_sum;
+    v.qnodes = g.qnodes.p;  // nullptr: the float nodes are traversed
+    v.pnodes = nullptr;     // (set by the SMALL kernels to their LDS copy)
+    for (int k = 0; k < 3; ++k) {
+        v.q_origin[k] = m.q_origin[k];
+        v.q_cell[k] = m.q_cell[k];
+    }
+    v.tri_geom = g.tri_geom.p;
+    v.tri_shade = g.tri_shade.p;
+    v.spheres = g.spheres.p;
+    v.mats = sc->mats.p;
+    v.lights = g.lights.p;
+    v.light_nodes = g.light_nodes.p;
+    v.light_tris = g.light_tris.p;
+    v.inst = m.n_instances == 0 ? nullptr : sc->inst.p;
+    v.n_leaf_prims = m.n_leaf_prims;
+    v.env = sc->env.p;
+    for (int k = 0; k < 3; ++k) {
+        v.root_min[k] = m.root_min[k];
+        v.root_max[k] = m.root_max[k];
+        v.background[k] = m.background[k];
+    }
+    v.root = m.root;
+    v.n_tri = m.n_triangles;
+    v.n_lights = m.n_lights;
+    v.env_w = m.env_w;
+    v.env_h = m.env_h;
+    v.height = m.height;
+    for (int k = 0; k < 3; ++k) v.light_center[k] = m.light_center[k];
+    v.light_radius = m.light_radius;
+    {  // the half-space rule's margin (direct_is_zero): relative to every length whose rounding enters, scaled by the checking build's knob
+        const float k = kHalfspaceSlack * sc->knobs.halfspace_slack_scale;
+        const float c1 = std::fabs(m.light_center[0]) + std::fabs(m.light_center[1]) + std::fabs(m.light_center[2]);
+        v.light_plane[0] = m.light_radius + k * (c1 + m.light_radius);
+        v.light_plane[1] = k;
+    }
+    v.tir_bound_factor = 1.001f * sc->knobs.tir_bound_scale;
+    v.n_inner = m.n_inner;
+    v.n_sphere_slots = m.n_sphere_slots;
+    v.n_mats = m.n_mats;
+    v.n_light_nodes = m.n_light_nodes;
+    v.n_light_tris = m.n_light_tris;
+    // the LDS-resident flavour (SMALL kernels): everything the traversal and light sampling read fits the kSmall* limits
+    v.small = 0;
+#if !defined(MCPT_FORCE_RETRY) && !defined(MCPT_LDS_ONLY_STACKS)
+    if (sc->knobs.small_scene && !v.inst && v.root >= 0 && v.n_inner <= kSmallNodes && v.n_tri <= kSmallTris && v.n_sphere_slots <= kSmallSphereSlots &&
+        v.n_mats <= kSmallMats && v.n_lights <= kSmallLights && v.n_light_nodes <= kSmallLightNodes && v.n_light_tris <= kSmallLightTris &&
+        v.height - 1 <= kSmallStk)
+        v.small = 1;
+#endif
+    v.dbg = sc->dbg.p;
+    sc->info.builder = m.builder;
+    sc->info.quantised = g.qnodes.p ? 1 : 0;
+    sc->info.n_instances = m.n_instances;
+    sc->info.lds_resident = v.small;
+    sc->info.n_nodes = m.n_inner;
+    sc->info.bvh_height = m.height;
+    sc->info.n_lights = v.n_lights;
+    sc->info.n_prims = m.n_triangles + m.n_objects;
+    sc->info.scene_bytes = g.nodes.bytes() + g.qnodes.bytes() + g.tri_geom.bytes() + g.tri_shade.bytes() + g.spheres.bytes() + sc->mats.bytes() +
+                           g.lights.bytes() + g.light_nodes.bytes() + g.light_tris.bytes() + sc->inst.bytes() + sc->env.bytes() + sc->tris0.bytes() +
+                           g.tris.bytes() + sc->sphere_obj.bytes();
+}
+
+bool emits(const mcpt_material &m) {  // Material::hasEmission (Material.hpp:262), as build_host_scene decides it
+    const mv::V3 e = mv::ld(m.emission);
+    return sqrtf(mv::dot3(e, e)) > kEps;
+}
+
+}  // namespace
+
 // The device half of mcpt_scene_create: copies a flattened scene to `device` (and, for MCPT_BUILD_GPU_LBVH, builds the tree there).
 // mcpt_group_create builds the host scene ONCE and calls this from one thread per device.
 int mcpt::upload_scene(const mcpt_scene_desc *desc, HostBuild &hb, int device, mcpt_scene **out) {
@@ -99,129 +265,191 @@ int mcpt::upload_scene(const mcpt_scene_desc *desc, HostBuild &hb, int device, m
     }
     for (int q = 0; q < sc->n_pools && e == hipSuccess; ++q) e = sc->pools[q].readback.create();
     if (e == hipSuccess) e = sc->fork.create();
-    auto up = [&](auto &buf, const auto &vec) {
-        if (e == hipSuccess) e = upload(buf, vec);
-    };
-    if (hs.builder < 2) {
-        up(sc->nodes, hs.nodes);
-        if (!hs.qnodes.empty()) up(sc->qnodes, hs.qnodes);
+    // the creation-time description stays with the scene: mcpt_scene_update starts from it every time
+    SceneSource &S = sc->src;
+    S.choice = choice;
+    S.triangles.assign(desc->triangles, desc->triangles + (desc->triangles ? desc->n_triangles : 0));
+    S.objects.assign(desc->objects, desc->objects + desc->n_objects);
+    S.materials.assign(desc->materials, desc->materials + desc->n_materials);
+    S.moved.assign((size_t)desc->n_objects, 0);
+    S.xf.assign((size_t)desc->n_objects * 12, 0.f);
+    if (e == hipSuccess) e = upload(sc->mats, hs.materials);
+    if (e == hipSuccess) e = upload(sc->env, hs.env);
+    if (e == hipSuccess && !hs.instances.empty()) e = upload(sc->inst, hs.instances);
+    if (e == hipSuccess && hs.builder >= 2) {  // the device builders read the caller's triangles; they stay resident for the device path of an update
+        e = upload(sc->tris0, desc->triangles, (size_t)hs.n_triangles);
+        if (e == hipSuccess) e = upload(sc->sphere_obj, hs.sphere_objects);
     }
-    up(sc->tri_geom, hs.tri_geom);
-    up(sc->tri_shade, hs.tri_shade);
-    up(sc->spheres, hs.spheres);
-    up(sc->mats, hs.materials);
-    up(sc->lights, hs.lights);
-    up(sc->light_nodes, hs.light_nodes);
-    up(sc->light_tris, hs.light_tris);
-    up(sc->env, hs.env);
-    if (!hs.instances.empty()) up(sc->inst, hs.instances);
     if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? MCPT_ERR_OOM : MCPT_ERR_HIP, std::string("scene upload: ") + hipGetErrorString(e));
+    SceneMeta meta = meta_of(hs);
     double gpu_build_ms = 0.0;
-    if (hs.builder >= 2) {  // the traversal tree is built on the device from the caller's triangles (csrc/mcpt_lbvh.hip)
-        const auto tb = Clock::now();
-        const int n_sph = (int)hs.sphere_objects.size();
-        const int n_prim = hs.n_triangles + n_sph;
-        DevBuf<mcpt_triangle> d_tris;
-        DevBuf<int32_t> d_sph;
-        e = upload(d_tris, desc->triangles, (size_t)hs.n_triangles);
-        if (e == hipSuccess) e = upload(d_sph, hs.sphere_objects);
-        if (e == hipSuccess) e = sc->nodes.alloc((size_t)n_prim - 1);
-        if (e == hipSuccess) e = sc->qnodes.alloc((size_t)n_prim - 1);
-        LbvhResult R;
-        if (e == hipSuccess) e = build_lbvh_device(d_tris.p, hs.n_triangles, d_sph.p, sc->spheres.p, n_sph, choice.quantise, hs.builder == 3 ? 1 : 0, choice.ploc_radius, choice.ploc_top,
-                                                 sc->nodes.p, sc->qnodes.p, &R, nullptr);
-        if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? MCPT_ERR_OOM : MCPT_ERR_HIP, std::string("GPU BVH build: ") + hipGetErrorString(e));
-        if (R.height > kMaxBvhHeight) return fail(MCPT_ERR_LIMIT, "the GPU-built BVH is deeper than the traversal stack (kMaxBvhHeight); use MCPT_BUILD_SAH");
-        hs.root = R.root;
-        hs.height = R.height;
-        for (int k = 0; k < 3; ++k) {
-            hs.root_min[k] = R.root_min[k];
-            hs.root_max[k] = R.root_max[k];
-            hs.q_origin[k] = R.q_origin[k];
-            hs.q_cell[k] = R.q_cell[k];
-        }
-        if (!R.quantised) sc->qnodes.release();
-        sc->n_inner = R.n_nodes;
-        gpu_build_ms = ms_since(tb);
-    } else {
-        sc->n_inner = hs.root < 0 ? 0 : (int32_t)hs.nodes.size();
-    }
-    if (traversal_stack_entries(hs.height) < hs.height - 1)  // whatever built the tree: a push beyond the stack (one entry per inner ancestor) would be dropped
-        return fail(MCPT_ERR_LIMIT, "the BVH is deeper than the traversal stack (kMaxBvhHeight)");
-    DevScene &v = sc->view;
-    v.nodes = sc->nodes.p;
-    v.light_area_sum = hs.light_area_sum;
-    v.qnodes = sc->qnodes.p;  // nullptr: the float nodes are traversed
-    v.pnodes = nullptr;       // (set by the SMALL kernels to their LDS copy)
-    for (int k = 0; k < 3; ++k) {
-        v.q_origin[k] = hs.q_origin[k];
-        v.q_cell[k] = hs.q_cell[k];
-    }
-    v.tri_geom = sc->tri_geom.p;
-    v.tri_shade = sc->tri_shade.p;
-    v.spheres = sc->spheres.p;
-    v.mats = sc->mats.p;
-    v.lights = sc->lights.p;
-    v.light_nodes = sc->light_nodes.p;
-    v.light_tris = sc->light_tris.p;
-    v.inst = hs.instances.empty() ? nullptr : sc->inst.p;
-    v.n_leaf_prims = hs.n_leaf_prims;
-    v.env = sc->env.p;
-    for (int k = 0; k < 3; ++k) {
-        v.root_min[k] = hs.root_min[k];
-        v.root_max[k] = hs.root_max[k];
-        v.background[k] = hs.background[k];
-    }
-    v.root = hs.root;
-    v.n_tri = hs.n_triangles;
-    v.n_lights = (int32_t)hs.lights.size();
-    v.env_w = hs.env_w;
-    v.env_h = hs.env_h;
-    v.height = hs.height;
-    for (int k = 0; k < 3; ++k) v.light_center[k] = hs.light_center[k];
-    v.light_radius = hs.light_radius;
-    {  // the half-space rule's margin (direct_is_zero): relative to every length whose rounding enters, scaled by the checking build's knob
-        const float k = kHalfspaceSlack * sc->knobs.halfspace_slack_scale;
-        const float c1 = std::fabs(hs.light_center[0]) + std::fabs(hs.light_center[1]) + std::fabs(hs.light_center[2]);
-        v.light_plane[0] = hs.light_radius + k * (c1 + hs.light_radius);
-        v.light_plane[1] = k;
-    }
-    v.tir_bound_factor = 1.001f * sc->knobs.tir_bound_scale;
-    v.n_inner = sc->n_inner;
-    v.n_sphere_slots = (int32_t)hs.spheres.size();
-    v.n_mats = (int32_t)hs.materials.size();
-    v.n_light_nodes = (int32_t)hs.light_nodes.size();
-    v.n_light_tris = (int32_t)hs.light_tris.size();
-    // the LDS-resident flavour (SMALL kernels): everything the traversal and light sampling read fits the kSmall* limits
-    v.small = 0;
-#if !defined(MCPT_FORCE_RETRY) && !defined(MCPT_LDS_ONLY_STACKS)
-    if (sc->knobs.small_scene && !v.inst && v.root >= 0 && v.n_inner <= kSmallNodes && v.n_tri <= kSmallTris && v.n_sphere_slots <= kSmallSphereSlots &&
-        v.n_mats <= kSmallMats && v.n_lights <= kSmallLights && v.n_light_nodes <= kSmallLightNodes && v.n_light_tris <= kSmallLightTris &&
-        v.height - 1 <= kSmallStk)
-        v.small = 1;
-#endif
-    v.dbg = nullptr;
+    const int rc = upload_geometry(hs, choice, sc->tris0.p, sc->sphere_obj.p, sc->geom, meta, gpu_build_ms);
+    if (rc != MCPT_OK) return rc;
+    sc->meta = meta;
 #if defined(MCPT_TRAVERSAL_STATS) || defined(MCPT_CHECK_DIRECT_SKIP)
     if (sc->dbg.alloc(36) == hipSuccess) {  // (16 reported by mcpt_debug_counters; the statistics build prints the rest at destruction)
         (void)hipMemset(sc->dbg.p, 0, 36 * sizeof(unsigned long long));
-        v.dbg = sc->dbg.p;
+    } else {
+        sc->dbg.release();
     }
 #endif
+    fill_view(sc.get());
     sc->info.build_ms = hb.build_ms + gpu_build_ms;
     sc->info.init_ms = hb.init_ms;
     sc->info.upload_ms = ms_since(t_upload) - gpu_build_ms;
-    sc->info.builder = hs.builder;
-    sc->info.quantised = sc->qnodes.p ? 1 : 0;
-    sc->info.n_instances = (int32_t)hs.instances.size();
-    sc->info.lds_resident = v.small;
-    sc->info.n_nodes = sc->n_inner;
-    sc->info.bvh_height = hs.height;
-    sc->info.n_lights = v.n_lights;
-    sc->info.n_prims = hs.n_triangles + hs.n_objects;
-    sc->info.scene_bytes = sc->nodes.bytes() + sc->qnodes.bytes() + sc->tri_geom.bytes() + sc->tri_shade.bytes() + sc->spheres.bytes() +
-                           sc->mats.bytes() + sc->lights.bytes() + sc->light_nodes.bytes() + sc->light_tris.bytes() + sc->inst.bytes() +
-                           sc->env.bytes();
     *out = sc.release();
+    return MCPT_OK;
+}
+
+int mcpt::check_moves(const mcpt_scene *sc, int32_t n, const mcpt_object_transform *moves, std::vector<uint8_t> &moved, std::vector<float> &xf,
+                      std::vector<int32_t> &touched) {
+    if (n < 0) return fail(MCPT_ERR_ARG, "mcpt_scene_update: n < 0");
+    if (n > 0 && !moves) return fail(MCPT_ERR_ARG, "mcpt_scene_update: null moves");
+    for (int32_t i = 0; i < n; ++i)
+        for (int k = 0; k < 12; ++k)
+            if (!std::isfinite(moves[i].m[k])) return fail(MCPT_ERR_ARG, "mcpt_scene_update: move " + std::to_string(i) + ": a matrix entry is not finite");
+    for (int32_t i = 0; i < n; ++i)
+        for (int32_t j = 0; j < i; ++j)
+            if (moves[i].object == moves[j].object) return fail(MCPT_ERR_ARG, "mcpt_scene_update: object " + std::to_string(moves[i].object) + " is listed twice");
+    if (!sc) return fail(MCPT_ERR_ARG, "mcpt_scene_update: null scene");
+    const SceneSource &S = sc->src;
+    for (int32_t i = 0; i < n; ++i)
+        if (moves[i].object < 0 || moves[i].object >= (int32_t)S.objects.size())
+            return fail(MCPT_ERR_ARG, "mcpt_scene_update: object index " + std::to_string(moves[i].object) + " out of range");
+    if (S.choice.builder == MCPT_BUILD_SAH && S.choice.instancing == 1)
+        return fail(MCPT_ERR_ARG, "mcpt_scene_update: the scene was built with node instancing on (instanced subtrees are shared between objects)");
+    moved = S.moved;
+    xf = S.xf;
+    touched.clear();
+    for (int32_t i = 0; i < n; ++i) {
+        const int32_t o = moves[i].object;
+        moved[(size_t)o] = 1;
+        std::memcpy(&xf[(size_t)o * 12], moves[i].m, 12 * sizeof(float));
+        touched.push_back(o);
+    }
+    return MCPT_OK;
+}
+
+int mcpt::apply_transforms(mcpt_scene *sc, const std::vector<uint8_t> &moved, const std::vector<float> &xf, const std::vector<int32_t> &touched,
+                           mcpt_update_info *info) {
+    const auto t0 = Clock::now();
+    mcpt_update_info ui;
+    std::memset(&ui, 0, sizeof ui);
+    SceneSource &S = sc->src;
+    bool emitter = false;
+    for (int32_t o : touched) {
+        const mcpt_object &ob = S.objects[(size_t)o];
+        if (ob.kind == MCPT_OBJ_MESH) ui.n_moved_tris += ob.n_tri;
+        emitter = emitter || emits(S.materials[(size_t)ob.material]);
+    }
+    if (touched.empty()) {
+        if (info) *info = ui;
+        return MCPT_OK;
+    }
+    HIP_TRY(hipSetDevice(sc->device));
+    GeomBufs g2;  // built aside; swapped in once the new tree is known to be usable
+    SceneMeta meta = sc->meta;
+    const size_t nt = (size_t)meta.n_triangles;
+    if (meta.builder >= 2 && !emitter) {
+        // ---- device path: the listed triangles and sphere centres are moved in HBM, the device builder runs again
+        ui.path = 1;
+        const auto tu = Clock::now();
+        HIP_TRY(g2.tri_geom.alloc(nt));
+        HIP_TRY(g2.tri_shade.alloc(nt));
+        HIP_TRY(g2.tris.alloc(nt));
+        HIP_TRY(g2.spheres.alloc(sc->geom.spheres.n));
+        if (nt) {
+            HIP_TRY(hipMemcpyAsync(g2.tri_geom.p, sc->geom.tri_geom.p, nt * sizeof(TriGeom), hipMemcpyDeviceToDevice, nullptr));
+            HIP_TRY(hipMemcpyAsync(g2.tri_shade.p, sc->geom.tri_shade.p, nt * sizeof(TriShade), hipMemcpyDeviceToDevice, nullptr));
+            HIP_TRY(hipMemcpyAsync(g2.tris.p, sc->geom.tris.p ? sc->geom.tris.p : sc->tris0.p, nt * sizeof(mcpt_triangle), hipMemcpyDeviceToDevice, nullptr));
+        }
+        if (sc->geom.spheres.n)
+            HIP_TRY(hipMemcpyAsync(g2.spheres.p, sc->geom.spheres.p, sc->geom.spheres.bytes(), hipMemcpyDeviceToDevice, nullptr));
+        HIP_TRY(hipStreamSynchronize(nullptr));
+        ui.upload_ms = ms_since(tu);
+        const auto tt = Clock::now();
+        std::vector<MoveSeg> segs;
+        int32_t lanes = 0;
+        for (int32_t o : touched) {
+            const mcpt_object &ob = S.objects[(size_t)o];
+            MoveSeg sg;
+            std::memset(&sg, 0, sizeof sg);
+            sg.first_lane = lanes;
+            sg.count = ob.kind == MCPT_OBJ_MESH ? ob.n_tri : 1;
+            sg.first_tri = ob.kind == MCPT_OBJ_MESH ? ob.first_tri : -1;
+            sg.object = o;
+            std::memcpy(sg.m, &xf[(size_t)o * 12], sizeof sg.m);
+            for (int k = 0; k < 3; ++k) sg.c0[k] = ob.center[k];
+            sg.raw = moved[(size_t)o] ? 0 : 1;
+            lanes += sg.count;
+            segs.push_back(sg);
+        }
+        HIP_TRY(upload(sc->segs, segs));
+        launch_move_objects(sc->segs.p, (int32_t)segs.size(), lanes, sc->tris0.p, g2.tris.p, g2.tri_geom.p, g2.tri_shade.p, g2.spheres.p, nullptr);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(nullptr));
+        ui.transform_ms = ms_since(tt);
+        const auto tb = Clock::now();
+        int rc = build_device_tree(g2.tris.p, sc->sphere_obj.p, (int)sc->sphere_obj.n, S.choice, g2, meta);
+        if (rc == MCPT_OK && traversal_stack_entries(meta.height) < meta.height - 1)
+            rc = fail(MCPT_ERR_LIMIT, "the BVH is deeper than the traversal stack (kMaxBvhHeight)");
+        if (rc != MCPT_OK) return rc;
+        ui.build_ms = ms_since(tb);
+        sc->geom.swap_prims(g2);
+    } else {
+        // ---- host path: desc' is flattened and its tree built as at creation; every array that depends on the geometry is copied again
+        ui.path = 0;
+        const auto tt = Clock::now();
+        std::vector<mcpt_triangle> tris = S.triangles;
+        std::vector<mcpt_object> objs = S.objects;
+        for (size_t o = 0; o < objs.size(); ++o) {
+            if (!moved[o]) continue;
+            const float *m = &xf[o * 12];
+            if (objs[o].kind == MCPT_OBJ_MESH) {
+                for (int32_t k = 0; k < objs[o].n_tri; ++k) mv::move_triangle(m, tris[(size_t)objs[o].first_tri + k], tris[(size_t)objs[o].first_tri + k]);
+            } else {
+                const mv::V3 c = mv::move_point(m, mv::ld(objs[o].center));
+                objs[o].center[0] = c.x;
+                objs[o].center[1] = c.y;
+                objs[o].center[2] = c.z;
+            }
+        }
+        ui.transform_ms = ms_since(tt);
+        const auto tb = Clock::now();
+        mcpt_scene_desc d;
+        std::memset(&d, 0, sizeof d);
+        d.n_objects = (int32_t)objs.size();
+        d.n_triangles = (int32_t)tris.size();
+        d.n_materials = (int32_t)S.materials.size();
+        for (int k = 0; k < 3; ++k) d.background[k] = meta.background[k];
+        d.objects = objs.data();
+        d.triangles = tris.data();
+        d.materials = S.materials.data();
+        HostScene hs;
+        const char *err = "";
+        int rc = build_host_scene(d, hs, &err, S.choice);
+        if (rc != MCPT_OK) return fail(rc, std::string("mcpt_scene_update: ") + err);
+        const double host_build_ms = ms_since(tb);
+        const auto tu = Clock::now();
+        const int32_t env_w = meta.env_w, env_h = meta.env_h;  // (the environment map is not part of desc': it stays where it is)
+        meta = meta_of(hs);
+        meta.env_w = env_w;
+        meta.env_h = env_h;
+        if (hs.builder >= 2) HIP_TRY(upload(g2.tris, tris));
+        double gpu_build_ms = 0.0;
+        rc = upload_geometry(hs, S.choice, g2.tris.p, sc->sphere_obj.p, g2, meta, gpu_build_ms);
+        if (rc != MCPT_OK) return rc;
+        ui.build_ms = host_build_ms + gpu_build_ms;
+        ui.upload_ms = ms_since(tu) - gpu_build_ms;
+        sc->geom.swap_prims(g2);
+        sc->geom.swap_lights(g2);
+    }
+    sc->meta = meta;
+    S.moved = moved;
+    S.xf = xf;
+    fill_view(sc);
+    ui.total_ms = ms_since(t0);
+    if (info) *info = ui;
     return MCPT_OK;
 }
 
@@ -279,6 +507,15 @@ int mcpt_scene_create_ex(const mcpt_scene_desc *desc, int device, const mcpt_bui
     if (rc != MCPT_OK) return rc;
     hb.init_ms = init_ms;
     return upload_scene(desc, hb, device, out);
+}
+
+int mcpt_scene_update(mcpt_scene *sc, int32_t n, const mcpt_object_transform *moves, mcpt_update_info *info) {
+    std::vector<uint8_t> moved;
+    std::vector<float> xf;
+    std::vector<int32_t> touched;
+    const int rc = check_moves(sc, n, moves, moved, xf, touched);
+    if (rc != MCPT_OK) return rc;
+    return apply_transforms(sc, moved, xf, touched, info);
 }
 
 void mcpt_scene_destroy(mcpt_scene *sc) {
@@ -354,7 +591,7 @@ int mcpt_scene_dump_bvh(mcpt_scene *sc, mcpt_bvh_info *info, float *boxes, int32
     HIP_TRY(hipSetDevice(sc->device));
     std::memset(info, 0, sizeof *info);
     const DevScene &v = sc->view;
-    info->n_nodes = sc->n_inner;
+    info->n_nodes = sc->meta.n_inner;
     info->root = v.root;
     info->stack_entries = v.height;
     info->quantised = v.qnodes ? 1 : 0;
@@ -377,11 +614,11 @@ int mcpt_scene_dump_bvh(mcpt_scene *sc, mcpt_bvh_info *info, float *boxes, int32
     }
     if (!boxes || !children || info->n_nodes == 0) return MCPT_OK;
     std::vector<Node> nodes((size_t)info->n_nodes);
-    HIP_TRY(download(nodes.data(), sc->nodes, nodes.size()));
+    HIP_TRY(download(nodes.data(), sc->geom.nodes, nodes.size()));
     std::vector<QNode> qn;
     if (qboxes && info->quantised) {
         qn.resize(nodes.size());
-        HIP_TRY(download(qn.data(), sc->qnodes, qn.size()));
+        HIP_TRY(download(qn.data(), sc->geom.qnodes, qn.size()));
     }
     export_nodes(info->n_nodes, nodes.data(), qn.empty() ? nullptr : qn.data(), boxes, children, qboxes);
     return MCPT_OK;

@@ -18,6 +18,7 @@ CHECK_LIB_PATH = os.path.join(HERE, "libmcpt_hip_check.so")  # the checking buil
 EXPORTS = ["mcpt_scene_create", "mcpt_scene_destroy", "mcpt_render", "mcpt_render_device", "mcpt_render_adaptive", "mcpt_render_aovs",
            "mcpt_render_aovs_ex", "mcpt_denoise", "mcpt_render_denoised", "mcpt_intersect",
            "mcpt_cast_rays", "mcpt_camera_rays", "mcpt_scene_get_info", "mcpt_bvh_dump", "mcpt_scene_create_ex", "mcpt_scene_dump_bvh", "mcpt_tonemap", "mcpt_tonemap_device", "mcpt_debug_fmath", "mcpt_debug_material", "mcpt_debug_scene", "mcpt_debug_counters",
+           "mcpt_scene_update", "mcpt_group_update", "mcpt_transform_triangles",
            "mcpt_group_create", "mcpt_group_render", "mcpt_group_size", "mcpt_group_get_info", "mcpt_group_scene", "mcpt_group_destroy", "mcpt_group_last_error",
            "mcpt_last_error", "mcpt_version"]
 
@@ -102,6 +103,31 @@ class GroupInfo(C.Structure):
                 ("init_ms_max", C.c_double), ("setup_ms", C.c_double)]
 
 
+class ObjectTransform(C.Structure):
+    _fields_ = [("object", C.c_int32), ("m", C.c_float * 12)]
+
+
+class UpdateInfo(C.Structure):
+    _fields_ = [("path", C.c_int32), ("n_moved_tris", C.c_int32), ("transform_ms", C.c_double), ("build_ms", C.c_double),
+                ("upload_ms", C.c_double), ("total_ms", C.c_double), ("reserved", C.c_int32 * 4)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
+def _moves(moves):
+    """An iterable of (object index, 3x4 array) as an array of mcpt_object_transform."""
+    moves = list(moves)
+    arr = (ObjectTransform * max(len(moves), 1))()
+    for k, (obj, m) in enumerate(moves):
+        m = np.asarray(m, dtype=np.float32)
+        if m.shape != (3, 4):
+            raise ValueError("a transform is a 3x4 array, not %s" % (m.shape,))
+        arr[k].object = int(obj)
+        arr[k].m = (C.c_float * 12)(*[float(x) for x in m.reshape(-1)])
+    return arr, len(moves)
+
+
 _libs = {}
 
 
@@ -158,6 +184,12 @@ def lib(path=None):
         L.mcpt_debug_scene.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p]
         L.mcpt_debug_material.restype = C.c_int
         L.mcpt_debug_material.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.mcpt_scene_update.restype = C.c_int
+        L.mcpt_scene_update.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(UpdateInfo)]
+        L.mcpt_group_update.restype = C.c_int
+        L.mcpt_group_update.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+        L.mcpt_transform_triangles.restype = C.c_int
+        L.mcpt_transform_triangles.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
         L.mcpt_group_create.restype = C.c_int
         L.mcpt_group_create.argtypes = [C.POINTER(SceneDesc), C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]
         L.mcpt_group_render.restype = C.c_int
@@ -207,6 +239,22 @@ def _make_desc(sd, keep):
         d.env_h, d.env_w = env.shape[:2]
         d.env_pixels = _ptr(env)
     return d
+
+
+def transform_triangles(m, tris, out=None):
+    """mcpt_transform_triangles (host only): the triangles (scenes.TRI_DTYPE) with every vertex moved by the row-major 3x4 matrix m under the
+    rule of mcpt_scene_update; the texture coordinates are copied.  out: the array to write (may be `tris` itself); default a new one."""
+    m = np.ascontiguousarray(m, dtype=np.float32).reshape(-1)
+    if m.size != 12:
+        raise ValueError("a transform is a 3x4 array")
+    if not tris.flags["C_CONTIGUOUS"]:
+        tris = np.ascontiguousarray(tris)
+    if out is None:
+        out = np.empty_like(tris)
+    if out.dtype != tris.dtype or out.shape != tris.shape or not out.flags["C_CONTIGUOUS"] or tris.dtype.itemsize != 60:
+        raise ValueError("transform_triangles: arrays of 60-byte triangles with one shape")
+    _check(lib().mcpt_transform_triangles(_ptr(m), tris.size, _ptr(tris), _ptr(out)))
+    return out
 
 
 def bvh_dump(sd):
@@ -260,6 +308,14 @@ class HipScene:
         shift, root_first = np.zeros((info.n_instances, 3), np.float32), np.zeros((info.n_instances, 2), np.int32)
         _check(self.L.mcpt_scene_dump_bvh(self.h, C.byref(info), _ptr(boxes), _ptr(children), _ptr(qboxes), _ptr(shift), _ptr(root_first)), L=self.L)
         return _bvh_info_dict(info, shift, root_first), boxes, children, (qboxes if info.quantised else None)
+
+    def update(self, moves):
+        """mcpt_scene_update: moves = an iterable of (object index, 3x4 array), absolute transforms of the creation-time geometry.  Afterwards
+        the scene behaves like one created from the moved description with the same build options.  Returns mcpt_update_info as a dict."""
+        arr, n = _moves(moves)
+        info = UpdateInfo()
+        _check(self.L.mcpt_scene_update(self.h, n, C.cast(arr, C.c_void_p), C.byref(info)), L=self.L)
+        return info.as_dict()
 
     def close(self):
         if getattr(self, "h", None):
@@ -463,6 +519,13 @@ class HipGroup:
             self.close()
         except Exception:
             pass
+
+    def update(self, moves):
+        """mcpt_group_update: HipScene.update on every replica."""
+        arr, n = _moves(moves)
+        rc = self.L.mcpt_group_update(self.h, n, C.cast(arr, C.c_void_p))
+        if rc != 0:
+            raise McptError(rc, self.L.mcpt_group_last_error().decode("utf-8", "replace"))
 
     def info(self):
         i = GroupInfo()

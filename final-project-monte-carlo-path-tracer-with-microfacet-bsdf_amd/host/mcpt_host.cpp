@@ -183,6 +183,7 @@ void Scene::buildBVH() {
         if (mcpt_group_get_info(group, &gi) == MCPT_OK)
             std::cout << "[mcpt] scene set-up on " << gi.n_devices << " GPU replicas: " << gi.setup_ms << " ms (tree built once: " << gi.build_ms
                       << " ms; slowest upload " << gi.upload_ms_max << " ms; device start-up " << gi.init_ms_max << " ms beside the build)" << std::endl;
+        allTransformsPending();
         return;
     }
     if (mcpt_scene_create(&d, devices.empty() ? -1 : devices[0], &gpu) != MCPT_OK) std::cerr << "mcpt: " << mcpt_last_error() << std::endl;
@@ -190,6 +191,60 @@ void Scene::buildBVH() {
     if (gpu && mcpt_scene_get_info(gpu, &si) == MCPT_OK)
         std::cout << "[mcpt] scene set-up: build " << si.build_ms << " ms, upload " << si.upload_ms << " ms, device start-up " << si.init_ms
                   << " ms beside the build" << std::endl;
+    allTransformsPending();
+}
+
+void Scene::allTransformsPending() {  // a fresh scene holds the geometry as it was added: every transform set so far is still to be applied
+    pendingTransforms.clear();
+    for (const auto &kv : objectTransforms) pendingTransforms.push_back(kv.first);
+    applyTransforms();
+}
+
+void Scene::setTransform(Object *object, const float m[12]) {
+    std::array<float, 12> a;
+    for (int k = 0; k < 12; ++k) a[k] = m[k];
+    objectTransforms[object] = a;
+    if (!gpu && !group) return;  // buildBVH applies it
+    for (const Object *o : pendingTransforms)
+        if (o == object) return;
+    pendingTransforms.push_back(object);
+}
+
+std::vector<mcpt_object_transform> Scene::transforms() const {
+    std::vector<mcpt_object_transform> out;
+    for (size_t i = 0; i < objects.size(); ++i) {
+        const auto it = objectTransforms.find(objects[i]);
+        if (it == objectTransforms.end()) continue;
+        mcpt_object_transform t{};
+        t.object = (int32_t)i;
+        for (int k = 0; k < 12; ++k) t.m[k] = it->second[k];
+        out.push_back(t);
+    }
+    return out;
+}
+
+void Scene::applyTransforms() const {
+    if (pendingTransforms.empty() || (!gpu && !group)) return;
+    std::vector<mcpt_object_transform> moves;
+    for (const mcpt_object_transform &t : transforms())
+        for (const Object *o : pendingTransforms)
+            if (o == objects[(size_t)t.object]) {
+                moves.push_back(t);
+                break;
+            }
+    pendingTransforms.clear();
+    if (moves.empty()) return;
+    if (group) {
+        if (mcpt_group_update(group, (int32_t)moves.size(), moves.data()) != MCPT_OK) std::cerr << "mcpt: " << mcpt_group_last_error() << std::endl;
+        return;
+    }
+    mcpt_update_info ui{};
+    if (mcpt_scene_update(gpu, (int32_t)moves.size(), moves.data(), &ui) != MCPT_OK) {
+        std::cerr << "mcpt: " << mcpt_last_error() << std::endl;
+        return;
+    }
+    std::cout << "[mcpt] scene update (" << (ui.path ? "device" : "host") << " path): " << moves.size() << " objects, " << ui.n_moved_tris
+              << " triangles, " << ui.total_ms << " ms (tree " << ui.build_ms << " ms)" << std::endl;
 }
 
 mcpt_params Scene::params(int spp) const {
@@ -222,7 +277,7 @@ mcpt_camera Scene::cameraDesc() const {
 
 Intersection Scene::intersect(const Ray &ray) const {
     Intersection r;
-    if (!gpu) return r;
+    if (!handle() || !gpu) return r;  // (handle(): a pending setTransform takes effect first)
     int32_t prim = -1;
     double t = r.distance;
     if (mcpt_intersect(gpu, 1, ray.origin.data(), ray.direction.data(), &t, &prim) == MCPT_OK) {
@@ -234,7 +289,7 @@ Intersection Scene::intersect(const Ray &ray) const {
 }
 
 float Scene::castRay(const Ray &ray, int depth, const WaveLenType &wavelen) const {
-    if (!gpu || depth != 0) return 0.f;
+    if (!handle() || !gpu || depth != 0) return 0.f;
     const mcpt_params p = params(1);
     const uint32_t zero = 0;
     const int32_t ch = (int32_t)wavelen;
@@ -277,6 +332,9 @@ uint32_t scene_hash(const Scene &scene) {
     h = fnv1a(objs.data(), objs.size() * sizeof(mcpt_object), h);
     h = fnv1a(&c, sizeof c, h);
     h = fnv1a(scene.backgroundColor.data(), 3 * sizeof(float), h);
+    // where the objects are now (Scene::setTransform): a resume after a move is refused like any other change of the scene
+    const std::vector<mcpt_object_transform> xf = scene.transforms();
+    if (!xf.empty()) h = fnv1a(xf.data(), xf.size() * sizeof(mcpt_object_transform), h);
     return h;
 }
 

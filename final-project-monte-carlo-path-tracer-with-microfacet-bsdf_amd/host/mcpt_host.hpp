@@ -6,7 +6,9 @@
 // MeshTriangle(filename, material, translation, zoom), Sphere(center, radius, material), Camera::lookAt) so that code
 // written against the reference compiles against this header; everything that is hot runs in libmcpt_hip.so.
 #pragma once
+#include <array>
 #include <cmath>
+#include <map>
 #include <memory>
 #include <string>
 #include <vector>
@@ -220,12 +222,25 @@ class Scene {
     Intersection intersect(const Ray &ray) const;                                // Scene.cpp:19-21
     float castRay(const Ray &ray, int depth, const WaveLenType &wavelen) const;  // Scene.cpp:85-184 (depth must be 0)
 
+    // Moves an object of a live scene: m is a row-major 3x4 matrix applied to the object's geometry AS IT WAS ADDED (transforms are
+    // absolute, mcpt_scene_update).  It takes effect at the next buildBVH(), or, when the scene is already built, at the next render,
+    // intersect or castRay (mcpt_scene_update / mcpt_group_update: the tree is rebuilt, the handle and its workspaces stay).
+    void setTransform(Object *object, const float m[12]);
+    // the transforms set so far, in Scene::Add order (object = index into `objects`); objects that are not in the scene are left out
+    std::vector<mcpt_object_transform> transforms() const;
+
     // used by Renderer
-    mcpt_scene *handle() const { return group ? mcpt_group_scene(group, 0) : gpu; }  // (with several GPUs: the replica on the first one)
+    mcpt_scene *handle() const {  // (with several GPUs: the replica on the first one)
+        applyTransforms();
+        return group ? mcpt_group_scene(group, 0) : gpu;
+    }
     // More than one entry: the frame is rendered by all listed GPUs (mcpt_group_*: tile partition + RCCL merge inside the
     // library; main() stays single-threaded).  Call before buildBVH.  {0, 0} rehearses the schedule on one GPU.
     void setDevices(const std::vector<int> &d) { devices = d; }
-    mcpt_group *groupHandle() const { return group; }
+    mcpt_group *groupHandle() const {
+        applyTransforms();
+        return group;
+    }
     mcpt_params params(int spp) const;
     mcpt_camera cameraDesc() const;
     // flat description (also used by the tests to compare with the Python assembly)
@@ -238,6 +253,10 @@ class Scene {
     mcpt_scene *gpu = nullptr;
     mcpt_group *group = nullptr;
     std::vector<int> devices;
+    void allTransformsPending();
+    void applyTransforms() const;  // sends the transforms set since the last call to the live scene
+    std::map<const Object *, std::array<float, 12>> objectTransforms;
+    mutable std::vector<const Object *> pendingTransforms;
 };
 
 // ============================================================================ renderer

@@ -152,6 +152,49 @@ typedef struct {
 enum { MCPT_INSTANCING_AUTO = 0, MCPT_INSTANCING_OFF = 1, MCPT_INSTANCING_ON = 2 };
 int mcpt_scene_create_ex(const mcpt_scene_desc *desc, int device, const mcpt_build_options *options, mcpt_scene **out);
 
+/* ---- Moving objects in a live scene.  The reference has no counterpart: its Scene is assembled once.
+ *
+ * mcpt_scene_update gives the listed objects a transform and rebuilds the traversal tree with the scene's own builder (never a refit).
+ *   Point transform, in float, no contraction (m row-major 3x4):
+ *       p'[r] = (m[4r]*p.x + (m[4r+1]*p.y + m[4r+2]*p.z)) + m[4r+3]            (the 3-term dot order, then the translation)
+ *   Meshes   every stored vertex of the object's triangles is transformed, the texture coordinates are kept.  Any finite affine map is
+ *            allowed: edges, normals and areas are derived from the moved vertices exactly as at creation (a reflection flips the
+ *            normals, as it would in a fresh scene).
+ *   Spheres  the centre is transformed, the radius is kept: the linear part acts on the centre only, spheres are not scaled.
+ *   Transforms are ABSOLUTE: they apply to the geometry the scene was created with and never accumulate.  An object listed in a call
+ *   gets that transform; an object not listed keeps the one it had; an object that never got one keeps its stored vertices bit for bit
+ *   (no identity is applied: -0 + 0 would change a sign bit).
+ * THE CONTRACT: after the call every entry point that takes the scene gives what it gives on
+ *       mcpt_scene_create_ex(desc', device, the same options)
+ * where desc' is the creation description with the current transforms applied by the rule above (what mcpt_transform_triangles
+ * computes): mcpt_render*, mcpt_intersect, mcpt_cast_rays, mcpt_render_aovs*, mcpt_render_denoised, mcpt_scene_dump_bvh,
+ * mcpt_debug_scene, and mcpt_scene_get_info in n_nodes, bvh_height, quantised, lds_resident, n_lights and n_prims.  With the host
+ * builders (MCPT_BUILD_SAH, MCPT_BUILD_REFERENCE) bit for bit, the tree dump included; with the device builders as far as two builds
+ * on the device agree: primitive ids equal ray for ray, a frame within a few values of a box-grazing ray.
+ * The handle, its streams and events and the wavefront workspaces survive; no workspace is reallocated because of an update.
+ *   info->path 0  host: desc' is flattened and its tree built as at creation, the geometry-derived arrays are copied to the device again
+ *                 (every host-built scene; a device-built scene when a listed object emits light: the light tables are host-built)
+ *   info->path 1  device: a kernel moves the listed triangles and sphere centres in HBM from the resident creation-time triangles and
+ *                 the device builder runs again; only the matrices cross the bus
+ * MCPT_ERR_ARG, before any device call: n < 0; n > 0 with moves == NULL; a matrix entry that is not finite; an object listed twice in
+ * one call; scene == NULL; an object index out of range; a scene built with node instancing on (instanced subtrees are shared between
+ * objects).  n == 0 is a valid no-op.  A failed rebuild (MCPT_ERR_LIMIT: the new tree is deeper than the traversal stack;
+ * MCPT_ERR_OOM) leaves the scene exactly as it was before the call: the new arrays are built aside and swapped in on success. */
+typedef struct { int32_t object; float m[12]; } mcpt_object_transform; /* 52 bytes; m row-major 3x4 */
+typedef struct {
+    int32_t path;         /* 0: host rebuild + re-upload, 1: device transform + device rebuild */
+    int32_t n_moved_tris; /* triangles of the listed meshes */
+    double transform_ms;  /* path 0: forming desc' on the host; path 1: the segment table's copy and the transform kernel */
+    double build_ms;      /* flattening + tree build (host and device parts) */
+    double upload_ms;     /* path 0: host -> HBM copies; path 1: the device-to-device copies into the new arrays */
+    double total_ms;      /* wall time of the call */
+    int32_t reserved[4];
+} mcpt_update_info; /* 56 bytes */
+int mcpt_scene_update(mcpt_scene *scene, int32_t n, const mcpt_object_transform *moves, mcpt_update_info *info /* nullable */);
+/* Host only, no GPU needed: out[i] = in[i] with its three vertices moved by the point transform above (uv copied); in == out allowed.
+ * MCPT_ERR_ARG for m == NULL, a matrix entry that is not finite, n < 0, or n > 0 with a null array. */
+int mcpt_transform_triangles(const float m[12], int64_t n, const mcpt_triangle *in, mcpt_triangle *out);
+
 /* Replaces the pixel/spp loop of Renderer::Render (Renderer.cpp:21-91): fb_host = W*H*3 floats,
  * row-major m = j*W + i, linear radiance averaged over spp -- what `framebuffer` holds at Renderer.cpp:91.
  * Blocking.  Tone map and PNG output (Renderer.cpp:95-109) stay with the caller. */
@@ -330,6 +373,9 @@ int mcpt_group_get_info(const mcpt_group *group, mcpt_group_info *info);
 /* The replica on the index-th device of the group (borrowed: it lives as long as the group), for calls that take a scene, e.g.
  * mcpt_tonemap after mcpt_group_render.  NULL when out of range. */
 mcpt_scene *mcpt_group_scene(mcpt_group *group, int index);
+/* mcpt_scene_update on every replica (one host thread per replica), with the same checks before any device call.  If a replica fails,
+ * the replicas that had succeeded are given their previous transforms back, so that the group stays one scene. */
+int mcpt_group_update(mcpt_group *group, int32_t n, const mcpt_object_transform *moves);
 void mcpt_group_destroy(mcpt_group *group);
 const char *mcpt_group_last_error(void);
 
