@@ -1,9 +1,9 @@
 // The host layer behind the C ABI (include/mcpt.h): error plumbing, the owners of device resources, the wavefront workspace, the
 // environment knobs, the event timer, struct mcpt_scene, and what its translation units call in each other:
 //   mcpt_wavefront.hip  the wavefront loop, workspace / pass sizing (render_list), the pixel list and sky cull set-up
-//   mcpt_upload.hip     scene create / upload / update / destroy / info, the BVH dumps
+//   mcpt_upload.hip     scene create / upload / update / snapshot / destroy / info, the BVH dumps
 //   mcpt_update.hip     the kernel that moves objects in HBM (the device path of mcpt_scene_update), mcpt_transform_triangles
-//   mcpt_render.hip     the frame-level entry points (render, adaptive, AOVs, denoise)
+//   mcpt_render.hip     the frame-level entry points (render, adaptive, AOVs, denoise, motion, temporal blend)
 //   mcpt_query.hip      ray queries, tone map and the debug entry points
 //   mcpt_multi.hip      mcpt_group_*
 #pragma once
@@ -365,6 +365,11 @@ struct mcpt_scene {
     mcpt::SceneMeta meta;
     mcpt::SceneSource src;
     mcpt::GeomBufs geom;
+    // mcpt_scene_snapshot: where the primitives were when it was last called (TriGeom and SphereRec arrays indexed like the live ones;
+    // primitive ids are stable across updates).  Empty until the first snapshot: the motion pass then reads the live arrays.
+    mcpt::DevBuf<mcpt::TriGeom> snap_tri;
+    mcpt::DevBuf<mcpt::SphereRec> snap_sph;
+    bool has_snapshot = false;
     mcpt::DevBuf<mcpt_triangle> tris0;   // device builders: the creation-time triangles
     mcpt::DevBuf<int32_t> sphere_obj;    // device builders: object index of every sphere (the builder's primitive list)
     mcpt::DevBuf<mcpt::MoveSeg> segs;    // the update kernel's segment table

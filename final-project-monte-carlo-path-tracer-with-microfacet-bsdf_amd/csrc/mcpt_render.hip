@@ -1,5 +1,5 @@
 // The frame-level entry points of the C ABI (include/mcpt.h): mcpt_render / mcpt_render_device, mcpt_render_adaptive, mcpt_render_aovs[_ex],
-// mcpt_denoise and mcpt_render_denoised.  What they share -- the checks of (camera, params), the start of a call, its statistics -- is
+// mcpt_denoise, mcpt_render_denoised, mcpt_render_motion and mcpt_temporal_blend.  What they share -- the checks of (camera, params), the start of a call, its statistics -- is
 // here once; each entry point is the part that differs.
 #include <cmath>
 #include <cstdio>
@@ -7,6 +7,7 @@
 #include "mcpt_host.h"
 #include "mcpt_adaptive.h"
 #include "mcpt_denoise.h"
+#include "mcpt_temporal.h"
 
 using namespace mcpt;
 
@@ -196,19 +197,19 @@ struct AovOwn {
     }
 };
 
-// The AOV pass (include/mcpt.h): aov_dev[8m ..] for every pixel of the frame, samples 0 .. aov_spp-1 of `seed`, queued on `st`.  Chunks of
-// whole pixels, pixel-major.  It runs inside the wavefront workspace of pool 0 when that holds at least one pixel's rays (after a render it
-// holds millions): camera rays and hits in wave 0's ray / hit arrays, the per-sample records in wave 1's, the keys in wave 1's path
-// records, the retrace list of the closest-hit rays.  Otherwise (no render yet on this scene) it uses buffers of its own for the call.
-// spec_depth > 0 (mcpt_render_aovs_ex): each chunk runs the specular chains instead of k_aov_resolve -- k_aov_chain on the traced list, then
-// up to spec_depth times k_trace_closest + k_aov_chain on the compacted list of the samples that continue (its length read back once per
-// bounce).  In the workspace the second ray list is vtx0 / vtx1 with wave 1's hits, the chain states wave 0's and wave 1's rec1 with the
-// sums in wave 0's rec0 and vtx2, the count vtx_j[0] (chunks then hold at most `pool` rays); otherwise the call allocates them for a chunk.
-int aov_pass(mcpt_scene *sc, const CameraConst &cc, uint32_t seed, int32_t aov_spp, int32_t spec_depth, float *aov_dev, hipStream_t st) {
+// The chunk loop the AOV pass and the motion pass share: for chunks of whole pixels, pixel-major, the keys, the camera rays and the closest
+// hits of samples 0 .. aov_spp-1 of `seed`, queued on `st`; resolve(a, p0, np, n) then turns the n traced rays of the chunk's np pixels
+// (from pixel p0) into the pass's own records and folds them (it returns an mcpt status).  The loop runs inside the wavefront workspace of
+// pool 0 when that holds at least one pixel's rays (after a render it holds millions): camera rays and hits in wave 0's ray / hit arrays,
+// the per-sample records in wave 1's, the keys in wave 1's path records, the retrace list of the closest-hit rays.  Otherwise (no render
+// yet on this scene) it uses buffers of its own for the call.  `chain`: the second ray list and the chain states of the specular chains
+// are needed too (in the workspace: vtx0 / vtx1 with wave 1's hits, wave 0's and wave 1's rec1, the sums in wave 0's rec0 and vtx2, the
+// count vtx_j[0]; chunks then hold at most `pool` rays).
+template <class Resolve>
+int first_hit_chunks(mcpt_scene *sc, const CameraConst &cc, uint32_t seed, int32_t aov_spp, bool chain, hipStream_t st, Resolve &&resolve) {
     const uint32_t n_px = (uint32_t)cc.width * (uint32_t)cc.height;
     const uint64_t need = std::min<uint64_t>(kAovChunkRays, (uint64_t)n_px * aov_spp);
     Workspace &w = sc->pools[0].ws;
-    const bool chain = spec_depth > 0;
     // rays that fit: the ray arrays (ray_cap entries) and, for the keys, two uint32 per ray in wave 1's rec0 (4 per entry); the chains use
     // arrays of `pool` entries too
     const uint64_t ws_rays = w.pool ? std::min<uint64_t>(w.ray_cap, (chain ? 1ull : 2ull) * w.pool) : 0;
@@ -224,6 +225,20 @@ int aov_pass(mcpt_scene *sc, const CameraConst &cc, uint32_t seed, int32_t aov_s
         launch_aov_keys(p0, n, aov_spp, a.key_pixel, a.key_sample, st);
         launch_camera_rays(cc, seed, n, a.key_pixel, a.key_sample, a.list_o[0], a.list_d[0], st);
         launch_trace_closest(sc->view, n, nullptr, a.list_o[0], a.list_d[0], a.list_hit[0], a.rl, st);
+        const int rc = resolve(a, p0, np, n);
+        if (rc != MCPT_OK) return rc;
+    }
+    HIP_TRY(hipGetLastError());
+    if (!in_ws) HIP_TRY(hipStreamSynchronize(st));  // (the call's own buffers are freed on return)
+    return MCPT_OK;
+}
+
+// The AOV pass (include/mcpt.h): aov_dev[8m ..] for every pixel of the frame.  Per chunk k_aov_resolve, or with spec_depth > 0
+// (mcpt_render_aovs_ex) the specular chains -- k_aov_chain on the traced list, then up to spec_depth times k_trace_closest + k_aov_chain on
+// the compacted list of the samples that continue (its length read back once per bounce) -- and k_aov_fold.
+int aov_pass(mcpt_scene *sc, const CameraConst &cc, uint32_t seed, int32_t aov_spp, int32_t spec_depth, float *aov_dev, hipStream_t st) {
+    const bool chain = spec_depth > 0;
+    return first_hit_chunks(sc, cc, seed, aov_spp, chain, st, [&](const AovPtrs &a, uint32_t p0, uint32_t np, uint32_t n) -> int {
         if (!chain) {
             launch_aov_resolve(sc->view, n, a.list_o[0], a.list_d[0], a.list_hit[0], a.rec0, a.rec1, st);
         } else {
@@ -241,10 +256,34 @@ int aov_pass(mcpt_scene *sc, const CameraConst &cc, uint32_t seed, int32_t aov_s
             }
         }
         launch_aov_fold(p0, np, aov_spp, a.rec0, a.rec1, aov_dev, st);
-    }
-    HIP_TRY(hipGetLastError());
-    if (!in_ws) HIP_TRY(hipStreamSynchronize(st));  // (the call's own buffers are freed on return)
-    return MCPT_OK;
+        return MCPT_OK;
+    });
+}
+
+// What a projection of the motion pass reads of a camera (csrc/mcpt_temporal.h)
+tp::Cam motion_camera(const CameraConst &cc) {
+    tp::Cam c;
+    c.width = cc.width;
+    c.height = cc.height;
+    c.scale = cc.scale;
+    c.aspect = cc.aspect;
+    for (int k = 0; k < 3; ++k) c.eye[k] = cc.eye[k];
+    for (int k = 0; k < 9; ++k) c.orient[k] = cc.orient[k];
+    return c;
+}
+
+// The motion pass (include/mcpt.h: mcpt_render_motion): motion_dev[4m ..] for every pixel of the frame, from the rays and hits of the AOV
+// pass.  Per chunk k_motion_resolve and k_motion_fold (csrc/mcpt_temporal.hip); prev_tri / prev_sph are the snapshot's arrays, or the live
+// ones for a scene without a snapshot.
+int motion_pass(mcpt_scene *sc, const CameraConst &cc, const CameraConst &prev_cc, uint32_t seed, int32_t aov_spp, float *motion_dev, hipStream_t st) {
+    const tp::Cam cur = motion_camera(cc), prev = motion_camera(prev_cc);
+    const TriGeom *prev_tri = sc->has_snapshot ? sc->snap_tri.p : sc->view.tri_geom;
+    const SphereRec *prev_sph = sc->has_snapshot ? sc->snap_sph.p : sc->view.spheres;
+    return first_hit_chunks(sc, cc, seed, aov_spp, false, st, [&](const AovPtrs &a, uint32_t p0, uint32_t np, uint32_t n) -> int {
+        launch_motion_resolve(sc->view, prev_tri, prev_sph, cur, prev, n, a.list_o[0], a.list_d[0], a.list_hit[0], a.rec0, st);
+        launch_motion_fold(p0, np, aov_spp, a.rec0, motion_dev, st);
+        return MCPT_OK;
+    });
 }
 
 // Working buffers of the filter for one call: two record buffers and the depth gradient, 72 bytes per pixel.
@@ -497,6 +536,51 @@ int mcpt_render_denoised(mcpt_scene *sc, const mcpt_camera *cam, const mcpt_para
         info->ms_total = ms_since(f.t0);
     }
     return f.end(stats, (uint64_t)ps.n_owned * p.spp, (uint64_t)ps.n_pix * p.spp, rt);
+}
+
+int mcpt_render_motion(mcpt_scene *sc, const mcpt_camera *cam, const mcpt_camera *prev_cam, uint32_t seed, int32_t aov_spp, float *motion_host) {
+    const auto bad = [&](const char *what) { return fail(MCPT_ERR_ARG, std::string("mcpt_render_motion: ") + what); };
+    if (!sc || !cam || !prev_cam || !motion_host) return bad("null argument");
+    if (!frame_ok(cam->width, cam->height)) return bad("width and height must be positive (and the frame not too large)");
+    if (prev_cam->width != cam->width || prev_cam->height != cam->height) return bad("prev_camera must have the width and height of camera");
+    if (aov_spp < 0 || aov_spp > kMaxAovSpp) return bad("aov_spp must be 0..65536");
+    const int32_t n_spp = aov_spp == 0 ? 4 : aov_spp;
+    HIP_TRY(hipSetDevice(sc->device));
+    (void)hipGetLastError();
+    const size_t n_px = (size_t)cam->width * cam->height;
+    DevBuf<float> motion;
+    HIP_TRY(motion.alloc(n_px * 4));
+    const CameraConst cc = make_camera(*cam);
+    const int rc = motion_pass(sc, cc, make_camera(*prev_cam), seed, n_spp, motion.p, nullptr);
+    if (rc != MCPT_OK) return drained(rc);
+    HIP_TRY(download(motion_host, motion, n_px * 4));
+    return MCPT_OK;
+}
+
+int mcpt_temporal_blend(mcpt_scene *sc, int32_t width, int32_t height, const float *color_host, const float *motion_host, const float *prev_color_host,
+                        const float *prev_depth_host, const float *prev_len_host, const mcpt_temporal_opts *opts, float *out_color_host,
+                        float *out_len_host) {
+    if (!sc || !color_host || !motion_host || !prev_color_host || !prev_depth_host || !prev_len_host || !opts || !out_color_host || !out_len_host)
+        return fail(MCPT_ERR_ARG, "mcpt_temporal_blend: null argument");
+    if (!frame_ok(width, height)) return fail(MCPT_ERR_ARG, "mcpt_temporal_blend: width and height must be positive (and the frame not too large)");
+    tp::Opts o;
+    if (tp::resolve_opts(*opts, o) != 0) return fail(MCPT_ERR_ARG, "mcpt_temporal_blend: option out of range");
+    HIP_TRY(hipSetDevice(sc->device));
+    (void)hipGetLastError();
+    const size_t n_px = (size_t)width * height;
+    DevBuf<float> col, mot, pcol, pz, plen, out, olen;
+    HIP_TRY(out.alloc(n_px * 3));
+    HIP_TRY(olen.alloc(n_px));
+    HIP_TRY(upload(col, color_host, n_px * 3));
+    HIP_TRY(upload(mot, motion_host, n_px * 4));
+    HIP_TRY(upload(pcol, prev_color_host, n_px * 3));
+    HIP_TRY(upload(pz, prev_depth_host, n_px));
+    HIP_TRY(upload(plen, prev_len_host, n_px));
+    launch_temporal_blend(width, height, o, col.p, mot.p, pcol.p, pz.p, plen.p, out.p, olen.p, nullptr);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(download(out_color_host, out, n_px * 3));
+    HIP_TRY(download(out_len_host, olen, n_px));
+    return MCPT_OK;
 }
 
 }  // extern "C"

@@ -1,0 +1,192 @@
+/*
+ * mcpt_temporal.h -- the per-sample and per-pixel arithmetic of temporal reuse (include/mcpt.h: mcpt_render_motion, mcpt_temporal_blend).
+ *
+ * Motion: where the surface point a feature sample hit was on the previous frame's screen.  Blend: the bilinear, depth-validated
+ * reprojection of the previous frame's colour and its running average with the new frame.  Every function here is callable from the
+ * host and from the device, and both compilations (hipcc -ffp-contract=off for gfx950; g++ -std=c++17 -O2 -ffp-contract=off) give the
+ * same bits: float32 arithmetic in a fixed order, no FMA, correctly rounded f32 division and square root, floorf.
+ * tests/test_temporal_cpu.py checks the host build against numpy restatements and tests/test_gpu_temporal.py checks the device against
+ * the host build bit for bit.  csrc/mcpt_temporal.hip holds the kernels.
+ *
+ * Per-sample motion record and per-pixel motion record alike: 4 floats {dx, dy, prev_depth, valid}.
+ */
+#ifndef MCPT_TEMPORAL_H
+#define MCPT_TEMPORAL_H
+
+#include <stddef.h>
+#include <stdint.h>
+
+#include "../../include/mcpt.h"
+
+#if defined(__HIPCC__) || defined(__HIP__)
+#include <hip/hip_runtime.h>
+#define MCPT_TP static __host__ __device__ __forceinline__
+#else
+#include <math.h>
+#define MCPT_TP static inline
+#endif
+
+namespace mcpt {
+namespace tp {
+
+constexpr int32_t kMaxHistory = 4096;
+
+// What a projection reads of a camera: scale and aspect exactly those of the camera rays (make_camera, csrc/mcpt_wavefront.hip).
+struct Cam {
+    int32_t width, height;
+    float scale, aspect;
+    float eye[3];
+    float orient[9];  // row-major, columns = left, up, forward
+};
+
+// Options after the defaults of include/mcpt.h have been applied.
+struct Opts {
+    float max_history;  // 1..4096, an integer value
+    float depth_tol;    // > 0
+};
+
+// 0 on success, -1 if an option is out of range.
+MCPT_TP int resolve_opts(const mcpt_temporal_opts &o, Opts &out) {
+    for (int k = 0; k < 6; ++k)
+        if (o.reserved[k] != 0) return -1;
+    const int32_t mh = o.max_history == 0 ? 32 : o.max_history;
+    if (mh < 1 || mh > kMaxHistory) return -1;
+    const float dt = o.depth_tol == 0.0f ? 0.02f : o.depth_tol;
+    if (!(dt > 0.0f && dt <= 3.0e38f)) return -1;  // (positive and finite; NaN fails)
+    out.max_history = (float)mh;
+    out.depth_tol = dt;
+    return 0;
+}
+
+MCPT_TP bool finite_f(float x) { return x - x == 0.0f; }  // false for +-inf and NaN
+
+/* The screen position of p: q = orient^T (p - eye) in the 3-term dot order x + (y + z); the inverse of the camera ray's x, y
+ * (a pinhole through eye: a lens offset is ignored), in pixels with pixel i covering [i, i + 1).  false if q.z <= 0 (or NaN). */
+MCPT_TP bool project(const Cam &c, const float p[3], float &sx, float &sy) {
+    const float dx = p[0] - c.eye[0], dy = p[1] - c.eye[1], dz = p[2] - c.eye[2];
+    const float qx = c.orient[0] * dx + (c.orient[3] * dy + c.orient[6] * dz);
+    const float qy = c.orient[1] * dx + (c.orient[4] * dy + c.orient[7] * dz);
+    const float qz = c.orient[2] * dx + (c.orient[5] * dy + c.orient[8] * dz);
+    if (!(qz > 0.0f)) return false;
+    sx = (1.0f - (qx / qz) / (c.aspect * c.scale)) * (0.5f * (float)c.width);
+    sy = (1.0f - (qy / qz) / c.scale) * (0.5f * (float)c.height);
+    return true;
+}
+
+// v0 + (e1 u + e2 v) of a triangle record whose first nine floats are v0, e1, e2 (TriGeom, csrc/mcpt_internal.h)
+MCPT_TP void tri_point(const float *g, float u, float v, float p[3]) {
+    p[0] = g[0] + (g[3] * u + g[6] * v);
+    p[1] = g[1] + (g[4] * u + g[7] * v);
+    p[2] = g[2] + (g[5] * u + g[8] * v);
+}
+
+/* The motion record of one hit sample: the point is at p_cur now and was at p_prev when the snapshot was taken.
+ *   {proj(prev, p_prev) - proj(cur, p_cur), |p_prev - eye_prev|, 1};  {0, 0, 0, 0} if either projection has q.z <= 0. */
+MCPT_TP void sample_motion(const Cam &cur, const Cam &prev, const float p_cur[3], const float p_prev[3], float out[4]) {
+    float cx, cy, px, py;
+    out[0] = out[1] = out[2] = out[3] = 0.0f;
+    if (!project(cur, p_cur, cx, cy) || !project(prev, p_prev, px, py)) return;
+    const float dx = p_prev[0] - prev.eye[0], dy = p_prev[1] - prev.eye[1], dz = p_prev[2] - prev.eye[2];
+    out[0] = px - cx;
+    out[1] = py - cy;
+    out[2] = sqrtf(dx * dx + (dy * dy + dz * dz));
+    out[3] = 1.0f;
+}
+
+/* The samples of a pixel (4 floats each) folded in sample order: dx, dy and prev_depth are sums over the valid samples divided by their
+ * number (0 without one); valid = that number / spp. */
+MCPT_TP void fold_pixel(const float *s, int32_t spp, float out[4]) {
+    float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f;
+    int32_t n = 0;
+    for (int32_t k = 0; k < spp; ++k) {
+        if (!(s[4 * k + 3] > 0.0f)) continue;
+        a0 = a0 + s[4 * k];
+        a1 = a1 + s[4 * k + 1];
+        a2 = a2 + s[4 * k + 2];
+        ++n;
+    }
+    const float fn = (float)n;
+    out[0] = n > 0 ? a0 / fn : 0.0f;
+    out[1] = n > 0 ? a1 / fn : 0.0f;
+    out[2] = n > 0 ? a2 / fn : 0.0f;
+    out[3] = fn / (float)spp;
+}
+
+/* The blend at pixel (i, j) of a W x H frame (include/mcpt.h has the rule): color, prev_color 3 floats per pixel; motion 4;
+ * prev_depth, prev_len 1.  Writes out_color[3 m ..] and out_len[m], m = j W + i.  The taps' positions are tested in float before they
+ * become indices, so a motion that is huge or not finite reads nothing. */
+MCPT_TP void blend_pixel(int W, int H, int i, int j, const float *color, const float *motion, const float *prev_color,
+                         const float *prev_depth, const float *prev_len, const Opts &o, float *out_color, float *out_len) {
+    const size_t m = (size_t)j * W + i;
+    const float c0 = color[m * 3], c1 = color[m * 3 + 1], c2 = color[m * 3 + 2];
+    const float *mv = motion + m * 4;
+    float r0 = c0, r1 = c1, r2 = c2, len = 1.0f;
+    if (mv[3] > 0.0f && finite_f(c0) && finite_f(c1) && finite_f(c2)) {
+        const float fx = (float)i + mv[0], fy = (float)j + mv[1];
+        const float x0 = floorf(fx), y0 = floorf(fy);
+        const float a = fx - x0, b = fy - y0;
+        const float wx[2] = {1.0f - a, a}, wy[2] = {1.0f - b, b};
+        const float zp = mv[2], ztol = o.depth_tol * zp;
+        float sw = 0.0f, s0 = 0.0f, s1 = 0.0f, s2 = 0.0f, nmin = 0.0f;
+        bool any = false;
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+        for (int t = 0; t < 4; ++t) {
+            const float w = wx[t & 1] * wy[t >> 1];
+            const float tx = x0 + (float)(t & 1), ty = y0 + (float)(t >> 1);
+            if (w == 0.0f) continue;
+            if (!(tx >= 0.0f && tx < (float)W && ty >= 0.0f && ty < (float)H)) continue;
+            const size_t q = (size_t)(int)ty * W + (size_t)(int)tx;
+            const float n = prev_len[q];
+            if (n <= 0.0f) continue;
+            const float p0 = prev_color[q * 3], p1 = prev_color[q * 3 + 1], p2 = prev_color[q * 3 + 2];
+            if (!(finite_f(p0) && finite_f(p1) && finite_f(p2))) continue;
+            const float dz = prev_depth[q] - zp;
+            if (!((dz < 0.0f ? -dz : dz) <= ztol)) continue;  // (a NaN depth on either side rejects the tap)
+            sw = sw + w;
+            s0 = s0 + w * p0;
+            s1 = s1 + w * p1;
+            s2 = s2 + w * p2;
+            nmin = (!any || n < nmin) ? n : nmin;
+            any = true;
+        }
+        if (any) {
+            const float h0 = s0 / sw, h1 = s1 / sw, h2 = s2 / sw;
+            const float n1 = nmin + 1.0f;
+            const float N = n1 < o.max_history ? n1 : o.max_history;
+            const float k = 1.0f / N;
+            r0 = h0 + (c0 - h0) * k;
+            r1 = h1 + (c1 - h1) * k;
+            r2 = h2 + (c2 - h2) * k;
+            len = N;
+        }
+    }
+    out_color[m * 3] = r0;
+    out_color[m * 3 + 1] = r1;
+    out_color[m * 3 + 2] = r2;
+    out_len[m] = len;
+}
+
+}  // namespace tp
+}  // namespace mcpt
+
+#undef MCPT_TP
+
+#if defined(__HIPCC__) || defined(__HIP__)
+#include "mcpt_kernels.h"
+
+namespace mcpt {
+// Launchers of csrc/mcpt_temporal.hip (all asynchronous on `st`).
+// The motion records of the n traced camera rays of a chunk of the AOV pass (csrc/mcpt_denoise.hip): prev_tri / prev_sph are the
+// snapshot's TriGeom and SphereRec arrays (the live ones for a scene without a snapshot) ...
+void launch_motion_resolve(const DevScene &S, const TriGeom *prev_tri, const SphereRec *prev_sph, const tp::Cam &cur, const tp::Cam &prev, uint32_t n,
+                           const float4 *ray_o, const float4 *ray_d, const uint4 *hit, float4 *rec, hipStream_t st);
+// ... folded in sample order into motion[4 (p0 + i) ...] for the chunk's n_pix pixels
+void launch_motion_fold(uint32_t p0, uint32_t n_pix, int32_t spp, const float4 *rec, float *motion, hipStream_t st);
+// The blend of a W x H frame
+void launch_temporal_blend(int W, int H, const tp::Opts &o, const float *color, const float *motion, const float *prev_color, const float *prev_depth,
+                           const float *prev_len, float *out_color, float *out_len, hipStream_t st);
+}  // namespace mcpt
+#endif
+#endif  // MCPT_TEMPORAL_H

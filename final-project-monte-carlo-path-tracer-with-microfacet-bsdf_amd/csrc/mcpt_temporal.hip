@@ -1,0 +1,99 @@
+// Temporal reuse (include/mcpt.h: mcpt_render_motion, mcpt_temporal_blend); csrc/mcpt_temporal.h has the arithmetic, shared with the
+// CPU build the tests compare against.
+//
+// Motion pass: the AOV pass's chunk loop (csrc/mcpt_render.hip: keys, camera rays, closest hits) with two kernels of its own
+//   k_motion_resolve  hit -> per-sample record {dx, dy, prev_depth, valid}: the hit point rebuilt on the live primitive and on the
+//                     snapshot's, both projected
+//   k_motion_fold     one lane per pixel: the samples folded in sample order into the 4-float motion record
+// Blend:
+//   k_temporal_blend  16 x 16 pixel blocks, one pixel per lane; a wave covers four rows of 16 pixels, so its loads of the pixel's own
+//                     colour, motion and its stores are four contiguous runs; up to four taps of the previous frame per lane, no LDS
+//                     (neighbouring lanes' taps are neighbouring pixels: the cache lines are shared in L1 / L2)
+#include <hip/hip_runtime.h>
+
+#include "mcpt_temporal.h"
+
+namespace mcpt {
+
+namespace {
+
+constexpr int kB = 256;
+constexpr int kTile = 16;
+inline uint32_t nblocks(uint32_t n) { return (n + kB - 1) / kB; }
+// tp::tri_point reads a TriGeom as nine floats v0, e1, e2
+static_assert(offsetof(TriGeom, e1x) == 12 && offsetof(TriGeom, e1yz) == 16 && offsetof(TriGeom, e2xy) == 24 && offsetof(TriGeom, e2z) == 32, "TriGeom layout");
+
+__global__ __launch_bounds__(kB) void k_motion_resolve(DevScene S, const TriGeom *__restrict__ prev_tri, const SphereRec *__restrict__ prev_sph,
+                                                       tp::Cam cur, tp::Cam prev, uint32_t n, const float4 *__restrict__ ray_o,
+                                                       const float4 *__restrict__ ray_d, const uint4 *__restrict__ hit, float4 *__restrict__ rec) {
+    const uint32_t j = blockIdx.x * kB + threadIdx.x;
+    if (j >= n) return;
+    const uint4 h = hit[j];
+    const int32_t prim = (int32_t)h.z;
+    float out[4] = {0.f, 0.f, 0.f, 0.f};
+    if (prim >= 0) {
+        const float4 o4 = ray_o[j], d4 = ray_d[j];
+        const f3 ro = mk3(o4.x, o4.y, o4.z), rd = mk3(d4.x, d4.y, d4.z);
+        float pc[3], pp[3];
+        bool ok = true;
+        if (prim < S.n_tri) {
+            const TriGeom g = S.tri_geom[prim];
+            double tt, u, v;
+            ok = tri_hit(g, make_ray(ro, rd), tt, u, v);  // (the test that recorded the hit: it succeeds again)
+            if (ok) {
+                tp::tri_point(reinterpret_cast<const float *>(&g), (float)u, (float)v, pc);
+                tp::tri_point(reinterpret_cast<const float *>(prev_tri + prim), (float)u, (float)v, pp);
+            }
+        } else {
+            const double t = __longlong_as_double((long long)(((unsigned long long)h.y << 32) | h.x));
+            const f3 p = ro + rd * (float)t;
+            const SphereRec &sc = S.spheres[prim - S.n_tri], &sp = prev_sph[prim - S.n_tri];
+            pc[0] = p.x;
+            pc[1] = p.y;
+            pc[2] = p.z;
+            pp[0] = p.x + (sp.c[0] - sc.c[0]);
+            pp[1] = p.y + (sp.c[1] - sc.c[1]);
+            pp[2] = p.z + (sp.c[2] - sc.c[2]);
+        }
+        if (ok) tp::sample_motion(cur, prev, pc, pp, out);
+    }
+    rec[j] = make_float4(out[0], out[1], out[2], out[3]);
+}
+
+__global__ __launch_bounds__(kB) void k_motion_fold(uint32_t p0, uint32_t n_pix, int32_t spp, const float4 *__restrict__ rec, float *__restrict__ motion) {
+    const uint32_t i = blockIdx.x * kB + threadIdx.x;
+    if (i >= n_pix) return;
+    float out[4];
+    tp::fold_pixel(reinterpret_cast<const float *>(rec + (size_t)i * spp), spp, out);
+    reinterpret_cast<float4 *>(motion)[p0 + i] = make_float4(out[0], out[1], out[2], out[3]);
+}
+
+__global__ __launch_bounds__(kTile *kTile) void k_temporal_blend(int W, int H, tp::Opts o, const float *__restrict__ color, const float *__restrict__ motion,
+                                                                const float *__restrict__ prev_color, const float *__restrict__ prev_depth,
+                                                                const float *__restrict__ prev_len, float *__restrict__ out_color,
+                                                                float *__restrict__ out_len) {
+    const int x = blockIdx.x * kTile + threadIdx.x, y = blockIdx.y * kTile + threadIdx.y;
+    if (x >= W || y >= H) return;
+    tp::blend_pixel(W, H, x, y, color, motion, prev_color, prev_depth, prev_len, o, out_color, out_len);
+}
+
+}  // namespace
+
+void launch_motion_resolve(const DevScene &S, const TriGeom *prev_tri, const SphereRec *prev_sph, const tp::Cam &cur, const tp::Cam &prev, uint32_t n,
+                           const float4 *ray_o, const float4 *ray_d, const uint4 *hit, float4 *rec, hipStream_t st) {
+    if (n == 0) return;
+    hipLaunchKernelGGL(k_motion_resolve, dim3(nblocks(n)), dim3(kB), 0, st, S, prev_tri, prev_sph, cur, prev, n, ray_o, ray_d, hit, rec);
+}
+
+void launch_motion_fold(uint32_t p0, uint32_t n_pix, int32_t spp, const float4 *rec, float *motion, hipStream_t st) {
+    if (n_pix == 0) return;
+    hipLaunchKernelGGL(k_motion_fold, dim3(nblocks(n_pix)), dim3(kB), 0, st, p0, n_pix, spp, rec, motion);
+}
+
+void launch_temporal_blend(int W, int H, const tp::Opts &o, const float *color, const float *motion, const float *prev_color, const float *prev_depth,
+                           const float *prev_len, float *out_color, float *out_len, hipStream_t st) {
+    const dim3 grid((W + kTile - 1) / kTile, (H + kTile - 1) / kTile), blk(kTile, kTile);
+    hipLaunchKernelGGL(k_temporal_blend, grid, blk, 0, st, W, H, o, color, motion, prev_color, prev_depth, prev_len, out_color, out_len);
+}
+
+}  // namespace mcpt

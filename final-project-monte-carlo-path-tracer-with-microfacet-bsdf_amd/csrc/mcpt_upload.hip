@@ -518,6 +518,30 @@ int mcpt_scene_update(mcpt_scene *sc, int32_t n, const mcpt_object_transform *mo
     return apply_transforms(sc, moved, xf, touched, info);
 }
 
+int mcpt_scene_snapshot(mcpt_scene *sc) {
+    if (!sc) return fail(MCPT_ERR_ARG, "mcpt_scene_snapshot: null scene");
+    HIP_TRY(hipSetDevice(sc->device));
+    (void)hipGetLastError();
+    const size_t nt = (size_t)sc->meta.n_triangles, ns = (size_t)sc->meta.n_sphere_slots;
+    const auto copy_into = [&](DevBuf<TriGeom> &t, DevBuf<SphereRec> &s) -> int {
+        if (nt) HIP_TRY(hipMemcpyAsync(t.p, sc->geom.tri_geom.p, nt * sizeof(TriGeom), hipMemcpyDeviceToDevice, nullptr));
+        if (ns) HIP_TRY(hipMemcpyAsync(s.p, sc->geom.spheres.p, ns * sizeof(SphereRec), hipMemcpyDeviceToDevice, nullptr));
+        HIP_TRY(hipStreamSynchronize(nullptr));
+        return MCPT_OK;
+    };
+    if (sc->has_snapshot && sc->snap_tri.n == nt && sc->snap_sph.n == ns) return copy_into(sc->snap_tri, sc->snap_sph);
+    DevBuf<TriGeom> t;  // new arrays aside: a failed allocation leaves the old snapshot as it was
+    DevBuf<SphereRec> s;
+    HIP_TRY(t.alloc(nt));
+    HIP_TRY(s.alloc(ns));
+    const int rc = copy_into(t, s);
+    if (rc != MCPT_OK) return rc;
+    sc->snap_tri.swap(t);
+    sc->snap_sph.swap(s);
+    sc->has_snapshot = true;
+    return MCPT_OK;
+}
+
 void mcpt_scene_destroy(mcpt_scene *sc) {
     if (!sc) return;
     (void)hipSetDevice(sc->device);

@@ -19,6 +19,7 @@ EXPORTS = ["mcpt_scene_create", "mcpt_scene_destroy", "mcpt_render", "mcpt_rende
            "mcpt_render_aovs_ex", "mcpt_denoise", "mcpt_render_denoised", "mcpt_intersect",
            "mcpt_cast_rays", "mcpt_camera_rays", "mcpt_scene_get_info", "mcpt_bvh_dump", "mcpt_scene_create_ex", "mcpt_scene_dump_bvh", "mcpt_tonemap", "mcpt_tonemap_device", "mcpt_debug_fmath", "mcpt_debug_material", "mcpt_debug_scene", "mcpt_debug_counters",
            "mcpt_scene_update", "mcpt_group_update", "mcpt_transform_triangles",
+           "mcpt_scene_snapshot", "mcpt_render_motion", "mcpt_temporal_blend",
            "mcpt_group_create", "mcpt_group_render", "mcpt_group_size", "mcpt_group_get_info", "mcpt_group_scene", "mcpt_group_destroy", "mcpt_group_last_error",
            "mcpt_last_error", "mcpt_version"]
 
@@ -83,6 +84,15 @@ def denoise_opts(aov_spp=0, iterations=0, sigma_l=0.0, sigma_n=0.0, sigma_z=0.0,
     """mcpt_denoise_opts (0 = the library's default for every field; specular_depth 0: first-hit AOVs)."""
     return DenoiseOpts(aov_spp=int(aov_spp), iterations=int(iterations), sigma_l=float(sigma_l), sigma_n=float(sigma_n), sigma_z=float(sigma_z),
                        specular_depth=int(specular_depth))
+
+
+class TemporalOpts(C.Structure):
+    _fields_ = [("max_history", C.c_int32), ("depth_tol", C.c_float), ("reserved", C.c_int32 * 6)]
+
+
+def temporal_opts(max_history=0, depth_tol=0.0):
+    """mcpt_temporal_opts (0 = the library's default: a history of at most 32 frames, a relative depth tolerance of 0.02)."""
+    return TemporalOpts(max_history=int(max_history), depth_tol=float(depth_tol))
 
 
 class BuildOptions(C.Structure):
@@ -170,6 +180,12 @@ def lib(path=None):
         L.mcpt_render_denoised.restype = C.c_int
         L.mcpt_render_denoised.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(Params), C.POINTER(DenoiseOpts), C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.POINTER(DenoiseInfo), C.POINTER(Stats)]
+        L.mcpt_scene_snapshot.restype = C.c_int
+        L.mcpt_scene_snapshot.argtypes = [C.c_void_p]
+        L.mcpt_render_motion.restype = C.c_int
+        L.mcpt_render_motion.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.c_void_p]
+        L.mcpt_temporal_blend.restype = C.c_int
+        L.mcpt_temporal_blend.argtypes = [C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 5 + [C.POINTER(TemporalOpts), C.c_void_p, C.c_void_p]
         L.mcpt_render_device.restype = C.c_int
         L.mcpt_render_device.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_void_p, C.POINTER(Stats)]
         L.mcpt_intersect.restype = C.c_int
@@ -426,6 +442,41 @@ class HipScene:
                                            None if aov is None else _ptr(aov), C.byref(info),
                                            C.byref(st)), L=self.L)
         return dict(fb=fb, denoised=den, variance=var, aov=aov, info=info.as_dict(), stats=st)
+
+    def snapshot(self):
+        """mcpt_scene_snapshot: remembers where the geometry is now, as the "previous" positions of render_motion (valid across any number of
+        update calls; without one, render_motion sees camera motion only)."""
+        _check(self.L.mcpt_scene_snapshot(self.h), L=self.L)
+
+    def render_motion(self, prev_camera=None, seed=1, aov_spp=0, camera=None):
+        """mcpt_render_motion: motion[H,W,4] float32 = {dx, dy, prev_depth, valid}: where the surface seen in each pixel was on the screen of
+        prev_camera (default: the camera itself) when snapshot() was last called, from the feature samples of render_aovs(aov_spp, seed)."""
+        cam = np.ascontiguousarray(camera if camera is not None else self.sd.camera)
+        prev = np.ascontiguousarray(prev_camera if prev_camera is not None else cam)
+        W, H = int(cam["width"].reshape(-1)[0]), int(cam["height"].reshape(-1)[0])
+        motion = np.zeros((H, W, 4), dtype=np.float32)
+        _check(self.L.mcpt_render_motion(self.h, _ptr(cam), _ptr(prev), int(seed), int(aov_spp), _ptr(motion)), L=self.L)
+        return motion
+
+    def temporal_blend(self, color, motion, prev_color, prev_depth, prev_len, **opts):
+        """mcpt_temporal_blend: color[H,W,3] the new frame, motion[H,W,4] (render_motion), prev_color[H,W,3] / prev_len[H,W] the previous
+        result of this call (prev_len 0 everywhere at the start), prev_depth[H,W] the depth channel of the previous frame's AOVs.
+        opts: max_history, depth_tol (0 = default; see include/mcpt.h).  Returns (out[H,W,3], out_len[H,W]) float32."""
+        color = np.ascontiguousarray(color, dtype=np.float32)
+        H, W = color.shape[:2]
+        motion = np.ascontiguousarray(motion, dtype=np.float32)
+        prev_color = np.ascontiguousarray(prev_color, dtype=np.float32)
+        prev_depth = np.ascontiguousarray(prev_depth, dtype=np.float32)
+        prev_len = np.ascontiguousarray(prev_len, dtype=np.float32)
+        if color.size != H * W * 3 or motion.size != H * W * 4 or prev_color.size != H * W * 3 or prev_depth.size != H * W or prev_len.size != H * W:
+            raise ValueError("temporal_blend: shapes %s %s %s %s %s do not describe one %dx%d frame"
+                             % (color.shape, motion.shape, prev_color.shape, prev_depth.shape, prev_len.shape, W, H))
+        out = np.zeros((H, W, 3), dtype=np.float32)
+        out_len = np.zeros((H, W), dtype=np.float32)
+        o = temporal_opts(**opts)
+        _check(self.L.mcpt_temporal_blend(self.h, W, H, _ptr(color), _ptr(motion), _ptr(prev_color), _ptr(prev_depth), _ptr(prev_len), C.byref(o),
+                                          _ptr(out), _ptr(out_len)), L=self.L)
+        return out, out_len
 
     def render_device(self, fb_ptr, stream_ptr=0, camera=None, **kw):
         """Same, into a device framebuffer (W*H*3 floats at fb_ptr) on the given hipStream_t handle."""

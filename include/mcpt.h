@@ -330,6 +330,68 @@ int mcpt_denoise(mcpt_scene *scene, int32_t width, int32_t height, const float *
 int mcpt_render_denoised(mcpt_scene *scene, const mcpt_camera *camera, const mcpt_params *params, const mcpt_denoise_opts *opts, float *fb_host,
                          float *denoised_host, float *variance_host, float *aov_host, mcpt_denoise_info *info, mcpt_stats *stats);
 
+/* ---- Temporal reuse for moving scenes: per-pixel motion and a validated blend of the reprojected history (csrc/mcpt_temporal.h has
+ * every expression in its order; the device and a CPU build of it agree bit for bit).  The frame loop is
+ *       mcpt_scene_snapshot;  mcpt_scene_update;  mcpt_render (+ mcpt_render_aovs);  mcpt_render_motion;  mcpt_temporal_blend.
+ *
+ * mcpt_scene_snapshot remembers where the geometry is now: the live triangle records (v0, e1, e2) and sphere centres are copied device to
+ * device into arrays the scene owns (allocated on first use, reallocated only if the counts change, freed by mcpt_scene_destroy).
+ * Primitive ids are stable across mcpt_scene_update, so entry p of the snapshot is primitive p, however many updates follow it.  A scene
+ * that was never snapshotted uses its live arrays as "previous" (camera motion only).  MCPT_ERR_ARG for a null scene; MCPT_ERR_OOM leaves
+ * the old snapshot intact. */
+int mcpt_scene_snapshot(mcpt_scene *scene);
+
+/* Motion record: 4 floats per pixel, row-major m = j*W + i:  {dx, dy, prev_depth, valid}.
+ * Feature sample k of pixel m is the camera ray of render sample k, traced exactly as for mcpt_render_aovs (same keys, same closest-hit
+ * traversal, no sky cull).  Per hit sample, in float unless stated:
+ *   triangle  (u, v) = the double barycentrics of the hit on the live record, each rounded once to float;
+ *             p_cur = v0 + (e1*u + e2*v) on the live record, p_prev = the same expression on the snapshot's record
+ *             (a static triangle gives p_prev == p_cur bit for bit)
+ *   sphere    p_cur = o + d * (float) t;  p_prev = p_cur + (c_prev - c_cur)   (the linear part of a transform acts on the centre only)
+ *   proj(cam, p):  q = orientation^T (p - position), each component in the 3-term dot order a.x*b.x + (a.y*b.y + a.z*b.z);
+ *             invalid if q.z <= 0;  sx = (1 - (q.x/q.z)/(aspect*scale)) * (0.5f*W),  sy = (1 - (q.y/q.z)/scale) * (0.5f*H)
+ *             with the scale = tan(fov/2) and aspect = W/H of the camera rays: the inverse of their x, y through a pinhole at `position`
+ *             (the lens offset of a depth-of-field camera is ignored), in pixels, pixel i covering [i, i+1)
+ *   motion    proj(prev_camera, p_prev) - proj(camera, p_cur): 0 bit for bit when nothing moved; the pixel jitter and the lens sample
+ *             cancel to first order
+ *   prev_depth  |p_prev - prev_camera.position|: the 3-term dot of the difference with itself, then sqrtf
+ *   A sample is invalid if it misses or if either projection has q.z <= 0.  A point that leaves the previous frustum sideways stays
+ *   valid: being off-screen is the blend's business.
+ * Folded per pixel in sample order: dx, dy and prev_depth are each the sum over the valid samples divided by their number (0 without
+ * one); valid = that number / aov_spp.
+ * motion_host: W*H*4 floats.  aov_spp 0 => 4, at most 65536.  MCPT_ERR_ARG, before any device call: a null pointer, width or height
+ * <= 0, aov_spp out of range, prev_camera with another width or height than camera.
+ * Limits: the motion is that of the first hit, so what is seen through mirrors and glass, and depth-of-field blur, are not reprojected. */
+int mcpt_render_motion(mcpt_scene *scene, const mcpt_camera *camera, const mcpt_camera *prev_camera, uint32_t seed, int32_t aov_spp,
+                       float *motion_host);
+
+/* The blend on host arrays (the scene only picks the device and stream, as in mcpt_denoise):
+ *   color_host W*H*3 the new frame;  motion_host W*H*4 (mcpt_render_motion);  prev_color_host W*H*3 the previous OUTPUT of this call;
+ *   prev_depth_host W*H the depth channel of the previous frame's AOVs;  prev_len_host / out_len_host W*H floats with integer values:
+ *   the number of frames already blended into a pixel (0 everywhere for the first frame);  out_color_host W*H*3.
+ * Per pixel (i, j), in float, in this order:
+ *   1. motion.valid <= 0, or a colour channel that is not finite: out = color, len = 1.
+ *   2. fx = i + dx, fy = j + dy (pixel-centre coordinates minus 0.5);  x0 = floorf(fx), a = fx - x0;  y0 = floorf(fy), b = fy - y0;
+ *      taps (x0,y0), (x0+1,y0), (x0,y0+1), (x0+1,y0+1) in that order with weights (1-a)(1-b), a(1-b), (1-a)b, ab.
+ *   3. a tap is skipped if its weight is 0 (a static frame reads exactly one tap), it lies outside the image, prev_len <= 0 there, a
+ *      channel of its colour is not finite, or |prev_depth[tap] - motion.prev_depth| > depth_tol * motion.prev_depth
+ *      (tested as !(|..| <= ..), so a depth that is NaN on either side skips the tap too).
+ *   4. no tap left: out = color, len = 1.
+ *   5. otherwise, per channel, sums from 0 in tap order:  hist = (sum w c) / (sum w);  n = the smallest prev_len of the used taps;
+ *      N = min(n + 1, max_history);  out = hist + (color - hist) * (1.f / N);  len = N.
+ * So a static scene accumulates the running mean of its frames (N frames after N calls, up to max_history, then an exponential average),
+ * and a pixel whose history fails the depth test restarts.  Only depth is validated: a rotating object keeps its history, and sky
+ * pixels (valid 0) restart every frame.
+ * MCPT_ERR_ARG for a null pointer, width or height <= 0 and out-of-range options (a non-zero reserved word included). */
+typedef struct {
+    int32_t max_history; /* cap of the running mean's length; 0 => 32; 1..4096 */
+    float depth_tol;     /* relative depth tolerance, > 0; 0 => 0.02 */
+    int32_t reserved[6]; /* must be 0 */
+} mcpt_temporal_opts;    /* 32 bytes */
+int mcpt_temporal_blend(mcpt_scene *scene, int32_t width, int32_t height, const float *color_host, const float *motion_host,
+                        const float *prev_color_host, const float *prev_depth_host, const float *prev_len_host, const mcpt_temporal_opts *opts,
+                        float *out_color_host, float *out_len_host);
+
 /* Replaces Scene::intersect (Scene.hpp:128, Scene.cpp:19-21) for a list of rays (host pointers; n*3 floats each).
  * out_t: hit distance as the reference's double Intersection::distance (DBL_MAX on a miss);
  * out_prim: global primitive id (triangle index, or n_triangles + object index for a sphere; -1 on a miss). */

@@ -1,0 +1,112 @@
+"""One 1920x1080 chess frame through the pieces of temporal reuse, beside what they are compared with: the AOV pass (the same rays as the
+motion pass) and the a-trous filter.  Run it under `rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/temporal.py`
+for the kernel times (each call is repeated --repeat times; the statistics average over the launches); on its own it prints wall times,
+which include the host copies of every call.
+python tools/temporal.py [--width 1920] [--height 1080] [--scene chess|cornell] [--repeat 5]
+python tools/temporal.py --trace KERNEL_TRACE_CSV [--repeat 5]   sums such a run's kernel trace per pass: the AOV pass and the motion pass
+launch the same three kernels first, which the statistics cannot tell apart, so the trace is cut at every k_aov_keys and each piece goes
+to the pass whose fold ends it.  The launch counts must fit the calls a run with that --repeat makes, or nothing is printed."""
+import argparse
+import csv
+import re
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, '.')
+import mcpt_loader  # noqa: E402
+
+
+def summarize_trace(path, repeat):
+    """Kernel time per call of each pass, from the sums over all the calls this script made."""
+    # render_denoised or the call that feeds the blend, the warm-up call, the repeats; the blend has no first call
+    calls_of = {"mcpt_render_aovs": repeat + 2, "mcpt_render_motion": repeat + 2, "a-trous filter": repeat + 2, "mcpt_temporal_blend": repeat + 1}
+    rows = []
+    with open(path) as f:
+        for r in csv.DictReader(f):
+            m = re.search(r"\b(k_\w+)", r["Kernel_Name"])
+            rows.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]) - int(r["Start_Timestamp"]), m.group(1) if m else r["Kernel_Name"][:40]))
+    rows.sort()
+    folds = {"k_aov_fold": "mcpt_render_aovs", "k_motion_fold": "mcpt_render_motion"}
+    alone = {"k_dn_prep": "a-trous filter", "k_dn_atrous": "a-trous filter", "k_dn_remod": "a-trous filter",
+             "k_temporal_blend": "mcpt_temporal_blend"}
+    per = {}  # pass -> kernel -> [launches, ns]
+    piece = None
+    # the kernels of a pass: the AOV pass inside render_denoised may overlap the frame's last render kernels, the motion pass runs alone
+    own, seen = {"k_aov_resolve", "k_aov_fold"}, None
+    for _, _, name in rows:
+        seen = set() if name == "k_aov_keys" else seen
+        if seen is not None:
+            seen.add(name)
+            if name in folds:
+                own |= seen if name == "k_motion_fold" else set()
+                seen = None
+    for _, dur, name in rows:
+        if piece is not None and name not in own and name not in alone:
+            continue
+        if name == "k_aov_keys":
+            piece = []
+        if piece is not None:
+            piece.append((name, dur))
+            if name in folds:
+                for n, d in piece:
+                    e = per.setdefault(folds[name], {}).setdefault(n, [0, 0])
+                    e[0] += 1
+                    e[1] += d
+                piece = None
+        elif name in alone:
+            e = per.setdefault(alone[name], {}).setdefault(name, [0, 0])
+            e[0] += 1
+            e[1] += dur
+    # what marks one call (the two passes run one fold per chunk of rays, the same number in every call)
+    once = {"mcpt_render_aovs": "k_aov_fold", "mcpt_render_motion": "k_motion_fold", "a-trous filter": "k_dn_prep", "mcpt_temporal_blend": "k_temporal_blend"}
+    for what in ("mcpt_render_aovs", "mcpt_render_motion", "a-trous filter", "mcpt_temporal_blend"):
+        k, calls = per.get(what, {}), calls_of[what]
+        n = k.get(once[what], [0, 0])[0]
+        if n == 0 or n % calls or (what in alone.values() and n != calls):
+            sys.exit("%s: %d launches of %s do not fit %d calls: is this the trace of a run with --repeat %d?" % (what, n, once[what], calls, repeat))
+        print("%-20s %8.3f ms per call (kernel time, %d calls)" % (what, sum(v[1] for v in k.values()) / calls / 1e6, calls))
+        for n, (cnt, ns) in sorted(k.items(), key=lambda kv: -kv[1][1]):
+            print("    %-18s %4d launches  %8.3f ms per call  %8.1f us per launch" % (n, cnt, ns / calls / 1e6, ns / cnt / 1e3))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--trace", help="a rocprofv3 kernel-trace CSV of a run of this script with the same --repeat: print the kernel time per pass")
+    ap.add_argument("--width", type=int, default=1920)
+    ap.add_argument("--height", type=int, default=1080)
+    ap.add_argument("--scene", default="chess", choices=["chess", "cornell"])
+    ap.add_argument("--repeat", type=int, default=5)
+    a = ap.parse_args()
+    if a.trace:
+        return summarize_trace(a.trace, a.repeat)
+    pkg = mcpt_loader.load()
+    W, H = a.width, a.height
+    sd = pkg.scenes.chess_scene(width=W, height=H, spp=4) if a.scene == "chess" else pkg.scenes.cornell_demo(W, H, 4)
+    hs = pkg.HipScene(sd)
+    r = hs.render_denoised(spp=4, seed=1, aov_spp=4)  # (also sizes the workspace the AOV and motion passes run in)
+    color, var, aov = r["fb"], r["variance"], r["aov"]
+    hs.snapshot()
+    length = np.ones((H, W), np.float32)
+
+    def wall(name, f):
+        f()
+        t = []
+        for _ in range(a.repeat):
+            t0 = time.perf_counter()
+            f()
+            t.append(time.perf_counter() - t0)
+        print("%-16s median wall %.2f ms (host copies included)" % (name, 1e3 * float(np.median(t))), flush=True)
+
+    wall("render_aovs", lambda: hs.render_aovs(aov_spp=4, seed=1))
+    wall("render_motion", lambda: hs.render_motion(seed=1, aov_spp=4))
+    motion = hs.render_motion(seed=1, aov_spp=4)
+    wall("denoise", lambda: hs.denoise(color, var, aov))
+    wall("temporal_blend", lambda: hs.temporal_blend(color, motion, color, aov[..., 6], length))
+    wall("snapshot", hs.snapshot)
+    print("valid pixels %.1f %%" % (100 * float((motion[..., 3] > 0).mean())))
+
+
+if __name__ == "__main__":
+    main()
