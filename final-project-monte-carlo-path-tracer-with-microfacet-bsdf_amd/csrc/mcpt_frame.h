@@ -1,0 +1,71 @@
+// What the frame-level translation units share (mcpt_render.hip defines it; mcpt_sequence.hip runs the same passes on buffers of its
+// own): the checks of (camera, params), the start and the end of a call, the AOV pass and the motion pass, the filter's working buffers.
+#pragma once
+#include "mcpt_host.h"
+#include "mcpt_adaptive.h"
+#include "mcpt_denoise.h"
+#include "mcpt_temporal.h"
+
+namespace mcpt {
+
+constexpr int32_t kMaxAovSpp = 65536;
+
+// a frame whose AOV records (8 floats per pixel) can be indexed
+inline bool frame_ok(int W, int H) { return W > 0 && H > 0 && (uint64_t)W * H <= 0x7fffffffull / 8; }
+
+// What an entry point forbids on top of the common checks of (cam, params).
+enum : unsigned {
+    kOneCallFrame = 1u,  // no progressive accumulation: accumulate, spp_total and sample_offset must be 0
+    kOneRank = 2u,       // nranks must be 1
+    kDenoisedFrame = 4u  // spp >= 2 (a variance needs two samples) and a frame the AOV pass can hold (frame_ok)
+};
+
+// The checks of (cam, params) every frame-level call makes before it touches the scene, in the order the entry points have always made
+// them; `name` is the entry point's, for the message.
+int check_frame_call(const char *name, const mcpt_camera &cam, const mcpt_params &p, unsigned forbid);
+
+// mcpt_stats of a call that rendered `samples` camera samples, `traced_primary` of them through the wavefront loop (the rest: sky cull).
+void fill_stats(mcpt_stats *stats, uint64_t samples, uint64_t traced_primary, int32_t n_dir, const Totals &rt, Clock::time_point t0);
+
+// The start and the end every frame-level render call shares, once its arguments have passed the checks.
+struct FrameCall {
+    mcpt_scene *sc;
+    const mcpt_params &p;
+    Clock::time_point t0;
+    CameraConst cc;
+    PixelSet ps;
+    int begin(const mcpt_camera &cam) {
+        HIP_TRY(hipSetDevice(sc->device));
+        (void)hipGetLastError();  // an earlier, already reported failure of this thread must not be taken for one of this call
+        t0 = Clock::now();
+        cc = make_camera(cam);
+        return MCPT_OK;
+    }
+    // the owned pixels, the cleared frame and the sky cull, whose pixels get `spp` additions of background / spp_total
+    int pixels(int32_t spp, float spp_total, float *fb_dev, hipStream_t st) { return prepare_pixels(sc, cc, p, spp, spp_total, fb_dev, st, ps); }
+    int end(mcpt_stats *stats, uint64_t samples, uint64_t traced_primary, const Totals &rt) const {
+        if (stats) fill_stats(stats, samples, traced_primary, p.n_dir_sample, rt, t0);
+        if (rt.overflow) return fail(MCPT_ERR_OVERFLOW, "some paths outran the clamp stack (raise params.max_depth)");
+        return MCPT_OK;
+    }
+};
+
+// The AOV pass (include/mcpt.h): aov_dev[8m ..] for every pixel of the frame, queued on `st` (with spec_depth > 0 it waits for the
+// stream once per bounce).
+int aov_pass(mcpt_scene *sc, const CameraConst &cc, uint32_t seed, int32_t aov_spp, int32_t spec_depth, float *aov_dev, hipStream_t st);
+// The motion pass (include/mcpt.h: mcpt_render_motion): motion_dev[4m ..] for every pixel of the frame, against the scene's snapshot.
+int motion_pass(mcpt_scene *sc, const CameraConst &cc, const CameraConst &prev_cc, uint32_t seed, int32_t aov_spp, float *motion_dev, hipStream_t st);
+
+// Working buffers of the filter: two record buffers and the depth gradient, 72 bytes per pixel.
+struct DenoiseBufs {
+    DevBuf<dn::Rec> rec[2];
+    DevBuf<float2> grad;
+    hipError_t alloc(size_t n_px) {
+        hipError_t e = rec[0].alloc(n_px);
+        if (e == hipSuccess) e = rec[1].alloc(n_px);
+        if (e == hipSuccess) e = grad.alloc(n_px);
+        return e;
+    }
+};
+
+}  // namespace mcpt

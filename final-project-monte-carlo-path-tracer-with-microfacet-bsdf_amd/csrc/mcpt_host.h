@@ -3,7 +3,9 @@
 //   mcpt_wavefront.hip  the wavefront loop, workspace / pass sizing (render_list), the pixel list and sky cull set-up
 //   mcpt_upload.hip     scene create / upload / update / snapshot / destroy / info, the BVH dumps
 //   mcpt_update.hip     the kernel that moves objects in HBM (the device path of mcpt_scene_update), mcpt_transform_triangles
-//   mcpt_render.hip     the frame-level entry points (render, adaptive, AOVs, denoise, motion, temporal blend)
+//   mcpt_render.hip     the frame-level entry points (render, adaptive, AOVs, denoise, motion, temporal blend); mcpt_frame.h has what
+//                       it shares with
+//   mcpt_sequence.hip   mcpt_temporal_accumulate and mcpt_sequence_*: a frame loop whose history and buffers stay on the device
 //   mcpt_query.hip      ray queries, tone map and the debug entry points
 //   mcpt_multi.hip      mcpt_group_*
 #pragma once

@@ -1,13 +1,10 @@
 // The frame-level entry points of the C ABI (include/mcpt.h): mcpt_render / mcpt_render_device, mcpt_render_adaptive, mcpt_render_aovs[_ex],
 // mcpt_denoise, mcpt_render_denoised, mcpt_render_motion and mcpt_temporal_blend.  What they share -- the checks of (camera, params), the start of a call, its statistics -- is
-// here once; each entry point is the part that differs.
+// here once; each entry point is the part that differs.  csrc/mcpt_frame.h declares what csrc/mcpt_sequence.hip uses of it.
 #include <cmath>
 #include <cstdio>
 
-#include "mcpt_host.h"
-#include "mcpt_adaptive.h"
-#include "mcpt_denoise.h"
-#include "mcpt_temporal.h"
+#include "mcpt_frame.h"
 
 using namespace mcpt;
 
@@ -21,24 +18,7 @@ void mcpt::add(mcpt_stats &a, const mcpt_stats &b) {
     a.n_generate += b.n_generate; a.n_resolve += b.n_resolve; a.n_direct += b.n_direct;
 }
 
-namespace {
-
-constexpr uint32_t kAovChunkRays = 4u << 20;  // at most this many rays per chunk of the AOV pass
-constexpr int32_t kMaxAovSpp = 65536;
-
-// a frame whose AOV records (8 floats per pixel) can be indexed
-bool frame_ok(int W, int H) { return W > 0 && H > 0 && (uint64_t)W * H <= 0x7fffffffull / 8; }
-
-// What an entry point forbids on top of the common checks of (cam, params).
-enum : unsigned {
-    kOneCallFrame = 1u,  // no progressive accumulation: accumulate, spp_total and sample_offset must be 0
-    kOneRank = 2u,       // nranks must be 1
-    kDenoisedFrame = 4u  // spp >= 2 (a variance needs two samples) and a frame the AOV pass can hold (frame_ok)
-};
-
-// The checks of (cam, params) every frame-level call makes before it touches the scene, in the order the entry points have always made
-// them; `name` is the entry point's, for the message.
-int check_frame_call(const char *name, const mcpt_camera &cam, const mcpt_params &p, unsigned forbid) {
+int mcpt::check_frame_call(const char *name, const mcpt_camera &cam, const mcpt_params &p, unsigned forbid) {
     const auto bad = [&](const char *what) { return fail(MCPT_ERR_ARG, std::string(name) + ": " + what); };
     const bool positive = cam.width > 0 && cam.height > 0 && p.n_dir_sample > 0 && p.rr_rate > 0.f;
     if (forbid & kDenoisedFrame) {
@@ -54,8 +34,7 @@ int check_frame_call(const char *name, const mcpt_camera &cam, const mcpt_params
     return MCPT_OK;
 }
 
-// mcpt_stats of a call that rendered `samples` camera samples, `traced_primary` of them through the wavefront loop (the rest: sky cull).
-void fill_stats(mcpt_stats *stats, uint64_t samples, uint64_t traced_primary, int32_t n_dir, const Totals &rt, Clock::time_point t0) {
+void mcpt::fill_stats(mcpt_stats *stats, uint64_t samples, uint64_t traced_primary, int32_t n_dir, const Totals &rt, Clock::time_point t0) {
     std::memset(stats, 0, sizeof *stats);
     // (culled pixels count like traced ones: the reference runs one camera ray and three castRay invocations, each with one
     // Scene::intersect, for every sample of them too)
@@ -87,28 +66,9 @@ void fill_stats(mcpt_stats *stats, uint64_t samples, uint64_t traced_primary, in
     stats->ms_total = ms_since(t0);
 }
 
-// The start and the end every frame-level render call shares, once its arguments have passed the checks.
-struct FrameCall {
-    mcpt_scene *sc;
-    const mcpt_params &p;
-    Clock::time_point t0;
-    CameraConst cc;
-    PixelSet ps;
-    int begin(const mcpt_camera &cam) {
-        HIP_TRY(hipSetDevice(sc->device));
-        (void)hipGetLastError();  // an earlier, already reported failure of this thread must not be taken for one of this call
-        t0 = Clock::now();
-        cc = make_camera(cam);
-        return MCPT_OK;
-    }
-    // the owned pixels, the cleared frame and the sky cull, whose pixels get `spp` additions of background / spp_total
-    int pixels(int32_t spp, float spp_total, float *fb_dev, hipStream_t st) { return prepare_pixels(sc, cc, p, spp, spp_total, fb_dev, st, ps); }
-    int end(mcpt_stats *stats, uint64_t samples, uint64_t traced_primary, const Totals &rt) const {
-        if (stats) fill_stats(stats, samples, traced_primary, p.n_dir_sample, rt, t0);
-        if (rt.overflow) return fail(MCPT_ERR_OVERFLOW, "some paths outran the clamp stack (raise params.max_depth)");
-        return MCPT_OK;
-    }
-};
+namespace {
+
+constexpr uint32_t kAovChunkRays = 4u << 20;  // at most this many rays per chunk of the AOV pass
 
 int render_impl(mcpt_scene *sc, const mcpt_camera *cam, const mcpt_params *pp, float *fb_dev, hipStream_t st, mcpt_stats *stats) {
     if (!sc || !cam || !pp || !fb_dev) return fail(MCPT_ERR_ARG, "mcpt_render: null argument");
@@ -233,10 +193,12 @@ int first_hit_chunks(mcpt_scene *sc, const CameraConst &cc, uint32_t seed, int32
     return MCPT_OK;
 }
 
+}  // namespace
+
 // The AOV pass (include/mcpt.h): aov_dev[8m ..] for every pixel of the frame.  Per chunk k_aov_resolve, or with spec_depth > 0
 // (mcpt_render_aovs_ex) the specular chains -- k_aov_chain on the traced list, then up to spec_depth times k_trace_closest + k_aov_chain on
 // the compacted list of the samples that continue (its length read back once per bounce) -- and k_aov_fold.
-int aov_pass(mcpt_scene *sc, const CameraConst &cc, uint32_t seed, int32_t aov_spp, int32_t spec_depth, float *aov_dev, hipStream_t st) {
+int mcpt::aov_pass(mcpt_scene *sc, const CameraConst &cc, uint32_t seed, int32_t aov_spp, int32_t spec_depth, float *aov_dev, hipStream_t st) {
     const bool chain = spec_depth > 0;
     return first_hit_chunks(sc, cc, seed, aov_spp, chain, st, [&](const AovPtrs &a, uint32_t p0, uint32_t np, uint32_t n) -> int {
         if (!chain) {
@@ -260,6 +222,8 @@ int aov_pass(mcpt_scene *sc, const CameraConst &cc, uint32_t seed, int32_t aov_s
     });
 }
 
+namespace {
+
 // What a projection of the motion pass reads of a camera (csrc/mcpt_temporal.h)
 tp::Cam motion_camera(const CameraConst &cc) {
     tp::Cam c;
@@ -272,10 +236,12 @@ tp::Cam motion_camera(const CameraConst &cc) {
     return c;
 }
 
+}  // namespace
+
 // The motion pass (include/mcpt.h: mcpt_render_motion): motion_dev[4m ..] for every pixel of the frame, from the rays and hits of the AOV
 // pass.  Per chunk k_motion_resolve and k_motion_fold (csrc/mcpt_temporal.hip); prev_tri / prev_sph are the snapshot's arrays, or the live
 // ones for a scene without a snapshot.
-int motion_pass(mcpt_scene *sc, const CameraConst &cc, const CameraConst &prev_cc, uint32_t seed, int32_t aov_spp, float *motion_dev, hipStream_t st) {
+int mcpt::motion_pass(mcpt_scene *sc, const CameraConst &cc, const CameraConst &prev_cc, uint32_t seed, int32_t aov_spp, float *motion_dev, hipStream_t st) {
     const tp::Cam cur = motion_camera(cc), prev = motion_camera(prev_cc);
     const TriGeom *prev_tri = sc->has_snapshot ? sc->snap_tri.p : sc->view.tri_geom;
     const SphereRec *prev_sph = sc->has_snapshot ? sc->snap_sph.p : sc->view.spheres;
@@ -286,17 +252,7 @@ int motion_pass(mcpt_scene *sc, const CameraConst &cc, const CameraConst &prev_c
     });
 }
 
-// Working buffers of the filter for one call: two record buffers and the depth gradient, 72 bytes per pixel.
-struct DenoiseBufs {
-    DevBuf<dn::Rec> rec[2];
-    DevBuf<float2> grad;
-    hipError_t alloc(size_t n_px) {
-        hipError_t e = rec[0].alloc(n_px);
-        if (e == hipSuccess) e = rec[1].alloc(n_px);
-        if (e == hipSuccess) e = grad.alloc(n_px);
-        return e;
-    }
-};
+namespace {
 
 // mcpt_render_aovs and mcpt_render_aovs_ex (`name` for the messages)
 int render_aovs(const char *name, mcpt_scene *sc, const mcpt_camera *cam, uint32_t seed, int32_t aov_spp, int32_t spec_depth, float *aov_host) {

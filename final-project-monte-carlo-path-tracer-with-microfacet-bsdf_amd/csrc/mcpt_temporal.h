@@ -2,7 +2,8 @@
  * mcpt_temporal.h -- the per-sample and per-pixel arithmetic of temporal reuse (include/mcpt.h: mcpt_render_motion, mcpt_temporal_blend).
  *
  * Motion: where the surface point a feature sample hit was on the previous frame's screen.  Blend: the bilinear, depth-validated
- * reprojection of the previous frame's colour and its running average with the new frame.  Every function here is callable from the
+ * reprojection of the previous frame's colour and its running average with the new frame.  Accumulate: the blend, and the variance of
+ * its result propagated from the variances of its inputs (mcpt_temporal_accumulate, mcpt_sequence_frame).  Every function here is callable from the
  * host and from the device, and both compilations (hipcc -ffp-contract=off for gfx950; g++ -std=c++17 -O2 -ffp-contract=off) give the
  * same bits: float32 arithmetic in a fixed order, no FMA, correctly rounded f32 division and square root, floorf.
  * tests/test_temporal_cpu.py checks the host build against numpy restatements and tests/test_gpu_temporal.py checks the device against
@@ -112,59 +113,120 @@ MCPT_TP void fold_pixel(const float *s, int32_t spp, float out[4]) {
     out[3] = fn / (float)spp;
 }
 
+/* What the taps of one pixel's history add up to (steps 2, 3 and the sums of step 5 of the rule in include/mcpt.h). */
+struct Taps {
+    float sw, s0, s1, s2;  // sum of w, sum of w * colour
+    float sv;              // sum of (w * w) * prev_variance (accumulate_pixel only)
+    float nmin;            // the smallest prev_len of the used taps
+};
+
+/* The tap loop the blend and the accumulation share: the four bilinear taps of pixel (i, j) moved by its motion record mv, in tap order,
+ * with every skip of the rule.  false if no tap is left.  kVar: also sum the taps' variances (prev_variance is not read without it).
+ * The taps' positions are tested in float before they become indices, so a motion that is huge or not finite reads nothing. */
+template <bool kVar>
+MCPT_TP bool gather_taps(int W, int H, int i, int j, const float *mv, const float *prev_color, const float *prev_variance, const float *prev_depth,
+                         const float *prev_len, const Opts &o, Taps &t) {
+    const float fx = (float)i + mv[0], fy = (float)j + mv[1];
+    const float x0 = floorf(fx), y0 = floorf(fy);
+    const float a = fx - x0, b = fy - y0;
+    const float wx[2] = {1.0f - a, a}, wy[2] = {1.0f - b, b};
+    const float zp = mv[2], ztol = o.depth_tol * zp;
+    float sw = 0.0f, s0 = 0.0f, s1 = 0.0f, s2 = 0.0f, sv = 0.0f, nmin = 0.0f;
+    bool any = false;
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int k = 0; k < 4; ++k) {
+        const float w = wx[k & 1] * wy[k >> 1];
+        const float tx = x0 + (float)(k & 1), ty = y0 + (float)(k >> 1);
+        if (w == 0.0f) continue;
+        if (!(tx >= 0.0f && tx < (float)W && ty >= 0.0f && ty < (float)H)) continue;
+        const size_t q = (size_t)(int)ty * W + (size_t)(int)tx;
+        const float n = prev_len[q];
+        if (n <= 0.0f) continue;
+        const float p0 = prev_color[q * 3], p1 = prev_color[q * 3 + 1], p2 = prev_color[q * 3 + 2];
+        if (!(finite_f(p0) && finite_f(p1) && finite_f(p2))) continue;
+        const float dz = prev_depth[q] - zp;
+        if (!((dz < 0.0f ? -dz : dz) <= ztol)) continue;  // (a NaN depth on either side rejects the tap)
+        sw = sw + w;
+        s0 = s0 + w * p0;
+        s1 = s1 + w * p1;
+        s2 = s2 + w * p2;
+        if (kVar) sv = sv + (w * w) * prev_variance[q];
+        nmin = (!any || n < nmin) ? n : nmin;
+        any = true;
+    }
+    t.sw = sw;
+    t.s0 = s0;
+    t.s1 = s1;
+    t.s2 = s2;
+    t.sv = sv;
+    t.nmin = nmin;
+    return any;
+}
+
 /* The blend at pixel (i, j) of a W x H frame (include/mcpt.h has the rule): color, prev_color 3 floats per pixel; motion 4;
- * prev_depth, prev_len 1.  Writes out_color[3 m ..] and out_len[m], m = j W + i.  The taps' positions are tested in float before they
- * become indices, so a motion that is huge or not finite reads nothing. */
+ * prev_depth, prev_len 1.  Writes out_color[3 m ..] and out_len[m], m = j W + i. */
 MCPT_TP void blend_pixel(int W, int H, int i, int j, const float *color, const float *motion, const float *prev_color,
                          const float *prev_depth, const float *prev_len, const Opts &o, float *out_color, float *out_len) {
     const size_t m = (size_t)j * W + i;
     const float c0 = color[m * 3], c1 = color[m * 3 + 1], c2 = color[m * 3 + 2];
     const float *mv = motion + m * 4;
     float r0 = c0, r1 = c1, r2 = c2, len = 1.0f;
-    if (mv[3] > 0.0f && finite_f(c0) && finite_f(c1) && finite_f(c2)) {
-        const float fx = (float)i + mv[0], fy = (float)j + mv[1];
-        const float x0 = floorf(fx), y0 = floorf(fy);
-        const float a = fx - x0, b = fy - y0;
-        const float wx[2] = {1.0f - a, a}, wy[2] = {1.0f - b, b};
-        const float zp = mv[2], ztol = o.depth_tol * zp;
-        float sw = 0.0f, s0 = 0.0f, s1 = 0.0f, s2 = 0.0f, nmin = 0.0f;
-        bool any = false;
-#if defined(__HIP_DEVICE_COMPILE__)
-#pragma unroll
-#endif
-        for (int t = 0; t < 4; ++t) {
-            const float w = wx[t & 1] * wy[t >> 1];
-            const float tx = x0 + (float)(t & 1), ty = y0 + (float)(t >> 1);
-            if (w == 0.0f) continue;
-            if (!(tx >= 0.0f && tx < (float)W && ty >= 0.0f && ty < (float)H)) continue;
-            const size_t q = (size_t)(int)ty * W + (size_t)(int)tx;
-            const float n = prev_len[q];
-            if (n <= 0.0f) continue;
-            const float p0 = prev_color[q * 3], p1 = prev_color[q * 3 + 1], p2 = prev_color[q * 3 + 2];
-            if (!(finite_f(p0) && finite_f(p1) && finite_f(p2))) continue;
-            const float dz = prev_depth[q] - zp;
-            if (!((dz < 0.0f ? -dz : dz) <= ztol)) continue;  // (a NaN depth on either side rejects the tap)
-            sw = sw + w;
-            s0 = s0 + w * p0;
-            s1 = s1 + w * p1;
-            s2 = s2 + w * p2;
-            nmin = (!any || n < nmin) ? n : nmin;
-            any = true;
-        }
-        if (any) {
-            const float h0 = s0 / sw, h1 = s1 / sw, h2 = s2 / sw;
-            const float n1 = nmin + 1.0f;
-            const float N = n1 < o.max_history ? n1 : o.max_history;
-            const float k = 1.0f / N;
-            r0 = h0 + (c0 - h0) * k;
-            r1 = h1 + (c1 - h1) * k;
-            r2 = h2 + (c2 - h2) * k;
-            len = N;
-        }
+    Taps t;
+    if (mv[3] > 0.0f && finite_f(c0) && finite_f(c1) && finite_f(c2) &&
+        gather_taps<false>(W, H, i, j, mv, prev_color, nullptr, prev_depth, prev_len, o, t)) {
+        const float h0 = t.s0 / t.sw, h1 = t.s1 / t.sw, h2 = t.s2 / t.sw;
+        const float n1 = t.nmin + 1.0f;
+        const float N = n1 < o.max_history ? n1 : o.max_history;
+        const float k = 1.0f / N;
+        r0 = h0 + (c0 - h0) * k;
+        r1 = h1 + (c1 - h1) * k;
+        r2 = h2 + (c2 - h2) * k;
+        len = N;
     }
     out_color[m * 3] = r0;
     out_color[m * 3 + 1] = r1;
     out_color[m * 3 + 2] = r2;
+    out_len[m] = len;
+}
+
+/* The blend with the variance of its result (include/mcpt.h: mcpt_temporal_accumulate).  variance[m] = v_c is this frame's luminance
+ * variance of the colour mean, prev_variance the previous out_variance.  Colour and length are blend_pixel's, expression for expression.
+ * Where the blend takes no history out_variance = v_c; otherwise, over the taps the colour used, in tap order and from 0,
+ *     sv = sv + (w*w) * prev_variance[q];  hv = sv / (sw*sw);  k = 1.f / N;  omk = 1.f - k;  out_variance = (omk*omk)*hv + (k*k)*v_c:
+ * the variance of hist + (color - hist)*k for independent terms, so a static pixel carries (sum of its frames' variances) / N^2 after N
+ * frames.  An hv that is not finite or is negative (a tap's stored variance was) gives v_c: one frame's variance over-estimates, so a
+ * filter guided by it smooths more, never less.  A NaN v_c propagates.
+ * The propagation treats the taps, and the pixels of the output, as independent.  Bilinear resampling correlates neighbouring pixels
+ * (two outputs that share a tap share its noise); that covariance is ignored. */
+MCPT_TP void accumulate_pixel(int W, int H, int i, int j, const float *color, const float *variance, const float *motion, const float *prev_color,
+                              const float *prev_variance, const float *prev_depth, const float *prev_len, const Opts &o, float *out_color,
+                              float *out_variance, float *out_len) {
+    const size_t m = (size_t)j * W + i;
+    const float c0 = color[m * 3], c1 = color[m * 3 + 1], c2 = color[m * 3 + 2];
+    const float vc = variance[m];
+    const float *mv = motion + m * 4;
+    float r0 = c0, r1 = c1, r2 = c2, rv = vc, len = 1.0f;
+    Taps t;
+    if (mv[3] > 0.0f && finite_f(c0) && finite_f(c1) && finite_f(c2) &&
+        gather_taps<true>(W, H, i, j, mv, prev_color, prev_variance, prev_depth, prev_len, o, t)) {
+        const float h0 = t.s0 / t.sw, h1 = t.s1 / t.sw, h2 = t.s2 / t.sw;
+        const float n1 = t.nmin + 1.0f;
+        const float N = n1 < o.max_history ? n1 : o.max_history;
+        const float k = 1.0f / N;
+        r0 = h0 + (c0 - h0) * k;
+        r1 = h1 + (c1 - h1) * k;
+        r2 = h2 + (c2 - h2) * k;
+        len = N;
+        const float hv = t.sv / (t.sw * t.sw);
+        const float omk = 1.0f - k;
+        if (finite_f(hv) && hv >= 0.0f) rv = (omk * omk) * hv + (k * k) * vc;
+    }
+    out_color[m * 3] = r0;
+    out_color[m * 3 + 1] = r1;
+    out_color[m * 3 + 2] = r2;
+    out_variance[m] = rv;
     out_len[m] = len;
 }
 
@@ -187,6 +249,11 @@ void launch_motion_fold(uint32_t p0, uint32_t n_pix, int32_t spp, const float4 *
 // The blend of a W x H frame
 void launch_temporal_blend(int W, int H, const tp::Opts &o, const float *color, const float *motion, const float *prev_color, const float *prev_depth,
                            const float *prev_len, float *out_color, float *out_len, hipStream_t st);
+// The blend with variance of a W x H frame.  depth != nullptr: out_depth[m] = depth[depth_stride * m] as well (the frame's first-hit depth
+// into the history's depth plane: depth points at the depth channel of an AOV array, depth_stride 8).
+void launch_temporal_accumulate(int W, int H, const tp::Opts &o, const float *color, const float *variance, const float *motion, const float *prev_color,
+                                const float *prev_variance, const float *prev_depth, const float *prev_len, const float *depth, int depth_stride,
+                                float *out_color, float *out_variance, float *out_depth, float *out_len, hipStream_t st);
 }  // namespace mcpt
 #endif
 #endif  // MCPT_TEMPORAL_H

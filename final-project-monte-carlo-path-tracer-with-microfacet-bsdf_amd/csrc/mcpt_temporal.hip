@@ -9,6 +9,9 @@
 //   k_temporal_blend  16 x 16 pixel blocks, one pixel per lane; a wave covers four rows of 16 pixels, so its loads of the pixel's own
 //                     colour, motion and its stores are four contiguous runs; up to four taps of the previous frame per lane, no LDS
 //                     (neighbouring lanes' taps are neighbouring pixels: the cache lines are shared in L1 / L2)
+// Accumulate (mcpt_temporal_accumulate, mcpt_sequence_frame):
+//   k_temporal_accumulate  the same shape; the blend with the variance of its result (tp::accumulate_pixel), and the frame's first-hit
+//                     depth copied into the history's depth plane, so that one launch leaves the history complete for the next frame
 #include <hip/hip_runtime.h>
 
 #include "mcpt_temporal.h"
@@ -77,6 +80,19 @@ __global__ __launch_bounds__(kTile *kTile) void k_temporal_blend(int W, int H, t
     tp::blend_pixel(W, H, x, y, color, motion, prev_color, prev_depth, prev_len, o, out_color, out_len);
 }
 
+__global__ __launch_bounds__(kTile *kTile) void k_temporal_accumulate(int W, int H, tp::Opts o, const float *__restrict__ color, const float *__restrict__ variance,
+                                                                     const float *__restrict__ motion, const float *__restrict__ prev_color,
+                                                                     const float *__restrict__ prev_variance, const float *__restrict__ prev_depth,
+                                                                     const float *__restrict__ prev_len, const float *__restrict__ depth, int depth_stride,
+                                                                     float *__restrict__ out_color, float *__restrict__ out_variance,
+                                                                     float *__restrict__ out_depth, float *__restrict__ out_len) {
+    const int x = blockIdx.x * kTile + threadIdx.x, y = blockIdx.y * kTile + threadIdx.y;
+    if (x >= W || y >= H) return;
+    tp::accumulate_pixel(W, H, x, y, color, variance, motion, prev_color, prev_variance, prev_depth, prev_len, o, out_color, out_variance, out_len);
+    const size_t m = (size_t)y * W + x;
+    if (depth) out_depth[m] = depth[m * (size_t)depth_stride];
+}
+
 }  // namespace
 
 void launch_motion_resolve(const DevScene &S, const TriGeom *prev_tri, const SphereRec *prev_sph, const tp::Cam &cur, const tp::Cam &prev, uint32_t n,
@@ -94,6 +110,14 @@ void launch_temporal_blend(int W, int H, const tp::Opts &o, const float *color, 
                            const float *prev_len, float *out_color, float *out_len, hipStream_t st) {
     const dim3 grid((W + kTile - 1) / kTile, (H + kTile - 1) / kTile), blk(kTile, kTile);
     hipLaunchKernelGGL(k_temporal_blend, grid, blk, 0, st, W, H, o, color, motion, prev_color, prev_depth, prev_len, out_color, out_len);
+}
+
+void launch_temporal_accumulate(int W, int H, const tp::Opts &o, const float *color, const float *variance, const float *motion, const float *prev_color,
+                                const float *prev_variance, const float *prev_depth, const float *prev_len, const float *depth, int depth_stride,
+                                float *out_color, float *out_variance, float *out_depth, float *out_len, hipStream_t st) {
+    const dim3 grid((W + kTile - 1) / kTile, (H + kTile - 1) / kTile), blk(kTile, kTile);
+    hipLaunchKernelGGL(k_temporal_accumulate, grid, blk, 0, st, W, H, o, color, variance, motion, prev_color, prev_variance, prev_depth, prev_len, depth,
+                       depth_stride, out_color, out_variance, out_depth, out_len);
 }
 
 }  // namespace mcpt

@@ -19,7 +19,8 @@ EXPORTS = ["mcpt_scene_create", "mcpt_scene_destroy", "mcpt_render", "mcpt_rende
            "mcpt_render_aovs_ex", "mcpt_denoise", "mcpt_render_denoised", "mcpt_intersect",
            "mcpt_cast_rays", "mcpt_camera_rays", "mcpt_scene_get_info", "mcpt_bvh_dump", "mcpt_scene_create_ex", "mcpt_scene_dump_bvh", "mcpt_tonemap", "mcpt_tonemap_device", "mcpt_debug_fmath", "mcpt_debug_material", "mcpt_debug_scene", "mcpt_debug_counters",
            "mcpt_scene_update", "mcpt_group_update", "mcpt_transform_triangles",
-           "mcpt_scene_snapshot", "mcpt_render_motion", "mcpt_temporal_blend",
+           "mcpt_scene_snapshot", "mcpt_render_motion", "mcpt_temporal_blend", "mcpt_temporal_accumulate",
+           "mcpt_sequence_create", "mcpt_sequence_frame", "mcpt_sequence_reset", "mcpt_sequence_destroy",
            "mcpt_group_create", "mcpt_group_render", "mcpt_group_size", "mcpt_group_get_info", "mcpt_group_scene", "mcpt_group_destroy", "mcpt_group_last_error",
            "mcpt_last_error", "mcpt_version"]
 
@@ -93,6 +94,29 @@ class TemporalOpts(C.Structure):
 def temporal_opts(max_history=0, depth_tol=0.0):
     """mcpt_temporal_opts (0 = the library's default: a history of at most 32 frames, a relative depth tolerance of 0.02)."""
     return TemporalOpts(max_history=int(max_history), depth_tol=float(depth_tol))
+
+
+class SequenceOpts(C.Structure):
+    _fields_ = [("temporal", TemporalOpts), ("denoise", DenoiseOpts), ("filter", C.c_int32), ("reserved", C.c_int32 * 7)]
+
+
+SEQUENCE_OUTPUTS = ("fb", "accumulated", "denoised", "variance", "len", "aov", "motion", "rgba")  # mcpt_sequence_outputs, in its order
+
+
+class SequenceOutputs(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in SEQUENCE_OUTPUTS]
+
+
+class SequenceInfo(C.Structure):
+    _fields_ = [("ms_render", C.c_double), ("ms_aov", C.c_double), ("ms_motion", C.c_double), ("ms_accumulate", C.c_double),
+                ("ms_filter", C.c_double), ("ms_total", C.c_double), ("frame_index", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
+assert C.sizeof(TemporalOpts) == 32 and C.sizeof(DenoiseOpts) == 32  # the sizes include/mcpt.h states
+assert C.sizeof(SequenceOpts) == 96 and C.sizeof(SequenceOutputs) == 64 and C.sizeof(SequenceInfo) == 64
 
 
 class BuildOptions(C.Structure):
@@ -186,6 +210,16 @@ def lib(path=None):
         L.mcpt_render_motion.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.c_void_p]
         L.mcpt_temporal_blend.restype = C.c_int
         L.mcpt_temporal_blend.argtypes = [C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 5 + [C.POINTER(TemporalOpts), C.c_void_p, C.c_void_p]
+        L.mcpt_temporal_accumulate.restype = C.c_int
+        L.mcpt_temporal_accumulate.argtypes = [C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 7 + [C.POINTER(TemporalOpts)] + [C.c_void_p] * 3
+        L.mcpt_sequence_create.restype = C.c_int
+        L.mcpt_sequence_create.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(SequenceOpts), C.POINTER(C.c_void_p)]
+        L.mcpt_sequence_frame.restype = C.c_int
+        L.mcpt_sequence_frame.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(Params), C.POINTER(SequenceOutputs), C.POINTER(SequenceInfo), C.POINTER(Stats)]
+        L.mcpt_sequence_reset.restype = C.c_int
+        L.mcpt_sequence_reset.argtypes = [C.c_void_p]
+        L.mcpt_sequence_destroy.restype = None
+        L.mcpt_sequence_destroy.argtypes = [C.c_void_p]
         L.mcpt_render_device.restype = C.c_int
         L.mcpt_render_device.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_void_p, C.POINTER(Stats)]
         L.mcpt_intersect.restype = C.c_int
@@ -478,6 +512,32 @@ class HipScene:
                                           _ptr(out), _ptr(out_len)), L=self.L)
         return out, out_len
 
+    def temporal_accumulate(self, color, variance, motion, prev_color, prev_variance, prev_depth, prev_len, **opts):
+        """mcpt_temporal_accumulate: temporal_blend with the variance of its result.  variance[H,W] is the new frame's luminance variance of the
+        colour mean (render_denoised), prev_variance[H,W] the previous out_variance of this call.  Returns (out[H,W,3], out_variance[H,W],
+        out_len[H,W]) float32; out and out_len are temporal_blend's bit for bit."""
+        color = np.ascontiguousarray(color, dtype=np.float32)
+        H, W = color.shape[:2]
+        variance, motion, prev_color, prev_variance, prev_depth, prev_len = (
+            np.ascontiguousarray(x, dtype=np.float32) for x in (variance, motion, prev_color, prev_variance, prev_depth, prev_len))
+        n = H * W
+        if (color.size != n * 3 or variance.size != n or motion.size != n * 4 or prev_color.size != n * 3 or prev_variance.size != n
+                or prev_depth.size != n or prev_len.size != n):
+            raise ValueError("temporal_accumulate: the arrays do not describe one %dx%d frame" % (W, H))
+        out = np.zeros((H, W, 3), dtype=np.float32)
+        out_var = np.zeros((H, W), dtype=np.float32)
+        out_len = np.zeros((H, W), dtype=np.float32)
+        o = temporal_opts(**opts)
+        _check(self.L.mcpt_temporal_accumulate(self.h, W, H, _ptr(color), _ptr(variance), _ptr(motion), _ptr(prev_color), _ptr(prev_variance),
+                                               _ptr(prev_depth), _ptr(prev_len), C.byref(o), _ptr(out), _ptr(out_var), _ptr(out_len)), L=self.L)
+        return out, out_var, out_len
+
+    def sequence(self, width=None, height=None, filter=True, max_history=0, depth_tol=0.0, **denoise_opts_kw):
+        """mcpt_sequence_create: a HipSequence of width x height frames (default: the scene camera's) on this scene.  filter: also denoise
+        the accumulated frame; max_history, depth_tol: mcpt_temporal_opts; the rest: mcpt_denoise_opts (aov_spp, iterations, sigma_l,
+        sigma_n, sigma_z, specular_depth).  The sequence owns the scene's snapshot while it lives; close it before the scene."""
+        return HipSequence(self, width, height, filter, max_history, depth_tol, **denoise_opts_kw)
+
     def render_device(self, fb_ptr, stream_ptr=0, camera=None, **kw):
         """Same, into a device framebuffer (W*H*3 floats at fb_ptr) on the given hipStream_t handle."""
         cam = np.ascontiguousarray(camera if camera is not None else self.sd.camera)
@@ -542,6 +602,57 @@ class HipScene:
         d = np.zeros((n, 3), dtype=np.float32)
         _check(self.L.mcpt_camera_rays(self.h, _ptr(cam), int(seed), n, _ptr(px), _ptr(sm), _ptr(o), _ptr(d)), L=self.L)
         return o, d
+
+
+class HipSequence:
+    """A frame sequence on a HipScene (mcpt_sequence_*): the history, its variance and every working buffer stay on the device.  The loop
+    is `scene.update(...); seq.frame(seed=k)`."""
+
+    _SHAPES = {"fb": (3,), "accumulated": (3,), "denoised": (3,), "variance": (), "len": (), "aov": (8,), "motion": (4,), "rgba": (4,)}
+
+    def __init__(self, scene, width=None, height=None, filter=True, max_history=0, depth_tol=0.0, **denoise_opts_kw):
+        self.scene = scene  # (keeps the scene alive as long as the sequence)
+        self.L = scene.L
+        self.h = None
+        cam = scene.sd.camera
+        self.W = int(width if width is not None else np.asarray(cam["width"]).reshape(-1)[0])
+        self.H = int(height if height is not None else np.asarray(cam["height"]).reshape(-1)[0])
+        o = SequenceOpts(temporal=temporal_opts(max_history, depth_tol), denoise=denoise_opts(**denoise_opts_kw), filter=int(bool(filter)))
+        h = C.c_void_p()
+        _check(self.L.mcpt_sequence_create(scene.h, self.W, self.H, C.byref(o), C.byref(h)), L=self.L)
+        self.h = h
+
+    def frame(self, camera=None, want=("denoised",), **params_kw):
+        """mcpt_sequence_frame: renders, accumulates and (filter) denoises one frame; vary `seed` from frame to frame.  want: the outputs to
+        copy to the host, of SEQUENCE_OUTPUTS.  Returns a dict of those arrays ([H,W,c] float32; rgba uint8), "info" (stage times in ms,
+        frame_index) and "stats"."""
+        cam = np.ascontiguousarray(camera if camera is not None else self.scene.sd.camera)
+        out, ptrs = {}, SequenceOutputs()
+        for k in want:
+            if k not in self._SHAPES:
+                raise ValueError("unknown sequence output %r (one of %s)" % (k, ", ".join(SEQUENCE_OUTPUTS)))
+            out[k] = np.empty((self.H, self.W) + self._SHAPES[k], dtype=np.uint8 if k == "rgba" else np.float32)
+            setattr(ptrs, k, out[k].ctypes.data)
+        p = self.scene.params(**params_kw)
+        info, st = SequenceInfo(), Stats()
+        _check(self.L.mcpt_sequence_frame(self.h, _ptr(cam), C.byref(p), C.byref(ptrs), C.byref(info), C.byref(st)), L=self.L)
+        out["info"], out["stats"] = info.as_dict(), st
+        return out
+
+    def reset(self):
+        """mcpt_sequence_reset, a camera cut: the next frame takes no history."""
+        _check(self.L.mcpt_sequence_reset(self.h), L=self.L)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.mcpt_sequence_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class HipGroup:

@@ -333,6 +333,7 @@ int mcpt_render_denoised(mcpt_scene *scene, const mcpt_camera *camera, const mcp
 /* ---- Temporal reuse for moving scenes: per-pixel motion and a validated blend of the reprojected history (csrc/mcpt_temporal.h has
  * every expression in its order; the device and a CPU build of it agree bit for bit).  The frame loop is
  *       mcpt_scene_snapshot;  mcpt_scene_update;  mcpt_render (+ mcpt_render_aovs);  mcpt_render_motion;  mcpt_temporal_blend.
+ * (mcpt_sequence_frame below runs that loop on the device, with the variance of the accumulated frame and the filter.)
  *
  * mcpt_scene_snapshot remembers where the geometry is now: the live triangle records (v0, e1, e2) and sphere centres are copied device to
  * device into arrays the scene owns (allocated on first use, reallocated only if the counts change, freed by mcpt_scene_destroy).
@@ -391,6 +392,96 @@ typedef struct {
 int mcpt_temporal_blend(mcpt_scene *scene, int32_t width, int32_t height, const float *color_host, const float *motion_host,
                         const float *prev_color_host, const float *prev_depth_host, const float *prev_len_host, const mcpt_temporal_opts *opts,
                         float *out_color_host, float *out_len_host);
+
+/* The blend with the variance of its result, on host arrays: the testable form of the kernel a sequence runs, as mcpt_temporal_blend is
+ * of its.  The arguments of mcpt_temporal_blend, and
+ *   variance_host W*H  this frame's luminance variance of the colour mean (the `variance` of mcpt_render_denoised, step 2), v_c below;
+ *   prev_variance_host W*H  the previous out_variance_host of this call;   out_variance_host W*H.
+ * out_color and out_len are EXACTLY those of mcpt_temporal_blend on the same inputs: the same taps, skips, hist, N and out.  Per pixel:
+ *   - where the blend takes no history (its steps 1 and 4):  out_variance = v_c;
+ *   - otherwise, over the taps the colour used, in tap order and from 0, in float:
+ *         sv = sv + (w*w) * prev_variance[tap];   hv = sv / (sw*sw)   (sw = the sum of w of step 5);
+ *         k = 1.f / N;   omk = 1.f - k;   out_variance = (omk*omk)*hv + (k*k)*v_c
+ *     -- the variance of hist + (color - hist)*k for independent terms: a static pixel carries (sum of its frames' variances) / N^2
+ *     after N frames;
+ *   - hv not finite or negative (a tap's stored variance was):  out_variance = v_c.  One frame's variance over-estimates that of the
+ *     accumulated pixel, so a filter guided by it smooths more, never less;
+ *   - a NaN v_c propagates (the filter passes such a pixel through unchanged).
+ * Bilinear resampling correlates neighbouring output pixels (two that share a tap share its noise); the propagation ignores that
+ * covariance, as it ignores the correlation of the taps themselves.
+ * MCPT_ERR_ARG as mcpt_temporal_blend. */
+int mcpt_temporal_accumulate(mcpt_scene *scene, int32_t width, int32_t height, const float *color_host, const float *variance_host,
+                             const float *motion_host, const float *prev_color_host, const float *prev_variance_host, const float *prev_depth_host,
+                             const float *prev_len_host, const mcpt_temporal_opts *opts, float *out_color_host, float *out_variance_host,
+                             float *out_len_host);
+
+/* ---- Frame sequences: the history, the variance of the accumulated frame and every working buffer stay on the device; one call runs a
+ * whole frame on one stream and only what the caller asks for crosses the bus.  The caller's loop is
+ *       mcpt_scene_update;  mcpt_sequence_frame          (params.seed varied from frame to frame).
+ *
+ * mcpt_sequence_create allocates everything once, per pixel: two history sets (colour 3, variance 1, depth 1, len 1 floats, used in
+ * turn), the frame 3, its moments 6 doubles, its variance 1, the AOVs 8 (8 more with denoise.specular_depth > 0), the motion 4, the
+ * filtered frame 3 and the tone-mapped one (4 bytes), and the filter's working buffers (72 bytes): 248 bytes per pixel.  It also takes
+ * the scene's snapshot (mcpt_scene_snapshot).  A failed allocation frees what it had: MCPT_ERR_OOM.  mcpt_sequence_frame allocates
+ * nothing of its own (the wavefront workspace is the scene's, sized by its first render as in mcpt_render).
+ * THE SEQUENCE OWNS THE SCENE'S SNAPSHOT WHILE IT LIVES: every frame ends with mcpt_scene_snapshot, so that this frame's geometry is
+ * "previous" for the next one; a caller that snapshots the scene itself changes what the next frame's motion refers to.  One sequence per
+ * scene at a time.  The sequence borrows the scene: destroy the sequence first; destroying the scene first is the caller's error.
+ *
+ * mcpt_sequence_frame, in this order on one stream:
+ *   1. the checks of mcpt_render_denoised on (camera, params, opts.denoise): params.spp >= 2, nranks == 1, accumulate / spp_total /
+ *      sample_offset 0, denoise.aov_spp <= params.spp; and camera.width / height must be the sequence's;
+ *   2. the frame with its moments and its variance: steps 1-2 of mcpt_render_denoised (fb is BIT-IDENTICAL to mcpt_render's frame);
+ *   3. the AOVs of mcpt_render_aovs_ex(params.seed, denoise.aov_spp, denoise.specular_depth).  The history is always validated against
+ *      FIRST-HIT depth, which is what a motion record's prev_depth measures: with specular_depth 0 that is the depth channel of these AOVs,
+ *      otherwise one more first-hit pass (specular_depth 0, the same aov_spp) supplies it;
+ *   4. the motion of mcpt_render_motion(camera, the camera of the sequence's previous frame, params.seed, denoise.aov_spp) against the
+ *      scene's snapshot; the first frame, and the first frame after a reset, use this frame's camera as the previous one;
+ *   5. mcpt_temporal_accumulate(frame, variance, motion, the history: colour, variance, first-hit depth, len; opts.temporal) from the
+ *      previous history set into the other, which also receives this frame's first-hit depth.  On the first frame and after a reset
+ *      prev_len is 0 everywhere, so every pixel starts;
+ *   6. opts.filter 1: mcpt_denoise(accumulated, the accumulated variance, the AOVs; opts.denoise).  The filter gets the variance of the
+ *      image it filters.  The history stays unfiltered: the filter is an output, not a feedback;
+ *   7. the tone map (mcpt_tonemap) if rgba was asked for; then the downloads;
+ *   8. mcpt_scene_snapshot.
+ * So every output equals what the separate calls give on the same inputs, bit for bit.
+ * mcpt_sequence_outputs: host pointers, each nullable; a null pointer costs no download (a null struct pointer: none at all).
+ * mcpt_sequence_info: HIP-event times of the stages, the host wall time, and the index of this frame since the last reset (0 for the
+ * first).  stats as mcpt_render (nullable).
+ * mcpt_sequence_reset is a camera cut: the next frame takes no history (len 1, accumulated == fb, variance == the frame's own).
+ * MCPT_ERR_OVERFLOW as mcpt_render: the outputs are still written and the history is still advanced.  Any other failure leaves the
+ * history, the frame index and the remembered camera as they were before the call.
+ * MCPT_ERR_ARG, before any device call: a null scene, sequence, camera, params, opts or out; width or height <= 0 or a frame too
+ * large; out-of-range temporal or denoise options, a non-zero reserved word; filter not 0 or 1; the failed checks of step 1;
+ * outputs.denoised non-null with filter 0. */
+typedef struct {
+    mcpt_temporal_opts temporal;
+    mcpt_denoise_opts denoise;
+    int32_t filter;      /* 0: accumulate only (what a zeroed struct asks for); 1: also filter the accumulated frame */
+    int32_t reserved[7]; /* must be 0 */
+} mcpt_sequence_opts;    /* 96 bytes */
+typedef struct {
+    float *fb;           /* this frame, W*H*3 */
+    float *accumulated;  /* the accumulated frame, W*H*3 */
+    float *denoised;     /* the filtered accumulated frame, W*H*3 (filter 1 only) */
+    float *variance;     /* W*H, of the accumulated frame */
+    float *len;          /* W*H */
+    float *aov;          /* W*H*8 */
+    float *motion;       /* W*H*4 */
+    uint8_t *rgba;       /* W*H*4 bytes: mcpt_tonemap of denoised, or of accumulated when filter is 0 */
+} mcpt_sequence_outputs; /* 64 bytes */
+typedef struct {
+    double ms_render, ms_aov, ms_motion, ms_accumulate, ms_filter; /* HIP-event times; ms_filter includes the tone map */
+    double ms_total;     /* host wall time of the call */
+    int32_t frame_index; /* frames since the last reset, this one not counted */
+    int32_t reserved[3];
+} mcpt_sequence_info;    /* 64 bytes */
+typedef struct mcpt_sequence mcpt_sequence;
+int mcpt_sequence_create(mcpt_scene *scene, int32_t width, int32_t height, const mcpt_sequence_opts *opts, mcpt_sequence **out);
+int mcpt_sequence_frame(mcpt_sequence *sequence, const mcpt_camera *camera, const mcpt_params *params, const mcpt_sequence_outputs *outputs,
+                        mcpt_sequence_info *info, mcpt_stats *stats);
+int mcpt_sequence_reset(mcpt_sequence *sequence);
+void mcpt_sequence_destroy(mcpt_sequence *sequence);
 
 /* Replaces Scene::intersect (Scene.hpp:128, Scene.cpp:19-21) for a list of rays (host pointers; n*3 floats each).
  * out_t: hit distance as the reference's double Intersection::distance (DBL_MAX on a miss);

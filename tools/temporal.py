@@ -5,7 +5,12 @@ which include the host copies of every call.
 python tools/temporal.py [--width 1920] [--height 1080] [--scene chess|cornell] [--repeat 5]
 python tools/temporal.py --trace KERNEL_TRACE_CSV [--repeat 5]   sums such a run's kernel trace per pass: the AOV pass and the motion pass
 launch the same three kernels first, which the statistics cannot tell apart, so the trace is cut at every k_aov_keys and each piece goes
-to the pass whose fold ends it.  The launch counts must fit the calls a run with that --repeat makes, or nothing is printed."""
+to the pass whose fold ends it.  The launch counts must fit the calls a run with that --repeat makes, or nothing is printed.
+python tools/temporal.py --sequence [--frames 8]   the same frames (seed k + 1 for frame k) twice in one process: through the host-array
+loop snapshot / render / render_aovs / render_motion / temporal_blend / denoise / tonemap, and through HipSequence.frame(want=("rgba",)).
+Prints the wall time per frame of both (the median over the frames after the first, which warms up) and the sequence's per-stage event
+times.  render() returns no variance, so the loop's denoise is fed the variance of one earlier frame: it does the filter's work on the
+accumulated image without the cost of getting a variance, which flatters the loop."""
 import argparse
 import csv
 import re
@@ -71,6 +76,41 @@ def summarize_trace(path, repeat):
             print("    %-18s %4d launches  %8.3f ms per call  %8.1f us per launch" % (n, cnt, ns / calls / 1e6, ns / cnt / 1e3))
 
 
+def sequence_timing(pkg, sd, W, H, frames):
+    hs = pkg.HipScene(sd)
+    var = hs.render_denoised(spp=4, seed=1, aov_spp=4)["variance"]  # (also sizes the workspace)
+    hist, length, prev_depth = np.zeros((H, W, 3), np.float32), np.zeros((H, W), np.float32), np.zeros((H, W), np.float32)
+    t_loop = []
+    for k in range(frames):
+        t0 = time.perf_counter()
+        hs.snapshot()
+        c, _ = hs.render(spp=4, seed=k + 1)
+        aov = hs.render_aovs(aov_spp=4, seed=k + 1)
+        motion = hs.render_motion(seed=k + 1, aov_spp=4)
+        hist, length = hs.temporal_blend(c, motion, hist, prev_depth, length)
+        rgba_loop = hs.tonemap(hs.denoise(hist, var, aov))
+        prev_depth = aov[..., 6].copy()
+        t_loop.append(time.perf_counter() - t0)
+    seq = hs.sequence(filter=True, aov_spp=4)
+    t_seq, stages = [], []
+    for k in range(frames):
+        t0 = time.perf_counter()
+        r = seq.frame(want=("rgba",), spp=4, seed=k + 1)
+        t_seq.append(time.perf_counter() - t0)
+        stages.append(r["info"])
+    same = float((r["rgba"] == rgba_loop).mean())
+    med = lambda t: 1e3 * float(np.median(t[1:]))  # noqa: E731
+    print("%dx%d, %d frames each, the first not counted" % (W, H, frames))
+    print("host-array loop   median wall %.2f ms per frame (min %.2f, max %.2f)" % (med(t_loop), 1e3 * min(t_loop[1:]), 1e3 * max(t_loop[1:])))
+    print("sequence          median wall %.2f ms per frame (min %.2f, max %.2f)" % (med(t_seq), 1e3 * min(t_seq[1:]), 1e3 * max(t_seq[1:])))
+    print("sequence stages, median event time in ms: " + ", ".join(
+        "%s %.3f" % (k[3:], float(np.median([s[k] for s in stages[1:]]))) for k in ("ms_render", "ms_aov", "ms_motion", "ms_accumulate", "ms_filter")))
+    print("sequence ms_total (wall time inside the call) median %.2f ms" % float(np.median([s["ms_total"] for s in stages[1:]])))
+    print("last frame: %.2f %% of the rgba bytes equal the loop's (the two filters are guided by different variances)" % (100 * same))
+    seq.close()
+    hs.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--trace", help="a rocprofv3 kernel-trace CSV of a run of this script with the same --repeat: print the kernel time per pass")
@@ -78,12 +118,18 @@ def main():
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--scene", default="chess", choices=["chess", "cornell"])
     ap.add_argument("--repeat", type=int, default=5)
+    ap.add_argument("--sequence", action="store_true", help="time the host-array frame loop against HipSequence.frame")
+    ap.add_argument("--frames", type=int, default=8, help="--sequence: frames per way (at least 6: one warm-up and five counted)")
     a = ap.parse_args()
     if a.trace:
         return summarize_trace(a.trace, a.repeat)
     pkg = mcpt_loader.load()
     W, H = a.width, a.height
     sd = pkg.scenes.chess_scene(width=W, height=H, spp=4) if a.scene == "chess" else pkg.scenes.cornell_demo(W, H, 4)
+    if a.sequence:
+        if a.frames < 6:
+            sys.exit("--frames must be at least 6")
+        return sequence_timing(pkg, sd, W, H, a.frames)
     hs = pkg.HipScene(sd)
     r = hs.render_denoised(spp=4, seed=1, aov_spp=4)  # (also sizes the workspace the AOV and motion passes run in)
     color, var, aov = r["fb"], r["variance"], r["aov"]
