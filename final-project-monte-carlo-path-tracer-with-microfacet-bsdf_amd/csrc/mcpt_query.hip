@@ -1,5 +1,7 @@
 // The query entry points of the C ABI (include/mcpt.h): mcpt_intersect, mcpt_cast_rays, mcpt_camera_rays, the tone map, and the debug
 // entry points.  Each stages its arguments in call-local device buffers (mcpt_cast_rays: in the wavefront workspace of pool 0).
+#include <cmath>
+
 #include "mcpt_host.h"
 
 using namespace mcpt;
@@ -178,6 +180,65 @@ int mcpt_debug_material(mcpt_scene *sc, int kind, int64_t n, const float *in, co
     HIP_TRY(upload(dS, sel, (size_t)n * 3));
     launch_debug_material(sc->view, kind, (uint32_t)n, dI.p, dS.p, dO.p, nullptr);
     HIP_TRY(download(out, dO, (size_t)n * 4));
+    return MCPT_OK;
+}
+
+int mcpt_debug_shadow(mcpt_scene *sc, int32_t list, int64_t n, const float *origins, const float *dirs, const float *dist, const uint8_t *found,
+                      const int32_t *shard, uint8_t *visible) {
+    if (!sc || n < 0 || list < 0 || list > 1 || (n > 0 && (!origins || !dirs || !dist || !found || !visible)))
+        return fail(MCPT_ERR_ARG, "mcpt_debug_shadow: bad argument");
+    if (n > (int64_t)1 << 22) return fail(MCPT_ERR_ARG, "mcpt_debug_shadow: too many rays for one call");
+    // the queue as k_direct leaves it (Counters, csrc/mcpt_kernels.h): per shard, found entries from the front of its region, the others
+    // from its back
+    uint32_t nf[kShadowShards] = {}, nw[kShadowShards] = {};
+    std::vector<uint32_t> slot(n);  // ray i: its shard and its rank among the shard's entries of its kind
+    for (int64_t i = 0; i < n; ++i) {
+        if (found[i] > 1) return fail(MCPT_ERR_ARG, "mcpt_debug_shadow: found must be 0 or 1");
+        if (!(dist[i] > 0.f) || !std::isfinite(dist[i])) return fail(MCPT_ERR_ARG, "mcpt_debug_shadow: dist must be finite and positive");
+        const int64_t s = shard ? (int64_t)shard[i] : (i / 64) % (int64_t)kShadowShards;
+        if (s < 0 || s >= (int64_t)kShadowShards) return fail(MCPT_ERR_ARG, "mcpt_debug_shadow: shard out of range");
+        slot[i] = (uint32_t)s << 24 | (found[i] ? nf[s]++ : nw[s]++);  // (a rank is below 2^22)
+    }
+    if (n == 0) return MCPT_OK;
+    uint32_t fill = 0;  // the fullest shard
+    for (uint32_t s = 0; s < kShadowShards; ++s) fill = std::max(fill, nf[s] + nw[s]);
+    const uint32_t cap = (fill + 63u) / 64u * 64u * kShadowShards;  // the smallest capacity whose region holds `fill` entries
+    const uint32_t region = shadow_region(cap);
+    std::vector<float4> qo((size_t)kShadowShards * region, make_float4(0.f, 0.f, 0.f, 0.f)), qd(qo);
+    for (int64_t i = 0; i < n; ++i) {
+        const uint32_t s = slot[i] >> 24, k = slot[i] & 0xffffffu;
+        const uint32_t e = found[i] ? s * region + k : (s + 1u) * region - 1u - k;
+        uint32_t bits = (uint32_t)i;
+        float w;
+        std::memcpy(&w, &bits, sizeof w);
+        qo[e] = make_float4(origins[3 * i], origins[3 * i + 1], origins[3 * i + 2], w);
+        qd[e] = make_float4(dirs[3 * i], dirs[3 * i + 1], dirs[3 * i + 2], dist[i]);
+    }
+    std::vector<Counters> hc(1);
+    std::memset(static_cast<void *>(hc.data()), 0, sizeof(Counters));
+    for (uint32_t s = 0; s < kShadowShards; ++s) {
+        hc[0].n_shadow[list][s].v = nf[s];
+        hc[0].n_shadow_w[list][s].v = nw[s];
+    }
+    HIP_TRY(hipSetDevice(sc->device));
+    DevBuf<float4> dO, dD;
+    DevBuf<Counters> dC;
+    DevBuf<float> dV;
+    HIP_TRY(upload(dO, qo));
+    HIP_TRY(upload(dD, qd));
+    HIP_TRY(upload(dC, hc));
+    HIP_TRY(upload(dV, std::vector<float>(n, 1.f)));
+    RetryBufs retry;
+    if (stack_uses_retry(sc->view.height)) {
+        const uint32_t want[3] = {1u, (uint32_t)n, 1u};  // (the list holds queue positions: at most n)
+        HIP_TRY(retry.alloc(want));
+    }
+    const Scratch X{nullptr, nullptr, nullptr, nullptr, dO.p, dD.p};
+    launch_trace_shadow(sc->view, dC.p, list, (uint32_t)n, cap, X, dV.p, sc->knobs.shadow_grid_per_cu, retry.list(1), nullptr);
+    HIP_TRY(hipGetLastError());
+    std::vector<float> c(n);
+    HIP_TRY(download(c.data(), dV, n));
+    for (int64_t i = 0; i < n; ++i) visible[i] = c[i] != 0.f;
     return MCPT_OK;
 }
 

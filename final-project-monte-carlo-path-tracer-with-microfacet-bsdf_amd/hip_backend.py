@@ -17,7 +17,7 @@ CHECK_LIB_PATH = os.path.join(HERE, "libmcpt_hip_check.so")  # the checking buil
 
 EXPORTS = ["mcpt_scene_create", "mcpt_scene_destroy", "mcpt_render", "mcpt_render_device", "mcpt_render_adaptive", "mcpt_render_aovs",
            "mcpt_render_aovs_ex", "mcpt_denoise", "mcpt_render_denoised", "mcpt_intersect",
-           "mcpt_cast_rays", "mcpt_camera_rays", "mcpt_scene_get_info", "mcpt_bvh_dump", "mcpt_scene_create_ex", "mcpt_scene_dump_bvh", "mcpt_tonemap", "mcpt_tonemap_device", "mcpt_debug_fmath", "mcpt_debug_material", "mcpt_debug_scene", "mcpt_debug_counters",
+           "mcpt_cast_rays", "mcpt_camera_rays", "mcpt_scene_get_info", "mcpt_bvh_dump", "mcpt_scene_create_ex", "mcpt_scene_dump_bvh", "mcpt_tonemap", "mcpt_tonemap_device", "mcpt_debug_fmath", "mcpt_debug_material", "mcpt_debug_scene", "mcpt_debug_shadow", "mcpt_debug_counters",
            "mcpt_scene_update", "mcpt_group_update", "mcpt_transform_triangles",
            "mcpt_scene_snapshot", "mcpt_render_motion", "mcpt_temporal_blend", "mcpt_temporal_accumulate",
            "mcpt_sequence_create", "mcpt_sequence_frame", "mcpt_sequence_reset", "mcpt_sequence_destroy",
@@ -232,6 +232,8 @@ def lib(path=None):
         L.mcpt_debug_fmath.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
         L.mcpt_debug_scene.restype = C.c_int
         L.mcpt_debug_scene.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p]
+        L.mcpt_debug_shadow.restype = C.c_int
+        L.mcpt_debug_shadow.argtypes = [C.c_void_p, C.c_int32, C.c_int64] + [C.c_void_p] * 6
         L.mcpt_debug_material.restype = C.c_int
         L.mcpt_debug_material.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
         L.mcpt_scene_update.restype = C.c_int
@@ -580,6 +582,23 @@ class HipScene:
         prim = np.zeros(n, dtype=np.int32)
         _check(self.L.mcpt_intersect(self.h, n, _ptr(o), _ptr(d), _ptr(t), _ptr(prim)), L=self.L)
         return t, prim
+
+    def shadow_visible(self, origins, dirs, dist, found=None, shard=None, list=0):
+        """mcpt_debug_shadow: the render loop's shadow query (k_trace_shadow, its retrace included) for rays of the caller's -> bool [n]:
+        the closest hit of ray i lies within EPSILON of dist[i].  found[i] = 1 asserts that some primitive is hit within EPSILON of dist[i]
+        (default: no assertion); shard[i] in 0..31 places ray i in the sharded queue (default: (i // 64) % 32); list: 0 or 1."""
+        o = np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(dirs, dtype=np.float32).reshape(-1, 3)
+        n = len(o)
+        ds = np.ascontiguousarray(dist, dtype=np.float32).reshape(-1)
+        f = np.zeros(n, dtype=np.uint8) if found is None else np.ascontiguousarray(found, dtype=np.uint8).reshape(-1)
+        sh = None if shard is None else np.ascontiguousarray(shard, dtype=np.int32).reshape(-1)
+        if len(d) != n or len(ds) != n or len(f) != n or (sh is not None and len(sh) != n):
+            raise ValueError("shadow_visible: the arrays do not describe %d rays" % n)
+        vis = np.zeros(n, dtype=np.uint8)
+        _check(self.L.mcpt_debug_shadow(self.h, int(list), n, _ptr(o), _ptr(d), _ptr(ds), _ptr(f), None if sh is None else _ptr(sh), _ptr(vis)),
+               L=self.L)
+        return vis.astype(bool)
 
     def cast_rays(self, origins, dirs, pixel, sample, channel, **kw):
         o = np.ascontiguousarray(origins, dtype=np.float32)

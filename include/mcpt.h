@@ -588,6 +588,26 @@ int mcpt_debug_material(mcpt_scene *scene, int kind, int64_t n, const float *in,
  * Scene::sampleEnv (Scene.hpp:60-99; kind 1: in = a direction per row, out = rgb) on arrays. */
 int mcpt_debug_scene(mcpt_scene *scene, int kind, int64_t n, const float *in, float *out);
 
+/* Diagnostic: the shadow-visibility query of the render loop (k_trace_shadow and, for trees that use the retry flavour of the
+ * traversal stack, k_retrace_shadow: the product's own launch, unchanged) for n rays of the caller's, so that tests can compare it
+ * ray by ray with the rule of Scene.cpp:74-75: a light sample is visible iff the CLOSEST hit of the ray lies within EPSILON (1e-4)
+ * of the light distance.  origins, dirs: n x 3 floats; dist: n floats, finite and > 0; visible: n bytes, 1 or 0.
+ * The call fills a shadow queue of its own exactly as the direct-lighting kernel leaves it: ray i goes to shard shard[i] (0..31;
+ * shard == NULL: shard (i / 64) % 32, where a wave of that kernel would put it), entries with found[i] == 1 from the front of the
+ * shard's region, the others from its back; the queue's capacity is the smallest whose region holds the fullest shard.  list (0 or
+ * 1) selects which of the two sets of per-shard counters carries the counts, as the path list a launch belongs to does.
+ * found[i] == 1 is the caller's ASSERTION that some primitive is hit within EPSILON of dist[i] -- what the direct-lighting kernel
+ * has established by testing the sampled light primitive when it sets the flag.  The query then skips its window search and only
+ * looks for an occluder.  With a false assertion the call returns what the render loop would compute from such an entry; nothing
+ * is promised about that value.  found[i] == 0 is always truthful: the full query runs.
+ * Origins are expected at scene scale, like every origin of the render loop (a point on a surface).
+ * Memory: the queue holds 32 regions of the fullest shard's size (rounded up to 64 entries), 32 bytes per entry, on the host and on
+ * the device: 8 MiB per 2^18 rays with the default placement, 2 x 2 GiB for 2^22 rays placed in ONE shard (MCPT_ERR_OOM if that fails).
+ * MCPT_ERR_ARG, before any device call: a null scene; list outside 0..1; n < 0 or n > 2^22; n > 0 with a null array other than
+ * shard; a shard index outside 0..31; found[i] > 1; a dist[i] that is not finite or not > 0.  n == 0 is a valid no-op. */
+int mcpt_debug_shadow(mcpt_scene *scene, int32_t list, int64_t n, const float *origins, const float *dirs, const float *dist,
+                      const uint8_t *found, const int32_t *shard /* nullable */, uint8_t *visible);
+
 /* Diagnostic: counters of the checking build (libmcpt_hip_check.so, compiled with -DMCPT_CHECK_DIRECT_SKIP; the traversal
  * entries are filled only by a -DMCPT_TRAVERSAL_STATS build); all zero in the product build.
  *   out[0..5]   closest-hit rays: rays, node visits, primitive tests, hits, 64 x wave iterations, -
