@@ -1,7 +1,8 @@
 // Frame sequences (include/mcpt.h: mcpt_temporal_accumulate, mcpt_sequence_*): the frame loop of temporal reuse with its history, the
 // variance of the accumulated frame and every working buffer resident on the device.  A frame is the passes of csrc/mcpt_render.hip
 // (csrc/mcpt_frame.h) on the sequence's buffers, k_temporal_accumulate (csrc/mcpt_temporal.hip) between the two history sets, the filter
-// and the tone map, all queued on one stream; only the outputs the caller asks for are copied to the host.
+// and the tone map, all queued on one stream; only the outputs the caller asks for are copied to the host.  A sequence created with
+// history rejection (mcpt_sequence_create_ex) runs k_temporal_accumulate_ex instead and keeps a normal and a flags plane per history set.
 #include <new>
 
 #include "mcpt_frame.h"
@@ -13,11 +14,15 @@ namespace {
 // One history set: what k_temporal_accumulate reads of the previous frame and writes for the next one.
 struct History {
     DevBuf<float> color, variance, depth, len;
-    hipError_t alloc(size_t n_px) {
+    DevBuf<float> normal;   // first-hit normals, 3 per pixel (history rejection with the normal test only)
+    DevBuf<uint8_t> flags;  // what the rejection did to each pixel of the frame that wrote this set (either switch on)
+    hipError_t alloc(size_t n_px, bool with_normal, bool with_flags) {
         hipError_t e = color.alloc(n_px * 3);
         if (e == hipSuccess) e = variance.alloc(n_px);
         if (e == hipSuccess) e = depth.alloc(n_px);
         if (e == hipSuccess) e = len.alloc(n_px);
+        if (e == hipSuccess && with_normal) e = normal.alloc(n_px * 3);
+        if (e == hipSuccess && with_flags) e = flags.alloc(n_px);
         return e;
     }
     hipError_t clear(size_t n_px) {
@@ -25,6 +30,8 @@ struct History {
         if (e == hipSuccess) e = hipMemset(variance.p, 0, n_px * sizeof(float));
         if (e == hipSuccess) e = hipMemset(depth.p, 0, n_px * sizeof(float));
         if (e == hipSuccess) e = hipMemset(len.p, 0, n_px * sizeof(float));
+        if (e == hipSuccess && normal.p) e = hipMemset(normal.p, 0, n_px * 3 * sizeof(float));
+        if (e == hipSuccess && flags.p) e = hipMemset(flags.p, 0, n_px);
         return e;
     }
 };
@@ -40,6 +47,7 @@ struct mcpt_sequence {
     int W = 0, H = 0;
     mcpt_sequence_opts opts{};
     tp::Opts temporal{};
+    tp::HistOpts reject{};  // both switches 0: the frame runs k_temporal_accumulate, as a sequence of mcpt_sequence_create
     dn::Opts denoise{};
     History hist[2];
     int cur = 0;        // the set that holds the history of the previous frame; a frame writes the other one
@@ -86,6 +94,58 @@ int mcpt_temporal_accumulate(mcpt_scene *sc, int32_t width, int32_t height, cons
     return MCPT_OK;
 }
 
+int mcpt_temporal_accumulate_ex(mcpt_scene *sc, int32_t width, int32_t height, const float *color_host, const float *variance_host, const float *motion_host,
+                                const float *normal_host, const float *prev_color_host, const float *prev_variance_host, const float *prev_depth_host,
+                                const float *prev_len_host, const float *prev_normal_host, const mcpt_temporal_opts *opts, const mcpt_history_opts *hopts,
+                                float *out_color_host, float *out_variance_host, float *out_len_host, uint8_t *out_flags_host) {
+    if (!sc || !color_host || !variance_host || !motion_host || !prev_color_host || !prev_variance_host || !prev_depth_host || !prev_len_host || !opts ||
+        !hopts || !out_color_host || !out_variance_host || !out_len_host)
+        return fail(MCPT_ERR_ARG, "mcpt_temporal_accumulate_ex: null argument");
+    if (!frame_ok(width, height)) return fail(MCPT_ERR_ARG, "mcpt_temporal_accumulate_ex: width and height must be positive (and the frame not too large)");
+    tp::Opts o;
+    tp::HistOpts ho;
+    if (tp::resolve_opts(*opts, o) != 0) return fail(MCPT_ERR_ARG, "mcpt_temporal_accumulate_ex: option out of range");
+    if (tp::resolve_history_opts(*hopts, ho) != 0) return fail(MCPT_ERR_ARG, "mcpt_temporal_accumulate_ex: history option out of range");
+    if (ho.normal_test && (!normal_host || !prev_normal_host)) return fail(MCPT_ERR_ARG, "mcpt_temporal_accumulate_ex: normal_test needs both normal arrays");
+    HIP_TRY(hipSetDevice(sc->device));
+    (void)hipGetLastError();
+    const size_t n_px = (size_t)width * height;
+    const bool reject = ho.normal_test || ho.color_clamp;
+    DevBuf<float> col, var, mot, nrm, pcol, pvar, pz, plen, pnrm, out, ovar, olen;
+    DevBuf<uint8_t> oflags;
+    HIP_TRY(out.alloc(n_px * 3));
+    HIP_TRY(ovar.alloc(n_px));
+    HIP_TRY(olen.alloc(n_px));
+    if (reject && out_flags_host) HIP_TRY(oflags.alloc(n_px));
+    HIP_TRY(upload(col, color_host, n_px * 3));
+    HIP_TRY(upload(var, variance_host, n_px));
+    HIP_TRY(upload(mot, motion_host, n_px * 4));
+    HIP_TRY(upload(pcol, prev_color_host, n_px * 3));
+    HIP_TRY(upload(pvar, prev_variance_host, n_px));
+    HIP_TRY(upload(pz, prev_depth_host, n_px));
+    HIP_TRY(upload(plen, prev_len_host, n_px));
+    if (ho.normal_test) {
+        HIP_TRY(upload(nrm, normal_host, n_px * 3));
+        HIP_TRY(upload(pnrm, prev_normal_host, n_px * 3));
+    }
+    if (reject)
+        launch_temporal_accumulate_ex(width, height, o, ho, col.p, var.p, mot.p, nrm.p, 3, pcol.p, pvar.p, pz.p, plen.p, pnrm.p, nullptr, 0, out.p, ovar.p, nullptr,
+                                      olen.p, nullptr, oflags.p, nullptr);
+    else  // both switches 0: mcpt_temporal_accumulate's kernel
+        launch_temporal_accumulate(width, height, o, col.p, var.p, mot.p, pcol.p, pvar.p, pz.p, plen.p, nullptr, 0, out.p, ovar.p, nullptr, olen.p, nullptr);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(download(out_color_host, out, n_px * 3));
+    HIP_TRY(download(out_variance_host, ovar, n_px));
+    HIP_TRY(download(out_len_host, olen, n_px));
+    if (out_flags_host) {
+        if (reject)
+            HIP_TRY(download(out_flags_host, oflags, n_px));
+        else
+            std::memset(out_flags_host, 0, n_px);
+    }
+    return MCPT_OK;
+}
+
 void mcpt_sequence_destroy(mcpt_sequence *seq) {
     if (!seq) return;
     (void)hipSetDevice(seq->device);
@@ -94,9 +154,16 @@ void mcpt_sequence_destroy(mcpt_sequence *seq) {
 }
 
 int mcpt_sequence_create(mcpt_scene *sc, int32_t width, int32_t height, const mcpt_sequence_opts *opts, mcpt_sequence **out) {
+    return mcpt_sequence_create_ex(sc, width, height, opts, nullptr, out);
+}
+
+int mcpt_sequence_create_ex(mcpt_scene *sc, int32_t width, int32_t height, const mcpt_sequence_opts *opts, const mcpt_history_opts *hopts,
+                            mcpt_sequence **out) {
     const auto bad = [](const char *what) { return fail(MCPT_ERR_ARG, std::string("mcpt_sequence_create: ") + what); };
     if (!sc || !opts || !out) return bad("null argument");
     *out = nullptr;
+    tp::HistOpts ho{};
+    if (hopts && tp::resolve_history_opts(*hopts, ho) != 0) return bad("history option out of range");
     if (!frame_ok(width, height)) return bad("width and height must be positive (and the frame not too large)");
     tp::Opts to;
     dn::Opts dno;
@@ -115,6 +182,7 @@ int mcpt_sequence_create(mcpt_scene *sc, int32_t width, int32_t height, const mc
     seq->H = height;
     seq->opts = *opts;
     seq->temporal = to;
+    seq->reject = ho;
     seq->denoise = dno;
     const size_t n_px = (size_t)width * height;
     hipError_t e = hipSuccess;
@@ -122,7 +190,7 @@ int mcpt_sequence_create(mcpt_scene *sc, int32_t width, int32_t height, const mc
         if (e == hipSuccess) e = buf.alloc(n);
     };
     for (int k = 0; k < 2; ++k) {
-        if (e == hipSuccess) e = seq->hist[k].alloc(n_px);
+        if (e == hipSuccess) e = seq->hist[k].alloc(n_px, ho.normal_test != 0, ho.normal_test || ho.color_clamp);
         if (e == hipSuccess) e = seq->hist[k].clear(n_px);
     }
     also(seq->fb, n_px * 3);
@@ -144,6 +212,15 @@ int mcpt_sequence_create(mcpt_scene *sc, int32_t width, int32_t height, const mc
         return rc;
     }
     *out = seq;
+    return MCPT_OK;
+}
+
+int mcpt_sequence_flags(mcpt_sequence *seq, uint8_t *flags_host) {
+    if (!seq || !flags_host) return fail(MCPT_ERR_ARG, "mcpt_sequence_flags: null argument");
+    const DevBuf<uint8_t> &flags = seq->hist[seq->cur].flags;  // (the set the last successful frame wrote)
+    if (!flags.p) return fail(MCPT_ERR_ARG, "mcpt_sequence_flags: the sequence was created without history rejection and keeps no flags");
+    HIP_TRY(hipSetDevice(seq->device));
+    HIP_TRY(download(flags_host, flags, (size_t)seq->W * seq->H));
     return MCPT_OK;
 }
 
@@ -202,8 +279,13 @@ int mcpt_sequence_frame(mcpt_sequence *seq, const mcpt_camera *cam, const mcpt_p
     HIP_TRY(hipEventRecord(ev[3], st));
     // 5. previous history set -> the other one
     if (seq->fresh) HIP_TRY(hipMemsetAsync(prev.len.p, 0, n_px * sizeof(float), st));
-    launch_temporal_accumulate(W, H, seq->temporal, seq->fb.p, seq->var.p, seq->motion.p, prev.color.p, prev.variance.p, prev.depth.p, prev.len.p,
-                               first_hit + 6, 8, next.color.p, next.variance.p, next.depth.p, next.len.p, st);
+    if (seq->reject.normal_test || seq->reject.color_clamp)  // (the normals come from the AOVs the depth comes from)
+        launch_temporal_accumulate_ex(W, H, seq->temporal, seq->reject, seq->fb.p, seq->var.p, seq->motion.p, first_hit + 3, 8, prev.color.p, prev.variance.p,
+                                      prev.depth.p, prev.len.p, prev.normal.p, first_hit + 6, 8, next.color.p, next.variance.p, next.depth.p, next.len.p,
+                                      next.normal.p, next.flags.p, st);
+    else
+        launch_temporal_accumulate(W, H, seq->temporal, seq->fb.p, seq->var.p, seq->motion.p, prev.color.p, prev.variance.p, prev.depth.p, prev.len.p,
+                                   first_hit + 6, 8, next.color.p, next.variance.p, next.depth.p, next.len.p, st);
     HIP_TRY(hipEventRecord(ev[4], st));
     // 6., 7. the filter and the tone map
     if (filter) launch_denoise(W, H, seq->denoise, next.color.p, next.variance.p, seq->aov.p, seq->db.rec[0].p, seq->db.rec[1].p, seq->db.grad.p, seq->out.p, st);

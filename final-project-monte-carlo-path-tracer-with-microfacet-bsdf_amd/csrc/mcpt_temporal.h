@@ -59,6 +59,31 @@ MCPT_TP int resolve_opts(const mcpt_temporal_opts &o, Opts &out) {
     return 0;
 }
 
+// History rejection after the defaults of include/mcpt.h have been applied (mcpt_history_opts).
+constexpr float kDefaultNormalMin = 0.9f;
+constexpr float kDefaultClampK = 1.0f;
+struct HistOpts {
+    int32_t normal_test, color_clamp;  // 0 or 1
+    float normal_min;                  // in (0, 1]
+    float clamp_k;                     // > 0, finite
+};
+
+// 0 on success, -1 if an option is out of range.  Both values are checked whether or not their switch is on.
+MCPT_TP int resolve_history_opts(const mcpt_history_opts &o, HistOpts &out) {
+    for (int k = 0; k < 4; ++k)
+        if (o.reserved[k] != 0) return -1;
+    if ((o.normal_test != 0 && o.normal_test != 1) || (o.color_clamp != 0 && o.color_clamp != 1)) return -1;
+    const float nm = o.normal_min == 0.0f ? kDefaultNormalMin : o.normal_min;
+    if (!(nm > 0.0f && nm <= 1.0f)) return -1;  // (NaN fails)
+    const float ck = o.clamp_k == 0.0f ? kDefaultClampK : o.clamp_k;
+    if (!(ck > 0.0f && ck <= 3.0e38f)) return -1;  // (positive and finite; NaN fails)
+    out.normal_test = o.normal_test;
+    out.color_clamp = o.color_clamp;
+    out.normal_min = nm;
+    out.clamp_k = ck;
+    return 0;
+}
+
 MCPT_TP bool finite_f(float x) { return x - x == 0.0f; }  // false for +-inf and NaN
 
 /* The screen position of p: q = orient^T (p - eye) in the 3-term dot order x + (y + z); the inverse of the camera ray's x, y
@@ -118,21 +143,25 @@ struct Taps {
     float sw, s0, s1, s2;  // sum of w, sum of w * colour
     float sv;              // sum of (w * w) * prev_variance (accumulate_pixel only)
     float nmin;            // the smallest prev_len of the used taps
+    bool nskip;            // the normal test skipped a tap that every older test had passed (kNorm only)
 };
 
 /* The tap loop the blend and the accumulation share: the four bilinear taps of pixel (i, j) moved by its motion record mv, in tap order,
  * with every skip of the rule.  false if no tap is left.  kVar: also sum the taps' variances (prev_variance is not read without it).
- * The taps' positions are tested in float before they become indices, so a motion that is huge or not finite reads nothing. */
-template <bool kVar>
+ * The taps' positions are tested in float before they become indices, so a motion that is huge or not finite reads nothing.
+ * kNorm: the normal test of mcpt_temporal_accumulate_ex after the depth test: a tap is skipped if !(d >= normal_min), d the 3-term dot
+ * x + (y + z) of prev_normal[tap] and this pixel's normal n (prev_normal is not read without it). */
+template <bool kVar, bool kNorm = false>
 MCPT_TP bool gather_taps(int W, int H, int i, int j, const float *mv, const float *prev_color, const float *prev_variance, const float *prev_depth,
-                         const float *prev_len, const Opts &o, Taps &t) {
+                         const float *prev_len, const Opts &o, Taps &t, const float *prev_normal = nullptr, const float *n3 = nullptr,
+                         float normal_min = 0.0f) {
     const float fx = (float)i + mv[0], fy = (float)j + mv[1];
     const float x0 = floorf(fx), y0 = floorf(fy);
     const float a = fx - x0, b = fy - y0;
     const float wx[2] = {1.0f - a, a}, wy[2] = {1.0f - b, b};
     const float zp = mv[2], ztol = o.depth_tol * zp;
     float sw = 0.0f, s0 = 0.0f, s1 = 0.0f, s2 = 0.0f, sv = 0.0f, nmin = 0.0f;
-    bool any = false;
+    bool any = false, nskip = false;
 #if defined(__HIP_DEVICE_COMPILE__)
 #pragma unroll
 #endif
@@ -148,6 +177,13 @@ MCPT_TP bool gather_taps(int W, int H, int i, int j, const float *mv, const floa
         if (!(finite_f(p0) && finite_f(p1) && finite_f(p2))) continue;
         const float dz = prev_depth[q] - zp;
         if (!((dz < 0.0f ? -dz : dz) <= ztol)) continue;  // (a NaN depth on either side rejects the tap)
+        if (kNorm) {
+            const float d = prev_normal[q * 3] * n3[0] + (prev_normal[q * 3 + 1] * n3[1] + prev_normal[q * 3 + 2] * n3[2]);
+            if (!(d >= normal_min)) {  // (a NaN normal on either side rejects the tap)
+                nskip = true;
+                continue;
+            }
+        }
         sw = sw + w;
         s0 = s0 + w * p0;
         s1 = s1 + w * p1;
@@ -162,6 +198,7 @@ MCPT_TP bool gather_taps(int W, int H, int i, int j, const float *mv, const floa
     t.s2 = s2;
     t.sv = sv;
     t.nmin = nmin;
+    t.nskip = nskip;
     return any;
 }
 
@@ -230,6 +267,95 @@ MCPT_TP void accumulate_pixel(int W, int H, int i, int j, const float *color, co
     out_len[m] = len;
 }
 
+/* One channel of the neighbourhood clamp: the history value h against the mean and deviation of the n finite 3 x 3 neighbours, whose sums
+ * s = sum c and s2 = sum c*c were taken from 0 in neighbour order.  max(x, 0) is x > 0 ? x : 0 (a NaN gives 0), and the clamp is two
+ * comparisons, t = h < lo ? lo : h;  t > hi ? hi : t, so a bound that is NaN leaves h as it is. */
+MCPT_TP float clamp_channel(float h, float s, float s2, float fn, float clamp_k) {
+    const float mu = s / fn;
+    const float v = s2 / fn - mu * mu;
+    const float var = v > 0.0f ? v : 0.0f;
+    const float sd = sqrtf(var);
+    const float ksd = clamp_k * sd;
+    const float lo = mu - ksd, hi = mu + ksd;
+    const float t = h < lo ? lo : h;
+    return t > hi ? hi : t;
+}
+
+/* accumulate_pixel with history rejection (include/mcpt.h: mcpt_temporal_accumulate_ex has the rule).  normal: this frame's first-hit
+ * normal of pixel m at normal[normal_stride m ..] (3 for a packed array, 8 for the normal channels of an AOV array); prev_normal packed.
+ * ho.normal_test 0: neither is read.  out_flags (nullable): bit 0 the normal test skipped a tap, bit 1 the clamp moved the history; 0
+ * where the pixel takes no history.  With both switches 0 every output is accumulate_pixel's, expression for expression. */
+MCPT_TP void accumulate_pixel_ex(int W, int H, int i, int j, const float *color, const float *variance, const float *motion, const float *normal,
+                                 int normal_stride, const float *prev_color, const float *prev_variance, const float *prev_depth, const float *prev_len,
+                                 const float *prev_normal, const Opts &o, const HistOpts &ho, float *out_color, float *out_variance, float *out_len,
+                                 uint8_t *out_flags) {
+    const size_t m = (size_t)j * W + i;
+    const float c0 = color[m * 3], c1 = color[m * 3 + 1], c2 = color[m * 3 + 2];
+    const float vc = variance[m];
+    const float *mv = motion + m * 4;
+    float r0 = c0, r1 = c1, r2 = c2, rv = vc, len = 1.0f;
+    uint8_t flags = 0;
+    Taps t;
+    if (mv[3] > 0.0f && finite_f(c0) && finite_f(c1) && finite_f(c2)) {
+        bool any;
+        if (ho.normal_test) {
+            const float n3[3] = {normal[m * (size_t)normal_stride], normal[m * (size_t)normal_stride + 1], normal[m * (size_t)normal_stride + 2]};
+            any = gather_taps<true, true>(W, H, i, j, mv, prev_color, prev_variance, prev_depth, prev_len, o, t, prev_normal, n3, ho.normal_min);
+        } else {
+            any = gather_taps<true>(W, H, i, j, mv, prev_color, prev_variance, prev_depth, prev_len, o, t);
+        }
+        if (any) {
+            float h0 = t.s0 / t.sw, h1 = t.s1 / t.sw, h2 = t.s2 / t.sw;
+            bool clamped = false;
+            if (ho.normal_test && t.nskip) flags |= 1;
+            if (ho.color_clamp) {
+                float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, b0 = 0.0f, b1 = 0.0f, b2 = 0.0f;
+                int n = 0;
+                for (int dy = -1; dy <= 1; ++dy)
+                    for (int dx = -1; dx <= 1; ++dx) {
+                        const int x = i + dx, y = j + dy;
+                        if (x < 0 || x >= W || y < 0 || y >= H) continue;
+                        const size_t q = (size_t)y * W + x;
+                        const float q0 = color[q * 3], q1 = color[q * 3 + 1], q2 = color[q * 3 + 2];
+                        if (!(finite_f(q0) && finite_f(q1) && finite_f(q2))) continue;
+                        a0 = a0 + q0;
+                        a1 = a1 + q1;
+                        a2 = a2 + q2;
+                        b0 = b0 + q0 * q0;
+                        b1 = b1 + q1 * q1;
+                        b2 = b2 + q2 * q2;
+                        ++n;
+                    }
+                const float fn = (float)n;  // (n >= 1: the pixel itself is finite)
+                const float g0 = clamp_channel(h0, a0, b0, fn, ho.clamp_k);
+                const float g1 = clamp_channel(h1, a1, b1, fn, ho.clamp_k);
+                const float g2 = clamp_channel(h2, a2, b2, fn, ho.clamp_k);
+                clamped = g0 != h0 || g1 != h1 || g2 != h2;
+                h0 = g0;
+                h1 = g1;
+                h2 = g2;
+                if (clamped) flags |= 2;
+            }
+            const float n1 = t.nmin + 1.0f;
+            const float N = n1 < o.max_history ? n1 : o.max_history;
+            const float k = 1.0f / N;
+            r0 = h0 + (c0 - h0) * k;
+            r1 = h1 + (c1 - h1) * k;
+            r2 = h2 + (c2 - h2) * k;
+            len = N;
+            const float hv = t.sv / (t.sw * t.sw);
+            const float omk = 1.0f - k;
+            if (!clamped && finite_f(hv) && hv >= 0.0f) rv = (omk * omk) * hv + (k * k) * vc;
+        }
+    }
+    out_color[m * 3] = r0;
+    out_color[m * 3 + 1] = r1;
+    out_color[m * 3 + 2] = r2;
+    out_variance[m] = rv;
+    out_len[m] = len;
+    if (out_flags) out_flags[m] = flags;
+}
+
 }  // namespace tp
 }  // namespace mcpt
 
@@ -254,6 +380,14 @@ void launch_temporal_blend(int W, int H, const tp::Opts &o, const float *color, 
 void launch_temporal_accumulate(int W, int H, const tp::Opts &o, const float *color, const float *variance, const float *motion, const float *prev_color,
                                 const float *prev_variance, const float *prev_depth, const float *prev_len, const float *depth, int depth_stride,
                                 float *out_color, float *out_variance, float *out_depth, float *out_len, hipStream_t st);
+// The blend with variance and history rejection of a W x H frame (k_temporal_accumulate_ex; at least one switch of ho is on).  normal: this
+// frame's first-hit normals, normal_stride floats from pixel to pixel (3 packed, 8 inside an AOV array); read only with ho.normal_test, as
+// prev_normal (packed).  out_normal != nullptr: the pixel's normal is also copied there (packed: the history's normal plane), as depth is
+// into out_depth.  out_flags: one byte per pixel, nullable.
+void launch_temporal_accumulate_ex(int W, int H, const tp::Opts &o, const tp::HistOpts &ho, const float *color, const float *variance, const float *motion,
+                                   const float *normal, int normal_stride, const float *prev_color, const float *prev_variance, const float *prev_depth,
+                                   const float *prev_len, const float *prev_normal, const float *depth, int depth_stride, float *out_color,
+                                   float *out_variance, float *out_depth, float *out_len, float *out_normal, uint8_t *out_flags, hipStream_t st);
 }  // namespace mcpt
 #endif
 #endif  // MCPT_TEMPORAL_H

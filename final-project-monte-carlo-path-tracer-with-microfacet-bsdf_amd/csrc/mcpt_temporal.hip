@@ -12,6 +12,13 @@
 // Accumulate (mcpt_temporal_accumulate, mcpt_sequence_frame):
 //   k_temporal_accumulate  the same shape; the blend with the variance of its result (tp::accumulate_pixel), and the frame's first-hit
 //                     depth copied into the history's depth plane, so that one launch leaves the history complete for the next frame
+// Accumulate with history rejection (mcpt_temporal_accumulate_ex, a sequence created with mcpt_sequence_create_ex):
+//   k_temporal_accumulate_ex  the same shape again; tp::accumulate_pixel_ex adds the normal test on every tap and the clamp of the history
+//                     to the 3 x 3 neighbourhood of the new frame.  The nine neighbours are read straight from global memory: a lane's row
+//                     neighbours are its wave neighbours' own pixels, so the 36-byte runs overlap in L1 (a 16 x 16 tile touches 18 x 18
+//                     pixels, 1.27 x its own colour bytes); an LDS tile with a halo would add a barrier and a second pass over the halo
+//                     to save loads that already hit.  It also copies the frame's first-hit normal into the history's normal plane and
+//                     writes the flags byte, both with plain vector stores.
 #include <hip/hip_runtime.h>
 
 #include "mcpt_temporal.h"
@@ -93,6 +100,26 @@ __global__ __launch_bounds__(kTile *kTile) void k_temporal_accumulate(int W, int
     if (depth) out_depth[m] = depth[m * (size_t)depth_stride];
 }
 
+__global__ __launch_bounds__(kTile *kTile) void k_temporal_accumulate_ex(
+    int W, int H, tp::Opts o, tp::HistOpts ho, const float *__restrict__ color, const float *__restrict__ variance, const float *__restrict__ motion,
+    const float *__restrict__ normal, int normal_stride, const float *__restrict__ prev_color, const float *__restrict__ prev_variance,
+    const float *__restrict__ prev_depth, const float *__restrict__ prev_len, const float *__restrict__ prev_normal, const float *__restrict__ depth,
+    int depth_stride, float *__restrict__ out_color, float *__restrict__ out_variance, float *__restrict__ out_depth, float *__restrict__ out_len,
+    float *__restrict__ out_normal, uint8_t *__restrict__ out_flags) {
+    const int x = blockIdx.x * kTile + threadIdx.x, y = blockIdx.y * kTile + threadIdx.y;
+    if (x >= W || y >= H) return;
+    tp::accumulate_pixel_ex(W, H, x, y, color, variance, motion, normal, normal_stride, prev_color, prev_variance, prev_depth, prev_len, prev_normal, o, ho,
+                            out_color, out_variance, out_len, out_flags);
+    const size_t m = (size_t)y * W + x;
+    if (depth) out_depth[m] = depth[m * (size_t)depth_stride];
+    if (out_normal) {
+        const float *n = normal + m * (size_t)normal_stride;
+        out_normal[m * 3] = n[0];
+        out_normal[m * 3 + 1] = n[1];
+        out_normal[m * 3 + 2] = n[2];
+    }
+}
+
 }  // namespace
 
 void launch_motion_resolve(const DevScene &S, const TriGeom *prev_tri, const SphereRec *prev_sph, const tp::Cam &cur, const tp::Cam &prev, uint32_t n,
@@ -118,6 +145,15 @@ void launch_temporal_accumulate(int W, int H, const tp::Opts &o, const float *co
     const dim3 grid((W + kTile - 1) / kTile, (H + kTile - 1) / kTile), blk(kTile, kTile);
     hipLaunchKernelGGL(k_temporal_accumulate, grid, blk, 0, st, W, H, o, color, variance, motion, prev_color, prev_variance, prev_depth, prev_len, depth,
                        depth_stride, out_color, out_variance, out_depth, out_len);
+}
+
+void launch_temporal_accumulate_ex(int W, int H, const tp::Opts &o, const tp::HistOpts &ho, const float *color, const float *variance, const float *motion,
+                                   const float *normal, int normal_stride, const float *prev_color, const float *prev_variance, const float *prev_depth,
+                                   const float *prev_len, const float *prev_normal, const float *depth, int depth_stride, float *out_color,
+                                   float *out_variance, float *out_depth, float *out_len, float *out_normal, uint8_t *out_flags, hipStream_t st) {
+    const dim3 grid((W + kTile - 1) / kTile, (H + kTile - 1) / kTile), blk(kTile, kTile);
+    hipLaunchKernelGGL(k_temporal_accumulate_ex, grid, blk, 0, st, W, H, o, ho, color, variance, motion, normal, normal_stride, prev_color, prev_variance,
+                       prev_depth, prev_len, prev_normal, depth, depth_stride, out_color, out_variance, out_depth, out_len, out_normal, out_flags);
 }
 
 }  // namespace mcpt

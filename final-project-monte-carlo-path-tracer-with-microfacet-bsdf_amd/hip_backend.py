@@ -20,7 +20,9 @@ EXPORTS = ["mcpt_scene_create", "mcpt_scene_destroy", "mcpt_render", "mcpt_rende
            "mcpt_cast_rays", "mcpt_camera_rays", "mcpt_scene_get_info", "mcpt_bvh_dump", "mcpt_scene_create_ex", "mcpt_scene_dump_bvh", "mcpt_tonemap", "mcpt_tonemap_device", "mcpt_debug_fmath", "mcpt_debug_material", "mcpt_debug_scene", "mcpt_debug_shadow", "mcpt_debug_counters",
            "mcpt_scene_update", "mcpt_group_update", "mcpt_transform_triangles",
            "mcpt_scene_snapshot", "mcpt_render_motion", "mcpt_temporal_blend", "mcpt_temporal_accumulate",
+           "mcpt_temporal_accumulate_ex",
            "mcpt_sequence_create", "mcpt_sequence_frame", "mcpt_sequence_reset", "mcpt_sequence_destroy",
+           "mcpt_sequence_create_ex", "mcpt_sequence_flags",
            "mcpt_group_create", "mcpt_group_render", "mcpt_group_size", "mcpt_group_get_info", "mcpt_group_scene", "mcpt_group_destroy", "mcpt_group_last_error",
            "mcpt_last_error", "mcpt_version"]
 
@@ -96,6 +98,19 @@ def temporal_opts(max_history=0, depth_tol=0.0):
     return TemporalOpts(max_history=int(max_history), depth_tol=float(depth_tol))
 
 
+class HistoryOpts(C.Structure):
+    _fields_ = [("normal_test", C.c_int32), ("color_clamp", C.c_int32), ("normal_min", C.c_float), ("clamp_k", C.c_float), ("reserved", C.c_int32 * 4)]
+
+
+def history_opts(normal_test=False, color_clamp=False, normal_min=0.0, clamp_k=0.0):
+    """mcpt_history_opts: the normal test on every tap and the neighbourhood colour clamp of the reprojected history, both off by default
+    (normal_min, clamp_k 0 = the library's defaults 0.9 and 1)."""
+    return HistoryOpts(normal_test=int(normal_test), color_clamp=int(color_clamp), normal_min=float(normal_min), clamp_k=float(clamp_k))
+
+
+FLAG_NORMAL, FLAG_CLAMP = 1, 2  # the bits of a history-rejection flags byte
+
+
 class SequenceOpts(C.Structure):
     _fields_ = [("temporal", TemporalOpts), ("denoise", DenoiseOpts), ("filter", C.c_int32), ("reserved", C.c_int32 * 7)]
 
@@ -115,7 +130,7 @@ class SequenceInfo(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
 
 
-assert C.sizeof(TemporalOpts) == 32 and C.sizeof(DenoiseOpts) == 32  # the sizes include/mcpt.h states
+assert C.sizeof(TemporalOpts) == 32 and C.sizeof(DenoiseOpts) == 32 and C.sizeof(HistoryOpts) == 32  # the sizes include/mcpt.h states
 assert C.sizeof(SequenceOpts) == 96 and C.sizeof(SequenceOutputs) == 64 and C.sizeof(SequenceInfo) == 64
 
 
@@ -212,6 +227,13 @@ def lib(path=None):
         L.mcpt_temporal_blend.argtypes = [C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 5 + [C.POINTER(TemporalOpts), C.c_void_p, C.c_void_p]
         L.mcpt_temporal_accumulate.restype = C.c_int
         L.mcpt_temporal_accumulate.argtypes = [C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 7 + [C.POINTER(TemporalOpts)] + [C.c_void_p] * 3
+        L.mcpt_temporal_accumulate_ex.restype = C.c_int
+        L.mcpt_temporal_accumulate_ex.argtypes = ([C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 9 + [C.POINTER(TemporalOpts), C.POINTER(HistoryOpts)]
+                                                  + [C.c_void_p] * 4)
+        L.mcpt_sequence_create_ex.restype = C.c_int
+        L.mcpt_sequence_create_ex.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(SequenceOpts), C.POINTER(HistoryOpts), C.POINTER(C.c_void_p)]
+        L.mcpt_sequence_flags.restype = C.c_int
+        L.mcpt_sequence_flags.argtypes = [C.c_void_p, C.c_void_p]
         L.mcpt_sequence_create.restype = C.c_int
         L.mcpt_sequence_create.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(SequenceOpts), C.POINTER(C.c_void_p)]
         L.mcpt_sequence_frame.restype = C.c_int
@@ -534,11 +556,42 @@ class HipScene:
                                                _ptr(prev_depth), _ptr(prev_len), C.byref(o), _ptr(out), _ptr(out_var), _ptr(out_len)), L=self.L)
         return out, out_var, out_len
 
-    def sequence(self, width=None, height=None, filter=True, max_history=0, depth_tol=0.0, **denoise_opts_kw):
+    def temporal_accumulate_ex(self, color, variance, motion, normal, prev_color, prev_variance, prev_depth, prev_len, prev_normal,
+                               normal_test=False, color_clamp=False, normal_min=0.0, clamp_k=0.0, **opts):
+        """mcpt_temporal_accumulate_ex: temporal_accumulate with history rejection.  normal[H,W,3] / prev_normal[H,W,3] are the first-hit
+        normals (render_aovs(...)[..., 3:6]) of this frame and of the previous one; both may be None unless normal_test is on.  Returns
+        (out[H,W,3], out_variance[H,W], out_len[H,W] float32, flags[H,W] uint8: FLAG_NORMAL the normal test skipped a tap, FLAG_CLAMP the
+        clamp moved the history).  With both switches off the first three are temporal_accumulate's bit for bit."""
+        color = np.ascontiguousarray(color, dtype=np.float32)
+        H, W = color.shape[:2]
+        variance, motion, prev_color, prev_variance, prev_depth, prev_len = (
+            np.ascontiguousarray(x, dtype=np.float32) for x in (variance, motion, prev_color, prev_variance, prev_depth, prev_len))
+        normal, prev_normal = (None if x is None else np.ascontiguousarray(x, dtype=np.float32) for x in (normal, prev_normal))
+        n = H * W
+        if (color.size != n * 3 or variance.size != n or motion.size != n * 4 or prev_color.size != n * 3 or prev_variance.size != n
+                or prev_depth.size != n or prev_len.size != n or any(x is not None and x.size != n * 3 for x in (normal, prev_normal))):
+            raise ValueError("temporal_accumulate_ex: the arrays do not describe one %dx%d frame" % (W, H))
+        out = np.zeros((H, W, 3), dtype=np.float32)
+        out_var = np.zeros((H, W), dtype=np.float32)
+        out_len = np.zeros((H, W), dtype=np.float32)
+        flags = np.zeros((H, W), dtype=np.uint8)
+        o = temporal_opts(**opts)
+        ho = history_opts(normal_test, color_clamp, normal_min, clamp_k)
+        _check(self.L.mcpt_temporal_accumulate_ex(self.h, W, H, _ptr(color), _ptr(variance), _ptr(motion), None if normal is None else _ptr(normal),
+                                                  _ptr(prev_color), _ptr(prev_variance), _ptr(prev_depth), _ptr(prev_len),
+                                                  None if prev_normal is None else _ptr(prev_normal), C.byref(o), C.byref(ho), _ptr(out), _ptr(out_var),
+                                                  _ptr(out_len), _ptr(flags)), L=self.L)
+        return out, out_var, out_len, flags
+
+    def sequence(self, width=None, height=None, filter=True, max_history=0, depth_tol=0.0, normal_test=False, color_clamp=False, normal_min=0.0,
+                 clamp_k=0.0, **denoise_opts_kw):
         """mcpt_sequence_create: a HipSequence of width x height frames (default: the scene camera's) on this scene.  filter: also denoise
         the accumulated frame; max_history, depth_tol: mcpt_temporal_opts; the rest: mcpt_denoise_opts (aov_spp, iterations, sigma_l,
-        sigma_n, sigma_z, specular_depth).  The sequence owns the scene's snapshot while it lives; close it before the scene."""
-        return HipSequence(self, width, height, filter, max_history, depth_tol, **denoise_opts_kw)
+        sigma_n, sigma_z, specular_depth).  normal_test / color_clamp (normal_min, clamp_k): history rejection, mcpt_history_opts; with
+        either on the sequence is made by mcpt_sequence_create_ex and HipSequence.flags() tells what the last frame rejected.
+        The sequence owns the scene's snapshot while it lives; close it before the scene."""
+        return HipSequence(self, width, height, filter, max_history, depth_tol, normal_test=normal_test, color_clamp=color_clamp,
+                           normal_min=normal_min, clamp_k=clamp_k, **denoise_opts_kw)
 
     def render_device(self, fb_ptr, stream_ptr=0, camera=None, **kw):
         """Same, into a device framebuffer (W*H*3 floats at fb_ptr) on the given hipStream_t handle."""
@@ -629,7 +682,9 @@ class HipSequence:
 
     _SHAPES = {"fb": (3,), "accumulated": (3,), "denoised": (3,), "variance": (), "len": (), "aov": (8,), "motion": (4,), "rgba": (4,)}
 
-    def __init__(self, scene, width=None, height=None, filter=True, max_history=0, depth_tol=0.0, **denoise_opts_kw):
+    def __init__(self, scene, width=None, height=None, filter=True, max_history=0, depth_tol=0.0, normal_test=False, color_clamp=False,
+                 normal_min=0.0, clamp_k=0.0, history=None, **denoise_opts_kw):
+        """history: a HistoryOpts passed to mcpt_sequence_create_ex as it is (tests: a zeroed one must give mcpt_sequence_create's sequence)."""
         self.scene = scene  # (keeps the scene alive as long as the sequence)
         self.L = scene.L
         self.h = None
@@ -638,7 +693,12 @@ class HipSequence:
         self.H = int(height if height is not None else np.asarray(cam["height"]).reshape(-1)[0])
         o = SequenceOpts(temporal=temporal_opts(max_history, depth_tol), denoise=denoise_opts(**denoise_opts_kw), filter=int(bool(filter)))
         h = C.c_void_p()
-        _check(self.L.mcpt_sequence_create(scene.h, self.W, self.H, C.byref(o), C.byref(h)), L=self.L)
+        if history is None and (normal_test or color_clamp):
+            history = history_opts(normal_test, color_clamp, normal_min, clamp_k)
+        if history is None:
+            _check(self.L.mcpt_sequence_create(scene.h, self.W, self.H, C.byref(o), C.byref(h)), L=self.L)
+        else:
+            _check(self.L.mcpt_sequence_create_ex(scene.h, self.W, self.H, C.byref(o), C.byref(history), C.byref(h)), L=self.L)
         self.h = h
 
     def frame(self, camera=None, want=("denoised",), **params_kw):
@@ -656,6 +716,13 @@ class HipSequence:
         info, st = SequenceInfo(), Stats()
         _check(self.L.mcpt_sequence_frame(self.h, _ptr(cam), C.byref(p), C.byref(ptrs), C.byref(info), C.byref(st)), L=self.L)
         out["info"], out["stats"] = info.as_dict(), st
+        return out
+
+    def flags(self):
+        """mcpt_sequence_flags: flags[H,W] uint8 of the last frame (FLAG_NORMAL | FLAG_CLAMP per pixel); a sequence without history
+        rejection keeps none and raises."""
+        out = np.zeros((self.H, self.W), dtype=np.uint8)
+        _check(self.L.mcpt_sequence_flags(self.h, _ptr(out)), L=self.L)
         return out
 
     def reset(self):

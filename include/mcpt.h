@@ -382,7 +382,7 @@ int mcpt_render_motion(mcpt_scene *scene, const mcpt_camera *camera, const mcpt_
  *      N = min(n + 1, max_history);  out = hist + (color - hist) * (1.f / N);  len = N.
  * So a static scene accumulates the running mean of its frames (N frames after N calls, up to max_history, then an exponential average),
  * and a pixel whose history fails the depth test restarts.  Only depth is validated: a rotating object keeps its history, and sky
- * pixels (valid 0) restart every frame.
+ * pixels (valid 0) restart every frame.  (mcpt_temporal_accumulate_ex below adds a normal test and a colour clamp.)
  * MCPT_ERR_ARG for a null pointer, width or height <= 0 and out-of-range options (a non-zero reserved word included). */
 typedef struct {
     int32_t max_history; /* cap of the running mean's length; 0 => 32; 1..4096 */
@@ -414,6 +414,48 @@ int mcpt_temporal_accumulate(mcpt_scene *scene, int32_t width, int32_t height, c
                              const float *motion_host, const float *prev_color_host, const float *prev_variance_host, const float *prev_depth_host,
                              const float *prev_len_host, const mcpt_temporal_opts *opts, float *out_color_host, float *out_variance_host,
                              float *out_len_host);
+
+/* History rejection: mcpt_temporal_accumulate with a normal test on every tap and a neighbourhood colour clamp of the reprojected
+ * history, so that a crease does not mix the colours of its two faces and a change of lighting (a moved emitter or occluder, which
+ * leaves the depth of the pixels it lights untouched) does not fade out over max_history frames.  The arguments of
+ * mcpt_temporal_accumulate, and
+ *   normal_host W*H*3  this frame's first-hit normals: channels 3..5 of the AOVs of mcpt_render_aovs (specular_depth 0), folded as they
+ *                      are -- a mean of unit vectors, not renormalised;
+ *   prev_normal_host W*H*3  the normal_host of the previous call;
+ *   out_flags_host W*H bytes, nullable: bit 0 (1) the normal test skipped a tap, bit 1 (2) the clamp moved the history.
+ * The rule is that of mcpt_temporal_blend / mcpt_temporal_accumulate with three additions, all in float, without contraction:
+ *   step 3, one more skip, tested last (normal_test 1):  pn = prev_normal[tap], n = normal[p];
+ *         d = pn.x*n.x + (pn.y*n.y + pn.z*n.z);   the tap is skipped if !(d >= normal_min)   (a NaN normal on either side skips it).
+ *      Flag bit 0 is set when this test skipped at least one tap that every older test had passed and the pixel still takes history.
+ *   after hist is formed in step 5 (color_clamp 1):  over the 3x3 neighbours q of p in the NEW frame `color` that lie inside the image, in
+ *      the order dy = -1..1, then dx = -1..1, p itself included, using only those whose three channels are finite; n = their number
+ *      (p is finite by step 1, so n >= 1), as a float.  Per channel, sums from 0 in that order:
+ *         s = s + c;   s2 = s2 + c*c;   mu = s/n;   var = max(s2/n - mu*mu, 0);   sd = sqrtf(var);
+ *         lo = mu - clamp_k*sd;   hi = mu + clamp_k*sd;   hist' = min(max(hist, lo), hi)
+ *      with max(x, 0) = x > 0 ? x : 0 (0 for a NaN) and the clamp as two comparisons, t = hist < lo ? lo : hist;  hist' = t > hi ? hi : t,
+ *      so a bound that is NaN (sums that overflowed) leaves hist as it is.  Then out = hist' + (color - hist') * (1.f / N);  len = N,
+ *      unchanged: a clamped history still counts its frames.
+ *   if any channel has hist' != hist:  flag bit 1 is set and out_variance = v_c -- the propagated variance describes a history that was
+ *      not used as it was, and one frame's variance over-estimates, so the filter smooths more, never less.
+ * Pixels that take no history (steps 1 and 4) have flags 0.  With both switches 0 the call gives mcpt_temporal_accumulate's outputs bit
+ * for bit (it launches the same kernel), flags 0 everywhere, and normal_host / prev_normal_host are not read and may be null.
+ * clamp_k: the default 1 is the smallest of 1, 1.5, 2, 3 whose cost on a static scene stays inside the seed-to-seed spread of the
+ * unclamped error (DESIGN section 8f has the figures).
+ * MCPT_ERR_ARG, before any device call: every case mcpt_temporal_accumulate refuses; a null history_opts; a switch that is not 0 or 1;
+ * normal_min or clamp_k out of range or NaN (checked whether or not their switch is on); a non-zero reserved word; normal_test 1 with a
+ * null normal_host or prev_normal_host. */
+typedef struct {
+    int32_t normal_test; /* 0 off, 1 on */
+    int32_t color_clamp; /* 0 off, 1 on */
+    float normal_min;    /* 0 => 0.9; otherwise in (0, 1] */
+    float clamp_k;       /* 0 => 1; otherwise > 0 and finite */
+    int32_t reserved[4]; /* must be 0 */
+} mcpt_history_opts;     /* 32 bytes; a zeroed struct switches both tests off */
+int mcpt_temporal_accumulate_ex(mcpt_scene *scene, int32_t width, int32_t height, const float *color_host, const float *variance_host,
+                                const float *motion_host, const float *normal_host, const float *prev_color_host,
+                                const float *prev_variance_host, const float *prev_depth_host, const float *prev_len_host,
+                                const float *prev_normal_host, const mcpt_temporal_opts *opts, const mcpt_history_opts *history_opts,
+                                float *out_color_host, float *out_variance_host, float *out_len_host, uint8_t *out_flags_host);
 
 /* ---- Frame sequences: the history, the variance of the accumulated frame and every working buffer stay on the device; one call runs a
  * whole frame on one stream and only what the caller asks for crosses the bus.  The caller's loop is
@@ -482,6 +524,21 @@ int mcpt_sequence_frame(mcpt_sequence *sequence, const mcpt_camera *camera, cons
                         mcpt_sequence_info *info, mcpt_stats *stats);
 int mcpt_sequence_reset(mcpt_sequence *sequence);
 void mcpt_sequence_destroy(mcpt_sequence *sequence);
+
+/* A sequence with history rejection (mcpt_history_opts above).  A null or zeroed history_opts: mcpt_sequence_create, exactly.  Otherwise
+ * step 5 of mcpt_sequence_frame is mcpt_temporal_accumulate_ex in place of mcpt_temporal_accumulate, and every output still equals what
+ * the separate calls give, bit for bit:
+ *   normal_test 1: each history set gains a normal plane (3 floats per pixel), which step 5 writes from channels 3..5 of the first-hit
+ *      AOVs -- the AOVs the depth plane comes from: those of step 3 with denoise.specular_depth 0, otherwise the extra first-hit pass;
+ *   either switch 1: each history set gains a flags plane (1 byte per pixel), which step 5 writes.
+ * Per pixel that is 24 bytes more with normal_test and 2 more with either switch: up to 274 with both (306 with specular_depth > 0).
+ * mcpt_sequence_flags copies the flags of the last successful frame to flags_host (W*H bytes; all 0 before the first frame).  A failed
+ * frame leaves history, normals and flags as they were; mcpt_sequence_reset leaves the flags of the last frame readable.
+ * MCPT_ERR_ARG, before any device call: as mcpt_sequence_create and mcpt_temporal_accumulate_ex; mcpt_sequence_flags for a null pointer
+ * or a sequence created with both switches 0 (it keeps no flags). */
+int mcpt_sequence_create_ex(mcpt_scene *scene, int32_t width, int32_t height, const mcpt_sequence_opts *opts, const mcpt_history_opts *history_opts,
+                            mcpt_sequence **out);
+int mcpt_sequence_flags(mcpt_sequence *sequence, uint8_t *flags_host);
 
 /* Replaces Scene::intersect (Scene.hpp:128, Scene.cpp:19-21) for a list of rays (host pointers; n*3 floats each).
  * out_t: hit distance as the reference's double Intersection::distance (DBL_MAX on a miss);

@@ -10,7 +10,10 @@ python tools/temporal.py --sequence [--frames 8]   the same frames (seed k + 1 f
 loop snapshot / render / render_aovs / render_motion / temporal_blend / denoise / tonemap, and through HipSequence.frame(want=("rgba",)).
 Prints the wall time per frame of both (the median over the frames after the first, which warms up) and the sequence's per-stage event
 times.  render() returns no variance, so the loop's denoise is fed the variance of one earlier frame: it does the filter's work on the
-accumulated image without the cost of getting a variance, which flatters the loop."""
+accumulated image without the cost of getting a variance, which flatters the loop.
+  --normal-test / --color-clamp [--clamp-k K]   the sequence rejects stale history (mcpt_sequence_create_ex): also prints, per frame, the
+share of pixels whose flags byte has bit 0 (the normal test skipped a tap) and bit 1 (the clamp moved the history).  --no-loop skips the
+host-array loop (the sequence alone, e.g. to compare ms_accumulate with and without the switches)."""
 import argparse
 import csv
 import re
@@ -76,12 +79,13 @@ def summarize_trace(path, repeat):
             print("    %-18s %4d launches  %8.3f ms per call  %8.1f us per launch" % (n, cnt, ns / calls / 1e6, ns / cnt / 1e3))
 
 
-def sequence_timing(pkg, sd, W, H, frames):
+def sequence_timing(pkg, sd, W, H, frames, reject=None, loop=True):
     hs = pkg.HipScene(sd)
     var = hs.render_denoised(spp=4, seed=1, aov_spp=4)["variance"]  # (also sizes the workspace)
     hist, length, prev_depth = np.zeros((H, W, 3), np.float32), np.zeros((H, W), np.float32), np.zeros((H, W), np.float32)
     t_loop = []
-    for k in range(frames):
+    rgba_loop = None
+    for k in range(frames if loop else 0):
         t0 = time.perf_counter()
         hs.snapshot()
         c, _ = hs.render(spp=4, seed=k + 1)
@@ -91,22 +95,32 @@ def sequence_timing(pkg, sd, W, H, frames):
         rgba_loop = hs.tonemap(hs.denoise(hist, var, aov))
         prev_depth = aov[..., 6].copy()
         t_loop.append(time.perf_counter() - t0)
-    seq = hs.sequence(filter=True, aov_spp=4)
-    t_seq, stages = [], []
+    seq = hs.sequence(filter=True, aov_spp=4, **(reject or {}))
+    t_seq, stages, shares = [], [], []
     for k in range(frames):
         t0 = time.perf_counter()
         r = seq.frame(want=("rgba",), spp=4, seed=k + 1)
         t_seq.append(time.perf_counter() - t0)
         stages.append(r["info"])
-    same = float((r["rgba"] == rgba_loop).mean())
+        if reject:  # (outside the timed part)
+            fl = seq.flags()
+            shares.append((100 * float((fl & 1).astype(bool).mean()), 100 * float((fl & 2).astype(bool).mean())))
     med = lambda t: 1e3 * float(np.median(t[1:]))  # noqa: E731
     print("%dx%d, %d frames each, the first not counted" % (W, H, frames))
-    print("host-array loop   median wall %.2f ms per frame (min %.2f, max %.2f)" % (med(t_loop), 1e3 * min(t_loop[1:]), 1e3 * max(t_loop[1:])))
+    if reject:
+        print("history rejection: " + ", ".join("%s %s" % kv for kv in sorted(reject.items())))
+        for k, (a, b) in enumerate(shares):
+            print("    frame %d: normal test skipped a tap in %.2f %% of the pixels, the clamp moved the history in %.2f %%" % (k, a, b))
+    if loop:
+        print("host-array loop   median wall %.2f ms per frame (min %.2f, max %.2f)" % (med(t_loop), 1e3 * min(t_loop[1:]), 1e3 * max(t_loop[1:])))
     print("sequence          median wall %.2f ms per frame (min %.2f, max %.2f)" % (med(t_seq), 1e3 * min(t_seq[1:]), 1e3 * max(t_seq[1:])))
     print("sequence stages, median event time in ms: " + ", ".join(
         "%s %.3f" % (k[3:], float(np.median([s[k] for s in stages[1:]]))) for k in ("ms_render", "ms_aov", "ms_motion", "ms_accumulate", "ms_filter")))
     print("sequence ms_total (wall time inside the call) median %.2f ms" % float(np.median([s["ms_total"] for s in stages[1:]])))
-    print("last frame: %.2f %% of the rgba bytes equal the loop's (the two filters are guided by different variances)" % (100 * same))
+    print("sequence ms_accumulate per frame: " + " ".join("%.4f" % s["ms_accumulate"] for s in stages[1:]))
+    if loop:
+        same = float((r["rgba"] == rgba_loop).mean())
+        print("last frame: %.2f %% of the rgba bytes equal the loop's (the two filters are guided by different variances)" % (100 * same))
     seq.close()
     hs.close()
 
@@ -120,6 +134,10 @@ def main():
     ap.add_argument("--repeat", type=int, default=5)
     ap.add_argument("--sequence", action="store_true", help="time the host-array frame loop against HipSequence.frame")
     ap.add_argument("--frames", type=int, default=8, help="--sequence: frames per way (at least 6: one warm-up and five counted)")
+    ap.add_argument("--normal-test", action="store_true", help="--sequence: reject taps whose normal differs (mcpt_history_opts)")
+    ap.add_argument("--color-clamp", action="store_true", help="--sequence: clamp the history to the new frame's 3x3 neighbourhood")
+    ap.add_argument("--clamp-k", type=float, default=0.0, help="--color-clamp: the box's half-width in standard deviations (0: the default)")
+    ap.add_argument("--no-loop", action="store_true", help="--sequence: skip the host-array loop")
     a = ap.parse_args()
     if a.trace:
         return summarize_trace(a.trace, a.repeat)
@@ -129,7 +147,10 @@ def main():
     if a.sequence:
         if a.frames < 6:
             sys.exit("--frames must be at least 6")
-        return sequence_timing(pkg, sd, W, H, a.frames)
+        reject = None
+        if a.normal_test or a.color_clamp:
+            reject = dict(normal_test=a.normal_test, color_clamp=a.color_clamp, clamp_k=a.clamp_k)
+        return sequence_timing(pkg, sd, W, H, a.frames, reject, not a.no_loop)
     hs = pkg.HipScene(sd)
     r = hs.render_denoised(spp=4, seed=1, aov_spp=4)  # (also sizes the workspace the AOV and motion passes run in)
     color, var, aov = r["fb"], r["variance"], r["aov"]
