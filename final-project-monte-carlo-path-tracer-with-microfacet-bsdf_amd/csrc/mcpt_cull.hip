@@ -20,12 +20,17 @@
 // background[c] / spp_total in sample order (k_sky_fill = k_accumulate's arithmetic).  Not used with an environment map (the miss
 // value then depends on each sample's direction) -- nothing is culled there.  tests/test_gpu_cull.py: frames bit-identical with the
 // culling on and off, thin geometry and depth of field included; MCPT_SKY_CULL=0 switches it off.
+// tests/test_cull_cpu.py checks the bound (cull_bound below, exported as mcpt_cull_bound) against brute-force camera rays at the
+// jitter-square corners and the lens rim, and a numpy restatement of k_classify (tests/cull_cases.py) against the oracle's closest hits;
+// tests/test_gpu_cull_classify.py: k_classify equals that restatement exactly (mcpt_debug_classify), frames through the candidate lists
+// equal frames through the tree, ties included, and a bound scaled to 0 (MCPT_CULL_RHO_SCALE, checking build) is caught.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
 #include <cmath>
 
 #include "mcpt_cull.h"
+#include "mcpt_host.h"
 
 namespace mcpt {
 
@@ -126,8 +131,8 @@ __global__ __launch_bounds__(kB) void k_sky_fill(const uint32_t *__restrict__ sk
 
 }  // namespace
 
-hipError_t cull_sky_pixels(const DevScene &S, const CameraConst &cam, const uint32_t *d_pixels, uint32_t n, uint32_t *d_out, uint8_t *d_flags,
-                           int4 *d_cand_tmp, int4 *d_cand_out, void *d_temp, size_t temp_bytes, uint32_t *d_count, uint32_t *n_trace, hipStream_t st) {
+// What k_classify reads of the camera (rho is set by cull_sky_pixels).
+static CullConst cull_const(const CameraConst &cam) {
     CullConst C;
     for (int a = 0; a < 3; ++a) C.eye[a] = cam.eye[a];
     for (int a = 0; a < 9; ++a) C.orient[a] = cam.orient[a];
@@ -137,30 +142,64 @@ hipError_t cull_sky_pixels(const DevScene &S, const CameraConst &cam, const uint
     C.lens = cam.use_dof ? fabsf(cam.aperture_radius) : 0.0f;
     C.width = cam.width;
     C.height = cam.height;
+    C.rho = 0.f;
+    return C;
+}
+
+// The host half of the classification: h, reach, fmin, s_far and rho of the header comment, all in double.
+// classified == false: the camera is outside what the bound covers (cull_sky_pixels then culls nothing).
+CullBound cull_bound(const CameraConst &cam, const float root_min[3], const float root_max[3]) {
+    const CullConst C = cull_const(cam);
+    CullBound B{};
+    B.scale = C.scale;
+    B.aspect = C.aspect;
+    B.focal = C.focal;
+    B.lens = C.lens;
     // the bound takes |O v| = |v| (Camera::lookAt builds an orthonormal matrix, Camera.hpp:17-24): any other matrix, no culling
     for (int a = 0; a < 3; ++a)
         for (int b = 0; b < 3; ++b) {
             double dotp = 0;
             for (int k = 0; k < 3; ++k) dotp += (double)C.orient[3 * k + a] * C.orient[3 * k + b];
-            if (std::fabs(dotp - (a == b ? 1.0 : 0.0)) > 1e-4) return hipSuccess;
+            if (std::fabs(dotp - (a == b ? 1.0 : 0.0)) > 1e-4) return B;
         }
     // h, s_far, rho (see the header comment), all on the host in double
     const double h = std::fabs((double)C.focal) * std::sqrt(std::pow((double)C.aspect * C.scale / C.width, 2) + std::pow((double)C.scale / C.height, 2));
     double centre[3], half = 0, eye_c = 0, eye_n = 0;
     for (int a = 0; a < 3; ++a) {
-        centre[a] = 0.5 * ((double)S.root_min[a] + S.root_max[a]);
-        half += std::pow(0.5 * ((double)S.root_max[a] - S.root_min[a]), 2);
+        centre[a] = 0.5 * ((double)root_min[a] + root_max[a]);
+        half += std::pow(0.5 * ((double)root_max[a] - root_min[a]), 2);
         eye_c += std::pow((double)C.eye[a] - centre[a], 2);
         eye_n += (double)C.eye[a] * C.eye[a];
     }
     half = std::sqrt(half);
     const double reach = std::sqrt(eye_c) + half + C.lens;            // farthest scene point from any lens point
     const double fmin = std::fabs((double)C.focal) - h - C.lens;      // shortest |P - L| (|fp0| >= focal)
-    if (!(fmin > 0.05 * std::fabs((double)C.focal)) || !std::isfinite(reach) || !std::isfinite(h)) return hipSuccess;  // odd camera: no culling
+    B.h = h;
+    B.reach = reach;
+    B.fmin = fmin;
+    if (!(fmin > 0.05 * std::fabs((double)C.focal)) || !std::isfinite(reach) || !std::isfinite(h)) return B;  // odd camera: no culling
     const double s_far = reach / fmin;
     const double rho = std::max((double)C.lens, std::fabs(1.0 - s_far) * C.lens + s_far * h);
-    C.rho = (float)(1.05 * rho + 1e-4 * (half + std::sqrt(eye_n) + std::sqrt(eye_c)) + 1e-3);
-    if (!std::isfinite(C.rho)) return hipSuccess;
+    B.s_far = s_far;
+    B.rho = (float)(1.05 * rho + 1e-4 * (half + std::sqrt(eye_n) + std::sqrt(eye_c)) + 1e-3);
+    if (!std::isfinite(B.rho)) return B;
+    B.classified = true;
+    return B;
+}
+
+hipError_t cull_sky_pixels(const DevScene &S, const CameraConst &cam, const uint32_t *d_pixels, uint32_t n, uint32_t *d_out, uint8_t *d_flags,
+                           int4 *d_cand_tmp, int4 *d_cand_out, void *d_temp, size_t temp_bytes, uint32_t *d_count, uint32_t *n_trace, float rho_scale,
+                           CullBound *used, hipStream_t st) {
+    CullConst C = cull_const(cam);
+    CullBound B = cull_bound(cam, S.root_min, S.root_max);
+#ifdef MCPT_TEST_HOOKS
+    B.rho *= rho_scale;  // MCPT_CULL_RHO_SCALE: below 1 the bound is wrong on purpose (the negative control of tests/test_gpu_cull_classify.py)
+#else
+    (void)rho_scale;
+#endif
+    if (used) *used = B;
+    if (!B.classified) return hipSuccess;
+    C.rho = B.rho;
     hipLaunchKernelGGL(k_classify, dim3(nblocks(n)), dim3(kB), 0, st, S, C, d_pixels, n, d_flags, d_cand_tmp);
     hipError_t e = hipcub::DevicePartition::Flagged(d_temp, temp_bytes, d_pixels, d_flags, d_out, d_count, (int)n, st);
     if (e != hipSuccess) return e;
@@ -189,3 +228,12 @@ void launch_sky_fill(const uint32_t *sky_pixels, uint32_t n_sky, const float bac
 }
 
 }  // namespace mcpt
+
+// Host only (include/mcpt.h): the bound cull_sky_pixels would use for this camera and root box.
+extern "C" int mcpt_cull_bound(const mcpt_camera *camera, const float root_min[3], const float root_max[3], mcpt_cull_info *info) {
+    using namespace mcpt;
+    if (!camera || !root_min || !root_max || !info) return fail(MCPT_ERR_ARG, "mcpt_cull_bound: null argument");
+    if (camera->width <= 0 || camera->height <= 0) return fail(MCPT_ERR_ARG, "mcpt_cull_bound: width and height must be positive");
+    fill_cull_info(cull_bound(make_camera(*camera), root_min, root_max), info);
+    return MCPT_OK;
+}

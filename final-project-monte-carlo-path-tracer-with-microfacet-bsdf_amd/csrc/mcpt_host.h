@@ -204,6 +204,8 @@ struct Knobs {
                                         // scale makes the rule wrong on purpose: the negative control of tests/test_gpu_direct_halfspace.py)
     float tir_bound_scale = 1.f;        // MCPT_TIR_BOUND_SCALE: multiplies the bound of direct_is_zero's total-internal-reflection rule (below
                                         // 1: wrong on purpose, the negative control of tests/test_gpu_direct_tir.py)
+    float cull_rho_scale = 1.f;         // MCPT_CULL_RHO_SCALE: multiplies the sky cull's final rho (below 1: wrong on purpose, the negative
+                                        // control of tests/test_gpu_cull_classify.py)
     bool sky_cull = true;       // MCPT_SKY_CULL=0: trace the pixels that can only see the background too
     bool small_scene = true;    // MCPT_SMALL_SCENE=0: no LDS-resident flavour for scenes of a few KB
     uint64_t fake_free_mb = 0;  // MCPT_FAKE_FREE_MB: pretend that only this much device memory is free (exercises the pool shrink)

@@ -2,6 +2,7 @@
 // entry points.  Each stages its arguments in call-local device buffers (mcpt_cast_rays: in the wavefront workspace of pool 0).
 #include <cmath>
 
+#include "mcpt_cull.h"
 #include "mcpt_host.h"
 
 using namespace mcpt;
@@ -239,6 +240,49 @@ int mcpt_debug_shadow(mcpt_scene *sc, int32_t list, int64_t n, const float *orig
     std::vector<float> c(n);
     HIP_TRY(download(c.data(), dV, n));
     for (int64_t i = 0; i < n; ++i) visible[i] = c[i] != 0.f;
+    return MCPT_OK;
+}
+
+int mcpt_debug_classify(mcpt_scene *sc, const mcpt_camera *cam, uint8_t *may_hit, int32_t *cand, mcpt_cull_info *info) {
+    if (!sc || !cam || !may_hit || !cand) return fail(MCPT_ERR_ARG, "mcpt_debug_classify: null argument");
+    if (cam->width <= 0 || cam->height <= 0) return fail(MCPT_ERR_ARG, "mcpt_debug_classify: width and height must be positive");
+    const int64_t n64 = (int64_t)cam->width * cam->height;
+    if (n64 > ((int64_t)1 << 26)) return fail(MCPT_ERR_ARG, "mcpt_debug_classify: frame too large");
+    const uint32_t n = (uint32_t)n64;
+    HIP_TRY(hipSetDevice(sc->device));
+    std::vector<uint32_t> pix(n);
+    for (uint32_t m = 0; m < n; ++m) pix[m] = m;
+    DevBuf<uint32_t> dP, dOut, dCount;
+    DevBuf<uint8_t> dF, dT;
+    DevBuf<int4> dC, dCo;
+    const size_t tb = cull_temp_bytes(n);
+    HIP_TRY(upload(dP, pix));
+    HIP_TRY(dOut.alloc(n));
+    HIP_TRY(dCount.alloc(1));
+    HIP_TRY(dF.alloc(n));
+    HIP_TRY(dT.alloc(tb));
+    HIP_TRY(dC.alloc(n));
+    HIP_TRY(dCo.alloc(n));
+    uint32_t n_trace = n + 1;  // (left untouched when the camera is outside what the bound covers)
+    CullBound B{};
+    HIP_TRY(cull_sky_pixels(sc->view, make_camera(*cam), dP.p, n, dOut.p, dF.p, dC.p, dCo.p, dT.p, tb, dCount.p, &n_trace, sc->knobs.cull_rho_scale, &B, nullptr));
+    if (info) fill_cull_info(B, info);
+    if (n_trace > n) {
+        for (uint32_t m = 0; m < n; ++m) {
+            may_hit[m] = 1;
+            cand[4 * (size_t)m] = -2;
+            cand[4 * (size_t)m + 1] = cand[4 * (size_t)m + 2] = cand[4 * (size_t)m + 3] = -1;
+        }
+        return MCPT_OK;
+    }
+    std::vector<int4> c(n);
+    HIP_TRY(download(may_hit, dF, n));
+    HIP_TRY(download(c.data(), dC, n));
+    for (uint32_t m = 0; m < n; ++m) {
+        const int32_t v[4] = {c[m].x, c[m].y, c[m].z, c[m].w};
+        const bool walk = v[0] == kCandTraverse;
+        for (int k = 0; k < 4; ++k) cand[4 * (size_t)m + k] = walk ? (k == 0 ? -2 : -1) : (v[k] == kCandNone ? -1 : ~v[k]);
+    }
     return MCPT_OK;
 }
 

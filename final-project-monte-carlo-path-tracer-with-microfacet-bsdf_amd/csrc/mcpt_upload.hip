@@ -32,6 +32,7 @@ void Knobs::read() {
     if ((v = std::getenv("MCPT_HOST_DELAY_US"))) host_delay_us = std::atoi(v);
     if ((v = std::getenv("MCPT_HALFSPACE_SLACK_SCALE"))) halfspace_slack_scale = (float)std::atof(v);
     if ((v = std::getenv("MCPT_TIR_BOUND_SCALE"))) tir_bound_scale = (float)std::atof(v);
+    if ((v = std::getenv("MCPT_CULL_RHO_SCALE"))) cull_rho_scale = (float)std::atof(v);
     if ((v = std::getenv("MCPT_FAKE_FREE_MB"))) fake_free_mb = (uint64_t)std::max(1, std::atoi(v));
 #endif
 }

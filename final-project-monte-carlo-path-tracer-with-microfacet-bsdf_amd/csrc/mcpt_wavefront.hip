@@ -402,7 +402,7 @@ int prepare_pixels(mcpt_scene *sc, const CameraConst &cc, const mcpt_params &p, 
         HIP_TRY(sh.cand_list.alloc(n_pix_owned));
         uint32_t n_trace = n_pix_owned + 1;  // (left untouched when the camera is outside what the bound covers)
         HIP_TRY(cull_sky_pixels(sc->view, cc, sh.pixel_list.p, n_pix_owned, sh.culled_list.p, sh.cull_flags.p, sh.cand_tmp.p, sh.cand_list.p, sh.cull_temp.p,
-                                tb, sh.cull_count.p, &n_trace, st));
+                                tb, sh.cull_count.p, &n_trace, sc->knobs.cull_rho_scale, nullptr, st));
         if (n_trace <= n_pix_owned) {  // classified: the traced pixels come first, in their original order, with their candidate lists
             sky = sh.culled_list.p + n_trace;
             launch_sky_fill(sky, n_pix_owned - n_trace, sc->view.background, spp, spp_total, fb_dev, st);

@@ -18,6 +18,7 @@ CHECK_LIB_PATH = os.path.join(HERE, "libmcpt_hip_check.so")  # the checking buil
 EXPORTS = ["mcpt_scene_create", "mcpt_scene_destroy", "mcpt_render", "mcpt_render_device", "mcpt_render_adaptive", "mcpt_render_aovs",
            "mcpt_render_aovs_ex", "mcpt_denoise", "mcpt_render_denoised", "mcpt_intersect",
            "mcpt_cast_rays", "mcpt_camera_rays", "mcpt_scene_get_info", "mcpt_bvh_dump", "mcpt_scene_create_ex", "mcpt_scene_dump_bvh", "mcpt_tonemap", "mcpt_tonemap_device", "mcpt_debug_fmath", "mcpt_debug_material", "mcpt_debug_scene", "mcpt_debug_shadow", "mcpt_debug_counters",
+           "mcpt_cull_bound", "mcpt_debug_classify",
            "mcpt_scene_update", "mcpt_group_update", "mcpt_transform_triangles",
            "mcpt_scene_snapshot", "mcpt_render_motion", "mcpt_temporal_blend", "mcpt_temporal_accumulate",
            "mcpt_temporal_accumulate_ex",
@@ -164,6 +165,15 @@ class UpdateInfo(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
 
 
+class CullInfo(C.Structure):
+    _fields_ = [("classified", C.c_int32), ("rho", C.c_float), ("scale", C.c_float), ("aspect", C.c_float), ("focal", C.c_float),
+                ("lens", C.c_float), ("h", C.c_double), ("s_far", C.c_double), ("reach", C.c_double), ("fmin", C.c_double)]
+
+    def as_dict(self):
+        """Floats as numpy float32, so that two records can be compared bit for bit and used in float32 arithmetic as they are."""
+        return {k: (np.float32(getattr(self, k)) if t is C.c_float else getattr(self, k)) for k, t in self._fields_}
+
+
 def _moves(moves):
     """An iterable of (object index, 3x4 array) as an array of mcpt_object_transform."""
     moves = list(moves)
@@ -279,6 +289,10 @@ def lib(path=None):
         L.mcpt_group_last_error.restype = C.c_char_p
         L.mcpt_debug_counters.restype = C.c_int
         L.mcpt_debug_counters.argtypes = [C.c_void_p, C.c_void_p]
+        L.mcpt_cull_bound.restype = C.c_int
+        L.mcpt_cull_bound.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(CullInfo)]
+        L.mcpt_debug_classify.restype = C.c_int
+        L.mcpt_debug_classify.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(CullInfo)]
         _libs[path] = L
     return _libs[path]
 
@@ -329,6 +343,16 @@ def transform_triangles(m, tris, out=None):
         raise ValueError("transform_triangles: arrays of 60-byte triangles with one shape")
     _check(lib().mcpt_transform_triangles(_ptr(m), tris.size, _ptr(tris), _ptr(out)))
     return out
+
+
+def cull_bound(camera, root_min, root_max, library=None):
+    """mcpt_cull_bound (host only): the sky cull's bound for a camera (scenes.CAM_DTYPE) over a root box, as a dict of mcpt_cull_info."""
+    cam = np.ascontiguousarray(camera)
+    lo, hi = np.ascontiguousarray(root_min, dtype=np.float32).reshape(3), np.ascontiguousarray(root_max, dtype=np.float32).reshape(3)
+    info = CullInfo()
+    L = lib(library)
+    _check(L.mcpt_cull_bound(_ptr(cam), _ptr(lo), _ptr(hi), C.byref(info)), L=L)
+    return info.as_dict()
 
 
 def bvh_dump(sd):
@@ -652,6 +676,16 @@ class HipScene:
         _check(self.L.mcpt_debug_shadow(self.h, int(list), n, _ptr(o), _ptr(d), _ptr(ds), _ptr(f), None if sh is None else _ptr(sh), _ptr(vis)),
                L=self.L)
         return vis.astype(bool)
+
+    def classify(self, camera=None):
+        """mcpt_debug_classify: the sky cull's classifier for every pixel -> (may_hit uint8 [H*W], cand int32 [H*W, 4], info dict); cand
+        holds primitive ids in the order the walk found them, -1 unused, or -2 in column 0: the pixel's rays walk the tree."""
+        cam = np.ascontiguousarray(camera if camera is not None else self.sd.camera)
+        n = int(cam["width"].reshape(-1)[0]) * int(cam["height"].reshape(-1)[0])
+        may_hit, cand = np.zeros(n, np.uint8), np.zeros((n, 4), np.int32)
+        info = CullInfo()
+        _check(self.L.mcpt_debug_classify(self.h, _ptr(cam), _ptr(may_hit), _ptr(cand), C.byref(info)), L=self.L)
+        return may_hit, cand, info.as_dict()
 
     def cast_rays(self, origins, dirs, pixel, sample, channel, **kw):
         o = np.ascontiguousarray(origins, dtype=np.float32)

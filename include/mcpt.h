@@ -665,6 +665,37 @@ int mcpt_debug_scene(mcpt_scene *scene, int kind, int64_t n, const float *in, fl
 int mcpt_debug_shadow(mcpt_scene *scene, int32_t list, int64_t n, const float *origins, const float *dirs, const float *dist,
                       const uint8_t *found, const int32_t *shard /* nullable */, uint8_t *visible);
 
+/* ---- Diagnostics of the sky cull (csrc/mcpt_cull.hip): the conservative per-pixel classification in front of every render.
+ *
+ * mcpt_cull_bound: host only, no GPU needed.  The geometric bound the classifier would use for `camera` over a scene whose root box is
+ * [root_min, root_max]: every camera ray of a pixel stays within rho of the pixel's central ray (pixel centre, lens centre) at equal
+ * parameter, as long as it is inside the root box.  It is the very function the render path calls.
+ *   classified  0: the camera is outside what the bound covers (a matrix that is not orthonormal, an aperture or pixel footprint too
+ *               large for the focal distance, a non-finite value); nothing is culled and rho is 0
+ *   rho         the widening of every box as the kernel gets it: 1.05 x the bound + a rounding allowance
+ *   scale, aspect, focal, lens   what the classifier reads of the camera: scale = tan(fov/2) and aspect = W/H exactly as the camera rays
+ *               use them; focal distance (1 without depth of field); aperture radius (0 without)
+ *   h, s_far, reach, fmin        the terms of the bound, in double (0 where the refusal came before they were formed)
+ * MCPT_ERR_ARG for a null pointer or a width or height <= 0. */
+typedef struct {
+    int32_t classified;
+    float rho, scale, aspect, focal, lens;
+    double h, s_far, reach, fmin;
+} mcpt_cull_info; /* 56 bytes */
+int mcpt_cull_bound(const mcpt_camera *camera, const float root_min[3], const float root_max[3], mcpt_cull_info *info);
+
+/* The classifier itself (the product's own launch, unchanged) for all W*H pixels of `camera` in pixel order m = j*W + i, as the kernel
+ * wrote it, before the pixels are partitioned:
+ *   may_hit[m]      0: no camera ray of the pixel can hit anything; 1: one might
+ *   cand[4m..4m+3]  the primitives every ray of the pixel can hit, as primitive ids (mcpt_intersect) in the order the walk found them,
+ *                   unused slots -1; or {-2, -1, -1, -1}: more than four, or an instance: the pixel's rays walk the tree
+ * With info->classified == 0 every pixel reports may_hit 1 and "walk the tree".  info (nullable) is the bound as the kernel got it:
+ * mcpt_cull_bound on the scene's root box.  The call classifies whatever MCPT_SKY_CULL says and for environment-map scenes too: it is
+ * the classifier, not the decision to use it.  MCPT_ERR_ARG, before any device call: a null pointer other than info, a width or
+ * height <= 0, more than 2^26 pixels. */
+int mcpt_debug_classify(mcpt_scene *scene, const mcpt_camera *camera, uint8_t *may_hit /* W*H */, int32_t *cand /* W*H*4 */,
+                        mcpt_cull_info *info /* nullable */);
+
 /* Diagnostic: counters of the checking build (libmcpt_hip_check.so, compiled with -DMCPT_CHECK_DIRECT_SKIP; the traversal
  * entries are filled only by a -DMCPT_TRAVERSAL_STATS build); all zero in the product build.
  *   out[0..5]   closest-hit rays: rays, node visits, primitive tests, hits, 64 x wave iterations, -

@@ -4,6 +4,8 @@ depth of field, with thin geometry crossing pixels, under tile partitions and pr
 import numpy as np
 import pytest
 
+from cull_cases import thin_scene as _thin_scene
+
 pytestmark = pytest.mark.gpu
 
 
@@ -13,33 +15,6 @@ def _render(hip, sd, monkeypatch, cull, **kw):
     else:
         monkeypatch.setenv("MCPT_SKY_CULL", "0")
     return hip.HipScene(sd).render(**kw)
-
-
-def _thin_scene(pkg, dof):
-    """Needles and slivers far thinner than a pixel, a small sphere, a floor: silhouettes everywhere."""
-    s = pkg.scenes
-    rng = np.random.default_rng(12)
-    P = s.material_presets()
-    b = s._Builder()
-    n = 300
-    tri = np.zeros(n, s.TRI_DTYPE)
-    base = rng.uniform([-40, 0, -40], [40, 60, 40], (n, 3)).astype(np.float32)
-    d1 = rng.normal(0, 1, (n, 3)).astype(np.float32)
-    d1 /= np.linalg.norm(d1, axis=1, keepdims=True)
-    tri["v0"] = base
-    tri["v1"] = base + d1 * rng.uniform(2, 30, (n, 1)).astype(np.float32)
-    tri["v2"] = base + rng.normal(0, 0.02, (n, 3)).astype(np.float32)  # slivers 0.02 units wide
-    b.add_mesh(tri, b.material("rough_white_conductor", P["rough_white_conductor"]))
-    fl = np.zeros(2, s.TRI_DTYPE)
-    fl["v0"], fl["v1"], fl["v2"] = [(-60, 0, -60)] * 2, [(-60, 0, 60), (60, 0, 60)], [(60, 0, 60), (60, 0, -60)]
-    b.add_mesh(fl, b.material("gold_conductor", P["gold_conductor"]))
-    light = s._mat(s.ROUGH_CONDUCTOR, emission=(30, 30, 30))
-    lt = np.zeros(2, s.TRI_DTYPE)
-    lt["v0"], lt["v1"], lt["v2"] = [(-10, 90, -10)] * 2, [(10, 90, -10), (10, 90, 10)], [(10, 90, 10), (-10, 90, 10)]
-    b.add_mesh(lt, b.material("light", light))
-    b.add_sphere((25, 40, 0), 1.5, b.material("smooth_glass", P["smooth_glass"]))
-    cam = s.make_camera(160, 100, 65, (0, 30, -150), (0, 30, 0), (0, 1, 0), dof, 150.0, 4.0)
-    return b.finish(camera=cam, rr_rate=0.5, spp=4, background=np.float32([0.3, 0.5, 0.8]), name="thin")
 
 
 @pytest.mark.parametrize("name", ["chess", "chess_nodof", "thin_dof", "thin", "cornell_demo"])
