@@ -256,9 +256,19 @@ __global__ __launch_bounds__(kB) void k_quantise(int n_nodes, const Node *__rest
 // neighbour -- the one whose union box has the smallest surface area -- among the kRadius clusters before and after them in the
 // array; mutual nearest neighbours are merged into a new inner node, the array is compacted (order preserved), and the round repeats until
 // one cluster is left.  Unlike the Karras hierarchy, whose splits follow the bits of the codes, every merge is chosen by surface area, which
-// is what the SAH measures.  Each round is three small kernels and a scan; the number of clusters falls by 35-45 % per round.
+// is what the SAH measures.  Each round is three small kernels, a scan and a stream synchronise.  On scenes whose union areas mostly
+// differ (the chess scenes, random soups) the number of clusters falls by 35-45 % per round; where many areas are equal it depends on
+// the tie rule alone.
+// Ties.  Pairs are ordered by (area, |i - j|, parity of min(i, j), min(i, j)): a strict total order of the unordered pairs within the
+// radius, so the best pair of the array is each other's nearest neighbour and every round merges at least one pair.  Among equal areas
+// the closest cluster wins and, of the two at one distance, the one that makes a pair (2k, 2k+1): n clusters with identical boxes pair
+// up everywhere and finish in ceil(log2 n) rounds with a tree of ceil(log2 n) + 1 levels.  (Ties used to go to the smaller index
+// alone: then cluster 0 chose 1 and every other cluster i chose max(0, i - radius), one merge per round, a chain of n levels -- refused
+// as too deep from 49 coincident primitives on; a row of 200 equal tiles took 108 rounds, now 9.)  Not a tie and unchanged: boxes nested
+// in order of size chain by area alone.  DESIGN.md section 6b has the round counts; tests/bvh_model.py restates these kernels and
+// tests/test_gpu_builders_model.py compares the trees node by node.
 //   k_ploc_init    cluster i = leaf of the primitive at sorted position i
-//   k_ploc_nn      nearest neighbour within +-radius (boxes staged through LDS; ties -> the smaller index, which guarantees a mutual pair)
+//   k_ploc_nn      nearest neighbour within +-radius (boxes staged through LDS; ties as above)
 //   k_ploc_flags   keep / merge decision per cluster: {stays in the array, creates a node}
 //   hipcub scan    positions in the compacted array and indices of the new nodes
 //   k_ploc_emit    writes the new nodes (both child boxes, child references) and the next round's cluster array
@@ -303,13 +313,18 @@ __global__ __launch_bounds__(kB) void k_ploc_nn(int m, int radius, PlocArrays C,
     if (i >= m) return;
     const float4 mn = smin[threadIdx.x + radius], mx = smax[threadIdx.x + radius];
     float best = INFINITY;
+    unsigned long long btie = 0;
     int bj = -1;
-    for (int d = -radius; d <= radius; ++d) {  // ascending j: a tie keeps the smaller index
+    for (int d = -radius; d <= radius; ++d) {
         const int j = i + d;
         if (d == 0 || j < 0 || j >= m) continue;
         const float a = union_half_area(mn, mx, smin[threadIdx.x + radius + d], smax[threadIdx.x + radius + d]);
-        if (a < best || bj < 0) {
+        // equal areas: (|i - j|, parity of min(i, j), min(i, j)) -- like the area a function of the unordered pair, see the header
+        const unsigned lo = (unsigned)min(i, j);
+        const unsigned long long tie = ((unsigned long long)abs(d) << 33) | ((unsigned long long)(lo & 1u) << 32) | lo;
+        if (bj < 0 || a < best || (a == best && tie < btie)) {
             best = a;
+            btie = tie;
             bj = j;
         }
     }

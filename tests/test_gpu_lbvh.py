@@ -107,7 +107,9 @@ def test_deep_trees_are_exact_and_too_deep_ones_are_refused(pkg, oracle, hip):
     heights = []
     for n in (24, 36, 45, 63):
         sd = _chain(pkg, n)
-        hp = hip.HipScene(sd, builder="ploc")  # (merges by surface area: no chain, whatever the codes look like)
+        # (merges by surface area, not by the codes: shallow here.  PLOC has chains of its own -- boxes nested in order of size and, before
+        # the tie rule of k_ploc_nn, coincident ones: tests/test_bvh_model_cpu.py)
+        hp = hip.HipScene(sd, builder="ploc")
         assert hp.info()["bvh_height"] <= 48
         try:
             hs = hip.HipScene(sd, builder="lbvh")
