@@ -3,7 +3,9 @@
 // A round renders every active pixel up to n samples (round 0: n = S0 for every owned pixel; later rounds: samples [n/2, n) of the
 // pixels that continued, divisor n).  Then:
 //   k_adapt_eval    one lane per active pixel: the estimate e from the double moments that k_accumulate<true> summed, written to the
-//                   error map, and a mark in a W x H byte image: (round stamp << 1) | (e > threshold)
+//                   error map, and a mark in a W x H byte image: (round stamp << 1) | (e > threshold).  k_adapt_eval<true> is the
+//                   guided flavour (mcpt_render_adaptive_guided): the pixel's threshold is tp::guided_threshold(threshold, guide[m]);
+//                   without a guide the plain flavour is launched, as it always was
 //   k_adapt_select  one lane per active pixel: continue iff the pixel's own mark is set or (dilate) a neighbour's mark of THIS round is,
 //                   and 2n <= spp; a continuing pixel's framebuffer value is halved (exact: DESIGN.md, adaptive sampling) and its
 //                   count becomes 2n
@@ -14,6 +16,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include "mcpt_adaptive.h"
+#include "mcpt_temporal.h"
 
 namespace mcpt {
 
@@ -50,16 +53,18 @@ __device__ __forceinline__ double estimate(const double *mo, double n, double re
     return e;
 }
 
+template <bool kGuided>
 __global__ __launch_bounds__(kB) void k_adapt_eval(const uint32_t *__restrict__ list, uint32_t n_list, const double *__restrict__ moments, int32_t n,
-                                                    double rel_floor, double threshold, uint32_t round_stamp, float *__restrict__ err,
-                                                    uint8_t *__restrict__ stamp, int32_t *__restrict__ spp_map) {
+                                                    double rel_floor, double threshold, const float *__restrict__ guide, uint32_t round_stamp,
+                                                    float *__restrict__ err, uint8_t *__restrict__ stamp, int32_t *__restrict__ spp_map) {
     const uint32_t i = blockIdx.x * kB + threadIdx.x;
     if (i >= n_list) return;
     const uint32_t m = list[i];
     const double e = estimate(moments + (size_t)m * 6, (double)n, rel_floor);
     err[m] = (float)e;
     spp_map[m] = n;
-    if (stamp) stamp[m] = (uint8_t)((round_stamp << 1) | (e > threshold ? 1u : 0u));
+    const double thr = kGuided ? tp::guided_threshold(threshold, guide[m]) : threshold;
+    if (stamp) stamp[m] = (uint8_t)((round_stamp << 1) | (e > thr ? 1u : 0u));
 }
 
 __global__ __launch_bounds__(kB) void k_adapt_select(const uint32_t *__restrict__ list, uint32_t n_list, int W, int H, const uint8_t *__restrict__ stamp,
@@ -98,11 +103,15 @@ void launch_sky_moments(const uint32_t *sky_pixels, uint32_t n_sky, const float 
                        spp, moments);
 }
 
-void launch_adapt_eval(const uint32_t *list, uint32_t n_list, const double *moments, int32_t n, double rel_floor, double threshold,
+void launch_adapt_eval(const uint32_t *list, uint32_t n_list, const double *moments, int32_t n, double rel_floor, double threshold, const float *guide,
                        uint32_t round_stamp, float *err, uint8_t *stamp, int32_t *spp_map, hipStream_t st) {
     if (n_list == 0) return;
-    hipLaunchKernelGGL(k_adapt_eval, dim3(nblocks(n_list)), dim3(kB), 0, st, list, n_list, moments, n, rel_floor, threshold, round_stamp, err, stamp,
-                       spp_map);
+    if (guide)
+        hipLaunchKernelGGL(k_adapt_eval<true>, dim3(nblocks(n_list)), dim3(kB), 0, st, list, n_list, moments, n, rel_floor, threshold, guide, round_stamp,
+                           err, stamp, spp_map);
+    else
+        hipLaunchKernelGGL(k_adapt_eval<false>, dim3(nblocks(n_list)), dim3(kB), 0, st, list, n_list, moments, n, rel_floor, threshold, nullptr, round_stamp,
+                           err, stamp, spp_map);
 }
 
 void launch_adapt_select(const uint32_t *list, uint32_t n_list, int width, int height, const uint8_t *stamp, uint32_t round_stamp, int dilate,

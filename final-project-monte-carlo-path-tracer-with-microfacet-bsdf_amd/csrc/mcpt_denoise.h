@@ -313,6 +313,8 @@ void launch_aov_chain(const DevScene &S, uint32_t n, int32_t b, int32_t max_b, c
 void launch_aov_fold(uint32_t p0, uint32_t n_pix, int32_t aov_spp, const float4 *s0, const float4 *s1, float *aov, hipStream_t st);
 // var[m] = dn::luminance_variance of the moments (6 doubles per pixel) of n samples, for every pixel of the frame
 void launch_dn_variance(uint32_t n_px, const double *moments, int32_t n, float *var, hipStream_t st);
+// var[m] = dn::luminance_variance of the moments of spp_map[m] samples (an adaptive frame's count map); 0 where spp_map[m] is 0
+void launch_dn_variance_map(uint32_t n_px, const double *moments, const int32_t *spp_map, float *var, hipStream_t st);
 // The whole filter: prep -> o.iterations a-trous passes (rec0 <-> rec1, W*H records each; grad W*H) -> remodulation into out (W*H*3).
 void launch_denoise(int W, int H, const dn::Opts &o, const float *color, const float *variance, const float *aov, dn::Rec *rec0, dn::Rec *rec1,
                     float2 *grad, float *out, hipStream_t st);

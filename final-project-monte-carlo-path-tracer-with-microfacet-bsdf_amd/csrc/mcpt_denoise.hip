@@ -13,6 +13,7 @@
 //   k_dn_atrous     one iteration (step 2^i), 16 x 16 pixel blocks, two 16-byte loads per tap, ping-pong between two record buffers
 //   k_dn_remod      out = e * A (or the colour, for a pixel that passes through)
 //   k_dn_variance   the luminance variance of the mean from the moments of k_accumulate<true> (mcpt_render_denoised)
+//   k_dn_variance_map  the same from each pixel's own sample count (an adaptive frame: mcpt_render_adaptive_guided)
 #include <hip/hip_runtime.h>
 
 #include "mcpt_denoise.h"
@@ -216,6 +217,16 @@ __global__ __launch_bounds__(kB) void k_dn_variance(uint32_t n_px, const double 
     var[m] = dn::luminance_variance(mo, mo + 3, (double)n);
 }
 
+// the same with each pixel's own sample count (an adaptive frame); a pixel without samples (unowned) gets 0
+__global__ __launch_bounds__(kB) void k_dn_variance_map(uint32_t n_px, const double *__restrict__ moments, const int32_t *__restrict__ spp_map,
+                                                         float *__restrict__ var) {
+    const uint32_t m = blockIdx.x * kB + threadIdx.x;
+    if (m >= n_px) return;
+    const int32_t n = spp_map[m];
+    const double *mo = moments + (size_t)m * 6;
+    var[m] = n > 0 ? dn::luminance_variance(mo, mo + 3, (double)n) : 0.f;
+}
+
 __global__ __launch_bounds__(kTile *kTile) void k_dn_prep(int W, int H, const float *__restrict__ color, const float *__restrict__ variance,
                                                          const float *__restrict__ aov, dn::Rec *__restrict__ rec, float2 *__restrict__ grad) {
     const int x = blockIdx.x * kTile + threadIdx.x, y = blockIdx.y * kTile + threadIdx.y;
@@ -282,6 +293,11 @@ void launch_aov_fold(uint32_t p0, uint32_t n_pix, int32_t aov_spp, const float4 
 void launch_dn_variance(uint32_t n_px, const double *moments, int32_t n, float *var, hipStream_t st) {
     if (n_px == 0) return;
     hipLaunchKernelGGL(k_dn_variance, dim3(nblocks(n_px)), dim3(kB), 0, st, n_px, moments, n, var);
+}
+
+void launch_dn_variance_map(uint32_t n_px, const double *moments, const int32_t *spp_map, float *var, hipStream_t st) {
+    if (n_px == 0) return;
+    hipLaunchKernelGGL(k_dn_variance_map, dim3(nblocks(n_px)), dim3(kB), 0, st, n_px, moments, spp_map, var);
 }
 
 void launch_denoise(int W, int H, const dn::Opts &o, const float *color, const float *variance, const float *aov, dn::Rec *rec0, dn::Rec *rec1,

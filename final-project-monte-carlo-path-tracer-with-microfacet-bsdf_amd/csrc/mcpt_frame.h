@@ -56,6 +56,74 @@ int aov_pass(mcpt_scene *sc, const CameraConst &cc, uint32_t seed, int32_t aov_s
 // The motion pass (include/mcpt.h: mcpt_render_motion): motion_dev[4m ..] for every pixel of the frame, against the scene's snapshot.
 int motion_pass(mcpt_scene *sc, const CameraConst &cc, const CameraConst &prev_cc, uint32_t seed, int32_t aov_spp, float *motion_dev, hipStream_t st);
 
+// What the rounds of an adaptive frame work in (adaptive_rounds): device buffers the caller owns.  Per pixel of the frame: fb 3 floats,
+// mom 6 doubles, spp, err, stamp (1 byte), guide (nullable: the plain rule).  Per listed pixel: the two lists in turn with their candidate
+// entries (read only when the sky cull produced some), the continue flags; the compaction's scratch and its count.
+struct AdaptiveBufs {
+    float *fb = nullptr;
+    double *mom = nullptr;
+    int32_t *spp = nullptr;
+    float *err = nullptr;
+    uint8_t *stamp = nullptr;
+    const float *guide = nullptr;
+    uint32_t *list[2] = {nullptr, nullptr};
+    int4 *cand[2] = {nullptr, nullptr};
+    uint8_t *flags = nullptr;
+    void *temp = nullptr;
+    size_t temp_bytes = 0;
+    uint32_t *count = nullptr;
+};
+
+// The list side of AdaptiveBufs as one owner: room for n listed pixels (at least 1), 9 bytes each and 32 more with the candidate entries,
+// plus the compaction's scratch (adapt_temp_bytes(n)).
+struct AdaptiveLists {
+    DevBuf<uint32_t> list[2], count;
+    DevBuf<int4> cand[2];
+    DevBuf<uint8_t> flags, temp;
+    size_t temp_bytes = 0;
+    hipError_t alloc(uint32_t n, bool with_cand) {
+        n = std::max<uint32_t>(n, 1u);
+        temp_bytes = adapt_temp_bytes(n);
+        hipError_t e = hipSuccess;
+        for (int k = 0; k < 2; ++k) {
+            if (e == hipSuccess) e = list[k].alloc(n);
+            if (e == hipSuccess && with_cand) e = cand[k].alloc(n);
+        }
+        if (e == hipSuccess) e = flags.alloc(n);
+        if (e == hipSuccess) e = temp.alloc(temp_bytes);
+        if (e == hipSuccess) e = count.alloc(1);
+        return e;
+    }
+    void into(AdaptiveBufs &b) const {
+        for (int k = 0; k < 2; ++k) {
+            b.list[k] = list[k].p;
+            b.cand[k] = cand[k].p;
+        }
+        b.flags = flags.p;
+        b.temp = temp.p;
+        b.temp_bytes = temp_bytes;
+        b.count = count.p;
+    }
+};
+
+// What adaptive_rounds reports besides the buffers: mcpt_adaptive_info, the kernel totals of all rounds, the samples rendered (the sum of
+// the count map) and how many of them were traced (the rest: sky cull).
+struct AdaptiveResult {
+    mcpt_adaptive_info info{};
+    Totals totals;
+    uint64_t samples = 0, traced_primary = 0;
+};
+
+// The checks of an adaptive rule against params.spp (mcpt_render_adaptive), `name` for the message.
+int check_adaptive(const char *name, const mcpt_adaptive &o, const mcpt_params &p);
+
+// The rounds of an adaptive frame (include/mcpt.h: mcpt_render_adaptive, with b.guide mcpt_render_adaptive_guided), queued on `st`, which it
+// waits for once per round: clears err, moments, counts and stamps; f.pixels at S0 (the frame cleared, the sky cull); the culled pixels'
+// moments and estimate; then round by round render_list, k_adapt_eval, k_adapt_select and the compaction.  own != nullptr: the list side
+// of b is allocated there once the number of traced pixels is known (a call that owns its buffers); otherwise b has room for every pixel
+// of the frame.  Returns with the stream drained.
+int adaptive_rounds(FrameCall &f, const mcpt_adaptive &o, AdaptiveBufs &b, AdaptiveLists *own, hipStream_t st, AdaptiveResult &res);
+
 // Working buffers of the filter: two record buffers and the depth gradient, 72 bytes per pixel.
 struct DenoiseBufs {
     DevBuf<dn::Rec> rec[2];

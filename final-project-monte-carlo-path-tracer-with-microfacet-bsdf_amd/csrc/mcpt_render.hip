@@ -1,4 +1,4 @@
-// The frame-level entry points of the C ABI (include/mcpt.h): mcpt_render / mcpt_render_device, mcpt_render_adaptive, mcpt_render_aovs[_ex],
+// The frame-level entry points of the C ABI (include/mcpt.h): mcpt_render / mcpt_render_device, mcpt_render_adaptive[_guided | _denoised], mcpt_render_aovs[_ex],
 // mcpt_denoise, mcpt_render_denoised, mcpt_render_motion and mcpt_temporal_blend.  What they share -- the checks of (camera, params), the start of a call, its statistics -- is
 // here once; each entry point is the part that differs.  csrc/mcpt_frame.h declares what csrc/mcpt_sequence.hip uses of it.
 #include <cmath>
@@ -275,6 +275,153 @@ int render_aovs(const char *name, mcpt_scene *sc, const mcpt_camera *cam, uint32
 
 }  // namespace
 
+int mcpt::check_adaptive(const char *name, const mcpt_adaptive &o, const mcpt_params &p) {
+    const auto bad = [&](const char *what) { return fail(MCPT_ERR_ARG, std::string(name) + ": " + what); };
+    if (o.min_spp < 2) return bad("min_spp must be at least 2");
+    int R = 0;
+    while (R <= 15 && ((int64_t)o.min_spp << R) < p.spp) ++R;
+    if (R > 15 || ((int64_t)o.min_spp << R) != p.spp) return bad("params.spp must be min_spp * 2^R, 0 <= R <= 15");
+    if (!(o.threshold >= 0.f) || !std::isfinite(o.threshold)) return bad("threshold must be finite and >= 0");
+    if (!(o.rel_floor > 0.f)) return bad("rel_floor must be > 0");
+    if (o.dilate != 0 && o.dilate != 1) return bad("dilate must be 0 or 1");
+    return MCPT_OK;
+}
+
+int mcpt::adaptive_rounds(FrameCall &f, const mcpt_adaptive &o, AdaptiveBufs &b, AdaptiveLists *own, hipStream_t st, AdaptiveResult &res) {
+    mcpt_scene *sc = f.sc;
+    const mcpt_params &p = f.p;
+    const int W = f.cc.width, H = f.cc.height;
+    const size_t n_px = (size_t)W * H;
+    const int32_t S0 = o.min_spp;
+    const double rel_floor = (double)o.rel_floor, threshold = (double)o.threshold;
+    int rc;
+    HIP_TRY(hipMemsetAsync(b.err, 0, n_px * sizeof(float), st));
+    HIP_TRY(hipMemsetAsync(b.mom, 0, n_px * 6 * sizeof(double), st));
+    HIP_TRY(hipMemsetAsync(b.spp, 0, n_px * sizeof(int32_t), st));
+    HIP_TRY(hipMemsetAsync(b.stamp, 0, n_px, st));
+    if ((rc = f.pixels(S0, (float)S0, b.fb, st)) != MCPT_OK) return rc;  // round 0 of the culled pixels: S0 additions of background / S0
+    const PixelSet &ps = f.ps;
+    mcpt_adaptive_info &inf = res.info;
+    std::memset(&inf, 0, sizeof inf);
+    Totals &all = res.totals;
+    uint64_t &samples = res.samples, &traced_primary = res.traced_primary;
+    samples = traced_primary = 0;
+    if (ps.n_owned > 0) {
+        // the culled pixels are final at S0: their estimate from the constant samples, no mark (they take no part in dilation)
+        const uint32_t n_sky = ps.n_owned - ps.n_pix;
+        if (n_sky > 0) {
+            launch_sky_moments(ps.sky, n_sky, sc->view.background, S0, b.mom, st);
+            launch_adapt_eval(ps.sky, n_sky, b.mom, S0, rel_floor, threshold, nullptr, 0u, b.err, nullptr, b.spp, st);
+        }
+        // the active pixels of the current and of the next round (with their candidate entries when the cull produced them)
+        uint32_t n_act = ps.n_pix;
+        if (own) {
+            HIP_TRY(own->alloc(n_act, ps.cand != nullptr));
+            own->into(b);
+        }
+        if (n_act > 0) {
+            HIP_TRY(hipMemcpyAsync(b.list[0], ps.list, n_act * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+            if (ps.cand) HIP_TRY(hipMemcpyAsync(b.cand[0], ps.cand, n_act * sizeof(int4), hipMemcpyDeviceToDevice, st));
+        }
+        samples = (uint64_t)ps.n_owned * S0;
+        int cur = 0;
+        for (int r = 0;; ++r) {
+            const auto tr = r == 0 ? f.t0 : Clock::now();
+            const int32_t n = S0 << r;                   // samples per active pixel after this round
+            const int32_t first = r == 0 ? 0 : n / 2;    // this round renders samples [first, n), divisor n
+            const bool can_double = 2 * (int64_t)n <= p.spp;
+            uint32_t n_next = 0;
+            if (n_act > 0) {
+                rc = render_list(sc, f.cc, p, b.list[cur], ps.cand ? b.cand[cur] : nullptr, n_act, first, n - first, (float)n, b.fb, b.mom, st, tr, all);
+                if (rc != MCPT_OK) return rc;
+                traced_primary += (uint64_t)n_act * (n - first);
+                if (r > 0) samples += (uint64_t)n_act * (n - first);
+                const uint32_t round_stamp = (uint32_t)r + 1u;
+                launch_adapt_eval(b.list[cur], n_act, b.mom, n, rel_floor, threshold, b.guide, round_stamp, b.err, b.stamp, b.spp, st);
+                launch_adapt_select(b.list[cur], n_act, W, H, b.stamp, round_stamp, o.dilate, can_double ? 1 : 0, n, b.fb, b.spp, b.flags, st);
+                if (can_double)
+                    HIP_TRY(adapt_compact(b.list[cur], ps.cand ? b.cand[cur] : nullptr, b.flags, n_act, b.list[cur ^ 1], ps.cand ? b.cand[cur ^ 1] : nullptr,
+                                          b.temp, b.temp_bytes, b.count, &n_next, st));
+                else
+                    HIP_TRY(hipStreamSynchronize(st));
+            }
+            inf.active_pixels[r] = r == 0 ? ps.n_owned : n_act;
+            inf.ms_round[r] = ms_since(tr);
+            inf.rounds = r + 1;
+            if (n_next == 0) break;
+            n_act = n_next;
+            cur ^= 1;
+        }
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    return MCPT_OK;
+}
+
+namespace {
+
+// The per-pixel buffers of an adaptive frame that owns them (mcpt_render_adaptive[_guided | _denoised]).
+struct AdaptiveFrame {
+    DevBuf<float> fb, err, var;
+    DevBuf<double> mom;
+    DevBuf<int32_t> sppm;
+    DevBuf<uint8_t> stamp;
+    hipError_t alloc(size_t n_px, bool with_var) {
+        hipError_t e = fb.alloc(n_px * 3);
+        if (e == hipSuccess) e = err.alloc(n_px);
+        if (e == hipSuccess) e = mom.alloc(n_px * 6);
+        if (e == hipSuccess) e = sppm.alloc(n_px);
+        if (e == hipSuccess) e = stamp.alloc(n_px);
+        if (e == hipSuccess && with_var) e = var.alloc(n_px);
+        return e;
+    }
+    AdaptiveBufs bufs(const float *guide) const {
+        AdaptiveBufs b;
+        b.fb = fb.p;
+        b.mom = mom.p;
+        b.spp = sppm.p;
+        b.err = err.p;
+        b.stamp = stamp.p;
+        b.guide = guide;
+        return b;
+    }
+};
+
+// mcpt_render_adaptive and mcpt_render_adaptive_guided (`name` for the messages; guide_host and variance_host null for the former)
+int render_adaptive_guided(const char *name, mcpt_scene *sc, const mcpt_camera *cam, const mcpt_params *pp, const mcpt_adaptive *opts,
+                           const float *guide_host, float *fb_host, int32_t *spp_host, float *err_host, float *variance_host, mcpt_adaptive_info *info,
+                           mcpt_stats *stats) {
+    if (!sc || !cam || !pp || !opts || !fb_host) return fail(MCPT_ERR_ARG, std::string(name) + ": null argument");
+    const mcpt_params &p = *pp;
+    int rc = check_frame_call(name, *cam, p, kOneCallFrame);
+    if (rc != MCPT_OK) return rc;
+    if ((rc = check_adaptive(name, *opts, p)) != MCPT_OK) return rc;
+    FrameCall f{sc, p};
+    if ((rc = f.begin(*cam)) != MCPT_OK) return rc;
+    const hipStream_t st = nullptr;
+    const size_t n_px = (size_t)cam->width * cam->height;
+    AdaptiveFrame af;
+    DevBuf<float> guide;
+    HIP_TRY(af.alloc(n_px, variance_host != nullptr));
+    if (guide_host) HIP_TRY(upload(guide, guide_host, n_px));
+    AdaptiveBufs b = af.bufs(guide_host ? guide.p : nullptr);
+    AdaptiveLists lists;
+    AdaptiveResult res;
+    if ((rc = adaptive_rounds(f, *opts, b, &lists, st, res)) != MCPT_OK) return rc;
+    if (variance_host) {
+        launch_dn_variance_map((uint32_t)n_px, af.mom.p, af.sppm.p, af.var.p, st);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    HIP_TRY(download(fb_host, af.fb, n_px * 3));
+    if (spp_host) HIP_TRY(download(spp_host, af.sppm, n_px));
+    if (err_host) HIP_TRY(download(err_host, af.err, n_px));
+    if (variance_host) HIP_TRY(download(variance_host, af.var, n_px));
+    if (info) *info = res.info;
+    return f.end(stats, res.samples, res.traced_primary, res.totals);
+}
+
+}  // namespace
+
 extern "C" {
 
 int mcpt_render_device(mcpt_scene *sc, const mcpt_camera *cam, const mcpt_params *p, float *fb_device, void *hip_stream,
@@ -299,106 +446,74 @@ int mcpt_render(mcpt_scene *sc, const mcpt_camera *cam, const mcpt_params *p, fl
 
 int mcpt_render_adaptive(mcpt_scene *sc, const mcpt_camera *cam, const mcpt_params *pp, const mcpt_adaptive *opts, float *fb_host, int32_t *spp_host,
                          float *err_host, mcpt_adaptive_info *info, mcpt_stats *stats) {
-    const auto bad = [](const char *what) { return fail(MCPT_ERR_ARG, std::string("mcpt_render_adaptive: ") + what); };
-    if (!sc || !cam || !pp || !opts || !fb_host) return bad("null argument");
+    return render_adaptive_guided("mcpt_render_adaptive", sc, cam, pp, opts, nullptr, fb_host, spp_host, err_host, nullptr, info, stats);
+}
+
+int mcpt_render_adaptive_guided(mcpt_scene *sc, const mcpt_camera *cam, const mcpt_params *pp, const mcpt_adaptive *rule, const float *guide_host,
+                                float *fb_host, int32_t *spp_host, float *err_host, float *variance_host, mcpt_adaptive_info *info, mcpt_stats *stats) {
+    return render_adaptive_guided("mcpt_render_adaptive_guided", sc, cam, pp, rule, guide_host, fb_host, spp_host, err_host, variance_host, info, stats);
+}
+
+int mcpt_render_adaptive_denoised(mcpt_scene *sc, const mcpt_camera *cam, const mcpt_params *pp, const mcpt_adaptive *rule, const float *guide_host,
+                                  const mcpt_denoise_opts *opts, float *fb_host, float *denoised_host, int32_t *spp_host, float *err_host,
+                                  float *variance_host, float *aov_host, mcpt_adaptive_info *ainfo, mcpt_denoise_info *info, mcpt_stats *stats) {
+    const char *name = "mcpt_render_adaptive_denoised";
+    const auto bad = [&](const char *what) { return fail(MCPT_ERR_ARG, std::string(name) + ": " + what); };
+    if (!sc || !cam || !pp || !rule || !opts || !fb_host || !denoised_host) return bad("null argument");
     const mcpt_params &p = *pp;
-    const mcpt_adaptive &o = *opts;
-    int rc = check_frame_call("mcpt_render_adaptive", *cam, p, kOneCallFrame);
+    int rc = check_frame_call(name, *cam, p, kDenoisedFrame | kOneRank | kOneCallFrame);
     if (rc != MCPT_OK) return rc;
-    if (o.min_spp < 2) return bad("min_spp must be at least 2");
-    int R = 0;
-    while (R <= 15 && ((int64_t)o.min_spp << R) < p.spp) ++R;
-    if (R > 15 || ((int64_t)o.min_spp << R) != p.spp) return bad("params.spp must be min_spp * 2^R, 0 <= R <= 15");
-    if (!(o.threshold >= 0.f) || !std::isfinite(o.threshold)) return bad("threshold must be finite and >= 0");
-    if (!(o.rel_floor > 0.f)) return bad("rel_floor must be > 0");
-    if (o.dilate != 0 && o.dilate != 1) return bad("dilate must be 0 or 1");
+    if ((rc = check_adaptive(name, *rule, p)) != MCPT_OK) return rc;
+    dn::Opts o;
+    if (dn::resolve_opts(*opts, o) != 0) return bad("option out of range");
+    // every pixel has at least min_spp samples, and feature sample k is render sample k
+    if (opts->aov_spp > rule->min_spp || opts->aov_spp > kMaxAovSpp) return bad("aov_spp must be at most min_spp and 65536");
+    const int32_t aov_spp = opts->aov_spp == 0 ? std::min(4, rule->min_spp) : opts->aov_spp;
     FrameCall f{sc, p};
     if ((rc = f.begin(*cam)) != MCPT_OK) return rc;
     const hipStream_t st = nullptr;
     const int W = cam->width, H = cam->height;
     const size_t n_px = (size_t)W * H;
-    const int32_t S0 = o.min_spp;
-    const double rel_floor = (double)o.rel_floor, threshold = (double)o.threshold;
-    DevBuf<float> fb, err;
-    DevBuf<double> mom;
-    DevBuf<int32_t> sppm;
-    DevBuf<uint8_t> stamp;
-    HIP_TRY(fb.alloc(n_px * 3));
-    HIP_TRY(err.alloc(n_px));
-    HIP_TRY(mom.alloc(n_px * 6));
-    HIP_TRY(sppm.alloc(n_px));
-    HIP_TRY(stamp.alloc(n_px));
-    HIP_TRY(hipMemsetAsync(err.p, 0, n_px * sizeof(float), st));
-    HIP_TRY(hipMemsetAsync(mom.p, 0, n_px * 6 * sizeof(double), st));
-    HIP_TRY(hipMemsetAsync(sppm.p, 0, n_px * sizeof(int32_t), st));
-    HIP_TRY(hipMemsetAsync(stamp.p, 0, n_px, st));
-    if ((rc = f.pixels(S0, (float)S0, fb.p, st)) != MCPT_OK) return rc;  // round 0 of the culled pixels: S0 additions of background / S0
-    const PixelSet &ps = f.ps;
-    mcpt_adaptive_info inf;
-    std::memset(&inf, 0, sizeof inf);
-    Totals all;
-    uint64_t samples = 0, traced_primary = 0;
-    if (ps.n_owned > 0) {
-        // the culled pixels are final at S0: their estimate from the constant samples, no mark (they take no part in dilation)
-        const uint32_t n_sky = ps.n_owned - ps.n_pix;
-        if (n_sky > 0) {
-            launch_sky_moments(ps.sky, n_sky, sc->view.background, S0, mom.p, st);
-            launch_adapt_eval(ps.sky, n_sky, mom.p, S0, rel_floor, threshold, 0u, err.p, nullptr, sppm.p, st);
-        }
-        // the active pixels of the current and of the next round (with their candidate entries when the cull produced them)
-        DevBuf<uint32_t> list[2];
-        DevBuf<int4> cand[2];
-        DevBuf<uint8_t> flags, temp;
-        DevBuf<uint32_t> count;
-        uint32_t n_act = ps.n_pix;
-        const size_t tb = adapt_temp_bytes(std::max<uint32_t>(n_act, 1u));
-        for (int k = 0; k < 2; ++k) {
-            HIP_TRY(list[k].alloc(std::max<uint32_t>(n_act, 1u)));
-            if (ps.cand) HIP_TRY(cand[k].alloc(std::max<uint32_t>(n_act, 1u)));
-        }
-        HIP_TRY(flags.alloc(std::max<uint32_t>(n_act, 1u)));
-        HIP_TRY(temp.alloc(tb));
-        HIP_TRY(count.alloc(1));
-        if (n_act > 0) {
-            HIP_TRY(hipMemcpyAsync(list[0].p, ps.list, n_act * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
-            if (ps.cand) HIP_TRY(hipMemcpyAsync(cand[0].p, ps.cand, n_act * sizeof(int4), hipMemcpyDeviceToDevice, st));
-        }
-        samples = (uint64_t)ps.n_owned * S0;
-        int cur = 0;
-        for (int r = 0;; ++r) {
-            const auto tr = r == 0 ? f.t0 : Clock::now();
-            const int32_t n = S0 << r;                   // samples per active pixel after this round
-            const int32_t first = r == 0 ? 0 : n / 2;    // this round renders samples [first, n), divisor n
-            const bool can_double = 2 * (int64_t)n <= p.spp;
-            uint32_t n_next = 0;
-            if (n_act > 0) {
-                rc = render_list(sc, f.cc, p, list[cur].p, ps.cand ? cand[cur].p : nullptr, n_act, first, n - first, (float)n, fb.p, mom.p, st, tr, all);
-                if (rc != MCPT_OK) return rc;
-                traced_primary += (uint64_t)n_act * (n - first);
-                if (r > 0) samples += (uint64_t)n_act * (n - first);
-                const uint32_t round_stamp = (uint32_t)r + 1u;
-                launch_adapt_eval(list[cur].p, n_act, mom.p, n, rel_floor, threshold, round_stamp, err.p, stamp.p, sppm.p, st);
-                launch_adapt_select(list[cur].p, n_act, W, H, stamp.p, round_stamp, o.dilate, can_double ? 1 : 0, n, fb.p, sppm.p, flags.p, st);
-                if (can_double)
-                    HIP_TRY(adapt_compact(list[cur].p, ps.cand ? cand[cur].p : nullptr, flags.p, n_act, list[cur ^ 1].p, ps.cand ? cand[cur ^ 1].p : nullptr,
-                                          temp.p, tb, count.p, &n_next, st));
-                else
-                    HIP_TRY(hipStreamSynchronize(st));
-            }
-            inf.active_pixels[r] = r == 0 ? ps.n_owned : n_act;
-            inf.ms_round[r] = ms_since(tr);
-            inf.rounds = r + 1;
-            if (n_next == 0) break;
-            n_act = n_next;
-            cur ^= 1;
-        }
-    }
+    AdaptiveFrame af;
+    DevBuf<float> aov, out, guide;
+    HIP_TRY(af.alloc(n_px, true));
+    HIP_TRY(aov.alloc(n_px * 8));
+    HIP_TRY(out.alloc(n_px * 3));
+    if (guide_host) HIP_TRY(upload(guide, guide_host, n_px));
+    DenoiseBufs db;
+    HIP_TRY(db.alloc(n_px));
+    Event ev[4];  // around the three stages: rounds, AOV pass, filter
+    for (int k = 0; k < 4; ++k) HIP_TRY(ev[k].create(true));
+    HIP_TRY(hipEventRecord(ev[0], st));
+    AdaptiveBufs b = af.bufs(guide_host ? guide.p : nullptr);
+    AdaptiveLists lists;
+    AdaptiveResult res;
+    if ((rc = adaptive_rounds(f, *rule, b, &lists, st, res)) != MCPT_OK) return rc;
+    launch_dn_variance_map((uint32_t)n_px, af.mom.p, af.sppm.p, af.var.p, st);
+    HIP_TRY(hipEventRecord(ev[1], st));
+    rc = aov_pass(sc, f.cc, p.seed, aov_spp, opts->specular_depth, aov.p, st);
+    if (rc != MCPT_OK) return drained(rc);
+    HIP_TRY(hipEventRecord(ev[2], st));
+    launch_denoise(W, H, o, af.fb.p, af.var.p, aov.p, db.rec[0].p, db.rec[1].p, db.grad.p, out.p, st);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(ev[3], st));
     HIP_TRY(hipStreamSynchronize(st));
-    HIP_TRY(download(fb_host, fb, n_px * 3));
-    if (spp_host) HIP_TRY(download(spp_host, sppm, n_px));
-    if (err_host) HIP_TRY(download(err_host, err, n_px));
-    if (info) *info = inf;
-    return f.end(stats, samples, traced_primary, all);
+    HIP_TRY(download(fb_host, af.fb, n_px * 3));
+    HIP_TRY(download(denoised_host, out, n_px * 3));
+    if (spp_host) HIP_TRY(download(spp_host, af.sppm, n_px));
+    if (err_host) HIP_TRY(download(err_host, af.err, n_px));
+    if (variance_host) HIP_TRY(download(variance_host, af.var, n_px));
+    if (aov_host) HIP_TRY(download(aov_host, aov, n_px * 8));
+    if (ainfo) *ainfo = res.info;
+    if (info) {
+        float ms[3] = {0.f, 0.f, 0.f};
+        for (int k = 0; k < 3; ++k) HIP_TRY(hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]));
+        info->ms_render = ms[0];
+        info->ms_aov = ms[1];
+        info->ms_denoise = ms[2];
+        info->ms_total = ms_since(f.t0);
+    }
+    return f.end(stats, res.samples, res.traced_primary, res.totals);
 }
 
 int mcpt_render_aovs(mcpt_scene *sc, const mcpt_camera *cam, uint32_t seed, int32_t aov_spp, float *aov_host) {

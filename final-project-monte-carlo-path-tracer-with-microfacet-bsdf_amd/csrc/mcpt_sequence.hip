@@ -3,6 +3,9 @@
 // (csrc/mcpt_frame.h) on the sequence's buffers, k_temporal_accumulate (csrc/mcpt_temporal.hip) between the two history sets, the filter
 // and the tone map, all queued on one stream; only the outputs the caller asks for are copied to the host.  A sequence created with
 // history rejection (mcpt_sequence_create_ex) runs k_temporal_accumulate_ex instead and keeps a normal and a flags plane per history set.
+// A sequence created with a rule (mcpt_sequence_create_adaptive) renders adaptive frames: the AOVs and the motion first, k_history_len from
+// the previous history set into the guide, then the rounds of csrc/mcpt_render.hip (adaptive_rounds) on the sequence's buffers and
+// k_dn_variance_map; mcpt_temporal_history_len is the guide's kernel on host arrays.
 #include <new>
 
 #include "mcpt_frame.h"
@@ -36,6 +39,22 @@ struct History {
     }
 };
 
+// The counts of one adaptive frame and the guide it was rendered with; two sets, used in turn with the history sets, so that a failed
+// frame leaves those of the last successful one.
+struct Counts {
+    DevBuf<int32_t> spp;
+    DevBuf<float> err, guide;
+    hipError_t alloc(size_t n_px) {
+        hipError_t e = spp.alloc(n_px);
+        if (e == hipSuccess) e = err.alloc(n_px);
+        if (e == hipSuccess) e = guide.alloc(n_px);
+        if (e == hipSuccess) e = hipMemset(spp.p, 0, n_px * sizeof(int32_t));
+        if (e == hipSuccess) e = hipMemset(err.p, 0, n_px * sizeof(float));
+        if (e == hipSuccess) e = hipMemset(guide.p, 0, n_px * sizeof(float));
+        return e;
+    }
+};
+
 constexpr int kStages = 5;  // render, AOVs, motion, accumulate, filter (+ tone map)
 
 }  // namespace
@@ -58,7 +77,15 @@ struct mcpt_sequence {
     DevBuf<double> mom;
     DevBuf<uint8_t> rgba;
     DenoiseBufs db;
-    Event ev[kStages + 1];
+    Event ev[kStages + 2];  // (the last one: the end of an adaptive sequence's rounds)
+    // a sequence created with mcpt_sequence_create_adaptive and a rule (all empty otherwise)
+    bool adaptive = false;
+    mcpt_adaptive rule{};
+    bool guided = false;
+    Counts cnt[2];  // indexed as hist
+    DevBuf<uint8_t> stamp;
+    AdaptiveLists lists;
+    mcpt_adaptive_info ainfo{};  // of the last successful frame
 };
 
 extern "C" {
@@ -146,6 +173,36 @@ int mcpt_temporal_accumulate_ex(mcpt_scene *sc, int32_t width, int32_t height, c
     return MCPT_OK;
 }
 
+int mcpt_temporal_history_len(mcpt_scene *sc, int32_t width, int32_t height, const float *motion_host, const float *normal_host,
+                              const float *prev_color_host, const float *prev_depth_host, const float *prev_len_host, const float *prev_normal_host,
+                              const mcpt_temporal_opts *opts, const mcpt_history_opts *hopts, float *len_host) {
+    const auto bad = [](const char *what) { return fail(MCPT_ERR_ARG, std::string("mcpt_temporal_history_len: ") + what); };
+    if (!sc || !motion_host || !prev_color_host || !prev_depth_host || !prev_len_host || !opts || !len_host) return bad("null argument");
+    if (!frame_ok(width, height)) return bad("width and height must be positive (and the frame not too large)");
+    tp::Opts o;
+    tp::HistOpts ho{};
+    if (tp::resolve_opts(*opts, o) != 0) return bad("option out of range");
+    if (hopts && tp::resolve_history_opts(*hopts, ho) != 0) return bad("history option out of range");
+    if (ho.normal_test && (!normal_host || !prev_normal_host)) return bad("normal_test needs both normal arrays");
+    HIP_TRY(hipSetDevice(sc->device));
+    (void)hipGetLastError();
+    const size_t n_px = (size_t)width * height;
+    DevBuf<float> mot, nrm, pcol, pz, plen, pnrm, len;
+    HIP_TRY(len.alloc(n_px));
+    HIP_TRY(upload(mot, motion_host, n_px * 4));
+    HIP_TRY(upload(pcol, prev_color_host, n_px * 3));
+    HIP_TRY(upload(pz, prev_depth_host, n_px));
+    HIP_TRY(upload(plen, prev_len_host, n_px));
+    if (ho.normal_test) {
+        HIP_TRY(upload(nrm, normal_host, n_px * 3));
+        HIP_TRY(upload(pnrm, prev_normal_host, n_px * 3));
+    }
+    launch_history_len(width, height, o, ho, mot.p, nrm.p, 3, pcol.p, pz.p, plen.p, pnrm.p, len.p, nullptr);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(download(len_host, len, n_px));
+    return MCPT_OK;
+}
+
 void mcpt_sequence_destroy(mcpt_sequence *seq) {
     if (!seq) return;
     (void)hipSetDevice(seq->device);
@@ -159,6 +216,11 @@ int mcpt_sequence_create(mcpt_scene *sc, int32_t width, int32_t height, const mc
 
 int mcpt_sequence_create_ex(mcpt_scene *sc, int32_t width, int32_t height, const mcpt_sequence_opts *opts, const mcpt_history_opts *hopts,
                             mcpt_sequence **out) {
+    return mcpt_sequence_create_adaptive(sc, width, height, opts, hopts, nullptr, out);
+}
+
+int mcpt_sequence_create_adaptive(mcpt_scene *sc, int32_t width, int32_t height, const mcpt_sequence_opts *opts, const mcpt_history_opts *hopts,
+                                  const mcpt_sequence_adaptive *aopts, mcpt_sequence **out) {
     const auto bad = [](const char *what) { return fail(MCPT_ERR_ARG, std::string("mcpt_sequence_create: ") + what); };
     if (!sc || !opts || !out) return bad("null argument");
     *out = nullptr;
@@ -172,6 +234,20 @@ int mcpt_sequence_create_ex(mcpt_scene *sc, int32_t width, int32_t height, const
     if (opts->filter != 0 && opts->filter != 1) return bad("filter must be 0 or 1");
     for (int k = 0; k < 7; ++k)
         if (opts->reserved[k] != 0) return bad("reserved words must be 0");
+    if (aopts) {
+        // what of the rule does not depend on a frame's params.spp (mcpt_sequence_frame checks the rest)
+        const mcpt_adaptive &r = aopts->rule;
+        if (r.min_spp < 2) return bad("adaptive: min_spp must be at least 2");
+        if (!(r.threshold >= 0.f) || !(r.threshold <= 3.0e38f)) return bad("adaptive: threshold must be finite and >= 0");
+        if (!(r.rel_floor > 0.f)) return bad("adaptive: rel_floor must be > 0");
+        if (r.dilate != 0 && r.dilate != 1) return bad("adaptive: dilate must be 0 or 1");
+        if (aopts->guided != 0 && aopts->guided != 1) return bad("adaptive: guided must be 0 or 1");
+        for (int k = 0; k < 4; ++k)
+            if (r.reserved[k] != 0) return bad("adaptive: reserved words must be 0");
+        for (int k = 0; k < 7; ++k)
+            if (aopts->reserved[k] != 0) return bad("adaptive: reserved words must be 0");
+        if (opts->denoise.aov_spp > r.min_spp) return bad("adaptive: denoise.aov_spp must be at most min_spp");
+    }
     HIP_TRY(hipSetDevice(sc->device));
     (void)hipGetLastError();
     mcpt_sequence *seq = new (std::nothrow) mcpt_sequence();
@@ -184,6 +260,11 @@ int mcpt_sequence_create_ex(mcpt_scene *sc, int32_t width, int32_t height, const
     seq->temporal = to;
     seq->reject = ho;
     seq->denoise = dno;
+    if (aopts) {
+        seq->adaptive = true;
+        seq->rule = aopts->rule;
+        seq->guided = aopts->guided != 0;
+    }
     const size_t n_px = (size_t)width * height;
     hipError_t e = hipSuccess;
     const auto also = [&](auto &buf, size_t n) {
@@ -202,7 +283,13 @@ int mcpt_sequence_create_ex(mcpt_scene *sc, int32_t width, int32_t height, const
     if (opts->filter) also(seq->out, n_px * 3);
     also(seq->rgba, n_px * 4);
     if (opts->filter && e == hipSuccess) e = seq->db.alloc(n_px);
-    for (int k = 0; k <= kStages; ++k)
+    if (aopts) {  // every working buffer of the rounds, for all pixels active
+        for (int k = 0; k < 2; ++k)
+            if (e == hipSuccess) e = seq->cnt[k].alloc(n_px);
+        also(seq->stamp, n_px);
+        if (e == hipSuccess) e = seq->lists.alloc((uint32_t)n_px, true);
+    }
+    for (int k = 0; k <= kStages + 1; ++k)
         if (e == hipSuccess) e = seq->ev[k].create(true);
     // the snapshot's arrays are allocated here too, so that the one at the end of a frame only copies
     const int rc = e == hipSuccess ? mcpt_scene_snapshot(sc)
@@ -221,6 +308,19 @@ int mcpt_sequence_flags(mcpt_sequence *seq, uint8_t *flags_host) {
     if (!flags.p) return fail(MCPT_ERR_ARG, "mcpt_sequence_flags: the sequence was created without history rejection and keeps no flags");
     HIP_TRY(hipSetDevice(seq->device));
     HIP_TRY(download(flags_host, flags, (size_t)seq->W * seq->H));
+    return MCPT_OK;
+}
+
+int mcpt_sequence_counts(mcpt_sequence *seq, int32_t *spp_host, float *err_host, float *guide_host, mcpt_adaptive_info *info) {
+    if (!seq) return fail(MCPT_ERR_ARG, "mcpt_sequence_counts: null sequence");
+    if (!seq->adaptive) return fail(MCPT_ERR_ARG, "mcpt_sequence_counts: the sequence was created without an adaptive rule and keeps no counts");
+    const Counts &c = seq->cnt[seq->cur];  // (the set the last successful frame wrote)
+    const size_t n_px = (size_t)seq->W * seq->H;
+    HIP_TRY(hipSetDevice(seq->device));
+    if (spp_host) HIP_TRY(download(spp_host, c.spp, n_px));
+    if (err_host) HIP_TRY(download(err_host, c.err, n_px));
+    if (guide_host) HIP_TRY(download(guide_host, c.guide, n_px));
+    if (info) *info = seq->ainfo;
     return MCPT_OK;
 }
 
@@ -244,7 +344,11 @@ int mcpt_sequence_frame(mcpt_sequence *seq, const mcpt_camera *cam, const mcpt_p
     const mcpt_sequence_outputs want = outputs ? *outputs : mcpt_sequence_outputs{};
     const bool filter = seq->opts.filter != 0;
     if (want.denoised && !filter) return bad("outputs.denoised needs a sequence created with filter 1");
-    const int32_t aov_spp = dopts.aov_spp == 0 ? std::min(4, p.spp) : dopts.aov_spp;
+    if (seq->adaptive) {
+        if ((rc = check_adaptive("mcpt_sequence_frame", seq->rule, p)) != MCPT_OK) return rc;
+        if (dopts.aov_spp > seq->rule.min_spp) return bad("denoise.aov_spp must be at most min_spp");
+    }
+    const int32_t aov_spp = dopts.aov_spp == 0 ? std::min(4, seq->adaptive ? seq->rule.min_spp : p.spp) : dopts.aov_spp;
     mcpt_scene *sc = seq->sc;
     FrameCall f{sc, p};
     if ((rc = f.begin(*cam)) != MCPT_OK) return rc;
@@ -254,31 +358,72 @@ int mcpt_sequence_frame(mcpt_sequence *seq, const mcpt_camera *cam, const mcpt_p
     const History &prev = seq->hist[seq->cur];
     History &next = seq->hist[seq->cur ^ 1];
     const Event *ev = seq->ev;
-    // 2. the frame with its moments, and its variance (mcpt_render_denoised, steps 1-2)
-    HIP_TRY(hipEventRecord(ev[0], st));
-    HIP_TRY(hipMemsetAsync(seq->mom.p, 0, n_px * 6 * sizeof(double), st));
-    if ((rc = f.pixels(p.spp, (float)p.spp, seq->fb.p, st)) != MCPT_OK) return rc;
-    const PixelSet &ps = f.ps;
     Totals rt;
-    if (ps.n_owned > ps.n_pix) launch_sky_moments(ps.sky, ps.n_owned - ps.n_pix, sc->view.background, p.spp, seq->mom.p, st);
-    if (ps.n_pix > 0) {
-        rc = render_list(sc, f.cc, p, ps.list, ps.cand, ps.n_pix, 0, p.spp, (float)p.spp, seq->fb.p, seq->mom.p, st, f.t0, rt);
-        if (rc != MCPT_OK) return rc;
-    }
-    launch_dn_variance((uint32_t)n_px, seq->mom.p, p.spp, seq->var.p, st);
-    HIP_TRY(hipEventRecord(ev[1], st));
-    // 3. the AOVs, and the first-hit depth the history is validated against
-    rc = aov_pass(sc, f.cc, p.seed, aov_spp, dopts.specular_depth, seq->aov.p, st);
-    if (rc == MCPT_OK && dopts.specular_depth > 0) rc = aov_pass(sc, f.cc, p.seed, aov_spp, 0, seq->aov_first.p, st);
-    if (rc != MCPT_OK) return drained(rc);
+    uint64_t samples = 0, traced_primary = 0;
+    mcpt_adaptive_info ainfo{};
     const float *first_hit = dopts.specular_depth > 0 ? seq->aov_first.p : seq->aov.p;
-    HIP_TRY(hipEventRecord(ev[2], st));
-    // 4. the motion against the snapshot and the previous frame's camera
-    rc = motion_pass(sc, f.cc, seq->fresh ? f.cc : seq->prev_cc, p.seed, aov_spp, seq->motion.p, st);
-    if (rc != MCPT_OK) return drained(rc);
-    HIP_TRY(hipEventRecord(ev[3], st));
+    if (!seq->adaptive) {
+        // 2. the frame with its moments, and its variance (mcpt_render_denoised, steps 1-2)
+        HIP_TRY(hipEventRecord(ev[0], st));
+        HIP_TRY(hipMemsetAsync(seq->mom.p, 0, n_px * 6 * sizeof(double), st));
+        if ((rc = f.pixels(p.spp, (float)p.spp, seq->fb.p, st)) != MCPT_OK) return rc;
+        const PixelSet &ps = f.ps;
+        if (ps.n_owned > ps.n_pix) launch_sky_moments(ps.sky, ps.n_owned - ps.n_pix, sc->view.background, p.spp, seq->mom.p, st);
+        if (ps.n_pix > 0) {
+            rc = render_list(sc, f.cc, p, ps.list, ps.cand, ps.n_pix, 0, p.spp, (float)p.spp, seq->fb.p, seq->mom.p, st, f.t0, rt);
+            if (rc != MCPT_OK) return rc;
+        }
+        launch_dn_variance((uint32_t)n_px, seq->mom.p, p.spp, seq->var.p, st);
+        samples = (uint64_t)ps.n_owned * p.spp;
+        traced_primary = (uint64_t)ps.n_pix * p.spp;
+        HIP_TRY(hipEventRecord(ev[1], st));
+        // 3. the AOVs, and the first-hit depth the history is validated against
+        rc = aov_pass(sc, f.cc, p.seed, aov_spp, dopts.specular_depth, seq->aov.p, st);
+        if (rc == MCPT_OK && dopts.specular_depth > 0) rc = aov_pass(sc, f.cc, p.seed, aov_spp, 0, seq->aov_first.p, st);
+        if (rc != MCPT_OK) return drained(rc);
+        HIP_TRY(hipEventRecord(ev[2], st));
+        // 4. the motion against the snapshot and the previous frame's camera
+        rc = motion_pass(sc, f.cc, seq->fresh ? f.cc : seq->prev_cc, p.seed, aov_spp, seq->motion.p, st);
+        if (rc != MCPT_OK) return drained(rc);
+        HIP_TRY(hipEventRecord(ev[3], st));
+        if (seq->fresh) HIP_TRY(hipMemsetAsync(prev.len.p, 0, n_px * sizeof(float), st));
+    } else {
+        // An adaptive sequence (mcpt_sequence_create_adaptive): the AOVs and the motion first -- neither depends on the frame -- so that the
+        // guide is known before the rounds.  The events keep their stages: ev[1], ev[2], ev[3] around the AOVs and the motion (with the
+        // guide), then ev[0] and ev[kStages + 1] around the rounds, which ms_render is taken between.
+        Counts &cn = seq->cnt[seq->cur ^ 1];
+        HIP_TRY(hipEventRecord(ev[1], st));
+        rc = aov_pass(sc, f.cc, p.seed, aov_spp, dopts.specular_depth, seq->aov.p, st);
+        if (rc == MCPT_OK && dopts.specular_depth > 0) rc = aov_pass(sc, f.cc, p.seed, aov_spp, 0, seq->aov_first.p, st);
+        if (rc != MCPT_OK) return drained(rc);
+        HIP_TRY(hipEventRecord(ev[2], st));
+        rc = motion_pass(sc, f.cc, seq->fresh ? f.cc : seq->prev_cc, p.seed, aov_spp, seq->motion.p, st);
+        if (rc != MCPT_OK) return drained(rc);
+        if (seq->fresh) HIP_TRY(hipMemsetAsync(prev.len.p, 0, n_px * sizeof(float), st));
+        // the guide: the history length each pixel is about to get (1 everywhere on a fresh sequence: prev_len is 0); counted with the motion
+        if (seq->guided)
+            launch_history_len(W, H, seq->temporal, seq->reject, seq->motion.p, first_hit + 3, 8, prev.color.p, prev.depth.p, prev.len.p, prev.normal.p,
+                               cn.guide.p, st);
+        HIP_TRY(hipEventRecord(ev[3], st));
+        AdaptiveBufs b;
+        b.fb = seq->fb.p;
+        b.mom = seq->mom.p;
+        b.spp = cn.spp.p;
+        b.err = cn.err.p;
+        b.stamp = seq->stamp.p;
+        b.guide = seq->guided ? cn.guide.p : nullptr;
+        seq->lists.into(b);
+        AdaptiveResult res;
+        HIP_TRY(hipEventRecord(ev[0], st));
+        if ((rc = adaptive_rounds(f, seq->rule, b, nullptr, st, res)) != MCPT_OK) return rc;
+        launch_dn_variance_map((uint32_t)n_px, seq->mom.p, cn.spp.p, seq->var.p, st);
+        HIP_TRY(hipEventRecord(ev[kStages + 1], st));
+        rt = res.totals;
+        samples = res.samples;
+        traced_primary = res.traced_primary;
+        ainfo = res.info;
+    }
     // 5. previous history set -> the other one
-    if (seq->fresh) HIP_TRY(hipMemsetAsync(prev.len.p, 0, n_px * sizeof(float), st));
     if (seq->reject.normal_test || seq->reject.color_clamp)  // (the normals come from the AOVs the depth comes from)
         launch_temporal_accumulate_ex(W, H, seq->temporal, seq->reject, seq->fb.p, seq->var.p, seq->motion.p, first_hit + 3, 8, prev.color.p, prev.variance.p,
                                       prev.depth.p, prev.len.p, prev.normal.p, first_hit + 6, 8, next.color.p, next.variance.p, next.depth.p, next.len.p,
@@ -302,8 +447,13 @@ int mcpt_sequence_frame(mcpt_sequence *seq, const mcpt_camera *cam, const mcpt_p
     if (want.motion) HIP_TRY(download(want.motion, seq->motion, n_px * 4));
     if (want.rgba) HIP_TRY(download(want.rgba, seq->rgba, n_px * 4));
     float ms[kStages] = {0.f, 0.f, 0.f, 0.f, 0.f};
-    if (info)
-        for (int k = 0; k < kStages; ++k) HIP_TRY(hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]));
+    if (info) {
+        for (int k = seq->adaptive ? 1 : 0; k < kStages; ++k) HIP_TRY(hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]));
+        if (seq->adaptive) {  // the rounds ran after the motion stage: ev[0] .. ev[kStages + 1]; the accumulate stage starts where they end
+            HIP_TRY(hipEventElapsedTime(&ms[0], ev[0], ev[kStages + 1]));
+            HIP_TRY(hipEventElapsedTime(&ms[3], ev[kStages + 1], ev[4]));
+        }
+    }
     // 8. this frame's geometry is "previous" for the next one
     if ((rc = mcpt_scene_snapshot(sc)) != MCPT_OK) return rc;
     // the stream has drained cleanly: the history advances
@@ -312,6 +462,7 @@ int mcpt_sequence_frame(mcpt_sequence *seq, const mcpt_camera *cam, const mcpt_p
     seq->fresh = false;
     seq->frame_index = index + 1;
     seq->prev_cc = f.cc;
+    seq->ainfo = ainfo;
     if (info) {
         std::memset(info, 0, sizeof *info);
         info->ms_render = ms[0];
@@ -322,7 +473,7 @@ int mcpt_sequence_frame(mcpt_sequence *seq, const mcpt_camera *cam, const mcpt_p
         info->ms_total = ms_since(f.t0);
         info->frame_index = index;
     }
-    return f.end(stats, (uint64_t)ps.n_owned * p.spp, (uint64_t)ps.n_pix * p.spp, rt);
+    return f.end(stats, samples, traced_primary, rt);
 }
 
 }  // extern "C"

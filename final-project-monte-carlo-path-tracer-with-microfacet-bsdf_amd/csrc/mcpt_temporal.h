@@ -356,6 +356,37 @@ MCPT_TP void accumulate_pixel_ex(int W, int H, int i, int j, const float *color,
     if (out_flags) out_flags[m] = flags;
 }
 
+/* The history length pixel (i, j) is about to get (include/mcpt.h: mcpt_temporal_history_len): steps 1-4 of the blend and the N of step 5,
+ * with the new colour taken to be finite.  motion.valid <= 0, or no tap left: 1; otherwise N = min(nmin + 1, max_history).  The taps and
+ * their skips are gather_taps<false, kNorm>'s, the normal test included when ho.normal_test is 1 (normal at normal[normal_stride m ..], as
+ * in accumulate_pixel_ex); the colour clamp does not enter, because a clamped history keeps its length.  So the value equals the out_len of
+ * accumulate_pixel / accumulate_pixel_ex on the same inputs for every pixel whose new colour is finite, and it is known before the frame
+ * is rendered: neither `color` nor `variance` is read. */
+MCPT_TP float history_len_pixel(int W, int H, int i, int j, const float *motion, const float *normal, int normal_stride, const float *prev_color,
+                                const float *prev_depth, const float *prev_len, const float *prev_normal, const Opts &o, const HistOpts &ho) {
+    const size_t m = (size_t)j * W + i;
+    const float *mv = motion + m * 4;
+    if (!(mv[3] > 0.0f)) return 1.0f;
+    Taps t;
+    bool any;
+    if (ho.normal_test) {
+        const float n3[3] = {normal[m * (size_t)normal_stride], normal[m * (size_t)normal_stride + 1], normal[m * (size_t)normal_stride + 2]};
+        any = gather_taps<false, true>(W, H, i, j, mv, prev_color, nullptr, prev_depth, prev_len, o, t, prev_normal, n3, ho.normal_min);
+    } else {
+        any = gather_taps<false>(W, H, i, j, mv, prev_color, nullptr, prev_depth, prev_len, o, t);
+    }
+    if (!any) return 1.0f;
+    const float n1 = t.nmin + 1.0f;
+    return n1 < o.max_history ? n1 : o.max_history;
+}
+
+/* The stopping threshold of a guided adaptive pixel (include/mcpt.h: mcpt_render_adaptive_guided): threshold * sqrt(g) in double, with
+ * g = guide if guide >= 1 and 1 otherwise, so that a NaN, zero or negative guide leaves the plain rule (sqrt(1.0) is exactly 1). */
+MCPT_TP double guided_threshold(double threshold, float guide) {
+    const double g = guide >= 1.0f ? (double)guide : 1.0;
+    return threshold * sqrt(g);
+}
+
 }  // namespace tp
 }  // namespace mcpt
 
@@ -388,6 +419,10 @@ void launch_temporal_accumulate_ex(int W, int H, const tp::Opts &o, const tp::Hi
                                    const float *normal, int normal_stride, const float *prev_color, const float *prev_variance, const float *prev_depth,
                                    const float *prev_len, const float *prev_normal, const float *depth, int depth_stride, float *out_color,
                                    float *out_variance, float *out_depth, float *out_len, float *out_normal, uint8_t *out_flags, hipStream_t st);
+// The history length every pixel of a W x H frame is about to get (k_history_len: tp::history_len_pixel) into len[m]; normal / prev_normal
+// as for launch_temporal_accumulate_ex, read only with ho.normal_test (ho with both switches 0: the lengths of launch_temporal_accumulate).
+void launch_history_len(int W, int H, const tp::Opts &o, const tp::HistOpts &ho, const float *motion, const float *normal, int normal_stride,
+                        const float *prev_color, const float *prev_depth, const float *prev_len, const float *prev_normal, float *len, hipStream_t st);
 }  // namespace mcpt
 #endif
 #endif  // MCPT_TEMPORAL_H

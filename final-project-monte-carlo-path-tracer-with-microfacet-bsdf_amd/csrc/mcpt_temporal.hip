@@ -19,6 +19,9 @@
 //                     pixels, 1.27 x its own colour bytes); an LDS tile with a halo would add a barrier and a second pass over the halo
 //                     to save loads that already hit.  It also copies the frame's first-hit normal into the history's normal plane and
 //                     writes the flags byte, both with plain vector stores.
+// Guide of an adaptive sequence (mcpt_temporal_history_len, a sequence created with mcpt_sequence_create_adaptive, guided 1):
+//   k_history_len     the same shape; tp::history_len_pixel: the taps and skips of the blend without its colour, so the length a pixel is
+//                     about to get is known before the frame is rendered.  One plain vector store per lane.
 #include <hip/hip_runtime.h>
 
 #include "mcpt_temporal.h"
@@ -120,6 +123,15 @@ __global__ __launch_bounds__(kTile *kTile) void k_temporal_accumulate_ex(
     }
 }
 
+__global__ __launch_bounds__(kTile *kTile) void k_history_len(int W, int H, tp::Opts o, tp::HistOpts ho, const float *__restrict__ motion,
+                                                              const float *__restrict__ normal, int normal_stride, const float *__restrict__ prev_color,
+                                                              const float *__restrict__ prev_depth, const float *__restrict__ prev_len,
+                                                              const float *__restrict__ prev_normal, float *__restrict__ len) {
+    const int x = blockIdx.x * kTile + threadIdx.x, y = blockIdx.y * kTile + threadIdx.y;
+    if (x >= W || y >= H) return;
+    len[(size_t)y * W + x] = tp::history_len_pixel(W, H, x, y, motion, normal, normal_stride, prev_color, prev_depth, prev_len, prev_normal, o, ho);
+}
+
 }  // namespace
 
 void launch_motion_resolve(const DevScene &S, const TriGeom *prev_tri, const SphereRec *prev_sph, const tp::Cam &cur, const tp::Cam &prev, uint32_t n,
@@ -154,6 +166,12 @@ void launch_temporal_accumulate_ex(int W, int H, const tp::Opts &o, const tp::Hi
     const dim3 grid((W + kTile - 1) / kTile, (H + kTile - 1) / kTile), blk(kTile, kTile);
     hipLaunchKernelGGL(k_temporal_accumulate_ex, grid, blk, 0, st, W, H, o, ho, color, variance, motion, normal, normal_stride, prev_color, prev_variance,
                        prev_depth, prev_len, prev_normal, depth, depth_stride, out_color, out_variance, out_depth, out_len, out_normal, out_flags);
+}
+
+void launch_history_len(int W, int H, const tp::Opts &o, const tp::HistOpts &ho, const float *motion, const float *normal, int normal_stride,
+                        const float *prev_color, const float *prev_depth, const float *prev_len, const float *prev_normal, float *len, hipStream_t st) {
+    const dim3 grid((W + kTile - 1) / kTile, (H + kTile - 1) / kTile), blk(kTile, kTile);
+    hipLaunchKernelGGL(k_history_len, grid, blk, 0, st, W, H, o, ho, motion, normal, normal_stride, prev_color, prev_depth, prev_len, prev_normal, len);
 }
 
 }  // namespace mcpt

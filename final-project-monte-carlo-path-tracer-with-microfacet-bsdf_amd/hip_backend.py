@@ -24,6 +24,8 @@ EXPORTS = ["mcpt_scene_create", "mcpt_scene_destroy", "mcpt_render", "mcpt_rende
            "mcpt_temporal_accumulate_ex",
            "mcpt_sequence_create", "mcpt_sequence_frame", "mcpt_sequence_reset", "mcpt_sequence_destroy",
            "mcpt_sequence_create_ex", "mcpt_sequence_flags",
+           "mcpt_temporal_history_len", "mcpt_render_adaptive_guided", "mcpt_render_adaptive_denoised",
+           "mcpt_sequence_create_adaptive", "mcpt_sequence_counts",
            "mcpt_group_create", "mcpt_group_render", "mcpt_group_size", "mcpt_group_get_info", "mcpt_group_scene", "mcpt_group_destroy", "mcpt_group_last_error",
            "mcpt_last_error", "mcpt_version"]
 
@@ -131,6 +133,18 @@ class SequenceInfo(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
 
 
+class SequenceAdaptive(C.Structure):
+    _fields_ = [("rule", Adaptive), ("guided", C.c_int32), ("reserved", C.c_int32 * 7)]
+
+
+def sequence_adaptive(min_spp, threshold, rel_floor=1e-3, dilate=1, guided=False):
+    """mcpt_sequence_adaptive: the rule of render_adaptive for every frame of a sequence (each frame's `spp` is the cap); guided: the
+    threshold of a pixel is scaled by sqrt(the history length it is about to get)."""
+    return SequenceAdaptive(rule=Adaptive(min_spp=int(min_spp), dilate=int(dilate), threshold=float(threshold), rel_floor=float(rel_floor)),
+                            guided=int(guided))
+
+
+assert C.sizeof(Adaptive) == 32 and C.sizeof(AdaptiveInfo) == 264 and C.sizeof(SequenceAdaptive) == 64
 assert C.sizeof(TemporalOpts) == 32 and C.sizeof(DenoiseOpts) == 32 and C.sizeof(HistoryOpts) == 32  # the sizes include/mcpt.h states
 assert C.sizeof(SequenceOpts) == 96 and C.sizeof(SequenceOutputs) == 64 and C.sizeof(SequenceInfo) == 64
 
@@ -244,6 +258,19 @@ def lib(path=None):
         L.mcpt_sequence_create_ex.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(SequenceOpts), C.POINTER(HistoryOpts), C.POINTER(C.c_void_p)]
         L.mcpt_sequence_flags.restype = C.c_int
         L.mcpt_sequence_flags.argtypes = [C.c_void_p, C.c_void_p]
+        L.mcpt_temporal_history_len.restype = C.c_int
+        L.mcpt_temporal_history_len.argtypes = [C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 6 + [C.POINTER(TemporalOpts), C.POINTER(HistoryOpts), C.c_void_p]
+        L.mcpt_render_adaptive_guided.restype = C.c_int
+        L.mcpt_render_adaptive_guided.argtypes = ([C.c_void_p, C.c_void_p, C.POINTER(Params), C.POINTER(Adaptive)] + [C.c_void_p] * 5
+                                                  + [C.POINTER(AdaptiveInfo), C.POINTER(Stats)])
+        L.mcpt_render_adaptive_denoised.restype = C.c_int
+        L.mcpt_render_adaptive_denoised.argtypes = ([C.c_void_p, C.c_void_p, C.POINTER(Params), C.POINTER(Adaptive), C.c_void_p, C.POINTER(DenoiseOpts)]
+                                                    + [C.c_void_p] * 6 + [C.POINTER(AdaptiveInfo), C.POINTER(DenoiseInfo), C.POINTER(Stats)])
+        L.mcpt_sequence_create_adaptive.restype = C.c_int
+        L.mcpt_sequence_create_adaptive.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(SequenceOpts), C.POINTER(HistoryOpts),
+                                                    C.POINTER(SequenceAdaptive), C.POINTER(C.c_void_p)]
+        L.mcpt_sequence_counts.restype = C.c_int
+        L.mcpt_sequence_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(AdaptiveInfo)]
         L.mcpt_sequence_create.restype = C.c_int
         L.mcpt_sequence_create.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(SequenceOpts), C.POINTER(C.c_void_p)]
         L.mcpt_sequence_frame.restype = C.c_int
@@ -480,6 +507,74 @@ class HipScene:
                L=self.L)
         return fb, spp, err, info.as_dict(), st
 
+    def _guide(self, guide, H, W):
+        if guide is None:
+            return None
+        guide = np.ascontiguousarray(guide, dtype=np.float32)
+        if guide.size != H * W:
+            raise ValueError("the guide %s does not describe one %dx%d frame" % (guide.shape, W, H))
+        return guide
+
+    def render_adaptive_guided(self, min_spp, threshold, guide=None, rel_floor=1e-3, dilate=1, camera=None, variance=True, **kw):
+        """mcpt_render_adaptive_guided: render_adaptive with pixel m's threshold scaled by sqrt(guide[m]) where guide[m] >= 1 (guide[H,W]
+        float32, e.g. history_len(...); None: the plain rule) and the luminance variance of each pixel's mean at its own count.
+        Returns (fb[H,W,3], spp[H,W] int32, err[H,W], variance[H,W] or None, info dict, Stats)."""
+        cam = np.ascontiguousarray(camera if camera is not None else self.sd.camera)
+        W, H = int(cam["width"].reshape(-1)[0]), int(cam["height"].reshape(-1)[0])
+        fb = np.zeros((H, W, 3), dtype=np.float32)
+        spp = np.zeros((H, W), dtype=np.int32)
+        err = np.zeros((H, W), dtype=np.float32)
+        var = np.zeros((H, W), dtype=np.float32) if variance else None
+        guide = self._guide(guide, H, W)
+        p = self.params(**kw)
+        o = Adaptive(min_spp=int(min_spp), dilate=int(dilate), threshold=float(threshold), rel_floor=float(rel_floor))
+        info = AdaptiveInfo()
+        st = Stats()
+        _check(self.L.mcpt_render_adaptive_guided(self.h, _ptr(cam), C.byref(p), C.byref(o), None if guide is None else _ptr(guide), _ptr(fb), _ptr(spp),
+                                                  _ptr(err), None if var is None else _ptr(var), C.byref(info), C.byref(st)), L=self.L)
+        return fb, spp, err, var, info.as_dict(), st
+
+    def render_adaptive_denoised(self, min_spp, threshold, guide=None, rel_floor=1e-3, dilate=1, camera=None, aov_spp=0, iterations=0, sigma_l=0.0,
+                                 sigma_n=0.0, sigma_z=0.0, specular_depth=0, **kw):
+        """mcpt_render_adaptive_denoised: render_adaptive_guided, the AOVs of render_aovs(aov_spp, seed, specular_depth) and the filter of the
+        three with each pixel's own variance.  Returns dict(fb, denoised [H,W,3], spp[H,W] int32, err, variance [H,W], aov[H,W,8],
+        adaptive_info, info, stats)."""
+        cam = np.ascontiguousarray(camera if camera is not None else self.sd.camera)
+        W, H = int(cam["width"].reshape(-1)[0]), int(cam["height"].reshape(-1)[0])
+        fb, den = np.zeros((H, W, 3), dtype=np.float32), np.zeros((H, W, 3), dtype=np.float32)
+        spp = np.zeros((H, W), dtype=np.int32)
+        err, var = np.zeros((H, W), dtype=np.float32), np.zeros((H, W), dtype=np.float32)
+        aov = np.zeros((H, W, 8), dtype=np.float32)
+        guide = self._guide(guide, H, W)
+        p = self.params(**kw)
+        r = Adaptive(min_spp=int(min_spp), dilate=int(dilate), threshold=float(threshold), rel_floor=float(rel_floor))
+        o = denoise_opts(aov_spp, iterations, sigma_l, sigma_n, sigma_z, specular_depth)
+        ainfo, info, st = AdaptiveInfo(), DenoiseInfo(), Stats()
+        _check(self.L.mcpt_render_adaptive_denoised(self.h, _ptr(cam), C.byref(p), C.byref(r), None if guide is None else _ptr(guide), C.byref(o),
+                                                    _ptr(fb), _ptr(den), _ptr(spp), _ptr(err), _ptr(var), _ptr(aov), C.byref(ainfo), C.byref(info),
+                                                    C.byref(st)), L=self.L)
+        return dict(fb=fb, denoised=den, spp=spp, err=err, variance=var, aov=aov, adaptive_info=ainfo.as_dict(), info=info.as_dict(), stats=st)
+
+    def history_len(self, motion, prev_color, prev_depth, prev_len, normal=None, prev_normal=None, normal_test=False, normal_min=0.0, **opts):
+        """mcpt_temporal_history_len: the out_len temporal_accumulate_ex will give every pixel whose new colour is finite, from what is known
+        before the frame is rendered (motion[H,W,4], the previous history: prev_color[H,W,3], prev_depth, prev_len [H,W]; with normal_test
+        the first-hit normals of both frames).  opts: max_history, depth_tol.  Returns len[H,W] float32."""
+        motion = np.ascontiguousarray(motion, dtype=np.float32)
+        H, W = motion.shape[:2]
+        prev_color, prev_depth, prev_len = (np.ascontiguousarray(x, dtype=np.float32) for x in (prev_color, prev_depth, prev_len))
+        normal, prev_normal = (None if x is None else np.ascontiguousarray(x, dtype=np.float32) for x in (normal, prev_normal))
+        n = H * W
+        if (motion.size != n * 4 or prev_color.size != n * 3 or prev_depth.size != n or prev_len.size != n
+                or any(x is not None and x.size != n * 3 for x in (normal, prev_normal))):
+            raise ValueError("history_len: the arrays do not describe one %dx%d frame" % (W, H))
+        out = np.zeros((H, W), dtype=np.float32)
+        o = temporal_opts(**opts)
+        ho = history_opts(normal_test, False, normal_min, 0.0)
+        _check(self.L.mcpt_temporal_history_len(self.h, W, H, _ptr(motion), None if normal is None else _ptr(normal), _ptr(prev_color), _ptr(prev_depth),
+                                                _ptr(prev_len), None if prev_normal is None else _ptr(prev_normal), C.byref(o), C.byref(ho), _ptr(out)),
+               L=self.L)
+        return out
+
     def render_aovs(self, aov_spp=0, seed=1, camera=None, specular_depth=0):
         """mcpt_render_aovs: aov[H,W,8] float32 = {albedo rgb, normal xyz, depth, coverage} from feature samples 0 .. aov_spp-1 (0: 4) of `seed`;
         specular_depth > 0: mcpt_render_aovs_ex, the features taken behind up to that many mirror / glass bounces."""
@@ -608,14 +703,16 @@ class HipScene:
         return out, out_var, out_len, flags
 
     def sequence(self, width=None, height=None, filter=True, max_history=0, depth_tol=0.0, normal_test=False, color_clamp=False, normal_min=0.0,
-                 clamp_k=0.0, **denoise_opts_kw):
+                 clamp_k=0.0, adaptive=None, **denoise_opts_kw):
         """mcpt_sequence_create: a HipSequence of width x height frames (default: the scene camera's) on this scene.  filter: also denoise
         the accumulated frame; max_history, depth_tol: mcpt_temporal_opts; the rest: mcpt_denoise_opts (aov_spp, iterations, sigma_l,
         sigma_n, sigma_z, specular_depth).  normal_test / color_clamp (normal_min, clamp_k): history rejection, mcpt_history_opts; with
         either on the sequence is made by mcpt_sequence_create_ex and HipSequence.flags() tells what the last frame rejected.
+        adaptive: dict(min_spp=, threshold=, rel_floor=, dilate=, guided=) (the keywords of sequence_adaptive): the frames are adaptive
+        (mcpt_sequence_create_adaptive), each frame's `spp` is the cap, and HipSequence.counts() gives the last frame's counts.
         The sequence owns the scene's snapshot while it lives; close it before the scene."""
         return HipSequence(self, width, height, filter, max_history, depth_tol, normal_test=normal_test, color_clamp=color_clamp,
-                           normal_min=normal_min, clamp_k=clamp_k, **denoise_opts_kw)
+                           normal_min=normal_min, clamp_k=clamp_k, adaptive=adaptive, **denoise_opts_kw)
 
     def render_device(self, fb_ptr, stream_ptr=0, camera=None, **kw):
         """Same, into a device framebuffer (W*H*3 floats at fb_ptr) on the given hipStream_t handle."""
@@ -717,8 +814,10 @@ class HipSequence:
     _SHAPES = {"fb": (3,), "accumulated": (3,), "denoised": (3,), "variance": (), "len": (), "aov": (8,), "motion": (4,), "rgba": (4,)}
 
     def __init__(self, scene, width=None, height=None, filter=True, max_history=0, depth_tol=0.0, normal_test=False, color_clamp=False,
-                 normal_min=0.0, clamp_k=0.0, history=None, **denoise_opts_kw):
-        """history: a HistoryOpts passed to mcpt_sequence_create_ex as it is (tests: a zeroed one must give mcpt_sequence_create's sequence)."""
+                 normal_min=0.0, clamp_k=0.0, history=None, adaptive=None, create_adaptive=False, **denoise_opts_kw):
+        """history: a HistoryOpts passed to mcpt_sequence_create_ex as it is (tests: a zeroed one must give mcpt_sequence_create's sequence).
+        adaptive: a dict of sequence_adaptive's keywords or a SequenceAdaptive; create_adaptive: go through mcpt_sequence_create_adaptive
+        even without one (tests: a null rule must give mcpt_sequence_create_ex's sequence)."""
         self.scene = scene  # (keeps the scene alive as long as the sequence)
         self.L = scene.L
         self.h = None
@@ -729,7 +828,12 @@ class HipSequence:
         h = C.c_void_p()
         if history is None and (normal_test or color_clamp):
             history = history_opts(normal_test, color_clamp, normal_min, clamp_k)
-        if history is None:
+        if isinstance(adaptive, dict):
+            adaptive = sequence_adaptive(**adaptive)
+        if adaptive is not None or create_adaptive:
+            _check(self.L.mcpt_sequence_create_adaptive(scene.h, self.W, self.H, C.byref(o), None if history is None else C.byref(history),
+                                                        None if adaptive is None else C.byref(adaptive), C.byref(h)), L=self.L)
+        elif history is None:
             _check(self.L.mcpt_sequence_create(scene.h, self.W, self.H, C.byref(o), C.byref(h)), L=self.L)
         else:
             _check(self.L.mcpt_sequence_create_ex(scene.h, self.W, self.H, C.byref(o), C.byref(history), C.byref(h)), L=self.L)
@@ -758,6 +862,15 @@ class HipSequence:
         out = np.zeros((self.H, self.W), dtype=np.uint8)
         _check(self.L.mcpt_sequence_flags(self.h, _ptr(out)), L=self.L)
         return out
+
+    def counts(self):
+        """mcpt_sequence_counts: dict(spp[H,W] int32, err[H,W], guide[H,W] float32 (0 without guided), info dict) of the last frame of an
+        adaptive sequence; any other sequence keeps none and raises."""
+        spp = np.zeros((self.H, self.W), dtype=np.int32)
+        err, guide = np.zeros((self.H, self.W), dtype=np.float32), np.zeros((self.H, self.W), dtype=np.float32)
+        info = AdaptiveInfo()
+        _check(self.L.mcpt_sequence_counts(self.h, _ptr(spp), _ptr(err), _ptr(guide), C.byref(info)), L=self.L)
+        return dict(spp=spp, err=err, guide=guide, info=info.as_dict())
 
     def reset(self):
         """mcpt_sequence_reset, a camera cut: the next frame takes no history."""

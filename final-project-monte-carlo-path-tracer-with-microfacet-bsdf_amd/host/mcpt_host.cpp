@@ -424,7 +424,29 @@ void Renderer::Render(const Scene &scene) {
         o.threshold = adaptive_threshold;
         o.rel_floor = 1e-3f;
         mcpt_adaptive_info ai{};
-        const int rc = mcpt_render_adaptive(scene.handle(), &c, &p, &o, framebuffer.data(), nullptr, nullptr, &ai, &st);
+        int rc;
+        if (adaptive_denoise_path.empty()) {
+            rc = mcpt_render_adaptive(scene.handle(), &c, &p, &o, framebuffer.data(), nullptr, nullptr, &ai, &st);
+        } else {
+            mcpt_denoise_opts d{};
+            d.aov_spp = denoise_aov_spp;
+            d.specular_depth = denoise_specular_depth;
+            mcpt_denoise_info di{};
+            std::vector<float> denoised(framebuffer.size());
+            rc = mcpt_render_adaptive_denoised(scene.handle(), &c, &p, &o, nullptr, &d, framebuffer.data(), denoised.data(), nullptr, nullptr, nullptr,
+                                               nullptr, &ai, &di, &st);
+            if (rc == MCPT_OK || rc == MCPT_ERR_OVERFLOW) {
+                std::cout << "[mcpt] denoise: rounds " << di.ms_render << " ms, AOVs " << di.ms_aov << " ms, filter " << di.ms_denoise << " ms" << std::endl;
+                std::cout << "Writing denoised image to " << adaptive_denoise_path << std::endl;
+                std::vector<unsigned char> raw((size_t)4 * camera.width * camera.height);
+                if (mcpt_tonemap(scene.handle(), denoised.data(), (int64_t)camera.width * camera.height, raw.data()) != MCPT_OK) {
+                    std::cerr << "mcpt: " << mcpt_last_error() << std::endl;
+                    return;
+                }
+                const std::string err = png_min::encode_rgba(adaptive_denoise_path, raw, camera.width, camera.height);
+                if (!err.empty()) std::cerr << "Error when writing image : " << err << std::endl;
+            }
+        }
         if (rc != MCPT_OK) std::cerr << "mcpt: " << mcpt_last_error() << std::endl;
         if (rc != MCPT_OK && rc != MCPT_ERR_OVERFLOW) return;
         total = st;

@@ -287,6 +287,9 @@ class Renderer {
     std::string denoise_path;
     int denoise_aov_spp = 0;
     int denoise_specular_depth = 0;
+    // With adaptive: the adaptive frame through mcpt_render_adaptive_denoised, the denoised frame to this path (denoise_aov_spp and
+    // denoise_specular_depth apply; denoise_aov_spp at most the first level).
+    std::string adaptive_denoise_path;
 
   private:
     int spp = 2048;

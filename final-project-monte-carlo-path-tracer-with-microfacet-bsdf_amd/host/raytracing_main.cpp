@@ -14,6 +14,9 @@
 //   --denoise FILE [--denoise-aov-spp N]   also write a denoised frame (mcpt_render_denoised: N feature samples per pixel, default
 //                 min(4, spp)) to FILE; --output stays the plain frame, byte for byte
 //   --denoise-specular-depth N   the feature samples follow up to N mirror / glass bounces (0..8, default 0: first-hit features)
+//   --adaptive-denoise FILE   with --adaptive: also write the denoised adaptive frame (mcpt_render_adaptive_denoised: the filter gets each
+//                 pixel's variance at its own count) to FILE; --denoise-aov-spp (at most the first level N) and --denoise-specular-depth
+//                 apply; --output stays the adaptive frame.  Not with --gpus / --devices or --checkpoint
 //   --dump FILE   write the flattened scene (what mcpt_scene_create receives) and exit without touching the GPU
 #include <chrono>
 #include <cstring>
@@ -72,6 +75,7 @@ int main(int argc, char **argv) {
         }
         else if (a == "--adaptive-min") r.adaptive_min = std::atoi(argv[i + 1]);
         else if (a == "--denoise") r.denoise_path = argv[i + 1];
+        else if (a == "--adaptive-denoise") r.adaptive_denoise_path = argv[i + 1];
         else if (a == "--denoise-aov-spp") r.denoise_aov_spp = std::atoi(argv[i + 1]);
         else if (a == "--denoise-specular-depth") r.denoise_specular_depth = std::atoi(argv[i + 1]);
         else if (a == "--gpus") {
@@ -90,6 +94,12 @@ int main(int argc, char **argv) {
     }
     if (!r.denoise_path.empty() && (r.adaptive || !r.checkpoint_path.empty() || n_devices > 1)) {
         std::cerr << "--denoise cannot be combined with " << (r.adaptive ? "--adaptive" : (!r.checkpoint_path.empty() ? "--checkpoint" : "more than one device"))
+                  << std::endl;
+        return 1;
+    }
+    if (!r.adaptive_denoise_path.empty() && (!r.adaptive || !r.denoise_path.empty() || n_devices > 1)) {
+        std::cerr << "--adaptive-denoise " << (!r.adaptive ? "needs --adaptive" : (!r.denoise_path.empty() ? "cannot be combined with --denoise"
+                                                                                                            : "cannot be combined with more than one device"))
                   << std::endl;
         return 1;
     }

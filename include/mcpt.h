@@ -239,6 +239,22 @@ typedef struct {
 int mcpt_render_adaptive(mcpt_scene *scene, const mcpt_camera *camera, const mcpt_params *params, const mcpt_adaptive *opts,
                          float *fb_host, int32_t *spp_host, float *err_host, mcpt_adaptive_info *info, mcpt_stats *stats);
 
+/* mcpt_render_adaptive with a per-pixel guide and the variance of the frame.  The rule above, with one change: pixel m's mark is
+ *     e > threshold * sqrt((double) g),   g = guide_host[m] if guide_host[m] >= 1, otherwise g = 1
+ * (the product and the square root in double), so a NaN, zero or negative guide leaves the plain rule, and so does a null guide_host.
+ * The guide is meant to be the history length the pixel is about to get in a temporal blend (mcpt_temporal_history_len): a running mean
+ * of N frames of equal variance has relative error e / sqrt(N), so the threshold becomes a target for the ACCUMULATED pixel.  err still
+ * reports the unscaled e.  Dilation, sky-culled pixels, halving and the cap are unchanged, so every pixel is still bit-identical to the
+ * same pixel of mcpt_render at its final count, and no pixel gets more samples than without the guide.
+ *   guide_host     W*H floats (nullable: mcpt_render_adaptive's fb, spp and err bit for bit; an all-ones guide gives them too)
+ *   variance_host  W*H floats (nullable): the luminance variance of the mean, step 2 of mcpt_render_denoised with n = the pixel's own
+ *                  final count:  for c in 0..2:  m = s1/n;  q = s2/n - m*m;  var_c = max(q, 0) * n / (n - 1) / n;  v = sum_c w_c^2 var_c,
+ *                  s1 / s2 the pixel's sums over all its samples; 0 for an unowned pixel (count 0)
+ * MCPT_ERR_ARG and MCPT_ERR_OVERFLOW as mcpt_render_adaptive. */
+int mcpt_render_adaptive_guided(mcpt_scene *scene, const mcpt_camera *camera, const mcpt_params *params, const mcpt_adaptive *rule,
+                                const float *guide_host, float *fb_host, int32_t *spp_host, float *err_host, float *variance_host,
+                                mcpt_adaptive_info *info, mcpt_stats *stats);
+
 /* ---- Feature buffers (AOVs) and a variance-guided a-trous denoiser (Dammertz et al. 2010; variance guidance of SVGF, Schied et al. 2017).
  *
  * AOV record: 8 floats per pixel, row-major m = j*W + i:  {albedo r,g,b, normal x,y,z, depth, coverage}.
@@ -329,6 +345,20 @@ int mcpt_denoise(mcpt_scene *scene, int32_t width, int32_t height, const float *
  * (a partial or partitioned frame is not denoised).  MCPT_ERR_OVERFLOW as mcpt_render (the outputs are still written). */
 int mcpt_render_denoised(mcpt_scene *scene, const mcpt_camera *camera, const mcpt_params *params, const mcpt_denoise_opts *opts, float *fb_host,
                          float *denoised_host, float *variance_host, float *aov_host, mcpt_denoise_info *info, mcpt_stats *stats);
+
+/* An adaptive frame, then the filter, on one stream:
+ *   mcpt_render_adaptive_guided(rule, guide_host) with its variance;  the AOVs of mcpt_render_aovs_ex(params.seed, opts.aov_spp,
+ *   opts.specular_depth);  mcpt_denoise of the three.
+ * fb, spp, err, variance and aov are what the separate calls return and denoised equals mcpt_denoise(fb, variance, aov, opts), bit for bit.
+ * The filter gets each pixel's own variance: a pixel that stopped early carries the larger one and is smoothed more.
+ *   guide_host nullable;  fb_host, denoised_host W*H*3;  spp_host, err_host, variance_host W*H, aov_host W*H*8 (each nullable);
+ *   adaptive_info, info, stats nullable (info.ms_render is the time of the rounds).
+ * MCPT_ERR_ARG: every case of mcpt_render_adaptive and of mcpt_render_denoised (params.spp >= 2, nranks == 1), and opts.aov_spp >
+ * rule.min_spp -- every pixel has at least min_spp samples and feature sample k is render sample k; aov_spp 0 => min(4, min_spp). */
+int mcpt_render_adaptive_denoised(mcpt_scene *scene, const mcpt_camera *camera, const mcpt_params *params, const mcpt_adaptive *rule,
+                                  const float *guide_host, const mcpt_denoise_opts *opts, float *fb_host, float *denoised_host,
+                                  int32_t *spp_host, float *err_host, float *variance_host, float *aov_host,
+                                  mcpt_adaptive_info *adaptive_info, mcpt_denoise_info *info, mcpt_stats *stats);
 
 /* ---- Temporal reuse for moving scenes: per-pixel motion and a validated blend of the reprojected history (csrc/mcpt_temporal.h has
  * every expression in its order; the device and a CPU build of it agree bit for bit).  The frame loop is
@@ -457,6 +487,22 @@ int mcpt_temporal_accumulate_ex(mcpt_scene *scene, int32_t width, int32_t height
                                 const float *prev_normal_host, const mcpt_temporal_opts *opts, const mcpt_history_opts *history_opts,
                                 float *out_color_host, float *out_variance_host, float *out_len_host, uint8_t *out_flags_host);
 
+/* The history length every pixel is ABOUT TO GET, before its frame is rendered: steps 1-4 of the blend and the N of step 5, with the new
+ * colour taken to be finite.  Per pixel, in float, in this order:
+ *   motion.valid <= 0:  1;   otherwise the taps of step 2 with every skip of step 3, the normal test of mcpt_temporal_accumulate_ex
+ *   included when history_opts.normal_test is 1;   no tap left:  1;   otherwise  N = min(n + 1, max_history), n the smallest prev_len of
+ *   the used taps.
+ * The colour clamp does not enter: a clamped history keeps its length.  Neither the new colour nor any variance is read.
+ * So len_host[m] EQUALS THE out_len[m] OF mcpt_temporal_accumulate_ex ON THE SAME INPUTS FOR EVERY PIXEL WHOSE NEW COLOUR IS FINITE
+ * (a pixel with a non-finite colour restarts there, len 1).  It is the guide of mcpt_render_adaptive_guided in a sequence.
+ *   motion_host W*H*4;  prev_color_host W*H*3 (only its finiteness is read), prev_depth_host, prev_len_host W*H;  normal_host,
+ *   prev_normal_host W*H*3, nullable unless normal_test is 1;  history_opts nullable (both switches off);  len_host W*H.
+ * The scene only picks the device and stream.  MCPT_ERR_ARG, before any device call: as mcpt_temporal_accumulate_ex. */
+int mcpt_temporal_history_len(mcpt_scene *scene, int32_t width, int32_t height, const float *motion_host, const float *normal_host,
+                              const float *prev_color_host, const float *prev_depth_host, const float *prev_len_host,
+                              const float *prev_normal_host, const mcpt_temporal_opts *opts, const mcpt_history_opts *history_opts,
+                              float *len_host);
+
 /* ---- Frame sequences: the history, the variance of the accumulated frame and every working buffer stay on the device; one call runs a
  * whole frame on one stream and only what the caller asks for crosses the bus.  The caller's loop is
  *       mcpt_scene_update;  mcpt_sequence_frame          (params.seed varied from frame to frame).
@@ -539,6 +585,36 @@ void mcpt_sequence_destroy(mcpt_sequence *sequence);
 int mcpt_sequence_create_ex(mcpt_scene *scene, int32_t width, int32_t height, const mcpt_sequence_opts *opts, const mcpt_history_opts *history_opts,
                             mcpt_sequence **out);
 int mcpt_sequence_flags(mcpt_sequence *sequence, uint8_t *flags_host);
+
+/* A sequence whose frames are adaptive, the stopping threshold relaxed by the history each pixel is about to have.  A null `adaptive`:
+ * mcpt_sequence_create_ex, exactly (the same allocations, the same frame).  Otherwise mcpt_sequence_frame takes params.spp as the CAP of
+ * the rule: step 1 also checks params.spp == rule.min_spp * 2^R (0 <= R <= 15) and denoise.aov_spp <= rule.min_spp (aov_spp 0 =>
+ * min(4, min_spp)), and the frame runs on one stream in this order:
+ *   a. the AOVs (step 3), and the first-hit pass when specular_depth > 0;   b. the motion (step 4) -- neither depends on the frame, so
+ *      moving them in front changes no output;
+ *   c. guided 1: the guide = mcpt_temporal_history_len(motion, the first-hit normals, the previous history set: colour, depth, len,
+ *      normals; opts.temporal, history_opts).  On the first frame and after a reset prev_len is 0, so the guide is 1 everywhere;
+ *   d. the rounds of mcpt_render_adaptive_guided(rule, the guide; guided 0: no guide) and its variance, each pixel at its own count;
+ *   e. steps 5-8 as they are: the history and the filter get each pixel's own variance.  A pixel's frames still weigh 1/N each in the
+ *      blend, whatever their counts.
+ * outputs.fb is the adaptive frame; every output equals what the separate calls give, bit for bit.  stats.samples is the sum of the
+ * count map.  In mcpt_sequence_info the guide is counted with ms_motion and ms_render is the time of the rounds.
+ * Allocated at create, for all W*H pixels active, per pixel: two sets of counts (spp 4, err 4, guide 4 bytes, used in turn with the
+ * history sets), the stamps 1, both lists 4 + 4 with their candidate entries 16 + 16, the flags 1: 66 bytes per pixel, plus the
+ * compaction's scratch (a few KiB).  A frame allocates nothing.
+ * mcpt_sequence_counts copies the counts, the estimates and the guide (0 everywhere without guided) of the last
+ * successful frame, each pointer nullable (all 0 before the first frame); a failed frame leaves history, counts and guide as they were.
+ * MCPT_ERR_ARG, before any device call: as mcpt_sequence_create_ex; min_spp < 2, a negative or non-finite threshold, rel_floor <= 0,
+ * dilate or guided not 0 or 1, a non-zero reserved word (of the rule too), denoise.aov_spp > min_spp; mcpt_sequence_counts for a null
+ * sequence or one created without a rule. */
+typedef struct {
+    mcpt_adaptive rule;  /* as mcpt_render_adaptive; the cap is each frame's params.spp */
+    int32_t guided;      /* 0: the plain rule; 1: the threshold scaled by sqrt(history length) */
+    int32_t reserved[7]; /* must be 0 */
+} mcpt_sequence_adaptive; /* 64 bytes */
+int mcpt_sequence_create_adaptive(mcpt_scene *scene, int32_t width, int32_t height, const mcpt_sequence_opts *opts,
+                                  const mcpt_history_opts *history_opts, const mcpt_sequence_adaptive *adaptive, mcpt_sequence **out);
+int mcpt_sequence_counts(mcpt_sequence *sequence, int32_t *spp_host, float *err_host, float *guide_host, mcpt_adaptive_info *info);
 
 /* Replaces Scene::intersect (Scene.hpp:128, Scene.cpp:19-21) for a list of rays (host pointers; n*3 floats each).
  * out_t: hit distance as the reference's double Intersection::distance (DBL_MAX on a miss);

@@ -13,7 +13,13 @@ times.  render() returns no variance, so the loop's denoise is fed the variance 
 accumulated image without the cost of getting a variance, which flatters the loop.
   --normal-test / --color-clamp [--clamp-k K]   the sequence rejects stale history (mcpt_sequence_create_ex): also prints, per frame, the
 share of pixels whose flags byte has bit 0 (the normal test skipped a tap) and bit 1 (the clamp moved the history).  --no-loop skips the
-host-array loop (the sequence alone, e.g. to compare ms_accumulate with and without the switches)."""
+host-array loop (the sequence alone, e.g. to compare ms_accumulate with and without the switches).
+python tools/temporal.py --sequence --adaptive T [--adaptive-min N] [--guided] [--spp CAP] [--move] [--ref-spp 2048]   an adaptive sequence
+(mcpt_sequence_create_adaptive: levels N, 2N, ..., CAP; --guided: the threshold relaxed by the history length each pixel is about to get).
+Prints, per frame, the total samples, the histogram of the counts, the stage times and the MSE of the accumulated frame against a
+--ref-spp render of that frame's geometry (seed 1000).  --move: the short box of the Cornell scene moves by translate(-32 k, 0, 0) before
+frame k (a reference per frame; a static scene renders one).  --quality instead of --adaptive: the same figures for a uniform sequence at
+--spp samples per pixel."""
 import argparse
 import csv
 import re
@@ -125,6 +131,38 @@ def sequence_timing(pkg, sd, W, H, frames, reject=None, loop=True):
     hs.close()
 
 
+def sequence_quality(pkg, sd, W, H, frames, spp, adaptive, reject, move, ref_spp):
+    """Per frame of a uniform (adaptive None) or adaptive sequence: samples, count histogram, stage times, MSE of `accumulated`."""
+    hs = pkg.HipScene(sd)
+    seq = hs.sequence(filter=False, aov_spp=min(4, adaptive["min_spp"] if adaptive else spp), adaptive=adaptive, **(reject or {}))
+    what = "uniform %d spp" % spp if not adaptive else "adaptive %s, levels %d..%d, threshold %g" % (
+        "guided" if adaptive["guided"] else "unguided", adaptive["min_spp"], spp, adaptive["threshold"])
+    print("%dx%d %s sequence, %s; reference %d spp" % (W, H, "moving" if move else "static", what, ref_spp))
+    truth, total = None, 0
+    for k in range(frames):
+        if move:
+            hs.update([(1, np.array([[1, 0, 0, -32.0 * k], [0, 1, 0, 0], [0, 0, 1, 0]], np.float32))])
+        if truth is None or move:
+            truth = hs.render(spp=ref_spp, seed=1000)[0].astype(np.float64)
+        r = seq.frame(want=("accumulated",), spp=spp, seed=k + 1)
+        mse = float(np.nanmean((r["accumulated"].astype(np.float64) - truth) ** 2))
+        n = int(r["stats"].samples)
+        total += n
+        hist = ""
+        if adaptive:
+            cn = seq.counts()
+            lv, cnt = np.unique(cn["spp"], return_counts=True)
+            hist = "  counts " + " ".join("%d:%d" % (a, b) for a, b in zip(lv, cnt))
+            if adaptive["guided"]:
+                hist += "  mean guide %.2f" % float(cn["guide"].mean())
+        i = r["info"]
+        print("frame %d: %d samples (%.2f per pixel)  MSE %.6g%s  ms: render %.3f aov %.3f motion %.3f accumulate %.3f total %.2f"
+              % (k, n, n / (W * H), mse, hist, i["ms_render"], i["ms_aov"], i["ms_motion"], i["ms_accumulate"], i["ms_total"]), flush=True)
+    print("all frames: %d samples (%.2f per pixel and frame)" % (total, total / (W * H * frames)))
+    seq.close()
+    hs.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--trace", help="a rocprofv3 kernel-trace CSV of a run of this script with the same --repeat: print the kernel time per pass")
@@ -138,12 +176,25 @@ def main():
     ap.add_argument("--color-clamp", action="store_true", help="--sequence: clamp the history to the new frame's 3x3 neighbourhood")
     ap.add_argument("--clamp-k", type=float, default=0.0, help="--color-clamp: the box's half-width in standard deviations (0: the default)")
     ap.add_argument("--no-loop", action="store_true", help="--sequence: skip the host-array loop")
+    ap.add_argument("--adaptive", type=float, default=None, help="--sequence: an adaptive sequence with this threshold; prints samples, counts and MSE")
+    ap.add_argument("--adaptive-min", type=int, default=4, help="--adaptive: the first level")
+    ap.add_argument("--guided", action="store_true", help="--adaptive: relax each pixel's threshold by sqrt(the history length it is about to get)")
+    ap.add_argument("--quality", action="store_true", help="--sequence: the figures of --adaptive for a uniform sequence at --spp")
+    ap.add_argument("--spp", type=int, default=64, help="--adaptive: the cap; --quality: the samples per pixel")
+    ap.add_argument("--move", action="store_true", help="--adaptive / --quality with --scene cornell: move the short box before every frame")
+    ap.add_argument("--ref-spp", type=int, default=2048, help="--adaptive / --quality: samples per pixel of the reference")
     a = ap.parse_args()
     if a.trace:
         return summarize_trace(a.trace, a.repeat)
     pkg = mcpt_loader.load()
     W, H = a.width, a.height
     sd = pkg.scenes.chess_scene(width=W, height=H, spp=4) if a.scene == "chess" else pkg.scenes.cornell_demo(W, H, 4)
+    if a.sequence and (a.adaptive is not None or a.quality):
+        reject = dict(normal_test=a.normal_test, color_clamp=a.color_clamp, clamp_k=a.clamp_k) if a.normal_test or a.color_clamp else None
+        rule = None if a.adaptive is None else dict(min_spp=a.adaptive_min, threshold=a.adaptive, dilate=1, guided=int(a.guided))
+        if a.move and a.scene != "cornell":
+            sys.exit("--move needs --scene cornell")
+        return sequence_quality(pkg, sd, W, H, a.frames, a.spp, rule, reject, a.move, a.ref_spp)
     if a.sequence:
         if a.frames < 6:
             sys.exit("--frames must be at least 6")
