@@ -124,6 +124,11 @@ int check_adaptive(const char *name, const mcpt_adaptive &o, const mcpt_params &
 // of the frame.  Returns with the stream drained.
 int adaptive_rounds(FrameCall &f, const mcpt_adaptive &o, AdaptiveBufs &b, AdaptiveLists *own, hipStream_t st, AdaptiveResult &res);
 
+// A uniform frame of f.p.spp samples with its moments, and the variance of its mean, on buffers the caller owns (fb 3 floats per pixel, mom 6
+// doubles, var 1), queued on `st` (steps 1-2 of mcpt_render_denoised): clears the moments; f.pixels; the culled pixels' moments;
+// render_list; k_dn_variance.  res gets the totals, the samples and how many were traced (res.info stays zero).
+int render_moments(FrameCall &f, float *fb, double *mom, float *var, hipStream_t st, AdaptiveResult &res);
+
 // Working buffers of the filter: two record buffers and the depth gradient, 72 bytes per pixel.
 struct DenoiseBufs {
     DevBuf<dn::Rec> rec[2];

@@ -1,5 +1,5 @@
 // The frame-level entry points of the C ABI (include/mcpt.h): mcpt_render / mcpt_render_device, mcpt_render_adaptive[_guided | _denoised], mcpt_render_aovs[_ex],
-// mcpt_denoise, mcpt_render_denoised, mcpt_render_motion and mcpt_temporal_blend.  What they share -- the checks of (camera, params), the start of a call, its statistics -- is
+// mcpt_denoise, mcpt_render_denoised and mcpt_render_motion.  What they share -- the checks of (camera, params), the start of a call, its statistics -- is
 // here once; each entry point is the part that differs.  csrc/mcpt_frame.h declares what csrc/mcpt_sequence.hip uses of it.
 #include <cmath>
 #include <cstdio>
@@ -357,6 +357,24 @@ int mcpt::adaptive_rounds(FrameCall &f, const mcpt_adaptive &o, AdaptiveBufs &b,
     return MCPT_OK;
 }
 
+int mcpt::render_moments(FrameCall &f, float *fb, double *mom, float *var, hipStream_t st, AdaptiveResult &res) {
+    const mcpt_params &p = f.p;
+    const size_t n_px = (size_t)f.cc.width * f.cc.height;
+    int rc;
+    HIP_TRY(hipMemsetAsync(mom, 0, n_px * 6 * sizeof(double), st));
+    if ((rc = f.pixels(p.spp, (float)p.spp, fb, st)) != MCPT_OK) return rc;
+    const PixelSet &ps = f.ps;
+    if (ps.n_owned > ps.n_pix) launch_sky_moments(ps.sky, ps.n_owned - ps.n_pix, f.sc->view.background, p.spp, mom, st);
+    if (ps.n_pix > 0) {
+        rc = render_list(f.sc, f.cc, p, ps.list, ps.cand, ps.n_pix, 0, p.spp, (float)p.spp, fb, mom, st, f.t0, res.totals);
+        if (rc != MCPT_OK) return rc;
+    }
+    launch_dn_variance((uint32_t)n_px, mom, p.spp, var, st);
+    res.samples = (uint64_t)ps.n_owned * p.spp;
+    res.traced_primary = (uint64_t)ps.n_pix * p.spp;
+    return MCPT_OK;
+}
+
 namespace {
 
 // The per-pixel buffers of an adaptive frame that owns them (mcpt_render_adaptive[_guided | _denoised]).
@@ -383,6 +401,47 @@ struct AdaptiveFrame {
         b.stamp = stamp.p;
         b.guide = guide;
         return b;
+    }
+};
+
+// What mcpt_render_denoised and mcpt_render_adaptive_denoised share: the buffers besides the frame's own, allocated before the render,
+// and everything after it.
+struct DenoisedTail {
+    DevBuf<float> aov, out;
+    DenoiseBufs db;
+    Event render_begin, render_end, aov_end, filter_end;  // around the three stages: render (or rounds), AOV pass, filter
+    int alloc(size_t n_px) {
+        HIP_TRY(aov.alloc(n_px * 8));
+        HIP_TRY(out.alloc(n_px * 3));
+        HIP_TRY(db.alloc(n_px));
+        for (Event *e : {&render_begin, &render_end, &aov_end, &filter_end}) HIP_TRY(e->create(true));
+        return MCPT_OK;
+    }
+    // The render stage ends here, with the frame in fb and its variance in var: the AOV pass, the filter, the downloads, the stage times.
+    int finish(FrameCall &f, const mcpt_denoise_opts &opts, const dn::Opts &o, int32_t aov_spp, const DevBuf<float> &fb, const DevBuf<float> &var,
+               hipStream_t st, float *fb_host, float *denoised_host, float *variance_host, float *aov_host, mcpt_denoise_info *info) {
+        const int W = f.cc.width, H = f.cc.height;
+        const size_t n_px = (size_t)W * H;
+        HIP_TRY(hipEventRecord(render_end, st));
+        const int rc = aov_pass(f.sc, f.cc, f.p.seed, aov_spp, opts.specular_depth, aov.p, st);
+        if (rc != MCPT_OK) return drained(rc);
+        HIP_TRY(hipEventRecord(aov_end, st));
+        launch_denoise(W, H, o, fb.p, var.p, aov.p, db.rec[0].p, db.rec[1].p, db.grad.p, out.p, st);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(filter_end, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        HIP_TRY(download(fb_host, fb, n_px * 3));
+        HIP_TRY(download(denoised_host, out, n_px * 3));
+        if (variance_host) HIP_TRY(download(variance_host, var, n_px));
+        if (aov_host) HIP_TRY(download(aov_host, aov, n_px * 8));
+        if (info) {
+            float render = 0.f, aovs = 0.f, filter = 0.f;
+            HIP_TRY(hipEventElapsedTime(&render, render_begin, render_end));
+            HIP_TRY(hipEventElapsedTime(&aovs, render_end, aov_end));
+            HIP_TRY(hipEventElapsedTime(&filter, aov_end, filter_end));
+            *info = {render, aovs, filter, ms_since(f.t0)};
+        }
+        return MCPT_OK;
     }
 };
 
@@ -472,47 +531,23 @@ int mcpt_render_adaptive_denoised(mcpt_scene *sc, const mcpt_camera *cam, const 
     FrameCall f{sc, p};
     if ((rc = f.begin(*cam)) != MCPT_OK) return rc;
     const hipStream_t st = nullptr;
-    const int W = cam->width, H = cam->height;
-    const size_t n_px = (size_t)W * H;
+    const size_t n_px = (size_t)cam->width * cam->height;
     AdaptiveFrame af;
-    DevBuf<float> aov, out, guide;
+    DevBuf<float> guide;
+    DenoisedTail tail;
     HIP_TRY(af.alloc(n_px, true));
-    HIP_TRY(aov.alloc(n_px * 8));
-    HIP_TRY(out.alloc(n_px * 3));
     if (guide_host) HIP_TRY(upload(guide, guide_host, n_px));
-    DenoiseBufs db;
-    HIP_TRY(db.alloc(n_px));
-    Event ev[4];  // around the three stages: rounds, AOV pass, filter
-    for (int k = 0; k < 4; ++k) HIP_TRY(ev[k].create(true));
-    HIP_TRY(hipEventRecord(ev[0], st));
+    if ((rc = tail.alloc(n_px)) != MCPT_OK) return rc;
+    HIP_TRY(hipEventRecord(tail.render_begin, st));
     AdaptiveBufs b = af.bufs(guide_host ? guide.p : nullptr);
     AdaptiveLists lists;
     AdaptiveResult res;
     if ((rc = adaptive_rounds(f, *rule, b, &lists, st, res)) != MCPT_OK) return rc;
     launch_dn_variance_map((uint32_t)n_px, af.mom.p, af.sppm.p, af.var.p, st);
-    HIP_TRY(hipEventRecord(ev[1], st));
-    rc = aov_pass(sc, f.cc, p.seed, aov_spp, opts->specular_depth, aov.p, st);
-    if (rc != MCPT_OK) return drained(rc);
-    HIP_TRY(hipEventRecord(ev[2], st));
-    launch_denoise(W, H, o, af.fb.p, af.var.p, aov.p, db.rec[0].p, db.rec[1].p, db.grad.p, out.p, st);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(ev[3], st));
-    HIP_TRY(hipStreamSynchronize(st));
-    HIP_TRY(download(fb_host, af.fb, n_px * 3));
-    HIP_TRY(download(denoised_host, out, n_px * 3));
+    if ((rc = tail.finish(f, *opts, o, aov_spp, af.fb, af.var, st, fb_host, denoised_host, variance_host, aov_host, info)) != MCPT_OK) return rc;
     if (spp_host) HIP_TRY(download(spp_host, af.sppm, n_px));
     if (err_host) HIP_TRY(download(err_host, af.err, n_px));
-    if (variance_host) HIP_TRY(download(variance_host, af.var, n_px));
-    if (aov_host) HIP_TRY(download(aov_host, aov, n_px * 8));
     if (ainfo) *ainfo = res.info;
-    if (info) {
-        float ms[3] = {0.f, 0.f, 0.f};
-        for (int k = 0; k < 3; ++k) HIP_TRY(hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]));
-        info->ms_render = ms[0];
-        info->ms_aov = ms[1];
-        info->ms_denoise = ms[2];
-        info->ms_total = ms_since(f.t0);
-    }
     return f.end(stats, res.samples, res.traced_primary, res.totals);
 }
 
@@ -562,51 +597,19 @@ int mcpt_render_denoised(mcpt_scene *sc, const mcpt_camera *cam, const mcpt_para
     FrameCall f{sc, p};
     if ((rc = f.begin(*cam)) != MCPT_OK) return rc;
     const hipStream_t st = nullptr;
-    const int W = cam->width, H = cam->height;
-    const size_t n_px = (size_t)W * H;
-    DevBuf<float> fb, var, aov, out;
+    const size_t n_px = (size_t)cam->width * cam->height;
+    DevBuf<float> fb, var;
     DevBuf<double> mom;
+    DenoisedTail tail;
     HIP_TRY(fb.alloc(n_px * 3));
     HIP_TRY(var.alloc(n_px));
-    HIP_TRY(aov.alloc(n_px * 8));
-    HIP_TRY(out.alloc(n_px * 3));
     HIP_TRY(mom.alloc(n_px * 6));
-    DenoiseBufs db;
-    HIP_TRY(db.alloc(n_px));
-    Event ev[4];  // around the three stages: render, AOV pass, filter
-    for (int k = 0; k < 4; ++k) HIP_TRY(ev[k].create(true));
-    HIP_TRY(hipEventRecord(ev[0], st));
-    HIP_TRY(hipMemsetAsync(mom.p, 0, n_px * 6 * sizeof(double), st));
-    if ((rc = f.pixels(p.spp, (float)p.spp, fb.p, st)) != MCPT_OK) return rc;
-    const PixelSet &ps = f.ps;
-    Totals rt;
-    if (ps.n_owned > ps.n_pix) launch_sky_moments(ps.sky, ps.n_owned - ps.n_pix, sc->view.background, p.spp, mom.p, st);
-    if (ps.n_pix > 0) {
-        rc = render_list(sc, f.cc, p, ps.list, ps.cand, ps.n_pix, 0, p.spp, (float)p.spp, fb.p, mom.p, st, f.t0, rt);
-        if (rc != MCPT_OK) return rc;
-    }
-    launch_dn_variance((uint32_t)n_px, mom.p, p.spp, var.p, st);
-    HIP_TRY(hipEventRecord(ev[1], st));
-    rc = aov_pass(sc, f.cc, p.seed, aov_spp, opts->specular_depth, aov.p, st);
-    if (rc != MCPT_OK) return drained(rc);
-    HIP_TRY(hipEventRecord(ev[2], st));
-    launch_denoise(W, H, o, fb.p, var.p, aov.p, db.rec[0].p, db.rec[1].p, db.grad.p, out.p, st);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(ev[3], st));
-    HIP_TRY(hipStreamSynchronize(st));
-    HIP_TRY(download(fb_host, fb, n_px * 3));
-    HIP_TRY(download(denoised_host, out, n_px * 3));
-    if (variance_host) HIP_TRY(download(variance_host, var, n_px));
-    if (aov_host) HIP_TRY(download(aov_host, aov, n_px * 8));
-    if (info) {
-        float ms[3] = {0.f, 0.f, 0.f};
-        for (int k = 0; k < 3; ++k) HIP_TRY(hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]));
-        info->ms_render = ms[0];
-        info->ms_aov = ms[1];
-        info->ms_denoise = ms[2];
-        info->ms_total = ms_since(f.t0);
-    }
-    return f.end(stats, (uint64_t)ps.n_owned * p.spp, (uint64_t)ps.n_pix * p.spp, rt);
+    if ((rc = tail.alloc(n_px)) != MCPT_OK) return rc;
+    HIP_TRY(hipEventRecord(tail.render_begin, st));
+    AdaptiveResult res;
+    if ((rc = render_moments(f, fb.p, mom.p, var.p, st, res)) != MCPT_OK) return rc;
+    if ((rc = tail.finish(f, *opts, o, aov_spp, fb, var, st, fb_host, denoised_host, variance_host, aov_host, info)) != MCPT_OK) return rc;
+    return f.end(stats, res.samples, res.traced_primary, res.totals);
 }
 
 int mcpt_render_motion(mcpt_scene *sc, const mcpt_camera *cam, const mcpt_camera *prev_cam, uint32_t seed, int32_t aov_spp, float *motion_host) {
@@ -625,32 +628,6 @@ int mcpt_render_motion(mcpt_scene *sc, const mcpt_camera *cam, const mcpt_camera
     const int rc = motion_pass(sc, cc, make_camera(*prev_cam), seed, n_spp, motion.p, nullptr);
     if (rc != MCPT_OK) return drained(rc);
     HIP_TRY(download(motion_host, motion, n_px * 4));
-    return MCPT_OK;
-}
-
-int mcpt_temporal_blend(mcpt_scene *sc, int32_t width, int32_t height, const float *color_host, const float *motion_host, const float *prev_color_host,
-                        const float *prev_depth_host, const float *prev_len_host, const mcpt_temporal_opts *opts, float *out_color_host,
-                        float *out_len_host) {
-    if (!sc || !color_host || !motion_host || !prev_color_host || !prev_depth_host || !prev_len_host || !opts || !out_color_host || !out_len_host)
-        return fail(MCPT_ERR_ARG, "mcpt_temporal_blend: null argument");
-    if (!frame_ok(width, height)) return fail(MCPT_ERR_ARG, "mcpt_temporal_blend: width and height must be positive (and the frame not too large)");
-    tp::Opts o;
-    if (tp::resolve_opts(*opts, o) != 0) return fail(MCPT_ERR_ARG, "mcpt_temporal_blend: option out of range");
-    HIP_TRY(hipSetDevice(sc->device));
-    (void)hipGetLastError();
-    const size_t n_px = (size_t)width * height;
-    DevBuf<float> col, mot, pcol, pz, plen, out, olen;
-    HIP_TRY(out.alloc(n_px * 3));
-    HIP_TRY(olen.alloc(n_px));
-    HIP_TRY(upload(col, color_host, n_px * 3));
-    HIP_TRY(upload(mot, motion_host, n_px * 4));
-    HIP_TRY(upload(pcol, prev_color_host, n_px * 3));
-    HIP_TRY(upload(pz, prev_depth_host, n_px));
-    HIP_TRY(upload(plen, prev_len_host, n_px));
-    launch_temporal_blend(width, height, o, col.p, mot.p, pcol.p, pz.p, plen.p, out.p, olen.p, nullptr);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(download(out_color_host, out, n_px * 3));
-    HIP_TRY(download(out_len_host, olen, n_px));
     return MCPT_OK;
 }
 

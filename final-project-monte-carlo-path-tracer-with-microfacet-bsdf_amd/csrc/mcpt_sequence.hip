@@ -1,11 +1,12 @@
-// Frame sequences (include/mcpt.h: mcpt_temporal_accumulate, mcpt_sequence_*): the frame loop of temporal reuse with its history, the
-// variance of the accumulated frame and every working buffer resident on the device.  A frame is the passes of csrc/mcpt_render.hip
-// (csrc/mcpt_frame.h) on the sequence's buffers, k_temporal_accumulate (csrc/mcpt_temporal.hip) between the two history sets, the filter
-// and the tone map, all queued on one stream; only the outputs the caller asks for are copied to the host.  A sequence created with
-// history rejection (mcpt_sequence_create_ex) runs k_temporal_accumulate_ex instead and keeps a normal and a flags plane per history set.
-// A sequence created with a rule (mcpt_sequence_create_adaptive) renders adaptive frames: the AOVs and the motion first, k_history_len from
-// the previous history set into the guide, then the rounds of csrc/mcpt_render.hip (adaptive_rounds) on the sequence's buffers and
-// k_dn_variance_map; mcpt_temporal_history_len is the guide's kernel on host arrays.
+// Temporal reuse on host arrays and frame sequences (include/mcpt.h: mcpt_temporal_blend, mcpt_temporal_accumulate[_ex],
+// mcpt_temporal_history_len, mcpt_sequence_*).  The host-array entry points stage their planes on the device and run one kernel of
+// csrc/mcpt_temporal.hip.  A sequence is the frame loop of temporal reuse with its history, the variance of the accumulated frame and every
+// working buffer resident on the device: a frame is the passes of csrc/mcpt_render.hip (csrc/mcpt_frame.h) on the sequence's buffers,
+// k_temporal_accumulate between the two history sets (the instantiation the sequence's history rejection selects; with rejection a set
+// also keeps a normal and a flags plane), the filter and the tone map, all queued on one stream; only the outputs the caller asks for are
+// copied to the host.  A sequence created with a rule (mcpt_sequence_create_adaptive) renders adaptive frames: the AOVs and the motion
+// first, k_history_len from the previous history set into the guide, then the rounds of csrc/mcpt_render.hip (adaptive_rounds) on the
+// sequence's buffers and k_dn_variance_map.
 #include <new>
 
 #include "mcpt_frame.h"
@@ -37,6 +38,9 @@ struct History {
         if (e == hipSuccess && flags.p) e = hipMemset(flags.p, 0, n_px);
         return e;
     }
+    // the set as the kernels take it: the previous frame's, or the one the frame writes
+    tp::Prev prev() const { return {color.p, variance.p, depth.p, len.p, normal.p}; }
+    tp::Next next() { return {color.p, variance.p, depth.p, len.p, normal.p, flags.p}; }
 };
 
 // The counts of one adaptive frame and the guide it was rendered with; two sets, used in turn with the history sets, so that a failed
@@ -55,7 +59,71 @@ struct Counts {
     }
 };
 
-constexpr int kStages = 5;  // render, AOVs, motion, accumulate, filter (+ tone map)
+// The HIP events of a frame, each named for the stage boundary it marks.  A uniform frame renders first, so render_end is where its AOV
+// pass begins and motion_end where its accumulation begins; an adaptive one takes its features first, from features_begin, and its
+// accumulation begins at render_end.
+struct StageEvents {
+    Event render_begin, render_end, features_begin, aov_end, motion_end, accumulate_end, filter_end;
+    hipError_t create() {
+        hipError_t e = hipSuccess;
+        for (Event *ev : {&render_begin, &render_end, &features_begin, &aov_end, &motion_end, &accumulate_end, &filter_end})
+            if (e == hipSuccess) e = ev->create(true);
+        return e;
+    }
+};
+
+// The host-array entry points mcpt_temporal_blend, mcpt_temporal_accumulate[_ex] and mcpt_temporal_history_len (`name` for the messages):
+// the checks in the order they have always had, the arrays that are given staged on the device (normals packed, no depth plane), one
+// kernel, the results back.  fh, ph and nh hold the host arrays; what a pass does not take is null.  hopts null: both switches 0.
+enum class Pass { blend, accumulate, history_len };
+int temporal_call(const char *name, Pass pass, mcpt_scene *sc, int32_t width, int32_t height, tp::Frame fh, tp::Prev ph, const mcpt_temporal_opts *opts,
+                  const mcpt_history_opts *hopts, const tp::Next &nh) {
+    const auto bad = [&](const char *what) { return fail(MCPT_ERR_ARG, std::string(name) + ": " + what); };
+    const bool color = pass != Pass::history_len, var = pass == Pass::accumulate;
+    if (!sc || !fh.motion || !ph.color || !ph.depth || !ph.len || !opts || !nh.len || (color && (!fh.color || !nh.color)) ||
+        (var && (!fh.variance || !ph.variance || !hopts || !nh.variance)))
+        return bad("null argument");
+    if (!frame_ok(width, height)) return bad("width and height must be positive (and the frame not too large)");
+    tp::Opts o;
+    tp::HistOpts ho{};
+    if (tp::resolve_opts(*opts, o) != 0) return bad("option out of range");
+    if (hopts && tp::resolve_history_opts(*hopts, ho) != 0) return bad("history option out of range");
+    if (ho.normal_test && (!fh.normal || !ph.normal)) return bad("normal_test needs both normal arrays");
+    if (!ho.normal_test) fh.normal = ph.normal = nullptr;  // (neither read nor uploaded)
+    HIP_TRY(hipSetDevice(sc->device));
+    (void)hipGetLastError();
+    const size_t n_px = (size_t)width * height;
+    const bool flags = nh.flags && (ho.normal_test || ho.color_clamp);  // (both switches 0: every flag is 0, and the kernel writes none)
+    DevBuf<float> in[9], out, ovar, olen;
+    DevBuf<uint8_t> oflags;
+    if (color) HIP_TRY(out.alloc(n_px * 3));
+    if (var) HIP_TRY(ovar.alloc(n_px));
+    HIP_TRY(olen.alloc(n_px));
+    if (flags) HIP_TRY(oflags.alloc(n_px));
+    hipError_t e = hipSuccess;
+    int k = 0;
+    const auto up = [&](const float *host, size_t per_px) -> const float * {  // a null array stays a null plane
+        DevBuf<float> &d = in[k++];
+        if (e == hipSuccess && host) e = upload(d, host, n_px * per_px);
+        return d.p;
+    };
+    const tp::Frame f = {up(fh.color, 3), up(fh.variance, 1), up(fh.motion, 4), up(fh.normal, 3), 3, nullptr, 1};
+    const tp::Prev p = {up(ph.color, 3), up(ph.variance, 1), up(ph.depth, 1), up(ph.len, 1), up(ph.normal, 3)};
+    HIP_TRY(e);
+    const tp::Next n = {out.p, ovar.p, nullptr, olen.p, nullptr, oflags.p};
+    if (pass == Pass::blend) launch_temporal_blend(width, height, o, f, p, n, nullptr);
+    if (pass == Pass::accumulate) launch_temporal_accumulate(width, height, o, ho, f, p, n, nullptr);
+    if (pass == Pass::history_len) launch_history_len(width, height, o, ho, f, p, olen.p, nullptr);
+    HIP_TRY(hipGetLastError());
+    if (color) HIP_TRY(download(nh.color, out, n_px * 3));
+    if (var) HIP_TRY(download(nh.variance, ovar, n_px));
+    HIP_TRY(download(nh.len, olen, n_px));
+    if (flags)
+        HIP_TRY(download(nh.flags, oflags, n_px));
+    else if (nh.flags)
+        std::memset(nh.flags, 0, n_px);
+    return MCPT_OK;
+}
 
 }  // namespace
 
@@ -66,7 +134,7 @@ struct mcpt_sequence {
     int W = 0, H = 0;
     mcpt_sequence_opts opts{};
     tp::Opts temporal{};
-    tp::HistOpts reject{};  // both switches 0: the frame runs k_temporal_accumulate, as a sequence of mcpt_sequence_create
+    tp::HistOpts reject{};  // both switches 0: a sequence of mcpt_sequence_create
     dn::Opts denoise{};
     History hist[2];
     int cur = 0;        // the set that holds the history of the previous frame; a frame writes the other one
@@ -77,7 +145,7 @@ struct mcpt_sequence {
     DevBuf<double> mom;
     DevBuf<uint8_t> rgba;
     DenoiseBufs db;
-    Event ev[kStages + 2];  // (the last one: the end of an adaptive sequence's rounds)
+    StageEvents ev;
     // a sequence created with mcpt_sequence_create_adaptive and a rule (all empty otherwise)
     bool adaptive = false;
     mcpt_adaptive rule{};
@@ -90,117 +158,38 @@ struct mcpt_sequence {
 
 extern "C" {
 
+int mcpt_temporal_blend(mcpt_scene *sc, int32_t width, int32_t height, const float *color_host, const float *motion_host, const float *prev_color_host,
+                        const float *prev_depth_host, const float *prev_len_host, const mcpt_temporal_opts *opts, float *out_color_host,
+                        float *out_len_host) {
+    return temporal_call("mcpt_temporal_blend", Pass::blend, sc, width, height, {color_host, nullptr, motion_host, nullptr, 3, nullptr, 1},
+                         {prev_color_host, nullptr, prev_depth_host, prev_len_host, nullptr}, opts, nullptr,
+                         {out_color_host, nullptr, nullptr, out_len_host, nullptr, nullptr});
+}
+
 int mcpt_temporal_accumulate(mcpt_scene *sc, int32_t width, int32_t height, const float *color_host, const float *variance_host, const float *motion_host,
                              const float *prev_color_host, const float *prev_variance_host, const float *prev_depth_host, const float *prev_len_host,
                              const mcpt_temporal_opts *opts, float *out_color_host, float *out_variance_host, float *out_len_host) {
-    if (!sc || !color_host || !variance_host || !motion_host || !prev_color_host || !prev_variance_host || !prev_depth_host || !prev_len_host || !opts ||
-        !out_color_host || !out_variance_host || !out_len_host)
-        return fail(MCPT_ERR_ARG, "mcpt_temporal_accumulate: null argument");
-    if (!frame_ok(width, height)) return fail(MCPT_ERR_ARG, "mcpt_temporal_accumulate: width and height must be positive (and the frame not too large)");
-    tp::Opts o;
-    if (tp::resolve_opts(*opts, o) != 0) return fail(MCPT_ERR_ARG, "mcpt_temporal_accumulate: option out of range");
-    HIP_TRY(hipSetDevice(sc->device));
-    (void)hipGetLastError();
-    const size_t n_px = (size_t)width * height;
-    DevBuf<float> col, var, mot, pcol, pvar, pz, plen, out, ovar, olen;
-    HIP_TRY(out.alloc(n_px * 3));
-    HIP_TRY(ovar.alloc(n_px));
-    HIP_TRY(olen.alloc(n_px));
-    HIP_TRY(upload(col, color_host, n_px * 3));
-    HIP_TRY(upload(var, variance_host, n_px));
-    HIP_TRY(upload(mot, motion_host, n_px * 4));
-    HIP_TRY(upload(pcol, prev_color_host, n_px * 3));
-    HIP_TRY(upload(pvar, prev_variance_host, n_px));
-    HIP_TRY(upload(pz, prev_depth_host, n_px));
-    HIP_TRY(upload(plen, prev_len_host, n_px));
-    launch_temporal_accumulate(width, height, o, col.p, var.p, mot.p, pcol.p, pvar.p, pz.p, plen.p, nullptr, 0, out.p, ovar.p, nullptr, olen.p, nullptr);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(download(out_color_host, out, n_px * 3));
-    HIP_TRY(download(out_variance_host, ovar, n_px));
-    HIP_TRY(download(out_len_host, olen, n_px));
-    return MCPT_OK;
+    const mcpt_history_opts off{};  // the _ex call with zeroed options, no normals and no flags
+    return temporal_call("mcpt_temporal_accumulate", Pass::accumulate, sc, width, height, {color_host, variance_host, motion_host, nullptr, 3, nullptr, 1},
+                         {prev_color_host, prev_variance_host, prev_depth_host, prev_len_host, nullptr}, opts, &off,
+                         {out_color_host, out_variance_host, nullptr, out_len_host, nullptr, nullptr});
 }
 
 int mcpt_temporal_accumulate_ex(mcpt_scene *sc, int32_t width, int32_t height, const float *color_host, const float *variance_host, const float *motion_host,
                                 const float *normal_host, const float *prev_color_host, const float *prev_variance_host, const float *prev_depth_host,
                                 const float *prev_len_host, const float *prev_normal_host, const mcpt_temporal_opts *opts, const mcpt_history_opts *hopts,
                                 float *out_color_host, float *out_variance_host, float *out_len_host, uint8_t *out_flags_host) {
-    if (!sc || !color_host || !variance_host || !motion_host || !prev_color_host || !prev_variance_host || !prev_depth_host || !prev_len_host || !opts ||
-        !hopts || !out_color_host || !out_variance_host || !out_len_host)
-        return fail(MCPT_ERR_ARG, "mcpt_temporal_accumulate_ex: null argument");
-    if (!frame_ok(width, height)) return fail(MCPT_ERR_ARG, "mcpt_temporal_accumulate_ex: width and height must be positive (and the frame not too large)");
-    tp::Opts o;
-    tp::HistOpts ho;
-    if (tp::resolve_opts(*opts, o) != 0) return fail(MCPT_ERR_ARG, "mcpt_temporal_accumulate_ex: option out of range");
-    if (tp::resolve_history_opts(*hopts, ho) != 0) return fail(MCPT_ERR_ARG, "mcpt_temporal_accumulate_ex: history option out of range");
-    if (ho.normal_test && (!normal_host || !prev_normal_host)) return fail(MCPT_ERR_ARG, "mcpt_temporal_accumulate_ex: normal_test needs both normal arrays");
-    HIP_TRY(hipSetDevice(sc->device));
-    (void)hipGetLastError();
-    const size_t n_px = (size_t)width * height;
-    const bool reject = ho.normal_test || ho.color_clamp;
-    DevBuf<float> col, var, mot, nrm, pcol, pvar, pz, plen, pnrm, out, ovar, olen;
-    DevBuf<uint8_t> oflags;
-    HIP_TRY(out.alloc(n_px * 3));
-    HIP_TRY(ovar.alloc(n_px));
-    HIP_TRY(olen.alloc(n_px));
-    if (reject && out_flags_host) HIP_TRY(oflags.alloc(n_px));
-    HIP_TRY(upload(col, color_host, n_px * 3));
-    HIP_TRY(upload(var, variance_host, n_px));
-    HIP_TRY(upload(mot, motion_host, n_px * 4));
-    HIP_TRY(upload(pcol, prev_color_host, n_px * 3));
-    HIP_TRY(upload(pvar, prev_variance_host, n_px));
-    HIP_TRY(upload(pz, prev_depth_host, n_px));
-    HIP_TRY(upload(plen, prev_len_host, n_px));
-    if (ho.normal_test) {
-        HIP_TRY(upload(nrm, normal_host, n_px * 3));
-        HIP_TRY(upload(pnrm, prev_normal_host, n_px * 3));
-    }
-    if (reject)
-        launch_temporal_accumulate_ex(width, height, o, ho, col.p, var.p, mot.p, nrm.p, 3, pcol.p, pvar.p, pz.p, plen.p, pnrm.p, nullptr, 0, out.p, ovar.p, nullptr,
-                                      olen.p, nullptr, oflags.p, nullptr);
-    else  // both switches 0: mcpt_temporal_accumulate's kernel
-        launch_temporal_accumulate(width, height, o, col.p, var.p, mot.p, pcol.p, pvar.p, pz.p, plen.p, nullptr, 0, out.p, ovar.p, nullptr, olen.p, nullptr);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(download(out_color_host, out, n_px * 3));
-    HIP_TRY(download(out_variance_host, ovar, n_px));
-    HIP_TRY(download(out_len_host, olen, n_px));
-    if (out_flags_host) {
-        if (reject)
-            HIP_TRY(download(out_flags_host, oflags, n_px));
-        else
-            std::memset(out_flags_host, 0, n_px);
-    }
-    return MCPT_OK;
+    return temporal_call("mcpt_temporal_accumulate_ex", Pass::accumulate, sc, width, height, {color_host, variance_host, motion_host, normal_host, 3, nullptr, 1},
+                         {prev_color_host, prev_variance_host, prev_depth_host, prev_len_host, prev_normal_host}, opts, hopts,
+                         {out_color_host, out_variance_host, nullptr, out_len_host, nullptr, out_flags_host});
 }
 
 int mcpt_temporal_history_len(mcpt_scene *sc, int32_t width, int32_t height, const float *motion_host, const float *normal_host,
                               const float *prev_color_host, const float *prev_depth_host, const float *prev_len_host, const float *prev_normal_host,
                               const mcpt_temporal_opts *opts, const mcpt_history_opts *hopts, float *len_host) {
-    const auto bad = [](const char *what) { return fail(MCPT_ERR_ARG, std::string("mcpt_temporal_history_len: ") + what); };
-    if (!sc || !motion_host || !prev_color_host || !prev_depth_host || !prev_len_host || !opts || !len_host) return bad("null argument");
-    if (!frame_ok(width, height)) return bad("width and height must be positive (and the frame not too large)");
-    tp::Opts o;
-    tp::HistOpts ho{};
-    if (tp::resolve_opts(*opts, o) != 0) return bad("option out of range");
-    if (hopts && tp::resolve_history_opts(*hopts, ho) != 0) return bad("history option out of range");
-    if (ho.normal_test && (!normal_host || !prev_normal_host)) return bad("normal_test needs both normal arrays");
-    HIP_TRY(hipSetDevice(sc->device));
-    (void)hipGetLastError();
-    const size_t n_px = (size_t)width * height;
-    DevBuf<float> mot, nrm, pcol, pz, plen, pnrm, len;
-    HIP_TRY(len.alloc(n_px));
-    HIP_TRY(upload(mot, motion_host, n_px * 4));
-    HIP_TRY(upload(pcol, prev_color_host, n_px * 3));
-    HIP_TRY(upload(pz, prev_depth_host, n_px));
-    HIP_TRY(upload(plen, prev_len_host, n_px));
-    if (ho.normal_test) {
-        HIP_TRY(upload(nrm, normal_host, n_px * 3));
-        HIP_TRY(upload(pnrm, prev_normal_host, n_px * 3));
-    }
-    launch_history_len(width, height, o, ho, mot.p, nrm.p, 3, pcol.p, pz.p, plen.p, pnrm.p, len.p, nullptr);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(download(len_host, len, n_px));
-    return MCPT_OK;
+    return temporal_call("mcpt_temporal_history_len", Pass::history_len, sc, width, height, {nullptr, nullptr, motion_host, normal_host, 3, nullptr, 1},
+                         {prev_color_host, nullptr, prev_depth_host, prev_len_host, prev_normal_host}, opts, hopts,
+                         {nullptr, nullptr, nullptr, len_host, nullptr, nullptr});
 }
 
 void mcpt_sequence_destroy(mcpt_sequence *seq) {
@@ -289,8 +278,7 @@ int mcpt_sequence_create_adaptive(mcpt_scene *sc, int32_t width, int32_t height,
         also(seq->stamp, n_px);
         if (e == hipSuccess) e = seq->lists.alloc((uint32_t)n_px, true);
     }
-    for (int k = 0; k <= kStages + 1; ++k)
-        if (e == hipSuccess) e = seq->ev[k].create(true);
+    if (e == hipSuccess) e = seq->ev.create();
     // the snapshot's arrays are allocated here too, so that the one at the end of a frame only copies
     const int rc = e == hipSuccess ? mcpt_scene_snapshot(sc)
                                    : fail(e == hipErrorOutOfMemory ? MCPT_ERR_OOM : MCPT_ERR_HIP, std::string("mcpt_sequence_create: ") + hipGetErrorString(e));
@@ -357,54 +345,39 @@ int mcpt_sequence_frame(mcpt_sequence *seq, const mcpt_camera *cam, const mcpt_p
     const size_t n_px = (size_t)W * H;
     const History &prev = seq->hist[seq->cur];
     History &next = seq->hist[seq->cur ^ 1];
-    const Event *ev = seq->ev;
-    Totals rt;
-    uint64_t samples = 0, traced_primary = 0;
-    mcpt_adaptive_info ainfo{};
+    const StageEvents &ev = seq->ev;
+    // the normals and the depth of the history come from the first-hit AOVs: channels 3-5 and 6 of the 8
     const float *first_hit = dopts.specular_depth > 0 ? seq->aov_first.p : seq->aov.p;
+    const tp::Frame planes = {seq->fb.p, seq->var.p, seq->motion.p, first_hit + 3, 8, first_hit + 6, 8};
+    // The feature stage, from an event the branch has recorded: the AOVs (3.) with the first-hit depth the history is validated against,
+    // and the motion (4.) against the snapshot and the previous frame's camera; a fresh sequence takes no history.
+    const auto features = [&]() -> int {
+        int rc = aov_pass(sc, f.cc, p.seed, aov_spp, dopts.specular_depth, seq->aov.p, st);
+        if (rc == MCPT_OK && dopts.specular_depth > 0) rc = aov_pass(sc, f.cc, p.seed, aov_spp, 0, seq->aov_first.p, st);
+        if (rc != MCPT_OK) return drained(rc);
+        HIP_TRY(hipEventRecord(ev.aov_end, st));
+        rc = motion_pass(sc, f.cc, seq->fresh ? f.cc : seq->prev_cc, p.seed, aov_spp, seq->motion.p, st);
+        if (rc != MCPT_OK) return drained(rc);
+        if (seq->fresh) HIP_TRY(hipMemsetAsync(prev.len.p, 0, n_px * sizeof(float), st));
+        return MCPT_OK;
+    };
+    AdaptiveResult res;
     if (!seq->adaptive) {
-        // 2. the frame with its moments, and its variance (mcpt_render_denoised, steps 1-2)
-        HIP_TRY(hipEventRecord(ev[0], st));
-        HIP_TRY(hipMemsetAsync(seq->mom.p, 0, n_px * 6 * sizeof(double), st));
-        if ((rc = f.pixels(p.spp, (float)p.spp, seq->fb.p, st)) != MCPT_OK) return rc;
-        const PixelSet &ps = f.ps;
-        if (ps.n_owned > ps.n_pix) launch_sky_moments(ps.sky, ps.n_owned - ps.n_pix, sc->view.background, p.spp, seq->mom.p, st);
-        if (ps.n_pix > 0) {
-            rc = render_list(sc, f.cc, p, ps.list, ps.cand, ps.n_pix, 0, p.spp, (float)p.spp, seq->fb.p, seq->mom.p, st, f.t0, rt);
-            if (rc != MCPT_OK) return rc;
-        }
-        launch_dn_variance((uint32_t)n_px, seq->mom.p, p.spp, seq->var.p, st);
-        samples = (uint64_t)ps.n_owned * p.spp;
-        traced_primary = (uint64_t)ps.n_pix * p.spp;
-        HIP_TRY(hipEventRecord(ev[1], st));
-        // 3. the AOVs, and the first-hit depth the history is validated against
-        rc = aov_pass(sc, f.cc, p.seed, aov_spp, dopts.specular_depth, seq->aov.p, st);
-        if (rc == MCPT_OK && dopts.specular_depth > 0) rc = aov_pass(sc, f.cc, p.seed, aov_spp, 0, seq->aov_first.p, st);
-        if (rc != MCPT_OK) return drained(rc);
-        HIP_TRY(hipEventRecord(ev[2], st));
-        // 4. the motion against the snapshot and the previous frame's camera
-        rc = motion_pass(sc, f.cc, seq->fresh ? f.cc : seq->prev_cc, p.seed, aov_spp, seq->motion.p, st);
-        if (rc != MCPT_OK) return drained(rc);
-        HIP_TRY(hipEventRecord(ev[3], st));
-        if (seq->fresh) HIP_TRY(hipMemsetAsync(prev.len.p, 0, n_px * sizeof(float), st));
+        // 2. the frame with its moments, and its variance (mcpt_render_denoised, steps 1-2), then the features
+        HIP_TRY(hipEventRecord(ev.render_begin, st));
+        if ((rc = render_moments(f, seq->fb.p, seq->mom.p, seq->var.p, st, res)) != MCPT_OK) return rc;
+        HIP_TRY(hipEventRecord(ev.render_end, st));
+        if ((rc = features()) != MCPT_OK) return rc;
+        HIP_TRY(hipEventRecord(ev.motion_end, st));
     } else {
-        // An adaptive sequence (mcpt_sequence_create_adaptive): the AOVs and the motion first -- neither depends on the frame -- so that the
-        // guide is known before the rounds.  The events keep their stages: ev[1], ev[2], ev[3] around the AOVs and the motion (with the
-        // guide), then ev[0] and ev[kStages + 1] around the rounds, which ms_render is taken between.
+        // An adaptive sequence (mcpt_sequence_create_adaptive): the features first -- they do not depend on the frame -- so that the guide
+        // is known before the rounds.
         Counts &cn = seq->cnt[seq->cur ^ 1];
-        HIP_TRY(hipEventRecord(ev[1], st));
-        rc = aov_pass(sc, f.cc, p.seed, aov_spp, dopts.specular_depth, seq->aov.p, st);
-        if (rc == MCPT_OK && dopts.specular_depth > 0) rc = aov_pass(sc, f.cc, p.seed, aov_spp, 0, seq->aov_first.p, st);
-        if (rc != MCPT_OK) return drained(rc);
-        HIP_TRY(hipEventRecord(ev[2], st));
-        rc = motion_pass(sc, f.cc, seq->fresh ? f.cc : seq->prev_cc, p.seed, aov_spp, seq->motion.p, st);
-        if (rc != MCPT_OK) return drained(rc);
-        if (seq->fresh) HIP_TRY(hipMemsetAsync(prev.len.p, 0, n_px * sizeof(float), st));
+        HIP_TRY(hipEventRecord(ev.features_begin, st));
+        if ((rc = features()) != MCPT_OK) return rc;
         // the guide: the history length each pixel is about to get (1 everywhere on a fresh sequence: prev_len is 0); counted with the motion
-        if (seq->guided)
-            launch_history_len(W, H, seq->temporal, seq->reject, seq->motion.p, first_hit + 3, 8, prev.color.p, prev.depth.p, prev.len.p, prev.normal.p,
-                               cn.guide.p, st);
-        HIP_TRY(hipEventRecord(ev[3], st));
+        if (seq->guided) launch_history_len(W, H, seq->temporal, seq->reject, planes, prev.prev(), cn.guide.p, st);
+        HIP_TRY(hipEventRecord(ev.motion_end, st));
         AdaptiveBufs b;
         b.fb = seq->fb.p;
         b.mom = seq->mom.p;
@@ -413,30 +386,19 @@ int mcpt_sequence_frame(mcpt_sequence *seq, const mcpt_camera *cam, const mcpt_p
         b.stamp = seq->stamp.p;
         b.guide = seq->guided ? cn.guide.p : nullptr;
         seq->lists.into(b);
-        AdaptiveResult res;
-        HIP_TRY(hipEventRecord(ev[0], st));
+        HIP_TRY(hipEventRecord(ev.render_begin, st));
         if ((rc = adaptive_rounds(f, seq->rule, b, nullptr, st, res)) != MCPT_OK) return rc;
         launch_dn_variance_map((uint32_t)n_px, seq->mom.p, cn.spp.p, seq->var.p, st);
-        HIP_TRY(hipEventRecord(ev[kStages + 1], st));
-        rt = res.totals;
-        samples = res.samples;
-        traced_primary = res.traced_primary;
-        ainfo = res.info;
+        HIP_TRY(hipEventRecord(ev.render_end, st));
     }
     // 5. previous history set -> the other one
-    if (seq->reject.normal_test || seq->reject.color_clamp)  // (the normals come from the AOVs the depth comes from)
-        launch_temporal_accumulate_ex(W, H, seq->temporal, seq->reject, seq->fb.p, seq->var.p, seq->motion.p, first_hit + 3, 8, prev.color.p, prev.variance.p,
-                                      prev.depth.p, prev.len.p, prev.normal.p, first_hit + 6, 8, next.color.p, next.variance.p, next.depth.p, next.len.p,
-                                      next.normal.p, next.flags.p, st);
-    else
-        launch_temporal_accumulate(W, H, seq->temporal, seq->fb.p, seq->var.p, seq->motion.p, prev.color.p, prev.variance.p, prev.depth.p, prev.len.p,
-                                   first_hit + 6, 8, next.color.p, next.variance.p, next.depth.p, next.len.p, st);
-    HIP_TRY(hipEventRecord(ev[4], st));
+    launch_temporal_accumulate(W, H, seq->temporal, seq->reject, planes, prev.prev(), next.next(), st);
+    HIP_TRY(hipEventRecord(ev.accumulate_end, st));
     // 6., 7. the filter and the tone map
     if (filter) launch_denoise(W, H, seq->denoise, next.color.p, next.variance.p, seq->aov.p, seq->db.rec[0].p, seq->db.rec[1].p, seq->db.grad.p, seq->out.p, st);
     if (want.rgba) launch_tonemap(filter ? seq->out.p : next.color.p, (uint32_t)n_px, seq->rgba.p, st);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(ev[5], st));
+    HIP_TRY(hipEventRecord(ev.filter_end, st));
     HIP_TRY(hipStreamSynchronize(st));
     if (want.fb) HIP_TRY(download(want.fb, seq->fb, n_px * 3));
     if (want.accumulated) HIP_TRY(download(want.accumulated, next.color, n_px * 3));
@@ -446,13 +408,19 @@ int mcpt_sequence_frame(mcpt_sequence *seq, const mcpt_camera *cam, const mcpt_p
     if (want.aov) HIP_TRY(download(want.aov, seq->aov, n_px * 8));
     if (want.motion) HIP_TRY(download(want.motion, seq->motion, n_px * 4));
     if (want.rgba) HIP_TRY(download(want.rgba, seq->rgba, n_px * 4));
-    float ms[kStages] = {0.f, 0.f, 0.f, 0.f, 0.f};
-    if (info) {
-        for (int k = seq->adaptive ? 1 : 0; k < kStages; ++k) HIP_TRY(hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]));
-        if (seq->adaptive) {  // the rounds ran after the motion stage: ev[0] .. ev[kStages + 1]; the accumulate stage starts where they end
-            HIP_TRY(hipEventElapsedTime(&ms[0], ev[0], ev[kStages + 1]));
-            HIP_TRY(hipEventElapsedTime(&ms[3], ev[kStages + 1], ev[4]));
-        }
+    mcpt_sequence_info timing{};
+    if (info) {  // each stage between its two events: the AOVs and the accumulation begin where the branch's previous stage ended
+        const auto span = [](const Event &from, const Event &to, double &ms) {
+            float t = 0.f;
+            const hipError_t e = hipEventElapsedTime(&t, from, to);
+            ms = t;
+            return e;
+        };
+        HIP_TRY(span(ev.render_begin, ev.render_end, timing.ms_render));
+        HIP_TRY(span(seq->adaptive ? ev.features_begin : ev.render_end, ev.aov_end, timing.ms_aov));
+        HIP_TRY(span(ev.aov_end, ev.motion_end, timing.ms_motion));
+        HIP_TRY(span(seq->adaptive ? ev.render_end : ev.motion_end, ev.accumulate_end, timing.ms_accumulate));
+        HIP_TRY(span(ev.accumulate_end, ev.filter_end, timing.ms_filter));
     }
     // 8. this frame's geometry is "previous" for the next one
     if ((rc = mcpt_scene_snapshot(sc)) != MCPT_OK) return rc;
@@ -462,18 +430,13 @@ int mcpt_sequence_frame(mcpt_sequence *seq, const mcpt_camera *cam, const mcpt_p
     seq->fresh = false;
     seq->frame_index = index + 1;
     seq->prev_cc = f.cc;
-    seq->ainfo = ainfo;
+    seq->ainfo = res.info;
     if (info) {
-        std::memset(info, 0, sizeof *info);
-        info->ms_render = ms[0];
-        info->ms_aov = ms[1];
-        info->ms_motion = ms[2];
-        info->ms_accumulate = ms[3];
-        info->ms_filter = ms[4];
-        info->ms_total = ms_since(f.t0);
-        info->frame_index = index;
+        timing.ms_total = ms_since(f.t0);
+        timing.frame_index = index;
+        *info = timing;
     }
-    return f.end(stats, samples, traced_primary, rt);
+    return f.end(stats, res.samples, res.traced_primary, res.totals);
 }
 
 }  // extern "C"

@@ -138,23 +138,37 @@ MCPT_TP void fold_pixel(const float *s, int32_t spp, float out[4]) {
     out[3] = fn / (float)spp;
 }
 
+/* The arrays of a W x H frame the rule reads and writes, as three small sets of pointers.  A member a flavour does not use may be null.
+ * This frame's planes: color 3 floats per pixel, variance 1 (its luminance variance of the colour mean), motion 4; the first-hit normal of
+ * pixel m at normal[normal_stride m ..] and its first-hit depth at depth[depth_stride m] (stride 3 and 1 for packed arrays, 8 for the
+ * channels of an AOV array).  The rule reads the normal only with the normal test and never the depth: the kernel copies both into the
+ * next history set (csrc/mcpt_temporal.hip). */
+struct Frame { const float *color, *variance, *motion, *normal; int normal_stride; const float *depth; int depth_stride; };
+// The previous history set: color 3 floats per pixel, normal 3 (packed), the others 1.
+struct Prev { const float *color, *variance, *depth, *len, *normal; };
+// The next one.  The rule writes color, variance, len and flags (one byte per pixel, nullable); depth and normal are the kernel's copies.
+struct Next { float *color, *variance, *depth, *len, *normal; uint8_t *flags; };
+
 /* What the taps of one pixel's history add up to (steps 2, 3 and the sums of step 5 of the rule in include/mcpt.h). */
 struct Taps {
     float sw, s0, s1, s2;  // sum of w, sum of w * colour
-    float sv;              // sum of (w * w) * prev_variance (accumulate_pixel only)
-    float nmin;            // the smallest prev_len of the used taps
+    float sv;              // sum of (w * w) * prev.variance (kVar only)
+    float nmin;            // the smallest prev.len of the used taps
     bool nskip;            // the normal test skipped a tap that every older test had passed (kNorm only)
 };
 
-/* The tap loop the blend and the accumulation share: the four bilinear taps of pixel (i, j) moved by its motion record mv, in tap order,
- * with every skip of the rule.  false if no tap is left.  kVar: also sum the taps' variances (prev_variance is not read without it).
+/* The tap loop every flavour shares: the four bilinear taps of pixel (i, j) moved by its motion record, in tap order, with every skip of
+ * the rule.  false if no tap is left.  kVar: also sum the taps' variances (p.variance is not read without it).
  * The taps' positions are tested in float before they become indices, so a motion that is huge or not finite reads nothing.
  * kNorm: the normal test of mcpt_temporal_accumulate_ex after the depth test: a tap is skipped if !(d >= normal_min), d the 3-term dot
- * x + (y + z) of prev_normal[tap] and this pixel's normal n (prev_normal is not read without it). */
-template <bool kVar, bool kNorm = false>
-MCPT_TP bool gather_taps(int W, int H, int i, int j, const float *mv, const float *prev_color, const float *prev_variance, const float *prev_depth,
-                         const float *prev_len, const Opts &o, Taps &t, const float *prev_normal = nullptr, const float *n3 = nullptr,
-                         float normal_min = 0.0f) {
+ * x + (y + z) of p.normal[tap] and this pixel's normal (neither f.normal nor p.normal is read without it). */
+template <bool kVar, bool kNorm>
+MCPT_TP bool gather_taps(int W, int H, int i, int j, const Frame &f, const Prev &p, const Opts &o, float normal_min, Taps &t) {
+    const size_t m = (size_t)j * W + i;
+    const float *mv = f.motion + m * 4;
+    float n3[3] = {0.0f, 0.0f, 0.0f};
+    if (kNorm)
+        for (int c = 0; c < 3; ++c) n3[c] = f.normal[m * (size_t)f.normal_stride + c];
     const float fx = (float)i + mv[0], fy = (float)j + mv[1];
     const float x0 = floorf(fx), y0 = floorf(fy);
     const float a = fx - x0, b = fy - y0;
@@ -171,14 +185,14 @@ MCPT_TP bool gather_taps(int W, int H, int i, int j, const float *mv, const floa
         if (w == 0.0f) continue;
         if (!(tx >= 0.0f && tx < (float)W && ty >= 0.0f && ty < (float)H)) continue;
         const size_t q = (size_t)(int)ty * W + (size_t)(int)tx;
-        const float n = prev_len[q];
+        const float n = p.len[q];
         if (n <= 0.0f) continue;
-        const float p0 = prev_color[q * 3], p1 = prev_color[q * 3 + 1], p2 = prev_color[q * 3 + 2];
+        const float p0 = p.color[q * 3], p1 = p.color[q * 3 + 1], p2 = p.color[q * 3 + 2];
         if (!(finite_f(p0) && finite_f(p1) && finite_f(p2))) continue;
-        const float dz = prev_depth[q] - zp;
+        const float dz = p.depth[q] - zp;
         if (!((dz < 0.0f ? -dz : dz) <= ztol)) continue;  // (a NaN depth on either side rejects the tap)
         if (kNorm) {
-            const float d = prev_normal[q * 3] * n3[0] + (prev_normal[q * 3 + 1] * n3[1] + prev_normal[q * 3 + 2] * n3[2]);
+            const float d = p.normal[q * 3] * n3[0] + (p.normal[q * 3 + 1] * n3[1] + p.normal[q * 3 + 2] * n3[2]);
             if (!(d >= normal_min)) {  // (a NaN normal on either side rejects the tap)
                 nskip = true;
                 continue;
@@ -188,83 +202,18 @@ MCPT_TP bool gather_taps(int W, int H, int i, int j, const float *mv, const floa
         s0 = s0 + w * p0;
         s1 = s1 + w * p1;
         s2 = s2 + w * p2;
-        if (kVar) sv = sv + (w * w) * prev_variance[q];
+        if (kVar) sv = sv + (w * w) * p.variance[q];
         nmin = (!any || n < nmin) ? n : nmin;
         any = true;
     }
-    t.sw = sw;
-    t.s0 = s0;
-    t.s1 = s1;
-    t.s2 = s2;
-    t.sv = sv;
-    t.nmin = nmin;
-    t.nskip = nskip;
+    t = {sw, s0, s1, s2, sv, nmin, nskip};
     return any;
 }
 
-/* The blend at pixel (i, j) of a W x H frame (include/mcpt.h has the rule): color, prev_color 3 floats per pixel; motion 4;
- * prev_depth, prev_len 1.  Writes out_color[3 m ..] and out_len[m], m = j W + i. */
-MCPT_TP void blend_pixel(int W, int H, int i, int j, const float *color, const float *motion, const float *prev_color,
-                         const float *prev_depth, const float *prev_len, const Opts &o, float *out_color, float *out_len) {
-    const size_t m = (size_t)j * W + i;
-    const float c0 = color[m * 3], c1 = color[m * 3 + 1], c2 = color[m * 3 + 2];
-    const float *mv = motion + m * 4;
-    float r0 = c0, r1 = c1, r2 = c2, len = 1.0f;
-    Taps t;
-    if (mv[3] > 0.0f && finite_f(c0) && finite_f(c1) && finite_f(c2) &&
-        gather_taps<false>(W, H, i, j, mv, prev_color, nullptr, prev_depth, prev_len, o, t)) {
-        const float h0 = t.s0 / t.sw, h1 = t.s1 / t.sw, h2 = t.s2 / t.sw;
-        const float n1 = t.nmin + 1.0f;
-        const float N = n1 < o.max_history ? n1 : o.max_history;
-        const float k = 1.0f / N;
-        r0 = h0 + (c0 - h0) * k;
-        r1 = h1 + (c1 - h1) * k;
-        r2 = h2 + (c2 - h2) * k;
-        len = N;
-    }
-    out_color[m * 3] = r0;
-    out_color[m * 3 + 1] = r1;
-    out_color[m * 3 + 2] = r2;
-    out_len[m] = len;
-}
-
-/* The blend with the variance of its result (include/mcpt.h: mcpt_temporal_accumulate).  variance[m] = v_c is this frame's luminance
- * variance of the colour mean, prev_variance the previous out_variance.  Colour and length are blend_pixel's, expression for expression.
- * Where the blend takes no history out_variance = v_c; otherwise, over the taps the colour used, in tap order and from 0,
- *     sv = sv + (w*w) * prev_variance[q];  hv = sv / (sw*sw);  k = 1.f / N;  omk = 1.f - k;  out_variance = (omk*omk)*hv + (k*k)*v_c:
- * the variance of hist + (color - hist)*k for independent terms, so a static pixel carries (sum of its frames' variances) / N^2 after N
- * frames.  An hv that is not finite or is negative (a tap's stored variance was) gives v_c: one frame's variance over-estimates, so a
- * filter guided by it smooths more, never less.  A NaN v_c propagates.
- * The propagation treats the taps, and the pixels of the output, as independent.  Bilinear resampling correlates neighbouring pixels
- * (two outputs that share a tap share its noise); that covariance is ignored. */
-MCPT_TP void accumulate_pixel(int W, int H, int i, int j, const float *color, const float *variance, const float *motion, const float *prev_color,
-                              const float *prev_variance, const float *prev_depth, const float *prev_len, const Opts &o, float *out_color,
-                              float *out_variance, float *out_len) {
-    const size_t m = (size_t)j * W + i;
-    const float c0 = color[m * 3], c1 = color[m * 3 + 1], c2 = color[m * 3 + 2];
-    const float vc = variance[m];
-    const float *mv = motion + m * 4;
-    float r0 = c0, r1 = c1, r2 = c2, rv = vc, len = 1.0f;
-    Taps t;
-    if (mv[3] > 0.0f && finite_f(c0) && finite_f(c1) && finite_f(c2) &&
-        gather_taps<true>(W, H, i, j, mv, prev_color, prev_variance, prev_depth, prev_len, o, t)) {
-        const float h0 = t.s0 / t.sw, h1 = t.s1 / t.sw, h2 = t.s2 / t.sw;
-        const float n1 = t.nmin + 1.0f;
-        const float N = n1 < o.max_history ? n1 : o.max_history;
-        const float k = 1.0f / N;
-        r0 = h0 + (c0 - h0) * k;
-        r1 = h1 + (c1 - h1) * k;
-        r2 = h2 + (c2 - h2) * k;
-        len = N;
-        const float hv = t.sv / (t.sw * t.sw);
-        const float omk = 1.0f - k;
-        if (finite_f(hv) && hv >= 0.0f) rv = (omk * omk) * hv + (k * k) * vc;
-    }
-    out_color[m * 3] = r0;
-    out_color[m * 3 + 1] = r1;
-    out_color[m * 3 + 2] = r2;
-    out_variance[m] = rv;
-    out_len[m] = len;
+// The length of a history whose shortest used tap has nmin frames (step 5 of the rule): N = min(nmin + 1, max_history).
+MCPT_TP float history_step(float nmin, const Opts &o) {
+    const float n1 = nmin + 1.0f;
+    return n1 < o.max_history ? n1 : o.max_history;
 }
 
 /* One channel of the neighbourhood clamp: the history value h against the mean and deviation of the n finite 3 x 3 neighbours, whose sums
@@ -281,103 +230,139 @@ MCPT_TP float clamp_channel(float h, float s, float s2, float fn, float clamp_k)
     return t > hi ? hi : t;
 }
 
-/* accumulate_pixel with history rejection (include/mcpt.h: mcpt_temporal_accumulate_ex has the rule).  normal: this frame's first-hit
- * normal of pixel m at normal[normal_stride m ..] (3 for a packed array, 8 for the normal channels of an AOV array); prev_normal packed.
- * ho.normal_test 0: neither is read.  out_flags (nullable): bit 0 the normal test skipped a tap, bit 1 the clamp moved the history; 0
- * where the pixel takes no history.  With both switches 0 every output is accumulate_pixel's, expression for expression. */
+// What the rule gives one pixel.  flags: bit 0 the normal test skipped a tap, bit 1 the clamp moved the history.
+struct Pixel {
+    float c0, c1, c2, variance, len;
+    uint8_t flags;
+};
+
+/* The rule at pixel (i, j) of a W x H frame (include/mcpt.h: mcpt_temporal_blend, mcpt_temporal_accumulate[_ex]), once, with compile-time
+ * switches; every entry point and kernel is one of its flavours.  Without a switch it is the blend: the bilinear, depth-validated
+ * reprojection of the previous colour and its running average with the new one; neither variance is read and Pixel::variance is 0.
+ *   kVar   also the variance of the result, from f.variance[m] = v_c, this frame's, and p.variance, the previous result's.  Where the
+ *          pixel takes no history it is v_c; otherwise, over the taps the colour used, in tap order and from 0,
+ *              sv = sv + (w*w) * p.variance[q];  hv = sv / (sw*sw);  k = 1.f / N;  omk = 1.f - k;  variance = (omk*omk)*hv + (k*k)*v_c:
+ *          the variance of hist + (color - hist)*k for independent terms, so a static pixel carries (sum of its frames' variances) / N^2
+ *          after N frames.  An hv that is not finite or is negative (a tap's stored variance was) gives v_c: one frame's variance
+ *          over-estimates, so a filter guided by it smooths more, never less.  A NaN v_c propagates.  Taps and output pixels are treated as
+ *          independent: the covariance bilinear resampling gives neighbours (two outputs that share a tap share its noise) is ignored.
+ *   kNorm  the normal test on every tap (gather_taps); flag bit 0.
+ *   kClamp the history mean clamped to the 3 x 3 neighbourhood of the new frame, neighbours in dy-then-dx order; a pixel whose history
+ *          moved gets flag bit 1 and keeps v_c.
+ * A pixel that takes no history (motion.valid <= 0, a colour that is not finite, no tap left) gets its own colour, v_c, length 1, flags 0. */
+template <bool kVar, bool kNorm, bool kClamp>
+MCPT_TP Pixel reuse_pixel(int W, int H, int i, int j, const Frame &f, const Prev &p, const Opts &o, const HistOpts &ho) {
+    const size_t m = (size_t)j * W + i;
+    const float c0 = f.color[m * 3], c1 = f.color[m * 3 + 1], c2 = f.color[m * 3 + 2];
+    const float vc = kVar ? f.variance[m] : 0.0f;
+    Pixel r = {c0, c1, c2, vc, 1.0f, 0};
+    Taps t;
+    if (f.motion[m * 4 + 3] > 0.0f && finite_f(c0) && finite_f(c1) && finite_f(c2) && gather_taps<kVar, kNorm>(W, H, i, j, f, p, o, ho.normal_min, t)) {
+        float h0 = t.s0 / t.sw, h1 = t.s1 / t.sw, h2 = t.s2 / t.sw;
+        bool clamped = false;
+        if (kNorm && t.nskip) r.flags |= 1;
+        if (kClamp) {
+            float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, b0 = 0.0f, b1 = 0.0f, b2 = 0.0f;
+            int n = 0;
+            for (int dy = -1; dy <= 1; ++dy)
+                for (int dx = -1; dx <= 1; ++dx) {
+                    const int x = i + dx, y = j + dy;
+                    if (x < 0 || x >= W || y < 0 || y >= H) continue;
+                    const size_t q = (size_t)y * W + x;
+                    const float q0 = f.color[q * 3], q1 = f.color[q * 3 + 1], q2 = f.color[q * 3 + 2];
+                    if (!(finite_f(q0) && finite_f(q1) && finite_f(q2))) continue;
+                    a0 = a0 + q0;
+                    a1 = a1 + q1;
+                    a2 = a2 + q2;
+                    b0 = b0 + q0 * q0;
+                    b1 = b1 + q1 * q1;
+                    b2 = b2 + q2 * q2;
+                    ++n;
+                }
+            const float fn = (float)n;  // (n >= 1: the pixel itself is finite)
+            const float a[3] = {a0, a1, a2}, b[3] = {b0, b1, b2};
+            float g[3] = {h0, h1, h2};
+            for (int c = 0; c < 3; ++c) g[c] = clamp_channel(g[c], a[c], b[c], fn, ho.clamp_k);
+            clamped = g[0] != h0 || g[1] != h1 || g[2] != h2;
+            h0 = g[0], h1 = g[1], h2 = g[2];
+            if (clamped) r.flags |= 2;
+        }
+        const float N = history_step(t.nmin, o);
+        const float k = 1.0f / N;
+        r.c0 = h0 + (c0 - h0) * k;
+        r.c1 = h1 + (c1 - h1) * k;
+        r.c2 = h2 + (c2 - h2) * k;
+        r.len = N;
+        if (kVar) {
+            const float hv = t.sv / (t.sw * t.sw);
+            const float omk = 1.0f - k;
+            if (!clamped && finite_f(hv) && hv >= 0.0f) r.variance = (omk * omk) * hv + (k * k) * vc;
+        }
+    }
+    return r;
+}
+
+// The pixel's results into the next set: n.color[3 m ..], n.len[m]; with kVar n.variance[m]; with kFlags n.flags[m] where given.
+template <bool kVar, bool kFlags>
+MCPT_TP void store_pixel(const Next &n, size_t m, const Pixel &r) {
+    n.color[m * 3] = r.c0;
+    n.color[m * 3 + 1] = r.c1;
+    n.color[m * 3 + 2] = r.c2;
+    if (kVar) n.variance[m] = r.variance;
+    n.len[m] = r.len;
+    if (kFlags && n.flags) n.flags[m] = r.flags;
+}
+
+// The blend at pixel (i, j) (mcpt_temporal_blend), stored.
+MCPT_TP void blend_pixel(int W, int H, int i, int j, const Frame &f, const Prev &p, const Opts &o, const Next &n) {
+    store_pixel<false, false>(n, (size_t)j * W + i, reuse_pixel<false, false, false>(W, H, i, j, f, p, o, HistOpts{}));
+}
+
+/* The accumulation with history rejection at pixel (i, j) (mcpt_temporal_accumulate_ex), stored: the flavour ho's switches select.  With
+ * ho.normal_test 0 neither normal array is read; with both switches 0 this is mcpt_temporal_accumulate's rule (flags 0). */
+MCPT_TP void accumulate_pixel_ex(int W, int H, int i, int j, const Frame &f, const Prev &p, const Opts &o, const HistOpts &ho, const Next &n) {
+    const Pixel r = ho.normal_test ? (ho.color_clamp ? reuse_pixel<true, true, true>(W, H, i, j, f, p, o, ho) : reuse_pixel<true, true, false>(W, H, i, j, f, p, o, ho))
+                                   : (ho.color_clamp ? reuse_pixel<true, false, true>(W, H, i, j, f, p, o, ho) : reuse_pixel<true, false, false>(W, H, i, j, f, p, o, ho));
+    store_pixel<true, true>(n, (size_t)j * W + i, r);
+}
+
+/* The history length pixel (i, j) is about to get (include/mcpt.h: mcpt_temporal_history_len): steps 1-4 of the rule and the N of step 5,
+ * with the new colour taken to be finite.  motion.valid <= 0, or no tap left: 1; otherwise history_step.  The taps and their skips are
+ * gather_taps<false, kNorm>'s, the normal test included when ho.normal_test is 1; the colour clamp does not enter, because a clamped
+ * history keeps its length.  So the value equals the length accumulate_pixel / accumulate_pixel_ex give on the same inputs for every pixel
+ * whose new colour is finite, and it is known before the frame is rendered: neither f.color nor f.variance is read. */
+MCPT_TP float history_len_pixel(int W, int H, int i, int j, const Frame &f, const Prev &p, const Opts &o, const HistOpts &ho) {
+    if (!(f.motion[((size_t)j * W + i) * 4 + 3] > 0.0f)) return 1.0f;
+    Taps t;
+    const bool any = ho.normal_test ? gather_taps<false, true>(W, H, i, j, f, p, o, ho.normal_min, t) : gather_taps<false, false>(W, H, i, j, f, p, o, ho.normal_min, t);
+    return any ? history_step(t.nmin, o) : 1.0f;
+}
+
+/* The same four on plain packed arrays, for callers without the structs (the CPU builds of tests/native): color, prev_color 3 floats per
+ * pixel; motion 4; normal at normal[normal_stride m ..], prev_normal packed, both read only with ho.normal_test; out_flags nullable. */
+MCPT_TP void blend_pixel(int W, int H, int i, int j, const float *color, const float *motion, const float *prev_color, const float *prev_depth,
+                         const float *prev_len, const Opts &o, float *out_color, float *out_len) {
+    blend_pixel(W, H, i, j, Frame{color, nullptr, motion, nullptr, 3, nullptr, 1}, Prev{prev_color, nullptr, prev_depth, prev_len, nullptr}, o,
+                Next{out_color, nullptr, nullptr, out_len, nullptr, nullptr});
+}
 MCPT_TP void accumulate_pixel_ex(int W, int H, int i, int j, const float *color, const float *variance, const float *motion, const float *normal,
                                  int normal_stride, const float *prev_color, const float *prev_variance, const float *prev_depth, const float *prev_len,
                                  const float *prev_normal, const Opts &o, const HistOpts &ho, float *out_color, float *out_variance, float *out_len,
                                  uint8_t *out_flags) {
-    const size_t m = (size_t)j * W + i;
-    const float c0 = color[m * 3], c1 = color[m * 3 + 1], c2 = color[m * 3 + 2];
-    const float vc = variance[m];
-    const float *mv = motion + m * 4;
-    float r0 = c0, r1 = c1, r2 = c2, rv = vc, len = 1.0f;
-    uint8_t flags = 0;
-    Taps t;
-    if (mv[3] > 0.0f && finite_f(c0) && finite_f(c1) && finite_f(c2)) {
-        bool any;
-        if (ho.normal_test) {
-            const float n3[3] = {normal[m * (size_t)normal_stride], normal[m * (size_t)normal_stride + 1], normal[m * (size_t)normal_stride + 2]};
-            any = gather_taps<true, true>(W, H, i, j, mv, prev_color, prev_variance, prev_depth, prev_len, o, t, prev_normal, n3, ho.normal_min);
-        } else {
-            any = gather_taps<true>(W, H, i, j, mv, prev_color, prev_variance, prev_depth, prev_len, o, t);
-        }
-        if (any) {
-            float h0 = t.s0 / t.sw, h1 = t.s1 / t.sw, h2 = t.s2 / t.sw;
-            bool clamped = false;
-            if (ho.normal_test && t.nskip) flags |= 1;
-            if (ho.color_clamp) {
-                float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, b0 = 0.0f, b1 = 0.0f, b2 = 0.0f;
-                int n = 0;
-                for (int dy = -1; dy <= 1; ++dy)
-                    for (int dx = -1; dx <= 1; ++dx) {
-                        const int x = i + dx, y = j + dy;
-                        if (x < 0 || x >= W || y < 0 || y >= H) continue;
-                        const size_t q = (size_t)y * W + x;
-                        const float q0 = color[q * 3], q1 = color[q * 3 + 1], q2 = color[q * 3 + 2];
-                        if (!(finite_f(q0) && finite_f(q1) && finite_f(q2))) continue;
-                        a0 = a0 + q0;
-                        a1 = a1 + q1;
-                        a2 = a2 + q2;
-                        b0 = b0 + q0 * q0;
-                        b1 = b1 + q1 * q1;
-                        b2 = b2 + q2 * q2;
-                        ++n;
-                    }
-                const float fn = (float)n;  // (n >= 1: the pixel itself is finite)
-                const float g0 = clamp_channel(h0, a0, b0, fn, ho.clamp_k);
-                const float g1 = clamp_channel(h1, a1, b1, fn, ho.clamp_k);
-                const float g2 = clamp_channel(h2, a2, b2, fn, ho.clamp_k);
-                clamped = g0 != h0 || g1 != h1 || g2 != h2;
-                h0 = g0;
-                h1 = g1;
-                h2 = g2;
-                if (clamped) flags |= 2;
-            }
-            const float n1 = t.nmin + 1.0f;
-            const float N = n1 < o.max_history ? n1 : o.max_history;
-            const float k = 1.0f / N;
-            r0 = h0 + (c0 - h0) * k;
-            r1 = h1 + (c1 - h1) * k;
-            r2 = h2 + (c2 - h2) * k;
-            len = N;
-            const float hv = t.sv / (t.sw * t.sw);
-            const float omk = 1.0f - k;
-            if (!clamped && finite_f(hv) && hv >= 0.0f) rv = (omk * omk) * hv + (k * k) * vc;
-        }
-    }
-    out_color[m * 3] = r0;
-    out_color[m * 3 + 1] = r1;
-    out_color[m * 3 + 2] = r2;
-    out_variance[m] = rv;
-    out_len[m] = len;
-    if (out_flags) out_flags[m] = flags;
+    accumulate_pixel_ex(W, H, i, j, Frame{color, variance, motion, normal, normal_stride, nullptr, 1},
+                        Prev{prev_color, prev_variance, prev_depth, prev_len, prev_normal}, o, ho,
+                        Next{out_color, out_variance, nullptr, out_len, nullptr, out_flags});
 }
-
-/* The history length pixel (i, j) is about to get (include/mcpt.h: mcpt_temporal_history_len): steps 1-4 of the blend and the N of step 5,
- * with the new colour taken to be finite.  motion.valid <= 0, or no tap left: 1; otherwise N = min(nmin + 1, max_history).  The taps and
- * their skips are gather_taps<false, kNorm>'s, the normal test included when ho.normal_test is 1 (normal at normal[normal_stride m ..], as
- * in accumulate_pixel_ex); the colour clamp does not enter, because a clamped history keeps its length.  So the value equals the out_len of
- * accumulate_pixel / accumulate_pixel_ex on the same inputs for every pixel whose new colour is finite, and it is known before the frame
- * is rendered: neither `color` nor `variance` is read. */
+MCPT_TP void accumulate_pixel(int W, int H, int i, int j, const float *color, const float *variance, const float *motion, const float *prev_color,
+                              const float *prev_variance, const float *prev_depth, const float *prev_len, const Opts &o, float *out_color,
+                              float *out_variance, float *out_len) {
+    accumulate_pixel_ex(W, H, i, j, color, variance, motion, nullptr, 3, prev_color, prev_variance, prev_depth, prev_len, nullptr, o, HistOpts{}, out_color,
+                        out_variance, out_len, nullptr);
+}
 MCPT_TP float history_len_pixel(int W, int H, int i, int j, const float *motion, const float *normal, int normal_stride, const float *prev_color,
                                 const float *prev_depth, const float *prev_len, const float *prev_normal, const Opts &o, const HistOpts &ho) {
-    const size_t m = (size_t)j * W + i;
-    const float *mv = motion + m * 4;
-    if (!(mv[3] > 0.0f)) return 1.0f;
-    Taps t;
-    bool any;
-    if (ho.normal_test) {
-        const float n3[3] = {normal[m * (size_t)normal_stride], normal[m * (size_t)normal_stride + 1], normal[m * (size_t)normal_stride + 2]};
-        any = gather_taps<false, true>(W, H, i, j, mv, prev_color, nullptr, prev_depth, prev_len, o, t, prev_normal, n3, ho.normal_min);
-    } else {
-        any = gather_taps<false>(W, H, i, j, mv, prev_color, nullptr, prev_depth, prev_len, o, t);
-    }
-    if (!any) return 1.0f;
-    const float n1 = t.nmin + 1.0f;
-    return n1 < o.max_history ? n1 : o.max_history;
+    return history_len_pixel(W, H, i, j, Frame{nullptr, nullptr, motion, normal, normal_stride, nullptr, 1},
+                             Prev{prev_color, nullptr, prev_depth, prev_len, prev_normal}, o, ho);
 }
 
 /* The stopping threshold of a guided adaptive pixel (include/mcpt.h: mcpt_render_adaptive_guided): threshold * sqrt(g) in double, with
@@ -403,26 +388,17 @@ void launch_motion_resolve(const DevScene &S, const TriGeom *prev_tri, const Sph
                            const float4 *ray_o, const float4 *ray_d, const uint4 *hit, float4 *rec, hipStream_t st);
 // ... folded in sample order into motion[4 (p0 + i) ...] for the chunk's n_pix pixels
 void launch_motion_fold(uint32_t p0, uint32_t n_pix, int32_t spp, const float4 *rec, float *motion, hipStream_t st);
-// The blend of a W x H frame
-void launch_temporal_blend(int W, int H, const tp::Opts &o, const float *color, const float *motion, const float *prev_color, const float *prev_depth,
-                           const float *prev_len, float *out_color, float *out_len, hipStream_t st);
-// The blend with variance of a W x H frame.  depth != nullptr: out_depth[m] = depth[depth_stride * m] as well (the frame's first-hit depth
-// into the history's depth plane: depth points at the depth channel of an AOV array, depth_stride 8).
-void launch_temporal_accumulate(int W, int H, const tp::Opts &o, const float *color, const float *variance, const float *motion, const float *prev_color,
-                                const float *prev_variance, const float *prev_depth, const float *prev_len, const float *depth, int depth_stride,
-                                float *out_color, float *out_variance, float *out_depth, float *out_len, hipStream_t st);
-// The blend with variance and history rejection of a W x H frame (k_temporal_accumulate_ex; at least one switch of ho is on).  normal: this
-// frame's first-hit normals, normal_stride floats from pixel to pixel (3 packed, 8 inside an AOV array); read only with ho.normal_test, as
-// prev_normal (packed).  out_normal != nullptr: the pixel's normal is also copied there (packed: the history's normal plane), as depth is
-// into out_depth.  out_flags: one byte per pixel, nullable.
-void launch_temporal_accumulate_ex(int W, int H, const tp::Opts &o, const tp::HistOpts &ho, const float *color, const float *variance, const float *motion,
-                                   const float *normal, int normal_stride, const float *prev_color, const float *prev_variance, const float *prev_depth,
-                                   const float *prev_len, const float *prev_normal, const float *depth, int depth_stride, float *out_color,
-                                   float *out_variance, float *out_depth, float *out_len, float *out_normal, uint8_t *out_flags, hipStream_t st);
-// The history length every pixel of a W x H frame is about to get (k_history_len: tp::history_len_pixel) into len[m]; normal / prev_normal
-// as for launch_temporal_accumulate_ex, read only with ho.normal_test (ho with both switches 0: the lengths of launch_temporal_accumulate).
-void launch_history_len(int W, int H, const tp::Opts &o, const tp::HistOpts &ho, const float *motion, const float *normal, int normal_stride,
-                        const float *prev_color, const float *prev_depth, const float *prev_len, const float *prev_normal, float *len, hipStream_t st);
+// The rule over a W x H frame, 16 x 16 pixels per block (tp::Frame, tp::Prev and tp::Next say what each flavour reads and writes).
+// The blend (k_temporal_blend)
+void launch_temporal_blend(int W, int H, const tp::Opts &o, const tp::Frame &f, const tp::Prev &p, const tp::Next &n, hipStream_t st);
+// The accumulation (k_temporal_accumulate<kNorm, kClamp>, the instantiation ho's switches select; both 0: mcpt_temporal_accumulate's).  It
+// also leaves the next history set complete: f.depth != nullptr: n.depth[m] = the frame's first-hit depth; with ho.normal_test and n.normal
+// != nullptr: n.normal[3 m ..] = the frame's first-hit normal.  n.flags is written with a switch on only (with both 0 every flag is 0, and
+// the plain instantiation has no store for it).
+void launch_temporal_accumulate(int W, int H, const tp::Opts &o, const tp::HistOpts &ho, const tp::Frame &f, const tp::Prev &p, const tp::Next &n,
+                                hipStream_t st);
+// The history length every pixel is about to get (k_history_len: tp::history_len_pixel) into len[m]
+void launch_history_len(int W, int H, const tp::Opts &o, const tp::HistOpts &ho, const tp::Frame &f, const tp::Prev &p, float *len, hipStream_t st);
 }  // namespace mcpt
 #endif
 #endif  // MCPT_TEMPORAL_H

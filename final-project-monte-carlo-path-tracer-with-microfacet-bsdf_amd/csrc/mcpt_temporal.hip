@@ -5,23 +5,22 @@
 //   k_motion_resolve  hit -> per-sample record {dx, dy, prev_depth, valid}: the hit point rebuilt on the live primitive and on the
 //                     snapshot's, both projected
 //   k_motion_fold     one lane per pixel: the samples folded in sample order into the 4-float motion record
-// Blend:
-//   k_temporal_blend  16 x 16 pixel blocks, one pixel per lane; a wave covers four rows of 16 pixels, so its loads of the pixel's own
-//                     colour, motion and its stores are four contiguous runs; up to four taps of the previous frame per lane, no LDS
-//                     (neighbouring lanes' taps are neighbouring pixels: the cache lines are shared in L1 / L2)
-// Accumulate (mcpt_temporal_accumulate, mcpt_sequence_frame):
-//   k_temporal_accumulate  the same shape; the blend with the variance of its result (tp::accumulate_pixel), and the frame's first-hit
-//                     depth copied into the history's depth plane, so that one launch leaves the history complete for the next frame
-// Accumulate with history rejection (mcpt_temporal_accumulate_ex, a sequence created with mcpt_sequence_create_ex):
-//   k_temporal_accumulate_ex  the same shape again; tp::accumulate_pixel_ex adds the normal test on every tap and the clamp of the history
-//                     to the 3 x 3 neighbourhood of the new frame.  The nine neighbours are read straight from global memory: a lane's row
-//                     neighbours are its wave neighbours' own pixels, so the 36-byte runs overlap in L1 (a 16 x 16 tile touches 18 x 18
-//                     pixels, 1.27 x its own colour bytes); an LDS tile with a halo would add a barrier and a second pass over the halo
-//                     to save loads that already hit.  It also copies the frame's first-hit normal into the history's normal plane and
-//                     writes the flags byte, both with plain vector stores.
-// Guide of an adaptive sequence (mcpt_temporal_history_len, a sequence created with mcpt_sequence_create_adaptive, guided 1):
-//   k_history_len     the same shape; tp::history_len_pixel: the taps and skips of the blend without its colour, so the length a pixel is
-//                     about to get is known before the frame is rendered.  One plain vector store per lane.
+// The pixel rule (tp::reuse_pixel, once, with compile-time switches) over a frame: 16 x 16 pixel blocks, one pixel per lane; a wave covers
+// four rows of 16 pixels, so its loads of the pixel's own colour, motion and its stores are four contiguous runs; up to four taps of the
+// previous frame per lane, no LDS (neighbouring lanes' taps are neighbouring pixels: the cache lines are shared in L1 / L2).  Three kernels
+// of that shape, every store a plain vector store:
+//   k_temporal_blend  the blend (mcpt_temporal_blend)
+//   k_temporal_accumulate<kNorm, kClamp>  the blend with the variance of its result (mcpt_temporal_accumulate[_ex], mcpt_sequence_frame):
+//                     four instantiations over the two switches of history rejection, picked by the launcher, so no lane branches on a
+//                     switch.  <false, false> is the plain accumulation; kNorm adds the normal test on every tap, kClamp the clamp of the
+//                     history to the 3 x 3 neighbourhood of the new frame.  The nine neighbours are read straight from global memory: a
+//                     lane's row neighbours are its wave neighbours' own pixels, so the 36-byte runs overlap in L1 (a 16 x 16 tile touches
+//                     18 x 18 pixels, 1.27 x its own colour bytes); an LDS tile with a halo would add a barrier and a second pass over the
+//                     halo to save loads that already hit.  Every instantiation copies the frame's first-hit depth into the next history
+//                     set, and kNorm the first-hit normal where that set has a normal plane, so that one launch leaves the history
+//                     complete for the next frame; with a switch on it writes the flags byte where there is a flags plane.
+//   k_history_len     the guide of an adaptive sequence (mcpt_temporal_history_len, mcpt_sequence_create_adaptive with guided 1):
+//                     tp::history_len_pixel, the taps and skips of the rule without its colour, known before the frame is rendered.
 #include <hip/hip_runtime.h>
 
 #include "mcpt_temporal.h"
@@ -81,56 +80,33 @@ __global__ __launch_bounds__(kB) void k_motion_fold(uint32_t p0, uint32_t n_pix,
     reinterpret_cast<float4 *>(motion)[p0 + i] = make_float4(out[0], out[1], out[2], out[3]);
 }
 
-__global__ __launch_bounds__(kTile *kTile) void k_temporal_blend(int W, int H, tp::Opts o, const float *__restrict__ color, const float *__restrict__ motion,
-                                                                const float *__restrict__ prev_color, const float *__restrict__ prev_depth,
-                                                                const float *__restrict__ prev_len, float *__restrict__ out_color,
-                                                                float *__restrict__ out_len) {
+__global__ __launch_bounds__(kTile *kTile) void k_temporal_blend(int W, int H, tp::Opts o, tp::Frame f, tp::Prev p, tp::Next n) {
     const int x = blockIdx.x * kTile + threadIdx.x, y = blockIdx.y * kTile + threadIdx.y;
     if (x >= W || y >= H) return;
-    tp::blend_pixel(W, H, x, y, color, motion, prev_color, prev_depth, prev_len, o, out_color, out_len);
+    tp::blend_pixel(W, H, x, y, f, p, o, n);
 }
 
-__global__ __launch_bounds__(kTile *kTile) void k_temporal_accumulate(int W, int H, tp::Opts o, const float *__restrict__ color, const float *__restrict__ variance,
-                                                                     const float *__restrict__ motion, const float *__restrict__ prev_color,
-                                                                     const float *__restrict__ prev_variance, const float *__restrict__ prev_depth,
-                                                                     const float *__restrict__ prev_len, const float *__restrict__ depth, int depth_stride,
-                                                                     float *__restrict__ out_color, float *__restrict__ out_variance,
-                                                                     float *__restrict__ out_depth, float *__restrict__ out_len) {
+template <bool kNorm, bool kClamp>
+__global__ __launch_bounds__(kTile *kTile) void k_temporal_accumulate(int W, int H, tp::Opts o, tp::HistOpts ho, tp::Frame f, tp::Prev p, tp::Next n) {
     const int x = blockIdx.x * kTile + threadIdx.x, y = blockIdx.y * kTile + threadIdx.y;
     if (x >= W || y >= H) return;
-    tp::accumulate_pixel(W, H, x, y, color, variance, motion, prev_color, prev_variance, prev_depth, prev_len, o, out_color, out_variance, out_len);
     const size_t m = (size_t)y * W + x;
-    if (depth) out_depth[m] = depth[m * (size_t)depth_stride];
-}
-
-__global__ __launch_bounds__(kTile *kTile) void k_temporal_accumulate_ex(
-    int W, int H, tp::Opts o, tp::HistOpts ho, const float *__restrict__ color, const float *__restrict__ variance, const float *__restrict__ motion,
-    const float *__restrict__ normal, int normal_stride, const float *__restrict__ prev_color, const float *__restrict__ prev_variance,
-    const float *__restrict__ prev_depth, const float *__restrict__ prev_len, const float *__restrict__ prev_normal, const float *__restrict__ depth,
-    int depth_stride, float *__restrict__ out_color, float *__restrict__ out_variance, float *__restrict__ out_depth, float *__restrict__ out_len,
-    float *__restrict__ out_normal, uint8_t *__restrict__ out_flags) {
-    const int x = blockIdx.x * kTile + threadIdx.x, y = blockIdx.y * kTile + threadIdx.y;
-    if (x >= W || y >= H) return;
-    tp::accumulate_pixel_ex(W, H, x, y, color, variance, motion, normal, normal_stride, prev_color, prev_variance, prev_depth, prev_len, prev_normal, o, ho,
-                            out_color, out_variance, out_len, out_flags);
-    const size_t m = (size_t)y * W + x;
-    if (depth) out_depth[m] = depth[m * (size_t)depth_stride];
-    if (out_normal) {
-        const float *n = normal + m * (size_t)normal_stride;
-        out_normal[m * 3] = n[0];
-        out_normal[m * 3 + 1] = n[1];
-        out_normal[m * 3 + 2] = n[2];
+    tp::store_pixel<true, kNorm || kClamp>(n, m, tp::reuse_pixel<true, kNorm, kClamp>(W, H, x, y, f, p, o, ho));
+    if (f.depth) n.depth[m] = f.depth[m * (size_t)f.depth_stride];
+    if (kNorm && n.normal) {  // (nothing reads the normals without the normal test; three loads, then three stores: one round trip)
+        const float *fn = f.normal + m * (size_t)f.normal_stride;
+        const float n0 = fn[0], n1 = fn[1], n2 = fn[2];
+        n.normal[m * 3] = n0, n.normal[m * 3 + 1] = n1, n.normal[m * 3 + 2] = n2;
     }
 }
 
-__global__ __launch_bounds__(kTile *kTile) void k_history_len(int W, int H, tp::Opts o, tp::HistOpts ho, const float *__restrict__ motion,
-                                                              const float *__restrict__ normal, int normal_stride, const float *__restrict__ prev_color,
-                                                              const float *__restrict__ prev_depth, const float *__restrict__ prev_len,
-                                                              const float *__restrict__ prev_normal, float *__restrict__ len) {
+__global__ __launch_bounds__(kTile *kTile) void k_history_len(int W, int H, tp::Opts o, tp::HistOpts ho, tp::Frame f, tp::Prev p, float *__restrict__ len) {
     const int x = blockIdx.x * kTile + threadIdx.x, y = blockIdx.y * kTile + threadIdx.y;
     if (x >= W || y >= H) return;
-    len[(size_t)y * W + x] = tp::history_len_pixel(W, H, x, y, motion, normal, normal_stride, prev_color, prev_depth, prev_len, prev_normal, o, ho);
+    len[(size_t)y * W + x] = tp::history_len_pixel(W, H, x, y, f, p, o, ho);
 }
+
+inline dim3 tiles(int W, int H) { return dim3((W + kTile - 1) / kTile, (H + kTile - 1) / kTile); }
 
 }  // namespace
 
@@ -145,33 +121,19 @@ void launch_motion_fold(uint32_t p0, uint32_t n_pix, int32_t spp, const float4 *
     hipLaunchKernelGGL(k_motion_fold, dim3(nblocks(n_pix)), dim3(kB), 0, st, p0, n_pix, spp, rec, motion);
 }
 
-void launch_temporal_blend(int W, int H, const tp::Opts &o, const float *color, const float *motion, const float *prev_color, const float *prev_depth,
-                           const float *prev_len, float *out_color, float *out_len, hipStream_t st) {
-    const dim3 grid((W + kTile - 1) / kTile, (H + kTile - 1) / kTile), blk(kTile, kTile);
-    hipLaunchKernelGGL(k_temporal_blend, grid, blk, 0, st, W, H, o, color, motion, prev_color, prev_depth, prev_len, out_color, out_len);
+void launch_temporal_blend(int W, int H, const tp::Opts &o, const tp::Frame &f, const tp::Prev &p, const tp::Next &n, hipStream_t st) {
+    hipLaunchKernelGGL(k_temporal_blend, tiles(W, H), dim3(kTile, kTile), 0, st, W, H, o, f, p, n);
 }
 
-void launch_temporal_accumulate(int W, int H, const tp::Opts &o, const float *color, const float *variance, const float *motion, const float *prev_color,
-                                const float *prev_variance, const float *prev_depth, const float *prev_len, const float *depth, int depth_stride,
-                                float *out_color, float *out_variance, float *out_depth, float *out_len, hipStream_t st) {
-    const dim3 grid((W + kTile - 1) / kTile, (H + kTile - 1) / kTile), blk(kTile, kTile);
-    hipLaunchKernelGGL(k_temporal_accumulate, grid, blk, 0, st, W, H, o, color, variance, motion, prev_color, prev_variance, prev_depth, prev_len, depth,
-                       depth_stride, out_color, out_variance, out_depth, out_len);
+void launch_temporal_accumulate(int W, int H, const tp::Opts &o, const tp::HistOpts &ho, const tp::Frame &f, const tp::Prev &p, const tp::Next &n,
+                                hipStream_t st) {
+    const auto k = ho.normal_test ? (ho.color_clamp ? k_temporal_accumulate<true, true> : k_temporal_accumulate<true, false>)
+                                  : (ho.color_clamp ? k_temporal_accumulate<false, true> : k_temporal_accumulate<false, false>);
+    hipLaunchKernelGGL(k, tiles(W, H), dim3(kTile, kTile), 0, st, W, H, o, ho, f, p, n);
 }
 
-void launch_temporal_accumulate_ex(int W, int H, const tp::Opts &o, const tp::HistOpts &ho, const float *color, const float *variance, const float *motion,
-                                   const float *normal, int normal_stride, const float *prev_color, const float *prev_variance, const float *prev_depth,
-                                   const float *prev_len, const float *prev_normal, const float *depth, int depth_stride, float *out_color,
-                                   float *out_variance, float *out_depth, float *out_len, float *out_normal, uint8_t *out_flags, hipStream_t st) {
-    const dim3 grid((W + kTile - 1) / kTile, (H + kTile - 1) / kTile), blk(kTile, kTile);
-    hipLaunchKernelGGL(k_temporal_accumulate_ex, grid, blk, 0, st, W, H, o, ho, color, variance, motion, normal, normal_stride, prev_color, prev_variance,
-                       prev_depth, prev_len, prev_normal, depth, depth_stride, out_color, out_variance, out_depth, out_len, out_normal, out_flags);
-}
-
-void launch_history_len(int W, int H, const tp::Opts &o, const tp::HistOpts &ho, const float *motion, const float *normal, int normal_stride,
-                        const float *prev_color, const float *prev_depth, const float *prev_len, const float *prev_normal, float *len, hipStream_t st) {
-    const dim3 grid((W + kTile - 1) / kTile, (H + kTile - 1) / kTile), blk(kTile, kTile);
-    hipLaunchKernelGGL(k_history_len, grid, blk, 0, st, W, H, o, ho, motion, normal, normal_stride, prev_color, prev_depth, prev_len, prev_normal, len);
+void launch_history_len(int W, int H, const tp::Opts &o, const tp::HistOpts &ho, const tp::Frame &f, const tp::Prev &p, float *len, hipStream_t st) {
+    hipLaunchKernelGGL(k_history_len, tiles(W, H), dim3(kTile, kTile), 0, st, W, H, o, ho, f, p, len);
 }
 
 }  // namespace mcpt

@@ -1,6 +1,6 @@
 // CPU build of the accumulation with history rejection (csrc/mcpt_temporal.h: tp::accumulate_pixel_ex), for tests/test_history_cpu.py and
 // tests/test_gpu_history.py.  Compiled into a shared library with g++ -std=c++17 -O2 -ffp-contract=off; the frame loop mirrors
-// k_temporal_accumulate_ex (csrc/mcpt_temporal.hip), every pixel through the same header function as the kernel.  tp_accumulate_plain is
+// k_temporal_accumulate (csrc/mcpt_temporal.hip), every pixel through the same header function as the kernel.  tp_accumulate_plain is
 // tp::accumulate_pixel, what the _ex function must equal with both switches off.
 #include <cstddef>
 

@@ -1,5 +1,5 @@
 """History rejection on the GPU (include/mcpt.h: mcpt_temporal_accumulate_ex, mcpt_sequence_create_ex, mcpt_sequence_flags):
-k_temporal_accumulate_ex gives the bits of the CPU build of tp::accumulate_pixel_ex, flags included; with zeroed options the call is
+every instantiation of k_temporal_accumulate gives the bits of the CPU build of tp::accumulate_pixel_ex, flags included; with zeroed options the call is
 mcpt_temporal_accumulate; a sequence with both switches on is the composition of the separate calls, bit for bit, and one with zeroed
 options is a plain sequence; a failed frame leaves history, normals and flags alone; after the light has moved the clamp brings the
 accumulated frame closer to the new lighting than the parent's blend does; and on a scene that never moves it costs no more than twice the

@@ -54,7 +54,7 @@ def test_accumulate_device_equals_host_build(hip, tiny, driver, kind, shape):
 
 
 # ---------------------------------------------------------------- 2. the sequence is the composition of the calls we already have
-@pytest.mark.parametrize("size", [8, 64])
+@pytest.mark.parametrize("size", [8, 17, 64])
 @pytest.mark.parametrize("builder", ["sah", "ploc"])
 def test_sequence_is_the_composition_of_the_calls(pkg, hip, builder, size):
     """Six frames, the short box moved by translate(-32 k, 0, 0) before frame k.  With the host builder the separate calls run on a second

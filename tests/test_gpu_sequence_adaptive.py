@@ -31,7 +31,7 @@ def _threshold(hs, q=0.5):
 @pytest.mark.parametrize("reject", [False, True])
 @pytest.mark.parametrize("guided", [0, 1])
 @pytest.mark.parametrize("builder", ["sah", "ploc"])
-@pytest.mark.parametrize("size", [8, 64])
+@pytest.mark.parametrize("size", [8, 17, 64])
 def test_adaptive_sequence_is_the_composition_of_the_calls(pkg, hip, size, builder, guided, reject):
     """Six frames, the short box moved by translate(-32 k, 0, 0) before frame k, as test_gpu_sequence does: with the host builder the
     separate calls run on a second handle, with PLOC on the sequence's own handle before its frame."""
