@@ -16,6 +16,7 @@
 //   k_dn_variance_map  the same from each pixel's own sample count (an adaptive frame: mcpt_render_adaptive_guided)
 #include <hip/hip_runtime.h>
 
+#include "mcpt_chain.h"
 #include "mcpt_denoise.h"
 
 namespace mcpt {
@@ -81,8 +82,6 @@ __global__ __launch_bounds__(kB) void k_aov_resolve(DevScene S, uint32_t n, cons
     s1[j] = make_float4(nrm.x, nrm.y, nrm.z, 1.f);
 }
 
-MCPT_DI uint32_t lane_id() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
-
 // One step of the specular chains (include/mcpt.h: mcpt_render_aovs_ex) for the n rays of a list whose samples have all followed b bounces:
 // ray i belongs to sample j with throughput thr and summed distance tsum (chain_in / tsum_in; nullptr for the camera rays: j = i, thr = 1,
 // tsum = 0).  A sample that stops writes its per-sample record s0[j], s1[j] as k_aov_resolve does; one that follows a Dirac bounce
@@ -141,14 +140,10 @@ __global__ __launch_bounds__(kB) void k_aov_chain(DevScene S, uint32_t n, int32_
             const MaterialRec &M = S.mats[mat_bits & kMatIndexMask];
             const bool emitter = (mat_bits >> 31) != 0;
             const bool conductor = M.type == MCPT_SMOOTH_CONDUCTOR || M.type == MCPT_ROUGH_CONDUCTOR;
-            cont = b < max_b && M.isDirac && !emitter;
-            if (cont) {  // k_shade's vertex (Scene.cpp:109-159) with mfn = n, channel 1, the more likely branch
+            cont = chain_continues(M, mat_bits, b, max_b);
+            if (cont) {  // the bounce both chain passes take (csrc/mcpt_chain.h)
                 const f3 wo = -rd;
-                const float kr = mat_fresnel(M, rd, nrm, 1);
-                const bool isReflect = kr > 0.5f;
-                if (isReflect) p2 = (dot(wo, nrm) < 0) ? (p - nrm * kEps) : (p + nrm * kEps);
-                else p2 = (dot(wo, nrm) < 0) ? (p + nrm * kEps) : (p - nrm * kEps);
-                wi = isReflect ? mat_reflect(wo, nrm) : mat_refract(M, rd, nrm, 1);
+                chain_bounce(M, rd, p, nrm, p2, wi);
                 if (conductor)
                     for (int c = 0; c < 3; ++c) thr[c] *= mat_eval(M, wi, wo, nrm, c, uv, true);
             } else {

@@ -1,5 +1,5 @@
 // The frame-level entry points of the C ABI (include/mcpt.h): mcpt_render / mcpt_render_device, mcpt_render_adaptive[_guided | _denoised], mcpt_render_aovs[_ex],
-// mcpt_denoise, mcpt_render_denoised and mcpt_render_motion.  What they share -- the checks of (camera, params), the start of a call, its statistics -- is
+// mcpt_denoise, mcpt_render_denoised and mcpt_render_motion[_ex].  What they share -- the checks of (camera, params), the start of a call, its statistics -- is
 // here once; each entry point is the part that differs.  csrc/mcpt_frame.h declares what csrc/mcpt_sequence.hip uses of it.
 #include <cmath>
 #include <cstdio>
@@ -68,7 +68,8 @@ void mcpt::fill_stats(mcpt_stats *stats, uint64_t samples, uint64_t traced_prima
 
 namespace {
 
-constexpr uint32_t kAovChunkRays = 4u << 20;  // at most this many rays per chunk of the AOV pass
+constexpr uint32_t kAovChunkRays = 4u << 20;   // at most this many rays per chunk of the AOV pass
+constexpr uint32_t kMotionMapRays = 1u << 20;  // ... and of the motion pass with specular chains: 96 bytes of maps per ray, 96 MiB
 
 int render_impl(mcpt_scene *sc, const mcpt_camera *cam, const mcpt_params *pp, float *fb_dev, hipStream_t st, mcpt_stats *stats) {
     if (!sc || !cam || !pp || !fb_dev) return fail(MCPT_ERR_ARG, "mcpt_render: null argument");
@@ -165,10 +166,11 @@ struct AovOwn {
 // yet on this scene) it uses buffers of its own for the call.  `chain`: the second ray list and the chain states of the specular chains
 // are needed too (in the workspace: vtx0 / vtx1 with wave 1's hits, wave 0's and wave 1's rec1, the sums in wave 0's rec0 and vtx2, the
 // count vtx_j[0]; chunks then hold at most `pool` rays).
+// max_rays > 0: no chunk holds more rays than that (at least aov_spp: the motion pass's map storage, motion_pass).
 template <class Resolve>
-int first_hit_chunks(mcpt_scene *sc, const CameraConst &cc, uint32_t seed, int32_t aov_spp, bool chain, hipStream_t st, Resolve &&resolve) {
+int first_hit_chunks(mcpt_scene *sc, const CameraConst &cc, uint32_t seed, int32_t aov_spp, bool chain, uint64_t max_rays, hipStream_t st, Resolve &&resolve) {
     const uint32_t n_px = (uint32_t)cc.width * (uint32_t)cc.height;
-    const uint64_t need = std::min<uint64_t>(kAovChunkRays, (uint64_t)n_px * aov_spp);
+    const uint64_t need = std::min<uint64_t>(max_rays ? std::min<uint64_t>(kAovChunkRays, max_rays) : kAovChunkRays, (uint64_t)n_px * aov_spp);
     Workspace &w = sc->pools[0].ws;
     // rays that fit: the ray arrays (ray_cap entries) and, for the keys, two uint32 per ray in wave 1's rec0 (4 per entry); the chains use
     // arrays of `pool` entries too
@@ -200,7 +202,7 @@ int first_hit_chunks(mcpt_scene *sc, const CameraConst &cc, uint32_t seed, int32
 // the compacted list of the samples that continue (its length read back once per bounce) -- and k_aov_fold.
 int mcpt::aov_pass(mcpt_scene *sc, const CameraConst &cc, uint32_t seed, int32_t aov_spp, int32_t spec_depth, float *aov_dev, hipStream_t st) {
     const bool chain = spec_depth > 0;
-    return first_hit_chunks(sc, cc, seed, aov_spp, chain, st, [&](const AovPtrs &a, uint32_t p0, uint32_t np, uint32_t n) -> int {
+    return first_hit_chunks(sc, cc, seed, aov_spp, chain, 0, st, [&](const AovPtrs &a, uint32_t p0, uint32_t np, uint32_t n) -> int {
         if (!chain) {
             launch_aov_resolve(sc->view, n, a.list_o[0], a.list_d[0], a.list_hit[0], a.rec0, a.rec1, st);
         } else {
@@ -238,18 +240,54 @@ tp::Cam motion_camera(const CameraConst &cc) {
 
 }  // namespace
 
-// The motion pass (include/mcpt.h: mcpt_render_motion): motion_dev[4m ..] for every pixel of the frame, from the rays and hits of the AOV
+uint64_t mcpt::motion_map_rays(uint64_t n_px, int32_t aov_spp) { return std::min<uint64_t>(kMotionMapRays, n_px * (uint64_t)aov_spp); }
+
+// The motion pass (include/mcpt.h: mcpt_render_motion[_ex]): motion_dev[4m ..] for every pixel of the frame, from the rays and hits of the AOV
 // pass.  Per chunk k_motion_resolve and k_motion_fold (csrc/mcpt_temporal.hip); prev_tri / prev_sph are the snapshot's arrays, or the live
-// ones for a scene without a snapshot.
-int mcpt::motion_pass(mcpt_scene *sc, const CameraConst &cc, const CameraConst &prev_cc, uint32_t seed, int32_t aov_spp, float *motion_dev, hipStream_t st) {
+// ones for a scene without a snapshot.  With spec_depth > 0 the specular chains: the bounce loop of aov_pass with k_motion_chain in
+// k_aov_chain's place, on the arrays of aov_in_workspace(.., chain = true) or AovOwn of which it uses the two ray lists with their hits,
+// chain_st[0 / 1] for {reflections, sample} of each list entry, rec0 for the records and n_next (chain_t and rec1 stay unused).  The maps,
+// 96 bytes per sample of a chunk, are aliased to nothing: they live in `maps` (room for map_rays samples, at least aov_spp: a sequence's,
+// allocated at its creation) or, with maps null, in a buffer of the call's own, freed after the stream has drained; either way outside the
+// workspace, so no array of aov_in_workspace -- wave 0 / 1 ray_o, ray_d, hit, rec0, rec1, vtx0, vtx1, vtx2, vtx_j -- can overlap them.
+// A chunk holds at most motion_map_rays(..) rays so that the storage stays below 96 MiB whatever the frame.
+int mcpt::motion_pass(mcpt_scene *sc, const CameraConst &cc, const CameraConst &prev_cc, uint32_t seed, int32_t aov_spp, int32_t spec_depth, float4 *maps,
+                      uint64_t map_rays, float *motion_dev, hipStream_t st) {
     const tp::Cam cur = motion_camera(cc), prev = motion_camera(prev_cc);
     const TriGeom *prev_tri = sc->has_snapshot ? sc->snap_tri.p : sc->view.tri_geom;
     const SphereRec *prev_sph = sc->has_snapshot ? sc->snap_sph.p : sc->view.spheres;
-    return first_hit_chunks(sc, cc, seed, aov_spp, false, st, [&](const AovPtrs &a, uint32_t p0, uint32_t np, uint32_t n) -> int {
-        launch_motion_resolve(sc->view, prev_tri, prev_sph, cur, prev, n, a.list_o[0], a.list_d[0], a.list_hit[0], a.rec0, st);
+    if (spec_depth == 0)
+        return first_hit_chunks(sc, cc, seed, aov_spp, false, 0, st, [&](const AovPtrs &a, uint32_t p0, uint32_t np, uint32_t n) -> int {
+            launch_motion_resolve(sc->view, prev_tri, prev_sph, cur, prev, n, a.list_o[0], a.list_d[0], a.list_hit[0], a.rec0, st);
+            launch_motion_fold(p0, np, aov_spp, a.rec0, motion_dev, st);
+            return MCPT_OK;
+        });
+    DevBuf<float4> own;
+    if (!maps) {
+        map_rays = motion_map_rays((uint64_t)cc.width * cc.height, aov_spp);
+        HIP_TRY(own.alloc(map_rays * 6));
+        maps = own.p;
+    }
+    if (map_rays < (uint64_t)aov_spp) return fail(MCPT_ERR_ARG, "motion pass: the map storage holds less than one pixel's samples");
+    const int rc = first_hit_chunks(sc, cc, seed, aov_spp, true, map_rays, st, [&](const AovPtrs &a, uint32_t p0, uint32_t np, uint32_t n) -> int {
+        uint32_t m = n;  // rays in list `lc`, whose samples have all followed b bounces
+        for (int b = 0, lc = 0;; ++b, lc ^= 1) {
+            if (b < spec_depth) HIP_TRY(hipMemsetAsync(a.n_next, 0, sizeof(uint32_t), st));
+            launch_motion_chain(sc->view, prev_tri, prev_sph, cur, prev, m, b, spec_depth, a.list_o[lc], a.list_d[lc], a.list_hit[lc],
+                                b == 0 ? nullptr : a.chain_st[lc], a.rec0, maps, (size_t)map_rays, a.list_o[lc ^ 1], a.list_d[lc ^ 1], a.chain_st[lc ^ 1],
+                                a.n_next, st);
+            if (b == spec_depth) break;
+            HIP_TRY(hipMemcpyAsync(&m, a.n_next, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            if (m == 0) break;
+            launch_trace_closest(sc->view, m, nullptr, a.list_o[lc ^ 1], a.list_d[lc ^ 1], a.list_hit[lc ^ 1], a.rl, st);
+        }
         launch_motion_fold(p0, np, aov_spp, a.rec0, motion_dev, st);
         return MCPT_OK;
     });
+    if (rc != MCPT_OK) return rc;
+    if (own.p) HIP_TRY(hipStreamSynchronize(st));  // (the call's own maps are freed on return)
+    return MCPT_OK;
 }
 
 namespace {
@@ -270,6 +308,28 @@ int render_aovs(const char *name, mcpt_scene *sc, const mcpt_camera *cam, uint32
     const int rc = aov_pass(sc, make_camera(*cam), seed, n_spp, spec_depth, aov.p, nullptr);
     if (rc != MCPT_OK) return drained(rc);
     HIP_TRY(download(aov_host, aov, n_px * 8));
+    return MCPT_OK;
+}
+
+// mcpt_render_motion and mcpt_render_motion_ex (`name` for the messages)
+int render_motion(const char *name, mcpt_scene *sc, const mcpt_camera *cam, const mcpt_camera *prev_cam, uint32_t seed, int32_t aov_spp, int32_t spec_depth,
+                  float *motion_host) {
+    const auto bad = [&](const char *what) { return fail(MCPT_ERR_ARG, std::string(name) + ": " + what); };
+    if (!sc || !cam || !prev_cam || !motion_host) return bad("null argument");
+    if (!frame_ok(cam->width, cam->height)) return bad("width and height must be positive (and the frame not too large)");
+    if (prev_cam->width != cam->width || prev_cam->height != cam->height) return bad("prev_camera must have the width and height of camera");
+    if (aov_spp < 0 || aov_spp > kMaxAovSpp) return bad("aov_spp must be 0..65536");
+    if (spec_depth < 0 || spec_depth > tp::kMaxSpecularMotionDepth) return bad("specular_depth must be 0..8");
+    const int32_t n_spp = aov_spp == 0 ? 4 : aov_spp;
+    HIP_TRY(hipSetDevice(sc->device));
+    (void)hipGetLastError();
+    const size_t n_px = (size_t)cam->width * cam->height;
+    DevBuf<float> motion;
+    HIP_TRY(motion.alloc(n_px * 4));
+    const CameraConst cc = make_camera(*cam);
+    const int rc = motion_pass(sc, cc, make_camera(*prev_cam), seed, n_spp, spec_depth, nullptr, 0, motion.p, nullptr);
+    if (rc != MCPT_OK) return drained(rc);
+    HIP_TRY(download(motion_host, motion, n_px * 4));
     return MCPT_OK;
 }
 
@@ -613,22 +673,12 @@ int mcpt_render_denoised(mcpt_scene *sc, const mcpt_camera *cam, const mcpt_para
 }
 
 int mcpt_render_motion(mcpt_scene *sc, const mcpt_camera *cam, const mcpt_camera *prev_cam, uint32_t seed, int32_t aov_spp, float *motion_host) {
-    const auto bad = [&](const char *what) { return fail(MCPT_ERR_ARG, std::string("mcpt_render_motion: ") + what); };
-    if (!sc || !cam || !prev_cam || !motion_host) return bad("null argument");
-    if (!frame_ok(cam->width, cam->height)) return bad("width and height must be positive (and the frame not too large)");
-    if (prev_cam->width != cam->width || prev_cam->height != cam->height) return bad("prev_camera must have the width and height of camera");
-    if (aov_spp < 0 || aov_spp > kMaxAovSpp) return bad("aov_spp must be 0..65536");
-    const int32_t n_spp = aov_spp == 0 ? 4 : aov_spp;
-    HIP_TRY(hipSetDevice(sc->device));
-    (void)hipGetLastError();
-    const size_t n_px = (size_t)cam->width * cam->height;
-    DevBuf<float> motion;
-    HIP_TRY(motion.alloc(n_px * 4));
-    const CameraConst cc = make_camera(*cam);
-    const int rc = motion_pass(sc, cc, make_camera(*prev_cam), seed, n_spp, motion.p, nullptr);
-    if (rc != MCPT_OK) return drained(rc);
-    HIP_TRY(download(motion_host, motion, n_px * 4));
-    return MCPT_OK;
+    return render_motion("mcpt_render_motion", sc, cam, prev_cam, seed, aov_spp, 0, motion_host);
+}
+
+int mcpt_render_motion_ex(mcpt_scene *sc, const mcpt_camera *cam, const mcpt_camera *prev_cam, uint32_t seed, int32_t aov_spp, int32_t specular_depth,
+                          float *motion_host) {
+    return render_motion("mcpt_render_motion_ex", sc, cam, prev_cam, seed, aov_spp, specular_depth, motion_host);
 }
 
 }  // extern "C"

@@ -6,7 +6,9 @@
 // also keeps a normal and a flags plane), the filter and the tone map, all queued on one stream; only the outputs the caller asks for are
 // copied to the host.  A sequence created with a rule (mcpt_sequence_create_adaptive) renders adaptive frames: the AOVs and the motion
 // first, k_history_len from the previous history set into the guide, then the rounds of csrc/mcpt_render.hip (adaptive_rounds) on the
-// sequence's buffers and k_dn_variance_map.
+// sequence's buffers and k_dn_variance_map.  A sequence created with specular motion (mcpt_sequence_create_motion) and a specular depth D > 0
+// takes its motion through the chains (motion_pass at depth D, its maps in a buffer of the sequence's) and the history's depth and normal
+// from the chain AOVs, and neither runs nor allocates the extra first-hit AOV pass.
 #include <new>
 
 #include "mcpt_frame.h"
@@ -153,6 +155,10 @@ struct mcpt_sequence {
     Counts cnt[2];  // indexed as hist
     DevBuf<uint8_t> stamp;
     AdaptiveLists lists;
+    // a sequence created with mcpt_sequence_create_motion, specular_motion 1 and a specular depth > 0 (false and empty otherwise)
+    bool chain_motion = false;
+    DevBuf<float4> maps;  // the maps of the motion pass's chains, six planes of map_rays entries
+    uint64_t map_rays = 0;
     mcpt_adaptive_info ainfo{};  // of the last successful frame
 };
 
@@ -210,6 +216,11 @@ int mcpt_sequence_create_ex(mcpt_scene *sc, int32_t width, int32_t height, const
 
 int mcpt_sequence_create_adaptive(mcpt_scene *sc, int32_t width, int32_t height, const mcpt_sequence_opts *opts, const mcpt_history_opts *hopts,
                                   const mcpt_sequence_adaptive *aopts, mcpt_sequence **out) {
+    return mcpt_sequence_create_motion(sc, width, height, opts, hopts, aopts, nullptr, out);
+}
+
+int mcpt_sequence_create_motion(mcpt_scene *sc, int32_t width, int32_t height, const mcpt_sequence_opts *opts, const mcpt_history_opts *hopts,
+                                const mcpt_sequence_adaptive *aopts, const mcpt_sequence_motion *mopts, mcpt_sequence **out) {
     const auto bad = [](const char *what) { return fail(MCPT_ERR_ARG, std::string("mcpt_sequence_create: ") + what); };
     if (!sc || !opts || !out) return bad("null argument");
     *out = nullptr;
@@ -237,6 +248,13 @@ int mcpt_sequence_create_adaptive(mcpt_scene *sc, int32_t width, int32_t height,
             if (aopts->reserved[k] != 0) return bad("adaptive: reserved words must be 0");
         if (opts->denoise.aov_spp > r.min_spp) return bad("adaptive: denoise.aov_spp must be at most min_spp");
     }
+    if (mopts) {
+        if (mopts->specular_motion != 0 && mopts->specular_motion != 1) return bad("motion: specular_motion must be 0 or 1");
+        for (int k = 0; k < 7; ++k)
+            if (mopts->reserved[k] != 0) return bad("motion: reserved words must be 0");
+    }
+    // (with a specular depth of 0 the chains are the first hits: the switch changes nothing)
+    const bool chain_motion = mopts && mopts->specular_motion == 1 && opts->denoise.specular_depth > 0;
     HIP_TRY(hipSetDevice(sc->device));
     (void)hipGetLastError();
     mcpt_sequence *seq = new (std::nothrow) mcpt_sequence();
@@ -254,6 +272,7 @@ int mcpt_sequence_create_adaptive(mcpt_scene *sc, int32_t width, int32_t height,
         seq->rule = aopts->rule;
         seq->guided = aopts->guided != 0;
     }
+    seq->chain_motion = chain_motion;
     const size_t n_px = (size_t)width * height;
     hipError_t e = hipSuccess;
     const auto also = [&](auto &buf, size_t n) {
@@ -267,7 +286,11 @@ int mcpt_sequence_create_adaptive(mcpt_scene *sc, int32_t width, int32_t height,
     also(seq->mom, n_px * 6);
     also(seq->var, n_px);
     also(seq->aov, n_px * 8);
-    if (opts->denoise.specular_depth > 0) also(seq->aov_first, n_px * 8);
+    if (opts->denoise.specular_depth > 0 && !chain_motion) also(seq->aov_first, n_px * 8);
+    if (chain_motion) {  // for the most feature samples a frame can ask for (aov_spp 0: at most 4)
+        seq->map_rays = motion_map_rays(n_px, opts->denoise.aov_spp == 0 ? 4 : opts->denoise.aov_spp);
+        also(seq->maps, seq->map_rays * 6);
+    }
     also(seq->motion, n_px * 4);
     if (opts->filter) also(seq->out, n_px * 3);
     also(seq->rgba, n_px * 4);
@@ -346,17 +369,19 @@ int mcpt_sequence_frame(mcpt_sequence *seq, const mcpt_camera *cam, const mcpt_p
     const History &prev = seq->hist[seq->cur];
     History &next = seq->hist[seq->cur ^ 1];
     const StageEvents &ev = seq->ev;
-    // the normals and the depth of the history come from the first-hit AOVs: channels 3-5 and 6 of the 8
-    const float *first_hit = dopts.specular_depth > 0 ? seq->aov_first.p : seq->aov.p;
+    // the normals and the depth of the history come from the first-hit AOVs: channels 3-5 and 6 of the 8 (with specular motion from the
+    // chain AOVs, which the motion's prev_depth is measured along)
+    const int32_t motion_depth = seq->chain_motion ? dopts.specular_depth : 0;
+    const float *first_hit = dopts.specular_depth > 0 && !seq->chain_motion ? seq->aov_first.p : seq->aov.p;
     const tp::Frame planes = {seq->fb.p, seq->var.p, seq->motion.p, first_hit + 3, 8, first_hit + 6, 8};
     // The feature stage, from an event the branch has recorded: the AOVs (3.) with the first-hit depth the history is validated against,
     // and the motion (4.) against the snapshot and the previous frame's camera; a fresh sequence takes no history.
     const auto features = [&]() -> int {
         int rc = aov_pass(sc, f.cc, p.seed, aov_spp, dopts.specular_depth, seq->aov.p, st);
-        if (rc == MCPT_OK && dopts.specular_depth > 0) rc = aov_pass(sc, f.cc, p.seed, aov_spp, 0, seq->aov_first.p, st);
+        if (rc == MCPT_OK && dopts.specular_depth > 0 && !seq->chain_motion) rc = aov_pass(sc, f.cc, p.seed, aov_spp, 0, seq->aov_first.p, st);
         if (rc != MCPT_OK) return drained(rc);
         HIP_TRY(hipEventRecord(ev.aov_end, st));
-        rc = motion_pass(sc, f.cc, seq->fresh ? f.cc : seq->prev_cc, p.seed, aov_spp, seq->motion.p, st);
+        rc = motion_pass(sc, f.cc, seq->fresh ? f.cc : seq->prev_cc, p.seed, aov_spp, motion_depth, seq->maps.p, seq->map_rays, seq->motion.p, st);
         if (rc != MCPT_OK) return drained(rc);
         if (seq->fresh) HIP_TRY(hipMemsetAsync(prev.len.p, 0, n_px * sizeof(float), st));
         return MCPT_OK;

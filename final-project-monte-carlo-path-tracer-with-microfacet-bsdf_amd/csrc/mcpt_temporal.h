@@ -375,6 +375,8 @@ MCPT_TP double guided_threshold(double threshold, float guide) {
 }  // namespace tp
 }  // namespace mcpt
 
+#include "mcpt_specular_motion.h"  // the motion of a sample seen through a mirror / glass chain (mcpt_render_motion_ex)
+
 #undef MCPT_TP
 
 #if defined(__HIPCC__) || defined(__HIP__)
@@ -386,6 +388,12 @@ namespace mcpt {
 // snapshot's TriGeom and SphereRec arrays (the live ones for a scene without a snapshot) ...
 void launch_motion_resolve(const DevScene &S, const TriGeom *prev_tri, const SphereRec *prev_sph, const tp::Cam &cur, const tp::Cam &prev, uint32_t n,
                            const float4 *ray_o, const float4 *ray_d, const uint4 *hit, float4 *rec, hipStream_t st);
+// One step of the specular chains (mcpt_render_motion_ex; k_motion_chain): list entry i is ray (ray_o, ray_d)[i] with its hit and, after the
+// first step, chain_in[i] = {reflections so far, -, -, sample j}; a sample that stops writes rec[j], one that goes on is appended to
+// (next_o, next_d, chain_out) at a position counted in *n_next.  maps: six planes of map_stride float4, entry j of each the sample's.
+void launch_motion_chain(const DevScene &S, const TriGeom *prev_tri, const SphereRec *prev_sph, const tp::Cam &cur, const tp::Cam &prev, uint32_t n, int32_t b,
+                         int32_t max_b, const float4 *ray_o, const float4 *ray_d, const uint4 *hit, const float4 *chain_in, float4 *rec, float4 *maps,
+                         size_t map_stride, float4 *next_o, float4 *next_d, float4 *chain_out, uint32_t *n_next, hipStream_t st);
 // ... folded in sample order into motion[4 (p0 + i) ...] for the chunk's n_pix pixels
 void launch_motion_fold(uint32_t p0, uint32_t n_pix, int32_t spp, const float4 *rec, float *motion, hipStream_t st);
 // The rule over a W x H frame, 16 x 16 pixels per block (tp::Frame, tp::Prev and tp::Next say what each flavour reads and writes).

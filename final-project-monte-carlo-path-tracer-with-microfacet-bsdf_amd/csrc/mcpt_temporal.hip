@@ -5,6 +5,9 @@
 //   k_motion_resolve  hit -> per-sample record {dx, dy, prev_depth, valid}: the hit point rebuilt on the live primitive and on the
 //                     snapshot's, both projected
 //   k_motion_fold     one lane per pixel: the samples folded in sample order into the 4-float motion record
+// With specular_depth > 0 (mcpt_render_motion_ex) k_motion_chain takes k_motion_resolve's place, as k_aov_chain takes k_aov_resolve's
+// (csrc/mcpt_denoise.hip): the same lists, the same bounce (csrc/mcpt_chain.h), the same compaction; a sample that reflects composes the
+// mirror plane into its two maps (csrc/mcpt_specular_motion.h), one that stops writes its record from the unfolded terminal hit.
 // The pixel rule (tp::reuse_pixel, once, with compile-time switches) over a frame: 16 x 16 pixel blocks, one pixel per lane; a wave covers
 // four rows of 16 pixels, so its loads of the pixel's own colour, motion and its stores are four contiguous runs; up to four taps of the
 // previous frame per lane, no LDS (neighbouring lanes' taps are neighbouring pixels: the cache lines are shared in L1 / L2).  Three kernels
@@ -23,6 +26,7 @@
 //                     tp::history_len_pixel, the taps and skips of the rule without its colour, known before the frame is rendered.
 #include <hip/hip_runtime.h>
 
+#include "mcpt_chain.h"
 #include "mcpt_temporal.h"
 
 namespace mcpt {
@@ -35,6 +39,30 @@ inline uint32_t nblocks(uint32_t n) { return (n + kB - 1) / kB; }
 // tp::tri_point reads a TriGeom as nine floats v0, e1, e2
 static_assert(offsetof(TriGeom, e1x) == 12 && offsetof(TriGeom, e1yz) == 16 && offsetof(TriGeom, e2xy) == 24 && offsetof(TriGeom, e2z) == 32, "TriGeom layout");
 
+// Where the hit of ray (ro, rd) on primitive prim is now (pc) and was in the snapshot (pp): the first-hit rule of mcpt_render_motion.
+// Triangles: the barycentrics of the test that recorded the hit (it succeeds again; false if not), each rounded once to float, on the live
+// record g and on the snapshot's.  Spheres: o + d (float)t, moved with the centre.
+MCPT_DI bool hit_points(const DevScene &S, const TriGeom *__restrict__ prev_tri, const SphereRec *__restrict__ prev_sph, int32_t prim, const uint4 &h,
+                        f3 ro, f3 rd, float pc[3], float pp[3]) {
+    if (prim < S.n_tri) {
+        const TriGeom g = S.tri_geom[prim];
+        double tt, u, v;
+        if (!tri_hit(g, make_ray(ro, rd), tt, u, v)) return false;
+        tp::tri_point(reinterpret_cast<const float *>(&g), (float)u, (float)v, pc);
+        tp::tri_point(reinterpret_cast<const float *>(prev_tri + prim), (float)u, (float)v, pp);
+    } else {
+        const f3 p = ro + rd * (float)hit_t(h);
+        const SphereRec &sc = S.spheres[prim - S.n_tri], &sp = prev_sph[prim - S.n_tri];
+        pc[0] = p.x;
+        pc[1] = p.y;
+        pc[2] = p.z;
+        pp[0] = p.x + (sp.c[0] - sc.c[0]);
+        pp[1] = p.y + (sp.c[1] - sc.c[1]);
+        pp[2] = p.z + (sp.c[2] - sc.c[2]);
+    }
+    return true;
+}
+
 __global__ __launch_bounds__(kB) void k_motion_resolve(DevScene S, const TriGeom *__restrict__ prev_tri, const SphereRec *__restrict__ prev_sph,
                                                        tp::Cam cur, tp::Cam prev, uint32_t n, const float4 *__restrict__ ray_o,
                                                        const float4 *__restrict__ ray_d, const uint4 *__restrict__ hit, float4 *__restrict__ rec) {
@@ -45,31 +73,109 @@ __global__ __launch_bounds__(kB) void k_motion_resolve(DevScene S, const TriGeom
     float out[4] = {0.f, 0.f, 0.f, 0.f};
     if (prim >= 0) {
         const float4 o4 = ray_o[j], d4 = ray_d[j];
-        const f3 ro = mk3(o4.x, o4.y, o4.z), rd = mk3(d4.x, d4.y, d4.z);
         float pc[3], pp[3];
-        bool ok = true;
-        if (prim < S.n_tri) {
-            const TriGeom g = S.tri_geom[prim];
-            double tt, u, v;
-            ok = tri_hit(g, make_ray(ro, rd), tt, u, v);  // (the test that recorded the hit: it succeeds again)
-            if (ok) {
-                tp::tri_point(reinterpret_cast<const float *>(&g), (float)u, (float)v, pc);
-                tp::tri_point(reinterpret_cast<const float *>(prev_tri + prim), (float)u, (float)v, pp);
-            }
-        } else {
-            const double t = __longlong_as_double((long long)(((unsigned long long)h.y << 32) | h.x));
-            const f3 p = ro + rd * (float)t;
-            const SphereRec &sc = S.spheres[prim - S.n_tri], &sp = prev_sph[prim - S.n_tri];
-            pc[0] = p.x;
-            pc[1] = p.y;
-            pc[2] = p.z;
-            pp[0] = p.x + (sp.c[0] - sc.c[0]);
-            pp[1] = p.y + (sp.c[1] - sc.c[1]);
-            pp[2] = p.z + (sp.c[2] - sc.c[2]);
-        }
-        if (ok) tp::sample_motion(cur, prev, pc, pp, out);
+        if (hit_points(S, prev_tri, prev_sph, prim, h, mk3(o4.x, o4.y, o4.z), mk3(d4.x, d4.y, d4.z), pc, pp)) tp::sample_motion(cur, prev, pc, pp, out);
     }
     rec[j] = make_float4(out[0], out[1], out[2], out[3]);
+}
+
+// The two maps of sample j: six float4, plane k of `stride` entries at maps + k stride (A_cur rows 0-2, then A_prev rows 0-2).
+MCPT_DI void load_maps(const float4 *__restrict__ maps, size_t stride, uint32_t j, float Ac[12], float Ap[12]) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float4 a = maps[k * stride + j], b = maps[(3 + k) * stride + j];
+        Ac[4 * k] = a.x, Ac[4 * k + 1] = a.y, Ac[4 * k + 2] = a.z, Ac[4 * k + 3] = a.w;
+        Ap[4 * k] = b.x, Ap[4 * k + 1] = b.y, Ap[4 * k + 2] = b.z, Ap[4 * k + 3] = b.w;
+    }
+}
+MCPT_DI void store_maps(float4 *__restrict__ maps, size_t stride, uint32_t j, const float Ac[12], const float Ap[12]) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        maps[k * stride + j] = make_float4(Ac[4 * k], Ac[4 * k + 1], Ac[4 * k + 2], Ac[4 * k + 3]);
+        maps[(3 + k) * stride + j] = make_float4(Ap[4 * k], Ap[4 * k + 1], Ap[4 * k + 2], Ap[4 * k + 3]);
+    }
+}
+
+// One step of the specular chains of the motion pass (include/mcpt.h: mcpt_render_motion_ex) for the n rays of a list whose samples have all
+// followed b bounces; the shape of k_aov_chain (csrc/mcpt_denoise.hip).  Ray i belongs to sample j, which has composed n_refl reflections into
+// its maps (chain_in[i] = {n_refl bits, -, -, j bits}; nullptr for the camera rays: j = i, n_refl = 0).  A sample that stops writes its record
+// rec[j] from its terminal hit, unfolded through its maps; one that follows a Dirac bounce (b < max_b) appends its next ray and state to the
+// next list (ballot + prefix count, one atomic per wave on n_next) and, if it reflects, composes the mirror plane into maps[.. j]: only
+// sample j's lane ever touches entry j, so one array serves every bounce.
+__global__ __launch_bounds__(kB) void k_motion_chain(DevScene S, const TriGeom *__restrict__ prev_tri, const SphereRec *__restrict__ prev_sph,
+                                                     tp::Cam cur, tp::Cam prev, uint32_t n, int32_t b, int32_t max_b,
+                                                     const float4 *__restrict__ ray_o, const float4 *__restrict__ ray_d, const uint4 *__restrict__ hit,
+                                                     const float4 *__restrict__ chain_in, float4 *__restrict__ rec, float4 *__restrict__ maps,
+                                                     size_t map_stride, float4 *__restrict__ next_o, float4 *__restrict__ next_d,
+                                                     float4 *__restrict__ chain_out, uint32_t *__restrict__ n_next) {
+    const uint32_t i = blockIdx.x * kB + threadIdx.x;
+    bool cont = false;  // (no early return: every lane takes part in the ballot)
+    uint32_t j = i;
+    int32_t n_refl = 0;
+    f3 p2 = mk3(0, 0, 0), wi = mk3(0, 0, 1);
+    if (i < n) {
+        if (chain_in) {
+            const float4 c = chain_in[i];
+            n_refl = (int32_t)__float_as_uint(c.x);
+            j = __float_as_uint(c.w);
+        }
+        const uint4 h = hit[i];
+        const int32_t prim = (int32_t)h.z;
+        float out[4] = {0.f, 0.f, 0.f, 0.f};
+        if (prim >= 0) {
+            const float4 o4 = ray_o[i], d4 = ray_d[i];
+            const f3 ro = mk3(o4.x, o4.y, o4.z), rd = mk3(d4.x, d4.y, d4.z);
+            const f3 p = ro + rd * (float)hit_t(h);
+            f3 nrm;
+            if (prim < S.n_tri) {
+                const float *tn = S.tri_shade[prim].n;
+                nrm = mk3(tn[0], tn[1], tn[2]);
+            } else {
+                const float *c = S.spheres[prim - S.n_tri].c;
+                nrm = normalized(p - mk3(c[0], c[1], c[2]));
+            }
+            const MaterialRec &M = S.mats[h.w & kMatIndexMask];
+            cont = chain_continues(M, h.w, b, max_b);
+            float Ac[12], Ap[12];
+            if (cont) {
+                if (chain_bounce(M, rd, p, nrm, p2, wi)) {
+                    if (n_refl > 0) load_maps(maps, map_stride, j, Ac, Ap);
+                    if (prim < S.n_tri) {
+                        const TriGeom g = S.tri_geom[prim];
+                        double tt, u, v;
+                        if (tri_hit(g, make_ray(ro, rd), tt, u, v))  // (the test that recorded the hit: it succeeds again)
+                            tp::chain_reflect_tri(Ac, Ap, n_refl, reinterpret_cast<const float *>(&g), reinterpret_cast<const float *>(prev_tri + prim),
+                                                  (float)u, (float)v);
+                        else
+                            cont = false;  // (as k_motion_resolve: no record without the barycentrics)
+                    } else {
+                        const float pf[3] = {p.x, p.y, p.z}, nf[3] = {nrm.x, nrm.y, nrm.z};
+                        tp::chain_reflect_sphere(Ac, Ap, n_refl, pf, nf, S.spheres[prim - S.n_tri].c, prev_sph[prim - S.n_tri].c);
+                    }
+                    if (cont) store_maps(maps, map_stride, j, Ac, Ap);
+                    ++n_refl;
+                }
+            } else {
+                float qc[3], qp[3];
+                if (hit_points(S, prev_tri, prev_sph, prim, h, ro, rd, qc, qp)) {
+                    if (n_refl > 0) load_maps(maps, map_stride, j, Ac, Ap);
+                    tp::chain_motion(cur, prev, Ac, Ap, n_refl, qc, qp, out);
+                }
+            }
+        }
+        if (!cont) rec[j] = make_float4(out[0], out[1], out[2], out[3]);
+    }
+    const unsigned long long mask = __ballot(cont);
+    if (mask == 0ull) return;
+    uint32_t base = 0;
+    if (lane_id() == 0) base = atomicAdd(n_next, (uint32_t)__popcll(mask));
+    base = __shfl(base, 0);
+    if (cont) {
+        const uint32_t k = base + __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+        next_o[k] = make_float4(p2.x, p2.y, p2.z, 0.f);
+        next_d[k] = make_float4(wi.x, wi.y, wi.z, 0.f);
+        chain_out[k] = make_float4(__uint_as_float((uint32_t)n_refl), 0.f, 0.f, __uint_as_float(j));
+    }
 }
 
 __global__ __launch_bounds__(kB) void k_motion_fold(uint32_t p0, uint32_t n_pix, int32_t spp, const float4 *__restrict__ rec, float *__restrict__ motion) {
@@ -114,6 +220,14 @@ void launch_motion_resolve(const DevScene &S, const TriGeom *prev_tri, const Sph
                            const float4 *ray_o, const float4 *ray_d, const uint4 *hit, float4 *rec, hipStream_t st) {
     if (n == 0) return;
     hipLaunchKernelGGL(k_motion_resolve, dim3(nblocks(n)), dim3(kB), 0, st, S, prev_tri, prev_sph, cur, prev, n, ray_o, ray_d, hit, rec);
+}
+
+void launch_motion_chain(const DevScene &S, const TriGeom *prev_tri, const SphereRec *prev_sph, const tp::Cam &cur, const tp::Cam &prev, uint32_t n, int32_t b,
+                         int32_t max_b, const float4 *ray_o, const float4 *ray_d, const uint4 *hit, const float4 *chain_in, float4 *rec, float4 *maps,
+                         size_t map_stride, float4 *next_o, float4 *next_d, float4 *chain_out, uint32_t *n_next, hipStream_t st) {
+    if (n == 0) return;
+    hipLaunchKernelGGL(k_motion_chain, dim3(nblocks(n)), dim3(kB), 0, st, S, prev_tri, prev_sph, cur, prev, n, b, max_b, ray_o, ray_d, hit, chain_in, rec,
+                       maps, map_stride, next_o, next_d, chain_out, n_next);
 }
 
 void launch_motion_fold(uint32_t p0, uint32_t n_pix, int32_t spp, const float4 *rec, float *motion, hipStream_t st) {

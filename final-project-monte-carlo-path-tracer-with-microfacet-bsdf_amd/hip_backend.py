@@ -26,6 +26,7 @@ EXPORTS = ["mcpt_scene_create", "mcpt_scene_destroy", "mcpt_render", "mcpt_rende
            "mcpt_sequence_create_ex", "mcpt_sequence_flags",
            "mcpt_temporal_history_len", "mcpt_render_adaptive_guided", "mcpt_render_adaptive_denoised",
            "mcpt_sequence_create_adaptive", "mcpt_sequence_counts",
+           "mcpt_render_motion_ex", "mcpt_sequence_create_motion",
            "mcpt_group_create", "mcpt_group_render", "mcpt_group_size", "mcpt_group_get_info", "mcpt_group_scene", "mcpt_group_destroy", "mcpt_group_last_error",
            "mcpt_last_error", "mcpt_version"]
 
@@ -144,6 +145,11 @@ def sequence_adaptive(min_spp, threshold, rel_floor=1e-3, dilate=1, guided=False
                             guided=int(guided))
 
 
+class SequenceMotion(C.Structure):
+    _fields_ = [("specular_motion", C.c_int32), ("reserved", C.c_int32 * 7)]
+
+
+assert C.sizeof(SequenceMotion) == 32
 assert C.sizeof(Adaptive) == 32 and C.sizeof(AdaptiveInfo) == 264 and C.sizeof(SequenceAdaptive) == 64
 assert C.sizeof(TemporalOpts) == 32 and C.sizeof(DenoiseOpts) == 32 and C.sizeof(HistoryOpts) == 32  # the sizes include/mcpt.h states
 assert C.sizeof(SequenceOpts) == 96 and C.sizeof(SequenceOutputs) == 64 and C.sizeof(SequenceInfo) == 64
@@ -247,6 +253,11 @@ def lib(path=None):
         L.mcpt_scene_snapshot.argtypes = [C.c_void_p]
         L.mcpt_render_motion.restype = C.c_int
         L.mcpt_render_motion.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.c_void_p]
+        L.mcpt_render_motion_ex.restype = C.c_int
+        L.mcpt_render_motion_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.c_int32, C.c_void_p]
+        L.mcpt_sequence_create_motion.restype = C.c_int
+        L.mcpt_sequence_create_motion.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(SequenceOpts), C.POINTER(HistoryOpts),
+                                                  C.POINTER(SequenceAdaptive), C.POINTER(SequenceMotion), C.POINTER(C.c_void_p)]
         L.mcpt_temporal_blend.restype = C.c_int
         L.mcpt_temporal_blend.argtypes = [C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 5 + [C.POINTER(TemporalOpts), C.c_void_p, C.c_void_p]
         L.mcpt_temporal_accumulate.restype = C.c_int
@@ -625,14 +636,19 @@ class HipScene:
         update calls; without one, render_motion sees camera motion only)."""
         _check(self.L.mcpt_scene_snapshot(self.h), L=self.L)
 
-    def render_motion(self, prev_camera=None, seed=1, aov_spp=0, camera=None):
+    def render_motion(self, prev_camera=None, seed=1, aov_spp=0, camera=None, specular_depth=0):
         """mcpt_render_motion: motion[H,W,4] float32 = {dx, dy, prev_depth, valid}: where the surface seen in each pixel was on the screen of
-        prev_camera (default: the camera itself) when snapshot() was last called, from the feature samples of render_aovs(aov_spp, seed)."""
+        prev_camera (default: the camera itself) when snapshot() was last called, from the feature samples of render_aovs(aov_spp, seed).
+        specular_depth > 0: mcpt_render_motion_ex, the motion of what is seen behind up to that many mirror / glass bounces (the chains of
+        render_aovs(aov_spp, seed, specular_depth=...)), as a virtual point on the primary ray."""
         cam = np.ascontiguousarray(camera if camera is not None else self.sd.camera)
         prev = np.ascontiguousarray(prev_camera if prev_camera is not None else cam)
         W, H = int(cam["width"].reshape(-1)[0]), int(cam["height"].reshape(-1)[0])
         motion = np.zeros((H, W, 4), dtype=np.float32)
-        _check(self.L.mcpt_render_motion(self.h, _ptr(cam), _ptr(prev), int(seed), int(aov_spp), _ptr(motion)), L=self.L)
+        if specular_depth == 0:
+            _check(self.L.mcpt_render_motion(self.h, _ptr(cam), _ptr(prev), int(seed), int(aov_spp), _ptr(motion)), L=self.L)
+        else:
+            _check(self.L.mcpt_render_motion_ex(self.h, _ptr(cam), _ptr(prev), int(seed), int(aov_spp), int(specular_depth), _ptr(motion)), L=self.L)
         return motion
 
     def temporal_blend(self, color, motion, prev_color, prev_depth, prev_len, **opts):
@@ -703,16 +719,18 @@ class HipScene:
         return out, out_var, out_len, flags
 
     def sequence(self, width=None, height=None, filter=True, max_history=0, depth_tol=0.0, normal_test=False, color_clamp=False, normal_min=0.0,
-                 clamp_k=0.0, adaptive=None, **denoise_opts_kw):
+                 clamp_k=0.0, adaptive=None, specular_motion=False, **denoise_opts_kw):
         """mcpt_sequence_create: a HipSequence of width x height frames (default: the scene camera's) on this scene.  filter: also denoise
         the accumulated frame; max_history, depth_tol: mcpt_temporal_opts; the rest: mcpt_denoise_opts (aov_spp, iterations, sigma_l,
         sigma_n, sigma_z, specular_depth).  normal_test / color_clamp (normal_min, clamp_k): history rejection, mcpt_history_opts; with
         either on the sequence is made by mcpt_sequence_create_ex and HipSequence.flags() tells what the last frame rejected.
         adaptive: dict(min_spp=, threshold=, rel_floor=, dilate=, guided=) (the keywords of sequence_adaptive): the frames are adaptive
         (mcpt_sequence_create_adaptive), each frame's `spp` is the cap, and HipSequence.counts() gives the last frame's counts.
+        specular_motion: with specular_depth > 0 the motion follows the mirror / glass chains too and the history is validated against the
+        chain depth (mcpt_sequence_create_motion).
         The sequence owns the scene's snapshot while it lives; close it before the scene."""
         return HipSequence(self, width, height, filter, max_history, depth_tol, normal_test=normal_test, color_clamp=color_clamp,
-                           normal_min=normal_min, clamp_k=clamp_k, adaptive=adaptive, **denoise_opts_kw)
+                           normal_min=normal_min, clamp_k=clamp_k, adaptive=adaptive, specular_motion=specular_motion, **denoise_opts_kw)
 
     def render_device(self, fb_ptr, stream_ptr=0, camera=None, **kw):
         """Same, into a device framebuffer (W*H*3 floats at fb_ptr) on the given hipStream_t handle."""
@@ -814,10 +832,13 @@ class HipSequence:
     _SHAPES = {"fb": (3,), "accumulated": (3,), "denoised": (3,), "variance": (), "len": (), "aov": (8,), "motion": (4,), "rgba": (4,)}
 
     def __init__(self, scene, width=None, height=None, filter=True, max_history=0, depth_tol=0.0, normal_test=False, color_clamp=False,
-                 normal_min=0.0, clamp_k=0.0, history=None, adaptive=None, create_adaptive=False, **denoise_opts_kw):
+                 normal_min=0.0, clamp_k=0.0, history=None, adaptive=None, create_adaptive=False, specular_motion=False, motion=None,
+                 **denoise_opts_kw):
         """history: a HistoryOpts passed to mcpt_sequence_create_ex as it is (tests: a zeroed one must give mcpt_sequence_create's sequence).
         adaptive: a dict of sequence_adaptive's keywords or a SequenceAdaptive; create_adaptive: go through mcpt_sequence_create_adaptive
-        even without one (tests: a null rule must give mcpt_sequence_create_ex's sequence)."""
+        even without one (tests: a null rule must give mcpt_sequence_create_ex's sequence).  specular_motion: mcpt_sequence_create_motion
+        with the switch on; motion: a SequenceMotion passed to it as it is, or "null" for a null pointer (tests: a null or zeroed one must
+        give mcpt_sequence_create_adaptive's sequence)."""
         self.scene = scene  # (keeps the scene alive as long as the sequence)
         self.L = scene.L
         self.h = None
@@ -830,7 +851,13 @@ class HipSequence:
             history = history_opts(normal_test, color_clamp, normal_min, clamp_k)
         if isinstance(adaptive, dict):
             adaptive = sequence_adaptive(**adaptive)
-        if adaptive is not None or create_adaptive:
+        if specular_motion and motion is None:
+            motion = SequenceMotion(specular_motion=1)
+        if motion is not None:
+            _check(self.L.mcpt_sequence_create_motion(scene.h, self.W, self.H, C.byref(o), None if history is None else C.byref(history),
+                                                      None if adaptive is None else C.byref(adaptive),
+                                                      None if isinstance(motion, str) else C.byref(motion), C.byref(h)), L=self.L)
+        elif adaptive is not None or create_adaptive:
             _check(self.L.mcpt_sequence_create_adaptive(scene.h, self.W, self.H, C.byref(o), None if history is None else C.byref(history),
                                                         None if adaptive is None else C.byref(adaptive), C.byref(h)), L=self.L)
         elif history is None:

@@ -392,9 +392,39 @@ int mcpt_scene_snapshot(mcpt_scene *scene);
  * one); valid = that number / aov_spp.
  * motion_host: W*H*4 floats.  aov_spp 0 => 4, at most 65536.  MCPT_ERR_ARG, before any device call: a null pointer, width or height
  * <= 0, aov_spp out of range, prev_camera with another width or height than camera.
- * Limits: the motion is that of the first hit, so what is seen through mirrors and glass, and depth-of-field blur, are not reprojected. */
+ * Limits: the motion is that of the first hit, so what is seen through mirrors and glass is not reprojected (mcpt_render_motion_ex below
+ * does that), nor is depth-of-field blur. */
 int mcpt_render_motion(mcpt_scene *scene, const mcpt_camera *camera, const mcpt_camera *prev_camera, uint32_t seed, int32_t aov_spp,
                        float *motion_host);
+
+/* The motion of what is seen through mirror and glass chains (csrc/mcpt_specular_motion.h has every expression in its order).
+ * specular_depth 0: mcpt_render_motion, bit for bit (the same kernels).  Otherwise feature sample k of pixel m walks exactly the chain of
+ * mcpt_render_aovs_ex(seed, aov_spp, specular_depth): the same camera ray, closest-hit traversal, stop rule (fewer than specular_depth
+ * bounces so far, a Dirac material, not an emitter), branch (kr = fresnel of channel 1, reflect iff kr > 0.5), next origin and direction --
+ * one device function decides the bounce for both passes.  A sample carries two affine maps of R^3, A_cur and A_prev (3 x 4 floats each),
+ * both "none" at the start; all arithmetic in float, no contraction, dots in the 3-term order:
+ *   followed reflect bounce  one mirror plane per map, anchor a and unit normal n (the sign of n does not matter):
+ *             triangle  (u, v) as above;  a_cur = v0 + (e1*u + e2*v) on the live record, a_prev the same on the snapshot's;  n = the unit
+ *                       normal derived from that record's own e1, e2: c = cross(e1, e2), z = c.c, n = z > 0 ? c / sqrtf(z) : c
+ *                       (equal records give equal normals bit for bit)
+ *             sphere    a_cur = o + d * (float) t,  a_prev = a_cur + (c_prev - c_cur),  n_cur = n_prev = normalized(a_cur - c_cur)
+ *             R(a, n)(x) = x - 2 n (n . (x - a)), as the map L = I - (2n) n^T, t = (2n)(n . a);  A <- A o R, so that the newest reflection
+ *             is applied first: v = R1(R2(... Rk(q)))
+ *   followed refract bounce  both maps stay as they are: glass is treated as straight-through
+ *   terminal hit (the vertex where the chain AOVs record)  q_cur, q_prev = p_cur, p_prev of the rule above on the last ray and its hit;
+ *             v_cur = A_cur(q_cur), v_prev = A_prev(q_prev), a map that is still none not applied (v = q bit for bit);  the record is that
+ *             of the points v_cur, v_prev: motion = proj(prev_camera, v_prev) - proj(camera, v_cur), prev_depth = |v_prev - prev position|
+ *   a chain that ends in a miss: an invalid sample.  The fold is unchanged.
+ * v is the *virtual point*: the terminal hit reflected back across the mirror planes the chain passed, which lies on the primary ray at
+ * about the chain's depth (channel 6 of the chain AOVs).  For planar mirrors that is exact under any rigid motion of object, mirror and
+ * camera; for a curved mirror (the tangent plane at the hit) and for refraction it is the usual approximation, and the depth test of
+ * the blend, against the chain depth of the previous frame, decides whether the history is usable.  So:
+ *   - equal cameras and a snapshot equal to the live geometry give dx = dy = 0 bit for bit (the same expressions on the same inputs);
+ *   - valid equals the coverage channel of the chain AOVs whenever both projections have q.z > 0.
+ * MCPT_ERR_ARG, before any device call: as mcpt_render_motion, and specular_depth outside 0..8.
+ * Limits: depth-of-field blur is not reprojected; refraction and curved mirrors as said. */
+int mcpt_render_motion_ex(mcpt_scene *scene, const mcpt_camera *camera, const mcpt_camera *prev_camera, uint32_t seed, int32_t aov_spp,
+                          int32_t specular_depth, float *motion_host);
 
 /* The blend on host arrays (the scene only picks the device and stream, as in mcpt_denoise):
  *   color_host W*H*3 the new frame;  motion_host W*H*4 (mcpt_render_motion);  prev_color_host W*H*3 the previous OUTPUT of this call;
@@ -615,6 +645,26 @@ typedef struct {
 int mcpt_sequence_create_adaptive(mcpt_scene *scene, int32_t width, int32_t height, const mcpt_sequence_opts *opts,
                                   const mcpt_history_opts *history_opts, const mcpt_sequence_adaptive *adaptive, mcpt_sequence **out);
 int mcpt_sequence_counts(mcpt_sequence *sequence, int32_t *spp_host, float *err_host, float *guide_host, mcpt_adaptive_info *info);
+
+/* A sequence that reprojects what it sees through mirrors and glass.  A null or zeroed `motion`: mcpt_sequence_create_adaptive, exactly (the
+ * same allocations, the same frame); with denoise.specular_depth 0 the switch changes nothing either.  With specular_motion 1 and
+ * denoise.specular_depth D > 0, mcpt_sequence_frame changes in two places and nowhere else:
+ *   step 4 is mcpt_render_motion_ex(camera, the previous frame's camera, params.seed, denoise.aov_spp, D);
+ *   the history's depth plane and, with normal_test, its normal plane are written from channel 6 and channels 3..5 of the CHAIN AOVs of
+ *   step 3 -- the depth a chain motion record's prev_depth measures -- and step 5 and the guide of an adaptive sequence read those; the
+ *   extra first-hit AOV pass is neither run nor allocated.
+ * Every output still equals what the separate calls give, bit for bit: mcpt_render_motion_ex, mcpt_temporal_accumulate[_ex],
+ * mcpt_temporal_history_len and mcpt_denoise, with those planes as their prev_depth, normal and prev_normal arguments.
+ * Allocated at create: the maps of the chains, 96 bytes per feature sample of a chunk of the motion pass, i.e. 96 * aov_spp bytes per
+ * pixel (aov_spp 0 counts as 4) up to 96 MiB in all, in place of the 32 bytes per pixel of the first-hit AOVs.  A frame allocates nothing.
+ * MCPT_ERR_ARG, before any device call: as mcpt_sequence_create_adaptive; specular_motion not 0 or 1, a non-zero reserved word. */
+typedef struct {
+    int32_t specular_motion; /* 0 | 1 */
+    int32_t reserved[7];     /* must be 0 */
+} mcpt_sequence_motion;      /* 32 bytes */
+int mcpt_sequence_create_motion(mcpt_scene *scene, int32_t width, int32_t height, const mcpt_sequence_opts *opts,
+                                const mcpt_history_opts *history_opts, const mcpt_sequence_adaptive *adaptive,
+                                const mcpt_sequence_motion *motion, mcpt_sequence **out);
 
 /* Replaces Scene::intersect (Scene.hpp:128, Scene.cpp:19-21) for a list of rays (host pointers; n*3 floats each).
  * out_t: hit distance as the reference's double Intersection::distance (DBL_MAX on a miss);

@@ -19,7 +19,11 @@ python tools/temporal.py --sequence --adaptive T [--adaptive-min N] [--guided] [
 Prints, per frame, the total samples, the histogram of the counts, the stage times and the MSE of the accumulated frame against a
 --ref-spp render of that frame's geometry (seed 1000).  --move: the short box of the Cornell scene moves by translate(-32 k, 0, 0) before
 frame k (a reference per frame; a static scene renders one).  --quality instead of --adaptive: the same figures for a uniform sequence at
---spp samples per pixel."""
+--spp samples per pixel.
+  --specular-depth N   the sequence's denoise.specular_depth (the features behind up to N mirror / glass bounces); with --specular-motion the
+motion follows those chains too and the history is validated against the chain depth (mcpt_sequence_create_motion).  --move with --scene
+chess moves the nearest rough pawn by 6 units (about 3.5 px at 1080p) along x per frame, and the MSE is also given over the pixels whose
+first hit is the floor mirror, where the pawn's reflection moves."""
 import argparse
 import csv
 import re
@@ -131,21 +135,32 @@ def sequence_timing(pkg, sd, W, H, frames, reject=None, loop=True):
     hs.close()
 
 
-def sequence_quality(pkg, sd, W, H, frames, spp, adaptive, reject, move, ref_spp):
+def sequence_quality(pkg, sd, W, H, frames, spp, adaptive, reject, move, ref_spp, specular_depth=0, specular_motion=False):
     """Per frame of a uniform (adaptive None) or adaptive sequence: samples, count histogram, stage times, MSE of `accumulated`."""
     hs = pkg.HipScene(sd)
-    seq = hs.sequence(filter=False, aov_spp=min(4, adaptive["min_spp"] if adaptive else spp), adaptive=adaptive, **(reject or {}))
+    seq = hs.sequence(filter=False, aov_spp=min(4, adaptive["min_spp"] if adaptive else spp), adaptive=adaptive, specular_depth=specular_depth,
+                      specular_motion=specular_motion, **(reject or {}))
+    chess = sd.name.startswith("chess")
+    step = 6.0 if chess else -32.0  # object 1: the nearest rough pawn of the chess scene, the short box of the Cornell scene
+    floor = None
+    if chess:  # Scene::Add order: 14 pawns, the light, the floor
+        a, n = int(sd.objects["first_tri"][15]), int(sd.objects["n_tri"][15])
+        o, d = hs.camera_rays(np.arange(W * H), np.zeros(W * H, np.int64), seed=1)
+        prim = hs.intersect(o, d)[1].reshape(H, W)
+        floor = (prim >= a) & (prim < a + n)
+        print("specular depth %d, specular motion %s; %.1f %% of the pixels see the floor mirror first" % (specular_depth, bool(specular_motion), 100 * floor.mean()))
     what = "uniform %d spp" % spp if not adaptive else "adaptive %s, levels %d..%d, threshold %g" % (
         "guided" if adaptive["guided"] else "unguided", adaptive["min_spp"], spp, adaptive["threshold"])
     print("%dx%d %s sequence, %s; reference %d spp" % (W, H, "moving" if move else "static", what, ref_spp))
     truth, total = None, 0
     for k in range(frames):
         if move:
-            hs.update([(1, np.array([[1, 0, 0, -32.0 * k], [0, 1, 0, 0], [0, 0, 1, 0]], np.float32))])
+            hs.update([(1, np.array([[1, 0, 0, step * k], [0, 1, 0, 0], [0, 0, 1, 0]], np.float32))])
         if truth is None or move:
             truth = hs.render(spp=ref_spp, seed=1000)[0].astype(np.float64)
         r = seq.frame(want=("accumulated",), spp=spp, seed=k + 1)
-        mse = float(np.nanmean((r["accumulated"].astype(np.float64) - truth) ** 2))
+        sq = (r["accumulated"].astype(np.float64) - truth) ** 2
+        mse = float(np.nanmean(sq))
         n = int(r["stats"].samples)
         total += n
         hist = ""
@@ -155,6 +170,8 @@ def sequence_quality(pkg, sd, W, H, frames, spp, adaptive, reject, move, ref_spp
             hist = "  counts " + " ".join("%d:%d" % (a, b) for a, b in zip(lv, cnt))
             if adaptive["guided"]:
                 hist += "  mean guide %.2f" % float(cn["guide"].mean())
+        if floor is not None:
+            hist += "  MSE on the floor mirror %.6g" % float(np.nanmean(sq[floor]))
         i = r["info"]
         print("frame %d: %d samples (%.2f per pixel)  MSE %.6g%s  ms: render %.3f aov %.3f motion %.3f accumulate %.3f total %.2f"
               % (k, n, n / (W * H), mse, hist, i["ms_render"], i["ms_aov"], i["ms_motion"], i["ms_accumulate"], i["ms_total"]), flush=True)
@@ -183,18 +200,20 @@ def main():
     ap.add_argument("--spp", type=int, default=64, help="--adaptive: the cap; --quality: the samples per pixel")
     ap.add_argument("--move", action="store_true", help="--adaptive / --quality with --scene cornell: move the short box before every frame")
     ap.add_argument("--ref-spp", type=int, default=2048, help="--adaptive / --quality: samples per pixel of the reference")
+    ap.add_argument("--specular-depth", type=int, default=0, help="--adaptive / --quality: denoise.specular_depth of the sequence, and the depth of --specular-motion")
+    ap.add_argument("--specular-motion", action="store_true", help="--adaptive / --quality: reproject what is seen through mirrors and glass (needs --specular-depth > 0)")
     a = ap.parse_args()
     if a.trace:
         return summarize_trace(a.trace, a.repeat)
     pkg = mcpt_loader.load()
     W, H = a.width, a.height
     sd = pkg.scenes.chess_scene(width=W, height=H, spp=4) if a.scene == "chess" else pkg.scenes.cornell_demo(W, H, 4)
-    if a.sequence and (a.adaptive is not None or a.quality):
+    if a.sequence and (a.adaptive is not None or a.quality or a.move or a.specular_depth > 0):  # (the last two imply --quality)
         reject = dict(normal_test=a.normal_test, color_clamp=a.color_clamp, clamp_k=a.clamp_k) if a.normal_test or a.color_clamp else None
         rule = None if a.adaptive is None else dict(min_spp=a.adaptive_min, threshold=a.adaptive, dilate=1, guided=int(a.guided))
-        if a.move and a.scene != "cornell":
-            sys.exit("--move needs --scene cornell")
-        return sequence_quality(pkg, sd, W, H, a.frames, a.spp, rule, reject, a.move, a.ref_spp)
+        if a.specular_motion and a.specular_depth <= 0:
+            sys.exit("--specular-motion needs --specular-depth N > 0")
+        return sequence_quality(pkg, sd, W, H, a.frames, a.spp, rule, reject, a.move, a.ref_spp, a.specular_depth, a.specular_motion)
     if a.sequence:
         if a.frames < 6:
             sys.exit("--frames must be at least 6")
