@@ -119,7 +119,7 @@ constexpr int kSmallNodes = 64, kSmallTris = 64, kSmallSphereSlots = 16;
 constexpr int kSmallMats = 12, kSmallLights = 4, kSmallLightNodes = 8, kSmallLightTris = 8;
 constexpr int kSmallStk = 8;  // LDS stack entries of the SMALL kernels: trees of up to 9 levels
 
-// Retrace list of one traversal kernel (retry flavour of the traversal stack, MCPT_STK_PUSH in mcpt_kernels.hip): the rays of a launch that
+// Retrace list of one traversal kernel (retry flavour of the traversal stack, Walk::push in mcpt_traverse.h): the rays of a launch that
 // lost a stack entry; the retrace kernel launched right behind traces them again with the scratch stack and clears the list.  `cap` is the
 // largest number of rays one launch can hold, so the list cannot overflow.
 struct RetryList {

@@ -19,18 +19,16 @@
 #include <cstdlib>
 
 #include "mcpt_kernels.h"
+#include "mcpt_traverse.h"
 
 namespace mcpt {
 
 namespace {
 
-constexpr int kBlock = 256;
 #ifndef MCPT_SHADE_BLOCK
 #define MCPT_SHADE_BLOCK 512
 #endif
 constexpr int kShadeBlock = MCPT_SHADE_BLOCK;  // k_shade: larger workgroups = fewer allocation atomics per hot counter
-
-MCPT_DI uint32_t lane_id() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
 
 // Block-aggregated queue allocation.  Up to kMaxAlloc counters are served by ONE round of atomics per
 // workgroup (lane k of wave 0 adds the block total of request k), instead of one returning atomic per
@@ -130,7 +128,7 @@ MCPT_DI void lds_copy16(void *dst, const void *src, uint32_t n16) {  // n16 16-b
 }
 // (the caller's __syncthreads follows: a kernel that stages both blocks pays for one barrier)
 MCPT_DI void stage_small_geom(DevScene &S, SmallGeomLds &L) {
-    // Quantised nodes become "prepared" nodes (traverse_loop, NF = 2): the 16-bit grid coordinates as floats relative to the grid origin,
+    // Quantised nodes become "prepared" nodes (node_visit, NF = 2): the 16-bit grid coordinates as floats relative to the grid origin,
     // x' = (float)q * cell, in the layout of Node.  Float nodes are copied as they are.  (Every node pointer the SMALL kernels follow ends up
     // as an LDS pointer or null on every path, so that the address-space inference sees no global / LDS mix.)
     const bool quant = S.qnodes != nullptr;
@@ -164,376 +162,6 @@ MCPT_DI void stage_small_lights(DevScene &S, SmallLightLds &L) {
     S.lights = L.lights;
     S.light_nodes = L.nodes;
     S.light_tris = L.tris;
-}
-
-// ------------------------------------------------------------------------------------------------
-// Traversal.  One lane per ray; the per-lane stack of child references lives in LDS as
-// stk[level][thread] so that the 64 lanes of a wave hit 64 consecutive banks.
-//
-// Result equivalence with BVHAccel::getIntersection (BVH.cpp:103-116), which visits both children and
-// never prunes: a primitive is tested here only if every ancestor box test of the reference passes
-// (same box test, same tree), children are visited near-first, and a subtree is skipped only when its
-// entry distance exceeds the best hit by a margin far above float rounding (closest hit) or lies beyond
-// the light sample (shadow rays).  Equal distances go to the larger primitive id.
-// ------------------------------------------------------------------------------------------------
-struct TraceResult {
-    double t;
-    int32_t prim;
-    uint32_t mat_bits;  // closest hit: material index | kMatTextured | kMatEmissive (TriGeom::mat_bits)
-    bool visible;       // shadow queries only
-    bool dropped;       // retry flavour: a stack entry was lost, the result is void (the ray goes to the retrace list)
-};
-
-// One traversal loop, three query kinds:
-//   kClosest   closest hit (BVH.cpp:95-116); subtrees entered beyond the best hit (+margin) are skipped.
-//   kWindow    shadow phase A: only subtrees whose [tmin,tmax] overlaps [dist-m, dist+m] are entered.  Finds
-//              every hit the visibility test |t - dist| < EPSILON (Scene.cpp:75) could accept; a hit with
-//              t <= dist - EPSILON met on the way proves occlusion at once.
-//   kOccluder  shadow phase B: any hit with t <= dist - EPSILON ends the search (subtrees entered beyond dist skipped).
-// The margin m = 1e-4*dist + 1e-2 is far above the float rounding of the slab test.
-enum { kClosest = 0, kWindow = 1, kOccluder = 2 };
-
-struct TraceState {
-    double best_t;
-    int32_t best_prim;
-    uint32_t best_mat;
-    bool occluded, found;
-    bool dropped;  // a stack entry was lost (retry flavour): the result is void
-#ifdef MCPT_TRAVERSAL_STATS
-    unsigned nv, nt, iters, maxsp;
-#endif
-};
-
-// The per-lane traversal stack: STK entries in LDS (column `tid` of stk[][kBlock]).  A ray holds at most one entry per inner ancestor
-// (tree height - 1), but the deepest stack any ray of the chess frames reaches is 11-12 entries (SAH trees of height 20-24) or 14-15
-// (LBVH, height 27-36; tools/traversal_stats_env.py), while every LDS entry costs 1 KB per workgroup and, beyond 19, resident
-// workgroups (up to 19 entries: 8 per CU, 20-22: 7, 23-26: 6, 32: 5, 48: 3).  Three flavours:
-//   plain   trees of up to 24 levels: STK >= height - 1 LDS entries, a push can never fail.
-//   retry   deeper trees (RETRY): 16 LDS entries; a push onto a full stack drops the entry and marks the ray (`dropped`).  The walk goes on
-//           (it only visits less) and its result is thrown away: the ray goes to the kernel's RETRACE LIST (RetryList), and a small
-//           kernel launched right behind (k_retrace_closest / k_retrace_shadow / k_primary_retrace) traces the listed rays again with the
-//   scratch flavour (STK = 0, SCR): the whole stack is a per-lane array of kMaxBvhHeight entries in scratch memory -- slow and exact.
-// The hot kernels carry no second copy of the loop: a retrace inlined behind the first walk was measured first and cost them 6-8 %
-// (registers, scratch set-up, instruction cache); so did an overflow array behind the LDS entries inside the loop (a compare per pop).
-// Results never depend on the stack size: the checking build (-DMCPT_FORCE_RETRY -DMCPT_STK_RETRY=4) sends most rays of every scene
-// through the lists and renders the same frames (tests/test_gpu_checks.py).  Measured, chess frame with the GPU-built tree (27
-// levels): 32 LDS entries 3700 Msamples/s, retry flavour 4160 (8 workgroups per CU instead of 5).
-#ifndef MCPT_STK_RETRY
-#define MCPT_STK_RETRY 16
-#endif
-constexpr int kStkRetry = MCPT_STK_RETRY;  // LDS entries of the retry flavour (the checking build: 4, and every tree uses it)
-// (Macros, not functions: the plain flavour must compile to exactly the statements it had before the other flavours existed.)
-#define MCPT_STK_PUSH(v)                                                                                           \
-    do {                                                                                                           \
-        if (SCR) {                                                                                                 \
-            if (sp < kMaxBvhHeight) scr[sp++] = (v); /* never full: mcpt_scene_create refuses deeper trees */      \
-        } else {                                                                                                   \
-            if (sp < STK) stk[sp++][tid] = (v); /* plain: never full (STK >= height - 1, asserted at creation) */  \
-            else if (MARK) st.dropped = true;   /* retry: the entry is lost, the ray is traced again */            \
-        }                                                                                                          \
-    } while (0)
-#define MCPT_STK_POP() (SCR ? scr[--sp] : stk[--sp][tid]) /* sp > 0 */
-
-// Speculative while-while loop (Aila & Laine 2009, "Understanding the efficiency of ray traversal on GPUs").  A plain
-// `if (inner) node-step else leaf-test` loop makes a wave pay for BOTH bodies in nearly every iteration (with 64 lanes, some lane
-// always holds a leaf).  Here a round has two phases:
-//   phase 1  inner nodes only.  A lane that reaches a leaf PARKS it and keeps descending from its stack (speculatively: the
-//            parked leaf might have shortened the ray); a lane that reaches a second leaf, or runs out of work, waits.  The phase ends
-//            when at most kLeafVote lanes of the wave are still looking for their first leaf.
-//   phase 2  every lane tests its parked leaf; a second leaf waiting in `cur` is parked for the next round.
-// Measured on the chess frame (A/B on one box, same build otherwise): plain loop 4190 Msamples/s; this loop with vote 0: 4375,
-// 4: 4515, 8: 4540, 12: 4540, 16: 4525; testing the second leaf in the same round instead of parking it: 4430.  The serialised
-// k_trace_closest went from 82.5 to 72 ms per 2 x 256 spp.  Same tests, same results: the order of primitive tests does not
-// matter (ties go to the larger primitive id), and the pruning margins are unchanged.
-//
-// INST (scenes with instanced objects, csrc/mcpt_scene.cpp): a leaf index >= n_leaf_prims is an instance.  Entering it moves the
-// origin used by the BOX tests by -shift, pushes an exit marker and continues in the prototype's shared subtree, whose leaves hold
-// local triangle indices; primitive tests always use the world ray and the object's own world-space triangle
-// (first_tri + local index), so hits are exactly those of the un-instanced tree.  Popping the marker restores the origin.
-constexpr int32_t kNoWork = (int32_t)0x80000000;   // neither an inner node (>= 0) nor a leaf (~index, index < 2^31 - 2)
-constexpr int32_t kInstExit = (int32_t)0x80000001; // stack marker: the subtree of the current instance is exhausted
-#ifndef MCPT_LEAF_VOTE
-#define MCPT_LEAF_VOTE 12
-#endif
-constexpr int kLeafVote = MCPT_LEAF_VOTE;
-// NF, the node format: 0 float boxes (the exact ones: the reference's own box semantics), 1 quantised (QNode), 2 "prepared" -- the
-// SMALL kernels' LDS copy of the quantised nodes, converted once per workgroup to floats RELATIVE to the grid origin (x' = q * cell), so that
-// a slab bound is ONE fma, x' * inv + (origin - o) * inv, with no integer-to-float conversion per visit (12 of the ~55 vector instructions
-// of a visit).  Same grid, same conservative boxes as format 1 (the error of the form is 0.4 % of the one-cell margin).
-template <int MODE, int STK, bool SCR, bool MARK, bool FAST, int NF, bool INST>
-MCPT_DI void traverse_loop(const DevScene &S, const Ray &r, float dist, int32_t (*stk)[kBlock], int32_t *scr, int tid, TraceState &st) {
-    constexpr bool QUANT = NF != 0;
-    static_assert(NF != 2 || !INST, "prepared nodes: small scenes, never instanced");
-    QRay qr;
-    if (QUANT) qr = make_qray(S, r);
-    Ray rb = r;               // the ray of the box tests (origin shifted inside an instance)
-    int32_t prim_base = 0;    // first triangle of the current instance (0 at the top level: leaf indices are primitive ids)
-    const uint32_t n_leaf_prims = INST ? (uint32_t)S.n_leaf_prims : 0x7ffffffeu;
-    const float margin = dist * 1e-4f + 1e-2f;
-    float lim = (MODE == kClosest) ? INFINITY : (dist + margin);
-    const float lo = dist - margin;
-    float tm, tx;
-    int32_t cur = S.root;
-    if (!box_hit<FAST>(S.root_min, S.root_max, r, tm, tx)) return;
-    int sp = 0;
-    int32_t leaf = kNoWork;
-    if (cur < 0 && (uint32_t)(~cur) < n_leaf_prims) {  // the root is a leaf (a scene of one primitive)
-        leaf = cur;
-        cur = kNoWork;
-    }
-    while (true) {
-        // ---- phase 1: inner nodes
-        while (true) {
-#ifdef MCPT_TRAVERSAL_STATS
-            st.iters++;
-#endif
-            if (INST) {
-                if (cur == kInstExit) {  // back to the top level
-                    rb.o = r.o;
-                    prim_base = 0;
-                    if (QUANT) qr.b = make_qray(S, r).b;
-                    cur = (sp == 0) ? kNoWork : MCPT_STK_POP();
-                }
-                if (cur > kInstExit && cur < 0 && (uint32_t)(~cur) >= n_leaf_prims) {  // an instance: enter its prototype's subtree
-                    const InstRec I = S.inst[(uint32_t)(~cur) - n_leaf_prims];
-                    rb.o = mk3(r.o.x - I.shift[0], r.o.y - I.shift[1], r.o.z - I.shift[2]);
-                    prim_base = I.first_tri;
-                    if (QUANT) qr.b = make_qray(S, rb).b;
-                    MCPT_STK_PUSH(kInstExit);
-                    cur = I.root;
-                }
-            }
-            if (cur >= 0) {
-#ifdef MCPT_TRAVERSAL_STATS
-                st.nv++;
-#endif
-                int32_t left, right;
-                float tl = 0.f, tr = 0.f, txl = 0.f, txr = 0.f;
-                bool hl, hr;
-                // every inner node has two children (the builders only emit an inner node for >= 2 primitives)
-                if (NF == 2) {  // prepared node (LDS): float boxes relative to the grid origin
-                    const float4 *np = S.pnodes + 4 * cur;
-                    const float4 a = np[0], b = np[1], c = np[2], e = np[3];
-                    left = __float_as_int(e.x);
-                    right = __float_as_int(e.y);
-                    hl = pbox_hit<FAST>(S, rb, qr, a.x, a.y, a.z, a.w, b.x, b.y, tl, txl);
-                    hr = pbox_hit<FAST>(S, rb, qr, b.z, b.w, c.x, c.y, c.z, c.w, tr, txr);
-                } else if (QUANT) {  // 32-byte node: two 16-byte requests per lane instead of four
-                    const uint4 *np = reinterpret_cast<const uint4 *>(S.qnodes + cur);
-                    const uint4 a = np[0], b = np[1];
-                    left = (int32_t)b.z;
-                    right = (int32_t)b.w;
-                    hl = qbox_hit<FAST>(S, rb, qr, a.x & 0xffffu, a.x >> 16, a.y & 0xffffu, a.y >> 16, a.z & 0xffffu, a.z >> 16, tl, txl);
-                    hr = qbox_hit<FAST>(S, rb, qr, a.w & 0xffffu, a.w >> 16, b.x & 0xffffu, b.x >> 16, b.y & 0xffffu, b.y >> 16, tr, txr);
-                } else {
-                    const float4 *np = reinterpret_cast<const float4 *>(S.nodes + cur);
-                    const float4 a = np[0], b = np[1], c = np[2], e = np[3];
-                    const float lmin[3] = {a.x, a.y, a.z}, lmax[3] = {a.w, b.x, b.y};
-                    const float rmin[3] = {b.z, b.w, c.x}, rmax[3] = {c.y, c.z, c.w};
-                    left = __float_as_int(e.x);
-                    right = __float_as_int(e.y);
-                    hl = box_hit<FAST>(lmin, lmax, rb, tl, txl);
-                    hr = box_hit<FAST>(rmin, rmax, rb, tr, txr);
-                }
-                hl = hl && !(tl > lim);
-                hr = hr && !(tr > lim);
-                if (MODE == kWindow) {
-                    hl = hl && !(txl < lo);
-                    hr = hr && !(txr < lo);
-                }
-                if (hl && hr) {
-                    const bool swap = tr < tl;
-                    const int32_t nearc = swap ? right : left, farc = swap ? left : right;
-#ifdef MCPT_TRAVERSAL_STATS
-                    const int sp_before = sp;
-#endif
-                    MCPT_STK_PUSH(farc);
-#ifdef MCPT_TRAVERSAL_STATS
-                    st.maxsp = max(st.maxsp, sp == sp_before ? 1000u : (unsigned)sp);  // (1000: a dropped entry)
-#endif
-                    cur = nearc;
-                } else if (hl) {
-                    cur = left;
-                } else if (hr) {
-                    cur = right;
-                } else {
-                    cur = (sp == 0) ? kNoWork : MCPT_STK_POP();
-                }
-                if (cur < 0 && (uint32_t)(~cur) < n_leaf_prims && leaf == kNoWork) {  // first leaf of the round: park it and keep traversing
-                    leaf = ~(prim_base + ~cur);  // (a global primitive id from here on)
-                    cur = (sp == 0) ? kNoWork : MCPT_STK_POP();
-                }
-            }
-            // a lane can still make progress on nodes if it holds an inner node (or, INST, an instance / exit marker)
-            const bool workable = INST ? (cur >= 0 || (cur > kNoWork && (uint32_t)(~cur) >= n_leaf_prims)) : (cur >= 0);
-            if (__popcll(__ballot(leaf == kNoWork && workable)) <= kLeafVote) break;
-        }
-        // ---- phase 2: the parked leaf
-        if (leaf != kNoWork) {
-#ifdef MCPT_TRAVERSAL_STATS
-            st.nt++;
-#endif
-            const int32_t prim = ~leaf;
-            double t = 0, u, v;
-            bool h;
-            uint32_t mb;
-            if (prim < S.n_tri) {
-                const TriGeom g = S.tri_geom[prim];
-                mb = g.mat_bits;
-                h = tri_hit(g, r, t, u, v);
-            } else {
-                float ts = 0.f;
-                const SphereRec sph = S.spheres[prim - S.n_tri];
-                mb = sph.mat_bits;
-                h = sphere_hit(sph, r, ts);
-                t = (double)ts;
-            }
-            if (h) {
-                if (MODE != kClosest) {
-                    const double dd = t - (double)dist;
-                    if (dd <= -(double)kEps) {
-                        st.occluded = true;
-                        return;
-                    }
-                    if (fabs(dd) < (double)kEps) st.found = true;
-                } else if (t < st.best_t || (t == st.best_t && prim > st.best_prim)) {
-                    st.best_t = t;
-                    st.best_prim = prim;
-                    st.best_mat = mb;
-                    lim = (float)(t + (fabs(t) * 1e-4 + 1e-2));
-                }
-            }
-            leaf = kNoWork;
-            if (cur < 0 && (uint32_t)(~cur) < n_leaf_prims) {  // a second leaf was waiting: park it for the next round
-                leaf = ~(prim_base + ~cur);
-                cur = (sp == 0) ? kNoWork : MCPT_STK_POP();
-            }
-        }
-        if (cur == kNoWork && leaf == kNoWork) return;
-    }
-}
-
-// Primitive test shared with the leaf branch of the loop (k_direct tests the sampled light primitive with it).
-MCPT_DI bool prim_hit(const DevScene &S, int32_t prim, const Ray &r, double &t) {
-    if (prim < S.n_tri) {
-        double u, v;
-        return tri_hit(S.tri_geom[prim], r, t, u, v);
-    }
-    float ts = 0.f;
-    const bool h = sphere_hit(S.spheres[prim - S.n_tri], r, ts);
-    t = (double)ts;
-    return h;
-}
-
-// The dispatch of one query over the loop's instantiations: slab-test flavour (wave-uniform: the exact NaN-faithful chain only when some
-// lane of the wave has a non-finite reciprocal, i.e. a zero direction component; otherwise the bit-identical max3/min3 form), node
-// format, instancing.  Shadow queries, Scene.cpp:74-75: a light sample counts iff the CLOSEST hit lies within EPSILON of the light
-// distance, i.e. iff some hit lies in the window AND no hit lies at or below dist - EPSILON; `found`: the window search is already
-// settled (k_direct found the sampled primitive in the window).
-#define MCPT_TL(MODE, FAST, STKN, SCRB, MARKB, SCRP)                                                                  \
-    do {                                                                                                              \
-        if (PREP && S.pnodes) { /* SMALL kernels of a scene with quantised nodes */                                   \
-            traverse_loop<MODE, STKN, SCRB, MARKB, FAST, (PREP ? 2 : 1), false>(S, r, dist, stk, SCRP, tid, st);      \
-        } else if (S.inst) {                                                                                          \
-            if (S.qnodes) traverse_loop<MODE, STKN, SCRB, MARKB, FAST, 1, true>(S, r, dist, stk, SCRP, tid, st);      \
-            else traverse_loop<MODE, STKN, SCRB, MARKB, FAST, 0, true>(S, r, dist, stk, SCRP, tid, st);               \
-        } else {                                                                                                      \
-            if (S.qnodes) traverse_loop<MODE, STKN, SCRB, MARKB, FAST, 1, false>(S, r, dist, stk, SCRP, tid, st);     \
-            else traverse_loop<MODE, STKN, SCRB, MARKB, FAST, 0, false>(S, r, dist, stk, SCRP, tid, st);              \
-        }                                                                                                             \
-    } while (0)
-#define MCPT_QUERY(STKN, SCRB, MARKB, SCRP)                                        \
-    do {                                                                           \
-        const bool plain = __all(ray_is_plain(r)) != 0;                            \
-        if (SHADOW) {                                                              \
-            if (plain) {                                                           \
-                if (!found) MCPT_TL(kWindow, true, STKN, SCRB, MARKB, SCRP);       \
-                if (st.found && !st.occluded) MCPT_TL(kOccluder, true, STKN, SCRB, MARKB, SCRP);  \
-            } else {                                                               \
-                if (!found) MCPT_TL(kWindow, false, STKN, SCRB, MARKB, SCRP);      \
-                if (st.found && !st.occluded) MCPT_TL(kOccluder, false, STKN, SCRB, MARKB, SCRP); \
-            }                                                                      \
-        } else if (plain) {                                                        \
-            MCPT_TL(kClosest, true, STKN, SCRB, MARKB, SCRP);                      \
-        } else {                                                                   \
-            MCPT_TL(kClosest, false, STKN, SCRB, MARKB, SCRP);                     \
-        }                                                                          \
-    } while (0)
-
-// The scratch flavour: the ray again, from the start, with the whole stack in a per-lane array (see MCPT_STK_PUSH).
-template <bool SHADOW>
-MCPT_DI void traverse_again(const DevScene &S, const Ray &r, float dist, int32_t (*stk)[kBlock], int tid, bool found, TraceState &st) {
-    constexpr bool PREP = false;
-    int32_t scr[kMaxBvhHeight];
-    st.best_t = DBL_MAX;
-    st.best_prim = -1;
-    st.best_mat = 0;
-    st.occluded = false;
-    st.found = found;
-    st.dropped = false;
-    MCPT_QUERY(0, true, false, scr);
-}
-
-template <bool SHADOW, int STK, bool RETRY, bool PREP = false>
-MCPT_DI TraceResult traverse(const DevScene &S, const Ray &r, float dist, int32_t (*stk)[kBlock], int tid, bool found = false) {
-    TraceState st;
-    st.best_t = DBL_MAX;
-    st.best_prim = -1;
-    st.best_mat = 0;
-    st.occluded = false;
-    st.found = found;
-    if (RETRY) st.dropped = false;
-#ifdef MCPT_TRAVERSAL_STATS
-    st.nv = st.nt = st.iters = st.maxsp = 0;
-#endif
-    MCPT_QUERY(STK, false, RETRY, nullptr);
-#ifdef MCPT_TRAVERSAL_STATS
-    if (S.dbg) {  // [kind*8 + {rays, node visits, prim tests, occluded/hit, wave-iterations*64, found}]
-        const int base = SHADOW ? 8 : 0;
-        atomicAdd(&S.dbg[base + 0], 1ull);
-        atomicAdd(&S.dbg[base + 1], (unsigned long long)st.nv);
-        atomicAdd(&S.dbg[base + 2], (unsigned long long)st.nt);
-        atomicAdd(&S.dbg[base + 3], (unsigned long long)(SHADOW ? (st.occluded ? 1 : 0) : (st.best_prim >= 0 ? 1 : 0)));
-        unsigned mx = st.iters;
-        for (int o = 32; o > 0; o >>= 1) mx = max(mx, (unsigned)__shfl_xor((int)mx, o));
-        if (lane_id() == 0) atomicAdd(&S.dbg[base + 4], (unsigned long long)mx * 64ull);
-        atomicAdd(&S.dbg[base + 5], (unsigned long long)(SHADOW ? (st.found ? 1 : 0) : 0));
-        atomicMax(&S.dbg[SHADOW ? 7 : 6], (unsigned long long)st.maxsp);  // deepest stack of any ray (1000: an entry was dropped)
-    }
-#endif
-    return TraceResult{st.best_t, st.best_prim, st.best_mat, !st.occluded && st.found, RETRY ? st.dropped : false};
-}
-
-// The retrace of one listed ray (scratch flavour).
-template <bool SHADOW>
-MCPT_DI TraceResult traverse_scratch(const DevScene &S, const Ray &r, float dist, int32_t (*stk)[kBlock], int tid, bool found = false) {
-    TraceState st;
-#ifdef MCPT_TRAVERSAL_STATS
-    st.nv = st.nt = st.iters = st.maxsp = 0;
-#endif
-    traverse_again<SHADOW>(S, r, dist, stk, tid, found, st);
-    return TraceResult{st.best_t, st.best_prim, st.best_mat, !st.occluded && st.found, false};
-}
-
-MCPT_DI void retry_append(const RetryList &rl, uint32_t v) {  // (one atomic per lost ray: there are next to none)
-    const uint32_t k = atomicAdd(rl.count, 1u);
-    if (k < rl.cap) rl.items[k] = v;
-}
-// end of a retrace kernel: the last workgroup to finish clears the list for the next launch
-MCPT_DI void retry_finish(const RetryList &rl) {
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        __threadfence();
-        if (atomicAdd(rl.done, 1u) == gridDim.x - 1u) {
-            *rl.count = 0u;
-            *rl.done = 0u;
-        }
-    }
-}
-
-MCPT_DI uint4 pack_hit(double t, int32_t prim, uint32_t mat_bits) {  // {t lo, t hi, prim, TriGeom::mat_bits}
-    const unsigned long long tb = (unsigned long long)__double_as_longlong(t);
-    return make_uint4((uint32_t)tb, (uint32_t)(tb >> 32), (uint32_t)prim, mat_bits);
 }
 
 template <int STK, bool RETRY, bool SMALL>
@@ -578,7 +206,7 @@ __global__ __launch_bounds__(kBlock) void k_retrace_closest(DevScene S, const fl
 // The common configuration only (quantised nodes, no instancing); the rays of the chunk that have a zero direction component are traced
 // by the generic path before the loop starts (round 3: tracing them inside a refill, with the rest of the wave parked in the middle of
 // its own walks, lost the rest of the chunk when a refill handed out nothing but such rays -- tests/test_gpu_small_scene.py has the
-// case).  Same tests per ray as traverse_loop<kClosest, STK, true, true, false>, hence the same hits.
+// case).  The walk itself is traverse_loop's, piece by piece (csrc/mcpt_traverse.h): quantised or prepared nodes, the plain slab test.
 #ifndef MCPT_REFILL_MIN
 #define MCPT_REFILL_MIN 16
 #endif
@@ -614,13 +242,9 @@ __global__ __launch_bounds__(kBlock, (STK <= 20 ? MCPT_REFILL_WAVES : 1)) void k
         int32_t my = -1;  // index of the ray this lane is tracing
         Ray r = make_ray(mk3(0, 0, 0), mk3(0, 0, 1));
         QRay qr = make_qray(S, r);
-        float lim = INFINITY;
-        double best_t = DBL_MAX;
-        int32_t best_prim = -1;
-        uint32_t best_mat = 0;
-        int32_t cur = kNoWork, leaf = kNoWork;
-        int sp = 0;
-        bool dropped = false;  // RETRY: this ray lost a stack entry (see MCPT_STK_PUSH)
+        TraceState st;
+        trace_reset(st, false);
+        Walk<STK, false, RETRY> w{StackMem{stk, nullptr, tid}};
         // Rays with a zero direction component (non-finite reciprocals: rare) need the NaN-faithful slab chain, which the loop below
         // does not carry.  They are traced first, by the generic path, with the whole wave at one place (a wave without such a ray
         // pays for four direction loads per lane, which the refills below then find in the cache); the refill skips them.
@@ -642,10 +266,10 @@ __global__ __launch_bounds__(kBlock, (STK <= 20 ? MCPT_REFILL_WAVES : 1)) void k
         }
         while (true) {
             // ---- finished lanes: store, refill
-            const bool idle = cur == kNoWork && leaf == kNoWork;
+            const bool idle = w.idle();
             if (idle && my >= 0) {
-                if (RETRY && dropped) retry_append(rl, (uint32_t)my);  // (k_retrace_closest traces it again)
-                else hit[my] = pack_hit(best_t, best_prim, best_mat);
+                if (RETRY && st.dropped) retry_append(rl, (uint32_t)my);  // (k_retrace_closest traces it again)
+                else hit[my] = pack_hit(st.best_t, st.best_prim, st.best_mat);
                 my = -1;
             }
             const unsigned long long im = __ballot(idle);
@@ -657,17 +281,8 @@ __global__ __launch_bounds__(kBlock, (STK <= 20 ? MCPT_REFILL_WAVES : 1)) void k
                     if (ray_is_plain(r)) {  // (the others were traced before the loop: the lane stays idle and is refilled again)
                         my = (int32_t)idx;
                         qr = make_qray(S, r);
-                        lim = INFINITY;
-                        best_t = DBL_MAX;
-                        best_prim = -1;
-                        best_mat = 0;
-                        sp = 0;
-                        dropped = false;
-                        float tm, tx;
-                        if (box_hit<true>(S.root_min, S.root_max, r, tm, tx)) {
-                            if (S.root >= 0) cur = S.root;
-                            else leaf = S.root;  // a scene of one primitive
-                        }
+                        trace_reset(st, false);
+                        walk_start<true, false>(w, S, r, INFINITY);
                     }
                 }
                 next += n_idle;
@@ -676,78 +291,12 @@ __global__ __launch_bounds__(kBlock, (STK <= 20 ? MCPT_REFILL_WAVES : 1)) void k
                 if (next < end) continue;  // every ray just handed out had been traced before the loop: hand out the next ones
                 break;
             }
-            // ---- phase 1: inner nodes (see traverse_loop)
+            // ---- one round of the speculative loop (traverse_loop): inner nodes until the vote, then the parked leaf
             while (true) {
-                if (cur >= 0) {
-                    int32_t left, right;
-                    float tl = 0.f, tr = 0.f, txl = 0.f, txr = 0.f;
-                    bool hl, hr;
-                    if constexpr (SMALL) {  // prepared nodes in LDS (stage_small_geom)
-                        const float4 *np = S.pnodes + 4 * cur;
-                        const float4 a = np[0], b = np[1], c = np[2], e = np[3];
-                        left = __float_as_int(e.x);
-                        right = __float_as_int(e.y);
-                        hl = pbox_hit<true>(S, r, qr, a.x, a.y, a.z, a.w, b.x, b.y, tl, txl);
-                        hr = pbox_hit<true>(S, r, qr, b.z, b.w, c.x, c.y, c.z, c.w, tr, txr);
-                    } else {
-                        const uint4 *np = reinterpret_cast<const uint4 *>(S.qnodes + cur);
-                        const uint4 a = np[0], b = np[1];
-                        left = (int32_t)b.z;
-                        right = (int32_t)b.w;
-                        hl = qbox_hit<true>(S, r, qr, a.x & 0xffffu, a.x >> 16, a.y & 0xffffu, a.y >> 16, a.z & 0xffffu, a.z >> 16, tl, txl);
-                        hr = qbox_hit<true>(S, r, qr, a.w & 0xffffu, a.w >> 16, b.x & 0xffffu, b.x >> 16, b.y & 0xffffu, b.y >> 16, tr, txr);
-                    }
-                    hl = hl && !(tl > lim);
-                    hr = hr && !(tr > lim);
-                    if (hl && hr) {
-                        const bool swap = tr < tl;
-                        const int32_t nearc = swap ? right : left, farc = swap ? left : right;
-                        if (sp < STK) stk[sp++][tid] = farc;
-                        else if (RETRY) dropped = true;
-                        cur = nearc;
-                    } else if (hl) {
-                        cur = left;
-                    } else if (hr) {
-                        cur = right;
-                    } else {
-                        cur = (sp == 0) ? kNoWork : stk[--sp][tid];
-                    }
-                    if (cur < 0 && cur != kNoWork && leaf == kNoWork) {
-                        leaf = cur;
-                        cur = (sp == 0) ? kNoWork : stk[--sp][tid];
-                    }
-                }
-                if (__popcll(__ballot(leaf == kNoWork && cur >= 0)) <= kLeafVote) break;
+                if (w.cur >= 0) descend<kClosest>(w, node_visit<(SMALL ? 2 : 1), true>(S, r, qr, w.cur), 0.f, st);
+                if (__popcll(__ballot(w.leaf == kNoWork && w.cur >= 0)) <= kLeafVote) break;
             }
-            // ---- phase 2: the parked leaf
-            if (leaf != kNoWork) {
-                const int32_t prim = ~leaf;
-                double t = 0, u, v;
-                bool h;
-                uint32_t mb;
-                if (prim < S.n_tri) {
-                    const TriGeom g = S.tri_geom[prim];
-                    mb = g.mat_bits;
-                    h = tri_hit(g, r, t, u, v);
-                } else {
-                    float ts = 0.f;
-                    const SphereRec sph = S.spheres[prim - S.n_tri];
-                    mb = sph.mat_bits;
-                    h = sphere_hit(sph, r, ts);
-                    t = (double)ts;
-                }
-                if (h && (t < best_t || (t == best_t && prim > best_prim))) {
-                    best_t = t;
-                    best_prim = prim;
-                    best_mat = mb;
-                    lim = (float)(t + (fabs(t) * 1e-4 + 1e-2));
-                }
-                leaf = kNoWork;
-                if (cur < 0 && cur != kNoWork) {
-                    leaf = cur;
-                    cur = (sp == 0) ? kNoWork : stk[--sp][tid];
-                }
-            }
+            leaf_step<kClosest>(w, S, r, 0.f, st);
         }
     }
 }
@@ -923,10 +472,11 @@ MCPT_DI bool primary_ray(const DevScene &S, const CameraConst &cam, const Render
         if (cs[q4] == kCandNone) continue;
         const int32_t prim = ~cs[q4];
         double t = 0;
-        if (prim_hit(S, prim, r, t) && (t < tr.t || (t == tr.t && prim > tr.prim))) {
+        uint32_t mb;
+        if (leaf_hit(S, prim, r, t, mb) && (t < tr.t || (t == tr.t && prim > tr.prim))) {
             tr.t = t;
             tr.prim = prim;
-            tr.mat_bits = prim < S.n_tri ? S.tri_geom[prim].mat_bits : S.spheres[prim - S.n_tri].mat_bits;
+            tr.mat_bits = mb;
         }
     }
     return true;
@@ -1635,8 +1185,9 @@ __global__ __launch_bounds__(kBlock, MCPT_DIRECT_WAVES) void k_direct(DevScene S
             // dist - EPSILON settles the sample as invisible (no ray at all); a hit inside the window settles the window
             // search, leaving only the occluder search to k_trace_shadow; otherwise the full query runs.
             double t = 0;
+            uint32_t mb;
             window = true;
-            if (prim_hit(S, light_prim, make_ray(q, ws), t)) {
+            if (leaf_hit(S, light_prim, make_ray(q, ws), t, mb)) {
                 const double dd = t - (double)dist;
                 if (dd <= -(double)kEps) {
                     c = 0.f;
@@ -1927,7 +1478,7 @@ void launch_init_free(uint32_t *free_slots, Counters *c, uint32_t pool, uint32_t
     hipLaunchKernelGGL(k_init_free, dim3(blocks(pool)), dim3(kBlock), 0, s, free_slots, c, pool, start, mask);
 }
 
-// Stack flavour by tree height (see MCPT_STK_PUSH): <= 17 levels: 16 LDS entries; <= 20: kStkB; <= kPlainMaxHeight (24): 24; deeper: the retry
+// Stack flavour by tree height (see Walk in mcpt_traverse.h): <= 17 levels: 16 LDS entries; <= 20: kStkB; <= kPlainMaxHeight (24): 24; deeper: the retry
 // flavour (16 LDS entries, retrace list).  (-DMCPT_LDS_ONLY_STACKS: 24 / 32 / 48-entry LDS stacks for deep trees instead, for A/B measurements;
 // -DMCPT_FORCE_RETRY, the checking build: the retry flavour for every tree with -DMCPT_STK_RETRY=4 LDS entries, so that most rays are
 // traced again.)  RETRACE: the launch of the retrace kernel, issued right behind a retry-flavour kernel on the same stream.

@@ -71,7 +71,7 @@ def test_skipped_direct_lighting_is_exactly_zero(pkg, hip, hip_check, oracle, na
 def test_retry_flavour_of_the_traversal_stack(pkg, hip, hip_check, builder):
     """Trees deeper than 24 levels are traversed with 16 stack entries in LDS; a ray that would need more loses an entry, is marked and
     put on the kernel's retrace list, and a small kernel launched right behind traces the listed rays again with a per-lane stack in
-    scratch memory (MCPT_STK_PUSH / RetryList / k_retrace_* in csrc/mcpt_kernels.hip) -- which no ray of these scenes needs.  The
+    scratch memory (Walk::push in csrc/mcpt_traverse.h, RetryList / k_retrace_* in csrc/mcpt_kernels.hip) -- which no ray of these scenes needs.  The
     checking build uses that flavour for every tree with FOUR LDS entries, so most of its rays (primary, continuation and shadow) go
     through the lists: same intersections, same frames, same counters."""
     rng = np.random.default_rng(11)
