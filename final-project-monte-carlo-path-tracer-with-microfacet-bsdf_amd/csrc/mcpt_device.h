@@ -106,6 +106,7 @@ struct DevScene {
     // vertex (q, n) if  n.L < -(light_plane[0] + light_plane[1] * |L|_1);  {R + kHalfspaceSlack * (|light_center|_1 + R), kHalfspaceSlack}
     float light_plane[2];
     float tir_bound_factor;  // read by the checking build only (tir_bound_factor(), mcpt_kernels.hip): 1.001 x MCPT_TIR_BOUND_SCALE
+    float cone_tol_scale;    // read by the checking build only (cone_tolerance(), mcpt_kernels.hip): MCPT_CONE_TOL_SCALE
     int32_t root, n_tri, n_lights, env_w, env_h, height;
     // Small-scene flavour (kernels' SMALL template flag, mcpt_kernels.hip): the whole traversal data set -- nodes, TriGeom, spheres -- and
     // the light tables fit a few KB, and every workgroup copies them into LDS once.  The counts say how much there is to copy.

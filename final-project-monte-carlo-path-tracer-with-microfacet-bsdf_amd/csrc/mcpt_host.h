@@ -204,6 +204,8 @@ struct Knobs {
                                         // scale makes the rule wrong on purpose: the negative control of tests/test_gpu_direct_halfspace.py)
     float tir_bound_scale = 1.f;        // MCPT_TIR_BOUND_SCALE: multiplies the bound of direct_is_zero's total-internal-reflection rule (below
                                         // 1: wrong on purpose, the negative control of tests/test_gpu_direct_tir.py)
+    float cone_tol_scale = 1.f;         // MCPT_CONE_TOL_SCALE: multiplies the two tolerances of direct_is_zero's cone rule (below 1: wrong
+                                        // on purpose, the negative control of tests/test_gpu_direct_cone.py)
     float cull_rho_scale = 1.f;         // MCPT_CULL_RHO_SCALE: multiplies the sky cull's final rho (below 1: wrong on purpose, the negative
                                         // control of tests/test_gpu_cull_classify.py)
     bool sky_cull = true;       // MCPT_SKY_CULL=0: trace the pixels that can only see the background too

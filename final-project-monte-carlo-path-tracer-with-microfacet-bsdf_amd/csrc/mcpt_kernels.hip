@@ -704,13 +704,22 @@ MCPT_DI bool sample_light(const DevScene &S, const float u[4], f3 &x_l, f3 &n_l,
 //   * no emitter in the scene;
 //   * a conductor seen from inside: directLighting is called with isReflect = false (Scene.cpp:115-116) and
 //     eval(.., false) returns 0 for both conductor types (Material.hpp:355-357,396-399);
-//   * a Dirac BSDF (Material.hpp:375-403) is non-zero only if h.N >= 1 - EPSILON, i.e. the half vector lies within
-//     acos(1 - 1e-4) = 0.01414 rad of N.  Reflection: ws then lies within 2 * 0.01414 rad of the mirror direction
-//     r = 2 (N.wo) N - wo.  Refraction (dielectric seen from inside, ws outside): ws = -ior*wo - lambda*h, so it
-//     lies within |lambda| * 0.01414 / cos(theta_i) <= 0.094 rad of the Snell direction when ior * sin(theta_o) <= 0.9.
+//   * a Dirac BSDF (Material.hpp:375-403) is non-zero only if h.N >= 1 - EPSILON, which in float means h.N >= 1 - 1.01e-4 exactly (see the
+//     total-internal-reflection rule below): the half vector lies within acos(1 - 1.01e-4) = 0.014213 rad of N, its part tangential to
+//     N is at most s = 0.014212 of its length.  Reflection: ws is the mirror image of wo about h, so it lies within 2 * 0.014213 =
+//     0.0285 rad of the mirror direction r = 2 (N.wo) N - wo, whatever the index.  Refraction (dielectric seen from inside, ws outside):
+//     h is the direction of hv = -ws - ior wo, so |ws_t + ior wo_t| = |hv_t| <= s |hv| <= s (1 + ior) =: d.  The Snell direction has
+//     r_t = -ior wo_t with |r_t| = sqrt(sin2) <= 0.9 behind the gate sin2 < 0.81, so ws_t lies within d of r_t in the unit disc.  Lifting
+//     the straight segment from r_t to ws_t onto the hemisphere stretches it by at most 1 / sqrt(1 - rho^2) at radius rho <= 0.9 + t after
+//     a length t, hence  angle(ws, r) <= asin(0.9 + d) - asin(0.9).  That bound GROWS with the index (ior 1.9: 0.106, 2.353: 0.126, 2.5:
+//     0.1327, 3: 0.156, 5: 0.279 rad; beyond ior 6.03 it does not exist, 0.9 + d >= 1), so the constant tolerance holds up to a limit only:
+//     the rule claims a refraction vertex for  0 < ior <= kConeMaxIor = 2.5  and declines above (and for an index that is not a number).
+//     Every index below one is covered too: the proof uses nothing but |hv| <= 1 + ior.  The shipped presets reach 2.353 (iorA 1.3,
+//     iorB 0.2, blue).  tests/test_direct_cone_cpu.py measures the farthest passing ws per index: 0.062 rad at 2.353, above 0.15 from 4.5.
 //     Every light sample lies inside the cone of half-angle asin(R / D) around the direction to the centre of the
 //     emitters' bounding sphere (radius R, distance D > 1.01 R).  If r is farther from that cone than the tolerance
-//     (0.06 rad for reflection, 0.15 rad for refraction: > 1.5x the bounds above) no sample can give a non-zero eval.
+//     (0.06 rad for reflection: 2.1x its bound; 0.15 rad for refraction: 1.13x its bound at ior 2.5, 0.017 rad to spare against float
+//     roundings of 1e-6) no sample can give a non-zero eval.
 //   * the half-space rule, for EVERY material (emitters_behind): all emitters lie behind the tangent plane of the vertex.
 //     k_direct evaluates eval(ws, wo, n, isReflect = !inside) with ws = normalized(x_l - q) and inside = (wo.n < 0).  If the float value
 //     ws.n it computes is < 0, every branch of mat_eval returns 0.f at its first test:
@@ -754,6 +763,24 @@ MCPT_DI float tir_bound_factor(const DevScene &S) {
 #endif
 }
 
+// The cone rule's refraction half is proven up to this index (see above); beyond it the rule declines.
+constexpr float kConeMaxIor = 2.5f;
+
+// cos and sin of a cone tolerance and the slack on the cosine that goes with it: the constants, or those of the angle and the slack
+// scaled by the checking build's knob MCPT_CONE_TOL_SCALE.  Returns the slack.
+MCPT_DI float cone_tolerance(const DevScene &S, float angle, float c, float s, float &cm, float &sm) {
+    cm = c;
+    sm = s;
+#ifdef MCPT_TEST_HOOKS
+    if (S.cone_tol_scale != 1.f) {
+        cm = cosf(angle * S.cone_tol_scale);
+        sm = sinf(angle * S.cone_tol_scale);
+        return 1e-3f * S.cone_tol_scale;
+    }
+#endif
+    return 1e-3f;
+}
+
 // kHalfspace = false / kTir = false: without the half-space rule / the total-internal-reflection rule (the statistics build lists those
 // vertices to count them, see k_direct).  by_tir (statistics and checking builds): the total-internal-reflection rule claims the vertex.
 template <bool kHalfspace = true, bool kTir = true>
@@ -770,11 +797,10 @@ MCPT_DI bool direct_is_zero(const DevScene &S, const MaterialRec &m, f3 q, f3 n,
     const float D = sqrtf(D2);
     const float sl = R / D, cl = sqrtf(1.0f - sl * sl);
     f3 r;
-    float cm, sm;
+    float cm, sm, slack;
     if (!inside) {
         r = n * (2 * dot(n, wo)) - wo;
-        cm = 0.99820054f;  // cos(0.06)
-        sm = 0.05996400f;  // sin(0.06)
+        slack = cone_tolerance(S, 0.06f, 0.99820054f, 0.05996400f, cm, sm);  // cos(0.06), sin(0.06)
     } else {
         const float ior = get_ior(m, ch);
         const float won = dot(wo, n);
@@ -786,14 +812,14 @@ MCPT_DI bool direct_is_zero(const DevScene &S, const MaterialRec &m, f3 q, f3 n,
             if (by_tir) *by_tir = tir;
             return kTir && tir;
         }
+        if (!(ior <= kConeMaxIor)) return false;  // the 0.15 rad below is not proven for this index
         r = wot * (-ior) + n * sqrtf(1.0f - sin2);
-        cm = 0.98877108f;  // cos(0.15)
-        sm = 0.14943813f;  // sin(0.15)
+        slack = cone_tolerance(S, 0.15f, 0.98877108f, 0.14943813f, cm, sm);  // cos(0.15), sin(0.15)
     }
     const float rl = norm(r);
     if (!(rl > 0.5f && rl < 2.0f)) return false;
     const float cos_a = dot(r, L) / (rl * D);
-    return cos_a < (cl * cm - sl * sm) - 1e-3f;
+    return cos_a < (cl * cm - sl * sm) - slack;
 }
 
 // ------------------------------------------------------------------------------------------------

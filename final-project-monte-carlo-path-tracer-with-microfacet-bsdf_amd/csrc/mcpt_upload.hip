@@ -32,6 +32,7 @@ void Knobs::read() {
     if ((v = std::getenv("MCPT_HOST_DELAY_US"))) host_delay_us = std::atoi(v);
     if ((v = std::getenv("MCPT_HALFSPACE_SLACK_SCALE"))) halfspace_slack_scale = (float)std::atof(v);
     if ((v = std::getenv("MCPT_TIR_BOUND_SCALE"))) tir_bound_scale = (float)std::atof(v);
+    if ((v = std::getenv("MCPT_CONE_TOL_SCALE"))) cone_tol_scale = (float)std::atof(v);
     if ((v = std::getenv("MCPT_CULL_RHO_SCALE"))) cull_rho_scale = (float)std::atof(v);
     if ((v = std::getenv("MCPT_FAKE_FREE_MB"))) fake_free_mb = (uint64_t)std::max(1, std::atoi(v));
 #endif
@@ -202,6 +203,7 @@ void fill_view(mcpt_scene *sc) {
         v.light_plane[1] = k;
     }
     v.tir_bound_factor = 1.001f * sc->knobs.tir_bound_scale;
+    v.cone_tol_scale = sc->knobs.cone_tol_scale;
     v.n_inner = m.n_inner;
     v.n_sphere_slots = m.n_sphere_slots;
     v.n_mats = m.n_mats;
