@@ -12,8 +12,10 @@ void launch_sky_moments(const uint32_t *sky_pixels, uint32_t n_sky, const float 
 // Pass 1, one lane per listed pixel with n samples: e = the stopping rule's estimate (include/mcpt.h), err[m] = (float)e, spp_map[m] = n;
 // stamp != nullptr: stamp[m] = (round_stamp << 1) | (e > threshold), the mark its neighbours read in pass 2.  guide != nullptr (W*H floats):
 // the pixel's threshold is threshold * sqrt(g) in double, g = guide[m] >= 1 ? guide[m] : 1 (tp::guided_threshold); err stays the unscaled e.
+// weight_max_history > 0 (with a guide): the plane holds history weights H and the threshold is threshold * sqrt((double)
+// tp::weight_guide(H[m], n, weight_max_history)) (mcpt_render_adaptive_weighted); 0: the plane holds history lengths.
 void launch_adapt_eval(const uint32_t *list, uint32_t n_list, const double *moments, int32_t n, double rel_floor, double threshold, const float *guide,
-                       uint32_t round_stamp, float *err, uint8_t *stamp, int32_t *spp_map, hipStream_t st);
+                       float weight_max_history, uint32_t round_stamp, float *err, uint8_t *stamp, int32_t *spp_map, hipStream_t st);
 // Pass 2: a listed pixel continues iff can_double and (its own mark, or with dilate a mark of an 8-neighbour stamped this round).
 // A continuing pixel's fb is scaled by 0.5 and spp_map[m] = 2n; flags[i] = 1 for continuing list entries, 0 otherwise.
 void launch_adapt_select(const uint32_t *list, uint32_t n_list, int width, int height, const uint8_t *stamp, uint32_t round_stamp, int dilate,

@@ -5,7 +5,10 @@
 //   k_adapt_eval    one lane per active pixel: the estimate e from the double moments that k_accumulate<true> summed, written to the
 //                   error map, and a mark in a W x H byte image: (round stamp << 1) | (e > threshold).  k_adapt_eval<true> is the
 //                   guided flavour (mcpt_render_adaptive_guided): the pixel's threshold is tp::guided_threshold(threshold, guide[m]);
-//                   without a guide the plain flavour is launched, as it always was
+//                   without a guide the plain flavour is launched, as it always was.  k_adapt_eval<2> is the weight mode
+//                   (mcpt_render_adaptive_weighted): the plane holds history weights H and the pixel's threshold is
+//                   threshold * sqrt((double)tp::weight_guide(H[m], n, max_history)), the Neff the weighted blend will use if the pixel
+//                   stops at its n samples
 //   k_adapt_select  one lane per active pixel: continue iff the pixel's own mark is set or (dilate) a neighbour's mark of THIS round is,
 //                   and 2n <= spp; a continuing pixel's framebuffer value is halved (exact: DESIGN.md, adaptive sampling) and its
 //                   count becomes 2n
@@ -53,17 +56,21 @@ __device__ __forceinline__ double estimate(const double *mo, double n, double re
     return e;
 }
 
-template <bool kGuided>
+enum : int { kGuideNone = 0, kGuideFrames = 1, kGuideWeight = 2 };
+
+template <int kGuide>
 __global__ __launch_bounds__(kB) void k_adapt_eval(const uint32_t *__restrict__ list, uint32_t n_list, const double *__restrict__ moments, int32_t n,
-                                                    double rel_floor, double threshold, const float *__restrict__ guide, uint32_t round_stamp,
-                                                    float *__restrict__ err, uint8_t *__restrict__ stamp, int32_t *__restrict__ spp_map) {
+                                                    double rel_floor, double threshold, const float *__restrict__ guide, float max_history,
+                                                    uint32_t round_stamp, float *__restrict__ err, uint8_t *__restrict__ stamp, int32_t *__restrict__ spp_map) {
     const uint32_t i = blockIdx.x * kB + threadIdx.x;
     if (i >= n_list) return;
     const uint32_t m = list[i];
     const double e = estimate(moments + (size_t)m * 6, (double)n, rel_floor);
     err[m] = (float)e;
     spp_map[m] = n;
-    const double thr = kGuided ? tp::guided_threshold(threshold, guide[m]) : threshold;
+    const double thr = kGuide == kGuideFrames   ? tp::guided_threshold(threshold, guide[m])
+                       : kGuide == kGuideWeight ? threshold * sqrt((double)tp::weight_guide(guide[m], n, max_history))
+                                                : threshold;
     if (stamp) stamp[m] = (uint8_t)((round_stamp << 1) | (e > thr ? 1u : 0u));
 }
 
@@ -104,14 +111,11 @@ void launch_sky_moments(const uint32_t *sky_pixels, uint32_t n_sky, const float 
 }
 
 void launch_adapt_eval(const uint32_t *list, uint32_t n_list, const double *moments, int32_t n, double rel_floor, double threshold, const float *guide,
-                       uint32_t round_stamp, float *err, uint8_t *stamp, int32_t *spp_map, hipStream_t st) {
+                       float weight_max_history, uint32_t round_stamp, float *err, uint8_t *stamp, int32_t *spp_map, hipStream_t st) {
     if (n_list == 0) return;
-    if (guide)
-        hipLaunchKernelGGL(k_adapt_eval<true>, dim3(nblocks(n_list)), dim3(kB), 0, st, list, n_list, moments, n, rel_floor, threshold, guide, round_stamp,
-                           err, stamp, spp_map);
-    else
-        hipLaunchKernelGGL(k_adapt_eval<false>, dim3(nblocks(n_list)), dim3(kB), 0, st, list, n_list, moments, n, rel_floor, threshold, nullptr, round_stamp,
-                           err, stamp, spp_map);
+    const auto k = !guide ? k_adapt_eval<kGuideNone> : (weight_max_history > 0.f ? k_adapt_eval<kGuideWeight> : k_adapt_eval<kGuideFrames>);
+    hipLaunchKernelGGL(k, dim3(nblocks(n_list)), dim3(kB), 0, st, list, n_list, moments, n, rel_floor, threshold, guide, weight_max_history, round_stamp, err,
+                       stamp, spp_map);
 }
 
 void launch_adapt_select(const uint32_t *list, uint32_t n_list, int width, int height, const uint8_t *stamp, uint32_t round_stamp, int dilate,

@@ -61,7 +61,8 @@ int motion_pass(mcpt_scene *sc, const CameraConst &cc, const CameraConst &prev_c
 uint64_t motion_map_rays(uint64_t n_px, int32_t aov_spp);
 
 // What the rounds of an adaptive frame work in (adaptive_rounds): device buffers the caller owns.  Per pixel of the frame: fb 3 floats,
-// mom 6 doubles, spp, err, stamp (1 byte), guide (nullable: the plain rule).  Per listed pixel: the two lists in turn with their candidate
+// mom 6 doubles, spp, err, stamp (1 byte), guide (nullable: the plain rule; history lengths, or with guide_max_history > 0 history weights
+// and the cap of the weighted blend: mcpt_render_adaptive_weighted).  Per listed pixel: the two lists in turn with their candidate
 // entries (read only when the sky cull produced some), the continue flags; the compaction's scratch and its count.
 struct AdaptiveBufs {
     float *fb = nullptr;
@@ -70,6 +71,7 @@ struct AdaptiveBufs {
     float *err = nullptr;
     uint8_t *stamp = nullptr;
     const float *guide = nullptr;
+    float guide_max_history = 0.f;
     uint32_t *list[2] = {nullptr, nullptr};
     int4 *cand[2] = {nullptr, nullptr};
     uint8_t *flags = nullptr;
@@ -121,7 +123,7 @@ struct AdaptiveResult {
 // The checks of an adaptive rule against params.spp (mcpt_render_adaptive), `name` for the message.
 int check_adaptive(const char *name, const mcpt_adaptive &o, const mcpt_params &p);
 
-// The rounds of an adaptive frame (include/mcpt.h: mcpt_render_adaptive, with b.guide mcpt_render_adaptive_guided), queued on `st`, which it
+// The rounds of an adaptive frame (include/mcpt.h: mcpt_render_adaptive, with b.guide mcpt_render_adaptive_guided / _weighted), queued on `st`, which it
 // waits for once per round: clears err, moments, counts and stamps; f.pixels at S0 (the frame cleared, the sky cull); the culled pixels'
 // moments and estimate; then round by round render_list, k_adapt_eval, k_adapt_select and the compaction.  own != nullptr: the list side
 // of b is allocated there once the number of traced pixels is known (a call that owns its buffers); otherwise b has room for every pixel

@@ -371,7 +371,7 @@ int mcpt::adaptive_rounds(FrameCall &f, const mcpt_adaptive &o, AdaptiveBufs &b,
         const uint32_t n_sky = ps.n_owned - ps.n_pix;
         if (n_sky > 0) {
             launch_sky_moments(ps.sky, n_sky, sc->view.background, S0, b.mom, st);
-            launch_adapt_eval(ps.sky, n_sky, b.mom, S0, rel_floor, threshold, nullptr, 0u, b.err, nullptr, b.spp, st);
+            launch_adapt_eval(ps.sky, n_sky, b.mom, S0, rel_floor, threshold, nullptr, 0.f, 0u, b.err, nullptr, b.spp, st);
         }
         // the active pixels of the current and of the next round (with their candidate entries when the cull produced them)
         uint32_t n_act = ps.n_pix;
@@ -397,7 +397,7 @@ int mcpt::adaptive_rounds(FrameCall &f, const mcpt_adaptive &o, AdaptiveBufs &b,
                 traced_primary += (uint64_t)n_act * (n - first);
                 if (r > 0) samples += (uint64_t)n_act * (n - first);
                 const uint32_t round_stamp = (uint32_t)r + 1u;
-                launch_adapt_eval(b.list[cur], n_act, b.mom, n, rel_floor, threshold, b.guide, round_stamp, b.err, b.stamp, b.spp, st);
+                launch_adapt_eval(b.list[cur], n_act, b.mom, n, rel_floor, threshold, b.guide, b.guide_max_history, round_stamp, b.err, b.stamp, b.spp, st);
                 launch_adapt_select(b.list[cur], n_act, W, H, b.stamp, round_stamp, o.dilate, can_double ? 1 : 0, n, b.fb, b.spp, b.flags, st);
                 if (can_double)
                     HIP_TRY(adapt_compact(b.list[cur], ps.cand ? b.cand[cur] : nullptr, b.flags, n_act, b.list[cur ^ 1], ps.cand ? b.cand[cur ^ 1] : nullptr,
@@ -452,7 +452,7 @@ struct AdaptiveFrame {
         if (e == hipSuccess && with_var) e = var.alloc(n_px);
         return e;
     }
-    AdaptiveBufs bufs(const float *guide) const {
+    AdaptiveBufs bufs(const float *guide, float guide_max_history = 0.f) const {
         AdaptiveBufs b;
         b.fb = fb.p;
         b.mom = mom.p;
@@ -460,6 +460,7 @@ struct AdaptiveFrame {
         b.err = err.p;
         b.stamp = stamp.p;
         b.guide = guide;
+        b.guide_max_history = guide_max_history;
         return b;
     }
 };
@@ -505,9 +506,10 @@ struct DenoisedTail {
     }
 };
 
-// mcpt_render_adaptive and mcpt_render_adaptive_guided (`name` for the messages; guide_host and variance_host null for the former)
+// mcpt_render_adaptive, mcpt_render_adaptive_guided and mcpt_render_adaptive_weighted (`name` for the messages; guide_host and variance_host
+// null for the first; weight_max_history > 0 for the last: the guide holds history weights)
 int render_adaptive_guided(const char *name, mcpt_scene *sc, const mcpt_camera *cam, const mcpt_params *pp, const mcpt_adaptive *opts,
-                           const float *guide_host, float *fb_host, int32_t *spp_host, float *err_host, float *variance_host, mcpt_adaptive_info *info,
+                           const float *guide_host, float weight_max_history, float *fb_host, int32_t *spp_host, float *err_host, float *variance_host, mcpt_adaptive_info *info,
                            mcpt_stats *stats) {
     if (!sc || !cam || !pp || !opts || !fb_host) return fail(MCPT_ERR_ARG, std::string(name) + ": null argument");
     const mcpt_params &p = *pp;
@@ -522,7 +524,7 @@ int render_adaptive_guided(const char *name, mcpt_scene *sc, const mcpt_camera *
     DevBuf<float> guide;
     HIP_TRY(af.alloc(n_px, variance_host != nullptr));
     if (guide_host) HIP_TRY(upload(guide, guide_host, n_px));
-    AdaptiveBufs b = af.bufs(guide_host ? guide.p : nullptr);
+    AdaptiveBufs b = af.bufs(guide_host ? guide.p : nullptr, weight_max_history);
     AdaptiveLists lists;
     AdaptiveResult res;
     if ((rc = adaptive_rounds(f, *opts, b, &lists, st, res)) != MCPT_OK) return rc;
@@ -565,12 +567,23 @@ int mcpt_render(mcpt_scene *sc, const mcpt_camera *cam, const mcpt_params *p, fl
 
 int mcpt_render_adaptive(mcpt_scene *sc, const mcpt_camera *cam, const mcpt_params *pp, const mcpt_adaptive *opts, float *fb_host, int32_t *spp_host,
                          float *err_host, mcpt_adaptive_info *info, mcpt_stats *stats) {
-    return render_adaptive_guided("mcpt_render_adaptive", sc, cam, pp, opts, nullptr, fb_host, spp_host, err_host, nullptr, info, stats);
+    return render_adaptive_guided("mcpt_render_adaptive", sc, cam, pp, opts, nullptr, 0.f, fb_host, spp_host, err_host, nullptr, info, stats);
 }
 
 int mcpt_render_adaptive_guided(mcpt_scene *sc, const mcpt_camera *cam, const mcpt_params *pp, const mcpt_adaptive *rule, const float *guide_host,
                                 float *fb_host, int32_t *spp_host, float *err_host, float *variance_host, mcpt_adaptive_info *info, mcpt_stats *stats) {
-    return render_adaptive_guided("mcpt_render_adaptive_guided", sc, cam, pp, rule, guide_host, fb_host, spp_host, err_host, variance_host, info, stats);
+    return render_adaptive_guided("mcpt_render_adaptive_guided", sc, cam, pp, rule, guide_host, 0.f, fb_host, spp_host, err_host, variance_host, info, stats);
+}
+
+int mcpt_render_adaptive_weighted(mcpt_scene *sc, const mcpt_camera *cam, const mcpt_params *pp, const mcpt_adaptive *rule, const float *history_weight_host,
+                                  int32_t max_history, float *fb_host, int32_t *spp_host, float *err_host, float *variance_host, mcpt_adaptive_info *info,
+                                  mcpt_stats *stats) {
+    const char *name = "mcpt_render_adaptive_weighted";
+    mcpt_temporal_opts to{};
+    to.max_history = max_history;
+    tp::Opts o;
+    if (tp::resolve_opts(to, o) != 0) return fail(MCPT_ERR_ARG, std::string(name) + ": max_history out of range");
+    return render_adaptive_guided(name, sc, cam, pp, rule, history_weight_host, o.max_history, fb_host, spp_host, err_host, variance_host, info, stats);
 }
 
 int mcpt_render_adaptive_denoised(mcpt_scene *sc, const mcpt_camera *cam, const mcpt_params *pp, const mcpt_adaptive *rule, const float *guide_host,

@@ -8,7 +8,9 @@
 // first, k_history_len from the previous history set into the guide, then the rounds of csrc/mcpt_render.hip (adaptive_rounds) on the
 // sequence's buffers and k_dn_variance_map.  A sequence created with specular motion (mcpt_sequence_create_motion) and a specular depth D > 0
 // takes its motion through the chains (motion_pass at depth D, its maps in a buffer of the sequence's) and the history's depth and normal
-// from the chain AOVs, and neither runs nor allocates the extra first-hit AOV pass.
+// from the chain AOVs, and neither runs nor allocates the extra first-hit AOV pass.  A sequence created with weighted 1
+// (mcpt_sequence_create_weighted) keeps a weight plane in each history set, accumulates with the kWeight instantiations and, adaptive and
+// guided, takes its guide from k_history_weight.
 #include <new>
 
 #include "mcpt_frame.h"
@@ -22,13 +24,15 @@ struct History {
     DevBuf<float> color, variance, depth, len;
     DevBuf<float> normal;   // first-hit normals, 3 per pixel (history rejection with the normal test only)
     DevBuf<uint8_t> flags;  // what the rejection did to each pixel of the frame that wrote this set (either switch on)
-    hipError_t alloc(size_t n_px, bool with_normal, bool with_flags) {
+    DevBuf<float> weight;   // the samples behind each pixel (a weighted sequence only)
+    hipError_t alloc(size_t n_px, bool with_normal, bool with_flags, bool with_weight) {
         hipError_t e = color.alloc(n_px * 3);
         if (e == hipSuccess) e = variance.alloc(n_px);
         if (e == hipSuccess) e = depth.alloc(n_px);
         if (e == hipSuccess) e = len.alloc(n_px);
         if (e == hipSuccess && with_normal) e = normal.alloc(n_px * 3);
         if (e == hipSuccess && with_flags) e = flags.alloc(n_px);
+        if (e == hipSuccess && with_weight) e = weight.alloc(n_px);
         return e;
     }
     hipError_t clear(size_t n_px) {
@@ -38,11 +42,12 @@ struct History {
         if (e == hipSuccess) e = hipMemset(len.p, 0, n_px * sizeof(float));
         if (e == hipSuccess && normal.p) e = hipMemset(normal.p, 0, n_px * 3 * sizeof(float));
         if (e == hipSuccess && flags.p) e = hipMemset(flags.p, 0, n_px);
+        if (e == hipSuccess && weight.p) e = hipMemset(weight.p, 0, n_px * sizeof(float));
         return e;
     }
     // the set as the kernels take it: the previous frame's, or the one the frame writes
-    tp::Prev prev() const { return {color.p, variance.p, depth.p, len.p, normal.p}; }
-    tp::Next next() { return {color.p, variance.p, depth.p, len.p, normal.p, flags.p}; }
+    tp::Prev prev() const { return {color.p, variance.p, depth.p, len.p, normal.p, weight.p}; }
+    tp::Next next() { return {color.p, variance.p, depth.p, len.p, normal.p, flags.p, weight.p}; }
 };
 
 // The counts of one adaptive frame and the guide it was rendered with; two sets, used in turn with the history sets, so that a failed
@@ -74,16 +79,19 @@ struct StageEvents {
     }
 };
 
-// The host-array entry points mcpt_temporal_blend, mcpt_temporal_accumulate[_ex] and mcpt_temporal_history_len (`name` for the messages):
-// the checks in the order they have always had, the arrays that are given staged on the device (normals packed, no depth plane), one
-// kernel, the results back.  fh, ph and nh hold the host arrays; what a pass does not take is null.  hopts null: both switches 0.
-enum class Pass { blend, accumulate, history_len };
+// The host-array entry points mcpt_temporal_blend, mcpt_temporal_accumulate[_ex | _weighted] and mcpt_temporal_history_len / _weight (`name`
+// for the messages): the checks in the order they have always had, the arrays that are given staged on the device (normals packed, no
+// depth plane), one kernel, the results back.  fh, ph and nh hold the host arrays; what a pass does not take is null.  hopts null: both
+// switches 0.  The two weighted passes take ph.weight and nh.weight (history_weight writes nh.weight and no len), accumulate_weighted
+// also fh.count (nullable) or fh.uniform_count.
+enum class Pass { blend, accumulate, history_len, accumulate_weighted, history_weight };
 int temporal_call(const char *name, Pass pass, mcpt_scene *sc, int32_t width, int32_t height, tp::Frame fh, tp::Prev ph, const mcpt_temporal_opts *opts,
                   const mcpt_history_opts *hopts, const tp::Next &nh) {
     const auto bad = [&](const char *what) { return fail(MCPT_ERR_ARG, std::string(name) + ": " + what); };
-    const bool color = pass != Pass::history_len, var = pass == Pass::accumulate;
-    if (!sc || !fh.motion || !ph.color || !ph.depth || !ph.len || !opts || !nh.len || (color && (!fh.color || !nh.color)) ||
-        (var && (!fh.variance || !ph.variance || !hopts || !nh.variance)))
+    const bool wacc = pass == Pass::accumulate_weighted, hweight = pass == Pass::history_weight, weighted = wacc || hweight;
+    const bool color = pass != Pass::history_len && !hweight, var = pass == Pass::accumulate || wacc;
+    if (!sc || !fh.motion || !ph.color || !ph.depth || !ph.len || !opts || (!hweight && !nh.len) || (color && (!fh.color || !nh.color)) ||
+        (var && (!fh.variance || !ph.variance || !hopts || !nh.variance)) || (weighted && (!ph.weight || !nh.weight)))
         return bad("null argument");
     if (!frame_ok(width, height)) return bad("width and height must be positive (and the frame not too large)");
     tp::Opts o;
@@ -92,15 +100,24 @@ int temporal_call(const char *name, Pass pass, mcpt_scene *sc, int32_t width, in
     if (hopts && tp::resolve_history_opts(*hopts, ho) != 0) return bad("history option out of range");
     if (ho.normal_test && (!fh.normal || !ph.normal)) return bad("normal_test needs both normal arrays");
     if (!ho.normal_test) fh.normal = ph.normal = nullptr;  // (neither read nor uploaded)
+    const size_t n_px = (size_t)width * height;
+    if (wacc && fh.count) {
+        for (size_t m = 0; m < n_px; ++m)
+            if (fh.count[m] < 1) return bad("every count must be at least 1");
+    } else if (wacc && !(fh.uniform_count >= 1.0f && fh.uniform_count <= 3.0e38f)) {  // (NaN fails)
+        return bad("uniform_count must be finite and at least 1");
+    }
     HIP_TRY(hipSetDevice(sc->device));
     (void)hipGetLastError();
-    const size_t n_px = (size_t)width * height;
     const bool flags = nh.flags && (ho.normal_test || ho.color_clamp);  // (both switches 0: every flag is 0, and the kernel writes none)
-    DevBuf<float> in[9], out, ovar, olen;
+    DevBuf<float> in[10], out, ovar, olen, oweight;
+    DevBuf<int32_t> count;
     DevBuf<uint8_t> oflags;
     if (color) HIP_TRY(out.alloc(n_px * 3));
     if (var) HIP_TRY(ovar.alloc(n_px));
-    HIP_TRY(olen.alloc(n_px));
+    if (!hweight) HIP_TRY(olen.alloc(n_px));
+    if (weighted) HIP_TRY(oweight.alloc(n_px));
+    if (wacc && fh.count) HIP_TRY(upload(count, fh.count, n_px));
     if (flags) HIP_TRY(oflags.alloc(n_px));
     hipError_t e = hipSuccess;
     int k = 0;
@@ -109,17 +126,19 @@ int temporal_call(const char *name, Pass pass, mcpt_scene *sc, int32_t width, in
         if (e == hipSuccess && host) e = upload(d, host, n_px * per_px);
         return d.p;
     };
-    const tp::Frame f = {up(fh.color, 3), up(fh.variance, 1), up(fh.motion, 4), up(fh.normal, 3), 3, nullptr, 1};
-    const tp::Prev p = {up(ph.color, 3), up(ph.variance, 1), up(ph.depth, 1), up(ph.len, 1), up(ph.normal, 3)};
+    const tp::Frame f = {up(fh.color, 3), up(fh.variance, 1), up(fh.motion, 4), up(fh.normal, 3), 3, nullptr, 1, count.p, fh.uniform_count};
+    const tp::Prev p = {up(ph.color, 3), up(ph.variance, 1), up(ph.depth, 1), up(ph.len, 1), up(ph.normal, 3), up(weighted ? ph.weight : nullptr, 1)};
     HIP_TRY(e);
-    const tp::Next n = {out.p, ovar.p, nullptr, olen.p, nullptr, oflags.p};
+    const tp::Next n = {out.p, ovar.p, nullptr, olen.p, nullptr, oflags.p, wacc ? oweight.p : nullptr};
     if (pass == Pass::blend) launch_temporal_blend(width, height, o, f, p, n, nullptr);
-    if (pass == Pass::accumulate) launch_temporal_accumulate(width, height, o, ho, f, p, n, nullptr);
+    if (pass == Pass::accumulate || wacc) launch_temporal_accumulate(width, height, o, ho, f, p, n, nullptr);
     if (pass == Pass::history_len) launch_history_len(width, height, o, ho, f, p, olen.p, nullptr);
+    if (hweight) launch_history_weight(width, height, o, ho, f, p, oweight.p, nullptr);
     HIP_TRY(hipGetLastError());
     if (color) HIP_TRY(download(nh.color, out, n_px * 3));
     if (var) HIP_TRY(download(nh.variance, ovar, n_px));
-    HIP_TRY(download(nh.len, olen, n_px));
+    if (!hweight) HIP_TRY(download(nh.len, olen, n_px));
+    if (weighted) HIP_TRY(download(nh.weight, oweight, n_px));
     if (flags)
         HIP_TRY(download(nh.flags, oflags, n_px));
     else if (nh.flags)
@@ -160,6 +179,7 @@ struct mcpt_sequence {
     DevBuf<float4> maps;  // the maps of the motion pass's chains, six planes of map_rays entries
     uint64_t map_rays = 0;
     mcpt_adaptive_info ainfo{};  // of the last successful frame
+    bool weighted = false;       // a sequence created with mcpt_sequence_create_weighted and weighted 1: the history sets have a weight plane
 };
 
 extern "C" {
@@ -188,6 +208,26 @@ int mcpt_temporal_accumulate_ex(mcpt_scene *sc, int32_t width, int32_t height, c
     return temporal_call("mcpt_temporal_accumulate_ex", Pass::accumulate, sc, width, height, {color_host, variance_host, motion_host, normal_host, 3, nullptr, 1},
                          {prev_color_host, prev_variance_host, prev_depth_host, prev_len_host, prev_normal_host}, opts, hopts,
                          {out_color_host, out_variance_host, nullptr, out_len_host, nullptr, out_flags_host});
+}
+
+int mcpt_temporal_accumulate_weighted(mcpt_scene *sc, int32_t width, int32_t height, const float *color_host, const float *variance_host,
+                                      const float *motion_host, const float *normal_host, const int32_t *count_host, float uniform_count,
+                                      const float *prev_color_host, const float *prev_variance_host, const float *prev_depth_host,
+                                      const float *prev_len_host, const float *prev_normal_host, const float *prev_weight_host,
+                                      const mcpt_temporal_opts *opts, const mcpt_history_opts *hopts, float *out_color_host, float *out_variance_host,
+                                      float *out_len_host, uint8_t *out_flags_host, float *out_weight_host) {
+    return temporal_call("mcpt_temporal_accumulate_weighted", Pass::accumulate_weighted, sc, width, height,
+                         {color_host, variance_host, motion_host, normal_host, 3, nullptr, 1, count_host, uniform_count},
+                         {prev_color_host, prev_variance_host, prev_depth_host, prev_len_host, prev_normal_host, prev_weight_host}, opts, hopts,
+                         {out_color_host, out_variance_host, nullptr, out_len_host, nullptr, out_flags_host, out_weight_host});
+}
+
+int mcpt_temporal_history_weight(mcpt_scene *sc, int32_t width, int32_t height, const float *motion_host, const float *normal_host,
+                                 const float *prev_color_host, const float *prev_depth_host, const float *prev_len_host, const float *prev_normal_host,
+                                 const float *prev_weight_host, const mcpt_temporal_opts *opts, const mcpt_history_opts *hopts, float *weight_host) {
+    return temporal_call("mcpt_temporal_history_weight", Pass::history_weight, sc, width, height, {nullptr, nullptr, motion_host, normal_host, 3, nullptr, 1},
+                         {prev_color_host, nullptr, prev_depth_host, prev_len_host, prev_normal_host, prev_weight_host}, opts, hopts,
+                         {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, weight_host});
 }
 
 int mcpt_temporal_history_len(mcpt_scene *sc, int32_t width, int32_t height, const float *motion_host, const float *normal_host,
@@ -221,6 +261,12 @@ int mcpt_sequence_create_adaptive(mcpt_scene *sc, int32_t width, int32_t height,
 
 int mcpt_sequence_create_motion(mcpt_scene *sc, int32_t width, int32_t height, const mcpt_sequence_opts *opts, const mcpt_history_opts *hopts,
                                 const mcpt_sequence_adaptive *aopts, const mcpt_sequence_motion *mopts, mcpt_sequence **out) {
+    return mcpt_sequence_create_weighted(sc, width, height, opts, hopts, aopts, mopts, nullptr, out);
+}
+
+int mcpt_sequence_create_weighted(mcpt_scene *sc, int32_t width, int32_t height, const mcpt_sequence_opts *opts, const mcpt_history_opts *hopts,
+                                  const mcpt_sequence_adaptive *aopts, const mcpt_sequence_motion *mopts, const mcpt_sequence_weighted *wopts,
+                                  mcpt_sequence **out) {
     const auto bad = [](const char *what) { return fail(MCPT_ERR_ARG, std::string("mcpt_sequence_create: ") + what); };
     if (!sc || !opts || !out) return bad("null argument");
     *out = nullptr;
@@ -253,6 +299,12 @@ int mcpt_sequence_create_motion(mcpt_scene *sc, int32_t width, int32_t height, c
         for (int k = 0; k < 7; ++k)
             if (mopts->reserved[k] != 0) return bad("motion: reserved words must be 0");
     }
+    if (wopts) {
+        if (wopts->weighted != 0 && wopts->weighted != 1) return bad("weighted: weighted must be 0 or 1");
+        for (int k = 0; k < 7; ++k)
+            if (wopts->reserved[k] != 0) return bad("weighted: reserved words must be 0");
+    }
+    const bool weighted = wopts && wopts->weighted == 1;
     // (with a specular depth of 0 the chains are the first hits: the switch changes nothing)
     const bool chain_motion = mopts && mopts->specular_motion == 1 && opts->denoise.specular_depth > 0;
     HIP_TRY(hipSetDevice(sc->device));
@@ -273,13 +325,14 @@ int mcpt_sequence_create_motion(mcpt_scene *sc, int32_t width, int32_t height, c
         seq->guided = aopts->guided != 0;
     }
     seq->chain_motion = chain_motion;
+    seq->weighted = weighted;
     const size_t n_px = (size_t)width * height;
     hipError_t e = hipSuccess;
     const auto also = [&](auto &buf, size_t n) {
         if (e == hipSuccess) e = buf.alloc(n);
     };
     for (int k = 0; k < 2; ++k) {
-        if (e == hipSuccess) e = seq->hist[k].alloc(n_px, ho.normal_test != 0, ho.normal_test || ho.color_clamp);
+        if (e == hipSuccess) e = seq->hist[k].alloc(n_px, ho.normal_test != 0, ho.normal_test || ho.color_clamp, weighted);
         if (e == hipSuccess) e = seq->hist[k].clear(n_px);
     }
     also(seq->fb, n_px * 3);
@@ -319,6 +372,15 @@ int mcpt_sequence_flags(mcpt_sequence *seq, uint8_t *flags_host) {
     if (!flags.p) return fail(MCPT_ERR_ARG, "mcpt_sequence_flags: the sequence was created without history rejection and keeps no flags");
     HIP_TRY(hipSetDevice(seq->device));
     HIP_TRY(download(flags_host, flags, (size_t)seq->W * seq->H));
+    return MCPT_OK;
+}
+
+int mcpt_sequence_weight(mcpt_sequence *seq, float *weight_host) {
+    if (!seq || !weight_host) return fail(MCPT_ERR_ARG, "mcpt_sequence_weight: null argument");
+    const DevBuf<float> &weight = seq->hist[seq->cur].weight;  // (the set the last successful frame wrote)
+    if (!weight.p) return fail(MCPT_ERR_ARG, "mcpt_sequence_weight: the sequence was created without weighted 1 and keeps no weights");
+    HIP_TRY(hipSetDevice(seq->device));
+    HIP_TRY(download(weight_host, weight, (size_t)seq->W * seq->H));
     return MCPT_OK;
 }
 
@@ -373,7 +435,9 @@ int mcpt_sequence_frame(mcpt_sequence *seq, const mcpt_camera *cam, const mcpt_p
     // chain AOVs, which the motion's prev_depth is measured along)
     const int32_t motion_depth = seq->chain_motion ? dopts.specular_depth : 0;
     const float *first_hit = dopts.specular_depth > 0 && !seq->chain_motion ? seq->aov_first.p : seq->aov.p;
-    const tp::Frame planes = {seq->fb.p, seq->var.p, seq->motion.p, first_hit + 3, 8, first_hit + 6, 8};
+    // a weighted sequence: the samples behind this frame's pixels are its count map (adaptive) or params.spp (uniform)
+    const int32_t *count = seq->weighted && seq->adaptive ? seq->cnt[seq->cur ^ 1].spp.p : nullptr;
+    const tp::Frame planes = {seq->fb.p, seq->var.p, seq->motion.p, first_hit + 3, 8, first_hit + 6, 8, count, seq->weighted ? (float)p.spp : 0.f};
     // The feature stage, from an event the branch has recorded: the AOVs (3.) with the first-hit depth the history is validated against,
     // and the motion (4.) against the snapshot and the previous frame's camera; a fresh sequence takes no history.
     const auto features = [&]() -> int {
@@ -401,7 +465,9 @@ int mcpt_sequence_frame(mcpt_sequence *seq, const mcpt_camera *cam, const mcpt_p
         HIP_TRY(hipEventRecord(ev.features_begin, st));
         if ((rc = features()) != MCPT_OK) return rc;
         // the guide: the history length each pixel is about to get (1 everywhere on a fresh sequence: prev_len is 0); counted with the motion
-        if (seq->guided) launch_history_len(W, H, seq->temporal, seq->reject, planes, prev.prev(), cn.guide.p, st);
+        // (a weighted sequence: the history weight, 0 everywhere on a fresh one)
+        if (seq->guided && seq->weighted) launch_history_weight(W, H, seq->temporal, seq->reject, planes, prev.prev(), cn.guide.p, st);
+        if (seq->guided && !seq->weighted) launch_history_len(W, H, seq->temporal, seq->reject, planes, prev.prev(), cn.guide.p, st);
         HIP_TRY(hipEventRecord(ev.motion_end, st));
         AdaptiveBufs b;
         b.fb = seq->fb.p;
@@ -410,6 +476,7 @@ int mcpt_sequence_frame(mcpt_sequence *seq, const mcpt_camera *cam, const mcpt_p
         b.err = cn.err.p;
         b.stamp = seq->stamp.p;
         b.guide = seq->guided ? cn.guide.p : nullptr;
+        b.guide_max_history = seq->guided && seq->weighted ? seq->temporal.max_history : 0.f;
         seq->lists.into(b);
         HIP_TRY(hipEventRecord(ev.render_begin, st));
         if ((rc = adaptive_rounds(f, seq->rule, b, nullptr, st, res)) != MCPT_OK) return rc;

@@ -142,12 +142,14 @@ MCPT_TP void fold_pixel(const float *s, int32_t spp, float out[4]) {
  * This frame's planes: color 3 floats per pixel, variance 1 (its luminance variance of the colour mean), motion 4; the first-hit normal of
  * pixel m at normal[normal_stride m ..] and its first-hit depth at depth[depth_stride m] (stride 3 and 1 for packed arrays, 8 for the
  * channels of an AOV array).  The rule reads the normal only with the normal test and never the depth: the kernel copies both into the
- * next history set (csrc/mcpt_temporal.hip). */
-struct Frame { const float *color, *variance, *motion, *normal; int normal_stride; const float *depth; int depth_stride; };
-// The previous history set: color 3 floats per pixel, normal 3 (packed), the others 1.
-struct Prev { const float *color, *variance, *depth, *len, *normal; };
-// The next one.  The rule writes color, variance, len and flags (one byte per pixel, nullable); depth and normal are the kernel's copies.
-struct Next { float *color, *variance, *depth, *len, *normal; uint8_t *flags; };
+ * next history set (csrc/mcpt_temporal.hip).  The kWeight flavour alone reads the last two: count, the W*H per-pixel sample counts of this
+ * frame, or, where count is null, uniform_count for every pixel (s of the rule; s >= 1). */
+struct Frame { const float *color, *variance, *motion, *normal; int normal_stride; const float *depth; int depth_stride; const int32_t *count; float uniform_count; };
+// The previous history set: color 3 floats per pixel, normal 3 (packed), the others 1.  weight (kWeight only): the samples behind the history.
+struct Prev { const float *color, *variance, *depth, *len, *normal, *weight; };
+// The next one.  The rule writes color, variance, len and flags (one byte per pixel, nullable), and with kWeight weight; depth and normal
+// are the kernel's copies.
+struct Next { float *color, *variance, *depth, *len, *normal; uint8_t *flags; float *weight; };
 
 /* What the taps of one pixel's history add up to (steps 2, 3 and the sums of step 5 of the rule in include/mcpt.h). */
 struct Taps {
@@ -155,14 +157,17 @@ struct Taps {
     float sv;              // sum of (w * w) * prev.variance (kVar only)
     float nmin;            // the smallest prev.len of the used taps
     bool nskip;            // the normal test skipped a tap that every older test had passed (kNorm only)
+    float hmin;            // the smallest prev.weight of the used taps (kWeight only): conservative, as nmin is for len
 };
 
 /* The tap loop every flavour shares: the four bilinear taps of pixel (i, j) moved by its motion record, in tap order, with every skip of
  * the rule.  false if no tap is left.  kVar: also sum the taps' variances (p.variance is not read without it).
  * The taps' positions are tested in float before they become indices, so a motion that is huge or not finite reads nothing.
  * kNorm: the normal test of mcpt_temporal_accumulate_ex after the depth test: a tap is skipped if !(d >= normal_min), d the 3-term dot
- * x + (y + z) of p.normal[tap] and this pixel's normal (neither f.normal nor p.normal is read without it). */
-template <bool kVar, bool kNorm>
+ * x + (y + z) of p.normal[tap] and this pixel's normal (neither f.normal nor p.normal is read without it).
+ * kWeight: a tap is also skipped, together with the prev_len <= 0 test, if !(p.weight[tap] > 0) (a NaN weight skips it), and hmin is the
+ * smallest weight of the used taps (p.weight is not read without it). */
+template <bool kVar, bool kNorm, bool kWeight = false>
 MCPT_TP bool gather_taps(int W, int H, int i, int j, const Frame &f, const Prev &p, const Opts &o, float normal_min, Taps &t) {
     const size_t m = (size_t)j * W + i;
     const float *mv = f.motion + m * 4;
@@ -174,7 +179,7 @@ MCPT_TP bool gather_taps(int W, int H, int i, int j, const Frame &f, const Prev 
     const float a = fx - x0, b = fy - y0;
     const float wx[2] = {1.0f - a, a}, wy[2] = {1.0f - b, b};
     const float zp = mv[2], ztol = o.depth_tol * zp;
-    float sw = 0.0f, s0 = 0.0f, s1 = 0.0f, s2 = 0.0f, sv = 0.0f, nmin = 0.0f;
+    float sw = 0.0f, s0 = 0.0f, s1 = 0.0f, s2 = 0.0f, sv = 0.0f, nmin = 0.0f, hmin = 0.0f;
     bool any = false, nskip = false;
 #if defined(__HIP_DEVICE_COMPILE__)
 #pragma unroll
@@ -187,6 +192,8 @@ MCPT_TP bool gather_taps(int W, int H, int i, int j, const Frame &f, const Prev 
         const size_t q = (size_t)(int)ty * W + (size_t)(int)tx;
         const float n = p.len[q];
         if (n <= 0.0f) continue;
+        const float hw = kWeight ? p.weight[q] : 0.0f;
+        if (kWeight && !(hw > 0.0f)) continue;
         const float p0 = p.color[q * 3], p1 = p.color[q * 3 + 1], p2 = p.color[q * 3 + 2];
         if (!(finite_f(p0) && finite_f(p1) && finite_f(p2))) continue;
         const float dz = p.depth[q] - zp;
@@ -204,9 +211,10 @@ MCPT_TP bool gather_taps(int W, int H, int i, int j, const Frame &f, const Prev 
         s2 = s2 + w * p2;
         if (kVar) sv = sv + (w * w) * p.variance[q];
         nmin = (!any || n < nmin) ? n : nmin;
+        if (kWeight) hmin = (!any || hw < hmin) ? hw : hmin;
         any = true;
     }
-    t = {sw, s0, s1, s2, sv, nmin, nskip};
+    t = {sw, s0, s1, s2, sv, nmin, nskip, hmin};
     return any;
 }
 
@@ -230,10 +238,26 @@ MCPT_TP float clamp_channel(float h, float s, float s2, float fn, float clamp_k)
     return t > hi ? hi : t;
 }
 
-// What the rule gives one pixel.  flags: bit 0 the normal test skipped a tap, bit 1 the clamp moved the history.
+/* Step 5 of the kWeight flavour: what a history of weight hmin (> 0) becomes when a frame of s samples joins it.
+ *   Hc = min(hmin, (max_history - 1) * s);   Neff = (Hc + s) / s;   the blend's k is 1.f / Neff;   the new weight is Hc + s.
+ * k is formed as 1.f / Neff and not as s / (Hc + s) on purpose: with uniform counts, history weights equal to prev_len * s and
+ * max_history * s < 2^24 every term is an integer below 2^24, so Neff is the integer N of history_step exactly and the flavour gives the
+ * unweighted rule's bits. */
+struct WeightStep {
+    float neff, weight;
+};
+MCPT_TP WeightStep weight_step(float hmin, float s, const Opts &o) {
+    const float cap = (o.max_history - 1.0f) * s;
+    const float hc = hmin < cap ? hmin : cap;
+    const float sum = hc + s;
+    return {sum / s, sum};
+}
+
+// What the rule gives one pixel.  flags: bit 0 the normal test skipped a tap, bit 1 the clamp moved the history.  weight: kWeight only.
 struct Pixel {
     float c0, c1, c2, variance, len;
     uint8_t flags;
+    float weight;
 };
 
 /* The rule at pixel (i, j) of a W x H frame (include/mcpt.h: mcpt_temporal_blend, mcpt_temporal_accumulate[_ex]), once, with compile-time
@@ -249,15 +273,23 @@ struct Pixel {
  *   kNorm  the normal test on every tap (gather_taps); flag bit 0.
  *   kClamp the history mean clamped to the 3 x 3 neighbourhood of the new frame, neighbours in dy-then-dx order; a pixel whose history
  *          moved gets flag bit 1 and keeps v_c.
+ *   kWeight the history weighted by sample counts (mcpt_temporal_accumulate_weighted): s = (float)f.count[m], or f.uniform_count where
+ *          f.count is null (s >= 1); the weight skip and hmin of gather_taps; and in step 5 k = 1.f / Neff, weight = Hc + s (weight_step)
+ *          in place of k = 1.f / N.  len stays history_step(nmin): it still counts frames; flags, the normal test, the clamp and the
+ *          formula of the variance are untouched.  A pixel that takes no history gets weight s.  For one pixel the per-sample variance
+ *          is the same from frame to frame, so counts are the inverse-variance weights up to a factor.  WITH UNIFORM COUNTS, HISTORY
+ *          WEIGHTS EQUAL TO prev_len * s AND max_history * s < 2^24 THE FLAVOUR GIVES THE COLOUR, VARIANCE, len AND FLAGS OF THE
+ *          UNWEIGHTED RULE BIT FOR BIT, AND weight = len * s (weight_step says why).
  * A pixel that takes no history (motion.valid <= 0, a colour that is not finite, no tap left) gets its own colour, v_c, length 1, flags 0. */
-template <bool kVar, bool kNorm, bool kClamp>
+template <bool kVar, bool kNorm, bool kClamp, bool kWeight = false>
 MCPT_TP Pixel reuse_pixel(int W, int H, int i, int j, const Frame &f, const Prev &p, const Opts &o, const HistOpts &ho) {
     const size_t m = (size_t)j * W + i;
     const float c0 = f.color[m * 3], c1 = f.color[m * 3 + 1], c2 = f.color[m * 3 + 2];
     const float vc = kVar ? f.variance[m] : 0.0f;
-    Pixel r = {c0, c1, c2, vc, 1.0f, 0};
+    const float s = kWeight ? (f.count ? (float)f.count[m] : f.uniform_count) : 0.0f;
+    Pixel r = {c0, c1, c2, vc, 1.0f, 0, s};
     Taps t;
-    if (f.motion[m * 4 + 3] > 0.0f && finite_f(c0) && finite_f(c1) && finite_f(c2) && gather_taps<kVar, kNorm>(W, H, i, j, f, p, o, ho.normal_min, t)) {
+    if (f.motion[m * 4 + 3] > 0.0f && finite_f(c0) && finite_f(c1) && finite_f(c2) && gather_taps<kVar, kNorm, kWeight>(W, H, i, j, f, p, o, ho.normal_min, t)) {
         float h0 = t.s0 / t.sw, h1 = t.s1 / t.sw, h2 = t.s2 / t.sw;
         bool clamped = false;
         if (kNorm && t.nskip) r.flags |= 1;
@@ -288,7 +320,12 @@ MCPT_TP Pixel reuse_pixel(int W, int H, int i, int j, const Frame &f, const Prev
             if (clamped) r.flags |= 2;
         }
         const float N = history_step(t.nmin, o);
-        const float k = 1.0f / N;
+        float k = 1.0f / N;
+        if (kWeight) {
+            const WeightStep ws = weight_step(t.hmin, s, o);
+            k = 1.0f / ws.neff;
+            r.weight = ws.weight;
+        }
         r.c0 = h0 + (c0 - h0) * k;
         r.c1 = h1 + (c1 - h1) * k;
         r.c2 = h2 + (c2 - h2) * k;
@@ -302,8 +339,9 @@ MCPT_TP Pixel reuse_pixel(int W, int H, int i, int j, const Frame &f, const Prev
     return r;
 }
 
-// The pixel's results into the next set: n.color[3 m ..], n.len[m]; with kVar n.variance[m]; with kFlags n.flags[m] where given.
-template <bool kVar, bool kFlags>
+// The pixel's results into the next set: n.color[3 m ..], n.len[m]; with kVar n.variance[m]; with kFlags n.flags[m] where given; with
+// kWeight n.weight[m].
+template <bool kVar, bool kFlags, bool kWeight = false>
 MCPT_TP void store_pixel(const Next &n, size_t m, const Pixel &r) {
     n.color[m * 3] = r.c0;
     n.color[m * 3 + 1] = r.c1;
@@ -311,6 +349,7 @@ MCPT_TP void store_pixel(const Next &n, size_t m, const Pixel &r) {
     if (kVar) n.variance[m] = r.variance;
     n.len[m] = r.len;
     if (kFlags && n.flags) n.flags[m] = r.flags;
+    if (kWeight) n.weight[m] = r.weight;
 }
 
 // The blend at pixel (i, j) (mcpt_temporal_blend), stored.
@@ -326,6 +365,13 @@ MCPT_TP void accumulate_pixel_ex(int W, int H, int i, int j, const Frame &f, con
     store_pixel<true, true>(n, (size_t)j * W + i, r);
 }
 
+/* The weighted accumulation at pixel (i, j) (mcpt_temporal_accumulate_weighted), stored: accumulate_pixel_ex's flavours with kWeight. */
+MCPT_TP void accumulate_pixel_weighted(int W, int H, int i, int j, const Frame &f, const Prev &p, const Opts &o, const HistOpts &ho, const Next &n) {
+    const Pixel r = ho.normal_test ? (ho.color_clamp ? reuse_pixel<true, true, true, true>(W, H, i, j, f, p, o, ho) : reuse_pixel<true, true, false, true>(W, H, i, j, f, p, o, ho))
+                                   : (ho.color_clamp ? reuse_pixel<true, false, true, true>(W, H, i, j, f, p, o, ho) : reuse_pixel<true, false, false, true>(W, H, i, j, f, p, o, ho));
+    store_pixel<true, true, true>(n, (size_t)j * W + i, r);
+}
+
 /* The history length pixel (i, j) is about to get (include/mcpt.h: mcpt_temporal_history_len): steps 1-4 of the rule and the N of step 5,
  * with the new colour taken to be finite.  motion.valid <= 0, or no tap left: 1; otherwise history_step.  The taps and their skips are
  * gather_taps<false, kNorm>'s, the normal test included when ho.normal_test is 1; the colour clamp does not enter, because a clamped
@@ -336,6 +382,25 @@ MCPT_TP float history_len_pixel(int W, int H, int i, int j, const Frame &f, cons
     Taps t;
     const bool any = ho.normal_test ? gather_taps<false, true>(W, H, i, j, f, p, o, ho.normal_min, t) : gather_taps<false, false>(W, H, i, j, f, p, o, ho.normal_min, t);
     return any ? history_step(t.nmin, o) : 1.0f;
+}
+
+/* The history weight pixel (i, j) is about to get (include/mcpt.h: mcpt_temporal_history_weight), the analogue of history_len_pixel: steps
+ * 1-4 of the kWeight flavour -- the weight skip, and the normal test when ho.normal_test is 1 -- and the hmin of its taps; 0 where the pixel
+ * takes no history (motion.valid <= 0, no tap left).  Neither colour nor variance is read.  So for every pixel whose new colour is finite
+ * the accumulation's weight equals min(this, (max_history - 1) * s) + s. */
+MCPT_TP float history_weight_pixel(int W, int H, int i, int j, const Frame &f, const Prev &p, const Opts &o, const HistOpts &ho) {
+    if (!(f.motion[((size_t)j * W + i) * 4 + 3] > 0.0f)) return 0.0f;
+    Taps t;
+    const bool any = ho.normal_test ? gather_taps<false, true, true>(W, H, i, j, f, p, o, ho.normal_min, t) : gather_taps<false, false, true>(W, H, i, j, f, p, o, ho.normal_min, t);
+    return any ? t.hmin : 0.0f;
+}
+
+/* The Neff the weighted blend will use for a pixel whose history has weight H if the pixel stops at n samples (weight_step with s = n),
+ * the guide of mcpt_render_adaptive_weighted; 1 if !(H > 0) (no history, or a NaN).  It is >= 1 and does not increase when n doubles. */
+MCPT_TP float weight_guide(float H, int32_t n, float max_history) {
+    if (!(H > 0.0f)) return 1.0f;
+    const Opts o = {max_history, 0.0f};
+    return weight_step(H, (float)n, o).neff;
 }
 
 /* The same four on plain packed arrays, for callers without the structs (the CPU builds of tests/native): color, prev_color 3 floats per
@@ -363,6 +428,22 @@ MCPT_TP float history_len_pixel(int W, int H, int i, int j, const float *motion,
                                 const float *prev_depth, const float *prev_len, const float *prev_normal, const Opts &o, const HistOpts &ho) {
     return history_len_pixel(W, H, i, j, Frame{nullptr, nullptr, motion, normal, normal_stride, nullptr, 1},
                              Prev{prev_color, nullptr, prev_depth, prev_len, prev_normal}, o, ho);
+}
+
+// count nullable (W*H int32): uniform_count for every pixel then
+MCPT_TP void accumulate_pixel_weighted(int W, int H, int i, int j, const float *color, const float *variance, const float *motion, const float *normal,
+                                       int normal_stride, const int32_t *count, float uniform_count, const float *prev_color, const float *prev_variance,
+                                       const float *prev_depth, const float *prev_len, const float *prev_normal, const float *prev_weight, const Opts &o,
+                                       const HistOpts &ho, float *out_color, float *out_variance, float *out_len, uint8_t *out_flags, float *out_weight) {
+    accumulate_pixel_weighted(W, H, i, j, Frame{color, variance, motion, normal, normal_stride, nullptr, 1, count, uniform_count},
+                              Prev{prev_color, prev_variance, prev_depth, prev_len, prev_normal, prev_weight}, o, ho,
+                              Next{out_color, out_variance, nullptr, out_len, nullptr, out_flags, out_weight});
+}
+MCPT_TP float history_weight_pixel(int W, int H, int i, int j, const float *motion, const float *normal, int normal_stride, const float *prev_color,
+                                   const float *prev_depth, const float *prev_len, const float *prev_normal, const float *prev_weight, const Opts &o,
+                                   const HistOpts &ho) {
+    return history_weight_pixel(W, H, i, j, Frame{nullptr, nullptr, motion, normal, normal_stride, nullptr, 1},
+                                Prev{prev_color, nullptr, prev_depth, prev_len, prev_normal, prev_weight}, o, ho);
 }
 
 /* The stopping threshold of a guided adaptive pixel (include/mcpt.h: mcpt_render_adaptive_guided): threshold * sqrt(g) in double, with
@@ -402,11 +483,14 @@ void launch_temporal_blend(int W, int H, const tp::Opts &o, const tp::Frame &f, 
 // The accumulation (k_temporal_accumulate<kNorm, kClamp>, the instantiation ho's switches select; both 0: mcpt_temporal_accumulate's).  It
 // also leaves the next history set complete: f.depth != nullptr: n.depth[m] = the frame's first-hit depth; with ho.normal_test and n.normal
 // != nullptr: n.normal[3 m ..] = the frame's first-hit normal.  n.flags is written with a switch on only (with both 0 every flag is 0, and
-// the plain instantiation has no store for it).
+// the plain instantiation has no store for it).  n.weight != nullptr: the kWeight instantiations (f.count or f.uniform_count, p.weight),
+// which also store n.weight[m]; otherwise the instantiations there have always been.
 void launch_temporal_accumulate(int W, int H, const tp::Opts &o, const tp::HistOpts &ho, const tp::Frame &f, const tp::Prev &p, const tp::Next &n,
                                 hipStream_t st);
 // The history length every pixel is about to get (k_history_len: tp::history_len_pixel) into len[m]
 void launch_history_len(int W, int H, const tp::Opts &o, const tp::HistOpts &ho, const tp::Frame &f, const tp::Prev &p, float *len, hipStream_t st);
+// The history weight every pixel is about to get (k_history_weight: tp::history_weight_pixel) into weight[m]
+void launch_history_weight(int W, int H, const tp::Opts &o, const tp::HistOpts &ho, const tp::Frame &f, const tp::Prev &p, float *weight, hipStream_t st);
 }  // namespace mcpt
 #endif
 #endif  // MCPT_TEMPORAL_H

@@ -22,8 +22,14 @@
 //                     halo to save loads that already hit.  Every instantiation copies the frame's first-hit depth into the next history
 //                     set, and kNorm the first-hit normal where that set has a normal plane, so that one launch leaves the history
 //                     complete for the next frame; with a switch on it writes the flags byte where there is a flags plane.
+//                     k_temporal_accumulate<kNorm, kClamp, true> are the four kWeight instantiations (mcpt_temporal_accumulate_weighted, a
+//                     sequence created with weighted 1): one more load per tap (the history weight), the pixel's count or the uniform
+//                     one, and one more store, the new weight; 8 bytes per pixel of traffic.  The weight-off instantiations are the four
+//                     there have always been.
 //   k_history_len     the guide of an adaptive sequence (mcpt_temporal_history_len, mcpt_sequence_create_adaptive with guided 1):
 //                     tp::history_len_pixel, the taps and skips of the rule without its colour, known before the frame is rendered.
+//   k_history_weight  the same for a weighted sequence (mcpt_temporal_history_weight): tp::history_weight_pixel, the smallest history
+//                     weight of the taps the kWeight flavour will use.
 #include <hip/hip_runtime.h>
 
 #include "mcpt_chain.h"
@@ -192,12 +198,12 @@ __global__ __launch_bounds__(kTile *kTile) void k_temporal_blend(int W, int H, t
     tp::blend_pixel(W, H, x, y, f, p, o, n);
 }
 
-template <bool kNorm, bool kClamp>
+template <bool kNorm, bool kClamp, bool kWeight>
 __global__ __launch_bounds__(kTile *kTile) void k_temporal_accumulate(int W, int H, tp::Opts o, tp::HistOpts ho, tp::Frame f, tp::Prev p, tp::Next n) {
     const int x = blockIdx.x * kTile + threadIdx.x, y = blockIdx.y * kTile + threadIdx.y;
     if (x >= W || y >= H) return;
     const size_t m = (size_t)y * W + x;
-    tp::store_pixel<true, kNorm || kClamp>(n, m, tp::reuse_pixel<true, kNorm, kClamp>(W, H, x, y, f, p, o, ho));
+    tp::store_pixel<true, kNorm || kClamp, kWeight>(n, m, tp::reuse_pixel<true, kNorm, kClamp, kWeight>(W, H, x, y, f, p, o, ho));
     if (f.depth) n.depth[m] = f.depth[m * (size_t)f.depth_stride];
     if (kNorm && n.normal) {  // (nothing reads the normals without the normal test; three loads, then three stores: one round trip)
         const float *fn = f.normal + m * (size_t)f.normal_stride;
@@ -210,6 +216,18 @@ __global__ __launch_bounds__(kTile *kTile) void k_history_len(int W, int H, tp::
     const int x = blockIdx.x * kTile + threadIdx.x, y = blockIdx.y * kTile + threadIdx.y;
     if (x >= W || y >= H) return;
     len[(size_t)y * W + x] = tp::history_len_pixel(W, H, x, y, f, p, o, ho);
+}
+
+__global__ __launch_bounds__(kTile *kTile) void k_history_weight(int W, int H, tp::Opts o, tp::HistOpts ho, tp::Frame f, tp::Prev p, float *__restrict__ weight) {
+    const int x = blockIdx.x * kTile + threadIdx.x, y = blockIdx.y * kTile + threadIdx.y;
+    if (x >= W || y >= H) return;
+    weight[(size_t)y * W + x] = tp::history_weight_pixel(W, H, x, y, f, p, o, ho);
+}
+
+template <bool kWeight>
+auto accumulate_kernel(const tp::HistOpts &ho) {
+    return ho.normal_test ? (ho.color_clamp ? k_temporal_accumulate<true, true, kWeight> : k_temporal_accumulate<true, false, kWeight>)
+                          : (ho.color_clamp ? k_temporal_accumulate<false, true, kWeight> : k_temporal_accumulate<false, false, kWeight>);
 }
 
 inline dim3 tiles(int W, int H) { return dim3((W + kTile - 1) / kTile, (H + kTile - 1) / kTile); }
@@ -241,13 +259,16 @@ void launch_temporal_blend(int W, int H, const tp::Opts &o, const tp::Frame &f, 
 
 void launch_temporal_accumulate(int W, int H, const tp::Opts &o, const tp::HistOpts &ho, const tp::Frame &f, const tp::Prev &p, const tp::Next &n,
                                 hipStream_t st) {
-    const auto k = ho.normal_test ? (ho.color_clamp ? k_temporal_accumulate<true, true> : k_temporal_accumulate<true, false>)
-                                  : (ho.color_clamp ? k_temporal_accumulate<false, true> : k_temporal_accumulate<false, false>);
+    const auto k = n.weight ? accumulate_kernel<true>(ho) : accumulate_kernel<false>(ho);
     hipLaunchKernelGGL(k, tiles(W, H), dim3(kTile, kTile), 0, st, W, H, o, ho, f, p, n);
 }
 
 void launch_history_len(int W, int H, const tp::Opts &o, const tp::HistOpts &ho, const tp::Frame &f, const tp::Prev &p, float *len, hipStream_t st) {
     hipLaunchKernelGGL(k_history_len, tiles(W, H), dim3(kTile, kTile), 0, st, W, H, o, ho, f, p, len);
+}
+
+void launch_history_weight(int W, int H, const tp::Opts &o, const tp::HistOpts &ho, const tp::Frame &f, const tp::Prev &p, float *weight, hipStream_t st) {
+    hipLaunchKernelGGL(k_history_weight, tiles(W, H), dim3(kTile, kTile), 0, st, W, H, o, ho, f, p, weight);
 }
 
 }  // namespace mcpt

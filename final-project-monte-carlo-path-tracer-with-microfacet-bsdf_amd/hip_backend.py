@@ -27,6 +27,8 @@ EXPORTS = ["mcpt_scene_create", "mcpt_scene_destroy", "mcpt_render", "mcpt_rende
            "mcpt_temporal_history_len", "mcpt_render_adaptive_guided", "mcpt_render_adaptive_denoised",
            "mcpt_sequence_create_adaptive", "mcpt_sequence_counts",
            "mcpt_render_motion_ex", "mcpt_sequence_create_motion",
+           "mcpt_temporal_accumulate_weighted", "mcpt_temporal_history_weight", "mcpt_render_adaptive_weighted",
+           "mcpt_sequence_create_weighted", "mcpt_sequence_weight",
            "mcpt_group_create", "mcpt_group_render", "mcpt_group_size", "mcpt_group_get_info", "mcpt_group_scene", "mcpt_group_destroy", "mcpt_group_last_error",
            "mcpt_last_error", "mcpt_version"]
 
@@ -149,7 +151,11 @@ class SequenceMotion(C.Structure):
     _fields_ = [("specular_motion", C.c_int32), ("reserved", C.c_int32 * 7)]
 
 
-assert C.sizeof(SequenceMotion) == 32
+class SequenceWeighted(C.Structure):
+    _fields_ = [("weighted", C.c_int32), ("reserved", C.c_int32 * 7)]
+
+
+assert C.sizeof(SequenceMotion) == 32 and C.sizeof(SequenceWeighted) == 32
 assert C.sizeof(Adaptive) == 32 and C.sizeof(AdaptiveInfo) == 264 and C.sizeof(SequenceAdaptive) == 64
 assert C.sizeof(TemporalOpts) == 32 and C.sizeof(DenoiseOpts) == 32 and C.sizeof(HistoryOpts) == 32  # the sizes include/mcpt.h states
 assert C.sizeof(SequenceOpts) == 96 and C.sizeof(SequenceOutputs) == 64 and C.sizeof(SequenceInfo) == 64
@@ -265,6 +271,21 @@ def lib(path=None):
         L.mcpt_temporal_accumulate_ex.restype = C.c_int
         L.mcpt_temporal_accumulate_ex.argtypes = ([C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 9 + [C.POINTER(TemporalOpts), C.POINTER(HistoryOpts)]
                                                   + [C.c_void_p] * 4)
+        L.mcpt_temporal_accumulate_weighted.restype = C.c_int
+        L.mcpt_temporal_accumulate_weighted.argtypes = ([C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 5 + [C.c_float] + [C.c_void_p] * 6
+                                                        + [C.POINTER(TemporalOpts), C.POINTER(HistoryOpts)] + [C.c_void_p] * 5)
+        L.mcpt_temporal_history_weight.restype = C.c_int
+        L.mcpt_temporal_history_weight.argtypes = ([C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 7
+                                                   + [C.POINTER(TemporalOpts), C.POINTER(HistoryOpts), C.c_void_p])
+        L.mcpt_render_adaptive_weighted.restype = C.c_int
+        L.mcpt_render_adaptive_weighted.argtypes = ([C.c_void_p, C.c_void_p, C.POINTER(Params), C.POINTER(Adaptive), C.c_void_p, C.c_int32]
+                                                    + [C.c_void_p] * 4 + [C.POINTER(AdaptiveInfo), C.POINTER(Stats)])
+        L.mcpt_sequence_create_weighted.restype = C.c_int
+        L.mcpt_sequence_create_weighted.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(SequenceOpts), C.POINTER(HistoryOpts),
+                                                    C.POINTER(SequenceAdaptive), C.POINTER(SequenceMotion), C.POINTER(SequenceWeighted),
+                                                    C.POINTER(C.c_void_p)]
+        L.mcpt_sequence_weight.restype = C.c_int
+        L.mcpt_sequence_weight.argtypes = [C.c_void_p, C.c_void_p]
         L.mcpt_sequence_create_ex.restype = C.c_int
         L.mcpt_sequence_create_ex.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(SequenceOpts), C.POINTER(HistoryOpts), C.POINTER(C.c_void_p)]
         L.mcpt_sequence_flags.restype = C.c_int
@@ -545,6 +566,28 @@ class HipScene:
                                                   _ptr(err), None if var is None else _ptr(var), C.byref(info), C.byref(st)), L=self.L)
         return fb, spp, err, var, info.as_dict(), st
 
+    def render_adaptive_weighted(self, min_spp, threshold, history_weight=None, max_history=0, rel_floor=1e-3, dilate=1, camera=None, variance=True,
+                                 **kw):
+        """mcpt_render_adaptive_weighted: render_adaptive_guided with the weight mode of the guide.  history_weight[H,W] float32 holds the
+        samples behind each pixel's history (history_weight(...); None: the plain rule); with n samples so far a pixel's threshold is scaled
+        by sqrt((min(H, (max_history - 1) n) + n) / n), the effective length the weighted blend will give it.  max_history: the blend's (0:
+        32).  Returns (fb[H,W,3], spp[H,W] int32, err[H,W], variance[H,W] or None, info dict, Stats)."""
+        cam = np.ascontiguousarray(camera if camera is not None else self.sd.camera)
+        W, H = int(cam["width"].reshape(-1)[0]), int(cam["height"].reshape(-1)[0])
+        fb = np.zeros((H, W, 3), dtype=np.float32)
+        spp = np.zeros((H, W), dtype=np.int32)
+        err = np.zeros((H, W), dtype=np.float32)
+        var = np.zeros((H, W), dtype=np.float32) if variance else None
+        guide = self._guide(history_weight, H, W)
+        p = self.params(**kw)
+        o = Adaptive(min_spp=int(min_spp), dilate=int(dilate), threshold=float(threshold), rel_floor=float(rel_floor))
+        info = AdaptiveInfo()
+        st = Stats()
+        _check(self.L.mcpt_render_adaptive_weighted(self.h, _ptr(cam), C.byref(p), C.byref(o), None if guide is None else _ptr(guide), int(max_history),
+                                                    _ptr(fb), _ptr(spp), _ptr(err), None if var is None else _ptr(var), C.byref(info), C.byref(st)),
+               L=self.L)
+        return fb, spp, err, var, info.as_dict(), st
+
     def render_adaptive_denoised(self, min_spp, threshold, guide=None, rel_floor=1e-3, dilate=1, camera=None, aov_spp=0, iterations=0, sigma_l=0.0,
                                  sigma_n=0.0, sigma_z=0.0, specular_depth=0, **kw):
         """mcpt_render_adaptive_denoised: render_adaptive_guided, the AOVs of render_aovs(aov_spp, seed, specular_depth) and the filter of the
@@ -584,6 +627,27 @@ class HipScene:
         _check(self.L.mcpt_temporal_history_len(self.h, W, H, _ptr(motion), None if normal is None else _ptr(normal), _ptr(prev_color), _ptr(prev_depth),
                                                 _ptr(prev_len), None if prev_normal is None else _ptr(prev_normal), C.byref(o), C.byref(ho), _ptr(out)),
                L=self.L)
+        return out
+
+    def history_weight(self, motion, prev_color, prev_depth, prev_len, prev_weight, normal=None, prev_normal=None, normal_test=False, normal_min=0.0,
+                       **opts):
+        """mcpt_temporal_history_weight: the history weight every pixel is about to get in temporal_accumulate_weighted (the smallest
+        prev_weight of the taps it will use; 0 without history), from what is known before the frame is rendered: the arguments of
+        history_len and prev_weight[H,W].  Returns weight[H,W] float32."""
+        motion = np.ascontiguousarray(motion, dtype=np.float32)
+        H, W = motion.shape[:2]
+        prev_color, prev_depth, prev_len, prev_weight = (np.ascontiguousarray(x, dtype=np.float32) for x in (prev_color, prev_depth, prev_len, prev_weight))
+        normal, prev_normal = (None if x is None else np.ascontiguousarray(x, dtype=np.float32) for x in (normal, prev_normal))
+        n = H * W
+        if (motion.size != n * 4 or prev_color.size != n * 3 or prev_depth.size != n or prev_len.size != n or prev_weight.size != n
+                or any(x is not None and x.size != n * 3 for x in (normal, prev_normal))):
+            raise ValueError("history_weight: the arrays do not describe one %dx%d frame" % (W, H))
+        out = np.zeros((H, W), dtype=np.float32)
+        o = temporal_opts(**opts)
+        ho = history_opts(normal_test, False, normal_min, 0.0)
+        _check(self.L.mcpt_temporal_history_weight(self.h, W, H, _ptr(motion), None if normal is None else _ptr(normal), _ptr(prev_color),
+                                                   _ptr(prev_depth), _ptr(prev_len), None if prev_normal is None else _ptr(prev_normal),
+                                                   _ptr(prev_weight), C.byref(o), C.byref(ho), _ptr(out)), L=self.L)
         return out
 
     def render_aovs(self, aov_spp=0, seed=1, camera=None, specular_depth=0):
@@ -718,8 +782,37 @@ class HipScene:
                                                   _ptr(out_len), _ptr(flags)), L=self.L)
         return out, out_var, out_len, flags
 
+    def temporal_accumulate_weighted(self, color, variance, motion, normal, count, prev_color, prev_variance, prev_depth, prev_len, prev_normal,
+                                     prev_weight, normal_test=False, color_clamp=False, normal_min=0.0, clamp_k=0.0, **opts):
+        """mcpt_temporal_accumulate_weighted: temporal_accumulate_ex with the history weighted by sample counts.  count: an int32 [H,W] array
+        of this frame's per-pixel sample counts, or a number, the count of every pixel; prev_weight[H,W]: the previous out_weight of this
+        call (0 for the first frame).  Returns (out[H,W,3], out_variance[H,W], out_len[H,W] float32, flags[H,W] uint8, out_weight[H,W]
+        float32).  With one count for every pixel and frame the first four are temporal_accumulate_ex's bit for bit."""
+        color = np.ascontiguousarray(color, dtype=np.float32)
+        H, W = color.shape[:2]
+        variance, motion, prev_color, prev_variance, prev_depth, prev_len, prev_weight = (
+            np.ascontiguousarray(x, dtype=np.float32) for x in (variance, motion, prev_color, prev_variance, prev_depth, prev_len, prev_weight))
+        normal, prev_normal = (None if x is None else np.ascontiguousarray(x, dtype=np.float32) for x in (normal, prev_normal))
+        counts = None if np.isscalar(count) else np.ascontiguousarray(count, dtype=np.int32)
+        n = H * W
+        if (color.size != n * 3 or variance.size != n or motion.size != n * 4 or prev_color.size != n * 3 or prev_variance.size != n
+                or prev_depth.size != n or prev_len.size != n or prev_weight.size != n or (counts is not None and counts.size != n)
+                or any(x is not None and x.size != n * 3 for x in (normal, prev_normal))):
+            raise ValueError("temporal_accumulate_weighted: the arrays do not describe one %dx%d frame" % (W, H))
+        out = np.zeros((H, W, 3), dtype=np.float32)
+        out_var, out_len, out_weight = (np.zeros((H, W), dtype=np.float32) for _ in range(3))
+        flags = np.zeros((H, W), dtype=np.uint8)
+        o = temporal_opts(**opts)
+        ho = history_opts(normal_test, color_clamp, normal_min, clamp_k)
+        _check(self.L.mcpt_temporal_accumulate_weighted(self.h, W, H, _ptr(color), _ptr(variance), _ptr(motion), None if normal is None else _ptr(normal),
+                                                        None if counts is None else _ptr(counts), 0.0 if counts is not None else float(count),
+                                                        _ptr(prev_color), _ptr(prev_variance), _ptr(prev_depth), _ptr(prev_len),
+                                                        None if prev_normal is None else _ptr(prev_normal), _ptr(prev_weight), C.byref(o), C.byref(ho),
+                                                        _ptr(out), _ptr(out_var), _ptr(out_len), _ptr(flags), _ptr(out_weight)), L=self.L)
+        return out, out_var, out_len, flags, out_weight
+
     def sequence(self, width=None, height=None, filter=True, max_history=0, depth_tol=0.0, normal_test=False, color_clamp=False, normal_min=0.0,
-                 clamp_k=0.0, adaptive=None, specular_motion=False, **denoise_opts_kw):
+                 clamp_k=0.0, adaptive=None, specular_motion=False, weighted=False, **denoise_opts_kw):
         """mcpt_sequence_create: a HipSequence of width x height frames (default: the scene camera's) on this scene.  filter: also denoise
         the accumulated frame; max_history, depth_tol: mcpt_temporal_opts; the rest: mcpt_denoise_opts (aov_spp, iterations, sigma_l,
         sigma_n, sigma_z, specular_depth).  normal_test / color_clamp (normal_min, clamp_k): history rejection, mcpt_history_opts; with
@@ -728,9 +821,12 @@ class HipScene:
         (mcpt_sequence_create_adaptive), each frame's `spp` is the cap, and HipSequence.counts() gives the last frame's counts.
         specular_motion: with specular_depth > 0 the motion follows the mirror / glass chains too and the history is validated against the
         chain depth (mcpt_sequence_create_motion).
+        weighted: the history is weighted by sample counts -- the count map of an adaptive frame, `spp` of a uniform one -- and a guided
+        adaptive rule is guided by the history weight (mcpt_sequence_create_weighted); HipSequence.weight() gives the last frame's weights.
         The sequence owns the scene's snapshot while it lives; close it before the scene."""
         return HipSequence(self, width, height, filter, max_history, depth_tol, normal_test=normal_test, color_clamp=color_clamp,
-                           normal_min=normal_min, clamp_k=clamp_k, adaptive=adaptive, specular_motion=specular_motion, **denoise_opts_kw)
+                           normal_min=normal_min, clamp_k=clamp_k, adaptive=adaptive, specular_motion=specular_motion, weighted=weighted,
+                           **denoise_opts_kw)
 
     def render_device(self, fb_ptr, stream_ptr=0, camera=None, **kw):
         """Same, into a device framebuffer (W*H*3 floats at fb_ptr) on the given hipStream_t handle."""
@@ -833,12 +929,14 @@ class HipSequence:
 
     def __init__(self, scene, width=None, height=None, filter=True, max_history=0, depth_tol=0.0, normal_test=False, color_clamp=False,
                  normal_min=0.0, clamp_k=0.0, history=None, adaptive=None, create_adaptive=False, specular_motion=False, motion=None,
-                 **denoise_opts_kw):
+                 weighted=None, **denoise_opts_kw):
         """history: a HistoryOpts passed to mcpt_sequence_create_ex as it is (tests: a zeroed one must give mcpt_sequence_create's sequence).
         adaptive: a dict of sequence_adaptive's keywords or a SequenceAdaptive; create_adaptive: go through mcpt_sequence_create_adaptive
         even without one (tests: a null rule must give mcpt_sequence_create_ex's sequence).  specular_motion: mcpt_sequence_create_motion
         with the switch on; motion: a SequenceMotion passed to it as it is, or "null" for a null pointer (tests: a null or zeroed one must
-        give mcpt_sequence_create_adaptive's sequence)."""
+        give mcpt_sequence_create_adaptive's sequence).  weighted: True for mcpt_sequence_create_weighted with the switch on; a
+        SequenceWeighted passed to it as it is, or "null" for a null pointer (tests: a null or zeroed one must give
+        mcpt_sequence_create_motion's sequence)."""
         self.scene = scene  # (keeps the scene alive as long as the sequence)
         self.L = scene.L
         self.h = None
@@ -853,7 +951,14 @@ class HipSequence:
             adaptive = sequence_adaptive(**adaptive)
         if specular_motion and motion is None:
             motion = SequenceMotion(specular_motion=1)
-        if motion is not None:
+        if weighted is True:
+            weighted = SequenceWeighted(weighted=1)
+        if weighted is not None and weighted is not False:
+            _check(self.L.mcpt_sequence_create_weighted(scene.h, self.W, self.H, C.byref(o), None if history is None else C.byref(history),
+                                                        None if adaptive is None else C.byref(adaptive),
+                                                        None if motion is None or isinstance(motion, str) else C.byref(motion),
+                                                        None if isinstance(weighted, str) else C.byref(weighted), C.byref(h)), L=self.L)
+        elif motion is not None:
             _check(self.L.mcpt_sequence_create_motion(scene.h, self.W, self.H, C.byref(o), None if history is None else C.byref(history),
                                                       None if adaptive is None else C.byref(adaptive),
                                                       None if isinstance(motion, str) else C.byref(motion), C.byref(h)), L=self.L)
@@ -890,8 +995,16 @@ class HipSequence:
         _check(self.L.mcpt_sequence_flags(self.h, _ptr(out)), L=self.L)
         return out
 
+    def weight(self):
+        """mcpt_sequence_weight: weight[H,W] float32, the samples behind each pixel of the last frame's history (0 before the first frame); a
+        sequence created without weighted keeps none and raises."""
+        out = np.zeros((self.H, self.W), dtype=np.float32)
+        _check(self.L.mcpt_sequence_weight(self.h, _ptr(out)), L=self.L)
+        return out
+
     def counts(self):
-        """mcpt_sequence_counts: dict(spp[H,W] int32, err[H,W], guide[H,W] float32 (0 without guided), info dict) of the last frame of an
+        """mcpt_sequence_counts: dict(spp[H,W] int32, err[H,W], guide[H,W] float32 (0 without guided; the history weights of a weighted
+        sequence), info dict) of the last frame of an
         adaptive sequence; any other sequence keeps none and raises."""
         spp = np.zeros((self.H, self.W), dtype=np.int32)
         err, guide = np.zeros((self.H, self.W), dtype=np.float32), np.zeros((self.H, self.W), dtype=np.float32)

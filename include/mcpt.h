@@ -255,6 +255,21 @@ int mcpt_render_adaptive_guided(mcpt_scene *scene, const mcpt_camera *camera, co
                                 const float *guide_host, float *fb_host, int32_t *spp_host, float *err_host, float *variance_host,
                                 mcpt_adaptive_info *info, mcpt_stats *stats);
 
+/* mcpt_render_adaptive_guided with the weight mode of the guide: the plane holds, per pixel, the HISTORY WEIGHT H the pixel is about to
+ * get in a weighted blend (mcpt_temporal_history_weight below): the samples behind its history.  With n samples so far pixel m's mark is
+ *     e > threshold * sqrt((double) g),   g = (min(H, (max_history - 1) * n) + n) / n in float  if H > 0,  otherwise g = 1
+ * (a zero, negative or NaN weight leaves the plain rule).  g is exactly the Neff the weighted blend will use if the pixel stops at n
+ * samples (mcpt_temporal_accumulate_weighted, step 5 with s = n), so the threshold is a target for the ACCUMULATED pixel whatever the
+ * counts of its earlier frames were; g >= 1, and it does not increase when n doubles, so a pixel's threshold tightens as it goes on.
+ * err still reports the unscaled e.  The rule, halving, dilation and the cap are otherwise unchanged: every pixel is still bit-identical
+ * to the same pixel of mcpt_render at its final count, and no pixel gets more samples than without the guide.
+ *   history_weight_host  W*H floats (nullable: mcpt_render_adaptive_guided with a null guide, bit for bit)
+ *   max_history          the cap of the blend the weights are meant for: 0 => 32; 1..4096 (mcpt_temporal_opts)
+ * MCPT_ERR_ARG and MCPT_ERR_OVERFLOW as mcpt_render_adaptive_guided; MCPT_ERR_ARG also for max_history out of range. */
+int mcpt_render_adaptive_weighted(mcpt_scene *scene, const mcpt_camera *camera, const mcpt_params *params, const mcpt_adaptive *rule,
+                                  const float *history_weight_host, int32_t max_history, float *fb_host, int32_t *spp_host, float *err_host,
+                                  float *variance_host, mcpt_adaptive_info *info, mcpt_stats *stats);
+
 /* ---- Feature buffers (AOVs) and a variance-guided a-trous denoiser (Dammertz et al. 2010; variance guidance of SVGF, Schied et al. 2017).
  *
  * AOV record: 8 floats per pixel, row-major m = j*W + i:  {albedo r,g,b, normal x,y,z, depth, coverage}.
@@ -533,6 +548,47 @@ int mcpt_temporal_history_len(mcpt_scene *scene, int32_t width, int32_t height, 
                               const float *prev_normal_host, const mcpt_temporal_opts *opts, const mcpt_history_opts *history_opts,
                               float *len_host);
 
+/* The accumulation with the history weighted by sample counts: frames of a sequence whose pixels have different counts (adaptive frames, or
+ * a params.spp that changes from frame to frame) weigh by their samples, not 1/N each.  For one pixel the per-sample variance is the same
+ * from frame to frame, so counts are the inverse-variance weights up to a factor, and unlike an estimated variance they carry no noise of
+ * their own into the weights.  The arguments of mcpt_temporal_accumulate_ex, and
+ *   count_host W*H int32, nullable  the samples behind each pixel of this frame (the spp map of an adaptive frame);
+ *   uniform_count                   used for every pixel when count_host is null (params.spp of a uniform frame);
+ *   prev_weight_host W*H            the previous out_weight_host of this call (0 everywhere for the first frame);   out_weight_host W*H.
+ * Per pixel s = (float) count[p], or uniform_count; s >= 1.  The rule of mcpt_temporal_accumulate_ex with three changes, all in float,
+ * without contraction, in this order:
+ *   step 3, one more skip, tested together with prev_len <= 0:  a tap is skipped if !(prev_weight[tap] > 0)  (a NaN weight skips it);
+ *   step 5:  Hmin = the smallest prev_weight of the used taps (conservative, as n is for len);
+ *         Hc = min(Hmin, (max_history - 1) * s);   Neff = (Hc + s) / s;   k = 1.f / Neff;
+ *         out = hist + (color - hist) * k;   out_weight = Hc + s;
+ *      len stays N = min(n + 1, max_history): it still counts frames; the flags and the depth, normal and clamp logic are untouched; the
+ *      variance keeps its formula, (omk*omk)*hv + (k*k)*v_c with this k and omk = 1.f - k;
+ *   a pixel that takes no history (steps 1 and 4) gets out_weight = s.
+ * So a static pixel carries sum(s_k c_k) / sum(s_k) and the weight sum(s_k), and max_history caps the weight at max_history * s of the
+ * current frame, as it caps len.  k is formed as 1.f / Neff and not as s / (Hc + s) on purpose: WITH UNIFORM COUNTS, prev_weight EQUAL TO
+ * prev_len * s AND max_history * s < 2^24, Neff IS THE INTEGER N EXACTLY (every term is an integer below 2^24), SO out_color,
+ * out_variance, out_len AND out_flags ARE THOSE OF mcpt_temporal_accumulate_ex BIT FOR BIT, AND out_weight = out_len * s.
+ * MCPT_ERR_ARG, before any device call: every case mcpt_temporal_accumulate_ex refuses; a null prev_weight_host or out_weight_host; a
+ * count below 1 anywhere in count_host (the array is scanned on the host); with a null count_host a uniform_count below 1 or not finite. */
+int mcpt_temporal_accumulate_weighted(mcpt_scene *scene, int32_t width, int32_t height, const float *color_host, const float *variance_host,
+                                      const float *motion_host, const float *normal_host, const int32_t *count_host, float uniform_count,
+                                      const float *prev_color_host, const float *prev_variance_host, const float *prev_depth_host,
+                                      const float *prev_len_host, const float *prev_normal_host, const float *prev_weight_host,
+                                      const mcpt_temporal_opts *opts, const mcpt_history_opts *history_opts, float *out_color_host,
+                                      float *out_variance_host, float *out_len_host, uint8_t *out_flags_host, float *out_weight_host);
+
+/* The history weight every pixel is ABOUT TO GET, before its frame is rendered, as mcpt_temporal_history_len is for the length: steps 1-4
+ * of mcpt_temporal_accumulate_weighted with the new colour taken to be finite -- the weight skip, and the normal test when
+ * history_opts.normal_test is 1 -- and the Hmin of step 5; 0 where the pixel takes no history.  Neither colour nor variance is read.
+ * So FOR EVERY PIXEL WHOSE NEW COLOUR IS FINITE  out_weight == min(weight, (max_history - 1) * s) + s  OF
+ * mcpt_temporal_accumulate_weighted ON THE SAME INPUTS.  It is the guide of mcpt_render_adaptive_weighted in a sequence.
+ * The arguments of mcpt_temporal_history_len, and prev_weight_host W*H;  weight_host W*H.
+ * MCPT_ERR_ARG, before any device call: as mcpt_temporal_history_len; a null prev_weight_host or weight_host. */
+int mcpt_temporal_history_weight(mcpt_scene *scene, int32_t width, int32_t height, const float *motion_host, const float *normal_host,
+                                 const float *prev_color_host, const float *prev_depth_host, const float *prev_len_host,
+                                 const float *prev_normal_host, const float *prev_weight_host, const mcpt_temporal_opts *opts,
+                                 const mcpt_history_opts *history_opts, float *weight_host);
+
 /* ---- Frame sequences: the history, the variance of the accumulated frame and every working buffer stay on the device; one call runs a
  * whole frame on one stream and only what the caller asks for crosses the bus.  The caller's loop is
  *       mcpt_scene_update;  mcpt_sequence_frame          (params.seed varied from frame to frame).
@@ -625,8 +681,8 @@ int mcpt_sequence_flags(mcpt_sequence *sequence, uint8_t *flags_host);
  *   c. guided 1: the guide = mcpt_temporal_history_len(motion, the first-hit normals, the previous history set: colour, depth, len,
  *      normals; opts.temporal, history_opts).  On the first frame and after a reset prev_len is 0, so the guide is 1 everywhere;
  *   d. the rounds of mcpt_render_adaptive_guided(rule, the guide; guided 0: no guide) and its variance, each pixel at its own count;
- *   e. steps 5-8 as they are: the history and the filter get each pixel's own variance.  A pixel's frames still weigh 1/N each in the
- *      blend, whatever their counts.
+ *   e. steps 5-8 as they are: the history and the filter get each pixel's own variance.  A pixel's frames weigh 1/N each in the blend,
+ *      whatever their counts, unless the sequence is weighted (mcpt_sequence_create_weighted below weighs them by their counts).
  * outputs.fb is the adaptive frame; every output equals what the separate calls give, bit for bit.  stats.samples is the sum of the
  * count map.  In mcpt_sequence_info the guide is counted with ms_motion and ms_render is the time of the rounds.
  * Allocated at create, for all W*H pixels active, per pixel: two sets of counts (spp 4, err 4, guide 4 bytes, used in turn with the
@@ -665,6 +721,28 @@ typedef struct {
 int mcpt_sequence_create_motion(mcpt_scene *scene, int32_t width, int32_t height, const mcpt_sequence_opts *opts,
                                 const mcpt_history_opts *history_opts, const mcpt_sequence_adaptive *adaptive,
                                 const mcpt_sequence_motion *motion, mcpt_sequence **out);
+
+/* A sequence whose history is weighted by sample counts.  A null or zeroed `weighted`: mcpt_sequence_create_motion, exactly (the same
+ * allocations, the same frames).  With weighted 1 each history set gains a weight plane (4 bytes per pixel, 8 in all), and
+ * mcpt_sequence_frame changes in these places and nowhere else:
+ *   step 5 is mcpt_temporal_accumulate_weighted; its counts are the frame's count map (an adaptive sequence) or uniform_count =
+ *   params.spp (a uniform one), its prev_weight the weight plane of the previous history set;
+ *   with an adaptive rule and guided 1, step c is mcpt_temporal_history_weight and step d mcpt_render_adaptive_weighted with
+ *   opts.temporal.max_history; the `guide` of mcpt_sequence_counts then reports the history weights H.
+ * Every output still equals what the separate calls give, bit for bit.  A uniform sequence at a constant params.spp gives the outputs of
+ * the unweighted sequence bit for bit, and weight = len * spp (mcpt_temporal_accumulate_weighted says why).  After a reset prev_len is 0,
+ * so the weights restart at s.  The weights live in the alternating history sets: a failed frame leaves them as they were.
+ * mcpt_sequence_weight copies the weights of the last successful frame to weight_host (W*H floats; all 0 before the first frame).
+ * MCPT_ERR_ARG, before any device call: as mcpt_sequence_create_motion; weighted not 0 or 1, a non-zero reserved word;
+ * mcpt_sequence_weight for a null pointer or a sequence created without weighted 1 (it keeps no weights). */
+typedef struct {
+    int32_t weighted;    /* 0 | 1 */
+    int32_t reserved[7]; /* must be 0 */
+} mcpt_sequence_weighted; /* 32 bytes */
+int mcpt_sequence_create_weighted(mcpt_scene *scene, int32_t width, int32_t height, const mcpt_sequence_opts *opts,
+                                  const mcpt_history_opts *history_opts, const mcpt_sequence_adaptive *adaptive,
+                                  const mcpt_sequence_motion *motion, const mcpt_sequence_weighted *weighted, mcpt_sequence **out);
+int mcpt_sequence_weight(mcpt_sequence *sequence, float *weight_host);
 
 /* Replaces Scene::intersect (Scene.hpp:128, Scene.cpp:19-21) for a list of rays (host pointers; n*3 floats each).
  * out_t: hit distance as the reference's double Intersection::distance (DBL_MAX on a miss);

@@ -20,6 +20,10 @@ Prints, per frame, the total samples, the histogram of the counts, the stage tim
 --ref-spp render of that frame's geometry (seed 1000).  --move: the short box of the Cornell scene moves by translate(-32 k, 0, 0) before
 frame k (a reference per frame; a static scene renders one).  --quality instead of --adaptive: the same figures for a uniform sequence at
 --spp samples per pixel.
+  --weighted   the history is weighted by sample counts (mcpt_sequence_create_weighted); with --adaptive T --guided the rule is guided by the
+history weight.  Prints the mean weight per frame.  --spp-list 64,4,4,4 with --quality: a uniform sequence whose frame k has the k-th count
+(the last one repeats), e.g. a caller that lowers params.spp while the camera moves.  --len-mask N: the MSE also over the pixels whose history
+length is N in that frame.
   --specular-depth N   the sequence's denoise.specular_depth (the features behind up to N mirror / glass bounces); with --specular-motion the
 motion follows those chains too and the history is validated against the chain depth (mcpt_sequence_create_motion).  --move with --scene
 chess moves the nearest rough pawn by 6 units (about 3.5 px at 1080p) along x per frame, and the MSE is also given over the pixels whose
@@ -135,11 +139,13 @@ def sequence_timing(pkg, sd, W, H, frames, reject=None, loop=True):
     hs.close()
 
 
-def sequence_quality(pkg, sd, W, H, frames, spp, adaptive, reject, move, ref_spp, specular_depth=0, specular_motion=False):
-    """Per frame of a uniform (adaptive None) or adaptive sequence: samples, count histogram, stage times, MSE of `accumulated`."""
+def sequence_quality(pkg, sd, W, H, frames, spp, adaptive, reject, move, ref_spp, specular_depth=0, specular_motion=False, weighted=False, spp_list=None,
+                     len_mask=0):
+    """Per frame of a uniform (adaptive None) or adaptive sequence: samples, count histogram, stage times, MSE of `accumulated`.
+    spp_list: the samples per pixel of frame k of a uniform sequence (the last entry repeats)."""
     hs = pkg.HipScene(sd)
-    seq = hs.sequence(filter=False, aov_spp=min(4, adaptive["min_spp"] if adaptive else spp), adaptive=adaptive, specular_depth=specular_depth,
-                      specular_motion=specular_motion, **(reject or {}))
+    seq = hs.sequence(filter=False, aov_spp=min(4, adaptive["min_spp"] if adaptive else min(spp_list or [spp])), adaptive=adaptive,
+                      specular_depth=specular_depth, specular_motion=specular_motion, weighted=weighted, **(reject or {}))
     chess = sd.name.startswith("chess")
     step = 6.0 if chess else -32.0  # object 1: the nearest rough pawn of the chess scene, the short box of the Cornell scene
     floor = None
@@ -149,7 +155,7 @@ def sequence_quality(pkg, sd, W, H, frames, spp, adaptive, reject, move, ref_spp
         prim = hs.intersect(o, d)[1].reshape(H, W)
         floor = (prim >= a) & (prim < a + n)
         print("specular depth %d, specular motion %s; %.1f %% of the pixels see the floor mirror first" % (specular_depth, bool(specular_motion), 100 * floor.mean()))
-    what = "uniform %d spp" % spp if not adaptive else "adaptive %s, levels %d..%d, threshold %g" % (
+    what = ("uniform %s spp" % (",".join(str(x) for x in spp_list) if spp_list else spp)) + (", weighted" if weighted else "") if not adaptive else ("weighted " if weighted else "") + "adaptive %s, levels %d..%d, threshold %g" % (
         "guided" if adaptive["guided"] else "unguided", adaptive["min_spp"], spp, adaptive["threshold"])
     print("%dx%d %s sequence, %s; reference %d spp" % (W, H, "moving" if move else "static", what, ref_spp))
     truth, total = None, 0
@@ -158,7 +164,8 @@ def sequence_quality(pkg, sd, W, H, frames, spp, adaptive, reject, move, ref_spp
             hs.update([(1, np.array([[1, 0, 0, step * k], [0, 1, 0, 0], [0, 0, 1, 0]], np.float32))])
         if truth is None or move:
             truth = hs.render(spp=ref_spp, seed=1000)[0].astype(np.float64)
-        r = seq.frame(want=("accumulated",), spp=spp, seed=k + 1)
+        spp_k = spp_list[min(k, len(spp_list) - 1)] if spp_list else spp
+        r = seq.frame(want=("accumulated", "len"), spp=spp_k, seed=k + 1)
         sq = (r["accumulated"].astype(np.float64) - truth) ** 2
         mse = float(np.nanmean(sq))
         n = int(r["stats"].samples)
@@ -170,6 +177,11 @@ def sequence_quality(pkg, sd, W, H, frames, spp, adaptive, reject, move, ref_spp
             hist = "  counts " + " ".join("%d:%d" % (a, b) for a, b in zip(lv, cnt))
             if adaptive["guided"]:
                 hist += "  mean guide %.2f" % float(cn["guide"].mean())
+        if weighted:
+            hist += "  mean weight %.2f" % float(seq.weight().mean())
+        if len_mask:
+            keep = r["len"] == len_mask
+            hist += "  MSE where len == %d (%.1f %% of the pixels) %.6g" % (len_mask, 100 * keep.mean(), float(np.nanmean(sq[keep])) if keep.any() else float("nan"))
         if floor is not None:
             hist += "  MSE on the floor mirror %.6g" % float(np.nanmean(sq[floor]))
         i = r["info"]
@@ -196,6 +208,9 @@ def main():
     ap.add_argument("--adaptive", type=float, default=None, help="--sequence: an adaptive sequence with this threshold; prints samples, counts and MSE")
     ap.add_argument("--adaptive-min", type=int, default=4, help="--adaptive: the first level")
     ap.add_argument("--guided", action="store_true", help="--adaptive: relax each pixel's threshold by sqrt(the history length it is about to get)")
+    ap.add_argument("--weighted", action="store_true", help="--adaptive / --quality: weigh the history by sample counts (mcpt_sequence_create_weighted)")
+    ap.add_argument("--spp-list", default=None, help="--quality: comma-separated samples per pixel of frame 0, 1, ... (the last one repeats)")
+    ap.add_argument("--len-mask", type=int, default=0, help="--adaptive / --quality: also the MSE over the pixels whose history length is this")
     ap.add_argument("--quality", action="store_true", help="--sequence: the figures of --adaptive for a uniform sequence at --spp")
     ap.add_argument("--spp", type=int, default=64, help="--adaptive: the cap; --quality: the samples per pixel")
     ap.add_argument("--move", action="store_true", help="--adaptive / --quality with --scene cornell: move the short box before every frame")
@@ -208,12 +223,16 @@ def main():
     pkg = mcpt_loader.load()
     W, H = a.width, a.height
     sd = pkg.scenes.chess_scene(width=W, height=H, spp=4) if a.scene == "chess" else pkg.scenes.cornell_demo(W, H, 4)
-    if a.sequence and (a.adaptive is not None or a.quality or a.move or a.specular_depth > 0):  # (the last two imply --quality)
+    spp_list = [int(x) for x in a.spp_list.split(",")] if a.spp_list else None
+    if spp_list and a.adaptive is not None:
+        sys.exit("--spp-list is for a uniform sequence (--quality)")
+    if a.sequence and (a.adaptive is not None or a.quality or a.move or a.specular_depth > 0 or a.weighted or spp_list):  # (the last four imply --quality)
         reject = dict(normal_test=a.normal_test, color_clamp=a.color_clamp, clamp_k=a.clamp_k) if a.normal_test or a.color_clamp else None
         rule = None if a.adaptive is None else dict(min_spp=a.adaptive_min, threshold=a.adaptive, dilate=1, guided=int(a.guided))
         if a.specular_motion and a.specular_depth <= 0:
             sys.exit("--specular-motion needs --specular-depth N > 0")
-        return sequence_quality(pkg, sd, W, H, a.frames, a.spp, rule, reject, a.move, a.ref_spp, a.specular_depth, a.specular_motion)
+        return sequence_quality(pkg, sd, W, H, a.frames, a.spp, rule, reject, a.move, a.ref_spp, a.specular_depth, a.specular_motion, a.weighted, spp_list,
+                                a.len_mask)
     if a.sequence:
         if a.frames < 6:
             sys.exit("--frames must be at least 6")
