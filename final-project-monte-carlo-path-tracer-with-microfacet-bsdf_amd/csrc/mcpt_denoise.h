@@ -117,10 +117,31 @@ MCPT_DN float pow_int(float b, int32_t n) {
     return r;
 }
 
+/* The depth gradient of pixel (x, y) from the AOV records (8 floats per pixel: depth at 6, coverage at 7): central differences over covered
+ * in-image neighbours ((z+ - z-) / 2; one-sided when one neighbour is missing; 0 when both are, and for an uncovered pixel).  prep_pixel
+ * and the window gate of the moments variance (csrc/mcpt_moments.h) both take it from here. */
+MCPT_DN void depth_gradient(int W, int H, int x, int y, const float *aov, float grad[2]) {
+    const float *a = aov + ((size_t)y * W + x) * 8;
+    const bool cov = a[7] > 0.0f;
+    const float z = a[6];
+    float g[2] = {0.0f, 0.0f};
+    if (cov) {
+        for (int axis = 0; axis < 2; ++axis) {
+            const int dx = axis == 0 ? 1 : 0, dy = axis == 0 ? 0 : 1;
+            const int xm = x - dx, ym = y - dy, xp = x + dx, yp = y + dy;
+            const bool hm = xm >= 0 && ym >= 0 && aov[((size_t)ym * W + xm) * 8 + 7] > 0.0f;
+            const bool hp = xp < W && yp < H && aov[((size_t)yp * W + xp) * 8 + 7] > 0.0f;
+            const float zm = hm ? aov[((size_t)ym * W + xm) * 8 + 6] : 0.0f, zp = hp ? aov[((size_t)yp * W + xp) * 8 + 6] : 0.0f;
+            g[axis] = (hm && hp) ? (zp - zm) * 0.5f : (hp ? zp - z : (hm ? z - zm : 0.0f));
+        }
+    }
+    grad[0] = g[0];
+    grad[1] = g[1];
+}
+
 /* Preparation of pixel (x, y) of a W x H frame: colour (3 floats), variance (1) and AOV record (8 floats: albedo, normal, depth,
  * coverage) per pixel, row-major.  Demodulation e = c / A, A = max(albedo, 1e-3), and v / lum(A)^2.  The pixel is usable iff c, v, e
- * and the scaled v are finite and v >= 0.  grad: the depth gradient, central differences over covered in-image neighbours
- * ((z+ - z-) / 2; one-sided when one neighbour is missing; 0 when both are, and for an uncovered pixel). */
+ * and the scaled v are finite and v >= 0.  grad: the depth gradient (depth_gradient above). */
 MCPT_DN void prep_pixel(int W, int H, int x, int y, const float *color, const float *variance, const float *aov, Rec &out, float grad[2]) {
     const size_t m = (size_t)y * W + x;
     const float *a = aov + m * 8;
@@ -139,22 +160,8 @@ MCPT_DN void prep_pixel(int W, int H, int x, int y, const float *color, const fl
     out.n[0] = a[3];
     out.n[1] = a[4];
     out.n[2] = a[5];
-    const bool cov = a[7] > 0.0f;
-    const float z = a[6];
-    out.z = cov ? z : kUncovered;
-    float g[2] = {0.0f, 0.0f};
-    if (cov) {
-        for (int axis = 0; axis < 2; ++axis) {
-            const int dx = axis == 0 ? 1 : 0, dy = axis == 0 ? 0 : 1;
-            const int xm = x - dx, ym = y - dy, xp = x + dx, yp = y + dy;
-            const bool hm = xm >= 0 && ym >= 0 && aov[((size_t)ym * W + xm) * 8 + 7] > 0.0f;
-            const bool hp = xp < W && yp < H && aov[((size_t)yp * W + xp) * 8 + 7] > 0.0f;
-            const float zm = hm ? aov[((size_t)ym * W + xm) * 8 + 6] : 0.0f, zp = hp ? aov[((size_t)yp * W + xp) * 8 + 6] : 0.0f;
-            g[axis] = (hm && hp) ? (zp - zm) * 0.5f : (hp ? zp - z : (hm ? z - zm : 0.0f));
-        }
-    }
-    grad[0] = g[0];
-    grad[1] = g[1];
+    out.z = a[7] > 0.0f ? a[6] : kUncovered;
+    depth_gradient(W, H, x, y, aov, grad);
 }
 
 /* Whether q may contribute to p at all: q is usable, and both are uncovered or both covered with n_p.n_q > 0.  The taps' weights are 0

@@ -17,7 +17,8 @@ inline bool frame_ok(int W, int H) { return W > 0 && H > 0 && (uint64_t)W * H <=
 enum : unsigned {
     kOneCallFrame = 1u,  // no progressive accumulation: accumulate, spp_total and sample_offset must be 0
     kOneRank = 2u,       // nranks must be 1
-    kDenoisedFrame = 4u  // spp >= 2 (a variance needs two samples) and a frame the AOV pass can hold (frame_ok)
+    kDenoisedFrame = 4u,  // spp >= 2 (a variance needs two samples) and a frame the AOV pass can hold (frame_ok)
+    kOneSample = 8u       // with kDenoisedFrame: spp >= 1 (a moments sequence takes its variance from the frames, csrc/mcpt_moments.h)
 };
 
 // The checks of (cam, params) every frame-level call makes before it touches the scene, in the order the entry points have always made
@@ -132,7 +133,8 @@ int adaptive_rounds(FrameCall &f, const mcpt_adaptive &o, AdaptiveBufs &b, Adapt
 
 // A uniform frame of f.p.spp samples with its moments, and the variance of its mean, on buffers the caller owns (fb 3 floats per pixel, mom 6
 // doubles, var 1), queued on `st` (steps 1-2 of mcpt_render_denoised): clears the moments; f.pixels; the culled pixels' moments;
-// render_list; k_dn_variance.  res gets the totals, the samples and how many were traced (res.info stays zero).
+// render_list; k_dn_variance.  res gets the totals, the samples and how many were traced (res.info stays zero).  mom null: the plain frame
+// of mcpt_render, without moments and without variance (var is not written).
 int render_moments(FrameCall &f, float *fb, double *mom, float *var, hipStream_t st, AdaptiveResult &res);
 
 // Working buffers of the filter: two record buffers and the depth gradient, 72 bytes per pixel.

@@ -23,7 +23,7 @@ int mcpt::check_frame_call(const char *name, const mcpt_camera &cam, const mcpt_
     const bool positive = cam.width > 0 && cam.height > 0 && p.n_dir_sample > 0 && p.rr_rate > 0.f;
     if (forbid & kDenoisedFrame) {
         if (!positive || !frame_ok(cam.width, cam.height)) return bad("width/height/n_dir_sample/rr_rate must be positive");
-        if (p.spp < 2) return bad("params.spp must be at least 2");
+        if (p.spp < ((forbid & kOneSample) ? 1 : 2)) return bad((forbid & kOneSample) ? "params.spp must be at least 1" : "params.spp must be at least 2");
     } else {
         if (!positive || p.spp <= 0) return bad("width/height/spp/n_dir_sample/rr_rate must be positive");
         if ((uint64_t)cam.width * cam.height > 0x7fffffffull) return bad("frame too large");
@@ -421,15 +421,15 @@ int mcpt::render_moments(FrameCall &f, float *fb, double *mom, float *var, hipSt
     const mcpt_params &p = f.p;
     const size_t n_px = (size_t)f.cc.width * f.cc.height;
     int rc;
-    HIP_TRY(hipMemsetAsync(mom, 0, n_px * 6 * sizeof(double), st));
+    if (mom) HIP_TRY(hipMemsetAsync(mom, 0, n_px * 6 * sizeof(double), st));
     if ((rc = f.pixels(p.spp, (float)p.spp, fb, st)) != MCPT_OK) return rc;
     const PixelSet &ps = f.ps;
-    if (ps.n_owned > ps.n_pix) launch_sky_moments(ps.sky, ps.n_owned - ps.n_pix, f.sc->view.background, p.spp, mom, st);
+    if (mom && ps.n_owned > ps.n_pix) launch_sky_moments(ps.sky, ps.n_owned - ps.n_pix, f.sc->view.background, p.spp, mom, st);
     if (ps.n_pix > 0) {
         rc = render_list(f.sc, f.cc, p, ps.list, ps.cand, ps.n_pix, 0, p.spp, (float)p.spp, fb, mom, st, f.t0, res.totals);
         if (rc != MCPT_OK) return rc;
     }
-    launch_dn_variance((uint32_t)n_px, mom, p.spp, var, st);
+    if (mom) launch_dn_variance((uint32_t)n_px, mom, p.spp, var, st);
     res.samples = (uint64_t)ps.n_owned * p.spp;
     res.traced_primary = (uint64_t)ps.n_pix * p.spp;
     return MCPT_OK;

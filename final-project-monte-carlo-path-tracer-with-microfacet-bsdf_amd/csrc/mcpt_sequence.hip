@@ -10,10 +10,13 @@
 // takes its motion through the chains (motion_pass at depth D, its maps in a buffer of the sequence's) and the history's depth and normal
 // from the chain AOVs, and neither runs nor allocates the extra first-hit AOV pass.  A sequence created with weighted 1
 // (mcpt_sequence_create_weighted) keeps a weight plane in each history set, accumulates with the kWeight instantiations and, adaptive and
-// guided, takes its guide from k_history_weight.
+// guided, takes its guide from k_history_weight.  A sequence created with moments (mcpt_sequence_create_moments, enabled 1) renders the plain
+// frame, keeps a moments plane in each history set, accumulates with the kMoments instantiations and takes the variance of the accumulated
+// frame from k_moments_variance (csrc/mcpt_moments.hip) right after; it has no moments of the render and runs at one sample per pixel.
 #include <new>
 
 #include "mcpt_frame.h"
+#include "mcpt_moments.h"
 
 using namespace mcpt;
 
@@ -25,7 +28,8 @@ struct History {
     DevBuf<float> normal;   // first-hit normals, 3 per pixel (history rejection with the normal test only)
     DevBuf<uint8_t> flags;  // what the rejection did to each pixel of the frame that wrote this set (either switch on)
     DevBuf<float> weight;   // the samples behind each pixel (a weighted sequence only)
-    hipError_t alloc(size_t n_px, bool with_normal, bool with_flags, bool with_weight) {
+    DevBuf<float> moments;  // the running luminance moments, 2 per pixel (a moments sequence only)
+    hipError_t alloc(size_t n_px, bool with_normal, bool with_flags, bool with_weight, bool with_moments) {
         hipError_t e = color.alloc(n_px * 3);
         if (e == hipSuccess) e = variance.alloc(n_px);
         if (e == hipSuccess) e = depth.alloc(n_px);
@@ -33,6 +37,7 @@ struct History {
         if (e == hipSuccess && with_normal) e = normal.alloc(n_px * 3);
         if (e == hipSuccess && with_flags) e = flags.alloc(n_px);
         if (e == hipSuccess && with_weight) e = weight.alloc(n_px);
+        if (e == hipSuccess && with_moments) e = moments.alloc(n_px * 2);
         return e;
     }
     hipError_t clear(size_t n_px) {
@@ -43,6 +48,7 @@ struct History {
         if (e == hipSuccess && normal.p) e = hipMemset(normal.p, 0, n_px * 3 * sizeof(float));
         if (e == hipSuccess && flags.p) e = hipMemset(flags.p, 0, n_px);
         if (e == hipSuccess && weight.p) e = hipMemset(weight.p, 0, n_px * sizeof(float));
+        if (e == hipSuccess && moments.p) e = hipMemset(moments.p, 0, n_px * 2 * sizeof(float));
         return e;
     }
     // the set as the kernels take it: the previous frame's, or the one the frame writes
@@ -83,15 +89,17 @@ struct StageEvents {
 // for the messages): the checks in the order they have always had, the arrays that are given staged on the device (normals packed, no
 // depth plane), one kernel, the results back.  fh, ph and nh hold the host arrays; what a pass does not take is null.  hopts null: both
 // switches 0.  The two weighted passes take ph.weight and nh.weight (history_weight writes nh.weight and no len), accumulate_weighted
-// also fh.count (nullable) or fh.uniform_count.
-enum class Pass { blend, accumulate, history_len, accumulate_weighted, history_weight };
+// also fh.count (nullable) or fh.uniform_count.  accumulate_moments takes the host moments mh and no variance array.
+enum class Pass { blend, accumulate, history_len, accumulate_weighted, history_weight, accumulate_moments };
 int temporal_call(const char *name, Pass pass, mcpt_scene *sc, int32_t width, int32_t height, tp::Frame fh, tp::Prev ph, const mcpt_temporal_opts *opts,
-                  const mcpt_history_opts *hopts, const tp::Next &nh) {
+                  const mcpt_history_opts *hopts, const tp::Next &nh, const tp::Moments mh = {}) {
     const auto bad = [&](const char *what) { return fail(MCPT_ERR_ARG, std::string(name) + ": " + what); };
     const bool wacc = pass == Pass::accumulate_weighted, hweight = pass == Pass::history_weight, weighted = wacc || hweight;
+    const bool macc = pass == Pass::accumulate_moments;
     const bool color = pass != Pass::history_len && !hweight, var = pass == Pass::accumulate || wacc;
     if (!sc || !fh.motion || !ph.color || !ph.depth || !ph.len || !opts || (!hweight && !nh.len) || (color && (!fh.color || !nh.color)) ||
-        (var && (!fh.variance || !ph.variance || !hopts || !nh.variance)) || (weighted && (!ph.weight || !nh.weight)))
+        (var && (!fh.variance || !ph.variance || !hopts || !nh.variance)) || (weighted && (!ph.weight || !nh.weight)) ||
+        (macc && (!hopts || !mh.prev || !mh.next)))
         return bad("null argument");
     if (!frame_ok(width, height)) return bad("width and height must be positive (and the frame not too large)");
     tp::Opts o;
@@ -110,13 +118,14 @@ int temporal_call(const char *name, Pass pass, mcpt_scene *sc, int32_t width, in
     HIP_TRY(hipSetDevice(sc->device));
     (void)hipGetLastError();
     const bool flags = nh.flags && (ho.normal_test || ho.color_clamp);  // (both switches 0: every flag is 0, and the kernel writes none)
-    DevBuf<float> in[10], out, ovar, olen, oweight;
+    DevBuf<float> in[11], out, ovar, olen, oweight, omoments;
     DevBuf<int32_t> count;
     DevBuf<uint8_t> oflags;
     if (color) HIP_TRY(out.alloc(n_px * 3));
     if (var) HIP_TRY(ovar.alloc(n_px));
     if (!hweight) HIP_TRY(olen.alloc(n_px));
     if (weighted) HIP_TRY(oweight.alloc(n_px));
+    if (macc) HIP_TRY(omoments.alloc(n_px * 2));
     if (wacc && fh.count) HIP_TRY(upload(count, fh.count, n_px));
     if (flags) HIP_TRY(oflags.alloc(n_px));
     hipError_t e = hipSuccess;
@@ -128,9 +137,11 @@ int temporal_call(const char *name, Pass pass, mcpt_scene *sc, int32_t width, in
     };
     const tp::Frame f = {up(fh.color, 3), up(fh.variance, 1), up(fh.motion, 4), up(fh.normal, 3), 3, nullptr, 1, count.p, fh.uniform_count};
     const tp::Prev p = {up(ph.color, 3), up(ph.variance, 1), up(ph.depth, 1), up(ph.len, 1), up(ph.normal, 3), up(weighted ? ph.weight : nullptr, 1)};
+    const tp::Moments mo = {up(mh.prev, 2), omoments.p};
     HIP_TRY(e);
     const tp::Next n = {out.p, ovar.p, nullptr, olen.p, nullptr, oflags.p, wacc ? oweight.p : nullptr};
     if (pass == Pass::blend) launch_temporal_blend(width, height, o, f, p, n, nullptr);
+    if (macc) launch_temporal_accumulate_moments(width, height, o, ho, f, p, n, mo, nullptr);
     if (pass == Pass::accumulate || wacc) launch_temporal_accumulate(width, height, o, ho, f, p, n, nullptr);
     if (pass == Pass::history_len) launch_history_len(width, height, o, ho, f, p, olen.p, nullptr);
     if (hweight) launch_history_weight(width, height, o, ho, f, p, oweight.p, nullptr);
@@ -139,6 +150,7 @@ int temporal_call(const char *name, Pass pass, mcpt_scene *sc, int32_t width, in
     if (var) HIP_TRY(download(nh.variance, ovar, n_px));
     if (!hweight) HIP_TRY(download(nh.len, olen, n_px));
     if (weighted) HIP_TRY(download(nh.weight, oweight, n_px));
+    if (macc) HIP_TRY(download(mh.next, omoments, n_px * 2));
     if (flags)
         HIP_TRY(download(nh.flags, oflags, n_px));
     else if (nh.flags)
@@ -180,6 +192,8 @@ struct mcpt_sequence {
     uint64_t map_rays = 0;
     mcpt_adaptive_info ainfo{};  // of the last successful frame
     bool weighted = false;       // a sequence created with mcpt_sequence_create_weighted and weighted 1: the history sets have a weight plane
+    bool moments = false;        // a sequence created with mcpt_sequence_create_moments and enabled 1: the history sets have a moments plane,
+    mo::Opts mopts{};            // there is no `mom`, and the variance of the accumulated frame is k_moments_variance's
 };
 
 extern "C" {
@@ -220,6 +234,39 @@ int mcpt_temporal_accumulate_weighted(mcpt_scene *sc, int32_t width, int32_t hei
                          {color_host, variance_host, motion_host, normal_host, 3, nullptr, 1, count_host, uniform_count},
                          {prev_color_host, prev_variance_host, prev_depth_host, prev_len_host, prev_normal_host, prev_weight_host}, opts, hopts,
                          {out_color_host, out_variance_host, nullptr, out_len_host, nullptr, out_flags_host, out_weight_host});
+}
+
+int mcpt_temporal_accumulate_moments(mcpt_scene *sc, int32_t width, int32_t height, const float *color_host, const float *motion_host,
+                                     const float *normal_host, const float *prev_color_host, const float *prev_depth_host, const float *prev_len_host,
+                                     const float *prev_normal_host, const float *prev_moments_host, const mcpt_temporal_opts *opts,
+                                     const mcpt_history_opts *hopts, float *out_color_host, float *out_len_host, uint8_t *out_flags_host,
+                                     float *out_moments_host) {
+    return temporal_call("mcpt_temporal_accumulate_moments", Pass::accumulate_moments, sc, width, height, {color_host, nullptr, motion_host, normal_host, 3, nullptr, 1},
+                         {prev_color_host, nullptr, prev_depth_host, prev_len_host, prev_normal_host}, opts, hopts,
+                         {out_color_host, nullptr, nullptr, out_len_host, nullptr, out_flags_host}, {prev_moments_host, out_moments_host});
+}
+
+int mcpt_moments_variance(mcpt_scene *sc, int32_t width, int32_t height, const float *moments_host, const float *len_host, const uint8_t *flags_host,
+                          const float *aov_host, const mcpt_moments_opts *opts, float *out_variance_host) {
+    const auto bad = [](const char *what) { return fail(MCPT_ERR_ARG, std::string("mcpt_moments_variance: ") + what); };
+    if (!sc || !moments_host || !len_host || !aov_host || !opts || !out_variance_host) return bad("null argument");
+    if (!frame_ok(width, height)) return bad("width and height must be positive (and the frame not too large)");
+    mo::Opts o;
+    if (mo::resolve_opts(*opts, o) != 0) return bad("option out of range");
+    HIP_TRY(hipSetDevice(sc->device));
+    (void)hipGetLastError();
+    const size_t n_px = (size_t)width * height;
+    DevBuf<float> mom, len, aov, out;
+    DevBuf<uint8_t> flags;
+    HIP_TRY(upload(mom, moments_host, n_px * 2));
+    HIP_TRY(upload(len, len_host, n_px));
+    HIP_TRY(upload(aov, aov_host, n_px * 8));
+    if (flags_host) HIP_TRY(upload(flags, flags_host, n_px));
+    HIP_TRY(out.alloc(n_px));
+    launch_moments_variance(width, height, o, mom.p, len.p, flags.p, aov.p, out.p, nullptr);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(download(out_variance_host, out, n_px));
+    return MCPT_OK;
 }
 
 int mcpt_temporal_history_weight(mcpt_scene *sc, int32_t width, int32_t height, const float *motion_host, const float *normal_host,
@@ -267,6 +314,12 @@ int mcpt_sequence_create_motion(mcpt_scene *sc, int32_t width, int32_t height, c
 int mcpt_sequence_create_weighted(mcpt_scene *sc, int32_t width, int32_t height, const mcpt_sequence_opts *opts, const mcpt_history_opts *hopts,
                                   const mcpt_sequence_adaptive *aopts, const mcpt_sequence_motion *mopts, const mcpt_sequence_weighted *wopts,
                                   mcpt_sequence **out) {
+    return mcpt_sequence_create_moments(sc, width, height, opts, hopts, aopts, mopts, wopts, nullptr, out);
+}
+
+int mcpt_sequence_create_moments(mcpt_scene *sc, int32_t width, int32_t height, const mcpt_sequence_opts *opts, const mcpt_history_opts *hopts,
+                                 const mcpt_sequence_adaptive *aopts, const mcpt_sequence_motion *mopts, const mcpt_sequence_weighted *wopts,
+                                 const mcpt_moments_opts *momopts, mcpt_sequence **out) {
     const auto bad = [](const char *what) { return fail(MCPT_ERR_ARG, std::string("mcpt_sequence_create: ") + what); };
     if (!sc || !opts || !out) return bad("null argument");
     *out = nullptr;
@@ -305,6 +358,11 @@ int mcpt_sequence_create_weighted(mcpt_scene *sc, int32_t width, int32_t height,
             if (wopts->reserved[k] != 0) return bad("weighted: reserved words must be 0");
     }
     const bool weighted = wopts && wopts->weighted == 1;
+    mo::Opts mo_opts{};
+    if (momopts && mo::resolve_opts(*momopts, mo_opts) != 0) return bad("moments: option out of range");
+    const bool moments = momopts && momopts->enabled == 1;
+    if (moments && aopts) return bad("moments: an adaptive rule brings its own variance (its counts need min_spp >= 2)");
+    if (moments && weighted) return bad("moments: weighted must be 0 (a one-sample sequence has uniform counts)");
     // (with a specular depth of 0 the chains are the first hits: the switch changes nothing)
     const bool chain_motion = mopts && mopts->specular_motion == 1 && opts->denoise.specular_depth > 0;
     HIP_TRY(hipSetDevice(sc->device));
@@ -326,18 +384,20 @@ int mcpt_sequence_create_weighted(mcpt_scene *sc, int32_t width, int32_t height,
     }
     seq->chain_motion = chain_motion;
     seq->weighted = weighted;
+    seq->moments = moments;
+    seq->mopts = mo_opts;
     const size_t n_px = (size_t)width * height;
     hipError_t e = hipSuccess;
     const auto also = [&](auto &buf, size_t n) {
         if (e == hipSuccess) e = buf.alloc(n);
     };
     for (int k = 0; k < 2; ++k) {
-        if (e == hipSuccess) e = seq->hist[k].alloc(n_px, ho.normal_test != 0, ho.normal_test || ho.color_clamp, weighted);
+        if (e == hipSuccess) e = seq->hist[k].alloc(n_px, ho.normal_test != 0, ho.normal_test || ho.color_clamp, weighted, moments);
         if (e == hipSuccess) e = seq->hist[k].clear(n_px);
     }
     also(seq->fb, n_px * 3);
-    also(seq->mom, n_px * 6);
-    also(seq->var, n_px);
+    if (!moments) also(seq->mom, n_px * 6);
+    if (!moments) also(seq->var, n_px);  // (a moments sequence has no variance of the frame)
     also(seq->aov, n_px * 8);
     if (opts->denoise.specular_depth > 0 && !chain_motion) also(seq->aov_first, n_px * 8);
     if (chain_motion) {  // for the most feature samples a frame can ask for (aov_spp 0: at most 4)
@@ -384,6 +444,15 @@ int mcpt_sequence_weight(mcpt_sequence *seq, float *weight_host) {
     return MCPT_OK;
 }
 
+int mcpt_sequence_moments(mcpt_sequence *seq, float *moments_host) {
+    if (!seq || !moments_host) return fail(MCPT_ERR_ARG, "mcpt_sequence_moments: null argument");
+    const DevBuf<float> &moments = seq->hist[seq->cur].moments;  // (the set the last successful frame wrote)
+    if (!moments.p) return fail(MCPT_ERR_ARG, "mcpt_sequence_moments: the sequence was created without moments and keeps none");
+    HIP_TRY(hipSetDevice(seq->device));
+    HIP_TRY(download(moments_host, moments, (size_t)seq->W * seq->H * 2));
+    return MCPT_OK;
+}
+
 int mcpt_sequence_counts(mcpt_sequence *seq, int32_t *spp_host, float *err_host, float *guide_host, mcpt_adaptive_info *info) {
     if (!seq) return fail(MCPT_ERR_ARG, "mcpt_sequence_counts: null sequence");
     if (!seq->adaptive) return fail(MCPT_ERR_ARG, "mcpt_sequence_counts: the sequence was created without an adaptive rule and keeps no counts");
@@ -409,7 +478,7 @@ int mcpt_sequence_frame(mcpt_sequence *seq, const mcpt_camera *cam, const mcpt_p
     const auto bad = [](const char *what) { return fail(MCPT_ERR_ARG, std::string("mcpt_sequence_frame: ") + what); };
     if (!seq || !cam || !pp) return bad("null argument");
     const mcpt_params &p = *pp;
-    int rc = check_frame_call("mcpt_sequence_frame", *cam, p, kDenoisedFrame | kOneRank | kOneCallFrame);
+    int rc = check_frame_call("mcpt_sequence_frame", *cam, p, kDenoisedFrame | kOneRank | kOneCallFrame | (seq->moments ? kOneSample : 0u));
     if (rc != MCPT_OK) return rc;
     if (cam->width != seq->W || cam->height != seq->H) return bad("the camera must have the width and height of the sequence");
     const mcpt_denoise_opts &dopts = seq->opts.denoise;
@@ -454,6 +523,7 @@ int mcpt_sequence_frame(mcpt_sequence *seq, const mcpt_camera *cam, const mcpt_p
     if (!seq->adaptive) {
         // 2. the frame with its moments, and its variance (mcpt_render_denoised, steps 1-2), then the features
         HIP_TRY(hipEventRecord(ev.render_begin, st));
+        // (a moments sequence: the plain frame; seq->mom is null and neither moments nor variance of the render are formed)
         if ((rc = render_moments(f, seq->fb.p, seq->mom.p, seq->var.p, st, res)) != MCPT_OK) return rc;
         HIP_TRY(hipEventRecord(ev.render_end, st));
         if ((rc = features()) != MCPT_OK) return rc;
@@ -484,7 +554,12 @@ int mcpt_sequence_frame(mcpt_sequence *seq, const mcpt_camera *cam, const mcpt_p
         HIP_TRY(hipEventRecord(ev.render_end, st));
     }
     // 5. previous history set -> the other one
-    launch_temporal_accumulate(W, H, seq->temporal, seq->reject, planes, prev.prev(), next.next(), st);
+    if (seq->moments)
+        launch_temporal_accumulate_moments(W, H, seq->temporal, seq->reject, planes, prev.prev(), next.next(), {prev.moments.p, next.moments.p}, st);
+    else
+        launch_temporal_accumulate(W, H, seq->temporal, seq->reject, planes, prev.prev(), next.next(), st);
+    // 5b. a moments sequence: the variance of the accumulated frame from the new set's moments, on the AOVs the filter reads
+    if (seq->moments) launch_moments_variance(W, H, seq->mopts, next.moments.p, next.len.p, next.flags.p, seq->aov.p, next.variance.p, st);
     HIP_TRY(hipEventRecord(ev.accumulate_end, st));
     // 6., 7. the filter and the tone map
     if (filter) launch_denoise(W, H, seq->denoise, next.color.p, next.variance.p, seq->aov.p, seq->db.rec[0].p, seq->db.rec[1].p, seq->db.grad.p, seq->out.p, st);

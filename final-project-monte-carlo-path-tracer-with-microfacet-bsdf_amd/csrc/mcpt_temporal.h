@@ -18,6 +18,7 @@
 #include <stdint.h>
 
 #include "../../include/mcpt.h"
+#include "mcpt_denoise.h"  // dn::lum: the luminance the kMoments flavour takes its moments of
 
 #if defined(__HIPCC__) || defined(__HIP__)
 #include <hip/hip_runtime.h>
@@ -150,6 +151,9 @@ struct Prev { const float *color, *variance, *depth, *len, *normal, *weight; };
 // The next one.  The rule writes color, variance, len and flags (one byte per pixel, nullable), and with kWeight weight; depth and normal
 // are the kernel's copies.
 struct Next { float *color, *variance, *depth, *len, *normal; uint8_t *flags; float *weight; };
+// The moments planes of the kMoments flavour, apart from the sets so that the flavours without it keep their argument layout: the running
+// first and second moment of each pixel's luminance, 2 floats per pixel, interleaved and 8-byte aligned; prev is read, next written.
+struct Moments { const float *prev; float *next; };
 
 /* What the taps of one pixel's history add up to (steps 2, 3 and the sums of step 5 of the rule in include/mcpt.h). */
 struct Taps {
@@ -158,7 +162,26 @@ struct Taps {
     float nmin;            // the smallest prev.len of the used taps
     bool nskip;            // the normal test skipped a tap that every older test had passed (kNorm only)
     float hmin;            // the smallest prev.weight of the used taps (kWeight only): conservative, as nmin is for len
+    float sm1, sm2;        // sum of w * the taps' first and second luminance moment (kMoments only)
 };
+
+// The two moments of pixel q: one 8-byte load on the device.
+struct Mom2 { float m1, m2; };
+MCPT_TP Mom2 load_moments(const float *moments, size_t q) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const float2 v = reinterpret_cast<const float2 *>(moments)[q];
+    return {v.x, v.y};
+#else
+    return {moments[q * 2], moments[q * 2 + 1]};
+#endif
+}
+MCPT_TP void store_moments(float *moments, size_t q, float m1, float m2) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    reinterpret_cast<float2 *>(moments)[q] = make_float2(m1, m2);
+#else
+    moments[q * 2] = m1, moments[q * 2 + 1] = m2;
+#endif
+}
 
 /* The tap loop every flavour shares: the four bilinear taps of pixel (i, j) moved by its motion record, in tap order, with every skip of
  * the rule.  false if no tap is left.  kVar: also sum the taps' variances (p.variance is not read without it).
@@ -166,9 +189,11 @@ struct Taps {
  * kNorm: the normal test of mcpt_temporal_accumulate_ex after the depth test: a tap is skipped if !(d >= normal_min), d the 3-term dot
  * x + (y + z) of p.normal[tap] and this pixel's normal (neither f.normal nor p.normal is read without it).
  * kWeight: a tap is also skipped, together with the prev_len <= 0 test, if !(p.weight[tap] > 0) (a NaN weight skips it), and hmin is the
- * smallest weight of the used taps (p.weight is not read without it). */
-template <bool kVar, bool kNorm, bool kWeight = false>
-MCPT_TP bool gather_taps(int W, int H, int i, int j, const Frame &f, const Prev &p, const Opts &o, float normal_min, Taps &t) {
+ * smallest weight of the used taps (p.weight is not read without it).
+ * kMoments: also sum w * the taps' luminance moments, over exactly the taps the colour uses (prev_moments is not read without it). */
+template <bool kVar, bool kNorm, bool kWeight = false, bool kMoments = false>
+MCPT_TP bool gather_taps(int W, int H, int i, int j, const Frame &f, const Prev &p, const Opts &o, float normal_min, Taps &t,
+                         const float *prev_moments = nullptr) {
     const size_t m = (size_t)j * W + i;
     const float *mv = f.motion + m * 4;
     float n3[3] = {0.0f, 0.0f, 0.0f};
@@ -179,7 +204,7 @@ MCPT_TP bool gather_taps(int W, int H, int i, int j, const Frame &f, const Prev 
     const float a = fx - x0, b = fy - y0;
     const float wx[2] = {1.0f - a, a}, wy[2] = {1.0f - b, b};
     const float zp = mv[2], ztol = o.depth_tol * zp;
-    float sw = 0.0f, s0 = 0.0f, s1 = 0.0f, s2 = 0.0f, sv = 0.0f, nmin = 0.0f, hmin = 0.0f;
+    float sw = 0.0f, s0 = 0.0f, s1 = 0.0f, s2 = 0.0f, sv = 0.0f, nmin = 0.0f, hmin = 0.0f, sm1 = 0.0f, sm2 = 0.0f;
     bool any = false, nskip = false;
 #if defined(__HIP_DEVICE_COMPILE__)
 #pragma unroll
@@ -210,11 +235,16 @@ MCPT_TP bool gather_taps(int W, int H, int i, int j, const Frame &f, const Prev 
         s1 = s1 + w * p1;
         s2 = s2 + w * p2;
         if (kVar) sv = sv + (w * w) * p.variance[q];
+        if (kMoments) {
+            const Mom2 mq = load_moments(prev_moments, q);
+            sm1 = sm1 + w * mq.m1;
+            sm2 = sm2 + w * mq.m2;
+        }
         nmin = (!any || n < nmin) ? n : nmin;
         if (kWeight) hmin = (!any || hw < hmin) ? hw : hmin;
         any = true;
     }
-    t = {sw, s0, s1, s2, sv, nmin, nskip, hmin};
+    t = {sw, s0, s1, s2, sv, nmin, nskip, hmin, sm1, sm2};
     return any;
 }
 
@@ -254,10 +284,12 @@ MCPT_TP WeightStep weight_step(float hmin, float s, const Opts &o) {
 }
 
 // What the rule gives one pixel.  flags: bit 0 the normal test skipped a tap, bit 1 the clamp moved the history.  weight: kWeight only.
+// mu1, mu2: kMoments only.
 struct Pixel {
     float c0, c1, c2, variance, len;
     uint8_t flags;
     float weight;
+    float mu1, mu2;
 };
 
 /* The rule at pixel (i, j) of a W x H frame (include/mcpt.h: mcpt_temporal_blend, mcpt_temporal_accumulate[_ex]), once, with compile-time
@@ -280,16 +312,25 @@ struct Pixel {
  *          is the same from frame to frame, so counts are the inverse-variance weights up to a factor.  WITH UNIFORM COUNTS, HISTORY
  *          WEIGHTS EQUAL TO prev_len * s AND max_history * s < 2^24 THE FLAVOUR GIVES THE COLOUR, VARIANCE, len AND FLAGS OF THE
  *          UNWEIGHTED RULE BIT FOR BIT, AND weight = len * s (weight_step says why).
+ *   kMoments the running first and second moment of the pixel's luminance (mcpt_temporal_accumulate_moments; used without kVar: this flavour
+ *          reads and writes no variance plane, csrc/mcpt_moments.h derives the variance from the moments).  l = dn::lum(colour) of the new
+ *          frame, m1 = l, m2 = l*l.  Where the pixel takes history, over the taps the colour used, in tap order and from 0,
+ *              sm1 = sm1 + w * mo.prev[tap].m1;  hm1 = sm1 / sw;  mu1 = hm1 + (m1 - hm1) * k    (likewise mu2), k the colour's own.
+ *          An hm1 or hm2 that is not finite (a tap's stored moment was not) restarts both: (mu1, mu2) = (m1, m2), as for a pixel that
+ *          takes no history.  The clamp moves the colour history only, never the moments.  Colour, len and flags are untouched.
  * A pixel that takes no history (motion.valid <= 0, a colour that is not finite, no tap left) gets its own colour, v_c, length 1, flags 0. */
-template <bool kVar, bool kNorm, bool kClamp, bool kWeight = false>
-MCPT_TP Pixel reuse_pixel(int W, int H, int i, int j, const Frame &f, const Prev &p, const Opts &o, const HistOpts &ho) {
+template <bool kVar, bool kNorm, bool kClamp, bool kWeight = false, bool kMoments = false>
+MCPT_TP Pixel reuse_pixel(int W, int H, int i, int j, const Frame &f, const Prev &p, const Opts &o, const HistOpts &ho, const Moments &mo = Moments{}) {
     const size_t m = (size_t)j * W + i;
     const float c0 = f.color[m * 3], c1 = f.color[m * 3 + 1], c2 = f.color[m * 3 + 2];
     const float vc = kVar ? f.variance[m] : 0.0f;
     const float s = kWeight ? (f.count ? (float)f.count[m] : f.uniform_count) : 0.0f;
-    Pixel r = {c0, c1, c2, vc, 1.0f, 0, s};
+    const float l = kMoments ? dn::lum(c0, c1, c2) : 0.0f;
+    const float m1 = l, m2 = l * l;
+    Pixel r = {c0, c1, c2, vc, 1.0f, 0, s, m1, m2};
     Taps t;
-    if (f.motion[m * 4 + 3] > 0.0f && finite_f(c0) && finite_f(c1) && finite_f(c2) && gather_taps<kVar, kNorm, kWeight>(W, H, i, j, f, p, o, ho.normal_min, t)) {
+    if (f.motion[m * 4 + 3] > 0.0f && finite_f(c0) && finite_f(c1) && finite_f(c2) &&
+        gather_taps<kVar, kNorm, kWeight, kMoments>(W, H, i, j, f, p, o, ho.normal_min, t, mo.prev)) {
         float h0 = t.s0 / t.sw, h1 = t.s1 / t.sw, h2 = t.s2 / t.sw;
         bool clamped = false;
         if (kNorm && t.nskip) r.flags |= 1;
@@ -335,14 +376,21 @@ MCPT_TP Pixel reuse_pixel(int W, int H, int i, int j, const Frame &f, const Prev
             const float omk = 1.0f - k;
             if (!clamped && finite_f(hv) && hv >= 0.0f) r.variance = (omk * omk) * hv + (k * k) * vc;
         }
+        if (kMoments) {
+            const float hm1 = t.sm1 / t.sw, hm2 = t.sm2 / t.sw;
+            if (finite_f(hm1) && finite_f(hm2)) {
+                r.mu1 = hm1 + (m1 - hm1) * k;
+                r.mu2 = hm2 + (m2 - hm2) * k;
+            }
+        }
     }
     return r;
 }
 
 // The pixel's results into the next set: n.color[3 m ..], n.len[m]; with kVar n.variance[m]; with kFlags n.flags[m] where given; with
-// kWeight n.weight[m].
-template <bool kVar, bool kFlags, bool kWeight = false>
-MCPT_TP void store_pixel(const Next &n, size_t m, const Pixel &r) {
+// kWeight n.weight[m]; with kMoments next_moments[2 m ..].
+template <bool kVar, bool kFlags, bool kWeight = false, bool kMoments = false>
+MCPT_TP void store_pixel(const Next &n, size_t m, const Pixel &r, float *next_moments = nullptr) {
     n.color[m * 3] = r.c0;
     n.color[m * 3 + 1] = r.c1;
     n.color[m * 3 + 2] = r.c2;
@@ -350,6 +398,7 @@ MCPT_TP void store_pixel(const Next &n, size_t m, const Pixel &r) {
     n.len[m] = r.len;
     if (kFlags && n.flags) n.flags[m] = r.flags;
     if (kWeight) n.weight[m] = r.weight;
+    if (kMoments) store_moments(next_moments, m, r.mu1, r.mu2);
 }
 
 // The blend at pixel (i, j) (mcpt_temporal_blend), stored.
@@ -370,6 +419,15 @@ MCPT_TP void accumulate_pixel_weighted(int W, int H, int i, int j, const Frame &
     const Pixel r = ho.normal_test ? (ho.color_clamp ? reuse_pixel<true, true, true, true>(W, H, i, j, f, p, o, ho) : reuse_pixel<true, true, false, true>(W, H, i, j, f, p, o, ho))
                                    : (ho.color_clamp ? reuse_pixel<true, false, true, true>(W, H, i, j, f, p, o, ho) : reuse_pixel<true, false, false, true>(W, H, i, j, f, p, o, ho));
     store_pixel<true, true, true>(n, (size_t)j * W + i, r);
+}
+
+/* The accumulation of colour and luminance moments at pixel (i, j) (mcpt_temporal_accumulate_moments), stored: accumulate_pixel_ex's
+ * flavours with kMoments in place of kVar.  Neither variance plane is touched. */
+MCPT_TP void accumulate_pixel_moments(int W, int H, int i, int j, const Frame &f, const Prev &p, const Opts &o, const HistOpts &ho, const Next &n,
+                                      const Moments &mo) {
+    const Pixel r = ho.normal_test ? (ho.color_clamp ? reuse_pixel<false, true, true, false, true>(W, H, i, j, f, p, o, ho, mo) : reuse_pixel<false, true, false, false, true>(W, H, i, j, f, p, o, ho, mo))
+                                   : (ho.color_clamp ? reuse_pixel<false, false, true, false, true>(W, H, i, j, f, p, o, ho, mo) : reuse_pixel<false, false, false, false, true>(W, H, i, j, f, p, o, ho, mo));
+    store_pixel<false, true, false, true>(n, (size_t)j * W + i, r, mo.next);
 }
 
 /* The history length pixel (i, j) is about to get (include/mcpt.h: mcpt_temporal_history_len): steps 1-4 of the rule and the N of step 5,
@@ -439,6 +497,14 @@ MCPT_TP void accumulate_pixel_weighted(int W, int H, int i, int j, const float *
                               Prev{prev_color, prev_variance, prev_depth, prev_len, prev_normal, prev_weight}, o, ho,
                               Next{out_color, out_variance, nullptr, out_len, nullptr, out_flags, out_weight});
 }
+MCPT_TP void accumulate_pixel_moments(int W, int H, int i, int j, const float *color, const float *motion, const float *normal, int normal_stride,
+                                      const float *prev_color, const float *prev_depth, const float *prev_len, const float *prev_normal,
+                                      const float *prev_moments, const Opts &o, const HistOpts &ho, float *out_color, float *out_len, uint8_t *out_flags,
+                                      float *out_moments) {
+    accumulate_pixel_moments(W, H, i, j, Frame{color, nullptr, motion, normal, normal_stride, nullptr, 1},
+                             Prev{prev_color, nullptr, prev_depth, prev_len, prev_normal}, o, ho,
+                             Next{out_color, nullptr, nullptr, out_len, nullptr, out_flags}, Moments{prev_moments, out_moments});
+}
 MCPT_TP float history_weight_pixel(int W, int H, int i, int j, const float *motion, const float *normal, int normal_stride, const float *prev_color,
                                    const float *prev_depth, const float *prev_len, const float *prev_normal, const float *prev_weight, const Opts &o,
                                    const HistOpts &ho) {
@@ -487,6 +553,10 @@ void launch_temporal_blend(int W, int H, const tp::Opts &o, const tp::Frame &f, 
 // which also store n.weight[m]; otherwise the instantiations there have always been.
 void launch_temporal_accumulate(int W, int H, const tp::Opts &o, const tp::HistOpts &ho, const tp::Frame &f, const tp::Prev &p, const tp::Next &n,
                                 hipStream_t st);
+// The accumulation of colour and luminance moments (k_temporal_accumulate<kNorm, kClamp, false, true>): as above without n.weight; reads
+// mo.prev, stores mo.next[2 m ..] and touches no variance plane.
+void launch_temporal_accumulate_moments(int W, int H, const tp::Opts &o, const tp::HistOpts &ho, const tp::Frame &f, const tp::Prev &p, const tp::Next &n,
+                                        const tp::Moments &mo, hipStream_t st);
 // The history length every pixel is about to get (k_history_len: tp::history_len_pixel) into len[m]
 void launch_history_len(int W, int H, const tp::Opts &o, const tp::HistOpts &ho, const tp::Frame &f, const tp::Prev &p, float *len, hipStream_t st);
 // The history weight every pixel is about to get (k_history_weight: tp::history_weight_pixel) into weight[m]

@@ -25,7 +25,10 @@
 //                     k_temporal_accumulate<kNorm, kClamp, true> are the four kWeight instantiations (mcpt_temporal_accumulate_weighted, a
 //                     sequence created with weighted 1): one more load per tap (the history weight), the pixel's count or the uniform
 //                     one, and one more store, the new weight; 8 bytes per pixel of traffic.  The weight-off instantiations are the four
-//                     there have always been.
+//                     there have always been.  k_temporal_accumulate<kNorm, kClamp, false, true> are the four kMoments instantiations
+//                     (mcpt_temporal_accumulate_moments, a sequence created with moments): no variance plane read or written; one
+//                     8-byte load per tap (the history's luminance moments) and one 8-byte store, 16 bytes per pixel of traffic in
+//                     place of the 12 of the three variance accesses.
 //   k_history_len     the guide of an adaptive sequence (mcpt_temporal_history_len, mcpt_sequence_create_adaptive with guided 1):
 //                     tp::history_len_pixel, the taps and skips of the rule without its colour, known before the frame is rendered.
 //   k_history_weight  the same for a weighted sequence (mcpt_temporal_history_weight): tp::history_weight_pixel, the smallest history
@@ -198,12 +201,12 @@ __global__ __launch_bounds__(kTile *kTile) void k_temporal_blend(int W, int H, t
     tp::blend_pixel(W, H, x, y, f, p, o, n);
 }
 
-template <bool kNorm, bool kClamp, bool kWeight>
-__global__ __launch_bounds__(kTile *kTile) void k_temporal_accumulate(int W, int H, tp::Opts o, tp::HistOpts ho, tp::Frame f, tp::Prev p, tp::Next n) {
+template <bool kNorm, bool kClamp, bool kWeight, bool kMoments>
+__global__ __launch_bounds__(kTile *kTile) void k_temporal_accumulate(int W, int H, tp::Opts o, tp::HistOpts ho, tp::Frame f, tp::Prev p, tp::Next n, tp::Moments mo) {
     const int x = blockIdx.x * kTile + threadIdx.x, y = blockIdx.y * kTile + threadIdx.y;
     if (x >= W || y >= H) return;
     const size_t m = (size_t)y * W + x;
-    tp::store_pixel<true, kNorm || kClamp, kWeight>(n, m, tp::reuse_pixel<true, kNorm, kClamp, kWeight>(W, H, x, y, f, p, o, ho));
+    tp::store_pixel<!kMoments, kNorm || kClamp, kWeight, kMoments>(n, m, tp::reuse_pixel<!kMoments, kNorm, kClamp, kWeight, kMoments>(W, H, x, y, f, p, o, ho, mo), mo.next);
     if (f.depth) n.depth[m] = f.depth[m * (size_t)f.depth_stride];
     if (kNorm && n.normal) {  // (nothing reads the normals without the normal test; three loads, then three stores: one round trip)
         const float *fn = f.normal + m * (size_t)f.normal_stride;
@@ -224,10 +227,10 @@ __global__ __launch_bounds__(kTile *kTile) void k_history_weight(int W, int H, t
     weight[(size_t)y * W + x] = tp::history_weight_pixel(W, H, x, y, f, p, o, ho);
 }
 
-template <bool kWeight>
+template <bool kWeight, bool kMoments>
 auto accumulate_kernel(const tp::HistOpts &ho) {
-    return ho.normal_test ? (ho.color_clamp ? k_temporal_accumulate<true, true, kWeight> : k_temporal_accumulate<true, false, kWeight>)
-                          : (ho.color_clamp ? k_temporal_accumulate<false, true, kWeight> : k_temporal_accumulate<false, false, kWeight>);
+    return ho.normal_test ? (ho.color_clamp ? k_temporal_accumulate<true, true, kWeight, kMoments> : k_temporal_accumulate<true, false, kWeight, kMoments>)
+                          : (ho.color_clamp ? k_temporal_accumulate<false, true, kWeight, kMoments> : k_temporal_accumulate<false, false, kWeight, kMoments>);
 }
 
 inline dim3 tiles(int W, int H) { return dim3((W + kTile - 1) / kTile, (H + kTile - 1) / kTile); }
@@ -259,8 +262,13 @@ void launch_temporal_blend(int W, int H, const tp::Opts &o, const tp::Frame &f, 
 
 void launch_temporal_accumulate(int W, int H, const tp::Opts &o, const tp::HistOpts &ho, const tp::Frame &f, const tp::Prev &p, const tp::Next &n,
                                 hipStream_t st) {
-    const auto k = n.weight ? accumulate_kernel<true>(ho) : accumulate_kernel<false>(ho);
-    hipLaunchKernelGGL(k, tiles(W, H), dim3(kTile, kTile), 0, st, W, H, o, ho, f, p, n);
+    const auto k = n.weight ? accumulate_kernel<true, false>(ho) : accumulate_kernel<false, false>(ho);
+    hipLaunchKernelGGL(k, tiles(W, H), dim3(kTile, kTile), 0, st, W, H, o, ho, f, p, n, tp::Moments{});
+}
+
+void launch_temporal_accumulate_moments(int W, int H, const tp::Opts &o, const tp::HistOpts &ho, const tp::Frame &f, const tp::Prev &p, const tp::Next &n,
+                                        const tp::Moments &mo, hipStream_t st) {
+    hipLaunchKernelGGL((accumulate_kernel<false, true>(ho)), tiles(W, H), dim3(kTile, kTile), 0, st, W, H, o, ho, f, p, n, mo);
 }
 
 void launch_history_len(int W, int H, const tp::Opts &o, const tp::HistOpts &ho, const tp::Frame &f, const tp::Prev &p, float *len, hipStream_t st) {

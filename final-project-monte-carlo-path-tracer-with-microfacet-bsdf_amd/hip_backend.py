@@ -29,6 +29,7 @@ EXPORTS = ["mcpt_scene_create", "mcpt_scene_destroy", "mcpt_render", "mcpt_rende
            "mcpt_render_motion_ex", "mcpt_sequence_create_motion",
            "mcpt_temporal_accumulate_weighted", "mcpt_temporal_history_weight", "mcpt_render_adaptive_weighted",
            "mcpt_sequence_create_weighted", "mcpt_sequence_weight",
+           "mcpt_temporal_accumulate_moments", "mcpt_moments_variance", "mcpt_sequence_create_moments", "mcpt_sequence_moments",
            "mcpt_group_create", "mcpt_group_render", "mcpt_group_size", "mcpt_group_get_info", "mcpt_group_scene", "mcpt_group_destroy", "mcpt_group_last_error",
            "mcpt_last_error", "mcpt_version"]
 
@@ -155,7 +156,17 @@ class SequenceWeighted(C.Structure):
     _fields_ = [("weighted", C.c_int32), ("reserved", C.c_int32 * 7)]
 
 
-assert C.sizeof(SequenceMotion) == 32 and C.sizeof(SequenceWeighted) == 32
+class MomentsOpts(C.Structure):
+    _fields_ = [("enabled", C.c_int32), ("min_len", C.c_int32), ("radius", C.c_int32), ("sigma_z", C.c_float), ("reserved", C.c_int32 * 4)]
+
+
+def moments_opts(enabled=True, min_len=0, radius=0, sigma_z=0.0):
+    """mcpt_moments_opts: the variance of a sequence from the temporal moments of its luminance.  min_len: the shortest history whose
+    variance is temporal (0: 4); radius, sigma_z: the window and the depth gate of the spatial estimate shorter histories get (0: 3, 1)."""
+    return MomentsOpts(enabled=int(bool(enabled)), min_len=int(min_len), radius=int(radius), sigma_z=float(sigma_z))
+
+
+assert C.sizeof(SequenceMotion) == 32 and C.sizeof(SequenceWeighted) == 32 and C.sizeof(MomentsOpts) == 32
 assert C.sizeof(Adaptive) == 32 and C.sizeof(AdaptiveInfo) == 264 and C.sizeof(SequenceAdaptive) == 64
 assert C.sizeof(TemporalOpts) == 32 and C.sizeof(DenoiseOpts) == 32 and C.sizeof(HistoryOpts) == 32  # the sizes include/mcpt.h states
 assert C.sizeof(SequenceOpts) == 96 and C.sizeof(SequenceOutputs) == 64 and C.sizeof(SequenceInfo) == 64
@@ -286,6 +297,17 @@ def lib(path=None):
                                                     C.POINTER(C.c_void_p)]
         L.mcpt_sequence_weight.restype = C.c_int
         L.mcpt_sequence_weight.argtypes = [C.c_void_p, C.c_void_p]
+        L.mcpt_temporal_accumulate_moments.restype = C.c_int
+        L.mcpt_temporal_accumulate_moments.argtypes = ([C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 8
+                                                       + [C.POINTER(TemporalOpts), C.POINTER(HistoryOpts)] + [C.c_void_p] * 4)
+        L.mcpt_moments_variance.restype = C.c_int
+        L.mcpt_moments_variance.argtypes = [C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 4 + [C.POINTER(MomentsOpts), C.c_void_p]
+        L.mcpt_sequence_create_moments.restype = C.c_int
+        L.mcpt_sequence_create_moments.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(SequenceOpts), C.POINTER(HistoryOpts),
+                                                   C.POINTER(SequenceAdaptive), C.POINTER(SequenceMotion), C.POINTER(SequenceWeighted),
+                                                   C.POINTER(MomentsOpts), C.POINTER(C.c_void_p)]
+        L.mcpt_sequence_moments.restype = C.c_int
+        L.mcpt_sequence_moments.argtypes = [C.c_void_p, C.c_void_p]
         L.mcpt_sequence_create_ex.restype = C.c_int
         L.mcpt_sequence_create_ex.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(SequenceOpts), C.POINTER(HistoryOpts), C.POINTER(C.c_void_p)]
         L.mcpt_sequence_flags.restype = C.c_int
@@ -811,8 +833,52 @@ class HipScene:
                                                         _ptr(out), _ptr(out_var), _ptr(out_len), _ptr(flags), _ptr(out_weight)), L=self.L)
         return out, out_var, out_len, flags, out_weight
 
+    def temporal_accumulate_moments(self, color, motion, normal, prev_color, prev_depth, prev_len, prev_normal, prev_moments, normal_test=False,
+                                    color_clamp=False, normal_min=0.0, clamp_k=0.0, **opts):
+        """mcpt_temporal_accumulate_moments: temporal_accumulate_ex without its variance planes, carrying the running first and second moment
+        of each pixel's luminance instead.  prev_moments[H,W,2]: the previous out_moments of this call (0 for the first frame).  Returns
+        (out[H,W,3], out_len[H,W] float32, flags[H,W] uint8, out_moments[H,W,2] float32); the first three are temporal_accumulate_ex's
+        bit for bit."""
+        color = np.ascontiguousarray(color, dtype=np.float32)
+        H, W = color.shape[:2]
+        motion, prev_color, prev_depth, prev_len, prev_moments = (
+            np.ascontiguousarray(x, dtype=np.float32) for x in (motion, prev_color, prev_depth, prev_len, prev_moments))
+        normal, prev_normal = (None if x is None else np.ascontiguousarray(x, dtype=np.float32) for x in (normal, prev_normal))
+        n = H * W
+        if (color.size != n * 3 or motion.size != n * 4 or prev_color.size != n * 3 or prev_depth.size != n or prev_len.size != n
+                or prev_moments.size != n * 2 or any(x is not None and x.size != n * 3 for x in (normal, prev_normal))):
+            raise ValueError("temporal_accumulate_moments: the arrays do not describe one %dx%d frame" % (W, H))
+        out = np.zeros((H, W, 3), dtype=np.float32)
+        out_len = np.zeros((H, W), dtype=np.float32)
+        flags = np.zeros((H, W), dtype=np.uint8)
+        out_moments = np.zeros((H, W, 2), dtype=np.float32)
+        o = temporal_opts(**opts)
+        ho = history_opts(normal_test, color_clamp, normal_min, clamp_k)
+        _check(self.L.mcpt_temporal_accumulate_moments(self.h, W, H, _ptr(color), _ptr(motion), None if normal is None else _ptr(normal),
+                                                       _ptr(prev_color), _ptr(prev_depth), _ptr(prev_len),
+                                                       None if prev_normal is None else _ptr(prev_normal), _ptr(prev_moments), C.byref(o),
+                                                       C.byref(ho), _ptr(out), _ptr(out_len), _ptr(flags), _ptr(out_moments)), L=self.L)
+        return out, out_len, flags, out_moments
+
+    def moments_variance(self, moments, len, aov, flags=None, min_len=0, radius=0, sigma_z=0.0):
+        """mcpt_moments_variance: variance[H,W] float32 of the accumulated frame's luminance from its moments[H,W,2] and history lengths
+        len[H,W] (temporal_accumulate_moments' outputs), that frame's flags[H,W] uint8 (None: no pixel counts as clamped) and the AOVs
+        aov[H,W,8] the filter will read: temporal where the history has min_len frames, a gated spatial estimate elsewhere."""
+        moments = np.ascontiguousarray(moments, dtype=np.float32)
+        H, W = moments.shape[:2]
+        len, aov = (np.ascontiguousarray(x, dtype=np.float32) for x in (len, aov))
+        flags = None if flags is None else np.ascontiguousarray(flags, dtype=np.uint8)
+        n = H * W
+        if moments.size != n * 2 or len.size != n or aov.size != n * 8 or (flags is not None and flags.size != n):
+            raise ValueError("moments_variance: the arrays do not describe one %dx%d frame" % (W, H))
+        out = np.zeros((H, W), dtype=np.float32)
+        o = moments_opts(True, min_len, radius, sigma_z)
+        _check(self.L.mcpt_moments_variance(self.h, W, H, _ptr(moments), _ptr(len), None if flags is None else _ptr(flags), _ptr(aov), C.byref(o),
+                                            _ptr(out)), L=self.L)
+        return out
+
     def sequence(self, width=None, height=None, filter=True, max_history=0, depth_tol=0.0, normal_test=False, color_clamp=False, normal_min=0.0,
-                 clamp_k=0.0, adaptive=None, specular_motion=False, weighted=False, **denoise_opts_kw):
+                 clamp_k=0.0, adaptive=None, specular_motion=False, weighted=False, moments=False, **denoise_opts_kw):
         """mcpt_sequence_create: a HipSequence of width x height frames (default: the scene camera's) on this scene.  filter: also denoise
         the accumulated frame; max_history, depth_tol: mcpt_temporal_opts; the rest: mcpt_denoise_opts (aov_spp, iterations, sigma_l,
         sigma_n, sigma_z, specular_depth).  normal_test / color_clamp (normal_min, clamp_k): history rejection, mcpt_history_opts; with
@@ -823,10 +889,12 @@ class HipScene:
         chain depth (mcpt_sequence_create_motion).
         weighted: the history is weighted by sample counts -- the count map of an adaptive frame, `spp` of a uniform one -- and a guided
         adaptive rule is guided by the history weight (mcpt_sequence_create_weighted); HipSequence.weight() gives the last frame's weights.
+        moments: True or dict(min_len=, radius=, sigma_z=): the variance comes from the temporal moments of each pixel's luminance, carried
+        in the history, and frames may have `spp` 1 (mcpt_sequence_create_moments); HipSequence.moments() gives the last frame's moments.
         The sequence owns the scene's snapshot while it lives; close it before the scene."""
         return HipSequence(self, width, height, filter, max_history, depth_tol, normal_test=normal_test, color_clamp=color_clamp,
                            normal_min=normal_min, clamp_k=clamp_k, adaptive=adaptive, specular_motion=specular_motion, weighted=weighted,
-                           **denoise_opts_kw)
+                           moments=moments, **denoise_opts_kw)
 
     def render_device(self, fb_ptr, stream_ptr=0, camera=None, **kw):
         """Same, into a device framebuffer (W*H*3 floats at fb_ptr) on the given hipStream_t handle."""
@@ -929,14 +997,16 @@ class HipSequence:
 
     def __init__(self, scene, width=None, height=None, filter=True, max_history=0, depth_tol=0.0, normal_test=False, color_clamp=False,
                  normal_min=0.0, clamp_k=0.0, history=None, adaptive=None, create_adaptive=False, specular_motion=False, motion=None,
-                 weighted=None, **denoise_opts_kw):
+                 weighted=None, moments=None, **denoise_opts_kw):
         """history: a HistoryOpts passed to mcpt_sequence_create_ex as it is (tests: a zeroed one must give mcpt_sequence_create's sequence).
         adaptive: a dict of sequence_adaptive's keywords or a SequenceAdaptive; create_adaptive: go through mcpt_sequence_create_adaptive
         even without one (tests: a null rule must give mcpt_sequence_create_ex's sequence).  specular_motion: mcpt_sequence_create_motion
         with the switch on; motion: a SequenceMotion passed to it as it is, or "null" for a null pointer (tests: a null or zeroed one must
         give mcpt_sequence_create_adaptive's sequence).  weighted: True for mcpt_sequence_create_weighted with the switch on; a
         SequenceWeighted passed to it as it is, or "null" for a null pointer (tests: a null or zeroed one must give
-        mcpt_sequence_create_motion's sequence)."""
+        mcpt_sequence_create_motion's sequence).  moments: True or a dict of moments_opts' keywords for mcpt_sequence_create_moments with
+        the switch on; a MomentsOpts passed to it as it is, or "null" for a null pointer (tests: a null or zeroed one must give
+        mcpt_sequence_create_weighted's sequence)."""
         self.scene = scene  # (keeps the scene alive as long as the sequence)
         self.L = scene.L
         self.h = None
@@ -953,7 +1023,18 @@ class HipSequence:
             motion = SequenceMotion(specular_motion=1)
         if weighted is True:
             weighted = SequenceWeighted(weighted=1)
-        if weighted is not None and weighted is not False:
+        if moments is True:
+            moments = moments_opts()
+        elif isinstance(moments, dict):
+            moments = moments_opts(**moments)
+        if moments is not None and moments is not False:
+            w = None if weighted is None or weighted is False or isinstance(weighted, str) else weighted
+            _check(self.L.mcpt_sequence_create_moments(scene.h, self.W, self.H, C.byref(o), None if history is None else C.byref(history),
+                                                       None if adaptive is None else C.byref(adaptive),
+                                                       None if motion is None or isinstance(motion, str) else C.byref(motion),
+                                                       None if w is None else C.byref(w),
+                                                       None if isinstance(moments, str) else C.byref(moments), C.byref(h)), L=self.L)
+        elif weighted is not None and weighted is not False:
             _check(self.L.mcpt_sequence_create_weighted(scene.h, self.W, self.H, C.byref(o), None if history is None else C.byref(history),
                                                         None if adaptive is None else C.byref(adaptive),
                                                         None if motion is None or isinstance(motion, str) else C.byref(motion),
@@ -1000,6 +1081,13 @@ class HipSequence:
         sequence created without weighted keeps none and raises."""
         out = np.zeros((self.H, self.W), dtype=np.float32)
         _check(self.L.mcpt_sequence_weight(self.h, _ptr(out)), L=self.L)
+        return out
+
+    def moments(self):
+        """mcpt_sequence_moments: moments[H,W,2] float32, the running first and second moment of each pixel's luminance after the last frame
+        (0 before the first frame); a sequence created without moments keeps none and raises."""
+        out = np.zeros((self.H, self.W, 2), dtype=np.float32)
+        _check(self.L.mcpt_sequence_moments(self.h, _ptr(out)), L=self.L)
         return out
 
     def counts(self):

@@ -744,6 +744,81 @@ int mcpt_sequence_create_weighted(mcpt_scene *scene, int32_t width, int32_t heig
                                   const mcpt_sequence_motion *motion, const mcpt_sequence_weighted *weighted, mcpt_sequence **out);
 int mcpt_sequence_weight(mcpt_sequence *sequence, float *weight_host);
 
+/* ---- Sequences at one sample per pixel: temporal luminance moments (the temporal half of SVGF, Schied et al. 2017).  The variance every
+ * sequence above rests on is that of a frame's own samples, which needs two of them.  Here the history carries the running first and
+ * second moment of each pixel's luminance instead, and the variance of the accumulated frame comes from the frames themselves.
+ *
+ * mcpt_temporal_accumulate_moments: the rule of mcpt_temporal_accumulate_ex without its three variance planes (none is read or written),
+ * with two moments planes: prev_moments_host and out_moments_host, W*H*2 floats, {mu1, mu2} interleaved per pixel (0 everywhere for the
+ * first frame).  Per pixel, in float, without contraction, in this order:
+ *   l = (0.2126f * r + 0.7152f * g) + 0.0722f * b of the new colour;   m1 = l;   m2 = l * l;
+ *   where the rule takes history (step 5), over exactly the taps, weights w and sum sw the colour used, in tap order and from 0:
+ *       sm1 = sm1 + w * prev_moments[tap].mu1;   hm1 = sm1 / sw;   out_mu1 = hm1 + (m1 - hm1) * k     (likewise mu2)
+ *     with the colour's own k = 1.f / N; an hm1 or hm2 that is not finite (a tap's stored moment was not) gives out_mu = (m1, m2);
+ *   where it takes none (steps 1 and 4): out_mu = (m1, m2).
+ * The colour clamp moves the colour history only, never the moments.  out_color, out_len AND out_flags ARE THOSE OF
+ * mcpt_temporal_accumulate_ex ON THE SAME INPUTS, BIT FOR BIT.
+ * MCPT_ERR_ARG, before any device call: every case mcpt_temporal_accumulate_ex refuses (its variance arrays apart); a null
+ * prev_moments_host or out_moments_host.
+ *
+ * mcpt_moments_variance: the variance of the accumulated frame's luminance from those moments.  moments_host W*H*2 and len_host W*H as
+ * mcpt_temporal_accumulate_moments wrote them, flags_host W*H bytes (nullable: no pixel counts as clamped), aov_host W*H*8 the AOVs the filter
+ * will read; out_variance_host W*H.  Per pixel p, with N = len[p] and clamped = flags != null && (flags[p] & 2), in float:
+ *   its own moments are not finite (its colour was not):  v = +inf, which mcpt_denoise passes through;
+ *   temporal branch, N >= min_len and not clamped:
+ *       q = mu2 - mu1*mu1;   q = q > 0 ? q : 0;   v = q / (N - 1.f)
+ *     -- the unbiased per-frame variance q N / (N - 1) divided by the N frames of a running mean.  Beyond max_history the mean is
+ *     exponential and its variance smaller, so this over-estimates: the filter smooths more, never less;
+ *   spatial branch, everything else (a short history after a disocclusion or a reset, a clamped one): over the window dy = -radius..radius
+ *     (outer), dx = -radius..radius, p itself included, a pixel q counts if it is in the image, has finite moments and passes a binary
+ *     gate on the AOVs: both uncovered (coverage <= 0); or both covered with n_p.n_q > 0 (x + (y + z)) and
+ *       |z_p - z_q| <= (sigma_z * |grad_p . (dx, dy)| + 1e-3f * max(z_p, z_q)) + 1e-6f,   grad_p the depth gradient of mcpt_denoise;
+ *       cnt = cnt + 1.f;  s1 = s1 + mu1_q;  s2 = s2 + mu2_q;   a = s1 / cnt;  b = s2 / cnt;  q = b - a*a;  q = q > 0 ? q : 0;
+ *       sig2 = q * (cnt / (cnt - 1.f));   cnt < 2: sig2 = mu2_p (a variance never exceeds the second moment);
+ *       v = sig2 / (clamped ? 1.f : N).
+ *     The spatial estimate takes undemodulated luminance, so texture contrast inside the window counts as noise: it over-smooths only.
+ * opts.enabled is checked (0 | 1) and otherwise ignored here.
+ * MCPT_ERR_ARG, before any device call: a null scene, moments_host, len_host, aov_host, opts or out_variance_host; width or height <= 0
+ * or a frame too large; an option out of range or NaN; a non-zero reserved word. */
+typedef struct {
+    int32_t enabled;     /* 0 | 1 (mcpt_sequence_create_moments) */
+    int32_t min_len;     /* the shortest history whose variance is temporal; 0 => 4; 2..4096 */
+    int32_t radius;      /* of the spatial window; 0 => 3; 1..4 */
+    float sigma_z;       /* of the window's depth gate; 0 => 1; > 0 and finite */
+    int32_t reserved[4]; /* must be 0 */
+} mcpt_moments_opts;     /* 32 bytes */
+int mcpt_temporal_accumulate_moments(mcpt_scene *scene, int32_t width, int32_t height, const float *color_host, const float *motion_host,
+                                     const float *normal_host, const float *prev_color_host, const float *prev_depth_host,
+                                     const float *prev_len_host, const float *prev_normal_host, const float *prev_moments_host,
+                                     const mcpt_temporal_opts *opts, const mcpt_history_opts *history_opts, float *out_color_host,
+                                     float *out_len_host, uint8_t *out_flags_host, float *out_moments_host);
+int mcpt_moments_variance(mcpt_scene *scene, int32_t width, int32_t height, const float *moments_host, const float *len_host,
+                          const uint8_t *flags_host /* nullable */, const float *aov_host, const mcpt_moments_opts *opts,
+                          float *out_variance_host);
+
+/* A sequence that takes its variance from temporal moments, and so runs at params.spp 1.  A null or zeroed `moments`:
+ * mcpt_sequence_create_weighted, exactly (the same allocations, the same frames; such a sequence keeps refusing params.spp < 2).  With
+ * enabled 1 each history set gains a moments plane (8 bytes per pixel, 16 in all), the 48 bytes per pixel of the render's moments are not
+ * allocated, and mcpt_sequence_frame changes in these places and nowhere else:
+ *   step 1 accepts params.spp >= 1 (denoise.aov_spp 0 => min(4, params.spp); aov_spp <= params.spp still holds);
+ *   step 2 is the plain frame: fb is mcpt_render's frame bit for bit, and no moments of the render are summed;
+ *   step 5 is mcpt_temporal_accumulate_moments between the alternating history sets;
+ *   step 5b, right after it, is mcpt_moments_variance(the new set's moments and len, this frame's flags -- null for a sequence without
+ *      history rejection --, the AOVs of step 3 -- the chain AOVs with specular_depth > 0 --; moments) into the variance plane that step 6
+ *      and outputs.variance read.  ms_accumulate covers steps 5 and 5b.
+ * Every output still equals what the separate calls give, bit for bit.  After a reset prev_len is 0, so the moments restart; they live in
+ * the alternating history sets, so a failed frame leaves them as they were.  It combines with history rejection and with specular motion.
+ * mcpt_sequence_moments copies the moments of the last successful frame to moments_host (W*H*2 floats; all 0 before the first frame).
+ * MCPT_ERR_ARG, before any device call: as mcpt_sequence_create_weighted; enabled not 0 or 1, an option out of range or NaN, a non-zero
+ * reserved word; enabled 1 with an adaptive rule (its counts need min_spp >= 2 and bring their own variance) or with weighted 1 (a
+ * one-sample sequence has uniform counts, where weighting changes nothing); mcpt_sequence_moments for a null pointer or a sequence created
+ * without moments. */
+int mcpt_sequence_create_moments(mcpt_scene *scene, int32_t width, int32_t height, const mcpt_sequence_opts *opts,
+                                 const mcpt_history_opts *history_opts, const mcpt_sequence_adaptive *adaptive,
+                                 const mcpt_sequence_motion *motion, const mcpt_sequence_weighted *weighted, const mcpt_moments_opts *moments,
+                                 mcpt_sequence **out);
+int mcpt_sequence_moments(mcpt_sequence *sequence, float *moments_host);
+
 /* Replaces Scene::intersect (Scene.hpp:128, Scene.cpp:19-21) for a list of rays (host pointers; n*3 floats each).
  * out_t: hit distance as the reference's double Intersection::distance (DBL_MAX on a miss);
  * out_prim: global primitive id (triangle index, or n_triangles + object index for a sphere; -1 on a miss). */

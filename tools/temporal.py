@@ -24,6 +24,12 @@ frame k (a reference per frame; a static scene renders one).  --quality instead 
 history weight.  Prints the mean weight per frame.  --spp-list 64,4,4,4 with --quality: a uniform sequence whose frame k has the k-th count
 (the last one repeats), e.g. a caller that lowers params.spp while the camera moves.  --len-mask N: the MSE also over the pixels whose history
 length is N in that frame.
+  --moments   the variance comes from the temporal moments of each pixel's luminance (mcpt_sequence_create_moments), so --spp 1 is allowed:
+python tools/temporal.py --sequence --quality --spp 1 --moments [--min-len 4] [--radius 3].  The sequence is created with filter 1 and every frame
+also prints the RMSE after the tone curve (clip(c, 0, 1)^0.45) of the accumulated and of the denoised frame against the reference, and the
+share of pixels whose variance is temporal (len >= min_len).  --filtered prints the same two figures for a sequence without moments, whose
+filter is guided by the render's own variance: the pair to compare at equal samples is --frames 16 --spp 1 --moments against --frames 8
+--spp 2 --filtered.
   --specular-depth N   the sequence's denoise.specular_depth (the features behind up to N mirror / glass bounces); with --specular-motion the
 motion follows those chains too and the history is validated against the chain depth (mcpt_sequence_create_motion).  --move with --scene
 chess moves the nearest rough pawn by 6 units (about 3.5 px at 1080p) along x per frame, and the MSE is also given over the pixels whose
@@ -140,11 +146,12 @@ def sequence_timing(pkg, sd, W, H, frames, reject=None, loop=True):
 
 
 def sequence_quality(pkg, sd, W, H, frames, spp, adaptive, reject, move, ref_spp, specular_depth=0, specular_motion=False, weighted=False, spp_list=None,
-                     len_mask=0):
+                     len_mask=0, moments=None, filtered=False):
     """Per frame of a uniform (adaptive None) or adaptive sequence: samples, count histogram, stage times, MSE of `accumulated`.
     spp_list: the samples per pixel of frame k of a uniform sequence (the last entry repeats)."""
     hs = pkg.HipScene(sd)
-    seq = hs.sequence(filter=False, aov_spp=min(4, adaptive["min_spp"] if adaptive else min(spp_list or [spp])), adaptive=adaptive,
+    filtered = filtered or moments is not None
+    seq = hs.sequence(filter=filtered, moments=moments if moments is not None else False, aov_spp=min(4, adaptive["min_spp"] if adaptive else min(spp_list or [spp])), adaptive=adaptive,
                       specular_depth=specular_depth, specular_motion=specular_motion, weighted=weighted, **(reject or {}))
     chess = sd.name.startswith("chess")
     step = 6.0 if chess else -32.0  # object 1: the nearest rough pawn of the chess scene, the short box of the Cornell scene
@@ -157,7 +164,15 @@ def sequence_quality(pkg, sd, W, H, frames, spp, adaptive, reject, move, ref_spp
         print("specular depth %d, specular motion %s; %.1f %% of the pixels see the floor mirror first" % (specular_depth, bool(specular_motion), 100 * floor.mean()))
     what = ("uniform %s spp" % (",".join(str(x) for x in spp_list) if spp_list else spp)) + (", weighted" if weighted else "") if not adaptive else ("weighted " if weighted else "") + "adaptive %s, levels %d..%d, threshold %g" % (
         "guided" if adaptive["guided"] else "unguided", adaptive["min_spp"], spp, adaptive["threshold"])
+    if moments is not None:
+        what += ", variance from temporal moments (min_len %d, radius %d)" % (moments["min_len"] or 4, moments["radius"] or 3)
     print("%dx%d %s sequence, %s; reference %d spp" % (W, H, "moving" if move else "static", what, ref_spp))
+
+    def tone_rmse(img):
+        with np.errstate(invalid="ignore"):
+            d = np.clip(img.astype(np.float64), 0, 1) ** 0.45 - np.clip(truth, 0, 1) ** 0.45
+        return float(np.sqrt(np.nanmean(d * d)))
+
     truth, total = None, 0
     for k in range(frames):
         if move:
@@ -165,7 +180,7 @@ def sequence_quality(pkg, sd, W, H, frames, spp, adaptive, reject, move, ref_spp
         if truth is None or move:
             truth = hs.render(spp=ref_spp, seed=1000)[0].astype(np.float64)
         spp_k = spp_list[min(k, len(spp_list) - 1)] if spp_list else spp
-        r = seq.frame(want=("accumulated", "len"), spp=spp_k, seed=k + 1)
+        r = seq.frame(want=("accumulated", "len") + (("denoised",) if filtered else ()), spp=spp_k, seed=k + 1)
         sq = (r["accumulated"].astype(np.float64) - truth) ** 2
         mse = float(np.nanmean(sq))
         n = int(r["stats"].samples)
@@ -182,6 +197,10 @@ def sequence_quality(pkg, sd, W, H, frames, spp, adaptive, reject, move, ref_spp
         if len_mask:
             keep = r["len"] == len_mask
             hist += "  MSE where len == %d (%.1f %% of the pixels) %.6g" % (len_mask, 100 * keep.mean(), float(np.nanmean(sq[keep])) if keep.any() else float("nan"))
+        if filtered:
+            hist += "  tone-curve RMSE accumulated %.5f denoised %.5f" % (tone_rmse(r["accumulated"]), tone_rmse(r["denoised"]))
+        if moments is not None:
+            hist += "  temporal variance in %.1f %% of the pixels" % (100 * float((r["len"] >= (moments["min_len"] or 4)).mean()))
         if floor is not None:
             hist += "  MSE on the floor mirror %.6g" % float(np.nanmean(sq[floor]))
         i = r["info"]
@@ -215,6 +234,10 @@ def main():
     ap.add_argument("--spp", type=int, default=64, help="--adaptive: the cap; --quality: the samples per pixel")
     ap.add_argument("--move", action="store_true", help="--adaptive / --quality with --scene cornell: move the short box before every frame")
     ap.add_argument("--ref-spp", type=int, default=2048, help="--adaptive / --quality: samples per pixel of the reference")
+    ap.add_argument("--moments", action="store_true", help="--quality: the variance from temporal luminance moments (mcpt_sequence_create_moments); allows --spp 1")
+    ap.add_argument("--min-len", type=int, default=0, help="--moments: the shortest history whose variance is temporal (0: 4)")
+    ap.add_argument("--radius", type=int, default=0, help="--moments: the radius of the spatial window (0: 3)")
+    ap.add_argument("--filtered", action="store_true", help="--quality: create the sequence with filter 1 and print the tone-curve RMSE of the denoised frame too")
     ap.add_argument("--specular-depth", type=int, default=0, help="--adaptive / --quality: denoise.specular_depth of the sequence, and the depth of --specular-motion")
     ap.add_argument("--specular-motion", action="store_true", help="--adaptive / --quality: reproject what is seen through mirrors and glass (needs --specular-depth > 0)")
     a = ap.parse_args()
@@ -226,13 +249,13 @@ def main():
     spp_list = [int(x) for x in a.spp_list.split(",")] if a.spp_list else None
     if spp_list and a.adaptive is not None:
         sys.exit("--spp-list is for a uniform sequence (--quality)")
-    if a.sequence and (a.adaptive is not None or a.quality or a.move or a.specular_depth > 0 or a.weighted or spp_list):  # (the last four imply --quality)
+    if a.sequence and (a.adaptive is not None or a.quality or a.move or a.specular_depth > 0 or a.weighted or spp_list or a.moments or a.filtered):  # (all but the first two imply --quality)
         reject = dict(normal_test=a.normal_test, color_clamp=a.color_clamp, clamp_k=a.clamp_k) if a.normal_test or a.color_clamp else None
         rule = None if a.adaptive is None else dict(min_spp=a.adaptive_min, threshold=a.adaptive, dilate=1, guided=int(a.guided))
         if a.specular_motion and a.specular_depth <= 0:
             sys.exit("--specular-motion needs --specular-depth N > 0")
         return sequence_quality(pkg, sd, W, H, a.frames, a.spp, rule, reject, a.move, a.ref_spp, a.specular_depth, a.specular_motion, a.weighted, spp_list,
-                                a.len_mask)
+                                a.len_mask, dict(min_len=a.min_len, radius=a.radius) if a.moments else None, a.filtered)
     if a.sequence:
         if a.frames < 6:
             sys.exit("--frames must be at least 6")
