@@ -6,6 +6,7 @@
 //   k_trace_closest the scene's closest-hit traversal (mcpt_intersect)
 //   k_aov_resolve   hit -> per-sample record {albedo.rgb, depth} {normal.xyz, hit}
 //   k_aov_fold      one lane per pixel: the samples folded in sample order into the 8-float AOV record
+// With centre features (mcpt_feature_opts) k_centre_rays (csrc/mcpt_kernels.hip) takes the place of the first two, at one ray per pixel.
 // With specular_depth > 0 (mcpt_render_aovs_ex) k_aov_chain takes k_aov_resolve's place: a sample whose hit is a Dirac (mirror or glass)
 // vertex continues, compacted into the next ray list, which k_trace_closest traces; at most specular_depth more steps, then k_aov_fold.
 // Denoise (csrc/mcpt_denoise.h has the arithmetic, shared with the CPU build the tests compare against):

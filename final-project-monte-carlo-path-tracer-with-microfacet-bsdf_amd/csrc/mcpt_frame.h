@@ -53,12 +53,16 @@ struct FrameCall {
 
 // The AOV pass (include/mcpt.h): aov_dev[8m ..] for every pixel of the frame, queued on `st` (with spec_depth > 0 it waits for the
 // stream once per bounce).
-int aov_pass(mcpt_scene *sc, const CameraConst &cc, uint32_t seed, int32_t aov_spp, int32_t spec_depth, float *aov_dev, hipStream_t st);
+// centre (mcpt_feature_opts, for both passes): one feature ray per pixel, its centre ray; aov_spp must then be 1 and seed is ignored.
+int aov_pass(mcpt_scene *sc, const CameraConst &cc, uint32_t seed, int32_t aov_spp, int32_t spec_depth, bool centre, float *aov_dev, hipStream_t st);
+// The checks of a mcpt_feature_opts (nullable: every switch off) beside the aov_spp it is used with: MCPT_ERR_ARG in `name`'s name for a
+// centre that is not 0 or 1, a non-zero reserved word, or centre 1 with aov_spp > 1; otherwise `centre` is set.
+int check_features(const char *name, const mcpt_feature_opts *features, int32_t aov_spp, bool &centre);
 // The motion pass (include/mcpt.h: mcpt_render_motion[_ex]): motion_dev[4m ..] for every pixel of the frame, against the scene's snapshot.
 // spec_depth > 0: through the specular chains of aov_pass(.., spec_depth, ..) (it then waits for the stream once per bounce); their maps go
 // into `maps`, six planes of map_rays float4 with map_rays >= motion_map_rays(pixels, aov_spp), or with maps null into a buffer of the call's.
-int motion_pass(mcpt_scene *sc, const CameraConst &cc, const CameraConst &prev_cc, uint32_t seed, int32_t aov_spp, int32_t spec_depth, float4 *maps,
-                uint64_t map_rays, float *motion_dev, hipStream_t st);
+int motion_pass(mcpt_scene *sc, const CameraConst &cc, const CameraConst &prev_cc, uint32_t seed, int32_t aov_spp, int32_t spec_depth, bool centre,
+                float4 *maps, uint64_t map_rays, float *motion_dev, hipStream_t st);
 uint64_t motion_map_rays(uint64_t n_px, int32_t aov_spp);
 
 // What the rounds of an adaptive frame work in (adaptive_rounds): device buffers the caller owns.  Per pixel of the frame: fb 3 floats,

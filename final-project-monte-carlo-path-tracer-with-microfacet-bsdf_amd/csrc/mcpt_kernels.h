@@ -175,6 +175,8 @@ void launch_primary(const DevScene &S, const CameraConst &cam, const RenderConst
 void launch_generate_explicit(const RenderConst &C, Wave next, int next_idx, uint32_t n, hipStream_t s);
 void launch_camera_rays(const CameraConst &cam, uint32_t seed, uint32_t n, const uint32_t *pixel, const uint32_t *sample,
                         float4 *o, float4 *d, hipStream_t s);
+// The centre ray of pixel p0 + j into entry j, j < n: through the pixel centre and the centre of the lens (mcpt_centre_rays).
+void launch_centre_rays(const CameraConst &cam, uint32_t p0, uint32_t n, float4 *o, float4 *d, hipStream_t s);
 // n_dev != nullptr: the ray count is read on the device (n then only sizes the grid, which strides over the queue).
 void launch_trace_closest(const DevScene &S, uint32_t n, const uint32_t *n_dev, const float4 *ray_o, const float4 *ray_d, uint4 *hit,
                           const RetryList &rl, hipStream_t s);

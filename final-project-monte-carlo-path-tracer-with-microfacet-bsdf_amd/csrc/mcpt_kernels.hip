@@ -429,11 +429,12 @@ MCPT_DI f3 mat3_mul(const float *M, f3 v) {
     return mk3(M[0] * v.x + (M[1] * v.y + M[2] * v.z), M[3] * v.x + (M[4] * v.y + M[5] * v.z), M[6] * v.x + (M[7] * v.y + M[8] * v.z));
 }
 
-MCPT_DI void camera_ray(const CameraConst &cam, uint32_t seed, uint32_t m, uint32_t k, f3 &pos, f3 &dir) {
-    const int i = (int)(m % (uint32_t)cam.width), j = (int)(m / (uint32_t)cam.width);
-    RngKey rk{seed, m, k, 3u};
-    float u[4];
-    rng_block(rk, 0u, 0u, u);
+// The ray of pixel (i, j) for the four uniforms u: pixel jitter (u[0], u[1]) and lens sample (u[2] radius, u[3] angle).  kCentre: the caller
+// passes u = {0.5, 0.5, 0, 0}, the pixel centre through the centre of the lens, and the lens angle theta = 0 takes the bits
+// mcpt_sincosf(0.f) gives -- sin +0.f, cos 1.f (csrc/mcpt_fmath.h: kd = 0, r = 0, sn = r + r * (z * ps) = +0, cs = 1 + 0) -- without the
+// call; every other expression is the one of the sampled ray, in its order.
+template <bool kCentre>
+MCPT_DI void camera_ray_from(const CameraConst &cam, int i, int j, const float (&u)[4], f3 &pos, f3 &dir) {
     const f3 eye = mk3(cam.eye[0], cam.eye[1], cam.eye[2]);
     const float x = (1 - 2 * (i + u[0]) / (float)cam.width) * cam.aspect * cam.scale;
     const float y = (1 - 2 * (j + u[1]) / (float)cam.height) * cam.scale;
@@ -441,8 +442,8 @@ MCPT_DI void camera_ray(const CameraConst &cam, uint32_t seed, uint32_t m, uint3
         const f3 focal_point = mk3(x, y, 1) * cam.focal_distance;
         const float r = cam.aperture_radius * sqrtf(u[2]);
         const float theta = 2 * kPi * u[3];
-        float st, ct;
-        mcpt_sincosf(theta, &st, &ct);  // Renderer.cpp:59-60
+        float st = 0.f, ct = 1.f;
+        if (!kCentre) mcpt_sincosf(theta, &st, &ct);  // Renderer.cpp:59-60
         const float dx = r * ct;
         const float dy = r * st;
         pos = eye + mat3_mul(cam.orient, mk3(dx, dy, 0));
@@ -452,6 +453,15 @@ MCPT_DI void camera_ray(const CameraConst &cam, uint32_t seed, uint32_t m, uint3
         pos = eye;
     }
     dir = mat3_mul(cam.orient, dir);  // Renderer.cpp:76
+}
+
+// The camera ray of render sample k of pixel m: the uniforms of Philox stream 3.
+MCPT_DI void camera_ray(const CameraConst &cam, uint32_t seed, uint32_t m, uint32_t k, f3 &pos, f3 &dir) {
+    const int i = (int)(m % (uint32_t)cam.width), j = (int)(m / (uint32_t)cam.width);
+    RngKey rk{seed, m, k, 3u};
+    float u[4];
+    rng_block(rk, 0u, 0u, u);
+    camera_ray_from<false>(cam, i, j, u, pos, dir);
 }
 
 // The camera ray of sample s and its closest hit among the pixel's candidate primitives, when it has a short list (csrc/mcpt_cull.hip);
@@ -615,6 +625,18 @@ __global__ __launch_bounds__(kBlock) void k_camera_rays(CameraConst cam, uint32_
     if (j >= n) return;
     f3 pos, dir;
     camera_ray(cam, seed, pixel[j], sample[j], pos, dir);
+    o[j] = make_float4(pos.x, pos.y, pos.z, 0.f);
+    d[j] = make_float4(dir.x, dir.y, dir.z, 0.f);
+}
+
+// The centre rays of pixels p0 .. p0+n-1 (mcpt_centre_rays; the feature passes with centre 1): one lane per pixel, no key arrays, no Philox.
+__global__ __launch_bounds__(kBlock) void k_centre_rays(CameraConst cam, uint32_t p0, uint32_t n, float4 *o, float4 *d) {
+    const uint32_t j = blockIdx.x * kBlock + threadIdx.x;
+    if (j >= n) return;
+    const uint32_t m = p0 + j;
+    const float u[4] = {0.5f, 0.5f, 0.f, 0.f};
+    f3 pos, dir;
+    camera_ray_from<true>(cam, (int)(m % (uint32_t)cam.width), (int)(m / (uint32_t)cam.width), u, pos, dir);
     o[j] = make_float4(pos.x, pos.y, pos.z, 0.f);
     d[j] = make_float4(dir.x, dir.y, dir.z, 0.f);
 }
@@ -1555,6 +1577,11 @@ void launch_camera_rays(const CameraConst &cam, uint32_t seed, uint32_t n, const
                         float4 *o, float4 *d, hipStream_t s) {
     if (n == 0) return;
     hipLaunchKernelGGL(k_camera_rays, dim3(blocks(n)), dim3(kBlock), 0, s, cam, seed, n, pixel, sample, o, d);
+}
+
+void launch_centre_rays(const CameraConst &cam, uint32_t p0, uint32_t n, float4 *o, float4 *d, hipStream_t s) {
+    if (n == 0) return;
+    hipLaunchKernelGGL(k_centre_rays, dim3(blocks(n)), dim3(kBlock), 0, s, cam, p0, n, o, d);
 }
 
 void launch_trace_closest(const DevScene &S, uint32_t n, const uint32_t *n_dev, const float4 *ray_o, const float4 *ray_d, uint4 *hit,

@@ -1,4 +1,4 @@
-// The query entry points of the C ABI (include/mcpt.h): mcpt_intersect, mcpt_cast_rays, mcpt_camera_rays, the tone map, and the debug
+// The query entry points of the C ABI (include/mcpt.h): mcpt_intersect, mcpt_cast_rays, mcpt_camera_rays, mcpt_centre_rays, the tone map, and the debug
 // entry points.  Each stages its arguments in call-local device buffers (mcpt_cast_rays: in the wavefront workspace of pool 0).
 #include <cmath>
 
@@ -108,6 +108,31 @@ int mcpt_camera_rays(mcpt_scene *sc, const mcpt_camera *cam, uint32_t seed, int6
     HIP_TRY(upload(dP, pixel, n));
     HIP_TRY(upload(dS, sample, n));
     launch_camera_rays(make_camera(*cam), seed, (uint32_t)n, dP.p, dS.p, dO.p, dD.p, nullptr);
+    std::vector<float4> o(n), d(n);
+    HIP_TRY(download(o.data(), dO, n));
+    HIP_TRY(download(d.data(), dD, n));
+    unpack3(o, origins);
+    unpack3(d, dirs);
+    return MCPT_OK;
+}
+
+// One launch of k_centre_rays per run of consecutive pixels (a whole frame in pixel order is one run).
+int mcpt_centre_rays(mcpt_scene *sc, const mcpt_camera *cam, int64_t n, const uint32_t *pixel, float *origins, float *dirs) {
+    if (!sc || !cam || n < 0 || (n > 0 && (!pixel || !origins || !dirs))) return fail(MCPT_ERR_ARG, "mcpt_centre_rays: bad argument");
+    if (n == 0) return MCPT_OK;
+    if (n > 0x7fffffff) return fail(MCPT_ERR_ARG, "mcpt_centre_rays: too many rays for one call");
+    if (cam->width <= 0 || cam->height <= 0) return fail(MCPT_ERR_ARG, "mcpt_centre_rays: width and height must be positive");
+    HIP_TRY(hipSetDevice(sc->device));
+    DevBuf<float4> dO, dD;
+    HIP_TRY(dO.alloc(n));
+    HIP_TRY(dD.alloc(n));
+    const CameraConst cc = make_camera(*cam);
+    for (int64_t a = 0, b; a < n; a = b) {
+        for (b = a + 1; b < n && pixel[b] == pixel[b - 1] + 1u; ++b) {
+        }
+        launch_centre_rays(cc, pixel[a], (uint32_t)(b - a), dO.p + a, dD.p + a, nullptr);
+    }
+    HIP_TRY(hipGetLastError());
     std::vector<float4> o(n), d(n);
     HIP_TRY(download(o.data(), dO, n));
     HIP_TRY(download(d.data(), dD, n));

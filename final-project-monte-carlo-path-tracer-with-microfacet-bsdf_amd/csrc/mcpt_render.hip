@@ -131,8 +131,8 @@ struct AovOwn {
     DevBuf<double> chain_t[2];
     DevBuf<uint4> hit[2];
     RetryBufs retry;
-    hipError_t alloc(uint64_t cap, bool chain, int height, AovPtrs &a) {
-        hipError_t e = keys.alloc(2 * cap);
+    hipError_t alloc(uint64_t cap, bool chain, bool with_keys, int height, AovPtrs &a) {
+        hipError_t e = with_keys ? keys.alloc(2 * cap) : hipSuccess;
         const auto also = [&](auto &buf, size_t n) {
             if (e == hipSuccess) e = buf.alloc(n);
         };
@@ -152,7 +152,7 @@ struct AovOwn {
                 also(chain_t[k], cap);
             }
         }
-        a = AovPtrs{keys.p, keys.p + cap, s0.p, s1.p, {ray_o[0].p, ray_o[1].p}, {ray_d[0].p, ray_d[1].p}, {hit[0].p, hit[1].p},
+        a = AovPtrs{keys.p, with_keys ? keys.p + cap : nullptr, s0.p, s1.p, {ray_o[0].p, ray_o[1].p}, {ray_d[0].p, ray_d[1].p}, {hit[0].p, hit[1].p},
                     {chain_st[0].p, chain_st[1].p}, {chain_t[0].p, chain_t[1].p}, count.p, retry.list(0)};
         return e;
     }
@@ -167,8 +167,11 @@ struct AovOwn {
 // are needed too (in the workspace: vtx0 / vtx1 with wave 1's hits, wave 0's and wave 1's rec1, the sums in wave 0's rec0 and vtx2, the
 // count vtx_j[0]; chunks then hold at most `pool` rays).
 // max_rays > 0: no chunk holds more rays than that (at least aov_spp: the motion pass's map storage, motion_pass).
+// centre (mcpt_feature_opts; aov_spp is then 1): ray j of a chunk is the centre ray of pixel p0 + j, from k_centre_rays alone; the key
+// arrays are neither written nor read (nor allocated, where the call owns its buffers) and `seed` is not looked at.
 template <class Resolve>
-int first_hit_chunks(mcpt_scene *sc, const CameraConst &cc, uint32_t seed, int32_t aov_spp, bool chain, uint64_t max_rays, hipStream_t st, Resolve &&resolve) {
+int first_hit_chunks(mcpt_scene *sc, const CameraConst &cc, uint32_t seed, int32_t aov_spp, bool centre, bool chain, uint64_t max_rays, hipStream_t st,
+                     Resolve &&resolve) {
     const uint32_t n_px = (uint32_t)cc.width * (uint32_t)cc.height;
     const uint64_t need = std::min<uint64_t>(max_rays ? std::min<uint64_t>(kAovChunkRays, max_rays) : kAovChunkRays, (uint64_t)n_px * aov_spp);
     Workspace &w = sc->pools[0].ws;
@@ -180,12 +183,16 @@ int first_hit_chunks(mcpt_scene *sc, const CameraConst &cc, uint32_t seed, int32
     AovOwn own;
     AovPtrs a;
     if (in_ws) a = aov_in_workspace(w, cap, chain);
-    else HIP_TRY(own.alloc(cap, chain, sc->view.height, a));
+    else HIP_TRY(own.alloc(cap, chain, !centre, sc->view.height, a));
     const uint32_t px_chunk = (uint32_t)std::max<uint64_t>(1, cap / (uint64_t)aov_spp);
     for (uint32_t p0 = 0; p0 < n_px; p0 += px_chunk) {
         const uint32_t np = std::min(px_chunk, n_px - p0), n = np * (uint32_t)aov_spp;
-        launch_aov_keys(p0, n, aov_spp, a.key_pixel, a.key_sample, st);
-        launch_camera_rays(cc, seed, n, a.key_pixel, a.key_sample, a.list_o[0], a.list_d[0], st);
+        if (centre) {
+            launch_centre_rays(cc, p0, n, a.list_o[0], a.list_d[0], st);
+        } else {
+            launch_aov_keys(p0, n, aov_spp, a.key_pixel, a.key_sample, st);
+            launch_camera_rays(cc, seed, n, a.key_pixel, a.key_sample, a.list_o[0], a.list_d[0], st);
+        }
         launch_trace_closest(sc->view, n, nullptr, a.list_o[0], a.list_d[0], a.list_hit[0], a.rl, st);
         const int rc = resolve(a, p0, np, n);
         if (rc != MCPT_OK) return rc;
@@ -200,9 +207,9 @@ int first_hit_chunks(mcpt_scene *sc, const CameraConst &cc, uint32_t seed, int32
 // The AOV pass (include/mcpt.h): aov_dev[8m ..] for every pixel of the frame.  Per chunk k_aov_resolve, or with spec_depth > 0
 // (mcpt_render_aovs_ex) the specular chains -- k_aov_chain on the traced list, then up to spec_depth times k_trace_closest + k_aov_chain on
 // the compacted list of the samples that continue (its length read back once per bounce) -- and k_aov_fold.
-int mcpt::aov_pass(mcpt_scene *sc, const CameraConst &cc, uint32_t seed, int32_t aov_spp, int32_t spec_depth, float *aov_dev, hipStream_t st) {
+int mcpt::aov_pass(mcpt_scene *sc, const CameraConst &cc, uint32_t seed, int32_t aov_spp, int32_t spec_depth, bool centre, float *aov_dev, hipStream_t st) {
     const bool chain = spec_depth > 0;
-    return first_hit_chunks(sc, cc, seed, aov_spp, chain, 0, st, [&](const AovPtrs &a, uint32_t p0, uint32_t np, uint32_t n) -> int {
+    return first_hit_chunks(sc, cc, seed, aov_spp, centre, chain, 0, st, [&](const AovPtrs &a, uint32_t p0, uint32_t np, uint32_t n) -> int {
         if (!chain) {
             launch_aov_resolve(sc->view, n, a.list_o[0], a.list_d[0], a.list_hit[0], a.rec0, a.rec1, st);
         } else {
@@ -240,6 +247,18 @@ tp::Cam motion_camera(const CameraConst &cc) {
 
 }  // namespace
 
+int mcpt::check_features(const char *name, const mcpt_feature_opts *features, int32_t aov_spp, bool &centre) {
+    const auto bad = [&](const char *what) { return fail(MCPT_ERR_ARG, std::string(name) + ": " + what); };
+    centre = false;
+    if (!features) return MCPT_OK;
+    if (features->centre != 0 && features->centre != 1) return bad("features: centre must be 0 or 1");
+    for (int k = 0; k < 7; ++k)
+        if (features->reserved[k] != 0) return bad("features: reserved words must be 0");
+    if (features->centre == 1 && aov_spp > 1) return bad("features: centre 1 takes one feature ray per pixel (aov_spp must be 0 or 1)");
+    centre = features->centre == 1;
+    return MCPT_OK;
+}
+
 uint64_t mcpt::motion_map_rays(uint64_t n_px, int32_t aov_spp) { return std::min<uint64_t>(kMotionMapRays, n_px * (uint64_t)aov_spp); }
 
 // The motion pass (include/mcpt.h: mcpt_render_motion[_ex]): motion_dev[4m ..] for every pixel of the frame, from the rays and hits of the AOV
@@ -251,13 +270,13 @@ uint64_t mcpt::motion_map_rays(uint64_t n_px, int32_t aov_spp) { return std::min
 // allocated at its creation) or, with maps null, in a buffer of the call's own, freed after the stream has drained; either way outside the
 // workspace, so no array of aov_in_workspace -- wave 0 / 1 ray_o, ray_d, hit, rec0, rec1, vtx0, vtx1, vtx2, vtx_j -- can overlap them.
 // A chunk holds at most motion_map_rays(..) rays so that the storage stays below 96 MiB whatever the frame.
-int mcpt::motion_pass(mcpt_scene *sc, const CameraConst &cc, const CameraConst &prev_cc, uint32_t seed, int32_t aov_spp, int32_t spec_depth, float4 *maps,
-                      uint64_t map_rays, float *motion_dev, hipStream_t st) {
+int mcpt::motion_pass(mcpt_scene *sc, const CameraConst &cc, const CameraConst &prev_cc, uint32_t seed, int32_t aov_spp, int32_t spec_depth, bool centre,
+                      float4 *maps, uint64_t map_rays, float *motion_dev, hipStream_t st) {
     const tp::Cam cur = motion_camera(cc), prev = motion_camera(prev_cc);
     const TriGeom *prev_tri = sc->has_snapshot ? sc->snap_tri.p : sc->view.tri_geom;
     const SphereRec *prev_sph = sc->has_snapshot ? sc->snap_sph.p : sc->view.spheres;
     if (spec_depth == 0)
-        return first_hit_chunks(sc, cc, seed, aov_spp, false, 0, st, [&](const AovPtrs &a, uint32_t p0, uint32_t np, uint32_t n) -> int {
+        return first_hit_chunks(sc, cc, seed, aov_spp, centre, false, 0, st, [&](const AovPtrs &a, uint32_t p0, uint32_t np, uint32_t n) -> int {
             launch_motion_resolve(sc->view, prev_tri, prev_sph, cur, prev, n, a.list_o[0], a.list_d[0], a.list_hit[0], a.rec0, st);
             launch_motion_fold(p0, np, aov_spp, a.rec0, motion_dev, st);
             return MCPT_OK;
@@ -269,7 +288,7 @@ int mcpt::motion_pass(mcpt_scene *sc, const CameraConst &cc, const CameraConst &
         maps = own.p;
     }
     if (map_rays < (uint64_t)aov_spp) return fail(MCPT_ERR_ARG, "motion pass: the map storage holds less than one pixel's samples");
-    const int rc = first_hit_chunks(sc, cc, seed, aov_spp, true, map_rays, st, [&](const AovPtrs &a, uint32_t p0, uint32_t np, uint32_t n) -> int {
+    const int rc = first_hit_chunks(sc, cc, seed, aov_spp, centre, true, map_rays, st, [&](const AovPtrs &a, uint32_t p0, uint32_t np, uint32_t n) -> int {
         uint32_t m = n;  // rays in list `lc`, whose samples have all followed b bounces
         for (int b = 0, lc = 0;; ++b, lc ^= 1) {
             if (b < spec_depth) HIP_TRY(hipMemsetAsync(a.n_next, 0, sizeof(uint32_t), st));
@@ -292,42 +311,47 @@ int mcpt::motion_pass(mcpt_scene *sc, const CameraConst &cc, const CameraConst &
 
 namespace {
 
-// mcpt_render_aovs and mcpt_render_aovs_ex (`name` for the messages)
-int render_aovs(const char *name, mcpt_scene *sc, const mcpt_camera *cam, uint32_t seed, int32_t aov_spp, int32_t spec_depth, float *aov_host) {
+// mcpt_render_aovs, mcpt_render_aovs_ex and mcpt_render_aovs_features (`name` for the messages; features null: every switch off)
+int render_aovs(const char *name, mcpt_scene *sc, const mcpt_camera *cam, uint32_t seed, int32_t aov_spp, int32_t spec_depth, const mcpt_feature_opts *features,
+                float *aov_host) {
     const auto bad = [&](const char *what) { return fail(MCPT_ERR_ARG, std::string(name) + ": " + what); };
     if (!sc || !cam || !aov_host) return bad("null argument");
+    bool centre = false;
+    if (const int rc = check_features(name, features, aov_spp, centre)) return rc;
     if (!frame_ok(cam->width, cam->height)) return bad("width and height must be positive (and the frame not too large)");
     if (aov_spp < 0 || aov_spp > kMaxAovSpp) return bad("aov_spp must be 0..65536");
     if (spec_depth < 0 || spec_depth > dn::kMaxSpecularDepth) return bad("specular_depth must be 0..8");
-    const int32_t n_spp = aov_spp == 0 ? 4 : aov_spp;
+    const int32_t n_spp = centre ? 1 : aov_spp == 0 ? 4 : aov_spp;
     HIP_TRY(hipSetDevice(sc->device));
     (void)hipGetLastError();
     const size_t n_px = (size_t)cam->width * cam->height;
     DevBuf<float> aov;
     HIP_TRY(aov.alloc(n_px * 8));
-    const int rc = aov_pass(sc, make_camera(*cam), seed, n_spp, spec_depth, aov.p, nullptr);
+    const int rc = aov_pass(sc, make_camera(*cam), seed, n_spp, spec_depth, centre, aov.p, nullptr);
     if (rc != MCPT_OK) return drained(rc);
     HIP_TRY(download(aov_host, aov, n_px * 8));
     return MCPT_OK;
 }
 
-// mcpt_render_motion and mcpt_render_motion_ex (`name` for the messages)
+// mcpt_render_motion, mcpt_render_motion_ex and mcpt_render_motion_features (`name` for the messages; features null: every switch off)
 int render_motion(const char *name, mcpt_scene *sc, const mcpt_camera *cam, const mcpt_camera *prev_cam, uint32_t seed, int32_t aov_spp, int32_t spec_depth,
-                  float *motion_host) {
+                  const mcpt_feature_opts *features, float *motion_host) {
     const auto bad = [&](const char *what) { return fail(MCPT_ERR_ARG, std::string(name) + ": " + what); };
     if (!sc || !cam || !prev_cam || !motion_host) return bad("null argument");
+    bool centre = false;
+    if (const int rc = check_features(name, features, aov_spp, centre)) return rc;
     if (!frame_ok(cam->width, cam->height)) return bad("width and height must be positive (and the frame not too large)");
     if (prev_cam->width != cam->width || prev_cam->height != cam->height) return bad("prev_camera must have the width and height of camera");
     if (aov_spp < 0 || aov_spp > kMaxAovSpp) return bad("aov_spp must be 0..65536");
     if (spec_depth < 0 || spec_depth > tp::kMaxSpecularMotionDepth) return bad("specular_depth must be 0..8");
-    const int32_t n_spp = aov_spp == 0 ? 4 : aov_spp;
+    const int32_t n_spp = centre ? 1 : aov_spp == 0 ? 4 : aov_spp;
     HIP_TRY(hipSetDevice(sc->device));
     (void)hipGetLastError();
     const size_t n_px = (size_t)cam->width * cam->height;
     DevBuf<float> motion;
     HIP_TRY(motion.alloc(n_px * 4));
     const CameraConst cc = make_camera(*cam);
-    const int rc = motion_pass(sc, cc, make_camera(*prev_cam), seed, n_spp, spec_depth, nullptr, 0, motion.p, nullptr);
+    const int rc = motion_pass(sc, cc, make_camera(*prev_cam), seed, n_spp, spec_depth, centre, nullptr, 0, motion.p, nullptr);
     if (rc != MCPT_OK) return drained(rc);
     HIP_TRY(download(motion_host, motion, n_px * 4));
     return MCPT_OK;
@@ -484,7 +508,7 @@ struct DenoisedTail {
         const int W = f.cc.width, H = f.cc.height;
         const size_t n_px = (size_t)W * H;
         HIP_TRY(hipEventRecord(render_end, st));
-        const int rc = aov_pass(f.sc, f.cc, f.p.seed, aov_spp, opts.specular_depth, aov.p, st);
+        const int rc = aov_pass(f.sc, f.cc, f.p.seed, aov_spp, opts.specular_depth, false, aov.p, st);
         if (rc != MCPT_OK) return drained(rc);
         HIP_TRY(hipEventRecord(aov_end, st));
         launch_denoise(W, H, o, fb.p, var.p, aov.p, db.rec[0].p, db.rec[1].p, db.grad.p, out.p, st);
@@ -625,11 +649,16 @@ int mcpt_render_adaptive_denoised(mcpt_scene *sc, const mcpt_camera *cam, const 
 }
 
 int mcpt_render_aovs(mcpt_scene *sc, const mcpt_camera *cam, uint32_t seed, int32_t aov_spp, float *aov_host) {
-    return render_aovs("mcpt_render_aovs", sc, cam, seed, aov_spp, 0, aov_host);
+    return render_aovs("mcpt_render_aovs", sc, cam, seed, aov_spp, 0, nullptr, aov_host);
 }
 
 int mcpt_render_aovs_ex(mcpt_scene *sc, const mcpt_camera *cam, uint32_t seed, int32_t aov_spp, int32_t specular_depth, float *aov_host) {
-    return render_aovs("mcpt_render_aovs_ex", sc, cam, seed, aov_spp, specular_depth, aov_host);
+    return render_aovs("mcpt_render_aovs_ex", sc, cam, seed, aov_spp, specular_depth, nullptr, aov_host);
+}
+
+int mcpt_render_aovs_features(mcpt_scene *sc, const mcpt_camera *cam, uint32_t seed, int32_t aov_spp, int32_t specular_depth,
+                              const mcpt_feature_opts *features, float *aov_host) {
+    return render_aovs("mcpt_render_aovs_features", sc, cam, seed, aov_spp, specular_depth, features, aov_host);
 }
 
 int mcpt_denoise(mcpt_scene *sc, int32_t width, int32_t height, const float *color_host, const float *variance_host, const float *aov_host,
@@ -686,12 +715,17 @@ int mcpt_render_denoised(mcpt_scene *sc, const mcpt_camera *cam, const mcpt_para
 }
 
 int mcpt_render_motion(mcpt_scene *sc, const mcpt_camera *cam, const mcpt_camera *prev_cam, uint32_t seed, int32_t aov_spp, float *motion_host) {
-    return render_motion("mcpt_render_motion", sc, cam, prev_cam, seed, aov_spp, 0, motion_host);
+    return render_motion("mcpt_render_motion", sc, cam, prev_cam, seed, aov_spp, 0, nullptr, motion_host);
 }
 
 int mcpt_render_motion_ex(mcpt_scene *sc, const mcpt_camera *cam, const mcpt_camera *prev_cam, uint32_t seed, int32_t aov_spp, int32_t specular_depth,
                           float *motion_host) {
-    return render_motion("mcpt_render_motion_ex", sc, cam, prev_cam, seed, aov_spp, specular_depth, motion_host);
+    return render_motion("mcpt_render_motion_ex", sc, cam, prev_cam, seed, aov_spp, specular_depth, nullptr, motion_host);
+}
+
+int mcpt_render_motion_features(mcpt_scene *sc, const mcpt_camera *cam, const mcpt_camera *prev_cam, uint32_t seed, int32_t aov_spp, int32_t specular_depth,
+                                const mcpt_feature_opts *features, float *motion_host) {
+    return render_motion("mcpt_render_motion_features", sc, cam, prev_cam, seed, aov_spp, specular_depth, features, motion_host);
 }
 
 }  // extern "C"

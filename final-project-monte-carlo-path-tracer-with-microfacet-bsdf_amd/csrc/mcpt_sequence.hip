@@ -13,6 +13,8 @@
 // guided, takes its guide from k_history_weight.  A sequence created with moments (mcpt_sequence_create_moments, enabled 1) renders the plain
 // frame, keeps a moments plane in each history set, accumulates with the kMoments instantiations and takes the variance of the accumulated
 // frame from k_moments_variance (csrc/mcpt_moments.hip) right after; it has no moments of the render and runs at one sample per pixel.
+// A sequence created with centre features (mcpt_sequence_create_features, centre 1) takes every feature pass of a frame from the centre
+// rays, one per pixel.
 #include <new>
 
 #include "mcpt_frame.h"
@@ -194,6 +196,7 @@ struct mcpt_sequence {
     bool weighted = false;       // a sequence created with mcpt_sequence_create_weighted and weighted 1: the history sets have a weight plane
     bool moments = false;        // a sequence created with mcpt_sequence_create_moments and enabled 1: the history sets have a moments plane,
     mo::Opts mopts{};            // there is no `mom`, and the variance of the accumulated frame is k_moments_variance's
+    bool centre = false;         // a sequence created with mcpt_sequence_create_features and centre 1: the feature passes run on the centre rays
 };
 
 extern "C" {
@@ -320,6 +323,12 @@ int mcpt_sequence_create_weighted(mcpt_scene *sc, int32_t width, int32_t height,
 int mcpt_sequence_create_moments(mcpt_scene *sc, int32_t width, int32_t height, const mcpt_sequence_opts *opts, const mcpt_history_opts *hopts,
                                  const mcpt_sequence_adaptive *aopts, const mcpt_sequence_motion *mopts, const mcpt_sequence_weighted *wopts,
                                  const mcpt_moments_opts *momopts, mcpt_sequence **out) {
+    return mcpt_sequence_create_features(sc, width, height, opts, hopts, aopts, mopts, wopts, momopts, nullptr, out);
+}
+
+int mcpt_sequence_create_features(mcpt_scene *sc, int32_t width, int32_t height, const mcpt_sequence_opts *opts, const mcpt_history_opts *hopts,
+                                  const mcpt_sequence_adaptive *aopts, const mcpt_sequence_motion *mopts, const mcpt_sequence_weighted *wopts,
+                                  const mcpt_moments_opts *momopts, const mcpt_feature_opts *fopts, mcpt_sequence **out) {
     const auto bad = [](const char *what) { return fail(MCPT_ERR_ARG, std::string("mcpt_sequence_create: ") + what); };
     if (!sc || !opts || !out) return bad("null argument");
     *out = nullptr;
@@ -363,6 +372,8 @@ int mcpt_sequence_create_moments(mcpt_scene *sc, int32_t width, int32_t height, 
     const bool moments = momopts && momopts->enabled == 1;
     if (moments && aopts) return bad("moments: an adaptive rule brings its own variance (its counts need min_spp >= 2)");
     if (moments && weighted) return bad("moments: weighted must be 0 (a one-sample sequence has uniform counts)");
+    bool centre = false;
+    if (const int rc = check_features("mcpt_sequence_create", fopts, opts->denoise.aov_spp, centre)) return rc;
     // (with a specular depth of 0 the chains are the first hits: the switch changes nothing)
     const bool chain_motion = mopts && mopts->specular_motion == 1 && opts->denoise.specular_depth > 0;
     HIP_TRY(hipSetDevice(sc->device));
@@ -386,6 +397,7 @@ int mcpt_sequence_create_moments(mcpt_scene *sc, int32_t width, int32_t height, 
     seq->weighted = weighted;
     seq->moments = moments;
     seq->mopts = mo_opts;
+    seq->centre = centre;
     const size_t n_px = (size_t)width * height;
     hipError_t e = hipSuccess;
     const auto also = [&](auto &buf, size_t n) {
@@ -400,8 +412,8 @@ int mcpt_sequence_create_moments(mcpt_scene *sc, int32_t width, int32_t height, 
     if (!moments) also(seq->var, n_px);  // (a moments sequence has no variance of the frame)
     also(seq->aov, n_px * 8);
     if (opts->denoise.specular_depth > 0 && !chain_motion) also(seq->aov_first, n_px * 8);
-    if (chain_motion) {  // for the most feature samples a frame can ask for (aov_spp 0: at most 4)
-        seq->map_rays = motion_map_rays(n_px, opts->denoise.aov_spp == 0 ? 4 : opts->denoise.aov_spp);
+    if (chain_motion) {  // for the most feature samples a frame can ask for (aov_spp 0: at most 4; centre features: always 1)
+        seq->map_rays = motion_map_rays(n_px, centre ? 1 : opts->denoise.aov_spp == 0 ? 4 : opts->denoise.aov_spp);
         also(seq->maps, seq->map_rays * 6);
     }
     also(seq->motion, n_px * 4);
@@ -490,7 +502,8 @@ int mcpt_sequence_frame(mcpt_sequence *seq, const mcpt_camera *cam, const mcpt_p
         if ((rc = check_adaptive("mcpt_sequence_frame", seq->rule, p)) != MCPT_OK) return rc;
         if (dopts.aov_spp > seq->rule.min_spp) return bad("denoise.aov_spp must be at most min_spp");
     }
-    const int32_t aov_spp = dopts.aov_spp == 0 ? std::min(4, seq->adaptive ? seq->rule.min_spp : p.spp) : dopts.aov_spp;
+    const bool centre = seq->centre;  // (denoise.aov_spp is then 0 or 1: one centre ray per pixel)
+    const int32_t aov_spp = centre ? 1 : dopts.aov_spp == 0 ? std::min(4, seq->adaptive ? seq->rule.min_spp : p.spp) : dopts.aov_spp;
     mcpt_scene *sc = seq->sc;
     FrameCall f{sc, p};
     if ((rc = f.begin(*cam)) != MCPT_OK) return rc;
@@ -510,11 +523,12 @@ int mcpt_sequence_frame(mcpt_sequence *seq, const mcpt_camera *cam, const mcpt_p
     // The feature stage, from an event the branch has recorded: the AOVs (3.) with the first-hit depth the history is validated against,
     // and the motion (4.) against the snapshot and the previous frame's camera; a fresh sequence takes no history.
     const auto features = [&]() -> int {
-        int rc = aov_pass(sc, f.cc, p.seed, aov_spp, dopts.specular_depth, seq->aov.p, st);
-        if (rc == MCPT_OK && dopts.specular_depth > 0 && !seq->chain_motion) rc = aov_pass(sc, f.cc, p.seed, aov_spp, 0, seq->aov_first.p, st);
+        int rc = aov_pass(sc, f.cc, p.seed, aov_spp, dopts.specular_depth, centre, seq->aov.p, st);
+        if (rc == MCPT_OK && dopts.specular_depth > 0 && !seq->chain_motion) rc = aov_pass(sc, f.cc, p.seed, aov_spp, 0, centre, seq->aov_first.p, st);
         if (rc != MCPT_OK) return drained(rc);
         HIP_TRY(hipEventRecord(ev.aov_end, st));
-        rc = motion_pass(sc, f.cc, seq->fresh ? f.cc : seq->prev_cc, p.seed, aov_spp, motion_depth, seq->maps.p, seq->map_rays, seq->motion.p, st);
+        rc = motion_pass(sc, f.cc, seq->fresh ? f.cc : seq->prev_cc, p.seed, aov_spp, motion_depth, centre, seq->maps.p, seq->map_rays,
+                         seq->motion.p, st);
         if (rc != MCPT_OK) return drained(rc);
         if (seq->fresh) HIP_TRY(hipMemsetAsync(prev.len.p, 0, n_px * sizeof(float), st));
         return MCPT_OK;

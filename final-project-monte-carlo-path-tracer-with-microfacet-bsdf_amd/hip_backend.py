@@ -30,6 +30,7 @@ EXPORTS = ["mcpt_scene_create", "mcpt_scene_destroy", "mcpt_render", "mcpt_rende
            "mcpt_temporal_accumulate_weighted", "mcpt_temporal_history_weight", "mcpt_render_adaptive_weighted",
            "mcpt_sequence_create_weighted", "mcpt_sequence_weight",
            "mcpt_temporal_accumulate_moments", "mcpt_moments_variance", "mcpt_sequence_create_moments", "mcpt_sequence_moments",
+           "mcpt_centre_rays", "mcpt_render_aovs_features", "mcpt_render_motion_features", "mcpt_sequence_create_features",
            "mcpt_group_create", "mcpt_group_render", "mcpt_group_size", "mcpt_group_get_info", "mcpt_group_scene", "mcpt_group_destroy", "mcpt_group_last_error",
            "mcpt_last_error", "mcpt_version"]
 
@@ -166,7 +167,11 @@ def moments_opts(enabled=True, min_len=0, radius=0, sigma_z=0.0):
     return MomentsOpts(enabled=int(bool(enabled)), min_len=int(min_len), radius=int(radius), sigma_z=float(sigma_z))
 
 
-assert C.sizeof(SequenceMotion) == 32 and C.sizeof(SequenceWeighted) == 32 and C.sizeof(MomentsOpts) == 32
+class FeatureOpts(C.Structure):
+    _fields_ = [("centre", C.c_int32), ("reserved", C.c_int32 * 7)]
+
+
+assert C.sizeof(SequenceMotion) == 32 and C.sizeof(SequenceWeighted) == 32 and C.sizeof(MomentsOpts) == 32 and C.sizeof(FeatureOpts) == 32
 assert C.sizeof(Adaptive) == 32 and C.sizeof(AdaptiveInfo) == 264 and C.sizeof(SequenceAdaptive) == 64
 assert C.sizeof(TemporalOpts) == 32 and C.sizeof(DenoiseOpts) == 32 and C.sizeof(HistoryOpts) == 32  # the sizes include/mcpt.h states
 assert C.sizeof(SequenceOpts) == 96 and C.sizeof(SequenceOutputs) == 64 and C.sizeof(SequenceInfo) == 64
@@ -306,6 +311,17 @@ def lib(path=None):
         L.mcpt_sequence_create_moments.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(SequenceOpts), C.POINTER(HistoryOpts),
                                                    C.POINTER(SequenceAdaptive), C.POINTER(SequenceMotion), C.POINTER(SequenceWeighted),
                                                    C.POINTER(MomentsOpts), C.POINTER(C.c_void_p)]
+        L.mcpt_sequence_create_features.restype = C.c_int
+        L.mcpt_sequence_create_features.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(SequenceOpts), C.POINTER(HistoryOpts),
+                                                    C.POINTER(SequenceAdaptive), C.POINTER(SequenceMotion), C.POINTER(SequenceWeighted),
+                                                    C.POINTER(MomentsOpts), C.POINTER(FeatureOpts), C.POINTER(C.c_void_p)]
+        L.mcpt_centre_rays.restype = C.c_int
+        L.mcpt_centre_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 3
+        L.mcpt_render_aovs_features.restype = C.c_int
+        L.mcpt_render_aovs_features.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.c_int32, C.POINTER(FeatureOpts), C.c_void_p]
+        L.mcpt_render_motion_features.restype = C.c_int
+        L.mcpt_render_motion_features.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.c_int32, C.POINTER(FeatureOpts),
+                                                  C.c_void_p]
         L.mcpt_sequence_moments.restype = C.c_int
         L.mcpt_sequence_moments.argtypes = [C.c_void_p, C.c_void_p]
         L.mcpt_sequence_create_ex.restype = C.c_int
@@ -672,13 +688,21 @@ class HipScene:
                                                    _ptr(prev_weight), C.byref(o), C.byref(ho), _ptr(out)), L=self.L)
         return out
 
-    def render_aovs(self, aov_spp=0, seed=1, camera=None, specular_depth=0):
+    def render_aovs(self, aov_spp=0, seed=1, camera=None, specular_depth=0, centre=False, features=None):
         """mcpt_render_aovs: aov[H,W,8] float32 = {albedo rgb, normal xyz, depth, coverage} from feature samples 0 .. aov_spp-1 (0: 4) of `seed`;
-        specular_depth > 0: mcpt_render_aovs_ex, the features taken behind up to that many mirror / glass bounces."""
+        specular_depth > 0: mcpt_render_aovs_ex, the features taken behind up to that many mirror / glass bounces.
+        centre: mcpt_render_aovs_features with centre 1, the features of each pixel's centre ray (aov_spp 0 or 1; `seed` is ignored).
+        features: a FeatureOpts passed to mcpt_render_aovs_features as it is, or "null" for a null pointer (tests: either must give
+        mcpt_render_aovs_ex's record)."""
         cam = np.ascontiguousarray(camera if camera is not None else self.sd.camera)
         W, H = int(cam["width"].reshape(-1)[0]), int(cam["height"].reshape(-1)[0])
         aov = np.zeros((H, W, 8), dtype=np.float32)
-        if specular_depth == 0:
+        if centre and features is None:
+            features = FeatureOpts(centre=1)
+        if features is not None:
+            _check(self.L.mcpt_render_aovs_features(self.h, _ptr(cam), int(seed), int(aov_spp), int(specular_depth),
+                                                    None if isinstance(features, str) else C.byref(features), _ptr(aov)), L=self.L)
+        elif specular_depth == 0:
             _check(self.L.mcpt_render_aovs(self.h, _ptr(cam), int(seed), int(aov_spp), _ptr(aov)), L=self.L)
         else:
             _check(self.L.mcpt_render_aovs_ex(self.h, _ptr(cam), int(seed), int(aov_spp), int(specular_depth), _ptr(aov)), L=self.L)
@@ -722,16 +746,23 @@ class HipScene:
         update calls; without one, render_motion sees camera motion only)."""
         _check(self.L.mcpt_scene_snapshot(self.h), L=self.L)
 
-    def render_motion(self, prev_camera=None, seed=1, aov_spp=0, camera=None, specular_depth=0):
+    def render_motion(self, prev_camera=None, seed=1, aov_spp=0, camera=None, specular_depth=0, centre=False, features=None):
         """mcpt_render_motion: motion[H,W,4] float32 = {dx, dy, prev_depth, valid}: where the surface seen in each pixel was on the screen of
         prev_camera (default: the camera itself) when snapshot() was last called, from the feature samples of render_aovs(aov_spp, seed).
         specular_depth > 0: mcpt_render_motion_ex, the motion of what is seen behind up to that many mirror / glass bounces (the chains of
-        render_aovs(aov_spp, seed, specular_depth=...)), as a virtual point on the primary ray."""
+        render_aovs(aov_spp, seed, specular_depth=...)), as a virtual point on the primary ray.
+        centre: mcpt_render_motion_features with centre 1, the motion of what each pixel's centre ray sees (aov_spp 0 or 1; `seed` is
+        ignored); features: a FeatureOpts or "null", as in render_aovs."""
         cam = np.ascontiguousarray(camera if camera is not None else self.sd.camera)
         prev = np.ascontiguousarray(prev_camera if prev_camera is not None else cam)
         W, H = int(cam["width"].reshape(-1)[0]), int(cam["height"].reshape(-1)[0])
         motion = np.zeros((H, W, 4), dtype=np.float32)
-        if specular_depth == 0:
+        if centre and features is None:
+            features = FeatureOpts(centre=1)
+        if features is not None:
+            _check(self.L.mcpt_render_motion_features(self.h, _ptr(cam), _ptr(prev), int(seed), int(aov_spp), int(specular_depth),
+                                                      None if isinstance(features, str) else C.byref(features), _ptr(motion)), L=self.L)
+        elif specular_depth == 0:
             _check(self.L.mcpt_render_motion(self.h, _ptr(cam), _ptr(prev), int(seed), int(aov_spp), _ptr(motion)), L=self.L)
         else:
             _check(self.L.mcpt_render_motion_ex(self.h, _ptr(cam), _ptr(prev), int(seed), int(aov_spp), int(specular_depth), _ptr(motion)), L=self.L)
@@ -878,7 +909,7 @@ class HipScene:
         return out
 
     def sequence(self, width=None, height=None, filter=True, max_history=0, depth_tol=0.0, normal_test=False, color_clamp=False, normal_min=0.0,
-                 clamp_k=0.0, adaptive=None, specular_motion=False, weighted=False, moments=False, **denoise_opts_kw):
+                 clamp_k=0.0, adaptive=None, specular_motion=False, weighted=False, moments=False, centre_features=False, **denoise_opts_kw):
         """mcpt_sequence_create: a HipSequence of width x height frames (default: the scene camera's) on this scene.  filter: also denoise
         the accumulated frame; max_history, depth_tol: mcpt_temporal_opts; the rest: mcpt_denoise_opts (aov_spp, iterations, sigma_l,
         sigma_n, sigma_z, specular_depth).  normal_test / color_clamp (normal_min, clamp_k): history rejection, mcpt_history_opts; with
@@ -891,10 +922,12 @@ class HipScene:
         adaptive rule is guided by the history weight (mcpt_sequence_create_weighted); HipSequence.weight() gives the last frame's weights.
         moments: True or dict(min_len=, radius=, sigma_z=): the variance comes from the temporal moments of each pixel's luminance, carried
         in the history, and frames may have `spp` 1 (mcpt_sequence_create_moments); HipSequence.moments() gives the last frame's moments.
+        centre_features: every feature pass of a frame (AOVs, motion) runs on the pixels' centre rays, one per pixel, so that a static
+        pixel's features are the same bits in every frame whatever the seed and the lens (mcpt_sequence_create_features; aov_spp 0 or 1).
         The sequence owns the scene's snapshot while it lives; close it before the scene."""
         return HipSequence(self, width, height, filter, max_history, depth_tol, normal_test=normal_test, color_clamp=color_clamp,
                            normal_min=normal_min, clamp_k=clamp_k, adaptive=adaptive, specular_motion=specular_motion, weighted=weighted,
-                           moments=moments, **denoise_opts_kw)
+                           moments=moments, features=FeatureOpts(centre=1) if centre_features else None, **denoise_opts_kw)
 
     def render_device(self, fb_ptr, stream_ptr=0, camera=None, **kw):
         """Same, into a device framebuffer (W*H*3 floats at fb_ptr) on the given hipStream_t handle."""
@@ -978,6 +1011,17 @@ class HipScene:
         _check(self.L.mcpt_cast_rays(self.h, C.byref(p), n, _ptr(o), _ptr(d), _ptr(px), _ptr(sm), _ptr(ch), _ptr(out)), L=self.L)
         return out
 
+    def centre_rays(self, pixels, camera=None):
+        """mcpt_centre_rays: the centre rays of `pixels` (m = j*W + i) -> (origins[n,3], dirs[n,3]) float32: through the pixel centre and
+        the centre of the lens, a function of the camera alone."""
+        cam = np.ascontiguousarray(camera if camera is not None else self.sd.camera)
+        px = np.ascontiguousarray(pixels, dtype=np.uint32)
+        n = len(px)
+        o = np.zeros((n, 3), dtype=np.float32)
+        d = np.zeros((n, 3), dtype=np.float32)
+        _check(self.L.mcpt_centre_rays(self.h, _ptr(cam), n, _ptr(px), _ptr(o), _ptr(d)), L=self.L)
+        return o, d
+
     def camera_rays(self, pixels, samples, seed=1, camera=None):
         cam = np.ascontiguousarray(camera if camera is not None else self.sd.camera)
         px = np.ascontiguousarray(pixels, dtype=np.uint32)
@@ -997,7 +1041,7 @@ class HipSequence:
 
     def __init__(self, scene, width=None, height=None, filter=True, max_history=0, depth_tol=0.0, normal_test=False, color_clamp=False,
                  normal_min=0.0, clamp_k=0.0, history=None, adaptive=None, create_adaptive=False, specular_motion=False, motion=None,
-                 weighted=None, moments=None, **denoise_opts_kw):
+                 weighted=None, moments=None, features=None, **denoise_opts_kw):
         """history: a HistoryOpts passed to mcpt_sequence_create_ex as it is (tests: a zeroed one must give mcpt_sequence_create's sequence).
         adaptive: a dict of sequence_adaptive's keywords or a SequenceAdaptive; create_adaptive: go through mcpt_sequence_create_adaptive
         even without one (tests: a null rule must give mcpt_sequence_create_ex's sequence).  specular_motion: mcpt_sequence_create_motion
@@ -1006,7 +1050,8 @@ class HipSequence:
         SequenceWeighted passed to it as it is, or "null" for a null pointer (tests: a null or zeroed one must give
         mcpt_sequence_create_motion's sequence).  moments: True or a dict of moments_opts' keywords for mcpt_sequence_create_moments with
         the switch on; a MomentsOpts passed to it as it is, or "null" for a null pointer (tests: a null or zeroed one must give
-        mcpt_sequence_create_weighted's sequence)."""
+        mcpt_sequence_create_weighted's sequence).  features: a FeatureOpts passed to mcpt_sequence_create_features as it is, or "null" for a
+        null pointer (tests: a null or zeroed one must give mcpt_sequence_create_moments' sequence)."""
         self.scene = scene  # (keeps the scene alive as long as the sequence)
         self.L = scene.L
         self.h = None
@@ -1027,7 +1072,15 @@ class HipSequence:
             moments = moments_opts()
         elif isinstance(moments, dict):
             moments = moments_opts(**moments)
-        if moments is not None and moments is not False:
+        if features is not None:
+            w = None if weighted is None or weighted is False or isinstance(weighted, str) else weighted
+            m = None if moments is None or moments is False or isinstance(moments, str) else moments
+            _check(self.L.mcpt_sequence_create_features(scene.h, self.W, self.H, C.byref(o), None if history is None else C.byref(history),
+                                                        None if adaptive is None else C.byref(adaptive),
+                                                        None if motion is None or isinstance(motion, str) else C.byref(motion),
+                                                        None if w is None else C.byref(w), None if m is None else C.byref(m),
+                                                        None if isinstance(features, str) else C.byref(features), C.byref(h)), L=self.L)
+        elif moments is not None and moments is not False:
             w = None if weighted is None or weighted is False or isinstance(weighted, str) else weighted
             _check(self.L.mcpt_sequence_create_moments(scene.h, self.W, self.H, C.byref(o), None if history is None else C.byref(history),
                                                        None if adaptive is None else C.byref(adaptive),

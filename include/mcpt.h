@@ -819,6 +819,54 @@ int mcpt_sequence_create_moments(mcpt_scene *scene, int32_t width, int32_t heigh
                                  mcpt_sequence **out);
 int mcpt_sequence_moments(mcpt_sequence *sequence, float *moments_host);
 
+/* ---- Pixel-centre feature rays.  Feature sample k above is the camera ray of render sample k: it carries the pixel jitter and the lens
+ * sample, so a pixel's features change with the seed, and under depth of field one such ray lands anywhere inside the circle of
+ * confusion.  With centre 1 the features of pixel m come from ONE deterministic ray instead, the centre ray of mcpt_centre_rays: through
+ * the pixel centre and the centre of the lens.  It is the camera ray of Renderer.cpp:44-76 for the uniforms u = {0.5f, 0.5f, 0.f, 0.f}
+ * in place of the Philox draw, every expression in its order, in float, without contraction:
+ *   i = m % W, j = m / W;   x = (1 - 2 * (i + 0.5f) / (float) W) * aspect * scale;   y = (1 - 2 * (j + 0.5f) / (float) H) * scale;
+ *   without depth of field  pos = eye,  dir = orient * normalized((x, y, 1));
+ *   with depth of field     focal_point = (x, y, 1) * focal_distance;  r = aperture_radius * sqrtf(0.f);  sin = +0.f and cos = 1.f, the
+ *                           bits the library's sincos gives at theta = 0;  dx = r * cos;  dy = r * sin;
+ *                           pos = eye + orient * (dx, dy, 0);  dir = orient * normalized(focal_point - (dx, dy, 0))
+ *   (normalized(v) = v / sqrtf(v.v) and the 3 x 3 products in the 3-term order a*x + (b*y + c*z), as for every camera ray).
+ * So a finite aperture gives pos = eye + orient * (0, 0, 0) and the direction through the focal point: the pinhole ray up to rounding.
+ * The ray is a function of the camera alone.  Everything behind it is unchanged: the closest-hit traversal, the first-hit records or the
+ * chains of mcpt_render_aovs_ex / mcpt_render_motion_ex (whose branch rule, kr > 0.5, is deterministic already) and the folds, at one
+ * sample per pixel.  A centre AOV or motion record therefore depends on scene, snapshot and cameras only, never on the seed: a static
+ * pixel's record is bit-identical from frame to frame, and the motion of a moving surface is that of the point the pinhole sees.
+ *
+ * mcpt_render_aovs_features / mcpt_render_motion_features: a null or zeroed `features` makes the call mcpt_render_aovs_ex /
+ * mcpt_render_motion_ex, exactly (the same kernels on the same keys).  With centre 1:
+ *   aov_spp must be 0 or 1, and 0 means 1;   seed is ignored;   the key arrays of the pass are neither written nor read;
+ *   the fold of one record: coverage and valid are exactly 0 or 1, the normal is the hit's unit normal (or 0), dx, dy, prev_depth those
+ *   of the one sample.
+ * MCPT_ERR_ARG, before any device call: every case of the _ex call; a centre that is not 0 or 1; a non-zero reserved word; aov_spp > 1
+ * with centre 1.
+ * Limits: inside a circle of confusion the guide's edges are sharper than the image's (the filter then stops at an edge the blur has
+ * crossed); the halo of a moving blurred object takes the motion of the background its centre rays see, for which the colour clamp of
+ * mcpt_history_opts is the remedy; pixels that see the sky have no depth to validate and still restart every frame. */
+typedef struct {
+    int32_t centre;      /* 0 | 1: features from the centre ray of each pixel */
+    int32_t reserved[7]; /* must be 0 */
+} mcpt_feature_opts;     /* 32 bytes */
+int mcpt_render_aovs_features(mcpt_scene *scene, const mcpt_camera *camera, uint32_t seed, int32_t aov_spp, int32_t specular_depth,
+                              const mcpt_feature_opts *features /* nullable */, float *aov_host);
+int mcpt_render_motion_features(mcpt_scene *scene, const mcpt_camera *camera, const mcpt_camera *prev_camera, uint32_t seed, int32_t aov_spp,
+                                int32_t specular_depth, const mcpt_feature_opts *features /* nullable */, float *motion_host);
+
+/* A sequence on centre features.  A null or zeroed `features`: mcpt_sequence_create_moments, exactly.  With centre 1 steps 3 and 4 of
+ * mcpt_sequence_frame are mcpt_render_aovs_features and mcpt_render_motion_features with these options and aov_spp 1, and so are the
+ * extra first-hit pass of specular_depth > 0 and the feature steps a and b of an adaptive sequence; nothing else changes, and every
+ * output still equals what the separate calls give, bit for bit.  The chain maps of specular motion shrink to 96 bytes per pixel of a
+ * chunk.  It combines with history rejection, specular motion, an adaptive rule, weighting and moments as those combine without it.
+ * MCPT_ERR_ARG, before any device call: as mcpt_sequence_create_moments; a centre that is not 0 or 1; a non-zero reserved word;
+ * centre 1 with opts.denoise.aov_spp > 1. */
+int mcpt_sequence_create_features(mcpt_scene *scene, int32_t width, int32_t height, const mcpt_sequence_opts *opts,
+                                  const mcpt_history_opts *history_opts, const mcpt_sequence_adaptive *adaptive,
+                                  const mcpt_sequence_motion *motion, const mcpt_sequence_weighted *weighted, const mcpt_moments_opts *moments,
+                                  const mcpt_feature_opts *features, mcpt_sequence **out);
+
 /* Replaces Scene::intersect (Scene.hpp:128, Scene.cpp:19-21) for a list of rays (host pointers; n*3 floats each).
  * out_t: hit distance as the reference's double Intersection::distance (DBL_MAX on a miss);
  * out_prim: global primitive id (triangle index, or n_triangles + object index for a sphere; -1 on a miss). */
@@ -833,6 +881,10 @@ int mcpt_cast_rays(mcpt_scene *scene, const mcpt_params *params, int64_t n, cons
 /* Camera ray generation of Renderer.cpp:44-76 for (pixel m, sample k) pairs (host pointers); origins/dirs: n*3 floats. */
 int mcpt_camera_rays(mcpt_scene *scene, const mcpt_camera *camera, uint32_t seed, int64_t n, const uint32_t *pixel,
                      const uint32_t *sample, float *origins, float *dirs);
+
+/* The centre rays (mcpt_feature_opts above) of the n pixels pixel[0 .. n-1] (host pointers); origins/dirs: n*3 floats.  No seed and no
+ * sample: the ray is a function of the camera.  MCPT_ERR_ARG for a null pointer with n > 0, n < 0 or above 2^31 - 1, width or height <= 0. */
+int mcpt_centre_rays(mcpt_scene *scene, const mcpt_camera *camera, int64_t n, const uint32_t *pixel, float *origins, float *dirs);
 
 /* Tone map of Renderer.cpp:95-103 on the GPU: rgba[4i + c] = (unsigned char) clamp(0, 255, 255 * pow(fb[3i + c], 0.45f)), alpha 255,
  * NaN -> 255 as the reference's std::min/std::max clamp gives.  std::pow is the library's own plain-IEEE pow (csrc/mcpt_fmath.h), within

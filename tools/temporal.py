@@ -33,7 +33,10 @@ filter is guided by the render's own variance: the pair to compare at equal samp
   --specular-depth N   the sequence's denoise.specular_depth (the features behind up to N mirror / glass bounces); with --specular-motion the
 motion follows those chains too and the history is validated against the chain depth (mcpt_sequence_create_motion).  --move with --scene
 chess moves the nearest rough pawn by 6 units (about 3.5 px at 1080p) along x per frame, and the MSE is also given over the pixels whose
-first hit is the floor mirror, where the pawn's reflection moves."""
+first hit is the floor mirror, where the pawn's reflection moves.
+  --centre-features   every feature pass of the sequence runs on the pixels' centre rays, one per pixel (mcpt_sequence_create_features): the
+pair to compare is the same command with and without it, e.g. --sequence --quality --spp 1 --moments [--move].  The last line of every
+--quality run gives the median stage times over the frames after the first and the share of pixels whose history reached 4 frames."""
 import argparse
 import csv
 import re
@@ -146,12 +149,13 @@ def sequence_timing(pkg, sd, W, H, frames, reject=None, loop=True):
 
 
 def sequence_quality(pkg, sd, W, H, frames, spp, adaptive, reject, move, ref_spp, specular_depth=0, specular_motion=False, weighted=False, spp_list=None,
-                     len_mask=0, moments=None, filtered=False):
+                     len_mask=0, moments=None, filtered=False, centre=False):
     """Per frame of a uniform (adaptive None) or adaptive sequence: samples, count histogram, stage times, MSE of `accumulated`.
     spp_list: the samples per pixel of frame k of a uniform sequence (the last entry repeats)."""
     hs = pkg.HipScene(sd)
     filtered = filtered or moments is not None
-    seq = hs.sequence(filter=filtered, moments=moments if moments is not None else False, aov_spp=min(4, adaptive["min_spp"] if adaptive else min(spp_list or [spp])), adaptive=adaptive,
+    aov_spp = 1 if centre else min(4, adaptive["min_spp"] if adaptive else min(spp_list or [spp]))
+    seq = hs.sequence(filter=filtered, moments=moments if moments is not None else False, aov_spp=aov_spp, adaptive=adaptive, centre_features=centre,
                       specular_depth=specular_depth, specular_motion=specular_motion, weighted=weighted, **(reject or {}))
     chess = sd.name.startswith("chess")
     step = 6.0 if chess else -32.0  # object 1: the nearest rough pawn of the chess scene, the short box of the Cornell scene
@@ -166,6 +170,7 @@ def sequence_quality(pkg, sd, W, H, frames, spp, adaptive, reject, move, ref_spp
         "guided" if adaptive["guided"] else "unguided", adaptive["min_spp"], spp, adaptive["threshold"])
     if moments is not None:
         what += ", variance from temporal moments (min_len %d, radius %d)" % (moments["min_len"] or 4, moments["radius"] or 3)
+    what += ", features from %s" % ("the centre ray of each pixel" if centre else "%d sampled camera ray%s per pixel" % (aov_spp, "s" * (aov_spp > 1)))
     print("%dx%d %s sequence, %s; reference %d spp" % (W, H, "moving" if move else "static", what, ref_spp))
 
     def tone_rmse(img):
@@ -173,7 +178,7 @@ def sequence_quality(pkg, sd, W, H, frames, spp, adaptive, reject, move, ref_spp
             d = np.clip(img.astype(np.float64), 0, 1) ** 0.45 - np.clip(truth, 0, 1) ** 0.45
         return float(np.sqrt(np.nanmean(d * d)))
 
-    truth, total = None, 0
+    truth, total, stages = None, 0, []
     for k in range(frames):
         if move:
             hs.update([(1, np.array([[1, 0, 0, step * k], [0, 1, 0, 0], [0, 0, 1, 0]], np.float32))])
@@ -204,9 +209,14 @@ def sequence_quality(pkg, sd, W, H, frames, spp, adaptive, reject, move, ref_spp
         if floor is not None:
             hist += "  MSE on the floor mirror %.6g" % float(np.nanmean(sq[floor]))
         i = r["info"]
+        stages.append(i)
         print("frame %d: %d samples (%.2f per pixel)  MSE %.6g%s  ms: render %.3f aov %.3f motion %.3f accumulate %.3f total %.2f"
               % (k, n, n / (W * H), mse, hist, i["ms_render"], i["ms_aov"], i["ms_motion"], i["ms_accumulate"], i["ms_total"]), flush=True)
     print("all frames: %d samples (%.2f per pixel and frame)" % (total, total / (W * H * frames)))
+    if frames > 1:
+        print("median over frames 1..%d, ms: " % (frames - 1) + ", ".join("%s %.3f" % (key[3:], float(np.median([s[key] for s in stages[1:]])))
+                                                                     for key in ("ms_render", "ms_aov", "ms_motion", "ms_accumulate", "ms_filter", "ms_total"))
+              + "; len >= 4 in %.1f %% of the pixels of the last frame" % (100 * float((r["len"] >= 4).mean())))
     seq.close()
     hs.close()
 
@@ -240,6 +250,7 @@ def main():
     ap.add_argument("--filtered", action="store_true", help="--quality: create the sequence with filter 1 and print the tone-curve RMSE of the denoised frame too")
     ap.add_argument("--specular-depth", type=int, default=0, help="--adaptive / --quality: denoise.specular_depth of the sequence, and the depth of --specular-motion")
     ap.add_argument("--specular-motion", action="store_true", help="--adaptive / --quality: reproject what is seen through mirrors and glass (needs --specular-depth > 0)")
+    ap.add_argument("--centre-features", action="store_true", help="--adaptive / --quality: the features of each pixel from its centre ray (mcpt_sequence_create_features)")
     a = ap.parse_args()
     if a.trace:
         return summarize_trace(a.trace, a.repeat)
@@ -249,13 +260,13 @@ def main():
     spp_list = [int(x) for x in a.spp_list.split(",")] if a.spp_list else None
     if spp_list and a.adaptive is not None:
         sys.exit("--spp-list is for a uniform sequence (--quality)")
-    if a.sequence and (a.adaptive is not None or a.quality or a.move or a.specular_depth > 0 or a.weighted or spp_list or a.moments or a.filtered):  # (all but the first two imply --quality)
+    if a.sequence and (a.adaptive is not None or a.quality or a.move or a.specular_depth > 0 or a.weighted or spp_list or a.moments or a.filtered or a.centre_features):  # (all but the first two imply --quality)
         reject = dict(normal_test=a.normal_test, color_clamp=a.color_clamp, clamp_k=a.clamp_k) if a.normal_test or a.color_clamp else None
         rule = None if a.adaptive is None else dict(min_spp=a.adaptive_min, threshold=a.adaptive, dilate=1, guided=int(a.guided))
         if a.specular_motion and a.specular_depth <= 0:
             sys.exit("--specular-motion needs --specular-depth N > 0")
         return sequence_quality(pkg, sd, W, H, a.frames, a.spp, rule, reject, a.move, a.ref_spp, a.specular_depth, a.specular_motion, a.weighted, spp_list,
-                                a.len_mask, dict(min_len=a.min_len, radius=a.radius) if a.moments else None, a.filtered)
+                                a.len_mask, dict(min_len=a.min_len, radius=a.radius) if a.moments else None, a.filtered, a.centre_features)
     if a.sequence:
         if a.frames < 6:
             sys.exit("--frames must be at least 6")
