@@ -68,6 +68,18 @@ MCPT_DN int resolve_opts(const mcpt_denoise_opts &o, Opts &out) {
     return 0;
 }
 
+// The iteration a feedback history is taken behind (mcpt_feedback_opts; null: 0, off), checked against the resolved options: 0 on success,
+// -1 for an iteration outside 0..o.iterations or a non-zero reserved word.
+MCPT_DN int resolve_feedback(const mcpt_feedback_opts *f, const Opts &o, int &k) {
+    k = 0;
+    if (!f) return 0;
+    for (int i = 0; i < 7; ++i)
+        if (f->reserved[i] != 0) return -1;
+    if (f->iteration < 0 || f->iteration > kMaxIterations || f->iteration > o.iterations) return -1;
+    k = f->iteration;
+    return 0;
+}
+
 MCPT_DN bool finite_f(float x) { return x - x == 0.0f; }  // false for +-inf and NaN
 MCPT_DN float max_f(float a, float b) { return a < b ? b : a; }
 MCPT_DN float abs_f(float a) { return a < 0.0f ? -a : a; }
@@ -281,6 +293,26 @@ MCPT_DN void remod_pixel(size_t m, const Rec &r, const float *color, const float
     out[m * 3 + 2] = r.e[2] * albedo_floor(a[2]);
 }
 
+/* The history a feedback sequence keeps of pixel m (include/mcpt.h: mcpt_denoise_feedback): r is the pixel's record after a-trous iteration
+ * k, 1 <= k <= iterations -- the buffer iteration k + 1 reads.  A usable record gives the colour remod_pixel would give there, e * A, and its
+ * variance with the scaling of prep_pixel undone, v * lum(A)^2; an unusable one passes colour and variance through with their bits.
+ * out_variance may be null (a moments sequence keeps no fed variance). */
+MCPT_DN void feedback_pixel(size_t m, const Rec &r, const float *color, const float *variance, const float *aov, float *out_color,
+                            float *out_variance) {
+    // (every load first and selects after, so that a lane has all of them in flight at once and the wave never diverges)
+    const float *a = aov + m * 8;
+    const float A0 = albedo_floor(a[0]), A1 = albedo_floor(a[1]), A2 = albedo_floor(a[2]);
+    const float c0 = color[m * 3], c1 = color[m * 3 + 1], c2 = color[m * 3 + 2];
+    const float v = out_variance ? variance[m] : 0.0f;
+    const bool ok = usable(r);
+    out_color[m * 3] = ok ? r.e[0] * A0 : c0;
+    out_color[m * 3 + 1] = ok ? r.e[1] * A1 : c1;
+    out_color[m * 3 + 2] = ok ? r.e[2] * A2 : c2;
+    if (!out_variance) return;
+    const float la = lum(A0, A1, A2);
+    out_variance[m] = ok ? r.v * (la * la) : v;
+}
+
 /* Luminance variance of the mean from the moments of n samples (s1, s2: sums of v and v*v per channel, in double):
  *   for c: m = s1[c]/n;  q = s2[c]/n - m*m;  var_c = max(q, 0) * n / (n - 1) / n;  v += (w_c * w_c) * var_c   (v from 0.0, c = 0, 1, 2)
  * rounded once to float (a NaN q stays NaN). */
@@ -325,6 +357,11 @@ void launch_dn_variance_map(uint32_t n_px, const double *moments, const int32_t 
 // The whole filter: prep -> o.iterations a-trous passes (rec0 <-> rec1, W*H records each; grad W*H) -> remodulation into out (W*H*3).
 void launch_denoise(int W, int H, const dn::Opts &o, const float *color, const float *variance, const float *aov, dn::Rec *rec0, dn::Rec *rec1,
                     float2 *grad, float *out, hipStream_t st);
+// The filter with the history a feedback sequence keeps: right after iteration k (1..o.iterations) k_dn_feedback writes dn::feedback_pixel of
+// that iteration's records into fb_color (W*H*3) and fb_variance (W*H; nullable).  It only reads the records, so iteration k + 1 follows it
+// at once.  k 0: launch_denoise, launch for launch.
+void launch_denoise_feedback(int W, int H, const dn::Opts &o, const float *color, const float *variance, const float *aov, dn::Rec *rec0,
+                             dn::Rec *rec1, float2 *grad, float *out, int k, float *fb_color, float *fb_variance, hipStream_t st);
 }  // namespace mcpt
 #endif
 #endif  // MCPT_DENOISE_H

@@ -13,6 +13,7 @@
 //   k_dn_prep       demodulation, scaled variance, depth gradient -> 32-byte records {e.rgb, v} {n.xyz, z}
 //   k_dn_atrous     one iteration (step 2^i), 16 x 16 pixel blocks, two 16-byte loads per tap, ping-pong between two record buffers
 //   k_dn_remod      out = e * A (or the colour, for a pixel that passes through)
+//   k_dn_feedback   the same of the records after iteration k, with their variance: the history of a feedback sequence (mcpt_denoise_feedback)
 //   k_dn_variance   the luminance variance of the mean from the moments of k_accumulate<true> (mcpt_render_denoised)
 //   k_dn_variance_map  the same from each pixel's own sample count (an adaptive frame: mcpt_render_adaptive_guided)
 #include <hip/hip_runtime.h>
@@ -261,6 +262,15 @@ __global__ __launch_bounds__(kB) void k_dn_remod(uint32_t n_px, const dn::Rec *_
     dn::remod_pixel(m, rec[m], color, aov, out);
 }
 
+// One pixel per lane: the record after iteration k, the pixel's colour, variance and albedo in; fed colour and variance out.
+__global__ __launch_bounds__(kB) void k_dn_feedback(uint32_t n_px, const dn::Rec *__restrict__ rec, const float *__restrict__ color,
+                                                    const float *__restrict__ variance, const float *__restrict__ aov, float *__restrict__ fb_color,
+                                                    float *__restrict__ fb_variance) {
+    const uint32_t m = blockIdx.x * kB + threadIdx.x;
+    if (m >= n_px) return;
+    dn::feedback_pixel(m, rec[m], color, variance, aov, fb_color, fb_variance);
+}
+
 }  // namespace
 
 void launch_aov_keys(uint32_t p0, uint32_t n, int32_t aov_spp, uint32_t *pixel, uint32_t *sample, hipStream_t st) {
@@ -298,12 +308,20 @@ void launch_dn_variance_map(uint32_t n_px, const double *moments, const int32_t 
 
 void launch_denoise(int W, int H, const dn::Opts &o, const float *color, const float *variance, const float *aov, dn::Rec *rec0, dn::Rec *rec1,
                     float2 *grad, float *out, hipStream_t st) {
+    launch_denoise_feedback(W, H, o, color, variance, aov, rec0, rec1, grad, out, 0, nullptr, nullptr, st);
+}
+
+void launch_denoise_feedback(int W, int H, const dn::Opts &o, const float *color, const float *variance, const float *aov, dn::Rec *rec0,
+                             dn::Rec *rec1, float2 *grad, float *out, int k, float *fb_color, float *fb_variance, hipStream_t st) {
     const dim3 grid((W + kTile - 1) / kTile, (H + kTile - 1) / kTile), blk(kTile, kTile);
+    const uint32_t n_px = (uint32_t)W * (uint32_t)H;
     hipLaunchKernelGGL(k_dn_prep, grid, blk, 0, st, W, H, color, variance, aov, rec0, grad);
     dn::Rec *buf[2] = {rec0, rec1};
-    for (int i = 0; i < o.iterations; ++i)
+    for (int i = 0; i < o.iterations; ++i) {
         hipLaunchKernelGGL(k_dn_atrous, grid, blk, 0, st, W, H, 1 << i, o, buf[i & 1], grad, buf[(i + 1) & 1]);
-    const uint32_t n_px = (uint32_t)W * (uint32_t)H;
+        if (i + 1 == k)  // (reads what iteration i + 1 reads; the next write to that buffer is iteration i + 2's, behind it on the stream)
+            hipLaunchKernelGGL(k_dn_feedback, dim3(nblocks(n_px)), dim3(kB), 0, st, n_px, buf[(i + 1) & 1], color, variance, aov, fb_color, fb_variance);
+    }
     hipLaunchKernelGGL(k_dn_remod, dim3(nblocks(n_px)), dim3(kB), 0, st, n_px, buf[o.iterations & 1], color, aov, out);
 }
 

@@ -565,6 +565,42 @@ int render_adaptive_guided(const char *name, mcpt_scene *sc, const mcpt_camera *
     return f.end(stats, res.samples, res.traced_primary, res.totals);
 }
 
+// mcpt_denoise and mcpt_denoise_feedback (`name` for the messages): the checks, the three planes staged on the device, the filter -- with the
+// feedback kernel behind iteration fopts->iteration when that is not 0 -- and the results back.
+int denoise_call(const char *name, mcpt_scene *sc, int32_t width, int32_t height, const float *color_host, const float *variance_host,
+                 const float *aov_host, const mcpt_denoise_opts *opts, const mcpt_feedback_opts *fopts, float *out_host, float *fb_color_host,
+                 float *fb_variance_host) {
+    const auto bad = [&](const char *what) { return fail(MCPT_ERR_ARG, std::string(name) + ": " + what); };
+    if (!sc || !color_host || !variance_host || !aov_host || !opts || !out_host) return bad("null argument");
+    if (!frame_ok(width, height)) return bad("width and height must be positive (and the frame not too large)");
+    dn::Opts o;
+    if (dn::resolve_opts(*opts, o) != 0) return bad("option out of range");
+    int k = 0;
+    if (dn::resolve_feedback(fopts, o, k) != 0) return bad("feedback: iteration must be 0 or 1..iterations, reserved words 0");
+    if (k > 0 && !fb_color_host) return bad("feedback: null feedback_color_host");
+    HIP_TRY(hipSetDevice(sc->device));
+    (void)hipGetLastError();
+    const size_t n_px = (size_t)width * height;
+    DevBuf<float> col, var, aov, out, fcol, fvar;
+    HIP_TRY(col.alloc(n_px * 3));
+    HIP_TRY(var.alloc(n_px));
+    HIP_TRY(aov.alloc(n_px * 8));
+    HIP_TRY(out.alloc(n_px * 3));
+    if (k > 0) HIP_TRY(fcol.alloc(n_px * 3));
+    if (k > 0 && fb_variance_host) HIP_TRY(fvar.alloc(n_px));
+    HIP_TRY(upload(col, color_host, n_px * 3));
+    HIP_TRY(upload(var, variance_host, n_px));
+    HIP_TRY(upload(aov, aov_host, n_px * 8));
+    DenoiseBufs db;
+    HIP_TRY(db.alloc(n_px));
+    launch_denoise_feedback(width, height, o, col.p, var.p, aov.p, db.rec[0].p, db.rec[1].p, db.grad.p, out.p, k, fcol.p, fvar.p, nullptr);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(download(out_host, out, n_px * 3));
+    if (k > 0) HIP_TRY(download(fb_color_host, fcol, n_px * 3));
+    if (k > 0 && fb_variance_host) HIP_TRY(download(fb_variance_host, fvar, n_px));
+    return MCPT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -663,27 +699,14 @@ int mcpt_render_aovs_features(mcpt_scene *sc, const mcpt_camera *cam, uint32_t s
 
 int mcpt_denoise(mcpt_scene *sc, int32_t width, int32_t height, const float *color_host, const float *variance_host, const float *aov_host,
                  const mcpt_denoise_opts *opts, float *out_host) {
-    if (!sc || !color_host || !variance_host || !aov_host || !opts || !out_host) return fail(MCPT_ERR_ARG, "mcpt_denoise: null argument");
-    if (!frame_ok(width, height)) return fail(MCPT_ERR_ARG, "mcpt_denoise: width and height must be positive (and the frame not too large)");
-    dn::Opts o;
-    if (dn::resolve_opts(*opts, o) != 0) return fail(MCPT_ERR_ARG, "mcpt_denoise: option out of range");
-    HIP_TRY(hipSetDevice(sc->device));
-    (void)hipGetLastError();
-    const size_t n_px = (size_t)width * height;
-    DevBuf<float> col, var, aov, out;
-    HIP_TRY(col.alloc(n_px * 3));
-    HIP_TRY(var.alloc(n_px));
-    HIP_TRY(aov.alloc(n_px * 8));
-    HIP_TRY(out.alloc(n_px * 3));
-    HIP_TRY(upload(col, color_host, n_px * 3));
-    HIP_TRY(upload(var, variance_host, n_px));
-    HIP_TRY(upload(aov, aov_host, n_px * 8));
-    DenoiseBufs db;
-    HIP_TRY(db.alloc(n_px));
-    launch_denoise(width, height, o, col.p, var.p, aov.p, db.rec[0].p, db.rec[1].p, db.grad.p, out.p, nullptr);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(download(out_host, out, n_px * 3));
-    return MCPT_OK;
+    return denoise_call("mcpt_denoise", sc, width, height, color_host, variance_host, aov_host, opts, nullptr, out_host, nullptr, nullptr);
+}
+
+int mcpt_denoise_feedback(mcpt_scene *sc, int32_t width, int32_t height, const float *color_host, const float *variance_host, const float *aov_host,
+                          const mcpt_denoise_opts *opts, const mcpt_feedback_opts *feedback, float *out_host, float *feedback_color_host,
+                          float *feedback_variance_host) {
+    return denoise_call("mcpt_denoise_feedback", sc, width, height, color_host, variance_host, aov_host, opts, feedback, out_host, feedback_color_host,
+                        feedback_variance_host);
 }
 
 int mcpt_render_denoised(mcpt_scene *sc, const mcpt_camera *cam, const mcpt_params *pp, const mcpt_denoise_opts *opts, float *fb_host,

@@ -14,7 +14,9 @@
 // frame, keeps a moments plane in each history set, accumulates with the kMoments instantiations and takes the variance of the accumulated
 // frame from k_moments_variance (csrc/mcpt_moments.hip) right after; it has no moments of the render and runs at one sample per pixel.
 // A sequence created with centre features (mcpt_sequence_create_features, centre 1) takes every feature pass of a frame from the centre
-// rays, one per pixel.
+// rays, one per pixel.  A sequence created with feedback (mcpt_sequence_create_feedback, iteration k > 0) keeps a fed colour plane (and,
+// without moments, a fed variance plane) in each history set: k_dn_feedback writes them behind iteration k of the frame's filter, and the
+// next frame's accumulation reads them where it read the set's colour and variance.
 #include <new>
 
 #include "mcpt_frame.h"
@@ -31,7 +33,8 @@ struct History {
     DevBuf<uint8_t> flags;  // what the rejection did to each pixel of the frame that wrote this set (either switch on)
     DevBuf<float> weight;   // the samples behind each pixel (a weighted sequence only)
     DevBuf<float> moments;  // the running luminance moments, 2 per pixel (a moments sequence only)
-    hipError_t alloc(size_t n_px, bool with_normal, bool with_flags, bool with_weight, bool with_moments) {
+    DevBuf<float> fed_color, fed_variance;  // iteration k of the filter of this set's frame (a feedback sequence only; no variance with moments)
+    hipError_t alloc(size_t n_px, bool with_normal, bool with_flags, bool with_weight, bool with_moments, bool with_fed) {
         hipError_t e = color.alloc(n_px * 3);
         if (e == hipSuccess) e = variance.alloc(n_px);
         if (e == hipSuccess) e = depth.alloc(n_px);
@@ -40,6 +43,8 @@ struct History {
         if (e == hipSuccess && with_flags) e = flags.alloc(n_px);
         if (e == hipSuccess && with_weight) e = weight.alloc(n_px);
         if (e == hipSuccess && with_moments) e = moments.alloc(n_px * 2);
+        if (e == hipSuccess && with_fed) e = fed_color.alloc(n_px * 3);
+        if (e == hipSuccess && with_fed && !with_moments) e = fed_variance.alloc(n_px);
         return e;
     }
     hipError_t clear(size_t n_px) {
@@ -51,10 +56,16 @@ struct History {
         if (e == hipSuccess && flags.p) e = hipMemset(flags.p, 0, n_px);
         if (e == hipSuccess && weight.p) e = hipMemset(weight.p, 0, n_px * sizeof(float));
         if (e == hipSuccess && moments.p) e = hipMemset(moments.p, 0, n_px * 2 * sizeof(float));
+        if (e == hipSuccess && fed_color.p) e = hipMemset(fed_color.p, 0, n_px * 3 * sizeof(float));
+        if (e == hipSuccess && fed_variance.p) e = hipMemset(fed_variance.p, 0, n_px * sizeof(float));
         return e;
     }
     // the set as the kernels take it: the previous frame's, or the one the frame writes
-    tp::Prev prev() const { return {color.p, variance.p, depth.p, len.p, normal.p, weight.p}; }
+    // (a feedback sequence reads the fed planes where the others read colour and variance; with moments no variance is read)
+    tp::Prev prev() const {
+        if (fed_color.p) return {fed_color.p, fed_variance.p, depth.p, len.p, normal.p, weight.p};
+        return {color.p, variance.p, depth.p, len.p, normal.p, weight.p};
+    }
     tp::Next next() { return {color.p, variance.p, depth.p, len.p, normal.p, flags.p, weight.p}; }
 };
 
@@ -197,6 +208,7 @@ struct mcpt_sequence {
     bool moments = false;        // a sequence created with mcpt_sequence_create_moments and enabled 1: the history sets have a moments plane,
     mo::Opts mopts{};            // there is no `mom`, and the variance of the accumulated frame is k_moments_variance's
     bool centre = false;         // a sequence created with mcpt_sequence_create_features and centre 1: the feature passes run on the centre rays
+    int feedback = 0;            // a sequence created with mcpt_sequence_create_feedback and iteration k > 0: k, and the sets have fed planes
 };
 
 extern "C" {
@@ -329,6 +341,13 @@ int mcpt_sequence_create_moments(mcpt_scene *sc, int32_t width, int32_t height, 
 int mcpt_sequence_create_features(mcpt_scene *sc, int32_t width, int32_t height, const mcpt_sequence_opts *opts, const mcpt_history_opts *hopts,
                                   const mcpt_sequence_adaptive *aopts, const mcpt_sequence_motion *mopts, const mcpt_sequence_weighted *wopts,
                                   const mcpt_moments_opts *momopts, const mcpt_feature_opts *fopts, mcpt_sequence **out) {
+    return mcpt_sequence_create_feedback(sc, width, height, opts, hopts, aopts, mopts, wopts, momopts, fopts, nullptr, out);
+}
+
+int mcpt_sequence_create_feedback(mcpt_scene *sc, int32_t width, int32_t height, const mcpt_sequence_opts *opts, const mcpt_history_opts *hopts,
+                                  const mcpt_sequence_adaptive *aopts, const mcpt_sequence_motion *mopts, const mcpt_sequence_weighted *wopts,
+                                  const mcpt_moments_opts *momopts, const mcpt_feature_opts *fopts, const mcpt_feedback_opts *fbopts,
+                                  mcpt_sequence **out) {
     const auto bad = [](const char *what) { return fail(MCPT_ERR_ARG, std::string("mcpt_sequence_create: ") + what); };
     if (!sc || !opts || !out) return bad("null argument");
     *out = nullptr;
@@ -374,6 +393,11 @@ int mcpt_sequence_create_features(mcpt_scene *sc, int32_t width, int32_t height,
     if (moments && weighted) return bad("moments: weighted must be 0 (a one-sample sequence has uniform counts)");
     bool centre = false;
     if (const int rc = check_features("mcpt_sequence_create", fopts, opts->denoise.aov_spp, centre)) return rc;
+    int feedback = 0;
+    if (dn::resolve_feedback(fbopts, dno, feedback) != 0) return bad("feedback: iteration must be 0 or 1..denoise.iterations, reserved words 0");
+    if (feedback > 0 && opts->filter == 0) return bad("feedback: needs filter 1 (the history is an iteration of the filter)");
+    if (feedback > 0 && aopts) return bad("feedback: does not combine with an adaptive rule");
+    if (feedback > 0 && weighted) return bad("feedback: weighted must be 0");
     // (with a specular depth of 0 the chains are the first hits: the switch changes nothing)
     const bool chain_motion = mopts && mopts->specular_motion == 1 && opts->denoise.specular_depth > 0;
     HIP_TRY(hipSetDevice(sc->device));
@@ -398,13 +422,14 @@ int mcpt_sequence_create_features(mcpt_scene *sc, int32_t width, int32_t height,
     seq->moments = moments;
     seq->mopts = mo_opts;
     seq->centre = centre;
+    seq->feedback = feedback;
     const size_t n_px = (size_t)width * height;
     hipError_t e = hipSuccess;
     const auto also = [&](auto &buf, size_t n) {
         if (e == hipSuccess) e = buf.alloc(n);
     };
     for (int k = 0; k < 2; ++k) {
-        if (e == hipSuccess) e = seq->hist[k].alloc(n_px, ho.normal_test != 0, ho.normal_test || ho.color_clamp, weighted, moments);
+        if (e == hipSuccess) e = seq->hist[k].alloc(n_px, ho.normal_test != 0, ho.normal_test || ho.color_clamp, weighted, moments, feedback > 0);
         if (e == hipSuccess) e = seq->hist[k].clear(n_px);
     }
     also(seq->fb, n_px * 3);
@@ -462,6 +487,19 @@ int mcpt_sequence_moments(mcpt_sequence *seq, float *moments_host) {
     if (!moments.p) return fail(MCPT_ERR_ARG, "mcpt_sequence_moments: the sequence was created without moments and keeps none");
     HIP_TRY(hipSetDevice(seq->device));
     HIP_TRY(download(moments_host, moments, (size_t)seq->W * seq->H * 2));
+    return MCPT_OK;
+}
+
+int mcpt_sequence_history(mcpt_sequence *seq, float *color_host, float *variance_host) {
+    if (!seq || !color_host) return fail(MCPT_ERR_ARG, "mcpt_sequence_history: null argument");
+    const History &h = seq->hist[seq->cur];  // (the set the last successful frame wrote: what the next frame reads)
+    const bool fed = seq->feedback > 0;
+    if (fed && variance_host && !h.fed_variance.p)
+        return fail(MCPT_ERR_ARG, "mcpt_sequence_history: a moments sequence with feedback keeps no fed variance");
+    const size_t n_px = (size_t)seq->W * seq->H;
+    HIP_TRY(hipSetDevice(seq->device));
+    HIP_TRY(download(color_host, fed ? h.fed_color : h.color, n_px * 3));
+    if (variance_host) HIP_TRY(download(variance_host, fed ? h.fed_variance : h.variance, n_px));
     return MCPT_OK;
 }
 
@@ -576,7 +614,10 @@ int mcpt_sequence_frame(mcpt_sequence *seq, const mcpt_camera *cam, const mcpt_p
     if (seq->moments) launch_moments_variance(W, H, seq->mopts, next.moments.p, next.len.p, next.flags.p, seq->aov.p, next.variance.p, st);
     HIP_TRY(hipEventRecord(ev.accumulate_end, st));
     // 6., 7. the filter and the tone map
-    if (filter) launch_denoise(W, H, seq->denoise, next.color.p, next.variance.p, seq->aov.p, seq->db.rec[0].p, seq->db.rec[1].p, seq->db.grad.p, seq->out.p, st);
+    // (a feedback sequence: k_dn_feedback behind iteration seq->feedback, into the new set's fed planes; 0: launch_denoise)
+    if (filter)
+        launch_denoise_feedback(W, H, seq->denoise, next.color.p, next.variance.p, seq->aov.p, seq->db.rec[0].p, seq->db.rec[1].p, seq->db.grad.p,
+                                seq->out.p, seq->feedback, next.fed_color.p, next.fed_variance.p, st);
     if (want.rgba) launch_tonemap(filter ? seq->out.p : next.color.p, (uint32_t)n_px, seq->rgba.p, st);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(ev.filter_end, st));

@@ -31,6 +31,7 @@ EXPORTS = ["mcpt_scene_create", "mcpt_scene_destroy", "mcpt_render", "mcpt_rende
            "mcpt_sequence_create_weighted", "mcpt_sequence_weight",
            "mcpt_temporal_accumulate_moments", "mcpt_moments_variance", "mcpt_sequence_create_moments", "mcpt_sequence_moments",
            "mcpt_centre_rays", "mcpt_render_aovs_features", "mcpt_render_motion_features", "mcpt_sequence_create_features",
+           "mcpt_denoise_feedback", "mcpt_sequence_create_feedback", "mcpt_sequence_history",
            "mcpt_group_create", "mcpt_group_render", "mcpt_group_size", "mcpt_group_get_info", "mcpt_group_scene", "mcpt_group_destroy", "mcpt_group_last_error",
            "mcpt_last_error", "mcpt_version"]
 
@@ -171,6 +172,11 @@ class FeatureOpts(C.Structure):
     _fields_ = [("centre", C.c_int32), ("reserved", C.c_int32 * 7)]
 
 
+class FeedbackOpts(C.Structure):
+    _fields_ = [("iteration", C.c_int32), ("reserved", C.c_int32 * 7)]
+
+
+assert C.sizeof(FeedbackOpts) == 32
 assert C.sizeof(SequenceMotion) == 32 and C.sizeof(SequenceWeighted) == 32 and C.sizeof(MomentsOpts) == 32 and C.sizeof(FeatureOpts) == 32
 assert C.sizeof(Adaptive) == 32 and C.sizeof(AdaptiveInfo) == 264 and C.sizeof(SequenceAdaptive) == 64
 assert C.sizeof(TemporalOpts) == 32 and C.sizeof(DenoiseOpts) == 32 and C.sizeof(HistoryOpts) == 32  # the sizes include/mcpt.h states
@@ -315,6 +321,15 @@ def lib(path=None):
         L.mcpt_sequence_create_features.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(SequenceOpts), C.POINTER(HistoryOpts),
                                                     C.POINTER(SequenceAdaptive), C.POINTER(SequenceMotion), C.POINTER(SequenceWeighted),
                                                     C.POINTER(MomentsOpts), C.POINTER(FeatureOpts), C.POINTER(C.c_void_p)]
+        L.mcpt_sequence_create_feedback.restype = C.c_int
+        L.mcpt_sequence_create_feedback.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(SequenceOpts), C.POINTER(HistoryOpts),
+                                                    C.POINTER(SequenceAdaptive), C.POINTER(SequenceMotion), C.POINTER(SequenceWeighted),
+                                                    C.POINTER(MomentsOpts), C.POINTER(FeatureOpts), C.POINTER(FeedbackOpts), C.POINTER(C.c_void_p)]
+        L.mcpt_sequence_history.restype = C.c_int
+        L.mcpt_sequence_history.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.mcpt_denoise_feedback.restype = C.c_int
+        L.mcpt_denoise_feedback.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(DenoiseOpts),
+                                            C.POINTER(FeedbackOpts), C.c_void_p, C.c_void_p, C.c_void_p]
         L.mcpt_centre_rays.restype = C.c_int
         L.mcpt_centre_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 3
         L.mcpt_render_aovs_features.restype = C.c_int
@@ -722,6 +737,25 @@ class HipScene:
         _check(self.L.mcpt_denoise(self.h, W, H, _ptr(color), _ptr(variance), _ptr(aov), C.byref(o), _ptr(out)), L=self.L)
         return out
 
+    def denoise_feedback(self, color, variance, aov, iteration=1, feedback=None, **opts):
+        """mcpt_denoise_feedback: denoise(), and the history a feedback sequence keeps: the filter's records after a-trous iteration
+        `iteration` (1..iterations), remodulated, with their variance.  Returns (out[H,W,3], fb_color[H,W,3], fb_variance[H,W]) float32.
+        feedback: a FeedbackOpts passed as it is, or "null" for a null pointer (tests: a null or zeroed one must give mcpt_denoise and
+        leave the feedback arrays, returned as zeros, untouched)."""
+        color = np.ascontiguousarray(color, dtype=np.float32)
+        H, W = color.shape[:2]
+        variance = np.ascontiguousarray(variance, dtype=np.float32)
+        aov = np.ascontiguousarray(aov, dtype=np.float32)
+        if variance.size != H * W or aov.size != H * W * 8 or color.size != H * W * 3:
+            raise ValueError("denoise_feedback: shapes %s %s %s do not describe one %dx%d frame" % (color.shape, variance.shape, aov.shape, W, H))
+        out, fc, fv = np.zeros((H, W, 3), dtype=np.float32), np.zeros((H, W, 3), dtype=np.float32), np.zeros((H, W), dtype=np.float32)
+        o = denoise_opts(**opts)
+        if feedback is None:
+            feedback = FeedbackOpts(iteration=int(iteration))
+        _check(self.L.mcpt_denoise_feedback(self.h, W, H, _ptr(color), _ptr(variance), _ptr(aov), C.byref(o),
+                                            None if isinstance(feedback, str) else C.byref(feedback), _ptr(out), _ptr(fc), _ptr(fv)), L=self.L)
+        return out, fc, fv
+
     def render_denoised(self, camera=None, aov_spp=0, iterations=0, sigma_l=0.0, sigma_n=0.0, sigma_z=0.0, features=True, specular_depth=0, **kw):
         """mcpt_render_denoised: the frame of render(**kw) (bit for bit), its luminance variance, the AOVs of render_aovs(aov_spp, seed, specular_depth) and
         the denoised frame.  Returns dict(fb[H,W,3], denoised[H,W,3], variance[H,W], aov[H,W,8], info dict, stats); features=False leaves
@@ -909,7 +943,8 @@ class HipScene:
         return out
 
     def sequence(self, width=None, height=None, filter=True, max_history=0, depth_tol=0.0, normal_test=False, color_clamp=False, normal_min=0.0,
-                 clamp_k=0.0, adaptive=None, specular_motion=False, weighted=False, moments=False, centre_features=False, **denoise_opts_kw):
+                 clamp_k=0.0, adaptive=None, specular_motion=False, weighted=False, moments=False, centre_features=False, feedback=0,
+                 **denoise_opts_kw):
         """mcpt_sequence_create: a HipSequence of width x height frames (default: the scene camera's) on this scene.  filter: also denoise
         the accumulated frame; max_history, depth_tol: mcpt_temporal_opts; the rest: mcpt_denoise_opts (aov_spp, iterations, sigma_l,
         sigma_n, sigma_z, specular_depth).  normal_test / color_clamp (normal_min, clamp_k): history rejection, mcpt_history_opts; with
@@ -924,10 +959,13 @@ class HipScene:
         in the history, and frames may have `spp` 1 (mcpt_sequence_create_moments); HipSequence.moments() gives the last frame's moments.
         centre_features: every feature pass of a frame (AOVs, motion) runs on the pixels' centre rays, one per pixel, so that a static
         pixel's features are the same bits in every frame whatever the seed and the lens (mcpt_sequence_create_features; aov_spp 0 or 1).
+        feedback: k > 0 feeds the filter's a-trous iteration k back into the history the next frame blends with, as SVGF does
+        (mcpt_sequence_create_feedback; needs filter, no adaptive rule, no weighting); HipSequence.history() gives that history.
         The sequence owns the scene's snapshot while it lives; close it before the scene."""
         return HipSequence(self, width, height, filter, max_history, depth_tol, normal_test=normal_test, color_clamp=color_clamp,
                            normal_min=normal_min, clamp_k=clamp_k, adaptive=adaptive, specular_motion=specular_motion, weighted=weighted,
-                           moments=moments, features=FeatureOpts(centre=1) if centre_features else None, **denoise_opts_kw)
+                           moments=moments, features=FeatureOpts(centre=1) if centre_features else None,
+                           feedback=FeedbackOpts(iteration=int(feedback)) if feedback else None, **denoise_opts_kw)
 
     def render_device(self, fb_ptr, stream_ptr=0, camera=None, **kw):
         """Same, into a device framebuffer (W*H*3 floats at fb_ptr) on the given hipStream_t handle."""
@@ -1041,7 +1079,7 @@ class HipSequence:
 
     def __init__(self, scene, width=None, height=None, filter=True, max_history=0, depth_tol=0.0, normal_test=False, color_clamp=False,
                  normal_min=0.0, clamp_k=0.0, history=None, adaptive=None, create_adaptive=False, specular_motion=False, motion=None,
-                 weighted=None, moments=None, features=None, **denoise_opts_kw):
+                 weighted=None, moments=None, features=None, feedback=None, **denoise_opts_kw):
         """history: a HistoryOpts passed to mcpt_sequence_create_ex as it is (tests: a zeroed one must give mcpt_sequence_create's sequence).
         adaptive: a dict of sequence_adaptive's keywords or a SequenceAdaptive; create_adaptive: go through mcpt_sequence_create_adaptive
         even without one (tests: a null rule must give mcpt_sequence_create_ex's sequence).  specular_motion: mcpt_sequence_create_motion
@@ -1051,7 +1089,9 @@ class HipSequence:
         mcpt_sequence_create_motion's sequence).  moments: True or a dict of moments_opts' keywords for mcpt_sequence_create_moments with
         the switch on; a MomentsOpts passed to it as it is, or "null" for a null pointer (tests: a null or zeroed one must give
         mcpt_sequence_create_weighted's sequence).  features: a FeatureOpts passed to mcpt_sequence_create_features as it is, or "null" for a
-        null pointer (tests: a null or zeroed one must give mcpt_sequence_create_moments' sequence)."""
+        null pointer (tests: a null or zeroed one must give mcpt_sequence_create_moments' sequence).  feedback: a FeedbackOpts passed to
+        mcpt_sequence_create_feedback as it is, or "null" for a null pointer (tests: a null or zeroed one must give
+        mcpt_sequence_create_features' sequence)."""
         self.scene = scene  # (keeps the scene alive as long as the sequence)
         self.L = scene.L
         self.h = None
@@ -1072,7 +1112,16 @@ class HipSequence:
             moments = moments_opts()
         elif isinstance(moments, dict):
             moments = moments_opts(**moments)
-        if features is not None:
+        if feedback is not None:
+            w = None if weighted is None or weighted is False or isinstance(weighted, str) else weighted
+            m = None if moments is None or moments is False or isinstance(moments, str) else moments
+            _check(self.L.mcpt_sequence_create_feedback(scene.h, self.W, self.H, C.byref(o), None if history is None else C.byref(history),
+                                                        None if adaptive is None else C.byref(adaptive),
+                                                        None if motion is None or isinstance(motion, str) else C.byref(motion),
+                                                        None if w is None else C.byref(w), None if m is None else C.byref(m),
+                                                        None if features is None or isinstance(features, str) else C.byref(features),
+                                                        None if isinstance(feedback, str) else C.byref(feedback), C.byref(h)), L=self.L)
+        elif features is not None:
             w = None if weighted is None or weighted is False or isinstance(weighted, str) else weighted
             m = None if moments is None or moments is False or isinstance(moments, str) else moments
             _check(self.L.mcpt_sequence_create_features(scene.h, self.W, self.H, C.byref(o), None if history is None else C.byref(history),
@@ -1142,6 +1191,15 @@ class HipSequence:
         out = np.zeros((self.H, self.W, 2), dtype=np.float32)
         _check(self.L.mcpt_sequence_moments(self.h, _ptr(out)), L=self.L)
         return out
+
+    def history(self, variance=True):
+        """mcpt_sequence_history: (color[H,W,3], variance[H,W]) float32, the history the next frame will blend with: the fed planes of a
+        feedback sequence, otherwise the accumulated colour and variance of the last frame (0 before the first).  variance=False passes a
+        null variance pointer and returns (color, None); a moments sequence with feedback keeps no fed variance and raises for True."""
+        color = np.zeros((self.H, self.W, 3), dtype=np.float32)
+        var = np.zeros((self.H, self.W), dtype=np.float32) if variance else None
+        _check(self.L.mcpt_sequence_history(self.h, _ptr(color), None if var is None else _ptr(var)), L=self.L)
+        return color, var
 
     def counts(self):
         """mcpt_sequence_counts: dict(spp[H,W] int32, err[H,W], guide[H,W] float32 (0 without guided; the history weights of a weighted

@@ -615,7 +615,8 @@ int mcpt_temporal_history_weight(mcpt_scene *scene, int32_t width, int32_t heigh
  *      previous history set into the other, which also receives this frame's first-hit depth.  On the first frame and after a reset
  *      prev_len is 0 everywhere, so every pixel starts;
  *   6. opts.filter 1: mcpt_denoise(accumulated, the accumulated variance, the AOVs; opts.denoise).  The filter gets the variance of the
- *      image it filters.  The history stays unfiltered: the filter is an output, not a feedback;
+ *      image it filters.  The history stays unfiltered: the filter is an output, not a feedback -- unless the sequence was created
+ *      with mcpt_sequence_create_feedback (below), which feeds the filter's iteration k back into the history;
  *   7. the tone map (mcpt_tonemap) if rgba was asked for; then the downloads;
  *   8. mcpt_scene_snapshot.
  * So every output equals what the separate calls give on the same inputs, bit for bit.
@@ -866,6 +867,50 @@ int mcpt_sequence_create_features(mcpt_scene *scene, int32_t width, int32_t heig
                                   const mcpt_history_opts *history_opts, const mcpt_sequence_adaptive *adaptive,
                                   const mcpt_sequence_motion *motion, const mcpt_sequence_weighted *weighted, const mcpt_moments_opts *moments,
                                   const mcpt_feature_opts *features, mcpt_sequence **out);
+
+/* ---- Filtered history (the feedback of SVGF, Schied et al. 2017).  Above, every frame's filter starts again from the raw running mean.
+ * With feedback the records after a-trous iteration k become the colour history of the next frame, so that the spatial and the temporal
+ * averaging compound.  Per pixel m, with r the record after iteration k (1 <= k <= the resolved iterations: the records iteration k + 1
+ * reads), A_c = max(albedo_c, 1e-3) and la = lum(A), in float, without contraction (csrc/mcpt_denoise.h: dn::feedback_pixel):
+ *   r usable (r.v >= 0):   feedback_color[3m + c] = r.e[c] * A_c   (the expression of step 4 of the filter);
+ *                          feedback_variance[m]   = r.v * (la * la)  (the scaling of step 1 undone);
+ *   otherwise:             colour and variance of the pixel pass through with their bits.
+ *
+ * mcpt_denoise_feedback: a null or zeroed `feedback` makes the call mcpt_denoise, exactly, and leaves the two feedback arrays untouched.
+ * Otherwise out_host is mcpt_denoise's output bit for bit (the same kernels in the same order, one more behind iteration k, which only reads)
+ * and feedback_color_host (W*H*3) and feedback_variance_host (W*H; nullable) hold the rule above at iteration `iteration`.
+ * MCPT_ERR_ARG, before any device call: every case of mcpt_denoise; an iteration outside 0..8 or above the resolved iterations; a non-zero
+ * reserved word; iteration > 0 with a null feedback_color_host. */
+typedef struct { int32_t iteration; int32_t reserved[7]; } mcpt_feedback_opts;   /* 32 bytes; iteration 0 = off, else 1..8 */
+int mcpt_denoise_feedback(mcpt_scene *scene, int32_t width, int32_t height, const float *color_host, const float *variance_host,
+                          const float *aov_host, const mcpt_denoise_opts *opts, const mcpt_feedback_opts *feedback /* nullable */,
+                          float *out_host, float *feedback_color_host, float *feedback_variance_host /* nullable */);
+
+/* A sequence with a filtered history.  A null or zeroed `feedback`: mcpt_sequence_create_features, exactly (the same allocations, the same
+ * frames).  With iteration k > 0 each history set gains a fed colour plane (12 bytes per pixel) and, unless the sequence keeps moments, a fed
+ * variance plane (4): up to 32 bytes per pixel more, allocated at creation.  In mcpt_sequence_frame
+ *   step 5 reads the previous set's fed colour as prev_color and its fed variance as prev_variance; depth, len, normals, flags and moments
+ *      are read as before (the moments of a moments sequence stay those of the raw luminance);
+ *   step 6 is mcpt_denoise_feedback(accumulated, the accumulated variance, the AOVs; opts.denoise; k), whose feedback arrays are the new
+ *      set's fed planes.
+ * outputs.accumulated stays the unfiltered blend of step 5 -- now of the new frame with a filtered history -- and outputs.variance and
+ * outputs.denoised stay as defined.  Every output still equals the composition of the separate calls, bit for bit:
+ * mcpt_temporal_accumulate_ex (or _moments, then mcpt_moments_variance) with the previous frame's feedback colour and variance as prev_color
+ * and prev_variance, then mcpt_denoise_feedback.  The fed planes live in the alternating history sets, so a failed or refused frame leaves
+ * them as they were; after mcpt_sequence_reset prev_len is 0 and they are not read.
+ * mcpt_sequence_history copies the history the next frame will read: the fed planes of a feedback sequence, otherwise the colour and the
+ * variance of the last successful frame's set; color_host W*H*3, variance_host W*H (nullable); all 0 before the first frame.
+ * MCPT_ERR_ARG, before any device call: as mcpt_sequence_create_features; an iteration outside 0..8 or a non-zero reserved word; k > 0
+ * with opts.filter 0, with k above the resolved iterations, with an adaptive rule or with weighted 1; mcpt_sequence_history for a null
+ * sequence or colour pointer, and for a non-null variance_host on a moments sequence with feedback (it keeps no fed variance).
+ * It combines with history rejection, specular motion, moments and centre features.
+ * Limits: no adaptive rule and no weighting; mcpt_group_* has no sequence; the variance of a moments sequence describes the unfiltered
+ * mean, so with feedback the filter over-smooths rather than under-smooths (as in SVGF); pixels that see the sky still restart every frame. */
+int mcpt_sequence_create_feedback(mcpt_scene *scene, int32_t width, int32_t height, const mcpt_sequence_opts *opts,
+                                  const mcpt_history_opts *history_opts, const mcpt_sequence_adaptive *adaptive,
+                                  const mcpt_sequence_motion *motion, const mcpt_sequence_weighted *weighted, const mcpt_moments_opts *moments,
+                                  const mcpt_feature_opts *features, const mcpt_feedback_opts *feedback, mcpt_sequence **out);
+int mcpt_sequence_history(mcpt_sequence *sequence, float *color_host, float *variance_host /* nullable */);
 
 /* Replaces Scene::intersect (Scene.hpp:128, Scene.cpp:19-21) for a list of rays (host pointers; n*3 floats each).
  * out_t: hit distance as the reference's double Intersection::distance (DBL_MAX on a miss);

@@ -36,7 +36,11 @@ chess moves the nearest rough pawn by 6 units (about 3.5 px at 1080p) along x pe
 first hit is the floor mirror, where the pawn's reflection moves.
   --centre-features   every feature pass of the sequence runs on the pixels' centre rays, one per pixel (mcpt_sequence_create_features): the
 pair to compare is the same command with and without it, e.g. --sequence --quality --spp 1 --moments [--move].  The last line of every
---quality run gives the median stage times over the frames after the first and the share of pixels whose history reached 4 frames."""
+--quality run gives the median stage times over the frames after the first and the share of pixels whose history reached 4 frames.
+  --feedback K   the filter's a-trous iteration K becomes the colour history of the next frame (mcpt_sequence_create_feedback; a filtered
+uniform sequence: --moments or --filtered): the pair to compare is the same command with and without it.  Every filtered --quality run of at
+least four frames also prints the flicker: the RMS of the frame-to-frame differences of the tone-mapped denoised output over its last four
+frames (of a moving scene that includes the motion itself)."""
 import argparse
 import csv
 import re
@@ -149,13 +153,13 @@ def sequence_timing(pkg, sd, W, H, frames, reject=None, loop=True):
 
 
 def sequence_quality(pkg, sd, W, H, frames, spp, adaptive, reject, move, ref_spp, specular_depth=0, specular_motion=False, weighted=False, spp_list=None,
-                     len_mask=0, moments=None, filtered=False, centre=False):
+                     len_mask=0, moments=None, filtered=False, centre=False, feedback=0):
     """Per frame of a uniform (adaptive None) or adaptive sequence: samples, count histogram, stage times, MSE of `accumulated`.
     spp_list: the samples per pixel of frame k of a uniform sequence (the last entry repeats)."""
     hs = pkg.HipScene(sd)
     filtered = filtered or moments is not None
     aov_spp = 1 if centre else min(4, adaptive["min_spp"] if adaptive else min(spp_list or [spp]))
-    seq = hs.sequence(filter=filtered, moments=moments if moments is not None else False, aov_spp=aov_spp, adaptive=adaptive, centre_features=centre,
+    seq = hs.sequence(filter=filtered, moments=moments if moments is not None else False, aov_spp=aov_spp, adaptive=adaptive, centre_features=centre, feedback=feedback,
                       specular_depth=specular_depth, specular_motion=specular_motion, weighted=weighted, **(reject or {}))
     chess = sd.name.startswith("chess")
     step = 6.0 if chess else -32.0  # object 1: the nearest rough pawn of the chess scene, the short box of the Cornell scene
@@ -171,6 +175,8 @@ def sequence_quality(pkg, sd, W, H, frames, spp, adaptive, reject, move, ref_spp
     if moments is not None:
         what += ", variance from temporal moments (min_len %d, radius %d)" % (moments["min_len"] or 4, moments["radius"] or 3)
     what += ", features from %s" % ("the centre ray of each pixel" if centre else "%d sampled camera ray%s per pixel" % (aov_spp, "s" * (aov_spp > 1)))
+    if feedback:
+        what += ", iteration %d of the filter fed back into the history" % feedback
     print("%dx%d %s sequence, %s; reference %d spp" % (W, H, "moving" if move else "static", what, ref_spp))
 
     def tone_rmse(img):
@@ -178,7 +184,7 @@ def sequence_quality(pkg, sd, W, H, frames, spp, adaptive, reject, move, ref_spp
             d = np.clip(img.astype(np.float64), 0, 1) ** 0.45 - np.clip(truth, 0, 1) ** 0.45
         return float(np.sqrt(np.nanmean(d * d)))
 
-    truth, total, stages = None, 0, []
+    truth, total, stages, toned = None, 0, [], []
     for k in range(frames):
         if move:
             hs.update([(1, np.array([[1, 0, 0, step * k], [0, 1, 0, 0], [0, 0, 1, 0]], np.float32))])
@@ -203,6 +209,7 @@ def sequence_quality(pkg, sd, W, H, frames, spp, adaptive, reject, move, ref_spp
             keep = r["len"] == len_mask
             hist += "  MSE where len == %d (%.1f %% of the pixels) %.6g" % (len_mask, 100 * keep.mean(), float(np.nanmean(sq[keep])) if keep.any() else float("nan"))
         if filtered:
+            toned = (toned + [np.clip(r["denoised"].astype(np.float64), 0, 1) ** 0.45])[-4:]
             hist += "  tone-curve RMSE accumulated %.5f denoised %.5f" % (tone_rmse(r["accumulated"]), tone_rmse(r["denoised"]))
         if moments is not None:
             hist += "  temporal variance in %.1f %% of the pixels" % (100 * float((r["len"] >= (moments["min_len"] or 4)).mean()))
@@ -217,6 +224,9 @@ def sequence_quality(pkg, sd, W, H, frames, spp, adaptive, reject, move, ref_spp
         print("median over frames 1..%d, ms: " % (frames - 1) + ", ".join("%s %.3f" % (key[3:], float(np.median([s[key] for s in stages[1:]])))
                                                                      for key in ("ms_render", "ms_aov", "ms_motion", "ms_accumulate", "ms_filter", "ms_total"))
               + "; len >= 4 in %.1f %% of the pixels of the last frame" % (100 * float((r["len"] >= 4).mean())))
+    if len(toned) == 4:
+        d = np.stack([toned[i + 1] - toned[i] for i in range(3)])
+        print("flicker: frame-to-frame RMS difference of the tone-mapped denoised output over the last four frames %.5f" % float(np.sqrt(np.nanmean(d * d))))
     seq.close()
     hs.close()
 
@@ -251,6 +261,7 @@ def main():
     ap.add_argument("--specular-depth", type=int, default=0, help="--adaptive / --quality: denoise.specular_depth of the sequence, and the depth of --specular-motion")
     ap.add_argument("--specular-motion", action="store_true", help="--adaptive / --quality: reproject what is seen through mirrors and glass (needs --specular-depth > 0)")
     ap.add_argument("--centre-features", action="store_true", help="--adaptive / --quality: the features of each pixel from its centre ray (mcpt_sequence_create_features)")
+    ap.add_argument("--feedback", type=int, default=0, help="--quality with --moments or --filtered: feed this a-trous iteration back into the history (mcpt_sequence_create_feedback)")
     a = ap.parse_args()
     if a.trace:
         return summarize_trace(a.trace, a.repeat)
@@ -260,13 +271,13 @@ def main():
     spp_list = [int(x) for x in a.spp_list.split(",")] if a.spp_list else None
     if spp_list and a.adaptive is not None:
         sys.exit("--spp-list is for a uniform sequence (--quality)")
-    if a.sequence and (a.adaptive is not None or a.quality or a.move or a.specular_depth > 0 or a.weighted or spp_list or a.moments or a.filtered or a.centre_features):  # (all but the first two imply --quality)
+    if a.sequence and (a.adaptive is not None or a.quality or a.move or a.specular_depth > 0 or a.weighted or spp_list or a.moments or a.filtered or a.centre_features or a.feedback):  # (all but the first two imply --quality)
         reject = dict(normal_test=a.normal_test, color_clamp=a.color_clamp, clamp_k=a.clamp_k) if a.normal_test or a.color_clamp else None
         rule = None if a.adaptive is None else dict(min_spp=a.adaptive_min, threshold=a.adaptive, dilate=1, guided=int(a.guided))
         if a.specular_motion and a.specular_depth <= 0:
             sys.exit("--specular-motion needs --specular-depth N > 0")
         return sequence_quality(pkg, sd, W, H, a.frames, a.spp, rule, reject, a.move, a.ref_spp, a.specular_depth, a.specular_motion, a.weighted, spp_list,
-                                a.len_mask, dict(min_len=a.min_len, radius=a.radius) if a.moments else None, a.filtered, a.centre_features)
+                                a.len_mask, dict(min_len=a.min_len, radius=a.radius) if a.moments else None, a.filtered, a.centre_features, a.feedback)
     if a.sequence:
         if a.frames < 6:
             sys.exit("--frames must be at least 6")
