@@ -46,6 +46,8 @@ struct FrameCall {
     int pixels(int32_t spp, float spp_total, float *fb_dev, hipStream_t st) { return prepare_pixels(sc, cc, p, spp, spp_total, fb_dev, st, ps); }
     int end(mcpt_stats *stats, uint64_t samples, uint64_t traced_primary, const Totals &rt) const {
         if (stats) fill_stats(stats, samples, traced_primary, p.n_dir_sample, rt, t0);
+        sc->last_cont_traced = rt.cont_traced;  // (mcpt_scene_ray_counts)
+        sc->last_cont_shared = rt.cont_shared;
         if (rt.overflow) return fail(MCPT_ERR_OVERFLOW, "some paths outran the clamp stack (raise params.max_depth)");
         return MCPT_OK;
     }

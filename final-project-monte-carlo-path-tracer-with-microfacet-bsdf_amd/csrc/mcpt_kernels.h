@@ -43,8 +43,9 @@ struct Counters {
     HotCounter pushes;      // recursion levels entered (castRay depth+1 calls); folded into tot_pushes by k_bookkeep
     HotCounter overflow;    // cumulative: paths cut by max_depth
     HotCounter ended;       // vertices shaded and finished in the same k_shade call (no record); folded into tot_ended
+    HotCounter shared;      // records that continue on a sibling's ray (k_shade stored no ray of their own); folded into tot_shared
     // cumulative totals kept on the device by k_bookkeep (the host does not see every iteration's counts)
-    unsigned long long tot_shaded, tot_direct, tot_shadow, tot_cont, tot_iterations, tot_pushes, tot_ended;
+    unsigned long long tot_shaded, tot_direct, tot_shadow, tot_cont, tot_iterations, tot_pushes, tot_ended, tot_shared;
     uint32_t last_shadow;  // length of the shadow queue k_bookkeep cleared last (the host sizes the next k_trace_shadow grid from it)
     // ---- everything above is what the host reads back every iteration (kCountersHeadBytes); the sharded counters stay on the device
     HotCounter n_shadow[2][kShadowShards];    // per shard: shadow rays whose light sample was found (indexed like the list the rays belong to)
@@ -96,6 +97,7 @@ struct RenderConst {
     const int32_t *key_channel;
     int32_t max_depth;
     int32_t track_live;  // maintain Counters::live (only needed when several passes are pipelined)
+    int32_t share_rays;  // channel paths that leave a smooth-conductor vertex together continue on one ray (k_shade; MCPT_SHARE_RAYS=0: off)
     uint32_t pool;  // clamp-stack row length (slots)
     float4 *stack;  // [level][slot] = {clamp(0,15,l_dir), eval, |wo.n| or -1, pdf}
     float *result[2];  // per pass parity, per pid: castRay(ray, 0, channel)

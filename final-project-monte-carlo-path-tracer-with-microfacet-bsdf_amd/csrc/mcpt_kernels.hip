@@ -34,7 +34,7 @@ constexpr int kShadeBlock = MCPT_SHADE_BLOCK;  // k_shade: larger workgroups = f
 // workgroup (lane k of wave 0 adds the block total of request k), instead of one returning atomic per
 // wave and counter: the hot counters are the only cross-workgroup contention points of the pipeline.
 // Must be called by every thread of the block (it contains barriers).
-constexpr int kMaxAlloc = 9;
+constexpr int kMaxAlloc = 10;
 constexpr int kMaxWaves = 16;
 struct BlockAllocShared {
     uint32_t cnt[kMaxWaves][kMaxAlloc];  // in: requests of wave w; out (after the first barrier): requests of the waves before w
@@ -660,8 +660,9 @@ __global__ __launch_bounds__(kBlock) void k_init_free(uint32_t *free_slots, Coun
         c->pushes.v = 0;
         c->overflow.v = 0;
         c->ended.v = 0;
+        c->shared.v = 0;
         c->last_shadow = 0;
-        c->tot_shaded = c->tot_direct = c->tot_shadow = c->tot_cont = c->tot_iterations = c->tot_pushes = c->tot_ended = 0;
+        c->tot_shaded = c->tot_direct = c->tot_shadow = c->tot_cont = c->tot_iterations = c->tot_pushes = c->tot_ended = c->tot_shared = 0;
     }
 }
 
@@ -1065,18 +1066,33 @@ __global__ __launch_bounds__(kShadeBlock, 8) void k_shade(DevScene S, RenderCons
     // record for the next iteration.
     const bool ends_here = do_shade && !has_cont && !need_direct;
     const bool done = finished || ends_here;
-    const bool want[9] = {done, do_shade && !ends_here, has_cont, need_direct, pushed, overflow, done && C.track_live && pq == 0,
-                          done && C.track_live && pq == 1, ends_here};
-    const uint32_t mult[9] = {1u, 1u, 1u, 1u, 1u, 1u, 1u, 1u, 1u};
-    uint32_t *const ctr[9] = {&C.counters->free_tail.v, &C.counters->n_paths[next_idx].v, &C.counters->n_rays[next_idx].v,
-                              &C.counters->n_direct[next_idx].v, &C.counters->pushes.v, &C.counters->overflow.v,
-                              &C.counters->live[0].v, &C.counters->live[1].v, &C.counters->ended.v};
-    const bool sub[9] = {false, false, false, false, false, false, true, true, false};
-    uint32_t prefix[9], idx[9];
+    // Shared continuation rays.  The channel paths of a sample read one incoming ray (the same ray_idx): the same p, n, wo and material.
+    // At a smooth conductor the next ray does not depend on the channel either: mat_sample returns n, mat_fresnel exactly 1, u0[3] < 1
+    // always reflects, so p2 and wi are functions of (p, n, wo) alone; only the roulette draw u0[2] differs.  The surviving siblings
+    // therefore continue on ONE ray: the lowest such lane (the leader) requests and stores it, the others (followers, `lead` lanes above
+    // it) point their records at it.  Siblings sit in adjacent lanes (fresh triples are lanes n_rec + 3k + c, compaction keeps the lane
+    // order of a workgroup) and a ray has at most three records, so lanes -1 and -2 are all there is to look at; a group cut by a wave
+    // boundary does not share.  Next iteration the records carry the same ray_idx again and the rule applies as long as they keep
+    // meeting smooth conductors.  (Explicit paths, mcpt_cast_rays, have one ray per record: nothing ever matches.)
+    uint32_t lead = 0;
+    {
+        const bool cand = has_cont && C.share_rays && m.type == MCPT_SMOOTH_CONDUCTOR;
+        const uint32_t mine = cand ? ray_idx : 0xffffffffu;  // (0xffffffff is never a ray index: ray_cap entries, 32-bit)
+        const uint32_t up1 = (uint32_t)__shfl_up((int)mine, 1), up2 = (uint32_t)__shfl_up((int)mine, 2);  // (lanes 0 / 0, 1 get their own value back)
+        if (cand) lead = (lane_id() >= 2u && up2 == mine) ? 2u : ((lane_id() >= 1u && up1 == mine) ? 1u : 0u);
+    }
+    const bool want[10] = {done, do_shade && !ends_here, has_cont && lead == 0u, need_direct, pushed, overflow, done && C.track_live && pq == 0,
+                           done && C.track_live && pq == 1, ends_here, lead != 0u};
+    const uint32_t mult[10] = {1u, 1u, 1u, 1u, 1u, 1u, 1u, 1u, 1u, 1u};
+    uint32_t *const ctr[10] = {&C.counters->free_tail.v, &C.counters->n_paths[next_idx].v, &C.counters->n_rays[next_idx].v,
+                               &C.counters->n_direct[next_idx].v, &C.counters->pushes.v, &C.counters->overflow.v,
+                               &C.counters->live[0].v, &C.counters->live[1].v, &C.counters->ended.v, &C.counters->shared.v};
+    const bool sub[10] = {false, false, false, false, false, false, true, true, false, false};
+    uint32_t prefix[10], idx[10];
 #ifdef MCPT_TRAVERSAL_STATS
     const long long tb0 = clock64();
 #endif
-    block_alloc_begin<9>(sh, want, mult, ctr, sub, prefix);
+    block_alloc_begin<10>(sh, want, mult, ctr, sub, prefix);
 #ifdef MCPT_TRAVERSAL_STATS
     const long long tb1 = clock64();
 #endif
@@ -1104,7 +1120,9 @@ __global__ __launch_bounds__(kShadeBlock, 8) void k_shade(DevScene S, RenderCons
 #ifdef MCPT_TRAVERSAL_STATS
     const long long tb2 = clock64();
 #endif
-    block_alloc_end<9>(sh, mult, prefix, idx);
+    block_alloc_end<10>(sh, mult, prefix, idx);
+    // a follower takes its leader's ray entry (read while every lane is still here: the returns are below)
+    const uint32_t rj = (uint32_t)__shfl((int)idx[2], (int)(lane_id() - lead));
 #ifdef MCPT_TRAVERSAL_STATS
     if (S.dbg && lane_id() == 0) {  // cycles of this wave: in block_alloc_begin (ballots + first barrier), in block_alloc_end (second barrier), since its start
         const long long tb3 = clock64();
@@ -1130,7 +1148,7 @@ __global__ __launch_bounds__(kShadeBlock, 8) void k_shade(DevScene S, RenderCons
         (pq ? C.result[1] : C.result[0])[pid] = unwind(C, slot, depth, l_dir);
         return;
     }
-    const uint32_t j = idx[1], rj = idx[2], dj = idx[3];
+    const uint32_t j = idx[1], dj = idx[3];
 
     if (need_direct) {  // work-list entry for k_direct (Scene::directLighting runs there, one lane per light sample)
         Xs.vtx0[dj] = make_float4(q.x, q.y, q.z, uv.x);
@@ -1142,8 +1160,10 @@ __global__ __launch_bounds__(kShadeBlock, 8) void k_shade(DevScene S, RenderCons
     }
     uint32_t flags = depth | (inside ? kInside : 0u) | (need_direct ? 0u : kNoDirect) | (pq ? kPassBit : 0u);
     if (has_cont) {
-        next.ray_o[rj] = make_float4(p2.x, p2.y, p2.z, 0.f);
-        next.ray_d[rj] = make_float4(wi.x, wi.y, wi.z, 0.f);
+        if (lead == 0u) {  // (a follower's p2 and wi are its leader's, bit for bit: see `lead`)
+            next.ray_o[rj] = make_float4(p2.x, p2.y, p2.z, 0.f);
+            next.ray_d[rj] = make_float4(wi.x, wi.y, wi.z, 0.f);
+        }
     } else {
         flags |= kTerminate;
     }
@@ -1498,7 +1518,7 @@ __global__ void k_bookkeep(Counters *c, int cur_idx, int from_host, uint32_t n_n
     case 2: c->tot_cont += from_host ? n_cont : c->n_rays[nxt].v; break;
     case 3: c->tot_direct += from_host ? n_direct : c->n_direct[nxt].v; break;
     case 4: c->tot_iterations += 1; break;
-    case 8: {  // only k_shade (same stream, already finished) writes these two
+    case 8: {  // only k_shade (same stream, already finished) writes these three
         const uint32_t v = c->ended.v;
         c->ended.v = 0;
         c->tot_ended += v;
@@ -1508,6 +1528,12 @@ __global__ void k_bookkeep(Counters *c, int cur_idx, int from_host, uint32_t n_n
         const uint32_t v = c->pushes.v;
         c->pushes.v = 0;
         c->tot_pushes += v;
+        break;
+    }
+    case 11: {
+        const uint32_t v = c->shared.v;
+        c->shared.v = 0;
+        c->tot_shared += v;
         break;
     }
     case 5: c->n_paths[cur_idx].v = 0; break;

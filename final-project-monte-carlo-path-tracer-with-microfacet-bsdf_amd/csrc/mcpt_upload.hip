@@ -21,6 +21,7 @@ void Knobs::read() {
     verbose = std::getenv("MCPT_RENDER_VERBOSE") != nullptr;
     sky_cull = !off("MCPT_SKY_CULL");
     small_scene = !off("MCPT_SMALL_SCENE");
+    share_rays = !off("MCPT_SHARE_RAYS");
     const char *v;
     if ((v = std::getenv("MCPT_POOLS"))) pools = (v[0] == '2') ? 2 : 1;
     if ((v = std::getenv("MCPT_DRAIN_BATCH"))) drain_batch = std::max(1, std::atoi(v));
@@ -648,6 +649,13 @@ int mcpt_scene_dump_bvh(mcpt_scene *sc, mcpt_bvh_info *info, float *boxes, int32
         HIP_TRY(download(qn.data(), sc->geom.qnodes, qn.size()));
     }
     export_nodes(info->n_nodes, nodes.data(), qn.empty() ? nullptr : qn.data(), boxes, children, qboxes);
+    return MCPT_OK;
+}
+
+int mcpt_scene_ray_counts(const mcpt_scene *sc, uint64_t *traced, uint64_t *shared) {
+    if (!sc || !traced || !shared) return fail(MCPT_ERR_ARG, "mcpt_scene_ray_counts: null argument");
+    *traced = sc->last_cont_traced;
+    *shared = sc->last_cont_shared;
     return MCPT_OK;
 }
 

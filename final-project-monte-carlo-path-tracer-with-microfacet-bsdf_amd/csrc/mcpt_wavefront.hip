@@ -132,6 +132,7 @@ int run_wavefront(mcpt_scene *sc, PoolCtx &ctx, const RenderConst &C0, const Cam
     const int P = (int)plan.size();
     C.track_live = (acc && P > 1) ? 1 : 0;
     const Knobs &K = sc->knobs;
+    C.share_rays = K.share_rays ? 1 : 0;
     launch_init_free(w.free_slots.p, w.counters.p, pool, K.ring_start, w.free_ring - 1u, st);
     if (ctx.side[1].s) {  // fork: the side streams start after everything queued on `st` so far (counters, pixel list, framebuffer)
         HIP_TRY(hipEventRecord(ctx.book, st));
@@ -342,7 +343,10 @@ int run_wavefront(mcpt_scene *sc, PoolCtx &ctx, const RenderConst &C0, const Cam
     tot.iterations += hc.tot_iterations;
     tot.shaded += hc.tot_shaded + hc.tot_ended + hc.ended.v;
     tot.direct += hc.tot_direct;
-    tot.closest += hc.tot_cont;
+    const uint64_t shared = hc.tot_shared + hc.shared.v;
+    tot.closest += hc.tot_cont + shared;  // resolved rays: the counts do not depend on how many of them shared a ray
+    tot.cont_traced += hc.tot_cont;
+    tot.cont_shared += shared;
     tot.shadow += hc.tot_shadow;
     for (uint32_t k = 0; k < kShadowShards; ++k) tot.shadow += hc.n_shadow[0][k].v + hc.n_shadow[1][k].v + hc.n_shadow_w[0][k].v + hc.n_shadow_w[1][k].v;
     return MCPT_OK;
@@ -557,6 +561,14 @@ int render_list(mcpt_scene *sc, const CameraConst &cc, const mcpt_params &p, con
             tot[k].cnt[c] = sc->pools[k].timer.count[c];
         }
         rt += tot[k];
+    }
+    if (sc->knobs.verbose) {
+        uint64_t traced = 0, shared = 0;
+        for (int k = 0; k < n_pools; ++k) {
+            traced += tot[k].cont_traced;
+            shared += tot[k].cont_shared;
+        }
+        std::fprintf(stderr, "[mcpt render] continuation rays: %llu traced, %llu shared with a sibling's\n", (unsigned long long)traced, (unsigned long long)shared);
     }
     return MCPT_OK;
 }

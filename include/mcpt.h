@@ -980,6 +980,13 @@ typedef struct {
 } mcpt_scene_info;
 int mcpt_scene_get_info(const mcpt_scene *scene, mcpt_scene_info *info);
 
+/* The continuation rays (every closest-hit ray beyond the primary rays) of the scene's last frame-level render call or mcpt_cast_rays
+ * call: `traced` walked the tree; `shared` are records that continued on the ray of a sibling channel path instead (the channel paths
+ * of a sample leave a smooth-conductor vertex in one direction; MCPT_SHARE_RAYS=0 switches the sharing off).  traced + shared is what
+ * mcpt_stats::closest_rays counts beyond the primary rays, so that field and ref_scene_rays do not depend on the sharing; how the sum
+ * splits depends on the schedule (pool size, pass size, ranks).  Zero before the first call. */
+int mcpt_scene_ray_counts(const mcpt_scene *scene, uint64_t *traced, uint64_t *shared);
+
 /* Host-only diagnostic (no GPU needed): builds the traversal tree of `desc` exactly as mcpt_scene_create does and copies it
  * out, so that the builder (the data producer of BVHAccel::recursiveBuild, BVH.cpp:27-93) can be checked on any machine.
  * Call with boxes == NULL to get the counts, then with arrays of n_nodes entries:
