@@ -2,7 +2,8 @@
 // environment knobs, the event timer, struct mcpt_scene, and what its translation units call in each other:
 //   mcpt_wavefront.hip  the wavefront loop, workspace / pass sizing (render_list), the pixel list and sky cull set-up
 //   mcpt_upload.hip     scene create / upload / update / snapshot / destroy / info, the BVH dumps
-//   mcpt_update.hip     the kernel that moves objects in HBM (the device path of mcpt_scene_update), mcpt_transform_triangles
+//   mcpt_update.hip     the kernels that move and deform objects in HBM (the device path of mcpt_scene_update / mcpt_scene_deform),
+//                       mcpt_transform_triangles, mcpt_deform_triangles
 //   mcpt_render.hip     the frame-level entry points (render, adaptive, AOVs, denoise, motion, temporal blend); mcpt_frame.h has what
 //                       it shares with
 //   mcpt_sequence.hip   mcpt_temporal_accumulate and mcpt_sequence_*: a frame loop whose history and buffers stay on the device
@@ -338,8 +339,9 @@ struct SceneMeta {
     float light_area_sum = 0.f, light_center[3] = {0, 0, 0}, light_radius = 0.f;
 };
 
-// The creation-time description of a scene and the transforms its objects currently have (mcpt_scene_update: transforms are absolute,
-// so every update starts from these arrays).
+// The base description of a scene and the transforms its objects currently have (mcpt_scene_update: transforms are absolute, so every
+// update starts from these arrays).  The triangles are the creation-time ones until mcpt_scene_deform replaces a mesh's positions; the
+// host copy is kept current by every successful deformation (positions given by device pointer are downloaded eagerly).
 struct SceneSource {
     std::vector<mcpt_triangle> triangles;
     std::vector<mcpt_object> objects;
@@ -365,6 +367,21 @@ static_assert(sizeof(MoveSeg) == 80, "MoveSeg must be 80 bytes");
 void launch_move_objects(const MoveSeg *d_segs, int32_t n_segs, int32_t n_lanes, const mcpt_triangle *tris0, mcpt_triangle *tris_cur,
                          TriGeom *tri_geom, TriShade *tri_shade, SphereRec *spheres, hipStream_t s);
 
+// One run of lanes of the deformation kernel (csrc/mcpt_update.hip): the triangles of one deformed mesh.
+struct alignas(16) DeformSeg {
+    int32_t first_lane;      // lanes [first_lane, first_lane + the mesh's triangle count) work on this segment
+    int32_t first_tri;       // the mesh's first triangle
+    int32_t object;
+    int32_t raw;             // 1: the object has no transform: the given floats are stored, not multiplied by an identity
+    float m[12];             // the object's current transform (unused when raw)
+    const float *positions;  // device pointer: 9 floats per triangle, the scene's staging buffer or the caller's array read in place
+};
+static_assert(sizeof(DeformSeg) == 80, "DeformSeg must be 80 bytes");
+// For every lane: the new base triangle (positions + the texture coordinates of tris0) into `base`, and what launch_move_objects writes
+// for it.  *flag (zeroed by the caller) becomes 1 when a position is not finite; such a lane writes nothing else.
+void launch_deform_objects(const DeformSeg *d_segs, int32_t n_segs, int32_t n_lanes, const mcpt_triangle *tris0, mcpt_triangle *base, mcpt_triangle *tris_cur,
+                           TriGeom *tri_geom, TriShade *tri_shade, uint32_t *flag, hipStream_t s);
+
 }  // namespace mcpt
 
 // Members are destroyed in reverse order, with the scene's device current (mcpt_scene_destroy): the pools' workspaces and timers, their
@@ -383,9 +400,12 @@ struct mcpt_scene {
     mcpt::DevBuf<mcpt::TriGeom> snap_tri;
     mcpt::DevBuf<mcpt::SphereRec> snap_sph;
     bool has_snapshot = false;
-    mcpt::DevBuf<mcpt_triangle> tris0;   // device builders: the creation-time triangles
+    mcpt::DevBuf<mcpt_triangle> tris0;   // device builders: the base triangles (creation time, then every mcpt_scene_deform)
     mcpt::DevBuf<int32_t> sphere_obj;    // device builders: object index of every sphere (the builder's primitive list)
     mcpt::DevBuf<mcpt::MoveSeg> segs;    // the update kernel's segment table
+    mcpt::DevBuf<mcpt::DeformSeg> dsegs; // the deformation kernel's segment table,
+    mcpt::DevBuf<float> stage;           // its staging buffer for host positions (36 B per triangle, grows to the largest call)
+    mcpt::DevBuf<uint32_t> dflag;        // and its flag word (a position that is not finite)
     mcpt::DevBuf<mcpt::MaterialRec> mats;
     mcpt::DevBuf<mcpt::InstRec> inst;
     mcpt::DevBuf<float> env;
@@ -433,6 +453,11 @@ int upload_scene(const mcpt_scene_desc *desc, HostBuild &hb, int device, mcpt_sc
 // differ from the table it has.  Also the way back for mcpt_group_update when another replica fails.
 int apply_transforms(mcpt_scene *sc, const std::vector<uint8_t> &moved, const std::vector<float> &xf, const std::vector<int32_t> &touched,
                      mcpt_update_info *info);
+// mcpt_scene_deform without the argument checks: the n listed meshes get the given positions as their base geometry; the transform
+// table stays.  Shares the rebuild with apply_transforms.  Also the way back for mcpt_group_deform when another replica fails.
+int apply_deform(mcpt_scene *sc, int32_t n, const mcpt_object_vertices *items, mcpt_update_info *info);
+// The argument checks of mcpt_scene_deform, before any device call.
+int check_deform(const mcpt_scene *sc, int32_t n, const mcpt_object_vertices *items);
 // The argument checks of mcpt_scene_update, before any device call; fills the table the scene would have afterwards.
 int check_moves(const mcpt_scene *sc, int32_t n, const mcpt_object_transform *moves, std::vector<uint8_t> &moved, std::vector<float> &xf,
                 std::vector<int32_t> &touched);

@@ -1,6 +1,6 @@
 /*
  * mcpt_move.h -- the arithmetic of moving an object and of deriving a triangle's records from its vertices (include/mcpt.h:
- * mcpt_scene_update, mcpt_transform_triangles).
+ * mcpt_scene_update, mcpt_transform_triangles, mcpt_scene_deform, mcpt_deform_triangles).
  *
  * Every function here is callable from the host and from the device.  The scene builder (csrc/mcpt_scene.cpp), the host helper
  * mcpt_transform_triangles and the update kernel (csrc/mcpt_update.hip) all compile these expressions, so a triangle moved on the device
@@ -84,6 +84,30 @@ MCPT_MV void move_triangle(const float *m, const mcpt_triangle &in, mcpt_triangl
     out.t1[1] = uv[3];
     out.t2[0] = uv[4];
     out.t2[1] = uv[5];
+}
+
+// Deformation (mcpt_scene_deform): the new base triangle is `in` with its nine position floats replaced by p[0..9) = v0, v1, v2, bit for
+// bit (a copy, no arithmetic: the sign of a zero survives); the texture coordinates are in's.
+MCPT_MV void deform_triangle(const float *p, const mcpt_triangle &in, mcpt_triangle &out) {
+    const float uv[6] = {in.t0[0], in.t0[1], in.t1[0], in.t1[1], in.t2[0], in.t2[1]};  // (in and out may be one triangle)
+    for (int k = 0; k < 3; ++k) {
+        out.v0[k] = p[k];
+        out.v1[k] = p[3 + k];
+        out.v2[k] = p[6 + k];
+    }
+    out.t0[0] = uv[0];
+    out.t0[1] = uv[1];
+    out.t1[0] = uv[2];
+    out.t1[1] = uv[3];
+    out.t2[0] = uv[4];
+    out.t2[1] = uv[5];
+}
+
+// True when all nine position floats are finite (a NaN fails every comparison).
+MCPT_MV bool positions_finite(const float *p) {
+    bool ok = true;
+    for (int k = 0; k < 9; ++k) ok = ok && (p[k] - p[k] == 0.f);
+    return ok;
 }
 
 }  // namespace mv

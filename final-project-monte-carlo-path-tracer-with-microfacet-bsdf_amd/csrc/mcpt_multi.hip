@@ -236,6 +236,57 @@ int mcpt_group_update(mcpt_group *g, int32_t n, const mcpt_object_transform *mov
     return gfail(code, e);
 }
 
+int mcpt_group_deform(mcpt_group *g, int32_t n, const mcpt_object_vertices *items) {
+    if (!g || g->scenes.empty()) return gfail(MCPT_ERR_ARG, "mcpt_group_deform: null group");
+    for (int32_t i = 0; i < n && items; ++i)
+        if (items[i].on_device != 0) return gfail(MCPT_ERR_ARG, "mcpt_group_deform: positions by device pointer (one pointer cannot be valid on several devices)");
+    // every replica holds the same base: one check, before any device call
+    const int rc0 = check_deform(g->scenes[0], n, items);
+    if (rc0 != MCPT_OK) return gfail(rc0, std::string("mcpt_group_deform: ") + mcpt_last_error());
+    const int N = (int)g->scenes.size();
+    // the way back: the positions the listed meshes have now
+    std::vector<std::vector<float>> old_pos((size_t)n);
+    std::vector<mcpt_object_vertices> old_items((size_t)n);
+    {
+        const SceneSource &S = g->scenes[0]->src;
+        for (int32_t i = 0; i < n; ++i) {
+            const mcpt_object &ob = S.objects[(size_t)items[i].object];
+            old_pos[(size_t)i].reserve((size_t)ob.n_tri * 9 + 1);
+            for (int32_t k = 0; k < ob.n_tri; ++k) {
+                const mcpt_triangle &t = S.triangles[(size_t)ob.first_tri + k];
+                old_pos[(size_t)i].insert(old_pos[(size_t)i].end(), {t.v0[0], t.v0[1], t.v0[2], t.v1[0], t.v1[1], t.v1[2], t.v2[0], t.v2[1], t.v2[2]});
+            }
+            old_pos[(size_t)i].push_back(0.f);  // (an empty mesh still needs a non-null pointer)
+            old_items[(size_t)i] = {items[i].object, 0, old_pos[(size_t)i].data()};
+        }
+    }
+    std::vector<int> rc((size_t)N, MCPT_OK);
+    std::vector<std::string> err((size_t)N);
+    auto run = [&](const mcpt_object_vertices *it, const std::vector<int> &which) {
+        auto work = [&](int i) {
+            rc[(size_t)i] = apply_deform(g->scenes[(size_t)i], n, it, nullptr);
+            if (rc[(size_t)i] != MCPT_OK) err[(size_t)i] = mcpt_last_error();
+        };
+        std::vector<std::thread> th;
+        for (size_t k = 1; k < which.size(); ++k) th.emplace_back(work, which[k]);
+        if (!which.empty()) work(which[0]);
+        for (std::thread &t : th) t.join();
+    };
+    std::vector<int> all, done;
+    for (int i = 0; i < N; ++i) all.push_back(i);
+    run(items, all);
+    int bad = -1;
+    for (int i = 0; i < N; ++i) {
+        if (rc[(size_t)i] == MCPT_OK) done.push_back(i);
+        else if (bad < 0) bad = i;
+    }
+    if (bad < 0) return MCPT_OK;
+    const int code = rc[(size_t)bad];
+    const std::string e = "mcpt_group_deform: device " + std::to_string(g->devices[(size_t)bad]) + ": " + err[(size_t)bad];
+    run(old_items.data(), done);  // the replicas that had deformed go back: the group stays one scene
+    return gfail(code, e);
+}
+
 int mcpt_group_get_info(const mcpt_group *g, mcpt_group_info *info) {
     if (!g || !info) return gfail(MCPT_ERR_ARG, "mcpt_group_get_info: null argument");
     std::memset(info, 0, sizeof *info);

@@ -334,8 +334,28 @@ int mcpt::check_moves(const mcpt_scene *sc, int32_t n, const mcpt_object_transfo
     return MCPT_OK;
 }
 
-int mcpt::apply_transforms(mcpt_scene *sc, const std::vector<uint8_t> &moved, const std::vector<float> &xf, const std::vector<int32_t> &touched,
-                           mcpt_update_info *info) {
+namespace {
+
+// The nine position floats of every triangle of the listed meshes on the host, item by item: the caller's own arrays, or downloads of
+// the arrays given by device pointer (kept in `owned`).  The scene's device must be current.
+int host_positions(const SceneSource &S, int32_t n, const mcpt_object_vertices *items, std::vector<std::vector<float>> &owned, std::vector<const float *> &pos) {
+    owned.assign((size_t)n, {});
+    pos.assign((size_t)n, nullptr);
+    for (int32_t i = 0; i < n; ++i) {
+        pos[(size_t)i] = items[i].positions;
+        const size_t nf = (size_t)S.objects[(size_t)items[i].object].n_tri * 9;
+        if (!items[i].on_device || nf == 0) continue;
+        owned[(size_t)i].resize(nf);
+        HIP_TRY(hipMemcpy(owned[(size_t)i].data(), items[i].positions, nf * sizeof(float), hipMemcpyDeviceToHost));
+        pos[(size_t)i] = owned[(size_t)i].data();
+    }
+    return MCPT_OK;
+}
+
+// The rebuild behind mcpt_scene_update and mcpt_scene_deform: the scene gets the transform table (moved, xf) and, when `deform` is given,
+// the listed meshes (touched[i] = deform[i].object) get new base positions.  Everything is built aside and committed on success.
+int rebuild(mcpt_scene *sc, const std::vector<uint8_t> &moved, const std::vector<float> &xf, const std::vector<int32_t> &touched,
+            const mcpt_object_vertices *deform, mcpt_update_info *info) {
     const auto t0 = Clock::now();
     mcpt_update_info ui;
     std::memset(&ui, 0, sizeof ui);
@@ -354,6 +374,11 @@ int mcpt::apply_transforms(mcpt_scene *sc, const std::vector<uint8_t> &moved, co
     GeomBufs g2;  // built aside; swapped in once the new tree is known to be usable
     SceneMeta meta = sc->meta;
     const size_t nt = (size_t)meta.n_triangles;
+    const int32_t n_def = deform ? (int32_t)touched.size() : 0;
+    DevBuf<mcpt_triangle> base2;              // deformation, device builders: the new base triangles, swapped with tris0 on success
+    std::vector<mcpt_triangle> base;          // deformation: the new host copy of the base, swapped with S.triangles on success
+    std::vector<std::vector<float>> fetched;  // deformation: positions downloaded from device pointers
+    std::vector<const float *> pos;
     if (meta.builder >= 2 && !emitter) {
         // ---- device path: the listed triangles and sphere centres are moved in HBM, the device builder runs again
         ui.path = 1;
@@ -369,29 +394,69 @@ int mcpt::apply_transforms(mcpt_scene *sc, const std::vector<uint8_t> &moved, co
         }
         if (sc->geom.spheres.n)
             HIP_TRY(hipMemcpyAsync(g2.spheres.p, sc->geom.spheres.p, sc->geom.spheres.bytes(), hipMemcpyDeviceToDevice, nullptr));
+        if (deform) {
+            HIP_TRY(base2.alloc(nt));
+            if (nt) HIP_TRY(hipMemcpyAsync(base2.p, sc->tris0.p, nt * sizeof(mcpt_triangle), hipMemcpyDeviceToDevice, nullptr));
+        }
         HIP_TRY(hipStreamSynchronize(nullptr));
         ui.upload_ms = ms_since(tu);
         const auto tt = Clock::now();
-        std::vector<MoveSeg> segs;
         int32_t lanes = 0;
-        for (int32_t o : touched) {
-            const mcpt_object &ob = S.objects[(size_t)o];
-            MoveSeg sg;
-            std::memset(&sg, 0, sizeof sg);
-            sg.first_lane = lanes;
-            sg.count = ob.kind == MCPT_OBJ_MESH ? ob.n_tri : 1;
-            sg.first_tri = ob.kind == MCPT_OBJ_MESH ? ob.first_tri : -1;
-            sg.object = o;
-            std::memcpy(sg.m, &xf[(size_t)o * 12], sizeof sg.m);
-            for (int k = 0; k < 3; ++k) sg.c0[k] = ob.center[k];
-            sg.raw = moved[(size_t)o] ? 0 : 1;
-            lanes += sg.count;
-            segs.push_back(sg);
+        if (deform) {
+            // host positions go through the staging buffer in one copy; device positions are read where they are
+            std::vector<float> staged;
+            std::vector<size_t> at((size_t)n_def, 0);
+            for (int32_t i = 0; i < n_def; ++i) {
+                if (deform[i].on_device) continue;
+                at[(size_t)i] = staged.size();
+                staged.insert(staged.end(), deform[i].positions, deform[i].positions + (size_t)S.objects[(size_t)touched[(size_t)i]].n_tri * 9);
+            }
+            HIP_TRY(upload(sc->stage, staged));
+            std::vector<DeformSeg> dsegs;
+            for (int32_t i = 0; i < n_def; ++i) {
+                const int32_t o = touched[(size_t)i];
+                const mcpt_object &ob = S.objects[(size_t)o];
+                if (ob.n_tri <= 0) continue;
+                DeformSeg sg;
+                std::memset(&sg, 0, sizeof sg);
+                sg.first_lane = lanes;
+                sg.first_tri = ob.first_tri;
+                sg.object = o;
+                sg.raw = moved[(size_t)o] ? 0 : 1;
+                std::memcpy(sg.m, &xf[(size_t)o * 12], sizeof sg.m);
+                sg.positions = deform[i].on_device ? deform[i].positions : sc->stage.p + at[(size_t)i];
+                lanes += ob.n_tri;
+                dsegs.push_back(sg);
+            }
+            HIP_TRY(upload(sc->dsegs, dsegs));
+            HIP_TRY(sc->dflag.alloc(1));
+            HIP_TRY(hipMemsetAsync(sc->dflag.p, 0, sizeof(uint32_t), nullptr));
+            launch_deform_objects(sc->dsegs.p, (int32_t)dsegs.size(), lanes, sc->tris0.p, base2.p, g2.tris.p, g2.tri_geom.p, g2.tri_shade.p, sc->dflag.p, nullptr);
+            HIP_TRY(hipGetLastError());
+            uint32_t flag = 0;  // (a blocking copy on the null stream: the kernel has finished when it returns)
+            HIP_TRY(download(&flag, sc->dflag, 1));
+            if (flag) return fail(MCPT_ERR_ARG, "mcpt_scene_deform: a position given by device pointer is not finite");
+        } else {
+            std::vector<MoveSeg> segs;
+            for (int32_t o : touched) {
+                const mcpt_object &ob = S.objects[(size_t)o];
+                MoveSeg sg;
+                std::memset(&sg, 0, sizeof sg);
+                sg.first_lane = lanes;
+                sg.count = ob.kind == MCPT_OBJ_MESH ? ob.n_tri : 1;
+                sg.first_tri = ob.kind == MCPT_OBJ_MESH ? ob.first_tri : -1;
+                sg.object = o;
+                std::memcpy(sg.m, &xf[(size_t)o * 12], sizeof sg.m);
+                for (int k = 0; k < 3; ++k) sg.c0[k] = ob.center[k];
+                sg.raw = moved[(size_t)o] ? 0 : 1;
+                lanes += sg.count;
+                segs.push_back(sg);
+            }
+            HIP_TRY(upload(sc->segs, segs));
+            launch_move_objects(sc->segs.p, (int32_t)segs.size(), lanes, sc->tris0.p, g2.tris.p, g2.tri_geom.p, g2.tri_shade.p, g2.spheres.p, nullptr);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipStreamSynchronize(nullptr));
         }
-        HIP_TRY(upload(sc->segs, segs));
-        launch_move_objects(sc->segs.p, (int32_t)segs.size(), lanes, sc->tris0.p, g2.tris.p, g2.tri_geom.p, g2.tri_shade.p, g2.spheres.p, nullptr);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipStreamSynchronize(nullptr));
         ui.transform_ms = ms_since(tt);
         const auto tb = Clock::now();
         int rc = build_device_tree(g2.tris.p, sc->sphere_obj.p, (int)sc->sphere_obj.n, S.choice, g2, meta);
@@ -399,12 +464,31 @@ int mcpt::apply_transforms(mcpt_scene *sc, const std::vector<uint8_t> &moved, co
             rc = fail(MCPT_ERR_LIMIT, "the BVH is deeper than the traversal stack (kMaxBvhHeight)");
         if (rc != MCPT_OK) return rc;
         ui.build_ms = ms_since(tb);
+        if (deform) {  // the host copy of the base follows at once (36 B per triangle come back for positions given by device pointer)
+            rc = host_positions(S, n_def, deform, fetched, pos);
+            if (rc != MCPT_OK) return rc;
+        }
         sc->geom.swap_prims(g2);
     } else {
         // ---- host path: desc' is flattened and its tree built as at creation; every array that depends on the geometry is copied again
         ui.path = 0;
         const auto tt = Clock::now();
+        if (deform) {  // positions given by device pointer are downloaded first, and checked here
+            const int rc = host_positions(S, n_def, deform, fetched, pos);
+            if (rc != MCPT_OK) return rc;
+            for (int32_t i = 0; i < n_def; ++i) {
+                if (!deform[i].on_device) continue;
+                for (int32_t k = 0; k < S.objects[(size_t)touched[(size_t)i]].n_tri; ++k)
+                    if (!mv::positions_finite(pos[(size_t)i] + (size_t)k * 9))
+                        return fail(MCPT_ERR_ARG, "mcpt_scene_deform: a position given by device pointer is not finite");
+            }
+        }
         std::vector<mcpt_triangle> tris = S.triangles;
+        for (int32_t i = 0; i < n_def; ++i) {
+            const mcpt_object &ob = S.objects[(size_t)touched[(size_t)i]];
+            for (int32_t k = 0; k < ob.n_tri; ++k) mv::deform_triangle(pos[(size_t)i] + (size_t)k * 9, tris[(size_t)ob.first_tri + k], tris[(size_t)ob.first_tri + k]);
+        }
+        if (deform) base = tris;
         std::vector<mcpt_object> objs = S.objects;
         for (size_t o = 0; o < objs.size(); ++o) {
             if (!moved[o]) continue;
@@ -444,9 +528,22 @@ int mcpt::apply_transforms(mcpt_scene *sc, const std::vector<uint8_t> &moved, co
         rc = upload_geometry(hs, S.choice, g2.tris.p, sc->sphere_obj.p, g2, meta, gpu_build_ms);
         if (rc != MCPT_OK) return rc;
         ui.build_ms = host_build_ms + gpu_build_ms;
+        if (deform && hs.builder >= 2) HIP_TRY(upload(base2, base));
         ui.upload_ms = ms_since(tu) - gpu_build_ms;
         sc->geom.swap_prims(g2);
         sc->geom.swap_lights(g2);
+    }
+    if (deform) {  // the new base: on the device (device builders) and on the host
+        if (meta.builder >= 2) sc->tris0.swap(base2);
+        if (ui.path == 1) {  // (the host copy is patched in place)
+            for (int32_t i = 0; i < n_def; ++i) {
+                const mcpt_object &ob = S.objects[(size_t)touched[(size_t)i]];
+                for (int32_t k = 0; k < ob.n_tri; ++k)
+                    mv::deform_triangle(pos[(size_t)i] + (size_t)k * 9, S.triangles[(size_t)ob.first_tri + k], S.triangles[(size_t)ob.first_tri + k]);
+            }
+        } else {
+            S.triangles.swap(base);
+        }
     }
     sc->meta = meta;
     S.moved = moved;
@@ -455,6 +552,48 @@ int mcpt::apply_transforms(mcpt_scene *sc, const std::vector<uint8_t> &moved, co
     ui.total_ms = ms_since(t0);
     if (info) *info = ui;
     return MCPT_OK;
+}
+
+}  // namespace
+
+int mcpt::apply_transforms(mcpt_scene *sc, const std::vector<uint8_t> &moved, const std::vector<float> &xf, const std::vector<int32_t> &touched,
+                           mcpt_update_info *info) {
+    return rebuild(sc, moved, xf, touched, nullptr, info);
+}
+
+int mcpt::check_deform(const mcpt_scene *sc, int32_t n, const mcpt_object_vertices *items) {
+    if (n < 0) return fail(MCPT_ERR_ARG, "mcpt_scene_deform: n < 0");
+    if (n > 0 && !items) return fail(MCPT_ERR_ARG, "mcpt_scene_deform: null items");
+    for (int32_t i = 0; i < n; ++i) {
+        if (!items[i].positions) return fail(MCPT_ERR_ARG, "mcpt_scene_deform: item " + std::to_string(i) + ": null positions");
+        if (items[i].on_device != 0 && items[i].on_device != 1) return fail(MCPT_ERR_ARG, "mcpt_scene_deform: item " + std::to_string(i) + ": on_device is not 0 or 1");
+    }
+    for (int32_t i = 0; i < n; ++i)
+        for (int32_t j = 0; j < i; ++j)
+            if (items[i].object == items[j].object) return fail(MCPT_ERR_ARG, "mcpt_scene_deform: object " + std::to_string(items[i].object) + " is listed twice");
+    if (!sc) return fail(MCPT_ERR_ARG, "mcpt_scene_deform: null scene");
+    const SceneSource &S = sc->src;
+    for (int32_t i = 0; i < n; ++i) {
+        if (items[i].object < 0 || items[i].object >= (int32_t)S.objects.size())
+            return fail(MCPT_ERR_ARG, "mcpt_scene_deform: object index " + std::to_string(items[i].object) + " out of range");
+        if (S.objects[(size_t)items[i].object].kind != MCPT_OBJ_MESH)
+            return fail(MCPT_ERR_ARG, "mcpt_scene_deform: object " + std::to_string(items[i].object) + " is a sphere");
+    }
+    if (S.choice.builder == MCPT_BUILD_SAH && S.choice.instancing == 1)
+        return fail(MCPT_ERR_ARG, "mcpt_scene_deform: the scene was built with node instancing on (instanced subtrees are shared between objects)");
+    for (int32_t i = 0; i < n; ++i) {
+        if (items[i].on_device) continue;
+        for (int32_t k = 0; k < S.objects[(size_t)items[i].object].n_tri; ++k)
+            if (!mv::positions_finite(items[i].positions + (size_t)k * 9))
+                return fail(MCPT_ERR_ARG, "mcpt_scene_deform: item " + std::to_string(i) + ": a position is not finite");
+    }
+    return MCPT_OK;
+}
+
+int mcpt::apply_deform(mcpt_scene *sc, int32_t n, const mcpt_object_vertices *items, mcpt_update_info *info) {
+    std::vector<int32_t> touched;
+    for (int32_t i = 0; i < n; ++i) touched.push_back(items[i].object);
+    return rebuild(sc, sc->src.moved, sc->src.xf, touched, n > 0 ? items : nullptr, info);
 }
 
 // The layout of mcpt_bvh_dump / mcpt_scene_dump_bvh: per node 12 floats {lmin, lmax, rmin, rmax}, two child references and (qn != nullptr) the
@@ -520,6 +659,12 @@ int mcpt_scene_update(mcpt_scene *sc, int32_t n, const mcpt_object_transform *mo
     const int rc = check_moves(sc, n, moves, moved, xf, touched);
     if (rc != MCPT_OK) return rc;
     return apply_transforms(sc, moved, xf, touched, info);
+}
+
+int mcpt_scene_deform(mcpt_scene *sc, int32_t n, const mcpt_object_vertices *items, mcpt_update_info *info) {
+    const int rc = check_deform(sc, n, items);
+    if (rc != MCPT_OK) return rc;
+    return apply_deform(sc, n, items, info);
 }
 
 int mcpt_scene_snapshot(mcpt_scene *sc) {

@@ -20,6 +20,7 @@ EXPORTS = ["mcpt_scene_create", "mcpt_scene_destroy", "mcpt_render", "mcpt_rende
            "mcpt_cast_rays", "mcpt_camera_rays", "mcpt_scene_get_info", "mcpt_bvh_dump", "mcpt_scene_create_ex", "mcpt_scene_dump_bvh", "mcpt_tonemap", "mcpt_tonemap_device", "mcpt_debug_fmath", "mcpt_debug_material", "mcpt_debug_scene", "mcpt_debug_shadow", "mcpt_debug_counters",
            "mcpt_cull_bound", "mcpt_debug_classify",
            "mcpt_scene_update", "mcpt_group_update", "mcpt_transform_triangles",
+           "mcpt_scene_deform", "mcpt_group_deform", "mcpt_deform_triangles",
            "mcpt_scene_snapshot", "mcpt_render_motion", "mcpt_temporal_blend", "mcpt_temporal_accumulate",
            "mcpt_temporal_accumulate_ex",
            "mcpt_sequence_create", "mcpt_sequence_frame", "mcpt_sequence_reset", "mcpt_sequence_destroy",
@@ -223,6 +224,83 @@ class CullInfo(C.Structure):
         return {k: (np.float32(getattr(self, k)) if t is C.c_float else getattr(self, k)) for k, t in self._fields_}
 
 
+class ObjectVertices(C.Structure):
+    _fields_ = [("object", C.c_int32), ("on_device", C.c_int32), ("positions", C.c_void_p)]
+
+
+class DevicePositions:
+    """Vertex positions that already sit in the memory of the scene's device: the address of n_tri * 9 contiguous float32 values (v0, v1, v2
+    of each triangle).  HipScene.deform also takes any object with __cuda_array_interface__, or with data_ptr() and is_cuda (a torch
+    tensor), directly."""
+
+    def __init__(self, ptr, n_tri):
+        self.ptr, self.n_tri = int(ptr), int(n_tri)
+        if self.ptr == 0 or self.n_tri < 0:
+            raise ValueError("DevicePositions: a non-null device address and a triangle count >= 0")
+
+
+def _device_positions(v):
+    """DevicePositions for a device buffer, None for anything else.  Shape, dtype and contiguity are checked here: the library reads
+    n_tri * 9 float32 values at the address."""
+    if isinstance(v, DevicePositions):
+        return v
+    cai = getattr(v, "__cuda_array_interface__", None)
+    if cai is not None:
+        shape, typestr, strides = tuple(cai["shape"]), cai["typestr"], cai.get("strides")
+        ptr = cai["data"][0]
+    elif hasattr(v, "data_ptr") and getattr(v, "is_cuda", False):
+        if not v.is_contiguous():
+            raise ValueError("deform: a device tensor must be contiguous")
+        shape, typestr, strides = tuple(v.shape), "<f4" if str(v.dtype).endswith("float32") else str(v.dtype), None
+        ptr = v.data_ptr()
+    else:
+        return None
+    if typestr not in ("<f4", "=f4", "|f4"):
+        raise ValueError("deform: device positions must be float32, not %s" % typestr)
+    if strides is not None:
+        want, acc = [], 4
+        for d in reversed(shape):
+            want.insert(0, acc)
+            acc *= d
+        if tuple(strides) != tuple(want):
+            raise ValueError("deform: device positions must be C-contiguous")
+    n = 1
+    for d in shape:
+        n *= int(d)
+    if not ((len(shape) == 3 and shape[1:] == (3, 3)) or len(shape) == 1) or n % 9:
+        raise ValueError("deform: positions have shape (n_tri, 3, 3) or (n_tri * 9,), not %s" % (shape,))
+    return DevicePositions(ptr, n // 9) if n else None
+
+
+def _vertex_items(items, n_tri_of):
+    """An iterable of (object index, vertices) as an array of mcpt_object_vertices.  n_tri_of: the triangle count of each mesh object, -1
+    for the objects the library refuses anyway; `keep` holds the host arrays for the duration of the call."""
+    items = list(items)
+    arr, keep = (ObjectVertices * max(len(items), 1))(), []
+    for k, (obj, v) in enumerate(items):
+        obj = int(obj)
+        dev = _device_positions(v)
+        if dev is not None:
+            n_tri, ptr, on_device = dev.n_tri, dev.ptr, 1
+        else:
+            if not isinstance(v, np.ndarray) or v.dtype != np.float32 or not v.flags["C_CONTIGUOUS"]:
+                raise ValueError("deform: vertices are a C-contiguous float32 array, a device buffer or DevicePositions")
+            if not ((v.ndim == 3 and v.shape[1:] == (3, 3)) or v.ndim == 1) or v.size % 9:
+                raise ValueError("deform: positions have shape (n_tri, 3, 3) or (n_tri * 9,), not %s" % (v.shape,))
+            keep.append(v)
+            n_tri, ptr, on_device = v.size // 9, (v.ctypes.data if v.size else C.addressof(arr)), 0
+        if 0 <= obj < len(n_tri_of) and n_tri_of[obj] >= 0 and n_tri != int(n_tri_of[obj]):
+            raise ValueError("deform: object %d has %d triangles, the positions given describe %d" % (obj, int(n_tri_of[obj]), n_tri))
+        arr[k].object, arr[k].on_device, arr[k].positions = obj, on_device, ptr
+    return arr, len(items), keep
+
+
+def _mesh_tri_counts(sd):
+    """Per object: its triangle count (-1 for a sphere, which the library refuses)."""
+    o = sd.objects
+    return np.where(o["kind"] == 0, o["n_tri"], -1)
+
+
 def _moves(moves):
     """An iterable of (object index, 3x4 array) as an array of mcpt_object_transform."""
     moves = list(moves)
@@ -389,6 +467,12 @@ def lib(path=None):
         L.mcpt_group_update.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
         L.mcpt_transform_triangles.restype = C.c_int
         L.mcpt_transform_triangles.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        L.mcpt_scene_deform.restype = C.c_int
+        L.mcpt_scene_deform.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(UpdateInfo)]
+        L.mcpt_group_deform.restype = C.c_int
+        L.mcpt_group_deform.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+        L.mcpt_deform_triangles.restype = C.c_int
+        L.mcpt_deform_triangles.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
         L.mcpt_group_create.restype = C.c_int
         L.mcpt_group_create.argtypes = [C.POINTER(SceneDesc), C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]
         L.mcpt_group_render.restype = C.c_int
@@ -460,6 +544,23 @@ def transform_triangles(m, tris, out=None):
     return out
 
 
+def deform_triangles(positions, tris, out=None):
+    """mcpt_deform_triangles (host only): the triangles (scenes.TRI_DTYPE) with their vertices replaced by `positions`, a C-contiguous float32
+    array of shape (n_tri, 3, 3) or (n_tri * 9,); the texture coordinates are copied.  out: the array to write (may be `tris` itself)."""
+    if not isinstance(positions, np.ndarray) or positions.dtype != np.float32 or not positions.flags["C_CONTIGUOUS"]:
+        raise ValueError("deform_triangles: positions are a C-contiguous float32 array")
+    if not tris.flags["C_CONTIGUOUS"]:
+        tris = np.ascontiguousarray(tris)
+    if positions.size != tris.size * 9:
+        raise ValueError("deform_triangles: %d triangles need %d position floats, not %d" % (tris.size, tris.size * 9, positions.size))
+    if out is None:
+        out = np.empty_like(tris)
+    if out.dtype != tris.dtype or out.shape != tris.shape or not out.flags["C_CONTIGUOUS"] or tris.dtype.itemsize != 60:
+        raise ValueError("deform_triangles: arrays of 60-byte triangles with one shape")
+    _check(lib().mcpt_deform_triangles(tris.size, _ptr(positions), _ptr(tris), _ptr(out)))
+    return out
+
+
 def cull_bound(camera, root_min, root_max, library=None):
     """mcpt_cull_bound (host only): the sky cull's bound for a camera (scenes.CAM_DTYPE) over a root box, as a dict of mcpt_cull_info."""
     cam = np.ascontiguousarray(camera)
@@ -528,6 +629,17 @@ class HipScene:
         arr, n = _moves(moves)
         info = UpdateInfo()
         _check(self.L.mcpt_scene_update(self.h, n, C.cast(arr, C.c_void_p), C.byref(info)), L=self.L)
+        return info.as_dict()
+
+    def deform(self, items):
+        """mcpt_scene_deform: items = an iterable of (object index, vertices), the new base positions of mesh objects.  vertices: a
+        C-contiguous float32 numpy array of shape (n_tri, 3, 3) or (n_tri * 9,); or a buffer in the memory of the scene's device, read in
+        place (anything with __cuda_array_interface__, or with data_ptr() and is_cuda such as a torch tensor, or DevicePositions(ptr,
+        n_tri)), which must be complete before the call.  Returns mcpt_update_info as a dict."""
+        arr, n, keep = _vertex_items(items, _mesh_tri_counts(self.sd))
+        info = UpdateInfo()
+        _check(self.L.mcpt_scene_deform(self.h, n, C.cast(arr, C.c_void_p), C.byref(info)), L=self.L)
+        del keep
         return info.as_dict()
 
     def close(self):
@@ -1267,6 +1379,15 @@ class HipGroup:
         """mcpt_group_update: HipScene.update on every replica."""
         arr, n = _moves(moves)
         rc = self.L.mcpt_group_update(self.h, n, C.cast(arr, C.c_void_p))
+        if rc != 0:
+            raise McptError(rc, self.L.mcpt_group_last_error().decode("utf-8", "replace"))
+
+    def deform(self, items):
+        """mcpt_group_deform: HipScene.deform on every replica; host arrays only (the library refuses a device buffer: one pointer cannot
+        be valid on several devices)."""
+        arr, n, keep = _vertex_items(items, _mesh_tri_counts(self.sd))
+        rc = self.L.mcpt_group_deform(self.h, n, C.cast(arr, C.c_void_p))
+        del keep
         if rc != 0:
             raise McptError(rc, self.L.mcpt_group_last_error().decode("utf-8", "replace"))
 

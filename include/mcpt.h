@@ -195,6 +195,51 @@ int mcpt_scene_update(mcpt_scene *scene, int32_t n, const mcpt_object_transform 
  * MCPT_ERR_ARG for m == NULL, a matrix entry that is not finite, n < 0, or n > 0 with a null array. */
 int mcpt_transform_triangles(const float m[12], int64_t n, const mcpt_triangle *in, mcpt_triangle *out);
 
+/* ---- Deforming meshes in a live scene: per-vertex updates from host or device memory.
+ *
+ * mcpt_scene_deform gives the listed meshes new vertex positions and rebuilds the traversal tree with the scene's own builder, exactly
+ * as mcpt_scene_update does (one rebuild serves both).
+ *   A deformation replaces the object's BASE geometry, the thing absolute transforms apply to.  The object's current transform, if it
+ *   ever got one, keeps applying to the new base by the point rule above; a later mcpt_scene_update applies its matrix to the latest
+ *   base.  An object that never got a transform stores the given floats bit for bit (the sign of a zero included).
+ *   positions holds n_tri * 9 floats: v0, v1, v2 of each of the object's triangles, in the object's triangle order.  The triangle count,
+ *   the triangle order, the texture coordinates and the material are unchanged.  Degenerate (zero-area) triangles are allowed, as at
+ *   creation.
+ *   on_device 0: positions is a host pointer.  on_device 1: a pointer into the memory of the scene's device (a PyTorch tensor, say), read
+ *   in place by the kernel; the positions must be complete before the call (the caller synchronises its producer stream).  The call is
+ *   blocking and works on the null stream, like mcpt_scene_update.
+ * THE CONTRACT: after the call every entry point listed at mcpt_scene_update gives what it gives on
+ *       mcpt_scene_create_ex(desc'', device, the same options)
+ * where desc'' is the creation description with each deformed object's positions replaced by the latest ones given (what
+ * mcpt_deform_triangles computes), then the current transforms applied (mcpt_transform_triangles).  With the host builders bit for bit,
+ * the tree dump included; with the device builders by the rule stated there: primitive ids equal ray for ray, a frame within a few
+ * values of a box-grazing ray.  Primitive ids are stable, so a snapshot taken before the call pairs every hit with the triangle's
+ * previous vertices: mcpt_render_motion gives the motion of a triangle whose three vertices moved independently.
+ *   info->path 1  device: the scene was built by MCPT_BUILD_GPU_LBVH or MCPT_BUILD_GPU_PLOC and no listed object emits light.  Host
+ *                 positions cross the bus once, 36 bytes per triangle, into a staging buffer the scene owns; device positions are read
+ *                 where they are.  One kernel forms the new base, applies the transforms and writes the records; the device builder
+ *                 runs again.  The scene's host copy of the base follows at once: positions given by device pointer are copied back
+ *                 (36 bytes per triangle) after the rebuild has succeeded, so that a later call on path 0 starts from the latest base.
+ *   info->path 0  host: otherwise, exactly as for mcpt_scene_update.  Positions given by device pointer are downloaded first.
+ *   info->n_moved_tris is the number of triangles of the listed meshes; the timing fields keep their meaning (on path 1 transform_ms
+ *   covers the staging copy, the segment table and the kernel).
+ * MCPT_ERR_ARG, before any device call: n < 0; n > 0 with items == NULL; a null positions; on_device not 0 or 1; an object listed twice in
+ * one call; scene == NULL; an object index out of range; a sphere object; a scene built with node instancing on; a host position that
+ * is not finite.  A position given by device pointer can only be checked once it is read: on path 1 the kernel raises one flag word
+ * that the host reads before anything is swapped, on path 0 the downloaded copy is checked; either way the call returns MCPT_ERR_ARG.
+ * n == 0 is a valid no-op.  Any failed call (MCPT_ERR_ARG, MCPT_ERR_LIMIT, MCPT_ERR_OOM) leaves the scene exactly as it was: the base
+ * geometry on the host and on the device, the transforms, the live arrays and the snapshot.  The new base is built aside and committed
+ * with the new tree. */
+typedef struct {
+    int32_t object;          /* a MESH object of the scene */
+    int32_t on_device;       /* 0: positions is a host pointer; 1: a pointer into the scene's device */
+    const float *positions;  /* n_tri * 9 floats: v0, v1, v2 of each triangle, in the object's triangle order */
+} mcpt_object_vertices;      /* 16 bytes */
+int mcpt_scene_deform(mcpt_scene *scene, int32_t n, const mcpt_object_vertices *items, mcpt_update_info *info /* nullable */);
+/* Host only, no GPU needed: out[i] = in[i] with its nine position floats replaced by positions[9i .. 9i+9) (uv copied); in == out allowed.
+ * MCPT_ERR_ARG for n < 0, or n > 0 with a null array. */
+int mcpt_deform_triangles(int64_t n, const float *positions, const mcpt_triangle *in, mcpt_triangle *out);
+
 /* Replaces the pixel/spp loop of Renderer::Render (Renderer.cpp:21-91): fb_host = W*H*3 floats,
  * row-major m = j*W + i, linear radiance averaged over spp -- what `framebuffer` holds at Renderer.cpp:91.
  * Blocking.  Tone map and PNG output (Renderer.cpp:95-109) stay with the caller. */
@@ -962,6 +1007,9 @@ mcpt_scene *mcpt_group_scene(mcpt_group *group, int index);
 /* mcpt_scene_update on every replica (one host thread per replica), with the same checks before any device call.  If a replica fails,
  * the replicas that had succeeded are given their previous transforms back, so that the group stays one scene. */
 int mcpt_group_update(mcpt_group *group, int32_t n, const mcpt_object_transform *moves);
+/* mcpt_scene_deform on every replica, host pointers only: an item with on_device 1 is refused with MCPT_ERR_ARG, since one pointer
+ * cannot be valid on several devices.  If a replica fails, the replicas that had succeeded get their previous positions back. */
+int mcpt_group_deform(mcpt_group *group, int32_t n, const mcpt_object_vertices *items);
 void mcpt_group_destroy(mcpt_group *group);
 const char *mcpt_group_last_error(void);
 
