@@ -13,6 +13,11 @@ LIB = os.path.join(HERE, "libmcpt_hip.so")
 # entries (so that most rays lose an entry, go through the retrace lists and are traced again with the scratch stack).  Tests load it explicitly; the product library carries none of it.
 LIB_CHECK = os.path.join(HERE, "libmcpt_hip_check.so")
 CHECK_DEFINES = ["-DMCPT_TEST_HOOKS", "-DMCPT_CHECK_DIRECT_SKIP", "-DMCPT_FORCE_RETRY", "-DMCPT_STK_RETRY=4"]
+# The hooks build: the test hooks and the forced retry flavour without the direct-lighting-skip check, so that what that check compiles
+# out (first hits on smooth conductors finished in k_primary) runs with the free ring started next to its 2^32 wrap and with reflected
+# rays that lose stack entries.  Tests only, like the checking build.
+LIB_HOOKS = os.path.join(HERE, "libmcpt_hip_hooks.so")
+HOOKS_DEFINES = ["-DMCPT_TEST_HOOKS", "-DMCPT_FORCE_RETRY", "-DMCPT_STK_RETRY=4"]
 SOURCES = ["mcpt_scene.cpp", "mcpt_kernels.hip", "mcpt_wavefront.hip", "mcpt_upload.hip", "mcpt_render.hip", "mcpt_query.hip", "mcpt_multi.hip", "mcpt_lbvh.hip", "mcpt_cull.hip", "mcpt_adaptive.hip", "mcpt_denoise.hip", "mcpt_update.hip", "mcpt_temporal.hip", "mcpt_moments.hip", "mcpt_sequence.hip"]
 HEADERS = ["mcpt_internal.h", "mcpt_device.h", "mcpt_fmath.h", "mcpt_kernels.h", "mcpt_traverse.h", "mcpt_host.h", "mcpt_lbvh.h", "mcpt_cull.h", "mcpt_adaptive.h", "mcpt_denoise.h", "mcpt_move.h", "mcpt_temporal.h", "mcpt_moments.h", "mcpt_specular_motion.h", "mcpt_chain.h", "mcpt_frame.h", os.path.join("..", "..", "include", "mcpt.h")]
 # -ffp-contract=off: the arithmetic contract of csrc/mcpt_device.h (no FMA contraction, so the same seeds
@@ -81,6 +86,13 @@ def build_check(force=False, verbose=False):
     return _compile(LIB_CHECK, CHECK_DEFINES, ".check", verbose)
 
 
+def build_hooks(force=False, verbose=False):
+    """libmcpt_hip_hooks.so (see LIB_HOOKS)."""
+    if not force and not needs_build(LIB_HOOKS):
+        return LIB_HOOKS
+    return _compile(LIB_HOOKS, HOOKS_DEFINES, ".hooks", verbose)
+
+
 def build_host(verbose=False):
     """The C++ host mirror of the reference's executable (host/RayTracing, host/RayTracingDemo)."""
     subprocess.check_call(["make", "-C", os.path.join(HERE, "host")], stdout=None if verbose else subprocess.DEVNULL)
@@ -98,3 +110,4 @@ if __name__ == "__main__":
         sys.exit(0)
     print(build(force="--force" in sys.argv, verbose=True))
     print(build_check(force="--force" in sys.argv, verbose=True))
+    print(build_hooks(force="--force" in sys.argv, verbose=True))

@@ -48,6 +48,8 @@ struct FrameCall {
         if (stats) fill_stats(stats, samples, traced_primary, p.n_dir_sample, rt, t0);
         sc->last_cont_traced = rt.cont_traced;  // (mcpt_scene_ray_counts)
         sc->last_cont_shared = rt.cont_shared;
+        sc->last_pc_samples = rt.pc_samples;  // (mcpt_scene_primary_conductor_counts)
+        sc->last_pc_rays = rt.pc_rays;
         if (rt.overflow) return fail(MCPT_ERR_OVERFLOW, "some paths outran the clamp stack (raise params.max_depth)");
         return MCPT_OK;
     }

@@ -212,6 +212,7 @@ struct Knobs {
     bool sky_cull = true;       // MCPT_SKY_CULL=0: trace the pixels that can only see the background too
     bool small_scene = true;    // MCPT_SMALL_SCENE=0: no LDS-resident flavour for scenes of a few KB
     bool share_rays = true;     // MCPT_SHARE_RAYS=0: every channel path stores and traces its own continuation ray (RenderConst::share_rays)
+    bool primary_conductor = true;  // MCPT_PRIMARY_CONDUCTOR=0: first hits on smooth conductors go through k_shade like every other (RenderConst::primary_conductor)
     uint64_t fake_free_mb = 0;  // MCPT_FAKE_FREE_MB: pretend that only this much device memory is free (exercises the pool shrink)
     void read();
 };
@@ -281,6 +282,8 @@ struct Totals {
     // `closest` counts resolved rays: every record's ray, whether k_trace_closest walked the tree for it or a sibling's ray served
     // (Counters::shared).  The continuation rays among them: cont_traced walked, cont_shared did not.
     uint64_t cont_traced = 0, cont_shared = 0;
+    // Of those, k_primary's short path (first hits on smooth conductors): its samples, and the reflected rays it walked itself (part of cont_traced).
+    uint64_t pc_samples = 0, pc_rays = 0;
     double ms[K_NCLASS] = {0, 0, 0, 0, 0, 0};
     uint64_t cnt[K_NCLASS] = {0, 0, 0, 0, 0, 0};
     Totals &operator+=(const Totals &o) {
@@ -293,6 +296,8 @@ struct Totals {
         overflow += o.overflow;
         cont_traced += o.cont_traced;
         cont_shared += o.cont_shared;
+        pc_samples += o.pc_samples;
+        pc_rays += o.pc_rays;
         for (int c = 0; c < K_NCLASS; ++c) {
             ms[c] += o.ms[c];
             cnt[c] += o.cnt[c];
@@ -391,6 +396,7 @@ struct mcpt_scene {
     int device_sharers = 1;  // scenes of one group that live on this device (mcpt_group_create with a device listed several times)
     mcpt::Knobs knobs;
     mcpt_scene_info info{};
+    uint64_t last_pc_samples = 0, last_pc_rays = 0;  // the short path of k_primary in that call (mcpt_scene_primary_conductor_counts)
     uint64_t last_cont_traced = 0, last_cont_shared = 0;  // continuation rays of the last render or mcpt_cast_rays call (mcpt_scene_ray_counts)
     mcpt::SceneMeta meta;
     mcpt::SceneSource src;

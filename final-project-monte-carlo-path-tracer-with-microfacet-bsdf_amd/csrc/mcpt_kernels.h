@@ -44,8 +44,12 @@ struct Counters {
     HotCounter overflow;    // cumulative: paths cut by max_depth
     HotCounter ended;       // vertices shaded and finished in the same k_shade call (no record); folded into tot_ended
     HotCounter shared;      // records that continue on a sibling's ray (k_shade stored no ray of their own); folded into tot_shared
+    // First hits on smooth conductors that k_primary finishes itself (primary_sample in mcpt_kernels.hip):
+    HotCounter n_brays[2];  // reflected rays of list 0 / 1 that k_primary has traced already: entries RenderConst::back2_base - k of the ray arrays
+    HotCounter pc_samples;  // samples that took the short path; folded into tot_pc_samples
+    HotCounter pc_rays;     // reflected rays it resolved beyond those counted in `shared`; folded into tot_pc_rays
     // cumulative totals kept on the device by k_bookkeep (the host does not see every iteration's counts)
-    unsigned long long tot_shaded, tot_direct, tot_shadow, tot_cont, tot_iterations, tot_pushes, tot_ended, tot_shared;
+    unsigned long long tot_shaded, tot_direct, tot_shadow, tot_cont, tot_iterations, tot_pushes, tot_ended, tot_shared, tot_pc_samples, tot_pc_rays;
     uint32_t last_shadow;  // length of the shadow queue k_bookkeep cleared last (the host sizes the next k_trace_shadow grid from it)
     // ---- everything above is what the host reads back every iteration (kCountersHeadBytes); the sharded counters stay on the device
     HotCounter n_shadow[2][kShadowShards];    // per shard: shadow rays whose light sample was found (indexed like the list the rays belong to)
@@ -104,6 +108,9 @@ struct RenderConst {
     uint32_t *free_slots;
     uint32_t free_mask;  // ring size - 1
     uint32_t ray_cap;    // entries of the ray / hit arrays
+    int32_t primary_conductor;  // k_primary finishes first hits on smooth conductors whose direct light is provably zero (MCPT_PRIMARY_CONDUCTOR=0: off)
+    int32_t first_fill;         // this k_primary fills the first list of a call: k_bookkeep never counts that list's records, so the short path counts them
+    uint32_t back2_base;        // ... and stores the reflected rays it traced at entries back2_base - k: below the back entries of this iteration's samples
     Counters *counters;
 };
 

@@ -6,7 +6,8 @@
 //                    emits a vertex record + at most one continuation ray; survivors are stream-compacted into
 //                    the next list with ballot/popcount wave-aggregated atomics.
 //   k_primary        camera ray + closest hit for new samples, fused (one primary ray feeds the three channel
-//                    paths); sky misses and depth-0 emitter hits are finished here and never become records.
+//                    paths); sky misses and depth-0 emitter hits are finished here and never become records, and so are first hits
+//                    on smooth conductors without direct light, whose reflected ray the kernel walks itself (primary_sample).
 //   k_direct         direct lighting, one lane per (vertex, light sample); non-zero samples enter the shadow queue.
 //   k_trace_closest  closest hit for continuation rays.
 //   k_trace_shadow   shadow queue (persistent grid): the distance-equality visibility of Scene.cpp:75.
@@ -83,14 +84,6 @@ MCPT_DI void block_alloc_end(BlockAllocShared &sh, const uint32_t (&mult)[N], co
     __syncthreads();
 #pragma unroll
     for (int k = 0; k < N; ++k) index[k] = sh.base[k] + (sh.cnt[wave][k] + prefix[k]) * mult[k];
-}
-
-template <int N>
-MCPT_DI void block_alloc(BlockAllocShared &sh, const bool (&want)[N], const uint32_t (&mult)[N], uint32_t *const (&counter)[N],
-                         const bool (&subtract)[N], uint32_t (&index)[N]) {
-    uint32_t prefix[N];
-    block_alloc_begin<N>(sh, want, mult, counter, subtract, prefix);
-    block_alloc_end<N>(sh, mult, prefix, index);
 }
 
 MCPT_DI f3 ld3(float4 v) { return mk3(v.x, v.y, v.z); }
@@ -492,120 +485,7 @@ MCPT_DI bool primary_ray(const DevScene &S, const CameraConst &cam, const Render
     return true;
 }
 
-// What follows the closest hit of a new sample (all lanes of the workgroup call it; `valid` lanes hold a sample):
-//   miss (Scene.cpp:88-95) ............ result[3 channels] = environment, no records
-//   depth-0 emitter (Scene.cpp:102-107)  result[3 channels] = clamp(0,1, emission * |wo.n|), no records
-//   surface ........................... one ray + hit entry, three fresh path records, three clamp-stack slots
-MCPT_DI void primary_finish(const DevScene &S, const RenderConst &C, const Wave &next, int next_idx, int q, uint32_t s, bool valid, f3 pos, f3 dir,
-                            const TraceResult &tr, BlockAllocShared &sh) {
-    bool surface = false;
-    float *const result = q ? C.result[1] : C.result[0];
-    if (valid) {
-        if (tr.prim < 0) {
-            const f3 env = sample_env(S, dir);
-            result[(size_t)s * 3 + 0] = env.x;
-            result[(size_t)s * 3 + 1] = env.y;
-            result[(size_t)s * 3 + 2] = env.z;
-        } else {
-            const int mat = (int)(tr.mat_bits & kMatIndexMask);
-            if (tr.mat_bits >> 31) {  // depth-0 emitter, Scene.cpp:102-107
-                const MaterialRec &M = S.mats[mat];
-                f3 n;
-                if (tr.prim < S.n_tri) {
-                    const TriShade ts = S.tri_shade[tr.prim];
-                    n = mk3(ts.n[0], ts.n[1], ts.n[2]);
-                } else {
-                    const SphereRec sp = S.spheres[tr.prim - S.n_tri];
-                    const f3 p = pos + dir * (float)tr.t;
-                    n = normalized(p - mk3(sp.c[0], sp.c[1], sp.c[2]));
-                }
-                const float c = fabsf(dot(-dir, n));
-                result[(size_t)s * 3 + 0] = clampf(0, 1, M.emit[0] * c);
-                result[(size_t)s * 3 + 1] = clampf(0, 1, M.emit[1] * c);
-                result[(size_t)s * 3 + 2] = clampf(0, 1, M.emit[2] * c);
-            } else {
-                surface = true;
-            }
-        }
-    }
-    const bool want[3] = {surface, surface, surface && C.track_live};
-    const uint32_t mult[3] = {1u, 3u, 3u};
-    uint32_t *const ctr[3] = {&C.counters->n_prays[next_idx].v, &C.counters->free_head.v, &C.counters->live[q].v};  // three more unfinished paths of this pass
-    const bool sub[3] = {false, false, false};
-    uint32_t idx[3];
-    block_alloc<3>(sh, want, mult, ctr, sub, idx);
-    if (!surface) return;
-    // the ray is already traced: it goes to the back of the ray arrays, away from the continuation rays that k_shade appends
-    // at the front for k_trace_closest.  The three channel paths get no records: k_shade derives them from the sample entry.
-    const uint32_t k = idx[0], ri = C.ray_cap - 1u - k;
-    next.ray_o[ri] = make_float4(pos.x, pos.y, pos.z, 0.f);
-    next.ray_d[ri] = make_float4(dir.x, dir.y, dir.z, 0.f);
-    next.hit[ri] = pack_hit(tr.t, tr.prim, tr.mat_bits);
-    next.fresh[k] = make_uint2(s | (q ? 0x80000000u : 0u), idx[1]);
-}
-
-// k_primary: Renderer.cpp:44-79 up to the first Scene::intersect of castRay (Scene.cpp:87) for new samples.
-// The three channel paths of a sample share the primary ray, so it is generated and traced once.
-template <int STK, bool RETRY, bool SMALL>
-__global__ __launch_bounds__(kBlock) void k_primary(DevScene S, CameraConst cam, RenderConst C, Wave next, int next_idx, int q,
-                                                    uint32_t first_sample, uint32_t n_samples, RetryList rl) {
-    __shared__ int32_t stk[STK][kBlock];
-    __shared__ BlockAllocShared sh;
-    if constexpr (SMALL) {
-        __shared__ SmallGeomLds small_geom;
-        stage_small_geom(S, small_geom);
-        __syncthreads();
-    }
-    const int tid = threadIdx.x;
-    const uint32_t j = blockIdx.x * kBlock + tid;
-    bool valid = j < n_samples;
-    const uint32_t s = first_sample + j;
-    f3 pos = mk3(0, 0, 0), dir = mk3(0, 0, 1);
-    TraceResult tr{DBL_MAX, -1, 0u, false, false};
-    if (valid) {
-        if (!primary_ray(S, cam, C, q, s, pos, dir, tr)) {
-            tr = traverse<false, STK, RETRY, SMALL>(S, make_ray(pos, dir), 0.f, stk, tid);
-            if (RETRY && tr.dropped) {  // the sample is finished by k_primary_retrace
-                retry_append(rl, s);
-                valid = false;
-            }
-        }
-    }
-#ifdef MCPT_TRAVERSAL_STATS
-    if (S.dbg) {  // how many DIFFERENT primitives the 64 primary rays of a wave hit: what a wave-shared (packet) walk would have to visit at least
-        const int myp = (valid && tr.prim >= 0) ? tr.prim : -2;
-        bool first = myp >= 0;
-        for (int l = 0; l < 64; ++l) {
-            const int op = __shfl(myp, l);
-            if ((uint32_t)l < lane_id() && op == myp) first = false;
-        }
-        const unsigned long long m = __ballot(first), mh = __ballot(myp >= 0);
-        if (lane_id() == 0 && mh) {
-            atomicAdd(&S.dbg[14], (unsigned long long)__popcll(m));
-            atomicAdd(&S.dbg[15], 1ull);
-        }
-    }
-#endif
-    primary_finish(S, C, next, next_idx, q, s, valid, pos, dir, tr, sh);
-}
-
-// The samples k_primary put on its retrace list: the same, with the scratch stack (a fixed grid strides over the list).
-__global__ __launch_bounds__(kBlock) void k_primary_retrace(DevScene S, CameraConst cam, RenderConst C, Wave next, int next_idx, int q, RetryList rl) {
-    __shared__ int32_t stk[1][kBlock];
-    __shared__ BlockAllocShared sh;
-    const uint32_t n = min(*rl.count, rl.cap);
-    for (uint32_t base = blockIdx.x * kBlock; base < n; base += gridDim.x * kBlock) {  // uniform trip count per workgroup
-        const uint32_t j = base + threadIdx.x;
-        const bool valid = j < n;
-        const uint32_t s = valid ? rl.items[j] : 0u;
-        f3 pos = mk3(0, 0, 0), dir = mk3(0, 0, 1);
-        TraceResult tr{DBL_MAX, -1, 0u, false, false};
-        if (valid && !primary_ray(S, cam, C, q, s, pos, dir, tr)) tr = traverse_scratch<false>(S, make_ray(pos, dir), 0.f, stk, threadIdx.x);
-        primary_finish(S, C, next, next_idx, q, s, valid, pos, dir, tr, sh);
-        __syncthreads();  // `sh` is reused by the next round
-    }
-    retry_finish(rl);
-}
+// (k_primary and k_primary_retrace, which finish the closest hit of a new sample, follow direct_is_zero below: they call it.)
 
 // mcpt_cast_rays: caller-supplied rays, one fresh record per ray; the rays are traced by k_trace_closest.
 __global__ __launch_bounds__(kBlock) void k_generate_explicit(Wave next, Counters *c, int next_idx, uint32_t n) {
@@ -651,6 +531,8 @@ __global__ __launch_bounds__(kBlock) void k_init_free(uint32_t *free_slots, Coun
         c->free_head.v = start;
         c->free_tail.v = start + pool;
         c->n_prays[0].v = c->n_prays[1].v = 0;
+        c->n_brays[0].v = c->n_brays[1].v = 0;
+        c->pc_samples.v = c->pc_rays.v = 0;
         c->live[0].v = c->live[1].v = 0;
         for (uint32_t k = 0; k < kShadowShards; ++k) {
             c->n_shadow[0][k].v = c->n_shadow[1][k].v = 0;
@@ -662,7 +544,7 @@ __global__ __launch_bounds__(kBlock) void k_init_free(uint32_t *free_slots, Coun
         c->ended.v = 0;
         c->shared.v = 0;
         c->last_shadow = 0;
-        c->tot_shaded = c->tot_direct = c->tot_shadow = c->tot_cont = c->tot_iterations = c->tot_pushes = c->tot_ended = c->tot_shared = 0;
+        c->tot_shaded = c->tot_direct = c->tot_shadow = c->tot_cont = c->tot_iterations = c->tot_pushes = c->tot_ended = c->tot_shared = c->tot_pc_samples = c->tot_pc_rays = 0;
     }
 }
 
@@ -843,6 +725,332 @@ MCPT_DI bool direct_is_zero(const DevScene &S, const MaterialRec &m, f3 q, f3 n,
     if (!(rl > 0.5f && rl < 2.0f)) return false;
     const float cos_a = dot(r, L) / (rl * D);
     return cos_a < (cl * cm - sl * sm) - slack;
+}
+
+// ------------------------------------------------------------------------------------------------
+// New samples: what follows the camera ray (k_primary, k_primary_retrace)
+// ------------------------------------------------------------------------------------------------
+// block_alloc for per-lane counts of 0..3: the lane gets cnt[k] consecutive entries of counter k, index[k] is the first.  Two ballots per
+// request (bit 0, bit 1), one where the caller says that the count is 0 or 1 (two_bits[k] false, a literal: the branch folds).
+template <int N>
+MCPT_DI void block_alloc_counts(BlockAllocShared &sh, const uint32_t (&cnt)[N], const bool (&two_bits)[N], uint32_t *const (&counter)[N],
+                                uint32_t (&index)[N]) {
+    static_assert(N <= kMaxAlloc, "too many allocation requests");
+    const uint32_t n_waves = blockDim.x >> 6;
+    const uint32_t lane = lane_id();
+    const uint32_t wave = threadIdx.x >> 6;
+    uint32_t prefix[N];
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+        const unsigned long long m0 = __ballot((cnt[k] & 1u) != 0u);
+        uint32_t pre = __builtin_amdgcn_mbcnt_hi((uint32_t)(m0 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m0, 0u));
+        uint32_t tot = (uint32_t)__popcll(m0);
+        if (two_bits[k]) {
+            const unsigned long long m1 = __ballot((cnt[k] & 2u) != 0u);
+            pre += 2u * __builtin_amdgcn_mbcnt_hi((uint32_t)(m1 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m1, 0u));
+            tot += 2u * (uint32_t)__popcll(m1);
+        }
+        prefix[k] = pre;
+        if (lane == 0) sh.cnt[wave][k] = tot;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+        if (threadIdx.x == (unsigned)k) {  // lanes 0..N-1 of wave 0 issue their atomics in the same instruction
+            uint32_t total = 0;
+            for (uint32_t w = 0; w < n_waves; ++w) {  // counts -> exclusive prefix over the waves, in place
+                const uint32_t c = sh.cnt[w][k];
+                sh.cnt[w][k] = total;
+                total += c;
+            }
+            sh.base[k] = total ? atomicAdd(counter[k], total) : 0u;
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < N; ++k) index[k] = sh.base[k] + sh.cnt[wave][k] + prefix[k];
+}
+
+// The short path below is compiled out of the checking build and the statistics build: there k_shade lists vertices for k_direct that the
+// regular build skips (need_direct, the marks of the rules), and a first vertex finished here would be missing from those lists.
+#if defined(MCPT_CHECK_DIRECT_SKIP) || defined(MCPT_TRAVERSAL_STATS)
+constexpr bool kPrimaryConductor = false;
+#else
+constexpr bool kPrimaryConductor = true;
+#endif
+
+// A new sample, from its camera ray on (all lanes of the workgroup call it; `valid` lanes hold a sample, `walk`: its closest hit is still to
+// be found, by trace(ray); otherwise `tr` has it):
+//   miss (Scene.cpp:88-95) ............ result[3 channels] = environment, no records
+//   depth-0 emitter (Scene.cpp:102-107)  result[3 channels] = clamp(0,1, emission * |wo.n|), no records
+//   smooth conductor, no direct light .. the short path, see below
+//   any other surface ................. one ray + hit entry, three fresh path records, three clamp-stack slots
+//
+// The short path (RenderConst::primary_conductor).  A first hit on a smooth conductor seen from outside, where direct_is_zero holds for
+// the three channels, is a vertex at which the channel lanes of k_shade do nothing that depends on the channel but one Philox block:
+// mat_sample returns n, mat_fresnel 1, u0[3] < 1 always reflects, no light sample is evaluated, so p2 and wi are functions of (p, n, wo)
+// alone and each channel either ends on roulette with l_dir = kr * 0 or continues along (p2, wi) with its own eval.  All of that is done
+// here, in the lane that owns the sample, with k_shade's expressions: the vertex is set up once instead of three times (the textured
+// floor's double-precision tri_hit included), and the lane walks the reflected ray itself -- the reflections of a pixel's samples are as
+// coherent as its camera rays.  If that ray leaves the scene the surviving channels are finished with the expressions of k_shade's
+// resolve branch; nothing leaves the kernel but three results.  If it hits, the ray and its hit go to a back entry of the ray arrays
+// (k_trace_closest only walks the front) and every surviving channel gets the record k_shade would have written for it: depth 0,
+// kNoDirect, kr, {eval, -1, 0, slot}, with a slot popped from the ring.  The survivors' records are adjacent and name one ray entry, so
+// k_shade's ray sharing goes on applying at the next conductor.  (Seen from inside the conductor rule of direct_is_zero would hold as well;
+// those rare samples take the ordinary path, which keeps l_dir's double-precision form out of this kernel.)
+// The second walk is a second trip through the loop around the ONE trace() call, left early by the waves that have no reflected ray: a
+// second inlined copy of the traversal loop costs the hot kernels 6-8 % (Walk, mcpt_traverse.h).
+// A reflected ray that loses a stack entry (retry flavour) puts its sample on the retrace list like a camera ray that does: nothing of the
+// short path has been written by then, and k_primary_retrace does the whole sample again.
+// Counters: see Counters::pc_samples / pc_rays; the vertices finished here are added to `ended`, the records that ride on a sibling's
+// ray to `shared`, so that every total of mcpt_stats is what k_shade would have made it.
+template <bool kCountPrims, class Trace>
+MCPT_DI void primary_sample(const DevScene &S, const RenderConst &C, const Wave &next, int next_idx, int q, uint32_t s, bool valid, bool walk, f3 pos,
+                            f3 dir, TraceResult tr, BlockAllocShared &sh, const RetryList &rl, Trace trace) {
+    float *const result = q ? C.result[1] : C.result[0];
+    bool go = valid && walk;
+    // Registers: a lane on the short path keeps nothing of its camera ray.  From the end of the first trip on, (pos, dir) are its reflected
+    // ray and, after the second trip, `tr` that ray's hit; what it carries besides is `spx` and, per surviving channel, eval and kr.
+    uint32_t spx = 0;  // bit c: channel c survives roulette at the first vertex; kShort: the sample is on the short path
+    constexpr uint32_t kShort = 8u;
+    float ev[3] = {0.f, 0.f, 0.f}, kr[3] = {0.f, 0.f, 0.f};
+#pragma unroll 1
+    for (int trip = 0; trip < (kPrimaryConductor ? 2 : 1); ++trip) {
+        const Ray r = make_ray(pos, dir);
+        if (go) {
+            tr = trace(r);
+            if (tr.dropped) {  // the sample is finished by k_primary_retrace, from its camera ray on (the scratch stack loses no entry)
+                retry_append(rl, s);
+                valid = false;
+            }
+        }
+        if (trip != 0) break;
+#ifdef MCPT_TRAVERSAL_STATS
+        if (kCountPrims && S.dbg) {  // how many DIFFERENT primitives the 64 primary rays of a wave hit: what a wave-shared (packet) walk would have to visit at least
+            const int myp = (valid && tr.prim >= 0) ? tr.prim : -2;
+            bool first = myp >= 0;
+            for (int l = 0; l < 64; ++l) {
+                const int op = __shfl(myp, l);
+                if ((uint32_t)l < lane_id() && op == myp) first = false;
+            }
+            const unsigned long long m = __ballot(first), mh = __ballot(myp >= 0);
+            if (lane_id() == 0 && mh) {
+                atomicAdd(&S.dbg[14], (unsigned long long)__popcll(m));
+                atomicAdd(&S.dbg[15], 1ull);
+            }
+        }
+#endif
+        go = false;
+        if (kPrimaryConductor && C.primary_conductor && valid && tr.prim >= 0 && !(tr.mat_bits >> 31)) {
+            const MaterialRec &m = S.mats[(int)(tr.mat_bits & kMatIndexMask)];
+            if (m.type == MCPT_SMOOTH_CONDUCTOR) {
+                // ---- vertex set-up: k_shade's (the texture coordinates follow below, for the samples that need them)
+                const f3 p = pos + dir * (float)tr.t;  // Triangle.hpp:245 / Ray.hpp:21; Sphere.hpp:40 (t0 is a float)
+                f3 n;
+                if (tr.prim < S.n_tri) {
+                    const TriShade &ts = S.tri_shade[tr.prim];
+                    n = mk3(ts.n[0], ts.n[1], ts.n[2]);
+                } else {
+                    const SphereRec &sr = S.spheres[tr.prim - S.n_tri];
+                    n = normalized(p - mk3(sr.c[0], sr.c[1], sr.c[2]));
+                }
+                const f3 wo = -dir;
+                // A smooth material's mat_sample is n whatever the two uniforms are (Scene.cpp:109), a conductor's kr is 1 (Scene.cpp:110)
+                // and u0[3] = k / 2^24 with k < 2^24 is below it: isReflect (Scene.cpp:123), always.  So the next ray is one for the channels.
+                // (kr here, in front of every store, with k_shade's arguments: the compiler still knows m.type and folds the call.)
+                const f3 mfn = mat_sample(m, n, 0.f, 0.f);
+#pragma unroll
+                for (int c = 0; c < 3; ++c) kr[c] = mat_fresnel(m, dir, mfn, c);  // Scene.cpp:110
+                const f3 qv = p + n * kEps;          // Scene.cpp:114
+                const bool inside = dot(wo, n) < 0;  // Scene.cpp:115
+                if (!inside && direct_is_zero(S, m, qv, n, wo, inside, 0) && direct_is_zero(S, m, qv, n, wo, inside, 1) &&
+                    direct_is_zero(S, m, qv, n, wo, inside, 2)) {
+                    spx = kShort;
+                    // roulette: the keys of paths 3 s + c differ in the stream (= channel) alone
+                    // (Registers: `s`, the pass parity and the seed go through an empty asm, so that the compiler cannot move what depends on
+                    // neither the hit nor the trip in front of the loop and carry it through the traversal: the pixel's indices and
+                    // addresses, the reciprocal of the pass size, the ten round keys of Philox and the address of the results cost the
+                    // kernel 20 VGPRs.  The seed in a vector register: added to one in a scalar register the round constants would each
+                    // need a vector register, and those are hoisted as well.)
+                    uint32_t s_key = s, seed = C.seed;
+                    int q_key = q;
+                    asm volatile("" : "+v"(s_key), "+v"(seed), "+s"(q_key));
+                    RngKey key;
+                    int ch0;
+                    path_key(C, 3u * s_key, q_key, key, ch0);
+                    key.seed = seed;
+#pragma unroll 1  // (three inlined Philox blocks side by side cost the kernel registers)
+                    for (int c = 0; c < 3; ++c) {
+                        key.stream = (uint32_t)c;
+                        float u0[4];
+                        rng_block(key, 0u, 0u, u0);
+                        if (!(u0[2] >= C.rr_rate)) spx |= 1u << c;  // Scene.cpp:121,129
+                    }
+                    // a channel that ends on roulette: Scene.cpp:129-131 with l_dir = kr * 0 (Scene.cpp:116-119; k_shade's ends_here), returned
+                    // unclamped; depth 0, nothing to unwind.  (Should the reflected ray lose a stack entry, k_primary_retrace writes it again.)
+#pragma unroll
+                    for (int c = 0; c < 3; ++c)
+                        if (!((spx >> c) & 1u)) (q_key ? C.result[1] : C.result[0])[(size_t)s_key * 3 + c] = kr[c] * 0.f;
+                    if (spx & 7u) {
+                        f2 uv{0.f, 0.f};
+                        if (tr.prim < S.n_tri && (tr.mat_bits & kMatTextured)) {  // Triangle.hpp:248
+                            const TriShade &ts = S.tri_shade[tr.prim];
+                            double t3, u, v;
+                            if (tri_hit(S.tri_geom[tr.prim], r, t3, u, v)) {
+                                const float a = (float)(1 - u - v), b = (float)u, c = (float)v;
+                                uv.x = a * ts.t0[0] + b * ts.t1[0] + c * ts.t2[0];
+                                uv.y = a * ts.t0[1] + b * ts.t1[1] + c * ts.t2[1];
+                            }
+                        }
+                        const f3 p2 = (dot(wo, mfn) < 0) ? (p - n * kEps) : (p + n * kEps);  // Scene.cpp:124-128
+                        const f3 wi = mat_reflect(wo, mfn);                                  // Scene.cpp:132
+#pragma unroll
+                        for (int c = 0; c < 3; ++c)
+                            if ((spx >> c) & 1u) ev[c] = mat_eval(m, wi, wo, n, c, uv, true);
+                        pos = p2;
+                        dir = wi;
+                        go = true;
+                    }
+                }
+            }
+        }
+        if (!__any(go)) break;
+    }
+
+    bool surface = false;  // the ordinary path
+    uint32_t n_rec = 0;    // records the short path hands on (the reflected ray hit something)
+    const uint32_t surv = spx & 7u;
+    const bool sp = valid && (spx & kShort);
+    if (sp) {
+        if (surv == 0u) {  // every channel ended on roulette: written at set-up
+        } else if (tr.prim >= 0) {
+            n_rec = (uint32_t)__popc(surv);
+        } else {
+            const f3 env3 = sample_env(S, dir);  // Scene.cpp:145-149 (one look-up: the three channels read the components of one colour)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                if ((surv >> c) & 1u) {
+                    const float l_dir = kr[c] * 0.f;  // Scene.cpp:116-119 with l_dir == 0 (k_shade: the resolve of a kNoDirect record)
+                    const float l_ind = comp(env3, c) * ev[c] * C.inv_rr;
+                    result[(size_t)s * 3 + c] = clampf(0, 15, l_dir) + clampf(0, 5, l_ind);
+                }
+            }
+        }
+    } else if (valid) {
+        if (tr.prim < 0) {
+            const f3 env = sample_env(S, dir);
+            result[(size_t)s * 3 + 0] = env.x;
+            result[(size_t)s * 3 + 1] = env.y;
+            result[(size_t)s * 3 + 2] = env.z;
+        } else {
+            const int mat = (int)(tr.mat_bits & kMatIndexMask);
+            if (tr.mat_bits >> 31) {  // depth-0 emitter, Scene.cpp:102-107
+                const MaterialRec &M = S.mats[mat];
+                f3 n;
+                if (tr.prim < S.n_tri) {
+                    const TriShade ts = S.tri_shade[tr.prim];
+                    n = mk3(ts.n[0], ts.n[1], ts.n[2]);
+                } else {
+                    const SphereRec sr = S.spheres[tr.prim - S.n_tri];
+                    const f3 p = pos + dir * (float)tr.t;
+                    n = normalized(p - mk3(sr.c[0], sr.c[1], sr.c[2]));
+                }
+                const float c = fabsf(dot(-dir, n));
+                result[(size_t)s * 3 + 0] = clampf(0, 1, M.emit[0] * c);
+                result[(size_t)s * 3 + 1] = clampf(0, 1, M.emit[1] * c);
+                result[(size_t)s * 3 + 2] = clampf(0, 1, M.emit[2] * c);
+            } else {
+                surface = true;
+            }
+        }
+    }
+    const uint32_t n_surv = sp ? (uint32_t)__popc(surv) : 0u;
+    const uint32_t n_slots = surface ? 3u : n_rec;
+    // (The four statistics of the short path ride in the workgroup's one round of atomics although nobody takes an index from them: added
+    // once per wave instead, 4 x as many atomics on four addresses, the frame lost 5 % and the other streams' kernels slowed down with it.)
+    const uint32_t cnt[9] = {surface ? 1u : 0u,
+                             n_slots,
+                             C.track_live ? n_slots : 0u,  // that many more unfinished paths of this pass
+                             n_rec,
+                             n_rec ? 1u : 0u,
+                             sp ? 3u - (C.first_fill ? 0u : n_rec) : 0u,          // first vertices shaded here that k_bookkeep does not see as records of list `next`
+                             (C.share_rays && n_surv) ? n_surv - 1u : 0u,         // survivors beyond the first ride on its ray
+                             n_surv ? (C.share_rays ? 1u : n_surv) : 0u,          // (sharing off: counted as a ray each, as k_shade would have stored them)
+                             sp ? 1u : 0u};
+    const bool two_bits[9] = {false, true, true, true, false, true, true, true, false};
+    uint32_t *const ctr[9] = {&C.counters->n_prays[next_idx].v, &C.counters->free_head.v, &C.counters->live[q].v,
+                              &C.counters->n_paths[next_idx].v, &C.counters->n_brays[next_idx].v, &C.counters->ended.v,
+                              &C.counters->shared.v, &C.counters->pc_rays.v, &C.counters->pc_samples.v};
+    uint32_t idx[9];
+    block_alloc_counts<9>(sh, cnt, two_bits, ctr, idx);
+    if (surface) {
+        // the ray is already traced: it goes to the back of the ray arrays, away from the continuation rays that k_shade appends
+        // at the front for k_trace_closest.  The three channel paths get no records: k_shade derives them from the sample entry.
+        const uint32_t k = idx[0], ri = C.ray_cap - 1u - k;
+        next.ray_o[ri] = make_float4(pos.x, pos.y, pos.z, 0.f);
+        next.ray_d[ri] = make_float4(dir.x, dir.y, dir.z, 0.f);
+        next.hit[ri] = pack_hit(tr.t, tr.prim, tr.mat_bits);
+        next.fresh[k] = make_uint2(s | (q ? 0x80000000u : 0u), idx[1]);
+    } else if (n_rec) {
+        // the reflected ray, traced as well: a back entry of its own region, below those of the samples issued in this iteration
+        const uint32_t ri = C.back2_base - idx[4];
+        next.ray_o[ri] = make_float4(pos.x, pos.y, pos.z, 0.f);
+        next.ray_d[ri] = make_float4(dir.x, dir.y, dir.z, 0.f);
+        next.hit[ri] = pack_hit(tr.t, tr.prim, tr.mat_bits);
+        uint32_t j = idx[3], ring = idx[1];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            if ((surv >> c) & 1u) {
+                const uint32_t slot = C.free_slots[ring & C.free_mask];
+                next.rec0[j] = make_uint4(3u * s + (uint32_t)c, ri, kNoDirect | (q ? kPassBit : 0u), __float_as_uint(kr[c]));
+                next.rec1[j] = make_float4(ev[c], -1.f, 0.f, __uint_as_float(slot));
+                ++j;
+                ++ring;
+            }
+        }
+    }
+}
+
+// k_primary: Renderer.cpp:44-79 up to the first Scene::intersect of castRay (Scene.cpp:87) for new samples.
+// The three channel paths of a sample share the primary ray, so it is generated and traced once.
+template <int STK, bool RETRY, bool SMALL>
+__global__ __launch_bounds__(kBlock) void k_primary(DevScene S, CameraConst cam, RenderConst C, Wave next, int next_idx, int q,
+                                                    uint32_t first_sample, uint32_t n_samples, RetryList rl) {
+    __shared__ int32_t stk[STK][kBlock];
+    __shared__ BlockAllocShared sh;
+    if constexpr (SMALL) {
+        __shared__ SmallGeomLds small_geom;
+        stage_small_geom(S, small_geom);
+        __syncthreads();
+    }
+    const int tid = threadIdx.x;
+    const uint32_t j = blockIdx.x * kBlock + tid;
+    const bool valid = j < n_samples;
+    const uint32_t s = first_sample + j;
+    f3 pos = mk3(0, 0, 0), dir = mk3(0, 0, 1);
+    TraceResult tr{DBL_MAX, -1, 0u, false, false};
+    const bool walk = valid && !primary_ray(S, cam, C, q, s, pos, dir, tr);
+    primary_sample<true>(S, C, next, next_idx, q, s, valid, walk, pos, dir, tr, sh, rl,
+                         [&](const Ray &r) { return traverse<false, STK, RETRY, SMALL>(S, r, 0.f, stk, tid); });
+}
+
+// The samples k_primary put on its retrace list: the same, with the scratch stack (a fixed grid strides over the list).
+__global__ __launch_bounds__(kBlock) void k_primary_retrace(DevScene S, CameraConst cam, RenderConst C, Wave next, int next_idx, int q, RetryList rl) {
+    __shared__ int32_t stk[1][kBlock];
+    __shared__ BlockAllocShared sh;
+    const uint32_t n = min(*rl.count, rl.cap);
+    for (uint32_t base = blockIdx.x * kBlock; base < n; base += gridDim.x * kBlock) {  // uniform trip count per workgroup
+        const uint32_t j = base + threadIdx.x;
+        const bool valid = j < n;
+        const uint32_t s = valid ? rl.items[j] : 0u;
+        f3 pos = mk3(0, 0, 0), dir = mk3(0, 0, 1);
+        TraceResult tr{DBL_MAX, -1, 0u, false, false};
+        const bool walk = valid && !primary_ray(S, cam, C, q, s, pos, dir, tr);
+        primary_sample<false>(S, C, next, next_idx, q, s, valid, walk, pos, dir, tr, sh, rl,
+                              [&](const Ray &r) { return traverse_scratch<false>(S, r, 0.f, stk, threadIdx.x); });
+        __syncthreads();  // `sh` is reused by the next round
+    }
+    retry_finish(rl);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1514,11 +1722,14 @@ __global__ void k_bookkeep(Counters *c, int cur_idx, int from_host, uint32_t n_n
         c->last_shadow = n_shadow;
         break;
     }
-    case 1: c->tot_shaded += from_host ? n_next : c->n_paths[nxt].v; break;  // (new samples have no records)
+    // (Records only, not the fresh entries of new samples.  The records k_primary's short path writes into list `nxt` are first vertices
+    // shaded there and are counted here like k_shade's; the first list of a call is never counted here, so for
+    // that one (RenderConst::first_fill) the short path adds them to `ended` itself.)
+    case 1: c->tot_shaded += from_host ? n_next : c->n_paths[nxt].v; break;
     case 2: c->tot_cont += from_host ? n_cont : c->n_rays[nxt].v; break;
     case 3: c->tot_direct += from_host ? n_direct : c->n_direct[nxt].v; break;
     case 4: c->tot_iterations += 1; break;
-    case 8: {  // only k_shade (same stream, already finished) writes these three
+    case 8: {  // only k_shade (same stream, already finished) and this iteration's k_primary (joined before the read-back that precedes this launch) write these
         const uint32_t v = c->ended.v;
         c->ended.v = 0;
         c->tot_ended += v;
@@ -1539,6 +1750,19 @@ __global__ void k_bookkeep(Counters *c, int cur_idx, int from_host, uint32_t n_n
     case 5: c->n_paths[cur_idx].v = 0; break;
     case 6: c->n_rays[cur_idx].v = 0; break;
     case 10: c->n_prays[cur_idx].v = 0; break;
+    case 12: c->n_brays[cur_idx].v = 0; break;
+    case 13: {
+        const uint32_t v = c->pc_samples.v;
+        c->pc_samples.v = 0;
+        c->tot_pc_samples += v;
+        break;
+    }
+    case 14: {
+        const uint32_t v = c->pc_rays.v;
+        c->pc_rays.v = 0;
+        c->tot_pc_rays += v;
+        break;
+    }
     case 7: c->n_direct[cur_idx].v = 0; break;
     default: break;
     }

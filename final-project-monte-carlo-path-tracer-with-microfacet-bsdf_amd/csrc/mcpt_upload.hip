@@ -22,6 +22,7 @@ void Knobs::read() {
     sky_cull = !off("MCPT_SKY_CULL");
     small_scene = !off("MCPT_SMALL_SCENE");
     share_rays = !off("MCPT_SHARE_RAYS");
+    primary_conductor = !off("MCPT_PRIMARY_CONDUCTOR");
     const char *v;
     if ((v = std::getenv("MCPT_POOLS"))) pools = (v[0] == '2') ? 2 : 1;
     if ((v = std::getenv("MCPT_DRAIN_BATCH"))) drain_batch = std::max(1, std::atoi(v));
@@ -801,6 +802,13 @@ int mcpt_scene_ray_counts(const mcpt_scene *sc, uint64_t *traced, uint64_t *shar
     if (!sc || !traced || !shared) return fail(MCPT_ERR_ARG, "mcpt_scene_ray_counts: null argument");
     *traced = sc->last_cont_traced;
     *shared = sc->last_cont_shared;
+    return MCPT_OK;
+}
+
+int mcpt_scene_primary_conductor_counts(const mcpt_scene *sc, uint64_t *samples, uint64_t *rays) {
+    if (!sc || !samples || !rays) return fail(MCPT_ERR_ARG, "mcpt_scene_primary_conductor_counts: null argument");
+    *samples = sc->last_pc_samples;
+    *rays = sc->last_pc_rays;
     return MCPT_OK;
 }
 

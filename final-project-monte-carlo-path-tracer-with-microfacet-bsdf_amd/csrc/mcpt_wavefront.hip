@@ -133,6 +133,7 @@ int run_wavefront(mcpt_scene *sc, PoolCtx &ctx, const RenderConst &C0, const Cam
     C.track_live = (acc && P > 1) ? 1 : 0;
     const Knobs &K = sc->knobs;
     C.share_rays = K.share_rays ? 1 : 0;
+    C.primary_conductor = (K.primary_conductor && C.mode == 0) ? 1 : 0;
     launch_init_free(w.free_slots.p, w.counters.p, pool, K.ring_start, w.free_ring - 1u, st);
     if (ctx.side[1].s) {  // fork: the side streams start after everything queued on `st` so far (counters, pixel list, framebuffer)
         HIP_TRY(hipEventRecord(ctx.book, st));
@@ -164,8 +165,15 @@ int run_wavefront(mcpt_scene *sc, PoolCtx &ctx, const RenderConst &C0, const Cam
         C.s_pass_shift[pi & 1] = sh;
     };
     // issues up to `room` new samples from the passes that may be in flight; returns how many
+    // Room in list `nxt` for the short path of k_primary (first hits on smooth conductors).  A sample still yields at most three records and
+    // three slots, so the callers' checks ((pool - n_cur_max) / 3, free_known / 3) hold as they are.  Ray entries: a sample takes ONE back
+    // entry, either among the first `room` (its camera ray, indexed by n_prays) or among the `room` below them (the reflected ray it traced
+    // itself, indexed by n_brays from back2_base down); k_shade's continuation rays fill the front, at most one per lane, n_cur_max in all.
+    // n_cur_max + 2 room <= n_cur_max + 2 (pool - n_cur_max) / 3 <= pool < ray_cap = pool + pool / 3 + 64 (the prologue: 2 pool / 3).
     auto issue = [&](Wave nx, int nxt, uint32_t room) -> uint32_t {
         uint32_t total = 0;
+        C.back2_base = C.ray_cap - 1u - room;
+        C.first_fill = it == 0 ? 1 : 0;
         while (room > 0 && issue_pass < P && (!acc || issue_pass < accum_next + 2)) {
             if (issued == 0) set_pass_consts(issue_pass);
             const uint32_t g = std::min<uint32_t>(room, plan[issue_pass].n_work - issued);
@@ -344,8 +352,11 @@ int run_wavefront(mcpt_scene *sc, PoolCtx &ctx, const RenderConst &C0, const Cam
     tot.shaded += hc.tot_shaded + hc.tot_ended + hc.ended.v;
     tot.direct += hc.tot_direct;
     const uint64_t shared = hc.tot_shared + hc.shared.v;
-    tot.closest += hc.tot_cont + shared;  // resolved rays: the counts do not depend on how many of them shared a ray
-    tot.cont_traced += hc.tot_cont;
+    const uint64_t pc_rays = hc.tot_pc_rays + hc.pc_rays.v;  // reflected rays k_primary walked itself (they never enter k_trace_closest's queue)
+    tot.closest += hc.tot_cont + shared + pc_rays;  // resolved rays: the counts do not depend on how many of them shared a ray, nor on which kernel walked them
+    tot.cont_traced += hc.tot_cont + pc_rays;
+    tot.pc_samples += hc.tot_pc_samples + hc.pc_samples.v;
+    tot.pc_rays += pc_rays;
     tot.cont_shared += shared;
     tot.shadow += hc.tot_shadow;
     for (uint32_t k = 0; k < kShadowShards; ++k) tot.shadow += hc.n_shadow[0][k].v + hc.n_shadow[1][k].v + hc.n_shadow_w[0][k].v + hc.n_shadow_w[1][k].v;
@@ -569,6 +580,13 @@ int render_list(mcpt_scene *sc, const CameraConst &cc, const mcpt_params &p, con
             shared += tot[k].cont_shared;
         }
         std::fprintf(stderr, "[mcpt render] continuation rays: %llu traced, %llu shared with a sibling's\n", (unsigned long long)traced, (unsigned long long)shared);
+        uint64_t pcs = 0, pcr = 0;
+        for (int k = 0; k < n_pools; ++k) {
+            pcs += tot[k].pc_samples;
+            pcr += tot[k].pc_rays;
+        }
+        std::fprintf(stderr, "[mcpt render] first hits on smooth conductors finished or handed on by k_primary: %llu samples, %llu reflected rays traced there\n",
+                     (unsigned long long)pcs, (unsigned long long)pcr);
     }
     return MCPT_OK;
 }

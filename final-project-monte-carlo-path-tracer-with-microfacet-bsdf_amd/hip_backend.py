@@ -33,7 +33,7 @@ EXPORTS = ["mcpt_scene_create", "mcpt_scene_destroy", "mcpt_render", "mcpt_rende
            "mcpt_temporal_accumulate_moments", "mcpt_moments_variance", "mcpt_sequence_create_moments", "mcpt_sequence_moments",
            "mcpt_centre_rays", "mcpt_render_aovs_features", "mcpt_render_motion_features", "mcpt_sequence_create_features",
            "mcpt_denoise_feedback", "mcpt_sequence_create_feedback", "mcpt_sequence_history",
-           "mcpt_scene_ray_counts",
+           "mcpt_scene_ray_counts", "mcpt_scene_primary_conductor_counts",
            "mcpt_group_create", "mcpt_group_render", "mcpt_group_size", "mcpt_group_get_info", "mcpt_group_scene", "mcpt_group_destroy", "mcpt_group_last_error",
            "mcpt_last_error", "mcpt_version"]
 
@@ -342,6 +342,8 @@ def lib(path=None):
         L.mcpt_scene_get_info.argtypes = [C.c_void_p, C.POINTER(SceneInfo)]
         L.mcpt_scene_ray_counts.restype = C.c_int
         L.mcpt_scene_ray_counts.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.mcpt_scene_primary_conductor_counts.restype = C.c_int
+        L.mcpt_scene_primary_conductor_counts.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.mcpt_bvh_dump.restype = C.c_int
         L.mcpt_bvh_dump.argtypes = [C.POINTER(SceneDesc), C.POINTER(BvhInfo), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.mcpt_render.restype = C.c_int
@@ -675,6 +677,12 @@ class HipScene:
         t, s = C.c_uint64(0), C.c_uint64(0)
         _check(self.L.mcpt_scene_ray_counts(self.h, C.byref(t), C.byref(s)), L=self.L)
         return int(t.value), int(s.value)
+
+    def primary_conductor_counts(self):
+        """mcpt_scene_primary_conductor_counts: (samples, rays) of the primary kernel's short path in the last render call."""
+        n, r = C.c_uint64(0), C.c_uint64(0)
+        _check(self.L.mcpt_scene_primary_conductor_counts(self.h, C.byref(n), C.byref(r)), L=self.L)
+        return int(n.value), int(r.value)
 
     def params(self, spp=None, seed=1, spp_total=0, sample_offset=0, accumulate=0, tile_size=32, rank=0, nranks=1,
                n_dir_sample=None, spp_per_pass=0, pool_paths=0, max_depth=0):

@@ -1035,6 +1035,13 @@ int mcpt_scene_get_info(const mcpt_scene *scene, mcpt_scene_info *info);
  * splits depends on the schedule (pool size, pass size, ranks).  Zero before the first call. */
 int mcpt_scene_ray_counts(const mcpt_scene *scene, uint64_t *traced, uint64_t *shared);
 
+/* First hits on smooth conductors that the primary-ray kernel finished itself in the scene's last frame-level render call (DESIGN.md
+ * section 6; MCPT_PRIMARY_CONDUCTOR=0 switches it off): `samples` took that path -- their three channel paths were finished in the
+ * kernel or handed on as ordinary records --, and `rays` of the `traced` count of mcpt_scene_ray_counts are reflected rays that kernel
+ * walked itself, one per sample with a surviving channel, so traced - rays is what the closest-hit queue kernel walked.  (With
+ * MCPT_SHARE_RAYS=0 `rays` counts one per surviving channel, as if each had stored its own.)  Zero before the first call. */
+int mcpt_scene_primary_conductor_counts(const mcpt_scene *scene, uint64_t *samples, uint64_t *rays);
+
 /* Host-only diagnostic (no GPU needed): builds the traversal tree of `desc` exactly as mcpt_scene_create does and copies it
  * out, so that the builder (the data producer of BVHAccel::recursiveBuild, BVH.cpp:27-93) can be checked on any machine.
  * Call with boxes == NULL to get the counts, then with arrays of n_nodes entries:
