@@ -1,7 +1,7 @@
 // The host layer behind the C ABI (include/mcpt.h): error plumbing, the owners of device resources, the wavefront workspace, the
 // environment knobs, the event timer, struct mcpt_scene, and what its translation units call in each other:
 //   mcpt_wavefront.hip  the wavefront loop, workspace / pass sizing (render_list), the pixel list and sky cull set-up
-//   mcpt_upload.hip     scene create / upload / update / snapshot / destroy / info, the BVH dumps
+//   mcpt_upload.hip     scene create / upload / update / material and environment edits / snapshot / destroy / info, the BVH dumps
 //   mcpt_update.hip     the kernels that move and deform objects in HBM (the device path of mcpt_scene_update / mcpt_scene_deform),
 //                       mcpt_transform_triangles, mcpt_deform_triangles
 //   mcpt_render.hip     the frame-level entry points (render, adaptive, AOVs, denoise, motion, temporal blend); mcpt_frame.h has what
@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "mcpt_kernels.h"
+#include "mcpt_material.h"
 
 namespace mcpt {
 
@@ -354,6 +355,8 @@ struct SceneSource {
     std::vector<uint8_t> moved;  // per object: 1 once it has been given a transform
     std::vector<float> xf;       // per object: its row-major 3x4 matrix (unused while moved == 0)
     BuildChoice choice;          // the builder and its options as resolved at creation
+    std::vector<float> env;      // the environment map (meta.env_w x env_h x 3; empty: the constant background), the way back of
+                                 // mcpt_group_set_environment
 };
 
 // One run of lanes of the update kernel (csrc/mcpt_update.hip): the triangles of a moved mesh, or one moved sphere.
@@ -386,6 +389,10 @@ static_assert(sizeof(DeformSeg) == 80, "DeformSeg must be 80 bytes");
 // for it.  *flag (zeroed by the caller) becomes 1 when a position is not finite; such a lane writes nothing else.
 void launch_deform_objects(const DeformSeg *d_segs, int32_t n_segs, int32_t n_lanes, const mcpt_triangle *tris0, mcpt_triangle *base, mcpt_triangle *tris_cur,
                            TriGeom *tri_geom, TriShade *tri_shade, uint32_t *flag, hipStream_t s);
+// Writes, for every lane of the listed segments (mat::MatSeg, csrc/mcpt_material.h), the segment's mat_bits and mat into the TriGeom /
+// TriShade records of its triangle, or into its SphereRec; nothing else in the records is read or written.
+void launch_set_materials(const mat::MatSeg *d_segs, int32_t n_segs, int32_t n_lanes, TriGeom *tri_geom, TriShade *tri_shade, SphereRec *spheres,
+                          hipStream_t s);
 
 }  // namespace mcpt
 
@@ -412,6 +419,7 @@ struct mcpt_scene {
     mcpt::DevBuf<mcpt::DeformSeg> dsegs; // the deformation kernel's segment table,
     mcpt::DevBuf<float> stage;           // its staging buffer for host positions (36 B per triangle, grows to the largest call)
     mcpt::DevBuf<uint32_t> dflag;        // and its flag word (a position that is not finite)
+    mcpt::DevBuf<mcpt::mat::MatSeg> msegs;  // the segment table of k_set_materials
     mcpt::DevBuf<mcpt::MaterialRec> mats;
     mcpt::DevBuf<mcpt::InstRec> inst;
     mcpt::DevBuf<float> env;
@@ -467,6 +475,13 @@ int check_deform(const mcpt_scene *sc, int32_t n, const mcpt_object_vertices *it
 // The argument checks of mcpt_scene_update, before any device call; fills the table the scene would have afterwards.
 int check_moves(const mcpt_scene *sc, int32_t n, const mcpt_object_transform *moves, std::vector<uint8_t> &moved, std::vector<float> &xf,
                 std::vector<int32_t> &touched);
+// mcpt_scene_set_materials in two halves, as above: the checks before any device call (which fill the plan), and the edit itself.  Also the
+// way back for mcpt_group_set_materials when another replica fails.
+int check_material_edit(const mcpt_scene *sc, int32_t n_edits, const mcpt_material_edit *edits, int32_t n_assign, const mcpt_object_material *assign,
+                        mat::EditPlan &plan);
+int apply_material_edit(mcpt_scene *sc, const mat::EditPlan &plan, mcpt_update_info *info);
+int check_environment(const mcpt_scene *sc, const float *background, int32_t env_w, int32_t env_h, const float *env_pixels);
+int apply_environment(mcpt_scene *sc, const float *background, int32_t env_w, int32_t env_h, const float *env_pixels, mcpt_update_info *info);
 double warm_up_device(int device);
 
 // ---- mcpt_wavefront.hip

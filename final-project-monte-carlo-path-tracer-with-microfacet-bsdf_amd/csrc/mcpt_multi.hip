@@ -80,6 +80,38 @@ int gfail(int code, const std::string &msg) {
     return code;
 }
 
+// `apply(scene)` on every replica, one host thread per replica.  If a replica fails, `undo(scene)` runs on the replicas that had changed,
+// so that the group stays one scene, and the first failure is reported under `name`.
+template <typename Apply, typename Undo>
+int on_replicas(mcpt_group *g, const char *name, Apply apply, Undo undo) {
+    const int N = (int)g->scenes.size();
+    std::vector<int> rc((size_t)N, MCPT_OK);
+    std::vector<std::string> err((size_t)N);
+    auto run = [&](auto &f, const std::vector<int> &which) {
+        auto work = [&](int i) {
+            rc[(size_t)i] = f(g->scenes[(size_t)i]);
+            if (rc[(size_t)i] != MCPT_OK) err[(size_t)i] = mcpt_last_error();
+        };
+        std::vector<std::thread> th;
+        for (size_t k = 1; k < which.size(); ++k) th.emplace_back(work, which[k]);
+        if (!which.empty()) work(which[0]);
+        for (std::thread &t : th) t.join();
+    };
+    std::vector<int> all, done;
+    for (int i = 0; i < N; ++i) all.push_back(i);
+    run(apply, all);
+    int bad = -1;
+    for (int i = 0; i < N; ++i) {
+        if (rc[(size_t)i] == MCPT_OK) done.push_back(i);
+        else if (bad < 0) bad = i;
+    }
+    if (bad < 0) return MCPT_OK;
+    const int code = rc[(size_t)bad];
+    const std::string e = std::string(name) + ": device " + std::to_string(g->devices[(size_t)bad]) + ": " + err[(size_t)bad];
+    run(undo, done);
+    return gfail(code, e);
+}
+
 }  // namespace
 
 extern "C" {
@@ -285,6 +317,36 @@ int mcpt_group_deform(mcpt_group *g, int32_t n, const mcpt_object_vertices *item
     const std::string e = "mcpt_group_deform: device " + std::to_string(g->devices[(size_t)bad]) + ": " + err[(size_t)bad];
     run(old_items.data(), done);  // the replicas that had deformed go back: the group stays one scene
     return gfail(code, e);
+}
+
+int mcpt_group_set_materials(mcpt_group *g, int32_t n_edits, const mcpt_material_edit *edits, int32_t n_assign, const mcpt_object_material *assign) {
+    if (!g || g->scenes.empty()) return gfail(MCPT_ERR_ARG, "mcpt_group_set_materials: null group");
+    // every replica holds the same description: one check and one plan, before any device call
+    mat::EditPlan plan, back;
+    const int rc0 = check_material_edit(g->scenes[0], n_edits, edits, n_assign, assign, plan);
+    if (rc0 != MCPT_OK) return gfail(rc0, std::string("mcpt_group_set_materials: ") + mcpt_last_error());
+    // the way back: the entries and the assignments the listed materials and objects have now (a plan over the edited description)
+    std::vector<mcpt_material_edit> old_edits((size_t)n_edits);
+    std::vector<mcpt_object_material> old_assign((size_t)n_assign);
+    const SceneSource &S = g->scenes[0]->src;
+    for (int32_t i = 0; i < n_edits; ++i) old_edits[(size_t)i] = {edits[i].index, S.materials[(size_t)edits[i].index]};
+    for (int32_t i = 0; i < n_assign; ++i) old_assign[(size_t)i] = {assign[i].object, S.objects[(size_t)assign[i].object].material};
+    std::string err;
+    if (mat::plan_edit(plan.materials, plan.objects, n_edits, old_edits.data(), n_assign, old_assign.data(), back, err) != MCPT_OK)
+        return gfail(MCPT_ERR_ARG, "mcpt_group_set_materials: " + err);
+    return on_replicas(g, "mcpt_group_set_materials", [&](mcpt_scene *sc) { return apply_material_edit(sc, plan, nullptr); },
+                       [&](mcpt_scene *sc) { return apply_material_edit(sc, back, nullptr); });
+}
+
+int mcpt_group_set_environment(mcpt_group *g, const float background[3], int32_t env_w, int32_t env_h, const float *env_pixels) {
+    if (!g || g->scenes.empty()) return gfail(MCPT_ERR_ARG, "mcpt_group_set_environment: null group");
+    const int rc0 = check_environment(g->scenes[0], background, env_w, env_h, env_pixels);
+    if (rc0 != MCPT_OK) return gfail(rc0, std::string("mcpt_group_set_environment: ") + mcpt_last_error());
+    // the way back: the scene's own copy of what it shows now
+    const std::vector<float> old_env = g->scenes[0]->src.env;
+    const SceneMeta old = g->scenes[0]->meta;
+    return on_replicas(g, "mcpt_group_set_environment", [&](mcpt_scene *sc) { return apply_environment(sc, background, env_w, env_h, env_pixels, nullptr); },
+                       [&](mcpt_scene *sc) { return apply_environment(sc, old.background, old.env_w, old.env_h, old_env.empty() ? nullptr : old_env.data(), nullptr); });
 }
 
 int mcpt_group_get_info(const mcpt_group *g, mcpt_group_info *info) {

@@ -19,6 +19,7 @@
 #include <chrono>
 
 #include "mcpt_internal.h"
+#include "mcpt_material.h"
 #include "mcpt_move.h"
 
 namespace mcpt {
@@ -573,26 +574,7 @@ int build_host_scene(const mcpt_scene_desc &d, HostScene &hs, const char **err, 
             *err = "material type out of range";
             return MCPT_ERR_ARG;
         }
-        MaterialRec &r = hs.materials[i];
-        std::memset(&r, 0, sizeof r);
-        r.type = m.type;
-        r.textured = m.textured ? 1 : 0;
-        r.isDirac = (m.type == MCPT_SMOOTH_CONDUCTOR || m.type == MCPT_SMOOTH_DIELECTRIC);
-        r.roughness = m.roughness;
-        r.iorA = m.iorA;
-        r.iorB = m.iorB;
-        for (int k = 0; k < 3; ++k) {
-            r.refl[k] = m.base_reflectance[k];
-            r.emit[k] = m.emission[k];
-        }
-        const V3 e = ld(m.emission);
-        r.hasEmission = sqrtf(dot3(e, e)) > kEps;  // Material::hasEmission, Material.hpp:262
-        const float wavelen[3] = {0.700f, 0.5461f, 0.4358f};  // WaveLen.hpp:7-18
-        for (int k = 0; k < 3; ++k) {
-            const float wl = wavelen[k];
-            r.ior[k] = m.iorA + m.iorB / (wl * wl);          // Material.hpp:178-183
-            r.inv_ior[k] = (float)(1. / (double)r.ior[k]);   // Material.hpp:299 `1. / ior`
-        }
+        mat::make_record(m, hs.materials[i]);  // (shared with mcpt_scene_set_materials: csrc/mcpt_material.h)
     }
 
     hs.tri_geom.resize(d.n_triangles);

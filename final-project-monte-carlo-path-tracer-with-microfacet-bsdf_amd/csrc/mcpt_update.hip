@@ -1,4 +1,5 @@
-// Moving and deforming objects in a live scene (include/mcpt.h: mcpt_scene_update, mcpt_scene_deform): the kernels of the device path
+// Moving and deforming objects in a live scene (include/mcpt.h: mcpt_scene_update, mcpt_scene_deform): the kernels of the device path,
+// the kernel that rewrites the material words of primitives (mcpt_scene_set_materials),
 // and the host helpers mcpt_transform_triangles and mcpt_deform_triangles.  The scene-level part (argument checks, the two paths, the swap of the new arrays) is beside
 // mcpt_scene_create in csrc/mcpt_upload.hip; the arithmetic is csrc/mcpt_move.h, shared with the scene builder.
 #include <cmath>
@@ -102,6 +103,35 @@ __global__ __launch_bounds__(kB) void k_deform_objects(const DeformSeg *__restri
     write_triangle(t, ti, tris_cur, tri_geom, tri_shade);
 }
 
+// One lane per primitive whose material words change (mcpt_scene_set_materials, path 2): the triangles of the affected meshes and one lane
+// per affected sphere.  The lane finds its segment by the bisection of k_move_objects and stores the segment's two words: single dword
+// stores, so that everything else in the records stays bit for bit without being read (a 16-byte quarter would need a load, a wait and
+// four times the bytes for the same number of store instructions).
+__global__ __launch_bounds__(kB) void k_set_materials(const mat::MatSeg *__restrict__ segs, int32_t n_segs, int32_t n_lanes, TriGeom *__restrict__ tri_geom,
+                                                       TriShade *__restrict__ tri_shade, SphereRec *__restrict__ spheres) {
+    const int32_t lane = (int32_t)(blockIdx.x * kB + threadIdx.x);
+    if (lane >= n_lanes) return;
+    int32_t lo = 0, hi = n_segs - 1;  // the last segment whose first_lane <= lane
+    while (lo < hi) {
+        const int32_t mid = (lo + hi + 1) >> 1;
+        if (segs[mid].first_lane <= lane) lo = mid;
+        else hi = mid - 1;
+    }
+    const uint4 a = *reinterpret_cast<const uint4 *>(segs + lo);        // {first_lane, count, first_tri, object}
+    const uint2 b = *(reinterpret_cast<const uint2 *>(segs + lo) + 2);  // {mat_bits, mat}
+    const int32_t k = lane - (int32_t)a.x;
+    if (k >= (int32_t)a.y) return;  // (never for a table whose segments tile the lanes)
+    if ((int32_t)a.z < 0) {
+        SphereRec *rec = spheres + (int32_t)a.w;
+        rec->mat = (int32_t)b.y;
+        rec->mat_bits = b.x;
+        return;
+    }
+    const int32_t ti = (int32_t)a.z + k;
+    tri_geom[ti].mat_bits = b.x;
+    tri_shade[ti].mat = (int32_t)b.y;
+}
+
 }  // namespace
 
 void launch_move_objects(const MoveSeg *d_segs, int32_t n_segs, int32_t n_lanes, const mcpt_triangle *tris0, mcpt_triangle *tris_cur, TriGeom *tri_geom,
@@ -116,6 +146,11 @@ void launch_deform_objects(const DeformSeg *d_segs, int32_t n_segs, int32_t n_la
     if (n_lanes <= 0 || n_segs <= 0) return;
     hipLaunchKernelGGL(k_deform_objects, dim3((uint32_t)((n_lanes + kB - 1) / kB)), dim3(kB), 0, s, d_segs, n_segs, n_lanes, tris0, base, tris_cur, tri_geom,
                        tri_shade, flag);
+}
+
+void launch_set_materials(const mat::MatSeg *d_segs, int32_t n_segs, int32_t n_lanes, TriGeom *tri_geom, TriShade *tri_shade, SphereRec *spheres, hipStream_t s) {
+    if (n_lanes <= 0 || n_segs <= 0) return;
+    hipLaunchKernelGGL(k_set_materials, dim3((uint32_t)((n_lanes + kB - 1) / kB)), dim3(kB), 0, s, d_segs, n_segs, n_lanes, tri_geom, tri_shade, spheres);
 }
 
 }  // namespace mcpt

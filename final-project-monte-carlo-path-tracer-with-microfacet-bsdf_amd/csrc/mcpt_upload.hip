@@ -233,10 +233,7 @@ void fill_view(mcpt_scene *sc) {
                            g.tris.bytes() + sc->sphere_obj.bytes();
 }
 
-bool emits(const mcpt_material &m) {  // Material::hasEmission (Material.hpp:262), as build_host_scene decides it
-    const mv::V3 e = mv::ld(m.emission);
-    return sqrtf(mv::dot3(e, e)) > kEps;
-}
+using mat::emits;  // Material::hasEmission (Material.hpp:262), as build_host_scene decides it
 
 }  // namespace
 
@@ -278,6 +275,7 @@ int mcpt::upload_scene(const mcpt_scene_desc *desc, HostBuild &hb, int device, m
     S.materials.assign(desc->materials, desc->materials + desc->n_materials);
     S.moved.assign((size_t)desc->n_objects, 0);
     S.xf.assign((size_t)desc->n_objects * 12, 0.f);
+    S.env = hs.env;
     if (e == hipSuccess) e = upload(sc->mats, hs.materials);
     if (e == hipSuccess) e = upload(sc->env, hs.env);
     if (e == hipSuccess && !hs.instances.empty()) e = upload(sc->inst, hs.instances);
@@ -355,8 +353,10 @@ int host_positions(const SceneSource &S, int32_t n, const mcpt_object_vertices *
 
 // The rebuild behind mcpt_scene_update and mcpt_scene_deform: the scene gets the transform table (moved, xf) and, when `deform` is given,
 // the listed meshes (touched[i] = deform[i].object) get new base positions.  Everything is built aside and committed on success.
+// `edit` (mcpt_scene_set_materials, path 0): the material table and the objects' material indices of the plan replace the scene's; the
+// host path is taken whatever the builder, and the new material table is uploaded aside with the rest.
 int rebuild(mcpt_scene *sc, const std::vector<uint8_t> &moved, const std::vector<float> &xf, const std::vector<int32_t> &touched,
-            const mcpt_object_vertices *deform, mcpt_update_info *info) {
+            const mcpt_object_vertices *deform, mcpt_update_info *info, const mat::EditPlan *edit = nullptr) {
     const auto t0 = Clock::now();
     mcpt_update_info ui;
     std::memset(&ui, 0, sizeof ui);
@@ -367,7 +367,8 @@ int rebuild(mcpt_scene *sc, const std::vector<uint8_t> &moved, const std::vector
         if (ob.kind == MCPT_OBJ_MESH) ui.n_moved_tris += ob.n_tri;
         emitter = emitter || emits(S.materials[(size_t)ob.material]);
     }
-    if (touched.empty()) {
+    if (edit) ui.n_moved_tris = edit->n_tris;
+    if (touched.empty() && !edit) {
         if (info) *info = ui;
         return MCPT_OK;
     }
@@ -380,7 +381,8 @@ int rebuild(mcpt_scene *sc, const std::vector<uint8_t> &moved, const std::vector
     std::vector<mcpt_triangle> base;          // deformation: the new host copy of the base, swapped with S.triangles on success
     std::vector<std::vector<float>> fetched;  // deformation: positions downloaded from device pointers
     std::vector<const float *> pos;
-    if (meta.builder >= 2 && !emitter) {
+    DevBuf<MaterialRec> mats2;  // material edit: the new table, swapped with sc->mats on success
+    if (meta.builder >= 2 && !emitter && !edit) {
         // ---- device path: the listed triangles and sphere centres are moved in HBM, the device builder runs again
         ui.path = 1;
         const auto tu = Clock::now();
@@ -490,7 +492,8 @@ int rebuild(mcpt_scene *sc, const std::vector<uint8_t> &moved, const std::vector
             for (int32_t k = 0; k < ob.n_tri; ++k) mv::deform_triangle(pos[(size_t)i] + (size_t)k * 9, tris[(size_t)ob.first_tri + k], tris[(size_t)ob.first_tri + k]);
         }
         if (deform) base = tris;
-        std::vector<mcpt_object> objs = S.objects;
+        std::vector<mcpt_object> objs = edit ? edit->objects : S.objects;
+        const std::vector<mcpt_material> &mats = edit ? edit->materials : S.materials;
         for (size_t o = 0; o < objs.size(); ++o) {
             if (!moved[o]) continue;
             const float *m = &xf[o * 12];
@@ -509,15 +512,15 @@ int rebuild(mcpt_scene *sc, const std::vector<uint8_t> &moved, const std::vector
         std::memset(&d, 0, sizeof d);
         d.n_objects = (int32_t)objs.size();
         d.n_triangles = (int32_t)tris.size();
-        d.n_materials = (int32_t)S.materials.size();
+        d.n_materials = (int32_t)mats.size();
         for (int k = 0; k < 3; ++k) d.background[k] = meta.background[k];
         d.objects = objs.data();
         d.triangles = tris.data();
-        d.materials = S.materials.data();
+        d.materials = mats.data();
         HostScene hs;
         const char *err = "";
         int rc = build_host_scene(d, hs, &err, S.choice);
-        if (rc != MCPT_OK) return fail(rc, std::string("mcpt_scene_update: ") + err);
+        if (rc != MCPT_OK) return fail(rc, std::string(edit ? "mcpt_scene_set_materials: " : (deform ? "mcpt_scene_deform: " : "mcpt_scene_update: ")) + err);
         const double host_build_ms = ms_since(tb);
         const auto tu = Clock::now();
         const int32_t env_w = meta.env_w, env_h = meta.env_h;  // (the environment map is not part of desc': it stays where it is)
@@ -530,6 +533,7 @@ int rebuild(mcpt_scene *sc, const std::vector<uint8_t> &moved, const std::vector
         if (rc != MCPT_OK) return rc;
         ui.build_ms = host_build_ms + gpu_build_ms;
         if (deform && hs.builder >= 2) HIP_TRY(upload(base2, base));
+        if (edit) HIP_TRY(upload(mats2, hs.materials));
         ui.upload_ms = ms_since(tu) - gpu_build_ms;
         sc->geom.swap_prims(g2);
         sc->geom.swap_lights(g2);
@@ -545,6 +549,11 @@ int rebuild(mcpt_scene *sc, const std::vector<uint8_t> &moved, const std::vector
         } else {
             S.triangles.swap(base);
         }
+    }
+    if (edit) {  // the material table on the device and the host copy of the description
+        sc->mats.swap(mats2);
+        S.materials = edit->materials;
+        S.objects = edit->objects;
     }
     sc->meta = meta;
     S.moved = moved;
@@ -595,6 +604,85 @@ int mcpt::apply_deform(mcpt_scene *sc, int32_t n, const mcpt_object_vertices *it
     std::vector<int32_t> touched;
     for (int32_t i = 0; i < n; ++i) touched.push_back(items[i].object);
     return rebuild(sc, sc->src.moved, sc->src.xf, touched, n > 0 ? items : nullptr, info);
+}
+
+int mcpt::check_material_edit(const mcpt_scene *sc, int32_t n_edits, const mcpt_material_edit *edits, int32_t n_assign, const mcpt_object_material *assign,
+                              mat::EditPlan &plan) {
+    if (!sc) return fail(MCPT_ERR_ARG, "mcpt_scene_set_materials: null scene");
+    const SceneSource &S = sc->src;
+    std::string err;
+    const int rc = mat::plan_edit(S.materials, S.objects, n_edits, edits, n_assign, assign, plan, err);
+    if (rc != MCPT_OK) return fail(rc, "mcpt_scene_set_materials: " + err);
+    if (S.choice.builder == MCPT_BUILD_SAH && S.choice.instancing == 1)
+        return fail(MCPT_ERR_ARG, "mcpt_scene_set_materials: the scene was built with node instancing on (instanced groups were formed from non-emitting meshes)");
+    return MCPT_OK;
+}
+
+int mcpt::apply_material_edit(mcpt_scene *sc, const mat::EditPlan &plan, mcpt_update_info *info) {
+    SceneSource &S = sc->src;
+    if (!plan.in_place)  // some object starts or stops emitting: the creation code forms the light tables again
+        return rebuild(sc, S.moved, S.xf, {}, nullptr, info, &plan);
+    const auto t0 = Clock::now();
+    mcpt_update_info ui;
+    std::memset(&ui, 0, sizeof ui);
+    ui.path = 2;
+    ui.n_moved_tris = plan.n_tris;
+    if (plan.mat_hi > plan.mat_lo || plan.n_lanes > 0 || !plan.lights.empty()) {
+        HIP_TRY(hipSetDevice(sc->device));
+        // the segment table first: after it nothing allocates, so only a failing copy or launch can leave the call half done
+        if (plan.n_lanes > 0) HIP_TRY(upload(sc->msegs, plan.segs));
+        if (plan.mat_hi > plan.mat_lo) {  // one copy of the span of the table that holds the listed entries
+            std::vector<MaterialRec> recs((size_t)(plan.mat_hi - plan.mat_lo));
+            for (int32_t i = plan.mat_lo; i < plan.mat_hi; ++i) mat::make_record(plan.materials[(size_t)i], recs[(size_t)(i - plan.mat_lo)]);
+            HIP_TRY(hipMemcpy(sc->mats.p + plan.mat_lo, recs.data(), recs.size() * sizeof(MaterialRec), hipMemcpyHostToDevice));
+        }
+        for (const mat::EditPlan::LightMat &l : plan.lights)
+            HIP_TRY(hipMemcpy(&sc->geom.lights.p[l.light].mat, &l.mat, sizeof(int32_t), hipMemcpyHostToDevice));
+        if (plan.n_lanes > 0) {
+            launch_set_materials(sc->msegs.p, (int32_t)plan.segs.size(), plan.n_lanes, sc->geom.tri_geom.p, sc->geom.tri_shade.p, sc->geom.spheres.p, nullptr);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipStreamSynchronize(nullptr));
+        }
+    }
+    S.materials = plan.materials;
+    S.objects = plan.objects;
+    ui.transform_ms = ui.total_ms = ms_since(t0);
+    if (info) *info = ui;
+    return MCPT_OK;
+}
+
+int mcpt::check_environment(const mcpt_scene *sc, const float *background, int32_t env_w, int32_t env_h, const float *env_pixels) {
+    if (!sc) return fail(MCPT_ERR_ARG, "mcpt_scene_set_environment: null scene");
+    if (!background) return fail(MCPT_ERR_ARG, "mcpt_scene_set_environment: null background");
+    if (env_pixels ? !(env_w > 0 && env_h > 0) : !(env_w == 0 && env_h == 0))
+        return fail(MCPT_ERR_ARG, "mcpt_scene_set_environment: env_w and env_h are both positive with a map and both zero without one");
+    for (int k = 0; k < 3; ++k)
+        if (!std::isfinite(background[k])) return fail(MCPT_ERR_ARG, "mcpt_scene_set_environment: a background value is not finite");
+    const size_t n = (size_t)env_w * (size_t)env_h * 3;
+    for (size_t i = 0; i < n; ++i)
+        if (!std::isfinite(env_pixels[i])) return fail(MCPT_ERR_ARG, "mcpt_scene_set_environment: a map value is not finite");
+    return MCPT_OK;
+}
+
+int mcpt::apply_environment(mcpt_scene *sc, const float *background, int32_t env_w, int32_t env_h, const float *env_pixels, mcpt_update_info *info) {
+    const auto t0 = Clock::now();
+    mcpt_update_info ui;
+    std::memset(&ui, 0, sizeof ui);
+    ui.path = 2;
+    HIP_TRY(hipSetDevice(sc->device));
+    const size_t n = (size_t)env_w * (size_t)env_h * 3;
+    std::vector<float> host(env_pixels, env_pixels + n);  // (first: the last thing that can fail is the upload)
+    DevBuf<float> env2;  // aside; swapped in on success
+    HIP_TRY(upload(env2, env_pixels, n));
+    sc->env.swap(env2);
+    sc->src.env.swap(host);
+    for (int k = 0; k < 3; ++k) sc->meta.background[k] = background[k];
+    sc->meta.env_w = env_w;
+    sc->meta.env_h = env_h;
+    fill_view(sc);
+    ui.upload_ms = ui.total_ms = ms_since(t0);
+    if (info) *info = ui;
+    return MCPT_OK;
 }
 
 // The layout of mcpt_bvh_dump / mcpt_scene_dump_bvh: per node 12 floats {lmin, lmax, rmin, rmax}, two child references and (qn != nullptr) the
@@ -666,6 +754,20 @@ int mcpt_scene_deform(mcpt_scene *sc, int32_t n, const mcpt_object_vertices *ite
     const int rc = check_deform(sc, n, items);
     if (rc != MCPT_OK) return rc;
     return apply_deform(sc, n, items, info);
+}
+
+int mcpt_scene_set_materials(mcpt_scene *sc, int32_t n_edits, const mcpt_material_edit *edits, int32_t n_assign, const mcpt_object_material *assign,
+                             mcpt_update_info *info) {
+    mat::EditPlan plan;
+    const int rc = check_material_edit(sc, n_edits, edits, n_assign, assign, plan);
+    if (rc != MCPT_OK) return rc;
+    return apply_material_edit(sc, plan, info);
+}
+
+int mcpt_scene_set_environment(mcpt_scene *sc, const float background[3], int32_t env_w, int32_t env_h, const float *env_pixels, mcpt_update_info *info) {
+    const int rc = check_environment(sc, background, env_w, env_h, env_pixels);
+    if (rc != MCPT_OK) return rc;
+    return apply_environment(sc, background, env_w, env_h, env_pixels, info);
 }
 
 int mcpt_scene_snapshot(mcpt_scene *sc) {

@@ -21,6 +21,7 @@ EXPORTS = ["mcpt_scene_create", "mcpt_scene_destroy", "mcpt_render", "mcpt_rende
            "mcpt_cull_bound", "mcpt_debug_classify",
            "mcpt_scene_update", "mcpt_group_update", "mcpt_transform_triangles",
            "mcpt_scene_deform", "mcpt_group_deform", "mcpt_deform_triangles",
+           "mcpt_scene_set_materials", "mcpt_scene_set_environment", "mcpt_group_set_materials", "mcpt_group_set_environment",
            "mcpt_scene_snapshot", "mcpt_render_motion", "mcpt_temporal_blend", "mcpt_temporal_accumulate",
            "mcpt_temporal_accumulate_ex",
            "mcpt_sequence_create", "mcpt_sequence_frame", "mcpt_sequence_reset", "mcpt_sequence_destroy",
@@ -212,7 +213,52 @@ class UpdateInfo(C.Structure):
                 ("upload_ms", C.c_double), ("total_ms", C.c_double), ("reserved", C.c_int32 * 4)]
 
     def as_dict(self):
+        """path 0: host rebuild, 1: device rebuild, 2: in place (set_materials / set_environment)."""
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
+class Material(C.Structure):
+    _fields_ = [("type", C.c_int32), ("textured", C.c_int32), ("roughness", C.c_float), ("iorA", C.c_float), ("iorB", C.c_float),
+                ("base_reflectance", C.c_float * 3), ("emission", C.c_float * 3)]
+
+
+class MaterialEdit(C.Structure):
+    _fields_ = [("index", C.c_int32), ("material", Material)]
+
+
+class ObjectMaterial(C.Structure):
+    _fields_ = [("object", C.c_int32), ("material", C.c_int32)]
+
+
+assert C.sizeof(Material) == 44 and C.sizeof(MaterialEdit) == 48 and C.sizeof(ObjectMaterial) == 8
+
+
+def _material_lists(edits, assign):
+    """edits: an iterable of (material index, material), a material being one record of scenes.MAT_DTYPE (or anything with its fields);
+    assign: an iterable of (object index, material index).  -> (mcpt_material_edit array, n, mcpt_object_material array, n)."""
+    edits, assign = list(edits), list(assign)
+    ea, aa = (MaterialEdit * max(len(edits), 1))(), (ObjectMaterial * max(len(assign), 1))()
+    for k, (idx, m) in enumerate(edits):
+        ea[k].index = int(idx)
+        mm = ea[k].material
+        mm.type, mm.textured = int(m["type"]), int(m["textured"])
+        mm.roughness, mm.iorA, mm.iorB = float(m["roughness"]), float(m["iorA"]), float(m["iorB"])
+        mm.base_reflectance = (C.c_float * 3)(*[float(x) for x in np.asarray(m["base_reflectance"]).reshape(3)])
+        mm.emission = (C.c_float * 3)(*[float(x) for x in np.asarray(m["emission"]).reshape(3)])
+    for k, (obj, mat) in enumerate(assign):
+        aa[k].object, aa[k].material = int(obj), int(mat)
+    return ea, len(edits), aa, len(assign)
+
+
+def _environment(background, env):
+    """(background float[3], env_w, env_h, pixel pointer or None, the array to keep alive)."""
+    bg = (C.c_float * 3)(*[float(x) for x in np.asarray(background, dtype=np.float64).reshape(3)])
+    if env is None:
+        return bg, 0, 0, None, None
+    env = np.ascontiguousarray(env, dtype=np.float32)
+    if env.ndim != 3 or env.shape[2] != 3 or env.size == 0:
+        raise ValueError("set_environment: a map has shape (h, w, 3), not %s" % (env.shape,))
+    return bg, int(env.shape[1]), int(env.shape[0]), _ptr(env), env
 
 
 class CullInfo(C.Structure):
@@ -473,6 +519,14 @@ def lib(path=None):
         L.mcpt_scene_deform.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(UpdateInfo)]
         L.mcpt_group_deform.restype = C.c_int
         L.mcpt_group_deform.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+        L.mcpt_scene_set_materials.restype = C.c_int
+        L.mcpt_scene_set_materials.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(UpdateInfo)]
+        L.mcpt_scene_set_environment.restype = C.c_int
+        L.mcpt_scene_set_environment.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(UpdateInfo)]
+        L.mcpt_group_set_materials.restype = C.c_int
+        L.mcpt_group_set_materials.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
+        L.mcpt_group_set_environment.restype = C.c_int
+        L.mcpt_group_set_environment.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
         L.mcpt_deform_triangles.restype = C.c_int
         L.mcpt_deform_triangles.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
         L.mcpt_group_create.restype = C.c_int
@@ -641,6 +695,24 @@ class HipScene:
         arr, n, keep = _vertex_items(items, _mesh_tri_counts(self.sd))
         info = UpdateInfo()
         _check(self.L.mcpt_scene_deform(self.h, n, C.cast(arr, C.c_void_p), C.byref(info)), L=self.L)
+        del keep
+        return info.as_dict()
+
+    def set_materials(self, edits=(), assign=()):
+        """mcpt_scene_set_materials: edits = an iterable of (material index, material record as in scenes.MAT_DTYPE), assign = an iterable of
+        (object index, material index).  Afterwards the scene behaves like one created from the edited description; in place (path 2)
+        unless an object starts or stops emitting light.  Returns mcpt_update_info as a dict."""
+        ea, ne, aa, na = _material_lists(edits, assign)
+        info = UpdateInfo()
+        _check(self.L.mcpt_scene_set_materials(self.h, ne, C.cast(ea, C.c_void_p), na, C.cast(aa, C.c_void_p), C.byref(info)), L=self.L)
+        return info.as_dict()
+
+    def set_environment(self, background, env=None):
+        """mcpt_scene_set_environment: the background colour and the environment map (an (h, w, 3) float32 array, or None for the constant
+        colour).  Returns mcpt_update_info as a dict."""
+        bg, w, h, px, keep = _environment(background, env)
+        info = UpdateInfo()
+        _check(self.L.mcpt_scene_set_environment(self.h, C.cast(bg, C.c_void_p), w, h, px, C.byref(info)), L=self.L)
         del keep
         return info.as_dict()
 
@@ -1395,6 +1467,21 @@ class HipGroup:
         be valid on several devices)."""
         arr, n, keep = _vertex_items(items, _mesh_tri_counts(self.sd))
         rc = self.L.mcpt_group_deform(self.h, n, C.cast(arr, C.c_void_p))
+        del keep
+        if rc != 0:
+            raise McptError(rc, self.L.mcpt_group_last_error().decode("utf-8", "replace"))
+
+    def set_materials(self, edits=(), assign=()):
+        """mcpt_group_set_materials: HipScene.set_materials on every replica."""
+        ea, ne, aa, na = _material_lists(edits, assign)
+        rc = self.L.mcpt_group_set_materials(self.h, ne, C.cast(ea, C.c_void_p), na, C.cast(aa, C.c_void_p))
+        if rc != 0:
+            raise McptError(rc, self.L.mcpt_group_last_error().decode("utf-8", "replace"))
+
+    def set_environment(self, background, env=None):
+        """mcpt_group_set_environment: HipScene.set_environment on every replica."""
+        bg, w, h, px, keep = _environment(background, env)
+        rc = self.L.mcpt_group_set_environment(self.h, C.cast(bg, C.c_void_p), w, h, px)
         del keep
         if rc != 0:
             raise McptError(rc, self.L.mcpt_group_last_error().decode("utf-8", "replace"))

@@ -1,6 +1,7 @@
 // Host side above the C ABI: MeshTriangle/OBJ loading, Scene and Renderer of the reference restated over
 // include/mcpt.h.  Reference behaviour mirrored: src/Triangle.hpp:83-135 (+ src/OBJ_Loader.hpp:363-521,633-729 for
 // the vertex stream), src/Scene.hpp:39-57,104-119, src/Scene.cpp:14-21, src/Renderer.cpp:21-110.
+#include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -150,6 +151,16 @@ void Scene::flatten(std::vector<mcpt_triangle> &tris, std::vector<mcpt_material>
     }
 }
 
+namespace {
+
+Material *material_of(Object *o) {
+    if (auto *mesh = dynamic_cast<MeshTriangle *>(o)) return mesh->m;
+    if (auto *s = dynamic_cast<Sphere *>(o)) return s->m;
+    return nullptr;
+}
+
+}  // namespace
+
 void Scene::buildBVH() {
     printf(" - Generating BVH...\n\n");
     std::vector<mcpt_triangle> tris;
@@ -169,6 +180,8 @@ void Scene::buildBVH() {
         d.env_h = (int)envHeight;
         d.env_pixels = envPixels.data();
     }
+    builtMaterialOf.clear();
+    for (Object *o : objects) builtMaterialOf.push_back(material_of(o));
     mcpt_scene_destroy(gpu);
     gpu = nullptr;
     mcpt_group_destroy(group);
@@ -208,6 +221,90 @@ void Scene::setTransform(Object *object, const float m[12]) {
     for (const Object *o : pendingTransforms)
         if (o == object) return;
     pendingTransforms.push_back(object);
+}
+
+bool Scene::setMaterial(Object *object, const Material &m) {
+    Material *own = material_of(object);
+    const bool built = gpu || group;
+    // the material of every object: as buildBVH() numbered them for the library's table, or, before it, as they are now
+    std::vector<const Material *> of;
+    if (built) of = builtMaterialOf;
+    else
+        for (Object *o : objects) of.push_back(material_of(o));
+    const size_t at = (size_t)(std::find(objects.begin(), objects.end(), object) - objects.begin());
+    if (!own || at >= objects.size() || at >= of.size()) {
+        std::cerr << "mcpt: Scene::setMaterial: the object is not in the " << (built ? "built " : "") << "scene" << std::endl;
+        return false;
+    }
+    if (of[at] != own) {
+        std::cerr << "mcpt: Scene::setMaterial: the object was given another Material after buildBVH(); the built scene's table cannot follow" << std::endl;
+        return false;
+    }
+    const long sharers = (long)std::count(of.begin(), of.end(), own);
+    if (sharers > 1) {
+        std::cerr << "mcpt: Scene::setMaterial: the object's material is shared with " << sharers - 1
+                  << " other object(s); a built scene cannot be given a new material (mcpt_scene_set_materials: n_materials is fixed)" << std::endl;
+        return false;
+    }
+    int index = 0;  // flatten()'s numbering: the materials in order of first appearance
+    for (size_t i = 0; i < at; ++i)
+        if (std::find(of.begin(), of.begin() + (long)i, of[i]) == of.begin() + (long)i) ++index;
+    // (applied at once through the scene's or the group's own entry point, so it works after setDevices; transforms still pending are
+    // not flushed first: a material edit and an update commute, either order gives the scene of the same description)
+    if (gpu || group) {
+        mcpt_material_edit e{};
+        e.index = index;
+        e.material.type = (int)m.m_type;
+        e.material.textured = m.textured ? 1 : 0;
+        e.material.roughness = m.roughness;
+        e.material.iorA = m.iorA;
+        e.material.iorB = m.iorB;
+        for (int k = 0; k < 3; ++k) {
+            e.material.base_reflectance[k] = m.base_reflectance[k];
+            e.material.emission[k] = m.m_emission[k];
+        }
+        if (group) {
+            if (mcpt_group_set_materials(group, 1, &e, 0, nullptr) != MCPT_OK) {
+                std::cerr << "mcpt: " << mcpt_group_last_error() << std::endl;
+                return false;
+            }
+        } else {
+            mcpt_update_info ui{};
+            if (mcpt_scene_set_materials(gpu, 1, &e, 0, nullptr, &ui) != MCPT_OK) {
+                std::cerr << "mcpt: " << mcpt_last_error() << std::endl;
+                return false;
+            }
+            std::cout << "[mcpt] material edit (" << (ui.path == 2 ? "in place" : "host path") << "): " << ui.n_moved_tris << " triangle records, "
+                      << ui.total_ms << " ms" << std::endl;
+        }
+    }
+    *own = m;
+    lightsObjects.clear();
+    for (Object *o : objects)
+        if (o->hasEmit()) lightsObjects.push_back(o);
+    return true;
+}
+
+bool Scene::setBackground(const Vector3f &color, unsigned env_w, unsigned env_h, const float *env_pixels) {
+    if (env_pixels ? !(env_w > 0 && env_h > 0) : !(env_w == 0 && env_h == 0)) {
+        std::cerr << "mcpt: Scene::setBackground: a map needs a positive size, the constant colour 0, 0" << std::endl;
+        return false;
+    }
+    if (gpu || group) {
+        const int rc = group ? mcpt_group_set_environment(group, color.data(), (int32_t)env_w, (int32_t)env_h, env_pixels)
+                             : mcpt_scene_set_environment(gpu, color.data(), (int32_t)env_w, (int32_t)env_h, env_pixels, nullptr);
+        if (rc != MCPT_OK) {
+            std::cerr << "mcpt: " << (group ? mcpt_group_last_error() : mcpt_last_error()) << std::endl;
+            return false;
+        }
+    }
+    backgroundColor = color;
+    useEnvMap = env_pixels != nullptr;
+    envWidth = env_w;
+    envHeight = env_h;
+    if (env_pixels != envPixels.data()) envPixels.assign(env_pixels, env_pixels + (size_t)env_w * env_h * 3);
+    else envPixels.resize((size_t)env_w * env_h * 3);
+    return true;
 }
 
 std::vector<mcpt_object_transform> Scene::transforms() const {

@@ -229,6 +229,16 @@ class Scene {
     // the transforms set so far, in Scene::Add order (object = index into `objects`); objects that are not in the scene are left out
     std::vector<mcpt_object_transform> transforms() const;
 
+    // Relights a live scene (mcpt_scene_set_materials / mcpt_scene_set_environment, or their group forms after setDevices).
+    // setMaterial gives the object's material the values of `m`: the scene's material table is fixed once built, so a material the scene
+    // does not hold cannot be added; the object's own entry is edited, which is refused (false, with a message) when another object
+    // shares that Material, or when the object was pointed at another Material after buildBVH().  Before buildBVH() it only changes
+    // the Material the object points to.  setBackground replaces the colour
+    // and the environment map (env_pixels: env_w * env_h * 3 floats in [0,1], or nullptr with 0, 0 for the constant colour).  On a
+    // built scene both take effect at once and return false, with the library's message on stderr, when the library refuses.
+    bool setMaterial(Object *object, const Material &m);
+    bool setBackground(const Vector3f &color, unsigned env_w = 0, unsigned env_h = 0, const float *env_pixels = nullptr);
+
     // used by Renderer
     mcpt_scene *handle() const {  // (with several GPUs: the replica on the first one)
         applyTransforms();
@@ -257,6 +267,9 @@ class Scene {
     void applyTransforms() const;  // sends the transforms set since the last call to the live scene
     std::map<const Object *, std::array<float, 12>> objectTransforms;
     mutable std::vector<const Object *> pendingTransforms;
+    // the Material every object pointed to when buildBVH() numbered the library's material table (flatten(): order of first
+    // appearance); setMaterial on a built scene reads the numbering from here, not from pointers that may have changed since
+    std::vector<const Material *> builtMaterialOf;
 };
 
 // ============================================================================ renderer

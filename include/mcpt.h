@@ -182,7 +182,7 @@ int mcpt_scene_create_ex(const mcpt_scene_desc *desc, int device, const mcpt_bui
  * MCPT_ERR_OOM) leaves the scene exactly as it was before the call: the new arrays are built aside and swapped in on success. */
 typedef struct { int32_t object; float m[12]; } mcpt_object_transform; /* 52 bytes; m row-major 3x4 */
 typedef struct {
-    int32_t path;         /* 0: host rebuild + re-upload, 1: device transform + device rebuild */
+    int32_t path;         /* 0: host rebuild + re-upload, 1: device transform + device rebuild, 2: in place (mcpt_scene_set_*) */
     int32_t n_moved_tris; /* triangles of the listed meshes */
     double transform_ms;  /* path 0: forming desc' on the host; path 1: the segment table's copy and the transform kernel */
     double build_ms;      /* flattening + tree build (host and device parts) */
@@ -239,6 +239,49 @@ int mcpt_scene_deform(mcpt_scene *scene, int32_t n, const mcpt_object_vertices *
 /* Host only, no GPU needed: out[i] = in[i] with its nine position floats replaced by positions[9i .. 9i+9) (uv copied); in == out allowed.
  * MCPT_ERR_ARG for n < 0, or n > 0 with a null array. */
 int mcpt_deform_triangles(int64_t n, const float *positions, const mcpt_triangle *in, mcpt_triangle *out);
+
+/* ---- Relighting a live scene: materials, emitters and the sky edited in place.
+ *
+ * mcpt_scene_set_materials replaces the listed entries of the material table (materials[index] = material) and gives the listed objects
+ * another entry of it (objects[object].material = material).  n_materials is fixed for the life of the scene: entries change, none is
+ * added.  Both lists may be given in one call; they are applied together.
+ * THE CONTRACT: after the call every entry point listed at mcpt_scene_update gives what it gives on
+ *       mcpt_scene_create_ex(desc', device, the same options)
+ * where desc' is the scene's current description (latest bases, current transforms) with the listed entries replaced and the listed
+ * objects reassigned.  With the host builders bit for bit, the tree dump included; with the device builders by the rule stated there.
+ * The scene's host copy of the description follows every successful call at once, so a later mcpt_scene_update / mcpt_scene_deform on
+ * path 0 flattens the edited scene.  The snapshot of mcpt_scene_snapshot is not touched (it holds positions only).
+ *   info->path 2  in place: every object emits light after the call if and only if it did before (Material::hasEmission of its
+ *                 material).  Colour, roughness, ior, type, `textured`, the emission VALUES of a light that stays a light, reassignments
+ *                 between non-emitting materials or between emitting ones.  The changed MaterialRecs are formed by the creation code and
+ *                 copied into the table; one kernel rewrites the material words of the affected primitives (an object that was listed, or
+ *                 a mesh whose material changed its `textured` flag); LightRec::mat of a reassigned emitter is patched.  The tree, the
+ *                 node arrays and the host flatten are not touched: build_ms is 0.
+ *   info->path 0  host: some object starts or stops emitting, so the light tables, the emitters' bounding sphere, n_lights and possibly
+ *                 the LDS-resident decision change.  desc' is flattened and uploaded as on path 0 of mcpt_scene_update, for every builder,
+ *                 together with the material table.
+ *   info->n_moved_tris is the number of triangle records whose material words change; the timing fields keep their meaning
+ *   (transform_ms: the table copy, the segment table and the kernel on path 2).
+ * MCPT_ERR_ARG, before any device call: scene == NULL; a negative count, or a positive count with a null list; a material index or an
+ * object index out of range; a material type outside 0..3; a material value that is not finite; the same material index, or the same
+ * object, listed twice in one call; a scene built with node instancing on.  Both counts zero is a valid no-op.  A refused call, and a
+ * call that fails on path 0, leaves the scene as it was: path 0 builds aside and swaps, path 2 does all its checking first, so only a HIP error can fail it afterwards.
+ * After such an error (MCPT_ERR_HIP from a copy or the launch on path 2) the device tables may hold part of the edit while the host copy
+ * of the description holds none of it, so a later host-path rebuild would drop that part: repeat the call, or destroy the scene.
+ * Blocking, on the null stream, like mcpt_scene_update.  History kept by the caller (mcpt_temporal_*, mcpt_sequence_*) does not know
+ * that the scene was relit: the colour clamp of mcpt_history_opts is the remedy for stale radiance, or mcpt_sequence_reset. */
+typedef struct { int32_t index; mcpt_material material; } mcpt_material_edit;   /* 48 bytes: materials[index] = material */
+typedef struct { int32_t object; int32_t material; } mcpt_object_material;      /* 8 bytes: objects[object].material = material */
+int mcpt_scene_set_materials(mcpt_scene *scene, int32_t n_edits, const mcpt_material_edit *edits, int32_t n_assign,
+                             const mcpt_object_material *assign, mcpt_update_info *info /* nullable */);
+/* mcpt_scene_set_environment replaces the background colour and the environment map (env_pixels: env_w * env_h * 3 floats as in
+ * mcpt_scene_desc, or NULL with env_w == env_h == 0 for the constant colour).  Map <-> colour and a change of map size are allowed.  Always
+ * in place (info->path 2, n_moved_tris 0): the new map is uploaded aside and swapped in on success; the sky cull, which only runs for a
+ * constant background, reads the scene per call and switches by itself.  The same contract as above, with desc' the current description
+ * with its background and environment replaced.  MCPT_ERR_ARG, before any device call: scene == NULL; background == NULL; env_w / env_h
+ * not both zero with a null map, or not both positive with one; a background or map value that is not finite. */
+int mcpt_scene_set_environment(mcpt_scene *scene, const float background[3], int32_t env_w, int32_t env_h, const float *env_pixels,
+                               mcpt_update_info *info /* nullable */);
 
 /* Replaces the pixel/spp loop of Renderer::Render (Renderer.cpp:21-91): fb_host = W*H*3 floats,
  * row-major m = j*W + i, linear radiance averaged over spp -- what `framebuffer` holds at Renderer.cpp:91.
@@ -1007,6 +1050,11 @@ mcpt_scene *mcpt_group_scene(mcpt_group *group, int index);
 /* mcpt_scene_update on every replica (one host thread per replica), with the same checks before any device call.  If a replica fails,
  * the replicas that had succeeded are given their previous transforms back, so that the group stays one scene. */
 int mcpt_group_update(mcpt_group *group, int32_t n, const mcpt_object_transform *moves);
+/* mcpt_scene_set_materials / mcpt_scene_set_environment on every replica, with the same checks before any device call.  If a replica
+ * fails, the replicas that had changed get their previous materials (environment) back: the group stays one scene. */
+int mcpt_group_set_materials(mcpt_group *group, int32_t n_edits, const mcpt_material_edit *edits, int32_t n_assign,
+                             const mcpt_object_material *assign);
+int mcpt_group_set_environment(mcpt_group *group, const float background[3], int32_t env_w, int32_t env_h, const float *env_pixels);
 /* mcpt_scene_deform on every replica, host pointers only: an item with on_device 1 is refused with MCPT_ERR_ARG, since one pointer
  * cannot be valid on several devices.  If a replica fails, the replicas that had succeeded get their previous positions back. */
 int mcpt_group_deform(mcpt_group *group, int32_t n, const mcpt_object_vertices *items);
