@@ -1,7 +1,7 @@
 // The host layer behind the C ABI (include/mcpt.h): error plumbing, the owners of device resources, the wavefront workspace, the
 // environment knobs, the event timer, struct mcpt_scene, and what its translation units call in each other:
 //   mcpt_wavefront.hip  the wavefront loop, workspace / pass sizing (render_list), the pixel list and sky cull set-up
-//   mcpt_upload.hip     scene create / upload / update / material and environment edits / snapshot / destroy / info, the BVH dumps
+//   mcpt_upload.hip     scene create / upload / update / material and environment edits / visibility / snapshot / destroy / info, the BVH dumps
 //   mcpt_update.hip     the kernels that move and deform objects in HBM (the device path of mcpt_scene_update / mcpt_scene_deform),
 //                       mcpt_transform_triangles, mcpt_deform_triangles
 //   mcpt_render.hip     the frame-level entry points (render, adaptive, AOVs, denoise, motion, temporal blend); mcpt_frame.h has what
@@ -319,6 +319,10 @@ struct GeomBufs {
     DevBuf<LightRec> lights;
     DevBuf<LightNode> light_nodes;
     DevBuf<LightTri> light_tris;
+    void swap_nodes(GeomBufs &o) {  // the tree alone (mcpt_scene_set_visibility, path 1: no record is written)
+        nodes.swap(o.nodes);
+        qnodes.swap(o.qnodes);
+    }
     void swap_prims(GeomBufs &o) {  // the tree and the primitive records
         nodes.swap(o.nodes);
         qnodes.swap(o.qnodes);
@@ -355,6 +359,7 @@ struct SceneSource {
     std::vector<uint8_t> moved;  // per object: 1 once it has been given a transform
     std::vector<float> xf;       // per object: its row-major 3x4 matrix (unused while moved == 0)
     BuildChoice choice;          // the builder and its options as resolved at creation
+    std::vector<uint8_t> visible;  // per object: 0 while hidden (mcpt_scene_set_visibility); every rebuild keeps hidden objects out of the tree
     std::vector<float> env;      // the environment map (meta.env_w x env_h x 3; empty: the constant background), the way back of
                                  // mcpt_group_set_environment
 };
@@ -480,6 +485,11 @@ int check_moves(const mcpt_scene *sc, int32_t n, const mcpt_object_transform *mo
 int check_material_edit(const mcpt_scene *sc, int32_t n_edits, const mcpt_material_edit *edits, int32_t n_assign, const mcpt_object_material *assign,
                         mat::EditPlan &plan);
 int apply_material_edit(mcpt_scene *sc, const mat::EditPlan &plan, mcpt_update_info *info);
+// mcpt_scene_set_visibility in two halves, as above: the checks before any device call, which fill the mask the scene would have
+// afterwards and the objects whose state differs from the one they have; and the rebuild.  Also the way back for
+// mcpt_group_set_visibility when another replica fails.
+int check_visibility(const mcpt_scene *sc, int32_t n, const mcpt_object_visibility *items, std::vector<uint8_t> &visible, std::vector<int32_t> &changed);
+int apply_visibility(mcpt_scene *sc, const std::vector<uint8_t> &visible, const std::vector<int32_t> &changed, mcpt_update_info *info);
 int check_environment(const mcpt_scene *sc, const float *background, int32_t env_w, int32_t env_h, const float *env_pixels);
 int apply_environment(mcpt_scene *sc, const float *background, int32_t env_w, int32_t env_h, const float *env_pixels, mcpt_update_info *info);
 double warm_up_device(int device);

@@ -177,6 +177,13 @@ void build_sah_over_clusters(int m, const float *cmin4, const float *cmax4, cons
 
 // Builds the flattened scene.  Returns MCPT_OK or an error code and fills `err`.  With MCPT_BUILD_GPU_LBVH / _PLOC the traversal tree is left
 // out (nodes empty, root/height unset): the caller builds it on the device (csrc/mcpt_lbvh.hip); everything else is filled.
-int build_host_scene(const mcpt_scene_desc &d, HostScene &out, const char **err, const BuildChoice &choice);
+// `visible` (n_objects flags, nullptr: all): mcpt_scene_set_visibility.  A hidden object gets its records like any other -- they keep
+// their places, so every primitive id stays what it is -- but its primitives are left out of the lists handed to the tree builders and
+// it is left out of the light tables and the emitters' bounding sphere: the tree and the light tables are those of the description
+// with the hidden objects removed (mcpt_compact_scene), with the stored ids in the leaves, LightTri::prim and the sphere slots.
+int build_host_scene(const mcpt_scene_desc &d, HostScene &out, const char **err, const BuildChoice &choice, const uint8_t *visible = nullptr);
+// mcpt_compact_scene (include/mcpt.h) after the null checks.
+int compact_scene_desc(const mcpt_scene_desc &d, const uint8_t *visible, mcpt_object *objects_out, mcpt_triangle *triangles_out, int32_t *n_objects_out,
+                       int32_t *n_triangles_out, int32_t *prim_map, const char **err);
 
 }  // namespace mcpt

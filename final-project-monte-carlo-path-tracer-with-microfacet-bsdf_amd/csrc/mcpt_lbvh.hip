@@ -7,6 +7,7 @@
 // Pipeline (Karras 2012, "Maximizing parallelism in the construction of BVHs, octrees and k-d trees"):
 //   k_prim_boxes   one lane per primitive: exact box of the stored vertices (Triangle::getBounds, Triangle.hpp:220) or of the
 //                  sphere (Sphere.hpp:58-63); scene bounds of the centroids by ordered-integer atomics
+//                  (k_prim_boxes_visible: the same over the visible primitives only, mcpt_scene_set_visibility)
 //   k_morton       63-bit Morton code of the centroid (21 bits per axis)
 //   hipcub         radix sort of (code, primitive) pairs
 //   k_hierarchy    one lane per inner node: range and split from common-prefix lengths (equal codes are told apart by position)
@@ -78,6 +79,47 @@ __global__ __launch_bounds__(kB) void k_prim_boxes(const mcpt_triangle *__restri
             mx[a] = s.c[a] + s.radius;
         }
         S.prim_id[i] = n_tri + oi;
+    }
+    for (int a = 0; a < 3; ++a) {
+        S.pmin[3 * i + a] = mn[a];
+        S.pmax[3 * i + a] = mx[a];
+        const float c = 0.5f * mn[a] + 0.5f * mx[a];
+        atomicMin(&S.bounds[a], f2o(c));
+        atomicMax(&S.bounds[3 + a], f2o(c));
+    }
+}
+
+// The flavour for a scene with hidden objects (VisTable, csrc/mcpt_lbvh.h): slot i is the i-th VISIBLE primitive in id order.  The mesh
+// segment of a triangle slot is found by bisection (the last segment whose first_slot <= i), as k_move_objects finds its segment.
+__global__ __launch_bounds__(kB) void k_prim_boxes_visible(const mcpt_triangle *__restrict__ tris, int n_tri, const int32_t *__restrict__ sphere_obj,
+                                                            const SphereRec *__restrict__ spheres, int n_sph, const VisSeg *__restrict__ segs, int n_segs,
+                                                            int n_tri_ids, BuildScratch S) {
+    const int i = blockIdx.x * kB + threadIdx.x;
+    if (i >= n_tri + n_sph) return;
+    float mn[3], mx[3];
+    if (i < n_tri) {
+        int lo = 0, hi = n_segs - 1;
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (segs[mid].first_slot <= i) lo = mid;
+            else hi = mid - 1;
+        }
+        const VisSeg sg = segs[lo];
+        const int ti = sg.first_tri + (i - sg.first_slot);
+        const mcpt_triangle t = tris[ti];
+        for (int a = 0; a < 3; ++a) {
+            mn[a] = fminf(fminf(t.v0[a], t.v1[a]), t.v2[a]);
+            mx[a] = fmaxf(fmaxf(t.v0[a], t.v1[a]), t.v2[a]);
+        }
+        S.prim_id[i] = ti;
+    } else {
+        const int oi = sphere_obj[i - n_tri];
+        const SphereRec s = spheres[oi];
+        for (int a = 0; a < 3; ++a) {
+            mn[a] = s.c[a] - s.radius;
+            mx[a] = s.c[a] + s.radius;
+        }
+        S.prim_id[i] = n_tri_ids + oi;
     }
     for (int a = 0; a < 3; ++a) {
         S.pmin[3 * i + a] = mn[a];
@@ -388,10 +430,12 @@ hipError_t dalloc(T *&p, size_t count) {
 }  // namespace
 
 hipError_t build_lbvh_device(const mcpt_triangle *d_tris, int n_tri, const int32_t *d_sphere_obj, const SphereRec *d_spheres, int n_sph,
-                             int quantise, int algo, int ploc_radius, int ploc_top, Node *d_nodes, QNode *d_qnodes, LbvhResult *out, hipStream_t st) {
+                             int quantise, int algo, int ploc_radius, int ploc_top, Node *d_nodes, QNode *d_qnodes, LbvhResult *out, hipStream_t st,
+                             const VisTable *vis) {
     const int n = n_tri + n_sph;
     std::memset(out, 0, sizeof *out);
     if (n < 2) return hipErrorInvalidValue;
+    if (vis && n_tri > 0 && (vis->n_segs < 1 || !vis->segs)) return hipErrorInvalidValue;
     BuildScratch S;
     std::memset(&S, 0, sizeof S);
     void *temp = nullptr;
@@ -426,7 +470,11 @@ hipError_t build_lbvh_device(const mcpt_triangle *d_tris, int n_tri, const int32
         chk(hipMemsetAsync(S.diag_sum, 0, sizeof(double), st));
     }
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_prim_boxes, dim3(nblocks(n)), dim3(kB), 0, st, d_tris, n_tri, d_sphere_obj, d_spheres, n_sph, S);
+        if (vis)
+            hipLaunchKernelGGL(k_prim_boxes_visible, dim3(nblocks(n)), dim3(kB), 0, st, d_tris, n_tri, d_sphere_obj, d_spheres, n_sph, vis->segs, vis->n_segs,
+                               vis->n_tri_ids, S);
+        else
+            hipLaunchKernelGGL(k_prim_boxes, dim3(nblocks(n)), dim3(kB), 0, st, d_tris, n_tri, d_sphere_obj, d_spheres, n_sph, S);
         uint32_t hb[6];
         chk(hipMemcpyAsync(hb, S.bounds, sizeof hb, hipMemcpyDeviceToHost, st));
         chk(hipStreamSynchronize(st));

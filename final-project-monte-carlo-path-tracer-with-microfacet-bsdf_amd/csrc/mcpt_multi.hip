@@ -338,6 +338,18 @@ int mcpt_group_set_materials(mcpt_group *g, int32_t n_edits, const mcpt_material
                        [&](mcpt_scene *sc) { return apply_material_edit(sc, back, nullptr); });
 }
 
+int mcpt_group_set_visibility(mcpt_group *g, int32_t n, const mcpt_object_visibility *items) {
+    if (!g || g->scenes.empty()) return gfail(MCPT_ERR_ARG, "mcpt_group_set_visibility: null group");
+    // every replica holds the same description and the same mask: one check, before any device call
+    std::vector<uint8_t> visible;
+    std::vector<int32_t> changed;
+    const int rc0 = check_visibility(g->scenes[0], n, items, visible, changed);
+    if (rc0 != MCPT_OK) return gfail(rc0, std::string("mcpt_group_set_visibility: ") + mcpt_last_error());
+    const std::vector<uint8_t> old = g->scenes[0]->src.visible;  // the way back: the same objects change state again
+    return on_replicas(g, "mcpt_group_set_visibility", [&](mcpt_scene *sc) { return apply_visibility(sc, visible, changed, nullptr); },
+                       [&](mcpt_scene *sc) { return apply_visibility(sc, old, changed, nullptr); });
+}
+
 int mcpt_group_set_environment(mcpt_group *g, const float background[3], int32_t env_w, int32_t env_h, const float *env_pixels) {
     if (!g || g->scenes.empty()) return gfail(MCPT_ERR_ARG, "mcpt_group_set_environment: null group");
     const int rc0 = check_environment(g->scenes[0], background, env_w, env_h, env_pixels);

@@ -542,8 +542,9 @@ BuildChoice resolve_build_choice(const mcpt_build_options *opt) {
     return c;
 }
 
-int build_host_scene(const mcpt_scene_desc &d, HostScene &hs, const char **err, const BuildChoice &choice) {
+int build_host_scene(const mcpt_scene_desc &d, HostScene &hs, const char **err, const BuildChoice &choice, const uint8_t *visible) {
     *err = "";
+    const auto shown = [visible](int oi) { return !visible || visible[oi] != 0; };
     if (choice.builder != MCPT_BUILD_SAH && choice.builder != MCPT_BUILD_REFERENCE && choice.builder != MCPT_BUILD_GPU_LBVH &&
         choice.builder != MCPT_BUILD_GPU_PLOC) {
         *err = "unknown builder in mcpt_build_options";
@@ -554,6 +555,10 @@ int build_host_scene(const mcpt_scene_desc &d, HostScene &hs, const char **err, 
     if (d.n_objects <= 0 || !d.objects || d.n_materials <= 0 || !d.materials || d.n_triangles < 0 ||
         (d.n_triangles > 0 && !d.triangles)) {
         *err = "scene description: empty or null arrays";
+        return MCPT_ERR_ARG;
+    }
+    if (visible && std::none_of(visible, visible + d.n_objects, [](uint8_t v) { return v != 0; })) {
+        *err = "no visible object";
         return MCPT_ERR_ARG;
     }
     hs.n_triangles = d.n_triangles;
@@ -661,7 +666,7 @@ int build_host_scene(const mcpt_scene_desc &d, HostScene &hs, const char **err, 
             B.area = area;
             // the per-mesh tree (Triangle.hpp:134) carries the traversal topology of the reference AND the area tree its light
             // sampling descends (BVH.cpp:118-129); with the GPU builder only emissive meshes still need it
-            B.mesh_root = (mesh_trees || hs.materials[o.material].hasEmission) ? recursive_build(arena, ptrs) : nullptr;
+            B.mesh_root = (shown(oi) && (mesh_trees || hs.materials[o.material].hasEmission)) ? recursive_build(arena, ptrs) : nullptr;
         } else {
             *err = "object kind out of range";
             return MCPT_ERR_ARG;
@@ -800,13 +805,15 @@ int build_host_scene(const mcpt_scene_desc &d, HostScene &hs, const char **err, 
     if (choice.builder == MCPT_BUILD_REFERENCE) {
         hs.builder = 1;
         std::vector<BObj *> tops;
-        for (BObj &b : top_objs) tops.push_back(&b);
+        for (int oi = 0; oi < d.n_objects; ++oi)
+            if (shown(oi)) tops.push_back(&top_objs[oi]);
         root = recursive_build(arena, tops);  // Scene::buildBVH, Scene.cpp:14-17
     } else {
         hs.builder = 0;
         std::vector<BObj *> prims;
         prims.reserve((size_t)d.n_triangles + d.n_objects);
         for (int oi = 0; oi < d.n_objects; ++oi) {
+            if (!shown(oi)) continue;  // hidden: its records exist, the tree does not reach them
             if (top_objs[oi].prim >= 0) prims.push_back(&top_objs[oi]);  // sphere
             else if (inst_of_object[oi] >= 0) prims.push_back(&inst_leaf_objs[inst_of_object[oi]]);  // one leaf for the whole object
             else
@@ -898,7 +905,7 @@ int build_host_scene(const mcpt_scene_desc &d, HostScene &hs, const char **err, 
     hs.light_area_sum = 0.f;
     for (int oi = 0; oi < d.n_objects; ++oi) {
         const mcpt_object &o = d.objects[oi];
-        if (!hs.materials[o.material].hasEmission) continue;
+        if (!hs.materials[o.material].hasEmission || !shown(oi)) continue;
         LightRec L;
         std::memset(&L, 0, sizeof L);
         L.area = top_objs[oi].area;
@@ -921,7 +928,7 @@ int build_host_scene(const mcpt_scene_desc &d, HostScene &hs, const char **err, 
     {
         Box lb = box_empty();
         for (int oi = 0; oi < d.n_objects; ++oi)
-            if (hs.materials[d.objects[oi].material].hasEmission) lb = box_union(lb, top_objs[oi].bounds);
+            if (hs.materials[d.objects[oi].material].hasEmission && shown(oi)) lb = box_union(lb, top_objs[oi].bounds);
         if (!hs.lights.empty()) {
             const V3 c = centroid(lb);
             double r2 = 0.0;
@@ -952,6 +959,80 @@ int build_host_scene(const mcpt_scene_desc &d, HostScene &hs, const char **err, 
         hs.env.assign(d.env_pixels, d.env_pixels + (size_t)d.env_w * d.env_h * 3);
     }
     phase("quantised nodes, light tables");
+    return MCPT_OK;
+}
+
+// What mcpt_compact_scene does once its arguments are known to be non-null: the checks of build_host_scene that need no tree, then the
+// compaction.  A null `objects_out` or `triangles_out` gives the counts and the map only.
+int compact_scene_desc(const mcpt_scene_desc &d, const uint8_t *visible, mcpt_object *objects_out, mcpt_triangle *triangles_out, int32_t *n_objects_out,
+                       int32_t *n_triangles_out, int32_t *prim_map, const char **err) {
+    *err = "";
+    if (d.n_objects <= 0 || !d.objects || d.n_materials <= 0 || !d.materials || d.n_triangles < 0 || (d.n_triangles > 0 && !d.triangles)) {
+        *err = "scene description: empty or null arrays";
+        return MCPT_ERR_ARG;
+    }
+    for (int i = 0; i < d.n_materials; ++i)
+        if (d.materials[i].type < 0 || d.materials[i].type > 3) {
+            *err = "material type out of range";
+            return MCPT_ERR_ARG;
+        }
+    std::vector<uint8_t> tri_seen((size_t)d.n_triangles, 0);
+    for (int oi = 0; oi < d.n_objects; ++oi) {
+        const mcpt_object &o = d.objects[oi];
+        if (o.material < 0 || o.material >= d.n_materials) {
+            *err = "object material index out of range";
+            return MCPT_ERR_ARG;
+        }
+        if (o.kind == MCPT_OBJ_SPHERE) continue;
+        if (o.kind != MCPT_OBJ_MESH) {
+            *err = "object kind out of range";
+            return MCPT_ERR_ARG;
+        }
+        if (o.first_tri < 0 || o.n_tri <= 0 || o.first_tri > d.n_triangles - o.n_tri) {
+            *err = "mesh triangle range out of bounds";
+            return MCPT_ERR_ARG;
+        }
+        for (int k = 0; k < o.n_tri; ++k) {
+            if (tri_seen[(size_t)o.first_tri + k]) {
+                *err = "triangle ranges of two meshes overlap";
+                return MCPT_ERR_ARG;
+            }
+            tri_seen[(size_t)o.first_tri + k] = 1;
+        }
+    }
+    // compacted triangle ids follow ARRAY order (so the map is increasing), whatever order the objects list their meshes in
+    std::vector<int32_t> mesh_of((size_t)d.n_triangles, -1);
+    for (int oi = 0; oi < d.n_objects; ++oi)
+        if (d.objects[oi].kind == MCPT_OBJ_MESH)
+            for (int k = 0; k < d.objects[oi].n_tri; ++k) mesh_of[(size_t)d.objects[oi].first_tri + k] = oi;
+    int32_t nt = 0;
+    std::vector<int32_t> new_first((size_t)d.n_objects, -1);
+    for (int32_t t = 0; t < d.n_triangles; ++t) {
+        const int32_t oi = mesh_of[(size_t)t];
+        const bool keep = oi >= 0 && visible[oi] != 0;
+        if (prim_map) prim_map[t] = keep ? nt : -1;
+        if (!keep) continue;
+        if (t == d.objects[oi].first_tri) new_first[(size_t)oi] = nt;
+        if (triangles_out) triangles_out[nt] = d.triangles[t];
+        ++nt;
+    }
+    int32_t no = 0;
+    for (int oi = 0; oi < d.n_objects; ++oi) {
+        const bool keep = visible[oi] != 0;
+        if (prim_map) prim_map[(size_t)d.n_triangles + oi] = keep && d.objects[oi].kind == MCPT_OBJ_SPHERE ? nt + no : -1;
+        if (!keep) continue;
+        if (objects_out) {
+            objects_out[no] = d.objects[oi];
+            if (d.objects[oi].kind == MCPT_OBJ_MESH) objects_out[no].first_tri = new_first[(size_t)oi];
+        }
+        ++no;
+    }
+    if (no == 0) {
+        *err = "no visible object";
+        return MCPT_ERR_ARG;
+    }
+    if (n_objects_out) *n_objects_out = no;
+    if (n_triangles_out) *n_triangles_out = nt;
     return MCPT_OK;
 }
 

@@ -107,15 +107,64 @@ SceneMeta meta_of(const HostScene &hs) {
     return m;
 }
 
+// What the device builders need to leave hidden objects out (VisTable, csrc/mcpt_lbvh.h): one {first_slot, first_tri, count} entry per
+// visible mesh in triangle-array order, and the visible sphere objects.  A few bytes per object; formed on the host from the object list.
+struct DevVis {
+    DevBuf<VisSeg> segs;
+    DevBuf<int32_t> sph;
+    int32_t n_segs = 0, n_tri = 0, n_sph = 0;
+    bool active = false;  // false: every object is visible, the builders run as they do without a table
+};
+int32_t count_visible_prims(const SceneSource &S, const std::vector<uint8_t> &visible) {
+    int32_t n = 0;
+    for (size_t o = 0; o < S.objects.size(); ++o)
+        if (visible[o]) n += S.objects[o].kind == MCPT_OBJ_MESH ? S.objects[o].n_tri : 1;
+    return n;
+}
+int upload_vis(const SceneSource &S, const std::vector<uint8_t> &visible, DevVis &dv) {
+    dv.active = std::find(visible.begin(), visible.end(), (uint8_t)0) != visible.end();
+    if (!dv.active) return MCPT_OK;
+    std::vector<VisSeg> segs;
+    std::vector<int32_t> sph;
+    for (size_t o = 0; o < S.objects.size(); ++o) {
+        if (!visible[o]) continue;
+        if (S.objects[o].kind == MCPT_OBJ_MESH) segs.push_back(VisSeg{0, S.objects[o].first_tri, S.objects[o].n_tri});
+        else sph.push_back((int32_t)o);
+    }
+    std::sort(segs.begin(), segs.end(), [](const VisSeg &a, const VisSeg &b) { return a.first_tri < b.first_tri; });
+    int32_t slot = 0;
+    for (VisSeg &sg : segs) {
+        sg.first_slot = slot;
+        slot += sg.count;
+    }
+    dv.n_segs = (int32_t)segs.size();
+    dv.n_tri = slot;
+    dv.n_sph = (int32_t)sph.size();
+    HIP_TRY(upload(dv.segs, segs));
+    HIP_TRY(upload(dv.sph, sph));
+    return MCPT_OK;
+}
+
 // The traversal tree of a device-built scene (csrc/mcpt_lbvh.hip), from triangles and sphere records that are on the device, into
 // g.nodes / g.qnodes; the tree fields of `meta` are the builder's.
-int build_device_tree(const mcpt_triangle *d_tris, const int32_t *d_sphere_obj, int n_sph, const BuildChoice &choice, GeomBufs &g, SceneMeta &meta) {
-    const int n_prim = meta.n_triangles + n_sph;
+// `dv` active (some object is hidden): the builder gets the visible triangle ranges and the visible spheres, and the node arrays are sized
+// by the visible count.  d_spheres: the SphereRec array the builder reads (g's own unless the caller builds a tree alone).
+int build_device_tree(const mcpt_triangle *d_tris, const int32_t *d_sphere_obj, int n_sph, const BuildChoice &choice, GeomBufs &g, SceneMeta &meta,
+                      const DevVis *dv = nullptr, const SphereRec *d_spheres = nullptr) {
+    const bool masked = dv && dv->active;
+    const int n_tri = masked ? dv->n_tri : meta.n_triangles;
+    if (masked) {
+        d_sphere_obj = dv->sph.p;
+        n_sph = dv->n_sph;
+    }
+    const VisTable vt{masked ? dv->segs.p : nullptr, masked ? dv->n_segs : 0, meta.n_triangles};
+    const int n_prim = n_tri + n_sph;
+    if (n_prim < 2) return fail(MCPT_ERR_ARG, "GPU BVH build: fewer than two visible primitives");
     hipError_t e = g.nodes.alloc((size_t)n_prim - 1);
     if (e == hipSuccess) e = g.qnodes.alloc((size_t)n_prim - 1);
     LbvhResult R;
-    if (e == hipSuccess) e = build_lbvh_device(d_tris, meta.n_triangles, d_sphere_obj, g.spheres.p, n_sph, choice.quantise, meta.builder == 3 ? 1 : 0, choice.ploc_radius, choice.ploc_top,
-                                             g.nodes.p, g.qnodes.p, &R, nullptr);
+    if (e == hipSuccess) e = build_lbvh_device(d_tris, n_tri, d_sphere_obj, d_spheres ? d_spheres : g.spheres.p, n_sph, choice.quantise, meta.builder == 3 ? 1 : 0, choice.ploc_radius, choice.ploc_top,
+                                             g.nodes.p, g.qnodes.p, &R, nullptr, masked ? &vt : nullptr);
     if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? MCPT_ERR_OOM : MCPT_ERR_HIP, std::string("GPU BVH build: ") + hipGetErrorString(e));
     if (R.height > kMaxBvhHeight) return fail(MCPT_ERR_LIMIT, "the GPU-built BVH is deeper than the traversal stack (kMaxBvhHeight); use MCPT_BUILD_SAH");
     meta.root = R.root;
@@ -134,7 +183,7 @@ int build_device_tree(const mcpt_triangle *d_tris, const int32_t *d_sphere_obj, 
 // Copies the arrays of a flattened scene that depend on where its objects are into `g`; for the device builders the tree is then built
 // there from d_tris (the triangles `hs` was flattened from).  Shared by mcpt_scene_create and the host path of mcpt_scene_update.
 int upload_geometry(const HostScene &hs, const BuildChoice &choice, const mcpt_triangle *d_tris, const int32_t *d_sphere_obj, GeomBufs &g, SceneMeta &meta,
-                    double &gpu_build_ms) {
+                    double &gpu_build_ms, const DevVis *dv = nullptr) {
     hipError_t e = hipSuccess;
     auto up = [&](auto &buf, const auto &vec) {
         if (e == hipSuccess) e = upload(buf, vec);
@@ -153,7 +202,7 @@ int upload_geometry(const HostScene &hs, const BuildChoice &choice, const mcpt_t
     gpu_build_ms = 0.0;
     if (hs.builder >= 2) {  // the traversal tree is built on the device from the caller's triangles (csrc/mcpt_lbvh.hip)
         const auto tb = Clock::now();
-        const int rc = build_device_tree(d_tris, d_sphere_obj, (int)hs.sphere_objects.size(), choice, g, meta);
+        const int rc = build_device_tree(d_tris, d_sphere_obj, (int)hs.sphere_objects.size(), choice, g, meta, dv);
         if (rc != MCPT_OK) return rc;
         gpu_build_ms = ms_since(tb);
     }
@@ -275,6 +324,7 @@ int mcpt::upload_scene(const mcpt_scene_desc *desc, HostBuild &hb, int device, m
     S.materials.assign(desc->materials, desc->materials + desc->n_materials);
     S.moved.assign((size_t)desc->n_objects, 0);
     S.xf.assign((size_t)desc->n_objects * 12, 0.f);
+    S.visible.assign((size_t)desc->n_objects, 1);
     S.env = hs.env;
     if (e == hipSuccess) e = upload(sc->mats, hs.materials);
     if (e == hipSuccess) e = upload(sc->env, hs.env);
@@ -355,8 +405,11 @@ int host_positions(const SceneSource &S, int32_t n, const mcpt_object_vertices *
 // the listed meshes (touched[i] = deform[i].object) get new base positions.  Everything is built aside and committed on success.
 // `edit` (mcpt_scene_set_materials, path 0): the material table and the objects' material indices of the plan replace the scene's; the
 // host path is taken whatever the builder, and the new material table is uploaded aside with the rest.
+// `show` (mcpt_scene_set_visibility): the mask the scene gets, `touched` being the objects whose state changes; the other edits rebuild
+// with the mask the scene has.  Either way hidden objects keep current records and stay out of the tree and the light tables.  A
+// change of visibility alone moves nothing: on the device path only the tree is built again, from the arrays that are live.
 int rebuild(mcpt_scene *sc, const std::vector<uint8_t> &moved, const std::vector<float> &xf, const std::vector<int32_t> &touched,
-            const mcpt_object_vertices *deform, mcpt_update_info *info, const mat::EditPlan *edit = nullptr) {
+            const mcpt_object_vertices *deform, mcpt_update_info *info, const mat::EditPlan *edit = nullptr, const std::vector<uint8_t> *show = nullptr) {
     const auto t0 = Clock::now();
     mcpt_update_info ui;
     std::memset(&ui, 0, sizeof ui);
@@ -382,7 +435,24 @@ int rebuild(mcpt_scene *sc, const std::vector<uint8_t> &moved, const std::vector
     std::vector<std::vector<float>> fetched;  // deformation: positions downloaded from device pointers
     std::vector<const float *> pos;
     DevBuf<MaterialRec> mats2;  // material edit: the new table, swapped with sc->mats on success
-    if (meta.builder >= 2 && !emitter && !edit) {
+    const std::vector<uint8_t> &visible = show ? *show : S.visible;
+    DevVis dv;
+    if (show && meta.builder >= 2 && !emitter) {
+        // ---- device path of a change of visibility: the tables of the visible ranges cross the bus, the device builder runs on the live
+        // triangles and sphere records, and the node arrays alone are exchanged
+        ui.path = 1;
+        const auto tt = Clock::now();
+        int rc = upload_vis(S, visible, dv);
+        if (rc != MCPT_OK) return rc;
+        ui.transform_ms = ms_since(tt);
+        const auto tb = Clock::now();
+        rc = build_device_tree(sc->geom.tris.p ? sc->geom.tris.p : sc->tris0.p, sc->sphere_obj.p, (int)sc->sphere_obj.n, S.choice, g2, meta, &dv, sc->geom.spheres.p);
+        if (rc == MCPT_OK && traversal_stack_entries(meta.height) < meta.height - 1)
+            rc = fail(MCPT_ERR_LIMIT, "the BVH is deeper than the traversal stack (kMaxBvhHeight)");
+        if (rc != MCPT_OK) return rc;
+        ui.build_ms = ms_since(tb);
+        sc->geom.swap_nodes(g2);
+    } else if (meta.builder >= 2 && !emitter && !edit) {
         // ---- device path: the listed triangles and sphere centres are moved in HBM, the device builder runs again
         ui.path = 1;
         const auto tu = Clock::now();
@@ -460,9 +530,11 @@ int rebuild(mcpt_scene *sc, const std::vector<uint8_t> &moved, const std::vector
             HIP_TRY(hipGetLastError());
             HIP_TRY(hipStreamSynchronize(nullptr));
         }
+        int rc = upload_vis(S, visible, dv);
+        if (rc != MCPT_OK) return rc;
         ui.transform_ms = ms_since(tt);
         const auto tb = Clock::now();
-        int rc = build_device_tree(g2.tris.p, sc->sphere_obj.p, (int)sc->sphere_obj.n, S.choice, g2, meta);
+        rc = build_device_tree(g2.tris.p, sc->sphere_obj.p, (int)sc->sphere_obj.n, S.choice, g2, meta, &dv);
         if (rc == MCPT_OK && traversal_stack_entries(meta.height) < meta.height - 1)
             rc = fail(MCPT_ERR_LIMIT, "the BVH is deeper than the traversal stack (kMaxBvhHeight)");
         if (rc != MCPT_OK) return rc;
@@ -519,17 +591,23 @@ int rebuild(mcpt_scene *sc, const std::vector<uint8_t> &moved, const std::vector
         d.materials = mats.data();
         HostScene hs;
         const char *err = "";
-        int rc = build_host_scene(d, hs, &err, S.choice);
-        if (rc != MCPT_OK) return fail(rc, std::string(edit ? "mcpt_scene_set_materials: " : (deform ? "mcpt_scene_deform: " : "mcpt_scene_update: ")) + err);
+        const bool masked = std::find(visible.begin(), visible.end(), (uint8_t)0) != visible.end();
+        int rc = build_host_scene(d, hs, &err, S.choice, masked ? visible.data() : nullptr);
+        if (rc != MCPT_OK)
+            return fail(rc, std::string(show ? "mcpt_scene_set_visibility: " : (edit ? "mcpt_scene_set_materials: " : (deform ? "mcpt_scene_deform: " : "mcpt_scene_update: "))) + err);
         const double host_build_ms = ms_since(tb);
         const auto tu = Clock::now();
         const int32_t env_w = meta.env_w, env_h = meta.env_h;  // (the environment map is not part of desc': it stays where it is)
         meta = meta_of(hs);
         meta.env_w = env_w;
         meta.env_h = env_h;
-        if (hs.builder >= 2) HIP_TRY(upload(g2.tris, tris));
+        if (hs.builder >= 2) {
+            HIP_TRY(upload(g2.tris, tris));
+            rc = upload_vis(S, visible, dv);
+            if (rc != MCPT_OK) return rc;
+        }
         double gpu_build_ms = 0.0;
-        rc = upload_geometry(hs, S.choice, g2.tris.p, sc->sphere_obj.p, g2, meta, gpu_build_ms);
+        rc = upload_geometry(hs, S.choice, g2.tris.p, sc->sphere_obj.p, g2, meta, gpu_build_ms, &dv);
         if (rc != MCPT_OK) return rc;
         ui.build_ms = host_build_ms + gpu_build_ms;
         if (deform && hs.builder >= 2) HIP_TRY(upload(base2, base));
@@ -558,6 +636,7 @@ int rebuild(mcpt_scene *sc, const std::vector<uint8_t> &moved, const std::vector
     sc->meta = meta;
     S.moved = moved;
     S.xf = xf;
+    if (show) S.visible = *show;
     fill_view(sc);
     ui.total_ms = ms_since(t0);
     if (info) *info = ui;
@@ -604,6 +683,38 @@ int mcpt::apply_deform(mcpt_scene *sc, int32_t n, const mcpt_object_vertices *it
     std::vector<int32_t> touched;
     for (int32_t i = 0; i < n; ++i) touched.push_back(items[i].object);
     return rebuild(sc, sc->src.moved, sc->src.xf, touched, n > 0 ? items : nullptr, info);
+}
+
+int mcpt::check_visibility(const mcpt_scene *sc, int32_t n, const mcpt_object_visibility *items, std::vector<uint8_t> &visible, std::vector<int32_t> &changed) {
+    if (!sc) return fail(MCPT_ERR_ARG, "mcpt_scene_set_visibility: null scene");
+    if (n < 0) return fail(MCPT_ERR_ARG, "mcpt_scene_set_visibility: n < 0");
+    if (n > 0 && !items) return fail(MCPT_ERR_ARG, "mcpt_scene_set_visibility: null items");
+    const SceneSource &S = sc->src;
+    visible = S.visible;
+    changed.clear();
+    std::vector<uint8_t> listed(S.objects.size(), 0);
+    for (int32_t i = 0; i < n; ++i) {
+        const int32_t o = items[i].object;
+        if (o < 0 || o >= (int32_t)S.objects.size()) return fail(MCPT_ERR_ARG, "mcpt_scene_set_visibility: object index " + std::to_string(o) + " out of range");
+        if (listed[(size_t)o]) return fail(MCPT_ERR_ARG, "mcpt_scene_set_visibility: object " + std::to_string(o) + " is listed twice");
+        if (items[i].visible != 0 && items[i].visible != 1) return fail(MCPT_ERR_ARG, "mcpt_scene_set_visibility: item " + std::to_string(i) + ": visible is not 0 or 1");
+        listed[(size_t)o] = 1;
+        visible[(size_t)o] = (uint8_t)items[i].visible;
+    }
+    if (S.choice.builder == MCPT_BUILD_SAH && S.choice.instancing == 1)
+        return fail(MCPT_ERR_ARG, "mcpt_scene_set_visibility: the scene was built with node instancing on (instanced subtrees are shared between objects)");
+    for (size_t o = 0; o < visible.size(); ++o)
+        if (visible[o] != S.visible[o]) changed.push_back((int32_t)o);
+    if (changed.empty()) return MCPT_OK;
+    const int32_t n_prims = count_visible_prims(S, visible);
+    if (n_prims == 0) return fail(MCPT_ERR_ARG, "mcpt_scene_set_visibility: no object would be visible (a scene cannot be empty)");
+    if (sc->meta.builder >= 2 && n_prims < 2)  // (build_lbvh_device needs two primitives; creation falls back to the host builder, a live scene keeps its builder)
+        return fail(MCPT_ERR_ARG, "mcpt_scene_set_visibility: a device-built scene needs at least two visible primitives");
+    return MCPT_OK;
+}
+
+int mcpt::apply_visibility(mcpt_scene *sc, const std::vector<uint8_t> &visible, const std::vector<int32_t> &changed, mcpt_update_info *info) {
+    return rebuild(sc, sc->src.moved, sc->src.xf, changed, nullptr, info, nullptr, &visible);
 }
 
 int mcpt::check_material_edit(const mcpt_scene *sc, int32_t n_edits, const mcpt_material_edit *edits, int32_t n_assign, const mcpt_object_material *assign,
@@ -768,6 +879,33 @@ int mcpt_scene_set_environment(mcpt_scene *sc, const float background[3], int32_
     const int rc = check_environment(sc, background, env_w, env_h, env_pixels);
     if (rc != MCPT_OK) return rc;
     return apply_environment(sc, background, env_w, env_h, env_pixels, info);
+}
+
+int mcpt_scene_set_visibility(mcpt_scene *sc, int32_t n, const mcpt_object_visibility *items, mcpt_update_info *info) {
+    std::vector<uint8_t> visible;
+    std::vector<int32_t> changed;
+    const int rc = check_visibility(sc, n, items, visible, changed);
+    if (rc != MCPT_OK) return rc;
+    return apply_visibility(sc, visible, changed, info);
+}
+
+int mcpt_scene_get_visibility(const mcpt_scene *sc, int32_t n_objects, uint8_t *visible, int32_t *n_visible_prims) {
+    if (!sc) return fail(MCPT_ERR_ARG, "mcpt_scene_get_visibility: null scene");
+    const SceneSource &S = sc->src;
+    if (visible) {
+        if (n_objects != (int32_t)S.objects.size()) return fail(MCPT_ERR_ARG, "mcpt_scene_get_visibility: n_objects is not the scene's object count");
+        std::memcpy(visible, S.visible.data(), S.visible.size());
+    }
+    if (n_visible_prims) *n_visible_prims = count_visible_prims(S, S.visible);
+    return MCPT_OK;
+}
+
+int mcpt_compact_scene(const mcpt_scene_desc *desc, const uint8_t *visible, mcpt_object *objects_out, mcpt_triangle *triangles_out, int32_t *n_objects_out,
+                       int32_t *n_triangles_out, int32_t *prim_map) {
+    if (!desc || !visible) return fail(MCPT_ERR_ARG, "mcpt_compact_scene: null argument");
+    const char *err = "";
+    const int rc = compact_scene_desc(*desc, visible, objects_out, triangles_out, n_objects_out, n_triangles_out, prim_map, &err);
+    return rc == MCPT_OK ? rc : fail(rc, std::string("mcpt_compact_scene: ") + err);
 }
 
 int mcpt_scene_snapshot(mcpt_scene *sc) {

@@ -22,6 +22,7 @@ EXPORTS = ["mcpt_scene_create", "mcpt_scene_destroy", "mcpt_render", "mcpt_rende
            "mcpt_scene_update", "mcpt_group_update", "mcpt_transform_triangles",
            "mcpt_scene_deform", "mcpt_group_deform", "mcpt_deform_triangles",
            "mcpt_scene_set_materials", "mcpt_scene_set_environment", "mcpt_group_set_materials", "mcpt_group_set_environment",
+           "mcpt_scene_set_visibility", "mcpt_scene_get_visibility", "mcpt_group_set_visibility", "mcpt_compact_scene",
            "mcpt_scene_snapshot", "mcpt_render_motion", "mcpt_temporal_blend", "mcpt_temporal_accumulate",
            "mcpt_temporal_accumulate_ex",
            "mcpt_sequence_create", "mcpt_sequence_frame", "mcpt_sequence_reset", "mcpt_sequence_destroy",
@@ -230,7 +231,21 @@ class ObjectMaterial(C.Structure):
     _fields_ = [("object", C.c_int32), ("material", C.c_int32)]
 
 
-assert C.sizeof(Material) == 44 and C.sizeof(MaterialEdit) == 48 and C.sizeof(ObjectMaterial) == 8
+class ObjectVisibility(C.Structure):
+    _fields_ = [("object", C.c_int32), ("visible", C.c_int32)]
+
+
+assert C.sizeof(Material) == 44 and C.sizeof(MaterialEdit) == 48 and C.sizeof(ObjectMaterial) == 8 and C.sizeof(ObjectVisibility) == 8
+
+
+def _visibility_items(items):
+    """An iterable of (object index, visible) as an array of mcpt_object_visibility.  `visible` is a bool, or the integer to pass as it
+    is (the library refuses anything but 0 and 1)."""
+    items = list(items)
+    arr = (ObjectVisibility * max(len(items), 1))()
+    for k, (obj, vis) in enumerate(items):
+        arr[k].object, arr[k].visible = int(obj), int(vis)
+    return arr, len(items)
 
 
 def _material_lists(edits, assign):
@@ -527,6 +542,14 @@ def lib(path=None):
         L.mcpt_group_set_materials.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
         L.mcpt_group_set_environment.restype = C.c_int
         L.mcpt_group_set_environment.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
+        L.mcpt_scene_set_visibility.restype = C.c_int
+        L.mcpt_scene_set_visibility.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(UpdateInfo)]
+        L.mcpt_scene_get_visibility.restype = C.c_int
+        L.mcpt_scene_get_visibility.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(C.c_int32)]
+        L.mcpt_group_set_visibility.restype = C.c_int
+        L.mcpt_group_set_visibility.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+        L.mcpt_compact_scene.restype = C.c_int
+        L.mcpt_compact_scene.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p]
         L.mcpt_deform_triangles.restype = C.c_int
         L.mcpt_deform_triangles.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
         L.mcpt_group_create.restype = C.c_int
@@ -615,6 +638,23 @@ def deform_triangles(positions, tris, out=None):
         raise ValueError("deform_triangles: arrays of 60-byte triangles with one shape")
     _check(lib().mcpt_deform_triangles(tris.size, _ptr(positions), _ptr(tris), _ptr(out)))
     return out
+
+
+def compact_scene(sd, visible):
+    """mcpt_compact_scene (host only): the description without the objects whose entry of `visible` (one per object) is false.  Returns
+    (SceneData, prim_map): prim_map[p] is the id that primitive p of `sd` has in the result, -1 if it is hidden."""
+    import dataclasses
+    vis = np.ascontiguousarray(np.asarray(visible).astype(bool), dtype=np.uint8)
+    if vis.shape != (len(sd.objects),):
+        raise ValueError("compact_scene: one flag per object (%d), not %s" % (len(sd.objects), vis.shape))
+    keep = []
+    d = _make_desc(sd, keep)
+    no, nt = C.c_int32(0), C.c_int32(0)
+    prim_map = np.full(len(sd.triangles) + len(sd.objects), -1, np.int32)
+    _check(lib().mcpt_compact_scene(C.byref(d), _ptr(vis), None, None, C.byref(no), C.byref(nt), _ptr(prim_map)))
+    objects, triangles = np.zeros(no.value, sd.objects.dtype), np.zeros(nt.value, sd.triangles.dtype)
+    _check(lib().mcpt_compact_scene(C.byref(d), _ptr(vis), _ptr(objects), _ptr(triangles), C.byref(no), C.byref(nt), _ptr(prim_map)))
+    return dataclasses.replace(sd, objects=objects, triangles=triangles), prim_map
 
 
 def cull_bound(camera, root_min, root_max, library=None):
@@ -706,6 +746,21 @@ class HipScene:
         info = UpdateInfo()
         _check(self.L.mcpt_scene_set_materials(self.h, ne, C.cast(ea, C.c_void_p), na, C.cast(aa, C.c_void_p), C.byref(info)), L=self.L)
         return info.as_dict()
+
+    def set_visibility(self, items):
+        """mcpt_scene_set_visibility: items = an iterable of (object index, visible).  Hidden objects leave the tree and the light tables
+        and keep their records and ids; afterwards the scene behaves like one created from compact_scene(current description, mask).
+        Returns mcpt_update_info as a dict."""
+        arr, n = _visibility_items(items)
+        info = UpdateInfo()
+        _check(self.L.mcpt_scene_set_visibility(self.h, n, C.cast(arr, C.c_void_p), C.byref(info)), L=self.L)
+        return info.as_dict()
+
+    def visibility(self):
+        """mcpt_scene_get_visibility: (mask as a uint8 array with one entry per object, number of primitives in the tree)."""
+        mask, n = np.zeros(len(self.sd.objects), np.uint8), C.c_int32(0)
+        _check(self.L.mcpt_scene_get_visibility(self.h, len(mask), _ptr(mask), C.byref(n)), L=self.L)
+        return mask, int(n.value)
 
     def set_environment(self, background, env=None):
         """mcpt_scene_set_environment: the background colour and the environment map (an (h, w, 3) float32 array, or None for the constant
@@ -1483,6 +1538,13 @@ class HipGroup:
         bg, w, h, px, keep = _environment(background, env)
         rc = self.L.mcpt_group_set_environment(self.h, C.cast(bg, C.c_void_p), w, h, px)
         del keep
+        if rc != 0:
+            raise McptError(rc, self.L.mcpt_group_last_error().decode("utf-8", "replace"))
+
+    def set_visibility(self, items):
+        """mcpt_group_set_visibility: HipScene.set_visibility on every replica."""
+        arr, n = _visibility_items(items)
+        rc = self.L.mcpt_group_set_visibility(self.h, n, C.cast(arr, C.c_void_p))
         if rc != 0:
             raise McptError(rc, self.L.mcpt_group_last_error().decode("utf-8", "replace"))
 

@@ -211,6 +211,45 @@ void Scene::allTransformsPending() {  // a fresh scene holds the geometry as it 
     pendingTransforms.clear();
     for (const auto &kv : objectTransforms) pendingTransforms.push_back(kv.first);
     applyTransforms();
+    pendingVisible.clear();  // (and every object is visible in it: the states set so far likewise)
+    for (const auto &kv : objectVisible)
+        if (!kv.second) pendingVisible.push_back(kv.first);
+    applyVisibility();
+}
+
+void Scene::setVisible(int object, bool visible) {
+    if (object < 0 || (size_t)object >= objects.size()) {
+        std::cerr << "mcpt: Scene::setVisible: object " << object << " is not in the scene" << std::endl;
+        return;
+    }
+    objectVisible[object] = visible;
+    if (!gpu && !group) return;  // buildBVH applies it
+    if (std::find(pendingVisible.begin(), pendingVisible.end(), object) == pendingVisible.end()) pendingVisible.push_back(object);
+}
+
+std::vector<int32_t> Scene::hidden() const {
+    std::vector<int32_t> out;
+    for (const auto &kv : objectVisible)
+        if (!kv.second) out.push_back((int32_t)kv.first);
+    return out;
+}
+
+void Scene::applyVisibility() const {
+    if (pendingVisible.empty() || (!gpu && !group)) return;
+    std::vector<mcpt_object_visibility> items;
+    for (int o : pendingVisible) items.push_back(mcpt_object_visibility{(int32_t)o, objectVisible.at(o) ? 1 : 0});
+    pendingVisible.clear();
+    if (group) {
+        if (mcpt_group_set_visibility(group, (int32_t)items.size(), items.data()) != MCPT_OK) std::cerr << "mcpt: " << mcpt_group_last_error() << std::endl;
+        return;
+    }
+    mcpt_update_info ui{};
+    if (mcpt_scene_set_visibility(gpu, (int32_t)items.size(), items.data(), &ui) != MCPT_OK) {
+        std::cerr << "mcpt: " << mcpt_last_error() << std::endl;
+        return;
+    }
+    std::cout << "[mcpt] visibility (" << (ui.path ? "device" : "host") << " path): " << items.size() << " objects, " << ui.n_moved_tris << " triangles, "
+              << ui.total_ms << " ms (tree " << ui.build_ms << " ms)" << std::endl;
 }
 
 void Scene::setTransform(Object *object, const float m[12]) {
@@ -432,6 +471,9 @@ uint32_t scene_hash(const Scene &scene) {
     // where the objects are now (Scene::setTransform): a resume after a move is refused like any other change of the scene
     const std::vector<mcpt_object_transform> xf = scene.transforms();
     if (!xf.empty()) h = fnv1a(xf.data(), xf.size() * sizeof(mcpt_object_transform), h);
+    // and which of them are hidden (Scene::setVisible)
+    const std::vector<int32_t> hid = scene.hidden();
+    if (!hid.empty()) h = fnv1a(hid.data(), hid.size() * sizeof(int32_t), h);
     return h;
 }
 

@@ -229,6 +229,14 @@ class Scene {
     // the transforms set so far, in Scene::Add order (object = index into `objects`); objects that are not in the scene are left out
     std::vector<mcpt_object_transform> transforms() const;
 
+    // Hides or shows an object (index into `objects`, Scene::Add order; every object is visible until hidden).  A hidden object keeps its
+    // geometry, transform and material and stays out of the tree and the light tables (mcpt_scene_set_visibility: primitive ids do not
+    // change).  Like setTransform it takes effect at the next buildBVH(), or, when the scene is already built, at the next render,
+    // intersect or castRay (mcpt_scene_set_visibility / mcpt_group_set_visibility).  An index outside the scene is ignored with a message.
+    void setVisible(int object, bool visible);
+    // the hidden objects, ascending
+    std::vector<int32_t> hidden() const;
+
     // Relights a live scene (mcpt_scene_set_materials / mcpt_scene_set_environment, or their group forms after setDevices).
     // setMaterial gives the object's material the values of `m`: the scene's material table is fixed once built, so a material the scene
     // does not hold cannot be added; the object's own entry is edited, which is refused (false, with a message) when another object
@@ -242,6 +250,7 @@ class Scene {
     // used by Renderer
     mcpt_scene *handle() const {  // (with several GPUs: the replica on the first one)
         applyTransforms();
+        applyVisibility();
         return group ? mcpt_group_scene(group, 0) : gpu;
     }
     // More than one entry: the frame is rendered by all listed GPUs (mcpt_group_*: tile partition + RCCL merge inside the
@@ -249,6 +258,7 @@ class Scene {
     void setDevices(const std::vector<int> &d) { devices = d; }
     mcpt_group *groupHandle() const {
         applyTransforms();
+        applyVisibility();
         return group;
     }
     mcpt_params params(int spp) const;
@@ -267,6 +277,9 @@ class Scene {
     void applyTransforms() const;  // sends the transforms set since the last call to the live scene
     std::map<const Object *, std::array<float, 12>> objectTransforms;
     mutable std::vector<const Object *> pendingTransforms;
+    void applyVisibility() const;  // sends the states set since the last call to the live scene
+    std::map<int, bool> objectVisible;         // the objects setVisible was called for
+    mutable std::vector<int> pendingVisible;   // those of them the live scene has not heard of yet
     // the Material every object pointed to when buildBVH() numbered the library's material table (flatten(): order of first
     // appearance); setMaterial on a built scene reads the numbering from here, not from pointers that may have changed since
     std::vector<const Material *> builtMaterialOf;

@@ -283,6 +283,57 @@ int mcpt_scene_set_materials(mcpt_scene *scene, int32_t n_edits, const mcpt_mate
 int mcpt_scene_set_environment(mcpt_scene *scene, const float background[3], int32_t env_w, int32_t env_h, const float *env_pixels,
                                mcpt_update_info *info /* nullable */);
 
+/* ---- Hiding and showing objects in a live scene: per-object visibility.
+ *
+ * mcpt_scene_set_visibility takes the primitives of hidden objects out of the traversal tree and, for emitters, out of the light tables.
+ *   Visibility is ABSOLUTE and per object: an object listed in a call gets that state, an object not listed keeps the one it had, every
+ *   object is visible after creation.  A hidden object keeps its records, its base geometry, its transform and its material where they
+ *   are: mcpt_scene_update, mcpt_scene_deform and mcpt_scene_set_materials act on it as on any object (their path rules look at the
+ *   listed objects as before, visible or not), it stays hidden until it is shown, and it then appears where those calls left it.
+ *   Primitive ids never change: a triangle index, or n_triangles + object for a sphere.
+ * THE CONTRACT: after the call every entry point listed at mcpt_scene_update gives what it gives on
+ *       mcpt_scene_create_ex(compact(desc'), device, the same options)
+ * where desc' is the scene's current description (latest bases, current transforms, current materials) and compact() is
+ * mcpt_compact_scene with the scene's mask.  Primitive ids are translated through its prim_map: mcpt_intersect's out_prim, the leaves of
+ * mcpt_scene_dump_bvh, the candidate ids of mcpt_debug_classify, the triangle ids of the light tables.  Everything else equals the fresh
+ * scene bit for bit with the host builders (frames, mcpt_stats work counters, AOVs, motion, cast rays, light samples, node boxes and
+ * quantised boxes), and by the rule of mcpt_scene_update with the device builders.
+ *   mcpt_scene_get_info: n_nodes, bvh_height, quantised and n_lights are those of the fresh scene; n_prims stays the number of STORED
+ *   records.  lds_resident is decided as at creation from the stored record counts and the new tree, since the stored arrays are what the
+ *   LDS kernels copy: it can be 0 where the fresh compacted scene's is 1, never the other way round.
+ *   info->path 1  device: the scene was built by MCPT_BUILD_GPU_LBVH or MCPT_BUILD_GPU_PLOC and no object whose state changes emits
+ *                 light.  Only the tree is rebuilt, from the live triangles and sphere records: no record array is copied or written, and
+ *                 only a table of the visible triangle ranges and the list of visible spheres cross the bus (transform_ms; build_ms is
+ *                 the builder).
+ *   info->path 0  host: every host-built scene, and any scene when an emitter is hidden or shown (the light tables, the emitters'
+ *                 bounding sphere and n_lights change).  As path 0 of mcpt_scene_update; the creation code gets the mask and only
+ *                 shortens the primitive lists it hands to the tree builders and the light table.
+ *   info->n_moved_tris is the number of triangles of the meshes whose state changed.  A call after which no object's state differs
+ *   (n == 0 included) rebuilds nothing and returns MCPT_OK with build_ms == 0.
+ * MCPT_ERR_ARG, before any device call: scene == NULL; n < 0; n > 0 with items == NULL; an object index out of range; an object listed
+ * twice in one call; visible not 0 or 1; a scene built with node instancing on; a result with no visible object (a scene cannot be
+ * empty); on a device-built scene a result with fewer than two visible primitives (the device builders need two).  A refused call, and a
+ * call whose rebuild fails (MCPT_ERR_LIMIT, MCPT_ERR_OOM), leaves the scene exactly as it was, mask included: the new tree is built aside
+ * and swapped in on success.  Blocking, on the null stream, like mcpt_scene_update.
+ * Temporal reuse: ids are stable, so the snapshot of mcpt_scene_snapshot keeps holding every record, hidden ones included, and keeps
+ * pairing hits with previous positions.  An object shown again reports motion against where its records were at the snapshot, with
+ * `valid` as for any object; the stale history behind it is rejected by the blend's depth validation and the colour clamp
+ * (mcpt_history_opts), or by mcpt_sequence_reset. */
+typedef struct { int32_t object; int32_t visible; } mcpt_object_visibility; /* 8 bytes; visible 0 | 1 */
+int mcpt_scene_set_visibility(mcpt_scene *scene, int32_t n, const mcpt_object_visibility *items, mcpt_update_info *info /* nullable */);
+/* The mask (visible: n_objects bytes, nullable; n_objects must then be the scene's object count) and the number of primitives in the
+ * tree (nullable). */
+int mcpt_scene_get_visibility(const mcpt_scene *scene, int32_t n_objects, uint8_t *visible /* nullable */, int32_t *n_visible_prims /* nullable */);
+/* Host only, no GPU needed: the description without its hidden objects, which defines what a scene with that mask is compared with.
+ * The visible objects are kept in their order and the triangles of the visible meshes in array order, with first_tri rewritten;
+ * materials and the environment are the caller's own (not copied).  objects_out: room for n_objects, triangles_out: room for
+ * n_triangles; both may be NULL to get the counts and the map only.  prim_map (nullable, n_triangles + n_objects entries): prim_map[p] is
+ * the id live primitive p has in the compacted description, or -1 if it is hidden (entries n_triangles + o of mesh objects are -1 too).
+ * The map is strictly increasing over the visible ids, so "the larger id wins a tie" means the same on both sides.
+ * MCPT_ERR_ARG for a null desc or visible, for a description that creation would refuse, and for a mask that hides every object. */
+int mcpt_compact_scene(const mcpt_scene_desc *desc, const uint8_t *visible /* n_objects */, mcpt_object *objects_out, mcpt_triangle *triangles_out,
+                       int32_t *n_objects_out, int32_t *n_triangles_out, int32_t *prim_map /* n_triangles + n_objects entries */);
+
 /* Replaces the pixel/spp loop of Renderer::Render (Renderer.cpp:21-91): fb_host = W*H*3 floats,
  * row-major m = j*W + i, linear radiance averaged over spp -- what `framebuffer` holds at Renderer.cpp:91.
  * Blocking.  Tone map and PNG output (Renderer.cpp:95-109) stay with the caller. */
@@ -1058,6 +1109,9 @@ int mcpt_group_set_environment(mcpt_group *group, const float background[3], int
 /* mcpt_scene_deform on every replica, host pointers only: an item with on_device 1 is refused with MCPT_ERR_ARG, since one pointer
  * cannot be valid on several devices.  If a replica fails, the replicas that had succeeded get their previous positions back. */
 int mcpt_group_deform(mcpt_group *group, int32_t n, const mcpt_object_vertices *items);
+/* mcpt_scene_set_visibility on every replica, with the same checks before any device call.  If a replica fails, the replicas that had
+ * succeeded get their previous mask back. */
+int mcpt_group_set_visibility(mcpt_group *group, int32_t n, const mcpt_object_visibility *items);
 void mcpt_group_destroy(mcpt_group *group);
 const char *mcpt_group_last_error(void);
 
