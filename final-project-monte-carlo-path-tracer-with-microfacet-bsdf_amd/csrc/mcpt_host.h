@@ -1,9 +1,10 @@
 // The host layer behind the C ABI (include/mcpt.h): error plumbing, the owners of device resources, the wavefront workspace, the
 // environment knobs, the event timer, struct mcpt_scene, and what its translation units call in each other:
 //   mcpt_wavefront.hip  the wavefront loop, workspace / pass sizing (render_list), the pixel list and sky cull set-up
-//   mcpt_upload.hip     scene create / upload / update / material and environment edits / visibility / snapshot / destroy / info, the BVH dumps
-//   mcpt_update.hip     the kernels that move and deform objects in HBM (the device path of mcpt_scene_update / mcpt_scene_deform),
-//                       mcpt_transform_triangles, mcpt_deform_triangles
+//   mcpt_upload.hip     scene create / upload / update / material and environment edits / visibility / added objects / snapshot / destroy /
+//                       info, the BVH dumps
+//   mcpt_update.hip     the kernels that move, deform and add objects in HBM (the device path of mcpt_scene_update / mcpt_scene_deform /
+//                       mcpt_scene_add_objects), mcpt_transform_triangles, mcpt_deform_triangles
 //   mcpt_render.hip     the frame-level entry points (render, adaptive, AOVs, denoise, motion, temporal blend); mcpt_frame.h has what
 //                       it shares with
 //   mcpt_sequence.hip   mcpt_temporal_accumulate and mcpt_sequence_*: a frame loop whose history and buffers stay on the device
@@ -399,6 +400,26 @@ void launch_deform_objects(const DeformSeg *d_segs, int32_t n_segs, int32_t n_la
 void launch_set_materials(const mat::MatSeg *d_segs, int32_t n_segs, int32_t n_lanes, TriGeom *tri_geom, TriShade *tri_shade, SphereRec *spheres,
                           hipStream_t s);
 
+// One run of lanes of k_add_objects (csrc/mcpt_update.hip): the triangles of one added mesh, or one added sphere.  Three 16-byte quarters.
+struct alignas(16) AddSeg {
+    int32_t first_lane;  // lanes [first_lane, first_lane + count) work on this segment
+    int32_t count;       // mesh: its triangles; sphere: 1
+    int32_t first_tri;   // mesh: its first triangle in the extended arrays; sphere: -1
+    int32_t object;      // sphere: its slot in the SphereRec array
+    uint32_t mat_bits;   // TriGeom::mat_bits / SphereRec::mat_bits (mat::tri_mat_bits / sphere_mat_bits)
+    int32_t mat;         // TriShade::mat / SphereRec::mat
+    float radius;        // sphere
+    int32_t pad0;
+    float c[3];          // sphere: its centre
+    int32_t pad1;
+};
+static_assert(sizeof(AddSeg) == 48, "AddSeg must be 48 bytes");
+// Writes, for every lane of the listed segments, the WHOLE records of an added primitive: a triangle lane reads its triangle from tris0
+// (the appended tail of the base array), stores it into tris_cur and writes its TriGeom and TriShade records; a sphere lane writes its
+// SphereRec.  Nothing is loaded from the record arrays.
+void launch_add_objects(const AddSeg *d_segs, int32_t n_segs, int32_t n_lanes, const mcpt_triangle *tris0, mcpt_triangle *tris_cur, TriGeom *tri_geom,
+                        TriShade *tri_shade, SphereRec *spheres, hipStream_t s);
+
 }  // namespace mcpt
 
 // Members are destroyed in reverse order, with the scene's device current (mcpt_scene_destroy): the pools' workspaces and timers, their
@@ -425,6 +446,7 @@ struct mcpt_scene {
     mcpt::DevBuf<float> stage;           // its staging buffer for host positions (36 B per triangle, grows to the largest call)
     mcpt::DevBuf<uint32_t> dflag;        // and its flag word (a position that is not finite)
     mcpt::DevBuf<mcpt::mat::MatSeg> msegs;  // the segment table of k_set_materials
+    mcpt::DevBuf<mcpt::AddSeg> asegs;    // the segment table of k_add_objects
     mcpt::DevBuf<mcpt::MaterialRec> mats;
     mcpt::DevBuf<mcpt::InstRec> inst;
     mcpt::DevBuf<float> env;
@@ -490,6 +512,23 @@ int apply_material_edit(mcpt_scene *sc, const mat::EditPlan &plan, mcpt_update_i
 // mcpt_group_set_visibility when another replica fails.
 int check_visibility(const mcpt_scene *sc, int32_t n, const mcpt_object_visibility *items, std::vector<uint8_t> &visible, std::vector<int32_t> &changed);
 int apply_visibility(mcpt_scene *sc, const std::vector<uint8_t> &visible, const std::vector<int32_t> &changed, mcpt_update_info *info);
+// mcpt_scene_add_objects in two halves, as above.  Everything a scene holds per primitive or per object is built aside in an AddAside and
+// exchanged with the scene's as the last step, so after a successful apply_add the AddAside holds what the scene had before:
+// undo_add puts it back (mcpt_group_add_objects, when another replica fails).  Freed with the scene's device current.
+struct AddAside {
+    GeomBufs geom;
+    DevBuf<mcpt_triangle> tris0;
+    DevBuf<int32_t> sphere_obj;
+    DevBuf<MaterialRec> mats;
+    DevBuf<TriGeom> snap_tri;
+    DevBuf<SphereRec> snap_sph;
+    SceneMeta meta;
+    bool lights = false;  // the light tables are part of the exchange (path 0)
+    size_t n_objects = 0, n_triangles = 0, n_materials = 0;  // what the scene's description held before the call
+};
+int check_add(const mcpt_scene *sc, const mcpt_scene_addition *add);
+int apply_add(mcpt_scene *sc, const mcpt_scene_addition *add, int32_t *first_object, mcpt_update_info *info, AddAside *keep = nullptr);
+int undo_add(mcpt_scene *sc, AddAside &aside);
 int check_environment(const mcpt_scene *sc, const float *background, int32_t env_w, int32_t env_h, const float *env_pixels);
 int apply_environment(mcpt_scene *sc, const float *background, int32_t env_w, int32_t env_h, const float *env_pixels, mcpt_update_info *info);
 double warm_up_device(int device);

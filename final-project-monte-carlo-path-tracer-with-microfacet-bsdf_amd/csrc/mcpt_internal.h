@@ -185,5 +185,11 @@ int build_host_scene(const mcpt_scene_desc &d, HostScene &out, const char **err,
 // mcpt_compact_scene (include/mcpt.h) after the null checks.
 int compact_scene_desc(const mcpt_scene_desc &d, const uint8_t *visible, mcpt_object *objects_out, mcpt_triangle *triangles_out, int32_t *n_objects_out,
                        int32_t *n_triangles_out, int32_t *prim_map, const char **err);
+// The argument checks of mcpt_scene_add_objects that need no scene handle: the addition against a description of n_objects objects,
+// n_triangles triangles and n_materials materials (only the counts of the base enter).
+int check_scene_addition(int32_t n_objects, int32_t n_triangles, int32_t n_materials, const mcpt_scene_addition &a, const char **err);
+// mcpt_extend_scene (include/mcpt.h) after the null checks: the checks of creation on `d`, check_scene_addition, then the append.
+int extend_scene_desc(const mcpt_scene_desc &d, const mcpt_scene_addition &a, mcpt_object *objects_out, mcpt_triangle *triangles_out,
+                      mcpt_material *materials_out, int32_t *n_objects_out, int32_t *n_triangles_out, int32_t *n_materials_out, const char **err);
 
 }  // namespace mcpt

@@ -18,6 +18,7 @@
 #include <chrono>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <thread>
 #include <vector>
@@ -348,6 +349,26 @@ int mcpt_group_set_visibility(mcpt_group *g, int32_t n, const mcpt_object_visibi
     const std::vector<uint8_t> old = g->scenes[0]->src.visible;  // the way back: the same objects change state again
     return on_replicas(g, "mcpt_group_set_visibility", [&](mcpt_scene *sc) { return apply_visibility(sc, visible, changed, nullptr); },
                        [&](mcpt_scene *sc) { return apply_visibility(sc, old, changed, nullptr); });
+}
+
+int mcpt_group_add_objects(mcpt_group *g, const mcpt_scene_addition *add, int32_t *first_object) {
+    if (!g || g->scenes.empty()) return gfail(MCPT_ERR_ARG, "mcpt_group_add_objects: null group");
+    const int rc0 = check_add(g->scenes[0], add);
+    if (rc0 != MCPT_OK) return gfail(rc0, std::string("mcpt_group_add_objects: ") + mcpt_last_error());
+    // the way back: every replica's previous arrays stay aside until all replicas have grown
+    const size_t N = g->scenes.size();
+    std::vector<std::unique_ptr<AddAside>> aside;
+    for (size_t i = 0; i < N; ++i) aside.emplace_back(new AddAside());
+    const auto slot = [&](mcpt_scene *sc) -> AddAside & { return *aside[(size_t)(std::find(g->scenes.begin(), g->scenes.end(), sc) - g->scenes.begin())]; };
+    const int32_t first = (int32_t)g->scenes[0]->src.objects.size();
+    const int rc = on_replicas(g, "mcpt_group_add_objects", [&](mcpt_scene *sc) { return apply_add(sc, add, nullptr, nullptr, &slot(sc)); },
+                               [&](mcpt_scene *sc) { return undo_add(sc, slot(sc)); });
+    for (size_t i = 0; i < N; ++i) {  // (each set is freed with its device current)
+        (void)hipSetDevice(g->devices[i]);
+        aside[i].reset();
+    }
+    if (rc == MCPT_OK && first_object) *first_object = first;
+    return rc;
 }
 
 int mcpt_group_set_environment(mcpt_group *g, const float background[3], int32_t env_w, int32_t env_h, const float *env_pixels) {

@@ -606,7 +606,7 @@ int build_host_scene(const mcpt_scene_desc &d, HostScene &hs, const char **err, 
             s.radius = o.radius;
             s.radius2 = o.radius * o.radius;
             s.mat = o.material;
-            s.mat_bits = (uint32_t)o.material | (hs.materials[o.material].hasEmission ? kMatEmissive : 0u);
+            s.mat_bits = mat::sphere_mat_bits(o.material, d.materials[o.material]);
             B.prim = d.n_triangles + oi;
             hs.sphere_objects.push_back(oi);
             const V3 c = ld(o.center);
@@ -638,7 +638,7 @@ int build_host_scene(const mcpt_scene_desc &d, HostScene &hs, const char **err, 
                 TriGeom &g = hs.tri_geom[ti];
                 std::memset(&g, 0, sizeof g);
                 mv::store_geom(g, v0, D);
-                g.mat_bits = (uint32_t)o.material | (hs.materials[o.material].hasEmission ? kMatEmissive : 0u) | (hs.materials[o.material].textured ? kMatTextured : 0u);
+                g.mat_bits = mat::tri_mat_bits(o.material, d.materials[o.material]);  // (one expression for every writer of these words: csrc/mcpt_material.h)
                 TriShade &s = hs.tri_shade[ti];
                 std::memset(&s, 0, sizeof s);
                 store3(s.n, n);
@@ -962,11 +962,8 @@ int build_host_scene(const mcpt_scene_desc &d, HostScene &hs, const char **err, 
     return MCPT_OK;
 }
 
-// What mcpt_compact_scene does once its arguments are known to be non-null: the checks of build_host_scene that need no tree, then the
-// compaction.  A null `objects_out` or `triangles_out` gives the counts and the map only.
-int compact_scene_desc(const mcpt_scene_desc &d, const uint8_t *visible, mcpt_object *objects_out, mcpt_triangle *triangles_out, int32_t *n_objects_out,
-                       int32_t *n_triangles_out, int32_t *prim_map, const char **err) {
-    *err = "";
+// The checks of build_host_scene that need no tree (mcpt_compact_scene, mcpt_extend_scene).
+static int check_scene_desc(const mcpt_scene_desc &d, const char **err) {
     if (d.n_objects <= 0 || !d.objects || d.n_materials <= 0 || !d.materials || d.n_triangles < 0 || (d.n_triangles > 0 && !d.triangles)) {
         *err = "scene description: empty or null arrays";
         return MCPT_ERR_ARG;
@@ -1000,6 +997,16 @@ int compact_scene_desc(const mcpt_scene_desc &d, const uint8_t *visible, mcpt_ob
             tri_seen[(size_t)o.first_tri + k] = 1;
         }
     }
+    return MCPT_OK;
+}
+
+// What mcpt_compact_scene does once its arguments are known to be non-null: the checks of build_host_scene that need no tree, then the
+// compaction.  A null `objects_out` or `triangles_out` gives the counts and the map only.
+int compact_scene_desc(const mcpt_scene_desc &d, const uint8_t *visible, mcpt_object *objects_out, mcpt_triangle *triangles_out, int32_t *n_objects_out,
+                       int32_t *n_triangles_out, int32_t *prim_map, const char **err) {
+    *err = "";
+    const int rc = check_scene_desc(d, err);
+    if (rc != MCPT_OK) return rc;
     // compacted triangle ids follow ARRAY order (so the map is increasing), whatever order the objects list their meshes in
     std::vector<int32_t> mesh_of((size_t)d.n_triangles, -1);
     for (int oi = 0; oi < d.n_objects; ++oi)
@@ -1033,6 +1040,76 @@ int compact_scene_desc(const mcpt_scene_desc &d, const uint8_t *visible, mcpt_ob
     }
     if (n_objects_out) *n_objects_out = no;
     if (n_triangles_out) *n_triangles_out = nt;
+    return MCPT_OK;
+}
+
+int check_scene_addition(int32_t n_objects, int32_t n_triangles, int32_t n_materials, const mcpt_scene_addition &a, const char **err) {
+    *err = "";
+    const auto bad = [err](const char *m) {
+        *err = m;
+        return (int)MCPT_ERR_ARG;
+    };
+    if (a.n_objects < 0 || a.n_triangles < 0 || a.n_materials < 0) return bad("addition: a negative count");
+    if (a.n_objects == 0) return bad("addition: no object");
+    for (int k = 0; k < 4; ++k)
+        if (a.reserved[k] != 0) return bad("addition: a reserved word is not 0");
+    if (!a.objects || (a.n_triangles > 0 && !a.triangles) || (a.n_materials > 0 && !a.materials)) return bad("addition: a positive count with a null array");
+    // every id of the extended scene, a sphere's n_triangles + object included, stays an int32
+    if ((int64_t)n_objects + a.n_objects + (int64_t)n_triangles + a.n_triangles > 0x7fffffffLL || (int64_t)n_materials + a.n_materials > 0x7fffffffLL)
+        return bad("addition: the totals overflow int32");
+    for (int32_t i = 0; i < a.n_materials; ++i)
+        if (!mat::type_ok(a.materials[i])) return bad("material type out of range");
+    const int32_t nm = n_materials + a.n_materials;
+    std::vector<uint8_t> tri_seen((size_t)a.n_triangles, 0);
+    for (int32_t i = 0; i < a.n_objects; ++i) {
+        const mcpt_object &o = a.objects[i];
+        if (o.material < 0 || o.material >= nm) return bad("object material index out of range");
+        if (o.kind == MCPT_OBJ_SPHERE) {
+            const float f[4] = {o.center[0], o.center[1], o.center[2], o.radius};
+            for (float v : f)
+                if (!(v - v == 0.f)) return bad("addition: a sphere's centre or radius is not finite");
+            continue;
+        }
+        if (o.kind != MCPT_OBJ_MESH) return bad("object kind out of range");
+        if (o.first_tri < 0 || o.n_tri <= 0 || o.first_tri > a.n_triangles - o.n_tri) return bad("mesh triangle range out of bounds");
+        for (int32_t k = 0; k < o.n_tri; ++k) {
+            if (tri_seen[(size_t)o.first_tri + k]) return bad("triangle ranges of two meshes overlap");
+            tri_seen[(size_t)o.first_tri + k] = 1;
+        }
+    }
+    for (int32_t t = 0; t < a.n_triangles; ++t) {
+        const mcpt_triangle &T = a.triangles[t];
+        const float p[9] = {T.v0[0], T.v0[1], T.v0[2], T.v1[0], T.v1[1], T.v1[2], T.v2[0], T.v2[1], T.v2[2]};
+        if (!mv::positions_finite(p)) return bad("addition: a vertex is not finite");
+    }
+    return MCPT_OK;
+}
+
+int extend_scene_desc(const mcpt_scene_desc &d, const mcpt_scene_addition &a, mcpt_object *objects_out, mcpt_triangle *triangles_out,
+                      mcpt_material *materials_out, int32_t *n_objects_out, int32_t *n_triangles_out, int32_t *n_materials_out, const char **err) {
+    *err = "";
+    int rc = check_scene_desc(d, err);
+    if (rc == MCPT_OK) rc = check_scene_addition(d.n_objects, d.n_triangles, d.n_materials, a, err);
+    if (rc != MCPT_OK) return rc;
+    if (objects_out) {
+        std::copy(d.objects, d.objects + d.n_objects, objects_out);
+        for (int32_t i = 0; i < a.n_objects; ++i) {
+            mcpt_object &o = objects_out[d.n_objects + i];
+            o = a.objects[i];
+            if (o.kind == MCPT_OBJ_MESH) o.first_tri += d.n_triangles;
+        }
+    }
+    if (triangles_out) {
+        if (d.n_triangles) std::copy(d.triangles, d.triangles + d.n_triangles, triangles_out);
+        if (a.n_triangles) std::copy(a.triangles, a.triangles + a.n_triangles, triangles_out + d.n_triangles);
+    }
+    if (materials_out) {
+        std::copy(d.materials, d.materials + d.n_materials, materials_out);
+        if (a.n_materials) std::copy(a.materials, a.materials + a.n_materials, materials_out + d.n_materials);
+    }
+    if (n_objects_out) *n_objects_out = d.n_objects + a.n_objects;
+    if (n_triangles_out) *n_triangles_out = d.n_triangles + a.n_triangles;
+    if (n_materials_out) *n_materials_out = d.n_materials + a.n_materials;
     return MCPT_OK;
 }
 

@@ -1,5 +1,6 @@
 // Moving and deforming objects in a live scene (include/mcpt.h: mcpt_scene_update, mcpt_scene_deform): the kernels of the device path,
-// the kernel that rewrites the material words of primitives (mcpt_scene_set_materials),
+// the kernel that rewrites the material words of primitives (mcpt_scene_set_materials), the kernel that writes the whole records of
+// added primitives (mcpt_scene_add_objects),
 // and the host helpers mcpt_transform_triangles and mcpt_deform_triangles.  The scene-level part (argument checks, the two paths, the swap of the new arrays) is beside
 // mcpt_scene_create in csrc/mcpt_upload.hip; the arithmetic is csrc/mcpt_move.h, shared with the scene builder.
 #include <cmath>
@@ -132,7 +133,59 @@ __global__ __launch_bounds__(kB) void k_set_materials(const mat::MatSeg *__restr
     tri_shade[ti].mat = (int32_t)b.y;
 }
 
+// One lane per added triangle and one per added sphere (mcpt_scene_add_objects, path 1).  The lane finds its segment by the bisection of
+// k_move_objects.  A triangle lane reads its triangle from the appended tail of the base array, stores it for the tree builder and
+// writes the WHOLE TriGeom and TriShade records -- the geometry words by mv::derive_triangle in the order of mv::store_geom, mat_bits, the
+// normal, mat, the six texture coordinates, and zeros for the padding as the host's memset leaves it -- with three 16-byte stores each
+// and no load: the records are 48 bytes on 16-byte boundaries, and a quarter is the widest store the hardware has.  A sphere lane
+// writes its whole SphereRec with two.  Integer words go through uint4, so no bit of them passes through a float register type.
+__global__ __launch_bounds__(kB) void k_add_objects(const AddSeg *__restrict__ segs, int32_t n_segs, int32_t n_lanes, const mcpt_triangle *__restrict__ tris0,
+                                                     mcpt_triangle *__restrict__ tris_cur, TriGeom *__restrict__ tri_geom, TriShade *__restrict__ tri_shade,
+                                                     SphereRec *__restrict__ spheres) {
+    const int32_t lane = (int32_t)(blockIdx.x * kB + threadIdx.x);
+    if (lane >= n_lanes) return;
+    int32_t lo = 0, hi = n_segs - 1;  // the last segment whose first_lane <= lane
+    while (lo < hi) {
+        const int32_t mid = (lo + hi + 1) >> 1;
+        if (segs[mid].first_lane <= lane) lo = mid;
+        else hi = mid - 1;
+    }
+    const uint4 a = *reinterpret_cast<const uint4 *>(segs + lo);        // {first_lane, count, first_tri, object}
+    const uint4 b = *(reinterpret_cast<const uint4 *>(segs + lo) + 1);  // {mat_bits, mat, radius, pad}
+    const int32_t k = lane - (int32_t)a.x;
+    if (k >= (int32_t)a.y) return;  // (never for a table whose segments tile the lanes)
+    if ((int32_t)a.z < 0) {
+        const uint4 c = *(reinterpret_cast<const uint4 *>(segs + lo) + 2);  // {c.xyz, pad}
+        const float radius = __uint_as_float(b.z);
+        uint4 *rec = reinterpret_cast<uint4 *>(spheres + (int32_t)a.w);
+        rec[0] = make_uint4(c.x, c.y, c.z, b.z);                                   // {c.xyz, radius}
+        rec[1] = make_uint4(__float_as_uint(radius * radius), b.y, b.x, 0u);       // {radius2, mat, mat_bits, pad}
+        return;
+    }
+    const int32_t ti = (int32_t)a.z + k;
+    const mcpt_triangle t = tris0[ti];
+    tris_cur[ti] = t;
+    const mv::V3 v0 = mv::ld(t.v0);
+    const mv::TriDerived D = mv::derive_triangle(v0, mv::ld(t.v1), mv::ld(t.v2));
+    const auto u = [](float f) { return __float_as_uint(f); };
+    uint4 *g = reinterpret_cast<uint4 *>(tri_geom + ti);
+    g[0] = make_uint4(u(v0.x), u(v0.y), u(v0.z), u(D.e1.x));
+    g[1] = make_uint4(u(D.e1.y), u(D.e1.z), u(D.e2.x), u(D.e2.y));
+    g[2] = make_uint4(u(D.e2.z), b.x, 0u, 0u);  // {e2z, mat_bits, pad, pad}
+    uint4 *s = reinterpret_cast<uint4 *>(tri_shade + ti);
+    s[0] = make_uint4(u(D.n.x), u(D.n.y), u(D.n.z), b.y);  // {n.xyz, mat}
+    s[1] = make_uint4(u(t.t0[0]), u(t.t0[1]), u(t.t1[0]), u(t.t1[1]));
+    s[2] = make_uint4(u(t.t2[0]), u(t.t2[1]), 0u, 0u);  // {t2, pad, pad}
+}
+
 }  // namespace
+
+void launch_add_objects(const AddSeg *d_segs, int32_t n_segs, int32_t n_lanes, const mcpt_triangle *tris0, mcpt_triangle *tris_cur, TriGeom *tri_geom,
+                        TriShade *tri_shade, SphereRec *spheres, hipStream_t s) {
+    if (n_lanes <= 0 || n_segs <= 0) return;
+    hipLaunchKernelGGL(k_add_objects, dim3((uint32_t)((n_lanes + kB - 1) / kB)), dim3(kB), 0, s, d_segs, n_segs, n_lanes, tris0, tris_cur, tri_geom, tri_shade,
+                       spheres);
+}
 
 void launch_move_objects(const MoveSeg *d_segs, int32_t n_segs, int32_t n_lanes, const mcpt_triangle *tris0, mcpt_triangle *tris_cur, TriGeom *tri_geom,
                          TriShade *tri_shade, SphereRec *spheres, hipStream_t s) {

@@ -180,6 +180,15 @@ int build_device_tree(const mcpt_triangle *d_tris, const int32_t *d_sphere_obj, 
     return MCPT_OK;
 }
 
+// The device tree of an edit's device path: build_device_tree, then the depth check every tree gets before it is swapped in.
+int build_device_tree_checked(const mcpt_triangle *d_tris, const int32_t *d_sphere_obj, int n_sph, const BuildChoice &choice, GeomBufs &g, SceneMeta &meta,
+                              const DevVis *dv, const SphereRec *d_spheres = nullptr) {
+    const int rc = build_device_tree(d_tris, d_sphere_obj, n_sph, choice, g, meta, dv, d_spheres);
+    if (rc == MCPT_OK && traversal_stack_entries(meta.height) < meta.height - 1)
+        return fail(MCPT_ERR_LIMIT, "the BVH is deeper than the traversal stack (kMaxBvhHeight)");
+    return rc;
+}
+
 // Copies the arrays of a flattened scene that depend on where its objects are into `g`; for the device builders the tree is then built
 // there from d_tris (the triangles `hs` was flattened from).  Shared by mcpt_scene_create and the host path of mcpt_scene_update.
 int upload_geometry(const HostScene &hs, const BuildChoice &choice, const mcpt_triangle *d_tris, const int32_t *d_sphere_obj, GeomBufs &g, SceneMeta &meta,
@@ -401,6 +410,62 @@ int host_positions(const SceneSource &S, int32_t n, const mcpt_object_vertices *
     return MCPT_OK;
 }
 
+// desc' from the base description: the objects that have a transform get it applied, meshes to their triangles, spheres to their centre.
+void apply_current_transforms(std::vector<mcpt_object> &objs, std::vector<mcpt_triangle> &tris, const std::vector<uint8_t> &moved, const std::vector<float> &xf) {
+    for (size_t o = 0; o < objs.size(); ++o) {
+        if (!moved[o]) continue;
+        const float *m = &xf[o * 12];
+        if (objs[o].kind == MCPT_OBJ_MESH) {
+            for (int32_t k = 0; k < objs[o].n_tri; ++k) mv::move_triangle(m, tris[(size_t)objs[o].first_tri + k], tris[(size_t)objs[o].first_tri + k]);
+        } else {
+            const mv::V3 c = mv::move_point(m, mv::ld(objs[o].center));
+            objs[o].center[0] = c.x;
+            objs[o].center[1] = c.y;
+            objs[o].center[2] = c.z;
+        }
+    }
+}
+
+// The host path every edit ends in: desc' (objs, tris, mats) is flattened and its tree built as at creation, with the mask `visible`;
+// every array that depends on the geometry is copied into g2 (device builders: the moved triangles too, and the tree is built there
+// over the spheres listed in d_sphere_obj); `meta` becomes that of the new arrays.  The caller swaps.
+struct HostPathTimes {
+    double host_build_ms = 0.0, gpu_build_ms = 0.0;
+    Clock::time_point upload_start;
+};
+int flatten_and_upload(mcpt_scene *sc, const std::vector<mcpt_object> &objs, const std::vector<mcpt_triangle> &tris, const std::vector<mcpt_material> &mats,
+                       const std::vector<uint8_t> &visible, const int32_t *d_sphere_obj, const char *who, HostScene &hs, GeomBufs &g2, SceneMeta &meta,
+                       HostPathTimes &T) {
+    const SceneSource &S = sc->src;
+    const auto tb = Clock::now();
+    mcpt_scene_desc d;
+    std::memset(&d, 0, sizeof d);
+    d.n_objects = (int32_t)objs.size();
+    d.n_triangles = (int32_t)tris.size();
+    d.n_materials = (int32_t)mats.size();
+    for (int k = 0; k < 3; ++k) d.background[k] = meta.background[k];
+    d.objects = objs.data();
+    d.triangles = tris.data();
+    d.materials = mats.data();
+    const char *err = "";
+    const bool masked = std::find(visible.begin(), visible.end(), (uint8_t)0) != visible.end();
+    int rc = build_host_scene(d, hs, &err, S.choice, masked ? visible.data() : nullptr);
+    if (rc != MCPT_OK) return fail(rc, std::string(who) + err);
+    T.host_build_ms = ms_since(tb);
+    T.upload_start = Clock::now();
+    const int32_t env_w = meta.env_w, env_h = meta.env_h;  // (the environment map is not part of desc': it stays where it is)
+    meta = meta_of(hs);
+    meta.env_w = env_w;
+    meta.env_h = env_h;
+    DevVis dv;
+    if (hs.builder >= 2) {
+        HIP_TRY(upload(g2.tris, tris));
+        rc = upload_vis(S, visible, dv);
+        if (rc != MCPT_OK) return rc;
+    }
+    return upload_geometry(hs, S.choice, g2.tris.p, d_sphere_obj, g2, meta, T.gpu_build_ms, &dv);
+}
+
 // The rebuild behind mcpt_scene_update and mcpt_scene_deform: the scene gets the transform table (moved, xf) and, when `deform` is given,
 // the listed meshes (touched[i] = deform[i].object) get new base positions.  Everything is built aside and committed on success.
 // `edit` (mcpt_scene_set_materials, path 0): the material table and the objects' material indices of the plan replace the scene's; the
@@ -446,9 +511,7 @@ int rebuild(mcpt_scene *sc, const std::vector<uint8_t> &moved, const std::vector
         if (rc != MCPT_OK) return rc;
         ui.transform_ms = ms_since(tt);
         const auto tb = Clock::now();
-        rc = build_device_tree(sc->geom.tris.p ? sc->geom.tris.p : sc->tris0.p, sc->sphere_obj.p, (int)sc->sphere_obj.n, S.choice, g2, meta, &dv, sc->geom.spheres.p);
-        if (rc == MCPT_OK && traversal_stack_entries(meta.height) < meta.height - 1)
-            rc = fail(MCPT_ERR_LIMIT, "the BVH is deeper than the traversal stack (kMaxBvhHeight)");
+        rc = build_device_tree_checked(sc->geom.tris.p ? sc->geom.tris.p : sc->tris0.p, sc->sphere_obj.p, (int)sc->sphere_obj.n, S.choice, g2, meta, &dv, sc->geom.spheres.p);
         if (rc != MCPT_OK) return rc;
         ui.build_ms = ms_since(tb);
         sc->geom.swap_nodes(g2);
@@ -534,9 +597,7 @@ int rebuild(mcpt_scene *sc, const std::vector<uint8_t> &moved, const std::vector
         if (rc != MCPT_OK) return rc;
         ui.transform_ms = ms_since(tt);
         const auto tb = Clock::now();
-        rc = build_device_tree(g2.tris.p, sc->sphere_obj.p, (int)sc->sphere_obj.n, S.choice, g2, meta, &dv);
-        if (rc == MCPT_OK && traversal_stack_entries(meta.height) < meta.height - 1)
-            rc = fail(MCPT_ERR_LIMIT, "the BVH is deeper than the traversal stack (kMaxBvhHeight)");
+        rc = build_device_tree_checked(g2.tris.p, sc->sphere_obj.p, (int)sc->sphere_obj.n, S.choice, g2, meta, &dv);
         if (rc != MCPT_OK) return rc;
         ui.build_ms = ms_since(tb);
         if (deform) {  // the host copy of the base follows at once (36 B per triangle come back for positions given by device pointer)
@@ -566,53 +627,18 @@ int rebuild(mcpt_scene *sc, const std::vector<uint8_t> &moved, const std::vector
         if (deform) base = tris;
         std::vector<mcpt_object> objs = edit ? edit->objects : S.objects;
         const std::vector<mcpt_material> &mats = edit ? edit->materials : S.materials;
-        for (size_t o = 0; o < objs.size(); ++o) {
-            if (!moved[o]) continue;
-            const float *m = &xf[o * 12];
-            if (objs[o].kind == MCPT_OBJ_MESH) {
-                for (int32_t k = 0; k < objs[o].n_tri; ++k) mv::move_triangle(m, tris[(size_t)objs[o].first_tri + k], tris[(size_t)objs[o].first_tri + k]);
-            } else {
-                const mv::V3 c = mv::move_point(m, mv::ld(objs[o].center));
-                objs[o].center[0] = c.x;
-                objs[o].center[1] = c.y;
-                objs[o].center[2] = c.z;
-            }
-        }
+        apply_current_transforms(objs, tris, moved, xf);
         ui.transform_ms = ms_since(tt);
-        const auto tb = Clock::now();
-        mcpt_scene_desc d;
-        std::memset(&d, 0, sizeof d);
-        d.n_objects = (int32_t)objs.size();
-        d.n_triangles = (int32_t)tris.size();
-        d.n_materials = (int32_t)mats.size();
-        for (int k = 0; k < 3; ++k) d.background[k] = meta.background[k];
-        d.objects = objs.data();
-        d.triangles = tris.data();
-        d.materials = mats.data();
         HostScene hs;
-        const char *err = "";
-        const bool masked = std::find(visible.begin(), visible.end(), (uint8_t)0) != visible.end();
-        int rc = build_host_scene(d, hs, &err, S.choice, masked ? visible.data() : nullptr);
-        if (rc != MCPT_OK)
-            return fail(rc, std::string(show ? "mcpt_scene_set_visibility: " : (edit ? "mcpt_scene_set_materials: " : (deform ? "mcpt_scene_deform: " : "mcpt_scene_update: "))) + err);
-        const double host_build_ms = ms_since(tb);
-        const auto tu = Clock::now();
-        const int32_t env_w = meta.env_w, env_h = meta.env_h;  // (the environment map is not part of desc': it stays where it is)
-        meta = meta_of(hs);
-        meta.env_w = env_w;
-        meta.env_h = env_h;
-        if (hs.builder >= 2) {
-            HIP_TRY(upload(g2.tris, tris));
-            rc = upload_vis(S, visible, dv);
-            if (rc != MCPT_OK) return rc;
-        }
-        double gpu_build_ms = 0.0;
-        rc = upload_geometry(hs, S.choice, g2.tris.p, sc->sphere_obj.p, g2, meta, gpu_build_ms, &dv);
+        HostPathTimes T;
+        const int rc = flatten_and_upload(sc, objs, tris, mats, visible, sc->sphere_obj.p,
+                                          show ? "mcpt_scene_set_visibility: " : (edit ? "mcpt_scene_set_materials: " : (deform ? "mcpt_scene_deform: " : "mcpt_scene_update: ")),
+                                          hs, g2, meta, T);
         if (rc != MCPT_OK) return rc;
-        ui.build_ms = host_build_ms + gpu_build_ms;
+        ui.build_ms = T.host_build_ms + T.gpu_build_ms;
         if (deform && hs.builder >= 2) HIP_TRY(upload(base2, base));
         if (edit) HIP_TRY(upload(mats2, hs.materials));
-        ui.upload_ms = ms_since(tu) - gpu_build_ms;
+        ui.upload_ms = ms_since(T.upload_start) - T.gpu_build_ms;
         sc->geom.swap_prims(g2);
         sc->geom.swap_lights(g2);
     }
@@ -715,6 +741,191 @@ int mcpt::check_visibility(const mcpt_scene *sc, int32_t n, const mcpt_object_vi
 
 int mcpt::apply_visibility(mcpt_scene *sc, const std::vector<uint8_t> &visible, const std::vector<int32_t> &changed, mcpt_update_info *info) {
     return rebuild(sc, sc->src.moved, sc->src.xf, changed, nullptr, info, nullptr, &visible);
+}
+
+int mcpt::check_add(const mcpt_scene *sc, const mcpt_scene_addition *add) {
+    if (!sc || !add) return fail(MCPT_ERR_ARG, "mcpt_scene_add_objects: null argument");
+    const SceneSource &S = sc->src;
+    const char *err = "";
+    const int rc = check_scene_addition((int32_t)S.objects.size(), (int32_t)S.triangles.size(), (int32_t)S.materials.size(), *add, &err);
+    if (rc != MCPT_OK) return fail(rc, std::string("mcpt_scene_add_objects: ") + err);
+    if (S.choice.builder == MCPT_BUILD_SAH && S.choice.instancing == 1)
+        return fail(MCPT_ERR_ARG, "mcpt_scene_add_objects: the scene was built with node instancing on (instanced subtrees are shared between objects)");
+    return MCPT_OK;
+}
+
+namespace {
+
+// Exchanges everything mcpt_scene_add_objects replaces between the scene and `A`: the commit of apply_add, and its way back.
+void exchange_add(mcpt_scene *sc, AddAside &A) {
+    sc->geom.swap_prims(A.geom);
+    if (A.lights) sc->geom.swap_lights(A.geom);
+    sc->tris0.swap(A.tris0);
+    sc->sphere_obj.swap(A.sphere_obj);
+    sc->mats.swap(A.mats);
+    if (sc->has_snapshot) {
+        sc->snap_tri.swap(A.snap_tri);
+        sc->snap_sph.swap(A.snap_sph);
+    }
+    std::swap(sc->meta, A.meta);
+}
+
+void resize_source(SceneSource &S, size_t n_objects, size_t n_triangles, size_t n_materials) {
+    S.objects.resize(n_objects);
+    S.triangles.resize(n_triangles);
+    S.materials.resize(n_materials);
+    S.moved.resize(n_objects, 0);
+    S.xf.resize(n_objects * 12, 0.f);
+    S.visible.resize(n_objects, 1);
+}
+
+}  // namespace
+
+// The scene's own description is extended in place first (mcpt_extend_scene's rule) and cut back if anything below fails; every device
+// array that is indexed by primitive or by object is built aside at the new size in `A` and exchanged with the scene's as the last step.
+int mcpt::apply_add(mcpt_scene *sc, const mcpt_scene_addition *add, int32_t *first_object, mcpt_update_info *info, AddAside *keep) {
+    const auto t0 = Clock::now();
+    mcpt_update_info ui;
+    std::memset(&ui, 0, sizeof ui);
+    ui.n_moved_tris = add->n_triangles;
+    SceneSource &S = sc->src;
+    HIP_TRY(hipSetDevice(sc->device));
+    AddAside local;
+    AddAside &A = keep ? *keep : local;
+    const size_t no = S.objects.size(), nt = S.triangles.size(), nm = S.materials.size();
+    const size_t no2 = no + (size_t)add->n_objects, nt2 = nt + (size_t)add->n_triangles;
+    A.n_objects = no;
+    A.n_triangles = nt;
+    A.n_materials = nm;
+    struct CutBack {  // a failed call leaves the description as it was
+        SceneSource &S;
+        size_t no, nt, nm;
+        bool keep = false;
+        ~CutBack() {
+            if (!keep) resize_source(S, no, nt, nm);
+        }
+    } cut{S, no, nt, nm};
+    resize_source(S, no2, nt2, nm + (size_t)add->n_materials);
+    for (int32_t i = 0; i < add->n_objects; ++i) {
+        mcpt_object &o = S.objects[no + (size_t)i];
+        o = add->objects[i];
+        if (o.kind == MCPT_OBJ_MESH) o.first_tri += (int32_t)nt;
+    }
+    std::copy(add->triangles, add->triangles + add->n_triangles, S.triangles.begin() + (ptrdiff_t)nt);
+    std::copy(add->materials, add->materials + add->n_materials, S.materials.begin() + (ptrdiff_t)nm);
+    bool emitter = false;
+    for (size_t o = no; o < no2; ++o) emitter = emitter || emits(S.materials[(size_t)S.objects[o].material]);
+    std::vector<int32_t> sph;  // the device builders' sphere list at the new size
+    for (size_t o = 0; o < no2; ++o)
+        if (S.objects[o].kind == MCPT_OBJ_SPHERE) sph.push_back((int32_t)o);
+    SceneMeta meta = sc->meta;
+    GeomBufs &g2 = A.geom;
+    if (meta.builder >= 2 && !emitter) {
+        // ---- device path: the live records are copied into arrays of the new size, a kernel writes the records of the added primitives
+        // from their triangles, the device builder runs at the new size
+        ui.path = 1;
+        const auto tu = Clock::now();
+        HIP_TRY(g2.tri_geom.alloc(nt2));
+        HIP_TRY(g2.tri_shade.alloc(nt2));
+        HIP_TRY(g2.tris.alloc(nt2));
+        HIP_TRY(g2.spheres.alloc(no2));
+        HIP_TRY(A.tris0.alloc(nt2));
+        HIP_TRY(A.sphere_obj.alloc(sph.size()));
+        if (nt) {
+            HIP_TRY(hipMemcpyAsync(g2.tri_geom.p, sc->geom.tri_geom.p, nt * sizeof(TriGeom), hipMemcpyDeviceToDevice, nullptr));
+            HIP_TRY(hipMemcpyAsync(g2.tri_shade.p, sc->geom.tri_shade.p, nt * sizeof(TriShade), hipMemcpyDeviceToDevice, nullptr));
+            HIP_TRY(hipMemcpyAsync(g2.tris.p, sc->geom.tris.p ? sc->geom.tris.p : sc->tris0.p, nt * sizeof(mcpt_triangle), hipMemcpyDeviceToDevice, nullptr));
+            HIP_TRY(hipMemcpyAsync(A.tris0.p, sc->tris0.p, nt * sizeof(mcpt_triangle), hipMemcpyDeviceToDevice, nullptr));
+        }
+        HIP_TRY(hipMemcpyAsync(g2.spheres.p, sc->geom.spheres.p, no * sizeof(SphereRec), hipMemcpyDeviceToDevice, nullptr));
+        HIP_TRY(hipMemsetAsync(g2.spheres.p + no, 0, (no2 - no) * sizeof(SphereRec), nullptr));  // (the slots of meshes stay zero, as the host leaves them)
+        HIP_TRY(hipStreamSynchronize(nullptr));
+        ui.upload_ms = ms_since(tu);
+        const auto tt = Clock::now();
+        if (add->n_triangles) HIP_TRY(hipMemcpy(A.tris0.p + nt, add->triangles, (size_t)add->n_triangles * sizeof(mcpt_triangle), hipMemcpyHostToDevice));
+        if (!sph.empty()) HIP_TRY(hipMemcpy(A.sphere_obj.p, sph.data(), sph.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+        std::vector<MaterialRec> recs(S.materials.size());
+        for (size_t i = 0; i < recs.size(); ++i) mat::make_record(S.materials[i], recs[i]);
+        HIP_TRY(upload(A.mats, recs));
+        std::vector<AddSeg> segs;
+        int32_t lanes = 0;
+        for (size_t o = no; o < no2; ++o) {
+            const mcpt_object &ob = S.objects[o];
+            const mcpt_material &m = S.materials[(size_t)ob.material];
+            const bool mesh = ob.kind == MCPT_OBJ_MESH;
+            AddSeg sg;
+            std::memset(&sg, 0, sizeof sg);
+            sg.first_lane = lanes;
+            sg.count = mesh ? ob.n_tri : 1;
+            sg.first_tri = mesh ? ob.first_tri : -1;
+            sg.object = (int32_t)o;
+            sg.mat_bits = mesh ? mat::tri_mat_bits(ob.material, m) : mat::sphere_mat_bits(ob.material, m);
+            sg.mat = ob.material;
+            sg.radius = ob.radius;
+            for (int k = 0; k < 3; ++k) sg.c[k] = ob.center[k];
+            lanes += sg.count;
+            segs.push_back(sg);
+        }
+        HIP_TRY(upload(sc->asegs, segs));
+        launch_add_objects(sc->asegs.p, (int32_t)segs.size(), lanes, A.tris0.p, g2.tris.p, g2.tri_geom.p, g2.tri_shade.p, g2.spheres.p, nullptr);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(nullptr));
+        DevVis dv;
+        int rc = upload_vis(S, S.visible, dv);
+        if (rc != MCPT_OK) return rc;
+        ui.transform_ms = ms_since(tt);
+        const auto tb = Clock::now();
+        meta.n_triangles = (int32_t)nt2;
+        meta.n_objects = (int32_t)no2;
+        meta.n_sphere_slots = (int32_t)no2;
+        meta.n_mats = (int32_t)S.materials.size();
+        rc = build_device_tree_checked(g2.tris.p, A.sphere_obj.p, (int)sph.size(), S.choice, g2, meta, &dv);
+        if (rc != MCPT_OK) return rc;
+        ui.build_ms = ms_since(tb);
+    } else {
+        // ---- host path: the extended desc' is flattened and uploaded by the creation code
+        ui.path = 0;
+        A.lights = true;
+        const auto tt = Clock::now();
+        std::vector<mcpt_triangle> tris = S.triangles;
+        std::vector<mcpt_object> objs = S.objects;
+        apply_current_transforms(objs, tris, S.moved, S.xf);
+        ui.transform_ms = ms_since(tt);
+        if (meta.builder >= 2) HIP_TRY(upload(A.sphere_obj, sph));
+        HostScene hs;
+        HostPathTimes T;
+        const int rc = flatten_and_upload(sc, objs, tris, S.materials, S.visible, A.sphere_obj.p, "mcpt_scene_add_objects: ", hs, g2, meta, T);
+        if (rc != MCPT_OK) return rc;
+        ui.build_ms = T.host_build_ms + T.gpu_build_ms;
+        if (hs.builder >= 2) HIP_TRY(upload(A.tris0, S.triangles));
+        HIP_TRY(upload(A.mats, hs.materials));
+        ui.upload_ms = ms_since(T.upload_start) - T.gpu_build_ms;
+    }
+    if (sc->has_snapshot) {  // the snapshot at the new size: what it held, then the added objects' records as added
+        HIP_TRY(A.snap_tri.alloc(nt2));
+        HIP_TRY(A.snap_sph.alloc(no2));
+        if (nt) HIP_TRY(hipMemcpyAsync(A.snap_tri.p, sc->snap_tri.p, nt * sizeof(TriGeom), hipMemcpyDeviceToDevice, nullptr));
+        if (nt2 > nt) HIP_TRY(hipMemcpyAsync(A.snap_tri.p + nt, g2.tri_geom.p + nt, (nt2 - nt) * sizeof(TriGeom), hipMemcpyDeviceToDevice, nullptr));
+        HIP_TRY(hipMemcpyAsync(A.snap_sph.p, sc->snap_sph.p, no * sizeof(SphereRec), hipMemcpyDeviceToDevice, nullptr));
+        HIP_TRY(hipMemcpyAsync(A.snap_sph.p + no, g2.spheres.p + no, (no2 - no) * sizeof(SphereRec), hipMemcpyDeviceToDevice, nullptr));
+        HIP_TRY(hipStreamSynchronize(nullptr));
+    }
+    A.meta = meta;
+    exchange_add(sc, A);
+    cut.keep = true;
+    fill_view(sc);
+    ui.total_ms = ms_since(t0);
+    if (first_object) *first_object = (int32_t)no;
+    if (info) *info = ui;
+    return MCPT_OK;
+}
+
+int mcpt::undo_add(mcpt_scene *sc, AddAside &A) {
+    HIP_TRY(hipSetDevice(sc->device));
+    exchange_add(sc, A);
+    resize_source(sc->src, A.n_objects, A.n_triangles, A.n_materials);
+    fill_view(sc);
+    return MCPT_OK;
 }
 
 int mcpt::check_material_edit(const mcpt_scene *sc, int32_t n_edits, const mcpt_material_edit *edits, int32_t n_assign, const mcpt_object_material *assign,
@@ -906,6 +1117,20 @@ int mcpt_compact_scene(const mcpt_scene_desc *desc, const uint8_t *visible, mcpt
     const char *err = "";
     const int rc = compact_scene_desc(*desc, visible, objects_out, triangles_out, n_objects_out, n_triangles_out, prim_map, &err);
     return rc == MCPT_OK ? rc : fail(rc, std::string("mcpt_compact_scene: ") + err);
+}
+
+int mcpt_scene_add_objects(mcpt_scene *sc, const mcpt_scene_addition *add, int32_t *first_object, mcpt_update_info *info) {
+    const int rc = check_add(sc, add);
+    if (rc != MCPT_OK) return rc;
+    return apply_add(sc, add, first_object, info);
+}
+
+int mcpt_extend_scene(const mcpt_scene_desc *desc, const mcpt_scene_addition *add, mcpt_object *objects_out, mcpt_triangle *triangles_out,
+                      mcpt_material *materials_out, int32_t *n_objects_out, int32_t *n_triangles_out, int32_t *n_materials_out) {
+    if (!desc || !add) return fail(MCPT_ERR_ARG, "mcpt_extend_scene: null argument");
+    const char *err = "";
+    const int rc = extend_scene_desc(*desc, *add, objects_out, triangles_out, materials_out, n_objects_out, n_triangles_out, n_materials_out, &err);
+    return rc == MCPT_OK ? rc : fail(rc, std::string("mcpt_extend_scene: ") + err);
 }
 
 int mcpt_scene_snapshot(mcpt_scene *sc) {

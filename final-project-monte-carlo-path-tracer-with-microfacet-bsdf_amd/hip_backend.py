@@ -23,6 +23,7 @@ EXPORTS = ["mcpt_scene_create", "mcpt_scene_destroy", "mcpt_render", "mcpt_rende
            "mcpt_scene_deform", "mcpt_group_deform", "mcpt_deform_triangles",
            "mcpt_scene_set_materials", "mcpt_scene_set_environment", "mcpt_group_set_materials", "mcpt_group_set_environment",
            "mcpt_scene_set_visibility", "mcpt_scene_get_visibility", "mcpt_group_set_visibility", "mcpt_compact_scene",
+           "mcpt_scene_add_objects", "mcpt_group_add_objects", "mcpt_extend_scene",
            "mcpt_scene_snapshot", "mcpt_render_motion", "mcpt_temporal_blend", "mcpt_temporal_accumulate",
            "mcpt_temporal_accumulate_ex",
            "mcpt_sequence_create", "mcpt_sequence_frame", "mcpt_sequence_reset", "mcpt_sequence_destroy",
@@ -236,6 +237,30 @@ class ObjectVisibility(C.Structure):
 
 
 assert C.sizeof(Material) == 44 and C.sizeof(MaterialEdit) == 48 and C.sizeof(ObjectMaterial) == 8 and C.sizeof(ObjectVisibility) == 8
+
+
+class SceneAddition(C.Structure):
+    _fields_ = [("n_objects", C.c_int32), ("n_triangles", C.c_int32), ("n_materials", C.c_int32),
+                ("objects", C.c_void_p), ("triangles", C.c_void_p), ("materials", C.c_void_p), ("reserved", C.c_int32 * 4)]
+
+
+def _addition(sd, objects, triangles, materials):
+    """mcpt_scene_addition over arrays with the dtypes of `sd` (objects: first_tri relative to `triangles`, material an index into the
+    table after the append); -> (struct, the arrays to keep alive)."""
+    def records(x, dtype):  # an array, or a sequence of single records
+        if x is None or (not isinstance(x, np.ndarray) and len(x) == 0):
+            return np.zeros(0, dtype)
+        if not isinstance(x, np.ndarray):
+            x = np.stack([np.asarray(r, dtype=dtype).reshape(()) for r in x])
+        return np.ascontiguousarray(x, dtype=dtype).reshape(-1)
+
+    obj, tri, mat = records(objects, sd.objects.dtype), records(triangles, sd.triangles.dtype), records(materials, sd.materials.dtype)
+    a = SceneAddition()
+    a.n_objects, a.n_triangles, a.n_materials = len(obj), len(tri), len(mat)
+    a.objects = obj.ctypes.data if len(obj) else None
+    a.triangles = tri.ctypes.data if len(tri) else None
+    a.materials = mat.ctypes.data if len(mat) else None
+    return a, (obj, tri, mat)
 
 
 def _visibility_items(items):
@@ -550,6 +575,13 @@ def lib(path=None):
         L.mcpt_group_set_visibility.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
         L.mcpt_compact_scene.restype = C.c_int
         L.mcpt_compact_scene.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p]
+        L.mcpt_scene_add_objects.restype = C.c_int
+        L.mcpt_scene_add_objects.argtypes = [C.c_void_p, C.POINTER(SceneAddition), C.POINTER(C.c_int32), C.POINTER(UpdateInfo)]
+        L.mcpt_group_add_objects.restype = C.c_int
+        L.mcpt_group_add_objects.argtypes = [C.c_void_p, C.POINTER(SceneAddition), C.POINTER(C.c_int32)]
+        L.mcpt_extend_scene.restype = C.c_int
+        L.mcpt_extend_scene.argtypes = [C.c_void_p, C.POINTER(SceneAddition), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                        C.POINTER(C.c_int32)]
         L.mcpt_deform_triangles.restype = C.c_int
         L.mcpt_deform_triangles.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
         L.mcpt_group_create.restype = C.c_int
@@ -657,6 +689,21 @@ def compact_scene(sd, visible):
     return dataclasses.replace(sd, objects=objects, triangles=triangles), prim_map
 
 
+def extend_scene(sd, objects, triangles, materials=None):
+    """mcpt_extend_scene (host only): the description `sd` followed by the given objects (records of sd.objects' dtype; first_tri relative
+    to `triangles`, material an index into the table after the append), their triangles and the given materials.  Returns the SceneData."""
+    import dataclasses
+    keep = []
+    d = _make_desc(sd, keep)
+    a, arrays = _addition(sd, objects, triangles, materials)
+    no, nt, nm = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+    _check(lib().mcpt_extend_scene(C.byref(d), C.byref(a), None, None, None, C.byref(no), C.byref(nt), C.byref(nm)))
+    obj, tri, mat = np.zeros(no.value, sd.objects.dtype), np.zeros(nt.value, sd.triangles.dtype), np.zeros(nm.value, sd.materials.dtype)
+    _check(lib().mcpt_extend_scene(C.byref(d), C.byref(a), _ptr(obj), _ptr(tri), _ptr(mat), C.byref(no), C.byref(nt), C.byref(nm)))
+    del arrays
+    return dataclasses.replace(sd, objects=obj, triangles=tri, materials=mat)
+
+
 def cull_bound(camera, root_min, root_max, library=None):
     """mcpt_cull_bound (host only): the sky cull's bound for a camera (scenes.CAM_DTYPE) over a root box, as a dict of mcpt_cull_info."""
     cam = np.ascontiguousarray(camera)
@@ -761,6 +808,17 @@ class HipScene:
         mask, n = np.zeros(len(self.sd.objects), np.uint8), C.c_int32(0)
         _check(self.L.mcpt_scene_get_visibility(self.h, len(mask), _ptr(mask), C.byref(n)), L=self.L)
         return mask, int(n.value)
+
+    def add_objects(self, objects, triangles, materials=None):
+        """mcpt_scene_add_objects: appends objects (records of scenes.OBJ_DTYPE; first_tri relative to `triangles`, material an index into
+        the material table after the append), their triangles and, optionally, materials.  Afterwards the scene behaves like one created
+        from extend_scene(current description, ...), and self.sd is the extended SceneData.  Returns (index of the first added object,
+        mcpt_update_info as a dict)."""
+        a, arrays = _addition(self.sd, objects, triangles, materials)
+        info, first = UpdateInfo(), C.c_int32(-1)
+        _check(self.L.mcpt_scene_add_objects(self.h, C.byref(a), C.byref(first), C.byref(info)), L=self.L)
+        self.sd = extend_scene(self.sd, *arrays)
+        return int(first.value), info.as_dict()
 
     def set_environment(self, background, env=None):
         """mcpt_scene_set_environment: the background colour and the environment map (an (h, w, 3) float32 array, or None for the constant
@@ -1547,6 +1605,16 @@ class HipGroup:
         rc = self.L.mcpt_group_set_visibility(self.h, n, C.cast(arr, C.c_void_p))
         if rc != 0:
             raise McptError(rc, self.L.mcpt_group_last_error().decode("utf-8", "replace"))
+
+    def add_objects(self, objects, triangles, materials=None):
+        """mcpt_group_add_objects: HipScene.add_objects on every replica.  Returns (index of the first added object, {})."""
+        a, arrays = _addition(self.sd, objects, triangles, materials)
+        first = C.c_int32(-1)
+        rc = self.L.mcpt_group_add_objects(self.h, C.byref(a), C.byref(first))
+        if rc != 0:
+            raise McptError(rc, self.L.mcpt_group_last_error().decode("utf-8", "replace"))
+        self.sd = extend_scene(self.sd, *arrays)
+        return int(first.value), {}
 
     def info(self):
         i = GroupInfo()

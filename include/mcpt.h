@@ -334,6 +334,59 @@ int mcpt_scene_get_visibility(const mcpt_scene *scene, int32_t n_objects, uint8_
 int mcpt_compact_scene(const mcpt_scene_desc *desc, const uint8_t *visible /* n_objects */, mcpt_object *objects_out, mcpt_triangle *triangles_out,
                        int32_t *n_objects_out, int32_t *n_triangles_out, int32_t *prim_map /* n_triangles + n_objects entries */);
 
+/* ---- Adding objects to a live scene: meshes, spheres and materials appended.
+ *
+ * mcpt_scene_add_objects appends the given objects, their triangles and the given materials to the scene's description and rebuilds the
+ * traversal tree with the scene's own builder.  "Appended" is what mcpt_extend_scene computes: the objects after the existing ones in the
+ * order given, the triangles after the existing ones with every first_tri shifted by the old triangle count, the materials after the
+ * existing ones; environment and background untouched.  *first_object receives the index of the first added object (the old count).
+ *   Ids: the triangles of existing objects keep their ids, the new triangles get n_triangles_old, n_triangles_old + 1, ...  A sphere's id
+ *   is n_triangles + object, so the id of EVERY sphere, old or new, moves up by the number of added triangles -- which is what a fresh scene
+ *   of the extended description reports.  Object indices never change.
+ *   The added objects start without a transform and visible; the given triangles are their base, stored bit for bit.  Afterwards they are
+ *   objects like any other to mcpt_scene_update, mcpt_scene_deform, mcpt_scene_set_materials and mcpt_scene_set_visibility.
+ * THE CONTRACT: after the call every entry point listed at mcpt_scene_update gives what it gives on
+ *       mcpt_scene_create_ex(compact(extend(desc', add)), device, the same options)
+ * where desc' is the scene's current description (latest bases, current transforms, current materials), extend() is mcpt_extend_scene and
+ * compact() is mcpt_compact_scene with the scene's current mask, in which the new objects are visible (ids translated as stated at
+ * mcpt_scene_set_visibility).  Bit for bit with the host builders, the tree dump included; by the rule of mcpt_scene_update with the device
+ * builders.  mcpt_scene_get_info equals the fresh scene's of extend(desc', add) in n_nodes, bvh_height, quantised, lds_resident, n_lights
+ * and n_prims while nothing is hidden: lds_resident goes from 1 to 0 when the records outgrow what the LDS kernels hold.  A live scene
+ * keeps the builder it was created with.
+ * The handle, its streams and events, the wavefront workspaces and every mcpt_sequence made from the scene survive (a sequence holds no
+ * primitive id and no array length of the scene).
+ *   info->path 0  host: every host-built scene, and any scene when an added object emits light.  The extended description is flattened
+ *                 and uploaded by the creation code, as path 0 of mcpt_scene_update.
+ *   info->path 1  device: MCPT_BUILD_GPU_LBVH / MCPT_BUILD_GPU_PLOC scenes when no added object emits.  Record arrays of the new size are
+ *                 allocated aside and the live records copied device to device (upload_ms); only the added triangles, a segment table and
+ *                 the new material table cross the bus, and a kernel writes the records of the added primitives (transform_ms); the
+ *                 device builder runs at the new size (build_ms).
+ *   info->n_moved_tris is the number of added triangles.
+ * Temporal reuse: when the scene has a snapshot (mcpt_scene_snapshot) it is extended in the same call with the added objects' records as
+ * added, so they report zero object motion until the next snapshot, as if they had been there, at rest, when it was taken.
+ * MCPT_ERR_ARG, before any device call: scene == NULL or add == NULL; a negative count; n_objects == 0; a non-zero reserved word; a null
+ * array with a positive count; whatever creation refuses on the extended description (a triangle range out of bounds of add->triangles,
+ * ranges that overlap, an object kind, material index or material type out of range); a vertex of an added triangle, a centre or a radius
+ * that is not finite; totals (objects + triangles) beyond int32; a scene built with node instancing on.  A refused call, and a call whose
+ * rebuild fails (MCPT_ERR_LIMIT: the new tree is deeper than the traversal stack; MCPT_ERR_OOM), leaves the scene exactly as it was, counts
+ * and snapshot included: everything is built aside and swapped in as the last step.  Blocking, on the null stream, like mcpt_scene_update.
+ * There is no removal: hide the object (mcpt_scene_set_visibility); removing it would renumber triangles. */
+typedef struct {
+    int32_t n_objects, n_triangles, n_materials;
+    const mcpt_object   *objects;    /* first_tri is relative to `triangles` below; material indexes the table AFTER the append:
+                                        0..M-1 the scene's entries, M..M+n_materials-1 the ones given here */
+    const mcpt_triangle *triangles;
+    const mcpt_material *materials;  /* appended to the material table; may be NULL with n_materials 0 */
+    int32_t reserved[4];             /* must be 0 */
+} mcpt_scene_addition;
+int mcpt_scene_add_objects(mcpt_scene *scene, const mcpt_scene_addition *add, int32_t *first_object /* nullable */, mcpt_update_info *info /* nullable */);
+/* Host only, no GPU needed: the description `desc` followed by the addition, which defines "appended".  Call it with the three arrays NULL
+ * to get the counts, then with arrays of that size (materials_out included: the table is copied, then extended).  The environment and the
+ * background stay the caller's.  MCPT_ERR_ARG for a null desc or add, for a description that creation would refuse, and for every
+ * addition mcpt_scene_add_objects refuses. */
+int mcpt_extend_scene(const mcpt_scene_desc *desc, const mcpt_scene_addition *add, mcpt_object *objects_out, mcpt_triangle *triangles_out,
+                      mcpt_material *materials_out, int32_t *n_objects_out, int32_t *n_triangles_out, int32_t *n_materials_out);
+
 /* Replaces the pixel/spp loop of Renderer::Render (Renderer.cpp:21-91): fb_host = W*H*3 floats,
  * row-major m = j*W + i, linear radiance averaged over spp -- what `framebuffer` holds at Renderer.cpp:91.
  * Blocking.  Tone map and PNG output (Renderer.cpp:95-109) stay with the caller. */
@@ -1112,6 +1165,9 @@ int mcpt_group_deform(mcpt_group *group, int32_t n, const mcpt_object_vertices *
 /* mcpt_scene_set_visibility on every replica, with the same checks before any device call.  If a replica fails, the replicas that had
  * succeeded get their previous mask back. */
 int mcpt_group_set_visibility(mcpt_group *group, int32_t n, const mcpt_object_visibility *items);
+/* mcpt_scene_add_objects on every replica, with the same checks once before any device call.  Every replica keeps its previous arrays
+ * aside until all have succeeded; if one fails, the replicas that had grown get them back, counts and snapshot included. */
+int mcpt_group_add_objects(mcpt_group *group, const mcpt_scene_addition *add, int32_t *first_object /* nullable */);
 void mcpt_group_destroy(mcpt_group *group);
 const char *mcpt_group_last_error(void);
 
