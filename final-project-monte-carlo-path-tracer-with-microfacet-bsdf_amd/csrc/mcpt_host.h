@@ -8,7 +8,8 @@
 //   mcpt_render.hip     the frame-level entry points (render, adaptive, AOVs, denoise, motion, temporal blend); mcpt_frame.h has what
 //                       it shares with
 //   mcpt_sequence.hip   mcpt_temporal_accumulate and mcpt_sequence_*: a frame loop whose history and buffers stay on the device
-//   mcpt_query.hip      ray queries, tone map and the debug entry points
+//   mcpt_query.hip      ray queries on host memory, tone map and the debug entry points
+//   mcpt_rayquery.hip   mcpt_query_closest / mcpt_query_occluded: ray queries on device memory, with their kernels
 //   mcpt_multi.hip      mcpt_group_*
 #pragma once
 #include <hip/hip_runtime.h>
@@ -185,6 +186,22 @@ struct SharedBufs {
     uint32_t n_pix = 0;
 };
 
+// What mcpt_query_closest / mcpt_query_occluded (csrc/mcpt_rayquery.hip) keep between calls.  The buffers only ever grow, so a call
+// allocates only when it stages more rays than any call before it.  `done` is recorded on the caller's stream behind every query: a call
+// that frees or swaps what a query reads (the geometry arrays, these buffers) waits for it on the host first (query_settle, below), and
+// a query on another stream waits for it on the device before it reuses the staging buffers.
+struct QueryBufs {
+    DevBuf<float4> ray_o, ray_d;     // one chunk of staged rays; ray_d.w = tmax
+    DevBuf<uint4> hit;               // their closest hits
+    RetryBufs retry;                 // list 0 alone: the rays of a chunk, for trees that run the retry flavour
+    DevBuf<int32_t> ranges;          // the mesh triangle ranges for the object lookup: m starts in ascending order, then their m objects
+    std::vector<int32_t> h_ranges;   // its host copy
+    bool table_valid = false;        // `ranges` describes the scene's objects (false again after mcpt_scene_add_objects)
+    Event done;
+    bool pending = false;            // `done` has been recorded and nobody has waited for it on the host since
+    hipStream_t last_stream = nullptr;
+};
+
 // Environment knobs, read ONCE per scene in mcpt_scene_create: a render call never calls getenv.
 struct Knobs {
     bool overlap = true;        // MCPT_OVERLAP=0: one stream instead of three
@@ -200,6 +217,7 @@ struct Knobs {
     // k_trace_shadow -11 %, k_direct -14 %; chess within noise for 64..1024.  8 per CU, a persistent grid, was 30 % slower in round 1).
     uint32_t shadow_grid_per_cu = 128;    // MCPT_SHADOW_GRID_PER_CU: grid cap of k_trace_shadow
     uint32_t direct_grid_per_cu = 64;     // MCPT_DIRECT_GRID_PER_CU: grid cap of k_direct for LDS-resident scenes (0: none)
+    uint32_t query_chunk = 1u << 20;      // MCPT_QUERY_CHUNK: most rays mcpt_query_closest / mcpt_query_occluded stage at once (at least 64)
     // pure test hooks, compiled only into the checking build (-DMCPT_TEST_HOOKS, libmcpt_hip_check.so)
     uint32_t ring_start = 0;    // MCPT_RING_START: the free ring's counters start here (exercises the 2^32 wrap)
     int host_delay_us = 0;      // MCPT_HOST_DELAY_US: a slow host
@@ -453,6 +471,7 @@ struct mcpt_scene {
     mcpt::DevBuf<unsigned long long> dbg;
     mcpt::DevScene view{};
     mcpt::Event fork;
+    mcpt::QueryBufs query;
     mcpt::SharedBufs shared;
     // A wavefront pool: its own path lists, queues, clamp stack, counters and streams.  With MCPT_POOLS=2 two pools
     // are driven by two host threads on disjoint halves of each pass, so that one pool's k_shade (and its host
@@ -478,6 +497,17 @@ struct mcpt_scene {
 namespace mcpt {
 
 using PoolCtx = mcpt_scene::PoolCtx;
+
+// Waits on the host for the last ray query enqueued on the scene (QueryBufs::done).  Called, with the scene's device current, by everything
+// that frees or swaps arrays a query reads; without a query in flight it does nothing.  objects_changed: the object table is no longer
+// the one the query's range table was made from.
+inline hipError_t query_settle(mcpt_scene *sc, bool objects_changed = false) {
+    if (objects_changed) sc->query.table_valid = false;
+    if (!sc->query.pending) return hipSuccess;
+    const hipError_t e = hipEventSynchronize(sc->query.done);
+    if (e == hipSuccess) sc->query.pending = false;
+    return e;
+}
 
 // ---- mcpt_upload.hip
 // The two halves of mcpt_scene_create, exposed for mcpt_group_create (csrc/mcpt_multi.hip), which flattens the scene and builds its

@@ -213,4 +213,20 @@ void launch_debug_material(const DevScene &S, int kind, uint32_t n, const float 
 void launch_accumulate(const float *result, const uint32_t *pixel_list, uint32_t n_pix, int32_t s_pass, float spp_total,
                        float *fb, double *moments, hipStream_t s);
 
+// Ray queries on device memory (csrc/mcpt_rayquery.hip).  The outputs of k_query_resolve: mcpt_hit_buffers moved to the first ray of the
+// chunk; a null member is not written.
+struct QueryOut {
+    double *t;
+    int32_t *prim, *object;
+    float *uv, *normal, *point;
+};
+// The caller's tight arrays (n*3 floats each; tmax: n floats or nullptr) -> the float4 ray arrays; ray_d[i].w = tmax[i], +inf without one.
+void launch_query_pack(uint32_t n, const float *origins, const float *dirs, const float *tmax, float4 *ray_o, float4 *ray_d, hipStream_t s);
+// The outputs of n staged rays from their closest hits (launch_trace_closest).  has_tmax: a ray keeps its hit iff t - ray_d.w <= -EPSILON.
+// starts / objs: the n_ranges mesh triangle ranges in ascending order of their first triangle, and the object of each.
+void launch_query_resolve(const DevScene &S, uint32_t n, const float4 *ray_o, const float4 *ray_d, const uint4 *hit, bool has_tmax, const int32_t *starts,
+                          const int32_t *objs, int32_t n_ranges, const QueryOut &out, hipStream_t s);
+// occluded[i] = 1 iff some primitive is hit with t - ray_d[i].w <= -EPSILON (the kOccluder walk; stops at the first such primitive).
+void launch_query_occluded(const DevScene &S, uint32_t n, const float4 *ray_o, const float4 *ray_d, uint8_t *occluded, const RetryList &rl, hipStream_t s);
+
 }  // namespace mcpt

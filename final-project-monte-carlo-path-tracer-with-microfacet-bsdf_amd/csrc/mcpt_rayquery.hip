@@ -1,0 +1,303 @@
+// Ray queries on device memory (include/mcpt.h: mcpt_query_closest, mcpt_query_occluded): rays are read from and results written to
+// the memory of the scene's device, on the caller's stream, through staging buffers the scene owns (QueryBufs, csrc/mcpt_host.h).
+//
+// Per chunk of at most MCPT_QUERY_CHUNK rays, all on the caller's stream:
+//   k_query_pack       the caller's tight n*3 arrays -> the traversal's float4 ray arrays; the direction's .w carries tmax (+inf without
+//                      one), the layout of a shadow-queue entry.  One lane per ray: a wave reads 768 contiguous bytes of each array.
+//   closest hits       launch_trace_closest (csrc/mcpt_kernels.hip) on the staged chunk: the refill kernel, every stack flavour, the
+//                      retrace and the LDS-resident flavour, exactly as mcpt_intersect runs them.  No second copy of the loop.
+//   k_query_resolve    {t, prim} hit + ray + live records -> the outputs the caller asked for.  The tmax filter first, on the finished
+//                      closest hit; for triangles the test that recorded the hit is repeated for (u, v) (hit_points, csrc/mcpt_temporal.hip).
+//   k_query_occluded   the any-hit query: one lane per staged ray, traverse<true, ...>(.., tmax, .., found = true), i.e. the kOccluder
+//                      walk alone, which ends at the first primitive with t - tmax <= -EPSILON.  k_query_occluded_retrace: the rays of a
+//                      retry-flavour launch that lost a stack entry, again with the scratch stack.
+// Small scenes: k_query_occluded's SMALL instantiation has no LDS prologue; it walks the global arrays (which exist for every scene)
+// with the 8-entry stack of the small flavour, the plain walk the checking build runs on those scenes too.
+#include <cfloat>
+#include <cmath>
+
+#include "mcpt_host.h"
+#include "mcpt_stack_dispatch.h"
+#include "mcpt_traverse.h"
+
+using namespace mcpt;
+
+namespace mcpt {
+
+namespace {
+
+inline uint32_t query_blocks(uint32_t n) { return (n + kBlock - 1) / kBlock; }
+
+MCPT_DI double query_hit_t(const uint4 &h) { return __longlong_as_double((long long)(((unsigned long long)h.y << 32) | h.x)); }
+
+__global__ __launch_bounds__(kBlock) void k_query_pack(uint32_t n, const float *__restrict__ origins, const float *__restrict__ dirs,
+                                                       const float *__restrict__ tmax, float4 *__restrict__ ray_o, float4 *__restrict__ ray_d) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const size_t j = 3 * (size_t)i;
+    ray_o[i] = make_float4(origins[j], origins[j + 1], origins[j + 2], 0.f);
+    ray_d[i] = make_float4(dirs[j], dirs[j + 1], dirs[j + 2], tmax ? tmax[i] : INFINITY);
+}
+
+// The object of triangle `prim`: the last mesh range whose first triangle is <= prim (the bisection of k_move_objects).
+MCPT_DI int32_t query_object_of(const int32_t *__restrict__ starts, const int32_t *__restrict__ objs, int32_t n_ranges, int32_t prim) {
+    int32_t lo = 0, hi = n_ranges - 1;
+    while (lo < hi) {
+        const int32_t mid = (lo + hi + 1) >> 1;
+        if (starts[mid] <= prim) lo = mid;
+        else hi = mid - 1;
+    }
+    return objs[lo];
+}
+
+// Which outputs are wanted is a wave-uniform branch on the pointers; every store is a plain vector store.
+__global__ __launch_bounds__(kBlock) void k_query_resolve(DevScene S, uint32_t n, const float4 *__restrict__ ray_o, const float4 *__restrict__ ray_d,
+                                                          const uint4 *__restrict__ hit, int has_tmax, const int32_t *__restrict__ starts,
+                                                          const int32_t *__restrict__ objs, int32_t n_ranges, QueryOut out) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const uint4 h = hit[i];
+    const float4 d4 = ray_d[i];
+    int32_t prim = (int32_t)h.z;
+    double t = query_hit_t(h);
+    // the occluder rule of leaf_step (csrc/mcpt_traverse.h) with dist = tmax, on the finished closest hit
+    const bool ok = prim >= 0 && (!has_tmax || t - (double)d4.w <= -(double)kEps);
+    if (!ok) {
+        t = DBL_MAX;
+        prim = -1;
+    }
+    if (out.t) out.t[i] = t;
+    if (out.prim) out.prim[i] = prim;
+    if (!(out.object || out.uv || out.normal || out.point)) return;
+    int32_t object = -1;
+    float uf = 0.f, vf = 0.f;
+    f3 nrm = mk3(0.f, 0.f, 0.f), p = mk3(0.f, 0.f, 0.f);
+    if (ok) {
+        const float4 o4 = ray_o[i];
+        const f3 ro = mk3(o4.x, o4.y, o4.z), rd = mk3(d4.x, d4.y, d4.z);
+        if (prim < S.n_tri) {
+            if (out.uv || out.point) {
+                const TriGeom g = S.tri_geom[prim];
+                double tt, u, v;
+                if (tri_hit(g, make_ray(ro, rd), tt, u, v)) {  // (the test that recorded the hit: it succeeds again)
+                    uf = (float)u;
+                    vf = (float)v;
+                }
+                p = mk3(g.v0[0] + (g.e1x * uf + g.e2xy[0] * vf), g.v0[1] + (g.e1yz[0] * uf + g.e2xy[1] * vf), g.v0[2] + (g.e1yz[1] * uf + g.e2z * vf));
+            }
+            if (out.normal) {
+                const float4 q = *reinterpret_cast<const float4 *>(S.tri_shade + prim);  // {n.xyz, mat}
+                nrm = mk3(q.x, q.y, q.z);
+            }
+            if (out.object) object = query_object_of(starts, objs, n_ranges, prim);
+        } else {
+            const int32_t k = prim - S.n_tri;  // a sphere's slot is its object index
+            object = k;
+            if (out.normal || out.point) {
+                const float4 c = *reinterpret_cast<const float4 *>(S.spheres + k);  // {c.xyz, radius}
+                p = ro + rd * (float)t;
+                nrm = normalized(p - mk3(c.x, c.y, c.z));
+            }
+        }
+    }
+    if (out.object) out.object[i] = object;
+    if (out.uv) {
+        out.uv[2 * (size_t)i] = uf;
+        out.uv[2 * (size_t)i + 1] = vf;
+    }
+    if (out.normal) {
+        out.normal[3 * (size_t)i] = nrm.x;
+        out.normal[3 * (size_t)i + 1] = nrm.y;
+        out.normal[3 * (size_t)i + 2] = nrm.z;
+    }
+    if (out.point) {
+        out.point[3 * (size_t)i] = p.x;
+        out.point[3 * (size_t)i + 1] = p.y;
+        out.point[3 * (size_t)i + 2] = p.z;
+    }
+}
+
+// Any-hit: `found = true` skips the window walk, so only the kOccluder walk runs and `visible` is "no primitive with t - tmax <= -EPSILON".
+// PREP (the dispatch's small-scene slot): the plain walk over the global arrays with STK = kSmallStk entries; no LDS copy of the scene.
+template <int STK, bool MARK, bool PREP>
+__global__ __launch_bounds__(kBlock) void k_query_occluded(DevScene S, uint32_t n, const float4 *__restrict__ ray_o, const float4 *__restrict__ ray_d,
+                                                           uint8_t *__restrict__ occluded, RetryList rl) {
+    __shared__ int32_t stk[STK][kBlock];
+    const int tid = threadIdx.x;
+    const uint32_t i = blockIdx.x * kBlock + tid;
+    if (i >= n) return;
+    const float4 o = ray_o[i], d = ray_d[i];
+    const Ray r = make_ray(mk3(o.x, o.y, o.z), mk3(d.x, d.y, d.z));
+    const TraceResult tr = traverse<true, STK, MARK, false>(S, r, d.w, stk, tid, /*found=*/true);
+    if (MARK && tr.dropped) retry_append(rl, i);  // (undecided: k_query_occluded_retrace)
+    else occluded[i] = tr.visible ? 0 : 1;
+}
+
+__global__ __launch_bounds__(kBlock) void k_query_occluded_retrace(DevScene S, const float4 *__restrict__ ray_o, const float4 *__restrict__ ray_d,
+                                                                   uint8_t *__restrict__ occluded, RetryList rl) {
+    __shared__ int32_t stk[1][kBlock];
+    const uint32_t n = min(*rl.count, rl.cap);
+    for (uint32_t k = blockIdx.x * kBlock + threadIdx.x; k < n; k += gridDim.x * kBlock) {
+        const uint32_t i = rl.items[k];
+        const float4 o = ray_o[i], d = ray_d[i];
+        const Ray r = make_ray(mk3(o.x, o.y, o.z), mk3(d.x, d.y, d.z));
+        const TraceResult tr = traverse_scratch<true>(S, r, d.w, stk, threadIdx.x, /*found=*/true);
+        occluded[i] = tr.visible ? 0 : 1;
+    }
+    retry_finish(rl);
+}
+
+}  // namespace
+
+void launch_query_pack(uint32_t n, const float *origins, const float *dirs, const float *tmax, float4 *ray_o, float4 *ray_d, hipStream_t s) {
+    if (n == 0) return;
+    hipLaunchKernelGGL(k_query_pack, dim3(query_blocks(n)), dim3(kBlock), 0, s, n, origins, dirs, tmax, ray_o, ray_d);
+}
+
+void launch_query_resolve(const DevScene &S, uint32_t n, const float4 *ray_o, const float4 *ray_d, const uint4 *hit, bool has_tmax, const int32_t *starts,
+                          const int32_t *objs, int32_t n_ranges, const QueryOut &out, hipStream_t s) {
+    if (n == 0) return;
+    hipLaunchKernelGGL(k_query_resolve, dim3(query_blocks(n)), dim3(kBlock), 0, s, S, n, ray_o, ray_d, hit, has_tmax ? 1 : 0, starts, objs, n_ranges, out);
+}
+
+void launch_query_occluded(const DevScene &S, uint32_t n, const float4 *ray_o, const float4 *ray_d, uint8_t *occluded, const RetryList &rl, hipStream_t s) {
+    if (n == 0) return;
+    const dim3 g(query_blocks(n)), b(kBlock);
+    MCPT_STACK_DISPATCH(S.height, k_query_occluded, hipLaunchKernelGGL(k_query_occluded_retrace, dim3(kRetraceGrid), b, 0, s, S, ray_o, ray_d, occluded, rl), g, b, 0,
+                        s, S, n, ray_o, ray_d, occluded, rl);
+}
+
+}  // namespace mcpt
+
+namespace {
+
+// hipPointerGetAttributes places p in the memory of `device`
+bool on_device(const void *p, int device) {
+    hipPointerAttribute_t a;
+    std::memset(&a, 0, sizeof a);
+    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
+        (void)hipGetLastError();  // (an address the runtime does not know: not a sticky error)
+        return false;
+    }
+    return a.type == hipMemoryTypeDevice && a.device == device;
+}
+
+// The table of mesh triangle-range starts for the object lookup, in ascending order of the first triangle: m starts, then the m objects.
+void build_range_table(const SceneSource &S, std::vector<int32_t> &table) {
+    std::vector<std::pair<int32_t, int32_t>> r;
+    for (size_t o = 0; o < S.objects.size(); ++o)
+        if (S.objects[o].kind == MCPT_OBJ_MESH) r.emplace_back(S.objects[o].first_tri, (int32_t)o);
+    std::sort(r.begin(), r.end());
+    const size_t m = r.size();
+    table.assign(2 * std::max<size_t>(m, 1), 0);
+    for (size_t k = 0; k < m; ++k) {
+        table[k] = r[k].first;
+        table[std::max<size_t>(m, 1) + k] = r[k].second;
+    }
+    if (m == 0) table[1] = -1;  // (no mesh: no triangle can be hit)
+}
+
+// Both queries after their argument checks.  occluded != nullptr: the any-hit query; else closest hits into `hits`.
+int run_query(mcpt_scene *sc, int64_t n, const mcpt_ray_buffers &rays, const mcpt_hit_buffers *hits, uint8_t *occluded, hipStream_t st, mcpt_query_info *info) {
+    mcpt_query_info qi;
+    std::memset(&qi, 0, sizeof qi);
+    HIP_TRY(hipSetDevice(sc->device));
+    QueryBufs &Q = sc->query;
+    const uint32_t chunk = (uint32_t)std::min<int64_t>(n, (int64_t)sc->knobs.query_chunk);
+    const bool need_retry = stack_uses_retry(sc->view.height);
+    if (!Q.table_valid) build_range_table(sc->src, Q.h_ranges);
+    const bool grow = Q.ray_o.n < chunk || Q.ray_d.n < chunk || Q.hit.n < chunk || (need_retry && Q.retry.cap[0] < chunk) || Q.ranges.n < Q.h_ranges.size() || !Q.done.e;
+    if (grow) {
+        HIP_TRY(query_settle(sc));  // the buffers about to be freed may still be read by an earlier query
+        if (!Q.done.e) HIP_TRY(Q.done.create());
+        HIP_TRY(Q.ray_o.alloc(chunk));
+        HIP_TRY(Q.ray_d.alloc(chunk));
+        HIP_TRY(Q.hit.alloc(chunk));
+        if (need_retry && Q.retry.cap[0] < chunk) {
+            HIP_TRY(Q.retry.ctl.alloc(8));
+            HIP_TRY(hipMemsetAsync(Q.retry.ctl.p, 0, 8 * sizeof(uint32_t), st));  // (the lists are empty between launches: zero again is the same state)
+            HIP_TRY(Q.retry.items[0].alloc(chunk));
+            Q.retry.cap[0] = chunk;
+        }
+        if (Q.ranges.n < Q.h_ranges.size()) {
+            HIP_TRY(Q.ranges.alloc(Q.h_ranges.size()));
+            Q.table_valid = false;
+        }
+        qi.grew = 1;
+    }
+    // a query on another stream may still be using the staging buffers
+    if (Q.pending && st != Q.last_stream) HIP_TRY(hipStreamWaitEvent(st, Q.done, 0));
+    if (!Q.table_valid) {  // (first call, and after mcpt_scene_add_objects, which has waited for every earlier query: a blocking copy, done before anything below is enqueued)
+        HIP_TRY(hipMemcpy(Q.ranges.p, Q.h_ranges.data(), Q.h_ranges.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+        Q.table_valid = true;
+    }
+    const int32_t n_ranges = (int32_t)(Q.h_ranges.size() / 2);
+    const RetryList rl = need_retry ? Q.retry.list(0) : RetryList{nullptr, nullptr, nullptr, 0u};
+    for (int64_t base = 0; base < n; base += chunk) {
+        const uint32_t m = (uint32_t)std::min<int64_t>(chunk, n - base);
+        launch_query_pack(m, rays.origins + 3 * base, rays.dirs + 3 * base, rays.tmax ? rays.tmax + base : nullptr, Q.ray_o.p, Q.ray_d.p, st);
+        if (occluded) {
+            launch_query_occluded(sc->view, m, Q.ray_o.p, Q.ray_d.p, occluded + base, rl, st);
+        } else {
+            launch_trace_closest(sc->view, m, nullptr, Q.ray_o.p, Q.ray_d.p, Q.hit.p, rl, st);
+            const QueryOut out{hits->t ? hits->t + base : nullptr,           hits->prim ? hits->prim + base : nullptr,
+                               hits->object ? hits->object + base : nullptr, hits->uv ? hits->uv + 2 * base : nullptr,
+                               hits->normal ? hits->normal + 3 * base : nullptr, hits->point ? hits->point + 3 * base : nullptr};
+            launch_query_resolve(sc->view, m, Q.ray_o.p, Q.ray_d.p, Q.hit.p, rays.tmax != nullptr, Q.ranges.p, Q.ranges.p + n_ranges, n_ranges, out, st);
+        }
+        qi.launches++;
+    }
+    const hipError_t le = hipGetLastError();
+    // behind the kernels even when a launch failed: whatever was enqueued still reads the scene
+    const hipError_t re = hipEventRecord(Q.done, st);
+    if (re == hipSuccess) {
+        Q.pending = true;
+        Q.last_stream = st;
+    }
+    HIP_TRY(le);
+    HIP_TRY(re);
+    qi.staged_bytes = (int64_t)(Q.ray_o.bytes() + Q.ray_d.bytes() + Q.hit.bytes() + Q.ranges.bytes() + Q.retry.items[0].bytes() + Q.retry.ctl.bytes());
+    if (info) *info = qi;
+    return MCPT_OK;
+}
+
+// The checks both calls share, before any device work.  0: go on; 1: n == 0, nothing to do; < 0: -(error code).
+int check_rays(const char *who, const mcpt_scene *sc, int64_t n, const mcpt_ray_buffers *rays, bool need_tmax, mcpt_query_info *info) {
+    if (info) std::memset(info, 0, sizeof *info);
+    const std::string w(who);
+    if (!sc) return -fail(MCPT_ERR_ARG, w + ": null scene");
+    if (n < 0 || n > 0x7fffffff) return -fail(MCPT_ERR_ARG, w + ": n must be in 0 .. 2^31 - 1");
+    if (n == 0) return 1;
+    if (!rays || !rays->origins || !rays->dirs) return -fail(MCPT_ERR_ARG, w + ": null rays, origins or dirs");
+    if (need_tmax && !rays->tmax) return -fail(MCPT_ERR_ARG, w + ": tmax is required");
+    if (!on_device(rays->origins, sc->device) || !on_device(rays->dirs, sc->device) || (rays->tmax && !on_device(rays->tmax, sc->device)))
+        return -fail(MCPT_ERR_ARG, w + ": origins, dirs and tmax must be memory of the scene's device");
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mcpt_query_closest(mcpt_scene *sc, int64_t n, const mcpt_ray_buffers *rays, const mcpt_hit_buffers *hits, void *hip_stream, mcpt_query_info *info) {
+    const int c = check_rays("mcpt_query_closest", sc, n, rays, false, info);
+    if (c < 0) return -c;
+    if (hits && !hits->t && !hits->prim && !hits->object && !hits->uv && !hits->normal && !hits->point) return fail(MCPT_ERR_ARG, "mcpt_query_closest: every hit pointer is null");
+    if (c == 1) return MCPT_OK;
+    if (!hits) return fail(MCPT_ERR_ARG, "mcpt_query_closest: null hits");
+    const void *outs[6] = {hits->t, hits->prim, hits->object, hits->uv, hits->normal, hits->point};
+    for (const void *p : outs)
+        if (p && !on_device(p, sc->device)) return fail(MCPT_ERR_ARG, "mcpt_query_closest: an output is not memory of the scene's device");
+    return run_query(sc, n, *rays, hits, nullptr, (hipStream_t)hip_stream, info);
+}
+
+int mcpt_query_occluded(mcpt_scene *sc, int64_t n, const mcpt_ray_buffers *rays, uint8_t *occluded, void *hip_stream, mcpt_query_info *info) {
+    const int c = check_rays("mcpt_query_occluded", sc, n, rays, true, info);
+    if (c < 0) return -c;
+    if (c == 1) return MCPT_OK;
+    if (!occluded) return fail(MCPT_ERR_ARG, "mcpt_query_occluded: null occluded");
+    if (!on_device(occluded, sc->device)) return fail(MCPT_ERR_ARG, "mcpt_query_occluded: occluded is not memory of the scene's device");
+    return run_query(sc, n, *rays, nullptr, occluded, (hipStream_t)hip_stream, info);
+}
+
+}  // extern "C"

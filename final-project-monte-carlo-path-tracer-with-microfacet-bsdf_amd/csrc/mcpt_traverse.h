@@ -1,7 +1,7 @@
 // The BVH walk of the wavefront path tracer: one definition of the node visit, the descend step, the stack, the leaf test and the
 // closest-hit update, used by the generic loop (traverse_loop: every query kind, node format and stack flavour) and by the lane-refill
 // kernel (k_trace_closest_refill in mcpt_kernels.hip, which traces nearly every closest-hit ray of a frame).  A change to what is tested
-// per ray is made here once.  Included by mcpt_kernels.hip only.
+// per ray is made here once.  Included by the translation units that define traversal kernels: mcpt_kernels.hip and mcpt_rayquery.hip.
 #pragma once
 
 #include <cfloat>

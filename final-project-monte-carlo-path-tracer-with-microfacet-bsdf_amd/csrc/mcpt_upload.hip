@@ -29,6 +29,7 @@ void Knobs::read() {
     if ((v = std::getenv("MCPT_POOL_MIN_WORK"))) pool_min_work = (uint64_t)std::max(1, std::atoi(v));
     if ((v = std::getenv("MCPT_SHADOW_GRID_PER_CU"))) shadow_grid_per_cu = (uint32_t)std::max(1, std::atoi(v));
     if ((v = std::getenv("MCPT_DIRECT_GRID_PER_CU"))) direct_grid_per_cu = (uint32_t)std::max(0, std::atoi(v));
+    if ((v = std::getenv("MCPT_QUERY_CHUNK"))) query_chunk = (uint32_t)std::max(64, std::atoi(v));
 #ifdef MCPT_TEST_HOOKS
     if ((v = std::getenv("MCPT_RING_START"))) ring_start = (uint32_t)std::strtoul(v, nullptr, 0);
     if ((v = std::getenv("MCPT_HOST_DELAY_US"))) host_delay_us = std::atoi(v);
@@ -491,6 +492,7 @@ int rebuild(mcpt_scene *sc, const std::vector<uint8_t> &moved, const std::vector
         return MCPT_OK;
     }
     HIP_TRY(hipSetDevice(sc->device));
+    HIP_TRY(query_settle(sc));  // a ray query still in flight reads the arrays this call swaps and frees
     GeomBufs g2;  // built aside; swapped in once the new tree is known to be usable
     SceneMeta meta = sc->meta;
     const size_t nt = (size_t)meta.n_triangles;
@@ -790,6 +792,7 @@ int mcpt::apply_add(mcpt_scene *sc, const mcpt_scene_addition *add, int32_t *fir
     ui.n_moved_tris = add->n_triangles;
     SceneSource &S = sc->src;
     HIP_TRY(hipSetDevice(sc->device));
+    HIP_TRY(query_settle(sc, true));
     AddAside local;
     AddAside &A = keep ? *keep : local;
     const size_t no = S.objects.size(), nt = S.triangles.size(), nm = S.materials.size();
@@ -922,6 +925,7 @@ int mcpt::apply_add(mcpt_scene *sc, const mcpt_scene_addition *add, int32_t *fir
 
 int mcpt::undo_add(mcpt_scene *sc, AddAside &A) {
     HIP_TRY(hipSetDevice(sc->device));
+    HIP_TRY(query_settle(sc, true));
     exchange_add(sc, A);
     resize_source(sc->src, A.n_objects, A.n_triangles, A.n_materials);
     fill_view(sc);
@@ -1160,6 +1164,7 @@ int mcpt_scene_snapshot(mcpt_scene *sc) {
 void mcpt_scene_destroy(mcpt_scene *sc) {
     if (!sc) return;
     (void)hipSetDevice(sc->device);
+    (void)query_settle(sc);
 #if defined(MCPT_TRAVERSAL_STATS) || defined(MCPT_CHECK_DIRECT_SKIP)
     if (sc->dbg.p) {
         unsigned long long h[36];

@@ -37,6 +37,7 @@ EXPORTS = ["mcpt_scene_create", "mcpt_scene_destroy", "mcpt_render", "mcpt_rende
            "mcpt_centre_rays", "mcpt_render_aovs_features", "mcpt_render_motion_features", "mcpt_sequence_create_features",
            "mcpt_denoise_feedback", "mcpt_sequence_create_feedback", "mcpt_sequence_history",
            "mcpt_scene_ray_counts", "mcpt_scene_primary_conductor_counts",
+           "mcpt_query_closest", "mcpt_query_occluded",
            "mcpt_group_create", "mcpt_group_render", "mcpt_group_size", "mcpt_group_get_info", "mcpt_group_scene", "mcpt_group_destroy", "mcpt_group_last_error",
            "mcpt_last_error", "mcpt_version"]
 
@@ -325,37 +326,104 @@ class DevicePositions:
             raise ValueError("DevicePositions: a non-null device address and a triangle count >= 0")
 
 
+_TORCH_TYPESTR = {"float32": "<f4", "float64": "<f8", "int32": "<i4", "uint8": "|u1"}
+
+
+def _device_buffer(v, who, what, typestrs=("<f4", "=f4", "|f4"), type_name="float32"):
+    """(address, shape) of a buffer in device memory -- anything with __cuda_array_interface__, or with data_ptr() and is_cuda (a torch
+    tensor) -- or None for anything else.  Element type and C-contiguity are checked here (ValueError); the shape is the caller's to check."""
+    cai = getattr(v, "__cuda_array_interface__", None)
+    if cai is not None:
+        shape, typestr, strides = tuple(int(d) for d in cai["shape"]), cai["typestr"], cai.get("strides")
+        ptr = cai["data"][0]
+    elif hasattr(v, "data_ptr") and getattr(v, "is_cuda", False):
+        if not v.is_contiguous():
+            raise ValueError("%s: a device tensor must be contiguous" % who)
+        name = str(v.dtype).rsplit(".", 1)[-1]
+        shape, typestr, strides = tuple(int(d) for d in v.shape), _TORCH_TYPESTR.get(name, name), None
+        ptr = v.data_ptr()
+    else:
+        return None
+    if typestr not in typestrs:
+        raise ValueError("%s: %s must be %s, not %s" % (who, what, type_name, typestr))
+    if strides is not None:
+        want, acc = [], int(typestr[2:])
+        for d in reversed(shape):
+            want.insert(0, acc)
+            acc *= d
+        if tuple(strides) != tuple(want):
+            raise ValueError("%s: %s must be C-contiguous" % (who, what))
+    return int(ptr), shape
+
+
 def _device_positions(v):
     """DevicePositions for a device buffer, None for anything else.  Shape, dtype and contiguity are checked here: the library reads
     n_tri * 9 float32 values at the address."""
     if isinstance(v, DevicePositions):
         return v
-    cai = getattr(v, "__cuda_array_interface__", None)
-    if cai is not None:
-        shape, typestr, strides = tuple(cai["shape"]), cai["typestr"], cai.get("strides")
-        ptr = cai["data"][0]
-    elif hasattr(v, "data_ptr") and getattr(v, "is_cuda", False):
-        if not v.is_contiguous():
-            raise ValueError("deform: a device tensor must be contiguous")
-        shape, typestr, strides = tuple(v.shape), "<f4" if str(v.dtype).endswith("float32") else str(v.dtype), None
-        ptr = v.data_ptr()
-    else:
+    b = _device_buffer(v, "deform", "device positions")
+    if b is None:
         return None
-    if typestr not in ("<f4", "=f4", "|f4"):
-        raise ValueError("deform: device positions must be float32, not %s" % typestr)
-    if strides is not None:
-        want, acc = [], 4
-        for d in reversed(shape):
-            want.insert(0, acc)
-            acc *= d
-        if tuple(strides) != tuple(want):
-            raise ValueError("deform: device positions must be C-contiguous")
+    ptr, shape = b
     n = 1
     for d in shape:
         n *= int(d)
     if not ((len(shape) == 3 and shape[1:] == (3, 3)) or len(shape) == 1) or n % 9:
         raise ValueError("deform: positions have shape (n_tri, 3, 3) or (n_tri * 9,), not %s" % (shape,))
     return DevicePositions(ptr, n // 9) if n else None
+
+
+class RayBuffers(C.Structure):
+    _fields_ = [("origins", C.c_void_p), ("dirs", C.c_void_p), ("tmax", C.c_void_p)]
+
+
+class HitBuffers(C.Structure):
+    _fields_ = [("t", C.c_void_p), ("prim", C.c_void_p), ("object", C.c_void_p), ("uv", C.c_void_p), ("normal", C.c_void_p), ("point", C.c_void_p)]
+
+
+class QueryInfo(C.Structure):
+    _fields_ = [("launches", C.c_int32), ("grew", C.c_int32), ("staged_bytes", C.c_int64), ("reserved", C.c_int32 * 4)]
+
+    def as_dict(self):
+        return {"launches": int(self.launches), "grew": int(self.grew), "staged_bytes": int(self.staged_bytes)}
+
+
+# The outputs of HipScene.query_closest: name -> (element type of __cuda_array_interface__, its name, values per ray, torch dtype name)
+QUERY_OUTPUTS = {"t": (("<f8", "=f8"), "float64", 1, "float64"), "prim": (("<i4", "=i4"), "int32", 1, "int32"),
+                 "object": (("<i4", "=i4"), "int32", 1, "int32"), "uv": (("<f4", "=f4", "|f4"), "float32", 2, "float32"),
+                 "normal": (("<f4", "=f4", "|f4"), "float32", 3, "float32"), "point": (("<f4", "=f4", "|f4"), "float32", 3, "float32")}
+
+
+def _query_rays(who, origins, dirs, tmax):
+    """The device addresses and the ray count of a query's inputs: float32, C-contiguous, (n, 3) and (n, 3), tmax (n,) or None."""
+    bo, bd = _device_buffer(origins, who, "origins"), _device_buffer(dirs, who, "dirs")
+    if bo is None or bd is None:
+        raise ValueError("%s: origins and dirs are buffers in device memory (__cuda_array_interface__, or data_ptr() and is_cuda)" % who)
+    if len(bo[1]) != 2 or bo[1][1] != 3 or bd[1] != bo[1]:
+        raise ValueError("%s: origins and dirs have shape (n, 3), not %s and %s" % (who, bo[1], bd[1]))
+    n = bo[1][0]
+    pt = 0
+    if tmax is not None:
+        bt = _device_buffer(tmax, who, "tmax")
+        if bt is None:
+            raise ValueError("%s: tmax is a buffer in device memory" % who)
+        if bt[1] != (n,):
+            raise ValueError("%s: tmax has shape (%d,), not %s" % (who, n, bt[1]))
+        pt = bt[0]
+    return n, RayBuffers(bo[0] or None, bd[0] or None, pt or None)
+
+
+def _query_output(who, name, v, n, typestrs, type_name, width):
+    b = _device_buffer(v, who, "out[%r]" % name, typestrs, type_name)
+    if b is None:
+        raise ValueError("%s: out[%r] is a buffer in device memory" % (who, name))
+    if b[1] != ((n,) if width == 1 else (n, width)):
+        raise ValueError("%s: out[%r] has shape %s, not %s" % (who, name, (n,) if width == 1 else (n, width), b[1]))
+    return b[0]
+
+
+def _is_torch(*vs):
+    return all(hasattr(v, "data_ptr") and getattr(v, "is_cuda", False) for v in vs)
 
 
 def _vertex_items(items, n_tri_of):
@@ -537,6 +605,10 @@ def lib(path=None):
         L.mcpt_render_device.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_void_p, C.POINTER(Stats)]
         L.mcpt_intersect.restype = C.c_int
         L.mcpt_intersect.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.mcpt_query_closest.restype = C.c_int
+        L.mcpt_query_closest.argtypes = [C.c_void_p, C.c_int64, C.POINTER(RayBuffers), C.POINTER(HitBuffers), C.c_void_p, C.POINTER(QueryInfo)]
+        L.mcpt_query_occluded.restype = C.c_int
+        L.mcpt_query_occluded.argtypes = [C.c_void_p, C.c_int64, C.POINTER(RayBuffers), C.c_void_p, C.c_void_p, C.POINTER(QueryInfo)]
         L.mcpt_cast_rays.restype = C.c_int
         L.mcpt_cast_rays.argtypes = [C.c_void_p, C.POINTER(Params), C.c_int64] + [C.c_void_p] * 6
         L.mcpt_camera_rays.restype = C.c_int
@@ -1323,6 +1395,57 @@ class HipScene:
         prim = np.zeros(n, dtype=np.int32)
         _check(self.L.mcpt_intersect(self.h, n, _ptr(o), _ptr(d), _ptr(t), _ptr(prim)), L=self.L)
         return t, prim
+
+    def query_closest(self, origins, dirs, tmax=None, want=("t", "prim"), out=None, stream=None):
+        """mcpt_query_closest: closest hits of rays that sit in the memory of the scene's device, enqueued on `stream` without a host
+        synchronisation.  origins, dirs: float32, C-contiguous, shape (n, 3); tmax: (n,) or None (no limit; with one, a ray keeps its hit
+        iff t - tmax <= -1e-4f).  Each is anything with __cuda_array_interface__, or with data_ptr() and is_cuda (a torch tensor).
+        want: names among t, prim, object, uv, normal, point.  out: dict name -> device buffer (float64 (n,), int32 (n,), int32 (n,),
+        float32 (n, 2), (n, 3), (n, 3)); it may be None when the inputs are torch tensors: the outputs are then torch.empty tensors on their
+        device and the stream defaults to torch's current one.  Returns (dict name -> buffer, mcpt_query_info as a dict); the results are
+        ready in stream order."""
+        who = "query_closest"
+        want = tuple(want)
+        if not want or any(w not in QUERY_OUTPUTS for w in want) or len(set(want)) != len(want):
+            raise ValueError("%s: want is a non-empty selection of %s without repeats, not %r" % (who, tuple(QUERY_OUTPUTS), want))
+        n, rays = _query_rays(who, origins, dirs, tmax)
+        if out is None:
+            if not _is_torch(origins, dirs):
+                raise ValueError("%s: out is required unless the rays are torch tensors" % who)
+            import torch
+            out = {w: torch.empty((n,) if QUERY_OUTPUTS[w][2] == 1 else (n, QUERY_OUTPUTS[w][2]), dtype=getattr(torch, QUERY_OUTPUTS[w][3]), device=origins.device)
+                   for w in want}
+            if stream is None:
+                stream = torch.cuda.current_stream(origins.device).cuda_stream
+        hits = HitBuffers()
+        for w in want:
+            if w not in out:
+                raise ValueError("%s: out has no buffer for %r" % (who, w))
+            ts, tn, width, _ = QUERY_OUTPUTS[w]
+            setattr(hits, w, _query_output(who, w, out[w], n, ts, tn, width) or None)
+        info = QueryInfo()
+        _check(self.L.mcpt_query_closest(self.h, n, C.byref(rays), C.byref(hits), C.c_void_p(int(stream or 0)), C.byref(info)), L=self.L)
+        return {w: out[w] for w in want}, info.as_dict()
+
+    def query_occluded(self, origins, dirs, tmax, out=None, stream=None):
+        """mcpt_query_occluded: the any-hit query for rays in device memory -> (uint8 (n,) device buffer, mcpt_query_info as a dict):
+        1 where some primitive is hit with t - tmax <= -1e-4f.  tmax = inf asks whether anything is hit.  Inputs, out and stream as in
+        query_closest."""
+        who = "query_occluded"
+        if tmax is None:
+            raise ValueError("%s: tmax is required" % who)
+        n, rays = _query_rays(who, origins, dirs, tmax)
+        if out is None:
+            if not _is_torch(origins, dirs):
+                raise ValueError("%s: out is required unless the rays are torch tensors" % who)
+            import torch
+            out = torch.empty((n,), dtype=torch.uint8, device=origins.device)
+            if stream is None:
+                stream = torch.cuda.current_stream(origins.device).cuda_stream
+        p = _query_output(who, "occluded", out, n, ("|u1", "<u1", "=u1"), "uint8", 1)
+        info = QueryInfo()
+        _check(self.L.mcpt_query_occluded(self.h, n, C.byref(rays), C.c_void_p(p or 0), C.c_void_p(int(stream or 0)), C.byref(info)), L=self.L)
+        return out, info.as_dict()
 
     def shadow_visible(self, origins, dirs, dist, found=None, shard=None, list=0):
         """mcpt_debug_shadow: the render loop's shadow query (k_trace_shadow, its retrace included) for rays of the caller's -> bool [n]:

@@ -1123,6 +1123,57 @@ int mcpt_camera_rays(mcpt_scene *scene, const mcpt_camera *camera, uint32_t seed
  * sample: the ray is a function of the camera.  MCPT_ERR_ARG for a null pointer with n > 0, n < 0 or above 2^31 - 1, width or height <= 0. */
 int mcpt_centre_rays(mcpt_scene *scene, const mcpt_camera *camera, int64_t n, const uint32_t *pixel, float *origins, float *dirs);
 
+/* ---- Ray queries on device memory: mcpt_intersect for rays that already sit in the memory of the scene's device, with the attributes
+ * of the hit, and an any-hit (occlusion) query.  Rays are read from and results written to device memory, the work is enqueued on the
+ * caller's stream and the calls return without synchronising the device: the caller's data must be ready in stream order, results are
+ * ready in stream order.  Nothing is written beyond element n of any output.  Staging lives in buffers the scene owns, which only ever
+ * grow: a call allocates only when it stages more rays than any call before it (mcpt_query_info::grew); rays are processed in chunks of
+ * at most MCPT_QUERY_CHUNK rays (environment, read at scene creation; default 2^20, at least 64).
+ *
+ * mcpt_query_closest, tmax == NULL: t and prim of every ray are bit for bit what mcpt_intersect gives on the same scene for the same ray.
+ * The occlusion rule: with t_i that distance and eps = (double)1e-4f (the render loop's EPSILON), ray i is occluded iff
+ * t_i - (double)tmax[i] <= -eps, the occluder rule of the render loop's shadow rays with the light distance tmax.  So tmax = +inf asks
+ * "is anything hit", and a NaN or a non-positive tmax is never occluded.
+ * mcpt_query_closest with tmax: a ray reports its closest hit iff the rule holds for it, a miss otherwise (the finished closest hit is
+ * filtered, so prim[i] >= 0 exactly where mcpt_query_occluded gives 1 for the same tmax).
+ * mcpt_query_occluded: occluded[i] = 1 or 0 by the rule; the walk stops at the first primitive that proves occlusion.
+ *
+ * Both see the scene as it is now (after mcpt_scene_update / _deform / _set_visibility / _add_objects: as a freshly created scene of the
+ * edited description; hidden objects are not hit).  The scene records one event on the caller's stream behind each query; every call
+ * that swaps or frees geometry arrays or the staging buffers (the four above, mcpt_scene_set_materials when it rebuilds, and
+ * mcpt_scene_destroy) waits for it on the host first, and a query on another stream waits for it on the device before it reuses the
+ * staging buffers.  So an edit issued right after an enqueued query leaves that query's results correct.
+ *
+ * MCPT_ERR_ARG, before any device work: a null scene; n < 0 or n > 2^31 - 1; n > 0 with a null rays, origins or dirs; a null occluded or
+ * tmax for mcpt_query_occluded; every hit pointer null; a pointer that hipPointerGetAttributes does not place on the scene's device.
+ * n == 0 is a valid no-op.  A group's replicas are queried through mcpt_group_scene. */
+typedef struct {            /* all pointers: memory of the scene's device, C-contiguous float32 */
+    const float *origins;   /* n*3 */
+    const float *dirs;      /* n*3, need not be normalised: t is in units of |d|, as in mcpt_intersect */
+    const float *tmax;      /* n; closest: nullable (no limit); occluded: required */
+} mcpt_ray_buffers;
+
+typedef struct {            /* every member nullable; at least one non-null */
+    double  *t;             /* n   the double mcpt_intersect returns, DBL_MAX on a miss */
+    int32_t *prim;          /* n   global primitive id, -1 on a miss */
+    int32_t *object;        /* n   index of the object in the scene's current object order (after mcpt_scene_add_objects: the extended order), -1 on a miss */
+    float   *uv;            /* n*2 triangles: the barycentrics (u, v) of the test that recorded the hit, each rounded once to float; spheres and misses: 0, 0 */
+    float   *normal;        /* n*3 the geometric normal of the scene's record (triangles), (p - c) normalised (spheres); misses: 0, 0, 0.  Never flipped towards the ray. */
+    float   *point;         /* n*3 triangles: v0 + u e1 + v e2 on the live record (the rule of the motion pass); spheres: o + d (float)t; misses: 0, 0, 0 */
+} mcpt_hit_buffers;
+
+typedef struct {
+    int32_t launches;       /* chunks the call was processed in */
+    int32_t grew;           /* 1: the call had to allocate */
+    int64_t staged_bytes;   /* device memory the scene holds for queries after the call */
+    int32_t reserved[4];
+} mcpt_query_info;
+
+int mcpt_query_closest(mcpt_scene *scene, int64_t n, const mcpt_ray_buffers *rays, const mcpt_hit_buffers *hits, void *hip_stream,
+                       mcpt_query_info *info /* nullable */);
+int mcpt_query_occluded(mcpt_scene *scene, int64_t n, const mcpt_ray_buffers *rays, uint8_t *occluded /* n, device */, void *hip_stream,
+                        mcpt_query_info *info /* nullable */);
+
 /* Tone map of Renderer.cpp:95-103 on the GPU: rgba[4i + c] = (unsigned char) clamp(0, 255, 255 * pow(fb[3i + c], 0.45f)), alpha 255,
  * NaN -> 255 as the reference's std::min/std::max clamp gives.  std::pow is the library's own plain-IEEE pow (csrc/mcpt_fmath.h), within
  * an ulp of any libm's.  Optional: the float frame of mcpt_render is the boundary's product; callers may keep their own tone map. */
