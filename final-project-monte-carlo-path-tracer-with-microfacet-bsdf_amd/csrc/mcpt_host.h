@@ -9,7 +9,8 @@
 //                       it shares with
 //   mcpt_sequence.hip   mcpt_temporal_accumulate and mcpt_sequence_*: a frame loop whose history and buffers stay on the device
 //   mcpt_query.hip      ray queries on host memory, tone map and the debug entry points
-//   mcpt_rayquery.hip   mcpt_query_closest / mcpt_query_occluded: ray queries on device memory, with their kernels
+//   mcpt_rayquery.hip   mcpt_query_closest / mcpt_query_occluded: ray queries on device memory, with their kernels; mcpt_query_radiance /
+//                       mcpt_sensor_rays: radiance at sensors in device memory (csrc/mcpt_sensor.h)
 //   mcpt_multi.hip      mcpt_group_*
 #pragma once
 #include <hip/hip_runtime.h>
@@ -182,6 +183,7 @@ struct SharedBufs {
     DevBuf<uint8_t> cull_flags, cull_temp;
     DevBuf<int4> cand_tmp, cand_list;  // per pixel: the few primitives its rays can hit (aligned with culled_list)
     DevBuf<int32_t> key_channel;
+    DevBuf<double> sensor_moments;  // mcpt_query_radiance with a variance: 6 doubles per sensor (sums of v and v*v per channel); grows to the largest call
     int pix_key[5] = {0, 0, 0, 0, 0};  // (W, H, tile, rank, nranks) of the pixel list currently in HBM
     uint32_t n_pix = 0;
 };
@@ -587,7 +589,17 @@ struct AccumPlan {
     double *moments;  // adaptive sampling: per-pixel sums of v and v*v (nullptr: the plain fold)
 };
 
-int run_wavefront(mcpt_scene *sc, PoolCtx &ctx, const RenderConst &C0, const CameraConst *cam, const std::vector<PassPlan> &plan,
+// Where the first rays of new samples come from (mode 0): the camera of a frame, or the sensors of mcpt_query_radiance.  Holds pointers:
+// what it is made from outlives the call it is passed to.  Neither (mode 1, mcpt_cast_rays): the caller has uploaded the rays.
+struct RaySource {
+    const CameraConst *cam = nullptr;
+    const SensorConst *sensors = nullptr;
+    RaySource() = default;
+    RaySource(const CameraConst &c) : cam(&c) {}
+    RaySource(const SensorConst &s) : sensors(&s) {}
+};
+
+int run_wavefront(mcpt_scene *sc, PoolCtx &ctx, const RenderConst &C0, const RaySource &src, const std::vector<PassPlan> &plan,
                   const AccumPlan *acc, hipStream_t st, Totals &tot);
 // After a failed run_wavefront the side streams may still hold kernels that use the workspace: wait for them before the
 // caller sees the error (and possibly frees buffers).  The error text of the failure is kept.
@@ -602,7 +614,7 @@ struct PixelSet {
 };
 int prepare_pixels(mcpt_scene *sc, const CameraConst &cc, const mcpt_params &p, int32_t spp, float spp_total, float *fb_dev, hipStream_t st,
                    PixelSet &ps);
-int render_list(mcpt_scene *sc, const CameraConst &cc, const mcpt_params &p, const uint32_t *pixel_list, const int4 *pixel_cand, uint32_t n_pix,
+int render_list(mcpt_scene *sc, const RaySource &src, const mcpt_params &p, const uint32_t *pixel_list, const int4 *pixel_cand, uint32_t n_pix,
                 int32_t sample_offset, int32_t spp, float spp_total, float *fb_dev, double *moments, hipStream_t st, Clock::time_point t0,
                 Totals &rt);
 

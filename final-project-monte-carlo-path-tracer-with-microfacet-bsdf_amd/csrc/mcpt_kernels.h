@@ -5,6 +5,7 @@
 #include <cstddef>
 
 #include "mcpt_device.h"
+#include "mcpt_sensor.h"
 
 namespace mcpt {
 
@@ -181,6 +182,14 @@ void launch_bookkeep(Counters *c, int cur_idx, bool from_host, uint32_t n_next, 
 // wave `next` (list index `next_idx`).
 void launch_primary(const DevScene &S, const CameraConst &cam, const RenderConst &C, Wave next, int next_idx, int parity,
                     uint32_t first_sample, uint32_t n_samples, const RetryList &rl, hipStream_t s);
+// The same for the samples of sensors (csrc/mcpt_sensor.h): position pl of the list is sensor pl, C.pixel_list and C.pixel_cand are null.
+void launch_sensor_primary(const DevScene &S, const SensorConst &sn, const RenderConst &C, Wave next, int next_idx, int parity,
+                           uint32_t first_sample, uint32_t n_samples, const RetryList &rl, hipStream_t s);
+// The first ray of (sensor[j], sample[j]) into entry j, j < n (mcpt_sensor_rays).
+void launch_sensor_rays(const SensorConst &sn, uint32_t seed, uint32_t n, const uint32_t *sensor, const uint32_t *sample, float4 *o, float4 *d,
+                        hipStream_t s);
+// variance[3i + c] = the variance of the mean of channel c of sensor i from the moments launch_accumulate summed over spp >= 2 samples.
+void launch_sensor_variance(uint32_t n_sensors, int32_t spp, const double *moments, float *variance, hipStream_t s);
 void launch_generate_explicit(const RenderConst &C, Wave next, int next_idx, uint32_t n, hipStream_t s);
 void launch_camera_rays(const CameraConst &cam, uint32_t seed, uint32_t n, const uint32_t *pixel, const uint32_t *sample,
                         float4 *o, float4 *d, hipStream_t s);

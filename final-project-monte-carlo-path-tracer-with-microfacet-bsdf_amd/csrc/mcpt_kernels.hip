@@ -1055,6 +1055,81 @@ __global__ __launch_bounds__(kBlock) void k_primary_retrace(DevScene S, CameraCo
 }
 
 // ------------------------------------------------------------------------------------------------
+// Sensors (mcpt_query_radiance): k_primary and k_primary_retrace with the camera replaced by the caller's sensors.  Position `pl` of the
+// list is sensor pl (no pixel list), so path_key gives the paths of its samples the key (seed, pl, sample, channel) by itself; a sensor
+// has no candidate list, every first ray walks the tree.  Everything behind the first ray is primary_sample as it stands.
+// ------------------------------------------------------------------------------------------------
+MCPT_DI void sensor_sample_ray(const SensorConst &sn, const RenderConst &C, int q, uint32_t s, f3 &pos, f3 &dir) {
+    uint32_t pl, ks;
+    split_sample(C, q, s, pl, ks);
+    sensor_ray(sn, C.seed, pl, (uint32_t)(q ? C.sample_offset[1] : C.sample_offset[0]) + ks, pos, dir);
+}
+
+template <int STK, bool RETRY, bool SMALL>
+__global__ __launch_bounds__(kBlock) void k_sensor_primary(DevScene S, SensorConst sn, RenderConst C, Wave next, int next_idx, int q,
+                                                           uint32_t first_sample, uint32_t n_samples, RetryList rl) {
+    __shared__ int32_t stk[STK][kBlock];
+    __shared__ BlockAllocShared sh;
+    if constexpr (SMALL) {
+        __shared__ SmallGeomLds small_geom;
+        stage_small_geom(S, small_geom);
+        __syncthreads();
+    }
+    const int tid = threadIdx.x;
+    const uint32_t j = blockIdx.x * kBlock + tid;
+    const bool valid = j < n_samples;
+    const uint32_t s = first_sample + j;
+    f3 pos = mk3(0, 0, 0), dir = mk3(0, 0, 1);
+    const TraceResult tr{DBL_MAX, -1, 0u, false, false};
+    if (valid) sensor_sample_ray(sn, C, q, s, pos, dir);  // (a lane past the end holds no sample: its index names no sensor)
+    primary_sample<true>(S, C, next, next_idx, q, s, valid, valid, pos, dir, tr, sh, rl,
+                         [&](const Ray &r) { return traverse<false, STK, RETRY, SMALL>(S, r, 0.f, stk, tid); });
+}
+
+__global__ __launch_bounds__(kBlock) void k_sensor_primary_retrace(DevScene S, SensorConst sn, RenderConst C, Wave next, int next_idx, int q, RetryList rl) {
+    __shared__ int32_t stk[1][kBlock];
+    __shared__ BlockAllocShared sh;
+    const uint32_t n = min(*rl.count, rl.cap);
+    for (uint32_t base = blockIdx.x * kBlock; base < n; base += gridDim.x * kBlock) {  // uniform trip count per workgroup
+        const uint32_t j = base + threadIdx.x;
+        const bool valid = j < n;
+        const uint32_t s = valid ? rl.items[j] : 0u;
+        f3 pos = mk3(0, 0, 0), dir = mk3(0, 0, 1);
+        const TraceResult tr{DBL_MAX, -1, 0u, false, false};
+        if (valid) sensor_sample_ray(sn, C, q, s, pos, dir);
+        primary_sample<false>(S, C, next, next_idx, q, s, valid, valid, pos, dir, tr, sh, rl,
+                              [&](const Ray &r) { return traverse_scratch<false>(S, r, 0.f, stk, threadIdx.x); });
+        __syncthreads();  // `sh` is reused by the next round
+    }
+    retry_finish(rl);
+}
+
+// mcpt_sensor_rays: the first ray of (sensor[j], sample[j]), one lane per pair.
+__global__ __launch_bounds__(kBlock) void k_sensor_rays(SensorConst sn, uint32_t seed, uint32_t n, const uint32_t *__restrict__ sensor,
+                                                        const uint32_t *__restrict__ sample, float4 *__restrict__ o, float4 *__restrict__ d) {
+    const uint32_t j = blockIdx.x * kBlock + threadIdx.x;
+    if (j >= n) return;
+    f3 pos, dir;
+    sensor_ray(sn, seed, sensor[j], sample[j], pos, dir);
+    o[j] = make_float4(pos.x, pos.y, pos.z, 0.f);
+    d[j] = make_float4(dir.x, dir.y, dir.z, 0.f);
+}
+
+// The variance of each channel's mean from the moments k_accumulate<true> summed (s1 = sum v, s2 = sum v*v, in double and in sample
+// order), one lane per (sensor, channel): max(s2/n - (s1/n)^2, 0) * n/(n-1) / n in double, rounded once to float.
+__global__ __launch_bounds__(kBlock) void k_sensor_variance(uint32_t n3, int32_t spp, const double *__restrict__ moments, float *__restrict__ variance) {
+    const uint32_t g = blockIdx.x * kBlock + threadIdx.x;
+    if (g >= n3) return;
+    const uint32_t i = g / 3u, c = g - 3u * i;
+    const double n = (double)spp;
+    const double s1 = moments[(size_t)i * 6 + c], s2 = moments[(size_t)i * 6 + 3 + c];
+    const double mean = s1 / n;
+    const double diff = s2 / n - mean * mean;
+    const double pop = diff < 0.0 ? 0.0 : diff;  // (a NaN stays one: a sensor whose radiance is NaN has no variance to report)
+    variance[g] = (float)(pop * n / (n - 1.0) / n);
+}
+
+// ------------------------------------------------------------------------------------------------
 // k_shade: Scene::castRay (Scene.cpp:85-184) turned inside out.
 //
 // The recursion  L_d = clamp(0,15,l_dir_d) + clamp(0,5, L_{d+1} * f_d)  is not multiplicative (per-level
@@ -1784,6 +1859,25 @@ void launch_primary(const DevScene &S, const CameraConst &cam, const RenderConst
     const dim3 g(blocks(n_samples)), b(kBlock);
     MCPT_STACK_DISPATCH(S.height, k_primary, hipLaunchKernelGGL(k_primary_retrace, dim3(kRetraceGrid), b, 0, s, S, cam, C, next, next_idx, parity, rl), g, b, 0, s, S,
                         cam, C, next, next_idx, parity, first_sample, n_samples, rl);
+}
+
+void launch_sensor_primary(const DevScene &S, const SensorConst &sn, const RenderConst &C, Wave next, int next_idx, int parity,
+                           uint32_t first_sample, uint32_t n_samples, const RetryList &rl, hipStream_t s) {
+    if (n_samples == 0) return;
+    const dim3 g(blocks(n_samples)), b(kBlock);
+    MCPT_STACK_DISPATCH(S.height, k_sensor_primary, hipLaunchKernelGGL(k_sensor_primary_retrace, dim3(kRetraceGrid), b, 0, s, S, sn, C, next, next_idx, parity, rl), g,
+                        b, 0, s, S, sn, C, next, next_idx, parity, first_sample, n_samples, rl);
+}
+
+void launch_sensor_rays(const SensorConst &sn, uint32_t seed, uint32_t n, const uint32_t *sensor, const uint32_t *sample, float4 *o, float4 *d,
+                        hipStream_t s) {
+    if (n == 0) return;
+    hipLaunchKernelGGL(k_sensor_rays, dim3(blocks(n)), dim3(kBlock), 0, s, sn, seed, n, sensor, sample, o, d);
+}
+
+void launch_sensor_variance(uint32_t n_sensors, int32_t spp, const double *moments, float *variance, hipStream_t s) {
+    if (n_sensors == 0) return;
+    hipLaunchKernelGGL(k_sensor_variance, dim3(blocks(n_sensors * 3u)), dim3(kBlock), 0, s, n_sensors * 3u, spp, moments, variance);
 }
 
 void launch_generate_explicit(const RenderConst &C, Wave next, int next_idx, uint32_t n, hipStream_t s) {

@@ -88,7 +88,7 @@ int mcpt_cast_rays(mcpt_scene *sc, const mcpt_params *pp, int64_t n, const float
         C.result[0] = C.result[1] = sh.result.p;
         Totals tot;
         const std::vector<PassPlan> plan{PassPlan{0u, m, 1, 0}};
-        const int rc = drained(run_wavefront(sc, ctx, C, nullptr, plan, nullptr, nullptr, tot));
+        const int rc = drained(run_wavefront(sc, ctx, C, RaySource{}, plan, nullptr, nullptr, tot));
         if (rc != MCPT_OK) return rc;
         if (base == 0) sc->last_cont_traced = sc->last_cont_shared = sc->last_pc_samples = sc->last_pc_rays = 0;  // (mcpt_scene_ray_counts: summed over the chunks)
         sc->last_cont_traced += tot.cont_traced;

@@ -13,9 +13,13 @@
 //                      retry-flavour launch that lost a stack entry, again with the scratch stack.
 // Small scenes: k_query_occluded's SMALL instantiation has no LDS prologue; it walks the global arrays (which exist for every scene)
 // with the 8-entry stack of the small flavour, the plain walk the checking build runs on those scenes too.
+//
+// Radiance at sensors in device memory (mcpt_query_radiance, mcpt_sensor_rays) is at the end of the file: the entry points alone; their
+// kernels sit beside k_primary in csrc/mcpt_kernels.hip, the first ray of a sensor's sample in csrc/mcpt_sensor.h.
 #include <cfloat>
 #include <cmath>
 
+#include "mcpt_frame.h"
 #include "mcpt_host.h"
 #include "mcpt_stack_dispatch.h"
 #include "mcpt_traverse.h"
@@ -298,6 +302,93 @@ int mcpt_query_occluded(mcpt_scene *sc, int64_t n, const mcpt_ray_buffers *rays,
     if (!occluded) return fail(MCPT_ERR_ARG, "mcpt_query_occluded: null occluded");
     if (!on_device(occluded, sc->device)) return fail(MCPT_ERR_ARG, "mcpt_query_occluded: occluded is not memory of the scene's device");
     return run_query(sc, n, *rays, nullptr, occluded, (hipStream_t)hip_stream, info);
+}
+
+// Radiance at sensors: a frame of n pixels whose first rays come from the caller's arrays (csrc/mcpt_sensor.h) instead of a camera.
+// render_list does the work -- workspace and pass sizing, regeneration, pipelined passes, the fold in sample order, the moments -- on the
+// scene's own buffers with the caller's `radiance` as the framebuffer and no pixel list.  It reads the geometry, which ray queries in
+// flight only read as well, and none of the staging buffers the ray-query event guards: there is nothing to settle first.
+int mcpt_query_radiance(mcpt_scene *sc, const mcpt_params *pp, int64_t n, const mcpt_sensor_buffers *sensors, const mcpt_sensor_outputs *out,
+                        void *hip_stream, mcpt_stats *stats) {
+    const auto bad = [](const char *what) { return fail(MCPT_ERR_ARG, std::string("mcpt_query_radiance: ") + what); };
+    if (!sc) return bad("null scene");
+    if (!pp || !sensors || !out) return bad("null params, sensors or out");
+    const mcpt_params &p = *pp;
+    if (n < 0 || n > 0x7fffffff / 3) return bad("n must be in 0 .. (2^31 - 1) / 3");
+    if (sensors->kind != MCPT_SENSOR_RAY && sensors->kind != MCPT_SENSOR_HEMISPHERE) return bad("unknown sensor kind");
+    if (sensors->reserved[0] || sensors->reserved[1] || sensors->reserved[2]) return bad("reserved words must be 0");
+    if (p.nranks > 1 || p.rank != 0) return bad("nranks must be 1 and rank 0 (sensors are not partitioned)");
+    if (p.spp <= 0 || p.n_dir_sample <= 0 || !(p.rr_rate > 0.f)) return bad("spp/n_dir_sample/rr_rate must be positive");
+    if (out->variance && (p.spp < 2 || p.accumulate != 0 || p.spp_total != 0 || p.sample_offset != 0))
+        return bad("variance needs spp >= 2 and accumulate, spp_total and sample_offset 0");
+    if (n == 0) {
+        if (stats) std::memset(stats, 0, sizeof *stats);
+        return MCPT_OK;
+    }
+    if (!sensors->origins || !sensors->dirs || !out->radiance) return bad("null origins, dirs or radiance");
+    if (!on_device(sensors->origins, sc->device) || !on_device(sensors->dirs, sc->device) || !on_device(out->radiance, sc->device) ||
+        (out->variance && !on_device(out->variance, sc->device)))
+        return bad("origins, dirs, radiance and variance must be memory of the scene's device");
+    HIP_TRY(hipSetDevice(sc->device));
+    (void)hipGetLastError();  // an earlier, already reported failure of this thread must not be taken for one of this call
+    const Clock::time_point t0 = Clock::now();
+    hipStream_t st = (hipStream_t)hip_stream;
+    const uint32_t ns = (uint32_t)n;
+    double *moments = nullptr;
+    if (out->variance) {
+        HIP_TRY(sc->shared.sensor_moments.alloc((size_t)ns * 6));
+        moments = sc->shared.sensor_moments.p;
+        HIP_TRY(hipMemsetAsync(moments, 0, (size_t)ns * 6 * sizeof(double), st));
+    }
+    if (!p.accumulate) HIP_TRY(hipMemsetAsync(out->radiance, 0, (size_t)ns * 3 * sizeof(float), st));
+    const SensorConst sn{sensors->origins, sensors->dirs, sensors->kind};
+    const float spp_total = (float)(p.spp_total > 0 ? p.spp_total : p.spp);
+    Totals rt;
+    const int rc = render_list(sc, sn, p, nullptr, nullptr, ns, p.sample_offset, p.spp, spp_total, out->radiance, moments, st, t0, rt);
+    if (rc != MCPT_OK) return rc;
+    if (out->variance) {
+        launch_sensor_variance(ns, p.spp, moments, out->variance, st);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    const uint64_t samples = (uint64_t)ns * (uint64_t)p.spp;
+    if (stats) fill_stats(stats, samples, samples, p.n_dir_sample, rt, t0);
+    sc->last_cont_traced = rt.cont_traced;  // (mcpt_scene_ray_counts)
+    sc->last_cont_shared = rt.cont_shared;
+    sc->last_pc_samples = rt.pc_samples;  // (mcpt_scene_primary_conductor_counts)
+    sc->last_pc_rays = rt.pc_rays;
+    if (rt.overflow) return fail(MCPT_ERR_OVERFLOW, "some paths outran the clamp stack (raise params.max_depth)");
+    return MCPT_OK;
+}
+
+int mcpt_sensor_rays(mcpt_scene *sc, int32_t kind, uint32_t seed, int64_t n, const float *origins, const float *dirs, const uint32_t *sensor,
+                     const uint32_t *sample, float *origins_out, float *dirs_out) {
+    if (!sc || n < 0 || (n > 0 && (!origins || !dirs || !sensor || !sample || !origins_out || !dirs_out))) return fail(MCPT_ERR_ARG, "mcpt_sensor_rays: bad argument");
+    if (kind != MCPT_SENSOR_RAY && kind != MCPT_SENSOR_HEMISPHERE) return fail(MCPT_ERR_ARG, "mcpt_sensor_rays: unknown sensor kind");
+    if (n == 0) return MCPT_OK;
+    if (n > 0x7fffffff) return fail(MCPT_ERR_ARG, "mcpt_sensor_rays: too many rays for one call");
+    size_t m = 0;  // the sensors the pairs name: rows 0 .. max(sensor) of origins and dirs
+    for (int64_t j = 0; j < n; ++j) m = std::max<size_t>(m, (size_t)sensor[j] + 1);
+    HIP_TRY(hipSetDevice(sc->device));
+    DevBuf<float> dPo, dPd;
+    DevBuf<uint32_t> dI, dS;
+    DevBuf<float4> dO, dD;
+    HIP_TRY(dO.alloc(n));
+    HIP_TRY(dD.alloc(n));
+    HIP_TRY(upload(dPo, origins, m * 3));
+    HIP_TRY(upload(dPd, dirs, m * 3));
+    HIP_TRY(upload(dI, sensor, n));
+    HIP_TRY(upload(dS, sample, n));
+    launch_sensor_rays(SensorConst{dPo.p, dPd.p, kind}, seed, (uint32_t)n, dI.p, dS.p, dO.p, dD.p, nullptr);
+    HIP_TRY(hipGetLastError());
+    std::vector<float4> o(n), d(n);
+    HIP_TRY(download(o.data(), dO, n));
+    HIP_TRY(download(d.data(), dD, n));
+    for (int64_t j = 0; j < n; ++j) {
+        origins_out[3 * j] = o[j].x, origins_out[3 * j + 1] = o[j].y, origins_out[3 * j + 2] = o[j].z;
+        dirs_out[3 * j] = d[j].x, dirs_out[3 * j + 1] = d[j].y, dirs_out[3 * j + 2] = d[j].z;
+    }
+    return MCPT_OK;
 }
 
 }  // extern "C"

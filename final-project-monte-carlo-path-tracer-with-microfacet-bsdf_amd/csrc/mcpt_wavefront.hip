@@ -116,7 +116,7 @@ static void build_pixel_list(int W, int H, int tile, int rank, int nranks, std::
 // Up to two passes are in flight: as soon as a pass has no samples left to issue, the next one starts filling the pool,
 // so the drain tail of a pass overlaps useful work.  A pass is complete when its live-path counter is 0 (and all its
 // samples were issued at least one iteration ago); passes are accumulated into the framebuffer strictly in order.
-int run_wavefront(mcpt_scene *sc, PoolCtx &ctx, const RenderConst &C0, const CameraConst *cam, const std::vector<PassPlan> &plan,
+int run_wavefront(mcpt_scene *sc, PoolCtx &ctx, const RenderConst &C0, const RaySource &src, const std::vector<PassPlan> &plan,
                   const AccumPlan *acc, hipStream_t st, Totals &tot) {
     Workspace &w = ctx.ws;
     Timer &T = ctx.timer;
@@ -178,7 +178,10 @@ int run_wavefront(mcpt_scene *sc, PoolCtx &ctx, const RenderConst &C0, const Cam
             if (issued == 0) set_pass_consts(issue_pass);
             const uint32_t g = std::min<uint32_t>(room, plan[issue_pass].n_work - issued);
             if (g > 0) {
-                T.timed(K_GENERATE, s_prim, [&] { launch_primary(sc->view, *cam, C, nx, nxt, issue_pass & 1, plan[issue_pass].first_work + issued, g, w.retry.list(2), s_prim); });
+                T.timed(K_GENERATE, s_prim, [&] {
+                    if (src.sensors) launch_sensor_primary(sc->view, *src.sensors, C, nx, nxt, issue_pass & 1, plan[issue_pass].first_work + issued, g, w.retry.list(2), s_prim);
+                    else launch_primary(sc->view, *src.cam, C, nx, nxt, issue_pass & 1, plan[issue_pass].first_work + issued, g, w.retry.list(2), s_prim);
+                });
                 tot.closest += g;
             }
             issued += g;
@@ -438,9 +441,10 @@ int prepare_pixels(mcpt_scene *sc, const CameraConst &cc, const mcpt_params &p, 
 }
 
 // Renders the n_pix listed pixels (with their candidate entries, or none) for samples [sample_offset, sample_offset + spp), each added as
-// value / spp_total into fb_dev in sample order (moments != nullptr: the per-pixel sums of v and v*v as well).  Blocks until done.
+// value / spp_total into fb_dev in sample order.  With sensors as the ray source: the n_pix sensors, pixel_list and pixel_cand null, fb_dev
+// the caller's n_pix * 3 floats (moments != nullptr: the per-pixel sums of v and v*v as well).  Blocks until done.
 // p supplies everything else (rr_rate, n_dir_sample, shadows, seed, spp_per_pass, pool_paths, max_depth).
-int render_list(mcpt_scene *sc, const CameraConst &cc, const mcpt_params &p, const uint32_t *pixel_list, const int4 *pixel_cand, uint32_t n_pix,
+int render_list(mcpt_scene *sc, const RaySource &src, const mcpt_params &p, const uint32_t *pixel_list, const int4 *pixel_cand, uint32_t n_pix,
                 int32_t sample_offset, int32_t spp, float spp_total, float *fb_dev, double *moments, hipStream_t st, Clock::time_point t0,
                 Totals &rt) {
     SharedBufs &sh = sc->shared;
@@ -531,7 +535,7 @@ int render_list(mcpt_scene *sc, const CameraConst &cc, const mcpt_params &p, con
             plan.push_back(PassPlan{0u, n_pix * (uint32_t)s_now, s_now, sample_offset + k0});
         }
         AccumPlan acc{fb_dev, spp_total, n_pix, pixel_list, {C.result[0], C.result[1]}, moments};
-        const int rc = drained(run_wavefront(sc, sc->pools[0], C, &cc, plan, &acc, st, tot[0]));
+        const int rc = drained(run_wavefront(sc, sc->pools[0], C, src, plan, &acc, st, tot[0]));
         if (rc != MCPT_OK) return rc;
     } else {
         for (int k0 = 0; k0 < spp; k0 += s_pass) {
@@ -552,10 +556,10 @@ int render_list(mcpt_scene *sc, const CameraConst &cc, const mcpt_params &p, con
                     c1.err = "hipSetDevice failed in the pool thread";
                     return;
                 }
-                c1.rc = run_wavefront(sc, c1, C, &cc, plan1, nullptr, c1.main, tot[1]);
+                c1.rc = run_wavefront(sc, c1, C, src, plan1, nullptr, c1.main, tot[1]);
                 if (c1.rc != MCPT_OK) c1.err = g_err;
             });
-            const int rc0 = run_wavefront(sc, sc->pools[0], C, &cc, plan0, nullptr, st, tot[0]);
+            const int rc0 = run_wavefront(sc, sc->pools[0], C, src, plan0, nullptr, st, tot[0]);
             worker.join();  // run_wavefront ends with a stream synchronise: both halves are complete here
             if (rc0 != MCPT_OK) return drained(rc0);
             if (c1.rc != MCPT_OK) return drained(fail(c1.rc, c1.err));

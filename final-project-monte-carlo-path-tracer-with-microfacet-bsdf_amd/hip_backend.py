@@ -37,7 +37,7 @@ EXPORTS = ["mcpt_scene_create", "mcpt_scene_destroy", "mcpt_render", "mcpt_rende
            "mcpt_centre_rays", "mcpt_render_aovs_features", "mcpt_render_motion_features", "mcpt_sequence_create_features",
            "mcpt_denoise_feedback", "mcpt_sequence_create_feedback", "mcpt_sequence_history",
            "mcpt_scene_ray_counts", "mcpt_scene_primary_conductor_counts",
-           "mcpt_query_closest", "mcpt_query_occluded",
+           "mcpt_query_closest", "mcpt_query_occluded", "mcpt_query_radiance", "mcpt_sensor_rays",
            "mcpt_group_create", "mcpt_group_render", "mcpt_group_size", "mcpt_group_get_info", "mcpt_group_scene", "mcpt_group_destroy", "mcpt_group_last_error",
            "mcpt_last_error", "mcpt_version"]
 
@@ -388,6 +388,23 @@ class QueryInfo(C.Structure):
         return {"launches": int(self.launches), "grew": int(self.grew), "staged_bytes": int(self.staged_bytes)}
 
 
+class SensorBuffers(C.Structure):
+    _fields_ = [("origins", C.c_void_p), ("dirs", C.c_void_p), ("kind", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+class SensorOutputs(C.Structure):
+    _fields_ = [("radiance", C.c_void_p), ("variance", C.c_void_p)]
+
+
+SENSOR_KINDS = {"ray": 0, "hemisphere": 1}  # MCPT_SENSOR_*
+
+
+def _sensor_kind(who, kind):
+    if not isinstance(kind, str) or kind not in SENSOR_KINDS:
+        raise ValueError("%s: kind is one of %s, not %r" % (who, tuple(SENSOR_KINDS), kind))
+    return SENSOR_KINDS[kind]
+
+
 # The outputs of HipScene.query_closest: name -> (element type of __cuda_array_interface__, its name, values per ray, torch dtype name)
 QUERY_OUTPUTS = {"t": (("<f8", "=f8"), "float64", 1, "float64"), "prim": (("<i4", "=i4"), "int32", 1, "int32"),
                  "object": (("<i4", "=i4"), "int32", 1, "int32"), "uv": (("<f4", "=f4", "|f4"), "float32", 2, "float32"),
@@ -609,6 +626,10 @@ def lib(path=None):
         L.mcpt_query_closest.argtypes = [C.c_void_p, C.c_int64, C.POINTER(RayBuffers), C.POINTER(HitBuffers), C.c_void_p, C.POINTER(QueryInfo)]
         L.mcpt_query_occluded.restype = C.c_int
         L.mcpt_query_occluded.argtypes = [C.c_void_p, C.c_int64, C.POINTER(RayBuffers), C.c_void_p, C.c_void_p, C.POINTER(QueryInfo)]
+        L.mcpt_query_radiance.restype = C.c_int
+        L.mcpt_query_radiance.argtypes = [C.c_void_p, C.POINTER(Params), C.c_int64, C.POINTER(SensorBuffers), C.POINTER(SensorOutputs), C.c_void_p, C.POINTER(Stats)]
+        L.mcpt_sensor_rays.restype = C.c_int
+        L.mcpt_sensor_rays.argtypes = [C.c_void_p, C.c_int32, C.c_uint32, C.c_int64] + [C.c_void_p] * 6
         L.mcpt_cast_rays.restype = C.c_int
         L.mcpt_cast_rays.argtypes = [C.c_void_p, C.POINTER(Params), C.c_int64] + [C.c_void_p] * 6
         L.mcpt_camera_rays.restype = C.c_int
@@ -1446,6 +1467,54 @@ class HipScene:
         info = QueryInfo()
         _check(self.L.mcpt_query_occluded(self.h, n, C.byref(rays), C.c_void_p(p or 0), C.c_void_p(int(stream or 0)), C.byref(info)), L=self.L)
         return out, info.as_dict()
+
+    def query_radiance(self, origins, dirs, kind="ray", variance=False, out=None, stream=None, **params):
+        """mcpt_query_radiance: path-traced radiance at sensors that sit in the memory of the scene's device -> (radiance (n, 3), variance
+        (n, 3) or None, Stats).  kind "ray": origins and dirs are rays, used as given; "hemisphere": surface points and unit normals, the
+        result is the cosine-weighted mean of the incoming radiance (E / pi).  Sensor i is keyed like pixel i of a frame: the result is
+        the fold of cast_rays(.., pixel=i, sample=sample_offset + k, channel=c) over the spp samples, bit for bit.  variance=True (spp >= 2,
+        no progressive parameters): also the variance of each channel's mean.  Inputs, out and stream as in query_closest: out is a dict
+        with "radiance" (and "variance") float32 (n, 3) device buffers, or None when the inputs are torch tensors.  params: the keywords
+        of HipScene.params (spp, seed, sample_offset, spp_total, accumulate, spp_per_pass, pool_paths, ...).  The call blocks until the
+        outputs are written."""
+        who = "query_radiance"
+        k = _sensor_kind(who, kind)
+        n, rays = _query_rays(who, origins, dirs, None)
+        names = ("radiance", "variance") if variance else ("radiance",)
+        if out is None:
+            if not _is_torch(origins, dirs):
+                raise ValueError("%s: out is required unless the sensors are torch tensors" % who)
+            import torch
+            out = {w: torch.empty((n, 3), dtype=torch.float32, device=origins.device) for w in names}
+            if stream is None:
+                stream = torch.cuda.current_stream(origins.device).cuda_stream
+        ptrs = []
+        for w in names:
+            if w not in out:
+                raise ValueError("%s: out has no buffer for %r" % (who, w))
+            ptrs.append(_query_output(who, w, out[w], n, ("<f4", "=f4", "|f4"), "float32", 3) or None)
+        sensors = SensorBuffers(rays.origins, rays.dirs, k, (C.c_int32 * 3)(0, 0, 0))
+        outs = SensorOutputs(ptrs[0], ptrs[1] if variance else None)
+        p = self.params(**params)
+        st = Stats()
+        _check(self.L.mcpt_query_radiance(self.h, C.byref(p), n, C.byref(sensors), C.byref(outs), C.c_void_p(int(stream or 0)), C.byref(st)), L=self.L)
+        return out["radiance"], (out["variance"] if variance else None), st
+
+    def sensor_rays(self, kind, origins, dirs, sensor, sample, seed=1):
+        """mcpt_sensor_rays: the first ray of (sensor[j], sample[j]) for sensors given on the host -> (origins[n,3], dirs[n,3]) float32.
+        origins, dirs: a row per sensor; sample is absolute (sample_offset + k)."""
+        k = _sensor_kind("sensor_rays", kind)
+        po = np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3)
+        pd = np.ascontiguousarray(dirs, dtype=np.float32).reshape(-1, 3)
+        si = np.ascontiguousarray(sensor, dtype=np.uint32).reshape(-1)
+        sm = np.ascontiguousarray(sample, dtype=np.uint32).reshape(-1)
+        n = len(si)
+        if len(sm) != n or len(po) != len(pd) or (n and int(si.max()) >= len(po)):
+            raise ValueError("sensor_rays: sensor and sample have one length, and every sensor named has a row in origins and dirs")
+        o = np.zeros((n, 3), dtype=np.float32)
+        d = np.zeros((n, 3), dtype=np.float32)
+        _check(self.L.mcpt_sensor_rays(self.h, k, int(seed), n, _ptr(po), _ptr(pd), _ptr(si), _ptr(sm), _ptr(o), _ptr(d)), L=self.L)
+        return o, d
 
     def shadow_visible(self, origins, dirs, dist, found=None, shard=None, list=0):
         """mcpt_debug_shadow: the render loop's shadow query (k_trace_shadow, its retrace included) for rays of the caller's -> bool [n]:

@@ -1174,6 +1174,59 @@ int mcpt_query_closest(mcpt_scene *scene, int64_t n, const mcpt_ray_buffers *ray
 int mcpt_query_occluded(mcpt_scene *scene, int64_t n, const mcpt_ray_buffers *rays, uint8_t *occluded /* n, device */, void *hip_stream,
                         mcpt_query_info *info /* nullable */);
 
+/* ---- Radiance at sensors: the radiometric companion of the ray queries.  How much light arrives along a ray, or at a surface point, for
+ * sensors that already sit in the memory of the scene's device: light probes, lightmap and irradiance baking, radiance caches,
+ * path-traced targets for rays of a training loop.  A set of n sensors is rendered as a frame whose pixels are the sensors.
+ *
+ * Let ray(i, k) be the first ray of sensor i, sample k, and v(i, k, c) what mcpt_cast_rays returns on the same scene for that ray with
+ * pixel = i, sample = params.sample_offset + k, channel = c and the same seed, rr_rate, n_dir_sample, enable_shadow and max_depth.  Then
+ *   radiance[3i + c] = the float fold  acc = (accumulate ? radiance[3i + c] : 0); for k in 0 .. spp-1: acc += v(i, k, c) / spp_total,
+ *                      spp_total = params.spp_total ? params.spp_total : params.spp   (the arithmetic of a pixel of mcpt_render), bit for bit;
+ *   variance[3i + c] = max(s2/n - (s1/n)^2, 0) * n/(n-1) / n  with n = spp, s1 = sum v, s2 = sum v*v summed in double in sample order,
+ *                      evaluated in double and rounded once to float: the variance of the channel's mean.
+ * A non-null variance needs spp >= 2 and accumulate == spp_total == sample_offset == 0.  Progressive calls (sample_offset, spp_total,
+ * accumulate) compose as they do for mcpt_render.
+ *
+ * Sensor kinds:
+ *   MCPT_SENSOR_RAY         ray(i, k) = (origins[i], dirs[i]) for every k; the direction is used as given, exactly as mcpt_cast_rays uses
+ *                           it.  No random numbers are spent on the ray.
+ *   MCPT_SENSOR_HEMISPHERE  origins[i] is a surface point p, dirs[i] its unit normal n.  With u the four uniforms of the Philox block
+ *                           (seed, i, sample_offset + k, stream 4) -- the channel paths use streams 0..2, the camera 3 --
+ *                           r = sqrtf(u[0]), phi = 2 pi u[1], local = (r cos phi, r sin phi, sqrtf(1 - u[0])), the direction is
+ *                           normalized(toWorld(local, n)) (Material.hpp:95-106) and the origin p + n * 1e-4f (Scene.cpp:114).  The
+ *                           result is the cosine-weighted mean of the incoming radiance, E / pi: multiplied by an albedo it is the
+ *                           Lambertian exitant radiance, what a lightmap stores.
+ * mcpt_sensor_rays returns ray(sensor[j], sample[j]) for sensors given on the host (host pointers, like mcpt_camera_rays; `sample` is
+ * absolute; origins and dirs have a row for every sensor the pairs name); for kind RAY these are the inputs of the named sensors.
+ *
+ * mcpt_query_radiance blocks like mcpt_render_device: the work is issued on hip_stream (the caller's data must be ready in stream order)
+ * and the call returns when the outputs are written; sensors and outputs never leave the device.  The wavefront workspace and the
+ * result buffers are the scene's own, sized as for a frame of n pixels; params.spp_per_pass and params.pool_paths are honoured.  stats
+ * is filled as for a frame of n pixels (samples = n * spp); mcpt_scene_ray_counts and mcpt_scene_primary_conductor_counts describe the
+ * call afterwards.  MCPT_ERR_OVERFLOW is returned as by mcpt_render, with the outputs written.  The call sees the scene as it is now.
+ * Non-finite or all-zero inputs are not checked: such a sensor behaves as mcpt_cast_rays does for the same ray.  The reference's
+ * per-level clamps bias the radiance of a sensor exactly as they bias a pixel.
+ *
+ * MCPT_ERR_ARG, before any device work: a null scene, params, sensors or out; n < 0 or n > (2^31 - 1) / 3; an unknown kind or a non-zero
+ * reserved word; nranks > 1 or a non-zero rank; spp <= 0, n_dir_sample <= 0 or rr_rate not positive; the variance conditions above; with
+ * n > 0 a null origins, dirs or radiance, or a pointer that hipPointerGetAttributes does not place on the scene's device.  n == 0 is a
+ * valid no-op.  There is no mcpt_group_* form: mcpt_group_scene hands out the replicas, each of which can be asked. */
+enum { MCPT_SENSOR_RAY = 0, MCPT_SENSOR_HEMISPHERE = 1 };
+typedef struct {            /* device memory of the scene's device, float32, C-contiguous */
+    const float *origins;   /* n*3  RAY: ray origin.        HEMISPHERE: surface point p */
+    const float *dirs;      /* n*3  RAY: direction, used as given, exactly as mcpt_cast_rays uses it.  HEMISPHERE: unit normal */
+    int32_t kind;           /* MCPT_SENSOR_* */
+    int32_t reserved[3];    /* must be 0 */
+} mcpt_sensor_buffers;      /* 32 bytes */
+typedef struct {            /* device memory */
+    float *radiance;        /* n*3, required */
+    float *variance;        /* n*3, nullable: variance of each channel's mean */
+} mcpt_sensor_outputs;      /* 16 bytes */
+int mcpt_query_radiance(mcpt_scene *scene, const mcpt_params *params, int64_t n, const mcpt_sensor_buffers *sensors,
+                        const mcpt_sensor_outputs *out, void *hip_stream, mcpt_stats *stats /* nullable */);
+int mcpt_sensor_rays(mcpt_scene *scene, int32_t kind, uint32_t seed, int64_t n, const float *origins, const float *dirs,
+                     const uint32_t *sensor, const uint32_t *sample, float *origins_out, float *dirs_out);
+
 /* Tone map of Renderer.cpp:95-103 on the GPU: rgba[4i + c] = (unsigned char) clamp(0, 255, 255 * pow(fb[3i + c], 0.45f)), alpha 255,
  * NaN -> 255 as the reference's std::min/std::max clamp gives.  std::pow is the library's own plain-IEEE pow (csrc/mcpt_fmath.h), within
  * an ulp of any libm's.  Optional: the float frame of mcpt_render is the boundary's product; callers may keep their own tone map. */
