@@ -11,6 +11,8 @@
 //   mcpt_query.hip      ray queries on host memory, tone map and the debug entry points
 //   mcpt_rayquery.hip   mcpt_query_closest / mcpt_query_occluded: ray queries on device memory, with their kernels; mcpt_query_radiance /
 //                       mcpt_sensor_rays: radiance at sensors in device memory (csrc/mcpt_sensor.h)
+//   mcpt_lightmap.hip   mcpt_lightmap_texels / mcpt_lightmap_scatter / mcpt_bake_lightmap and their host forms, with their kernels
+//                       (csrc/mcpt_lightmap.h)
 //   mcpt_multi.hip      mcpt_group_*
 #pragma once
 #include <hip/hip_runtime.h>
@@ -202,6 +204,22 @@ struct QueryBufs {
     Event done;
     bool pending = false;            // `done` has been recorded and nobody has waited for it on the host since
     hipStream_t last_stream = nullptr;
+};
+
+// What the lightmap calls (csrc/mcpt_lightmap.hip) keep between calls.  Like QueryBufs the buffers only ever grow, and everything these
+// calls enqueue is followed by a record of QueryBufs::done, so whatever settles a ray query settles a lightmap call too.
+struct LightmapBufs {
+    DevBuf<unsigned long long> counts, scan;  // per triangle of the object (+ 1): tiles its chart touches, and their exclusive sum
+    DevBuf<int32_t> owner;                    // W*H: the lowest primitive id covering the texel, lm::kNoOwner for none
+    DevBuf<uint8_t> temp;                     // hipcub's scratch (scan and select)
+    DevBuf<int32_t> n_sel;                    // the select's count
+    DevBuf<float> plane;                      // W*H*3: the second plane of the dilation's ping-pong
+    DevBuf<uint8_t> cov[2];                   // W*H each: the second coverage plane, and the first when the caller passes none
+    // mcpt_bake_lightmap: the sensors and their results
+    DevBuf<int32_t> texel;                    // W*H
+    DevBuf<float> origins, normals, radiance, variance;  // n*3 each
+    int64_t last_items = 0;                   // of the last mcpt_lightmap_texels
+    bool grew = false;                        // a buffer above was (re)allocated since the flag was last cleared
 };
 
 // Environment knobs, read ONCE per scene in mcpt_scene_create: a render call never calls getenv.
@@ -474,6 +492,7 @@ struct mcpt_scene {
     mcpt::DevScene view{};
     mcpt::Event fork;
     mcpt::QueryBufs query;
+    mcpt::LightmapBufs lightmap;
     mcpt::SharedBufs shared;
     // A wavefront pool: its own path lists, queues, clamp stack, counters and streams.  With MCPT_POOLS=2 two pools
     // are driven by two host threads on disjoint halves of each pass, so that one pool's k_shade (and its host
@@ -509,6 +528,17 @@ inline hipError_t query_settle(mcpt_scene *sc, bool objects_changed = false) {
     const hipError_t e = hipEventSynchronize(sc->query.done);
     if (e == hipSuccess) sc->query.pending = false;
     return e;
+}
+
+// hipPointerGetAttributes places p in the memory of `device` (the pointer checks of the ray queries and the lightmap calls)
+inline bool on_device(const void *p, int device) {
+    hipPointerAttribute_t a;
+    std::memset(&a, 0, sizeof a);
+    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
+        (void)hipGetLastError();  // (an address the runtime does not know: not a sticky error)
+        return false;
+    }
+    return a.type == hipMemoryTypeDevice && a.device == device;
 }
 
 // ---- mcpt_upload.hip

@@ -175,17 +175,6 @@ void launch_query_occluded(const DevScene &S, uint32_t n, const float4 *ray_o, c
 
 namespace {
 
-// hipPointerGetAttributes places p in the memory of `device`
-bool on_device(const void *p, int device) {
-    hipPointerAttribute_t a;
-    std::memset(&a, 0, sizeof a);
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
-        (void)hipGetLastError();  // (an address the runtime does not know: not a sticky error)
-        return false;
-    }
-    return a.type == hipMemoryTypeDevice && a.device == device;
-}
-
 // The table of mesh triangle-range starts for the object lookup, in ascending order of the first triangle: m starts, then the m objects.
 void build_range_table(const SceneSource &S, std::vector<int32_t> &table) {
     std::vector<std::pair<int32_t, int32_t>> r;

@@ -38,6 +38,7 @@ EXPORTS = ["mcpt_scene_create", "mcpt_scene_destroy", "mcpt_render", "mcpt_rende
            "mcpt_denoise_feedback", "mcpt_sequence_create_feedback", "mcpt_sequence_history",
            "mcpt_scene_ray_counts", "mcpt_scene_primary_conductor_counts",
            "mcpt_query_closest", "mcpt_query_occluded", "mcpt_query_radiance", "mcpt_sensor_rays",
+           "mcpt_lightmap_texels", "mcpt_lightmap_scatter", "mcpt_bake_lightmap", "mcpt_lightmap_texels_host", "mcpt_lightmap_dilate_host",
            "mcpt_group_create", "mcpt_group_render", "mcpt_group_size", "mcpt_group_get_info", "mcpt_group_scene", "mcpt_group_destroy", "mcpt_group_last_error",
            "mcpt_last_error", "mcpt_version"]
 
@@ -439,6 +440,33 @@ def _query_output(who, name, v, n, typestrs, type_name, width):
     return b[0]
 
 
+class LightmapDesc(C.Structure):
+    _fields_ = [("object", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("flip_normals", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
+class LightmapTexelsOut(C.Structure):
+    _fields_ = [("texel", C.c_void_p), ("prim", C.c_void_p), ("bary", C.c_void_p), ("origins", C.c_void_p), ("normals", C.c_void_p)]
+
+
+class LightmapInfo(C.Structure):
+    _fields_ = [("n_texels", C.c_int64), ("items", C.c_int64), ("grew", C.c_int32), ("reserved0", C.c_int32), ("ms_texels", C.c_double),
+                ("ms_radiance", C.c_double), ("ms_scatter", C.c_double), ("reserved", C.c_int32 * 4)]
+
+    def as_dict(self):
+        return {"n_texels": int(self.n_texels), "items": int(self.items), "grew": int(self.grew), "ms_texels": float(self.ms_texels),
+                "ms_radiance": float(self.ms_radiance), "ms_scatter": float(self.ms_scatter)}
+
+
+# The outputs of HipScene.lightmap_texels: name -> (element types of __cuda_array_interface__, type name, values per texel, numpy dtype)
+LIGHTMAP_OUTPUTS = {"texel": (("<i4", "=i4"), "int32", 1, np.int32), "prim": (("<i4", "=i4"), "int32", 1, np.int32),
+                    "bary": (("<f4", "=f4", "|f4"), "float32", 2, np.float32), "origins": (("<f4", "=f4", "|f4"), "float32", 3, np.float32),
+                    "normals": (("<f4", "=f4", "|f4"), "float32", 3, np.float32)}
+
+
+def _lightmap_desc(object, width, height, flip_normals=False):
+    return LightmapDesc(int(object), int(width), int(height), 1 if flip_normals else 0, (C.c_int32 * 4)(0, 0, 0, 0))
+
+
 def _is_torch(*vs):
     return all(hasattr(v, "data_ptr") and getattr(v, "is_cuda", False) for v in vs)
 
@@ -630,6 +658,17 @@ def lib(path=None):
         L.mcpt_query_radiance.argtypes = [C.c_void_p, C.POINTER(Params), C.c_int64, C.POINTER(SensorBuffers), C.POINTER(SensorOutputs), C.c_void_p, C.POINTER(Stats)]
         L.mcpt_sensor_rays.restype = C.c_int
         L.mcpt_sensor_rays.argtypes = [C.c_void_p, C.c_int32, C.c_uint32, C.c_int64] + [C.c_void_p] * 6
+        L.mcpt_lightmap_texels.restype = C.c_int
+        L.mcpt_lightmap_texels.argtypes = [C.c_void_p, C.POINTER(LightmapDesc), C.POINTER(LightmapTexelsOut), C.POINTER(C.c_int64), C.c_void_p]
+        L.mcpt_lightmap_scatter.restype = C.c_int
+        L.mcpt_lightmap_scatter.argtypes = [C.c_void_p, C.POINTER(LightmapDesc), C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.mcpt_bake_lightmap.restype = C.c_int
+        L.mcpt_bake_lightmap.argtypes = [C.c_void_p, C.POINTER(LightmapDesc), C.POINTER(Params), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.POINTER(LightmapInfo), C.POINTER(Stats)]
+        L.mcpt_lightmap_texels_host.restype = C.c_int
+        L.mcpt_lightmap_texels_host.argtypes = [C.POINTER(SceneDesc), C.POINTER(LightmapDesc)] + [C.c_void_p] * 5 + [C.POINTER(C.c_int64)]
+        L.mcpt_lightmap_dilate_host.restype = C.c_int
+        L.mcpt_lightmap_dilate_host.argtypes = [C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
         L.mcpt_cast_rays.restype = C.c_int
         L.mcpt_cast_rays.argtypes = [C.c_void_p, C.POINTER(Params), C.c_int64] + [C.c_void_p] * 6
         L.mcpt_camera_rays.restype = C.c_int
@@ -797,6 +836,36 @@ def extend_scene(sd, objects, triangles, materials=None):
     return dataclasses.replace(sd, objects=obj, triangles=tri, materials=mat)
 
 
+def lightmap_texels(sd, object, width, height, flip_normals=False):
+    """mcpt_lightmap_texels_host (host only): the texel sensors of one mesh object of a description under the rule of include/mcpt.h ->
+    dict of numpy arrays texel (n,), prim (n,), bary (n, 2), origins (n, 3), normals (n, 3), in ascending texel order."""
+    keep = []
+    d = _make_desc(sd, keep)
+    ld = _lightmap_desc(object, width, height, flip_normals)
+    cap = max(int(width), 0) * max(int(height), 0)
+    if cap > (2 ** 31 - 1) // 3:
+        cap = 0  # (the library refuses the size before it writes anything)
+    out = {w: np.zeros((cap,) if k == 1 else (cap, k), dt) for w, (_, _, k, dt) in LIGHTMAP_OUTPUTS.items()}
+    n = C.c_int64(0)
+    _check(lib().mcpt_lightmap_texels_host(C.byref(d), C.byref(ld), *[_ptr(out[w]) for w in LIGHTMAP_OUTPUTS], C.byref(n)))
+    return {w: out[w][:n.value].copy() for w in LIGHTMAP_OUTPUTS}
+
+
+def lightmap_dilate(width, height, texel, values, dilate):
+    """mcpt_lightmap_dilate_host (host only): scatter `values` (n, 3) to the listed texels of a zero map and run `dilate` rounds of the
+    dilation of include/mcpt.h -> (image (height, width, 3) float32, coverage (height, width) uint8: 0 empty, 1 scattered, 2 dilated)."""
+    tx = np.ascontiguousarray(texel, dtype=np.int32).reshape(-1)
+    v = np.ascontiguousarray(values, dtype=np.float32).reshape(-1, 3)
+    if len(v) != len(tx):
+        raise ValueError("lightmap_dilate: one value row per texel")
+    W, H = int(width), int(height)
+    big = W < 1 or H < 1 or W * H > (2 ** 31 - 1) // 3
+    image = np.zeros((1, 1, 3) if big else (H, W, 3), np.float32)
+    cov = np.zeros((1, 1) if big else (H, W), np.uint8)
+    _check(lib().mcpt_lightmap_dilate_host(W, H, len(tx), _ptr(tx), _ptr(v), int(dilate), _ptr(image), _ptr(cov)))
+    return image, cov
+
+
 def cull_bound(camera, root_min, root_max, library=None):
     """mcpt_cull_bound (host only): the sky cull's bound for a camera (scenes.CAM_DTYPE) over a root box, as a dict of mcpt_cull_info."""
     cam = np.ascontiguousarray(camera)
@@ -835,6 +904,7 @@ class HipScene:
         """library: path of an alternative build of the same ABI (the checking build); None = the product library.
         builder: None (mcpt_scene_create: environment / default) or "sah" | "reference" | "lbvh" | "ploc" (mcpt_scene_create_ex)."""
         self.sd = sd
+        self.device = int(device)  # (-1: the current device)
         self._keep = []
         self.L = lib(library)
         d = _make_desc(sd, self._keep)
@@ -1499,6 +1569,126 @@ class HipScene:
         st = Stats()
         _check(self.L.mcpt_query_radiance(self.h, C.byref(p), n, C.byref(sensors), C.byref(outs), C.c_void_p(int(stream or 0)), C.byref(st)), L=self.L)
         return out["radiance"], (out["variance"] if variance else None), st
+
+    def _torch_device(self):
+        """The torch device of the scene (outputs the lightmap calls allocate themselves)."""
+        import torch
+        return torch.device("cuda", self.device if self.device >= 0 else torch.cuda.current_device())
+
+    def lightmap_texels(self, object, width, height, flip_normals=False, want=("texel", "prim", "bary", "origins", "normals"), out=None, stream=None):
+        """mcpt_lightmap_texels: the texel sensors of mesh `object` for a width x height map, from the scene as it is now -> (dict name ->
+        buffer, n).  Row i < n describes covered texel texel[i] (ascending y*width + x): prim its owner, bary (u, v), origins the point on the
+        live triangle, normals the live normal (negated with flip_normals): origins and normals are sensors for query_radiance(kind=
+        "hemisphere").  want: names among texel, prim, bary, origins, normals ("texel" is always written).  out: dict name -> device buffer
+        of width*height rows (int32 (N,), int32 (N,), float32 (N, 2), (N, 3), (N, 3)); None: torch tensors on the scene's device, returned
+        cut to their first n rows, and the stream defaults to torch's current one.  Blocks until n is known."""
+        who = "lightmap_texels"
+        want = tuple(want)
+        if any(w not in LIGHTMAP_OUTPUTS for w in want) or len(set(want)) != len(want):
+            raise ValueError("%s: want is a selection of %s without repeats, not %r" % (who, tuple(LIGHTMAP_OUTPUTS), want))
+        if "texel" not in want:
+            want = ("texel",) + want
+        d = _lightmap_desc(object, width, height, flip_normals)
+        cap = max(int(width), 0) * max(int(height), 0)
+        made = out is None
+        if made:
+            import torch
+            dev = self._torch_device()
+            rows = cap if cap <= (2 ** 31 - 1) // 3 else 0  # (the library refuses the size before it writes anything)
+            out = {w: torch.empty((rows,) if LIGHTMAP_OUTPUTS[w][2] == 1 else (rows, LIGHTMAP_OUTPUTS[w][2]),
+                                  dtype=getattr(torch, LIGHTMAP_OUTPUTS[w][1]), device=dev) for w in want}
+            if stream is None:
+                stream = torch.cuda.current_stream(dev).cuda_stream
+        bufs = LightmapTexelsOut()
+        for w in want:
+            if w not in out:
+                raise ValueError("%s: out has no buffer for %r" % (who, w))
+            ts, tn, k, _ = LIGHTMAP_OUTPUTS[w]
+            b = _device_buffer(out[w], who, "out[%r]" % w, ts, tn)
+            if b is None:
+                raise ValueError("%s: out[%r] is a buffer in device memory" % (who, w))
+            if not made and b[1] != ((cap,) if k == 1 else (cap, k)):
+                raise ValueError("%s: out[%r] has shape %s, not %s" % (who, w, (cap,) if k == 1 else (cap, k), b[1]))
+            setattr(bufs, w, b[0] or None)
+        n = C.c_int64(0)
+        _check(self.L.mcpt_lightmap_texels(self.h, C.byref(d), C.byref(bufs), C.byref(n), C.c_void_p(int(stream or 0))), L=self.L)
+        return {w: (out[w][:n.value] if made else out[w]) for w in want}, int(n.value)
+
+    def _lightmap_planes(self, who, width, height, out, names, stream):
+        """The device addresses of the planes `names` (image / variance: float32 (height, width, 3); coverage: uint8 (height, width)) in
+        `out`, torch tensors on the scene's device when out is None -> (out, {name: address}, stream)."""
+        W, H = int(width), int(height)
+        if out is None:
+            import torch
+            dev = self._torch_device()
+            ok = W >= 1 and H >= 1 and W * H <= (2 ** 31 - 1) // 3  # (otherwise the library refuses before it writes anything)
+            out = {w: torch.empty(((H, W) if ok else (1, 1)) + (() if w == "coverage" else (3,)), dtype=torch.uint8 if w == "coverage" else torch.float32,
+                                  device=dev) for w in names}
+            if stream is None:
+                stream = torch.cuda.current_stream(dev).cuda_stream
+            return out, {w: out[w].data_ptr() for w in names}, stream
+        ptrs = {}
+        for w in names:
+            if w not in out:
+                raise ValueError("%s: out has no buffer for %r" % (who, w))
+            ts, tn = ((("|u1", "<u1", "=u1"), "uint8") if w == "coverage" else (("<f4", "=f4", "|f4"), "float32"))
+            b = _device_buffer(out[w], who, "out[%r]" % w, ts, tn)
+            if b is None:
+                raise ValueError("%s: out[%r] is a buffer in device memory" % (who, w))
+            shape = (H, W) if w == "coverage" else (H, W, 3)
+            if b[1] != shape:
+                raise ValueError("%s: out[%r] has shape %s, not %s" % (who, w, shape, b[1]))
+            ptrs[w] = b[0]
+        return out, ptrs, stream
+
+    def lightmap_scatter(self, object, width, height, texel, values, dilate=2, coverage=True, out=None, stream=None):
+        """mcpt_lightmap_scatter: image[texel[i]] = values[i] on a zero map, then `dilate` rounds of the dilation of include/mcpt.h ->
+        (image (height, width, 3), coverage (height, width) uint8 or None).  texel: int32 (n,), values: float32 (n, 3); device buffers
+        (torch tensors, __cuda_array_interface__) are read in place, numpy arrays are staged through torch.  out: dict with "image" (and
+        "coverage") device buffers; None: torch tensors.  Enqueued on `stream` (default with torch inputs or outputs: torch's current one)."""
+        who = "lightmap_scatter"
+        bt, bv = _device_buffer(texel, who, "texel", ("<i4", "=i4"), "int32"), _device_buffer(values, who, "values")
+        keep = []
+        if bt is None or bv is None:
+            import torch
+            dev = self._torch_device()
+            texel = torch.from_numpy(np.ascontiguousarray(texel, dtype=np.int32).reshape(-1)).to(dev)
+            values = torch.from_numpy(np.ascontiguousarray(values, dtype=np.float32).reshape(-1, 3)).to(dev)
+            keep = [texel, values]
+            bt, bv = _device_buffer(texel, who, "texel", ("<i4", "=i4"), "int32"), _device_buffer(values, who, "values")
+            if stream is None:
+                stream = torch.cuda.current_stream(dev).cuda_stream
+        if len(bt[1]) != 1 or bv[1] != (bt[1][0], 3):
+            raise ValueError("%s: texel has shape (n,) and values (n, 3), not %s and %s" % (who, bt[1], bv[1]))
+        if out is None and stream is None and _is_torch(texel, values):
+            import torch
+            stream = torch.cuda.current_stream(texel.device).cuda_stream
+        names = ("image", "coverage") if coverage else ("image",)
+        out, ptrs, stream = self._lightmap_planes(who, width, height, out, names, stream)
+        d = _lightmap_desc(object, width, height)
+        _check(self.L.mcpt_lightmap_scatter(self.h, C.byref(d), bt[1][0], C.c_void_p(bt[0] or 0), C.c_void_p(bv[0] or 0), int(dilate),
+                                            C.c_void_p(ptrs["image"]), C.c_void_p(ptrs.get("coverage") or 0), C.c_void_p(int(stream or 0))), L=self.L)
+        if keep:  # the staged inputs must outlive the kernels that read them
+            import torch
+            torch.cuda.synchronize(keep[0].device)
+        return out["image"], (out["coverage"] if coverage else None)
+
+    def bake_lightmap(self, object, width, height, dilate=2, variance=False, out=None, stream=None, flip_normals=False, **params):
+        """mcpt_bake_lightmap: the lightmap of mesh `object` -- lightmap_texels, query_radiance(kind="hemisphere") at those sensors and
+        lightmap_scatter in one call -> (image (height, width, 3), coverage (height, width) uint8, variance (height, width, 3) or None,
+        mcpt_lightmap_info as a dict, Stats).  The image holds E / pi at covered texels, `dilate` rounds of dilation around them, 0
+        elsewhere; the variance (spp >= 2) is that of each covered texel's mean, not dilated.  out: dict with "image", "coverage" (and
+        "variance") device buffers; None: torch tensors on the scene's device.  params: the keywords of HipScene.params; sample_offset,
+        spp_total and accumulate must stay 0.  The call blocks until the map is written."""
+        who = "bake_lightmap"
+        names = ("image", "coverage", "variance") if variance else ("image", "coverage")
+        out, ptrs, stream = self._lightmap_planes(who, width, height, out, names, stream)
+        d = _lightmap_desc(object, width, height, flip_normals)
+        p = self.params(**params)
+        info, st = LightmapInfo(), Stats()
+        _check(self.L.mcpt_bake_lightmap(self.h, C.byref(d), C.byref(p), int(dilate), C.c_void_p(ptrs["image"]), C.c_void_p(ptrs["coverage"]),
+                                         C.c_void_p(ptrs.get("variance") or 0), C.c_void_p(int(stream or 0)), C.byref(info), C.byref(st)), L=self.L)
+        return out["image"], out["coverage"], (out["variance"] if variance else None), info.as_dict(), st
 
     def sensor_rays(self, kind, origins, dirs, sensor, sample, seed=1):
         """mcpt_sensor_rays: the first ray of (sensor[j], sample[j]) for sensors given on the host -> (origins[n,3], dirs[n,3]) float32.

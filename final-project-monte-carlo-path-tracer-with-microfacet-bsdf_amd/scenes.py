@@ -209,6 +209,24 @@ class _Builder:
                          objects=np.stack(self.objs).astype(OBJ_DTYPE), **kw)
 
 
+def with_planar_uvs(sd, obj, axes=(0, 2), margin=0.05, triangles=None):
+    """`sd` with a UV chart for mesh object `obj` (lightmap baking: HipScene.bake_lightmap; the shipped models carry none): the vertices
+    projected onto the two coordinate `axes` and scaled so that the bounding box of the charted triangles fills [margin, 1 - margin]^2.
+    triangles: indices into the object's triangle range that get the chart (None: all); the others keep the texture coordinates they have."""
+    import dataclasses
+    a, n = int(sd.objects["first_tri"][obj]), int(sd.objects["n_tri"][obj])
+    idx = a + (np.arange(n) if triangles is None else np.asarray(list(triangles), dtype=np.int64))
+    tris = sd.triangles.copy()
+    P = np.stack([tris[k][idx][:, list(axes)] for k in ("v0", "v1", "v2")], axis=1).astype(np.float64)  # (m, 3, 2)
+    lo, hi = P.reshape(-1, 2).min(0), P.reshape(-1, 2).max(0)
+    uv = (margin + (1.0 - 2.0 * margin) * (P - lo) / np.where(hi > lo, hi - lo, 1.0)).astype(f32)
+    for j, k in enumerate(("t0", "t1", "t2")):
+        t = tris[k]
+        t[idx] = uv[:, j]
+        tris[k] = t
+    return dataclasses.replace(sd, triangles=tris)
+
+
 # --------------------------------------------------------------------------- DEMO Cornell box (BASELINE config 1)
 def cornell_demo(width=384, height=384, spp=2048, assets=ASSETS):
     """main.cpp:99-129 + defaults main.cpp:28-31 (384x384, camera (278,273,-800)->(278,273,0), fov 40, rr 0.7)."""

@@ -1406,6 +1406,69 @@ int mcpt_debug_classify(mcpt_scene *scene, const mcpt_camera *camera, uint8_t *m
  *   out[15]     how many of those had a non-zero contribution (must be 0) */
 int mcpt_debug_counters(mcpt_scene *scene, uint64_t out[16]);
 
+/* ---- Lightmaps: from an object's UV layout to texel sensors, and from their radiance back to an image (csrc/mcpt_lightmap.h states the
+ * rule once, for the host and the device; csrc/mcpt_lightmap.hip holds the kernels).
+ *
+ * Coverage.  Texel (x, y) of a width x height map has its centre at px = ((double)x + 0.5) / width, py = ((double)y + 0.5) / height.  A
+ * triangle of the object with texture coordinates a = t0, b = t1, c = t2 (widened to double; never wrapped) covers it iff, with
+ *   area2 = (bx-ax)*(cy-ay) - (by-ay)*(cx-ax)                      zero or not finite: the triangle covers nothing
+ *   w1 = ((px-ax)*(cy-ay) - (py-ay)*(cx-ax)) / area2,  w2 = ((bx-ax)*(py-ay) - (by-ay)*(px-ax)) / area2,  w0 = 1 - w1 - w2
+ * all of w0, w1, w2 are >= 0 (a NaN fails).  Among the object's triangles that cover a texel the lowest global primitive id owns it;
+ * the chart's winding does not matter.
+ * Sensor.  bary = {(float)w1, (float)w2} = (u, v); origin = v0 + (e1*u + e2*v) per component in float on the LIVE triangle record (the
+ * `point` of mcpt_query_closest); normal = the live record's normal, negated with flip_normals.  Together they are a sensor of kind
+ * MCPT_SENSOR_HEMISPHERE, which applies its own offset along the normal.
+ * Order.  Covered texels are listed in ascending texel index y*width + x; entry i is sensor i (Philox key (seed, i)).
+ * Scatter and dilation.  image[texel[i]] = values[i], every other texel 0; coverage 1 where scattered.  Then `dilate` rounds: every texel
+ * whose coverage is still 0 and that has n >= 1 of its 8 neighbours with coverage != 0 AT THE START OF THE ROUND takes, per channel, the
+ * float sum of those neighbours (added to 0.f in the order (-1,-1) (0,-1) (1,-1) (-1,0) (1,0) (-1,1) (0,1) (1,1)) divided by (float)n,
+ * and coverage 2.  A texel index listed twice gives one of its values; an index outside the map is ignored.
+ *
+ * MCPT_ERR_ARG, before any device work: a null scene, desc or required pointer; a non-zero reserved word; an object out of range or a
+ * sphere; an instanced scene; width or height < 1 or width*height > (2^31 - 1) / 3; dilate < 0; n outside 0 .. width*height; a pointer
+ * that is not memory of the scene's device.  An object without a covered texel: MCPT_OK, n_out = 0, a zero image.  A hidden object may be
+ * asked: its records exist, and the light it receives is that of the scene without it. */
+typedef struct {
+    int32_t object, width, height, flip_normals;
+    int32_t reserved[4]; /* must be 0 */
+} mcpt_lightmap_desc; /* 32 bytes */
+typedef struct { /* device memory, capacity width*height rows each; every member nullable except texel */
+    int32_t *texel;
+    int32_t *prim;  /* global primitive id of the owner */
+    float *bary;    /* *2 */
+    float *origins; /* *3 */
+    float *normals; /* *3 */
+} mcpt_lightmap_texels_out;
+typedef struct {
+    int64_t n_texels;   /* covered texels = sensors */
+    int64_t items;      /* (triangle, 8x8 tile) pairs the rasteriser tested, one wave each */
+    int32_t grew;       /* 1: a scene-owned buffer was allocated or enlarged in this call; 0 in the steady state */
+    int32_t reserved0;
+    double ms_texels, ms_radiance, ms_scatter; /* host wall clock of the three legs */
+    int32_t reserved[4];
+} mcpt_lightmap_info; /* 64 bytes */
+/* Emits the object's texel sensors from the scene as it is now (after every update, deformation, addition) on hip_stream.  Blocks until
+ * *n_out is known; the rows of prim, bary, origins, normals are then ready in stream order.  All staging is scene-owned and only grows. */
+int mcpt_lightmap_texels(mcpt_scene *scene, const mcpt_lightmap_desc *desc, const mcpt_lightmap_texels_out *out, int64_t *n_out, void *hip_stream);
+/* image (width*height*3 floats) and coverage (width*height bytes, nullable) from n values at the listed texels; enqueued on hip_stream
+ * without a host synchronisation.  All pointers are device memory. */
+int mcpt_lightmap_scatter(mcpt_scene *scene, const mcpt_lightmap_desc *desc, int64_t n, const int32_t *texel, const float *values /* n*3 */,
+                          int32_t dilate, float *image /* W*H*3 */, uint8_t *coverage /* W*H, nullable */, void *hip_stream);
+/* mcpt_lightmap_texels -> mcpt_query_radiance (kind hemisphere, on scene-owned sensor buffers) -> mcpt_lightmap_scatter: the map of
+ * E / pi.  variance (nullable, needs spp >= 2): the variance of each texel's mean, scattered without dilation.  Blocks like
+ * mcpt_render_device.  Also MCPT_ERR_ARG: nranks > 1 or rank != 0; non-positive spp, n_dir_sample or rr_rate; non-zero sample_offset,
+ * spp_total or accumulate (progressive bakes are composed from the three pieces). */
+int mcpt_bake_lightmap(mcpt_scene *scene, const mcpt_lightmap_desc *desc, const mcpt_params *params, int32_t dilate, float *image,
+                       uint8_t *coverage /* nullable */, float *variance /* W*H*3, nullable */, void *hip_stream,
+                       mcpt_lightmap_info *info /* nullable */, mcpt_stats *stats /* nullable */);
+/* Host only, no GPU needed: the same header compiled for the CPU, on a description (as mcpt_compact_scene and mcpt_cull_bound are).  The
+ * records are built by the routine scene construction uses, so a fresh scene of `desc` gives the same bits.  Arrays of width*height rows;
+ * every array nullable (all null: only the count). */
+int mcpt_lightmap_texels_host(const mcpt_scene_desc *desc, const mcpt_lightmap_desc *lightmap, int32_t *texel, int32_t *prim, float *bary,
+                              float *origins, float *normals, int64_t *n_out);
+int mcpt_lightmap_dilate_host(int32_t width, int32_t height, int64_t n, const int32_t *texel, const float *values, int32_t dilate,
+                              float *image, uint8_t *coverage /* nullable */);
+
 const char *mcpt_last_error(void);
 const char *mcpt_version(void);
 
