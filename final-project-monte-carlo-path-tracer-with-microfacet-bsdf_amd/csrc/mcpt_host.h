@@ -222,6 +222,13 @@ struct LightmapBufs {
     bool grew = false;                        // a buffer above was (re)allocated since the flag was last cleared
 };
 
+// What the light-probe calls (csrc/mcpt_probes.hip) keep between calls; the buffers only ever grow.
+struct ProbeBufs {
+    DevBuf<float> points;    // mcpt_bake_probe_grid: the grid's points, n*3
+    DevBuf<float> radiance;  // mcpt_query_probes without a caller's radiance: the plain fold still needs a place, n*3
+    int64_t allocations = 0; // how often one of them was (re)allocated (mcpt_scene_probe_buffers)
+};
+
 // Environment knobs, read ONCE per scene in mcpt_scene_create: a render call never calls getenv.
 struct Knobs {
     bool overlap = true;        // MCPT_OVERLAP=0: one stream instead of three
@@ -493,6 +500,7 @@ struct mcpt_scene {
     mcpt::Event fork;
     mcpt::QueryBufs query;
     mcpt::LightmapBufs lightmap;
+    mcpt::ProbeBufs probes;
     mcpt::SharedBufs shared;
     // A wavefront pool: its own path lists, queues, clamp stack, counters and streams.  With MCPT_POOLS=2 two pools
     // are driven by two host threads on disjoint halves of each pass, so that one pool's k_shade (and its host
@@ -617,6 +625,7 @@ struct AccumPlan {
     const uint32_t *pixel_list;
     float *result[2];
     double *moments;  // adaptive sampling: per-pixel sums of v and v*v (nullptr: the plain fold)
+    const ShSink *sh = nullptr;  // mcpt_query_probes: every pass is also projected by k_accumulate_sh (nullptr: nothing changes)
 };
 
 // Where the first rays of new samples come from (mode 0): the camera of a frame, or the sensors of mcpt_query_radiance.  Holds pointers:
@@ -646,7 +655,13 @@ int prepare_pixels(mcpt_scene *sc, const CameraConst &cc, const mcpt_params &p, 
                    PixelSet &ps);
 int render_list(mcpt_scene *sc, const RaySource &src, const mcpt_params &p, const uint32_t *pixel_list, const int4 *pixel_cand, uint32_t n_pix,
                 int32_t sample_offset, int32_t spp, float spp_total, float *fb_dev, double *moments, hipStream_t st, Clock::time_point t0,
-                Totals &rt);
+                Totals &rt, const ShSink *sh = nullptr);
+
+// ---- mcpt_rayquery.hip
+// mcpt_query_radiance after its checks, shared with mcpt_query_probes (csrc/mcpt_probes.hip): n > 0 sensors `sn` into radiance (cleared
+// unless p.accumulate), the variance when asked, and with sh != nullptr the projection fold into sh (cleared likewise).  Blocks.
+int sensor_radiance(mcpt_scene *sc, const mcpt_params &p, uint32_t n, const SensorConst &sn, float *radiance, float *variance, float *sh,
+                    hipStream_t st, mcpt_stats *stats);
 
 // ---- mcpt_render.hip
 void add(mcpt_stats &a, const mcpt_stats &b);  // every count and kernel time of b into a (ms_total is the caller's)

@@ -6,6 +6,7 @@
 
 #include "mcpt_device.h"
 #include "mcpt_sensor.h"
+#include "mcpt_sh.h"
 
 namespace mcpt {
 
@@ -221,6 +222,16 @@ void launch_debug_material(const DevScene &S, int kind, uint32_t n, const float 
 // the per-pixel sums of v and v*v in double, moments[6m + c] and moments[6m + 3 + c]
 void launch_accumulate(const float *result, const uint32_t *pixel_list, uint32_t n_pix, int32_t s_pass, float spp_total,
                        float *fb, double *moments, hipStream_t s);
+// The optional second sink of a sensor call (mcpt_query_probes): the projection of every sample onto the nine spherical harmonics of its
+// own first direction, which k_accumulate_sh recomputes from (sn, seed, sensor, absolute sample).
+struct ShSink {
+    SensorConst sn;
+    uint32_t seed;
+    float *sh;  // n * 27
+};
+// sh[27i + 3j + c] += (result value * (4 pi * Y_j(first direction))) / spp_total over the pass's s_pass samples per probe, in sample
+// order; first_sample: the absolute index of the pass's first sample.  9 n_probes lanes: n_probes <= sh::kMaxProbes.
+void launch_accumulate_sh(const float *result, const ShSink &sink, uint32_t n_probes, int32_t s_pass, int32_t first_sample, float spp_total, hipStream_t s);
 
 // Ray queries on device memory (csrc/mcpt_rayquery.hip).  The outputs of k_query_resolve: mcpt_hit_buffers moved to the first ray of the
 // chunk; a null member is not written.

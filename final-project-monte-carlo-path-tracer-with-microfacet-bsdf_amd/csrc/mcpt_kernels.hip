@@ -1679,6 +1679,62 @@ __global__ __launch_bounds__(kBlock) void k_accumulate(const float *__restrict__
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// k_accumulate_sh: the projection fold of the light probes (mcpt_query_probes), beside k_accumulate on the same pass of `result`.
+//   sh[27i + 3j + c] += (v(i, k, c) * (kFourPi * Y_j(d(i, k)))) / spp_total   for the pass's samples k in sample order
+// One lane per (probe, coefficient) with the three channel sums: the direction d(i, k) is sensor_ray's, recomputed from (seed, i, k)
+// rather than stored, once per sample; the three values of a sample are one 12-byte run that the nine lanes of a probe share.  Eight
+// samples' loads are in flight, as in k_accumulate.  The coefficient is picked with selects: an indexed Y[j] would live in scratch.
+// ------------------------------------------------------------------------------------------------
+MCPT_DI float sh_weight(const SensorConst &sn, uint32_t seed, uint32_t i, uint32_t k, uint32_t j) {
+    f3 pos, dir;
+    sensor_ray(sn, seed, i, k, pos, dir);
+    const float d[3] = {dir.x, dir.y, dir.z};
+    float Y[9];
+    sh::sh9_basis(d, Y);
+    float y = Y[0];
+#pragma unroll
+    for (uint32_t q = 1; q < 9; ++q) y = j == q ? Y[q] : y;
+    return sh::kFourPi * y;
+}
+
+__global__ __launch_bounds__(kBlock) void k_accumulate_sh(const float *__restrict__ result, SensorConst sn, uint32_t seed, uint32_t n_probes,
+                                                          int32_t s_pass, uint32_t first_sample, float spp_total, float *__restrict__ sh_out) {
+    const uint32_t g = blockIdx.x * kBlock + threadIdx.x;
+    if (g >= n_probes * 9u) return;
+    const uint32_t i = g / 9u, j = g - 9u * i;
+    float *dst = sh_out + (size_t)i * 27 + 3 * j;
+    float a0 = dst[0], a1 = dst[1], a2 = dst[2];
+    const float *src = result + (size_t)i * s_pass * 3;
+    int k = 0;
+    for (; k + 8 <= s_pass; k += 8) {
+        float v[8][3];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            v[u][0] = src[(size_t)(k + u) * 3];
+            v[u][1] = src[(size_t)(k + u) * 3 + 1];
+            v[u][2] = src[(size_t)(k + u) * 3 + 2];
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const float w = sh_weight(sn, seed, i, first_sample + (uint32_t)(k + u), j);
+            a0 += (v[u][0] * w) / spp_total;
+            a1 += (v[u][1] * w) / spp_total;
+            a2 += (v[u][2] * w) / spp_total;
+        }
+    }
+    for (; k < s_pass; ++k) {
+        const float v0 = src[(size_t)k * 3], v1 = src[(size_t)k * 3 + 1], v2 = src[(size_t)k * 3 + 2];
+        const float w = sh_weight(sn, seed, i, first_sample + (uint32_t)k, j);
+        a0 += (v0 * w) / spp_total;
+        a1 += (v1 * w) / spp_total;
+        a2 += (v2 * w) / spp_total;
+    }
+    dst[0] = a0;
+    dst[1] = a1;
+    dst[2] = a2;
+}
+
 __global__ __launch_bounds__(kBlock) void k_mask_unowned(float *fb, int W, int H, int tile, int rank, int nranks) {
     const uint32_t m = blockIdx.x * kBlock + threadIdx.x;
     if (m >= (uint32_t)W * (uint32_t)H) return;
@@ -1975,6 +2031,12 @@ void launch_accumulate(const float *result, const uint32_t *pixel_list, uint32_t
         hipLaunchKernelGGL(k_accumulate<true>, dim3(blocks(n_pix * 3u)), dim3(kBlock), 0, s, result, pixel_list, n_pix, s_pass, spp_total, fb, moments);
     else
         hipLaunchKernelGGL(k_accumulate<false>, dim3(blocks(n_pix * 3u)), dim3(kBlock), 0, s, result, pixel_list, n_pix, s_pass, spp_total, fb, moments);
+}
+
+void launch_accumulate_sh(const float *result, const ShSink &sink, uint32_t n_probes, int32_t s_pass, int32_t first_sample, float spp_total, hipStream_t s) {
+    if (n_probes == 0) return;
+    hipLaunchKernelGGL(k_accumulate_sh, dim3(blocks(n_probes * 9u)), dim3(kBlock), 0, s, result, sink.sn, sink.seed, n_probes, s_pass, (uint32_t)first_sample,
+                       spp_total, sink.sh);
 }
 
 }  // namespace mcpt

@@ -318,25 +318,36 @@ int mcpt_query_radiance(mcpt_scene *sc, const mcpt_params *pp, int64_t n, const 
     if (!on_device(sensors->origins, sc->device) || !on_device(sensors->dirs, sc->device) || !on_device(out->radiance, sc->device) ||
         (out->variance && !on_device(out->variance, sc->device)))
         return bad("origins, dirs, radiance and variance must be memory of the scene's device");
+    return sensor_radiance(sc, p, (uint32_t)n, SensorConst{sensors->origins, sensors->dirs, sensors->kind}, out->radiance, out->variance, nullptr,
+                           (hipStream_t)hip_stream, stats);
+}
+
+}  // extern "C"
+
+namespace mcpt {
+
+int sensor_radiance(mcpt_scene *sc, const mcpt_params &p, uint32_t ns, const SensorConst &sn, float *radiance, float *variance, float *sh,
+                    hipStream_t st, mcpt_stats *stats) {
     HIP_TRY(hipSetDevice(sc->device));
     (void)hipGetLastError();  // an earlier, already reported failure of this thread must not be taken for one of this call
     const Clock::time_point t0 = Clock::now();
-    hipStream_t st = (hipStream_t)hip_stream;
-    const uint32_t ns = (uint32_t)n;
     double *moments = nullptr;
-    if (out->variance) {
+    if (variance) {
         HIP_TRY(sc->shared.sensor_moments.alloc((size_t)ns * 6));
         moments = sc->shared.sensor_moments.p;
         HIP_TRY(hipMemsetAsync(moments, 0, (size_t)ns * 6 * sizeof(double), st));
     }
-    if (!p.accumulate) HIP_TRY(hipMemsetAsync(out->radiance, 0, (size_t)ns * 3 * sizeof(float), st));
-    const SensorConst sn{sensors->origins, sensors->dirs, sensors->kind};
+    if (!p.accumulate) {
+        HIP_TRY(hipMemsetAsync(radiance, 0, (size_t)ns * 3 * sizeof(float), st));
+        if (sh) HIP_TRY(hipMemsetAsync(sh, 0, (size_t)ns * 27 * sizeof(float), st));
+    }
     const float spp_total = (float)(p.spp_total > 0 ? p.spp_total : p.spp);
+    const ShSink sink{sn, p.seed, sh};
     Totals rt;
-    const int rc = render_list(sc, sn, p, nullptr, nullptr, ns, p.sample_offset, p.spp, spp_total, out->radiance, moments, st, t0, rt);
+    const int rc = render_list(sc, sn, p, nullptr, nullptr, ns, p.sample_offset, p.spp, spp_total, radiance, moments, st, t0, rt, sh ? &sink : nullptr);
     if (rc != MCPT_OK) return rc;
-    if (out->variance) {
-        launch_sensor_variance(ns, p.spp, moments, out->variance, st);
+    if (variance) {
+        launch_sensor_variance(ns, p.spp, moments, variance, st);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipStreamSynchronize(st));
     }
@@ -349,6 +360,10 @@ int mcpt_query_radiance(mcpt_scene *sc, const mcpt_params *pp, int64_t n, const 
     if (rt.overflow) return fail(MCPT_ERR_OVERFLOW, "some paths outran the clamp stack (raise params.max_depth)");
     return MCPT_OK;
 }
+
+}  // namespace mcpt
+
+extern "C" {
 
 int mcpt_sensor_rays(mcpt_scene *sc, int32_t kind, uint32_t seed, int64_t n, const float *origins, const float *dirs, const uint32_t *sensor,
                      const uint32_t *sample, float *origins_out, float *dirs_out) {

@@ -202,6 +202,8 @@ int run_wavefront(mcpt_scene *sc, PoolCtx &ctx, const RenderConst &C0, const Ray
         while (acc && have_counters && accum_next < issue_pass && issue_done_iter[accum_next] < it &&
                (C.track_live ? w.h_counters->live[accum_next & 1].v == 0 : (n_cur_max == 0 && issue_pass >= P))) {
             T.timed(K_RESOLVE, s, [&] { launch_accumulate(acc->result[accum_next & 1], acc->pixel_list, acc->n_pix, plan[accum_next].s_pass, acc->spp_total, acc->fb, acc->moments, s); });
+            if (acc->sh)  // (light probes: the same pass of `result`, before the half is handed to the pass after next)
+                T.timed(K_RESOLVE, s, [&] { launch_accumulate_sh(acc->result[accum_next & 1], *acc->sh, acc->n_pix, plan[accum_next].s_pass, plan[accum_next].sample_offset, acc->spp_total, s); });
             accum_next++;
         }
     };
@@ -444,9 +446,10 @@ int prepare_pixels(mcpt_scene *sc, const CameraConst &cc, const mcpt_params &p, 
 // value / spp_total into fb_dev in sample order.  With sensors as the ray source: the n_pix sensors, pixel_list and pixel_cand null, fb_dev
 // the caller's n_pix * 3 floats (moments != nullptr: the per-pixel sums of v and v*v as well).  Blocks until done.
 // p supplies everything else (rr_rate, n_dir_sample, shadows, seed, spp_per_pass, pool_paths, max_depth).
+// sh_sink (light probes, sensors only): every pass is also folded by k_accumulate_sh, right behind k_accumulate; null: nothing changes.
 int render_list(mcpt_scene *sc, const RaySource &src, const mcpt_params &p, const uint32_t *pixel_list, const int4 *pixel_cand, uint32_t n_pix,
                 int32_t sample_offset, int32_t spp, float spp_total, float *fb_dev, double *moments, hipStream_t st, Clock::time_point t0,
-                Totals &rt) {
+                Totals &rt, const ShSink *sh_sink) {
     SharedBufs &sh = sc->shared;
     const int max_depth = derive_max_depth(p);
     // default: the smallest pool within 1 % of the best rate.  Measured on the chess frame (round 3, A/B on one box): 40 Mi paths 5031-5045,
@@ -534,7 +537,7 @@ int render_list(mcpt_scene *sc, const RaySource &src, const mcpt_params &p, cons
             const int s_now = std::min(s_pass, spp - k0);
             plan.push_back(PassPlan{0u, n_pix * (uint32_t)s_now, s_now, sample_offset + k0});
         }
-        AccumPlan acc{fb_dev, spp_total, n_pix, pixel_list, {C.result[0], C.result[1]}, moments};
+        AccumPlan acc{fb_dev, spp_total, n_pix, pixel_list, {C.result[0], C.result[1]}, moments, sh_sink};
         const int rc = drained(run_wavefront(sc, sc->pools[0], C, src, plan, &acc, st, tot[0]));
         if (rc != MCPT_OK) return rc;
     } else {
@@ -565,6 +568,7 @@ int render_list(mcpt_scene *sc, const RaySource &src, const mcpt_params &p, cons
             if (c1.rc != MCPT_OK) return drained(fail(c1.rc, c1.err));
             Timer &T0 = sc->pools[0].timer;
             T0.timed(K_RESOLVE, st, [&] { launch_accumulate(C.result[0], pixel_list, n_pix, s_now, spp_total, fb_dev, moments, st); });
+            if (sh_sink) T0.timed(K_RESOLVE, st, [&] { launch_accumulate_sh(C.result[0], *sh_sink, n_pix, s_now, sample_offset + k0, spp_total, st); });
         }
     }
     HIP_TRY(hipStreamSynchronize(st));

@@ -39,6 +39,8 @@ EXPORTS = ["mcpt_scene_create", "mcpt_scene_destroy", "mcpt_render", "mcpt_rende
            "mcpt_scene_ray_counts", "mcpt_scene_primary_conductor_counts",
            "mcpt_query_closest", "mcpt_query_occluded", "mcpt_query_radiance", "mcpt_sensor_rays",
            "mcpt_lightmap_texels", "mcpt_lightmap_scatter", "mcpt_bake_lightmap", "mcpt_lightmap_texels_host", "mcpt_lightmap_dilate_host",
+           "mcpt_query_probes", "mcpt_probe_rays", "mcpt_probe_shade", "mcpt_bake_probe_grid", "mcpt_scene_probe_buffers",
+           "mcpt_sh_basis_host", "mcpt_sh_irradiance_host", "mcpt_probe_grid_points_host", "mcpt_probe_shade_host",
            "mcpt_group_create", "mcpt_group_render", "mcpt_group_size", "mcpt_group_get_info", "mcpt_group_scene", "mcpt_group_destroy", "mcpt_group_last_error",
            "mcpt_last_error", "mcpt_version"]
 
@@ -467,6 +469,41 @@ def _lightmap_desc(object, width, height, flip_normals=False):
     return LightmapDesc(int(object), int(width), int(height), 1 if flip_normals else 0, (C.c_int32 * 4)(0, 0, 0, 0))
 
 
+class ProbeGrid(C.Structure):
+    _fields_ = [("origin", C.c_float * 3), ("spacing", C.c_float * 3), ("dims", C.c_int32 * 3), ("reserved", C.c_int32 * 3)]
+
+
+class ProbeOutputs(C.Structure):
+    _fields_ = [("sh", C.c_void_p), ("radiance", C.c_void_p), ("variance", C.c_void_p), ("reserved", C.c_void_p)]
+
+
+def _probe_grid(who, origin, spacing, dims):
+    """mcpt_probe_grid from three triples; the library's refusals (dims < 1, too many probes, a spacing that is not positive and finite) are
+    made here as well, before any buffer is sized from the grid."""
+    try:
+        o, s = [float(v) for v in origin], [float(v) for v in spacing]
+        d = [int(v) for v in dims]
+    except (TypeError, ValueError):
+        raise ValueError("%s: origin, spacing and dims are triples of numbers" % who)
+    if len(o) != 3 or len(s) != 3 or len(d) != 3 or any(int(v) != v for v in dims):
+        raise ValueError("%s: origin, spacing and dims are triples (dims of integers)" % who)
+    if any(v < 1 for v in d) or d[0] * d[1] * d[2] > (2 ** 31 - 1) // 27:
+        raise ValueError("%s: every member of dims is >= 1 and the grid has at most (2^31 - 1) / 27 probes, not %s" % (who, d))
+    if any(not (v > 0 and np.isfinite(np.float32(v))) for v in s):
+        raise ValueError("%s: spacing is positive and finite, not %s" % (who, s))
+    return ProbeGrid((C.c_float * 3)(*o), (C.c_float * 3)(*s), (C.c_int32 * 3)(*d), (C.c_int32 * 3)(0, 0, 0)), d[0] * d[1] * d[2]
+
+
+def _probe_rows(who, what, v, width, n=None):
+    """The device address and row count of a float32, C-contiguous (n, width) device buffer."""
+    b = _device_buffer(v, who, what)
+    if b is None:
+        raise ValueError("%s: %s is a buffer in device memory (__cuda_array_interface__, or data_ptr() and is_cuda)" % (who, what))
+    if len(b[1]) != 2 or b[1][1] != width or (n is not None and b[1][0] != n):
+        raise ValueError("%s: %s has shape (%s, %d), not %s" % (who, what, "n" if n is None else n, width, b[1]))
+    return b[0], b[1][0]
+
+
 def _is_torch(*vs):
     return all(hasattr(v, "data_ptr") and getattr(v, "is_cuda", False) for v in vs)
 
@@ -658,6 +695,24 @@ def lib(path=None):
         L.mcpt_query_radiance.argtypes = [C.c_void_p, C.POINTER(Params), C.c_int64, C.POINTER(SensorBuffers), C.POINTER(SensorOutputs), C.c_void_p, C.POINTER(Stats)]
         L.mcpt_sensor_rays.restype = C.c_int
         L.mcpt_sensor_rays.argtypes = [C.c_void_p, C.c_int32, C.c_uint32, C.c_int64] + [C.c_void_p] * 6
+        L.mcpt_query_probes.restype = C.c_int
+        L.mcpt_query_probes.argtypes = [C.c_void_p, C.POINTER(Params), C.c_int64, C.c_void_p, C.POINTER(ProbeOutputs), C.c_void_p, C.POINTER(Stats)]
+        L.mcpt_probe_rays.restype = C.c_int
+        L.mcpt_probe_rays.argtypes = [C.c_void_p, C.c_uint32, C.c_int64] + [C.c_void_p] * 5
+        L.mcpt_probe_shade.restype = C.c_int
+        L.mcpt_probe_shade.argtypes = [C.c_void_p, C.POINTER(ProbeGrid), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.mcpt_bake_probe_grid.restype = C.c_int
+        L.mcpt_bake_probe_grid.argtypes = [C.c_void_p, C.POINTER(ProbeGrid), C.POINTER(Params), C.c_void_p, C.c_void_p, C.POINTER(Stats)]
+        L.mcpt_scene_probe_buffers.restype = C.c_int
+        L.mcpt_scene_probe_buffers.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        L.mcpt_sh_basis_host.restype = C.c_int
+        L.mcpt_sh_basis_host.argtypes = [C.c_int64, C.c_void_p, C.c_void_p]
+        L.mcpt_sh_irradiance_host.restype = C.c_int
+        L.mcpt_sh_irradiance_host.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.mcpt_probe_grid_points_host.restype = C.c_int
+        L.mcpt_probe_grid_points_host.argtypes = [C.POINTER(ProbeGrid), C.c_void_p]
+        L.mcpt_probe_shade_host.restype = C.c_int
+        L.mcpt_probe_shade_host.argtypes = [C.POINTER(ProbeGrid), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
         L.mcpt_lightmap_texels.restype = C.c_int
         L.mcpt_lightmap_texels.argtypes = [C.c_void_p, C.POINTER(LightmapDesc), C.POINTER(LightmapTexelsOut), C.POINTER(C.c_int64), C.c_void_p]
         L.mcpt_lightmap_scatter.restype = C.c_int
@@ -864,6 +919,52 @@ def lightmap_dilate(width, height, texel, values, dilate):
     cov = np.zeros((1, 1) if big else (H, W), np.uint8)
     _check(lib().mcpt_lightmap_dilate_host(W, H, len(tx), _ptr(tx), _ptr(v), int(dilate), _ptr(image), _ptr(cov)))
     return image, cov
+
+
+def sh_basis(dirs):
+    """mcpt_sh_basis_host (host only): the nine real spherical harmonics of order <= 2 at unit directions (n, 3) -> (n, 9) float32, in the
+    index order of include/mcpt.h."""
+    d = np.ascontiguousarray(dirs, dtype=np.float32).reshape(-1, 3)
+    out = np.zeros((len(d), 9), np.float32)
+    _check(lib().mcpt_sh_basis_host(len(d), _ptr(d), _ptr(out)))
+    return out
+
+
+def sh_irradiance(sh, normals):
+    """mcpt_sh_irradiance_host (host only): E / pi for unit normals (n, 3) from coefficients (n, 27), or (27,) for all of them -> (n, 3)
+    float32.  Not clamped at zero."""
+    nr = np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 3)
+    L = np.ascontiguousarray(sh, dtype=np.float32)
+    if L.size == 27:
+        L = np.ascontiguousarray(np.broadcast_to(L.reshape(1, 27), (len(nr), 27)))
+    if L.shape != (len(nr), 27):
+        raise ValueError("sh_irradiance: sh has shape (27,) or (n, 27), not %s" % (L.shape,))
+    out = np.zeros((len(nr), 3), np.float32)
+    _check(lib().mcpt_sh_irradiance_host(len(nr), _ptr(L), _ptr(nr), _ptr(out)))
+    return out
+
+
+def probe_grid_points(origin, spacing, dims):
+    """mcpt_probe_grid_points_host (host only): the points of a probe grid -> (nx*ny*nz, 3) float32, probe (ix, iy, iz) in row
+    (iz * ny + iy) * nx + ix."""
+    g, n = _probe_grid("probe_grid_points", origin, spacing, dims)
+    out = np.zeros((n, 3), np.float32)
+    _check(lib().mcpt_probe_grid_points_host(C.byref(g), _ptr(out)))
+    return out
+
+
+def probe_shade(origin, spacing, dims, sh, points, normals):
+    """mcpt_probe_shade_host (host only): the trilinear grid lookup of include/mcpt.h, E / pi at `points` (n, 3) for `normals` (n, 3) from
+    the grid's coefficients sh (probes, 27) -> (n, 3) float32."""
+    g, m = _probe_grid("probe_shade", origin, spacing, dims)
+    L = np.ascontiguousarray(sh, dtype=np.float32)
+    p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+    nr = np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 3)
+    if L.shape != (m, 27) or len(nr) != len(p):
+        raise ValueError("probe_shade: sh has shape (%d, 27) and there is one normal per point, not %s, %d and %d" % (m, L.shape, len(nr), len(p)))
+    out = np.zeros((len(p), 3), np.float32)
+    _check(lib().mcpt_probe_shade_host(C.byref(g), _ptr(L), len(p), _ptr(p), _ptr(nr), _ptr(out)))
+    return out
 
 
 def cull_bound(camera, root_min, root_max, library=None):
@@ -1705,6 +1806,93 @@ class HipScene:
         d = np.zeros((n, 3), dtype=np.float32)
         _check(self.L.mcpt_sensor_rays(self.h, k, int(seed), n, _ptr(po), _ptr(pd), _ptr(si), _ptr(sm), _ptr(o), _ptr(d)), L=self.L)
         return o, d
+
+    def query_probes(self, origins, radiance=False, variance=False, out=None, stream=None, **params):
+        """mcpt_query_probes: light probes at points (n, 3) in the memory of the scene's device -> (sh (n, 27), radiance (n, 3) or None,
+        variance (n, 3) or None, Stats).  sh[i, 3j + c] is coefficient j of channel c of the incoming radiance over the whole sphere at
+        point i, the fold of include/mcpt.h over the first rays probe_rays gives; radiance is the mean over the sphere.  Inputs, out and
+        stream as in query_radiance: out is a dict with "sh" (and "radiance", "variance") float32 device buffers, or None when origins
+        is a torch tensor.  params: the keywords of HipScene.params.  The call blocks until the outputs are written."""
+        who = "query_probes"
+        po, n = _probe_rows(who, "origins", origins, 3)
+        if n > (2 ** 31 - 1) // 27:
+            raise ValueError("%s: at most (2^31 - 1) / 27 probes, not %d" % (who, n))
+        names = ("sh",) + (("radiance",) if radiance or variance else ()) + (("variance",) if variance else ())
+        if out is None:
+            if not _is_torch(origins):
+                raise ValueError("%s: out is required unless origins is a torch tensor" % who)
+            import torch
+            out = {w: torch.empty((n, 27 if w == "sh" else 3), dtype=torch.float32, device=origins.device) for w in names}
+            if stream is None:
+                stream = torch.cuda.current_stream(origins.device).cuda_stream
+        ptrs = {}
+        for w in names:
+            if w not in out:
+                raise ValueError("%s: out has no buffer for %r" % (who, w))
+            ptrs[w] = _probe_rows(who, "out[%r]" % w, out[w], 27 if w == "sh" else 3, n)[0] or None
+        outs = ProbeOutputs(ptrs["sh"], ptrs.get("radiance"), ptrs.get("variance"), None)
+        p = self.params(**params)
+        st = Stats()
+        _check(self.L.mcpt_query_probes(self.h, C.byref(p), n, C.c_void_p(po or 0), C.byref(outs), C.c_void_p(int(stream or 0)), C.byref(st)), L=self.L)
+        return out["sh"], out.get("radiance") if "radiance" in names else None, (out["variance"] if variance else None), st
+
+    def probe_rays(self, origins, sensor, sample, seed=1):
+        """mcpt_probe_rays: the first ray of (probe sensor[j], sample[j]) for probes given on the host -> (origins[n,3], dirs[n,3]) float32;
+        sample is absolute (sample_offset + k)."""
+        po = np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3)
+        si = np.ascontiguousarray(sensor, dtype=np.uint32).reshape(-1)
+        sm = np.ascontiguousarray(sample, dtype=np.uint32).reshape(-1)
+        n = len(si)
+        if len(sm) != n or (n and int(si.max()) >= len(po)):
+            raise ValueError("probe_rays: sensor and sample have one length, and every probe named has a row in origins")
+        o = np.zeros((n, 3), dtype=np.float32)
+        d = np.zeros((n, 3), dtype=np.float32)
+        _check(self.L.mcpt_probe_rays(self.h, int(seed), n, _ptr(po), _ptr(si), _ptr(sm), _ptr(o), _ptr(d)), L=self.L)
+        return o, d
+
+    def probe_shade(self, origin, spacing, dims, sh, points, normals, out=None, stream=None):
+        """mcpt_probe_shade: the grid lookup of include/mcpt.h on the device, E / pi at points (n, 3) for normals (n, 3) from the grid's
+        coefficients sh (probes, 27) -> (n, 3) float32 device buffer.  All are device buffers; out may be None with torch inputs.  Enqueued
+        on `stream` without a synchronisation."""
+        who = "probe_shade"
+        g, m = _probe_grid(who, origin, spacing, dims)
+        ps = _probe_rows(who, "sh", sh, 27, m)[0]
+        pp, n = _probe_rows(who, "points", points, 3)
+        pn = _probe_rows(who, "normals", normals, 3, n)[0]
+        if out is None:
+            if not _is_torch(sh, points, normals):
+                raise ValueError("%s: out is required unless the inputs are torch tensors" % who)
+            import torch
+            out = torch.empty((n, 3), dtype=torch.float32, device=points.device)
+            if stream is None:
+                stream = torch.cuda.current_stream(points.device).cuda_stream
+        pout = _probe_rows(who, "out", out, 3, n)[0]
+        _check(self.L.mcpt_probe_shade(self.h, C.byref(g), C.c_void_p(ps or 0), n, C.c_void_p(pp or 0), C.c_void_p(pn or 0), C.c_void_p(pout or 0),
+                                       C.c_void_p(int(stream or 0))), L=self.L)
+        return out
+
+    def bake_probe_grid(self, origin, spacing, dims, out=None, stream=None, **params):
+        """mcpt_bake_probe_grid: probe_grid_points on the device into a scene-owned buffer, then query_probes there -> (sh (probes, 27),
+        Stats).  out: a float32 (probes, 27) device buffer; None: a torch tensor on the scene's device."""
+        who = "bake_probe_grid"
+        g, m = _probe_grid(who, origin, spacing, dims)
+        if out is None:
+            import torch
+            dev = self._torch_device()
+            out = torch.empty((m, 27), dtype=torch.float32, device=dev)
+            if stream is None:
+                stream = torch.cuda.current_stream(dev).cuda_stream
+        ps = _probe_rows(who, "out", out, 27, m)[0]
+        p = self.params(**params)
+        st = Stats()
+        _check(self.L.mcpt_bake_probe_grid(self.h, C.byref(g), C.byref(p), C.c_void_p(ps or 0), C.c_void_p(int(stream or 0)), C.byref(st)), L=self.L)
+        return out, st
+
+    def probe_buffers(self):
+        """mcpt_scene_probe_buffers -> (floats the scene-owned probe buffers hold, how often one of them was (re)allocated)."""
+        f, a = C.c_int64(0), C.c_int64(0)
+        _check(self.L.mcpt_scene_probe_buffers(self.h, C.byref(f), C.byref(a)), L=self.L)
+        return int(f.value), int(a.value)
 
     def shadow_visible(self, origins, dirs, dist, found=None, shard=None, list=0):
         """mcpt_debug_shadow: the render loop's shadow query (k_trace_shadow, its retrace included) for rays of the caller's -> bool [n]:

@@ -1469,6 +1469,61 @@ int mcpt_lightmap_texels_host(const mcpt_scene_desc *desc, const mcpt_lightmap_d
 int mcpt_lightmap_dilate_host(int32_t width, int32_t height, int64_t n, const int32_t *texel, const float *values, int32_t dilate,
                               float *image, uint8_t *coverage /* nullable */);
 
+/* ---- Light probes: the incoming radiance over the whole sphere at points in free space, projected onto the nine real spherical
+ * harmonics of order <= 2, and the irradiance of any normal from those 27 floats (csrc/mcpt_sh.h states the rule once, for the host and
+ * the device; csrc/mcpt_probes.hip holds the kernels).  A regular grid of probes blended trilinearly is the irradiance volume.
+ *
+ * Basis, for a unit d = (x, y, z), in float with a*b*c = (a*b)*c:  Y0 = 0.28209479f, Y1 = 0.48860251f y, Y2 = 0.48860251f z,
+ * Y3 = 0.48860251f x, Y4 = 1.0925484f x y, Y5 = 1.0925484f y z, Y6 = 0.31539157f (3 z z - 1), Y7 = 1.0925484f x z,
+ * Y8 = 0.54627422f (x x - y y): the float roundings of sqrt(1/4pi), sqrt(3/4pi), sqrt(15/4pi), sqrt(5/16pi), sqrt(15/16pi).
+ * First ray of (probe i, sample k): with u the uniforms of the Philox block (seed, i, sample_offset + k, stream 4), z = 1 - 2 u[0],
+ * r = sqrtf(fmaxf(0, 1 - z z)), phi = 2 pi u[1], direction d(i, k) = normalized((r cos phi, r sin phi, z)), origin origins[i] itself (no
+ * offset: a probe sits in free space).  mcpt_probe_rays returns these rays for probes given on the host, like mcpt_sensor_rays.
+ * Projection, with v(i, k, c) as for mcpt_query_radiance and spp_total likewise:
+ *   sh[27i + 3j + c]:  acc = accumulate ? sh[27i + 3j + c] : 0;  for k in 0 .. spp-1:  acc += (v(i,k,c) * (kFourPi * Y_j(d(i,k)))) / spp_total
+ * in float, kFourPi = (float)(4 pi), the reciprocal of the uniform pdf.  radiance (nullable) is the plain fold of mcpt_query_radiance
+ * over the same samples, the mean radiance over the sphere; variance (nullable) its variance under the same conditions.
+ * Irradiance: mcpt_sh_irradiance_host gives E / pi for a unit normal n, out[c] = sum over j in index order, from 0, of
+ * (A(j) * L[3j + c]) * Y_j(n), A = 1, 2/3 (j = 1..3), 1/4 (j = 4..8): the clamped-cosine convolution over pi.  It is NOT clamped at 0:
+ * the truncated series rings and can go slightly negative.
+ * Grid: probe (ix, iy, iz) sits at origin + (float)i * spacing per axis, index (iz * ny + iy) * nx + ix.  Lookup of a point p, per axis:
+ * g = (p - origin) / spacing clamped to [0, dim - 1], i0 = min((int)floorf(g), dim - 2), t = g - i0; dim == 1: i0 = 0, t = 0 and the
+ * missing neighbour is the probe itself.  Each of the 27 coefficients is blended over the eight corners, b = 0; b += w * L_corner in the
+ * order (dz, dy, dx) = 000, 001, 010, .. 111, w = (wz * wy) * wx with w_axis = 1 - t or t; then the irradiance sum above.  No visibility
+ * test: a probe inside an object reports what mcpt_cast_rays gives there.
+ *
+ * mcpt_query_probes blocks like mcpt_query_radiance, makes the same refusals before any device work, and also refuses n > (2^31 - 1) / 27;
+ * n == 0, MCPT_ERR_OVERFLOW, stats and the ray counts follow the same rules; it sees the live scene as it is now.  mcpt_probe_shade is
+ * enqueued on hip_stream without a synchronisation or an allocation.  mcpt_bake_probe_grid writes the grid's points into a scene-owned
+ * buffer that only grows and runs mcpt_query_probes on it.  MCPT_ERR_ARG for a grid: a dims member < 1, more than (2^31 - 1) / 27
+ * probes, a spacing that is not positive and finite, a non-zero reserved word.  No mcpt_group_* form (mcpt_group_scene). */
+typedef struct {
+    float origin[3], spacing[3];
+    int32_t dims[3];     /* nx, ny, nz */
+    int32_t reserved[3]; /* must be 0 */
+} mcpt_probe_grid; /* 48 bytes */
+typedef struct {        /* device memory */
+    float *sh;          /* n*27, required */
+    float *radiance;    /* n*3, nullable */
+    float *variance;    /* n*3, nullable */
+    void *reserved;     /* must be null */
+} mcpt_probe_outputs;  /* 32 bytes */
+int mcpt_query_probes(mcpt_scene *scene, const mcpt_params *params, int64_t n, const float *origins /* n*3, device */,
+                      const mcpt_probe_outputs *out, void *hip_stream, mcpt_stats *stats /* nullable */);
+int mcpt_probe_rays(mcpt_scene *scene, uint32_t seed, int64_t n, const float *origins, const uint32_t *sensor, const uint32_t *sample,
+                    float *origins_out, float *dirs_out);
+int mcpt_probe_shade(mcpt_scene *scene, const mcpt_probe_grid *grid, const float *sh /* probes*27, device */, int64_t n,
+                     const float *points /* n*3, device */, const float *normals /* n*3, device */, float *out /* n*3, device */, void *hip_stream);
+int mcpt_bake_probe_grid(mcpt_scene *scene, const mcpt_probe_grid *grid, const mcpt_params *params, float *sh /* probes*27, device */,
+                         void *hip_stream, mcpt_stats *stats /* nullable */);
+/* The floats the scene-owned probe buffers hold and how often one of them was (re)allocated: 0 more in the steady state. */
+int mcpt_scene_probe_buffers(const mcpt_scene *scene, int64_t *floats, int64_t *allocations);
+/* Host only, no GPU needed: csrc/mcpt_sh.h compiled for the CPU. */
+int mcpt_sh_basis_host(int64_t n, const float *dirs /* n*3 */, float *basis /* n*9 */);
+int mcpt_sh_irradiance_host(int64_t n, const float *sh /* n*27 */, const float *normals /* n*3 */, float *out /* n*3 */);
+int mcpt_probe_grid_points_host(const mcpt_probe_grid *grid, float *points /* probes*3 */);
+int mcpt_probe_shade_host(const mcpt_probe_grid *grid, const float *sh, int64_t n, const float *points, const float *normals, float *out);
+
 const char *mcpt_last_error(void);
 const char *mcpt_version(void);
 

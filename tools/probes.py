@@ -1,0 +1,83 @@
+"""A small probe grid in the Cornell demo scene against hemisphere sensors: what the SH-9 truncation plus the grid's trilinear interpolation
+cost.  The command behind the "Light probes" figures of DESIGN.md section 6c.
+python tools/probes.py [--dims 5 4 5] [--spp 16384] [--sensor-spp 262144] [--seed 3]
+The grid spans the box's interior.  At a handful of (point, normal) pairs in free space the tool prints the lookup (probe_shade on the
+baked coefficients) next to query_radiance(kind="hemisphere") at the same point and normal, with the sensor's reported standard error:
+both are E / pi.  Also printed: the lookup AT a probe against a sensor there (truncation alone, no interpolation), and the wall times of
+the bake and of the lookup.  Device buffers come from the HIP runtime the library is linked to, through ctypes; torch is not needed."""
+import argparse
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, '.')
+sys.path.insert(0, 'tools')
+import mcpt_loader  # noqa: E402
+from ray_query import Dev, runtime  # noqa: E402
+
+f32 = np.float32
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--dims", type=int, nargs=3, default=[5, 4, 5])
+    ap.add_argument("--spp", type=int, default=16384)
+    ap.add_argument("--sensor-spp", type=int, default=262144)
+    ap.add_argument("--seed", type=int, default=3)
+    args = ap.parse_args()
+    pkg = mcpt_loader.load()
+    hip = pkg.hip_backend
+    sd = pkg.scenes.cornell_demo(64, 64, 4)
+    hs = hip.HipScene(sd, builder="sah")
+    rt = runtime()
+    dims = tuple(args.dims)
+    lo, hi = np.array([40.0, 40.0, 40.0]), np.array([516.0, 500.0, 516.0])
+    origin = tuple(lo)
+    spacing = tuple((hi - lo) / np.maximum(np.array(dims) - 1, 1))
+    m = dims[0] * dims[1] * dims[2]
+    sh = Dev(rt, shape=(m, 27))
+    t0 = time.perf_counter()
+    _, st = hs.bake_probe_grid(origin, spacing, dims, out=sh, spp=args.spp, seed=args.seed)
+    t_bake = (time.perf_counter() - t0) * 1e3
+    print("grid %dx%dx%d = %d probes, spacing %s, %d spp: bake %.1f ms (%d samples, %d wavefront iterations; resolve kernels %.3f ms in %d launches)"
+          % (dims + (m, np.round(spacing, 1), args.spp, t_bake, st.samples, st.iterations, st.ms_resolve, st.n_resolve)))
+    pts = hip.probe_grid_points(origin, spacing, dims)
+    # free-space points: above the boxes and the spheres, and in the open front part of the room; three normals each
+    P = np.array([[278, 420, 278], [150, 450, 150], [430, 380, 120], [278, 250, 60], [80, 200, 120], [480, 120, 80]], f32)
+    N = np.array([[0, 1, 0], [0, -1, 0], [0.57735027, 0.57735027, -0.57735027]], f32)
+    # ... and two probes themselves (interpolation weights 1 and 0): the truncation alone
+    at = pts[[m // 2, m - dims[0] * dims[1] // 2 - 1]]
+    p = np.repeat(np.concatenate([P, at]), len(N), axis=0)
+    n = np.tile(N, (len(P) + len(at), 1))
+    dp, dn = Dev(rt, p), Dev(rt, n)
+    out = Dev(rt, shape=(len(p), 3))
+    t0 = time.perf_counter()
+    hs.probe_shade(origin, spacing, dims, sh, dp, dn, out=out)
+    look = out.get()
+    t_look = (time.perf_counter() - t0) * 1e3
+    so = {"radiance": Dev(rt, shape=(len(p), 3)), "variance": Dev(rt, shape=(len(p), 3))}
+    hs.query_radiance(dp, dn, kind="hemisphere", variance=True, out=so, spp=args.sensor_spp, seed=args.seed + 1)
+    ref, se = so["radiance"].get(), np.sqrt(so["variance"].get())
+    print("lookup of %d pairs: %.2f ms (first call, with its read-back); hemisphere sensors at %d spp" % (len(p), t_look, args.sensor_spp))
+    print("%-22s %-22s %-28s %-28s %-10s %s" % ("point", "normal", "lookup E/pi (rgb)", "sensor E/pi (rgb)", "rel. diff", "sensor s.e. / value"))
+    rel_all = []
+    for i in range(len(p)):
+        lum_l, lum_r = look[i].mean(), ref[i].mean()
+        rel = abs(lum_l - lum_r) / max(lum_r, 1e-12)
+        rel_all.append(rel)
+        tag = "  (at a probe)" if i >= len(P) * len(N) else ""
+        if not (lum_r > 0):  # zero: the point lies inside an object; NaN: one of the sensor's samples was not finite.  Left out of the summary
+            rel_all[-1] = np.nan
+            tag += "  (sensor zero or not finite: skipped)"
+        print("%-22s %-22s %-28s %-28s %-10.4f %.4f%s" % (np.round(p[i], 1), np.round(n[i], 2), np.round(look[i], 4), np.round(ref[i], 4), rel,
+                                                          se[i].mean() / max(lum_r, 1e-12), tag))
+    rel_all = np.array(rel_all)
+    k = len(P) * len(N)
+    print("relative difference of the channel mean: interpolated pairs mean %.4f, max %.4f; at probes mean %.4f, max %.4f; negative lookups: %d"
+          % (np.nanmean(rel_all[:k]), np.nanmax(rel_all[:k]), np.nanmean(rel_all[k:]), np.nanmax(rel_all[k:]), int((look < 0).sum())))
+    hs.close()
+
+
+if __name__ == "__main__":
+    main()
