@@ -549,6 +549,13 @@ inline bool on_device(const void *p, int device) {
     return a.type == hipMemoryTypeDevice && a.device == device;
 }
 
+// ---- mcpt_rayquery.hip
+// The two ends of everything that uses the ray queries' staging buffers: query_stage makes them hold `chunk` rays on stream st (growth
+// behind query_settle, the wait for a query on another stream, the range table; qi.grew says whether it allocated) and gives the retry
+// list of the chunk's launches; query_finish records QueryBufs::done behind what was enqueued since.  With the scene's device current.
+int query_stage(mcpt_scene *sc, uint32_t chunk, hipStream_t st, mcpt_query_info &qi, RetryList &rl);
+int query_finish(mcpt_scene *sc, hipStream_t st, mcpt_query_info &qi);
+
 // ---- mcpt_upload.hip
 // The two halves of mcpt_scene_create, exposed for mcpt_group_create (csrc/mcpt_multi.hip), which flattens the scene and builds its
 // tree once and then uploads it to every device from one thread per device.

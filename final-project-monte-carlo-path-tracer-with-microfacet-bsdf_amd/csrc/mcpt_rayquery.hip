@@ -190,13 +190,15 @@ void build_range_table(const SceneSource &S, std::vector<int32_t> &table) {
     if (m == 0) table[1] = -1;  // (no mesh: no triangle can be hit)
 }
 
-// Both queries after their argument checks.  occluded != nullptr: the any-hit query; else closest hits into `hits`.
-int run_query(mcpt_scene *sc, int64_t n, const mcpt_ray_buffers &rays, const mcpt_hit_buffers *hits, uint8_t *occluded, hipStream_t st, mcpt_query_info *info) {
-    mcpt_query_info qi;
-    std::memset(&qi, 0, sizeof qi);
-    HIP_TRY(hipSetDevice(sc->device));
+}  // namespace
+
+namespace mcpt {
+
+// Makes the scene's staging buffers hold `chunk` rays on stream st (QueryBufs, csrc/mcpt_host.h): growth behind query_settle, the wait
+// for a query on another stream, the range table.  rl: the retry list of the chunk's launches.  Shared by the ray queries and
+// mcpt_query_probe_depth (csrc/mcpt_probes.hip); whatever is enqueued afterwards is closed with query_finish.
+int query_stage(mcpt_scene *sc, uint32_t chunk, hipStream_t st, mcpt_query_info &qi, RetryList &rl) {
     QueryBufs &Q = sc->query;
-    const uint32_t chunk = (uint32_t)std::min<int64_t>(n, (int64_t)sc->knobs.query_chunk);
     const bool need_retry = stack_uses_retry(sc->view.height);
     if (!Q.table_valid) build_range_table(sc->src, Q.h_ranges);
     const bool grow = Q.ray_o.n < chunk || Q.ray_d.n < chunk || Q.hit.n < chunk || (need_retry && Q.retry.cap[0] < chunk) || Q.ranges.n < Q.h_ranges.size() || !Q.done.e;
@@ -224,8 +226,41 @@ int run_query(mcpt_scene *sc, int64_t n, const mcpt_ray_buffers &rays, const mcp
         HIP_TRY(hipMemcpy(Q.ranges.p, Q.h_ranges.data(), Q.h_ranges.size() * sizeof(int32_t), hipMemcpyHostToDevice));
         Q.table_valid = true;
     }
+    rl = need_retry ? Q.retry.list(0) : RetryList{nullptr, nullptr, nullptr, 0u};
+    return MCPT_OK;
+}
+
+// Records QueryBufs::done behind what a call enqueued on st since query_stage, and reports the staging's size.
+int query_finish(mcpt_scene *sc, hipStream_t st, mcpt_query_info &qi) {
+    QueryBufs &Q = sc->query;
+    const hipError_t le = hipGetLastError();
+    // behind the kernels even when a launch failed: whatever was enqueued still reads the scene
+    const hipError_t re = hipEventRecord(Q.done, st);
+    if (re == hipSuccess) {
+        Q.pending = true;
+        Q.last_stream = st;
+    }
+    HIP_TRY(le);
+    HIP_TRY(re);
+    qi.staged_bytes = (int64_t)(Q.ray_o.bytes() + Q.ray_d.bytes() + Q.hit.bytes() + Q.ranges.bytes() + Q.retry.items[0].bytes() + Q.retry.ctl.bytes());
+    return MCPT_OK;
+}
+
+}  // namespace mcpt
+
+namespace {
+
+// Both queries after their argument checks.  occluded != nullptr: the any-hit query; else closest hits into `hits`.
+int run_query(mcpt_scene *sc, int64_t n, const mcpt_ray_buffers &rays, const mcpt_hit_buffers *hits, uint8_t *occluded, hipStream_t st, mcpt_query_info *info) {
+    mcpt_query_info qi;
+    std::memset(&qi, 0, sizeof qi);
+    HIP_TRY(hipSetDevice(sc->device));
+    QueryBufs &Q = sc->query;
+    const uint32_t chunk = (uint32_t)std::min<int64_t>(n, (int64_t)sc->knobs.query_chunk);
+    RetryList rl;
+    const int sc_rc = query_stage(sc, chunk, st, qi, rl);
+    if (sc_rc != MCPT_OK) return sc_rc;
     const int32_t n_ranges = (int32_t)(Q.h_ranges.size() / 2);
-    const RetryList rl = need_retry ? Q.retry.list(0) : RetryList{nullptr, nullptr, nullptr, 0u};
     for (int64_t base = 0; base < n; base += chunk) {
         const uint32_t m = (uint32_t)std::min<int64_t>(chunk, n - base);
         launch_query_pack(m, rays.origins + 3 * base, rays.dirs + 3 * base, rays.tmax ? rays.tmax + base : nullptr, Q.ray_o.p, Q.ray_d.p, st);
@@ -240,16 +275,8 @@ int run_query(mcpt_scene *sc, int64_t n, const mcpt_ray_buffers &rays, const mcp
         }
         qi.launches++;
     }
-    const hipError_t le = hipGetLastError();
-    // behind the kernels even when a launch failed: whatever was enqueued still reads the scene
-    const hipError_t re = hipEventRecord(Q.done, st);
-    if (re == hipSuccess) {
-        Q.pending = true;
-        Q.last_stream = st;
-    }
-    HIP_TRY(le);
-    HIP_TRY(re);
-    qi.staged_bytes = (int64_t)(Q.ray_o.bytes() + Q.ray_d.bytes() + Q.hit.bytes() + Q.ranges.bytes() + Q.retry.items[0].bytes() + Q.retry.ctl.bytes());
+    const int fr = query_finish(sc, st, qi);
+    if (fr != MCPT_OK) return fr;
     if (info) *info = qi;
     return MCPT_OK;
 }

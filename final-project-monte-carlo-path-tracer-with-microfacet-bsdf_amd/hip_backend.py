@@ -41,6 +41,8 @@ EXPORTS = ["mcpt_scene_create", "mcpt_scene_destroy", "mcpt_render", "mcpt_rende
            "mcpt_lightmap_texels", "mcpt_lightmap_scatter", "mcpt_bake_lightmap", "mcpt_lightmap_texels_host", "mcpt_lightmap_dilate_host",
            "mcpt_query_probes", "mcpt_probe_rays", "mcpt_probe_shade", "mcpt_bake_probe_grid", "mcpt_scene_probe_buffers",
            "mcpt_sh_basis_host", "mcpt_sh_irradiance_host", "mcpt_probe_grid_points_host", "mcpt_probe_shade_host",
+           "mcpt_query_probe_depth", "mcpt_probe_shade_visible", "mcpt_bake_probe_volume",
+           "mcpt_probe_depth_dirs_host", "mcpt_probe_depth_texel_host", "mcpt_probe_depth_fold_host", "mcpt_probe_shade_visible_host",
            "mcpt_group_create", "mcpt_group_render", "mcpt_group_size", "mcpt_group_get_info", "mcpt_group_scene", "mcpt_group_destroy", "mcpt_group_last_error",
            "mcpt_last_error", "mcpt_version"]
 
@@ -504,6 +506,47 @@ def _probe_rows(who, what, v, width, n=None):
     return b[0], b[1][0]
 
 
+class ProbeDepthParams(C.Structure):
+    _fields_ = [("seed", C.c_uint32), ("spp", C.c_int32), ("sample_offset", C.c_int32), ("accumulate", C.c_int32), ("max_distance", C.c_float),
+                ("reserved", C.c_int32 * 3)]
+
+
+class ProbeVisibility(C.Structure):
+    _fields_ = [("normal_bias", C.c_float), ("backface_max", C.c_float), ("reserved", C.c_int32 * 2)]
+
+
+PROBE_DEPTH_RES = 8  # MCPT_PROBE_DEPTH_RES
+PROBE_DEPTH_ROW = PROBE_DEPTH_RES * PROBE_DEPTH_RES * 3  # floats of moments per probe
+
+
+def _probe_depth_params(who, spp, max_distance, seed=1, sample_offset=0, accumulate=0):
+    """mcpt_probe_depth_params; the library's refusals that depend on the parameters alone are made here as well."""
+    spp, sample_offset, accumulate = int(spp), int(sample_offset), int(bool(accumulate))
+    if spp <= 0 or sample_offset < 0 or sample_offset + spp > 2 ** 31 - 1:
+        raise ValueError("%s: spp is positive, sample_offset >= 0 and sample_offset + spp at most 2^31 - 1, not %d and %d" % (who, spp, sample_offset))
+    md = np.float32(max_distance)
+    if not (md > 0 and np.isfinite(md)):
+        raise ValueError("%s: max_distance is positive and finite, not %r" % (who, max_distance))
+    return ProbeDepthParams(int(seed) & 0xffffffff, spp, sample_offset, accumulate, float(md), (C.c_int32 * 3)(0, 0, 0))
+
+
+def _probe_visibility(who, normal_bias, backface_max):
+    nb, bm = np.float32(normal_bias), np.float32(backface_max)
+    if not (nb >= 0 and np.isfinite(nb) and bm >= 0 and np.isfinite(bm)):
+        raise ValueError("%s: normal_bias and backface_max are finite and not negative, not %r and %r" % (who, normal_bias, backface_max))
+    return ProbeVisibility(float(nb), float(bm), (C.c_int32 * 2)(0, 0))
+
+
+def _probe_counts(who, what, v, n):
+    """The device address of an int32, C-contiguous (n, 2) device buffer."""
+    b = _device_buffer(v, who, what, ("<i4", "=i4"), "int32")
+    if b is None:
+        raise ValueError("%s: %s is a buffer in device memory (__cuda_array_interface__, or data_ptr() and is_cuda)" % (who, what))
+    if b[1] != (n, 2):
+        raise ValueError("%s: %s has shape (%d, 2), not %s" % (who, what, n, b[1]))
+    return b[0]
+
+
 def _is_torch(*vs):
     return all(hasattr(v, "data_ptr") and getattr(v, "is_cuda", False) for v in vs)
 
@@ -713,6 +756,20 @@ def lib(path=None):
         L.mcpt_probe_grid_points_host.argtypes = [C.POINTER(ProbeGrid), C.c_void_p]
         L.mcpt_probe_shade_host.restype = C.c_int
         L.mcpt_probe_shade_host.argtypes = [C.POINTER(ProbeGrid), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.mcpt_query_probe_depth.restype = C.c_int
+        L.mcpt_query_probe_depth.argtypes = [C.c_void_p, C.POINTER(ProbeDepthParams), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(QueryInfo)]
+        L.mcpt_probe_shade_visible.restype = C.c_int
+        L.mcpt_probe_shade_visible.argtypes = [C.c_void_p, C.POINTER(ProbeGrid), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(ProbeVisibility), C.c_int64] + [C.c_void_p] * 5
+        L.mcpt_bake_probe_volume.restype = C.c_int
+        L.mcpt_bake_probe_volume.argtypes = [C.c_void_p, C.POINTER(ProbeGrid), C.POINTER(Params), C.POINTER(ProbeDepthParams)] + [C.c_void_p] * 4 + [C.POINTER(Stats)]
+        L.mcpt_probe_depth_dirs_host.restype = C.c_int
+        L.mcpt_probe_depth_dirs_host.argtypes = [C.c_void_p]
+        L.mcpt_probe_depth_texel_host.restype = C.c_int
+        L.mcpt_probe_depth_texel_host.argtypes = [C.c_int64, C.c_void_p, C.c_void_p]
+        L.mcpt_probe_depth_fold_host.restype = C.c_int
+        L.mcpt_probe_depth_fold_host.argtypes = [C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+        L.mcpt_probe_shade_visible_host.restype = C.c_int
+        L.mcpt_probe_shade_visible_host.argtypes = [C.POINTER(ProbeGrid), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(ProbeVisibility), C.c_int64] + [C.c_void_p] * 4
         L.mcpt_lightmap_texels.restype = C.c_int
         L.mcpt_lightmap_texels.argtypes = [C.c_void_p, C.POINTER(LightmapDesc), C.POINTER(LightmapTexelsOut), C.POINTER(C.c_int64), C.c_void_p]
         L.mcpt_lightmap_scatter.restype = C.c_int
@@ -965,6 +1022,65 @@ def probe_shade(origin, spacing, dims, sh, points, normals):
     out = np.zeros((len(p), 3), np.float32)
     _check(lib().mcpt_probe_shade_host(C.byref(g), _ptr(L), len(p), _ptr(p), _ptr(nr), _ptr(out)))
     return out
+
+
+def probe_depth_dirs():
+    """mcpt_probe_depth_dirs_host (host only): the unit directions of the 64 texels of a probe's depth map -> (64, 3) float32."""
+    out = np.zeros((PROBE_DEPTH_RES * PROBE_DEPTH_RES, 3), np.float32)
+    _check(lib().mcpt_probe_depth_dirs_host(_ptr(out)))
+    return out
+
+
+def probe_depth_texel(v):
+    """mcpt_probe_depth_texel_host (host only): the nearest depth-map texel of vectors (n, 3) -> (n,) int32."""
+    v = np.ascontiguousarray(v, dtype=np.float32).reshape(-1, 3)
+    out = np.zeros(len(v), np.int32)
+    _check(lib().mcpt_probe_depth_texel_host(len(v), _ptr(v), _ptr(out)))
+    return out
+
+
+def probe_depth_fold(dirs, r, backfacing, moments=None, counts=None):
+    """mcpt_probe_depth_fold_host (host only): the fold of include/mcpt.h over given samples -- dirs (n, spp, 3), r (n, spp), backfacing
+    (n, spp) -> (moments (n, 192) float32, counts (n, 2) int32).  With moments and counts (both or neither) the fold continues them
+    (accumulate = 1); the inputs are not changed."""
+    d = np.ascontiguousarray(dirs, dtype=np.float32)
+    if d.ndim != 3 or d.shape[2] != 3 or d.shape[1] < 1:
+        raise ValueError("probe_depth_fold: dirs has shape (n, spp, 3) with spp >= 1, not %s" % (d.shape,))
+    n, spp = d.shape[0], d.shape[1]
+    rr = np.ascontiguousarray(r, dtype=np.float32)
+    bf = np.ascontiguousarray(np.asarray(backfacing) != 0, dtype=np.uint8)
+    if rr.shape != (n, spp) or bf.shape != (n, spp):
+        raise ValueError("probe_depth_fold: r and backfacing have shape (%d, %d), not %s and %s" % (n, spp, rr.shape, bf.shape))
+    if (moments is None) != (counts is None):
+        raise ValueError("probe_depth_fold: moments and counts come together")
+    acc = moments is not None
+    m = np.array(moments, dtype=np.float32).reshape(-1, PROBE_DEPTH_ROW) if acc else np.zeros((n, PROBE_DEPTH_ROW), np.float32)
+    c = np.array(counts, dtype=np.int32).reshape(-1, 2) if acc else np.zeros((n, 2), np.int32)
+    if len(m) != n or len(c) != n:
+        raise ValueError("probe_depth_fold: moments has shape (%d, %d) and counts (%d, 2)" % (n, PROBE_DEPTH_ROW, n))
+    m, c = np.ascontiguousarray(m), np.ascontiguousarray(c)
+    _check(lib().mcpt_probe_depth_fold_host(n, spp, _ptr(d), _ptr(rr), _ptr(bf), 1 if acc else 0, _ptr(m), _ptr(c)))
+    return m, c
+
+
+def probe_shade_visible(origin, spacing, dims, sh, moments, counts, points, normals, normal_bias=0.0, backface_max=0.25, weight=False):
+    """mcpt_probe_shade_visible_host (host only): the occlusion-aware grid lookup of include/mcpt.h -> (n, 3) float32, or (that, the
+    summed weights A (n,)) with weight=True.  sh (probes, 27), moments (probes, 192), counts (probes, 2) int32."""
+    who = "probe_shade_visible"
+    g, m = _probe_grid(who, origin, spacing, dims)
+    o = _probe_visibility(who, normal_bias, backface_max)
+    p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+    nr = np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 3)
+    L = np.ascontiguousarray(sh, dtype=np.float32)
+    M = np.ascontiguousarray(moments, dtype=np.float32)
+    cn = np.ascontiguousarray(counts, dtype=np.int32)
+    if L.shape != (m, 27) or M.shape != (m, PROBE_DEPTH_ROW) or cn.shape != (m, 2) or len(nr) != len(p) or m > (2 ** 31 - 1) // PROBE_DEPTH_ROW:
+        raise ValueError("%s: sh, moments and counts have shape (%d, 27), (%d, %d) and (%d, 2), with at most (2^31 - 1) / 192 probes, and there is "
+                         "one normal per point, not %s, %s, %s, %d and %d" % (who, m, m, PROBE_DEPTH_ROW, m, L.shape, M.shape, cn.shape, len(nr), len(p)))
+    out = np.zeros((len(p), 3), np.float32)
+    wt = np.zeros(len(p), np.float32)
+    _check(lib().mcpt_probe_shade_visible_host(C.byref(g), _ptr(L), _ptr(M), _ptr(cn), C.byref(o), len(p), _ptr(p), _ptr(nr), _ptr(out), _ptr(wt)))
+    return (out, wt) if weight else out
 
 
 def cull_bound(camera, root_min, root_max, library=None):
@@ -1887,6 +2003,100 @@ class HipScene:
         st = Stats()
         _check(self.L.mcpt_bake_probe_grid(self.h, C.byref(g), C.byref(p), C.c_void_p(ps or 0), C.c_void_p(int(stream or 0)), C.byref(st)), L=self.L)
         return out, st
+
+    def query_probe_depth(self, origins, spp, max_distance, seed=1, sample_offset=0, accumulate=0, out=None, stream=None):
+        """mcpt_query_probe_depth: the depth maps of probes at points (n, 3) in the memory of the scene's device -> (moments (n, 192)
+        float32, counts (n, 2) int32, mcpt_query_info as a dict): per probe and texel of the 8 x 8 octahedral map the sums (W, S1, S2) of
+        include/mcpt.h over the first rays probe_rays gives, and per probe its samples and how many of them hit a back face.  out: a dict
+        with "moments" and "counts" device buffers (required with accumulate), or None when origins is a torch tensor.  Enqueued on
+        `stream` without a synchronisation, through the staging buffers of the ray queries."""
+        who = "query_probe_depth"
+        po, n = _probe_rows(who, "origins", origins, 3)
+        if n > (2 ** 31 - 1) // PROBE_DEPTH_ROW:
+            raise ValueError("%s: at most (2^31 - 1) / 192 probes, not %d" % (who, n))
+        p = _probe_depth_params(who, spp, max_distance, seed, sample_offset, accumulate)
+        if out is None:
+            if not _is_torch(origins):
+                raise ValueError("%s: out is required unless origins is a torch tensor" % who)
+            if p.accumulate:
+                raise ValueError("%s: accumulate continues the buffers given in out" % who)
+            import torch
+            out = {"moments": torch.empty((n, PROBE_DEPTH_ROW), dtype=torch.float32, device=origins.device),
+                   "counts": torch.empty((n, 2), dtype=torch.int32, device=origins.device)}
+            if stream is None:
+                stream = torch.cuda.current_stream(origins.device).cuda_stream
+        for w in ("moments", "counts"):
+            if w not in out:
+                raise ValueError("%s: out has no buffer for %r" % (who, w))
+        pm = _probe_rows(who, "out['moments']", out["moments"], PROBE_DEPTH_ROW, n)[0]
+        pn = _probe_counts(who, "out['counts']", out["counts"], n)
+        info = QueryInfo()
+        _check(self.L.mcpt_query_probe_depth(self.h, C.byref(p), n, C.c_void_p(po or 0), C.c_void_p(pm or 0), C.c_void_p(pn or 0),
+                                             C.c_void_p(int(stream or 0)), C.byref(info)), L=self.L)
+        return out["moments"], out["counts"], info.as_dict()
+
+    def probe_shade_visible(self, origin, spacing, dims, sh, moments, counts, points, normals, normal_bias=0.0, backface_max=0.25, weight=None,
+                            out=None, stream=None):
+        """mcpt_probe_shade_visible: the occlusion-aware grid lookup of include/mcpt.h on the device, E / pi at points (n, 3) for normals
+        (n, 3) from the grid's coefficients sh (probes, 27), depth moments (probes, 192) and counts (probes, 2) -> (n, 3) float32 device
+        buffer.  weight: an optional float32 (n,) device buffer for the summed weights A.  All are device buffers; out may be None with
+        torch inputs.  Enqueued on `stream` without a synchronisation."""
+        who = "probe_shade_visible"
+        g, m = _probe_grid(who, origin, spacing, dims)
+        if m > (2 ** 31 - 1) // PROBE_DEPTH_ROW:
+            raise ValueError("%s: at most (2^31 - 1) / 192 probes, not %d" % (who, m))
+        o = _probe_visibility(who, normal_bias, backface_max)
+        ps = _probe_rows(who, "sh", sh, 27, m)[0]
+        pm = _probe_rows(who, "moments", moments, PROBE_DEPTH_ROW, m)[0]
+        pc = _probe_counts(who, "counts", counts, m)
+        pp, n = _probe_rows(who, "points", points, 3)
+        pn = _probe_rows(who, "normals", normals, 3, n)[0]
+        pw = 0
+        if weight is not None:
+            b = _device_buffer(weight, who, "weight")
+            if b is None or b[1] != (n,):
+                raise ValueError("%s: weight is a float32 device buffer of shape (%d,)" % (who, n))
+            pw = b[0]
+        if out is None:
+            if not _is_torch(sh, moments, counts, points, normals):
+                raise ValueError("%s: out is required unless the inputs are torch tensors" % who)
+            import torch
+            out = torch.empty((n, 3), dtype=torch.float32, device=points.device)
+            if stream is None:
+                stream = torch.cuda.current_stream(points.device).cuda_stream
+        pout = _probe_rows(who, "out", out, 3, n)[0]
+        _check(self.L.mcpt_probe_shade_visible(self.h, C.byref(g), C.c_void_p(ps or 0), C.c_void_p(pm or 0), C.c_void_p(pc or 0), C.byref(o), n,
+                                               C.c_void_p(pp or 0), C.c_void_p(pn or 0), C.c_void_p(pout or 0), C.c_void_p(pw or 0),
+                                               C.c_void_p(int(stream or 0))), L=self.L)
+        return out
+
+    def bake_probe_volume(self, origin, spacing, dims, depth_spp, max_distance, depth_seed=1, out=None, stream=None, **params):
+        """mcpt_bake_probe_volume: bake_probe_grid, then query_probe_depth (depth_spp samples, max_distance, depth_seed) on the same
+        scene-owned points -> (sh (probes, 27), moments (probes, 192), counts (probes, 2), Stats).  out: a dict with "sh", "moments" and
+        "counts" device buffers; None: torch tensors on the scene's device."""
+        who = "bake_probe_volume"
+        g, m = _probe_grid(who, origin, spacing, dims)
+        if m > (2 ** 31 - 1) // PROBE_DEPTH_ROW:
+            raise ValueError("%s: at most (2^31 - 1) / 192 probes, not %d" % (who, m))
+        dp = _probe_depth_params(who, depth_spp, max_distance, depth_seed)
+        if out is None:
+            import torch
+            dev = self._torch_device()
+            out = {"sh": torch.empty((m, 27), dtype=torch.float32, device=dev), "moments": torch.empty((m, PROBE_DEPTH_ROW), dtype=torch.float32, device=dev),
+                   "counts": torch.empty((m, 2), dtype=torch.int32, device=dev)}
+            if stream is None:
+                stream = torch.cuda.current_stream(dev).cuda_stream
+        for w in ("sh", "moments", "counts"):
+            if w not in out:
+                raise ValueError("%s: out has no buffer for %r" % (who, w))
+        ps = _probe_rows(who, "out['sh']", out["sh"], 27, m)[0]
+        pm = _probe_rows(who, "out['moments']", out["moments"], PROBE_DEPTH_ROW, m)[0]
+        pn = _probe_counts(who, "out['counts']", out["counts"], m)
+        p = self.params(**params)
+        st = Stats()
+        _check(self.L.mcpt_bake_probe_volume(self.h, C.byref(g), C.byref(p), C.byref(dp), C.c_void_p(ps or 0), C.c_void_p(pm or 0), C.c_void_p(pn or 0),
+                                             C.c_void_p(int(stream or 0)), C.byref(st)), L=self.L)
+        return out["sh"], out["moments"], out["counts"], st
 
     def probe_buffers(self):
         """mcpt_scene_probe_buffers -> (floats the scene-owned probe buffers hold, how often one of them was (re)allocated)."""

@@ -1524,6 +1524,76 @@ int mcpt_sh_irradiance_host(int64_t n, const float *sh /* n*27 */, const float *
 int mcpt_probe_grid_points_host(const mcpt_probe_grid *grid, float *points /* probes*3 */);
 int mcpt_probe_shade_host(const mcpt_probe_grid *grid, const float *sh, int64_t n, const float *points, const float *normals, float *out);
 
+/* ---- Probe visibility: a small octahedral map of distance moments per probe, a Chebyshev visibility weight at lookup and a back-face
+ * count that retires buried probes, so that the irradiance volume above works next to walls and around objects (csrc/mcpt_probe_depth.h
+ * states the rule once, for the host and the device; csrc/mcpt_probes.hip holds the kernels).  Float32 in the written order, no FMA;
+ * only + - * /, sqrtf, fabsf, fminf, fmaxf, floorf.  dot(a, b) = a.x b.x + (a.y b.y + a.z b.z); sgn(v) = v >= 0 ? 1 : -1.
+ *
+ * Depth map: MCPT_PROBE_DEPTH_RES x MCPT_PROBE_DEPTH_RES = 8 x 8 texels per probe, texel j = 8 ty + tx.
+ * Texel direction c_j: ox = ((float)tx + 0.5f) * 0.25f - 1.0f, oy likewise from ty; az = (1 - |ox|) - |oy|; if az < 0:
+ * (x, y) = ((1 - |oy|) sgn(ox), (1 - |ox|) sgn(oy)), else (x, y) = (ox, oy); c = (x, y, az), each divided by sqrtf((x x + y y) + az az).
+ * Texel of a vector v (nearest texel; v need not be unit): s = (|vx| + |vy|) + |vz|; if s is zero or not finite (not s > 0, or
+ * s > FLT_MAX, or NaN) the texel is 0; else px = vx / s, py = vy / s; if vz < 0: (px, py) = ((1 - |py|) sgn(px), (1 - |px|) sgn(py))
+ * from the old values; tx = clamp((int)floorf((px + 1) * 4), 0, 7), ty likewise from py.
+ * Sample: d(i, k) is the direction mcpt_probe_rays gives for (seed, probe i, absolute sample sample_offset + k), t(i, k) the double
+ * mcpt_intersect gives for that ray from origins[i], ng the normal mcpt_query_closest reports for the hit;
+ * r = hit ? fminf((float)t, max_distance) : max_distance; the sample is back-facing iff it is a hit and dot(ng, d) > 0.
+ * Fold, per (probe i, texel j): w = fmaxf(dot(c_j, d), 0), then w = w * w five times (cos^32).  moments[(64 i + j) * 3 + 0..2] =
+ * (W, S1, S2): acc = accumulate ? existing : 0; for k in sample order: W = W + w; S1 = S1 + w * r; S2 = S2 + w * (r * r).
+ * counts[2i] (+)= spp, counts[2i + 1] (+)= the back-facing samples (int32; with accumulate = 0 both are overwritten).  One call over
+ * a + b samples equals a call over a followed by one over b with sample_offset = a, accumulate = 1, bit for bit.
+ * Lookup of point p, unit normal n with {normal_bias, backface_max}: cell and axis weights from p exactly as in mcpt_probe_shade;
+ * q = p + normal_bias * n per component.  For the corners in the order (dz, dy, dx) = 000 .. 111: wt = (wz wy) wx; the corner's probe i
+ * sits at P; it is dead iff counts[2i] > 0 && (float)counts[2i + 1] > backface_max * (float)counts[2i], and a dead probe has a = 0;
+ * else u = P - p, lu = sqrtf(dot(u, u)), cosn = lu > 0 ? dot(u, n) / lu : 1, h = (cosn + 1) * 0.5f, wb = h * h + 0.2f; v = q - P,
+ * dist = sqrtf(dot(v, v)), (W, S1, S2) of the texel of v; ch = 1; if W > 0: m = S1 / W, m2 = S2 / W, var = fabsf(m2 - m * m), and if
+ * dist > m: dd = dist - m, den = var + dd * dd, ch = den > 0 ? var / den : 0, ch = (ch * ch) * ch; a = (wt * wb) * ch.  A = the sum of
+ * a in corner order from 0.  If A > 0: every coefficient is b = sum of a_c * L_c in corner order from 0, and out[ch] =
+ * mcpt_sh_irradiance_host(b, n)[ch] / A; otherwise (every corner dead or invisible, or A not a number) out is mcpt_probe_shade's value
+ * for the same inputs.  weight_out[i] = A (nullable).
+ *
+ * mcpt_query_probe_depth is enqueued on hip_stream without a synchronisation, through the staging buffers of the ray queries and under
+ * their protocol (mcpt_query_closest): info->grew is 0 in the steady state; rays are staged in chunks of at most MCPT_QUERY_CHUNK, whole
+ * probes or whole 64-sample blocks of one probe, and the result does not depend on it.  It sees the live scene as it is now.
+ * mcpt_probe_shade_visible is enqueued like mcpt_probe_shade.  mcpt_bake_probe_volume runs mcpt_bake_probe_grid, then
+ * mcpt_query_probe_depth on the same scene-owned points, and equals the two bit for bit.
+ * MCPT_ERR_ARG before any device work: a null scene, params, options or output; n < 0 or n > (2^31 - 1) / 192 (a grid: more probes than
+ * that); spp <= 0, sample_offset < 0, or sample_offset + spp > 2^31 - 1 (a progressive caller's sample_offset is the count the probe
+ * already has, so this is where counts would stop fitting an int32; the host fold checks the counts themselves); accumulate other than 0
+ * or 1; max_distance not positive and finite; normal_bias or backface_max negative or not finite; a non-zero reserved word; a pointer
+ * that is not memory of the scene's device; the grid refusals of mcpt_probe_shade.  n == 0 is a valid no-op.  No mcpt_group_* form. */
+#define MCPT_PROBE_DEPTH_RES 8
+typedef struct {
+    uint32_t seed;
+    int32_t spp, sample_offset, accumulate;
+    float max_distance;
+    int32_t reserved[3]; /* must be 0 */
+} mcpt_probe_depth_params; /* 32 bytes */
+typedef struct {
+    float normal_bias, backface_max;
+    int32_t reserved[2]; /* must be 0 */
+} mcpt_probe_visibility; /* 16 bytes */
+int mcpt_query_probe_depth(mcpt_scene *scene, const mcpt_probe_depth_params *params, int64_t n, const float *origins /* n*3, device */,
+                           float *moments /* n*192, device */, int32_t *counts /* n*2, device */, void *hip_stream,
+                           mcpt_query_info *info /* nullable */);
+int mcpt_probe_shade_visible(mcpt_scene *scene, const mcpt_probe_grid *grid, const float *sh /* probes*27, device */,
+                             const float *moments /* probes*192, device */, const int32_t *counts /* probes*2, device */,
+                             const mcpt_probe_visibility *opts, int64_t n, const float *points /* n*3, device */,
+                             const float *normals /* n*3, device */, float *out /* n*3, device */, float *weight_out /* n, device, nullable */,
+                             void *hip_stream);
+int mcpt_bake_probe_volume(mcpt_scene *scene, const mcpt_probe_grid *grid, const mcpt_params *params, const mcpt_probe_depth_params *depth_params,
+                           float *sh /* probes*27, device */, float *moments /* probes*192, device */, int32_t *counts /* probes*2, device */,
+                           void *hip_stream, mcpt_stats *stats /* nullable */);
+/* Host only, no GPU needed: csrc/mcpt_probe_depth.h compiled for the CPU.  mcpt_probe_depth_fold_host folds given samples: dirs n*spp*3,
+ * r n*spp, backfacing n*spp (non-zero: back-facing), probe-major in sample order. */
+int mcpt_probe_depth_dirs_host(float *dirs /* 64*3 */);
+int mcpt_probe_depth_texel_host(int64_t n, const float *v /* n*3 */, int32_t *texel /* n */);
+int mcpt_probe_depth_fold_host(int64_t n, int32_t spp, const float *dirs, const float *r, const uint8_t *backfacing, int32_t accumulate,
+                               float *moments /* n*192 */, int32_t *counts /* n*2 */);
+int mcpt_probe_shade_visible_host(const mcpt_probe_grid *grid, const float *sh, const float *moments, const int32_t *counts,
+                                  const mcpt_probe_visibility *opts, int64_t n, const float *points, const float *normals, float *out,
+                                  float *weight_out /* nullable */);
+
 const char *mcpt_last_error(void);
 const char *mcpt_version(void);
 

@@ -1,10 +1,12 @@
 """A small probe grid in the Cornell demo scene against hemisphere sensors: what the SH-9 truncation plus the grid's trilinear interpolation
 cost.  The command behind the "Light probes" figures of DESIGN.md section 6c.
-python tools/probes.py [--dims 5 4 5] [--spp 16384] [--sensor-spp 262144] [--seed 3]
+python tools/probes.py [--dims 5 4 5] [--spp 16384] [--sensor-spp 262144] [--seed 3] [--visibility [--depth-spp 4096]]
 The grid spans the box's interior.  At a handful of (point, normal) pairs in free space the tool prints the lookup (probe_shade on the
 baked coefficients) next to query_radiance(kind="hemisphere") at the same point and normal, with the sensor's reported standard error:
 both are E / pi.  Also printed: the lookup AT a probe against a sensor there (truncation alone, no interpolation), and the wall times of
-the bake and of the lookup.  Device buffers come from the HIP runtime the library is linked to, through ctypes; torch is not needed."""
+the bake and of the lookup.  --visibility: the probes' depth maps are made as well (query_probe_depth at the grid's points) and the
+occlusion-aware lookup (probe_shade_visible) is printed and summarised next to the plain one; without the flag the output is unchanged.
+Device buffers come from the HIP runtime the library is linked to, through ctypes; torch is not needed."""
 import argparse
 import sys
 import time
@@ -25,6 +27,9 @@ def main():
     ap.add_argument("--spp", type=int, default=16384)
     ap.add_argument("--sensor-spp", type=int, default=262144)
     ap.add_argument("--seed", type=int, default=3)
+    ap.add_argument("--visibility", action="store_true", help="also the occlusion-aware lookup (probe depth maps, probe_shade_visible)")
+    ap.add_argument("--depth-spp", type=int, default=4096, help="samples per probe of the depth maps (--visibility)")
+    ap.add_argument("--normal-bias", type=float, default=2.0, help="normal_bias of the occlusion-aware lookup, in scene units (--visibility)")
     args = ap.parse_args()
     pkg = mcpt_loader.load()
     hip = pkg.hip_backend
@@ -56,6 +61,22 @@ def main():
     hs.probe_shade(origin, spacing, dims, sh, dp, dn, out=out)
     look = out.get()
     t_look = (time.perf_counter() - t0) * 1e3
+    if args.visibility:
+        max_distance = 1.5 * float(np.linalg.norm(spacing))
+        dpts = Dev(rt, pts)
+        dm = {"moments": Dev(rt, shape=(m, hip.PROBE_DEPTH_ROW)), "counts": Dev(rt, shape=(m, 2), dtype=np.int32)}
+        t0 = time.perf_counter()
+        _, _, qi = hs.query_probe_depth(dpts, args.depth_spp, max_distance, seed=args.seed + 2, out=dm)
+        counts = dm["counts"].get()
+        t_depth = (time.perf_counter() - t0) * 1e3
+        vout = Dev(rt, shape=(len(p), 3))
+        t0 = time.perf_counter()
+        hs.probe_shade_visible(origin, spacing, dims, sh, dm["moments"], dm["counts"], dp, dn, normal_bias=args.normal_bias, backface_max=0.25, out=vout)
+        vlook = vout.get()
+        t_vlook = (time.perf_counter() - t0) * 1e3
+        print("visibility: depth maps at %d spp, max_distance %.1f: %.1f ms with the read-back (%d launches); %d of %d probes have more than a quarter "
+              "of their samples back-facing; occlusion-aware lookup of %d pairs (normal_bias %.1f): %.2f ms"
+              % (args.depth_spp, max_distance, t_depth, qi["launches"], int((counts[:, 1] > 0.25 * counts[:, 0]).sum()), m, len(p), args.normal_bias, t_vlook))
     so = {"radiance": Dev(rt, shape=(len(p), 3)), "variance": Dev(rt, shape=(len(p), 3))}
     hs.query_radiance(dp, dn, kind="hemisphere", variance=True, out=so, spp=args.sensor_spp, seed=args.seed + 1)
     ref, se = so["radiance"].get(), np.sqrt(so["variance"].get())
@@ -74,6 +95,16 @@ def main():
                                                           se[i].mean() / max(lum_r, 1e-12), tag))
     rel_all = np.array(rel_all)
     k = len(P) * len(N)
+    if args.visibility:
+        print("%-22s %-22s %-28s %-28s %-10s %s" % ("point", "normal", "visible lookup E/pi (rgb)", "plain lookup E/pi (rgb)", "rel. diff", "plain rel. diff"))
+        rel_vis = []
+        for i in range(len(p)):
+            lum_v, lum_r = vlook[i].mean(), ref[i].mean()
+            rel_vis.append(abs(lum_v - lum_r) / max(lum_r, 1e-12) if lum_r > 0 else np.nan)
+            print("%-22s %-22s %-28s %-28s %-10.4f %.4f" % (np.round(p[i], 1), np.round(n[i], 2), np.round(vlook[i], 4), np.round(look[i], 4), rel_vis[-1], rel_all[i]))
+        rel_vis = np.array(rel_vis)
+        print("occlusion-aware lookup, relative difference of the channel mean: interpolated pairs mean %.4f, max %.4f; at probes mean %.4f, max %.4f; "
+              "negative lookups: %d" % (np.nanmean(rel_vis[:k]), np.nanmax(rel_vis[:k]), np.nanmean(rel_vis[k:]), np.nanmax(rel_vis[k:]), int((vlook < 0).sum())))
     print("relative difference of the channel mean: interpolated pairs mean %.4f, max %.4f; at probes mean %.4f, max %.4f; negative lookups: %d"
           % (np.nanmean(rel_all[:k]), np.nanmax(rel_all[:k]), np.nanmean(rel_all[k:]), np.nanmax(rel_all[k:]), int((look < 0).sum())))
     hs.close()
