@@ -54,32 +54,11 @@ __global__ __launch_bounds__(kB) void k_aov_resolve(DevScene S, uint32_t n, cons
     const float4 o4 = ray_o[j], d4 = ray_d[j];
     const f3 ro = mk3(o4.x, o4.y, o4.z), rd = mk3(d4.x, d4.y, d4.z);
     f3 nrm;
-    f2 uv{0.f, 0.f};
-    if (prim < S.n_tri) {
-        const TriShade ts = S.tri_shade[prim];
-        nrm = mk3(ts.n[0], ts.n[1], ts.n[2]);
-        if (mat_bits & kMatTextured) {
-            double tt, u, v;
-            const Ray rr = make_ray(ro, rd);
-            if (tri_hit(S.tri_geom[prim], rr, tt, u, v)) {
-                const float a = (float)(1 - u - v), b = (float)u, c = (float)v;
-                uv.x = a * ts.t0[0] + b * ts.t1[0] + c * ts.t2[0];
-                uv.y = a * ts.t0[1] + b * ts.t1[1] + c * ts.t2[1];
-            }
-        }
-    } else {
-        const SphereRec sp = S.spheres[prim - S.n_tri];
-        const f3 p = ro + rd * (float)t;
-        nrm = normalized(p - mk3(sp.c[0], sp.c[1], sp.c[2]));
-    }
+    f2 uv;
+    hit_surface(S, prim, mat_bits, ro, rd, ro + rd * (float)t, nrm, uv);
     if (dot(nrm, rd) > 0) nrm = -nrm;
-    const MaterialRec &M = S.mats[mat_bits & kMatIndexMask];
-    float alb[3] = {1.f, 1.f, 1.f};
-    if (!(mat_bits >> 31) && (M.type == MCPT_SMOOTH_CONDUCTOR || M.type == MCPT_ROUGH_CONDUCTOR)) {
-        alb[0] = get_reflectance(M, uv, 0);
-        alb[1] = get_reflectance(M, uv, 1);
-        alb[2] = get_reflectance(M, uv, 2);
-    }
+    float alb[3];
+    hit_albedo(S.mats[mat_bits & kMatIndexMask], mat_bits, uv, alb);
     s0[j] = make_float4(alb[0], alb[1], alb[2], (float)t);
     s1[j] = make_float4(nrm.x, nrm.y, nrm.z, 1.f);
 }
@@ -122,25 +101,9 @@ __global__ __launch_bounds__(kB) void k_aov_chain(DevScene S, uint32_t n, int32_
             const f3 ro = mk3(o4.x, o4.y, o4.z), rd = mk3(d4.x, d4.y, d4.z);
             const f3 p = ro + rd * (float)t;
             f3 nrm;
-            f2 uv{0.f, 0.f};
-            if (prim < S.n_tri) {
-                const TriShade ts = S.tri_shade[prim];
-                nrm = mk3(ts.n[0], ts.n[1], ts.n[2]);
-                if (mat_bits & kMatTextured) {
-                    double tt, u, v;
-                    const Ray rr = make_ray(ro, rd);
-                    if (tri_hit(S.tri_geom[prim], rr, tt, u, v)) {
-                        const float a = (float)(1 - u - v), bb = (float)u, c = (float)v;
-                        uv.x = a * ts.t0[0] + bb * ts.t1[0] + c * ts.t2[0];
-                        uv.y = a * ts.t0[1] + bb * ts.t1[1] + c * ts.t2[1];
-                    }
-                }
-            } else {
-                const SphereRec sp = S.spheres[prim - S.n_tri];
-                nrm = normalized(p - mk3(sp.c[0], sp.c[1], sp.c[2]));
-            }
+            f2 uv;
+            hit_surface(S, prim, mat_bits, ro, rd, p, nrm, uv);
             const MaterialRec &M = S.mats[mat_bits & kMatIndexMask];
-            const bool emitter = (mat_bits >> 31) != 0;
             const bool conductor = M.type == MCPT_SMOOTH_CONDUCTOR || M.type == MCPT_ROUGH_CONDUCTOR;
             cont = chain_continues(M, mat_bits, b, max_b);
             if (cont) {  // the bounce both chain passes take (csrc/mcpt_chain.h)
@@ -150,12 +113,8 @@ __global__ __launch_bounds__(kB) void k_aov_chain(DevScene S, uint32_t n, int32_
                     for (int c = 0; c < 3; ++c) thr[c] *= mat_eval(M, wi, wo, nrm, c, uv, true);
             } else {
                 if (dot(nrm, rd) > 0) nrm = -nrm;
-                float alb[3] = {1.f, 1.f, 1.f};
-                if (!emitter && conductor) {
-                    alb[0] = get_reflectance(M, uv, 0);
-                    alb[1] = get_reflectance(M, uv, 1);
-                    alb[2] = get_reflectance(M, uv, 2);
-                }
+                float alb[3];
+                hit_albedo(M, mat_bits, uv, alb);
                 s0[j] = make_float4(thr[0] * alb[0], thr[1] * alb[1], thr[2] * alb[2], (float)tsum);
                 s1[j] = make_float4(nrm.x, nrm.y, nrm.z, 1.f);
             }

@@ -4,6 +4,7 @@
 #include "mcpt_host.h"
 #include "mcpt_adaptive.h"
 #include "mcpt_denoise.h"
+#include "mcpt_sh.h"
 #include "mcpt_temporal.h"
 
 namespace mcpt {
@@ -68,6 +69,30 @@ int check_features(const char *name, const mcpt_feature_opts *features, int32_t 
 int motion_pass(mcpt_scene *sc, const CameraConst &cc, const CameraConst &prev_cc, uint32_t seed, int32_t aov_spp, int32_t spec_depth, bool centre,
                 float4 *maps, uint64_t map_rays, float *motion_dev, hipStream_t st);
 uint64_t motion_map_rays(uint64_t n_px, int32_t aov_spp);
+
+// The probe volume a lit pass shades from: the grid and device arrays of mcpt_probe_volume after their checks.  moments null: the plain
+// lookup (sh::probe_shade), counts and the two options are then not read.
+struct LitVolume {
+    sh::Grid g;
+    const float *sh = nullptr, *moments = nullptr;
+    const int32_t *counts = nullptr;
+    float normal_bias = 0.f, backface_max = 0.f;
+};
+// The lit pass (include/mcpt.h: mcpt_render_probe_lit): lit_dev[3m ..] and, when not null, position_dev[3m ..] for every pixel of the frame,
+// queued on `st` (with spec_depth > 0 it waits for the stream once per bounce).  The chunk loop and the bounce loop of aov_pass with
+// k_lit_terminal in k_aov_chain's place, then k_lit_shade and k_lit_fold (csrc/mcpt_probes.hip).  Besides the arrays of the AOV pass a
+// chunk keeps p per sample: in the workspace's shadow queue origins (shq_o, which no feature pass touches) when they hold a chunk, else in
+// a buffer of the call's own.  lookups_dev: one device counter, cleared here, that ends as info.lookups.  Returns with the stream drained.
+int lit_pass(mcpt_scene *sc, const CameraConst &cc, uint32_t seed, int32_t aov_spp, int32_t spec_depth, bool centre, const LitVolume &vol, float *lit_dev,
+             float *position_dev, unsigned long long *lookups_dev, hipStream_t st, mcpt_lit_info &info);
+// csrc/mcpt_probes.hip.  One step of the lit pass's chains: launch_aov_chain's arguments (max_b == 0: every sample stops, the lists of the
+// next step may be null) with the three per-sample records {a or v, kind} {nf} {p} in place of the AOV pass's two.
+void launch_lit_terminal(const DevScene &S, uint32_t n, int32_t b, int32_t max_b, const float4 *ray_o, const float4 *ray_d, const uint4 *hit,
+                         const float4 *chain_in, float4 *r0, float4 *r1, float4 *r2, float4 *next_o, float4 *next_d, float4 *chain_out,
+                         uint32_t *n_next, hipStream_t st);
+// The lookup of the n samples of a chunk: r0[j].xyz = a * max(E, 0) for the samples that ended on a surface; their number is added to *lookups.
+void launch_lit_shade(const LitVolume &vol, uint32_t n, float4 *r0, const float4 *r1, const float4 *r2, unsigned long long *lookups, hipStream_t st);
+void launch_lit_fold(uint32_t p0, uint32_t n_pix, int32_t aov_spp, const float4 *r0, const float4 *r2, float *lit, float *position, hipStream_t st);
 
 // What the rounds of an adaptive frame work in (adaptive_rounds): device buffers the caller owns.  Per pixel of the frame: fb 3 floats,
 // mom 6 doubles, spp, err, stamp (1 byte), guide (nullable: the plain rule; history lengths, or with guide_max_history > 0 history weights

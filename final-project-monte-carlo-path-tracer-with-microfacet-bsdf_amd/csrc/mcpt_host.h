@@ -227,6 +227,9 @@ struct ProbeBufs {
     DevBuf<float> points;    // mcpt_bake_probe_grid: the grid's points, n*3
     DevBuf<float> radiance;  // mcpt_query_probes without a caller's radiance: the plain fold still needs a place, n*3
     int64_t allocations = 0; // how often one of them was (re)allocated (mcpt_scene_probe_buffers)
+    // mcpt_render_probe_lit: the eight-byte counter of its lookups, made by the scene's first such call.  Working storage of that call, no
+    // probe buffer: it is in neither figure of mcpt_scene_probe_buffers.
+    DevBuf<unsigned long long> lit_count;
 };
 
 // Environment knobs, read ONCE per scene in mcpt_scene_create: a render call never calls getenv.

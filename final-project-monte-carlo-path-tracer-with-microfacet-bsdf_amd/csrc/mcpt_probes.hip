@@ -16,9 +16,16 @@
 //                          the wave walks the block in sample order with (d, r) broadcast from lane s by a wave-uniform lane read, and
 //                          every lane adds to its texel's three sums in registers
 //   k_probe_shade_visible  one lane per (point, normal): pd::shade_visible
-// Every store is a plain vector store; nothing here uses atomics, LDS, scratch or inline assembly.
+// Every store is a plain vector store; nothing above uses atomics, LDS, scratch or inline assembly.
+//
+// Probe-lit frames (mcpt_render_probe_lit; lit_pass in csrc/mcpt_render.hip runs them per chunk of the AOV pass's chunk loop):
+//   k_lit_terminal  one lane per ray of a list: the chain step of k_aov_chain; a sample that stops records {v or a, kind} {nf} {p}
+//   k_lit_shade     one lane per sample: the grid lookup (plain or occlusion-aware) of a sample that ended on a surface
+//   k_lit_fold      one lane per pixel, in sample order
+// Their only atomics are integer ones, one per wave: the next list's length (as k_aov_chain) and the count of lookups.
 #include <cmath>
 
+#include "mcpt_chain.h"
 #include "mcpt_frame.h"
 #include "mcpt_host.h"
 #include "mcpt_probe_depth.h"
@@ -148,6 +155,145 @@ __global__ __launch_bounds__(kPbBlock) void k_probe_shade_visible(sh::Grid g, co
     if (weight_out) weight_out[i] = A;
 }
 
+// How a lit sample ended (r0[j].w of the lit pass's records, as bits).
+constexpr uint32_t kLitMiss = 0u, kLitEmitter = 1u, kLitSurface = 2u;
+
+// One step of the lit pass's chains: k_aov_chain (csrc/mcpt_denoise.hip) with the lit sample's records in place of the AOV record.  A
+// sample that stops writes r0[j] = {v or a, kind}, r1[j] = {nf, 0}, r2[j] = {p, 0}: for a miss and an emitter v is the sample's final
+// value, for any other hit a = thr * albedo waits for k_lit_shade.  A sample that follows a Dirac bounce (b < max_b) appends its next ray
+// and state to the next list (ballot + prefix count, one atomic per wave on n_next).
+__global__ __launch_bounds__(kPbBlock) void k_lit_terminal(DevScene S, uint32_t n, int32_t b, int32_t max_b, const float4 *__restrict__ ray_o,
+                                                         const float4 *__restrict__ ray_d, const uint4 *__restrict__ hit,
+                                                         const float4 *__restrict__ chain_in, float4 *__restrict__ r0, float4 *__restrict__ r1,
+                                                         float4 *__restrict__ r2, float4 *__restrict__ next_o, float4 *__restrict__ next_d,
+                                                         float4 *__restrict__ chain_out, uint32_t *__restrict__ n_next) {
+    const uint32_t i = blockIdx.x * kPbBlock + threadIdx.x;
+    bool cont = false;  // (no early return: every lane takes part in the ballot)
+    uint32_t j = i;
+    float thr[3] = {1.f, 1.f, 1.f};
+    f3 p2 = mk3(0, 0, 0), wi = mk3(0, 0, 1);
+    if (i < n) {
+        if (chain_in) {
+            const float4 c = chain_in[i];
+            thr[0] = c.x;
+            thr[1] = c.y;
+            thr[2] = c.z;
+            j = __float_as_uint(c.w);
+        }
+        const uint4 h = hit[i];
+        const int32_t prim = (int32_t)h.z;
+        const float4 d4 = ray_d[i];
+        const f3 rd = mk3(d4.x, d4.y, d4.z);
+        if (prim < 0) {
+            const f3 env = sample_env(S, rd);
+            r0[j] = make_float4(thr[0] * env.x, thr[1] * env.y, thr[2] * env.z, __uint_as_float(kLitMiss));
+            r1[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+            r2[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+        } else {
+            const double t = hit_t(h);
+            const uint32_t mat_bits = h.w;
+            const float4 o4 = ray_o[i];
+            const f3 ro = mk3(o4.x, o4.y, o4.z);
+            const f3 p = ro + rd * (float)t;
+            f3 nrm;
+            f2 uv;
+            hit_surface(S, prim, mat_bits, ro, rd, p, nrm, uv);
+            const MaterialRec &M = S.mats[mat_bits & kMatIndexMask];
+            cont = chain_continues(M, mat_bits, b, max_b);
+            if (cont) {  // the bounce every chain pass takes (csrc/mcpt_chain.h)
+                const f3 wo = -rd;
+                chain_bounce(M, rd, p, nrm, p2, wi);
+                if (M.type == MCPT_SMOOTH_CONDUCTOR || M.type == MCPT_ROUGH_CONDUCTOR)
+                    for (int c = 0; c < 3; ++c) thr[c] *= mat_eval(M, wi, wo, nrm, c, uv, true);
+            } else if (mat_bits >> 31) {  // Scene.cpp:102-107, at every chain depth
+                const float cs = fabsf(dot(-rd, nrm));
+                r0[j] = make_float4(thr[0] * clampf(0, 1, M.emit[0] * cs), thr[1] * clampf(0, 1, M.emit[1] * cs), thr[2] * clampf(0, 1, M.emit[2] * cs),
+                                    __uint_as_float(kLitEmitter));
+                r1[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+                r2[j] = make_float4(p.x, p.y, p.z, 0.f);
+            } else {
+                float alb[3];
+                hit_albedo(M, mat_bits, uv, alb);
+                if (dot(nrm, rd) > 0) nrm = -nrm;
+                r0[j] = make_float4(thr[0] * alb[0], thr[1] * alb[1], thr[2] * alb[2], __uint_as_float(kLitSurface));
+                r1[j] = make_float4(nrm.x, nrm.y, nrm.z, 0.f);
+                r2[j] = make_float4(p.x, p.y, p.z, 0.f);
+            }
+        }
+    }
+    const unsigned long long mask = __ballot(cont);
+    if (mask == 0ull) return;
+    uint32_t base = 0;
+    if (lane_id() == 0) base = atomicAdd(n_next, (uint32_t)__popcll(mask));
+    base = __shfl(base, 0);
+    if (cont) {
+        const uint32_t k = base + __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+        next_o[k] = make_float4(p2.x, p2.y, p2.z, 0.f);
+        next_d[k] = make_float4(wi.x, wi.y, wi.z, 0.f);
+        chain_out[k] = make_float4(thr[0], thr[1], thr[2], __uint_as_float(j));
+    }
+}
+
+// One lane per sample of a chunk: the lookup of a sample that ended on a surface, r0[j].xyz = a * max(E, 0).  VIS: pd::shade_visible,
+// else sh::probe_shade.  The surface samples of the launch are counted by ballot, one integer atomic per wave.
+template <bool VIS>
+__global__ __launch_bounds__(kPbBlock) void k_lit_shade(sh::Grid g, const float *__restrict__ coef, const float *__restrict__ moments,
+                                                      const int32_t *__restrict__ counts, float normal_bias, float backface_max, uint32_t n,
+                                                      float4 *__restrict__ r0, const float4 *__restrict__ r1, const float4 *__restrict__ r2,
+                                                      unsigned long long *__restrict__ lookups) {
+    const uint32_t j = blockIdx.x * kPbBlock + threadIdx.x;
+    bool surface = false;
+    float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (j < n) {
+        a = r0[j];
+        surface = __float_as_uint(a.w) == kLitSurface;
+    }
+    if (surface) {
+        const float4 n4 = r1[j], p4 = r2[j];
+        const float p[3] = {p4.x, p4.y, p4.z}, nf[3] = {n4.x, n4.y, n4.z};
+        float e[3];
+        if (VIS) pd::shade_visible(g, coef, moments, counts, normal_bias, backface_max, p, nf, e, nullptr);
+        else sh::probe_shade(g, coef, p, nf, e);
+        r0[j] = make_float4(a.x * fmaxf(e[0], 0.f), a.y * fmaxf(e[1], 0.f), a.z * fmaxf(e[2], 0.f), a.w);
+    }
+    const unsigned long long mask = __ballot(surface);
+    if (mask != 0ull && (threadIdx.x & 63u) == 0u) atomicAdd(lookups, (unsigned long long)__popcll(mask));
+}
+
+// One lane per pixel: the samples' values and hit points folded in sample order.
+__global__ __launch_bounds__(kPbBlock) void k_lit_fold(uint32_t p0, uint32_t n_pix, int32_t aov_spp, const float4 *__restrict__ r0,
+                                                     const float4 *__restrict__ r2, float *__restrict__ lit, float *__restrict__ position) {
+    const uint32_t i = blockIdx.x * kPbBlock + threadIdx.x;
+    if (i >= n_pix) return;
+    const float fn = (float)aov_spp;
+    float v0 = 0.f, v1 = 0.f, v2 = 0.f, q0 = 0.f, q1 = 0.f, q2 = 0.f;
+    int32_t hits = 0;
+    const size_t base = (size_t)i * aov_spp;
+    for (int32_t k = 0; k < aov_spp; ++k) {
+        const float4 v = r0[base + k];
+        v0 += v.x / fn;
+        v1 += v.y / fn;
+        v2 += v.z / fn;
+        if (__float_as_uint(v.w) != kLitMiss) {
+            const float4 q = r2[base + k];
+            q0 += q.x;
+            q1 += q.y;
+            q2 += q.z;
+            ++hits;
+        }
+    }
+    const size_t m = 3 * (size_t)(p0 + i);
+    lit[m] = v0;
+    lit[m + 1] = v1;
+    lit[m + 2] = v2;
+    if (position) {
+        const float fh = (float)hits;
+        position[m] = hits > 0 ? q0 / fh : 0.f;
+        position[m + 1] = hits > 0 ? q1 / fh : 0.f;
+        position[m + 2] = hits > 0 ? q2 / fh : 0.f;
+    }
+}
+
 inline uint32_t probe_blocks(uint32_t n) { return (n + kPbBlock - 1) / kPbBlock; }
 
 // The grid of a call, or the reason it is refused.
@@ -208,9 +354,80 @@ int check_visibility(const std::string &w, const mcpt_probe_visibility *o) {
 }
 
 }  // namespace
+
+void launch_lit_terminal(const DevScene &S, uint32_t n, int32_t b, int32_t max_b, const float4 *ray_o, const float4 *ray_d, const uint4 *hit,
+                         const float4 *chain_in, float4 *r0, float4 *r1, float4 *r2, float4 *next_o, float4 *next_d, float4 *chain_out,
+                         uint32_t *n_next, hipStream_t st) {
+    if (n == 0) return;
+    hipLaunchKernelGGL(k_lit_terminal, dim3(probe_blocks(n)), dim3(kPbBlock), 0, st, S, n, b, max_b, ray_o, ray_d, hit, chain_in, r0, r1, r2, next_o, next_d,
+                       chain_out, n_next);
+}
+
+void launch_lit_shade(const LitVolume &vol, uint32_t n, float4 *r0, const float4 *r1, const float4 *r2, unsigned long long *lookups, hipStream_t st) {
+    if (n == 0) return;
+    if (vol.moments)
+        hipLaunchKernelGGL(k_lit_shade<true>, dim3(probe_blocks(n)), dim3(kPbBlock), 0, st, vol.g, vol.sh, vol.moments, vol.counts, vol.normal_bias,
+                           vol.backface_max, n, r0, r1, r2, lookups);
+    else
+        hipLaunchKernelGGL(k_lit_shade<false>, dim3(probe_blocks(n)), dim3(kPbBlock), 0, st, vol.g, vol.sh, vol.moments, vol.counts, vol.normal_bias,
+                           vol.backface_max, n, r0, r1, r2, lookups);
+}
+
+void launch_lit_fold(uint32_t p0, uint32_t n_pix, int32_t aov_spp, const float4 *r0, const float4 *r2, float *lit, float *position, hipStream_t st) {
+    if (n_pix == 0) return;
+    hipLaunchKernelGGL(k_lit_fold, dim3(probe_blocks(n_pix)), dim3(kPbBlock), 0, st, p0, n_pix, aov_spp, r0, r2, lit, position);
+}
+
 }  // namespace mcpt
 
 extern "C" {
+
+int mcpt_render_probe_lit(mcpt_scene *sc, const mcpt_camera *cam, const mcpt_lit_opts *opts, const mcpt_probe_volume *vol, const mcpt_lit_outputs *out,
+                          void *hip_stream, mcpt_lit_info *info) {
+    const std::string w = "mcpt_render_probe_lit";
+    const auto bad = [&](const char *what) { return fail(MCPT_ERR_ARG, w + ": " + what); };
+    if (info) std::memset(info, 0, sizeof *info);
+    if (!sc || !cam || !opts || !vol || !out) return bad("null scene, camera, opts, volume or outputs");
+    if (!out->lit || !vol->sh) return bad("null lit or sh");
+    if (opts->aov_spp < 0 || opts->aov_spp > kMaxAovSpp) return bad("aov_spp must be 0..65536");
+    if (opts->specular_depth < 0 || opts->specular_depth > dn::kMaxSpecularDepth) return bad("specular_depth must be 0..8");
+    if (opts->centre != 0 && opts->centre != 1) return bad("centre must be 0 or 1");
+    if (opts->reserved[0] || opts->reserved[1] || opts->reserved[2] || opts->reserved[3] || out->reserved[0] || out->reserved[1])
+        return bad("reserved words and pointers must be 0");
+    if (opts->centre == 1 && opts->aov_spp > 1) return bad("centre 1 takes one ray per pixel (aov_spp must be 0 or 1)");
+    const bool vis = vol->moments != nullptr;
+    if ((vol->counts != nullptr) != vis || (vol->visibility != nullptr) != vis) return bad("moments, counts and visibility must be all null or all non-null");
+    if (!frame_ok(cam->width, cam->height)) return bad("width and height must be positive (and the frame not too large)");
+    LitVolume lv;
+    const int gc = check_grid(w, vol->grid, lv.g);
+    if (gc != MCPT_OK) return gc;
+    if (vis) {
+        if (grid_probes(lv.g) > (int64_t)pd::kMaxProbes) return bad("dims must name at most (2^31 - 1) / 192 probes");
+        const int vc = check_visibility(w, vol->visibility);
+        if (vc != MCPT_OK) return vc;
+        lv.normal_bias = vol->visibility->normal_bias;
+        lv.backface_max = vol->visibility->backface_max;
+    }
+    lv.sh = vol->sh;
+    lv.moments = vol->moments;
+    lv.counts = vol->counts;
+    if (!on_device(out->lit, sc->device) || !on_device(vol->sh, sc->device) || (out->position && !on_device(out->position, sc->device)) ||
+        (vis && (!on_device(vol->moments, sc->device) || !on_device(vol->counts, sc->device))))
+        return bad("lit, position, sh, moments and counts must be memory of the scene's device");
+    const Clock::time_point t0 = Clock::now();
+    HIP_TRY(hipSetDevice(sc->device));
+    (void)hipGetLastError();
+    if (!sc->probes.lit_count.p) HIP_TRY(sc->probes.lit_count.alloc(1));
+    mcpt_lit_info li;
+    std::memset(&li, 0, sizeof li);
+    const int32_t n_spp = opts->aov_spp == 0 ? 1 : opts->aov_spp;
+    const int rc = lit_pass(sc, make_camera(*cam), opts->seed, n_spp, opts->specular_depth, opts->centre == 1, lv, out->lit, out->position,
+                            sc->probes.lit_count.p, (hipStream_t)hip_stream, li);
+    if (rc != MCPT_OK) return drained(rc);
+    li.ms_total = ms_since(t0);
+    if (info) *info = li;
+    return MCPT_OK;
+}
 
 int mcpt_query_probes(mcpt_scene *sc, const mcpt_params *pp, int64_t n, const float *origins, const mcpt_probe_outputs *out, void *hip_stream,
                       mcpt_stats *stats) {

@@ -104,13 +104,16 @@ struct AovPtrs {
     double *chain_t[2];
     uint32_t *n_next;
     RetryList rl;
+    bool in_ws;  // the arrays are the workspace's (aov_in_workspace), not the call's own (AovOwn)
 };
 
 // ... inside the wavefront workspace (aov_pass says what goes where) ...
+// Not named here and free for a feature pass to use: the shadow queue (shq_o, shq_d), the clamp stack, contrib and fresh.  Nothing in them
+// outlives a render: k_shade fills the shadow queue and k_trace_shadow drains it within one iteration.  lit_pass keeps p in shq_o.
 AovPtrs aov_in_workspace(const Workspace &w, uint64_t cap, bool chain) {
     uint32_t *keys = reinterpret_cast<uint32_t *>(w.wave[1].rec0.p);
     AovPtrs a{keys, keys + cap, w.wave[1].ray_o.p, w.wave[1].ray_d.p, {w.wave[0].ray_o.p, nullptr}, {w.wave[0].ray_d.p, nullptr}, {w.wave[0].hit.p, nullptr},
-              {nullptr, nullptr}, {nullptr, nullptr}, nullptr, w.retry.list(0)};
+              {nullptr, nullptr}, {nullptr, nullptr}, nullptr, w.retry.list(0), true};
     if (chain) {
         a.list_o[1] = w.vtx0.p;
         a.list_d[1] = w.vtx1.p;
@@ -153,7 +156,7 @@ struct AovOwn {
             }
         }
         a = AovPtrs{keys.p, with_keys ? keys.p + cap : nullptr, s0.p, s1.p, {ray_o[0].p, ray_o[1].p}, {ray_d[0].p, ray_d[1].p}, {hit[0].p, hit[1].p},
-                    {chain_st[0].p, chain_st[1].p}, {chain_t[0].p, chain_t[1].p}, count.p, retry.list(0)};
+                    {chain_st[0].p, chain_st[1].p}, {chain_t[0].p, chain_t[1].p}, count.p, retry.list(0), false};
         return e;
     }
 };
@@ -229,6 +232,45 @@ int mcpt::aov_pass(mcpt_scene *sc, const CameraConst &cc, uint32_t seed, int32_t
         launch_aov_fold(p0, np, aov_spp, a.rec0, a.rec1, aov_dev, st);
         return MCPT_OK;
     });
+}
+
+// The lit pass (include/mcpt.h: mcpt_render_probe_lit; csrc/mcpt_frame.h says what goes where).
+int mcpt::lit_pass(mcpt_scene *sc, const CameraConst &cc, uint32_t seed, int32_t aov_spp, int32_t spec_depth, bool centre, const LitVolume &vol,
+                   float *lit_dev, float *position_dev, unsigned long long *lookups_dev, hipStream_t st, mcpt_lit_info &info) {
+    const bool chain = spec_depth > 0;
+    const Workspace &w = sc->pools[0].ws;
+    DevBuf<float4> own_p;  // p per sample of a chunk, when the workspace has no room for it (the first chunk is the largest)
+    HIP_TRY(hipMemsetAsync(lookups_dev, 0, sizeof(unsigned long long), st));
+    const int rc = first_hit_chunks(sc, cc, seed, aov_spp, centre, chain, 0, st, [&](const AovPtrs &a, uint32_t p0, uint32_t np, uint32_t n) -> int {
+        float4 *rec2 = a.in_ws && w.shq_o.n >= n ? w.shq_o.p : nullptr;
+        if (!rec2) {
+            HIP_TRY(own_p.alloc(n));
+            rec2 = own_p.p;
+        }
+        info.in_workspace = a.in_ws ? 1 : 0;
+        info.chunks++;
+        uint32_t m = n;  // rays in list `cur`, whose samples have all followed b bounces
+        for (int b = 0, cur = 0;; ++b, cur ^= 1) {
+            if (b < spec_depth) HIP_TRY(hipMemsetAsync(a.n_next, 0, sizeof(uint32_t), st));
+            launch_lit_terminal(sc->view, m, b, spec_depth, a.list_o[cur], a.list_d[cur], a.list_hit[cur], b == 0 ? nullptr : a.chain_st[cur], a.rec0, a.rec1,
+                                rec2, a.list_o[cur ^ 1], a.list_d[cur ^ 1], a.chain_st[cur ^ 1], a.n_next, st);
+            if (b == spec_depth) break;
+            HIP_TRY(hipMemcpyAsync(&m, a.n_next, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            if (m == 0) break;
+            launch_trace_closest(sc->view, m, nullptr, a.list_o[cur ^ 1], a.list_d[cur ^ 1], a.list_hit[cur ^ 1], a.rl, st);
+        }
+        launch_lit_shade(vol, n, a.rec0, a.rec1, rec2, lookups_dev, st);
+        launch_lit_fold(p0, np, aov_spp, a.rec0, rec2, lit_dev, position_dev, st);
+        return MCPT_OK;
+    });
+    if (rc != MCPT_OK) return rc;
+    unsigned long long lookups = 0;
+    HIP_TRY(hipMemcpyAsync(&lookups, lookups_dev, sizeof lookups, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    info.samples = (int64_t)cc.width * cc.height * aov_spp;
+    info.lookups = (int64_t)lookups;
+    return MCPT_OK;
 }
 
 namespace {

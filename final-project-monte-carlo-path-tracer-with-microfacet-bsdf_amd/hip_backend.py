@@ -43,6 +43,7 @@ EXPORTS = ["mcpt_scene_create", "mcpt_scene_destroy", "mcpt_render", "mcpt_rende
            "mcpt_sh_basis_host", "mcpt_sh_irradiance_host", "mcpt_probe_grid_points_host", "mcpt_probe_shade_host",
            "mcpt_query_probe_depth", "mcpt_probe_shade_visible", "mcpt_bake_probe_volume",
            "mcpt_probe_depth_dirs_host", "mcpt_probe_depth_texel_host", "mcpt_probe_depth_fold_host", "mcpt_probe_shade_visible_host",
+           "mcpt_render_probe_lit",
            "mcpt_group_create", "mcpt_group_render", "mcpt_group_size", "mcpt_group_get_info", "mcpt_group_scene", "mcpt_group_destroy", "mcpt_group_last_error",
            "mcpt_last_error", "mcpt_version"]
 
@@ -537,6 +538,37 @@ def _probe_visibility(who, normal_bias, backface_max):
     return ProbeVisibility(float(nb), float(bm), (C.c_int32 * 2)(0, 0))
 
 
+class LitOpts(C.Structure):
+    _fields_ = [("aov_spp", C.c_int32), ("specular_depth", C.c_int32), ("centre", C.c_int32), ("seed", C.c_uint32), ("reserved", C.c_int32 * 4)]
+
+
+class ProbeVolume(C.Structure):
+    _fields_ = [("grid", C.POINTER(ProbeGrid)), ("sh", C.c_void_p), ("moments", C.c_void_p), ("counts", C.c_void_p),
+                ("visibility", C.POINTER(ProbeVisibility))]
+
+
+class LitOutputs(C.Structure):
+    _fields_ = [("lit", C.c_void_p), ("position", C.c_void_p), ("reserved", C.c_void_p * 2)]
+
+
+class LitInfo(C.Structure):
+    _fields_ = [("chunks", C.c_int32), ("in_workspace", C.c_int32), ("samples", C.c_int64), ("lookups", C.c_int64), ("ms_total", C.c_double)]
+
+    def as_dict(self):
+        return {"chunks": int(self.chunks), "in_workspace": int(self.in_workspace), "samples": int(self.samples), "lookups": int(self.lookups),
+                "ms_total": float(self.ms_total)}
+
+
+def _lit_opts(who, aov_spp, specular_depth, centre, seed):
+    """mcpt_lit_opts; the library's refusals that depend on the options alone are made here as well."""
+    aov_spp, specular_depth, centre = int(aov_spp), int(specular_depth), int(bool(centre))
+    if not 0 <= aov_spp <= 65536 or not 0 <= specular_depth <= 8:
+        raise ValueError("%s: aov_spp is 0..65536 and specular_depth 0..8, not %d and %d" % (who, aov_spp, specular_depth))
+    if centre and aov_spp > 1:
+        raise ValueError("%s: centre takes one ray per pixel (aov_spp 0 or 1), not %d" % (who, aov_spp))
+    return LitOpts(aov_spp, specular_depth, centre, int(seed) & 0xffffffff, (C.c_int32 * 4)(0, 0, 0, 0))
+
+
 def _probe_counts(who, what, v, n):
     """The device address of an int32, C-contiguous (n, 2) device buffer."""
     b = _device_buffer(v, who, what, ("<i4", "=i4"), "int32")
@@ -768,6 +800,8 @@ def lib(path=None):
         L.mcpt_probe_depth_texel_host.argtypes = [C.c_int64, C.c_void_p, C.c_void_p]
         L.mcpt_probe_depth_fold_host.restype = C.c_int
         L.mcpt_probe_depth_fold_host.argtypes = [C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+        L.mcpt_render_probe_lit.restype = C.c_int
+        L.mcpt_render_probe_lit.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(LitOpts), C.POINTER(ProbeVolume), C.POINTER(LitOutputs), C.c_void_p, C.POINTER(LitInfo)]
         L.mcpt_probe_shade_visible_host.restype = C.c_int
         L.mcpt_probe_shade_visible_host.argtypes = [C.POINTER(ProbeGrid), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(ProbeVisibility), C.c_int64] + [C.c_void_p] * 4
         L.mcpt_lightmap_texels.restype = C.c_int
@@ -2097,6 +2131,52 @@ class HipScene:
         _check(self.L.mcpt_bake_probe_volume(self.h, C.byref(g), C.byref(p), C.byref(dp), C.c_void_p(ps or 0), C.c_void_p(pm or 0), C.c_void_p(pn or 0),
                                              C.c_void_p(int(stream or 0)), C.byref(st)), L=self.L)
         return out["sh"], out["moments"], out["counts"], st
+
+    def render_probe_lit(self, origin, spacing, dims, sh, moments=None, counts=None, normal_bias=0.0, backface_max=0.25, aov_spp=0, specular_depth=0,
+                         centre=False, seed=1, camera=None, position=False, out=None, stream=None):
+        """mcpt_render_probe_lit: a frame of the live scene lit by the probe volume (origin, spacing, dims, sh (probes, 27)) -> (lit (H, W, 3),
+        position (H, W, 3) or None, mcpt_lit_info as a dict), float32 device buffers.  moments (probes, 192) and counts (probes, 2) together:
+        the occlusion-aware lookup with (normal_bias, backface_max); both None: the plain one.  aov_spp (0: 1), specular_depth, centre, seed
+        and camera as for render_aovs.  out: a dict with a "lit" device buffer (and "position" when position is asked); None: torch
+        tensors on the scene's device.  Works on `stream` and blocks until the outputs are complete."""
+        who = "render_probe_lit"
+        g, m = _probe_grid(who, origin, spacing, dims)
+        if (moments is None) != (counts is None):
+            raise ValueError("%s: moments and counts come together (both None: the plain lookup)" % who)
+        o = _lit_opts(who, aov_spp, specular_depth, centre, seed)
+        ps = _probe_rows(who, "sh", sh, 27, m)[0]
+        pm = pc = 0
+        vis = None
+        if moments is not None:
+            if m > (2 ** 31 - 1) // PROBE_DEPTH_ROW:
+                raise ValueError("%s: at most (2^31 - 1) / 192 probes, not %d" % (who, m))
+            vis = _probe_visibility(who, normal_bias, backface_max)
+            pm = _probe_rows(who, "moments", moments, PROBE_DEPTH_ROW, m)[0]
+            pc = _probe_counts(who, "counts", counts, m)
+        cam = np.ascontiguousarray(camera if camera is not None else self.sd.camera)
+        W, H = int(cam["width"].reshape(-1)[0]), int(cam["height"].reshape(-1)[0])
+        if W <= 0 or H <= 0:
+            raise ValueError("%s: the camera's width and height are positive, not %d x %d" % (who, W, H))
+        names = ("lit", "position") if position else ("lit",)
+        if out is None:
+            import torch
+            dev = self._torch_device()
+            out = {w: torch.empty((H, W, 3), dtype=torch.float32, device=dev) for w in names}
+            if stream is None:
+                stream = torch.cuda.current_stream(dev).cuda_stream
+        ptrs = {}
+        for w in names:
+            if w not in out:
+                raise ValueError("%s: out has no buffer for %r" % (who, w))
+            b = _device_buffer(out[w], who, "out[%r]" % w)
+            if b is None or b[1] != (H, W, 3):
+                raise ValueError("%s: out[%r] is a float32 device buffer of shape (%d, %d, 3)" % (who, w, H, W))
+            ptrs[w] = b[0]
+        vol = ProbeVolume(C.pointer(g), ps or None, pm or None, pc or None, C.pointer(vis) if vis is not None else None)
+        outs = LitOutputs(ptrs["lit"] or None, ptrs.get("position") or None, (C.c_void_p * 2)(None, None))
+        info = LitInfo()
+        _check(self.L.mcpt_render_probe_lit(self.h, _ptr(cam), C.byref(o), C.byref(vol), C.byref(outs), C.c_void_p(int(stream or 0)), C.byref(info)), L=self.L)
+        return out["lit"], (out["position"] if position else None), info.as_dict()
 
     def probe_buffers(self):
         """mcpt_scene_probe_buffers -> (floats the scene-owned probe buffers hold, how often one of them was (re)allocated)."""

@@ -1594,6 +1594,61 @@ int mcpt_probe_shade_visible_host(const mcpt_probe_grid *grid, const float *sh, 
                                   const mcpt_probe_visibility *opts, int64_t n, const float *points, const float *normals, float *out,
                                   float *weight_out /* nullable */);
 
+/* ---- Probe-lit frames: a picture of the live scene lit by a baked probe volume, at one closest-hit ray and one grid lookup per camera
+ * sample: deterministic for a given seed, free of path noise, and as good as the volume (csrc/mcpt_probes.hip holds the kernels,
+ * csrc/mcpt_render.hip the pass).  Float32 in the written order, no FMA.
+ *
+ * Sample k of pixel m is the feature sample of mcpt_render_aovs_features with the same seed, aov_spp, specular_depth and centre: the same
+ * first ray and the same chain steps 1-5, which give the throughput thr, the ray (o, d) of its last segment, and at a hit the double t,
+ * p = o + d * (float)t, the shading normal n as stored (not flipped), the uv and the material.  Where that sample would record, the lit
+ * sample takes a value v[c]:
+ *   miss:     v[c] = thr[c] * sample_env(d)[c]  (the environment map or the background, as mcpt_sample_env gives it for d)
+ *   emitter:  v[c] = thr[c] * clampf(0, 1, emit[c] * fabsf(dot(-d, n))), the depth-0 rule of Scene::castRay, here at every chain depth:
+ *             an emitter seen in a mirror shows as the emitter.  (The reference shows the sky in its place; that is deliberately not
+ *             reproduced.)
+ *   other:    a[c] = thr[c] * alb[c], the product the AOV record stores (alb: the conductor reflectance at uv, 1 for dielectrics);
+ *             nf = dot(n, d) > 0 ? -n : n;  E = mcpt_probe_shade_visible's value for (p, nf) with volume->visibility when moments are
+ *             given, else mcpt_probe_shade's;  v[c] = a[c] * fmaxf(E[c], 0.f)  (the truncated series can ring negative, a picture cannot).
+ * Fold per pixel, in sample order:  lit[3m + c]: acc = 0; acc += v_k[c] / (float)aov_spp.  position[3m + ..] (nullable): the sum of p over
+ * the samples that ended on a hit (emitters included) divided by their number, 0 without one.  No pixel is sky-culled.
+ *
+ * The call works on hip_stream and blocks until the outputs are complete, like mcpt_bake_lightmap.  It sees the live scene as it is now
+ * and changes no scene state that a later render, query or sequence can observe; it works in the wavefront workspace when a render has
+ * left one (info->in_workspace), else in buffers of its own; the scene keeps one eight-byte counter from its first such call on, which no
+ * other call reads or reports.  info->chunks: chunks of whole pixels the frame was cut into;
+ * info->samples = width * height * aov_spp; info->lookups: samples that ended on a hit that is not an emitter.
+ * MCPT_ERR_ARG before any device work: a null scene, camera, opts, volume, outputs, lit, grid or sh; aov_spp outside 0..65536,
+ * specular_depth outside 0..8, centre other than 0 or 1, centre 1 with aov_spp > 1; a non-zero reserved word or pointer; moments, counts
+ * and visibility not all null or all non-null; a frame mcpt_render_aovs refuses; every grid and visibility refusal of
+ * mcpt_probe_shade_visible (with moments null the grid may hold (2^31 - 1) / 27 probes, as for mcpt_probe_shade); a buffer that is not
+ * memory of the scene's device.  No mcpt_group_* form. */
+typedef struct {
+    int32_t aov_spp;        /* camera samples per pixel, 0 => 1, at most 65536; with centre 1: 0 or 1 */
+    int32_t specular_depth; /* 0..8, the chains of mcpt_render_aovs_ex */
+    int32_t centre;         /* 0 | 1, the centre rays of mcpt_feature_opts */
+    uint32_t seed;          /* ignored with centre 1 */
+    int32_t reserved[4];    /* must be 0 */
+} mcpt_lit_opts;            /* 32 bytes */
+typedef struct {            /* device memory of the scene's device, as the probe calls take it */
+    const mcpt_probe_grid *grid;             /* host struct */
+    const float *sh;                         /* probes*27 */
+    const float *moments;                    /* probes*192, nullable: null => the plain lookup (mcpt_probe_shade) */
+    const int32_t *counts;                   /* probes*2, null iff moments is null */
+    const mcpt_probe_visibility *visibility; /* host struct, null iff moments is null */
+} mcpt_probe_volume;        /* 40 bytes */
+typedef struct {            /* device memory */
+    float *lit;             /* W*H*3, required */
+    float *position;        /* W*H*3, nullable */
+    void *reserved[2];      /* must be null */
+} mcpt_lit_outputs;         /* 32 bytes */
+typedef struct {
+    int32_t chunks, in_workspace;
+    int64_t samples, lookups;
+    double ms_total;        /* host wall clock of the call */
+} mcpt_lit_info;            /* 32 bytes */
+int mcpt_render_probe_lit(mcpt_scene *scene, const mcpt_camera *camera, const mcpt_lit_opts *opts, const mcpt_probe_volume *volume,
+                          const mcpt_lit_outputs *outputs, void *hip_stream, mcpt_lit_info *info /* nullable */);
+
 const char *mcpt_last_error(void);
 const char *mcpt_version(void);
 

@@ -1,11 +1,16 @@
 """A small probe grid in the Cornell demo scene against hemisphere sensors: what the SH-9 truncation plus the grid's trilinear interpolation
 cost.  The command behind the "Light probes" figures of DESIGN.md section 6c.
 python tools/probes.py [--dims 5 4 5] [--spp 16384] [--sensor-spp 262144] [--seed 3] [--visibility [--depth-spp 4096]]
+python tools/probes.py --lit [--lit-out FILE.png] [--width 1920 --height 1080] [--ref-spp 256]
 The grid spans the box's interior.  At a handful of (point, normal) pairs in free space the tool prints the lookup (probe_shade on the
 baked coefficients) next to query_radiance(kind="hemisphere") at the same point and normal, with the sensor's reported standard error:
 both are E / pi.  Also printed: the lookup AT a probe against a sensor there (truncation alone, no interpolation), and the wall times of
 the bake and of the lookup.  --visibility: the probes' depth maps are made as well (query_probe_depth at the grid's points) and the
 occlusion-aware lookup (probe_shade_visible) is printed and summarised next to the plain one; without the flag the output is unchanged.
+--lit: the volume of the same defaults (coefficients and depth maps) is baked, render_probe_lit draws the Cornell demo scene from it with
+centre rays -- depth 0 and depth 2, occlusion-aware and plain, the host wall clock of each call next to one 1-spp render of the same camera
+-- the occlusion-aware depth-2 frame is tone-mapped (HipScene.tonemap) and written as a PNG, and the tone-mapped RMSE of every lit frame
+against a path-traced frame of --ref-spp samples is printed per region of the picture.
 Device buffers come from the HIP runtime the library is linked to, through ctypes; torch is not needed."""
 import argparse
 import sys
@@ -21,6 +26,62 @@ from ray_query import Dev, runtime  # noqa: E402
 f32 = np.float32
 
 
+def lit(args):
+    """--lit: bake, render the lit frames, time them, write the PNG, compare with a path-traced frame."""
+    pkg = mcpt_loader.load()
+    hip = pkg.hip_backend
+    W, H = args.width, args.height
+    sd = pkg.scenes.cornell_demo(W, H, 4)
+    hs = hip.HipScene(sd, builder="sah")
+    rt = runtime()
+    dims = tuple(args.dims)
+    lo, hi = np.array([40.0, 40.0, 40.0]), np.array([516.0, 500.0, 516.0])
+    origin, spacing = tuple(lo), tuple((hi - lo) / np.maximum(np.array(dims) - 1, 1))
+    m = dims[0] * dims[1] * dims[2]
+    max_distance = 1.5 * float(np.linalg.norm(spacing))
+    vol = {"sh": Dev(rt, shape=(m, 27)), "moments": Dev(rt, shape=(m, hip.PROBE_DEPTH_ROW)), "counts": Dev(rt, shape=(m, 2), dtype=np.int32)}
+    t0 = time.perf_counter()
+    hs.bake_probe_volume(origin, spacing, dims, args.depth_spp, max_distance, depth_seed=args.seed + 2, out=vol, spp=args.spp, seed=args.seed)
+    print("volume %dx%dx%d = %d probes at %d spp, depth maps at %d spp, max_distance %.1f: bake %.1f ms"
+          % (dims + (m, args.spp, args.depth_spp, max_distance, (time.perf_counter() - t0) * 1e3)))
+    # the reference first: it leaves the wavefront workspace the lit calls then work in, as in an interactive session
+    t0 = time.perf_counter()
+    ref, _ = hs.render(spp=args.ref_spp, seed=args.seed + 7)
+    t_ref = (time.perf_counter() - t0) * 1e3
+    hs.render(spp=1, seed=1)
+    t0 = time.perf_counter()
+    _, st = hs.render(spp=1, seed=2)
+    t_one = (time.perf_counter() - t0) * 1e3
+    print("%d x %d: path-traced reference at %d spp %.1f ms; one 1-spp render %.2f ms wall clock with its read-back (%.2f ms in the library)"
+          % (W, H, args.ref_spp, t_ref, t_one, st.ms_total))
+    out = {"lit": Dev(rt, shape=(H, W, 3))}
+    ref8 = hs.tonemap(ref)[..., :3].astype(np.float64)
+    y, x = np.mgrid[0:H, 0:W]
+    u, v = (x + 0.5) / W, (y + 0.5) / H
+    mid = (np.abs(u - 0.5) < 0.5 * H / W * 0.98)  # the box's opening: the frame is wider than the box is
+    regions = [("whole frame", np.ones((H, W), bool)), ("ceiling and light (top fifth of the box)", mid & (v < 0.2)),
+               ("left wall (rough red conductor)", mid & (u < 0.5 - 0.3 * H / W)), ("right wall (gold conductor)", mid & (u > 0.5 + 0.3 * H / W)),
+               ("floor (bottom fifth)", mid & (v > 0.8)), ("centre (boxes, spheres, back wall)", (np.abs(u - 0.5) < 0.25 * H / W) & (np.abs(v - 0.5) < 0.25))]
+    frames = {}
+    for depth in (0, 2):
+        for visible in (True, False):
+            kw = dict(moments=vol["moments"], counts=vol["counts"], normal_bias=args.normal_bias) if visible else {}
+            hs.render_probe_lit(origin, spacing, dims, vol["sh"], centre=True, specular_depth=depth, out=out, **kw)  # (warm: code objects, the counter)
+            t0 = time.perf_counter()
+            _, _, info = hs.render_probe_lit(origin, spacing, dims, vol["sh"], centre=True, specular_depth=depth, out=out, **kw)
+            t_call = (time.perf_counter() - t0) * 1e3
+            fb = out["lit"].get()
+            frames[(depth, visible)] = fb
+            d8 = hs.tonemap(fb)[..., :3].astype(np.float64) - ref8
+            print("lit frame, specular_depth %d, %s lookup: %.3f ms wall clock (%.3f ms in the library), %d chunk(s), in_workspace %d, %d lookups of %d samples"
+                  % (depth, "occlusion-aware" if visible else "plain", t_call, info["ms_total"], info["chunks"], info["in_workspace"], info["lookups"],
+                     info["samples"]))
+            print("    tone-mapped RMSE against the reference (0..255): " + "; ".join("%s %.2f" % (nm, np.sqrt((d8[mk] ** 2).mean())) for nm, mk in regions if mk.any()))
+    pkg.pngio.write_png(args.lit_out, hs.tonemap(frames[(2, True)])[..., :3])
+    print("wrote %s (specular_depth 2, occlusion-aware)" % args.lit_out)
+    hs.close()
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--dims", type=int, nargs=3, default=[5, 4, 5])
@@ -30,7 +91,14 @@ def main():
     ap.add_argument("--visibility", action="store_true", help="also the occlusion-aware lookup (probe depth maps, probe_shade_visible)")
     ap.add_argument("--depth-spp", type=int, default=4096, help="samples per probe of the depth maps (--visibility)")
     ap.add_argument("--normal-bias", type=float, default=2.0, help="normal_bias of the occlusion-aware lookup, in scene units (--visibility)")
+    ap.add_argument("--lit", action="store_true", help="render probe-lit frames from the baked volume and compare them with a path-traced frame")
+    ap.add_argument("--lit-out", default="probe_lit.png", help="the PNG of the occlusion-aware depth-2 frame (--lit)")
+    ap.add_argument("--width", type=int, default=1920, help="frame width (--lit)")
+    ap.add_argument("--height", type=int, default=1080, help="frame height (--lit)")
+    ap.add_argument("--ref-spp", type=int, default=256, help="samples per pixel of the path-traced reference frame (--lit)")
     args = ap.parse_args()
+    if args.lit:
+        return lit(args)
     pkg = mcpt_loader.load()
     hip = pkg.hip_backend
     sd = pkg.scenes.cornell_demo(64, 64, 4)
