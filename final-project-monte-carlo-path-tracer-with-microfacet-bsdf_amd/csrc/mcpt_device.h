@@ -22,6 +22,7 @@ struct f2 {
 };
 
 #define MCPT_DI __device__ __forceinline__
+#define MCPT_HDI __host__ __device__ __forceinline__  // integer and exactly rounded float code that the host forms run too
 
 MCPT_DI f3 mk3(float x, float y, float z) { return {x, y, z}; }
 MCPT_DI f3 operator+(f3 a, f3 b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
@@ -53,7 +54,7 @@ struct RngKey {
     uint32_t seed, pixel, sample, stream;
 };
 
-MCPT_DI void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t out[4]) {
+MCPT_HDI void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t out[4]) {
 #pragma unroll
     for (int r = 0; r < 10; ++r) {
         // one 32 x 32 -> 64 multiply per product (v_mad_u64_u32) instead of a mul_hi / mul_lo pair
@@ -75,7 +76,7 @@ MCPT_DI void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, u
 }
 
 // One block = 4 uniforms in [0,1).  key = (seed, pixel); counter = (sample, depth, block, stream).
-MCPT_DI void rng_block(const RngKey &k, uint32_t depth, uint32_t block, float u[4]) {
+MCPT_HDI void rng_block(const RngKey &k, uint32_t depth, uint32_t block, float u[4]) {
     uint32_t o[4];
     philox4x32_10(k.sample, depth, block, k.stream, k.seed, k.pixel, o);
 #pragma unroll

@@ -83,15 +83,39 @@ struct LitVolume {
 // k_lit_terminal in k_aov_chain's place, then k_lit_shade and k_lit_fold (csrc/mcpt_probes.hip).  Besides the arrays of the AOV pass a
 // chunk keeps p per sample: in the workspace's shadow queue origins (shq_o, which no feature pass touches) when they hold a chunk, else in
 // a buffer of the call's own.  lookups_dev: one device counter, cleared here, that ends as info.lookups.  Returns with the stream drained.
+// direct (mcpt_render_probe_lit_direct; null: off): n_samples >= 1 light samples per surface sample through direct_term, staged after the
+// chain loop in the chunk's two ray lists, which are free by then -- shadow rays and hits in list 0, the sample records in list 1's
+// origins, D per sample in the chain states of list 0, the piece's ray count in n_next -- so the chunk loop then always runs with the
+// chain arrays.  lookups_dev then holds a second counter, the live light samples, which ends as dinfo.shadow_rays.
+struct LitDirect {
+    int32_t n_samples;
+    uint32_t seed;
+};
 int lit_pass(mcpt_scene *sc, const CameraConst &cc, uint32_t seed, int32_t aov_spp, int32_t spec_depth, bool centre, const LitVolume &vol, float *lit_dev,
-             float *position_dev, unsigned long long *lookups_dev, hipStream_t st, mcpt_lit_info &info);
+             float *position_dev, unsigned long long *lookups_dev, hipStream_t st, mcpt_lit_info &info, const LitDirect *direct = nullptr,
+             mcpt_lit_direct_info *dinfo = nullptr);
 // csrc/mcpt_probes.hip.  One step of the lit pass's chains: launch_aov_chain's arguments (max_b == 0: every sample stops, the lists of the
 // next step may be null) with the three per-sample records {a or v, kind} {nf} {p} in place of the AOV pass's two.
 void launch_lit_terminal(const DevScene &S, uint32_t n, int32_t b, int32_t max_b, const float4 *ray_o, const float4 *ray_d, const uint4 *hit,
                          const float4 *chain_in, float4 *r0, float4 *r1, float4 *r2, float4 *next_o, float4 *next_d, float4 *chain_out,
                          uint32_t *n_next, hipStream_t st);
 // The lookup of the n samples of a chunk: r0[j].xyz = a * max(E, 0) for the samples that ended on a surface; their number is added to *lookups.
-void launch_lit_shade(const LitVolume &vol, uint32_t n, float4 *r0, const float4 *r1, const float4 *r2, unsigned long long *lookups, hipStream_t st);
+// direct_d (nullable): D per sample in .xyz; the samples then get a * (max(E, 0) + D).
+void launch_lit_shade(const LitVolume &vol, uint32_t n, float4 *r0, const float4 *r1, const float4 *r2, const float4 *direct_d, unsigned long long *lookups,
+                      hipStream_t st);
+constexpr uint32_t kLitSurfaceKind = 2u;  // r0[j].w of a lit sample that ended on a surface (kLitSurface, csrc/mcpt_probes.hip)
+// The sampled direct term (csrc/mcpt_direct.h) of n points into out[stride * i + 0..2], staged in pieces of at most stg.cap light samples
+// through arrays the caller owns: per piece k_direct_rays (csrc/mcpt_kernels.hip), launch_trace_closest over the compacted shadow rays
+// and k_direct_fold.  src: where the points and keys come from (DirectRays, csrc/mcpt_kernels.h; the staging and piece members are set
+// here).  pieces: the launches are added to it.  The result does not depend on the cut.
+struct DirectStage {
+    float4 *ray_o, *ray_d, *slot;
+    uint4 *hit;
+    uint32_t *n_rays;
+    uint64_t cap;
+    RetryList rl;
+};
+int direct_term(const DevScene &S, DirectRays src, uint64_t n, const DirectStage &stg, float *out, uint32_t stride, hipStream_t st, int32_t &pieces);
 void launch_lit_fold(uint32_t p0, uint32_t n_pix, int32_t aov_spp, const float4 *r0, const float4 *r2, float *lit, float *position, hipStream_t st);
 
 // What the rounds of an adaptive frame work in (adaptive_rounds): device buffers the caller owns.  Per pixel of the frame: fb 3 floats,

@@ -201,6 +201,9 @@ struct QueryBufs {
     DevBuf<int32_t> ranges;          // the mesh triangle ranges for the object lookup: m starts in ascending order, then their m objects
     std::vector<int32_t> h_ranges;   // its host copy
     bool table_valid = false;        // `ranges` describes the scene's objects (false again after mcpt_scene_add_objects)
+    // mcpt_query_direct alone: one record per (point, light sample) of a chunk, and the length of the chunk's compacted shadow-ray list
+    DevBuf<float4> direct_slot;
+    DevBuf<uint32_t> direct_n;
     Event done;
     bool pending = false;            // `done` has been recorded and nobody has waited for it on the host since
     hipStream_t last_stream = nullptr;
@@ -227,7 +230,7 @@ struct ProbeBufs {
     DevBuf<float> points;    // mcpt_bake_probe_grid: the grid's points, n*3
     DevBuf<float> radiance;  // mcpt_query_probes without a caller's radiance: the plain fold still needs a place, n*3
     int64_t allocations = 0; // how often one of them was (re)allocated (mcpt_scene_probe_buffers)
-    // mcpt_render_probe_lit: the eight-byte counter of its lookups, made by the scene's first such call.  Working storage of that call, no
+    // mcpt_render_probe_lit[_direct]: the eight-byte counters of its lookups and live light samples, made by the scene's first such call.  Working storage, no
     // probe buffer: it is in neither figure of mcpt_scene_probe_buffers.
     DevBuf<unsigned long long> lit_count;
 };

@@ -210,6 +210,29 @@ void launch_trace_shadow(const DevScene &S, const Counters *counters, int next_i
 // Shades list `cur_idx` (at most n_cur_max records; the true count is read from the device counter) into the other list.
 void launch_shade(const DevScene &S, const RenderConst &C, Wave cur, Wave next, Scratch X, int cur_idx, uint32_t n_cur_max,
                   hipStream_t s);
+// The sampled direct term (csrc/mcpt_direct.h; mcpt_query_direct and the lit pass): light samples j0 .. j0 + jc - 1 (of N) of the points
+// i0 .. i0 + m - 1, one lane per (point, sample), the samples of a point in consecutive lanes.  Lane g = pi * jc + s draws the Philox block
+// of key (seed, key pixel), counter (key sample, 0, j0 + s, kDirectStream), runs sample_light and dl::sample_geometry, and writes
+// slot[g] = {contrib, index of its shadow ray or kDirectDead}.  The shadow rays of the live samples alone are appended to the ray arrays
+// (ballot + prefix count, one integer atomic per wave on *n_rays, which the caller has zeroed): ray_o = {q, g}, ray_d = {ws, dist}.
+// Points: rows of the caller's arrays with key (i, key_sample) (r0 null), or the records of the lit pass's chunk, where sample i of the
+// chunk has p = r2[i], nf = r1[i] and the key (p0 + i / aov_spp, i % aov_spp), and a sample that did not end on a surface (r0[i].w !=
+// surface_kind) has no light sample at all.  total (nullable): the live samples are added to it as well.
+constexpr uint32_t kDirectDead = 0xffffffffu;
+struct DirectRays {
+    const float *points, *normals;  // the call's n*3 arrays
+    uint32_t seed, key_sample;
+    uint32_t i0, m;
+    int32_t N;
+    uint32_t j0, jc;
+    float4 *ray_o, *ray_d, *slot;   // m * jc entries each
+    uint32_t *n_rays;
+    const float4 *r0, *r1, *r2;     // the lit pass's records, or null
+    uint32_t surface_kind, p0;
+    int32_t aov_spp;
+    unsigned long long *total;
+};
+void launch_direct_rays(const DevScene &S, const DirectRays &a, hipStream_t s);
 // Multi-GPU merge helpers (csrc/mcpt_multi.hip): zero the pixels rank `rank` does not own (tile rule of mcpt_params); a += b.
 void launch_mask_unowned(float *fb, int width, int height, int tile, int rank, int nranks, hipStream_t s);
 void launch_add_frame(float *a, const float *b, uint32_t n, hipStream_t s);

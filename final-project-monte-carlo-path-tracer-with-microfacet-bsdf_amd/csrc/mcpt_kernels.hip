@@ -19,6 +19,7 @@
 #include <cfloat>
 #include <cstdlib>
 
+#include "mcpt_direct.h"
 #include "mcpt_kernels.h"
 #include "mcpt_stack_dispatch.h"
 #include "mcpt_traverse.h"
@@ -805,7 +806,9 @@ constexpr bool kPrimaryConductor = true;
 // short path has been written by then, and k_primary_retrace does the whole sample again.
 // Counters: see Counters::pc_samples / pc_rays; the vertices finished here are added to `ended`, the records that ride on a sibling's
 // ray to `shared`, so that every total of mcpt_stats is what k_shade would have made it.
-template <bool kCountPrims, class Trace>
+// kNoEmitter (the indirect-only probes, mcpt_query_probes_ex: only instantiations of the sensor kernels select it): a first ray whose
+// closest hit is an emitter contributes 0 in place of the depth-0 rule.
+template <bool kCountPrims, bool kNoEmitter = false, class Trace>
 MCPT_DI void primary_sample(const DevScene &S, const RenderConst &C, const Wave &next, int next_idx, int q, uint32_t s, bool valid, bool walk, f3 pos,
                             f3 dir, TraceResult tr, BlockAllocShared &sh, const RetryList &rl, Trace trace) {
     float *const result = q ? C.result[1] : C.result[0];
@@ -945,7 +948,15 @@ MCPT_DI void primary_sample(const DevScene &S, const RenderConst &C, const Wave 
             result[(size_t)s * 3 + 2] = env.z;
         } else {
             const int mat = (int)(tr.mat_bits & kMatIndexMask);
-            if (tr.mat_bits >> 31) {  // depth-0 emitter, Scene.cpp:102-107
+            if constexpr (kNoEmitter) {
+                if (tr.mat_bits >> 31) {
+                    result[(size_t)s * 3 + 0] = 0.f;
+                    result[(size_t)s * 3 + 1] = 0.f;
+                    result[(size_t)s * 3 + 2] = 0.f;
+                } else {
+                    surface = true;
+                }
+            } else if (tr.mat_bits >> 31) {  // depth-0 emitter, Scene.cpp:102-107
                 const MaterialRec &M = S.mats[mat];
                 f3 n;
                 if (tr.prim < S.n_tri) {
@@ -1065,11 +1076,10 @@ MCPT_DI void sensor_sample_ray(const SensorConst &sn, const RenderConst &C, int 
     sensor_ray(sn, C.seed, pl, (uint32_t)(q ? C.sample_offset[1] : C.sample_offset[0]) + ks, pos, dir);
 }
 
-template <int STK, bool RETRY, bool SMALL>
-__global__ __launch_bounds__(kBlock) void k_sensor_primary(DevScene S, SensorConst sn, RenderConst C, Wave next, int next_idx, int q,
-                                                           uint32_t first_sample, uint32_t n_samples, RetryList rl) {
-    __shared__ int32_t stk[STK][kBlock];
-    __shared__ BlockAllocShared sh;
+// INDIRECT: primary_sample's kNoEmitter.
+template <int STK, bool RETRY, bool SMALL, bool INDIRECT>
+MCPT_DI void sensor_primary(DevScene &S, const SensorConst &sn, const RenderConst &C, const Wave &next, int next_idx, int q, uint32_t first_sample,
+                            uint32_t n_samples, const RetryList &rl, int32_t (*stk)[kBlock], BlockAllocShared &sh) {
     if constexpr (SMALL) {
         __shared__ SmallGeomLds small_geom;
         stage_small_geom(S, small_geom);
@@ -1082,13 +1092,29 @@ __global__ __launch_bounds__(kBlock) void k_sensor_primary(DevScene S, SensorCon
     f3 pos = mk3(0, 0, 0), dir = mk3(0, 0, 1);
     const TraceResult tr{DBL_MAX, -1, 0u, false, false};
     if (valid) sensor_sample_ray(sn, C, q, s, pos, dir);  // (a lane past the end holds no sample: its index names no sensor)
-    primary_sample<true>(S, C, next, next_idx, q, s, valid, valid, pos, dir, tr, sh, rl,
-                         [&](const Ray &r) { return traverse<false, STK, RETRY, SMALL>(S, r, 0.f, stk, tid); });
+    primary_sample<true, INDIRECT>(S, C, next, next_idx, q, s, valid, valid, pos, dir, tr, sh, rl,
+                                   [&](const Ray &r) { return traverse<false, STK, RETRY, SMALL>(S, r, 0.f, stk, tid); });
 }
 
-__global__ __launch_bounds__(kBlock) void k_sensor_primary_retrace(DevScene S, SensorConst sn, RenderConst C, Wave next, int next_idx, int q, RetryList rl) {
-    __shared__ int32_t stk[1][kBlock];
+template <int STK, bool RETRY, bool SMALL>
+__global__ __launch_bounds__(kBlock) void k_sensor_primary(DevScene S, SensorConst sn, RenderConst C, Wave next, int next_idx, int q,
+                                                           uint32_t first_sample, uint32_t n_samples, RetryList rl) {
+    __shared__ int32_t stk[STK][kBlock];
     __shared__ BlockAllocShared sh;
+    sensor_primary<STK, RETRY, SMALL, false>(S, sn, C, next, next_idx, q, first_sample, n_samples, rl, stk, sh);
+}
+
+template <int STK, bool RETRY, bool SMALL>
+__global__ __launch_bounds__(kBlock) void k_sensor_primary_indirect(DevScene S, SensorConst sn, RenderConst C, Wave next, int next_idx, int q,
+                                                                    uint32_t first_sample, uint32_t n_samples, RetryList rl) {
+    __shared__ int32_t stk[STK][kBlock];
+    __shared__ BlockAllocShared sh;
+    sensor_primary<STK, RETRY, SMALL, true>(S, sn, C, next, next_idx, q, first_sample, n_samples, rl, stk, sh);
+}
+
+template <bool INDIRECT>
+MCPT_DI void sensor_primary_retrace(const DevScene &S, const SensorConst &sn, const RenderConst &C, const Wave &next, int next_idx, int q, const RetryList &rl,
+                                    int32_t (*stk)[kBlock], BlockAllocShared &sh) {
     const uint32_t n = min(*rl.count, rl.cap);
     for (uint32_t base = blockIdx.x * kBlock; base < n; base += gridDim.x * kBlock) {  // uniform trip count per workgroup
         const uint32_t j = base + threadIdx.x;
@@ -1097,11 +1123,24 @@ __global__ __launch_bounds__(kBlock) void k_sensor_primary_retrace(DevScene S, S
         f3 pos = mk3(0, 0, 0), dir = mk3(0, 0, 1);
         const TraceResult tr{DBL_MAX, -1, 0u, false, false};
         if (valid) sensor_sample_ray(sn, C, q, s, pos, dir);
-        primary_sample<false>(S, C, next, next_idx, q, s, valid, valid, pos, dir, tr, sh, rl,
-                              [&](const Ray &r) { return traverse_scratch<false>(S, r, 0.f, stk, threadIdx.x); });
+        primary_sample<false, INDIRECT>(S, C, next, next_idx, q, s, valid, valid, pos, dir, tr, sh, rl,
+                                        [&](const Ray &r) { return traverse_scratch<false>(S, r, 0.f, stk, threadIdx.x); });
         __syncthreads();  // `sh` is reused by the next round
     }
     retry_finish(rl);
+}
+
+__global__ __launch_bounds__(kBlock) void k_sensor_primary_retrace(DevScene S, SensorConst sn, RenderConst C, Wave next, int next_idx, int q, RetryList rl) {
+    __shared__ int32_t stk[1][kBlock];
+    __shared__ BlockAllocShared sh;
+    sensor_primary_retrace<false>(S, sn, C, next, next_idx, q, rl, stk, sh);
+}
+
+__global__ __launch_bounds__(kBlock) void k_sensor_primary_retrace_indirect(DevScene S, SensorConst sn, RenderConst C, Wave next, int next_idx, int q,
+                                                                            RetryList rl) {
+    __shared__ int32_t stk[1][kBlock];
+    __shared__ BlockAllocShared sh;
+    sensor_primary_retrace<true>(S, sn, C, next, next_idx, q, rl, stk, sh);
 }
 
 // mcpt_sensor_rays: the first ray of (sensor[j], sample[j]), one lane per pair.
@@ -1822,6 +1861,70 @@ __global__ __launch_bounds__(kBlock) void k_debug_scene(DevScene S, int kind, ui
     }
 }
 
+// The light samples and shadow rays of the sampled direct term (launch_direct_rays, csrc/mcpt_kernels.h).  It sits here for sample_light,
+// which it runs as k_debug_scene does; the geometry is dl::sample_geometry.  LIT: the points are the lit pass's records.  No early
+// return: every lane takes part in the ballot.
+template <bool LIT>
+__global__ __launch_bounds__(kBlock) void k_direct_rays(DevScene S, DirectRays a) {
+    const uint32_t g = blockIdx.x * kBlock + threadIdx.x;
+    const bool in = g < a.m * a.jc;
+    bool live = false, sampled = false;
+    float q[3], ws[3], dist = 0.f, contrib[3] = {0.f, 0.f, 0.f};
+    if (in) {
+        const uint32_t pi = g / a.jc, s = g - pi * a.jc, i = a.i0 + pi;
+        float p[3], nf[3];
+        RngKey rk{a.seed, i, a.key_sample, kDirectStream};
+        bool point = true;
+        if (LIT) {
+            point = __float_as_uint(a.r0[i].w) == a.surface_kind;
+            const float4 p4 = a.r2[i], n4 = a.r1[i];
+            p[0] = p4.x, p[1] = p4.y, p[2] = p4.z;
+            nf[0] = n4.x, nf[1] = n4.y, nf[2] = n4.z;
+            rk.pixel = a.p0 + i / (uint32_t)a.aov_spp;
+            rk.sample = i % (uint32_t)a.aov_spp;
+        } else {
+            const size_t b = 3 * (size_t)i;
+            p[0] = a.points[b], p[1] = a.points[b + 1], p[2] = a.points[b + 2];
+            nf[0] = a.normals[b], nf[1] = a.normals[b + 1], nf[2] = a.normals[b + 2];
+        }
+        if (point) {
+            float u[4];
+            rng_block(rk, 0u, a.j0 + s, u);
+            f3 x = mk3(0, 0, 0), nl = mk3(0, 0, 0), e = mk3(0, 0, 0);
+            float pdf = 0.f;
+            int32_t prim = -1;
+            (void)sample_light(S, u, x, nl, e, pdf, prim);
+            const float row[dl::kLightRow] = {x.x, x.y, x.z, nl.x, nl.y, nl.z, e.x, e.y, e.z, pdf};
+            live = dl::sample_geometry(p, nf, row, a.N, q, ws, dist, contrib);
+            sampled = true;
+        }
+    }
+    (void)sampled;
+    bool ray = live;  // the lanes whose shadow ray is traced
+#ifdef MCPT_DIRECT_TRACE_DEAD
+    // A/B only (tools/ab.sh, DESIGN.md "Direct light in probe-lit frames"): a dead sample with a usable direction is traced as well, and
+    // its hit ignored, to measure what the compaction saves.
+    ray = live || (sampled && dist > 0.f && dist <= dl::kFltMax);
+#endif
+    const unsigned long long mask = __ballot(ray), lmask = __ballot(live);
+    uint32_t k = kDirectDead;
+    if (mask != 0ull) {
+        uint32_t base = 0;
+        if (lane_id() == 0) {
+            base = atomicAdd(a.n_rays, (uint32_t)__popcll(mask));
+            if (a.total && lmask != 0ull) atomicAdd(a.total, (unsigned long long)__popcll(lmask));
+        }
+        base = __shfl(base, 0);
+        if (ray) {
+            const uint32_t kr = base + __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+            a.ray_o[kr] = make_float4(q[0], q[1], q[2], __uint_as_float(g));
+            a.ray_d[kr] = make_float4(ws[0], ws[1], ws[2], dist);
+            if (live) k = kr;
+        }
+    }
+    if (in) a.slot[g] = make_float4(contrib[0], contrib[1], contrib[2], __uint_as_float(k));
+}
+
 // Renderer.cpp:95-103 on the device: one lane per pixel, RGBA8 out (alpha 255).
 __global__ __launch_bounds__(kBlock) void k_tonemap(const float *__restrict__ fb, uint32_t n_pix, uchar4 *__restrict__ rgba) {
     const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
@@ -1921,6 +2024,12 @@ void launch_sensor_primary(const DevScene &S, const SensorConst &sn, const Rende
                            uint32_t first_sample, uint32_t n_samples, const RetryList &rl, hipStream_t s) {
     if (n_samples == 0) return;
     const dim3 g(blocks(n_samples)), b(kBlock);
+    if (sn.indirect_only) {
+        MCPT_STACK_DISPATCH(S.height, k_sensor_primary_indirect,
+                            hipLaunchKernelGGL(k_sensor_primary_retrace_indirect, dim3(kRetraceGrid), b, 0, s, S, sn, C, next, next_idx, parity, rl), g, b, 0, s, S, sn,
+                            C, next, next_idx, parity, first_sample, n_samples, rl);
+        return;
+    }
     MCPT_STACK_DISPATCH(S.height, k_sensor_primary, hipLaunchKernelGGL(k_sensor_primary_retrace, dim3(kRetraceGrid), b, 0, s, S, sn, C, next, next_idx, parity, rl), g,
                         b, 0, s, S, sn, C, next, next_idx, parity, first_sample, n_samples, rl);
 }
@@ -1993,6 +2102,12 @@ void launch_shade(const DevScene &S, const RenderConst &C, Wave cur, Wave next, 
                   hipStream_t s) {
     if (n_cur_max == 0) return;
     hipLaunchKernelGGL(k_shade, dim3((n_cur_max + kShadeBlock - 1) / kShadeBlock), dim3(kShadeBlock), 0, s, S, C, cur, next, X, cur_idx);
+}
+
+void launch_direct_rays(const DevScene &S, const DirectRays &a, hipStream_t s) {
+    if (a.m == 0 || a.jc == 0) return;
+    if (a.r0) hipLaunchKernelGGL(k_direct_rays<true>, dim3(blocks(a.m * a.jc)), dim3(kBlock), 0, s, S, a);
+    else hipLaunchKernelGGL(k_direct_rays<false>, dim3(blocks(a.m * a.jc)), dim3(kBlock), 0, s, S, a);
 }
 
 void launch_tonemap(const float *fb, uint32_t n_pix, unsigned char *rgba, hipStream_t s) {

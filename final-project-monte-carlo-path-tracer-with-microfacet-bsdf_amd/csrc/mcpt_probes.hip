@@ -23,9 +23,16 @@
 //   k_lit_shade     one lane per sample: the grid lookup (plain or occlusion-aware) of a sample that ended on a surface
 //   k_lit_fold      one lane per pixel, in sample order
 // Their only atomics are integer ones, one per wave: the next list's length (as k_aov_chain) and the count of lookups.
+//
+// The sampled direct term (mcpt_query_direct; csrc/mcpt_direct.h states the rule).  Per chunk of the ray queries' staging buffers:
+//   k_direct_rays   (csrc/mcpt_kernels.hip, beside sample_light) one lane per (point, light sample): Philox block, sample_light,
+//                   dl::sample_geometry; the record of the sample, and the shadow ray of a live one appended to the compacted ray list
+//   closest hits    launch_trace_closest over that list, its length read on the device: a dead sample costs no traversal
+//   k_direct_fold   one lane per point, in sample order: the visibility window in double, the sum, and at a point's last sample / pi
 #include <cmath>
 
 #include "mcpt_chain.h"
+#include "mcpt_direct.h"
 #include "mcpt_frame.h"
 #include "mcpt_host.h"
 #include "mcpt_probe_depth.h"
@@ -155,8 +162,34 @@ __global__ __launch_bounds__(kPbBlock) void k_probe_shade_visible(sh::Grid g, co
     if (weight_out) weight_out[i] = A;
 }
 
+// Samples s < jc of the points i0 .. i0 + m - 1 folded into out (`stride` floats per point).  load: the sums continue what out holds (an earlier piece of the same
+// points' samples); last: these are the points' last samples, so the sums are divided by pi.
+__global__ __launch_bounds__(kPbBlock) void k_direct_fold(uint32_t i0, uint32_t m, uint32_t jc, int load, int last, const float4 *__restrict__ slot,
+                                                        const float4 *__restrict__ ray_d, const uint4 *__restrict__ hit, float *__restrict__ out,
+                                                        uint32_t stride) {
+    const uint32_t pi = blockIdx.x * kPbBlock + threadIdx.x;
+    if (pi >= m) return;
+    float *o = out + (size_t)stride * ((size_t)i0 + pi);
+    float acc[3] = {0.f, 0.f, 0.f};
+    if (load) acc[0] = o[0], acc[1] = o[1], acc[2] = o[2];
+    const float4 *row = slot + (size_t)pi * jc;
+    for (uint32_t s = 0; s < jc; ++s) {
+        const float4 r = row[s];
+        const uint32_t k = __float_as_uint(r.w);
+        if (k == kDirectDead) continue;
+        const uint4 h = hit[k];
+        if ((int32_t)h.z < 0 || !dl::in_window(hit_t(h), ray_d[k].w)) continue;
+        const float c[3] = {r.x, r.y, r.z};
+        dl::fold_sample(c, acc);
+    }
+    if (last) dl::fold_end(acc, acc);
+    o[0] = acc[0];
+    o[1] = acc[1];
+    o[2] = acc[2];
+}
+
 // How a lit sample ended (r0[j].w of the lit pass's records, as bits).
-constexpr uint32_t kLitMiss = 0u, kLitEmitter = 1u, kLitSurface = 2u;
+constexpr uint32_t kLitMiss = 0u, kLitEmitter = 1u, kLitSurface = kLitSurfaceKind;
 
 // One step of the lit pass's chains: k_aov_chain (csrc/mcpt_denoise.hip) with the lit sample's records in place of the AOV record.  A
 // sample that stops writes r0[j] = {v or a, kind}, r1[j] = {nf, 0}, r2[j] = {p, 0}: for a miss and an emitter v is the sample's final
@@ -236,11 +269,12 @@ __global__ __launch_bounds__(kPbBlock) void k_lit_terminal(DevScene S, uint32_t 
 
 // One lane per sample of a chunk: the lookup of a sample that ended on a surface, r0[j].xyz = a * max(E, 0).  VIS: pd::shade_visible,
 // else sh::probe_shade.  The surface samples of the launch are counted by ballot, one integer atomic per wave.
-template <bool VIS>
+// DIRECT: the sampled direct term D of the sample waits in dd[j].xyz, and r0[j].xyz = a * (max(E, 0) + D).
+template <bool VIS, bool DIRECT>
 __global__ __launch_bounds__(kPbBlock) void k_lit_shade(sh::Grid g, const float *__restrict__ coef, const float *__restrict__ moments,
                                                       const int32_t *__restrict__ counts, float normal_bias, float backface_max, uint32_t n,
                                                       float4 *__restrict__ r0, const float4 *__restrict__ r1, const float4 *__restrict__ r2,
-                                                      unsigned long long *__restrict__ lookups) {
+                                                      const float4 *__restrict__ dd, unsigned long long *__restrict__ lookups) {
     const uint32_t j = blockIdx.x * kPbBlock + threadIdx.x;
     bool surface = false;
     float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -254,7 +288,12 @@ __global__ __launch_bounds__(kPbBlock) void k_lit_shade(sh::Grid g, const float 
         float e[3];
         if (VIS) pd::shade_visible(g, coef, moments, counts, normal_bias, backface_max, p, nf, e, nullptr);
         else sh::probe_shade(g, coef, p, nf, e);
-        r0[j] = make_float4(a.x * fmaxf(e[0], 0.f), a.y * fmaxf(e[1], 0.f), a.z * fmaxf(e[2], 0.f), a.w);
+        if (DIRECT) {
+            const float4 d = dd[j];
+            r0[j] = make_float4(a.x * (fmaxf(e[0], 0.f) + d.x), a.y * (fmaxf(e[1], 0.f) + d.y), a.z * (fmaxf(e[2], 0.f) + d.z), a.w);
+        } else {
+            r0[j] = make_float4(a.x * fmaxf(e[0], 0.f), a.y * fmaxf(e[1], 0.f), a.z * fmaxf(e[2], 0.f), a.w);
+        }
     }
     const unsigned long long mask = __ballot(surface);
     if (mask != 0ull && (threadIdx.x & 63u) == 0u) atomicAdd(lookups, (unsigned long long)__popcll(mask));
@@ -345,6 +384,17 @@ int check_depth_params(const std::string &w, const mcpt_probe_depth_params *p) {
     return MCPT_OK;
 }
 
+// The options of the _ex probe calls (nullable: every switch off).
+int check_probe_opts(const std::string &w, const mcpt_probe_opts *o, bool &indirect_only) {
+    indirect_only = false;
+    if (!o) return MCPT_OK;
+    if (o->indirect_only != 0 && o->indirect_only != 1) return fail(MCPT_ERR_ARG, w + ": indirect_only must be 0 or 1");
+    for (int k = 0; k < 7; ++k)
+        if (o->reserved[k]) return fail(MCPT_ERR_ARG, w + ": reserved words of the probe options must be 0");
+    indirect_only = o->indirect_only == 1;
+    return MCPT_OK;
+}
+
 int check_visibility(const std::string &w, const mcpt_probe_visibility *o) {
     if (!o) return fail(MCPT_ERR_ARG, w + ": null visibility options");
     if (o->reserved[0] || o->reserved[1]) return fail(MCPT_ERR_ARG, w + ": reserved words must be 0");
@@ -363,14 +413,42 @@ void launch_lit_terminal(const DevScene &S, uint32_t n, int32_t b, int32_t max_b
                        chain_out, n_next);
 }
 
-void launch_lit_shade(const LitVolume &vol, uint32_t n, float4 *r0, const float4 *r1, const float4 *r2, unsigned long long *lookups, hipStream_t st) {
+void launch_lit_shade(const LitVolume &vol, uint32_t n, float4 *r0, const float4 *r1, const float4 *r2, const float4 *direct_d, unsigned long long *lookups,
+                      hipStream_t st) {
     if (n == 0) return;
-    if (vol.moments)
-        hipLaunchKernelGGL(k_lit_shade<true>, dim3(probe_blocks(n)), dim3(kPbBlock), 0, st, vol.g, vol.sh, vol.moments, vol.counts, vol.normal_bias,
-                           vol.backface_max, n, r0, r1, r2, lookups);
-    else
-        hipLaunchKernelGGL(k_lit_shade<false>, dim3(probe_blocks(n)), dim3(kPbBlock), 0, st, vol.g, vol.sh, vol.moments, vol.counts, vol.normal_bias,
-                           vol.backface_max, n, r0, r1, r2, lookups);
+    const auto go = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(probe_blocks(n)), dim3(kPbBlock), 0, st, vol.g, vol.sh, vol.moments, vol.counts, vol.normal_bias, vol.backface_max, n, r0,
+                           r1, r2, direct_d, lookups);
+    };
+    if (vol.moments) direct_d ? go(k_lit_shade<true, true>) : go(k_lit_shade<true, false>);
+    else direct_d ? go(k_lit_shade<false, true>) : go(k_lit_shade<false, false>);
+}
+
+int direct_term(const DevScene &S, DirectRays src, uint64_t n, const DirectStage &stg, float *out, uint32_t stride, hipStream_t st, int32_t &pieces) {
+    // A piece holds whole points when a point's samples fit the staging, else a run of one point's samples (the sum passes through `out`
+    // between launches).  Either way a point's additions run in sample order.
+    const uint64_t N = (uint64_t)src.N;
+    const uint64_t per = N <= stg.cap ? std::min<uint64_t>(n, stg.cap / N) : 1;  // points per launch
+    const uint64_t jmax = N <= stg.cap ? N : stg.cap;                            // samples of a point per launch
+    src.ray_o = stg.ray_o;
+    src.ray_d = stg.ray_d;
+    src.slot = stg.slot;
+    src.n_rays = stg.n_rays;
+    for (uint64_t i0 = 0; i0 < n; i0 += per) {
+        src.i0 = (uint32_t)i0;
+        src.m = (uint32_t)std::min<uint64_t>(per, n - i0);
+        for (uint64_t j0 = 0; j0 < N; j0 += jmax) {
+            src.j0 = (uint32_t)j0;
+            src.jc = (uint32_t)std::min<uint64_t>(jmax, N - j0);
+            HIP_TRY(hipMemsetAsync(stg.n_rays, 0, sizeof(uint32_t), st));
+            launch_direct_rays(S, src, st);
+            launch_trace_closest(S, src.m * src.jc, stg.n_rays, stg.ray_o, stg.ray_d, stg.hit, stg.rl, st);
+            hipLaunchKernelGGL(k_direct_fold, dim3(probe_blocks(src.m)), dim3(kPbBlock), 0, st, src.i0, src.m, src.jc, j0 > 0 ? 1 : 0,
+                               j0 + src.jc == N ? 1 : 0, stg.slot, stg.ray_d, stg.hit, out, stride);
+            pieces++;
+        }
+    }
+    return MCPT_OK;
 }
 
 void launch_lit_fold(uint32_t p0, uint32_t n_pix, int32_t aov_spp, const float4 *r0, const float4 *r2, float *lit, float *position, hipStream_t st) {
@@ -380,13 +458,10 @@ void launch_lit_fold(uint32_t p0, uint32_t n_pix, int32_t aov_spp, const float4 
 
 }  // namespace mcpt
 
-extern "C" {
-
-int mcpt_render_probe_lit(mcpt_scene *sc, const mcpt_camera *cam, const mcpt_lit_opts *opts, const mcpt_probe_volume *vol, const mcpt_lit_outputs *out,
-                          void *hip_stream, mcpt_lit_info *info) {
-    const std::string w = "mcpt_render_probe_lit";
+// mcpt_render_probe_lit and mcpt_render_probe_lit_direct after the former has cleared its info: every refusal, then the pass.
+static int render_probe_lit(const std::string &w, mcpt_scene *sc, const mcpt_camera *cam, const mcpt_lit_opts *opts, const mcpt_lit_direct_opts *direct,
+                            const mcpt_probe_volume *vol, const mcpt_lit_outputs *out, void *hip_stream, mcpt_lit_info *info, mcpt_lit_direct_info *dinfo) {
     const auto bad = [&](const char *what) { return fail(MCPT_ERR_ARG, w + ": " + what); };
-    if (info) std::memset(info, 0, sizeof *info);
     if (!sc || !cam || !opts || !vol || !out) return bad("null scene, camera, opts, volume or outputs");
     if (!out->lit || !vol->sh) return bad("null lit or sh");
     if (opts->aov_spp < 0 || opts->aov_spp > kMaxAovSpp) return bad("aov_spp must be 0..65536");
@@ -395,6 +470,11 @@ int mcpt_render_probe_lit(mcpt_scene *sc, const mcpt_camera *cam, const mcpt_lit
     if (opts->reserved[0] || opts->reserved[1] || opts->reserved[2] || opts->reserved[3] || out->reserved[0] || out->reserved[1])
         return bad("reserved words and pointers must be 0");
     if (opts->centre == 1 && opts->aov_spp > 1) return bad("centre 1 takes one ray per pixel (aov_spp must be 0 or 1)");
+    if (direct) {
+        if (direct->n_samples < 0 || direct->n_samples > dl::kMaxSamples) return bad("direct: n_samples must be 0 (off) or 1 .. 4096");
+        for (int k = 0; k < 6; ++k)
+            if (direct->reserved[k]) return bad("direct: reserved words must be 0");
+    }
     const bool vis = vol->moments != nullptr;
     if ((vol->counts != nullptr) != vis || (vol->visibility != nullptr) != vis) return bad("moments, counts and visibility must be all null or all non-null");
     if (!frame_ok(cam->width, cam->height)) return bad("width and height must be positive (and the frame not too large)");
@@ -417,22 +497,48 @@ int mcpt_render_probe_lit(mcpt_scene *sc, const mcpt_camera *cam, const mcpt_lit
     const Clock::time_point t0 = Clock::now();
     HIP_TRY(hipSetDevice(sc->device));
     (void)hipGetLastError();
-    if (!sc->probes.lit_count.p) HIP_TRY(sc->probes.lit_count.alloc(1));
+    if (!sc->probes.lit_count.p) HIP_TRY(sc->probes.lit_count.alloc(2));  // {lookups, live light samples}
     mcpt_lit_info li;
     std::memset(&li, 0, sizeof li);
+    mcpt_lit_direct_info di;
+    std::memset(&di, 0, sizeof di);
     const int32_t n_spp = opts->aov_spp == 0 ? 1 : opts->aov_spp;
+    const LitDirect ld{direct ? direct->n_samples : 0, direct ? direct->seed : 0u};
     const int rc = lit_pass(sc, make_camera(*cam), opts->seed, n_spp, opts->specular_depth, opts->centre == 1, lv, out->lit, out->position,
-                            sc->probes.lit_count.p, (hipStream_t)hip_stream, li);
+                            sc->probes.lit_count.p, (hipStream_t)hip_stream, li, ld.n_samples > 0 ? &ld : nullptr, &di);
     if (rc != MCPT_OK) return drained(rc);
     li.ms_total = ms_since(t0);
     if (info) *info = li;
+    if (dinfo) *dinfo = di;
     return MCPT_OK;
+}
+
+extern "C" {
+
+int mcpt_render_probe_lit(mcpt_scene *sc, const mcpt_camera *cam, const mcpt_lit_opts *opts, const mcpt_probe_volume *vol, const mcpt_lit_outputs *out,
+                          void *hip_stream, mcpt_lit_info *info) {
+    if (info) std::memset(info, 0, sizeof *info);
+    return render_probe_lit("mcpt_render_probe_lit", sc, cam, opts, nullptr, vol, out, hip_stream, info, nullptr);
+}
+
+int mcpt_render_probe_lit_direct(mcpt_scene *sc, const mcpt_camera *cam, const mcpt_lit_opts *opts, const mcpt_lit_direct_opts *direct,
+                                 const mcpt_probe_volume *vol, const mcpt_lit_outputs *out, void *hip_stream, mcpt_lit_info *info,
+                                 mcpt_lit_direct_info *dinfo) {
+    return render_probe_lit("mcpt_render_probe_lit_direct", sc, cam, opts, direct, vol, out, hip_stream, info, dinfo);
 }
 
 int mcpt_query_probes(mcpt_scene *sc, const mcpt_params *pp, int64_t n, const float *origins, const mcpt_probe_outputs *out, void *hip_stream,
                       mcpt_stats *stats) {
+    return mcpt_query_probes_ex(sc, pp, n, origins, out, hip_stream, stats, nullptr);
+}
+
+int mcpt_query_probes_ex(mcpt_scene *sc, const mcpt_params *pp, int64_t n, const float *origins, const mcpt_probe_outputs *out, void *hip_stream,
+                         mcpt_stats *stats, const mcpt_probe_opts *opts) {
     const auto bad = [](const char *what) { return fail(MCPT_ERR_ARG, std::string("mcpt_query_probes: ") + what); };
     if (!sc) return bad("null scene");
+    bool indirect_only = false;
+    const int oc = check_probe_opts("mcpt_query_probes", opts, indirect_only);
+    if (oc != MCPT_OK) return oc;
     if (!pp || !out) return bad("null params or out");
     const mcpt_params &p = *pp;
     if (n < 0 || n > (int64_t)sh::kMaxProbes) return bad("n must be in 0 .. (2^31 - 1) / 27");
@@ -453,7 +559,8 @@ int mcpt_query_probes(mcpt_scene *sc, const mcpt_params *pp, int64_t n, const fl
         HIP_TRY(probe_grow(sc, sc->probes.radiance, (size_t)n * 3));
         radiance = sc->probes.radiance.p;
     }
-    return sensor_radiance(sc, p, (uint32_t)n, SensorConst{origins, nullptr, kSensorSphere}, radiance, out->variance, out->sh, (hipStream_t)hip_stream, stats);
+    return sensor_radiance(sc, p, (uint32_t)n, SensorConst{origins, nullptr, kSensorSphere, indirect_only ? 1 : 0}, radiance, out->variance, out->sh,
+                           (hipStream_t)hip_stream, stats);
 }
 
 int mcpt_probe_rays(mcpt_scene *sc, uint32_t seed, int64_t n, const float *origins, const uint32_t *sensor, const uint32_t *sample, float *origins_out,
@@ -504,8 +611,16 @@ int mcpt_probe_shade(mcpt_scene *sc, const mcpt_probe_grid *grid, const float *c
 }
 
 int mcpt_bake_probe_grid(mcpt_scene *sc, const mcpt_probe_grid *grid, const mcpt_params *pp, float *coef, void *hip_stream, mcpt_stats *stats) {
+    return mcpt_bake_probe_grid_ex(sc, grid, pp, coef, hip_stream, stats, nullptr);
+}
+
+int mcpt_bake_probe_grid_ex(mcpt_scene *sc, const mcpt_probe_grid *grid, const mcpt_params *pp, float *coef, void *hip_stream, mcpt_stats *stats,
+                            const mcpt_probe_opts *opts) {
     const std::string w = "mcpt_bake_probe_grid";
     if (!sc) return fail(MCPT_ERR_ARG, w + ": null scene");
+    bool indirect_only = false;
+    const int oc = check_probe_opts(w, opts, indirect_only);
+    if (oc != MCPT_OK) return oc;
     sh::Grid g;
     const int c = check_grid(w, grid, g);
     if (c != MCPT_OK) return c;
@@ -520,7 +635,7 @@ int mcpt_bake_probe_grid(mcpt_scene *sc, const mcpt_probe_grid *grid, const mcpt
     hipLaunchKernelGGL(k_probe_grid_points, dim3(probe_blocks(n)), dim3(kPbBlock), 0, (hipStream_t)hip_stream, g, n, sc->probes.points.p);
     HIP_TRY(hipGetLastError());
     const mcpt_probe_outputs out{coef, nullptr, nullptr, nullptr};
-    return mcpt_query_probes(sc, pp, n, sc->probes.points.p, &out, hip_stream, stats);
+    return mcpt_query_probes_ex(sc, pp, n, sc->probes.points.p, &out, hip_stream, stats, opts);
 }
 
 int mcpt_query_probe_depth(mcpt_scene *sc, const mcpt_probe_depth_params *pp, int64_t n, const float *origins, float *moments, int32_t *counts,
@@ -569,6 +684,60 @@ int mcpt_query_probe_depth(mcpt_scene *sc, const mcpt_probe_depth_params *pp, in
     return MCPT_OK;
 }
 
+int mcpt_query_direct(mcpt_scene *sc, const mcpt_direct_opts *op, int64_t n, const float *points, const float *normals, float *out, void *hip_stream,
+                      mcpt_query_info *info) {
+    const std::string w = "mcpt_query_direct";
+    if (!sc) return fail(MCPT_ERR_ARG, w + ": null scene");
+    if (!op) return fail(MCPT_ERR_ARG, w + ": null opts");
+    if (op->n_samples < 1 || op->n_samples > dl::kMaxSamples) return fail(MCPT_ERR_ARG, w + ": n_samples must be in 1 .. 4096");
+    for (int k = 0; k < 5; ++k)
+        if (op->reserved[k]) return fail(MCPT_ERR_ARG, w + ": reserved words must be 0");
+    if (n < 0 || n > (int64_t)0x7fffffff / op->n_samples) return fail(MCPT_ERR_ARG, w + ": n must not be negative and n * n_samples at most 2^31 - 1");
+    if (n > 0 && (!points || !normals || !out)) return fail(MCPT_ERR_ARG, w + ": null points, normals or out");
+    if (n > 0 && (!on_device(points, sc->device) || !on_device(normals, sc->device) || !on_device(out, sc->device)))
+        return fail(MCPT_ERR_ARG, w + ": points, normals and out must be memory of the scene's device");
+    if (info) std::memset(info, 0, sizeof *info);
+    if (n == 0) return MCPT_OK;
+    const hipStream_t st = (hipStream_t)hip_stream;
+    mcpt_query_info qi;
+    std::memset(&qi, 0, sizeof qi);
+    HIP_TRY(hipSetDevice(sc->device));
+    // (direct_term's cut of the call into pieces of at most `chunk` light samples)
+    const uint64_t chunk = std::max<uint32_t>(sc->knobs.query_chunk, 64u);
+    const uint64_t N = (uint64_t)op->n_samples;
+    const uint64_t per = N <= chunk ? std::min<uint64_t>((uint64_t)n, chunk / N) : 1, jmax = N <= chunk ? N : chunk;
+    const bool lit = sc->view.n_lights > 0;  // (an empty light table: exact zeros, no ray)
+    RetryList rl;
+    const int sr = query_stage(sc, lit ? (uint32_t)(per * jmax) : 1u, st, qi, rl);
+    if (sr != MCPT_OK) return sr;
+    QueryBufs &Q = sc->query;
+    if (!lit) {
+        HIP_TRY(hipMemsetAsync(out, 0, (size_t)n * 3 * sizeof(float), st));
+        qi.launches = 1;
+    } else {
+        if (Q.direct_slot.n < per * jmax || !Q.direct_n.p) {
+            HIP_TRY(query_settle(sc));
+            HIP_TRY(Q.direct_slot.alloc(per * jmax));
+            HIP_TRY(Q.direct_n.alloc(1));
+            qi.grew = 1;
+        }
+        DirectRays src{};
+        src.points = points;
+        src.normals = normals;
+        src.seed = op->seed;
+        src.key_sample = op->key_sample;
+        src.N = op->n_samples;
+        const int dr = direct_term(sc->view, src, (uint64_t)n, DirectStage{Q.ray_o.p, Q.ray_d.p, Q.direct_slot.p, Q.hit.p, Q.direct_n.p, per * jmax, rl}, out, 3u, st,
+                                   qi.launches);
+        if (dr != MCPT_OK) return dr;
+    }
+    const int fr = query_finish(sc, st, qi);
+    if (fr != MCPT_OK) return fr;
+    qi.staged_bytes += (int64_t)(Q.direct_slot.bytes() + Q.direct_n.bytes());
+    if (info) *info = qi;
+    return MCPT_OK;
+}
+
 int mcpt_probe_shade_visible(mcpt_scene *sc, const mcpt_probe_grid *grid, const float *coef, const float *moments, const int32_t *counts,
                              const mcpt_probe_visibility *opts, int64_t n, const float *points, const float *normals, float *out, float *weight_out,
                              void *hip_stream) {
@@ -596,8 +765,16 @@ int mcpt_probe_shade_visible(mcpt_scene *sc, const mcpt_probe_grid *grid, const 
 
 int mcpt_bake_probe_volume(mcpt_scene *sc, const mcpt_probe_grid *grid, const mcpt_params *pp, const mcpt_probe_depth_params *dp, float *coef,
                            float *moments, int32_t *counts, void *hip_stream, mcpt_stats *stats) {
+    return mcpt_bake_probe_volume_ex(sc, grid, pp, dp, coef, moments, counts, hip_stream, stats, nullptr);
+}
+
+int mcpt_bake_probe_volume_ex(mcpt_scene *sc, const mcpt_probe_grid *grid, const mcpt_params *pp, const mcpt_probe_depth_params *dp, float *coef,
+                              float *moments, int32_t *counts, void *hip_stream, mcpt_stats *stats, const mcpt_probe_opts *opts) {
     const std::string w = "mcpt_bake_probe_volume";
     if (!sc) return fail(MCPT_ERR_ARG, w + ": null scene");
+    bool indirect_only = false;
+    const int oc = check_probe_opts(w, opts, indirect_only);
+    if (oc != MCPT_OK) return oc;
     sh::Grid g;
     const int c = check_grid(w, grid, g);
     if (c != MCPT_OK) return c;
@@ -609,7 +786,7 @@ int mcpt_bake_probe_volume(mcpt_scene *sc, const mcpt_probe_grid *grid, const mc
     if (dc != MCPT_OK) return dc;
     if (!on_device(coef, sc->device) || !on_device(moments, sc->device) || !on_device(counts, sc->device))
         return fail(MCPT_ERR_ARG, w + ": sh, moments and counts must be memory of the scene's device");
-    const int rc = mcpt_bake_probe_grid(sc, grid, pp, coef, hip_stream, stats);
+    const int rc = mcpt_bake_probe_grid_ex(sc, grid, pp, coef, hip_stream, stats, opts);
     if (rc != MCPT_OK) return rc;
     return mcpt_query_probe_depth(sc, dp, grid_probes(g), sc->probes.points.p, moments, counts, hip_stream, nullptr);
 }
@@ -695,6 +872,34 @@ int mcpt_probe_depth_fold_host(int64_t n, int32_t spp, const float *dirs, const 
         counts[2 * i] = (accumulate ? counts[2 * i] : 0) + spp;
         counts[2 * i + 1] = (accumulate ? counts[2 * i + 1] : 0) + back;
     }
+    return MCPT_OK;
+}
+
+int mcpt_rng_uniforms_host(uint32_t seed, uint32_t pixel, int64_t n, const uint32_t *sample, const uint32_t *depth, const uint32_t *block,
+                           const uint32_t *stream, float *out) {
+    if (n < 0 || (n > 0 && (!sample || !depth || !block || !stream || !out)))
+        return fail(MCPT_ERR_ARG, "mcpt_rng_uniforms_host: n < 0, or null sample, depth, block, stream or out");
+    for (int64_t i = 0; i < n; ++i) rng_block(RngKey{seed, pixel, sample[i], stream[i]}, depth[i], block[i], out + 4 * i);
+    return MCPT_OK;
+}
+
+int mcpt_direct_samples_host(int64_t n, int32_t N, const float *points, const float *normals, const float *light_rows, float *q_out, float *ws_out,
+                             float *dist_out, uint8_t *live_out, float *contrib_out) {
+    const std::string w = "mcpt_direct_samples_host";
+    if (N < 1 || N > dl::kMaxSamples) return fail(MCPT_ERR_ARG, w + ": N must be in 1 .. 4096");
+    if (n < 0 || n > (int64_t)0x7fffffff / N) return fail(MCPT_ERR_ARG, w + ": n must not be negative and n * N at most 2^31 - 1");
+    if (n > 0 && (!points || !normals || !light_rows || !q_out || !ws_out || !dist_out || !live_out || !contrib_out))
+        return fail(MCPT_ERR_ARG, w + ": null points, normals, light_rows or output");
+    dl::samples_host(n, N, points, normals, light_rows, q_out, ws_out, dist_out, live_out, contrib_out);
+    return MCPT_OK;
+}
+
+int mcpt_direct_fold_host(int64_t n, int32_t N, const float *contrib, const uint8_t *visible, float *out) {
+    const std::string w = "mcpt_direct_fold_host";
+    if (N < 1 || N > dl::kMaxSamples) return fail(MCPT_ERR_ARG, w + ": N must be in 1 .. 4096");
+    if (n < 0 || n > (int64_t)0x7fffffff / N) return fail(MCPT_ERR_ARG, w + ": n must not be negative and n * N at most 2^31 - 1");
+    if (n > 0 && (!contrib || !visible || !out)) return fail(MCPT_ERR_ARG, w + ": null contrib, visible or out");
+    dl::fold_host(n, N, contrib, visible, out);
     return MCPT_OK;
 }
 

@@ -236,11 +236,14 @@ int mcpt::aov_pass(mcpt_scene *sc, const CameraConst &cc, uint32_t seed, int32_t
 
 // The lit pass (include/mcpt.h: mcpt_render_probe_lit; csrc/mcpt_frame.h says what goes where).
 int mcpt::lit_pass(mcpt_scene *sc, const CameraConst &cc, uint32_t seed, int32_t aov_spp, int32_t spec_depth, bool centre, const LitVolume &vol,
-                   float *lit_dev, float *position_dev, unsigned long long *lookups_dev, hipStream_t st, mcpt_lit_info &info) {
-    const bool chain = spec_depth > 0;
+                   float *lit_dev, float *position_dev, unsigned long long *lookups_dev, hipStream_t st, mcpt_lit_info &info, const LitDirect *direct,
+                   mcpt_lit_direct_info *dinfo) {
+    const bool chain = spec_depth > 0 || direct;
     const Workspace &w = sc->pools[0].ws;
     DevBuf<float4> own_p;  // p per sample of a chunk, when the workspace has no room for it (the first chunk is the largest)
-    HIP_TRY(hipMemsetAsync(lookups_dev, 0, sizeof(unsigned long long), st));
+    HIP_TRY(hipMemsetAsync(lookups_dev, 0, (direct ? 2 : 1) * sizeof(unsigned long long), st));
+    int32_t pieces = 0;
+    uint32_t stage_cap = 0;  // light samples a piece of the direct term may stage
     const int rc = first_hit_chunks(sc, cc, seed, aov_spp, centre, chain, 0, st, [&](const AovPtrs &a, uint32_t p0, uint32_t np, uint32_t n) -> int {
         float4 *rec2 = a.in_ws && w.shq_o.n >= n ? w.shq_o.p : nullptr;
         if (!rec2) {
@@ -260,16 +263,44 @@ int mcpt::lit_pass(mcpt_scene *sc, const CameraConst &cc, uint32_t seed, int32_t
             if (m == 0) break;
             launch_trace_closest(sc->view, m, nullptr, a.list_o[cur ^ 1], a.list_d[cur ^ 1], a.list_hit[cur ^ 1], a.rl, st);
         }
-        launch_lit_shade(vol, n, a.rec0, a.rec1, rec2, lookups_dev, st);
+        float4 *direct_d = nullptr;
+        if (direct) {
+            direct_d = a.chain_st[0];
+            if (sc->view.n_lights == 0) {  // (an empty light table: D = 0, no ray)
+                HIP_TRY(hipMemsetAsync(direct_d, 0, (size_t)n * sizeof(float4), st));
+            } else {
+                DirectRays src{};
+                src.seed = direct->seed;
+                src.N = direct->n_samples;
+                src.r0 = a.rec0;
+                src.r1 = a.rec1;
+                src.r2 = rec2;
+                src.surface_kind = kLitSurfaceKind;
+                src.p0 = p0;
+                src.aov_spp = aov_spp;
+                src.total = lookups_dev + 1;
+                if (!stage_cap) stage_cap = n;  // (the first chunk is the largest, and every list array holds at least its rays)
+                const uint64_t cap = stage_cap;
+                const int dr = direct_term(sc->view, src, n, DirectStage{a.list_o[0], a.list_d[0], a.list_o[1], a.list_hit[0], a.n_next, cap, a.rl},
+                                           reinterpret_cast<float *>(direct_d), 4u, st, pieces);
+                if (dr != MCPT_OK) return dr;
+            }
+        }
+        launch_lit_shade(vol, n, a.rec0, a.rec1, rec2, direct_d, lookups_dev, st);
         launch_lit_fold(p0, np, aov_spp, a.rec0, rec2, lit_dev, position_dev, st);
         return MCPT_OK;
     });
     if (rc != MCPT_OK) return rc;
-    unsigned long long lookups = 0;
-    HIP_TRY(hipMemcpyAsync(&lookups, lookups_dev, sizeof lookups, hipMemcpyDeviceToHost, st));
+    unsigned long long lookups[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(lookups, lookups_dev, (direct ? 2 : 1) * sizeof lookups[0], hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     info.samples = (int64_t)cc.width * cc.height * aov_spp;
-    info.lookups = (int64_t)lookups;
+    info.lookups = (int64_t)lookups[0];
+    if (direct && dinfo) {
+        dinfo->light_samples = (int64_t)lookups[0] * direct->n_samples;
+        dinfo->shadow_rays = (int64_t)lookups[1];
+        dinfo->pieces = pieces;
+    }
     return MCPT_OK;
 }
 

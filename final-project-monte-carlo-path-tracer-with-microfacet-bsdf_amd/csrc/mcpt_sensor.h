@@ -13,9 +13,11 @@ struct SensorConst {
     const float *origins;  // n*3  RAY: ray origin.  HEMISPHERE: surface point p
     const float *dirs;     // n*3  RAY: direction, used as given.  HEMISPHERE: unit normal
     int32_t kind;          // MCPT_SENSOR_*, or kSensorSphere
+    int32_t indirect_only = 0;  // 1 (mcpt_query_probes_ex): a first ray whose closest hit is an emitter contributes 0 (k_sensor_primary_indirect)
 };
 
 constexpr uint32_t kSensorStream = 4u;  // Philox stream of the hemisphere and sphere samples: the channel paths use 0..2, the camera 3
+constexpr uint32_t kDirectStream = 5u;  // Philox stream of the light samples of the sampled direct term (csrc/mcpt_direct.h)
 // The whole-sphere source of the light probes (mcpt_query_probes, mcpt_probe_rays): internal, the public enum does not have it, and
 // mcpt_query_radiance and mcpt_sensor_rays refuse it.
 constexpr int32_t kSensorSphere = 2;

@@ -44,6 +44,8 @@ EXPORTS = ["mcpt_scene_create", "mcpt_scene_destroy", "mcpt_render", "mcpt_rende
            "mcpt_query_probe_depth", "mcpt_probe_shade_visible", "mcpt_bake_probe_volume",
            "mcpt_probe_depth_dirs_host", "mcpt_probe_depth_texel_host", "mcpt_probe_depth_fold_host", "mcpt_probe_shade_visible_host",
            "mcpt_render_probe_lit",
+           "mcpt_query_probes_ex", "mcpt_bake_probe_grid_ex", "mcpt_bake_probe_volume_ex", "mcpt_render_probe_lit_direct",
+           "mcpt_query_direct", "mcpt_rng_uniforms_host", "mcpt_direct_samples_host", "mcpt_direct_fold_host",
            "mcpt_group_create", "mcpt_group_render", "mcpt_group_size", "mcpt_group_get_info", "mcpt_group_scene", "mcpt_group_destroy", "mcpt_group_last_error",
            "mcpt_last_error", "mcpt_version"]
 
@@ -516,6 +518,27 @@ class ProbeVisibility(C.Structure):
     _fields_ = [("normal_bias", C.c_float), ("backface_max", C.c_float), ("reserved", C.c_int32 * 2)]
 
 
+class ProbeOpts(C.Structure):
+    _fields_ = [("indirect_only", C.c_int32), ("reserved", C.c_int32 * 7)]
+
+
+class LitDirectOpts(C.Structure):
+    _fields_ = [("n_samples", C.c_int32), ("seed", C.c_uint32), ("reserved", C.c_int32 * 6)]
+
+
+class LitDirectInfo(C.Structure):
+    _fields_ = [("light_samples", C.c_int64), ("shadow_rays", C.c_int64), ("pieces", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+    def as_dict(self):
+        return {"light_samples": int(self.light_samples), "shadow_rays": int(self.shadow_rays), "pieces": int(self.pieces)}
+
+
+class DirectOpts(C.Structure):
+    _fields_ = [("seed", C.c_uint32), ("n_samples", C.c_int32), ("key_sample", C.c_uint32), ("reserved", C.c_int32 * 5)]
+
+
+DIRECT_MAX_SAMPLES = 4096  # light samples per point of mcpt_query_direct
+DIRECT_STREAM = 5          # the Philox stream of its light samples
 PROBE_DEPTH_RES = 8  # MCPT_PROBE_DEPTH_RES
 PROBE_DEPTH_ROW = PROBE_DEPTH_RES * PROBE_DEPTH_RES * 3  # floats of moments per probe
 
@@ -794,6 +817,23 @@ def lib(path=None):
         L.mcpt_probe_shade_visible.argtypes = [C.c_void_p, C.POINTER(ProbeGrid), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(ProbeVisibility), C.c_int64] + [C.c_void_p] * 5
         L.mcpt_bake_probe_volume.restype = C.c_int
         L.mcpt_bake_probe_volume.argtypes = [C.c_void_p, C.POINTER(ProbeGrid), C.POINTER(Params), C.POINTER(ProbeDepthParams)] + [C.c_void_p] * 4 + [C.POINTER(Stats)]
+        L.mcpt_query_probes_ex.restype = C.c_int
+        L.mcpt_query_probes_ex.argtypes = list(L.mcpt_query_probes.argtypes) + [C.POINTER(ProbeOpts)]
+        L.mcpt_bake_probe_grid_ex.restype = C.c_int
+        L.mcpt_bake_probe_grid_ex.argtypes = list(L.mcpt_bake_probe_grid.argtypes) + [C.POINTER(ProbeOpts)]
+        L.mcpt_bake_probe_volume_ex.restype = C.c_int
+        L.mcpt_bake_probe_volume_ex.argtypes = list(L.mcpt_bake_probe_volume.argtypes) + [C.POINTER(ProbeOpts)]
+        L.mcpt_render_probe_lit_direct.restype = C.c_int
+        L.mcpt_render_probe_lit_direct.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(LitOpts), C.POINTER(LitDirectOpts), C.POINTER(ProbeVolume), C.POINTER(LitOutputs),
+                                                   C.c_void_p, C.POINTER(LitInfo), C.POINTER(LitDirectInfo)]
+        L.mcpt_query_direct.restype = C.c_int
+        L.mcpt_query_direct.argtypes = [C.c_void_p, C.POINTER(DirectOpts), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(QueryInfo)]
+        L.mcpt_rng_uniforms_host.restype = C.c_int
+        L.mcpt_rng_uniforms_host.argtypes = [C.c_uint32, C.c_uint32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.mcpt_direct_samples_host.restype = C.c_int
+        L.mcpt_direct_samples_host.argtypes = [C.c_int64, C.c_int32] + [C.c_void_p] * 8
+        L.mcpt_direct_fold_host.restype = C.c_int
+        L.mcpt_direct_fold_host.argtypes = [C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.mcpt_probe_depth_dirs_host.restype = C.c_int
         L.mcpt_probe_depth_dirs_host.argtypes = [C.c_void_p]
         L.mcpt_probe_depth_texel_host.restype = C.c_int
@@ -1055,6 +1095,51 @@ def probe_shade(origin, spacing, dims, sh, points, normals):
         raise ValueError("probe_shade: sh has shape (%d, 27) and there is one normal per point, not %s, %d and %d" % (m, L.shape, len(nr), len(p)))
     out = np.zeros((len(p), 3), np.float32)
     _check(lib().mcpt_probe_shade_host(C.byref(g), _ptr(L), len(p), _ptr(p), _ptr(nr), _ptr(out)))
+    return out
+
+
+def rng_uniforms(seed, pixel, sample, depth, block, stream):
+    """mcpt_rng_uniforms_host (host only): the Philox block of key (seed, pixel) and counter (sample, depth, block, stream) as four uniforms
+    per row -> (n, 4) float32.  sample, depth, block and stream broadcast against each other."""
+    a = np.broadcast_arrays(*[np.asarray(v, dtype=np.uint32) for v in (sample, depth, block, stream)])
+    a = [np.ascontiguousarray(v.reshape(-1)) for v in a]
+    n = len(a[0])
+    out = np.zeros((n, 4), dtype=np.float32)
+    _check(lib().mcpt_rng_uniforms_host(int(seed) & 0xffffffff, int(pixel) & 0xffffffff, n, _ptr(a[0]), _ptr(a[1]), _ptr(a[2]), _ptr(a[3]), _ptr(out)))
+    return out
+
+
+def direct_samples(points, normals, light_rows):
+    """mcpt_direct_samples_host (host only): the geometry of the sampled direct term of include/mcpt.h for points (n, 3), unit normals (n, 3)
+    and light samples light_rows (n, N, 10: the rows of HipScene.sample_light) -> a dict of q (n, N, 3), ws (n, N, 3), dist (n, N), live
+    (n, N) uint8 and contrib (n, N, 3) = emit * g / N."""
+    p = np.ascontiguousarray(points, dtype=np.float32)
+    nr = np.ascontiguousarray(normals, dtype=np.float32)
+    r = np.ascontiguousarray(light_rows, dtype=np.float32)
+    if p.ndim != 2 or p.shape[1] != 3 or nr.shape != p.shape:
+        raise ValueError("direct_samples: points and normals have shape (n, 3), not %s and %s" % (p.shape, nr.shape))
+    n = len(p)
+    if r.ndim != 3 or r.shape[0] != n or r.shape[1] < 1 or r.shape[2] != 10:
+        raise ValueError("direct_samples: light_rows has shape (%d, N, 10) with N >= 1, not %s" % (n, r.shape))
+    N = r.shape[1]
+    out = {"q": np.zeros((n, N, 3), np.float32), "ws": np.zeros((n, N, 3), np.float32), "dist": np.zeros((n, N), np.float32),
+           "live": np.zeros((n, N), np.uint8), "contrib": np.zeros((n, N, 3), np.float32)}
+    _check(lib().mcpt_direct_samples_host(n, N, _ptr(p), _ptr(nr), _ptr(r), _ptr(out["q"]), _ptr(out["ws"]), _ptr(out["dist"]), _ptr(out["live"]),
+                                          _ptr(out["contrib"])))
+    return out
+
+
+def direct_fold(contrib, visible):
+    """mcpt_direct_fold_host (host only): D of include/mcpt.h from the contributions (n, N, 3) and the visibility (n, N; non-zero: visible)
+    of every light sample -> (n, 3) float32."""
+    c = np.ascontiguousarray(contrib, dtype=np.float32)
+    if c.ndim != 3 or c.shape[1] < 1 or c.shape[2] != 3:
+        raise ValueError("direct_fold: contrib has shape (n, N, 3) with N >= 1, not %s" % (c.shape,))
+    v = np.ascontiguousarray(np.asarray(visible) != 0, dtype=np.uint8)
+    if v.shape != c.shape[:2]:
+        raise ValueError("direct_fold: visible has shape %s, not %s" % (c.shape[:2], v.shape))
+    out = np.zeros((c.shape[0], 3), dtype=np.float32)
+    _check(lib().mcpt_direct_fold_host(c.shape[0], c.shape[1], _ptr(c), _ptr(v), _ptr(out)))
     return out
 
 
@@ -1957,12 +2042,13 @@ class HipScene:
         _check(self.L.mcpt_sensor_rays(self.h, k, int(seed), n, _ptr(po), _ptr(pd), _ptr(si), _ptr(sm), _ptr(o), _ptr(d)), L=self.L)
         return o, d
 
-    def query_probes(self, origins, radiance=False, variance=False, out=None, stream=None, **params):
+    def query_probes(self, origins, radiance=False, variance=False, out=None, stream=None, indirect_only=False, **params):
         """mcpt_query_probes: light probes at points (n, 3) in the memory of the scene's device -> (sh (n, 27), radiance (n, 3) or None,
         variance (n, 3) or None, Stats).  sh[i, 3j + c] is coefficient j of channel c of the incoming radiance over the whole sphere at
         point i, the fold of include/mcpt.h over the first rays probe_rays gives; radiance is the mean over the sphere.  Inputs, out and
         stream as in query_radiance: out is a dict with "sh" (and "radiance", "variance") float32 device buffers, or None when origins
-        is a torch tensor.  params: the keywords of HipScene.params.  The call blocks until the outputs are written."""
+        is a torch tensor.  params: the keywords of HipScene.params.  The call blocks until the outputs are written.  indirect_only
+        (mcpt_query_probes_ex): a sample whose first ray hits an emitter contributes 0, the volume that goes with query_direct."""
         who = "query_probes"
         po, n = _probe_rows(who, "origins", origins, 3)
         if n > (2 ** 31 - 1) // 27:
@@ -1983,7 +2069,11 @@ class HipScene:
         outs = ProbeOutputs(ptrs["sh"], ptrs.get("radiance"), ptrs.get("variance"), None)
         p = self.params(**params)
         st = Stats()
-        _check(self.L.mcpt_query_probes(self.h, C.byref(p), n, C.c_void_p(po or 0), C.byref(outs), C.c_void_p(int(stream or 0)), C.byref(st)), L=self.L)
+        if indirect_only:
+            _check(self.L.mcpt_query_probes_ex(self.h, C.byref(p), n, C.c_void_p(po or 0), C.byref(outs), C.c_void_p(int(stream or 0)), C.byref(st),
+                                               C.byref(ProbeOpts(indirect_only=1))), L=self.L)
+        else:
+            _check(self.L.mcpt_query_probes(self.h, C.byref(p), n, C.c_void_p(po or 0), C.byref(outs), C.c_void_p(int(stream or 0)), C.byref(st)), L=self.L)
         return out["sh"], out.get("radiance") if "radiance" in names else None, (out["variance"] if variance else None), st
 
     def probe_rays(self, origins, sensor, sample, seed=1):
@@ -2021,9 +2111,10 @@ class HipScene:
                                        C.c_void_p(int(stream or 0))), L=self.L)
         return out
 
-    def bake_probe_grid(self, origin, spacing, dims, out=None, stream=None, **params):
+    def bake_probe_grid(self, origin, spacing, dims, out=None, stream=None, indirect_only=False, **params):
         """mcpt_bake_probe_grid: probe_grid_points on the device into a scene-owned buffer, then query_probes there -> (sh (probes, 27),
-        Stats).  out: a float32 (probes, 27) device buffer; None: a torch tensor on the scene's device."""
+        Stats).  out: a float32 (probes, 27) device buffer; None: a torch tensor on the scene's device.  indirect_only: as for query_probes
+        (mcpt_bake_probe_grid_ex)."""
         who = "bake_probe_grid"
         g, m = _probe_grid(who, origin, spacing, dims)
         if out is None:
@@ -2035,7 +2126,11 @@ class HipScene:
         ps = _probe_rows(who, "out", out, 27, m)[0]
         p = self.params(**params)
         st = Stats()
-        _check(self.L.mcpt_bake_probe_grid(self.h, C.byref(g), C.byref(p), C.c_void_p(ps or 0), C.c_void_p(int(stream or 0)), C.byref(st)), L=self.L)
+        if indirect_only:
+            _check(self.L.mcpt_bake_probe_grid_ex(self.h, C.byref(g), C.byref(p), C.c_void_p(ps or 0), C.c_void_p(int(stream or 0)), C.byref(st),
+                                                  C.byref(ProbeOpts(indirect_only=1))), L=self.L)
+        else:
+            _check(self.L.mcpt_bake_probe_grid(self.h, C.byref(g), C.byref(p), C.c_void_p(ps or 0), C.c_void_p(int(stream or 0)), C.byref(st)), L=self.L)
         return out, st
 
     def query_probe_depth(self, origins, spp, max_distance, seed=1, sample_offset=0, accumulate=0, out=None, stream=None):
@@ -2068,6 +2163,32 @@ class HipScene:
         _check(self.L.mcpt_query_probe_depth(self.h, C.byref(p), n, C.c_void_p(po or 0), C.c_void_p(pm or 0), C.c_void_p(pn or 0),
                                              C.c_void_p(int(stream or 0)), C.byref(info)), L=self.L)
         return out["moments"], out["counts"], info.as_dict()
+
+    def query_direct(self, points, normals, n_samples, seed=1, key_sample=0, out=None, stream=None):
+        """mcpt_query_direct: the sampled direct term D of include/mcpt.h (E_direct / pi of a Lambertian surface) at points (n, 3) with unit
+        normals (n, 3) in the memory of the scene's device, from n_samples light samples and shadow rays per point -> ((n, 3) float32
+        device buffer, mcpt_query_info as a dict).  Point i draws with the Philox key (seed, i) and the sample word key_sample.  out may
+        be None with torch inputs.  Enqueued on `stream` without a synchronisation, through the staging buffers of the ray queries."""
+        who = "query_direct"
+        pp, n = _probe_rows(who, "points", points, 3)
+        pn = _probe_rows(who, "normals", normals, 3, n)[0]
+        if not 1 <= int(n_samples) <= DIRECT_MAX_SAMPLES:
+            raise ValueError("%s: n_samples must be in 1 .. %d, not %r" % (who, DIRECT_MAX_SAMPLES, n_samples))
+        if n * int(n_samples) > 2 ** 31 - 1:
+            raise ValueError("%s: n * n_samples must be at most 2^31 - 1" % who)
+        if out is None:
+            if not _is_torch(points, normals):
+                raise ValueError("%s: out is required unless the inputs are torch tensors" % who)
+            import torch
+            out = torch.empty((n, 3), dtype=torch.float32, device=points.device)
+            if stream is None:
+                stream = torch.cuda.current_stream(points.device).cuda_stream
+        pout = _probe_rows(who, "out", out, 3, n)[0]
+        o = DirectOpts(seed=int(seed) & 0xffffffff, n_samples=int(n_samples), key_sample=int(key_sample) & 0xffffffff)
+        info = QueryInfo()
+        _check(self.L.mcpt_query_direct(self.h, C.byref(o), n, C.c_void_p(pp or 0), C.c_void_p(pn or 0), C.c_void_p(pout or 0),
+                                        C.c_void_p(int(stream or 0)), C.byref(info)), L=self.L)
+        return out, info.as_dict()
 
     def probe_shade_visible(self, origin, spacing, dims, sh, moments, counts, points, normals, normal_bias=0.0, backface_max=0.25, weight=None,
                             out=None, stream=None):
@@ -2104,10 +2225,10 @@ class HipScene:
                                                C.c_void_p(int(stream or 0))), L=self.L)
         return out
 
-    def bake_probe_volume(self, origin, spacing, dims, depth_spp, max_distance, depth_seed=1, out=None, stream=None, **params):
+    def bake_probe_volume(self, origin, spacing, dims, depth_spp, max_distance, depth_seed=1, out=None, stream=None, indirect_only=False, **params):
         """mcpt_bake_probe_volume: bake_probe_grid, then query_probe_depth (depth_spp samples, max_distance, depth_seed) on the same
         scene-owned points -> (sh (probes, 27), moments (probes, 192), counts (probes, 2), Stats).  out: a dict with "sh", "moments" and
-        "counts" device buffers; None: torch tensors on the scene's device."""
+        "counts" device buffers; None: torch tensors on the scene's device.  indirect_only: as for query_probes (mcpt_bake_probe_volume_ex)."""
         who = "bake_probe_volume"
         g, m = _probe_grid(who, origin, spacing, dims)
         if m > (2 ** 31 - 1) // PROBE_DEPTH_ROW:
@@ -2128,18 +2249,26 @@ class HipScene:
         pn = _probe_counts(who, "out['counts']", out["counts"], m)
         p = self.params(**params)
         st = Stats()
-        _check(self.L.mcpt_bake_probe_volume(self.h, C.byref(g), C.byref(p), C.byref(dp), C.c_void_p(ps or 0), C.c_void_p(pm or 0), C.c_void_p(pn or 0),
-                                             C.c_void_p(int(stream or 0)), C.byref(st)), L=self.L)
+        if indirect_only:
+            _check(self.L.mcpt_bake_probe_volume_ex(self.h, C.byref(g), C.byref(p), C.byref(dp), C.c_void_p(ps or 0), C.c_void_p(pm or 0), C.c_void_p(pn or 0),
+                                                    C.c_void_p(int(stream or 0)), C.byref(st), C.byref(ProbeOpts(indirect_only=1))), L=self.L)
+        else:
+            _check(self.L.mcpt_bake_probe_volume(self.h, C.byref(g), C.byref(p), C.byref(dp), C.c_void_p(ps or 0), C.c_void_p(pm or 0), C.c_void_p(pn or 0),
+                                                 C.c_void_p(int(stream or 0)), C.byref(st)), L=self.L)
         return out["sh"], out["moments"], out["counts"], st
 
     def render_probe_lit(self, origin, spacing, dims, sh, moments=None, counts=None, normal_bias=0.0, backface_max=0.25, aov_spp=0, specular_depth=0,
-                         centre=False, seed=1, camera=None, position=False, out=None, stream=None):
+                         centre=False, seed=1, camera=None, position=False, out=None, stream=None, direct_samples=0, direct_seed=1):
         """mcpt_render_probe_lit: a frame of the live scene lit by the probe volume (origin, spacing, dims, sh (probes, 27)) -> (lit (H, W, 3),
         position (H, W, 3) or None, mcpt_lit_info as a dict), float32 device buffers.  moments (probes, 192) and counts (probes, 2) together:
         the occlusion-aware lookup with (normal_bias, backface_max); both None: the plain one.  aov_spp (0: 1), specular_depth, centre, seed
         and camera as for render_aovs.  out: a dict with a "lit" device buffer (and "position" when position is asked); None: torch
-        tensors on the scene's device.  Works on `stream` and blocks until the outputs are complete."""
+        tensors on the scene's device.  Works on `stream` and blocks until the outputs are complete.  direct_samples > 0
+        (mcpt_render_probe_lit_direct): that many light samples of the sampled direct term per surface sample, drawn with direct_seed, are
+        added to the lookup; the dict then also holds light_samples, shadow_rays and pieces."""
         who = "render_probe_lit"
+        if not 0 <= int(direct_samples) <= DIRECT_MAX_SAMPLES:
+            raise ValueError("%s: direct_samples must be in 0 .. %d, not %r" % (who, DIRECT_MAX_SAMPLES, direct_samples))
         g, m = _probe_grid(who, origin, spacing, dims)
         if (moments is None) != (counts is None):
             raise ValueError("%s: moments and counts come together (both None: the plain lookup)" % who)
@@ -2175,6 +2304,11 @@ class HipScene:
         vol = ProbeVolume(C.pointer(g), ps or None, pm or None, pc or None, C.pointer(vis) if vis is not None else None)
         outs = LitOutputs(ptrs["lit"] or None, ptrs.get("position") or None, (C.c_void_p * 2)(None, None))
         info = LitInfo()
+        if int(direct_samples) > 0:
+            d, di = LitDirectOpts(n_samples=int(direct_samples), seed=int(direct_seed) & 0xffffffff), LitDirectInfo()
+            _check(self.L.mcpt_render_probe_lit_direct(self.h, _ptr(cam), C.byref(o), C.byref(d), C.byref(vol), C.byref(outs), C.c_void_p(int(stream or 0)),
+                                                       C.byref(info), C.byref(di)), L=self.L)
+            return out["lit"], (out["position"] if position else None), dict(info.as_dict(), **di.as_dict())
         _check(self.L.mcpt_render_probe_lit(self.h, _ptr(cam), C.byref(o), C.byref(vol), C.byref(outs), C.c_void_p(int(stream or 0)), C.byref(info)), L=self.L)
         return out["lit"], (out["position"] if position else None), info.as_dict()
 

@@ -1614,7 +1614,7 @@ int mcpt_probe_shade_visible_host(const mcpt_probe_grid *grid, const float *sh, 
  *
  * The call works on hip_stream and blocks until the outputs are complete, like mcpt_bake_lightmap.  It sees the live scene as it is now
  * and changes no scene state that a later render, query or sequence can observe; it works in the wavefront workspace when a render has
- * left one (info->in_workspace), else in buffers of its own; the scene keeps one eight-byte counter from its first such call on, which no
+ * left one (info->in_workspace), else in buffers of its own; the scene keeps two eight-byte counters from its first such call on, which no
  * other call reads or reports.  info->chunks: chunks of whole pixels the frame was cut into;
  * info->samples = width * height * aov_spp; info->lookups: samples that ended on a hit that is not an emitter.
  * MCPT_ERR_ARG before any device work: a null scene, camera, opts, volume, outputs, lit, grid or sh; aov_spp outside 0..65536,
@@ -1648,6 +1648,105 @@ typedef struct {
 } mcpt_lit_info;            /* 32 bytes */
 int mcpt_render_probe_lit(mcpt_scene *scene, const mcpt_camera *camera, const mcpt_lit_opts *opts, const mcpt_probe_volume *volume,
                           const mcpt_lit_outputs *outputs, void *hip_stream, mcpt_lit_info *info /* nullable */);
+
+/* ---- The sampled direct term: the light that reaches a Lambertian point straight from the emitters, by light samples and shadow rays,
+ * for points that already sit in the memory of the scene's device (csrc/mcpt_direct.h states the arithmetic once for host and device;
+ * float32 in the written order, no FMA).  It is the part of Scene::directLighting a Lambertian preview needs, and the complement of a
+ * probe volume: the order-2 series of a probe cannot hold a contact shadow, a shadow ray can.
+ *
+ * D(seed, key_pixel, key_sample, N; p, nf)[c] is E_direct / pi at the point p with unit normal nf.  dot, norm and normalized are those of
+ * the render loop (a three-term dot is a.x * b.x + (a.y * b.y + a.z * b.z); normalized leaves a zero vector unchanged), EPS = 1e-4f.
+ *   If the scene's light table is empty: D = 0, and no ray is traced.
+ *   q = p + nf * EPS per component (Scene.cpp:114, with the normal that faces the viewer).
+ *   acc[c] = 0; for j = 0 .. N - 1 in order:
+ *     u = the four uniforms of the Philox block with key (seed, key_pixel) and counter (key_sample, depth 0, block j, stream 5)
+ *         (mcpt_rng_uniforms_host; streams 0..2 are the channel paths, 3 the camera, 4 the sensors);
+ *     (x_l, n_l, emit, pdf) = the scene's light sample for u: the ten floats of mcpt_debug_scene kind 0, the reference's quirks included
+ *         (the biased triangle pick inside a mesh light, BVH.cpp:132; a sphere emitter's sample carries emission 0);
+ *     w = x_l - q; dist = norm(w); ws = normalized(w); cs = dot(ws, nf); cl = dot(-ws, n_l); g = ((cs * cl) / (dist * dist)) / pdf;
+ *     live = cs > 0 && cl > 0 && g <= FLT_MAX  (a NaN fails, and so does a zero distance); a sample that is not live traces no ray;
+ *     visible = live && the closest hit of the ray (q, ws) exists with fabs(t - (double)dist) < (double)EPS, t the double of
+ *         mcpt_intersect (Scene.cpp:72-75);
+ *     if visible: acc[c] = acc[c] + (emit[c] * g) / (float)N.
+ *   D[c] = acc[c] / pi (the float pi of the render loop).
+ *
+ * mcpt_query_direct: out[3i + c] = D(seed, i, key_sample, n_samples; points[i], normals[i])[c].  The call is enqueued on hip_stream
+ * without a synchronisation, through the staging buffers of the ray queries and under their protocol (mcpt_query_closest): the buffers
+ * are the scene's and only grow, info->grew is 0 in the steady state; the light samples are staged in chunks of at most MCPT_QUERY_CHUNK,
+ * whole points or runs of one point's samples, and the result does not depend on it; the scene's query event is recorded behind the
+ * call, so an edit issued after it waits.  Only the shadow rays of live samples are traced.  It sees the live scene as it is now.
+ * MCPT_ERR_ARG before any device work, with out and info untouched: a null scene or opts; n_samples outside 1..4096; a non-zero reserved
+ * word; n < 0 or n * n_samples > 2^31 - 1; n > 0 with a null points, normals or out, or with one that is not memory of the scene's
+ * device.  n == 0 is a valid no-op.  No mcpt_group_* form. */
+typedef struct {
+    uint32_t seed;
+    int32_t n_samples;   /* 1..4096 light samples per point */
+    uint32_t key_sample; /* the sample word of the Philox counter */
+    int32_t reserved[5]; /* must be 0 */
+} mcpt_direct_opts;      /* 32 bytes */
+int mcpt_query_direct(mcpt_scene *scene, const mcpt_direct_opts *opts, int64_t n, const float *points /* n*3, device */,
+                      const float *normals /* n*3, device */, float *out /* n*3, device */, void *hip_stream,
+                      mcpt_query_info *info /* nullable */);
+/* Host only, no GPU needed.  mcpt_rng_uniforms_host: the Philox block of key (seed, pixel) and counter (sample[i], depth[i], block[i],
+ * stream[i]) as four uniforms in [0, 1) per row, as every kernel draws them.  mcpt_direct_samples_host: the geometry of N light samples
+ * per point, point-major (light_rows: the ten floats of mcpt_debug_scene kind 0 per sample) -> the shadow ray's origin q and direction
+ * ws, dist, live (0 | 1) and contrib = (emit * g) / N, which is 0 where live is 0.  mcpt_direct_fold_host: D from the contributions and
+ * the visibility of every sample (non-zero: visible).  MCPT_ERR_ARG: N outside 1..4096, n < 0 or n * N > 2^31 - 1, a null pointer
+ * with n > 0. */
+int mcpt_rng_uniforms_host(uint32_t seed, uint32_t pixel, int64_t n, const uint32_t *sample, const uint32_t *depth, const uint32_t *block,
+                           const uint32_t *stream, float *out /* n*4 */);
+int mcpt_direct_samples_host(int64_t n, int32_t N, const float *points /* n*3 */, const float *normals /* n*3 */,
+                             const float *light_rows /* n*N*10 */, float *q_out /* n*N*3 */, float *ws_out /* n*N*3 */,
+                             float *dist_out /* n*N */, uint8_t *live_out /* n*N */, float *contrib_out /* n*N*3 */);
+int mcpt_direct_fold_host(int64_t n, int32_t N, const float *contrib /* n*N*3 */, const uint8_t *visible /* n*N */, float *out /* n*3 */);
+
+/* ---- Indirect-only probes: the volume that goes with the sampled direct term.  The _ex forms take the arguments of mcpt_query_probes,
+ * mcpt_bake_probe_grid and mcpt_bake_probe_volume and one option struct; opts null or zeroed gives the plain call bit for bit.
+ * indirect_only = 1: in the projection, and in radiance and variance, the value v(i, k, c) of every sample whose first ray
+ * mcpt_probe_rays(i, sample_offset + k) has its closest hit on an emitting primitive is replaced by 0.f (the plain call records the
+ * depth-0 rule clamp(0, 1, emission * |cos|) there, which is direct light, and clamped).  Everything else is unchanged: a miss keeps the
+ * sky, the fold order is the same, accumulate / spp_total compose the same way, and the depth maps of mcpt_bake_probe_volume_ex are
+ * those of mcpt_bake_probe_volume.  The switch is a compile-time flavour of the sensor kernels' first-hit code (k_sensor_primary_indirect,
+ * csrc/mcpt_kernels.hip); the render loop's kernels do not carry it.
+ * MCPT_ERR_ARG besides the plain calls' refusals: indirect_only other than 0 or 1, a non-zero reserved word.  No mcpt_group_* form. */
+typedef struct {
+    int32_t indirect_only; /* 0 | 1 */
+    int32_t reserved[7];   /* must be 0 */
+} mcpt_probe_opts;         /* 32 bytes */
+int mcpt_query_probes_ex(mcpt_scene *scene, const mcpt_params *params, int64_t n, const float *origins /* n*3, device */,
+                         const mcpt_probe_outputs *out, void *hip_stream, mcpt_stats *stats /* nullable */, const mcpt_probe_opts *opts /* nullable */);
+int mcpt_bake_probe_grid_ex(mcpt_scene *scene, const mcpt_probe_grid *grid, const mcpt_params *params, float *sh /* probes*27, device */,
+                            void *hip_stream, mcpt_stats *stats /* nullable */, const mcpt_probe_opts *opts /* nullable */);
+int mcpt_bake_probe_volume_ex(mcpt_scene *scene, const mcpt_probe_grid *grid, const mcpt_params *params, const mcpt_probe_depth_params *depth_params,
+                              float *sh /* probes*27, device */, float *moments /* probes*192, device */, int32_t *counts /* probes*2, device */,
+                              void *hip_stream, mcpt_stats *stats /* nullable */, const mcpt_probe_opts *opts /* nullable */);
+
+/* ---- Probe-lit frames with direct light: mcpt_render_probe_lit with the sampled direct term added at every surface sample, so that a
+ * preview shows contact shadows under moved, deformed and added objects.  Meant for an indirect-only volume (above); with a full volume
+ * the direct light is counted twice.  direct null or n_samples == 0 gives mcpt_render_probe_lit bit for bit, info included.  Otherwise
+ * only the surface samples ("other" in the rule of mcpt_render_probe_lit) change:
+ *   v[c] = a[c] * (fmaxf(E[c], 0.f) + D(direct->seed, m, k, n_samples; p, nf)[c])
+ * with m the pixel, k the sample's index within the pixel and p, nf, a the sample's own; direct->seed is used with centre = 1 as well.  At
+ * the end of a mirror or glass chain the term is applied like the lookup, with thr inside a.  Sky and emitter samples, the fold,
+ * position, info->samples and info->lookups are unchanged.  dinfo->light_samples = lookups * n_samples; dinfo->shadow_rays: the live
+ * light samples, each of which traced one shadow ray; dinfo->pieces: the pieces the light samples of the chunks were staged in (a chunk's
+ * n * n_samples light samples can exceed its ray arrays; the result does not depend on the cut).  The call blocks, changes nothing a
+ * later render, query or sequence can observe, and a second call allocates nothing; the scene's counter of mcpt_render_probe_lit is
+ * sixteen bytes.  MCPT_ERR_ARG before any device work, with the outputs, info and dinfo untouched: every refusal of
+ * mcpt_render_probe_lit; n_samples outside 0..4096; a non-zero reserved word of direct.  No mcpt_group_* form. */
+typedef struct {
+    int32_t n_samples;   /* 0 = off, else 1..4096 light samples per surface sample */
+    uint32_t seed;
+    int32_t reserved[6]; /* must be 0 */
+} mcpt_lit_direct_opts;  /* 32 bytes */
+typedef struct {
+    int64_t light_samples, shadow_rays;
+    int32_t pieces;
+    int32_t reserved[3];
+} mcpt_lit_direct_info;  /* 32 bytes */
+int mcpt_render_probe_lit_direct(mcpt_scene *scene, const mcpt_camera *camera, const mcpt_lit_opts *opts,
+                                 const mcpt_lit_direct_opts *direct /* nullable */, const mcpt_probe_volume *volume, const mcpt_lit_outputs *outputs,
+                                 void *hip_stream, mcpt_lit_info *info /* nullable */, mcpt_lit_direct_info *dinfo /* nullable */);
 
 const char *mcpt_last_error(void);
 const char *mcpt_version(void);

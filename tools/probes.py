@@ -1,7 +1,7 @@
 """A small probe grid in the Cornell demo scene against hemisphere sensors: what the SH-9 truncation plus the grid's trilinear interpolation
 cost.  The command behind the "Light probes" figures of DESIGN.md section 6c.
 python tools/probes.py [--dims 5 4 5] [--spp 16384] [--sensor-spp 262144] [--seed 3] [--visibility [--depth-spp 4096]]
-python tools/probes.py --lit [--lit-out FILE.png] [--width 1920 --height 1080] [--ref-spp 256]
+python tools/probes.py --lit [--lit-out FILE.png] [--width 1920 --height 1080] [--ref-spp 256] [--direct N [N ...] [--indirect-only]]
 The grid spans the box's interior.  At a handful of (point, normal) pairs in free space the tool prints the lookup (probe_shade on the
 baked coefficients) next to query_radiance(kind="hemisphere") at the same point and normal, with the sensor's reported standard error:
 both are E / pi.  Also printed: the lookup AT a probe against a sensor there (truncation alone, no interpolation), and the wall times of
@@ -10,7 +10,11 @@ occlusion-aware lookup (probe_shade_visible) is printed and summarised next to t
 --lit: the volume of the same defaults (coefficients and depth maps) is baked, render_probe_lit draws the Cornell demo scene from it with
 centre rays -- depth 0 and depth 2, occlusion-aware and plain, the host wall clock of each call next to one 1-spp render of the same camera
 -- the occlusion-aware depth-2 frame is tone-mapped (HipScene.tonemap) and written as a PNG, and the tone-mapped RMSE of every lit frame
-against a path-traced frame of --ref-spp samples is printed per region of the picture.
+against a path-traced frame of --ref-spp samples is printed per region of the picture.  --direct N: after those, the occlusion-aware
+frames at depth 0 and 2 with N light samples of the sampled direct term per surface sample (render_probe_lit(direct_samples=N)), timed
+and compared in the same way, and the depth-2 frame of the last N written beside the other PNG; --indirect-only: they shade from a
+second volume baked with indirect_only, the volume the term is meant for (without the flag: from the full volume, which counts the
+direct light twice).  Without --direct the output is unchanged.
 Device buffers come from the HIP runtime the library is linked to, through ctypes; torch is not needed."""
 import argparse
 import sys
@@ -79,6 +83,32 @@ def lit(args):
             print("    tone-mapped RMSE against the reference (0..255): " + "; ".join("%s %.2f" % (nm, np.sqrt((d8[mk] ** 2).mean())) for nm, mk in regions if mk.any()))
     pkg.pngio.write_png(args.lit_out, hs.tonemap(frames[(2, True)])[..., :3])
     print("wrote %s (specular_depth 2, occlusion-aware)" % args.lit_out)
+    if args.direct:
+        dvol = vol
+        if args.indirect_only:
+            dvol = {"sh": Dev(rt, shape=(m, 27)), "moments": vol["moments"], "counts": vol["counts"]}
+            t0 = time.perf_counter()
+            hs.bake_probe_grid(origin, spacing, dims, out=dvol["sh"], spp=args.spp, seed=args.seed, indirect_only=True)
+            print("indirect-only volume (the same seeds; the depth maps are the full volume's): bake %.1f ms" % ((time.perf_counter() - t0) * 1e3))
+        kw = dict(moments=dvol["moments"], counts=dvol["counts"], normal_bias=args.normal_bias)
+        for N in args.direct:
+            for depth in (0, 2):
+                call = lambda: hs.render_probe_lit(origin, spacing, dims, dvol["sh"], centre=True, specular_depth=depth, out=out, direct_samples=N,  # noqa: E731
+                                                   direct_seed=args.seed + 11, **kw)
+                call()
+                t0 = time.perf_counter()
+                _, _, info = call()
+                t_call = (time.perf_counter() - t0) * 1e3
+                fb = out["lit"].get()
+                d8 = hs.tonemap(fb)[..., :3].astype(np.float64) - ref8
+                print("lit frame with direct light, %s volume, N %d, specular_depth %d: %.3f ms wall clock (%.3f ms in the library), %d chunk(s), %d piece(s), "
+                      "%d light samples, %d shadow rays (%.1f %% of the lanes dead)"
+                      % ("indirect-only" if args.indirect_only else "full", N, depth, t_call, info["ms_total"], info["chunks"], info["pieces"], info["light_samples"],
+                         info["shadow_rays"], 100.0 * (1 - info["shadow_rays"] / max(info["light_samples"], 1))))
+                print("    tone-mapped RMSE against the reference (0..255): " + "; ".join("%s %.2f" % (nm, np.sqrt((d8[mk] ** 2).mean())) for nm, mk in regions if mk.any()))
+        name = args.lit_out[:-4] + "_direct.png" if args.lit_out.endswith(".png") else args.lit_out + "_direct"
+        pkg.pngio.write_png(name, hs.tonemap(fb)[..., :3])
+        print("wrote %s (specular_depth 2, N %d)" % (name, args.direct[-1]))
     hs.close()
 
 
@@ -96,6 +126,8 @@ def main():
     ap.add_argument("--width", type=int, default=1920, help="frame width (--lit)")
     ap.add_argument("--height", type=int, default=1080, help="frame height (--lit)")
     ap.add_argument("--ref-spp", type=int, default=256, help="samples per pixel of the path-traced reference frame (--lit)")
+    ap.add_argument("--direct", type=int, nargs="+", default=[], metavar="N", help="also frames with N light samples of the sampled direct term (--lit)")
+    ap.add_argument("--indirect-only", action="store_true", help="the --direct frames shade from a volume baked with indirect_only (--lit)")
     args = ap.parse_args()
     if args.lit:
         return lit(args)
