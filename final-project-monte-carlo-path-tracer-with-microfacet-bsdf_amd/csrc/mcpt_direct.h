@@ -7,6 +7,9 @@
  * norm and normalized are those of csrc/mcpt_device.h.  The light sample itself (sample_light, csrc/mcpt_kernels.hip) and the Philox
  * block (rng_block, csrc/mcpt_device.h) are not restated here.  tests/test_direct_cpu.py checks the host loops against the numpy
  * restatement of tests/direct_cases.py, tests/test_gpu_direct.py the device against the host composition, bit for bit.
+ *
+ * At the end, host only: the cut of a staged query into launches (piece_cut, for_each_piece), which the direct term shares with the
+ * probe depth query.
  */
 #ifndef MCPT_DIRECT_H
 #define MCPT_DIRECT_H
@@ -91,6 +94,33 @@ static inline void fold_host(int64_t n, int32_t N, const float *contrib, const u
 }
 
 }  // namespace dl
+
+// The cut of a staged query (mcpt_query_probe_depth, mcpt_query_direct, the direct term of the lit pass) into launches: n items of
+// `samples` samples each through a staging of `capacity` samples.  A launch holds whole items when an item's samples fit the staging,
+// else a run of one item's samples, whole blocks of `block` but for the item's last run (capacity >= block).  The one place that says
+// so: the staging is sized by staged(), the loops are for_each_piece's.  tests/native/piece_cut_driver.cpp walks it.
+struct PieceCut {
+    uint64_t per, smax;  // items per launch, samples of an item per launch
+    uint64_t staged() const { return per * smax; }
+};
+
+static inline PieceCut piece_cut(uint64_t n, uint64_t samples, uint64_t capacity, uint64_t block) {
+    if (samples <= capacity) return PieceCut{n < capacity / samples ? n : capacity / samples, samples};
+    return PieceCut{1, capacity / block * block};
+}
+
+// f(i0, m, s0, sc) for every launch, items outermost and an item's runs in sample order: samples s0 .. s0 + sc - 1 of items i0 .. i0 + m - 1.
+// It returns an mcpt status; the first that is not 0 ends the walk and is returned.
+template <class F>
+int for_each_piece(const PieceCut &c, uint64_t n, uint64_t samples, F &&f) {
+    for (uint64_t i0 = 0; i0 < n; i0 += c.per)
+        for (uint64_t s0 = 0; s0 < samples; s0 += c.smax) {
+            const uint64_t m = c.per < n - i0 ? c.per : n - i0, sc = c.smax < samples - s0 ? c.smax : samples - s0;
+            if (const int rc = f((uint32_t)i0, (uint32_t)m, (uint32_t)s0, (uint32_t)sc)) return rc;
+        }
+    return 0;
+}
+
 }  // namespace mcpt
 
 #endif /* MCPT_DIRECT_H */

@@ -4,6 +4,7 @@
 #include "mcpt_host.h"
 #include "mcpt_adaptive.h"
 #include "mcpt_denoise.h"
+#include "mcpt_direct.h"
 #include "mcpt_sh.h"
 #include "mcpt_temporal.h"
 
@@ -79,7 +80,7 @@ struct LitVolume {
     float normal_bias = 0.f, backface_max = 0.f;
 };
 // The lit pass (include/mcpt.h: mcpt_render_probe_lit): lit_dev[3m ..] and, when not null, position_dev[3m ..] for every pixel of the frame,
-// queued on `st` (with spec_depth > 0 it waits for the stream once per bounce).  The chunk loop and the bounce loop of aov_pass with
+// queued on `st` (with spec_depth > 0 it waits for the stream once per bounce).  The chunk loop and the bounce loop of aov_pass (first_hit_chunks, chain_bounces) with
 // k_lit_terminal in k_aov_chain's place, then k_lit_shade and k_lit_fold (csrc/mcpt_probes.hip).  Besides the arrays of the AOV pass a
 // chunk keeps p per sample: in the workspace's shadow queue origins (shq_o, which no feature pass touches) when they hold a chunk, else in
 // a buffer of the call's own.  lookups_dev: one device counter, cleared here, that ends as info.lookups.  Returns with the stream drained.
@@ -104,15 +105,16 @@ void launch_lit_terminal(const DevScene &S, uint32_t n, int32_t b, int32_t max_b
 void launch_lit_shade(const LitVolume &vol, uint32_t n, float4 *r0, const float4 *r1, const float4 *r2, const float4 *direct_d, unsigned long long *lookups,
                       hipStream_t st);
 constexpr uint32_t kLitSurfaceKind = 2u;  // r0[j].w of a lit sample that ended on a surface (kLitSurface, csrc/mcpt_probes.hip)
-// The sampled direct term (csrc/mcpt_direct.h) of n points into out[stride * i + 0..2], staged in pieces of at most stg.cap light samples
-// through arrays the caller owns: per piece k_direct_rays (csrc/mcpt_kernels.hip), launch_trace_closest over the compacted shadow rays
-// and k_direct_fold.  src: where the points and keys come from (DirectRays, csrc/mcpt_kernels.h; the staging and piece members are set
-// here).  pieces: the launches are added to it.  The result does not depend on the cut.
+// The sampled direct term (csrc/mcpt_direct.h) of n points into out[stride * i + 0..2], staged in the pieces of stg.cut -- the caller's
+// piece_cut(n, src.N, capacity, 1), whose staged() light samples every array here holds -- through arrays the caller owns: per piece
+// k_direct_rays (csrc/mcpt_kernels.hip), launch_trace_closest over the compacted shadow rays and k_direct_fold.  src: where the points
+// and keys come from (DirectRays, csrc/mcpt_kernels.h; the staging and piece members are set here).  pieces: the launches are added to
+// it.  The result does not depend on the cut.
 struct DirectStage {
     float4 *ray_o, *ray_d, *slot;
     uint4 *hit;
     uint32_t *n_rays;
-    uint64_t cap;
+    PieceCut cut;
     RetryList rl;
 };
 int direct_term(const DevScene &S, DirectRays src, uint64_t n, const DirectStage &stg, float *out, uint32_t stride, hipStream_t st, int32_t &pieces);

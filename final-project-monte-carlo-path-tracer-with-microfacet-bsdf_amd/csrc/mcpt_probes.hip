@@ -8,7 +8,8 @@
 //   k_probe_shade        one lane per (point, normal): sh::probe_shade from the coefficient buffer; eight 108-byte rows are read per lane
 //
 // Probe visibility (mcpt_query_probe_depth, mcpt_probe_shade_visible, mcpt_bake_probe_volume and their host forms; csrc/mcpt_probe_depth.h
-// states the rule).  Per chunk of the ray queries' staging buffers (QueryBufs, csrc/mcpt_host.h), on the caller's stream:
+// states the rule).  Per chunk of the ray queries' staging buffers (QueryBufs, csrc/mcpt_host.h; piece_cut of csrc/mcpt_direct.h cuts this
+// query and the direct term below into chunks, and sizes the staging), on the caller's stream:
 //   k_probe_depth_rays     one lane per (probe, sample): sensor_ray's whole-sphere ray straight into the staged float4 arrays, tmax = +inf
 //   closest hits           launch_trace_closest on the staged chunk, as run_query (csrc/mcpt_rayquery.hip) runs it: no second tree walk
 //   k_probe_depth_fold     one wave per probe, lane = texel of the 8 x 8 map: per block of 64 samples lane l prepares sample l (hit word,
@@ -425,30 +426,25 @@ void launch_lit_shade(const LitVolume &vol, uint32_t n, float4 *r0, const float4
 }
 
 int direct_term(const DevScene &S, DirectRays src, uint64_t n, const DirectStage &stg, float *out, uint32_t stride, hipStream_t st, int32_t &pieces) {
-    // A piece holds whole points when a point's samples fit the staging, else a run of one point's samples (the sum passes through `out`
-    // between launches).  Either way a point's additions run in sample order.
-    const uint64_t N = (uint64_t)src.N;
-    const uint64_t per = N <= stg.cap ? std::min<uint64_t>(n, stg.cap / N) : 1;  // points per launch
-    const uint64_t jmax = N <= stg.cap ? N : stg.cap;                            // samples of a point per launch
+    // Where a point's samples take several pieces (piece_cut, csrc/mcpt_direct.h) its sum passes through `out` between launches; either way
+    // a point's additions run in sample order.
     src.ray_o = stg.ray_o;
     src.ray_d = stg.ray_d;
     src.slot = stg.slot;
     src.n_rays = stg.n_rays;
-    for (uint64_t i0 = 0; i0 < n; i0 += per) {
-        src.i0 = (uint32_t)i0;
-        src.m = (uint32_t)std::min<uint64_t>(per, n - i0);
-        for (uint64_t j0 = 0; j0 < N; j0 += jmax) {
-            src.j0 = (uint32_t)j0;
-            src.jc = (uint32_t)std::min<uint64_t>(jmax, N - j0);
-            HIP_TRY(hipMemsetAsync(stg.n_rays, 0, sizeof(uint32_t), st));
-            launch_direct_rays(S, src, st);
-            launch_trace_closest(S, src.m * src.jc, stg.n_rays, stg.ray_o, stg.ray_d, stg.hit, stg.rl, st);
-            hipLaunchKernelGGL(k_direct_fold, dim3(probe_blocks(src.m)), dim3(kPbBlock), 0, st, src.i0, src.m, src.jc, j0 > 0 ? 1 : 0,
-                               j0 + src.jc == N ? 1 : 0, stg.slot, stg.ray_d, stg.hit, out, stride);
-            pieces++;
-        }
-    }
-    return MCPT_OK;
+    return for_each_piece(stg.cut, n, (uint64_t)src.N, [&](uint32_t i0, uint32_t m, uint32_t j0, uint32_t jc) -> int {
+        src.i0 = i0;
+        src.m = m;
+        src.j0 = j0;
+        src.jc = jc;
+        HIP_TRY(hipMemsetAsync(stg.n_rays, 0, sizeof(uint32_t), st));
+        launch_direct_rays(S, src, st);
+        launch_trace_closest(S, m * jc, stg.n_rays, stg.ray_o, stg.ray_d, stg.hit, stg.rl, st);
+        hipLaunchKernelGGL(k_direct_fold, dim3(probe_blocks(m)), dim3(kPbBlock), 0, st, i0, m, jc, j0 > 0 ? 1 : 0, j0 + jc == (uint32_t)src.N ? 1 : 0,
+                           stg.slot, stg.ray_d, stg.hit, out, stride);
+        pieces++;
+        return MCPT_OK;
+    });
 }
 
 void launch_lit_fold(uint32_t p0, uint32_t n_pix, int32_t aov_spp, const float4 *r0, const float4 *r2, float *lit, float *position, hipStream_t st) {
@@ -655,29 +651,23 @@ int mcpt_query_probe_depth(mcpt_scene *sc, const mcpt_probe_depth_params *pp, in
     mcpt_query_info qi;
     std::memset(&qi, 0, sizeof qi);
     HIP_TRY(hipSetDevice(sc->device));
-    // A chunk holds whole probes when a probe's samples fit it (their sums never leave the registers), else whole 64-sample blocks of one
-    // probe (the sums pass through `moments` between launches).  Either way a texel's additions run in sample order.
-    const uint64_t chunk = std::max<uint32_t>(sc->knobs.query_chunk, 64u);
-    const uint64_t spp = (uint64_t)p.spp;
-    const bool whole = spp <= chunk;
-    const uint64_t per = whole ? std::min<uint64_t>((uint64_t)n, chunk / spp) : 1;  // probes per launch
-    const uint64_t kmax = whole ? spp : chunk / 64 * 64;                               // samples of a probe per launch
+    // A launch holds whole probes when a probe's samples fit the staging (their sums never leave the registers), else whole 64-sample blocks
+    // of one probe (the sums pass through `moments` between launches).  Either way a texel's additions run in sample order.
+    const PieceCut cut = piece_cut((uint64_t)n, (uint64_t)p.spp, std::max<uint32_t>(sc->knobs.query_chunk, 64u), 64);
     RetryList rl;
-    const int sr = query_stage(sc, (uint32_t)(per * kmax), st, qi, rl);
+    const int sr = query_stage(sc, (uint32_t)cut.staged(), st, qi, rl);
     if (sr != MCPT_OK) return sr;
     QueryBufs &Q = sc->query;
-    for (uint64_t i0 = 0; i0 < (uint64_t)n; i0 += per) {
-        const uint32_t m = (uint32_t)std::min<uint64_t>(per, (uint64_t)n - i0);
-        for (uint64_t k0 = 0; k0 < spp; k0 += kmax) {
-            const uint32_t kc = (uint32_t)std::min<uint64_t>(kmax, spp - k0), rays = m * kc;
-            hipLaunchKernelGGL(k_probe_depth_rays, dim3(probe_blocks(rays)), dim3(kPbBlock), 0, st, origins, p.seed, (uint32_t)i0, kc,
-                               (uint32_t)p.sample_offset + (uint32_t)k0, rays, Q.ray_o.p, Q.ray_d.p);
-            launch_trace_closest(sc->view, rays, nullptr, Q.ray_o.p, Q.ray_d.p, Q.hit.p, rl, st);
-            hipLaunchKernelGGL(k_probe_depth_fold, dim3((m + kPbBlock / 64 - 1) / (kPbBlock / 64)), dim3(kPbBlock), 0, st, sc->view, Q.ray_o.p, Q.ray_d.p, Q.hit.p,
-                               (uint32_t)i0, m, kc, (p.accumulate || k0 > 0) ? 1 : 0, p.max_distance, moments, counts);
-            qi.launches++;
-        }
-    }
+    for_each_piece(cut, (uint64_t)n, (uint64_t)p.spp, [&](uint32_t i0, uint32_t m, uint32_t k0, uint32_t kc) -> int {
+        const uint32_t rays = m * kc;
+        hipLaunchKernelGGL(k_probe_depth_rays, dim3(probe_blocks(rays)), dim3(kPbBlock), 0, st, origins, p.seed, i0, kc, (uint32_t)p.sample_offset + k0, rays,
+                           Q.ray_o.p, Q.ray_d.p);
+        launch_trace_closest(sc->view, rays, nullptr, Q.ray_o.p, Q.ray_d.p, Q.hit.p, rl, st);
+        hipLaunchKernelGGL(k_probe_depth_fold, dim3((m + kPbBlock / 64 - 1) / (kPbBlock / 64)), dim3(kPbBlock), 0, st, sc->view, Q.ray_o.p, Q.ray_d.p, Q.hit.p,
+                           i0, m, kc, (p.accumulate || k0 > 0) ? 1 : 0, p.max_distance, moments, counts);
+        qi.launches++;
+        return MCPT_OK;
+    });
     const int fr = query_finish(sc, st, qi);
     if (fr != MCPT_OK) return fr;
     if (info) *info = qi;
@@ -702,22 +692,19 @@ int mcpt_query_direct(mcpt_scene *sc, const mcpt_direct_opts *op, int64_t n, con
     mcpt_query_info qi;
     std::memset(&qi, 0, sizeof qi);
     HIP_TRY(hipSetDevice(sc->device));
-    // (direct_term's cut of the call into pieces of at most `chunk` light samples)
-    const uint64_t chunk = std::max<uint32_t>(sc->knobs.query_chunk, 64u);
-    const uint64_t N = (uint64_t)op->n_samples;
-    const uint64_t per = N <= chunk ? std::min<uint64_t>((uint64_t)n, chunk / N) : 1, jmax = N <= chunk ? N : chunk;
+    const PieceCut cut = piece_cut((uint64_t)n, (uint64_t)op->n_samples, std::max<uint32_t>(sc->knobs.query_chunk, 64u), 1);
     const bool lit = sc->view.n_lights > 0;  // (an empty light table: exact zeros, no ray)
     RetryList rl;
-    const int sr = query_stage(sc, lit ? (uint32_t)(per * jmax) : 1u, st, qi, rl);
+    const int sr = query_stage(sc, lit ? (uint32_t)cut.staged() : 1u, st, qi, rl);
     if (sr != MCPT_OK) return sr;
     QueryBufs &Q = sc->query;
     if (!lit) {
         HIP_TRY(hipMemsetAsync(out, 0, (size_t)n * 3 * sizeof(float), st));
         qi.launches = 1;
     } else {
-        if (Q.direct_slot.n < per * jmax || !Q.direct_n.p) {
+        if (Q.direct_slot.n < cut.staged() || !Q.direct_n.p) {
             HIP_TRY(query_settle(sc));
-            HIP_TRY(Q.direct_slot.alloc(per * jmax));
+            HIP_TRY(Q.direct_slot.alloc(cut.staged()));
             HIP_TRY(Q.direct_n.alloc(1));
             qi.grew = 1;
         }
@@ -727,8 +714,7 @@ int mcpt_query_direct(mcpt_scene *sc, const mcpt_direct_opts *op, int64_t n, con
         src.seed = op->seed;
         src.key_sample = op->key_sample;
         src.N = op->n_samples;
-        const int dr = direct_term(sc->view, src, (uint64_t)n, DirectStage{Q.ray_o.p, Q.ray_d.p, Q.direct_slot.p, Q.hit.p, Q.direct_n.p, per * jmax, rl}, out, 3u, st,
-                                   qi.launches);
+        const int dr = direct_term(sc->view, src, (uint64_t)n, DirectStage{Q.ray_o.p, Q.ray_d.p, Q.direct_slot.p, Q.hit.p, Q.direct_n.p, cut, rl}, out, 3u, st, qi.launches);
         if (dr != MCPT_OK) return dr;
     }
     const int fr = query_finish(sc, st, qi);

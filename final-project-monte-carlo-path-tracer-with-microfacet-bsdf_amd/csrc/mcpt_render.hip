@@ -168,7 +168,7 @@ struct AovOwn {
 // the per-sample records in wave 1's, the keys in wave 1's path records, the retrace list of the closest-hit rays.  Otherwise (no render
 // yet on this scene) it uses buffers of its own for the call.  `chain`: the second ray list and the chain states of the specular chains
 // are needed too (in the workspace: vtx0 / vtx1 with wave 1's hits, wave 0's and wave 1's rec1, the sums in wave 0's rec0 and vtx2, the
-// count vtx_j[0]; chunks then hold at most `pool` rays).
+// count vtx_j[0]; chunks then hold at most `pool` rays); chain_bounces, below, is the loop a resolve runs over them.
 // max_rays > 0: no chunk holds more rays than that (at least aov_spp: the motion pass's map storage, motion_pass).
 // centre (mcpt_feature_opts; aov_spp is then 1): ray j of a chunk is the centre ray of pixel p0 + j, from k_centre_rays alone; the key
 // arrays are neither written nor read (nor allocated, where the call owns its buffers) and `seed` is not looked at.
@@ -205,29 +205,43 @@ int first_hit_chunks(mcpt_scene *sc, const CameraConst &cc, uint32_t seed, int32
     return MCPT_OK;
 }
 
+// The bounce loop of a chunk's specular chains, which aov_pass, lit_pass and motion_pass share: step(b, cur, m) launches the pass's chain
+// kernel on the m rays of list `cur`, whose samples have all followed b bounces (list 0 holds the chunk's n traced camera rays); the kernel
+// appends the rays that continue to list cur ^ 1 and counts them in n_next, which is read back once per bounce (the stream drains) before
+// their closest hits are traced.  The loop ends after the step of bounce spec_depth, or when no sample continues.  spec_depth 0: one
+// step, and n_next is neither cleared nor read.
+template <class Step>
+int chain_bounces(const DevScene &S, const AovPtrs &a, uint32_t n, int32_t spec_depth, hipStream_t st, Step &&step) {
+    uint32_t m = n;
+    for (int b = 0, cur = 0;; ++b, cur ^= 1) {
+        if (b < spec_depth) HIP_TRY(hipMemsetAsync(a.n_next, 0, sizeof(uint32_t), st));
+        step(b, cur, m);
+        if (b == spec_depth) break;
+        HIP_TRY(hipMemcpyAsync(&m, a.n_next, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (m == 0) break;
+        launch_trace_closest(S, m, nullptr, a.list_o[cur ^ 1], a.list_d[cur ^ 1], a.list_hit[cur ^ 1], a.rl, st);
+    }
+    return MCPT_OK;
+}
+
 }  // namespace
 
 // The AOV pass (include/mcpt.h): aov_dev[8m ..] for every pixel of the frame.  Per chunk k_aov_resolve, or with spec_depth > 0
-// (mcpt_render_aovs_ex) the specular chains -- k_aov_chain on the traced list, then up to spec_depth times k_trace_closest + k_aov_chain on
-// the compacted list of the samples that continue (its length read back once per bounce) -- and k_aov_fold.
+// (mcpt_render_aovs_ex) the specular chains -- chain_bounces: k_aov_chain on the traced list, then up to spec_depth times k_trace_closest +
+// k_aov_chain on the compacted list of the samples that continue -- and k_aov_fold.
 int mcpt::aov_pass(mcpt_scene *sc, const CameraConst &cc, uint32_t seed, int32_t aov_spp, int32_t spec_depth, bool centre, float *aov_dev, hipStream_t st) {
     const bool chain = spec_depth > 0;
     return first_hit_chunks(sc, cc, seed, aov_spp, centre, chain, 0, st, [&](const AovPtrs &a, uint32_t p0, uint32_t np, uint32_t n) -> int {
         if (!chain) {
             launch_aov_resolve(sc->view, n, a.list_o[0], a.list_d[0], a.list_hit[0], a.rec0, a.rec1, st);
         } else {
-            uint32_t m = n;  // rays in list `cur`, whose samples have all followed b bounces
-            for (int b = 0, cur = 0;; ++b, cur ^= 1) {
-                if (b < spec_depth) HIP_TRY(hipMemsetAsync(a.n_next, 0, sizeof(uint32_t), st));
+            const int rc = chain_bounces(sc->view, a, n, spec_depth, st, [&](int b, int cur, uint32_t m) {
                 launch_aov_chain(sc->view, m, b, spec_depth, a.list_o[cur], a.list_d[cur], a.list_hit[cur], b == 0 ? nullptr : a.chain_st[cur],
                                  b == 0 ? nullptr : a.chain_t[cur], a.rec0, a.rec1, a.list_o[cur ^ 1], a.list_d[cur ^ 1], a.chain_st[cur ^ 1],
                                  a.chain_t[cur ^ 1], a.n_next, st);
-                if (b == spec_depth) break;
-                HIP_TRY(hipMemcpyAsync(&m, a.n_next, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-                HIP_TRY(hipStreamSynchronize(st));
-                if (m == 0) break;
-                launch_trace_closest(sc->view, m, nullptr, a.list_o[cur ^ 1], a.list_d[cur ^ 1], a.list_hit[cur ^ 1], a.rl, st);
-            }
+            });
+            if (rc != MCPT_OK) return rc;
         }
         launch_aov_fold(p0, np, aov_spp, a.rec0, a.rec1, aov_dev, st);
         return MCPT_OK;
@@ -252,17 +266,11 @@ int mcpt::lit_pass(mcpt_scene *sc, const CameraConst &cc, uint32_t seed, int32_t
         }
         info.in_workspace = a.in_ws ? 1 : 0;
         info.chunks++;
-        uint32_t m = n;  // rays in list `cur`, whose samples have all followed b bounces
-        for (int b = 0, cur = 0;; ++b, cur ^= 1) {
-            if (b < spec_depth) HIP_TRY(hipMemsetAsync(a.n_next, 0, sizeof(uint32_t), st));
+        const int cr = chain_bounces(sc->view, a, n, spec_depth, st, [&](int b, int cur, uint32_t m) {
             launch_lit_terminal(sc->view, m, b, spec_depth, a.list_o[cur], a.list_d[cur], a.list_hit[cur], b == 0 ? nullptr : a.chain_st[cur], a.rec0, a.rec1,
                                 rec2, a.list_o[cur ^ 1], a.list_d[cur ^ 1], a.chain_st[cur ^ 1], a.n_next, st);
-            if (b == spec_depth) break;
-            HIP_TRY(hipMemcpyAsync(&m, a.n_next, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipStreamSynchronize(st));
-            if (m == 0) break;
-            launch_trace_closest(sc->view, m, nullptr, a.list_o[cur ^ 1], a.list_d[cur ^ 1], a.list_hit[cur ^ 1], a.rl, st);
-        }
+        });
+        if (cr != MCPT_OK) return cr;
         float4 *direct_d = nullptr;
         if (direct) {
             direct_d = a.chain_st[0];
@@ -280,8 +288,8 @@ int mcpt::lit_pass(mcpt_scene *sc, const CameraConst &cc, uint32_t seed, int32_t
                 src.aov_spp = aov_spp;
                 src.total = lookups_dev + 1;
                 if (!stage_cap) stage_cap = n;  // (the first chunk is the largest, and every list array holds at least its rays)
-                const uint64_t cap = stage_cap;
-                const int dr = direct_term(sc->view, src, n, DirectStage{a.list_o[0], a.list_d[0], a.list_o[1], a.list_hit[0], a.n_next, cap, a.rl},
+                const PieceCut cut = piece_cut(n, (uint64_t)direct->n_samples, stage_cap, 1);
+                const int dr = direct_term(sc->view, src, n, DirectStage{a.list_o[0], a.list_d[0], a.list_o[1], a.list_hit[0], a.n_next, cut, a.rl},
                                            reinterpret_cast<float *>(direct_d), 4u, st, pieces);
                 if (dr != MCPT_OK) return dr;
             }
@@ -336,7 +344,7 @@ uint64_t mcpt::motion_map_rays(uint64_t n_px, int32_t aov_spp) { return std::min
 
 // The motion pass (include/mcpt.h: mcpt_render_motion[_ex]): motion_dev[4m ..] for every pixel of the frame, from the rays and hits of the AOV
 // pass.  Per chunk k_motion_resolve and k_motion_fold (csrc/mcpt_temporal.hip); prev_tri / prev_sph are the snapshot's arrays, or the live
-// ones for a scene without a snapshot.  With spec_depth > 0 the specular chains: the bounce loop of aov_pass with k_motion_chain in
+// ones for a scene without a snapshot.  With spec_depth > 0 the specular chains: chain_bounces with k_motion_chain in
 // k_aov_chain's place, on the arrays of aov_in_workspace(.., chain = true) or AovOwn of which it uses the two ray lists with their hits,
 // chain_st[0 / 1] for {reflections, sample} of each list entry, rec0 for the records and n_next (chain_t and rec1 stay unused).  The maps,
 // 96 bytes per sample of a chunk, are aliased to nothing: they live in `maps` (room for map_rays samples, at least aov_spp: a sequence's,
@@ -362,18 +370,12 @@ int mcpt::motion_pass(mcpt_scene *sc, const CameraConst &cc, const CameraConst &
     }
     if (map_rays < (uint64_t)aov_spp) return fail(MCPT_ERR_ARG, "motion pass: the map storage holds less than one pixel's samples");
     const int rc = first_hit_chunks(sc, cc, seed, aov_spp, centre, true, map_rays, st, [&](const AovPtrs &a, uint32_t p0, uint32_t np, uint32_t n) -> int {
-        uint32_t m = n;  // rays in list `lc`, whose samples have all followed b bounces
-        for (int b = 0, lc = 0;; ++b, lc ^= 1) {
-            if (b < spec_depth) HIP_TRY(hipMemsetAsync(a.n_next, 0, sizeof(uint32_t), st));
+        const int cr = chain_bounces(sc->view, a, n, spec_depth, st, [&](int b, int lc, uint32_t m) {
             launch_motion_chain(sc->view, prev_tri, prev_sph, cur, prev, m, b, spec_depth, a.list_o[lc], a.list_d[lc], a.list_hit[lc],
                                 b == 0 ? nullptr : a.chain_st[lc], a.rec0, maps, (size_t)map_rays, a.list_o[lc ^ 1], a.list_d[lc ^ 1], a.chain_st[lc ^ 1],
                                 a.n_next, st);
-            if (b == spec_depth) break;
-            HIP_TRY(hipMemcpyAsync(&m, a.n_next, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipStreamSynchronize(st));
-            if (m == 0) break;
-            launch_trace_closest(sc->view, m, nullptr, a.list_o[lc ^ 1], a.list_d[lc ^ 1], a.list_hit[lc ^ 1], a.rl, st);
-        }
+        });
+        if (cr != MCPT_OK) return cr;
         launch_motion_fold(p0, np, aov_spp, a.rec0, motion_dev, st);
         return MCPT_OK;
     });

@@ -334,10 +334,12 @@ class DevicePositions:
             raise ValueError("DevicePositions: a non-null device address and a triangle count >= 0")
 
 
-_TORCH_TYPESTR = {"float32": "<f4", "float64": "<f8", "int32": "<i4", "uint8": "|u1"}
+# Element types of device buffers: name (numpy's, and the attribute of torch that is its dtype) -> the typestrs of
+# __cuda_array_interface__ that mean it, the one a torch tensor of that dtype stands for first.
+DTYPES = {"float32": ("<f4", "=f4", "|f4"), "float64": ("<f8", "=f8"), "int32": ("<i4", "=i4"), "uint8": ("|u1", "<u1", "=u1")}
 
 
-def _device_buffer(v, who, what, typestrs=("<f4", "=f4", "|f4"), type_name="float32"):
+def _device_buffer(v, who, what, dtype="float32"):
     """(address, shape) of a buffer in device memory -- anything with __cuda_array_interface__, or with data_ptr() and is_cuda (a torch
     tensor) -- or None for anything else.  Element type and C-contiguity are checked here (ValueError); the shape is the caller's to check."""
     cai = getattr(v, "__cuda_array_interface__", None)
@@ -348,12 +350,12 @@ def _device_buffer(v, who, what, typestrs=("<f4", "=f4", "|f4"), type_name="floa
         if not v.is_contiguous():
             raise ValueError("%s: a device tensor must be contiguous" % who)
         name = str(v.dtype).rsplit(".", 1)[-1]
-        shape, typestr, strides = tuple(int(d) for d in v.shape), _TORCH_TYPESTR.get(name, name), None
+        shape, typestr, strides = tuple(int(d) for d in v.shape), DTYPES.get(name, (name,))[0], None
         ptr = v.data_ptr()
     else:
         return None
-    if typestr not in typestrs:
-        raise ValueError("%s: %s must be %s, not %s" % (who, what, type_name, typestr))
+    if typestr not in DTYPES[dtype]:
+        raise ValueError("%s: %s must be %s, not %s" % (who, what, dtype, typestr))
     if strides is not None:
         want, acc = [], int(typestr[2:])
         for d in reversed(shape):
@@ -362,6 +364,58 @@ def _device_buffer(v, who, what, typestrs=("<f4", "=f4", "|f4"), type_name="floa
         if tuple(strides) != tuple(want):
             raise ValueError("%s: %s must be C-contiguous" % (who, what))
     return int(ptr), shape
+
+
+def _device_array(who, what, v, shape, dtype="float32"):
+    """The address of a C-contiguous device buffer of `dtype` and `shape`; a None in `shape` leaves that extent free (_rows).  ValueError
+    for anything that is not a device buffer, and for another element type, layout or shape."""
+    b = _device_buffer(v, who, what, dtype)
+    if b is None:
+        raise ValueError("%s: %s is a buffer in device memory (__cuda_array_interface__, or data_ptr() and is_cuda)" % (who, what))
+    if len(b[1]) != len(shape) or any(w is not None and w != d for w, d in zip(shape, b[1])):
+        raise ValueError("%s: %s has shape (%s), not %s" % (who, what, ", ".join("n" if w is None else str(w) for w in shape), b[1]))
+    return b[0]
+
+
+def _rows(who, what, v, width):
+    """(address, n) of a float32 (n, width) device input: the item count of a call comes from its first input."""
+    return _device_array(who, what, v, (None, width)), _device_buffer(v, who, what)[1][0]
+
+
+def _is_torch(*vs):
+    return all(hasattr(v, "data_ptr") and getattr(v, "is_cuda", False) for v in vs)
+
+
+def _device_of(*vs):
+    """The torch device of the first of a call's device inputs when all of them are torch tensors, else None: the call cannot allocate."""
+    return vs[0].device if _is_torch(*vs) else None
+
+
+def _outputs(who, spec, out, device, stream):
+    """The output buffers of a call -> (out, {name: address}, stream).  spec: name -> (shape, dtype name), in the call's order; the one
+    name None stands for a call whose `out` is a bare buffer, not a dict.  out None: torch.empty tensors on the torch device `device`
+    (None: the call cannot allocate, its device inputs are not torch tensors), and the stream then defaults to torch's current one
+    there.  Every buffer, allocated or the caller's, passes _device_array."""
+    bare = None in spec
+    if out is None:
+        if device is None:
+            raise ValueError("%s: out is required unless the device inputs are torch tensors" % who)
+        import torch
+        out = {w: torch.empty(shape, dtype=getattr(torch, dt), device=device) for w, (shape, dt) in spec.items()}
+        if stream is None:
+            stream = torch.cuda.current_stream(device).cuda_stream
+        if bare:
+            out = out[None]
+    bufs, ptrs = ({None: out} if bare else out), {}
+    for w, (shape, dt) in spec.items():
+        if w not in bufs:
+            raise ValueError("%s: out has no buffer for %r" % (who, w))
+        ptrs[w] = _device_array(who, "out" if bare else "out[%r]" % w, bufs[w], shape, dt)
+    return out, ptrs, stream
+
+
+def _row_shape(n, width):
+    return (n,) if width == 1 else (n, width)
 
 
 def _device_positions(v):
@@ -413,10 +467,9 @@ def _sensor_kind(who, kind):
     return SENSOR_KINDS[kind]
 
 
-# The outputs of HipScene.query_closest: name -> (element type of __cuda_array_interface__, its name, values per ray, torch dtype name)
-QUERY_OUTPUTS = {"t": (("<f8", "=f8"), "float64", 1, "float64"), "prim": (("<i4", "=i4"), "int32", 1, "int32"),
-                 "object": (("<i4", "=i4"), "int32", 1, "int32"), "uv": (("<f4", "=f4", "|f4"), "float32", 2, "float32"),
-                 "normal": (("<f4", "=f4", "|f4"), "float32", 3, "float32"), "point": (("<f4", "=f4", "|f4"), "float32", 3, "float32")}
+# The outputs of HipScene.query_closest: name -> (element type, values per ray)
+QUERY_OUTPUTS = {"t": ("float64", 1), "prim": ("int32", 1), "object": ("int32", 1), "uv": ("float32", 2), "normal": ("float32", 3),
+                 "point": ("float32", 3)}
 
 
 def _query_rays(who, origins, dirs, tmax):
@@ -427,24 +480,8 @@ def _query_rays(who, origins, dirs, tmax):
     if len(bo[1]) != 2 or bo[1][1] != 3 or bd[1] != bo[1]:
         raise ValueError("%s: origins and dirs have shape (n, 3), not %s and %s" % (who, bo[1], bd[1]))
     n = bo[1][0]
-    pt = 0
-    if tmax is not None:
-        bt = _device_buffer(tmax, who, "tmax")
-        if bt is None:
-            raise ValueError("%s: tmax is a buffer in device memory" % who)
-        if bt[1] != (n,):
-            raise ValueError("%s: tmax has shape (%d,), not %s" % (who, n, bt[1]))
-        pt = bt[0]
+    pt = _device_array(who, "tmax", tmax, (n,)) if tmax is not None else 0
     return n, RayBuffers(bo[0] or None, bd[0] or None, pt or None)
-
-
-def _query_output(who, name, v, n, typestrs, type_name, width):
-    b = _device_buffer(v, who, "out[%r]" % name, typestrs, type_name)
-    if b is None:
-        raise ValueError("%s: out[%r] is a buffer in device memory" % (who, name))
-    if b[1] != ((n,) if width == 1 else (n, width)):
-        raise ValueError("%s: out[%r] has shape %s, not %s" % (who, name, (n,) if width == 1 else (n, width), b[1]))
-    return b[0]
 
 
 class LightmapDesc(C.Structure):
@@ -464,10 +501,8 @@ class LightmapInfo(C.Structure):
                 "ms_radiance": float(self.ms_radiance), "ms_scatter": float(self.ms_scatter)}
 
 
-# The outputs of HipScene.lightmap_texels: name -> (element types of __cuda_array_interface__, type name, values per texel, numpy dtype)
-LIGHTMAP_OUTPUTS = {"texel": (("<i4", "=i4"), "int32", 1, np.int32), "prim": (("<i4", "=i4"), "int32", 1, np.int32),
-                    "bary": (("<f4", "=f4", "|f4"), "float32", 2, np.float32), "origins": (("<f4", "=f4", "|f4"), "float32", 3, np.float32),
-                    "normals": (("<f4", "=f4", "|f4"), "float32", 3, np.float32)}
+# The outputs of HipScene.lightmap_texels: name -> (element type, values per texel)
+LIGHTMAP_OUTPUTS = {"texel": ("int32", 1), "prim": ("int32", 1), "bary": ("float32", 2), "origins": ("float32", 3), "normals": ("float32", 3)}
 
 
 def _lightmap_desc(object, width, height, flip_normals=False):
@@ -499,16 +534,6 @@ def _probe_grid(who, origin, spacing, dims):
     return ProbeGrid((C.c_float * 3)(*o), (C.c_float * 3)(*s), (C.c_int32 * 3)(*d), (C.c_int32 * 3)(0, 0, 0)), d[0] * d[1] * d[2]
 
 
-def _probe_rows(who, what, v, width, n=None):
-    """The device address and row count of a float32, C-contiguous (n, width) device buffer."""
-    b = _device_buffer(v, who, what)
-    if b is None:
-        raise ValueError("%s: %s is a buffer in device memory (__cuda_array_interface__, or data_ptr() and is_cuda)" % (who, what))
-    if len(b[1]) != 2 or b[1][1] != width or (n is not None and b[1][0] != n):
-        raise ValueError("%s: %s has shape (%s, %d), not %s" % (who, what, "n" if n is None else n, width, b[1]))
-    return b[0], b[1][0]
-
-
 class ProbeDepthParams(C.Structure):
     _fields_ = [("seed", C.c_uint32), ("spp", C.c_int32), ("sample_offset", C.c_int32), ("accumulate", C.c_int32), ("max_distance", C.c_float),
                 ("reserved", C.c_int32 * 3)]
@@ -520,6 +545,11 @@ class ProbeVisibility(C.Structure):
 
 class ProbeOpts(C.Structure):
     _fields_ = [("indirect_only", C.c_int32), ("reserved", C.c_int32 * 7)]
+
+
+def _probe_opts(indirect_only):
+    """The options argument of the probe calls' _ex entries: None (the plain call, include/mcpt.h) unless indirect_only is set."""
+    return C.byref(ProbeOpts(indirect_only=1)) if indirect_only else None
 
 
 class LitDirectOpts(C.Structure):
@@ -590,20 +620,6 @@ def _lit_opts(who, aov_spp, specular_depth, centre, seed):
     if centre and aov_spp > 1:
         raise ValueError("%s: centre takes one ray per pixel (aov_spp 0 or 1), not %d" % (who, aov_spp))
     return LitOpts(aov_spp, specular_depth, centre, int(seed) & 0xffffffff, (C.c_int32 * 4)(0, 0, 0, 0))
-
-
-def _probe_counts(who, what, v, n):
-    """The device address of an int32, C-contiguous (n, 2) device buffer."""
-    b = _device_buffer(v, who, what, ("<i4", "=i4"), "int32")
-    if b is None:
-        raise ValueError("%s: %s is a buffer in device memory (__cuda_array_interface__, or data_ptr() and is_cuda)" % (who, what))
-    if b[1] != (n, 2):
-        raise ValueError("%s: %s has shape (%d, 2), not %s" % (who, what, n, b[1]))
-    return b[0]
-
-
-def _is_torch(*vs):
-    return all(hasattr(v, "data_ptr") and getattr(v, "is_cuda", False) for v in vs)
 
 
 def _vertex_items(items, n_tri_of):
@@ -1031,7 +1047,7 @@ def lightmap_texels(sd, object, width, height, flip_normals=False):
     cap = max(int(width), 0) * max(int(height), 0)
     if cap > (2 ** 31 - 1) // 3:
         cap = 0  # (the library refuses the size before it writes anything)
-    out = {w: np.zeros((cap,) if k == 1 else (cap, k), dt) for w, (_, _, k, dt) in LIGHTMAP_OUTPUTS.items()}
+    out = {w: np.zeros(_row_shape(cap, k), dt) for w, (dt, k) in LIGHTMAP_OUTPUTS.items()}
     n = C.c_int64(0)
     _check(lib().mcpt_lightmap_texels_host(C.byref(d), C.byref(ld), *[_ptr(out[w]) for w in LIGHTMAP_OUTPUTS], C.byref(n)))
     return {w: out[w][:n.value].copy() for w in LIGHTMAP_OUTPUTS}
@@ -1836,20 +1852,9 @@ class HipScene:
         if not want or any(w not in QUERY_OUTPUTS for w in want) or len(set(want)) != len(want):
             raise ValueError("%s: want is a non-empty selection of %s without repeats, not %r" % (who, tuple(QUERY_OUTPUTS), want))
         n, rays = _query_rays(who, origins, dirs, tmax)
-        if out is None:
-            if not _is_torch(origins, dirs):
-                raise ValueError("%s: out is required unless the rays are torch tensors" % who)
-            import torch
-            out = {w: torch.empty((n,) if QUERY_OUTPUTS[w][2] == 1 else (n, QUERY_OUTPUTS[w][2]), dtype=getattr(torch, QUERY_OUTPUTS[w][3]), device=origins.device)
-                   for w in want}
-            if stream is None:
-                stream = torch.cuda.current_stream(origins.device).cuda_stream
-        hits = HitBuffers()
-        for w in want:
-            if w not in out:
-                raise ValueError("%s: out has no buffer for %r" % (who, w))
-            ts, tn, width, _ = QUERY_OUTPUTS[w]
-            setattr(hits, w, _query_output(who, w, out[w], n, ts, tn, width) or None)
+        spec = {w: (_row_shape(n, QUERY_OUTPUTS[w][1]), QUERY_OUTPUTS[w][0]) for w in want}
+        out, ptrs, stream = _outputs(who, spec, out, _device_of(origins, dirs), stream)
+        hits = HitBuffers(**{w: ptrs[w] or None for w in want})
         info = QueryInfo()
         _check(self.L.mcpt_query_closest(self.h, n, C.byref(rays), C.byref(hits), C.c_void_p(int(stream or 0)), C.byref(info)), L=self.L)
         return {w: out[w] for w in want}, info.as_dict()
@@ -1862,16 +1867,9 @@ class HipScene:
         if tmax is None:
             raise ValueError("%s: tmax is required" % who)
         n, rays = _query_rays(who, origins, dirs, tmax)
-        if out is None:
-            if not _is_torch(origins, dirs):
-                raise ValueError("%s: out is required unless the rays are torch tensors" % who)
-            import torch
-            out = torch.empty((n,), dtype=torch.uint8, device=origins.device)
-            if stream is None:
-                stream = torch.cuda.current_stream(origins.device).cuda_stream
-        p = _query_output(who, "occluded", out, n, ("|u1", "<u1", "=u1"), "uint8", 1)
+        out, ptrs, stream = _outputs(who, {None: ((n,), "uint8")}, out, _device_of(origins, dirs), stream)
         info = QueryInfo()
-        _check(self.L.mcpt_query_occluded(self.h, n, C.byref(rays), C.c_void_p(p or 0), C.c_void_p(int(stream or 0)), C.byref(info)), L=self.L)
+        _check(self.L.mcpt_query_occluded(self.h, n, C.byref(rays), C.c_void_p(ptrs[None]), C.c_void_p(int(stream or 0)), C.byref(info)), L=self.L)
         return out, info.as_dict()
 
     def query_radiance(self, origins, dirs, kind="ray", variance=False, out=None, stream=None, **params):
@@ -1887,20 +1885,9 @@ class HipScene:
         k = _sensor_kind(who, kind)
         n, rays = _query_rays(who, origins, dirs, None)
         names = ("radiance", "variance") if variance else ("radiance",)
-        if out is None:
-            if not _is_torch(origins, dirs):
-                raise ValueError("%s: out is required unless the sensors are torch tensors" % who)
-            import torch
-            out = {w: torch.empty((n, 3), dtype=torch.float32, device=origins.device) for w in names}
-            if stream is None:
-                stream = torch.cuda.current_stream(origins.device).cuda_stream
-        ptrs = []
-        for w in names:
-            if w not in out:
-                raise ValueError("%s: out has no buffer for %r" % (who, w))
-            ptrs.append(_query_output(who, w, out[w], n, ("<f4", "=f4", "|f4"), "float32", 3) or None)
+        out, ptrs, stream = _outputs(who, {w: ((n, 3), "float32") for w in names}, out, _device_of(origins, dirs), stream)
         sensors = SensorBuffers(rays.origins, rays.dirs, k, (C.c_int32 * 3)(0, 0, 0))
-        outs = SensorOutputs(ptrs[0], ptrs[1] if variance else None)
+        outs = SensorOutputs(ptrs["radiance"] or None, ptrs.get("variance") or None)
         p = self.params(**params)
         st = Stats()
         _check(self.L.mcpt_query_radiance(self.h, C.byref(p), n, C.byref(sensors), C.byref(outs), C.c_void_p(int(stream or 0)), C.byref(st)), L=self.L)
@@ -1927,25 +1914,10 @@ class HipScene:
         d = _lightmap_desc(object, width, height, flip_normals)
         cap = max(int(width), 0) * max(int(height), 0)
         made = out is None
-        if made:
-            import torch
-            dev = self._torch_device()
-            rows = cap if cap <= (2 ** 31 - 1) // 3 else 0  # (the library refuses the size before it writes anything)
-            out = {w: torch.empty((rows,) if LIGHTMAP_OUTPUTS[w][2] == 1 else (rows, LIGHTMAP_OUTPUTS[w][2]),
-                                  dtype=getattr(torch, LIGHTMAP_OUTPUTS[w][1]), device=dev) for w in want}
-            if stream is None:
-                stream = torch.cuda.current_stream(dev).cuda_stream
-        bufs = LightmapTexelsOut()
-        for w in want:
-            if w not in out:
-                raise ValueError("%s: out has no buffer for %r" % (who, w))
-            ts, tn, k, _ = LIGHTMAP_OUTPUTS[w]
-            b = _device_buffer(out[w], who, "out[%r]" % w, ts, tn)
-            if b is None:
-                raise ValueError("%s: out[%r] is a buffer in device memory" % (who, w))
-            if not made and b[1] != ((cap,) if k == 1 else (cap, k)):
-                raise ValueError("%s: out[%r] has shape %s, not %s" % (who, w, (cap,) if k == 1 else (cap, k), b[1]))
-            setattr(bufs, w, b[0] or None)
+        rows = 0 if made and cap > (2 ** 31 - 1) // 3 else cap  # (the library refuses the size before it writes anything)
+        spec = {w: (_row_shape(rows, LIGHTMAP_OUTPUTS[w][1]), LIGHTMAP_OUTPUTS[w][0]) for w in want}
+        out, ptrs, stream = _outputs(who, spec, out, self._torch_device() if made else None, stream)
+        bufs = LightmapTexelsOut(**{w: ptrs[w] or None for w in want})
         n = C.c_int64(0)
         _check(self.L.mcpt_lightmap_texels(self.h, C.byref(d), C.byref(bufs), C.byref(n), C.c_void_p(int(stream or 0))), L=self.L)
         return {w: (out[w][:n.value] if made else out[w]) for w in want}, int(n.value)
@@ -1954,28 +1926,11 @@ class HipScene:
         """The device addresses of the planes `names` (image / variance: float32 (height, width, 3); coverage: uint8 (height, width)) in
         `out`, torch tensors on the scene's device when out is None -> (out, {name: address}, stream)."""
         W, H = int(width), int(height)
-        if out is None:
-            import torch
-            dev = self._torch_device()
-            ok = W >= 1 and H >= 1 and W * H <= (2 ** 31 - 1) // 3  # (otherwise the library refuses before it writes anything)
-            out = {w: torch.empty(((H, W) if ok else (1, 1)) + (() if w == "coverage" else (3,)), dtype=torch.uint8 if w == "coverage" else torch.float32,
-                                  device=dev) for w in names}
-            if stream is None:
-                stream = torch.cuda.current_stream(dev).cuda_stream
-            return out, {w: out[w].data_ptr() for w in names}, stream
-        ptrs = {}
-        for w in names:
-            if w not in out:
-                raise ValueError("%s: out has no buffer for %r" % (who, w))
-            ts, tn = ((("|u1", "<u1", "=u1"), "uint8") if w == "coverage" else (("<f4", "=f4", "|f4"), "float32"))
-            b = _device_buffer(out[w], who, "out[%r]" % w, ts, tn)
-            if b is None:
-                raise ValueError("%s: out[%r] is a buffer in device memory" % (who, w))
-            shape = (H, W) if w == "coverage" else (H, W, 3)
-            if b[1] != shape:
-                raise ValueError("%s: out[%r] has shape %s, not %s" % (who, w, shape, b[1]))
-            ptrs[w] = b[0]
-        return out, ptrs, stream
+        made = out is None
+        if made and not (W >= 1 and H >= 1 and W * H <= (2 ** 31 - 1) // 3):
+            H = W = 1  # (the library refuses the size before it writes anything)
+        spec = {w: ((H, W), "uint8") if w == "coverage" else ((H, W, 3), "float32") for w in names}
+        return _outputs(who, spec, out, self._torch_device() if made else None, stream)
 
     def lightmap_scatter(self, object, width, height, texel, values, dilate=2, coverage=True, out=None, stream=None):
         """mcpt_lightmap_scatter: image[texel[i]] = values[i] on a zero map, then `dilate` rounds of the dilation of include/mcpt.h ->
@@ -1983,7 +1938,7 @@ class HipScene:
         (torch tensors, __cuda_array_interface__) are read in place, numpy arrays are staged through torch.  out: dict with "image" (and
         "coverage") device buffers; None: torch tensors.  Enqueued on `stream` (default with torch inputs or outputs: torch's current one)."""
         who = "lightmap_scatter"
-        bt, bv = _device_buffer(texel, who, "texel", ("<i4", "=i4"), "int32"), _device_buffer(values, who, "values")
+        bt, bv = _device_buffer(texel, who, "texel", "int32"), _device_buffer(values, who, "values")
         keep = []
         if bt is None or bv is None:
             import torch
@@ -1991,7 +1946,7 @@ class HipScene:
             texel = torch.from_numpy(np.ascontiguousarray(texel, dtype=np.int32).reshape(-1)).to(dev)
             values = torch.from_numpy(np.ascontiguousarray(values, dtype=np.float32).reshape(-1, 3)).to(dev)
             keep = [texel, values]
-            bt, bv = _device_buffer(texel, who, "texel", ("<i4", "=i4"), "int32"), _device_buffer(values, who, "values")
+            bt, bv = _device_buffer(texel, who, "texel", "int32"), _device_buffer(values, who, "values")
             if stream is None:
                 stream = torch.cuda.current_stream(dev).cuda_stream
         if len(bt[1]) != 1 or bv[1] != (bt[1][0], 3):
@@ -2050,30 +2005,17 @@ class HipScene:
         is a torch tensor.  params: the keywords of HipScene.params.  The call blocks until the outputs are written.  indirect_only
         (mcpt_query_probes_ex): a sample whose first ray hits an emitter contributes 0, the volume that goes with query_direct."""
         who = "query_probes"
-        po, n = _probe_rows(who, "origins", origins, 3)
+        po, n = _rows(who, "origins", origins, 3)
         if n > (2 ** 31 - 1) // 27:
             raise ValueError("%s: at most (2^31 - 1) / 27 probes, not %d" % (who, n))
         names = ("sh",) + (("radiance",) if radiance or variance else ()) + (("variance",) if variance else ())
-        if out is None:
-            if not _is_torch(origins):
-                raise ValueError("%s: out is required unless origins is a torch tensor" % who)
-            import torch
-            out = {w: torch.empty((n, 27 if w == "sh" else 3), dtype=torch.float32, device=origins.device) for w in names}
-            if stream is None:
-                stream = torch.cuda.current_stream(origins.device).cuda_stream
-        ptrs = {}
-        for w in names:
-            if w not in out:
-                raise ValueError("%s: out has no buffer for %r" % (who, w))
-            ptrs[w] = _probe_rows(who, "out[%r]" % w, out[w], 27 if w == "sh" else 3, n)[0] or None
-        outs = ProbeOutputs(ptrs["sh"], ptrs.get("radiance"), ptrs.get("variance"), None)
+        spec = {w: ((n, 27 if w == "sh" else 3), "float32") for w in names}
+        out, ptrs, stream = _outputs(who, spec, out, _device_of(origins), stream)
+        outs = ProbeOutputs(ptrs["sh"] or None, ptrs.get("radiance") or None, ptrs.get("variance") or None, None)
         p = self.params(**params)
         st = Stats()
-        if indirect_only:
-            _check(self.L.mcpt_query_probes_ex(self.h, C.byref(p), n, C.c_void_p(po or 0), C.byref(outs), C.c_void_p(int(stream or 0)), C.byref(st),
-                                               C.byref(ProbeOpts(indirect_only=1))), L=self.L)
-        else:
-            _check(self.L.mcpt_query_probes(self.h, C.byref(p), n, C.c_void_p(po or 0), C.byref(outs), C.c_void_p(int(stream or 0)), C.byref(st)), L=self.L)
+        _check(self.L.mcpt_query_probes_ex(self.h, C.byref(p), n, C.c_void_p(po or 0), C.byref(outs), C.c_void_p(int(stream or 0)), C.byref(st),
+                                           _probe_opts(indirect_only)), L=self.L)
         return out["sh"], out.get("radiance") if "radiance" in names else None, (out["variance"] if variance else None), st
 
     def probe_rays(self, origins, sensor, sample, seed=1):
@@ -2096,18 +2038,11 @@ class HipScene:
         on `stream` without a synchronisation."""
         who = "probe_shade"
         g, m = _probe_grid(who, origin, spacing, dims)
-        ps = _probe_rows(who, "sh", sh, 27, m)[0]
-        pp, n = _probe_rows(who, "points", points, 3)
-        pn = _probe_rows(who, "normals", normals, 3, n)[0]
-        if out is None:
-            if not _is_torch(sh, points, normals):
-                raise ValueError("%s: out is required unless the inputs are torch tensors" % who)
-            import torch
-            out = torch.empty((n, 3), dtype=torch.float32, device=points.device)
-            if stream is None:
-                stream = torch.cuda.current_stream(points.device).cuda_stream
-        pout = _probe_rows(who, "out", out, 3, n)[0]
-        _check(self.L.mcpt_probe_shade(self.h, C.byref(g), C.c_void_p(ps or 0), n, C.c_void_p(pp or 0), C.c_void_p(pn or 0), C.c_void_p(pout or 0),
+        ps = _device_array(who, "sh", sh, (m, 27))
+        pp, n = _rows(who, "points", points, 3)
+        pn = _device_array(who, "normals", normals, (n, 3))
+        out, ptrs, stream = _outputs(who, {None: ((n, 3), "float32")}, out, _device_of(points, normals, sh), stream)
+        _check(self.L.mcpt_probe_shade(self.h, C.byref(g), C.c_void_p(ps or 0), n, C.c_void_p(pp or 0), C.c_void_p(pn or 0), C.c_void_p(ptrs[None]),
                                        C.c_void_p(int(stream or 0))), L=self.L)
         return out
 
@@ -2117,20 +2052,11 @@ class HipScene:
         (mcpt_bake_probe_grid_ex)."""
         who = "bake_probe_grid"
         g, m = _probe_grid(who, origin, spacing, dims)
-        if out is None:
-            import torch
-            dev = self._torch_device()
-            out = torch.empty((m, 27), dtype=torch.float32, device=dev)
-            if stream is None:
-                stream = torch.cuda.current_stream(dev).cuda_stream
-        ps = _probe_rows(who, "out", out, 27, m)[0]
+        out, ptrs, stream = _outputs(who, {None: ((m, 27), "float32")}, out, self._torch_device() if out is None else None, stream)
         p = self.params(**params)
         st = Stats()
-        if indirect_only:
-            _check(self.L.mcpt_bake_probe_grid_ex(self.h, C.byref(g), C.byref(p), C.c_void_p(ps or 0), C.c_void_p(int(stream or 0)), C.byref(st),
-                                                  C.byref(ProbeOpts(indirect_only=1))), L=self.L)
-        else:
-            _check(self.L.mcpt_bake_probe_grid(self.h, C.byref(g), C.byref(p), C.c_void_p(ps or 0), C.c_void_p(int(stream or 0)), C.byref(st)), L=self.L)
+        _check(self.L.mcpt_bake_probe_grid_ex(self.h, C.byref(g), C.byref(p), C.c_void_p(ptrs[None]), C.c_void_p(int(stream or 0)), C.byref(st),
+                                              _probe_opts(indirect_only)), L=self.L)
         return out, st
 
     def query_probe_depth(self, origins, spp, max_distance, seed=1, sample_offset=0, accumulate=0, out=None, stream=None):
@@ -2140,27 +2066,16 @@ class HipScene:
         with "moments" and "counts" device buffers (required with accumulate), or None when origins is a torch tensor.  Enqueued on
         `stream` without a synchronisation, through the staging buffers of the ray queries."""
         who = "query_probe_depth"
-        po, n = _probe_rows(who, "origins", origins, 3)
+        po, n = _rows(who, "origins", origins, 3)
         if n > (2 ** 31 - 1) // PROBE_DEPTH_ROW:
             raise ValueError("%s: at most (2^31 - 1) / 192 probes, not %d" % (who, n))
         p = _probe_depth_params(who, spp, max_distance, seed, sample_offset, accumulate)
-        if out is None:
-            if not _is_torch(origins):
-                raise ValueError("%s: out is required unless origins is a torch tensor" % who)
-            if p.accumulate:
-                raise ValueError("%s: accumulate continues the buffers given in out" % who)
-            import torch
-            out = {"moments": torch.empty((n, PROBE_DEPTH_ROW), dtype=torch.float32, device=origins.device),
-                   "counts": torch.empty((n, 2), dtype=torch.int32, device=origins.device)}
-            if stream is None:
-                stream = torch.cuda.current_stream(origins.device).cuda_stream
-        for w in ("moments", "counts"):
-            if w not in out:
-                raise ValueError("%s: out has no buffer for %r" % (who, w))
-        pm = _probe_rows(who, "out['moments']", out["moments"], PROBE_DEPTH_ROW, n)[0]
-        pn = _probe_counts(who, "out['counts']", out["counts"], n)
+        if out is None and p.accumulate:
+            raise ValueError("%s: accumulate continues the buffers given in out" % who)
+        spec = {"moments": ((n, PROBE_DEPTH_ROW), "float32"), "counts": ((n, 2), "int32")}
+        out, ptrs, stream = _outputs(who, spec, out, _device_of(origins), stream)
         info = QueryInfo()
-        _check(self.L.mcpt_query_probe_depth(self.h, C.byref(p), n, C.c_void_p(po or 0), C.c_void_p(pm or 0), C.c_void_p(pn or 0),
+        _check(self.L.mcpt_query_probe_depth(self.h, C.byref(p), n, C.c_void_p(po or 0), C.c_void_p(ptrs["moments"]), C.c_void_p(ptrs["counts"]),
                                              C.c_void_p(int(stream or 0)), C.byref(info)), L=self.L)
         return out["moments"], out["counts"], info.as_dict()
 
@@ -2170,23 +2085,16 @@ class HipScene:
         device buffer, mcpt_query_info as a dict).  Point i draws with the Philox key (seed, i) and the sample word key_sample.  out may
         be None with torch inputs.  Enqueued on `stream` without a synchronisation, through the staging buffers of the ray queries."""
         who = "query_direct"
-        pp, n = _probe_rows(who, "points", points, 3)
-        pn = _probe_rows(who, "normals", normals, 3, n)[0]
+        pp, n = _rows(who, "points", points, 3)
+        pn = _device_array(who, "normals", normals, (n, 3))
         if not 1 <= int(n_samples) <= DIRECT_MAX_SAMPLES:
             raise ValueError("%s: n_samples must be in 1 .. %d, not %r" % (who, DIRECT_MAX_SAMPLES, n_samples))
         if n * int(n_samples) > 2 ** 31 - 1:
             raise ValueError("%s: n * n_samples must be at most 2^31 - 1" % who)
-        if out is None:
-            if not _is_torch(points, normals):
-                raise ValueError("%s: out is required unless the inputs are torch tensors" % who)
-            import torch
-            out = torch.empty((n, 3), dtype=torch.float32, device=points.device)
-            if stream is None:
-                stream = torch.cuda.current_stream(points.device).cuda_stream
-        pout = _probe_rows(who, "out", out, 3, n)[0]
+        out, ptrs, stream = _outputs(who, {None: ((n, 3), "float32")}, out, _device_of(points, normals), stream)
         o = DirectOpts(seed=int(seed) & 0xffffffff, n_samples=int(n_samples), key_sample=int(key_sample) & 0xffffffff)
         info = QueryInfo()
-        _check(self.L.mcpt_query_direct(self.h, C.byref(o), n, C.c_void_p(pp or 0), C.c_void_p(pn or 0), C.c_void_p(pout or 0),
+        _check(self.L.mcpt_query_direct(self.h, C.byref(o), n, C.c_void_p(pp or 0), C.c_void_p(pn or 0), C.c_void_p(ptrs[None]),
                                         C.c_void_p(int(stream or 0)), C.byref(info)), L=self.L)
         return out, info.as_dict()
 
@@ -2201,27 +2109,15 @@ class HipScene:
         if m > (2 ** 31 - 1) // PROBE_DEPTH_ROW:
             raise ValueError("%s: at most (2^31 - 1) / 192 probes, not %d" % (who, m))
         o = _probe_visibility(who, normal_bias, backface_max)
-        ps = _probe_rows(who, "sh", sh, 27, m)[0]
-        pm = _probe_rows(who, "moments", moments, PROBE_DEPTH_ROW, m)[0]
-        pc = _probe_counts(who, "counts", counts, m)
-        pp, n = _probe_rows(who, "points", points, 3)
-        pn = _probe_rows(who, "normals", normals, 3, n)[0]
-        pw = 0
-        if weight is not None:
-            b = _device_buffer(weight, who, "weight")
-            if b is None or b[1] != (n,):
-                raise ValueError("%s: weight is a float32 device buffer of shape (%d,)" % (who, n))
-            pw = b[0]
-        if out is None:
-            if not _is_torch(sh, moments, counts, points, normals):
-                raise ValueError("%s: out is required unless the inputs are torch tensors" % who)
-            import torch
-            out = torch.empty((n, 3), dtype=torch.float32, device=points.device)
-            if stream is None:
-                stream = torch.cuda.current_stream(points.device).cuda_stream
-        pout = _probe_rows(who, "out", out, 3, n)[0]
+        ps = _device_array(who, "sh", sh, (m, 27))
+        pm = _device_array(who, "moments", moments, (m, PROBE_DEPTH_ROW))
+        pc = _device_array(who, "counts", counts, (m, 2), "int32")
+        pp, n = _rows(who, "points", points, 3)
+        pn = _device_array(who, "normals", normals, (n, 3))
+        pw = _device_array(who, "weight", weight, (n,)) if weight is not None else 0
+        out, ptrs, stream = _outputs(who, {None: ((n, 3), "float32")}, out, _device_of(points, normals, sh, moments, counts), stream)
         _check(self.L.mcpt_probe_shade_visible(self.h, C.byref(g), C.c_void_p(ps or 0), C.c_void_p(pm or 0), C.c_void_p(pc or 0), C.byref(o), n,
-                                               C.c_void_p(pp or 0), C.c_void_p(pn or 0), C.c_void_p(pout or 0), C.c_void_p(pw or 0),
+                                               C.c_void_p(pp or 0), C.c_void_p(pn or 0), C.c_void_p(ptrs[None]), C.c_void_p(pw or 0),
                                                C.c_void_p(int(stream or 0))), L=self.L)
         return out
 
@@ -2234,27 +2130,12 @@ class HipScene:
         if m > (2 ** 31 - 1) // PROBE_DEPTH_ROW:
             raise ValueError("%s: at most (2^31 - 1) / 192 probes, not %d" % (who, m))
         dp = _probe_depth_params(who, depth_spp, max_distance, depth_seed)
-        if out is None:
-            import torch
-            dev = self._torch_device()
-            out = {"sh": torch.empty((m, 27), dtype=torch.float32, device=dev), "moments": torch.empty((m, PROBE_DEPTH_ROW), dtype=torch.float32, device=dev),
-                   "counts": torch.empty((m, 2), dtype=torch.int32, device=dev)}
-            if stream is None:
-                stream = torch.cuda.current_stream(dev).cuda_stream
-        for w in ("sh", "moments", "counts"):
-            if w not in out:
-                raise ValueError("%s: out has no buffer for %r" % (who, w))
-        ps = _probe_rows(who, "out['sh']", out["sh"], 27, m)[0]
-        pm = _probe_rows(who, "out['moments']", out["moments"], PROBE_DEPTH_ROW, m)[0]
-        pn = _probe_counts(who, "out['counts']", out["counts"], m)
+        spec = {"sh": ((m, 27), "float32"), "moments": ((m, PROBE_DEPTH_ROW), "float32"), "counts": ((m, 2), "int32")}
+        out, ptrs, stream = _outputs(who, spec, out, self._torch_device() if out is None else None, stream)
         p = self.params(**params)
         st = Stats()
-        if indirect_only:
-            _check(self.L.mcpt_bake_probe_volume_ex(self.h, C.byref(g), C.byref(p), C.byref(dp), C.c_void_p(ps or 0), C.c_void_p(pm or 0), C.c_void_p(pn or 0),
-                                                    C.c_void_p(int(stream or 0)), C.byref(st), C.byref(ProbeOpts(indirect_only=1))), L=self.L)
-        else:
-            _check(self.L.mcpt_bake_probe_volume(self.h, C.byref(g), C.byref(p), C.byref(dp), C.c_void_p(ps or 0), C.c_void_p(pm or 0), C.c_void_p(pn or 0),
-                                                 C.c_void_p(int(stream or 0)), C.byref(st)), L=self.L)
+        _check(self.L.mcpt_bake_probe_volume_ex(self.h, C.byref(g), C.byref(p), C.byref(dp), C.c_void_p(ptrs["sh"]), C.c_void_p(ptrs["moments"]),
+                                                C.c_void_p(ptrs["counts"]), C.c_void_p(int(stream or 0)), C.byref(st), _probe_opts(indirect_only)), L=self.L)
         return out["sh"], out["moments"], out["counts"], st
 
     def render_probe_lit(self, origin, spacing, dims, sh, moments=None, counts=None, normal_bias=0.0, backface_max=0.25, aov_spp=0, specular_depth=0,
@@ -2273,34 +2154,21 @@ class HipScene:
         if (moments is None) != (counts is None):
             raise ValueError("%s: moments and counts come together (both None: the plain lookup)" % who)
         o = _lit_opts(who, aov_spp, specular_depth, centre, seed)
-        ps = _probe_rows(who, "sh", sh, 27, m)[0]
+        ps = _device_array(who, "sh", sh, (m, 27))
         pm = pc = 0
         vis = None
         if moments is not None:
             if m > (2 ** 31 - 1) // PROBE_DEPTH_ROW:
                 raise ValueError("%s: at most (2^31 - 1) / 192 probes, not %d" % (who, m))
             vis = _probe_visibility(who, normal_bias, backface_max)
-            pm = _probe_rows(who, "moments", moments, PROBE_DEPTH_ROW, m)[0]
-            pc = _probe_counts(who, "counts", counts, m)
+            pm = _device_array(who, "moments", moments, (m, PROBE_DEPTH_ROW))
+            pc = _device_array(who, "counts", counts, (m, 2), "int32")
         cam = np.ascontiguousarray(camera if camera is not None else self.sd.camera)
         W, H = int(cam["width"].reshape(-1)[0]), int(cam["height"].reshape(-1)[0])
         if W <= 0 or H <= 0:
             raise ValueError("%s: the camera's width and height are positive, not %d x %d" % (who, W, H))
         names = ("lit", "position") if position else ("lit",)
-        if out is None:
-            import torch
-            dev = self._torch_device()
-            out = {w: torch.empty((H, W, 3), dtype=torch.float32, device=dev) for w in names}
-            if stream is None:
-                stream = torch.cuda.current_stream(dev).cuda_stream
-        ptrs = {}
-        for w in names:
-            if w not in out:
-                raise ValueError("%s: out has no buffer for %r" % (who, w))
-            b = _device_buffer(out[w], who, "out[%r]" % w)
-            if b is None or b[1] != (H, W, 3):
-                raise ValueError("%s: out[%r] is a float32 device buffer of shape (%d, %d, 3)" % (who, w, H, W))
-            ptrs[w] = b[0]
+        out, ptrs, stream = _outputs(who, {w: ((H, W, 3), "float32") for w in names}, out, self._torch_device() if out is None else None, stream)
         vol = ProbeVolume(C.pointer(g), ps or None, pm or None, pc or None, C.pointer(vis) if vis is not None else None)
         outs = LitOutputs(ptrs["lit"] or None, ptrs.get("position") or None, (C.c_void_p * 2)(None, None))
         info = LitInfo()
