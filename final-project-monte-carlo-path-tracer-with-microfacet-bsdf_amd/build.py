@@ -18,8 +18,8 @@ CHECK_DEFINES = ["-DMCPT_TEST_HOOKS", "-DMCPT_CHECK_DIRECT_SKIP", "-DMCPT_FORCE_
 # rays that lose stack entries.  Tests only, like the checking build.
 LIB_HOOKS = os.path.join(HERE, "libmcpt_hip_hooks.so")
 HOOKS_DEFINES = ["-DMCPT_TEST_HOOKS", "-DMCPT_FORCE_RETRY", "-DMCPT_STK_RETRY=4"]
-SOURCES = ["mcpt_scene.cpp", "mcpt_kernels.hip", "mcpt_wavefront.hip", "mcpt_upload.hip", "mcpt_render.hip", "mcpt_query.hip", "mcpt_multi.hip", "mcpt_lbvh.hip", "mcpt_cull.hip", "mcpt_adaptive.hip", "mcpt_denoise.hip", "mcpt_update.hip", "mcpt_temporal.hip", "mcpt_moments.hip", "mcpt_sequence.hip", "mcpt_rayquery.hip", "mcpt_lightmap.hip", "mcpt_probes.hip"]
-HEADERS = ["mcpt_internal.h", "mcpt_device.h", "mcpt_fmath.h", "mcpt_kernels.h", "mcpt_traverse.h", "mcpt_stack_dispatch.h", "mcpt_host.h", "mcpt_lbvh.h", "mcpt_cull.h", "mcpt_adaptive.h", "mcpt_denoise.h", "mcpt_move.h", "mcpt_material.h", "mcpt_temporal.h", "mcpt_moments.h", "mcpt_specular_motion.h", "mcpt_chain.h", "mcpt_frame.h", "mcpt_sensor.h", "mcpt_lightmap.h", "mcpt_sh.h", "mcpt_probe_depth.h", "mcpt_direct.h", os.path.join("..", "..", "include", "mcpt.h")]
+SOURCES = ["mcpt_scene.cpp", "mcpt_kernels.hip", "mcpt_wavefront.hip", "mcpt_upload.hip", "mcpt_edit.hip", "mcpt_render.hip", "mcpt_query.hip", "mcpt_multi.hip", "mcpt_lbvh.hip", "mcpt_cull.hip", "mcpt_adaptive.hip", "mcpt_denoise.hip", "mcpt_update.hip", "mcpt_temporal.hip", "mcpt_moments.hip", "mcpt_sequence.hip", "mcpt_rayquery.hip", "mcpt_lightmap.hip", "mcpt_probes.hip"]
+HEADERS = ["mcpt_internal.h", "mcpt_device.h", "mcpt_fmath.h", "mcpt_kernels.h", "mcpt_traverse.h", "mcpt_stack_dispatch.h", "mcpt_host.h", "mcpt_replicas.h", "mcpt_lbvh.h", "mcpt_cull.h", "mcpt_adaptive.h", "mcpt_denoise.h", "mcpt_move.h", "mcpt_material.h", "mcpt_temporal.h", "mcpt_moments.h", "mcpt_specular_motion.h", "mcpt_chain.h", "mcpt_frame.h", "mcpt_sensor.h", "mcpt_lightmap.h", "mcpt_sh.h", "mcpt_probe_depth.h", "mcpt_direct.h", os.path.join("..", "..", "include", "mcpt.h")]
 # -ffp-contract=off: the arithmetic contract of csrc/mcpt_device.h (no FMA contraction, so the same seeds
 # give the same paths as the CPU restatement).  f32 divide/sqrt stay correctly rounded (hipcc default).
 # -fno-slp-vectorize: the SLP vectoriser pairs scalar f32 adds/muls into v_pk_*_f32, which issue slower than the two

@@ -1,8 +1,8 @@
 // The host layer behind the C ABI (include/mcpt.h): error plumbing, the owners of device resources, the wavefront workspace, the
 // environment knobs, the event timer, struct mcpt_scene, and what its translation units call in each other:
 //   mcpt_wavefront.hip  the wavefront loop, workspace / pass sizing (render_list), the pixel list and sky cull set-up
-//   mcpt_upload.hip     scene create / upload / update / material and environment edits / visibility / added objects / snapshot / destroy /
-//                       info, the BVH dumps
+//   mcpt_upload.hip     scene create / upload / snapshot / destroy / info, the BVH dumps
+//   mcpt_edit.hip       the live edits: update / deform / material and environment edits / visibility / added objects
 //   mcpt_update.hip     the kernels that move, deform and add objects in HBM (the device path of mcpt_scene_update / mcpt_scene_deform /
 //                       mcpt_scene_add_objects), mcpt_transform_triangles, mcpt_deform_triangles
 //   mcpt_render.hip     the frame-level entry points (render, adaptive, AOVs, denoise, motion, temporal blend); mcpt_frame.h has what
@@ -21,9 +21,11 @@
 #include <chrono>
 #include <cstring>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "mcpt_kernels.h"
+#include "mcpt_lbvh.h"
 #include "mcpt_material.h"
 
 namespace mcpt {
@@ -42,6 +44,8 @@ inline int fail(int code, const std::string &msg) {
             return fail(e_ == hipErrorOutOfMemory ? MCPT_ERR_OOM : MCPT_ERR_HIP,                        \
                         std::string(#expr) + ": " + hipGetErrorString(e_));                             \
     } while (0)
+
+#define MCPT_LOCAL __attribute__((visibility("hidden")))  // shared between translation units, not in the library's dynamic symbol table
 
 using Clock = std::chrono::steady_clock;
 inline double ms_since(Clock::time_point t) { return std::chrono::duration<double, std::milli>(Clock::now() - t).count(); }
@@ -359,8 +363,8 @@ struct Totals {
     }
 };
 
-// The device arrays that depend on where the objects are.  mcpt_scene_update fills a second set beside the live one and swaps the two
-// once the new tree is known to be usable, so that a failed update leaves the scene as it was.
+// The device arrays that depend on where the objects are.  Every live edit (csrc/mcpt_edit.hip) fills a second set beside the live one,
+// in its EditAside, and the commit swaps the two once the new tree is known to be usable, so that a failed edit leaves the scene as it was.
 struct GeomBufs {
     DevBuf<Node> nodes;
     DevBuf<QNode> qnodes;
@@ -573,48 +577,73 @@ struct HostBuild {
 };
 int build_scene_host(const mcpt_scene_desc *desc, const mcpt_build_options *options, HostBuild &hb);
 int upload_scene(const mcpt_scene_desc *desc, HostBuild &hb, int device, mcpt_scene **out);
-// mcpt_scene_update without the argument checks: gives the scene the transform table (moved, xf), of which the objects in `touched`
-// differ from the table it has.  Also the way back for mcpt_group_update when another replica fails.
-int apply_transforms(mcpt_scene *sc, const std::vector<uint8_t> &moved, const std::vector<float> &xf, const std::vector<int32_t> &touched,
-                     mcpt_update_info *info);
-// mcpt_scene_deform without the argument checks: the n listed meshes get the given positions as their base geometry; the transform
-// table stays.  Shares the rebuild with apply_transforms.  Also the way back for mcpt_group_deform when another replica fails.
-int apply_deform(mcpt_scene *sc, int32_t n, const mcpt_object_vertices *items, mcpt_update_info *info);
-// The argument checks of mcpt_scene_deform, before any device call.
-int check_deform(const mcpt_scene *sc, int32_t n, const mcpt_object_vertices *items);
-// The argument checks of mcpt_scene_update, before any device call; fills the table the scene would have afterwards.
+double warm_up_device(int device);
+// What the edit layer (csrc/mcpt_edit.hip) shares with creation.
+MCPT_LOCAL SceneMeta meta_of(const HostScene &hs);
+// What the device builders need to leave hidden objects out (VisTable, csrc/mcpt_lbvh.h): one entry per visible mesh in triangle-array
+// order, and the visible sphere objects.
+struct DevVis {
+    DevBuf<VisSeg> segs;
+    DevBuf<int32_t> sph;
+    int32_t n_segs = 0, n_tri = 0, n_sph = 0;
+    bool active = false;  // false: every object is visible, the builders run as they do without a table
+};
+MCPT_LOCAL int upload_vis(const std::vector<mcpt_object> &objects, const std::vector<uint8_t> &visible, DevVis &dv);
+MCPT_LOCAL int32_t count_visible_prims(const SceneSource &S, const std::vector<uint8_t> &visible);
+// The device builders' tree into g.nodes / g.qnodes, depth check included (see the definition).
+MCPT_LOCAL int build_device_tree_checked(const mcpt_triangle *d_tris, const int32_t *d_sphere_obj, int n_sph, const BuildChoice &choice, GeomBufs &g, SceneMeta &meta,
+                                         const DevVis *dv, const SphereRec *d_spheres = nullptr);
+// Copies the arrays of a flattened scene that depend on where its objects are into `g`; for the device builders the tree is then built
+// there from d_tris (the triangles `hs` was flattened from).  Shared by mcpt_scene_create and the host path of every edit.
+MCPT_LOCAL int upload_geometry(const HostScene &hs, const BuildChoice &choice, const mcpt_triangle *d_tris, const int32_t *d_sphere_obj, GeomBufs &g, SceneMeta &meta,
+                               double &gpu_build_ms, const DevVis *dv = nullptr);
+// DevScene and the geometry fields of mcpt_scene_info from the scene's arrays and sc->meta: after creation and after every edit.
+MCPT_LOCAL void fill_view(mcpt_scene *sc);
+
+// ---- mcpt_edit.hip
+// Every edit in two halves: check_* are the argument checks, before any device call (they fill what the scene would hold afterwards);
+// apply_* is the edit without them, which mcpt_group_* (csrc/mcpt_multi.hip) runs on every replica and, with the previous values, as the
+// way back when another replica fails.  update: the table (moved, xf) the scene gets, of which the objects in `touched`
+// differ; deform: the n listed meshes get the given positions as their base; visibility: the mask, and the objects whose state changes.
 int check_moves(const mcpt_scene *sc, int32_t n, const mcpt_object_transform *moves, std::vector<uint8_t> &moved, std::vector<float> &xf,
                 std::vector<int32_t> &touched);
-// mcpt_scene_set_materials in two halves, as above: the checks before any device call (which fill the plan), and the edit itself.  Also the
-// way back for mcpt_group_set_materials when another replica fails.
+int apply_transforms(mcpt_scene *sc, const std::vector<uint8_t> &moved, const std::vector<float> &xf, const std::vector<int32_t> &touched,
+                     mcpt_update_info *info);
+int check_deform(const mcpt_scene *sc, int32_t n, const mcpt_object_vertices *items);
+int apply_deform(mcpt_scene *sc, int32_t n, const mcpt_object_vertices *items, mcpt_update_info *info);
 int check_material_edit(const mcpt_scene *sc, int32_t n_edits, const mcpt_material_edit *edits, int32_t n_assign, const mcpt_object_material *assign,
                         mat::EditPlan &plan);
 int apply_material_edit(mcpt_scene *sc, const mat::EditPlan &plan, mcpt_update_info *info);
-// mcpt_scene_set_visibility in two halves, as above: the checks before any device call, which fill the mask the scene would have
-// afterwards and the objects whose state differs from the one they have; and the rebuild.  Also the way back for
-// mcpt_group_set_visibility when another replica fails.
 int check_visibility(const mcpt_scene *sc, int32_t n, const mcpt_object_visibility *items, std::vector<uint8_t> &visible, std::vector<int32_t> &changed);
 int apply_visibility(mcpt_scene *sc, const std::vector<uint8_t> &visible, const std::vector<int32_t> &changed, mcpt_update_info *info);
-// mcpt_scene_add_objects in two halves, as above.  Everything a scene holds per primitive or per object is built aside in an AddAside and
-// exchanged with the scene's as the last step, so after a successful apply_add the AddAside holds what the scene had before:
-// undo_add puts it back (mcpt_group_add_objects, when another replica fails).  Freed with the scene's device current.
-struct AddAside {
+// What an edit builds aside: `parts` says which of the members below replace the scene's, and the commit exchanges exactly those, so
+// afterwards the aside holds what the scene had.  Freed with the scene's device current.
+struct EditAside {
+    enum Part : uint32_t {  // geom's tree, its primitive records (and the tree with them), its light tables; the device builders' base triangles and sphere
+                            // list; the material table; the snapshot; a deformation's new base on the host, or PATCH: the meshes in `patch` are overwritten in place
+        TREE = 1u << 0, PRIMS = 1u << 1, LIGHTS = 1u << 2, TRIS0 = 1u << 3, SPHERE_OBJ = 1u << 4, MATS = 1u << 5, SNAPSHOT = 1u << 6,
+        TRIANGLES = 1u << 7, PATCH = 1u << 8,
+    };
+    uint32_t parts = 0;
     GeomBufs geom;
     DevBuf<mcpt_triangle> tris0;
     DevBuf<int32_t> sphere_obj;
     DevBuf<MaterialRec> mats;
     DevBuf<TriGeom> snap_tri;
     DevBuf<SphereRec> snap_sph;
-    SceneMeta meta;
-    bool lights = false;  // the light tables are part of the exchange (path 0)
-    size_t n_objects = 0, n_triangles = 0, n_materials = 0;  // what the scene's description held before the call
+    SceneMeta meta;  // (always part of the exchange)
+    std::vector<mcpt_triangle> triangles;
+    std::vector<std::pair<int32_t, const float *>> patch;  // a deformation: (object, its 9 floats per triangle on the host)
+    std::vector<std::vector<float>> fetched;                // of which those downloaded from device pointers live here
 };
+// mcpt_scene_add_objects.  After a successful apply_add with `keep`, *keep holds the arrays the scene had: undo_add commits them back
+// (mcpt_group_add_objects, when another replica fails).  A type of its own only so that apply_add and undo_add keep their exported names.
+struct AddAside : EditAside {};
 int check_add(const mcpt_scene *sc, const mcpt_scene_addition *add);
 int apply_add(mcpt_scene *sc, const mcpt_scene_addition *add, int32_t *first_object, mcpt_update_info *info, AddAside *keep = nullptr);
 int undo_add(mcpt_scene *sc, AddAside &aside);
 int check_environment(const mcpt_scene *sc, const float *background, int32_t env_w, int32_t env_h, const float *env_pixels);
 int apply_environment(mcpt_scene *sc, const float *background, int32_t env_w, int32_t env_h, const float *env_pixels, mcpt_update_info *info);
-double warm_up_device(int device);
 
 // ---- mcpt_wavefront.hip
 hipError_t ensure_workspace(PoolCtx &ctx, uint32_t pool, int32_t n_dir, int32_t max_depth, bool retry_lists);

@@ -2,7 +2,7 @@
  * mcpt_material.h -- what a material means to the device tables, and the plan of an in-place material edit (include/mcpt.h:
  * mcpt_scene_set_materials).
  *
- * Host only, no HIP: the scene builder (csrc/mcpt_scene.cpp), the edit call (csrc/mcpt_upload.hip) and the CPU tests
+ * Host only, no HIP: the scene builder (csrc/mcpt_scene.cpp), the edit call (csrc/mcpt_edit.hip) and the CPU tests
  * (tests/native/material_driver.cpp, built with g++) all compile these functions, so the MaterialRec of an edited entry is the one a
  * fresh scene would hold bit for bit, and the decision between the in-place path and the host path is one predicate.
  */

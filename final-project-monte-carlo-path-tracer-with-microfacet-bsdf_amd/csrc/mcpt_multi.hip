@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "mcpt_host.h"
+#include "mcpt_replicas.h"
 
 using namespace mcpt;
 
@@ -82,35 +83,13 @@ int gfail(int code, const std::string &msg) {
 }
 
 // `apply(scene)` on every replica, one host thread per replica.  If a replica fails, `undo(scene)` runs on the replicas that had changed,
-// so that the group stays one scene, and the first failure is reported under `name`.
+// so that the group stays one scene (csrc/mcpt_replicas.h), and the first failure is reported under `name`.
 template <typename Apply, typename Undo>
 int on_replicas(mcpt_group *g, const char *name, Apply apply, Undo undo) {
-    const int N = (int)g->scenes.size();
-    std::vector<int> rc((size_t)N, MCPT_OK);
-    std::vector<std::string> err((size_t)N);
-    auto run = [&](auto &f, const std::vector<int> &which) {
-        auto work = [&](int i) {
-            rc[(size_t)i] = f(g->scenes[(size_t)i]);
-            if (rc[(size_t)i] != MCPT_OK) err[(size_t)i] = mcpt_last_error();
-        };
-        std::vector<std::thread> th;
-        for (size_t k = 1; k < which.size(); ++k) th.emplace_back(work, which[k]);
-        if (!which.empty()) work(which[0]);
-        for (std::thread &t : th) t.join();
-    };
-    std::vector<int> all, done;
-    for (int i = 0; i < N; ++i) all.push_back(i);
-    run(apply, all);
-    int bad = -1;
-    for (int i = 0; i < N; ++i) {
-        if (rc[(size_t)i] == MCPT_OK) done.push_back(i);
-        else if (bad < 0) bad = i;
-    }
-    if (bad < 0) return MCPT_OK;
-    const int code = rc[(size_t)bad];
-    const std::string e = std::string(name) + ": device " + std::to_string(g->devices[(size_t)bad]) + ": " + err[(size_t)bad];
-    run(undo, done);
-    return gfail(code, e);
+    const ReplicaFailure f = mcpt::on_replicas((int)g->scenes.size(), [&](int i) { return apply(g->scenes[(size_t)i]); },
+                                         [&](int i) { return undo(g->scenes[(size_t)i]); }, mcpt_last_error);
+    if (f.index < 0) return MCPT_OK;
+    return gfail(f.code, std::string(name) + ": device " + std::to_string(g->devices[(size_t)f.index]) + ": " + f.message);
 }
 
 }  // namespace
@@ -192,33 +171,20 @@ int mcpt_group_create(const mcpt_scene_desc *desc, int n_devices, const int *dev
         for (double v : warm_ms) hb.init_ms = std::max(hb.init_ms, v);
     }
     g->build_ms = hb.build_ms;
-    std::vector<int> rc((size_t)n_devices, MCPT_OK);
-    std::vector<std::string> err((size_t)n_devices);
-    auto up = [&](int i) {
+    // one thread per entry; nothing to undo, a failure destroys the group
+    const ReplicaFailure f = mcpt::on_replicas(n_devices, [&](int i) -> int {
         HostBuild mine = hb;  // (upload_scene fills in what a device-side tree build returns: every thread works on its own copy)
-        rc[(size_t)i] = upload_scene(desc, mine, devices[i], &g->scenes[(size_t)i]);
-        if (rc[(size_t)i] != MCPT_OK) {
-            err[(size_t)i] = mcpt_last_error();
-            return;
-        }
-        if (hipSetDevice(devices[i]) != hipSuccess || hipStreamCreateWithFlags(&g->streams[(size_t)i], hipStreamNonBlocking) != hipSuccess) {
-            rc[(size_t)i] = MCPT_ERR_HIP;
-            err[(size_t)i] = "cannot create a stream";
-        }
-    };
-    {
-        std::vector<std::thread> th;
-        for (int i = 1; i < n_devices; ++i) th.emplace_back(up, i);
-        up(0);
-        for (std::thread &t : th) t.join();
+        const int rc = upload_scene(desc, mine, devices[i], &g->scenes[(size_t)i]);
+        if (rc != MCPT_OK) return rc;
+        if (hipSetDevice(devices[i]) != hipSuccess || hipStreamCreateWithFlags(&g->streams[(size_t)i], hipStreamNonBlocking) != hipSuccess)
+            return fail(MCPT_ERR_HIP, "cannot create a stream");
+        return MCPT_OK;
+    }, [](int) { return 0; }, mcpt_last_error);
+    if (f.index >= 0) {
+        const std::string e = "mcpt_group_create: device " + std::to_string(devices[f.index]) + ": " + f.message;
+        mcpt_group_destroy(g);
+        return gfail(f.code, e);
     }
-    for (int i = 0; i < n_devices; ++i)
-        if (rc[(size_t)i] != MCPT_OK) {
-            const int code = rc[(size_t)i];
-            const std::string e = "mcpt_group_create: device " + std::to_string(devices[i]) + ": " + err[(size_t)i];
-            mcpt_group_destroy(g);
-            return gfail(code, e);
-        }
     for (int i = 0; i < n_devices; ++i) {
         int sharers = 0;
         for (int j = 0; j < n_devices; ++j) sharers += devices[j] == devices[i] ? 1 : 0;
@@ -235,38 +201,16 @@ mcpt_scene *mcpt_group_scene(mcpt_group *g, int index) { return (g && index >= 0
 
 int mcpt_group_update(mcpt_group *g, int32_t n, const mcpt_object_transform *moves) {
     if (!g || g->scenes.empty()) return gfail(MCPT_ERR_ARG, "mcpt_group_update: null group");
-    const int N = (int)g->scenes.size();
     // every replica holds the same description and the same transforms: one check, before any device call
-    std::vector<uint8_t> moved, moved_old = g->scenes[0]->src.moved;
-    std::vector<float> xf, xf_old = g->scenes[0]->src.xf;
+    std::vector<uint8_t> moved;
+    std::vector<float> xf;
     std::vector<int32_t> touched;
+    const std::vector<uint8_t> moved_old = g->scenes[0]->src.moved;  // the way back: the table the replicas have now
+    const std::vector<float> xf_old = g->scenes[0]->src.xf;
     const int rc0 = check_moves(g->scenes[0], n, moves, moved, xf, touched);
     if (rc0 != MCPT_OK) return gfail(rc0, std::string("mcpt_group_update: ") + mcpt_last_error());
-    std::vector<int> rc((size_t)N, MCPT_OK);
-    std::vector<std::string> err((size_t)N);
-    auto run = [&](const std::vector<uint8_t> &mv_, const std::vector<float> &xf_, const std::vector<int> &which) {
-        auto work = [&](int i) {
-            rc[(size_t)i] = apply_transforms(g->scenes[(size_t)i], mv_, xf_, touched, nullptr);
-            if (rc[(size_t)i] != MCPT_OK) err[(size_t)i] = mcpt_last_error();
-        };
-        std::vector<std::thread> th;
-        for (size_t k = 1; k < which.size(); ++k) th.emplace_back(work, which[k]);
-        if (!which.empty()) work(which[0]);
-        for (std::thread &t : th) t.join();
-    };
-    std::vector<int> all, done;
-    for (int i = 0; i < N; ++i) all.push_back(i);
-    run(moved, xf, all);
-    int bad = -1;
-    for (int i = 0; i < N; ++i) {
-        if (rc[(size_t)i] == MCPT_OK) done.push_back(i);
-        else if (bad < 0) bad = i;
-    }
-    if (bad < 0) return MCPT_OK;
-    const int code = rc[(size_t)bad];
-    const std::string e = "mcpt_group_update: device " + std::to_string(g->devices[(size_t)bad]) + ": " + err[(size_t)bad];
-    run(moved_old, xf_old, done);  // the replicas that had moved go back: the group stays one scene
-    return gfail(code, e);
+    return on_replicas(g, "mcpt_group_update", [&](mcpt_scene *sc) { return apply_transforms(sc, moved, xf, touched, nullptr); },
+                       [&](mcpt_scene *sc) { return apply_transforms(sc, moved_old, xf_old, touched, nullptr); });
 }
 
 int mcpt_group_deform(mcpt_group *g, int32_t n, const mcpt_object_vertices *items) {
@@ -276,48 +220,22 @@ int mcpt_group_deform(mcpt_group *g, int32_t n, const mcpt_object_vertices *item
     // every replica holds the same base: one check, before any device call
     const int rc0 = check_deform(g->scenes[0], n, items);
     if (rc0 != MCPT_OK) return gfail(rc0, std::string("mcpt_group_deform: ") + mcpt_last_error());
-    const int N = (int)g->scenes.size();
-    // the way back: the positions the listed meshes have now
+    // the way back: the positions the listed meshes have now, as host items
     std::vector<std::vector<float>> old_pos((size_t)n);
     std::vector<mcpt_object_vertices> old_items((size_t)n);
-    {
-        const SceneSource &S = g->scenes[0]->src;
-        for (int32_t i = 0; i < n; ++i) {
-            const mcpt_object &ob = S.objects[(size_t)items[i].object];
-            old_pos[(size_t)i].reserve((size_t)ob.n_tri * 9 + 1);
-            for (int32_t k = 0; k < ob.n_tri; ++k) {
-                const mcpt_triangle &t = S.triangles[(size_t)ob.first_tri + k];
-                old_pos[(size_t)i].insert(old_pos[(size_t)i].end(), {t.v0[0], t.v0[1], t.v0[2], t.v1[0], t.v1[1], t.v1[2], t.v2[0], t.v2[1], t.v2[2]});
-            }
-            old_pos[(size_t)i].push_back(0.f);  // (an empty mesh still needs a non-null pointer)
-            old_items[(size_t)i] = {items[i].object, 0, old_pos[(size_t)i].data()};
+    const SceneSource &S = g->scenes[0]->src;
+    for (int32_t i = 0; i < n; ++i) {
+        const mcpt_object &ob = S.objects[(size_t)items[i].object];
+        old_pos[(size_t)i].reserve((size_t)ob.n_tri * 9 + 1);
+        for (int32_t k = 0; k < ob.n_tri; ++k) {
+            const mcpt_triangle &t = S.triangles[(size_t)ob.first_tri + k];
+            old_pos[(size_t)i].insert(old_pos[(size_t)i].end(), {t.v0[0], t.v0[1], t.v0[2], t.v1[0], t.v1[1], t.v1[2], t.v2[0], t.v2[1], t.v2[2]});
         }
+        old_pos[(size_t)i].push_back(0.f);  // (an empty mesh still needs a non-null pointer)
+        old_items[(size_t)i] = {items[i].object, 0, old_pos[(size_t)i].data()};
     }
-    std::vector<int> rc((size_t)N, MCPT_OK);
-    std::vector<std::string> err((size_t)N);
-    auto run = [&](const mcpt_object_vertices *it, const std::vector<int> &which) {
-        auto work = [&](int i) {
-            rc[(size_t)i] = apply_deform(g->scenes[(size_t)i], n, it, nullptr);
-            if (rc[(size_t)i] != MCPT_OK) err[(size_t)i] = mcpt_last_error();
-        };
-        std::vector<std::thread> th;
-        for (size_t k = 1; k < which.size(); ++k) th.emplace_back(work, which[k]);
-        if (!which.empty()) work(which[0]);
-        for (std::thread &t : th) t.join();
-    };
-    std::vector<int> all, done;
-    for (int i = 0; i < N; ++i) all.push_back(i);
-    run(items, all);
-    int bad = -1;
-    for (int i = 0; i < N; ++i) {
-        if (rc[(size_t)i] == MCPT_OK) done.push_back(i);
-        else if (bad < 0) bad = i;
-    }
-    if (bad < 0) return MCPT_OK;
-    const int code = rc[(size_t)bad];
-    const std::string e = "mcpt_group_deform: device " + std::to_string(g->devices[(size_t)bad]) + ": " + err[(size_t)bad];
-    run(old_items.data(), done);  // the replicas that had deformed go back: the group stays one scene
-    return gfail(code, e);
+    return on_replicas(g, "mcpt_group_deform", [&](mcpt_scene *sc) { return apply_deform(sc, n, items, nullptr); },
+                       [&](mcpt_scene *sc) { return apply_deform(sc, n, old_items.data(), nullptr); });
 }
 
 int mcpt_group_set_materials(mcpt_group *g, int32_t n_edits, const mcpt_material_edit *edits, int32_t n_assign, const mcpt_object_material *assign) {
