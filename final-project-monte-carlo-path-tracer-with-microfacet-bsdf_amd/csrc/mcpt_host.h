@@ -237,6 +237,13 @@ struct ProbeBufs {
     // mcpt_render_probe_lit[_direct]: the eight-byte counters of its lookups and live light samples, made by the scene's first such call.  Working storage, no
     // probe buffer: it is in neither figure of mcpt_scene_probe_buffers.
     DevBuf<unsigned long long> lit_count;
+    // mcpt_probe_volume_relight: per probe ray of a piece the lit sample's records {v or a, kind} {nf} {p} and its direct term D, and the
+    // staging of the direct term's light samples (shadow rays, their hits, the per-sample records and the compacted list's length).  Probe
+    // buffers: counted in both figures of mcpt_scene_probe_buffers (four floats per entry; the two scalars are not).
+    DevBuf<float4> relit_r0, relit_r1, relit_r2, relit_d, relit_ray_o, relit_ray_d, relit_slot;
+    DevBuf<uint4> relit_hit;
+    DevBuf<uint32_t> relit_n;
+    DevBuf<unsigned long long> relit_count;  // k_lit_shade's count of lookups; never read back
 };
 
 // Environment knobs, read ONCE per scene in mcpt_scene_create: a render call never calls getenv.

@@ -216,8 +216,9 @@ void launch_shade(const DevScene &S, const RenderConst &C, Wave cur, Wave next, 
 // slot[g] = {contrib, index of its shadow ray or kDirectDead}.  The shadow rays of the live samples alone are appended to the ray arrays
 // (ballot + prefix count, one integer atomic per wave on *n_rays, which the caller has zeroed): ray_o = {q, g}, ray_d = {ws, dist}.
 // Points: rows of the caller's arrays with key (i, key_sample) (r0 null), or the records of the lit pass's chunk, where sample i of the
-// chunk has p = r2[i], nf = r1[i] and the key (p0 + i / aov_spp, i % aov_spp), and a sample that did not end on a surface (r0[i].w !=
-// surface_kind) has no light sample at all.  total (nullable): the live samples are added to it as well.
+// chunk has p = r2[i], nf = r1[i] and the key (p0 + i / aov_spp, sample0 + i % aov_spp), and a sample that did not end on a surface
+// (r0[i].w != surface_kind) has no light sample at all.  sample0 is 0 for the lit pass; mcpt_probe_volume_relight, whose records are a run
+// of a probe's samples, passes the absolute index of the run's first sample.  total (nullable): the live samples are added to it as well.
 constexpr uint32_t kDirectDead = 0xffffffffu;
 struct DirectRays {
     const float *points, *normals;  // the call's n*3 arrays
@@ -231,6 +232,7 @@ struct DirectRays {
     uint32_t surface_kind, p0;
     int32_t aov_spp;
     unsigned long long *total;
+    uint32_t sample0;
 };
 void launch_direct_rays(const DevScene &S, const DirectRays &a, hipStream_t s);
 // Multi-GPU merge helpers (csrc/mcpt_multi.hip): zero the pixels rank `rank` does not own (tile rule of mcpt_params); a += b.

@@ -1881,7 +1881,7 @@ __global__ __launch_bounds__(kBlock) void k_direct_rays(DevScene S, DirectRays a
             p[0] = p4.x, p[1] = p4.y, p[2] = p4.z;
             nf[0] = n4.x, nf[1] = n4.y, nf[2] = n4.z;
             rk.pixel = a.p0 + i / (uint32_t)a.aov_spp;
-            rk.sample = i % (uint32_t)a.aov_spp;
+            rk.sample = a.sample0 + i % (uint32_t)a.aov_spp;
         } else {
             const size_t b = 3 * (size_t)i;
             p[0] = a.points[b], p[1] = a.points[b + 1], p[2] = a.points[b + 2];

@@ -19,6 +19,17 @@
 //   k_probe_shade_visible  one lane per (point, normal): pd::shade_visible
 // Every store is a plain vector store; nothing above uses atomics, LDS, scratch or inline assembly.
 //
+// Relighting a probe volume (mcpt_probe_volume_relight; csrc/mcpt_probe_relight.h states the fold and the blend).  Per piece of the ray
+// queries' staging buffers, as the depth query cuts them:
+//   k_probe_depth_rays, closest hits   as above: the probes' whole-sphere rays and their hits, staged once
+//   k_lit_terminal (b = 0, max_b = 0)  the lit sample's records {v or a, kind} {nf} {p} into scene-owned buffers (ProbeBufs, csrc/mcpt_host.h)
+//   direct_term                        when asked: D per record, through shadow-ray staging of its own, keys (probe, sample_offset + k)
+//   k_lit_shade                        the lookup in the previous volume: r0.xyz = a * (max(E, 0) + D)
+//   k_probe_relight_fold               one wave per probe, lane = (coefficient, channel): the 27 sums in sample order and, at a probe's last
+//                                      piece, the blend with the previous coefficients
+//   k_probe_depth_fold                 when depth outputs are given: from the same staged hits
+// The new kernel uses plain vector stores, no atomics, no LDS and no scratch.
+//
 // Probe-lit frames (mcpt_render_probe_lit; lit_pass in csrc/mcpt_render.hip runs them per chunk of the AOV pass's chunk loop):
 //   k_lit_terminal  one lane per ray of a list: the chain step of k_aov_chain; a sample that stops records {v or a, kind} {nf} {p}
 //   k_lit_shade     one lane per sample: the grid lookup (plain or occlusion-aware) of a sample that ended on a surface
@@ -37,6 +48,7 @@
 #include "mcpt_frame.h"
 #include "mcpt_host.h"
 #include "mcpt_probe_depth.h"
+#include "mcpt_probe_relight.h"
 #include "mcpt_sh.h"
 
 using namespace mcpt;
@@ -334,6 +346,59 @@ __global__ __launch_bounds__(kPbBlock) void k_lit_fold(uint32_t p0, uint32_t n_p
     }
 }
 
+// The projection fold of mcpt_probe_volume_relight: one wave per probe, lane l < 27 owns coefficient j = l / 3 of channel c = l % 3 (the
+// other lanes prepare samples and walk along, and store nothing).  Per block of 64 samples lane s prepares sample s: its value r0[g].xyz
+// (0.f for an emitter with zero_emitters: the indirect_only flavour is consumed here, k_lit_terminal does not know it) and the nine
+// weights of its staged direction ray_d[g].xyz.  Then the wave walks the block in sample order with the sample's three values and nine
+// weights broadcast from lane s by wave-uniform lane reads; a lane picks its own with selects (an indexed w[j] would live in scratch) and
+// adds to its sum in a register.  load: the sums continue what out holds (an earlier piece of the same probe's samples); last: these
+// are the probes' last samples, so the blend with prev (the previous volume's coefficients, read only with h != 0) is applied.
+__global__ __launch_bounds__(kPbBlock) void k_probe_relight_fold(const float4 *__restrict__ r0, const float4 *__restrict__ ray_d, uint32_t i0, uint32_t m,
+                                                               uint32_t kc, int load, int last, int zero_emitters, float fn, float h,
+                                                               const float *__restrict__ prev, float *__restrict__ out) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t pi = blockIdx.x * (kPbBlock / 64) + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (pi >= m) return;  // (wave-uniform)
+    const bool owner = lane < (uint32_t)sh::kRow;
+    const uint32_t q = owner ? lane : 0u, j = q / 3u, c = q - 3u * j;
+    const size_t row = ((size_t)i0 + pi) * (size_t)sh::kRow + q;
+    float acc = 0.f;
+    if (load) acc = out[row];
+    const size_t base = (size_t)pi * kc;
+    for (uint32_t kb = 0; kb < kc; kb += 64u) {
+        const uint32_t cnt = kc - kb < 64u ? kc - kb : 64u;
+        float v0 = 0.f, v1 = 0.f, v2 = 0.f, w[sh::kCoef];
+#pragma unroll
+        for (int32_t b = 0; b < sh::kCoef; ++b) w[b] = 0.f;
+        if (lane < cnt) {
+            const size_t g = base + kb + lane;
+            const float4 r = r0[g], d4 = ray_d[g];
+            const bool zero = zero_emitters && __float_as_uint(r.w) == kLitEmitter;
+            v0 = zero ? 0.f : r.x;
+            v1 = zero ? 0.f : r.y;
+            v2 = zero ? 0.f : r.z;
+            const float d[3] = {d4.x, d4.y, d4.z};
+            float Y[sh::kCoef];
+            sh::sh9_basis(d, Y);
+#pragma unroll
+            for (int32_t b = 0; b < sh::kCoef; ++b) w[b] = pr::weight(Y[b]);
+        }
+        for (uint32_t s = 0; s < cnt; ++s) {  // (a uniform bound: the tail of a short block is not walked)
+            const float s0 = lane_read(v0, s), s1 = lane_read(v1, s), s2 = lane_read(v2, s);
+            const float vs = c == 0u ? s0 : (c == 1u ? s1 : s2);
+            float ws = lane_read(w[0], s);
+#pragma unroll
+            for (uint32_t b = 1; b < (uint32_t)sh::kCoef; ++b) {
+                const float wb = lane_read(w[b], s);
+                ws = j == b ? wb : ws;
+            }
+            acc = pr::fold_term(acc, vs, ws, fn);
+        }
+    }
+    if (last) acc = pr::blend(h, h != 0.0f ? prev[row] : 0.f, acc);
+    if (owner) out[row] = acc;
+}
+
 inline uint32_t probe_blocks(uint32_t n) { return (n + kPbBlock - 1) / kPbBlock; }
 
 // The grid of a call, or the reason it is refused.
@@ -402,6 +467,23 @@ int check_visibility(const std::string &w, const mcpt_probe_visibility *o) {
     if (!(o->normal_bias >= 0.f) || !std::isfinite(o->normal_bias) || !(o->backface_max >= 0.f) || !std::isfinite(o->backface_max))
         return fail(MCPT_ERR_ARG, w + ": normal_bias and backface_max must be finite and not negative");
     return MCPT_OK;
+}
+
+// Whether the byte ranges [a, a + na) and [b, b + nb) share a byte.
+bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb) {
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + nb && y < x + na;
+}
+
+// A scene-owned buffer of mcpt_probe_volume_relight of at least n entries; grown behind query_settle, like probe_grow.
+template <class T>
+hipError_t relit_grow(mcpt_scene *sc, DevBuf<T> &b, size_t n, mcpt_query_info &qi) {
+    if (b.p && b.n >= n) return hipSuccess;
+    const hipError_t e = query_settle(sc);
+    if (e != hipSuccess) return e;
+    sc->probes.allocations++;
+    qi.grew = 1;
+    return b.alloc(n);
 }
 
 }  // namespace
@@ -724,6 +806,137 @@ int mcpt_query_direct(mcpt_scene *sc, const mcpt_direct_opts *op, int64_t n, con
     return MCPT_OK;
 }
 
+int mcpt_probe_volume_relight(mcpt_scene *sc, const mcpt_probe_volume *vol, const mcpt_probe_relight_opts *op, const mcpt_probe_relight_outputs *out,
+                              void *hip_stream, mcpt_query_info *info) {
+    const std::string w = "mcpt_probe_volume_relight";
+    const auto bad = [&](const char *what) { return fail(MCPT_ERR_ARG, w + ": " + what); };
+    if (!sc || !vol || !op || !out) return bad("null scene, volume, opts or outputs");
+    if (!out->sh || !vol->sh) return bad("null sh");
+    if (op->spp < 1 || op->sample_offset < 0 || (int64_t)op->sample_offset + (int64_t)op->spp > 0x7fffffff)
+        return bad("spp must be positive, sample_offset >= 0 and sample_offset + spp at most 2^31 - 1");
+    if (!(op->hysteresis >= 0.f) || !(op->hysteresis < 1.f)) return bad("hysteresis must be in [0, 1)");
+    if (op->indirect_only != 0 && op->indirect_only != 1) return bad("indirect_only must be 0 or 1");
+    if (op->direct_samples < 0 || op->direct_samples > dl::kMaxSamples) return bad("direct_samples must be 0 (off) or 1 .. 4096");
+    for (int k = 0; k < 8; ++k)
+        if (op->reserved[k]) return bad("reserved words must be 0");
+    if (out->reserved) return bad("the reserved pointer must be null");
+    const bool depth = out->moments != nullptr;
+    if ((out->counts != nullptr) != depth) return bad("the outputs moments and counts must be both null or both non-null");
+    if (depth && (!(op->max_distance > 0.f) || !std::isfinite(op->max_distance))) return bad("max_distance must be positive and finite when depth outputs are given");
+    const bool vis = vol->moments != nullptr;
+    if ((vol->counts != nullptr) != vis || (vol->visibility != nullptr) != vis) return bad("moments, counts and visibility must be all null or all non-null");
+    LitVolume lv;
+    const int gc = check_grid(w, vol->grid, lv.g);
+    if (gc != MCPT_OK) return gc;
+    const int64_t n = grid_probes(lv.g);
+    if ((vis || depth) && n > (int64_t)pd::kMaxProbes) return bad("dims must name at most (2^31 - 1) / 192 probes");
+    if (vis) {
+        const int vc = check_visibility(w, vol->visibility);
+        if (vc != MCPT_OK) return vc;
+        lv.normal_bias = vol->visibility->normal_bias;
+        lv.backface_max = vol->visibility->backface_max;
+    }
+    if (n > (int64_t)0x7fffffff / op->spp) return bad("probes * spp must be at most 2^31 - 1");
+    if (op->direct_samples > 0 && n * op->spp > (int64_t)0x7fffffff / op->direct_samples) return bad("probes * spp * direct_samples must be at most 2^31 - 1");
+    const size_t sh_bytes = (size_t)n * sh::kRow * sizeof(float), mom_bytes = (size_t)n * pd::kTexels * 3 * sizeof(float), cnt_bytes = (size_t)n * 2 * sizeof(int32_t);
+    if (ranges_overlap(out->sh, sh_bytes, vol->sh, sh_bytes)) return bad("the output sh must not overlap the volume's sh");
+    if (depth && vis && (ranges_overlap(out->moments, mom_bytes, vol->moments, mom_bytes) || ranges_overlap(out->counts, cnt_bytes, vol->counts, cnt_bytes)))
+        return bad("the output moments and counts must not overlap the volume's");
+    lv.sh = vol->sh;
+    lv.moments = vol->moments;
+    lv.counts = vol->counts;
+    if (!on_device(out->sh, sc->device) || !on_device(vol->sh, sc->device) || (depth && (!on_device(out->moments, sc->device) || !on_device(out->counts, sc->device))) ||
+        (vis && (!on_device(vol->moments, sc->device) || !on_device(vol->counts, sc->device))))
+        return bad("sh, moments and counts of the volume and of the outputs must be memory of the scene's device");
+    const hipStream_t st = (hipStream_t)hip_stream;
+    mcpt_query_info qi;
+    std::memset(&qi, 0, sizeof qi);
+    HIP_TRY(hipSetDevice(sc->device));
+    (void)hipGetLastError();
+    ProbeBufs &P = sc->probes;
+    const int32_t N = sc->view.n_lights > 0 ? op->direct_samples : 0;  // (an empty light table: D = 0, no ray)
+    const uint32_t cap = std::max<uint32_t>(sc->knobs.query_chunk, 64u);
+    // the probe rays are cut as mcpt_query_probe_depth cuts them; the light samples of a piece's records as the lit pass cuts a chunk's
+    const PieceCut cut = piece_cut((uint64_t)n, (uint64_t)op->spp, cap, 64);
+    const uint64_t rec = cut.staged();
+    const PieceCut dcut = piece_cut(rec, (uint64_t)std::max(N, 1), cap, 1);
+    HIP_TRY(probe_grow(sc, P.points, (size_t)n * 3));
+    HIP_TRY(relit_grow(sc, P.relit_r0, rec, qi));
+    HIP_TRY(relit_grow(sc, P.relit_r1, rec, qi));
+    HIP_TRY(relit_grow(sc, P.relit_r2, rec, qi));
+    HIP_TRY(relit_grow(sc, P.relit_count, 1, qi));
+    if (op->direct_samples > 0) HIP_TRY(relit_grow(sc, P.relit_d, rec, qi));
+    if (N > 0) {
+        HIP_TRY(relit_grow(sc, P.relit_ray_o, dcut.staged(), qi));
+        HIP_TRY(relit_grow(sc, P.relit_ray_d, dcut.staged(), qi));
+        HIP_TRY(relit_grow(sc, P.relit_slot, dcut.staged(), qi));
+        HIP_TRY(relit_grow(sc, P.relit_hit, dcut.staged(), qi));
+        HIP_TRY(relit_grow(sc, P.relit_n, 1, qi));
+    }
+    RetryList rl;
+    const int sr = query_stage(sc, (uint32_t)std::max<uint64_t>(rec, N > 0 ? dcut.staged() : 0), st, qi, rl);
+    if (sr != MCPT_OK) return sr;
+    QueryBufs &Q = sc->query;
+    HIP_TRY(hipMemsetAsync(P.relit_count.p, 0, sizeof(unsigned long long), st));
+    hipLaunchKernelGGL(k_probe_grid_points, dim3(probe_blocks((uint32_t)n)), dim3(kPbBlock), 0, st, lv.g, (uint32_t)n, P.points.p);
+    const float fn = (float)op->spp;
+    const int rc = for_each_piece(cut, (uint64_t)n, (uint64_t)op->spp, [&](uint32_t i0, uint32_t m, uint32_t k0, uint32_t kc) -> int {
+        const uint32_t rays = m * kc;
+        const uint32_t first = (uint32_t)op->sample_offset + k0;
+        const int load = k0 > 0 ? 1 : 0, last = k0 + kc == (uint32_t)op->spp ? 1 : 0;
+        hipLaunchKernelGGL(k_probe_depth_rays, dim3(probe_blocks(rays)), dim3(kPbBlock), 0, st, P.points.p, op->seed, i0, kc, first, rays, Q.ray_o.p, Q.ray_d.p);
+        launch_trace_closest(sc->view, rays, nullptr, Q.ray_o.p, Q.ray_d.p, Q.hit.p, rl, st);
+        launch_lit_terminal(sc->view, rays, 0, 0, Q.ray_o.p, Q.ray_d.p, Q.hit.p, nullptr, P.relit_r0.p, P.relit_r1.p, P.relit_r2.p, nullptr, nullptr, nullptr, nullptr, st);
+        float4 *direct_d = nullptr;
+        if (op->direct_samples > 0) {
+            direct_d = P.relit_d.p;
+            if (N == 0) {
+                HIP_TRY(hipMemsetAsync(direct_d, 0, (size_t)rays * sizeof(float4), st));
+            } else {
+                DirectRays src{};
+                src.seed = op->direct_seed;
+                src.N = N;
+                src.r0 = P.relit_r0.p;
+                src.r1 = P.relit_r1.p;
+                src.r2 = P.relit_r2.p;
+                src.surface_kind = kLitSurfaceKind;
+                src.p0 = i0;  // record g of the piece is sample first + g % kc of probe i0 + g / kc
+                src.aov_spp = (int32_t)kc;
+                src.sample0 = first;
+                const int dr = direct_term(sc->view, src, rays, DirectStage{P.relit_ray_o.p, P.relit_ray_d.p, P.relit_slot.p, P.relit_hit.p, P.relit_n.p, dcut, rl},
+                                           reinterpret_cast<float *>(direct_d), 4u, st, qi.launches);
+                if (dr != MCPT_OK) return dr;
+            }
+        }
+        launch_lit_shade(lv, rays, P.relit_r0.p, P.relit_r1.p, P.relit_r2.p, direct_d, P.relit_count.p, st);
+        const dim3 waves((m + kPbBlock / 64 - 1) / (kPbBlock / 64));
+        hipLaunchKernelGGL(k_probe_relight_fold, waves, dim3(kPbBlock), 0, st, P.relit_r0.p, Q.ray_d.p, i0, m, kc, load, last, op->indirect_only, fn, op->hysteresis,
+                           vol->sh, out->sh);
+        if (depth)
+            hipLaunchKernelGGL(k_probe_depth_fold, waves, dim3(kPbBlock), 0, st, sc->view, Q.ray_o.p, Q.ray_d.p, Q.hit.p, i0, m, kc, load, op->max_distance,
+                               out->moments, out->counts);
+        qi.launches++;
+        return MCPT_OK;
+    });
+    const int fr = query_finish(sc, st, qi);  // (behind whatever was enqueued, also when a piece failed)
+    if (rc != MCPT_OK) return rc;
+    if (fr != MCPT_OK) return fr;
+    qi.staged_bytes += (int64_t)(P.relit_r0.bytes() + P.relit_r1.bytes() + P.relit_r2.bytes() + P.relit_d.bytes() + P.relit_ray_o.bytes() + P.relit_ray_d.bytes() +
+                                 P.relit_slot.bytes() + P.relit_hit.bytes() + P.relit_n.bytes());
+    if (info) *info = qi;
+    return MCPT_OK;
+}
+
+int mcpt_probe_relight_fold_host(int64_t n, int32_t spp, const float *dirs, const float *values, float hysteresis, const float *prev, float *out) {
+    const std::string w = "mcpt_probe_relight_fold_host";
+    if (n < 0 || n > (int64_t)sh::kMaxProbes) return fail(MCPT_ERR_ARG, w + ": n must be in 0 .. (2^31 - 1) / 27");
+    if (spp < 1) return fail(MCPT_ERR_ARG, w + ": spp must be positive");
+    if (!(hysteresis >= 0.f) || !(hysteresis < 1.f)) return fail(MCPT_ERR_ARG, w + ": hysteresis must be in [0, 1)");
+    if (n > 0 && (!dirs || !values || !out || (hysteresis != 0.f && !prev))) return fail(MCPT_ERR_ARG, w + ": null dirs, values or out, or null prev with a hysteresis");
+    pr::fold_host(n, spp, dirs, values, hysteresis, prev, out);
+    return MCPT_OK;
+}
+
 int mcpt_probe_shade_visible(mcpt_scene *sc, const mcpt_probe_grid *grid, const float *coef, const float *moments, const int32_t *counts,
                              const mcpt_probe_visibility *opts, int64_t n, const float *points, const float *normals, float *out, float *weight_out,
                              void *hip_stream) {
@@ -779,7 +992,10 @@ int mcpt_bake_probe_volume_ex(mcpt_scene *sc, const mcpt_probe_grid *grid, const
 
 int mcpt_scene_probe_buffers(const mcpt_scene *sc, int64_t *floats, int64_t *allocations) {
     if (!sc) return fail(MCPT_ERR_ARG, "mcpt_scene_probe_buffers: null scene");
-    if (floats) *floats = (int64_t)(sc->probes.points.n + sc->probes.radiance.n);
+    const ProbeBufs &P = sc->probes;
+    if (floats)
+        *floats = (int64_t)(P.points.n + P.radiance.n +
+                            4 * (P.relit_r0.n + P.relit_r1.n + P.relit_r2.n + P.relit_d.n + P.relit_ray_o.n + P.relit_ray_d.n + P.relit_slot.n + P.relit_hit.n));
     if (allocations) *allocations = sc->probes.allocations;
     return MCPT_OK;
 }

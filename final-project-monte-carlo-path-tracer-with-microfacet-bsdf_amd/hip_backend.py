@@ -46,6 +46,7 @@ EXPORTS = ["mcpt_scene_create", "mcpt_scene_destroy", "mcpt_render", "mcpt_rende
            "mcpt_render_probe_lit",
            "mcpt_query_probes_ex", "mcpt_bake_probe_grid_ex", "mcpt_bake_probe_volume_ex", "mcpt_render_probe_lit_direct",
            "mcpt_query_direct", "mcpt_rng_uniforms_host", "mcpt_direct_samples_host", "mcpt_direct_fold_host",
+           "mcpt_probe_volume_relight", "mcpt_probe_relight_fold_host",
            "mcpt_group_create", "mcpt_group_render", "mcpt_group_size", "mcpt_group_get_info", "mcpt_group_scene", "mcpt_group_destroy", "mcpt_group_last_error",
            "mcpt_last_error", "mcpt_version"]
 
@@ -612,6 +613,32 @@ class LitInfo(C.Structure):
                 "ms_total": float(self.ms_total)}
 
 
+class ProbeRelightOpts(C.Structure):
+    _fields_ = [("seed", C.c_uint32), ("spp", C.c_int32), ("sample_offset", C.c_int32), ("hysteresis", C.c_float), ("indirect_only", C.c_int32),
+                ("direct_samples", C.c_int32), ("direct_seed", C.c_uint32), ("max_distance", C.c_float), ("reserved", C.c_int32 * 8)]
+
+
+class ProbeRelightOutputs(C.Structure):
+    _fields_ = [("sh", C.c_void_p), ("moments", C.c_void_p), ("counts", C.c_void_p), ("reserved", C.c_void_p)]
+
+
+def _probe_relight_opts(who, spp, seed, sample_offset, hysteresis, indirect_only, direct_samples, direct_seed, depth, max_distance):
+    """mcpt_probe_relight_opts; the library's refusals that depend on the options alone are made here as well."""
+    spp, sample_offset, direct_samples = int(spp), int(sample_offset), int(direct_samples)
+    if spp < 1 or sample_offset < 0 or sample_offset + spp > 2 ** 31 - 1:
+        raise ValueError("%s: spp is positive, sample_offset >= 0 and sample_offset + spp at most 2^31 - 1, not %d and %d" % (who, spp, sample_offset))
+    h = np.float32(hysteresis)
+    if not (h >= 0 and h < 1):
+        raise ValueError("%s: hysteresis is in [0, 1) as a float32, not %r" % (who, hysteresis))
+    if not 0 <= direct_samples <= DIRECT_MAX_SAMPLES:
+        raise ValueError("%s: direct_samples must be in 0 .. %d, not %r" % (who, DIRECT_MAX_SAMPLES, direct_samples))
+    md = np.float32(0.0 if max_distance is None else max_distance)
+    if depth and not (md > 0 and np.isfinite(md)):
+        raise ValueError("%s: max_distance is positive and finite when depth is asked, not %r" % (who, max_distance))
+    return ProbeRelightOpts(int(seed) & 0xffffffff, spp, sample_offset, float(h), int(bool(indirect_only)), direct_samples, int(direct_seed) & 0xffffffff,
+                            float(md), (C.c_int32 * 8)(*([0] * 8)))
+
+
 def _lit_opts(who, aov_spp, specular_depth, centre, seed):
     """mcpt_lit_opts; the library's refusals that depend on the options alone are made here as well."""
     aov_spp, specular_depth, centre = int(aov_spp), int(specular_depth), int(bool(centre))
@@ -842,6 +869,11 @@ def lib(path=None):
         L.mcpt_render_probe_lit_direct.restype = C.c_int
         L.mcpt_render_probe_lit_direct.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(LitOpts), C.POINTER(LitDirectOpts), C.POINTER(ProbeVolume), C.POINTER(LitOutputs),
                                                    C.c_void_p, C.POINTER(LitInfo), C.POINTER(LitDirectInfo)]
+        L.mcpt_probe_volume_relight.restype = C.c_int
+        L.mcpt_probe_volume_relight.argtypes = [C.c_void_p, C.POINTER(ProbeVolume), C.POINTER(ProbeRelightOpts), C.POINTER(ProbeRelightOutputs), C.c_void_p,
+                                                C.POINTER(QueryInfo)]
+        L.mcpt_probe_relight_fold_host.restype = C.c_int
+        L.mcpt_probe_relight_fold_host.argtypes = [C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]
         L.mcpt_query_direct.restype = C.c_int
         L.mcpt_query_direct.argtypes = [C.c_void_p, C.POINTER(DirectOpts), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(QueryInfo)]
         L.mcpt_rng_uniforms_host.restype = C.c_int
@@ -1196,6 +1228,31 @@ def probe_depth_fold(dirs, r, backfacing, moments=None, counts=None):
     m, c = np.ascontiguousarray(m), np.ascontiguousarray(c)
     _check(lib().mcpt_probe_depth_fold_host(n, spp, _ptr(d), _ptr(rr), _ptr(bf), 1 if acc else 0, _ptr(m), _ptr(c)))
     return m, c
+
+
+def probe_relight_fold(dirs, values, hysteresis=0.0, prev=None):
+    """mcpt_probe_relight_fold_host (host only): the projection fold and the hysteresis blend of include/mcpt.h over given samples -- dirs
+    (n, spp, 3), values (n, spp, 3), prev (n, 27) (required unless hysteresis is 0) -> (n, 27) float32.  The inputs are not changed."""
+    d = np.ascontiguousarray(dirs, dtype=np.float32)
+    if d.ndim != 3 or d.shape[2] != 3 or d.shape[1] < 1:
+        raise ValueError("probe_relight_fold: dirs has shape (n, spp, 3) with spp >= 1, not %s" % (d.shape,))
+    n, spp = d.shape[0], d.shape[1]
+    v = np.ascontiguousarray(values, dtype=np.float32)
+    if v.shape != d.shape:
+        raise ValueError("probe_relight_fold: values has the shape of dirs %s, not %s" % (d.shape, v.shape))
+    h = np.float32(hysteresis)
+    if not (h >= 0 and h < 1):
+        raise ValueError("probe_relight_fold: hysteresis is in [0, 1) as a float32, not %r" % (hysteresis,))
+    p = None
+    if prev is not None:
+        p = np.ascontiguousarray(prev, dtype=np.float32)
+        if p.shape != (n, 27):
+            raise ValueError("probe_relight_fold: prev has shape (%d, 27), not %s" % (n, p.shape))
+    elif h != 0:
+        raise ValueError("probe_relight_fold: a hysteresis needs prev")
+    out = np.zeros((n, 27), np.float32)
+    _check(lib().mcpt_probe_relight_fold_host(n, spp, _ptr(d), _ptr(v), C.c_float(float(h)), _ptr(p) if p is not None else None, _ptr(out)))
+    return out
 
 
 def probe_shade_visible(origin, spacing, dims, sh, moments, counts, points, normals, normal_bias=0.0, backface_max=0.25, weight=False):
@@ -2179,6 +2236,43 @@ class HipScene:
             return out["lit"], (out["position"] if position else None), dict(info.as_dict(), **di.as_dict())
         _check(self.L.mcpt_render_probe_lit(self.h, _ptr(cam), C.byref(o), C.byref(vol), C.byref(outs), C.c_void_p(int(stream or 0)), C.byref(info)), L=self.L)
         return out["lit"], (out["position"] if position else None), info.as_dict()
+
+    def relight_probe_volume(self, origin, spacing, dims, sh, moments=None, counts=None, normal_bias=0.0, backface_max=0.25, spp=64, seed=1, sample_offset=0,
+                             hysteresis=0.0, indirect_only=False, direct_samples=0, direct_seed=1, depth=False, max_distance=None, out=None, stream=None):
+        """mcpt_probe_volume_relight: one update of the probe volume (origin, spacing, dims, sh (probes, 27)) from itself -> (sh (probes, 27),
+        moments (probes, 192) or None, counts (probes, 2) or None, mcpt_query_info as a dict), device buffers.  Every probe gathers spp
+        whole-sphere rays (seed, sample_offset): a ray's hit is shaded from the previous volume -- moments and counts together: the
+        occlusion-aware lookup with (normal_bias, backface_max); both None: the plain one -- plus direct_samples light samples drawn with
+        direct_seed, and the fresh projection is blended with the previous coefficients: hysteresis is the share kept.  indirect_only: a
+        ray that ends on an emitter records 0 (for a volume baked with indirect_only, together with direct_samples > 0).  depth: the depth
+        maps of the same rays (max_distance required) come back as well.  out: a dict with an "sh" device buffer (and "moments", "counts"
+        with depth) that must not overlap the inputs; None: torch tensors on the scene's device.  Enqueued on `stream` without a
+        synchronisation, through the staging buffers of the ray queries; the inputs are not written."""
+        who = "relight_probe_volume"
+        g, m = _probe_grid(who, origin, spacing, dims)
+        if (moments is None) != (counts is None):
+            raise ValueError("%s: moments and counts come together (both None: the plain lookup)" % who)
+        o = _probe_relight_opts(who, spp, seed, sample_offset, hysteresis, indirect_only, direct_samples, direct_seed, depth, max_distance)
+        if m * o.spp > 2 ** 31 - 1 or m * o.spp * max(o.direct_samples, 1) > 2 ** 31 - 1:
+            raise ValueError("%s: probes * spp and probes * spp * direct_samples must be at most 2^31 - 1" % who)
+        ps = _device_array(who, "sh", sh, (m, 27))
+        pm = pc = 0
+        vis = None
+        if (moments is not None or depth) and m > (2 ** 31 - 1) // PROBE_DEPTH_ROW:
+            raise ValueError("%s: at most (2^31 - 1) / 192 probes, not %d" % (who, m))
+        if moments is not None:
+            vis = _probe_visibility(who, normal_bias, backface_max)
+            pm = _device_array(who, "moments", moments, (m, PROBE_DEPTH_ROW))
+            pc = _device_array(who, "counts", counts, (m, 2), "int32")
+        spec = {"sh": ((m, 27), "float32")}
+        if depth:
+            spec.update({"moments": ((m, PROBE_DEPTH_ROW), "float32"), "counts": ((m, 2), "int32")})
+        out, ptrs, stream = _outputs(who, spec, out, self._torch_device() if out is None else None, stream)
+        vol = ProbeVolume(C.pointer(g), ps or None, pm or None, pc or None, C.pointer(vis) if vis is not None else None)
+        outs = ProbeRelightOutputs(ptrs["sh"] or None, ptrs.get("moments") or None, ptrs.get("counts") or None, None)
+        info = QueryInfo()
+        _check(self.L.mcpt_probe_volume_relight(self.h, C.byref(vol), C.byref(o), C.byref(outs), C.c_void_p(int(stream or 0)), C.byref(info)), L=self.L)
+        return out["sh"], (out["moments"] if depth else None), (out["counts"] if depth else None), info.as_dict()
 
     def probe_buffers(self):
         """mcpt_scene_probe_buffers -> (floats the scene-owned probe buffers hold, how often one of them was (re)allocated)."""

@@ -1748,6 +1748,71 @@ int mcpt_render_probe_lit_direct(mcpt_scene *scene, const mcpt_camera *camera, c
                                  const mcpt_lit_direct_opts *direct /* nullable */, const mcpt_probe_volume *volume, const mcpt_lit_outputs *outputs,
                                  void *hip_stream, mcpt_lit_info *info /* nullable */, mcpt_lit_direct_info *dinfo /* nullable */);
 
+/* ---- Relighting a probe volume from itself: one bounce of light gathered at every probe of a grid from the previous volume plus
+ * sampled direct light, blended into the probe with a hysteresis.  One closest-hit ray per probe sample instead of a path: iterating
+ * the update gives multi-bounce indirect light, and the volume follows mcpt_scene_update / _deform / _add_objects / _set_materials /
+ * _set_visibility frame by frame (csrc/mcpt_probe_relight.h states the fold and the blend once for host and device; csrc/mcpt_probes.hip
+ * holds the kernels).  Float32 in the written order, no FMA.  The probes are the grid's, at the scene-owned points of
+ * mcpt_bake_probe_grid.
+ *
+ * Sample k of probe i is the lit sample of mcpt_render_probe_lit_direct at specular_depth 0 with thr = 1: its first ray is
+ * mcpt_probe_rays(seed, i, sample_offset + k), with origin the probe and direction d, and its value v is
+ *   miss:     v = sample_env(d)
+ *   emitter:  indirect_only 0: v[c] = clampf(0, 1, emit[c] * fabsf(dot(-d, n)));  indirect_only 1: v = 0.f
+ *   other:    v[c] = alb[c] * (fmaxf(E[c], 0.f) + D[c]), with p, nf and alb exactly as in the lit rule, E the lookup of (p, nf) in
+ *             `volume` (mcpt_probe_shade when volume->moments is null, else mcpt_probe_shade_visible with volume->visibility) and
+ *             D = D(direct_seed, key pixel i, key sample sample_offset + k, direct_samples; p, nf), mcpt_query_direct's term; D is 0
+ *             with direct_samples == 0 or an empty light table, and no shadow ray is traced then.
+ * Surfaces are treated as Lambertian with the AOV albedo (dielectrics 1, conductors their reflectance): the lit pass's approximation.
+ * Fold:   fresh[27i + 3j + c]: acc = 0; for k in sample order acc = acc + (v_k[c] * (kFourPi * Y_j(d_k))) / (float)spp, which is
+ *         mcpt_query_probes' projection with spp_total = spp and accumulate = 0.
+ * Blend:  hysteresis == 0: out->sh = fresh; otherwise out->sh = hysteresis * volume->sh + (1.f - hysteresis) * fresh, two products and
+ *         one sum.  volume->sh is never written.
+ * Depth (optional): when out->moments is given, moments and counts are what mcpt_query_probe_depth{seed, spp, sample_offset,
+ *         accumulate = 0, max_distance} gives for the same points, bit for bit, from the same traced hits (no second trace).  A limit:
+ *         depth is not blended, the maps are those of this call's samples alone.
+ * Use with a split volume: for a volume baked with indirect_only, call with indirect_only = 1 and direct_samples > 0; for a full volume
+ * with both 0.  The other two combinations are legal: indirect_only = 0 with direct_samples > 0 counts direct light twice,
+ * indirect_only = 1 with direct_samples = 0 not at all.
+ *
+ * Protocol, as mcpt_query_probe_depth and mcpt_query_direct: the call is enqueued on hip_stream without a host synchronisation, through
+ * the staging buffers of the ray queries; info->grew is 0 and nothing is allocated on a second call of the same size; the scene's query
+ * event is recorded behind it, so an edit issued afterwards waits.  Probe rays are staged in chunks of at most MCPT_QUERY_CHUNK, whole
+ * probes or whole 64-sample blocks of one probe, and the result does not depend on the cut: a probe whose samples span pieces passes its
+ * partial sums through out->sh and blends at its last piece.  The per-sample records, D and the shadow-ray staging live in scene-owned
+ * buffers that only grow and are counted by mcpt_scene_probe_buffers.
+ * MCPT_ERR_ARG before any device work, with the outputs and info untouched: a null scene, volume, opts, out or out->sh; every grid,
+ * visibility and all-or-none refusal of mcpt_render_probe_lit; spp < 1, sample_offset < 0 or sample_offset + spp > 2^31 - 1; hysteresis
+ * outside [0, 1) or not a number; indirect_only other than 0 or 1; direct_samples outside 0..4096; max_distance not positive and finite
+ * while depth outputs are given; out->moments and out->counts not both null or both non-null; a non-zero reserved word or pointer;
+ * probes * spp or probes * spp * direct_samples beyond 2^31 - 1; out->sh overlapping volume->sh, or out->moments / out->counts
+ * overlapping the volume's; a pointer that is not memory of the scene's device.  No mcpt_group_* form. */
+typedef struct {
+    uint32_t seed;            /* probe rays: mcpt_probe_rays(seed, i, sample_offset + k) */
+    int32_t  spp;             /* >= 1 probe rays per probe */
+    int32_t  sample_offset;   /* >= 0, sample_offset + spp <= 2^31 - 1 */
+    float    hysteresis;      /* 0 <= h < 1: share of the previous coefficients kept */
+    int32_t  indirect_only;   /* 0 | 1: a probe ray that ends on an emitter records 0 */
+    int32_t  direct_samples;  /* 0 = off, else 1..4096 light samples per surface hit */
+    uint32_t direct_seed;
+    float    max_distance;    /* read only when depth outputs are given: positive, finite */
+    int32_t  reserved[8];     /* must be 0 */
+} mcpt_probe_relight_opts;    /* 64 bytes */
+typedef struct {              /* device memory */
+    float   *sh;              /* probes*27, required; must not overlap volume->sh */
+    float   *moments;         /* probes*192, nullable */
+    int32_t *counts;          /* probes*2, null iff moments is null */
+    void    *reserved;        /* must be null */
+} mcpt_probe_relight_outputs; /* 32 bytes */
+int mcpt_probe_volume_relight(mcpt_scene *scene, const mcpt_probe_volume *volume /* the previous volume, read only */,
+                              const mcpt_probe_relight_opts *opts, const mcpt_probe_relight_outputs *out, void *hip_stream,
+                              mcpt_query_info *info /* nullable */);
+/* Host only, no GPU needed: the projection fold and the blend of csrc/mcpt_probe_relight.h compiled for the CPU.  dirs and values are
+ * n*spp*3, probe-major in sample order.  MCPT_ERR_ARG: n < 0 or n > (2^31 - 1) / 27, spp < 1, hysteresis outside [0, 1), a null dirs,
+ * values or out with n > 0, a null prev with hysteresis != 0. */
+int mcpt_probe_relight_fold_host(int64_t n, int32_t spp, const float *dirs /* n*spp*3 */, const float *values /* n*spp*3 */,
+                                 float hysteresis, const float *prev /* n*27, nullable iff hysteresis == 0 */, float *out /* n*27 */);
+
 const char *mcpt_last_error(void);
 const char *mcpt_version(void);
 

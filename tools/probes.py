@@ -15,6 +15,13 @@ frames at depth 0 and 2 with N light samples of the sampled direct term per surf
 and compared in the same way, and the depth-2 frame of the last N written beside the other PNG; --indirect-only: they shade from a
 second volume baked with indirect_only, the volume the term is meant for (without the flag: from the full volume, which counts the
 direct light twice).  Without --direct the output is unchanged.
+python tools/probes.py --relight ITER [--hysteresis 0.7] [--relight-spp 256] [--direct N] [--indirect-only] [--scene cornell|chess] [--repeat 10]
+--relight ITER: starting from a zero volume, relight_probe_volume is iterated ITER times with a new seed per update, for hysteresis 0 and
+--hysteresis; after every update the RMS difference of E / pi between the relit volume and the path-traced bake_probe_volume of the same
+grid (--spp; full, or indirect-only with --indirect-only, which goes with --direct N) is printed, taken at the surface points of a 160 x 90
+centre-ray frame with the occlusion-aware lookup.  Then the wall time of one update against one bake at the same samples per probe (warm-up
+runs, the median and the spread of --repeat runs, each timed to the end of the device work), and on the Cornell scene the short box is
+moved and ITER more updates from the now stale volume are compared with a fresh bake of the moved scene.
 Device buffers come from the HIP runtime the library is linked to, through ctypes; torch is not needed."""
 import argparse
 import sys
@@ -112,8 +119,125 @@ def lit(args):
     hs.close()
 
 
+def timed(call, sync, warm, repeat):
+    """(median, min, max) ms of `repeat` runs of call() + sync() after `warm` warm-up runs."""
+    for _ in range(warm):
+        call()
+        sync()
+    ts = []
+    for _ in range(repeat):
+        t0 = time.perf_counter()
+        call()
+        sync()
+        ts.append((time.perf_counter() - t0) * 1e3)
+    return float(np.median(ts)), min(ts), max(ts)
+
+
+def relight(args):
+    """--relight ITER: iterate relight_probe_volume from a zero volume and compare with the path-traced bake; time both; move an object."""
+    pkg = mcpt_loader.load()
+    hip = pkg.hip_backend
+    W, H = 160, 90
+    dims = tuple(args.dims)
+    if args.scene == "chess":
+        sd = pkg.scenes.chess_scene(width=W, height=H, spp=4)
+        hs = hip.HipScene(sd, builder="sah", quantise=1)
+        v = np.concatenate([sd.triangles["v0"], sd.triangles["v1"], sd.triangles["v2"]]).astype(np.float64)
+        mid, half = (v.min(0) + v.max(0)) / 2, (v.max(0) - v.min(0)) / 2 * 0.8
+        lo, hi = mid - half, mid + half
+    else:
+        sd = pkg.scenes.cornell_demo(W, H, 4)
+        hs = hip.HipScene(sd, builder="sah")
+        lo, hi = np.array([40.0, 40.0, 40.0]), np.array([516.0, 500.0, 516.0])
+    rt = runtime()
+    sync = lambda: rt.hipStreamSynchronize(None)  # noqa: E731
+    origin, spacing = tuple(lo), tuple((hi - lo) / np.maximum(np.array(dims) - 1, 1))
+    m = dims[0] * dims[1] * dims[2]
+    max_distance = 1.5 * float(np.linalg.norm(spacing))
+    N, io, spp = args.direct[0] if args.direct else 0, args.indirect_only, args.relight_spp
+    print("%s, grid %dx%dx%d = %d probes; update: %d probe rays per probe, hysteresis %g, %d light samples per hit, indirect_only %d; "
+          "bake: %d spp, depth maps %d spp" % (args.scene, *dims, m, spp, args.hysteresis, N, int(io), args.spp, args.depth_spp))
+
+    def volume():
+        return {"sh": Dev(rt, np.zeros((m, 27), f32)), "moments": Dev(rt, np.zeros((m, hip.PROBE_DEPTH_ROW), f32)), "counts": Dev(rt, np.zeros((m, 2), np.int32))}
+
+    def bake(vol, n_spp, seed):
+        hs.bake_probe_volume(origin, spacing, dims, args.depth_spp, max_distance, depth_seed=args.seed + 2, out=vol, spp=n_spp, seed=seed, indirect_only=io)
+
+    # the surface points of a centre-ray frame, with the normals that face the camera
+    o, d = hs.centre_rays(np.arange(W * H, dtype=np.uint32))
+    dpts = Dev(rt, hip.probe_grid_points(origin, spacing, dims))
+
+    def surface():
+        do, dd = Dev(rt, o), Dev(rt, d)
+        res, _ = hs.query_closest(do, dd, want=("t", "prim", "normal"), out={"t": Dev(rt, shape=(len(o),), dtype=np.float64),
+                                                                             "prim": Dev(rt, shape=(len(o),), dtype=np.int32), "normal": Dev(rt, shape=(len(o), 3))})
+        t, ng = res["t"].get(), res["normal"].get()
+        hit = res["prim"].get() >= 0
+        t = np.where(hit, t, 0.0)
+        p = (o + d * t.astype(f32)[:, None])[hit].astype(f32)
+        nf = np.where(((ng * d).sum(axis=1) > 0)[:, None], -ng, ng)[hit].astype(f32)
+        return Dev(rt, p), Dev(rt, nf), int(hit.sum())
+
+    def e_over_pi(vol, pts):
+        out = Dev(rt, shape=(pts[2], 3))
+        hs.probe_shade_visible(origin, spacing, dims, vol["sh"], vol["moments"], vol["counts"], pts[0], pts[1], normal_bias=args.normal_bias, out=out)
+        return out.get().astype(np.float64)
+
+    def update(src, dst, seed, h):
+        hs.relight_probe_volume(origin, spacing, dims, src["sh"], src["moments"], src["counts"], normal_bias=args.normal_bias, spp=spp, seed=seed, hysteresis=h,
+                                indirect_only=io, direct_samples=N, direct_seed=seed + 1000, out={"sh": dst["sh"]})
+
+    def iterate(ref, pts, iters, h, start=None, what=""):
+        """iters updates, a new seed each, between two volumes that share the live scene's depth maps -> the last volume."""
+        a, b = volume(), volume()
+        hs.query_probe_depth(dpts, args.depth_spp, max_distance, seed=args.seed + 2, out={"moments": a["moments"], "counts": a["counts"]})
+        b["moments"], b["counts"] = a["moments"], a["counts"]
+        if start is not None:
+            a["sh"] = start["sh"]
+        want = e_over_pi(ref, pts)
+        print("%s hysteresis %g: RMS of E/pi (relit - baked) over %d surface points, the baked mean is %.4f" % (what, h, pts[2], want.mean()))
+        for it in range(iters):
+            update(a, b, args.seed + 100 + it, h)
+            a, b = b, a
+            got = e_over_pi(a, pts)
+            print("    update %2d: rms %.5f  (relative to the baked mean %.4f), relit mean %.4f" % (it + 1, np.sqrt(((got - want) ** 2).mean()),
+                                                                                                   np.sqrt(((got - want) ** 2).mean()) / want.mean(), got.mean()))
+        return a
+
+    ref = volume()
+    bake(ref, args.spp, args.seed)
+    sync()
+    pts = surface()
+    last = None
+    for h in sorted({0.0, args.hysteresis}):
+        last = iterate(ref, pts, args.relight, h, what="from a zero volume,")
+    # time: one update against one bake at the same samples per probe
+    scratch, tmp = volume(), volume()
+    t_upd = timed(lambda: update(last, scratch, args.seed + 7, args.hysteresis), sync, 3, args.repeat)
+    t_bake = timed(lambda: bake(tmp, spp, args.seed + 9), sync, 2, args.repeat)
+    print("time, %d probes x %d samples: update %.3f ms (min %.3f, max %.3f); bake_probe_volume_ex %.3f ms (min %.3f, max %.3f), of %d runs each; bake / update = %.1f"
+          % (m, spp, *t_upd, *t_bake, args.repeat, t_bake[0] / t_upd[0]))
+    if args.scene == "cornell":
+        move = np.array([[1, 0, 0, 120.0], [0, 1, 0, 0.0], [0, 0, 1, -60.0]], f32)
+        hs.update([(1, move)])  # the short box
+        moved = volume()
+        bake(moved, args.spp, args.seed)
+        sync()
+        pts = surface()
+        stale = np.sqrt(((e_over_pi(last, pts) - e_over_pi(moved, pts)) ** 2).mean())
+        print("the short box moved by (120, 0, -60); the stale volume against a fresh bake of the moved scene: rms %.5f" % stale)
+        iterate(moved, pts, args.relight, args.hysteresis, start=last, what="after the move, from the stale volume,")
+    hs.close()
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--relight", type=int, default=0, metavar="ITER", help="iterate relight_probe_volume ITER times from a zero volume (see the module text)")
+    ap.add_argument("--hysteresis", type=float, default=0.7, help="share of the previous coefficients an update keeps (--relight)")
+    ap.add_argument("--relight-spp", type=int, default=256, help="probe rays per probe and update (--relight)")
+    ap.add_argument("--scene", choices=("cornell", "chess"), default="cornell", help="the scene of --relight (chess: timing and convergence only, nothing moves)")
+    ap.add_argument("--repeat", type=int, default=10, help="timed runs per figure (--relight)")
     ap.add_argument("--dims", type=int, nargs=3, default=[5, 4, 5])
     ap.add_argument("--spp", type=int, default=16384)
     ap.add_argument("--sensor-spp", type=int, default=262144)
@@ -129,6 +253,8 @@ def main():
     ap.add_argument("--direct", type=int, nargs="+", default=[], metavar="N", help="also frames with N light samples of the sampled direct term (--lit)")
     ap.add_argument("--indirect-only", action="store_true", help="the --direct frames shade from a volume baked with indirect_only (--lit)")
     args = ap.parse_args()
+    if args.relight:
+        return relight(args)
     if args.lit:
         return lit(args)
     pkg = mcpt_loader.load()
